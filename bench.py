@@ -4,12 +4,16 @@
     python bench.py --gpus N --steps K --warmup W        (N > 1 without a launcher: starts its N ranks itself, see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+    python bench.py --full                               (everything else the line can carry, see below)
+    python bench.py --dump-outputs DIR                   (also write what the last timed step computed, DIR/<name>.npy)
 
 A "step" is one RealESRNet optimisation step (reference train_realesrnet.py:258-413 loop body) on a
 batch of synthetic HR tiles already resident in HBM: second-order degradation -> RRDBNet forward ->
 L1 -> backward (data + weight gradients) -> RCCL all-reduce of the flat gradient arena (N > 1) ->
-fused Adam -> EMA.  Rank 0 prints ONE JSON line (contract in the task statement) carrying
-`roofline` (dominant MFMA kernel, timed live with events on the launch stream) and `cpu_baseline`
+fused Adam -> EMA.  Rank 0 prints ONE JSON line: `metric`, `value`, `unit`, `ms_per_step` (K timed steps
+after W warm-up steps) and the workload.  A plain run does only that.  With --full the line also carries
+`roofline` (dominant MFMA kernel, timed live with events on the launch stream, one extra step), `parity_mode`
+(exact16 sub-runs and probes), `other_configs`, `box_reference`, `power`, `host` and `cpu_baseline`
 (the CPU oracle timed on the host cores, N = 1 only).
 """
 import argparse
@@ -69,12 +73,19 @@ MAC_PER_LR_PX = 17_926_848          # generator x4 forward MACs per LR pixel (SU
 PEAK_F16_TFLOPS = 2500.0            # dense f16/bf16 MFMA peak, MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0              # HBM3E peak (spec; ~6300 achievable), MI355X_MICROARCH.md
 PEAK_F32_TFLOPS = 157.3
+DUMP_SAMPLE = 1 << 21               # --dump-outputs: elements kept of a larger array (8 MB each; the six arrays of a step stay under 64 MB)
 
 
 def parse():
-    args = _parser().parse_args()
+    ap = _parser()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.lr_size is None:
         args.lr_size = 64 if args.gan else 256
+    if not args.full:
+        # a plain run does what its headline needs: set-up, warm-up, the timed steps, the outputs, the line
+        args.no_cpu_baseline = args.no_parity_mode = args.no_other_configs = args.no_probe = args.no_sustained = True
     return args
 
 
@@ -110,6 +121,14 @@ def _parser():
     ap.add_argument("--single-policy", action="store_true",
                     help="N > 1: time only the exchange policy the environment selects (default: BOTH -- sequential, then RESR_DP_OVERLAP=1 + "
                          "RESR_CHAIN_CUS_PER_XCD=31 -- K timed steps each, the better one is `value`, both under dist.policies)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: parity_mode (exact16 sub-runs, probes), other_configs, cpu_baseline, the in-situ "
+                         "roofline step and the degradation record, box_reference (~3 s frontier measurement), power, host and "
+                         "unclamped_output_fraction; the --no-* options above switch parts of it off.  Without it: set-up, warm-up, the timed "
+                         "steps and the result line only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; arrays above "
+                         f"{DUMP_SAMPLE} elements as a fixed seeded sample of that many; rank 0)")
     return ap
 
 
@@ -634,6 +653,36 @@ def timed_region(fn, steps, world, sampler=None):
     return dt, out
 
 
+class LastCall:
+    """--dump-outputs: keeps the input and output of a module's most recent forward (detached references, no copy and no
+    synchronisation), so that what the last timed step fed and produced can be written after the timed region."""
+
+    def __init__(self, module):
+        self.x = self.y = self.out = None       # out: what the step itself returned (set by the step's caller)
+        self._h = module.register_forward_hook(self._hook)
+
+    def _hook(self, module, inputs, output):
+        self.x, self.y = inputs[0].detach(), output.detach()
+
+    def close(self):
+        self._h.remove()
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every tensor of `arrays` (None: skipped) as out_dir/<name>.npy in float32.  One of more than DUMP_SAMPLE elements is
+    written as the flattened values at DUMP_SAMPLE sorted indices drawn from a fixed seed: the same arguments give the same indices."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def host_record(fn, world, reps=3):
     """What a step costs the HOST: wall time of issuing one step onto an idle device, no synchronisation inside (the launches
     are asynchronous, so this is Python + ctypes + runtime enqueue time, collectives' enqueue included).  A step whose enqueue
@@ -761,9 +810,10 @@ def make_hr_tiles(args, B, hr_edge, rank):
     return hr
 
 
-def run_mode(args, precision, steps, warmup, world, rank, probe=True, centre_output=False, degradation_record=False):
+def run_mode(args, precision, steps, warmup, world, rank, probe=True, centre_output=False, degradation_record=False, dump_dir=None):
     """Build the training state in `precision`, run `warmup` untimed + `steps` timed steps (barrier + synchronize on both
-    sides, max over ranks) and, optionally, one more step with per-launch events for the roofline record."""
+    sides, max over ranks), optionally write what the last of them computed (dump_dir) and, with --full, one more step with
+    per-launch events for the roofline record."""
     import real_esrgan_pytorch_amd as R
     from real_esrgan_pytorch_amd.train import DataParallel, RealESRNetStep
 
@@ -797,17 +847,27 @@ def run_mode(args, precision, steps, warmup, world, rank, probe=True, centre_out
     if degrade is None:
         lr_fixed = torch.nn.functional.interpolate(hr, scale_factor=0.25, mode="area")
     step = RealESRNetStep(model, ema, opt, scaler, degrade)
+    cap = LastCall(model) if dump_dir and rank == 0 else None
 
     def one():
-        return step(hr, lr_fixed)
+        out = step(hr, lr_fixed)
+        if cap is not None:
+            cap.out = out
+        return out
 
     for _ in range(warmup):
         one()
-    sampler = PowerSampler()
+    sampler = PowerSampler() if args.full else None
     dt, loss = timed_region(one, steps, world, sampler)
     dt, policies = time_policies(args, steps, warmup, world, one, dp, model, dt)
     res = {"precision": precision, "dt": dt, "steps": steps, "warmup": warmup, "loss": float(loss), "degradation": degradation,
-           "power": sampler.summary(), "policies": policies, "host": host_record(one, world)}
+           "policies": policies}
+    if cap is not None:     # before any further step changes the state
+        cap.close()
+        dump_outputs(dump_dir, {"loss": cap.out, "lr": cap.x, "sr": cap.y, "params": model.flat_parameters(), "grad": model.flat_grad(),
+                                "ema": torch.cat([ema.shadow[n].reshape(-1) for n, _ in model.named_parameters()])})
+    if args.full:
+        res.update(power=sampler.summary(), host=host_record(one, world))
 
     # The in-situ roofline probe is one more (untimed) train step.  With several ranks that step contains the gradient
     # all-reduce, so every rank runs it; only rank 0 brackets its launches with events and reports.  A failure on any rank
@@ -845,7 +905,7 @@ def run_mode(args, precision, steps, warmup, world, rank, probe=True, centre_out
         except Exception as e:  # pragma: no cover
             res["degradation_roofline"] = {"error": repr(e)}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         with torch.no_grad():
             sr_probe = model(torch.nn.functional.interpolate(hr[:2], scale_factor=0.25, mode="area"))
             res["unclamped"] = round(float(((sr_probe > 0) & (sr_probe < 1)).float().mean()), 4)
@@ -859,7 +919,7 @@ def run_mode(args, precision, steps, warmup, world, rank, probe=True, centre_out
 D_MAC_PER_HR_PX = 395_520          # discriminator forward MACs per input pixel (SURVEY.md §8 geometry)
 
 
-def run_gan(args, world, rank):
+def run_gan(args, world, rank, dump_dir=None):
     """BASELINE config 4, this rank's share: one RealESRGAN optimisation step per `step` on synthetic HR tiles resident in
     HBM.  Data parallel: generator gradients from its backward hook, discriminator gradients once after the second backward."""
     import real_esrgan_pytorch_amd as R
@@ -889,12 +949,25 @@ def run_gan(args, world, rank):
     degrade = Degrader(batch=B, hr_size=tile, upscale=4, crop=crop, seed=rank)
     scaler = torch.amp.GradScaler("cuda") if args.precision != "strict" else None
     step = RealESRGANStep(g, d, ema, g_opt, d_opt, scaler, degrade, content_criterion=content, dp=dp)
-    for _ in range(args.warmup):
+    cap = LastCall(g) if dump_dir and rank == 0 else None
+
+    def one():
         out = step(hr)
-    dt, out = timed_region(lambda: step(hr), args.steps, world)
-    dt, policies = time_policies(args, args.steps, args.warmup, world, lambda: step(hr), dp, g, dt)
-    res = {"dt": dt, "losses": {k: round(float(v), 6) for k, v in out.items()}, "tile": tile, "crop": crop, "policies": policies,
-           "host": host_record(lambda: step(hr), world)}
+        if cap is not None:
+            cap.out = out
+        return out
+
+    for _ in range(args.warmup):
+        out = one()
+    dt, out = timed_region(one, args.steps, world)
+    dt, policies = time_policies(args, args.steps, args.warmup, world, one, dp, g, dt)
+    res = {"dt": dt, "losses": {k: round(float(v), 6) for k, v in out.items()}, "tile": tile, "crop": crop, "policies": policies}
+    if cap is not None:     # before any further step changes the state
+        cap.close()
+        dump_outputs(dump_dir, {**cap.out, "lr": cap.x, "sr": cap.y, "g_params": g.flat_parameters(),
+                                "d_params": d.flat_parameters(), "ema": torch.cat([ema.shadow[n].reshape(-1) for n, _ in g.named_parameters()])})
+    if args.full:
+        res["host"] = host_record(one, world)
     if not args.no_probe:
         err = None
         try:
@@ -917,7 +990,7 @@ def run_gan(args, world, rank):
 
 
 def gan_main(args, world, rank):
-    res = run_gan(args, world, rank)
+    res = run_gan(args, world, rank, dump_dir=args.dump_outputs)
     res["devices"] = gather_devices(world, rank)     # a collective: every rank
     if rank != 0:
         return
@@ -941,10 +1014,10 @@ def gan_main(args, world, rank):
         "losses": res["losses"],
         "chain_errors": int(__import__("real_esrgan_pytorch_amd")._lib.lib().resr_debug_chain_errors()),
         "dist": dist_record(world, res.get("devices"), res.get("policies")),
-        "host": res.get("host"),
     }
-    if "roofline" in res:
-        out["roofline"] = res["roofline"]
+    for k in ("host", "roofline"):     # --full
+        if k in res:
+            out[k] = res[k]
     print(json.dumps(out), flush=True)
 
 
@@ -1224,7 +1297,8 @@ def main():
         return
     B, lr_edge = args.batch, args.lr_size
     hr_edge = lr_edge * 4
-    main_res = run_mode(args, args.precision, args.steps, args.warmup, world, rank, centre_output=args.centre_output, degradation_record=True)
+    main_res = run_mode(args, args.precision, args.steps, args.warmup, world, rank, centre_output=args.centre_output, degradation_record=True,
+                        dump_dir=args.dump_outputs)
     devices = gather_devices(world, rank)      # a collective: every rank
     # the mode that meets north_star's 1e-3 tolerance, timed on the same workload (fewer steps: it is ~2.5x slower)
     parity_res = parity_hi = parity_p7 = None
@@ -1265,17 +1339,18 @@ def main():
                        "global_batch": B * world, "parallelism": f"dp{world}"},
             "generator_tflops_per_gpu": round(value / world * flop_per_image / 1e12, 2),
             "loss": main_res["loss"],
-            # health of the timed regime: the share of output values strictly inside the training-time clamp (model.py:270).
-            # Near 0 the backward pass multiplies (almost) only zeros and runs faster than on real gradients (see --noise-data)
-            "unclamped_output_fraction": main_res.get("unclamped"),
             # chained dense-block launches: polls that timed out + workgroups beyond an XCD's share (resr_debug_chain_errors); must be 0
             "chain_errors": int(__import__("real_esrgan_pytorch_amd")._lib.lib().resr_debug_chain_errors()),
-            # rank 0's board power / shader clock over the timed steps (the step runs at the power cap: DESIGN section 5)
-            "power": main_res.get("power"),
             "dist": dist_record(world, devices, main_res.get("policies")),
-            # host side of a step (enqueue time without a sync, CPUs this process may run on): max over ranks
-            "host": main_res.get("host"),
         }
+        if args.full:
+            # health of the timed regime: the share of output values strictly inside the training-time clamp (model.py:270).
+            # Near 0 the backward pass multiplies (almost) only zeros and runs faster than on real gradients (see --noise-data)
+            out["unclamped_output_fraction"] = main_res.get("unclamped")
+            # rank 0's board power / shader clock over the timed steps (the step runs at the power cap: DESIGN section 5)
+            out["power"] = main_res.get("power")
+            # host side of a step (enqueue time without a sync, CPUs this process may run on): max over ranks
+            out["host"] = main_res.get("host")
         if "roofline" in main_res:
             out["roofline"] = main_res["roofline"]
             if "degradation_roofline" in main_res and isinstance(out["roofline"], dict):

@@ -192,7 +192,7 @@ def test_bench_two_ranks_prints_one_line():
     env = dict(os.environ, RESR_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "2", "--lr-size", "64", "--no-parity-mode", "--no-sustained"]   # (the exact16 sub-runs of the line are single-rank matters: 40 s of this test)
+           "--batch", "2", "--lr-size", "64", "--full", "--no-parity-mode", "--no-sustained"]   # (the exact16 sub-runs of the line are single-rank matters: 40 s of this test)
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -222,7 +222,7 @@ def test_bench_gan_two_ranks_plain_launch_prints_one_line():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "2", "--lr-size", "32", "--gan", "--no-parity-mode", "--no-sustained"]   # (LR 16: a resize1 factor of 0.15 leaves 9 pixels for the 21-tap blur, which reflect padding refuses -- as F.pad does)
+           "--batch", "2", "--lr-size", "32", "--gan", "--full", "--no-parity-mode", "--no-sustained"]   # (LR 16: a resize1 factor of 0.15 leaves 9 pixels for the 21-tap blur, which reflect padding refuses -- as F.pad does)
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     assert "starting 2 ranks" in r.stderr
@@ -247,7 +247,7 @@ def test_bench_gan_eight_ranks_on_one_gpu():
     env = dict(os.environ, RESR_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_port()), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--batch", "1", "--lr-size", "32", "--gan", "--no-sustained"]
+           "--batch", "1", "--lr-size", "32", "--gan", "--full", "--no-sustained"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -442,7 +442,7 @@ def test_bench_force_nccl_one_gpu(overlap_env):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, RESR_BENCH_FORCE_NCCL="1", RESR_DP_OVERLAP=overlap_env, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--lr-size", "64", "--no-other-configs", "--no-cpu-baseline", "--no-parity-mode"]
+           "--lr-size", "64", "--full", "--no-other-configs", "--no-cpu-baseline", "--no-parity-mode"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

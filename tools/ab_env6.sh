@@ -4,7 +4,7 @@ KV=$1; R=${2:-2}; OUT=${3:-gpurun_out/ab_env6.jsonl}; mkdir -p "$(dirname "$OUT"
 for i in $(seq 1 $R); do
   for which in default switched; do
     if [ $which = switched ]; then export "$KV"; else unset "${KV%%=*}"; fi
-    timeout 300 python3 bench.py --no-cpu-baseline --no-parity-mode --no-other-configs --steps 16 --warmup 4 2>/dev/null | python3 -c "
+    timeout 300 python3 bench.py --full --no-cpu-baseline --no-parity-mode --no-other-configs --steps 16 --warmup 4 2>/dev/null | python3 -c "
 import json,sys
 l=[x for x in sys.stdin.read().splitlines() if x.startswith('{')]
 d=json.loads(l[-1]); print(json.dumps({'arm':'$which','env':'$KV','round':$i,'what':'headline','value':d['value'],'ms_per_step':d['ms_per_step'],'power_w':d.get('power',{}).get('mean_w')}))" >> $OUT

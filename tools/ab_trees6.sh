@@ -20,7 +20,8 @@ print(json.dumps(r))" "$@"; }
 for i in $(seq 1 $R); do
   for which in head other; do
     if [ $which = other ]; then cd $HERE/$O; else cd $HERE; fi
-    timeout 300 python3 bench.py --no-cpu-baseline --no-parity-mode --no-other-configs --steps 16 --warmup 4 2>/dev/null | pick $which $i headline value,ms_per_step,roofline.vs_sustained.matrix_alone_tflops >> $HERE/$OUT
+    FULL=$(grep -q '"--full"' bench.py && echo --full)     # a tree from before bench.py's --full runs everything by default
+    timeout 300 python3 bench.py $FULL --no-cpu-baseline --no-parity-mode --no-other-configs --steps 16 --warmup 4 2>/dev/null | pick $which $i headline value,ms_per_step,roofline.vs_sustained.matrix_alone_tflops >> $HERE/$OUT
     STEPS=60 timeout 200 python3 tools/bench_cfg3.py 2>/dev/null | pick $which $i cfg3 images_per_s,ms_per_step >> $HERE/$OUT
     timeout 200 python3 tools/bench_gan.py --steps 16 2>/dev/null | pick $which $i gan ms_per_step >> $HERE/$OUT
     INF=$(timeout 300 python3 tools/bench_infer.py 2>/dev/null)

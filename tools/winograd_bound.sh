@@ -13,10 +13,10 @@ done
 for i in 1 2; do
   for which in tree wino4 wino4v; do
     if [ $which != tree ]; then export RESR_LIB_PATH=$PWD/tools/ab/$which.so; else unset RESR_LIB_PATH; fi
-    python bench.py --no-cpu-baseline --no-parity-mode --no-other-configs --steps 12 --warmup 4 2>/dev/null | tail -1 > gpurun_out/wb_${which}_$i.json
-    python - <<PY
-import json
-d=json.load(open("gpurun_out/wb_${which}_$i.json"))
+    LINE=$(python bench.py --full --no-cpu-baseline --no-parity-mode --no-other-configs --steps 12 --warmup 4 2>/dev/null | tail -1)
+    LINE=$LINE python - <<PY
+import json, os
+d=json.loads(os.environ["LINE"])
 pi=d["roofline"]["per_instance"]
 pw=d.get("power") or {}
 print("== step, $which $i:", d["value"], "images/s", d["ms_per_step"], "ms;", pw.get("avg_w"), "W", pw.get("sclk_mhz_avg"), "MHz;",
