@@ -82,8 +82,12 @@ enum {
      * are stored times 2^12).  Every pair operand then needs its q tensor (in0_q_offset / in1_q_offset), the weights their MX blocks
      * (w_mx_offset); out_q_offset != 0 makes a pass EMIT the q tensor of its (pair) output for the passes behind it.  The
      * corrections need ~4 good bits, not 11: forward 0.8-1.2e-4 of the fp32 result over 23 blocks, 2/3 of the
-     * matrix time of a pair chunk.  Inference epilogues only (bias / LeakyReLU / residuals). */
-    RESR_CONV_MX_PAIRS = 1 << 12
+     * matrix time of a pair chunk.  Inference epilogues only (bias / LeakyReLU / residuals) -- and, with MX_SIGNBITS, the sign words. */
+    RESR_CONV_MX_PAIRS = 1 << 12,
+    /* with MX_PAIRS: the pass may also WRITE_SIGNBITS (the training forward of RESR_X2_PLAN_MX_TRAIN_FORWARD: LeakyReLU with
+     * 0 <= slope <= 1, no residuals, pair or single-f16 output).  Bit c of a sign word is taken from the fp32 value the stored
+     * output is rounded from.  MX_PAIRS | WRITE_SIGNBITS without this flag is an argument error; the flag alone changes nothing. */
+    RESR_CONV_MX_SIGNBITS = 1 << 13
 };
 
 /* One 3x3, stride 1, pad 1 convolution pass (forward conv or backward-data conv):
@@ -314,7 +318,15 @@ enum {
      * incoming gradient in and the two masked tail passes emit those of the gradient tensors, the three tail passes that read them run one
      * f16 + one MX stage per chunk, and the three weight gradients take their correction tap-products as MX jobs.  upsampling1 keeps its f16
      * form (its gradient comes out of a 2 x 2 sum-pool). */
-    RESR_X2_PLAN_MX_TAIL = 1024
+    RESR_X2_PLAN_MX_TAIL = 1024,
+    /* opt-in, with GROWTH_F16_INFER + GROWTH_W16_INFER + MX_INFER + F16_BACKWARD (the named plan 2401, "output parity"): a TRAINING
+     * forward runs the inference MX plan -- growth planes o1..o4 single f16 against f16 weights (one stage per growth chunk), pair
+     * chunks on one f16 + one MX stage (RESR_CONV_MX_PAIRS | RESR_CONV_MX_SIGNBITS) --, every LeakyReLU still writes its sign words
+     * (from the fp32 value the stored output is rounded from), and F16_BACKWARD's pass runs behind it on the hi tensors and the sign
+     * words.  The training forward is bit-identical to an inference forward of plan 97 (output 0.9-1.1e-4 of the fp32 oracle, gate
+     * 2e-4); the gradients are in fast mode's class (a fifth of its distance from the all-pairs plan: the MX forward's mask flips).
+     * The workspace grows by the q tensors, the packed buffer holds its MX region.  Without its four prerequisites resr_generator_forward / _backward return RESR_ERR_ARG and resr_generator_workspace_bytes 0. */
+    RESR_X2_PLAN_MX_TRAIN_FORWARD = 2048
 };
 
 size_t resr_generator_param_count(const ResrGeneratorDesc* d);

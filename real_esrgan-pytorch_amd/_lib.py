@@ -27,7 +27,12 @@ X2_PLAN_MX_BWD = 128
 X2_PLAN_F16_BACKWARD = 256
 X2_PLAN_MX_WGRAD = 512
 X2_PLAN_MX_TAIL = 1024
+X2_PLAN_MX_TRAIN_FORWARD = 2048
+# the named "output parity" training plan: bits 0 + 5 + 6 (the inference MX forward) + 8 (f16 backward) + 11 (MX_TRAIN_FORWARD)
+X2_PLAN_OUTPUT_PARITY = (X2_PLAN_GROWTH_F16_INFER | X2_PLAN_GROWTH_W16_INFER | X2_PLAN_MX_INFER | X2_PLAN_F16_BACKWARD
+                         | X2_PLAN_MX_TRAIN_FORWARD)   # 2401
 CONV_MX_PAIRS = 1 << 12
+CONV_MX_SIGNBITS = 1 << 13
 RESR_VERSION = 3   # include/resr.h: the structures below mirror THIS version of the header
 
 

@@ -340,7 +340,7 @@ static int conv3x3_args(const ResrConvDesc* d, const void* in0, const void* in1,
     a.in0_chunk_b = (size_t)chunk(d->in0_chunk_stride) * es; a.in1_chunk_b = (size_t)chunk(d->in1_chunk_stride) * es;
     a.out_chunk = chunk(d->out_chunk_stride); a.res0_chunk = chunk(d->res0_chunk_stride);
     a.res1_chunk = chunk(d->res1_chunk_stride); a.mask_chunk = chunk(d->mask_chunk_stride);
-    a.flags = d->flags & ~(RESR_CONV_OUT_SINGLE | RESR_CONV_SINGLE_W16 | RESR_CONV_MX_PAIRS); a.s0 = d->s0; a.t0 = d->t0; a.s1 = d->s1; a.t1 = d->t1; a.slope = d->slope;
+    a.flags = d->flags & ~(RESR_CONV_OUT_SINGLE | RESR_CONV_SINGLE_W16 | RESR_CONV_MX_PAIRS | RESR_CONV_MX_SIGNBITS); a.s0 = d->s0; a.t0 = d->t0; a.s1 = d->s1; a.t1 = d->t1; a.slope = d->slope;
     a.s2d_c = 0; a.tap_c = 0; a.ngroups = 1; a.w_group_b = 0;
     // RESR_F16X2: leading pair chunks / a single-f16 output (kept out of a.flags: the kernels and the chain checks never see the bit)
     a.pair_chunks = d->cin / 32; a.out_single = 0;
@@ -364,6 +364,9 @@ static int conv3x3_args(const ResrConvDesc* d, const void* in0, const void* in1,
                 return fail(RESR_ERR_ARG, "conv3x3: RESR_CONV_MX_PAIRS needs the q offset of every pair operand and w_mx_offset");
             if (d->cout_groups > 1 || d->s2d_in_channels > 0 || d->s2d_out_channels > 0)
                 return fail(RESR_ERR_ARG, "conv3x3: RESR_CONV_MX_PAIRS is a dense 3x3 pass of one output group");
+            // the sign words of a training forward only where the caller asks for an MX training forward explicitly
+            if ((d->flags & RESR_CONV_WRITE_SIGNBITS) && !(d->flags & RESR_CONV_MX_SIGNBITS))
+                return fail(RESR_ERR_ARG, "conv3x3: RESR_CONV_MX_PAIRS with WRITE_SIGNBITS needs RESR_CONV_MX_SIGNBITS");
             a.mx = 1;
             a.in0_q_b = (size_t)d->in0_q_offset * 2; a.in1_q_b = (size_t)d->in1_q_offset * 2;
             a.w_mx = (const char*)w + d->w_mx_offset;

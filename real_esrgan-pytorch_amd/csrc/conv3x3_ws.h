@@ -1680,9 +1680,14 @@ static int launch_ws_epi(const ConvArgs& a, hipStream_t stream) {
 
 template <typename T, int MT, int NT, int NWC, int X2 = 0>
 static int launch_ws(const ConvArgs& a, hipStream_t stream) {
-    if constexpr (X2 == 2) {   // MX stages (RESR_CONV_MX_PAIRS): the lean epilogues -- bias / LeakyReLU / residuals, or the sign-word mask of a backward-data pass
+    if constexpr (X2 == 2) {   // MX stages (RESR_CONV_MX_PAIRS): the lean epilogues -- bias / LeakyReLU / residuals, the sign words of a training
+                               // forward (RESR_CONV_MX_SIGNBITS, checked with the descriptor), or the sign-word mask of a backward-data pass
         if ((a.flags & RESR_CONV_MASK_BITS) && !a.aux && !a.res0 && !a.res1 && !(a.flags & ~(RESR_CONV_MASK | RESR_CONV_MASK_BITS | RESR_CONV_NO_BIAS)))
             return launch_ws_epi<T, MT, NT, NWC, 33, X2>(a, stream);
+        if ((a.flags & RESR_CONV_WRITE_SIGNBITS) && a.aux && !a.mask && !a.res0 && !a.res1 &&
+            !(a.flags & ~(RESR_CONV_LRELU | RESR_CONV_NO_BIAS | RESR_CONV_UPSAMPLE_IN | RESR_CONV_WRITE_SIGNBITS)) &&
+            !((a.flags & RESR_CONV_LRELU) && !(a.slope >= 0.f && a.slope <= 1.f)))
+            return launch_ws_epi<T, MT, NT, NWC, 16, X2>(a, stream);
         const bool lean_ok = !a.aux && !a.mask && !(a.flags & ~(RESR_CONV_LRELU | RESR_CONV_NO_BIAS | RESR_CONV_UPSAMPLE_IN)) &&
                              !((a.flags & RESR_CONV_LRELU) && !(a.slope >= 0.f && a.slope <= 1.f)) && !((a.res0 || a.res1) && (a.cout & 15));
         if (!lean_ok) return fail(RESR_ERR_ARG, "conv3x3: RESR_CONV_MX_PAIRS supports bias / LeakyReLU (0 <= slope <= 1) / residual / sign-word-mask epilogues only");

@@ -56,17 +56,13 @@ static int launch_chain(const ConvArgs& a, const ChainArgs& cj, double flop, dou
 }
 
 // kind: 0 = forward at inference (LeakyReLU), 1 = forward in training (LeakyReLU + sign words), 2 = mirrored backward-data;
-// jobs of kind "residual half" (the closing convolution inside the chain) take the instantiation with the per-job switches
+// jobs of kind "residual half" (the closing convolution inside the chain) take the instantiation with the per-job switches.
+// MX stages (X2 = 2) have all three: kind 1 is the training forward of RESR_X2_PLAN_MX_TRAIN_FORWARD (RESR_CONV_MX_SIGNBITS on the
+// descriptors, checked in conv3x3.hip)
 template <int NT, int CH, int X2>
 static int launch_chain_kind(const ConvArgs& a, const ChainArgs& cj, int kind, double flop, double bytes, hipStream_t stream) {
-    if constexpr (X2 == 2) {   // MX stages: inference forward chains (LeakyReLU) and the mirrored backward-data chains (sign-word mask)
-        if (kind == 1) return fail(RESR_ERR_ARG, "conv3x3_chain: a training forward keeps every pair chunk on three f16 stages (no RESR_CONV_MX_PAIRS)");
-        if (kind == 2) return launch_chain<NT, 33, CH, X2>(a, cj, flop, bytes, stream);
-        return launch_chain<NT, 0, CH, X2>(a, cj, flop, bytes, stream);
-    } else {
-        if (kind == 2) return launch_chain<NT, 33, CH, X2>(a, cj, flop, bytes, stream);
-        return kind == 1 ? launch_chain<NT, 16, CH, X2>(a, cj, flop, bytes, stream) : launch_chain<NT, 0, CH, X2>(a, cj, flop, bytes, stream);
-    }
+    if (kind == 2) return launch_chain<NT, 33, CH, X2>(a, cj, flop, bytes, stream);
+    return kind == 1 ? launch_chain<NT, 16, CH, X2>(a, cj, flop, bytes, stream) : launch_chain<NT, 0, CH, X2>(a, cj, flop, bytes, stream);
 }
 
 template <int X2>

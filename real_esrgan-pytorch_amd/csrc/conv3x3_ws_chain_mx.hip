@@ -1,5 +1,6 @@
-// Chained dense-block passes of an exact16 INFERENCE forward with MX stages on the pair chunks (RESR_CONV_MX_PAIRS; kernel:
-// conv3x3_ws.h, X2 = 2; launchers: conv3x3_ws_chain.h).
+// Chained dense-block passes of an exact16 forward with MX stages on the pair chunks (RESR_CONV_MX_PAIRS; kernel: conv3x3_ws.h, X2 = 2;
+// launchers: conv3x3_ws_chain.h): inference (LeakyReLU) and the training forward of RESR_X2_PLAN_MX_TRAIN_FORWARD (+ sign words,
+// RESR_CONV_MX_SIGNBITS), and the mirrored backward-data passes of RESR_X2_PLAN_MX_BWD.
 #include "conv3x3_ws_chain.h"
 
 namespace resr {

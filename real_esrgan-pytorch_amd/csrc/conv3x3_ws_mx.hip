@@ -1,5 +1,6 @@
 // RESR_CONV_MX_PAIRS instantiations of the producer/consumer convolution (exact16 with one f16 stage + one MX-fp8 stage per pair
-// chunk; kernel: conv3x3_ws.h, X2 = 2): the inference epilogues of both output widths, same tile shapes as the plain exact16 ones.
+// chunk; kernel: conv3x3_ws.h, X2 = 2): the inference epilogues and the sign words of a training forward (RESR_CONV_MX_SIGNBITS) of both
+// output widths, same tile shapes as the plain exact16 ones.
 #include "conv3x3_ws.h"
 
 namespace resr {

@@ -96,9 +96,20 @@ bool plan_mx_wgrad(const ResrGeneratorDesc& d) {
 }
 // RESR_X2_PLAN_MX_TAIL: conv3, conv4, upsampling2 the same way; u1, u2, c3 and the tail's gradient tensors g4, gA, gB carry q tensors
 bool plan_mx_tail(const ResrGeneratorDesc& d) { return plan_mx_wgrad(d) && (d.x2_plan & RESR_X2_PLAN_MX_TAIL); }
+// RESR_X2_PLAN_MX_TRAIN_FORWARD: a TRAINING forward on the inference MX plan (sign words from the MX epilogues, RESR_CONV_MX_SIGNBITS),
+// followed by F16_BACKWARD's pass on the hi tensors -- the bit and its four prerequisites
+constexpr int kMxTrainNeeds = RESR_X2_PLAN_GROWTH_F16_INFER | RESR_X2_PLAN_GROWTH_W16_INFER | RESR_X2_PLAN_MX_INFER | RESR_X2_PLAN_F16_BACKWARD;
+bool plan_mx_train(const ResrGeneratorDesc& d) {
+    return d.dtype == RESR_F16X2 && d.training && (d.x2_plan & RESR_X2_PLAN_MX_TRAIN_FORWARD) && (d.x2_plan & kMxTrainNeeds) == kMxTrainNeeds;
+}
+// the bit without its prerequisites is refused (forward, backward, workspace size), not ignored
+bool plan_mx_train_ok(const ResrGeneratorDesc& d) {
+    return d.dtype != RESR_F16X2 || !(d.x2_plan & RESR_X2_PLAN_MX_TRAIN_FORWARD) || (d.x2_plan & kMxTrainNeeds) == kMxTrainNeeds;
+}
+// the forward passes run the MX plan: an inference forward of bits 0 + 5 + 6, or a training forward of RESR_X2_PLAN_MX_TRAIN_FORWARD
 bool plan_mx(const ResrGeneratorDesc& d) {
     const int need = RESR_X2_PLAN_GROWTH_F16_INFER | RESR_X2_PLAN_GROWTH_W16_INFER | RESR_X2_PLAN_MX_INFER;
-    return d.dtype == RESR_F16X2 && !d.training && (d.x2_plan & need) == need;
+    return (d.dtype == RESR_F16X2 && !d.training && (d.x2_plan & need) == need) || plan_mx_train(d);
 }
 
 bool build_plan(const ResrGeneratorDesc* d, Plan& p) {
@@ -350,6 +361,7 @@ size_t generator_chain_state_bytes(const ResrGeneratorDesc* d) {
 size_t generator_workspace_bytes(const ResrGeneratorDesc* d) {
     Plan p;
     if (!build_plan(d, p)) return 0;
+    if (!plan_mx_train_ok(*d)) { (void)fail(RESR_ERR_ARG, "generator: x2_plan MX_TRAIN_FORWARD (2048) needs bits 1 + 32 + 64 + 256"); return 0; }
     Bufs b;
     carve(p, nullptr, b);
     return b.total;
@@ -459,6 +471,7 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
                       void* workspace, size_t workspace_bytes, float* y, hipStream_t st) {
     Plan p;
     if (!build_plan(d, p)) return fail(RESR_ERR_ARG, "generator_forward: bad descriptor");
+    if (!plan_mx_train_ok(*d)) return fail(RESR_ERR_ARG, "generator_forward: x2_plan MX_TRAIN_FORWARD (2048) needs bits 1 + 32 + 64 + 256");
     if (!x || !params || !packed || !workspace || !y) return fail(RESR_ERR_ARG, "generator_forward: null argument");
     Bufs b;
     carve(p, (char*)workspace, b);
@@ -472,8 +485,10 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
     if ((long)N * h * w * 32 * 16 > 0x7fffffffL) return fail(RESR_ERR_ARG, "generator: batch x resolution too large for 32-bit chunk strides");
     const int plane = N * h * w * 32;  // elements per 32-channel plane of the chunk-planar trunk tensors
     // exact16 inference with single-f16 growth planes (RESR_X2_PLAN_GROWTH_F16_INFER): o1..o4 are stored without a lo tensor and
-    // read as two-stage chunks; a training forward keeps every pre-activation fp32-class (a rounded input flips LeakyReLU masks)
-    const bool growth_single = x2 && !d->training && (d->x2_plan & RESR_X2_PLAN_GROWTH_F16_INFER);
+    // read as two-stage chunks; a training forward keeps every pre-activation fp32-class (a rounded input flips LeakyReLU masks) --
+    // unless it runs the inference MX plan on purpose (RESR_X2_PLAN_MX_TRAIN_FORWARD: the same bits as that inference forward)
+    const bool mx_train = plan_mx_train(*d);
+    const bool growth_single = x2 && (!d->training || mx_train) && (d->x2_plan & RESR_X2_PLAN_GROWTH_F16_INFER);
     const bool growth_w16 = growth_single && (d->x2_plan & RESR_X2_PLAN_GROWTH_W16_INFER);   // ... and meet f16 weights: one stage per growth chunk
     // RESR_F16X2: element offset hi -> lo of a buffer holding `planes` 32-channel planes of `pl` elements
     auto LO = [&](long planes, long pl) -> int64_t { return x2 ? planes * pl : 0; };
@@ -490,7 +505,7 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
     const char* pk_mx = mx ? pk + generator_mx_offset(d) : nullptr;
     auto MXP = [&](ResrConvDesc& cd, const ConvSpec& c, int64_t in_q, int64_t out_q) {
         if (!mx) return;
-        cd.flags |= RESR_CONV_MX_PAIRS;
+        cd.flags |= RESR_CONV_MX_PAIRS | (mx_train ? RESR_CONV_MX_SIGNBITS : 0);   // (a training forward's LeakyReLU passes write sign words)
         cd.in0_q_offset = in_q; cd.out_q_offset = out_q;
         cd.w_mx_offset = (int64_t)((pk_mx + c.pk_fwd * 2) - W(c));
     };
@@ -610,6 +625,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
     (void)params;
     Plan p;
     if (!build_plan(d, p)) return fail(RESR_ERR_ARG, "generator_backward: bad descriptor");
+    if (!plan_mx_train_ok(*d)) return fail(RESR_ERR_ARG, "generator_backward: x2_plan MX_TRAIN_FORWARD (2048) needs bits 1 + 32 + 64 + 256");
     if (n_events != 0 && (!events || n_events != d->n_blocks + 2))
         return fail(RESR_ERR_ARG, "generator_backward: grad_ready_events needs n_blocks + 2 = %d events, got %d", d->n_blocks + 2, n_events);
     // a range of the gradient arena is final once its weight-gradient reductions are enqueued: tell the caller's comm stream

@@ -231,7 +231,11 @@ class Generator(nn.Module):
     2^-12-weighted tap-products of every stream chunk as ONE MX job (8-bit transpose reads of the q records, K = 32 pixels twice) --
     conv1..conv4 get their (x_hi, g_lo) term back at no cost: worst gradient tensor 5-7e-5 against the all-pairs plan instead of 2-3e-4;
     bit 8 (opt-in): exact16's forward in front of fast mode's backward pass; bit 10 (opt-in, with bit 9): the 4x-resolution tail (conv3, conv4, upsampling2)
-    on MX stages / MX jobs too -- + 0.85 % on the step, every gradient tensor still within 6-8e-5 of the all-pairs plan (median 2.6e-5 -> 4.3e-5).  x2_plan=0 = pairs everywhere: forward 1.8e-6, every gradient tensor 5.8e-6.
+    on MX stages / MX jobs too -- + 0.85 % on the step, every gradient tensor still within 6-8e-5 of the all-pairs plan (median 2.6e-5 -> 4.3e-5);
+    bit 11 (opt-in, with bits 0 + 5 + 6 + 8; the named plan _lib.X2_PLAN_OUTPUT_PARITY = 2401, "output parity"): a TRAINING forward runs the
+    inference MX plan of bits 0 + 5 + 6 -- the same bits as an inference forward of plan 97, output ~1e-4 of the fp32 oracle (gate 2e-4) --,
+    its LeakyReLU passes still write their sign words, and bit 8's f16 backward pass runs behind it (gradients in fast mode's class: a fifth of
+    its distance from the all-pairs plan, the MX forward's mask flips); 108 images/s where bit 8 runs 83 and the default plan 61.  x2_plan=0 = pairs everywhere: forward 1.8e-6, every gradient tensor 5.8e-6.
     The backward pass of the 16-bit modes (exact16, fast) does not depend on the caller's loss scale: an incoming gradient whose largest element is below 2^6 is
     lifted by a power of two inside the native pass and the results are handed back unscaled (bit-identical gradients at loss scale
     1 and 2^20; csrc/generator.hip, $RESR_X2_GRAD_PRESCALE_LOG2 / RESR_X2_NO_GRAD_PRESCALE=1).
@@ -249,17 +253,20 @@ class Generator(nn.Module):
         self.precision = precision or os.environ.get("RESR_PRECISION", "fast")
         self._dtype = _precision_to_dtype(self.precision)
         self.x2_plan = int(os.environ.get("RESR_X2_PLAN", "763")) if x2_plan is None else int(x2_plan)
-        if not 0 <= self.x2_plan <= 2047:
+        if not 0 <= self.x2_plan <= 4095:
             raise ValueError(f"x2_plan must be a bit set of X2_PLAN_GROWTH_F16_INFER (1) | X2_PLAN_GROWTH_GRAD_F16 (2) | "
                              f"X2_PLAN_GROWTH_GRAD_STORE_F16 (4) | X2_PLAN_GROWTH_ACT_F16_WGRAD (8) | X2_PLAN_GROWTH_ACT_G_HI_WGRAD (16) | X2_PLAN_GROWTH_W16_INFER (32) | "
-                             f"X2_PLAN_MX_INFER (64) | X2_PLAN_MX_BWD (128) | X2_PLAN_F16_BACKWARD (256) | X2_PLAN_MX_WGRAD (512) | X2_PLAN_MX_TAIL (1024), got {self.x2_plan}")
+                             f"X2_PLAN_MX_INFER (64) | X2_PLAN_MX_BWD (128) | X2_PLAN_F16_BACKWARD (256) | X2_PLAN_MX_WGRAD (512) | X2_PLAN_MX_TAIL (1024) | "
+                             f"X2_PLAN_MX_TRAIN_FORWARD (2048), got {self.x2_plan}")
         if (self.x2_plan & 128) and (self.x2_plan & 4):
             raise ValueError(f"x2_plan={self.x2_plan}: MX_BWD (128) reads the growth-plane gradients as pairs; GROWTH_GRAD_STORE_F16 (4) stores them single")
         # a bit that only refines another one means nothing without it: refuse instead of silently ignoring it
         for bit, needs, name in ((4, 2, "GROWTH_GRAD_STORE_F16 (4) refines GROWTH_GRAD_F16 (2)"), (16, 8, "GROWTH_ACT_G_HI_WGRAD (16) refines GROWTH_ACT_F16_WGRAD (8)"),
                                  (32, 1, "GROWTH_W16_INFER (32) refines GROWTH_F16_INFER (1)"), (64, 33, "MX_INFER (64) rides on GROWTH_F16_INFER (1) + GROWTH_W16_INFER (32)"),
                                  (512, 128 + 8, "MX_WGRAD (512) rides on MX_BWD (128: the gradient planes' q tensors) + GROWTH_ACT_F16_WGRAD (8: the stream chunks are the pair chunks)"),
-                                 (1024, 512 + 128 + 8, "MX_TAIL (1024) extends MX_WGRAD (512) to the 4x-resolution tail")):
+                                 (1024, 512 + 128 + 8, "MX_TAIL (1024) extends MX_WGRAD (512) to the 4x-resolution tail"),
+                                 (2048, 1 + 32 + 64 + 256, "MX_TRAIN_FORWARD (2048) runs the inference MX forward (1 + 32 + 64) in training, "
+                                                           "in front of the f16 backward pass (256)")):
             if (self.x2_plan & bit) and (self.x2_plan & needs) != needs:
                 raise ValueError(f"x2_plan={self.x2_plan}: {name}")
         self.n_blocks = n_blocks or self.N_BLOCKS
@@ -405,7 +412,7 @@ class Generator(nn.Module):
             _lib.check(L.resr_pack_weights(_lib.ptr(raw), n, _lib.ptr(flat), _lib.ptr(self._packed_f16), _lib.RESR_F16, _lib.stream_ptr(flat)),
                        "resr_pack_weights (f16 backward)")
         if self._dtype == _lib.RESR_F16X2 and (((desc.x2_plan & _lib.X2_PLAN_MX_INFER) and not desc.training) or
-                                               ((desc.x2_plan & _lib.X2_PLAN_MX_BWD) and desc.training)):
+                                               ((desc.x2_plan & (_lib.X2_PLAN_MX_BWD | _lib.X2_PLAN_MX_TRAIN_FORWARD)) and desc.training)):
             # the MX blocks of the same table ([bf8(W1) | bf8(W2)] per tap and row), behind the f16 blocks of the packed buffer
             mx_off = int(L.resr_generator_mx_offset(C.byref(desc)))
             _lib.check(L.resr_pack_weights_mx(_lib.ptr(raw), n, _lib.ptr(flat), C.c_void_p(self._packed.data_ptr() + mx_off),
@@ -413,7 +420,7 @@ class Generator(nn.Module):
 
     def _workspace(self, desc: _lib.GeneratorDesc, device) -> _Workspace:
         L = _lib.lib()
-        key = (desc.n, desc.h, desc.w, desc.training, desc.dtype, desc.wgrad_splits, desc.x2_plan & (_lib.X2_PLAN_MX_INFER | _lib.X2_PLAN_MX_BWD | _lib.X2_PLAN_MX_WGRAD | _lib.X2_PLAN_MX_TAIL))   # (the MX plans carry q tensors)
+        key = (desc.n, desc.h, desc.w, desc.training, desc.dtype, desc.wgrad_splits, desc.x2_plan & (_lib.X2_PLAN_MX_INFER | _lib.X2_PLAN_MX_BWD | _lib.X2_PLAN_MX_WGRAD | _lib.X2_PLAN_MX_TAIL | _lib.X2_PLAN_MX_TRAIN_FORWARD))   # (the MX plans carry q tensors)
         pool = self._workspaces.setdefault(key, [])
         for ws in pool:
             if not ws.busy:
