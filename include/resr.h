@@ -516,6 +516,19 @@ int resr_discriminator_forward(const ResrDiscriminatorDesc* d, const float* x_nc
 /* grad_params = NULL: gradient wrt the input only (the generator's adversarial term, discriminator frozen); gx_nchw optional */
 int resr_discriminator_backward(const ResrDiscriminatorDesc* d, const float* gy_nchw, const float* params, void* workspace,
                                 size_t workspace_bytes, float* grad_params, float* gx_nchw, void* stream);
+/* Output-parity backward (opt-in): after a RESR_F16X2 forward with training = 1 (d->dtype = RESR_F16X2, the same descriptor and
+ * workspace), the backward pass in RESR_F16 arithmetic -- fast mode's kernels (backward-data conv, weight gradients, bilinear /
+ * depth-to-space glue with their LeakyReLU masks, fold, spectral-norm backward with THIS call's u, v and sigma) on the hi halves
+ * of the activations the forward stored (same pixel strides, lo offsets 0).  The forward and its outputs are exact16's, untouched;
+ * the gradients are in fast mode's class.  LeakyReLU masks come from sign(hi): that is the sign of the forward's fp32 value
+ * except where |value| < 2^-25 (hi rounds to a signed zero).  The f16 weights are packed inside this call, from the 1/sigma the
+ * forward left at the head of the workspace, into the workspace's packed region (the next forward repacks its own form there);
+ * `table_dev` / `n_chunks` are the forward's: resr_discriminator_pack_table does not depend on the dtype.  Same contract as
+ * resr_discriminator_backward otherwise: grad_params = NULL gives the input gradient only, gx_nchw is optional, the gradient
+ * lift and its sticky back-off use the same workspace slot; no allocation, no host synchronisation. */
+int resr_discriminator_backward_f16(const ResrDiscriminatorDesc* d, const float* gy_nchw, const float* params,
+                                    const ResrPackChunk* table_dev, int32_t n_chunks, void* workspace, size_t workspace_bytes,
+                                    float* grad_params, float* gx_nchw, void* stream);
 
 /* EMA.update (model.py:43-48) over the flat parameter arena, one launch. */
 int resr_ema_update(float* shadow, const float* params, int64_t count, double decay, void* stream);

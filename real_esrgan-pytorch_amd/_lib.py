@@ -91,6 +91,7 @@ _PROTOS = {
     "resr_discriminator_pack_table": (C.c_int64, [C.POINTER(DiscriminatorDesc), _P, _P, C.c_int64]),
     "resr_discriminator_forward": (C.c_int, [C.POINTER(DiscriminatorDesc), _P, _P, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P]),
     "resr_discriminator_backward": (C.c_int, [C.POINTER(DiscriminatorDesc), _P, _P, _P, C.c_size_t, _P, _P, _P]),
+    "resr_discriminator_backward_f16": (C.c_int, [C.POINTER(DiscriminatorDesc), _P, _P, _P, C.c_int32, _P, C.c_size_t, _P, _P, _P]),
     "resr_version": (C.c_int, []),
     "resr_last_error": (C.c_char_p, []),
     "resr_conv3x3": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),

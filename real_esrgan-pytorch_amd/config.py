@@ -60,7 +60,14 @@ device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
 #   inference.py:52-53 and test.py:79-80 run the generator in plain fp32 (no autocast)               ->  `inference_precision`,
 #     default "exact16" = split-operand f16 MFMA, fp32-class results (the mode inside the 1e-3 parity tolerance).
 # "strict" (f32 MFMA) is accepted by both; inference.py --precision, $RESR_PRECISION (train) and $RESR_INFERENCE_PRECISION override.
-precision = os.environ.get("RESR_PRECISION", "fast")
+# Output parity ($RESR_OUTPUT_PARITY=1; off by default): outputs and losses inside the 1e-3 tolerance, gradients in fast mode's class.
+# Precision exact16, the generator on x2_plan 2401 (_lib.X2_PLAN_OUTPUT_PARITY: the inference MX forward in training, an f16
+# backward pass behind it), the discriminator and ContentLoss with f16_backward=True (exact16 forward, fast mode's backward pass).
+# The train scripts take their module arguments from generator_options() / backward_options() below.
+output_parity = os.environ.get("RESR_OUTPUT_PARITY", "0") == "1"
+precision = os.environ.get("RESR_PRECISION", "exact16" if output_parity else "fast")
+if output_parity and precision != "exact16":
+    raise ValueError(f"RESR_OUTPUT_PARITY=1 runs in exact16; RESR_PRECISION={precision!r} contradicts it")
 inference_precision = os.environ.get("RESR_INFERENCE_PRECISION", "exact16")
 niqe_model_path = "./results/pretrained_models/niqe_model.mat"
 in_channels = 3
@@ -116,3 +123,25 @@ if mode == "test":
     sr_dir = f"./results/test/{exp_name}"
     hr_dir = "./data/Set5/GTmod12"
     model_path = "./results/pretrained_models/RealESRGAN_x4-DFO2K-678bf481.pth.tar"
+
+
+def train_precision() -> str:
+    """The training modules' precision: exact16 in output-parity mode, `precision` otherwise."""
+    return "exact16" if output_parity else precision
+
+
+def generator_options() -> dict:
+    """Keyword arguments of the training Generator (train_realesrnet.py, train_realesrgan.py)."""
+    from . import _lib
+    opts = {"precision": train_precision()}
+    if output_parity:
+        opts["x2_plan"] = _lib.X2_PLAN_OUTPUT_PARITY
+    return opts
+
+
+def backward_options() -> dict:
+    """Keyword arguments of the training Discriminator and ContentLoss."""
+    opts = {"precision": train_precision()}
+    if output_parity:
+        opts["f16_backward"] = True
+    return opts

@@ -15,6 +15,9 @@ last one alias its ReLU-ed value -- reproduced here under `inplace_relu_aliasing
 extractor over a plain-torch clone of the module structure (tests/test_oracle_vgg_extractor.py), not against torchvision itself.
 
 precision: "fast" (f16), "exact16" (hi/lo f16 pairs, fp32-class) or "strict" (f32), as for `Generator`.
+f16_backward (exact16 only, as for `Discriminator`; default $RESR_X2_F16_BACKWARD = "1"): the output-parity operating point -- the
+forward and the five losses are exact16's, the backward pass (detached=False only: the detached term has none) is fast mode's,
+RESR_F16 on the hi halves of the saved activations (ReLU masks, max-pool argmax) against an f16 packing of the same frozen weights.
 """
 from __future__ import annotations
 
@@ -27,7 +30,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .model import _precision_to_dtype
+from .model import _f16_backward_flag, _precision_to_dtype
 
 _CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512, 512, 512, 512, "M", 512, 512, 512, 512]
 
@@ -93,11 +96,12 @@ class _FeatureFn(torch.autograd.Function):
 class ContentLoss(nn.Module):
     def __init__(self, feature_model_extractor_nodes: list, feature_model_normalize_mean: list,
                  feature_model_normalize_std: list, precision: Optional[str] = None,
-                 inplace_relu_aliasing: bool = True, detached: bool = True) -> None:
+                 inplace_relu_aliasing: bool = True, detached: bool = True, f16_backward: Optional[bool] = None) -> None:
         super().__init__()
         self.feature_model_extractor_nodes = feature_model_extractor_nodes
         self.precision = precision or os.environ.get("RESR_PRECISION", "fast")
         self._dtype = _precision_to_dtype(self.precision)
+        self.f16_backward = _f16_backward_flag(self.precision, f16_backward, "ContentLoss")
         self.aliasing = inplace_relu_aliasing
         self.detached = detached
         self.features = nn.Module()
@@ -120,12 +124,14 @@ class ContentLoss(nn.Module):
         for p in self.parameters():               # reference model.py:307-309
             p.requires_grad = False
         self._packed = None
+        self._packed_f16 = None                   # f16_backward: the f16 packing of the same weights (same table, plain layout)
 
     # ---- weights ---------------------------------------------------------------------------------------------
     def _pack(self, device):
         """Pack all 16 convs once (frozen weights): the forward form per conv -- cout groups of 64, K chunks of 32 -- and the
-        backward-data form (M = cin groups of 64, K = cout chunks, taps flipped)."""
-        if self._packed is not None and self._packed[0].device == device:
+        backward-data form (M = cin groups of 64, K = cout chunks, taps flipped).  f16_backward: the same table once more in
+        RESR_F16 (the table counts elements of the plain layout, so the group offsets serve both buffers)."""
+        if self._packed is not None and self._packed[0].device == device and (self._packed_f16 is not None or not self.f16_backward):
             return
         L = _lib
         flat = torch.cat([getattr(self.features, str(l[1])).weight.detach().float().reshape(-1) for l in self.layers if l[0] == "conv"]).to(device)
@@ -151,10 +157,15 @@ class ContentLoss(nn.Module):
         packed = torch.zeros(off * self._wes + 16384, dtype=torch.uint8, device=device)
         L.check(L.lib().resr_pack_weights(L.ptr(table), len(chunks), L.ptr(flat), L.ptr(packed), self._dtype, L.stream_ptr(flat)),
                 "resr_pack_weights")
+        self._packed_f16 = None
+        if self.f16_backward:
+            self._packed_f16 = torch.zeros(off * 2 + 16384, dtype=torch.uint8, device=device)
+            L.check(L.lib().resr_pack_weights(L.ptr(table), len(chunks), L.ptr(flat), L.ptr(self._packed_f16), L.RESR_F16,
+                                              L.stream_ptr(flat)), "resr_pack_weights (f16 backward)")
         self._packed = (packed, fwd, bwd)
 
     def load_state_dict(self, state_dict, strict: bool = True):
-        self._packed = None
+        self._packed = self._packed_f16 = None
         sd = {("features." + k[len("features."):]) if k.startswith("features.") else k: v for k, v in state_dict.items()}
         sd = {k: v for k, v in sd.items() if k.startswith("features.") and int(k.split(".")[1]) <= 34}
         sd.setdefault("mean", self.mean)
@@ -163,20 +174,22 @@ class ContentLoss(nn.Module):
 
     # ---- native passes ---------------------------------------------------------------------------------------
     def _conv(self, x: _Act, groups, k_real: int, m_real: int, out: _Act, flags: int, bias, aux: Optional[_Act], mask: Optional[_Act],
-              n: int, st) -> None:
-        """One 3x3 convolution as launches of 64 output channels: x (first r32(k_real) channels) -> out (m_real channels)."""
+              n: int, st, dtype: Optional[int] = None) -> None:
+        """One 3x3 convolution as launches of 64 output channels: x (first r32(k_real) channels) -> out (m_real channels).
+        dtype: the launch arithmetic, the module's by default; RESR_F16 in an exact16 module is the f16 backward's (its own pack)."""
         L, lib = _lib, _lib.lib()
-        packed = self._packed[0]
+        dt = self._dtype if dtype is None else dtype
+        packed, wes = (self._packed[0], self._wes) if dt == self._dtype else (self._packed_f16, 2)
         # All 64-channel output groups of a 128..512-channel layer as ONE launch (ResrConvDesc.cout_groups: tile index = group x
         # spatial tiles, per-group packed weights, biases and channel offsets).  One launch per group left the deep layers --
         # 512 channels at 32^2 / 16^2 pixels: 128 / 32 tiles per launch -- on an eighth of the 256 CUs.
-        if (len(groups) > 1 and len(groups) <= 8 and self._dtype != L.RESR_F32 and m_real == 64 * len(groups)
+        if (len(groups) > 1 and len(groups) <= 8 and dt != L.RESR_F32 and m_real == 64 * len(groups)
                 and all(mt == 2 for _, mt in groups) and os.environ.get("RESR_VGG_PER_GROUP") != "1"):
             d = L.ConvDesc(n, x.h, x.w, _r32(k_real), _r32(k_real), x.c, 0, 64, 64, out.c,
-                           0, 0, 0 if mask is None else mask.c, self._dtype, flags, 1.0, 1.0, 1.0, 1.0, 0.0)
+                           0, 0, 0 if mask is None else mask.c, dt, flags, 1.0, 1.0, 1.0, 1.0, 0.0)
             d.in0_lo_offset, d.out_lo_offset = x.lo, out.lo
             d.cout_groups = len(groups)
-            L.check(lib.resr_conv3x3(C.byref(d), x.ptr(), None, C.c_void_p(packed.data_ptr() + groups[0][0] * self._wes),
+            L.check(lib.resr_conv3x3(C.byref(d), x.ptr(), None, C.c_void_p(packed.data_ptr() + groups[0][0] * wes),
                                      None if bias is None else L.ptr(bias), None, None,
                                      None if mask is None else mask.ptr(), out.ptr(), None if aux is None else aux.ptr(), st),
                     "resr_conv3x3")
@@ -184,9 +197,9 @@ class ContentLoss(nn.Module):
         for gi, (off, mt) in enumerate(groups):
             g0 = gi * 64
             d = L.ConvDesc(n, x.h, x.w, _r32(k_real), _r32(k_real), x.c, 0, min(mt * 32, m_real - g0), mt * 32, out.c,
-                           0, 0, 0 if mask is None else mask.c, self._dtype, flags, 1.0, 1.0, 1.0, 1.0, 0.0)
+                           0, 0, 0 if mask is None else mask.c, dt, flags, 1.0, 1.0, 1.0, 1.0, 0.0)
             d.in0_lo_offset, d.out_lo_offset = x.lo, out.lo
-            L.check(lib.resr_conv3x3(C.byref(d), x.ptr(), None, C.c_void_p(packed.data_ptr() + off * self._wes),
+            L.check(lib.resr_conv3x3(C.byref(d), x.ptr(), None, C.c_void_p(packed.data_ptr() + off * wes),
                                      None if bias is None else C.c_void_p(bias.data_ptr() + g0 * 4), None, None,
                                      None if mask is None else mask.ptr(g0), out.ptr(g0), None if aux is None else aux.ptr(g0), st),
                     "resr_conv3x3")
@@ -231,32 +244,35 @@ class ContentLoss(nn.Module):
         return out, saved
 
     def _backward(self, saved, grads: Dict[str, torch.Tensor], b: int) -> torch.Tensor:
-        """d(sum of the tapped-feature cotangents) / d(sr): the first `b` images of the saved batch, layers in reverse."""
+        """d(sum of the tapped-feature cotangents) / d(sr): the first `b` images of the saved batch, layers in reverse.
+        f16_backward: every gradient tensor single f16 (RESR_F16 launches); the saved pair activations are read as their hi
+        halves -- the ReLU masks are hi-only in either arithmetic, the pool argmax bytes have no dtype."""
         L, lib = _lib, _lib.lib()
         _, _, bwd = self._packed
+        dt = L.RESR_F16 if self.f16_backward else self._dtype
         dev = self.mean.device
         st = L.stream_ptr(self.mean)
         g: Optional[_Act] = None                     # gradient wrt the current layer's OUTPUT (post-ReLU / pooled)
         for rec in reversed(saved):
             if rec[0] == "pool":
                 _, arg, ih, iw, c = rec
-                gin = _Act(b, ih, iw, c, self._dtype, dev)
-                L.check(lib.resr_maxpool2x2_bwd(g.ptr(), L.ptr(arg), gin.ptr(), b, ih // 2, iw // 2, c, self._dtype, st), "resr_maxpool2x2_bwd")
+                gin = _Act(b, ih, iw, c, dt, dev)
+                L.check(lib.resr_maxpool2x2_bwd(g.ptr(), L.ptr(arg), gin.ptr(), b, ih // 2, iw // 2, c, dt, st), "resr_maxpool2x2_bwd")
                 g = gin
                 continue
             _, idx, cin, cout, x_in, relu_out, tap_pre = rec
             tap = grads.get(f"features.{idx}")
             tap_act = None
             if tap is not None:
-                tap_act = _Act(b, relu_out.h, relu_out.w, cout, self._dtype, dev)
+                tap_act = _Act(b, relu_out.h, relu_out.w, cout, dt, dev)
                 tap_act.assign(tap.float())
             count = b * relu_out.h * relu_out.w * cout
             mask_view = _view(relu_out, b)
 
             def add_mask(a, bb, mask):
-                o = _Act(b, relu_out.h, relu_out.w, cout, self._dtype, dev)
+                o = _Act(b, relu_out.h, relu_out.w, cout, dt, dev)
                 L.check(lib.resr_add_mask(a.ptr(), None if bb is None else bb.ptr(), None if mask is None else mask.ptr(), o.ptr(), count,
-                                          self._dtype, 0.0, st), "resr_add_mask")
+                                          dt, 0.0, st), "resr_add_mask")
                 return o
             # gradient wrt the pre-activation: ReLU'(pre) = (relu_out > 0); a tap of the pre-activation joins behind the mask, a
             # tap of the (aliased) post-ReLU value in front of it
@@ -270,11 +286,11 @@ class ContentLoss(nn.Module):
                 g_pre = add_mask(g, tap_act, mask_view)
             if getattr(self, "_debug_grads", None) is not None:      # tools/diag_content_loss.py: gradient wrt every pre-activation
                 self._debug_grads[idx] = g_pre.value().permute(0, 3, 1, 2).cpu()
-            gin = _Act(b, x_in.h, x_in.w, x_in.c, self._dtype, dev)
-            self._conv(g_pre, bwd[idx], cout, _r32(cin), gin, L.CONV_NO_BIAS, None, None, None, b, st)
+            gin = _Act(b, x_in.h, x_in.w, x_in.c, dt, dev)
+            self._conv(g_pre, bwd[idx], cout, _r32(cin), gin, L.CONV_NO_BIAS, None, None, None, b, st, dt)
             g = gin
         gx = torch.empty((b, 3, g.h, g.w), dtype=torch.float32, device=dev)
-        L.check(lib.resr_nhwc_to_nchw(g.ptr(), L.ptr(gx), b, 3, g.h, g.w, 1, 32, self._dtype, st), "resr_nhwc_to_nchw")
+        L.check(lib.resr_nhwc_to_nchw(g.ptr(), L.ptr(gx), b, 3, g.h, g.w, 1, 32, dt, st), "resr_nhwc_to_nchw")
         return gx / self.std
 
     def _l1_halves(self, act: _Act, b: int) -> torch.Tensor:

@@ -104,6 +104,8 @@ int64_t discriminator_pack_table(const ResrDiscriminatorDesc*, const void*, Resr
 int discriminator_forward(const ResrDiscriminatorDesc*, const float*, const float*, float*, const ResrPackChunk*, int, void*, size_t, float*,
                           hipStream_t);
 int discriminator_backward(const ResrDiscriminatorDesc*, const float*, const float*, void*, size_t, float*, float*, hipStream_t);
+int discriminator_backward_f16(const ResrDiscriminatorDesc*, const float*, const float*, const ResrPackChunk*, int, void*, size_t, float*,
+                               float*, hipStream_t);
 
 int filter2d_dispatch(const float*, float*, const float*, int, int, int, int, int, int, int, hipStream_t);
 int usm_dispatch(const float*, float*, float*, const float*, int, float, float, int, int, int, int, hipStream_t, int);
@@ -267,6 +269,14 @@ int resr_discriminator_backward(const ResrDiscriminatorDesc* d, const float* gy_
                                 size_t workspace_bytes, float* grad_params, float* gx_nchw, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return discriminator_backward(d, gy_nchw, params, workspace, workspace_bytes, grad_params, gx_nchw, (hipStream_t)stream);
+}
+
+int resr_discriminator_backward_f16(const ResrDiscriminatorDesc* d, const float* gy_nchw, const float* params,
+                                    const ResrPackChunk* table_dev, int32_t n_chunks, void* workspace, size_t workspace_bytes,
+                                    float* grad_params, float* gx_nchw, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return discriminator_backward_f16(d, gy_nchw, params, table_dev, n_chunks, workspace, workspace_bytes, grad_params, gx_nchw,
+                                      (hipStream_t)stream);
 }
 
 int resr_ema_update(float* shadow, const float* params, int64_t count, double decay, void* stream) {

@@ -391,16 +391,19 @@ int discriminator_forward(const ResrDiscriminatorDesc* d, const float* x, const 
     return RESR_OK;
 }
 
-int discriminator_backward(const ResrDiscriminatorDesc* d, const float* gy, const float* params, void* workspace, size_t workspace_bytes,
-                           float* grad, float* gx, hipStream_t st) {
-    DPlan p;
-    if (!build(d, p)) return fail(RESR_ERR_ARG, "discriminator_backward: bad descriptor");
-    if (!d->training) return fail(RESR_ERR_ARG, "discriminator_backward: forward was not run with training=1");
-    if (!gy || !params || !workspace) return fail(RESR_ERR_ARG, "discriminator_backward: null argument");
+namespace {
+
+// The backward pass over the workspace plan `pc` (its carve: buffer addresses, slab room) in the arithmetic `dt`: pc.d.dtype itself,
+// or RESR_F16 over an exact16 workspace (discriminator_backward_f16: every pair buffer read and written as its hi half -- the hi
+// tensor starts the buffer, pixel strides are the same, lo offsets 0; the f16 packed weights are already in the packed region).
+int backward_pass(const DPlan& pc, int dt, const float* gy, const float* params, void* workspace, size_t workspace_bytes, float* grad,
+                  float* gx, hipStream_t st) {
     DBufs b;
-    carve(p, (char*)workspace, b);
+    carve(pc, (char*)workspace, b);
     if (b.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "discriminator_backward: workspace %zu < %zu", workspace_bytes, b.total);
-    const int dt = d->dtype, N = d->n, S = d->h, W = d->w;
+    DPlan p = pc;
+    p.d.dtype = dt;      // conv_layer's launches and element sizes follow the pass's arithmetic
+    const int N = p.d.n, S = p.d.h, W = p.d.w;
     const size_t es = elem_size(dt);
     const int H1 = S / 2, W1 = W / 2, H2 = S / 4, W2 = W / 4, H3 = S / 8, W3 = W / 8;
     const int NB = RESR_CONV_NO_BIAS, MK = RESR_CONV_MASK;
@@ -529,6 +532,36 @@ int discriminator_backward(const ResrDiscriminatorDesc* d, const float* gy, cons
         DRUN(nhwc_to_nchw_scaled_dispatch(b.gxin, gx, N, 3, S, W, 1, 32, dt, st, lo_in, gsc));
     }
     return RESR_OK;
+}
+
+}  // namespace
+
+int discriminator_backward(const ResrDiscriminatorDesc* d, const float* gy, const float* params, void* workspace, size_t workspace_bytes,
+                           float* grad, float* gx, hipStream_t st) {
+    DPlan p;
+    if (!build(d, p)) return fail(RESR_ERR_ARG, "discriminator_backward: bad descriptor");
+    if (!d->training) return fail(RESR_ERR_ARG, "discriminator_backward: forward was not run with training=1");
+    if (!gy || !params || !workspace) return fail(RESR_ERR_ARG, "discriminator_backward: null argument");
+    return backward_pass(p, d->dtype, gy, params, workspace, workspace_bytes, grad, gx, st);
+}
+
+// Output-parity backward: fast mode's pass behind an exact16 forward.  The f16 pack overwrites the start of the exact16 packed
+// region (its plain layout is a third of the pair layout's size); every forward packs its own form again, so the next forward on
+// this workspace computes what it computes on a fresh one.
+int discriminator_backward_f16(const ResrDiscriminatorDesc* d, const float* gy, const float* params, const ResrPackChunk* table,
+                               int n_chunks, void* workspace, size_t workspace_bytes, float* grad, float* gx, hipStream_t st) {
+    DPlan p;
+    if (!build(d, p)) return fail(RESR_ERR_ARG, "discriminator_backward_f16: bad descriptor");
+    if (d->dtype != RESR_F16X2) return fail(RESR_ERR_ARG, "discriminator_backward_f16: the forward must be RESR_F16X2 (exact16)");
+    if (!d->training) return fail(RESR_ERR_ARG, "discriminator_backward_f16: forward was not run with training=1");
+    if (!gy || !params || !table || !workspace) return fail(RESR_ERR_ARG, "discriminator_backward_f16: null argument");
+    if (n_chunks != p.n_chunks) return fail(RESR_ERR_ARG, "discriminator_backward_f16: pack table has %d chunks, expected %d", n_chunks, p.n_chunks);
+    DBufs b;
+    carve(p, (char*)workspace, b);
+    if (b.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "discriminator_backward_f16: workspace %zu < %zu", workspace_bytes, b.total);
+    // the table's scale_ptr entries read 1/sigma of THIS call's forward from the workspace head
+    DRUN(pack_dispatch(table, n_chunks, params, b.packed, RESR_F16, st));
+    return backward_pass(p, RESR_F16, gy, params, workspace, workspace_bytes, grad, gx, st);
 }
 
 }  // namespace resr

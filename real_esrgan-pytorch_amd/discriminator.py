@@ -25,7 +25,7 @@ from torch import nn
 from torch.nn.utils import spectral_norm
 
 from . import _lib
-from .model import _precision_to_dtype
+from .model import _f16_backward_flag, _precision_to_dtype
 
 
 class _DWorkspace:
@@ -86,12 +86,19 @@ class _DiscFn(torch.autograd.Function):
 class Discriminator(nn.Module):
     """Reference `Discriminator()` (model.py:135-203).  Extra keyword `precision`, as for `Generator`: "fast" (f16 MFMA, fp32
     accumulate), "exact16" (split-operand f16 MFMA on hi/lo pairs: fp32-class results, the mode that meets the 1e-3 parity
-    tolerance) or "strict" (f32 MFMA); anything else raises."""
+    tolerance) or "strict" (f32 MFMA); anything else raises.
 
-    def __init__(self, precision: Optional[str] = None) -> None:
+    `f16_backward` (exact16 only; default $RESR_X2_F16_BACKWARD = "1", read for exact16 modules only): the output-parity
+    operating point, the discriminator's counterpart of the generator's x2_plan bit 8.  The forward -- logits, u / v updates --
+    is exact16's, bit for bit; the backward pass is fast mode's f16 pass on the hi halves of the saved pair activations, with
+    an f16 packing of the same weights and this call's sigma (`resr_discriminator_backward_f16`).  Gradients are then in fast
+    mode's class.  An explicit True with "fast" or "strict" raises ValueError."""
+
+    def __init__(self, precision: Optional[str] = None, f16_backward: Optional[bool] = None) -> None:
         super().__init__()
         self.precision = precision or os.environ.get("RESR_PRECISION", "fast")
         self._dtype = _precision_to_dtype(self.precision)          # ValueError for an unknown precision: never a silent downgrade
+        self.f16_backward = _f16_backward_flag(self.precision, f16_backward, "Discriminator")
         self.conv1 = nn.Conv2d(3, 64, (3, 3), (1, 1), (1, 1))
         self.down_block1 = nn.Sequential(spectral_norm(nn.Conv2d(64, 128, (4, 4), (2, 2), (1, 1), bias=False)), nn.LeakyReLU(0.2, True))
         self.down_block2 = nn.Sequential(spectral_norm(nn.Conv2d(128, 256, (4, 4), (2, 2), (1, 1), bias=False)), nn.LeakyReLU(0.2, True))
@@ -200,7 +207,8 @@ class Discriminator(nn.Module):
 
     # ---- C-ABI plumbing ---------------------------------------------------------------------------------------
     def _workspace(self, desc, device) -> _DWorkspace:
-        key = (desc.n, desc.h, desc.w, desc.training, desc.dtype)
+        # the output-parity backward leaves f16 weights in a training workspace's packed region: a pool of its own
+        key = (desc.n, desc.h, desc.w, desc.training, desc.dtype) + ((True,) if self.f16_backward and desc.training else ())
         pool = self._workspaces.setdefault(key, [])
         for ws in pool:
             if not ws.busy and ws.buf.device == device:
@@ -236,8 +244,13 @@ class Discriminator(nn.Module):
         # and the per-parameter views it is handed stay consecutive in memory (one all-reduce for the data-parallel exchange)
         gflat = torch.zeros_like(flat) if need_w else None
         gx = torch.empty((desc.n, 3, desc.h, desc.w), dtype=torch.float32, device=gy.device) if need_gx else None
-        _lib.check(L.resr_discriminator_backward(C.byref(desc), _lib.ptr(gy), _lib.ptr(flat), _lib.ptr(ws.buf), ws.buf.numel(),
-                                                 _lib.ptr(gflat), _lib.ptr(gx), _lib.stream_ptr(gy)), "resr_discriminator_backward")
+        if self.f16_backward:
+            _lib.check(L.resr_discriminator_backward_f16(C.byref(desc), _lib.ptr(gy), _lib.ptr(flat), _lib.ptr(ws.table), ws.n_chunks,
+                                                         _lib.ptr(ws.buf), ws.buf.numel(), _lib.ptr(gflat), _lib.ptr(gx),
+                                                         _lib.stream_ptr(gy)), "resr_discriminator_backward_f16")
+        else:
+            _lib.check(L.resr_discriminator_backward(C.byref(desc), _lib.ptr(gy), _lib.ptr(flat), _lib.ptr(ws.buf), ws.buf.numel(),
+                                                     _lib.ptr(gflat), _lib.ptr(gx), _lib.stream_ptr(gy)), "resr_discriminator_backward")
         if not need_w:
             return [None] * len(self._ordered_params()), gx
         if self.grad_hook is not None:

@@ -34,6 +34,17 @@ def _precision_to_dtype(precision: str) -> int:
                      f"fp32-class results) or 'strict' (f32 MFMA), got {precision!r}")
 
 
+def _f16_backward_flag(precision: str, f16_backward: Optional[bool], what: str) -> bool:
+    """The output-parity backward of `Discriminator` / `ContentLoss`: exact16's forward, fast mode's f16 backward behind it.
+    None = $RESR_X2_F16_BACKWARD ("1" = on), applied to exact16 modules only; an explicit True outside exact16 raises."""
+    if f16_backward is None:
+        return precision == "exact16" and os.environ.get("RESR_X2_F16_BACKWARD", "0") == "1"
+    if f16_backward and precision != "exact16":
+        raise ValueError(f"{what}: f16_backward=True runs fast mode's backward behind an exact16 forward; precision={precision!r} "
+                         "has no such pass (fast is f16 throughout, strict f32)")
+    return bool(f16_backward)
+
+
 class ResidualDenseBlock(nn.Module):
     """Parameter container for one dense block (reference model.py:64-106).
 

@@ -36,10 +36,9 @@ from .train_realesrnet import ScalarWriter, load_dataset, validate  # noqa: F401
 
 def build_model() -> List[nn.Module]:
     """Reference train_realesrgan.py:223-237."""
-    precision = getattr(config, "precision", "fast")
-    discriminator = Discriminator(precision=precision).to(device=config.device)
+    discriminator = Discriminator(**config.backward_options()).to(device=config.device)    # (output parity: config.py)
     generator = Generator(config.in_channels, config.out_channels, config.upscale_factor,
-                          precision=precision).to(device=config.device)
+                          **config.generator_options()).to(device=config.device)
     ema_model = EMA(generator, config.ema_model_weight_decay).to(device=config.device)
     ema_model.register()
     return [discriminator, generator, ema_model]
@@ -52,7 +51,7 @@ def define_loss() -> List[nn.Module]:
     pixel_criterion = nn.L1Loss().to(device=config.device)
     content_criterion = ContentLoss(config.feature_model_extractor_nodes, config.feature_model_normalize_mean,
                                     config.feature_model_normalize_std,
-                                    precision=getattr(config, "precision", "fast")).to(device=config.device)
+                                    **config.backward_options()).to(device=config.device)
     adversarial_criterion = nn.BCEWithLogitsLoss().to(device=config.device)
     return [pixel_criterion, content_criterion, adversarial_criterion]
 
@@ -122,7 +121,7 @@ def main() -> None:
     os.makedirs(samples_dir, exist_ok=True)
     os.makedirs(results_dir, exist_ok=True)
     writer = ScalarWriter(os.path.join("samples", "logs", config.exp_name), enabled=rank == 0)
-    scaler = torch.amp.GradScaler("cuda") if getattr(config, "precision", "fast") != "strict" else None
+    scaler = torch.amp.GradScaler("cuda") if config.train_precision() != "strict" else None
     niqe_model = NIQE(config.upscale_factor, config.niqe_model_path).to(device=config.device)
     for epoch in range(start_epoch, config.epochs):
         sampler = getattr(train_prefetcher.original_dataloader, "sampler", None)

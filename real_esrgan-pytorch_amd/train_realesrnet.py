@@ -83,7 +83,7 @@ def load_dataset() -> List[CUDAPrefetcher]:
 def build_model() -> List[nn.Module]:
     """Reference train_realesrnet.py:175-183."""
     model = Generator(config.in_channels, config.out_channels, config.upscale_factor,
-                      precision=getattr(config, "precision", "fast")).to(device=config.device)
+                      **config.generator_options()).to(device=config.device)        # (output parity: config.py)
     ema_model = EMA(model, config.ema_model_weight_decay).to(device=config.device)
     ema_model.register()
     return [model, ema_model]
@@ -151,7 +151,7 @@ def main() -> None:
     os.makedirs(samples_dir, exist_ok=True)
     os.makedirs(results_dir, exist_ok=True)
     writer = ScalarWriter(os.path.join("samples", "logs", config.exp_name), enabled=_RANK == 0)
-    scaler = torch.amp.GradScaler("cuda") if getattr(config, "precision", "fast") != "strict" else None
+    scaler = torch.amp.GradScaler("cuda") if config.train_precision() != "strict" else None
     niqe_model = NIQE(config.upscale_factor, config.niqe_model_path).to(device=config.device)
     for epoch in range(start_epoch, config.epochs):
         sampler = getattr(train_prefetcher.original_dataloader, "sampler", None)
