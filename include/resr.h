@@ -366,6 +366,34 @@ int resr_generator_backward(const ResrGeneratorDesc* d, const float* gy_nchw, co
                             float* grad_params, float* gx_nchw, void* stream,
                             void* const* grad_ready_events, int32_t n_events);
 
+/* Compact generator (upstream Real-ESRGAN's SRVGGNetCompact: realesr-animevideov3, realesr-general-x4v3), forward only.
+ * x [N,3,H,W] -> conv 3->64, act, num_conv x (conv 64->64, act), conv 64->3*s*s, pixel-shuffle(s), + nearest-upsampled x
+ * -> y [N,3,sH,sW] fp32 NCHW, no clamp.  Any H, W >= 1 (no padding beyond each conv's own).  Parameters in the upstream
+ * module's named_parameters() order: per conv k = 0 .. num_conv + 1 its weight [cout,cin,3,3] and bias [cout], and behind
+ * every conv but the last, with act = RESR_COMPACT_PRELU, the 64 PReLU slopes.  Passes: the input as NHWC (channels padded to
+ * 32), num_conv + 1 64-channel convolutions ping-ponging between two NHWC workspace buffers (bias + activation in the
+ * epilogue: per-channel PReLU as v > 0 ? v : a[c] * v, LeakyReLU 0.1, ReLU), the last conv as an fp32 NCHW tensor, then one
+ * launch for pixel-shuffle + residual.  See real_esrgan-pytorch_amd/csrc/compact.hip. */
+enum { RESR_COMPACT_PRELU = 0, RESR_COMPACT_LRELU = 1, RESR_COMPACT_RELU = 2 };
+typedef struct {
+    int32_t n, h, w;          /* input batch / height / width                                     */
+    int32_t num_conv;         /* 64->64 body convs (upstream num_conv: 16 or 32)                  */
+    int32_t upscale;          /* 1, 2, 3 or 4                                                     */
+    int32_t act;              /* RESR_COMPACT_*                                                   */
+    int32_t dtype;            /* RESR_F16 fast / RESR_F16X2 exact16 (three-stage pairs) / RESR_F32 strict */
+    int32_t reserved_;
+} ResrCompactDesc;
+
+/* Host planning calls (no GPU needed); 0 (or RESR_ERR_ARG from the pack table) for an invalid descriptor. */
+size_t resr_compact_param_count(const ResrCompactDesc* d);
+/* bytes of the packed-weight buffer resr_pack_weights fills from resr_compact_pack_table(d) (dst offsets relative to it) */
+size_t resr_compact_packed_bytes(const ResrCompactDesc* d);
+int64_t resr_compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* chunks, int64_t capacity);
+size_t resr_compact_workspace_bytes(const ResrCompactDesc* d);
+/* Enqueues the whole network on `stream`: no allocation, no synchronisation, graph-capture safe (as resr_generator_forward). */
+int resr_compact_forward(const ResrCompactDesc* d, const float* x_nchw, const float* params, const void* packed,
+                         void* workspace, size_t workspace_bytes, float* y_nchw, void* stream);
+
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */
 

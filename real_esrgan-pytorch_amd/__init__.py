@@ -3,12 +3,14 @@
 Import as `real_esrgan_pytorch_amd` (the sibling shim package maps the importable name onto this
 directory, whose name is fixed by the project layout and is not a valid Python identifier).
 
-Contents: `model` (Generator / EMA behind the reference's nn.Module surface), `_lib` (ctypes
+Contents: `model` (Generator / EMA behind the reference's nn.Module surface), `compact` (upstream's SRVGGNetCompact, forward only), `_lib` (ctypes
 binding of csrc/libresr_hip.so, C-ABI in include/resr.h), `csrc/` (HIP kernels + the C-ABI).
 """
 from . import _lib  # noqa: F401
-from .model import EMA, Generator, ResidualDenseBlock, ResidualResidualDenseBlock  # noqa: F401
+from .model import EMA, Generator, ResidualDenseBlock, ResidualResidualDenseBlock, load_official_state_dict  # noqa: F401
+from .compact import SRVGGNetCompact  # noqa: F401
 from .discriminator import Discriminator  # noqa: F401
 from .content_loss import ContentLoss  # noqa: F401
 
-__all__ = ["EMA", "Generator", "Discriminator", "ContentLoss", "ResidualDenseBlock", "ResidualResidualDenseBlock"]
+__all__ = ["EMA", "Generator", "SRVGGNetCompact", "Discriminator", "ContentLoss", "ResidualDenseBlock", "ResidualResidualDenseBlock",
+           "load_official_state_dict"]

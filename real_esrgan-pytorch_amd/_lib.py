@@ -78,6 +78,14 @@ class GeneratorDesc(C.Structure):
                 ("x2_plan", C.c_int32), ("reserved_", C.c_int32)]
 
 
+COMPACT_PRELU, COMPACT_LRELU, COMPACT_RELU = 0, 1, 2   # ResrCompactDesc.act
+
+
+class CompactDesc(C.Structure):
+    _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("num_conv", C.c_int32), ("upscale", C.c_int32),
+                ("act", C.c_int32), ("dtype", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class DiscriminatorDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("dtype", C.c_int32), ("training", C.c_int32),
                 ("sn_training", C.c_int32)]
@@ -117,6 +125,11 @@ _PROTOS = {
     "resr_generator_buffer_offsets": (C.c_int64, [C.POINTER(GeneratorDesc), _P, C.c_int64]),
     "resr_generator_forward": (C.c_int, [C.POINTER(GeneratorDesc), _P, _P, _P, _P, C.c_size_t, _P, _P]),
     "resr_generator_backward": (C.c_int, [C.POINTER(GeneratorDesc), _P, _P, _P, _P, C.c_size_t, _P, _P, _P, _P, C.c_int32]),
+    "resr_compact_param_count": (C.c_size_t, [C.POINTER(CompactDesc)]),
+    "resr_compact_packed_bytes": (C.c_size_t, [C.POINTER(CompactDesc)]),
+    "resr_compact_workspace_bytes": (C.c_size_t, [C.POINTER(CompactDesc)]),
+    "resr_compact_pack_table": (C.c_int64, [C.POINTER(CompactDesc), _P, C.c_int64]),
+    "resr_compact_forward": (C.c_int, [C.POINTER(CompactDesc), _P, _P, _P, _P, C.c_size_t, _P, _P]),
     "resr_ema_update": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P]),
     "resr_debug_tr_probe": (C.c_int, [_P, _P]),
     "resr_debug_conv_trace": (C.c_int, [_P]),

@@ -1,0 +1,181 @@
+"""The compact generator of upstream Real-ESRGAN (`SRVGGNetCompact`: the realesr-animevideov3 and realesr-general-x4v3
+models) on the MI355X conv kernels, forward only.
+
+Same constructor, module tree and state_dict keys as upstream (`body` = ModuleList of conv / activation, `upsampler` =
+PixelShuffle), so an official `.pth` loads with a plain `load_state_dict` (or `model.load_official_state_dict`).  `forward` is
+one C-ABI call, `resr_compact_forward` (include/resr.h, csrc/compact.hip): conv 3->64 + act, num_conv x (conv 64->64 + act),
+conv 64->3*s*s, pixel-shuffle, + the nearest-upsampled input.  There is no PyTorch / CPU fallback and no backward pass.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from typing import Dict, List, Optional
+
+import torch
+from torch import nn
+
+from . import _lib
+from .model import _precision_to_dtype
+
+__all__ = ["SRVGGNetCompact"]
+
+_ACTS = {"prelu": _lib.COMPACT_PRELU, "leakyrelu": _lib.COMPACT_LRELU, "relu": _lib.COMPACT_RELU}
+
+
+class SRVGGNetCompact(nn.Module):
+    """SRVGGNetCompact(num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type="prelu") as upstream.
+
+    Keyword `precision`: "fast" (f16 MFMA), "exact16" (split-operand f16 pairs, three stages per chunk, fp32-class results) or
+    "strict" (f32 MFMA); default $RESR_PRECISION, else "fast" -- the rule of `Generator`.
+    forward(x [N,3,H,W] float, NCHW or channels_last, any H, W >= 1) -> [N,3,sH,sW] fp32 NCHW, not clamped.  Forward only:
+    a call with grad enabled and an input or parameter that requires grad raises (wrap inference in torch.no_grad()).
+    """
+
+    def __init__(self, num_in_ch: int = 3, num_out_ch: int = 3, num_feat: int = 64, num_conv: int = 16, upscale: int = 4,
+                 act_type: str = "prelu", precision: Optional[str] = None) -> None:
+        super().__init__()
+        if num_in_ch != 3 or num_out_ch != 3:
+            raise ValueError(f"SRVGGNetCompact: num_in_ch = num_out_ch = 3 on this path, got {num_in_ch}, {num_out_ch}")
+        if num_feat != 64:
+            raise ValueError(f"SRVGGNetCompact: num_feat must be 64 (the conv kernels' channel tiles), got {num_feat}")
+        if isinstance(num_conv, bool) or not isinstance(num_conv, int) or not 0 <= num_conv <= 4096:
+            raise ValueError(f"SRVGGNetCompact: num_conv must be an int in [0, 4096], got {num_conv!r}")
+        if isinstance(upscale, bool) or upscale not in (1, 2, 3, 4):
+            raise ValueError(f"SRVGGNetCompact: upscale must be 1, 2, 3 or 4, got {upscale!r}")
+        if act_type not in _ACTS:
+            raise ValueError(f"SRVGGNetCompact: act_type must be 'prelu', 'leakyrelu' or 'relu', got {act_type!r}")
+        self.num_in_ch, self.num_out_ch, self.num_feat = num_in_ch, num_out_ch, num_feat
+        self.num_conv, self.upscale, self.act_type = num_conv, upscale, act_type
+        self.precision = precision or os.environ.get("RESR_PRECISION", "fast")
+        self._dtype = _precision_to_dtype(self.precision)
+
+        # upstream's module tree (same construction order, hence the same init under the same seed)
+        self.body = nn.ModuleList()
+        self.body.append(nn.Conv2d(num_in_ch, num_feat, 3, 1, 1))
+        self.body.append(self._activation(num_feat))
+        for _ in range(num_conv):
+            self.body.append(nn.Conv2d(num_feat, num_feat, 3, 1, 1))
+            self.body.append(self._activation(num_feat))
+        self.body.append(nn.Conv2d(num_feat, num_out_ch * upscale * upscale, 3, 1, 1))
+        self.upsampler = nn.PixelShuffle(upscale)
+
+        self._flat: Optional[torch.Tensor] = None
+        self._packed: Optional[torch.Tensor] = None
+        self._table_dev: Optional[tuple] = None
+        self._workspaces: Dict[tuple, torch.Tensor] = {}
+
+    def _activation(self, num_feat: int) -> nn.Module:
+        if self.act_type == "prelu":
+            return nn.PReLU(num_parameters=num_feat)
+        if self.act_type == "leakyrelu":
+            return nn.LeakyReLU(negative_slope=0.1, inplace=True)
+        return nn.ReLU(inplace=True)
+
+    # ---- what the tiler needs (tiling.py; Generator defines the same) ----------------------------------------------------
+    @property
+    def upscale_factor(self) -> int:
+        return self.upscale
+
+    @property
+    def out_channels(self) -> int:
+        return self.num_out_ch
+
+    pixel_unshuffle_factor = 1   # every conv runs at the input's resolution
+    conv_scale = 1               # ... so the largest conv tensor is LR-sized (the tail's shuffle + residual is 64-bit indexed)
+
+    @property
+    def receptive_radius(self) -> int:
+        """LR pixels a window needs around a tile for the tiled output to equal whole-frame output: one per conv."""
+        return self.num_conv + 2
+
+    # ---- flat arena (as Generator: parameters are views of one fp32 buffer in named_parameters order) -------------------
+    def _ordered_params(self) -> List[nn.Parameter]:
+        return [p for _, p in self.named_parameters()]
+
+    def _arena_ok(self) -> bool:
+        if self._flat is None:
+            return False
+        base, off = self._flat.data_ptr(), 0
+        for p in self._ordered_params():
+            if p.data_ptr() != base + off * 4 or p.dtype != torch.float32:
+                return False
+            off += p.numel()
+        return off == self._flat.numel()
+
+    def flat_parameters(self) -> torch.Tensor:
+        """The fp32 arena all parameters are views of (named_parameters order = resr_compact_forward's layout)."""
+        if not self._arena_ok():
+            params = self._ordered_params()
+            flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=params[0].device)
+            off = 0
+            for p in params:
+                n = p.numel()
+                flat[off:off + n].copy_(p.data.reshape(-1).float())
+                p.data = flat[off:off + n].view(p.shape)
+                off += n
+            self._flat = flat
+            self._packed = None
+            self._table_dev = None
+            self._workspaces.clear()
+        return self._flat
+
+    # ---- C-ABI plumbing ---------------------------------------------------------------------------------------------------
+    def _desc(self, n: int, h: int, w: int) -> _lib.CompactDesc:
+        return _lib.CompactDesc(n, h, w, self.num_conv, self.upscale, _ACTS[self.act_type], self._dtype, 0)
+
+    def _pack(self, desc: _lib.CompactDesc, flat: torch.Tensor) -> None:
+        """One resr_pack_weights launch per forward: a load_state_dict or an in-place edit is always seen (graph replays too)."""
+        L = _lib.lib()
+        if self._table_dev is None or self._table_dev[0].device != flat.device:
+            n = L.resr_compact_pack_table(C.byref(desc), None, 0)
+            if n <= 0:
+                _lib.check(int(n) if n < 0 else -1, "resr_compact_pack_table")
+            host = (_lib.PackChunk * n)()
+            assert L.resr_compact_pack_table(C.byref(desc), C.cast(host, C.c_void_p), n) == n
+            self._table_dev = (torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(flat.device), int(n))
+        nbytes = L.resr_compact_packed_bytes(C.byref(desc))
+        if self._packed is None or self._packed.numel() < nbytes or self._packed.device != flat.device:
+            self._packed = torch.zeros(nbytes, dtype=torch.uint8, device=flat.device)
+        raw, n = self._table_dev
+        _lib.check(L.resr_pack_weights(_lib.ptr(raw), n, _lib.ptr(flat), _lib.ptr(self._packed), self._dtype,
+                                       _lib.stream_ptr(flat)), "resr_pack_weights")
+
+    def _workspace(self, desc: _lib.CompactDesc, device) -> torch.Tensor:
+        key = (desc.n, desc.h, desc.w, desc.dtype, str(device))
+        ws = self._workspaces.get(key)
+        if ws is None:
+            nbytes = _lib.lib().resr_compact_workspace_bytes(C.byref(desc))
+            if nbytes == 0:
+                raise RuntimeError(f"resr_compact_workspace_bytes: unsupported shape {desc.n}x{desc.h}x{desc.w} for precision "
+                                   f"{self.precision!r} (exact16 takes at most 2^24 pixels per call: use tiling.TiledGenerator)")
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            self._workspaces[key] = ws
+        return ws
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        params = self._ordered_params()
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            raise RuntimeError("SRVGGNetCompact: the compact generator's backward pass is not implemented on the MI355X path; "
+                               "run inference under torch.no_grad() (or with requires_grad_(False) parameters)")
+        _lib.require_cuda(x, "SRVGGNetCompact.forward")
+        if x.dim() != 4 or x.shape[1] != self.num_in_ch:
+            raise RuntimeError(f"SRVGGNetCompact: expected an [N,{self.num_in_ch},H,W] input, got {tuple(x.shape)}")
+        flat = self.flat_parameters()
+        _lib.require_cuda(flat, "SRVGGNetCompact parameters")
+        xc = x.detach().float().contiguous()   # also normalises channels_last strides
+        n, _, h, w = xc.shape
+        desc = self._desc(n, h, w)
+        self._pack(desc, flat)
+        ws = self._workspace(desc, xc.device)
+        s = self.upscale
+        y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=xc.device)
+        _lib.check(_lib.lib().resr_compact_forward(C.byref(desc), _lib.ptr(xc), _lib.ptr(flat), _lib.ptr(self._packed),
+                                                   _lib.ptr(ws), ws.numel(), _lib.ptr(y), _lib.stream_ptr(xc)),
+                   "resr_compact_forward")
+        return y
+
+    def load_official_state_dict(self, checkpoint) -> None:
+        """Upstream's `{"params_ema": sd}` / `{"params": sd}` (params_ema preferred) or a bare state dict (model.load_official_state_dict)."""
+        from .model import load_official_state_dict
+        load_official_state_dict(self, checkpoint)

@@ -97,6 +97,12 @@ int generator_forward(const ResrGeneratorDesc*, const float*, const float*, cons
 int generator_backward(const ResrGeneratorDesc*, const float*, const float*, const void*, void*, size_t, float*, float*,
                        hipStream_t, void* const*, int);
 
+size_t compact_param_count(const ResrCompactDesc*);
+size_t compact_packed_bytes(const ResrCompactDesc*);
+size_t compact_workspace_bytes(const ResrCompactDesc*);
+int64_t compact_pack_table(const ResrCompactDesc*, ResrPackChunk*, int64_t);
+int compact_forward(const ResrCompactDesc*, const float*, const float*, const void*, void*, size_t, float*, hipStream_t);
+
 size_t discriminator_param_count();
 size_t discriminator_uv_count();
 size_t discriminator_workspace_bytes(const ResrDiscriminatorDesc*);
@@ -249,6 +255,19 @@ int resr_generator_backward(const ResrGeneratorDesc* d, const float* gy_nchw, co
     RESR_DEVICE_SCOPE(stream);
     return generator_backward(d, gy_nchw, params, packed, workspace, workspace_bytes, grad_params, gx_nchw,
                               (hipStream_t)stream, grad_ready_events, n_events);
+}
+
+size_t resr_compact_param_count(const ResrCompactDesc* d) { return compact_param_count(d); }
+size_t resr_compact_packed_bytes(const ResrCompactDesc* d) { return compact_packed_bytes(d); }
+size_t resr_compact_workspace_bytes(const ResrCompactDesc* d) { return compact_workspace_bytes(d); }
+int64_t resr_compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* chunks, int64_t capacity) {
+    return compact_pack_table(d, chunks, capacity);
+}
+
+int resr_compact_forward(const ResrCompactDesc* d, const float* x_nchw, const float* params, const void* packed,
+                         void* workspace, size_t workspace_bytes, float* y_nchw, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward(d, x_nchw, params, packed, workspace, workspace_bytes, y_nchw, (hipStream_t)stream);
 }
 
 size_t resr_discriminator_param_count(void) { return discriminator_param_count(); }

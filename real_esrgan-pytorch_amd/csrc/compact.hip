@@ -1,0 +1,220 @@
+// compact.hip -- the compact generator (upstream Real-ESRGAN's SRVGGNetCompact) as one natively enqueued forward pass:
+// the HBM plan, the launch order and the one kernel of its own (pixel-shuffle + nearest-upsampled residual).
+//
+//   x [N,3,H,W] fp32 -> x_in [N,H,W,32] (layout.hip, channels 3..31 zero)
+//   conv 3->64 + act            x_in -> A      (act: per-channel PReLU -- conv3x3_dispatch_prelu --, LeakyReLU 0.1 or ReLU)
+//   num_conv x conv 64->64 + act   A -> B -> A ...
+//   conv 64->3*s*s              -> t [N,3s^2,H,W] fp32 NCHW (the conv's fp32 epilogue: exact16 keeps its fp32-class value)
+//   y[n,c,Y,X] = t[n, c*s*s + (Y%s)*s + X%s, Y/s, X/s] + x[n,c,Y/s,X/s]      (one launch, 64-bit indexing)
+// T = f16 (fast) / f32 (strict); RESR_F16X2 (exact16): every NHWC tensor is a hi/lo pair, the lo tensor right behind the hi one,
+// three stages per chunk.  No padding beyond each conv's own pad = 1: any H, W >= 1.
+#include <vector>
+
+#include "common.h"
+
+namespace resr {
+
+int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*, const float*, const void*,
+                     const void*, const void*, void*, void*, hipStream_t);
+int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const float*, const float*, void*, hipStream_t);
+int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
+
+namespace {
+
+struct CConv {
+    int cin, cin_pad, cout, cout_pad;
+    size_t w_off, b_off;   // element offsets in the fp32 parameter arena
+    long a_off;            // PReLU slopes (-1: none)
+    size_t pk;             // element offset in the packed buffer
+};
+
+struct CPlan {
+    ResrCompactDesc d;
+    std::vector<CConv> convs;   // conv 0 (3 -> 64), num_conv body convs, the last conv (64 -> 3 s^2)
+    size_t n_params, pk_elems;
+    long px;                    // N * H * W
+    size_t off_xin, off_a, off_b, off_t, total;
+};
+
+bool build_cplan(const ResrCompactDesc* d, CPlan& p) {
+    if (!d) return false;
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->num_conv < 0 || d->num_conv > 4096 || d->upscale < 1 || d->upscale > 4 ||
+        d->act < RESR_COMPACT_PRELU || d->act > RESR_COMPACT_RELU ||
+        (d->dtype != RESR_F16 && d->dtype != RESR_F32 && d->dtype != RESR_F16X2))
+        return false;
+    p.d = *d;
+    p.px = (long)d->n * d->h * d->w;
+    // element offsets of a 64-channel NHWC tensor stay below 2^31; the pair kernels address at most 2^24 pixels per tensor
+    if (p.px > 0x7fffffffL / 64 || (d->dtype == RESR_F16X2 && p.px > (1L << 24))) return false;
+    const int s = d->upscale;
+    size_t off = 0;
+    auto add = [&](int cin, int cout, bool act) {
+        CConv c;
+        c.cin = cin; c.cin_pad = (cin + 31) / 32 * 32; c.cout = cout; c.cout_pad = (cout + 31) / 32 * 32;
+        c.w_off = off; off += (size_t)cout * cin * 9;
+        c.b_off = off; off += cout;
+        c.a_off = -1;
+        if (act && d->act == RESR_COMPACT_PRELU) { c.a_off = (long)off; off += cout; }
+        c.pk = 0;
+        p.convs.push_back(c);
+    };
+    add(3, 64, true);
+    for (int i = 0; i < d->num_conv; ++i) add(64, 64, true);
+    add(64, 3 * s * s, false);
+    p.n_params = off;
+    size_t pk = 0;
+    for (auto& c : p.convs) {
+        c.pk = pk;
+        pk += (size_t)(c.cin_pad / 32) * 9 * (c.cout_pad / 32) * 1024;
+    }
+    p.pk_elems = pk;
+    const size_t es = elem_size(d->dtype) * act_tensors(d->dtype);
+    size_t ws = 0;
+    auto carve = [&](size_t bytes) { const size_t o = ws; ws = align_up(ws + bytes, 256); return o; };
+    p.off_xin = carve((size_t)p.px * 32 * es);
+    p.off_a = carve((size_t)p.px * 64 * es);
+    p.off_b = carve((size_t)p.px * 64 * es);
+    p.off_t = carve((size_t)p.px * 3 * s * s * 4);
+    p.total = ws;
+    return true;
+}
+
+// y [n,3,hS,wS] = pixel_shuffle(t [n,3S^2,h,w], S) + nearest_upsample(x [n,3,h,w], S): one output row per (grid-strided) y block,
+// columns across x blocks; every index that can pass 2^31 is 64-bit
+template <int S>
+__global__ __launch_bounds__(256) void compact_tail_kernel(const float* __restrict__ t, const float* __restrict__ x,
+                                                           float* __restrict__ y, int n, int h, int w) {
+    const int HS = h * S, WS = w * S;
+    const long rows = (long)n * 3 * HS;
+    const long plane = (long)h * w;
+    for (long row = blockIdx.y; row < rows; row += gridDim.y) {
+        const int Y = (int)(row % HS);
+        const long bc = row / HS;              // n * 3 + c
+        const long b = bc / 3;
+        const int c = (int)(bc - b * 3);
+        const int yy = Y / S, sy = Y - yy * S;
+        const float* trow = t + ((b * 3 * S * S + (long)c * S * S + sy * S) * plane) + (long)yy * w;
+        const float* xrow = x + (bc * h + yy) * (long)w;
+        float* yrow = y + row * (long)WS;
+        for (int X = blockIdx.x * 256 + threadIdx.x; X < WS; X += gridDim.x * 256) {
+            const int xx = X / S, sx = X - xx * S;
+            yrow[X] = trow[sx * plane + xx] + xrow[xx];
+        }
+    }
+}
+
+int compact_tail(const float* t, const float* x, float* y, int n, int h, int w, int s, hipStream_t st) {
+    const long rows = (long)n * 3 * h * s;
+    const dim3 grid((unsigned)((w * s + 255) / 256), (unsigned)(rows > 65535 ? 65535 : rows));
+    prof_before(st);
+    switch (s) {
+        case 1: hipLaunchKernelGGL(compact_tail_kernel<1>, grid, dim3(256), 0, st, t, x, y, n, h, w); break;
+        case 2: hipLaunchKernelGGL(compact_tail_kernel<2>, grid, dim3(256), 0, st, t, x, y, n, h, w); break;
+        case 3: hipLaunchKernelGGL(compact_tail_kernel<3>, grid, dim3(256), 0, st, t, x, y, n, h, w); break;
+        case 4: hipLaunchKernelGGL(compact_tail_kernel<4>, grid, dim3(256), 0, st, t, x, y, n, h, w); break;
+        default: return fail(RESR_ERR_ARG, "compact_tail: upscale %d", s);
+    }
+    prof_after(st, 31000 + s, 0.0, (double)n * 3 * h * w * (s * s * 8.0 + 4.0));
+    RESR_CHECK_LAUNCH("compact_tail_kernel");
+    return RESR_OK;
+}
+
+}  // namespace
+
+size_t compact_param_count(const ResrCompactDesc* d) {
+    CPlan p;
+    return build_cplan(d, p) ? p.n_params : 0;
+}
+
+size_t compact_packed_bytes(const ResrCompactDesc* d) {
+    CPlan p;
+    if (!build_cplan(d, p)) return 0;
+    // + slack: the one-role kernel prefetches two (chunk, tap) blocks past the end
+    return p.pk_elems * elem_size(d->dtype) * (d->dtype == RESR_F16X2 ? 3 : 1) + 16384;
+}
+
+size_t compact_workspace_bytes(const ResrCompactDesc* d) {
+    CPlan p;
+    return build_cplan(d, p) ? p.total : 0;
+}
+
+int64_t compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t cap) {
+    CPlan p;
+    if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "compact: bad descriptor");
+    std::vector<ResrPackChunk> t;
+    for (const auto& c : p.convs) {
+        const int mt = c.cout_pad / 32;
+        for (int ck = 0; ck < c.cin_pad / 32; ++ck) {
+            ResrPackChunk ch;
+            memset(&ch, 0, sizeof(ch));
+            const int kc = c.cin - ck * 32;
+            ch.src_off = (int64_t)c.w_off; ch.dst_off = (int64_t)(c.pk + (size_t)ck * 9 * mt * 1024);
+            ch.src_cout = c.cout; ch.src_cin = c.cin;
+            ch.m_off = 0; ch.m_count = c.cout; ch.k_off = ck * 32; ch.k_count = kc > 32 ? 32 : kc;
+            ch.mt = mt; ch.transposed = 0; ch.scale = 1.f;
+            t.push_back(ch);
+        }
+    }
+    if (out) {
+        if ((int64_t)t.size() > cap) return fail(RESR_ERR_ARG, "compact_pack_table: capacity %lld < %zu", (long long)cap, t.size());
+        memcpy(out, t.data(), t.size() * sizeof(ResrPackChunk));
+    }
+    return (int64_t)t.size();
+}
+
+int compact_forward(const ResrCompactDesc* d, const float* x, const float* params, const void* packed, void* workspace,
+                    size_t workspace_bytes, float* y, hipStream_t st) {
+    CPlan p;
+    if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "compact_forward: bad descriptor");
+    if (!x || !params || !packed || !workspace || !y) return fail(RESR_ERR_ARG, "compact_forward: null argument");
+    if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "compact_forward: workspace %zu < %zu", workspace_bytes, p.total);
+    const bool x2 = d->dtype == RESR_F16X2;
+    const size_t wes = elem_size(d->dtype) * (x2 ? 3 : 1);   // bytes per element of the packed layout
+    const char* pk = (const char*)packed;
+    char* base = (char*)workspace;
+    char* xin = base + p.off_xin;
+    char* buf[2] = {base + p.off_a, base + p.off_b};
+    float* t = reinterpret_cast<float*>(base + p.off_t);
+    const int N = d->n, H = d->h, W = d->w;
+    const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
+    int rc = nchw_to_nhwc_dispatch(x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
+    if (rc) return rc;
+    auto desc = [&](const CConv& c, int flags) {
+        ResrConvDesc cd;
+        memset(&cd, 0, sizeof(cd));
+        cd.n = N; cd.h = H; cd.w = W;
+        cd.cin = cd.cin0 = cd.in0_stride = c.cin_pad;
+        cd.cout = c.cout; cd.cout_pad = c.cout_pad;
+        cd.out_stride = (flags & RESR_CONV_OUT_NCHW_F32) ? 0 : c.cout_pad;
+        cd.dtype = d->dtype; cd.flags = flags;
+        cd.s0 = cd.s1 = cd.t0 = cd.t1 = 1.f;
+        cd.slope = d->act == RESR_COMPACT_LRELU ? 0.1f : 0.f;
+        cd.in0_lo_offset = c.cin_pad == 32 ? lo32 : lo64;
+        cd.out_lo_offset = (flags & RESR_CONV_OUT_NCHW_F32) ? 0 : lo64;
+        return cd;
+    };
+    const int nbody = (int)p.convs.size() - 1;   // conv 0 + the num_conv body convs: 64 channels + activation
+    const char* in = xin;
+    for (int k = 0; k < nbody; ++k) {
+        const CConv& c = p.convs[k];
+        char* out = buf[k & 1];
+        if (d->act == RESR_COMPACT_PRELU) {
+            ResrConvDesc cd = desc(c, 0);
+            rc = conv3x3_dispatch_prelu(&cd, in, pk + c.pk * wes, params + c.b_off, params + c.a_off, out, st);
+        } else {
+            ResrConvDesc cd = desc(c, RESR_CONV_LRELU);
+            rc = conv3x3_dispatch(&cd, in, nullptr, pk + c.pk * wes, params + c.b_off, nullptr, nullptr, nullptr, out, nullptr, st);
+        }
+        if (rc) return rc;
+        in = out;
+    }
+    {   // the last conv: fp32 NCHW [N, 3 s^2, H, W]
+        const CConv& c = p.convs[nbody];
+        ResrConvDesc cd = desc(c, RESR_CONV_OUT_NCHW_F32);
+        rc = conv3x3_dispatch(&cd, in, nullptr, pk + c.pk * wes, params + c.b_off, nullptr, nullptr, nullptr, t, nullptr, st);
+        if (rc) return rc;
+    }
+    return compact_tail(t, x, y, N, H, W, d->upscale, st);
+}
+
+}  // namespace resr

@@ -50,6 +50,9 @@ struct ConvArgs {
     size_t w_group_b;
     const char* zero;  // 16 zero bytes in device memory (source of out-of-image LDS-DMA lanes)
     unsigned long long* trace;  // debug: per-workgroup s_memrealtime stamps (resr_debug_conv_trace), else null
+    // per-output-channel PReLU slopes (the compact generator, compact.hip; conv3x3_dispatch_prelu): v > 0 ? v : prelu[c] * v after
+    // the bias -- the select form, for any slope (trained slopes can be negative or above 1).  Null everywhere else.
+    const float* prelu;
 };
 
 // A chain of dependent cout-32 convolutions of one dense block in ONE persistent launch (conv3x3_ws.h, CH): job j reads

@@ -220,6 +220,11 @@ __global__ __launch_bounds__(64 * NW) void conv3x3_kernel(const ConvArgs a) {
 #pragma unroll
                     for (int r = 0; r < 4; ++r) v[r] = v[r] > 0.f ? v[r] : v[r] * a.slope;
                 }
+                if (a.prelu) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (co + r < a.cout) v[r] = v[r] > 0.f ? v[r] : a.prelu[co + r] * v[r];
+                }
                 if (f_aux_res) store4<T>(reinterpret_cast<char*>(a.aux), p * a.out_stride + (size_t)m * a.out_chunk + cq, v);
                 if (a.res0) {
                     float rr[4];
@@ -399,6 +404,20 @@ static int conv3x3_args(const ResrConvDesc* d, const void* in0, const void* in1,
         a.tap_c = d->s2d_out_channels;
     }
     return RESR_OK;
+}
+
+// One pass of the compact generator (compact.hip): bias + per-output-channel PReLU slopes (prelu, cout floats) on a plain
+// single-input convolution.  Routed like any other pass: the producer/consumer kernels (f16, f16x2) or the one-role kernel.
+int conv3x3_dispatch_prelu(const ResrConvDesc* d, const void* in0, const void* w, const float* bias, const float* prelu,
+                           void* out, hipStream_t stream) {
+    if (!prelu) return fail(RESR_ERR_ARG, "conv3x3_prelu: null slopes");
+    if ((d->flags & ~RESR_CONV_NO_BIAS) || d->cout_groups > 1 || d->s2d_in_channels > 0 || d->s2d_out_channels > 0 || d->out_q_offset != 0)
+        return fail(RESR_ERR_ARG, "conv3x3_prelu: a plain pass (bias, NHWC output) of one output group");
+    ConvArgs a;
+    const int rc = conv3x3_args(d, in0, nullptr, w, bias, nullptr, nullptr, nullptr, out, nullptr, a);
+    if (rc) return rc;
+    a.prelu = prelu;
+    return conv3x3_route(d, a, bias != nullptr, false, stream);
 }
 
 int conv3x3_dispatch(const ResrConvDesc* d, const void* in0, const void* in1, const void* w,

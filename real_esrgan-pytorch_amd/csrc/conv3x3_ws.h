@@ -357,7 +357,11 @@ __global__ __launch_bounds__(64 * (NWC + WsCfg<T, MT, NT, NWC>::NP), (NWC + WsCf
     }
     // FAST: instantiations with the lean epilogue (the generator's hot forms: plain / LeakyReLU, residuals, sign-bit
     // output, sign-bit mask); everything else keeps the general one
-    constexpr bool FAST = EPI == 0 || EPI == 2 || EPI == 6 || EPI == 16 || EPI == 33;
+    // EPI 128: EPI 0 with the per-channel PReLU slopes of ConvArgs::prelu (the compact generator's body), kept in the table's LDS slot
+    constexpr bool FAST = EPI == 0 || EPI == 2 || EPI == 6 || EPI == 16 || EPI == 33 || EPI == 128;
+    if constexpr (EPI == 128) {
+        if (wave == 1) reinterpret_cast<float*>(smem + C::LUT_OFF)[lane] = lane < a.cout ? a.prelu[lane] : 0.f;
+    }
     if constexpr (FAST && EPI == 33) {
         if (wave == 1 && lane < 16) {
             float4v m;
@@ -1269,6 +1273,16 @@ __global__ __launch_bounds__(64 * (NWC + WsCfg<T, MT, NT, NWC>::NP), (NWC + WsCf
                                 q[k][1] = vmax_f32(q[k][1], sq[1]);
                             }
                         }
+                        if constexpr (EPI == 128) {   // PReLU: v > 0 ? v : a[c] * v (any slope: no max form), slopes of couts (2j + kh) * 8 + 0..7
+                            const float* sl = reinterpret_cast<const float*>(smem + C::LUT_OFF) + m * 32 + (2 * j + kh_e) * 8;
+                            const float4v sa = *reinterpret_cast<const float4v*>(sl), sb = *reinterpret_cast<const float4v*>(sl + 4);
+                            const float s8[8] = {sa[0], sa[1], sa[2], sa[3], sb[0], sb[1], sb[2], sb[3]};
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                const float u0 = q[k][0], u1 = q[k][1];
+                                q[k] = float2v{u0 > 0.f ? u0 : s8[2 * k] * u0, u1 > 0.f ? u1 : s8[2 * k + 1] * u1};
+                            }
+                        }
                         if (r0) {
                             const float2v s02 = {e.s0, e.s0};
 #pragma unroll
@@ -1638,7 +1652,7 @@ static int launch_ws_epi(const ConvArgs& a, hipStream_t stream) {
     args.tiles_y = (a.h + C::TH - 1) / C::TH;
     // halo buffers, bias, weight buffers (+ the mask-multiplier table; + the biases of the output groups of a grouped launch)
     const bool gbias = MT == 2 && a.ngroups > 1 && !(a.flags & RESR_CONV_NO_BIAS) && a.bias != nullptr;
-    const size_t lds = C::LDS_BYTES + ((EPI == 33 || gbias) ? C::LUT_BYTES : 0) + (gbias ? C::GB_BYTES : 0);
+    const size_t lds = C::LDS_BYTES + ((EPI == 33 || EPI == 128 || gbias) ? C::LUT_BYTES : 0) + (gbias ? C::GB_BYTES : 0);
     // per device (the boundary is callable with any current device): workgroups the device holds at once and the
     // address of this translation unit's zero page there; idempotent, so a race between two first calls is benign
     static int resident_dev[kMaxDevices] = {0};
@@ -1680,6 +1694,15 @@ static int launch_ws_epi(const ConvArgs& a, hipStream_t stream) {
 
 template <typename T, int MT, int NT, int NWC, int X2 = 0>
 static int launch_ws(const ConvArgs& a, hipStream_t stream) {
+    if (a.prelu) {   // per-channel PReLU (conv3x3_dispatch_prelu: a plain single-input pass of one output group)
+        if constexpr (X2 == 2) return fail(RESR_ERR_ARG, "conv3x3: PReLU slopes with MX stages");
+        else {
+        // (the lean epilogue only: the general one -- NCHW fp32 output, aux tensors -- has no PReLU form)
+        if (a.ngroups > 1 || a.in1 || a.mask || a.res0 || a.res1 || a.aux || a.out_q || (a.flags & ~(RESR_CONV_NO_BIAS | RESR_CONV_UPSAMPLE_IN)))
+            return fail(RESR_ERR_ARG, "conv3x3: PReLU slopes go with a plain NHWC pass (no MX stages, groups, residuals, masks, aux tensors or NCHW output)");
+        return launch_ws_epi<T, MT, NT, NWC, 128, X2>(a, stream);
+        }
+    }
     if constexpr (X2 == 2) {   // MX stages (RESR_CONV_MX_PAIRS): the lean epilogues -- bias / LeakyReLU / residuals, the sign words of a training
                                // forward (RESR_CONV_MX_SIGNBITS, checked with the descriptor), or the sign-word mask of a backward-data pass
         if ((a.flags & RESR_CONV_MASK_BITS) && !a.aux && !a.res0 && !a.res1 && !(a.flags & ~(RESR_CONV_MASK | RESR_CONV_MASK_BITS | RESR_CONV_NO_BIAS)))

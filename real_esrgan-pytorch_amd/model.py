@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 from typing import Dict, List, Optional
 
 import torch
@@ -20,7 +21,7 @@ from torch import nn
 
 from . import _lib
 
-__all__ = ["EMA", "ResidualDenseBlock", "ResidualResidualDenseBlock", "Generator"]
+__all__ = ["EMA", "ResidualDenseBlock", "ResidualResidualDenseBlock", "Generator", "load_official_state_dict"]
 
 
 def _precision_to_dtype(precision: str) -> int:
@@ -311,6 +312,23 @@ class Generator(nn.Module):
         self._live_graphs = 0   # training-mode forwards whose backward has not run yet
         self.__dict__["_flat_param"] = None   # see flat_parameter(); kept out of nn.Module's parameter registry
 
+    # ---- what the tiler needs (tiling.py; SRVGGNetCompact defines the same) ---------------------------------------------
+    @property
+    def pixel_unshuffle_factor(self) -> int:
+        """model.py:257: the trunk runs at 1/r of the input's resolution (windows stay multiples of r)."""
+        return {4: 1, 2: 2, 1: 4}[self.upscale_factor]
+
+    @property
+    def conv_scale(self) -> int:
+        """Resolution of the largest conv tensor relative to the input: the tail (conv3, conv4) runs at the output's."""
+        return self.upscale_factor
+
+    @property
+    def receptive_radius(self) -> int:
+        """Upper bound of the receptive-field radius in input pixels: conv1, 15 convs per RRDB, conv2 and the tail's four convs
+        (at 2x / 4x the trunk's resolution), times the pixel-unshuffle factor (~350 for the 23-block trunk)."""
+        return self.pixel_unshuffle_factor * (15 * self.n_blocks + 4)
+
     # ---- flat arena ---------------------------------------------------------------------------
     def _ordered_params(self) -> List[nn.Parameter]:
         return [p for _, p in self.named_parameters()]
@@ -526,6 +544,46 @@ class Generator(nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self._forward_impl(x)
+
+
+# upstream Real-ESRGAN's RRDBNet parameter names -> this module's (the reference's), anchored at the start of the key
+_RRDB_NAMES = [(re.compile(r"^conv_first\."), "conv1."), (re.compile(r"^body\.(\d+)\.(rdb[123])\.(conv[1-5])\."), r"trunk.\1.\2.\3."),
+               (re.compile(r"^conv_body\."), "conv2."), (re.compile(r"^conv_up1\."), "upsampling1.0."),
+               (re.compile(r"^conv_up2\."), "upsampling2.0."), (re.compile(r"^conv_hr\."), "conv3.0."),
+               (re.compile(r"^conv_last\."), "conv4.")]
+
+
+def _rrdb_name(key: str) -> Optional[str]:
+    for pat, rep in _RRDB_NAMES:
+        new, n = pat.subn(rep, key, count=1)
+        if n:
+            return new
+    return None
+
+
+def load_official_state_dict(module: nn.Module, checkpoint) -> None:
+    """Load an upstream Real-ESRGAN checkpoint: `{"params_ema": sd}` or `{"params": sd}` (params_ema preferred) or a bare state
+    dict.  `Generator` takes upstream RRDBNet names (RealESRGAN_x4plus, RealESRNet_x4plus, RealESRGAN_x2plus; the 6-block anime
+    model with `Generator(..., n_blocks=6)`), mapped onto the reference's: conv_first -> conv1, body.i.rdbj.convk ->
+    trunk.i.rdbj.convk, conv_body -> conv2, conv_up1 -> upsampling1.0, conv_up2 -> upsampling2.0, conv_hr -> conv3.0,
+    conv_last -> conv4.  `SRVGGNetCompact` keys pass through unchanged.  Unknown or missing keys raise RuntimeError naming them."""
+    sd = checkpoint
+    if isinstance(checkpoint, dict) and ("params_ema" in checkpoint or "params" in checkpoint):
+        sd = checkpoint["params_ema"] if "params_ema" in checkpoint else checkpoint["params"]
+    if not isinstance(sd, dict):
+        raise RuntimeError(f"load_official_state_dict: expected a state dict, got {type(sd).__name__}")
+    expected = set(module.state_dict().keys())
+    renamed, unknown = {}, []
+    for k, v in sd.items():
+        new = _rrdb_name(k) if isinstance(module, Generator) else k
+        if new is None or new not in expected:
+            unknown.append(k)
+        else:
+            renamed[new] = v
+    missing = sorted(expected - set(renamed))
+    if unknown or missing:
+        raise RuntimeError(f"load_official_state_dict ({type(module).__name__}): unknown keys {sorted(unknown)}, missing keys {missing}")
+    module.load_state_dict(renamed, strict=True)
 
 
 class EMA(nn.Module):

@@ -30,6 +30,11 @@ import torch
 
 from .model import Generator
 
+# The tiler runs a `Generator` or an `SRVGGNetCompact` (compact.py); it reads from the model: upscale_factor, out_channels,
+# pixel_unshuffle_factor (windows stay multiples of it), conv_scale (resolution of the largest conv tensor relative to the
+# input: the per-tensor pixel limit applies there) and receptive_radius (the halo that makes tiled output equal whole-frame
+# output), plus flat_parameters() / _packed / _workspaces for the graph's lifetime.
+
 _MAX_OUT_PIXELS = 1 << 24        # conv3x3_ws.hip: per-tensor pixel limit of the 32-bit lane offsets
 # Halo (LR pixels) of the tiles `super_resolve` cuts when a frame exceeds that limit.  The 23-block trunk's receptive field is
 # ~350 LR pixels, but what a far pixel contributes decays fast (every dense block and every RRDB adds its branch times 0.2):
@@ -42,8 +47,7 @@ def fits_whole(model: Generator, n: int, H: int, W: int) -> bool:
     """Can `model` take an [n, c, H, W] batch as ONE launch sequence?  The producer/consumer conv kernels address a tensor with
     24 x 24-bit offsets: at most 2^24 pixels per tensor, i.e. of the HR-resolution tail (csrc/conv3x3_ws.hip,
     conv3x3_ws_supported; csrc/generator.hip additionally wants n * h * w * 512 < 2^31 elements per plane stack)."""
-    s = model.upscale_factor
-    r = {4: 1, 2: 2, 1: 4}[s]
+    s, r = model.conv_scale, model.pixel_unshuffle_factor
     return n * H * s * W * s <= _MAX_OUT_PIXELS and n * (H // r) * (W // r) * 512 <= 0x7fffffff
 
 
@@ -74,8 +78,8 @@ class TiledGenerator:
         if self.tile is not None:
             th, tw = (self.tile, self.tile) if isinstance(self.tile, int) else self.tile
             return max(1, math.ceil(H / th)), max(1, math.ceil(W / tw))
-        s = self.model.upscale_factor
-        r = {4: 1, 2: 2, 1: 4}[s]                       # windows are rounded up to the pixel-unshuffle factor (plan()): price them that way
+        s = self.model.conv_scale
+        r = self.model.pixel_unshuffle_factor           # windows are rounded up to the pixel-unshuffle factor (plan()): price them that way
         halo = math.ceil(self.halo / r) * r
         best = None
         for ny in range(1, 65):
@@ -93,7 +97,7 @@ class TiledGenerator:
 
     def plan(self, n: int, H: int, W: int):
         """[(y0, y1, x0, x1, wy, wx)] tile bounds and window origins, plus the common window size."""
-        r = {4: 1, 2: 2, 1: 4}[self.model.upscale_factor]          # pixel-unshuffle factor: windows stay multiples of it
+        r = self.model.pixel_unshuffle_factor                     # windows stay multiples of it
         ny, nx = self._grid(n, H, W)
         th, tw = math.ceil(H / ny), math.ceil(W / nx)
         th, tw = math.ceil(th / r) * r, math.ceil(tw / r) * r
