@@ -394,6 +394,26 @@ size_t resr_compact_workspace_bytes(const ResrCompactDesc* d);
 int resr_compact_forward(const ResrCompactDesc* d, const float* x_nchw, const float* params, const void* packed,
                          void* workspace, size_t workspace_bytes, float* y_nchw, void* stream);
 
+/* The uint8 frame path (real_esrgan-pytorch_amd/csrc/frames.hip).  Images are uint8 HWC, contiguous: x_u8 [N,H,W,3] ->
+ * y_u8 [N,sH,sW,3].  The result is defined as what the float path followed by the host's truncating uint8 conversion gives,
+ * bit for bit: every input channel enters as (float)u8 / 255.0f (one IEEE division), converted to the model's arithmetic
+ * exactly as resr_nchw_to_nhwc converts that float; every output channel leaves as v * 255.0f, clamped to [0, 255], truncated,
+ * where v is the fp32 value the float path would have stored (for the compact net: t + x, one add).  A NaN in v is outside
+ * the contract (the host's float -> uint8 cast of a NaN is undefined too).  y_u8 / dst_u8 must be 4-byte aligned (the kernels
+ * store dwords); a misaligned pointer is RESR_ERR_ARG.
+ *
+ * resr_compact_forward_u8: the launch sequence of resr_compact_forward with the conversions fused into its first and last
+ * kernel.  Same descriptor, packed weights and workspace (resr_compact_workspace_bytes: this path needs nothing more), same
+ * checks and error codes, all before the first launch.  No fp32 copy of the frame exists on this path: the tail re-reads x_u8
+ * for the residual, so x_u8 must stay valid until the call has run. */
+int resr_compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
+                            void* workspace, size_t workspace_bytes, uint8_t* y_u8, void* stream);
+/* The generic conversions, one launch each, for models whose first / last kernel is not fused (the RRDB generator, tiled
+ * frames): u8 [N,H,W,3] -> fp32 [N,3,H,W] (/ 255.0f) and fp32 [N,3,H,W] -> u8 [N,H,W,3] (* 255.0f, clamp, truncate).
+ * n, h, w <= 0 or a null pointer: RESR_ERR_ARG, before any launch. */
+int resr_u8_to_nchw(const uint8_t* src_u8, float* dst_f32, int32_t n, int32_t h, int32_t w, void* stream);
+int resr_nchw_to_u8(const float* src_f32, uint8_t* dst_u8, int32_t n, int32_t h, int32_t w, void* stream);
+
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */
 

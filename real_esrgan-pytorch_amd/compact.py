@@ -5,6 +5,11 @@ Same constructor, module tree and state_dict keys as upstream (`body` = ModuleLi
 PixelShuffle), so an official `.pth` loads with a plain `load_state_dict` (or `model.load_official_state_dict`).  `forward` is
 one C-ABI call, `resr_compact_forward` (include/resr.h, csrc/compact.hip): conv 3->64 + act, num_conv x (conv 64->64 + act),
 conv 64->3*s*s, pixel-shuffle, + the nearest-upsampled input.  There is no PyTorch / CPU fallback and no backward pass.
+
+`forward_u8` is the same launch sequence for uint8 HWC frames (`resr_compact_forward_u8`, csrc/frames.hip): the `/ 255` of the
+way in is fused into the first kernel and the `* 255`, clamp and truncation of `imgproc.tensor_to_image` into the last, so its
+result equals `tensor_to_image(forward(float frame))` bit for bit and a quarter of the output bytes leave the device.  It is
+forward only as well (frames.py builds the pipelined host-to-host stream on it).
 """
 from __future__ import annotations
 
@@ -173,6 +178,32 @@ class SRVGGNetCompact(nn.Module):
         _lib.check(_lib.lib().resr_compact_forward(C.byref(desc), _lib.ptr(xc), _lib.ptr(flat), _lib.ptr(self._packed),
                                                    _lib.ptr(ws), ws.numel(), _lib.ptr(y), _lib.stream_ptr(xc)),
                    "resr_compact_forward")
+        return y
+
+    def forward_u8(self, frames: torch.Tensor) -> torch.Tensor:
+        """frames uint8 [N,H,W,3] on the model's device, contiguous -> uint8 [N,H*s,W*s,3]: bit for bit
+        `imgproc.tensor_to_image(self(frames / 255 as NCHW fp32))` per image (a NaN inside the net is outside that contract).
+        Same guard (a call with grad enabled and parameters that require grad raises), packing and workspace caches as `forward`."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self._ordered_params()):
+            raise RuntimeError("SRVGGNetCompact: the compact generator's backward pass is not implemented on the MI355X path; "
+                               "run inference under torch.no_grad() (or with requires_grad_(False) parameters)")
+        _lib.require_cuda(frames, "SRVGGNetCompact.forward_u8")
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != self.num_in_ch:
+            raise RuntimeError(f"SRVGGNetCompact.forward_u8: expected a uint8 [N,H,W,{self.num_in_ch}] tensor, got "
+                               f"{frames.dtype} {tuple(frames.shape)}")
+        if not frames.is_contiguous():
+            raise RuntimeError("SRVGGNetCompact.forward_u8: frames must be contiguous (HWC bytes, as an image decoder leaves them)")
+        flat = self.flat_parameters()
+        _lib.require_cuda(flat, "SRVGGNetCompact parameters")
+        n, h, w, _ = frames.shape
+        desc = self._desc(n, h, w)
+        self._pack(desc, flat)
+        ws = self._workspace(desc, frames.device)
+        s = self.upscale
+        y = torch.empty((n, h * s, w * s, self.num_out_ch), dtype=torch.uint8, device=frames.device)
+        _lib.check(_lib.lib().resr_compact_forward_u8(C.byref(desc), _lib.ptr(frames), _lib.ptr(flat), _lib.ptr(self._packed),
+                                                      _lib.ptr(ws), ws.numel(), _lib.ptr(y), _lib.stream_ptr(frames)),
+                   "resr_compact_forward_u8")
         return y
 
     def load_official_state_dict(self, checkpoint) -> None:

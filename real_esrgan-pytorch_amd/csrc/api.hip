@@ -102,6 +102,9 @@ size_t compact_packed_bytes(const ResrCompactDesc*);
 size_t compact_workspace_bytes(const ResrCompactDesc*);
 int64_t compact_pack_table(const ResrCompactDesc*, ResrPackChunk*, int64_t);
 int compact_forward(const ResrCompactDesc*, const float*, const float*, const void*, void*, size_t, float*, hipStream_t);
+int compact_forward_u8(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, hipStream_t);
+int u8_to_nchw_dispatch(const uint8_t*, float*, int, int, int, hipStream_t);
+int nchw_to_u8_dispatch(const float*, uint8_t*, int, int, int, hipStream_t);
 
 size_t discriminator_param_count();
 size_t discriminator_uv_count();
@@ -268,6 +271,22 @@ int resr_compact_forward(const ResrCompactDesc* d, const float* x_nchw, const fl
                          void* workspace, size_t workspace_bytes, float* y_nchw, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return compact_forward(d, x_nchw, params, packed, workspace, workspace_bytes, y_nchw, (hipStream_t)stream);
+}
+
+int resr_compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
+                            void* workspace, size_t workspace_bytes, uint8_t* y_u8, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_u8(d, x_u8, params, packed, workspace, workspace_bytes, y_u8, (hipStream_t)stream);
+}
+
+int resr_u8_to_nchw(const uint8_t* src_u8, float* dst_f32, int32_t n, int32_t h, int32_t w, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return u8_to_nchw_dispatch(src_u8, dst_f32, n, h, w, (hipStream_t)stream);
+}
+
+int resr_nchw_to_u8(const float* src_f32, uint8_t* dst_u8, int32_t n, int32_t h, int32_t w, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return nchw_to_u8_dispatch(src_f32, dst_u8, n, h, w, (hipStream_t)stream);
 }
 
 size_t resr_discriminator_param_count(void) { return discriminator_param_count(); }

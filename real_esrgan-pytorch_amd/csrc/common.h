@@ -40,6 +40,13 @@ constexpr float kLoScale = 4096.f, kLoInv = 1.f / 4096.f;
 constexpr int kMaxDevices = 16;   // per-device caches (occupancy, zero pages, CU counts) are indexed by hipGetDevice()
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// RESR_F16X2 (lo_off != 0 with T = f16): every tensor of T is a (hi, lo) pair, lo at element offset lo_off; values are
+// split / recombined in fp32 (see include/resr.h).  Shared by layout.hip and frames.hip: one rounding for every way in.
+__device__ __forceinline__ void split_f16(float v, half_t& hi, half_t& lo) {
+    hi = (half_t)v;
+    lo = (half_t)((v - (float)hi) * kLoScale);
+}
+
 // Power-of-two gradient pre-scale of a backward pass (generator.hip, RESR_F16X2).  absmax_dispatch (layout.hip) leaves the bits of
 // m = max |g_y| * 2^-t; when m < 1 the pass runs on g_y * s with s = 2^-floor(log2 m) -- max |g_y * s| in [2^t, 2^(t+1)): f16's
 // normal range however small the caller's loss scale is -- and every result leaves through * 1/s.  Both factors are exact.  Gradients

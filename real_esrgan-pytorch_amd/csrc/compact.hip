@@ -8,6 +8,8 @@
 //   y[n,c,Y,X] = t[n, c*s*s + (Y%s)*s + X%s, Y/s, X/s] + x[n,c,Y/s,X/s]      (one launch, 64-bit indexing)
 // T = f16 (fast) / f32 (strict); RESR_F16X2 (exact16): every NHWC tensor is a hi/lo pair, the lo tensor right behind the hi one,
 // three stages per chunk.  No padding beyond each conv's own pad = 1: any H, W >= 1.
+// compact_forward_u8 is the same sequence for uint8 HWC frames: frames.hip's u8 head in place of the layout kernel, its u8 tail
+// (pixel-shuffle + residual + * 255, clamp, truncate) in place of compact_tail_kernel; same plan, same workspace.
 #include <vector>
 
 #include "common.h"
@@ -18,6 +20,8 @@ int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*,
                      const void*, const void*, void*, void*, hipStream_t);
 int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const float*, const float*, void*, hipStream_t);
 int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
+int u8_head_dispatch(const uint8_t*, void*, int, int, int, int, hipStream_t, long);                      // frames.hip
+int compact_tail_u8(const float*, const uint8_t*, uint8_t*, int, int, int, int, hipStream_t);
 
 namespace {
 
@@ -162,12 +166,19 @@ int64_t compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t
     return (int64_t)t.size();
 }
 
-int compact_forward(const ResrCompactDesc* d, const float* x, const float* params, const void* packed, void* workspace,
-                    size_t workspace_bytes, float* y, hipStream_t st) {
+namespace {
+
+// The launch sequence both entries share.  U8 = false: x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32 (layout.hip head, compact_tail);
+// U8 = true: x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8 (frames.hip: the conversions fused into the head and the tail; the convs,
+// the packed weights and the workspace plan are the same).  Every argument check comes before the first launch.
+template <bool U8>
+int compact_run(const ResrCompactDesc* d, const void* x, const float* params, const void* packed, void* workspace,
+                size_t workspace_bytes, void* y, hipStream_t st, const char* who) {
     CPlan p;
-    if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "compact_forward: bad descriptor");
-    if (!x || !params || !packed || !workspace || !y) return fail(RESR_ERR_ARG, "compact_forward: null argument");
-    if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "compact_forward: workspace %zu < %zu", workspace_bytes, p.total);
+    if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "%s: bad descriptor", who);
+    if (!x || !params || !packed || !workspace || !y) return fail(RESR_ERR_ARG, "%s: null argument", who);
+    if (U8 && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
+    if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
     const bool x2 = d->dtype == RESR_F16X2;
     const size_t wes = elem_size(d->dtype) * (x2 ? 3 : 1);   // bytes per element of the packed layout
     const char* pk = (const char*)packed;
@@ -177,7 +188,8 @@ int compact_forward(const ResrCompactDesc* d, const float* x, const float* param
     float* t = reinterpret_cast<float*>(base + p.off_t);
     const int N = d->n, H = d->h, W = d->w;
     const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
-    int rc = nchw_to_nhwc_dispatch(x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
+    int rc = U8 ? u8_head_dispatch((const uint8_t*)x, xin, N, H, W, d->dtype, st, (long)lo32)
+                : nchw_to_nhwc_dispatch((const float*)x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) {
         ResrConvDesc cd;
@@ -214,7 +226,20 @@ int compact_forward(const ResrCompactDesc* d, const float* x, const float* param
         rc = conv3x3_dispatch(&cd, in, nullptr, pk + c.pk * wes, params + c.b_off, nullptr, nullptr, nullptr, t, nullptr, st);
         if (rc) return rc;
     }
-    return compact_tail(t, x, y, N, H, W, d->upscale, st);
+    if (U8) return compact_tail_u8(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, st);
+    return compact_tail(t, (const float*)x, (float*)y, N, H, W, d->upscale, st);
+}
+
+}  // namespace
+
+int compact_forward(const ResrCompactDesc* d, const float* x, const float* params, const void* packed, void* workspace,
+                    size_t workspace_bytes, float* y, hipStream_t st) {
+    return compact_run<false>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward");
+}
+
+int compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
+                       size_t workspace_bytes, uint8_t* y, hipStream_t st) {
+    return compact_run<true>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward_u8");
 }
 
 }  // namespace resr

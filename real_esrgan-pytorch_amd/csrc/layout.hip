@@ -14,12 +14,7 @@
 
 namespace resr {
 
-// RESR_F16X2 (lo_off != 0 with T = f16): every tensor of T is a (hi, lo) pair, lo at element offset lo_off; values are
-// split / recombined in fp32 (see include/resr.h).
-__device__ __forceinline__ void split_f16(float v, half_t& hi, half_t& lo) {
-    hi = (half_t)v;
-    lo = (half_t)((v - (float)hi) * kLoScale);
-}
+// (split_f16, the RESR_F16X2 hi/lo split, lives in common.h: frames.hip converts with it too)
 
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ src, T* __restrict__ dst,

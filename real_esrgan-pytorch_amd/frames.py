@@ -1,0 +1,205 @@
+"""The uint8 frame path: uint8 HWC images in, uint8 HWC images out (csrc/frames.hip).
+
+The result of every function here is DEFINED as what the float path followed by `imgproc.tensor_to_image` produces, bit for
+bit: a frame enters as `u8 / 255.0f`, runs through the model in the model's arithmetic, and leaves as `v * 255`, clamped to
+[0, 255] and truncated (a NaN inside the net is outside that definition, as it is for `astype(uint8)`).
+
+    from_u8(frames)            uint8 [N,H,W,3] -> fp32 [N,3,H,W]           one launch (resr_u8_to_nchw)
+    to_u8(sr)                  fp32 [N,3,H,W]  -> uint8 [N,H,W,3]          one launch (resr_nchw_to_u8)
+    upscale_u8(model, frames)  uint8 [N,H,W,3] -> uint8 [N,sH,sW,3]        any model, any frame size
+    FrameStream(model, depth)  host ndarray in -> host ndarray out, `depth` frames in flight
+
+`upscale_u8` is the one definition of the path: a model with a fused entry (`SRVGGNetCompact.forward_u8`) runs it when the frame
+fits one call; every other case (the RRDB `Generator`, frames the tiler has to cut) is `to_u8(super_resolve(model, from_u8(f)))`.
+There is no PyTorch fallback for the conversions: a missing kernel is an error of `_lib`.
+"""
+from __future__ import annotations
+
+import collections
+from typing import Deque, Iterable, Iterator, List, Optional
+
+import numpy as np
+import torch
+
+from . import _lib, tiling
+
+__all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream"]
+
+
+def _check_frames(frames: torch.Tensor, what: str) -> None:
+    _lib.require_cuda(frames, what)
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or min(frames.shape) < 1:
+        raise RuntimeError(f"{what}: expected a uint8 [N,H,W,3] tensor, got {frames.dtype} {tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise RuntimeError(f"{what}: frames must be contiguous (HWC bytes, as an image decoder leaves them)")
+
+
+@torch.no_grad()
+def from_u8(frames: torch.Tensor) -> torch.Tensor:
+    """uint8 [N,H,W,3] -> fp32 [N,3,H,W], every value `u8 / 255.0f` (numpy's `astype(float32) / 255.0`)."""
+    _check_frames(frames, "from_u8")
+    n, h, w, _ = frames.shape
+    x = torch.empty((n, 3, h, w), dtype=torch.float32, device=frames.device)
+    _lib.check(_lib.lib().resr_u8_to_nchw(_lib.ptr(frames), _lib.ptr(x), n, h, w, _lib.stream_ptr(frames)), "resr_u8_to_nchw")
+    return x
+
+
+@torch.no_grad()
+def to_u8(sr: torch.Tensor) -> torch.Tensor:
+    """fp32 [N,3,H,W] -> uint8 [N,H,W,3]: `* 255`, clamp to [0, 255], truncate -- `imgproc.tensor_to_image` per image."""
+    _lib.require_cuda(sr, "to_u8")
+    if sr.dtype != torch.float32 or sr.dim() != 4 or sr.shape[1] != 3 or min(sr.shape) < 1:
+        raise RuntimeError(f"to_u8: expected an fp32 [N,3,H,W] tensor, got {sr.dtype} {tuple(sr.shape)}")
+    if not sr.is_contiguous():
+        sr = sr.contiguous()
+    n, _, h, w = sr.shape
+    y = torch.empty((n, h, w, 3), dtype=torch.uint8, device=sr.device)
+    _lib.check(_lib.lib().resr_nchw_to_u8(_lib.ptr(sr), _lib.ptr(y), n, h, w, _lib.stream_ptr(sr)), "resr_nchw_to_u8")
+    return y
+
+
+@torch.no_grad()
+def upscale_u8(model, frames: torch.Tensor, halo: Optional[int] = None) -> torch.Tensor:
+    """uint8 [N,H,W,3] on the model's device -> uint8 [N,sH,sW,3].  `halo`: the tiler's, for frames it has to cut
+    (tiling.super_resolve; with halo >= model.receptive_radius the tiled result equals the whole-frame one)."""
+    _check_frames(frames, "upscale_u8")
+    n, h, w, _ = frames.shape
+    if hasattr(model, "forward_u8") and tiling.fits_whole(model, n, h, w):
+        return model.forward_u8(frames)
+    return to_u8(tiling.super_resolve(model, from_u8(frames), halo))
+
+
+class _Slot:
+    """One frame in flight: pinned host buffers, the device input, the events that order its three stages."""
+
+    def __init__(self, h: int, w: int, s: int, device) -> None:
+        self.pin_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
+        self.pin_out = torch.empty((1, h * s, w * s, 3), dtype=torch.uint8, pin_memory=True)
+        self.np_in, self.np_out = self.pin_in.numpy()[0], self.pin_out.numpy()[0]
+        self.dev_in = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
+        self.dev_out: Optional[torch.Tensor] = None      # held until the slot's next submit: its download has been waited for by then
+        self.uploaded, self.computed, self.downloaded = (torch.cuda.Event() for _ in range(3))
+        self.used = False
+
+
+class FrameStream:
+    """Pipelined host-to-host frames: `depth` slots, each a pinned uint8 input buffer, a pinned uint8 output buffer and their
+    device twins; an upload stream, the compute stream (the current stream at the first submit) and a download stream, ordered
+    by events only.  The host waits for one thing: the download event of the frame it hands back.
+
+        with FrameStream(model, depth=2) as fs:
+            for sr in fs.map(frames):          # HxWx3 uint8 ndarrays in, (sH)x(sW)x3 uint8 ndarrays out, input order
+                ...
+
+    `submit(frame)` enqueues a frame (at most `depth` may be pending), `result()` returns the oldest pending one.  With
+    `copy=True` (default) the returned array is the caller's own; with `copy=False` it is a view of the slot's pinned buffer,
+    valid until that slot is submitted to again, i.e. for `depth - 1` further submits (the `depth`-th overwrites it).  A frame of
+    another size drains the pipeline (pending results are kept, in order) and reallocates.  No graph capture here."""
+
+    def __init__(self, model, depth: int = 2) -> None:
+        if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
+            raise ValueError(f"FrameStream: depth must be an int >= 1, got {depth!r}")
+        param = next(iter(model.parameters()), None)
+        if param is None or not param.is_cuda:
+            raise RuntimeError("FrameStream: the model must be on the MI355X device (model.cuda()); this package has no CPU path")
+        self.model, self.depth, self.device = model, depth, param.device
+        self._slots: List[_Slot] = []
+        self._shape = None
+        self._next = 0
+        self._pending: Deque[_Slot] = collections.deque()
+        self._ready: Deque[np.ndarray] = collections.deque()     # results drained by a change of frame size
+        self._up = self._down = self._compute = None
+        self._closed = False
+
+    @staticmethod
+    def check_frame(frame) -> None:
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3 or min(frame.shape) < 1:
+            got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
+            raise ValueError(f"FrameStream: expected an HxWx3 uint8 ndarray, got {got}")
+
+    def __len__(self) -> int:
+        """Results not yet taken."""
+        return len(self._ready) + len(self._pending)
+
+    def _drain(self) -> None:
+        while self._pending:
+            self._ready.append(self._take(self._pending.popleft(), True))
+
+    def _take(self, slot: _Slot, copy: bool) -> np.ndarray:
+        slot.downloaded.synchronize()
+        _lib.chain_health()          # every launch of this frame has reported: a broken chained launch must not reach the caller
+        return slot.np_out.copy() if copy else slot.np_out
+
+    def _allocate(self, h: int, w: int) -> None:
+        self._drain()
+        if self._compute is None:
+            self._compute = torch.cuda.current_stream(self.device)
+            self._up, self._down = torch.cuda.Stream(self.device), torch.cuda.Stream(self.device)
+        else:                        # the old slots' device buffers return to the allocator: nothing may still be reading them
+            for st in (self._up, self._compute, self._down):
+                st.synchronize()
+        s = self.model.upscale_factor
+        with torch.cuda.device(self.device):
+            self._slots = [_Slot(h, w, s, self.device) for _ in range(self.depth)]
+        self._shape, self._next = (h, w), 0
+
+    def submit(self, frame: np.ndarray) -> None:
+        if self._closed:
+            raise RuntimeError("FrameStream: closed")
+        self.check_frame(frame)
+        if len(self._pending) >= self.depth:
+            raise RuntimeError(f"FrameStream: {self.depth} frames are pending already; take a result() first")
+        if frame.shape[:2] != self._shape:
+            self._allocate(frame.shape[0], frame.shape[1])
+        slot = self._slots[self._next]
+        self._next = (self._next + 1) % self.depth
+        np.copyto(slot.np_in, frame)                 # (the slot's previous upload finished before its result was handed back)
+        with torch.cuda.stream(self._up):
+            if slot.used:
+                self._up.wait_event(slot.computed)   # the tail of the previous frame in this slot re-read dev_in
+            slot.dev_in.copy_(slot.pin_in, non_blocking=True)
+            slot.uploaded.record(self._up)
+        with torch.cuda.stream(self._compute):
+            self._compute.wait_event(slot.uploaded)
+            slot.dev_out = upscale_u8(self.model, slot.dev_in)
+            slot.computed.record(self._compute)
+        with torch.cuda.stream(self._down):
+            self._down.wait_event(slot.computed)
+            slot.pin_out.copy_(slot.dev_out, non_blocking=True)
+            slot.downloaded.record(self._down)
+        slot.used = True
+        self._pending.append(slot)
+
+    def result(self, copy: bool = True) -> np.ndarray:
+        """The oldest result not yet taken (see the class docstring for `copy=False`)."""
+        if self._ready:
+            return self._ready.popleft()
+        if not self._pending:
+            raise RuntimeError("FrameStream: no frame is pending")
+        return self._take(self._pending.popleft(), copy)
+
+    def map(self, frames: Iterable[np.ndarray], copy: bool = True) -> Iterator[np.ndarray]:
+        """Results of `frames` in input order, `depth` frames in flight."""
+        for frame in frames:
+            while self._ready or len(self._pending) >= self.depth:
+                yield self.result(copy)
+            self.submit(frame)
+        while len(self):
+            yield self.result(copy)
+
+    def close(self) -> None:
+        if self._closed:
+            return
+        self._closed = True
+        if self._compute is not None:
+            for st in (self._up, self._compute, self._down):
+                st.synchronize()
+        self._pending.clear()
+        self._ready.clear()
+        self._slots = []
+
+    def __enter__(self) -> "FrameStream":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()

@@ -1,0 +1,86 @@
+"""Directory super-resolution on the uint8 frame path (frames.py): every image of a folder, pipelined.
+
+    python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
+        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2]
+
+The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
+walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
+encode under the same file name in `--output_dir`.  Each written image equals what `inference.py` writes for that file on its
+own.  Frames of different sizes may be mixed (a change of size drains the pipeline).  Video containers are not read here: extract
+frames first (ffmpeg -i in.mp4 lr/%06d.png), as upstream's inference_realesrgan_video.py does internally.
+"""
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import config
+from .compact import SRVGGNetCompact
+from .frames import FrameStream
+from .model import Generator, load_official_state_dict
+
+IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
+
+
+def build_model(args):
+    """The model of `inference.main` (same constructor arguments, same checkpoint formats), in eval mode on config.device."""
+    model_type = getattr(args, "model_type", "rrdb") or "rrdb"
+    precision = getattr(args, "precision", None) or config.inference_precision
+    if model_type == "compact":
+        model = SRVGGNetCompact(config.in_channels, config.out_channels, 64, getattr(args, "num_conv", 16) or 16,
+                                config.upscale_factor, getattr(args, "act_type", "prelu") or "prelu", precision=precision)
+    elif model_type == "rrdb":
+        model = Generator(config.in_channels, config.out_channels, config.upscale_factor, precision=precision)
+    else:
+        raise ValueError(f"--model_type must be 'rrdb' or 'compact', got {model_type!r}")
+    model = model.to(memory_format=torch.channels_last, device=config.device)
+    print("Build Real_ESRGAN model successfully.")
+    checkpoint = torch.load(args.weights_path, map_location=lambda storage, loc: storage, weights_only=False)
+    if isinstance(checkpoint, dict) and "state_dict" in checkpoint:
+        model.load_state_dict({k.replace("model.", ""): v for k, v in checkpoint["state_dict"].items()})
+    else:
+        load_official_state_dict(model, checkpoint)
+    print(f"Load Real_ESRGAN model weights `{args.weights_path}` successfully.")
+    return model.eval()
+
+
+def list_images(inputs_dir: str):
+    return sorted(f for f in os.listdir(inputs_dir) if f.lower().endswith(IMAGE_EXTENSIONS))
+
+
+def main(args) -> None:
+    from PIL import Image
+    torch.cuda.set_device(config.device)
+    model = build_model(args)
+    names = list_images(args.inputs_dir)
+    os.makedirs(args.output_dir, exist_ok=True)
+
+    def decode():
+        for name in names:
+            yield np.asarray(Image.open(os.path.join(args.inputs_dir, name)).convert("RGB"))
+
+    with FrameStream(model, depth=getattr(args, "depth", 2) or 2) as stream:
+        # copy=False: the pinned view is encoded before the next result is asked for, i.e. before its slot is submitted to again
+        for name, sr_image in zip(names, stream.map(decode(), copy=False)):
+            Image.fromarray(sr_image).save(os.path.join(args.output_dir, name))
+            print(f"SR image save to `{os.path.join(args.output_dir, name)}`")
+
+
+def get_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(description="Using the Real_ESRGAN model generator super-resolution a directory of images.")
+    parser.add_argument("--inputs_dir", type=str, required=True, help="Low-resolution image directory.")
+    parser.add_argument("--output_dir", type=str, required=True, help="Super-resolution image directory (same file names).")
+    parser.add_argument("--weights_path", type=str, required=True, help="Model weights file path.")
+    parser.add_argument("--precision", type=str, default=None, choices=["fast", "exact16", "strict"],
+                        help="kernel arithmetic; default config.inference_precision = exact16")
+    parser.add_argument("--model_type", type=str, default="rrdb", choices=["rrdb", "compact"],
+                        help="rrdb: Generator (RRDBNet); compact: upstream's SRVGGNetCompact (realesr-animevideov3 / realesr-general-x4v3)")
+    parser.add_argument("--num_conv", type=int, default=16, help="compact: body convs (16 animevideov3, 32 general-x4v3)")
+    parser.add_argument("--act_type", type=str, default="prelu", choices=["prelu", "leakyrelu", "relu"], help="compact: activation")
+    parser.add_argument("--depth", type=int, default=2, help="frames in flight (FrameStream)")
+    return parser
+
+
+if __name__ == "__main__":
+    main(get_parser().parse_args())

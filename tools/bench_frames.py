@@ -1,0 +1,148 @@
+"""Host-to-host throughput of the uint8 frame path against the single-image float flow, 1920x1080 -> x4 with the compact
+generator (num_conv 16 and 32, `fast` and `exact16`): a host uint8 HxWx3 array in, a host uint8 array out.
+
+Paths, run ALTERNATING (A, B1, B2/2, B2/3, A, ...) for `--rounds` rounds in one process, so that drift of the box hits all alike:
+  A      what inference.py does per image: astype(float32) / 255 -> image_to_tensor -> .to(device) -> model -> clamp_ -> tensor_to_image
+  B1     upscale_u8 one frame at a time, plain .cuda() / .cpu()
+  B2/d   FrameStream(depth=d).map, d = 2 and 3 (copy=True: the caller owns every result), and d = 2 with copy=False
+  dev    device only, HIP events: model(frame fp32) against model.forward_u8(frame uint8), alternated too
+Wall clock around a loop of frames that ends with every result on the host, after a warm-up of each path.  One JSON line per
+(case, path): the per-round ms per frame, their median and spread (max - min), frames/s, bytes moved each way, the device name;
+one `summary` line per case with the ratios and whether each exceeds the spread of the alternated repeats.
+
+    python tools/bench_frames.py [--rounds 3] [--frames 6] [--out profiles/frames_bench_1080p.jsonl]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import real_esrgan_pytorch_amd as R  # noqa: E402
+from real_esrgan_pytorch_amd import imgproc  # noqa: E402
+
+H, W, S = 1080, 1920, 4
+IN_U8, OUT_U8 = H * W * 3, H * S * W * S * 3
+
+
+def path_a(model, frame):
+    lr = frame.astype(np.float32) / 255.0
+    t = imgproc.image_to_tensor(lr, False, False).unsqueeze_(0)
+    t = t.to(device="cuda", memory_format=torch.channels_last, non_blocking=True)
+    with torch.no_grad():
+        sr = model(t)
+    return imgproc.tensor_to_image(sr.clamp_(0, 1), False, False)
+
+
+def path_b1(model, frame):
+    return R.upscale_u8(model, torch.from_numpy(frame)[None].cuda())[0].cpu().numpy()
+
+
+def wall_ms(run, frames):
+    """ms per frame of `run(frames)`, which returns with every result on the host."""
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    n = run(frames)
+    torch.cuda.synchronize()
+    assert n == len(frames)
+    return (time.perf_counter() - t0) * 1e3 / len(frames)
+
+
+def device_ms(fn, steps):
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    start.record()
+    for _ in range(steps):
+        fn()
+    end.record()
+    torch.cuda.synchronize()
+    return start.elapsed_time(end) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--frames", type=int, default=6, help="frames per timed loop of path A and B1 (the streams take 4x as many)")
+    ap.add_argument("--device-steps", type=int, default=20)
+    ap.add_argument("--out", default=None, help="also append the lines to this file")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_frames.py measures on the GPU"
+    torch.cuda.set_device(0)
+    box = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]}
+    rs = np.random.RandomState(0)
+    pool = [rs.randint(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(4)]
+    few = [pool[i % 4] for i in range(args.frames)]
+    many = [pool[i % 4] for i in range(args.frames * 4)]
+    lines = []
+
+    def emit(line):
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+
+    for num_conv in (16, 32):
+        for precision in ("fast", "exact16"):
+            torch.manual_seed(0)
+            model = R.SRVGGNetCompact(num_conv=num_conv, upscale=S, precision=precision).cuda().eval().requires_grad_(False)
+            streams = {d: R.FrameStream(model, depth=d) for d in (2, 3)}
+            paths = {
+                "A": (few, lambda fr: sum(1 for f in fr if path_a(model, f) is not None), IN_U8 * 4, OUT_U8 * 4),
+                "B1": (few, lambda fr: sum(1 for f in fr if path_b1(model, f) is not None), IN_U8, OUT_U8),
+                "B2/2": (many, lambda fr: sum(1 for _ in streams[2].map(fr)), IN_U8, OUT_U8),
+                "B2/3": (many, lambda fr: sum(1 for _ in streams[3].map(fr)), IN_U8, OUT_U8),
+                "B2/2/view": (many, lambda fr: sum(1 for _ in streams[2].map(fr, copy=False)), IN_U8, OUT_U8),
+            }
+            # results must not change: the two ends of the comparison give the same bytes on a timed frame
+            same = bool(np.array_equal(path_a(model, pool[0]), path_b1(model, pool[0])) and
+                        np.array_equal(next(iter(streams[2].map(pool[:1]))), path_b1(model, pool[0])))
+            x_f32 = R.from_u8(torch.from_numpy(pool[0])[None].cuda())
+            x_u8 = torch.from_numpy(pool[0])[None].cuda()
+            dev = {"dev/forward": lambda: model(x_f32), "dev/forward_u8": lambda: model.forward_u8(x_u8)}
+            for name, (fr, run, _, _) in paths.items():      # warm-up of every path
+                run(fr[:2])
+            with torch.no_grad():
+                for fn in dev.values():
+                    for _ in range(3):
+                        fn()
+            ms = {name: [] for name in list(paths) + list(dev)}
+            for _ in range(args.rounds):
+                for name, (fr, run, _, _) in paths.items():
+                    ms[name].append(wall_ms(run, fr))
+                with torch.no_grad():
+                    for name, fn in dev.items():
+                        ms[name].append(device_ms(fn, args.device_steps))
+            case = dict(tool="bench_frames", num_conv=num_conv, precision=precision, frame=f"{W}x{H}->x{S}", **box)
+            med, spread = {}, {}
+            for name, v in ms.items():
+                med[name], spread[name] = statistics.median(v), max(v) - min(v)
+                extra = {}
+                if name in paths:
+                    extra = dict(frames_per_loop=len(paths[name][0]), h2d_bytes_per_frame=paths[name][2], d2h_bytes_per_frame=paths[name][3],
+                                 d2h_gb_per_s=round(paths[name][3] / (med[name] * 1e-3) / 1e9, 2))
+                else:
+                    extra = dict(steps=args.device_steps, out_bytes_per_frame=OUT_U8 * (4 if name == "dev/forward" else 1))
+                emit(dict(case, path=name, ms_per_frame_rounds=[round(x, 3) for x in v], ms_per_frame=round(med[name], 3),
+                          spread_ms=round(spread[name], 3), frames_per_s=round(1e3 / med[name], 2), **extra))
+            best = min(("B2/2", "B2/3"), key=lambda k: med[k])
+            emit(dict(case, path="summary", outputs_equal=same,
+                      speedup_b1_over_a=round(med["A"] / med["B1"], 2), speedup_b2_depth2_over_a=round(med["A"] / med["B2/2"], 2),
+                      speedup_b2_depth3_over_a=round(med["A"] / med["B2/3"], 2),
+                      b2_faster_than_a_beyond_spread=bool(max(ms[best]) + 0.0 < min(ms["A"])),
+                      device_u8_over_float=round(med["dev/forward_u8"] / med["dev/forward"], 3),
+                      device_u8_not_slower_beyond_spread=bool(med["dev/forward_u8"] <= med["dev/forward"] + max(spread["dev/forward"], spread["dev/forward_u8"]))))
+            for st in streams.values():
+                st.close()
+            del model, streams, paths, dev
+            torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
