@@ -414,6 +414,31 @@ int resr_compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x_u8, const
 int resr_u8_to_nchw(const uint8_t* src_u8, float* dst_f32, int32_t n, int32_t h, int32_t w, void* stream);
 int resr_nchw_to_u8(const float* src_f32, uint8_t* dst_u8, int32_t n, int32_t h, int32_t w, void* stream);
 
+/* Outscale: a final size that is not the network's factor (real_esrgan-pytorch_amd/csrc/image_resize.hip).  The resampler is the
+ * MATLAB-style bicubic of the reference's image_resize (a = -0.5, antialiased when shrinking, symmetric edges, output size
+ * ceil(in * scale)), given per axis as a banded tap table on the device: idx [out, taps] int32 (0-based source positions, the
+ * reflection folded in) and w [out, taps] float32, rows contiguous -- imgproc.resize_band_tables builds them.
+ *   out = W-pass(H-pass(src)), each pass acc = fmaf(v[idx[k]], w[k], acc) from 0, k ascending, fp32 throughout.
+ * An idx entry outside the source is clamped into it (never read out of bounds); tables whose rows are not the band of a resize
+ * (a tile's entries further apart than floor((t - 1) * in / (out - 1)) + 2 + taps) give undefined VALUES, not undefined accesses.
+ *
+ * resr_image_resize: src fp32 [N,C,H,W] -> dst fp32 [N,C,oh,ow] (out_u8 = 0) or uint8 [N,oh,ow,3] (out_u8 = 1: C must be 3, dst
+ * 4-byte aligned; * 255.0f, clamp, truncate as resr_nchw_to_u8; a NaN is outside the contract as above).
+ * resr_compact_forward_u8_scaled: resr_compact_forward_u8 with the resize fused into its last kernel: y_u8 is [N,oh,ow,3], the
+ * source of the resize is the [N,3,H*s,W*s] frame resr_compact_forward would have stored (t + x, one add), which is never written;
+ * same descriptor, packed weights and workspace (resr_compact_workspace_bytes: nothing more).  Its result equals
+ * resr_image_resize(out_u8 = 1) of that frame bit for bit.
+ * Both: a null pointer, n, c, h, w, oh, ow <= 0, taps outside [1, 4096], N * ceil(C / 3) > 65535, or a scale so small that the taps
+ * of ONE output pixel do not fit a 64 KB LDS tile are RESR_ERR_ARG; every check comes before the first launch.  The caller
+ * guarantees the tables' lengths (oh * taps_y, ow * taps_x entries). */
+int resr_image_resize(const float* src_f32, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow,
+                      const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x, int32_t taps_x,
+                      int32_t out_u8, void* stream);
+int resr_compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
+                                   void* workspace, size_t workspace_bytes, uint8_t* y_u8, int32_t oh, int32_t ow,
+                                   const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
+                                   int32_t taps_x, void* stream);
+
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */
 

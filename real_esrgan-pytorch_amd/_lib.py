@@ -131,6 +131,9 @@ _PROTOS = {
     "resr_compact_pack_table": (C.c_int64, [C.POINTER(CompactDesc), _P, C.c_int64]),
     "resr_compact_forward": (C.c_int, [C.POINTER(CompactDesc), _P, _P, _P, _P, C.c_size_t, _P, _P]),
     "resr_compact_forward_u8": (C.c_int, [C.POINTER(CompactDesc), _P, _P, _P, _P, C.c_size_t, _P, _P]),
+    "resr_compact_forward_u8_scaled": (C.c_int, [C.POINTER(CompactDesc), _P, _P, _P, _P, C.c_size_t, _P, C.c_int32, C.c_int32,
+                                                 _P, _P, C.c_int32, _P, _P, C.c_int32, _P]),
+    "resr_image_resize": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
     "resr_u8_to_nchw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "resr_nchw_to_u8": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "resr_ema_update": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P]),

@@ -180,10 +180,19 @@ class SRVGGNetCompact(nn.Module):
                    "resr_compact_forward")
         return y
 
-    def forward_u8(self, frames: torch.Tensor) -> torch.Tensor:
+    def forward_u8(self, frames: torch.Tensor, outscale: Optional[float] = None, plan=None) -> torch.Tensor:
         """frames uint8 [N,H,W,3] on the model's device, contiguous -> uint8 [N,H*s,W*s,3]: bit for bit
         `imgproc.tensor_to_image(self(frames / 255 as NCHW fp32))` per image (a NaN inside the net is outside that contract).
-        Same guard (a call with grad enabled and parameters that require grad raises), packing and workspace caches as `forward`."""
+        Same guard (a call with grad enabled and parameters that require grad raises), packing and workspace caches as `forward`.
+
+        `outscale` (a finite positive number other than the model's factor): the final size is `frames.output_size(H, W, s,
+        outscale)` instead -- `resr_compact_forward_u8_scaled`: the last kernel resizes the frame it would have stored by
+        r = outscale / s (the reference's `image_resize`: antialiased bicubic, csrc/image_resize.hip) tile by tile in LDS and writes
+        only the resized uint8 frame; bit for bit `imgproc.image_resize_native(self(float frames), r, u8=True)`.  `plan`: a cached
+        `imgproc.ResizePlan` for this frame size and r (FrameStream keeps one).  None or the model's factor: the path above."""
+        from . import frames as _frames
+        from .imgproc import ResizePlan
+        o = _frames.check_outscale(outscale, self.upscale, "SRVGGNetCompact.forward_u8")
         if torch.is_grad_enabled() and any(p.requires_grad for p in self._ordered_params()):
             raise RuntimeError("SRVGGNetCompact: the compact generator's backward pass is not implemented on the MI355X path; "
                                "run inference under torch.no_grad() (or with requires_grad_(False) parameters)")
@@ -196,10 +205,23 @@ class SRVGGNetCompact(nn.Module):
         flat = self.flat_parameters()
         _lib.require_cuda(flat, "SRVGGNetCompact parameters")
         n, h, w, _ = frames.shape
+        s = self.upscale
+        if o is not None:
+            if plan is None:
+                plan = ResizePlan(h * s, w * s, o / s, frames.device)      # raises before any launch for a frame the rule refuses
+            elif (plan.in_h, plan.in_w, plan.scale_factor) != (h * s, w * s, o / s) or plan.idx_y.device != frames.device:
+                raise ValueError(f"SRVGGNetCompact.forward_u8: a plan for {plan.in_h}x{plan.in_w} x {plan.scale_factor}, "
+                                 f"the call is {h * s}x{w * s} x {o / s}")
+            plan.check("SRVGGNetCompact.forward_u8")
         desc = self._desc(n, h, w)
         self._pack(desc, flat)
         ws = self._workspace(desc, frames.device)
-        s = self.upscale
+        if o is not None:
+            y = torch.empty((n, plan.out_h, plan.out_w, self.num_out_ch), dtype=torch.uint8, device=frames.device)
+            _lib.check(_lib.lib().resr_compact_forward_u8_scaled(C.byref(desc), _lib.ptr(frames), _lib.ptr(flat), _lib.ptr(self._packed),
+                                                                 _lib.ptr(ws), ws.numel(), _lib.ptr(y), *plan.args(),
+                                                                 _lib.stream_ptr(frames)), "resr_compact_forward_u8_scaled")
+            return y
         y = torch.empty((n, h * s, w * s, self.num_out_ch), dtype=torch.uint8, device=frames.device)
         _lib.check(_lib.lib().resr_compact_forward_u8(C.byref(desc), _lib.ptr(frames), _lib.ptr(flat), _lib.ptr(self._packed),
                                                       _lib.ptr(ws), ws.numel(), _lib.ptr(y), _lib.stream_ptr(frames)),

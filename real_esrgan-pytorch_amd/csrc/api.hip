@@ -103,6 +103,10 @@ size_t compact_workspace_bytes(const ResrCompactDesc*);
 int64_t compact_pack_table(const ResrCompactDesc*, ResrPackChunk*, int64_t);
 int compact_forward(const ResrCompactDesc*, const float*, const float*, const void*, void*, size_t, float*, hipStream_t);
 int compact_forward_u8(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, hipStream_t);
+int compact_forward_u8_scaled(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, int, int,
+                              const int32_t*, const float*, int, const int32_t*, const float*, int, hipStream_t);
+int image_resize_dispatch(const float*, void*, int, int, int, int, int, int, const int32_t*, const float*, int, const int32_t*,
+                          const float*, int, int, hipStream_t);
 int u8_to_nchw_dispatch(const uint8_t*, float*, int, int, int, hipStream_t);
 int nchw_to_u8_dispatch(const float*, uint8_t*, int, int, int, hipStream_t);
 
@@ -277,6 +281,22 @@ int resr_compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x_u8, const
                             void* workspace, size_t workspace_bytes, uint8_t* y_u8, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return compact_forward_u8(d, x_u8, params, packed, workspace, workspace_bytes, y_u8, (hipStream_t)stream);
+}
+
+int resr_compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
+                                   void* workspace, size_t workspace_bytes, uint8_t* y_u8, int32_t oh, int32_t ow,
+                                   const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
+                                   int32_t taps_x, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_u8_scaled(d, x_u8, params, packed, workspace, workspace_bytes, y_u8, oh, ow, idx_y, w_y, taps_y, idx_x, w_x,
+                                     taps_x, (hipStream_t)stream);
+}
+
+int resr_image_resize(const float* src_f32, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow,
+                      const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x, int32_t taps_x,
+                      int32_t out_u8, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return image_resize_dispatch(src_f32, dst, n, c, h, w, oh, ow, idx_y, w_y, taps_y, idx_x, w_x, taps_x, out_u8, (hipStream_t)stream);
 }
 
 int resr_u8_to_nchw(const uint8_t* src_u8, float* dst_f32, int32_t n, int32_t h, int32_t w, void* stream) {

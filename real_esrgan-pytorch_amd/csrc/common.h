@@ -88,4 +88,14 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
     return base + idx;
 }
 
+// image_resize.hip: one planned resize launch (resize_plan fills it on the host; the kernels take it by value)
+struct ResizeGeom {
+    int c, h, w;          // source: channels, rows, columns (of the HR frame on the fused path)
+    int oh, ow;
+    int py, px;           // taps per output row / column
+    int th, tw;           // output tile
+    int rh, rw, pitch;    // capacity of the staged region, LDS row pitch (floats)
+    int cgroups;          // ceil(c / 3)
+};
+
 }  // namespace resr

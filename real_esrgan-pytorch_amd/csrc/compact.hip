@@ -10,6 +10,8 @@
 // three stages per chunk.  No padding beyond each conv's own pad = 1: any H, W >= 1.
 // compact_forward_u8 is the same sequence for uint8 HWC frames: frames.hip's u8 head in place of the layout kernel, its u8 tail
 // (pixel-shuffle + residual + * 255, clamp, truncate) in place of compact_tail_kernel; same plan, same workspace.
+// compact_forward_u8_scaled ("outscale") is that sequence with image_resize.hip's fused tail in place of the u8 tail: the HR
+// frame is formed tile by tile in LDS and only the resized uint8 frame [N,oh,ow,3] is written; same plan, same workspace.
 #include <vector>
 
 #include "common.h"
@@ -22,6 +24,10 @@ int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const 
 int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
 int u8_head_dispatch(const uint8_t*, void*, int, int, int, int, hipStream_t, long);                      // frames.hip
 int compact_tail_u8(const float*, const uint8_t*, uint8_t*, int, int, int, int, hipStream_t);
+int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, bool,
+                const void*, ResizeGeom*);                                                                      // image_resize.hip
+int compact_tail_u8_scaled(const float*, const uint8_t*, uint8_t*, int, int, int, int, const int32_t*, const float*, const int32_t*,
+                           const float*, const ResizeGeom*, hipStream_t);
 
 namespace {
 
@@ -170,14 +176,27 @@ namespace {
 
 // The launch sequence both entries share.  U8 = false: x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32 (layout.hip head, compact_tail);
 // U8 = true: x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8 (frames.hip: the conversions fused into the head and the tail; the convs,
-// the packed weights and the workspace plan are the same).  Every argument check comes before the first launch.
+// the packed weights and the workspace plan are the same).  sc (U8 only): the resized tail of compact_forward_u8_scaled.
+// Every argument check comes before the first launch.
+struct ScaledTail {
+    int oh, ow, taps_y, taps_x;
+    const int32_t *idx_y, *idx_x;
+    const float *w_y, *w_x;
+};
+
 template <bool U8>
 int compact_run(const ResrCompactDesc* d, const void* x, const float* params, const void* packed, void* workspace,
-                size_t workspace_bytes, void* y, hipStream_t st, const char* who) {
+                size_t workspace_bytes, void* y, hipStream_t st, const char* who, const ScaledTail* sc = nullptr) {
     CPlan p;
     if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "%s: bad descriptor", who);
     if (!x || !params || !packed || !workspace || !y) return fail(RESR_ERR_ARG, "%s: null argument", who);
     if (U8 && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
+    ResizeGeom geom;
+    if (sc) {
+        const int rc = resize_plan(who, d->n, 3, d->h * d->upscale, d->w * d->upscale, sc->oh, sc->ow, sc->idx_y, sc->w_y, sc->taps_y,
+                                   sc->idx_x, sc->w_x, sc->taps_x, true, y, &geom);
+        if (rc) return rc;
+    }
     if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
     const bool x2 = d->dtype == RESR_F16X2;
     const size_t wes = elem_size(d->dtype) * (x2 ? 3 : 1);   // bytes per element of the packed layout
@@ -226,6 +245,9 @@ int compact_run(const ResrCompactDesc* d, const void* x, const float* params, co
         rc = conv3x3_dispatch(&cd, in, nullptr, pk + c.pk * wes, params + c.b_off, nullptr, nullptr, nullptr, t, nullptr, st);
         if (rc) return rc;
     }
+    if (U8 && sc)
+        return compact_tail_u8_scaled(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, sc->idx_y, sc->w_y, sc->idx_x, sc->w_x,
+                                      &geom, st);
     if (U8) return compact_tail_u8(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, st);
     return compact_tail(t, (const float*)x, (float*)y, N, H, W, d->upscale, st);
 }
@@ -240,6 +262,13 @@ int compact_forward(const ResrCompactDesc* d, const float* x, const float* param
 int compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
                        size_t workspace_bytes, uint8_t* y, hipStream_t st) {
     return compact_run<true>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward_u8");
+}
+
+int compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
+                              size_t workspace_bytes, uint8_t* y, int oh, int ow, const int32_t* idx_y, const float* w_y, int taps_y,
+                              const int32_t* idx_x, const float* w_x, int taps_x, hipStream_t st) {
+    const ScaledTail sc{oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x};
+    return compact_run<true>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward_u8_scaled", &sc);
 }
 
 }  // namespace resr

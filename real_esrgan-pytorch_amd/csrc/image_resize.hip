@@ -1,0 +1,306 @@
+// image_resize.hip -- the MATLAB-style antialiased bicubic resize of imgproc.image_resize as one tiled kernel, and the same
+// kernel as the tail of the compact generator ("outscale": a final size that is not the network's own factor).
+//
+// DEFINITION.  For a model of factor s, an LR frame H x W and outscale o (a positive float, o != s):
+//   sr  = model(x)                         fp32, not clamped: the float path
+//   r   = o / s                            out_h = ceil(H * s * r), out_w = ceil(W * s * r)   (the reference's ceil(in * scale))
+//   per axis a banded tap table            idx [out, P] int32, w [out, P] float32, P = ceil(4 / min(r, 1)) + 2: the non-zero band of
+//                                          imgproc._resize_matrix with the symmetric reflection folded into idx, built on the host
+//                                          in float32 (imgproc.resize_band_tables)
+//   out = W-pass(H-pass(sr))               each pass acc = fmaf(v[idx[k]], w[k], acc) from acc = 0, k ascending, fp32; the
+//                                          intermediate is fp32
+//   u8  : out * 255.0f, clamp to [0, 255], truncate (imgproc.tensor_to_image, as everywhere on the frame path)
+//
+// KERNEL.  One workgroup of 256 threads per output tile (th x tw pixels, up to three channels).  It finds the source region its
+// tile reads (rows min..max of the tile's idx_y entries by columns min..max of its idx_x entries), stages the tables and that
+// region in LDS, runs the H pass LDS -> LDS (lanes along a source row: consecutive LDS words, no bank conflict whatever the row
+// pitch), the W pass LDS -> registers (lanes along an output row: a stride of 1/r words, 2-way conflicts at r = 0.5; the pitch is
+// odd so that the two rows a wavefront covers do not add to them) and stores.  resr_image_resize stages fp32 NCHW; the fused
+// tail of resr_compact_forward_u8_scaled forms the staged value of HR pixel (Y, X), channel c, on the fly as
+//   t[c*s*s + (Y%s)*s + X%s][Y/s][X/s] + x_u8[Y/s][X/s][c] / 255.0f        (the single fp32 add of compact_tail_u8_kernel)
+// so the HR frame exists as LDS tiles only.  Both call resize_tile(): fused and generic results are the same bits.
+//
+// The host picks the largest tile of a fixed list whose tables + region + intermediate (+ the u8 row buffer) stay within 64 KB:
+// two workgroups or more per CU (160 KB of LDS) and no per-kernel LDS opt-in.  The region of t consecutive outputs is bounded by
+// floor((t - 1) * in / (out - 1)) + 2 + P source pixels (the left tap moves 1/r < in / (out - 1) per output; reflection only
+// folds the band inwards), at most `in`.  At r = 0.5 (P = 10) that is a 16 x 32 tile: 42 x 74 x 3 source floats + 16 x 74 x 3
+// intermediate ~ 51 KB.  An r whose single-pixel footprint does not fit is RESR_ERR_ARG: there is no other path.
+// A table entry outside the region bound (tables not built by the rule above) is clamped into it: never an access out of bounds.
+// u8 rows leave as dword stores where the address is 4-byte aligned and byte stores at the row ends; every index that can pass
+// 2^31 is 64-bit.  Vector stores only.
+#include <limits.h>
+
+#include "common.h"
+
+namespace resr {
+
+namespace {
+
+constexpr int kResizeThreads = 256;
+constexpr size_t kResizeLdsBudget = 64 * 1024;
+constexpr int kResizeMaxTaps = 4096;
+
+__device__ __forceinline__ float u8_unit(unsigned v) { return (float)v / 255.0f; }
+
+__device__ __forceinline__ unsigned quantise_u8(float v) {   // frames.hip's
+    v *= 255.0f;
+    v = v > 0.f ? v : 0.f;
+    v = v < 255.f ? v : 255.f;
+    return (unsigned)v;
+}
+
+// fp32 [N,C,H,W]
+struct PlanarSrc {
+    const float* x;
+    int c, h, w;
+    __device__ __forceinline__ float load(long b, int ch, int Y, int X) const {
+        return x[((b * c + ch) * h + Y) * (long)w + X];
+    }
+};
+
+// the compact net's last conv t [N,3S^2,h,w] + its u8 input frame [N,h,w,3]: pixel-shuffle + residual of HR pixel (Y, X)
+template <int S>
+struct ShuffleSrc {
+    const float* t;
+    const uint8_t* x;
+    int h, w;             // LR
+    __device__ __forceinline__ float load(long b, int ch, int Y, int X) const {
+        const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
+        const long plane = (long)h * w;
+        const float tv = t[(b * 3 * S * S + ch * S * S + sy * S + sx) * plane + (long)yy * w + xx];
+        return tv + u8_unit(x[((b * h + yy) * (long)w + xx) * 3 + ch]);
+    }
+};
+
+// The whole tile: region bounds, staging, both passes, quantisation and stores.  y: fp32 [N,C,oh,ow] or u8 [N,oh,ow,3] (U8).
+template <typename Src, bool U8>
+__device__ __forceinline__ void resize_tile(const Src& src, void* __restrict__ y, const int32_t* __restrict__ idx_y,
+                                            const float* __restrict__ w_y, const int32_t* __restrict__ idx_x,
+                                            const float* __restrict__ w_x, const ResizeGeom& g) {
+    extern __shared__ __attribute__((aligned(16))) char resize_smem[];
+    __shared__ int s_bounds[4];
+    const int tid = threadIdx.x;
+    const int ox0 = blockIdx.x * g.tw, oy0 = blockIdx.y * g.th;
+    const int th = min(g.th, g.oh - oy0), tw = min(g.tw, g.ow - ox0);
+    const long b = blockIdx.z / g.cgroups;
+    const int c0 = (int)(blockIdx.z - b * g.cgroups) * 3;
+    const int nc = min(3, g.c - c0);
+
+    int* s_iy = reinterpret_cast<int*>(resize_smem);
+    float* s_wy = reinterpret_cast<float*>(s_iy + g.th * g.py);
+    int* s_ix = reinterpret_cast<int*>(s_wy + g.th * g.py);
+    float* s_wx = reinterpret_cast<float*>(s_ix + g.tw * g.px);
+    float* s_src = s_wx + g.tw * g.px;
+    float* s_mid = s_src + 3 * g.rh * g.pitch;
+    uint8_t* s_out = reinterpret_cast<uint8_t*>(s_mid + 3 * g.th * g.pitch);
+
+    // ---- the region this tile reads -----------------------------------------------------------------------------------------
+    if (tid == 0) { s_bounds[0] = INT_MAX; s_bounds[1] = INT_MIN; s_bounds[2] = INT_MAX; s_bounds[3] = INT_MIN; }
+    __syncthreads();
+    {
+        int lo = INT_MAX, hi = INT_MIN;
+        const int32_t* p = idx_y + (long)oy0 * g.py;
+        for (int i = tid; i < th * g.py; i += kResizeThreads) { const int v = p[i]; lo = min(lo, v); hi = max(hi, v); }
+        if (lo <= hi) { atomicMin(&s_bounds[0], lo); atomicMax(&s_bounds[1], hi); }
+        lo = INT_MAX; hi = INT_MIN;
+        p = idx_x + (long)ox0 * g.px;
+        for (int i = tid; i < tw * g.px; i += kResizeThreads) { const int v = p[i]; lo = min(lo, v); hi = max(hi, v); }
+        if (lo <= hi) { atomicMin(&s_bounds[2], lo); atomicMax(&s_bounds[3], hi); }
+    }
+    __syncthreads();
+    const int ymin = min(max(s_bounds[0], 0), g.h - 1), xmin = min(max(s_bounds[2], 0), g.w - 1);
+    const int rh = min(min(max(s_bounds[1], ymin), g.h - 1) - ymin + 1, g.rh);
+    const int rw = min(min(max(s_bounds[3], xmin), g.w - 1) - xmin + 1, g.rw);
+
+    // ---- tables (region-relative, clamped into the region) and the region itself ----------------------------------------------
+    for (int i = tid; i < th * g.py; i += kResizeThreads) {
+        s_iy[i] = min(max(idx_y[(long)oy0 * g.py + i] - ymin, 0), rh - 1);
+        s_wy[i] = w_y[(long)oy0 * g.py + i];
+    }
+    for (int i = tid; i < tw * g.px; i += kResizeThreads) {
+        s_ix[i] = min(max(idx_x[(long)ox0 * g.px + i] - xmin, 0), rw - 1);
+        s_wx[i] = w_x[(long)ox0 * g.px + i];
+    }
+    const int region = rh * rw;
+    for (int c = 0; c < nc; ++c)
+        for (int i = tid; i < region; i += kResizeThreads) {
+            const int ry = i / rw, rx = i - ry * rw;
+            s_src[(c * g.rh + ry) * g.pitch + rx] = src.load(b, c0 + c, ymin + ry, xmin + rx);
+        }
+    __syncthreads();
+
+    // ---- H pass: LDS -> LDS ---------------------------------------------------------------------------------------------------
+    const int mid = th * rw;
+    for (int c = 0; c < nc; ++c)
+        for (int i = tid; i < mid; i += kResizeThreads) {
+            const int ty = i / rw, col = i - ty * rw;
+            const float* col_p = s_src + c * g.rh * g.pitch + col;
+            const int* iy = s_iy + ty * g.py;
+            const float* wy = s_wy + ty * g.py;
+            float acc = 0.f;
+            for (int k = 0; k < g.py; ++k) acc = fmaf(col_p[iy[k] * g.pitch], wy[k], acc);
+            s_mid[(c * g.th + ty) * g.pitch + col] = acc;
+        }
+    __syncthreads();
+
+    // ---- W pass: LDS -> registers, store --------------------------------------------------------------------------------------
+    if constexpr (!U8) {
+        float* yf = reinterpret_cast<float*>(y);
+        const int outs = th * tw;
+        for (int c = 0; c < nc; ++c)
+            for (int i = tid; i < outs; i += kResizeThreads) {
+                const int ty = i / tw, tx = i - ty * tw;
+                const float* row = s_mid + (c * g.th + ty) * g.pitch;
+                const int* ix = s_ix + tx * g.px;
+                const float* wx = s_wx + tx * g.px;
+                float acc = 0.f;
+                for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
+                yf[((b * g.c + c0 + c) * g.oh + oy0 + ty) * (long)g.ow + ox0 + tx] = acc;
+            }
+    } else {
+        const int outs = th * tw;
+        for (int i = tid; i < outs; i += kResizeThreads) {
+            const int ty = i / tw, tx = i - ty * tw;
+            const int* ix = s_ix + tx * g.px;
+            const float* wx = s_wx + tx * g.px;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float* row = s_mid + (c * g.th + ty) * g.pitch;
+                float acc = 0.f;
+                for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
+                s_out[i * 3 + c] = (uint8_t)quantise_u8(acc);
+            }
+        }
+        __syncthreads();
+        // a tile row is tw * 3 contiguous bytes of y: slot 0 writes the bytes before the first 4-byte boundary, slot j >= 1 one
+        // dword (or, at the row's end, the bytes that are left)
+        uint8_t* yb = reinterpret_cast<uint8_t*>(y);
+        const int len = tw * 3;
+        const int slots = len / 4 + 2;
+        for (int i = tid; i < th * slots; i += kResizeThreads) {
+            const int ty = i / slots, j = i - ty * slots;
+            const long g0 = ((b * g.oh + oy0 + ty) * (long)g.ow + ox0) * 3;
+            const uint8_t* sp = s_out + ty * len;
+            const int head = min((int)((4 - (g0 & 3)) & 3), len);
+            if (j == 0) {
+                for (int q = 0; q < head; ++q) yb[g0 + q] = sp[q];
+            } else {
+                const int off = head + 4 * (j - 1);
+                if (off + 4 <= len) {
+                    *reinterpret_cast<unsigned*>(yb + g0 + off) =
+                        (unsigned)sp[off] | ((unsigned)sp[off + 1] << 8) | ((unsigned)sp[off + 2] << 16) | ((unsigned)sp[off + 3] << 24);
+                } else {
+                    for (int q = off; q < len; ++q) yb[g0 + q] = sp[q];
+                }
+            }
+        }
+    }
+}
+
+template <bool U8>
+__global__ __launch_bounds__(kResizeThreads) void image_resize_kernel(PlanarSrc src, void* __restrict__ y, const int32_t* __restrict__ idx_y,
+                                                                      const float* __restrict__ w_y, const int32_t* __restrict__ idx_x,
+                                                                      const float* __restrict__ w_x, ResizeGeom g) {
+    resize_tile<PlanarSrc, U8>(src, y, idx_y, w_y, idx_x, w_x, g);
+}
+
+template <int S>
+__global__ __launch_bounds__(kResizeThreads) void compact_tail_u8_scaled_kernel(ShuffleSrc<S> src, void* __restrict__ y,
+                                                                                const int32_t* __restrict__ idx_y, const float* __restrict__ w_y,
+                                                                                const int32_t* __restrict__ idx_x, const float* __restrict__ w_x,
+                                                                                ResizeGeom g) {
+    resize_tile<ShuffleSrc<S>, true>(src, y, idx_y, w_y, idx_x, w_x, g);
+}
+
+// source pixels that t consecutive outputs of an axis (in -> out pixels, p taps) can reach
+int span_bound(int t, int in, int out, int p) {
+    long s = p;
+    if (t > 1) s += (long)(t - 1) * in / (out - 1) + 2;
+    return (int)(s < in ? s : in);
+}
+
+size_t lds_bytes(const ResizeGeom& g, bool u8) {
+    size_t floats = 2 * ((size_t)g.th * g.py + (size_t)g.tw * g.px) + 3 * ((size_t)g.rh + g.th) * g.pitch;
+    return floats * 4 + (u8 ? align_up((size_t)g.th * g.tw * 3, 4) : 0);
+}
+
+}  // namespace
+
+// Every check of a resize launch and the choice of its tile: no device work.  c, h, w: the source; who: the entry's name.
+int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, const void* idx_y, const void* w_y, int taps_y,
+                const void* idx_x, const void* w_x, int taps_x, bool u8, const void* y, ResizeGeom* out) {
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0)
+        return fail(RESR_ERR_ARG, "%s: bad shape (n=%d c=%d h=%d w=%d oh=%d ow=%d)", who, n, c, h, w, oh, ow);
+    if (!idx_y || !w_y || !idx_x || !w_x) return fail(RESR_ERR_ARG, "%s: null tap table", who);
+    if (taps_y < 1 || taps_y > kResizeMaxTaps || taps_x < 1 || taps_x > kResizeMaxTaps)
+        return fail(RESR_ERR_ARG, "%s: taps %d, %d outside [1, %d]", who, taps_y, taps_x, kResizeMaxTaps);
+    if (u8 && c != 3) return fail(RESR_ERR_ARG, "%s: uint8 output wants 3 channels, got %d", who, c);
+    if (u8 && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the uint8 output must be 4-byte aligned", who);
+    ResizeGeom g;
+    g.c = c; g.h = h; g.w = w; g.oh = oh; g.ow = ow; g.py = taps_y; g.px = taps_x;
+    g.cgroups = (c + 2) / 3;
+    if ((long)n * g.cgroups > 65535) return fail(RESR_ERR_ARG, "%s: n * ceil(c / 3) = %ld beyond the grid", who, (long)n * g.cgroups);
+    static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {8, 8}, {4, 8}, {4, 4}, {2, 4}, {2, 2}, {1, 2}, {1, 1}};
+    for (const auto& t : tiles) {
+        g.th = t[0]; g.tw = t[1];
+        g.rh = span_bound(g.th < oh ? g.th : oh, h, oh, taps_y);
+        g.rw = span_bound(g.tw < ow ? g.tw : ow, w, ow, taps_x);
+        g.pitch = g.rw | 1;
+        if (lds_bytes(g, u8) <= kResizeLdsBudget) {
+            if ((oh + g.th - 1) / g.th > 65535)
+                return fail(RESR_ERR_ARG, "%s: %d x %d outputs in %d x %d tiles beyond the grid", who, oh, ow, g.th, g.tw);
+            *out = g;
+            return RESR_OK;
+        }
+    }
+    return fail(RESR_ERR_ARG, "%s: the footprint of one output pixel (%d x %d taps) does not fit the LDS tile: scale too small", who,
+                taps_y, taps_x);
+}
+
+int image_resize_dispatch(const float* x, void* y, int n, int c, int h, int w, int oh, int ow, const int32_t* idx_y, const float* w_y,
+                          int taps_y, const int32_t* idx_x, const float* w_x, int taps_x, int u8, hipStream_t st) {
+    if (!x || !y) return fail(RESR_ERR_ARG, "image_resize: null argument");
+    ResizeGeom g;
+    const int rc = resize_plan("image_resize", n, c, h, w, oh, ow, idx_y, w_y, taps_y, idx_x, w_x, taps_x, u8 != 0, y, &g);
+    if (rc) return rc;
+    const dim3 grid((unsigned)((ow + g.tw - 1) / g.tw), (unsigned)((oh + g.th - 1) / g.th), (unsigned)(n * g.cgroups));
+    const PlanarSrc src{x, c, h, w};
+    const size_t lds = lds_bytes(g, u8 != 0);
+    prof_before(st);
+    if (u8)
+        hipLaunchKernelGGL(image_resize_kernel<true>, grid, dim3(kResizeThreads), lds, st, src, y, idx_y, w_y, idx_x, w_x, g);
+    else
+        hipLaunchKernelGGL(image_resize_kernel<false>, grid, dim3(kResizeThreads), lds, st, src, y, idx_y, w_y, idx_x, w_x, g);
+    prof_after(st, 31040 + (u8 ? 1 : 0), 2.0 * n * c * ((double)oh * w * taps_y + (double)oh * ow * taps_x),
+               (double)n * c * ((double)h * w * 4.0 + (double)oh * ow * (u8 ? 1.0 : 4.0)));
+    RESR_CHECK_LAUNCH("image_resize_kernel");
+    return RESR_OK;
+}
+
+// The fused tail of compact_forward_u8_scaled: g planned by resize_plan for c = 3, h = H * s, w = W * s, u8.
+int compact_tail_u8_scaled(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, const int32_t* idx_y,
+                           const float* w_y, const int32_t* idx_x, const float* w_x, const ResizeGeom* gp, hipStream_t st) {
+    const ResizeGeom g = *gp;
+    const dim3 grid((unsigned)((g.ow + g.tw - 1) / g.tw), (unsigned)((g.oh + g.th - 1) / g.th), (unsigned)n);
+    const size_t lds = lds_bytes(g, true);
+    prof_before(st);
+    switch (s) {
+#define RESR_SCALED_TAIL(S)                                                                                                       \
+    case S:                                                                                                                       \
+        hipLaunchKernelGGL(compact_tail_u8_scaled_kernel<S>, grid, dim3(kResizeThreads), lds, st, (ShuffleSrc<S>{t, x, h, w}), (void*)y, \
+                           idx_y, w_y, idx_x, w_x, g);                                                                            \
+        break;
+        RESR_SCALED_TAIL(1)
+        RESR_SCALED_TAIL(2)
+        RESR_SCALED_TAIL(3)
+        RESR_SCALED_TAIL(4)
+#undef RESR_SCALED_TAIL
+        default: return fail(RESR_ERR_ARG, "compact_tail_u8_scaled: upscale %d", s);
+    }
+    prof_after(st, 31050 + s, 2.0 * n * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
+               (double)n * h * w * (s * s * 12.0 + 3.0) + (double)n * g.oh * g.ow * 3.0);
+    RESR_CHECK_LAUNCH("compact_tail_u8_scaled_kernel");
+    return RESR_OK;
+}
+
+}  // namespace resr

@@ -8,22 +8,60 @@ bit: a frame enters as `u8 / 255.0f`, runs through the model in the model's arit
     to_u8(sr)                  fp32 [N,3,H,W]  -> uint8 [N,H,W,3]          one launch (resr_nchw_to_u8)
     upscale_u8(model, frames)  uint8 [N,H,W,3] -> uint8 [N,sH,sW,3]        any model, any frame size
     FrameStream(model, depth)  host ndarray in -> host ndarray out, `depth` frames in flight
+    output_size(h, w, s, o)    the size of a frame upscaled with `outscale=o`: the one place that formula lives
 
 `upscale_u8` is the one definition of the path: a model with a fused entry (`SRVGGNetCompact.forward_u8`) runs it when the frame
 fits one call; every other case (the RRDB `Generator`, frames the tiler has to cut) is `to_u8(super_resolve(model, from_u8(f)))`.
 There is no PyTorch fallback for the conversions: a missing kernel is an error of `_lib`.
+
+OUTSCALE -- a final size that is not the network's factor (upstream's `-s / --outscale`).  For a model of factor `s`, an LR frame
+`H x W` and `outscale = o` (a finite positive number, `o != s`; `None` or `o == s` is the path above, untouched):
+
+    sr = model(x)                              fp32, not clamped: exactly the float path
+    r = o / s                                  out_h = ceil(H * s * r), out_w = ceil(W * s * r)   (`output_size`)
+    per axis a banded tap table                `imgproc.resize_band_tables`: idx [out, P] int32, w [out, P] float32,
+                                               P = ceil(4 / min(r, 1)) + 2 -- the non-zero band of `imgproc._resize_matrix` (the
+                                               reference's MATLAB-style `image_resize`: bicubic a = -0.5, antialiased when
+                                               shrinking, symmetric edges), the reflection folded into idx, float32 arithmetic
+    out = W-pass(H-pass(sr))                   each pass acc = fmaf(v[idx[k]], w[k], acc) from 0, k ascending, fp32 throughout
+    u8 = trunc(clamp(out * 255.0f, 0, 255))    `imgproc.tensor_to_image`, as everywhere on this path
+
+A model with a fused entry runs `resr_compact_forward_u8_scaled` (the full-size frame exists as LDS tiles only); every other case is
+`super_resolve` -> `resr_image_resize` with uint8 output, the same device routine, hence the same bits.  A frame too small for the
+reference's symmetric edge copy raises ValueError before any launch, as the reference's `image_resize` raises.
 """
 from __future__ import annotations
 
 import collections
-from typing import Deque, Iterable, Iterator, List, Optional
+import math
+from typing import Deque, Iterable, Iterator, List, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib, tiling
 
-__all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream"]
+__all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream", "output_size", "check_outscale"]
+
+
+def check_outscale(outscale, s: int, what: str) -> Optional[float]:
+    """None when `outscale` asks for the network's own factor (None or == s), else the float; ValueError for anything that is not a
+    finite positive number (a bool included)."""
+    if outscale is None:
+        return None
+    if isinstance(outscale, bool) or not isinstance(outscale, (int, float)) or not math.isfinite(outscale) or outscale <= 0:
+        raise ValueError(f"{what}: outscale must be a finite positive number, got {outscale!r}")
+    return None if float(outscale) == float(s) else float(outscale)
+
+
+def output_size(h: int, w: int, s: int, outscale=None) -> Tuple[int, int]:
+    """(out_h, out_w) of an h x w frame through a model of factor s: (h * s, w * s), or with an outscale o != s the reference's
+    `ceil(in * scale)` for in = h * s and scale r = o / s (Python float division)."""
+    o = check_outscale(outscale, s, "output_size")
+    if o is None:
+        return h * s, w * s
+    r = o / s
+    return math.ceil(h * s * r), math.ceil(w * s * r)
 
 
 def _check_frames(frames: torch.Tensor, what: str) -> None:
@@ -59,22 +97,33 @@ def to_u8(sr: torch.Tensor) -> torch.Tensor:
 
 
 @torch.no_grad()
-def upscale_u8(model, frames: torch.Tensor, halo: Optional[int] = None) -> torch.Tensor:
+def upscale_u8(model, frames: torch.Tensor, halo: Optional[int] = None, outscale: Optional[float] = None, plan=None) -> torch.Tensor:
     """uint8 [N,H,W,3] on the model's device -> uint8 [N,sH,sW,3].  `halo`: the tiler's, for frames it has to cut
-    (tiling.super_resolve; with halo >= model.receptive_radius the tiled result equals the whole-frame one)."""
+    (tiling.super_resolve; with halo >= model.receptive_radius the tiled result equals the whole-frame one).
+    `outscale`: the final factor when it is not the model's (module docstring) -> uint8 [N, *output_size(H, W, s, outscale), 3];
+    `plan`: a cached `imgproc.ResizePlan` of this frame size (FrameStream keeps one)."""
     _check_frames(frames, "upscale_u8")
     n, h, w, _ = frames.shape
+    s = model.upscale_factor
+    o = check_outscale(outscale, s, "upscale_u8")
+    if o is None:
+        if hasattr(model, "forward_u8") and tiling.fits_whole(model, n, h, w):
+            return model.forward_u8(frames)
+        return to_u8(tiling.super_resolve(model, from_u8(frames), halo))
+    from .imgproc import ResizePlan, resize_with_plan
+    if plan is None:
+        plan = ResizePlan(h * s, w * s, o / s, frames.device)         # ValueError before any launch for a frame the rule refuses
     if hasattr(model, "forward_u8") and tiling.fits_whole(model, n, h, w):
-        return model.forward_u8(frames)
-    return to_u8(tiling.super_resolve(model, from_u8(frames), halo))
+        return model.forward_u8(frames, outscale=o, plan=plan)
+    return resize_with_plan(tiling.super_resolve(model, from_u8(frames), halo), plan, u8=True)
 
 
 class _Slot:
     """One frame in flight: pinned host buffers, the device input, the events that order its three stages."""
 
-    def __init__(self, h: int, w: int, s: int, device) -> None:
+    def __init__(self, h: int, w: int, out_h: int, out_w: int, device) -> None:
         self.pin_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
-        self.pin_out = torch.empty((1, h * s, w * s, 3), dtype=torch.uint8, pin_memory=True)
+        self.pin_out = torch.empty((1, out_h, out_w, 3), dtype=torch.uint8, pin_memory=True)
         self.np_in, self.np_out = self.pin_in.numpy()[0], self.pin_out.numpy()[0]
         self.dev_in = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
         self.dev_out: Optional[torch.Tensor] = None      # held until the slot's next submit: its download has been waited for by then
@@ -94,11 +143,16 @@ class FrameStream:
     `submit(frame)` enqueues a frame (at most `depth` may be pending), `result()` returns the oldest pending one.  With
     `copy=True` (default) the returned array is the caller's own; with `copy=False` it is a view of the slot's pinned buffer,
     valid until that slot is submitted to again, i.e. for `depth - 1` further submits (the `depth`-th overwrites it).  A frame of
-    another size drains the pipeline (pending results are kept, in order) and reallocates.  No graph capture here."""
+    another size drains the pipeline (pending results are kept, in order) and reallocates.  No graph capture here.
 
-    def __init__(self, model, depth: int = 2) -> None:
+    `outscale` (module docstring): results are `output_size(H, W, s, outscale)` frames; the slots are sized by it and the tap
+    tables of the frame size are built once, kept with the slots and dropped with them on a change of size."""
+
+    def __init__(self, model, depth: int = 2, outscale: Optional[float] = None) -> None:
         if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
             raise ValueError(f"FrameStream: depth must be an int >= 1, got {depth!r}")
+        self.outscale = check_outscale(outscale, getattr(model, "upscale_factor", 0), "FrameStream")
+        self._plan = None
         param = next(iter(model.parameters()), None)
         if param is None or not param.is_cuda:
             raise RuntimeError("FrameStream: the model must be on the MI355X device (model.cuda()); this package has no CPU path")
@@ -139,8 +193,13 @@ class FrameStream:
             for st in (self._up, self._compute, self._down):
                 st.synchronize()
         s = self.model.upscale_factor
+        self._plan = None
+        if self.outscale is not None:
+            from .imgproc import ResizePlan
+            self._plan = ResizePlan(h * s, w * s, self.outscale / s, self.device)
+        out_h, out_w = output_size(h, w, s, self.outscale)
         with torch.cuda.device(self.device):
-            self._slots = [_Slot(h, w, s, self.device) for _ in range(self.depth)]
+            self._slots = [_Slot(h, w, out_h, out_w, self.device) for _ in range(self.depth)]
         self._shape, self._next = (h, w), 0
 
     def submit(self, frame: np.ndarray) -> None:
@@ -161,7 +220,7 @@ class FrameStream:
             slot.uploaded.record(self._up)
         with torch.cuda.stream(self._compute):
             self._compute.wait_event(slot.uploaded)
-            slot.dev_out = upscale_u8(self.model, slot.dev_in)
+            slot.dev_out = upscale_u8(self.model, slot.dev_in, outscale=self.outscale, plan=self._plan)
             slot.computed.record(self._compute)
         with torch.cuda.stream(self._down):
             self._down.wait_event(slot.computed)

@@ -20,7 +20,7 @@ from . import _lib
 
 __all__ = ["random_add_gaussian_noise_torch", "random_add_poisson_noise_torch", "random_mixed_kernels",
            "generate_sinc_kernel", "image_to_tensor", "tensor_to_image", "random_crop", "filter2d_torch",
-           "interpolate", "filter2d_u8", "interpolate_u8", "jpeg_u8", "quantize_kernel_q14", "resize_tap_tables", "DiffJPEG", "USMSharp", "image_resize", "center_crop", "random_rotate",
+           "interpolate", "filter2d_u8", "interpolate_u8", "jpeg_u8", "quantize_kernel_q14", "resize_tap_tables", "DiffJPEG", "USMSharp", "image_resize", "image_resize_native", "resize_band_tables", "ResizePlan", "center_crop", "random_rotate",
            "random_horizontally_flip", "random_vertically_flip", "rgb2ycbcr_torch", "read_image_rgb"]
 
 _MODES = {"area": 0, "bilinear": 1, "bicubic": 2}
@@ -473,10 +473,10 @@ def _cubic_kernel(x: np.ndarray) -> np.ndarray:
     return ((1.5 * ax3 - 2.5 * ax2 + 1) * (ax <= 1) + (-0.5 * ax3 + 2.5 * ax2 - 4 * ax + 2) * ((ax > 1) & (ax <= 2))).astype(x.dtype)
 
 
-def _resize_matrix(in_length: int, out_length: int, scale: float, antialiasing: bool, dtype=np.float32) -> np.ndarray:
-    """[out_length, in_length] matrix of the 1-D MATLAB `imresize` bicubic pass, symmetric edge replication folded in
-    (reference imgproc.py:93-167 builds the same weights/indices in float32 and applies them row by row; NIQE's
-    half-size pass, image_quality_assessment.py:520-591, is the same construction in float64)."""
+def _resize_taps(in_length: int, out_length: int, scale: float, antialiasing: bool, dtype=np.float32) -> Tuple[np.ndarray, np.ndarray]:
+    """The taps of the 1-D MATLAB `imresize` bicubic pass in `dtype` arithmetic (reference imgproc.py:93-150): (idx [out, P] int64,
+    1-based input positions BEFORE the symmetric reflection, w [out, P] normalised weights), P = ceil(kernel_width) + 2.
+    Shared by `_resize_matrix` (dense) and `resize_band_tables` (banded, for csrc/image_resize.hip)."""
     kernel_width = 4.0
     aa = scale < 1 and antialiasing
     if aa:
@@ -490,12 +490,59 @@ def _resize_matrix(in_length: int, out_length: int, scale: float, antialiasing: 
     dist = (u[:, None] - idx).astype(f)
     w = f(scale) * _cubic_kernel(dist * f(scale)) if aa else _cubic_kernel(dist)
     w = (w / w.sum(1, keepdims=True)).astype(f)
-    idx = idx.astype(np.int64)
+    return idx.astype(np.int64), w
+
+
+def _reflect_symmetric(idx: np.ndarray, in_length: int) -> np.ndarray:
     idx = np.where(idx < 1, 1 - idx, idx)                                     # symmetric: 0 -> 1, -1 -> 2, ...
-    idx = np.where(idx > in_length, 2 * in_length + 1 - idx, idx)             # n+1 -> n, n+2 -> n-1, ...
-    m = np.zeros((out_length, in_length), dtype=f)
+    return np.where(idx > in_length, 2 * in_length + 1 - idx, idx)            # n+1 -> n, n+2 -> n-1, ...
+
+
+def _resize_matrix(in_length: int, out_length: int, scale: float, antialiasing: bool, dtype=np.float32) -> np.ndarray:
+    """[out_length, in_length] matrix of the 1-D MATLAB `imresize` bicubic pass, symmetric edge replication folded in
+    (reference imgproc.py:93-167 builds the same weights/indices in float32 and applies them row by row; NIQE's
+    half-size pass, image_quality_assessment.py:520-591, is the same construction in float64)."""
+    idx, w = _resize_taps(in_length, out_length, scale, antialiasing, dtype)
+    p = idx.shape[1]
+    idx = _reflect_symmetric(idx, in_length)
+    m = np.zeros((out_length, in_length), dtype=dtype)
     np.add.at(m, (np.repeat(np.arange(out_length), p), (idx - 1).reshape(-1)), w.reshape(-1))
     return m
+
+
+def resize_band_tables(in_length: int, out_length: int, scale: float, antialiasing: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """The non-zero band of `_resize_matrix(in_length, out_length, scale, antialiasing)` as the tap tables of
+    csrc/image_resize.hip: (idx [out, P] int32, 0-based, the symmetric reflection folded in; w [out, P] float32),
+    P = ceil(4 / min(scale, 1)) + 2.  Scattered back (`m[i, idx[i, k]] += w[i, k]`, k ascending) they give that matrix exactly.
+
+    Raises ValueError where the reference's `image_resize` raises: an axis shorter than the symmetric copy its taps reach for
+    (`sym_len_s` or `sym_len_e` of its `_calculate_weights_indices`, imgproc.py:152-167, larger than the axis)."""
+    if isinstance(in_length, bool) or isinstance(out_length, bool) or int(in_length) < 1 or int(out_length) < 1:
+        raise ValueError(f"resize_band_tables: lengths must be positive ints, got {in_length!r}, {out_length!r}")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale) or scale <= 0:
+        raise ValueError(f"resize_band_tables: scale must be a finite positive number, got {scale!r}")
+    idx, w = _resize_taps(in_length, out_length, scale, antialiasing, np.float32)
+    # the columns the reference keeps (it drops the outer pair when any weight of column 0 is zero, then looks at the last
+    # column once more) decide how many rows / columns it copies symmetrically at either end
+    kept = idx
+    p = idx.shape[1]
+    wk = w
+    if p > 2 and np.count_nonzero(wk[:, 0] == 0) != 0:
+        kept, wk = kept[:, 1:p - 1], wk[:, 1:p - 1]
+    if np.count_nonzero(wk[:, -1] == 0) != 0:
+        kept = kept[:, :p - 2]
+    sym_len_s, sym_len_e = int(1 - kept.min()), int(kept.max() - in_length)
+    if in_length == 1:            # (the reference broadcasts a one-pixel axis into its symmetric copies: every tap reads that pixel)
+        return np.zeros(idx.shape, np.int32), np.ascontiguousarray(w.astype(np.float32))
+    if sym_len_s > in_length or sym_len_e > in_length:
+        raise ValueError(f"resize_band_tables: an axis of {in_length} pixels is shorter than the symmetric copy of {max(sym_len_s, sym_len_e)} "
+                         f"pixels that scale {scale} needs (the reference's image_resize raises here too)")
+    idx = _reflect_symmetric(idx, in_length) - 1
+    # taps outside the kept columns carry zero weight; where one reflection leaves them outside the axis they are pinned to it
+    idx = np.where(w == 0, np.clip(idx, 0, in_length - 1), idx)
+    if idx.min() < 0 or idx.max() >= in_length:
+        raise ValueError(f"resize_band_tables: taps of scale {scale} leave an axis of {in_length} pixels")
+    return np.ascontiguousarray(idx.astype(np.int32)), np.ascontiguousarray(w.astype(np.float32))
 
 
 def image_resize(image: Any, scale_factor: float, antialiasing: bool = True) -> Any:
@@ -518,6 +565,70 @@ def image_resize(image: Any, scale_factor: float, antialiasing: bool = True) -> 
         out = out.squeeze(-1) if squeeze else out
         return out.numpy()
     return out.squeeze(0) if squeeze else out
+
+
+class ResizePlan:
+    """The four tap tables of one resize (in_h x in_w -> ceil(in * scale) per axis) on `device`, as csrc/image_resize.hip reads
+    them.  Building it raises ValueError where the reference's `image_resize` raises (`resize_band_tables`); nothing is launched."""
+
+    def __init__(self, in_h: int, in_w: int, scale_factor: float, device, antialiasing: bool = True) -> None:
+        if isinstance(scale_factor, bool) or not isinstance(scale_factor, (int, float)) or not math.isfinite(scale_factor) or scale_factor <= 0:
+            raise ValueError(f"ResizePlan: scale_factor must be a finite positive number, got {scale_factor!r}")
+        self.in_h, self.in_w, self.scale_factor = int(in_h), int(in_w), float(scale_factor)
+        self.out_h, self.out_w = math.ceil(in_h * scale_factor), math.ceil(in_w * scale_factor)
+        iy, wy = resize_band_tables(in_h, self.out_h, scale_factor, antialiasing)
+        ix, wx = resize_band_tables(in_w, self.out_w, scale_factor, antialiasing)
+        self.taps_y, self.taps_x = iy.shape[1], ix.shape[1]
+        self.idx_y, self.w_y, self.idx_x, self.w_x = (torch.from_numpy(a).to(device) for a in (iy, wy, ix, wx))
+
+    def check(self, what: str) -> None:
+        """The lengths the C entries take on trust: out * taps entries per table, of the right type, contiguous."""
+        for t, n, dt in ((self.idx_y, self.out_h * self.taps_y, torch.int32), (self.w_y, self.out_h * self.taps_y, torch.float32),
+                         (self.idx_x, self.out_w * self.taps_x, torch.int32), (self.w_x, self.out_w * self.taps_x, torch.float32)):
+            if t.dtype != dt or t.numel() != n or not t.is_contiguous():
+                raise ValueError(f"{what}: a tap table of {t.numel()} {t.dtype} entries where {n} {dt} are due "
+                                 f"(out {self.out_h}x{self.out_w}, taps {self.taps_y}, {self.taps_x})")
+
+    def args(self):
+        """(oh, ow, idx_y, w_y, taps_y, idx_x, w_x, taps_x) as the C entries take them."""
+        return (self.out_h, self.out_w, _lib.ptr(self.idx_y), _lib.ptr(self.w_y), self.taps_y, _lib.ptr(self.idx_x), _lib.ptr(self.w_x),
+                self.taps_x)
+
+
+@torch.no_grad()
+def resize_with_plan(x: torch.Tensor, plan: ResizePlan, u8: bool = False) -> torch.Tensor:
+    """`resr_image_resize`: fp32 [N,C,H,W] on the device -> fp32 [N,C,oh,ow], or (u8) uint8 [N,oh,ow,3] quantised as
+    `tensor_to_image` does (C = 3)."""
+    _lib.require_cuda(x, "image_resize_native")
+    if x.dim() != 4 or x.dtype != torch.float32 or min(x.shape) < 1:
+        raise RuntimeError(f"image_resize_native: expected an fp32 [N,C,H,W] tensor, got {x.dtype} {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    if (h, w) != (plan.in_h, plan.in_w):
+        raise ValueError(f"image_resize_native: a plan for {plan.in_h}x{plan.in_w} inputs, got {h}x{w}")
+    if u8 and c != 3:
+        raise ValueError(f"image_resize_native: uint8 output wants 3 channels, got {c}")
+    if plan.idx_y.device != x.device:
+        raise ValueError(f"image_resize_native: tables on {plan.idx_y.device}, input on {x.device}")
+    plan.check("image_resize_native")
+    x = x.contiguous()
+    oh, ow = plan.out_h, plan.out_w
+    y = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=x.device) if u8 else torch.empty((n, c, oh, ow), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().resr_image_resize(_lib.ptr(x), _lib.ptr(y), n, c, h, w, *plan.args(), 1 if u8 else 0, _lib.stream_ptr(x)),
+               "resr_image_resize")
+    return y
+
+
+def image_resize_native(tensor: torch.Tensor, scale_factor: float, antialiasing: bool = True, u8: bool = False) -> torch.Tensor:
+    """`image_resize` for a batch on the device, as one HIP kernel (csrc/image_resize.hip): fp32 [N,C,H,W] -> fp32
+    [N,C,ceil(H*scale),ceil(W*scale)], the reference's MATLAB-style bicubic (antialiased when shrinking, symmetric edges) by
+    banded tap tables, fp32 fused multiply-adds in tap order.  `u8=True` (C = 3): uint8 [N,oh,ow,3], `* 255`, clamp, truncate.
+    Raises ValueError, before any launch, where the reference raises (an axis shorter than the symmetric copy it needs).
+    `image_resize` itself keeps its two dense matmuls (dataset.py, NIQE)."""
+    _lib.require_cuda(tensor, "image_resize_native")
+    if tensor.dim() != 4:
+        raise RuntimeError(f"image_resize_native: expected an fp32 [N,C,H,W] tensor, got {tensor.dtype} {tuple(tensor.shape)}")
+    plan = ResizePlan(tensor.shape[2], tensor.shape[3], scale_factor, tensor.device, antialiasing)
+    return resize_with_plan(tensor, plan, u8)
 
 
 def center_crop(image: np.ndarray, image_size: int) -> np.ndarray:

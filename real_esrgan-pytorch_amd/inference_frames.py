@@ -1,12 +1,13 @@
 """Directory super-resolution on the uint8 frame path (frames.py): every image of a folder, pipelined.
 
     python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
-        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2]
+        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2]
 
 The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
 walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
 encode under the same file name in `--output_dir`.  Each written image equals what `inference.py` writes for that file on its
-own.  Frames of different sizes may be mixed (a change of size drains the pipeline).  Video containers are not read here: extract
+own.  `--outscale F` (default: the model's factor) writes `frames.output_size` images instead: the model's output resized by
+F / factor with the reference's antialiased bicubic `image_resize`, on the device (frames.py, OUTSCALE).  Frames of different sizes may be mixed (a change of size drains the pipeline).  Video containers are not read here: extract
 frames first (ffmpeg -i in.mp4 lr/%06d.png), as upstream's inference_realesrgan_video.py does internally.
 """
 import argparse
@@ -60,7 +61,7 @@ def main(args) -> None:
         for name in names:
             yield np.asarray(Image.open(os.path.join(args.inputs_dir, name)).convert("RGB"))
 
-    with FrameStream(model, depth=getattr(args, "depth", 2) or 2) as stream:
+    with FrameStream(model, depth=getattr(args, "depth", 2) or 2, outscale=getattr(args, "outscale", None)) as stream:
         # copy=False: the pinned view is encoded before the next result is asked for, i.e. before its slot is submitted to again
         for name, sr_image in zip(names, stream.map(decode(), copy=False)):
             Image.fromarray(sr_image).save(os.path.join(args.output_dir, name))
@@ -79,6 +80,8 @@ def get_parser() -> argparse.ArgumentParser:
     parser.add_argument("--num_conv", type=int, default=16, help="compact: body convs (16 animevideov3, 32 general-x4v3)")
     parser.add_argument("--act_type", type=str, default="prelu", choices=["prelu", "leakyrelu", "relu"], help="compact: activation")
     parser.add_argument("--depth", type=int, default=2, help="frames in flight (FrameStream)")
+    parser.add_argument("--outscale", type=float, default=None,
+                        help="final upscaling factor (default: the model's own); e.g. 2 writes 2x images from the x4 model")
     return parser
 
 

@@ -11,6 +11,15 @@ Wall clock around a loop of frames that ends with every result on the host, afte
 one `summary` line per case with the ratios and whether each exceeds the spread of the alternated repeats.
 
     python tools/bench_frames.py [--rounds 3] [--frames 6] [--out profiles/frames_bench_1080p.jsonl]
+
+`--outscale O` measures the outscale path instead (frames.py, OUTSCALE), alternated the same way, per case:
+  dev/forward_u8            the x4 call (untouched by outscale: the parent's launches)
+  dev/forward_u8_outscale   model.forward_u8(frame, outscale=O): the fused tail (resr_compact_forward_u8_scaled)
+  dev/unfused_outscale      model(frame fp32) -> resr_image_resize with uint8 output: the same result without the fusion
+  B2/2, B2/2/view           FrameStream(depth=2) at x4, copy=True / copy=False
+  B2/2/outscale, .../view   FrameStream(depth=2, outscale=O), copy=True / copy=False
+
+    python tools/bench_frames.py --outscale 2 --out profiles/frames_outscale_1080p.jsonl
 """
 import argparse
 import json
@@ -64,14 +73,80 @@ def device_ms(fn, steps):
     return start.elapsed_time(end) / steps
 
 
+def main_outscale(args):
+    o = args.outscale
+    torch.cuda.set_device(0)
+    box = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]}
+    rs = np.random.RandomState(0)
+    pool = [rs.randint(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(4)]
+    many = [pool[i % 4] for i in range(args.frames * 4)]
+    oh, ow = R.output_size(H, W, S, o)
+    lines = []
+    for num_conv in (16, 32):
+        for precision in ("fast", "exact16"):
+            torch.manual_seed(0)
+            model = R.SRVGGNetCompact(num_conv=num_conv, upscale=S, precision=precision).cuda().eval().requires_grad_(False)
+            x4, scaled = R.FrameStream(model, depth=2), R.FrameStream(model, depth=2, outscale=o)
+            x_u8 = torch.from_numpy(pool[0])[None].cuda()
+            x_f32 = R.from_u8(x_u8)
+            plan = imgproc.ResizePlan(H * S, W * S, o / S, x_u8.device)
+            dev = {"dev/forward_u8": lambda: model.forward_u8(x_u8),
+                   "dev/forward_u8_outscale": lambda: model.forward_u8(x_u8, outscale=o, plan=plan),
+                   "dev/unfused_outscale": lambda: imgproc.resize_with_plan(model(x_f32), plan, u8=True)}
+            paths = {"B2/2": (lambda fr: sum(1 for _ in x4.map(fr)), OUT_U8),
+                     "B2/2/view": (lambda fr: sum(1 for _ in x4.map(fr, copy=False)), OUT_U8),
+                     "B2/2/outscale": (lambda fr: sum(1 for _ in scaled.map(fr)), oh * ow * 3),
+                     "B2/2/outscale/view": (lambda fr: sum(1 for _ in scaled.map(fr, copy=False)), oh * ow * 3)}
+            with torch.no_grad():
+                same = bool(torch.equal(dev["dev/forward_u8_outscale"](), dev["dev/unfused_outscale"]()))
+                for fn in dev.values():
+                    for _ in range(3):
+                        fn()
+            for run, _ in paths.values():
+                run(many[:2])
+            ms = {name: [] for name in list(dev) + list(paths)}
+            for _ in range(args.rounds):
+                with torch.no_grad():
+                    for name, fn in dev.items():
+                        ms[name].append(device_ms(fn, args.device_steps))
+                for name, (run, _) in paths.items():
+                    ms[name].append(wall_ms(run, many))
+            case = dict(tool="bench_frames", outscale=o, num_conv=num_conv, precision=precision, frame=f"{W}x{H}->{ow}x{oh}", **box)
+            med = {name: statistics.median(v) for name, v in ms.items()}
+            for name, v in ms.items():
+                extra = dict(d2h_bytes_per_frame=paths[name][1]) if name in paths else dict(steps=args.device_steps)
+                line = dict(case, path=name, ms_per_frame_rounds=[round(x, 3) for x in v], ms_per_frame=round(med[name], 3),
+                            spread_ms=round(max(v) - min(v), 3), frames_per_s=round(1e3 / med[name], 2), **extra)
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+            line = dict(case, path="summary", fused_equals_unfused=same,
+                        fused_over_x4_device=round(med["dev/forward_u8_outscale"] / med["dev/forward_u8"], 3),
+                        fused_over_unfused_device=round(med["dev/forward_u8_outscale"] / med["dev/unfused_outscale"], 3),
+                        stream_outscale_over_x4_frames_per_s=round(med["B2/2"] / med["B2/2/outscale"], 2),
+                        stream_view_outscale_over_x4_frames_per_s=round(med["B2/2/view"] / med["B2/2/outscale/view"], 2))
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            x4.close()
+            scaled.close()
+            del model, x4, scaled, dev, paths
+            torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--frames", type=int, default=6, help="frames per timed loop of path A and B1 (the streams take 4x as many)")
     ap.add_argument("--device-steps", type=int, default=20)
     ap.add_argument("--out", default=None, help="also append the lines to this file")
+    ap.add_argument("--outscale", type=float, default=None, help="measure the outscale path at this final factor instead (see above)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_frames.py measures on the GPU"
+    if args.outscale is not None:
+        return main_outscale(args)
     torch.cuda.set_device(0)
     box = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]}
     rs = np.random.RandomState(0)
