@@ -260,6 +260,18 @@ typedef struct {
     int32_t x2_plan;
     int32_t reserved_;
 } ResrGeneratorDesc;
+/* Prerequisites of the x2_plan bits.  With dtype RESR_F16X2 a plan that breaks one is refused by every call that takes the descriptor,
+ * whatever `training` says: the size queries return 0, resr_generator_forward / _backward / _pack_table / _buffer_offsets RESR_ERR_ARG, and
+ * resr_last_error() names the rule.  Other dtypes ignore the field.
+ *      bit                                needs
+ *      GROWTH_GRAD_STORE_F16 (4)          GROWTH_GRAD_F16 (2)
+ *      GROWTH_ACT_G_HI_WGRAD (16)         GROWTH_ACT_F16_WGRAD (8)
+ *      GROWTH_W16_INFER (32)              GROWTH_F16_INFER (1)
+ *      MX_INFER (64)                      1 + 32
+ *      MX_WGRAD (512)                     MX_BWD (128) + GROWTH_ACT_F16_WGRAD (8)
+ *      MX_TAIL (1024)                     512 + 128 + 8
+ *      MX_TRAIN_FORWARD (2048)            1 + 32 + 64 + F16_BACKWARD (256)
+ * MX_BWD (128) excludes GROWTH_GRAD_STORE_F16 (4); bits at or above 4096 are refused. */
 enum {
     /* inference forward (training = 0) only: the growth planes o1..o4 of every dense block are single f16 tensors, the residual
      * stream and the HR tail stay pairs, weights stay split: 50 instead of 60 stages per block (forward 1e-6 at the reference's
@@ -305,7 +317,7 @@ enum {
      * mode's gradient error is its own forward's mask flips, not its backward pass's roundings (emulation: median 4-6e-3 -> 5-7e-4 under the
      * L1 loss): a third operating point between fast and exact16.  Overrides the other backward bits. */
     RESR_X2_PLAN_F16_BACKWARD = 256,
-    /* with MX_BWD: the weight gradients of the dense blocks take the two 2^-12-weighted tap-products (x_hi, g_lo) + (x_lo, g_hi) of every
+    /* with MX_BWD + GROWTH_ACT_F16_WGRAD (the stream chunks are then the pair chunks): the weight gradients of the dense blocks take the two 2^-12-weighted tap-products (x_hi, g_lo) + (x_lo, g_hi) of every
      * STREAM chunk as ONE MX job -- K is pixels there: 8-bit transpose reads (ds_read_b64_tr_b8) of the staged q records feed one
      * v_mfma_scale_f32_32x32x64_f8f6f4 per output row and tap, block 0 = (g_lo, x_hi), block 1 = (g_hi, x_lo) -- half the staged bytes
      * and half the matrix time of the two f16 tap-products, and conv1..conv4 get their (x_hi, g_lo) term back (GROWTH_GRAD_F16 drops it).
@@ -325,7 +337,7 @@ enum {
      * (from the fp32 value the stored output is rounded from), and F16_BACKWARD's pass runs behind it on the hi tensors and the sign
      * words.  The training forward is bit-identical to an inference forward of plan 97 (output 0.9-1.1e-4 of the fp32 oracle, gate
      * 2e-4); the gradients are in fast mode's class (a fifth of its distance from the all-pairs plan: the MX forward's mask flips).
-     * The workspace grows by the q tensors, the packed buffer holds its MX region.  Without its four prerequisites resr_generator_forward / _backward return RESR_ERR_ARG and resr_generator_workspace_bytes 0. */
+     * The workspace grows by the q tensors, the packed buffer holds its MX region. */
     RESR_X2_PLAN_MX_TRAIN_FORWARD = 2048
 };
 

@@ -31,6 +31,49 @@ X2_PLAN_MX_TRAIN_FORWARD = 2048
 # the named "output parity" training plan: bits 0 + 5 + 6 (the inference MX forward) + 8 (f16 backward) + 11 (MX_TRAIN_FORWARD)
 X2_PLAN_OUTPUT_PARITY = (X2_PLAN_GROWTH_F16_INFER | X2_PLAN_GROWTH_W16_INFER | X2_PLAN_MX_INFER | X2_PLAN_F16_BACKWARD
                          | X2_PLAN_MX_TRAIN_FORWARD)   # 2401
+# The prerequisite rules of the plan bits, (bit, the bits it needs, text): the table of include/resr.h, which the library checks itself
+# (csrc/generator.hip resolve_x2_plan).  A bit that only refines another one means nothing without it: refused, not silently ignored.
+X2_PLAN_RULES = (
+    (4, 2, "GROWTH_GRAD_STORE_F16 (4) refines GROWTH_GRAD_F16 (2)"),
+    (16, 8, "GROWTH_ACT_G_HI_WGRAD (16) refines GROWTH_ACT_F16_WGRAD (8)"),
+    (32, 1, "GROWTH_W16_INFER (32) refines GROWTH_F16_INFER (1)"),
+    (64, 1 + 32, "MX_INFER (64) rides on GROWTH_F16_INFER (1) + GROWTH_W16_INFER (32)"),
+    (512, 128 + 8, "MX_WGRAD (512) rides on MX_BWD (128: the gradient planes' q tensors) + GROWTH_ACT_F16_WGRAD (8: the stream chunks are the pair chunks)"),
+    (1024, 512 + 128 + 8, "MX_TAIL (1024) extends MX_WGRAD (512) to the 4x-resolution tail"),
+    (2048, 1 + 32 + 64 + 256, "MX_TRAIN_FORWARD (2048) runs the inference MX forward (1 + 32 + 64) in training, in front of the f16 backward pass (256)"),
+)
+
+
+def x2_plan_error(plan: int):
+    """None for a plan the library accepts (with RESR_F16X2), else the text of the first rule it breaks."""
+    if not 0 <= plan <= 4095:
+        return ("x2_plan must be a bit set of X2_PLAN_GROWTH_F16_INFER (1) | X2_PLAN_GROWTH_GRAD_F16 (2) | X2_PLAN_GROWTH_GRAD_STORE_F16 (4) | "
+                "X2_PLAN_GROWTH_ACT_F16_WGRAD (8) | X2_PLAN_GROWTH_ACT_G_HI_WGRAD (16) | X2_PLAN_GROWTH_W16_INFER (32) | X2_PLAN_MX_INFER (64) | "
+                f"X2_PLAN_MX_BWD (128) | X2_PLAN_F16_BACKWARD (256) | X2_PLAN_MX_WGRAD (512) | X2_PLAN_MX_TAIL (1024) | X2_PLAN_MX_TRAIN_FORWARD (2048), got {plan}")
+    if (plan & X2_PLAN_MX_BWD) and (plan & X2_PLAN_GROWTH_GRAD_STORE_F16):
+        return f"x2_plan={plan}: MX_BWD (128) reads the growth-plane gradients as pairs; GROWTH_GRAD_STORE_F16 (4) stores them single"
+    for bit, needs, text in X2_PLAN_RULES:
+        if (plan & bit) and (plan & needs) != needs:
+            return f"x2_plan={plan}: {text}"
+    return None
+
+
+# What the module itself has to know about a valid exact16 plan (everything else is the library's business):
+def x2_plan_f16_backward(plan: int) -> bool:
+    """The backward pass takes a RESR_F16 packing of the weight table."""
+    return bool(plan & X2_PLAN_F16_BACKWARD)
+
+
+def x2_plan_packs_mx(plan: int, training: bool) -> bool:
+    """A pass of this descriptor reads the MX region of the packed buffer (resr_pack_weights_mx fills it)."""
+    return bool(plan & ((X2_PLAN_MX_BWD | X2_PLAN_MX_TRAIN_FORWARD) if training else X2_PLAN_MX_INFER))
+
+
+def x2_plan_layout_key(plan: int) -> int:
+    """The bits that size a workspace (the q tensors of the MX plans): workspaces of plans with equal keys are interchangeable."""
+    return plan & (X2_PLAN_MX_INFER | X2_PLAN_MX_BWD | X2_PLAN_MX_WGRAD | X2_PLAN_MX_TAIL | X2_PLAN_MX_TRAIN_FORWARD)
+
+
 CONV_MX_PAIRS = 1 << 12
 CONV_MX_SIGNBITS = 1 << 13
 RESR_VERSION = 3   # include/resr.h: the structures below mirror THIS version of the header

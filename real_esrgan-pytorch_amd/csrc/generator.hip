@@ -3,9 +3,7 @@
 //
 // RESR_F16X2 ("exact16"): every activation / gradient tensor below is a (hi, lo) pair of f16 tensors -- the lo tensor
 // directly follows the hi tensor of the same buffer -- and packed weights take three blocks per chunk (include/resr.h).
-// ResrGeneratorDesc.x2_plan (RESR_X2_PLAN_*) turns the dense blocks' growth planes (inference forward) / their gradients
-// (backward) into single f16 tensors: their chunks then take two stages instead of three and conv1..conv4's weight gradients
-// two tap-products instead of three; the lo halves of those planes stay allocated and unused.
+// ResrGeneratorDesc.x2_plan (RESR_X2_PLAN_*; struct X2Plan below) reads some of them as single f16 tensors or through MX stages; unused lo halves stay allocated.
 // HBM plan (T = f16 fast / f32 strict, all tensors pixel-major / NHWC):
 //   x_in              [N,h,w,CI]      input image, pixel-unshuffled, channels padded to 32/64
 //   ws[r], r=0..3B-1  [6][N,h,w,32]   one dense-block workspace per RDB, chunk-planar: planes [x0 x1 | o1 | o2 | o3 | o4]
@@ -47,10 +45,7 @@ int wgrad_batch_jobs(const WgradConv*, int, int);
 int wgrad_batch_quads(const WgradConv*, int, int);
 int wgrad_tile_rows(int dtype);
 int wgrad_x2_products();
-int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
-int nhwc_to_nchw_dispatch(const void*, float*, int, int, int, int, int, int, int, hipStream_t, long);
 int absmax_dispatch(const float*, long, unsigned*, int, hipStream_t);
-int nchw_to_nhwc_scaled_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long, const unsigned*);
 int nchw_to_nhwc_q_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long, const unsigned*, long);
 int nhwc_to_nchw_scaled_dispatch(const void*, float*, int, int, int, int, int, int, int, hipStream_t, long, const unsigned*);
 int sumpool2x2_dispatch(const void*, void*, const void*, int, int, int, int, int, float, hipStream_t, long, long);
@@ -64,8 +59,28 @@ struct ConvSpec {
     size_t pk_fwd, pk_bwd;    // element offsets in the packed buffer (bwd: first pass of this conv)
 };
 
+// ResrGeneratorDesc.x2_plan (RESR_X2_PLAN_*, include/resr.h) validated and resolved once by resolve_x2_plan(): one named answer per question the layout or a pass asks, all
+// false / 0 outside RESR_F16X2.  A buffer "carries a q tensor": behind its hi and lo tensors lies the bf8 of both (2 bytes per element) for an MX stage or MX weight-gradient job.
+struct X2Plan {
+    bool mx_train;        // forward: a TRAINING forward on the inference MX plan, sign words from the MX epilogues (RESR_CONV_MX_SIGNBITS)
+    bool mx;              // forward: the pair chunks take one f16 + one MX stage (MX inference, or mx_train); EVERY activation buffer carries a q tensor
+    bool growth_single, growth_w16;   // forward: o1..o4 are stored single f16 and read as two-stage chunks / as one stage, against f16 weights (inference, or mx_train: any
+                                      // other training forward keeps every pre-activation fp32-class -- a rounded input flips LeakyReLU masks)
+    bool f16_backward;    // backward: fast mode's pass on the hi tensors behind the exact16 forward; every other backward answer is then off
+    bool mx_bwd;          // the dense blocks' backward-data passes read every gradient chunk on one f16 + one MX stage
+    bool mx_wgrad;        // the dense blocks' weight gradients take the stream chunks' corrections as MX jobs: planes 0, 1 of every ws[] carry a q tensor, written by the training forward
+    bool mx_tail;         // conv3, conv4, upsampling2 the same way: u1, u2, c3 and the tail gradients g4, gA, gB carry q tensors
+    bool gg_single;       // the growth-plane gradients g_o1..g_o4 are READ as single f16 tensors; still stored as pairs, for the bias sums (hi + lo: include/resr.h)
+    bool gg_store_single; // ... and stored single too (no lo store, biases from hi alone)
+    int wx_pairs;         // 2: the weight products read the growth planes (X chunks 2..) as their hi tensor; 0: every chunk a pair
+    bool x_single_g_hi;   // ... and conv5's products of the growth planes take g_y's hi tensor alone as well
+    bool grad_q;          // LAYOUT only: gT / gS carry q tensors.  NOT mx_bwd: under MX_BWD | F16_BACKWARD the planes keep the room although the f16 pass never touches it (on purpose: workspace sizes and offsets are part of the surface)
+    bool packed_mx;       // LAYOUT only: the packed buffer holds an MX region behind its f16 blocks, whatever `training` says
+};
+
 struct Plan {
     ResrGeneratorDesc d;
+    X2Plan x2;    // d.x2_plan, validated and resolved: nothing below build_plan() looks at the bits again
     int r;        // pixel-unshuffle factor
     int h, w;     // trunk resolution
     int ci_real, ci_pad;
@@ -82,48 +97,58 @@ struct Plan {
 
 int round32(int v) { return (v + 31) / 32 * 32; }
 
-// RESR_X2_PLAN_MX_INFER: an exact16 INFERENCE forward whose pair chunks take one f16 stage + one MX stage (RESR_CONV_MX_PAIRS).  Rides
-// on the single-f16 growth planes against f16 weights (bits 0 + 5): every activation buffer then holds THREE tensors -- hi, lo and the
-// q tensor (bf8 of both, 2 bytes per element) -- and the packed weights an MX region behind the f16 blocks (generator_mx_offset).
-// RESR_X2_PLAN_MX_BWD: the trunk's backward-data passes on MX stages; the gradient planes gT / gS carry q tensors.
-bool plan_mx_bwd(const ResrGeneratorDesc& d) {
-    return d.dtype == RESR_F16X2 && d.training && (d.x2_plan & RESR_X2_PLAN_MX_BWD) && !(d.x2_plan & RESR_X2_PLAN_GROWTH_GRAD_STORE_F16);
-}
-// RESR_X2_PLAN_MX_WGRAD: the stream chunks' correction tap-products of the dense blocks' weight gradients as MX jobs; the residual stream
-// (planes 0, 1 of every dense-block workspace) carries a q tensor written by the training forward
-bool plan_mx_wgrad(const ResrGeneratorDesc& d) {
-    return plan_mx_bwd(d) && (d.x2_plan & RESR_X2_PLAN_MX_WGRAD) && !(d.x2_plan & RESR_X2_PLAN_F16_BACKWARD);
-}
-// RESR_X2_PLAN_MX_TAIL: conv3, conv4, upsampling2 the same way; u1, u2, c3 and the tail's gradient tensors g4, gA, gB carry q tensors
-bool plan_mx_tail(const ResrGeneratorDesc& d) { return plan_mx_wgrad(d) && (d.x2_plan & RESR_X2_PLAN_MX_TAIL); }
-// RESR_X2_PLAN_MX_TRAIN_FORWARD: a TRAINING forward on the inference MX plan (sign words from the MX epilogues, RESR_CONV_MX_SIGNBITS),
-// followed by F16_BACKWARD's pass on the hi tensors -- the bit and its four prerequisites
-constexpr int kMxTrainNeeds = RESR_X2_PLAN_GROWTH_F16_INFER | RESR_X2_PLAN_GROWTH_W16_INFER | RESR_X2_PLAN_MX_INFER | RESR_X2_PLAN_F16_BACKWARD;
-bool plan_mx_train(const ResrGeneratorDesc& d) {
-    return d.dtype == RESR_F16X2 && d.training && (d.x2_plan & RESR_X2_PLAN_MX_TRAIN_FORWARD) && (d.x2_plan & kMxTrainNeeds) == kMxTrainNeeds;
-}
-// the bit without its prerequisites is refused (forward, backward, workspace size), not ignored
-bool plan_mx_train_ok(const ResrGeneratorDesc& d) {
-    return d.dtype != RESR_F16X2 || !(d.x2_plan & RESR_X2_PLAN_MX_TRAIN_FORWARD) || (d.x2_plan & kMxTrainNeeds) == kMxTrainNeeds;
-}
-// the forward passes run the MX plan: an inference forward of bits 0 + 5 + 6, or a training forward of RESR_X2_PLAN_MX_TRAIN_FORWARD
-bool plan_mx(const ResrGeneratorDesc& d) {
-    const int need = RESR_X2_PLAN_GROWTH_F16_INFER | RESR_X2_PLAN_GROWTH_W16_INFER | RESR_X2_PLAN_MX_INFER;
-    return (d.dtype == RESR_F16X2 && !d.training && (d.x2_plan & need) == need) || plan_mx_train(d);
+// The prerequisite rules of the plan bits, {bit, the bits it needs, text}: the table of include/resr.h (real_esrgan-pytorch_amd/_lib.py holds the same one for the module)
+constexpr struct X2Rule { int bit, needs; const char* text; } kX2Rules[] = {
+    {RESR_X2_PLAN_GROWTH_GRAD_STORE_F16, 2, "GROWTH_GRAD_STORE_F16 (4) refines GROWTH_GRAD_F16 (2)"},
+    {RESR_X2_PLAN_GROWTH_ACT_G_HI_WGRAD, 8, "GROWTH_ACT_G_HI_WGRAD (16) refines GROWTH_ACT_F16_WGRAD (8)"},
+    {RESR_X2_PLAN_GROWTH_W16_INFER, 1, "GROWTH_W16_INFER (32) refines GROWTH_F16_INFER (1)"},
+    {RESR_X2_PLAN_MX_INFER, 1 | 32, "MX_INFER (64) rides on GROWTH_F16_INFER (1) + GROWTH_W16_INFER (32)"},
+    {RESR_X2_PLAN_MX_WGRAD, 128 | 8, "MX_WGRAD (512) rides on MX_BWD (128) + GROWTH_ACT_F16_WGRAD (8)"},
+    {RESR_X2_PLAN_MX_TAIL, 512 | 128 | 8, "MX_TAIL (1024) extends MX_WGRAD (512, with its 128 + 8) to the 4x-resolution tail"},
+    {RESR_X2_PLAN_MX_TRAIN_FORWARD, 1 | 32 | 64 | 256, "MX_TRAIN_FORWARD (2048) needs bits 1 + 32 + 64 + 256"},
+};
+
+// Fills `x`, or refuses the plan with the broken rule as the error text.  Validity does not depend on `training`: one descriptor value serves both passes.
+bool resolve_x2_plan(const ResrGeneratorDesc& d, X2Plan& x) {
+    x = X2Plan{};
+    if (d.dtype != RESR_F16X2) return true;
+    const int plan = d.x2_plan, training = d.training;
+    auto has = [&](int bits) { return (plan & bits) == bits; };
+    if (plan < 0 || plan >= 4096) return fail(RESR_ERR_ARG, "generator: x2_plan=%d: not a set of the RESR_X2_PLAN_* bits (all below 4096)", plan), false;
+    if (has(RESR_X2_PLAN_MX_BWD | RESR_X2_PLAN_GROWTH_GRAD_STORE_F16)) return fail(RESR_ERR_ARG, "generator: x2_plan=%d: MX_BWD (128) reads the growth-plane gradients as pairs; GROWTH_GRAD_STORE_F16 (4) stores them single", plan), false;
+    for (const X2Rule& r : kX2Rules)
+        if (has(r.bit) && !has(r.needs)) return fail(RESR_ERR_ARG, "generator: x2_plan=%d: %s", plan, r.text), false;
+    x.mx_train = training && has(RESR_X2_PLAN_MX_TRAIN_FORWARD);
+    x.mx = x.mx_train || (!training && has(RESR_X2_PLAN_MX_INFER));
+    x.growth_single = (!training || x.mx_train) && has(RESR_X2_PLAN_GROWTH_F16_INFER);
+    x.growth_w16 = x.growth_single && has(RESR_X2_PLAN_GROWTH_W16_INFER);
+    x.f16_backward = has(RESR_X2_PLAN_F16_BACKWARD);
+    x.grad_q = training && has(RESR_X2_PLAN_MX_BWD);
+    x.mx_bwd = x.grad_q && !x.f16_backward;
+    x.mx_wgrad = x.mx_bwd && has(RESR_X2_PLAN_MX_WGRAD);
+    x.mx_tail = x.mx_wgrad && has(RESR_X2_PLAN_MX_TAIL);
+    x.gg_single = !x.f16_backward && has(RESR_X2_PLAN_GROWTH_GRAD_F16);
+    x.gg_store_single = x.gg_single && has(RESR_X2_PLAN_GROWTH_GRAD_STORE_F16);
+    x.wx_pairs = (!x.f16_backward && has(RESR_X2_PLAN_GROWTH_ACT_F16_WGRAD)) ? 2 : 0;
+    x.x_single_g_hi = x.wx_pairs && has(RESR_X2_PLAN_GROWTH_ACT_G_HI_WGRAD);
+    x.packed_mx = has(RESR_X2_PLAN_MX_INFER) || has(RESR_X2_PLAN_MX_BWD);
+    return true;
 }
 
 bool build_plan(const ResrGeneratorDesc* d, Plan& p) {
-    if (!d) return false;
-    if (d->upscale != 4 && d->upscale != 2 && d->upscale != 1) return false;
-    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->n_blocks <= 0 || d->in_channels <= 0 || d->out_channels <= 0) return false;
+    auto bad = [](const char* why) { return fail(RESR_ERR_ARG, "generator: bad descriptor (%s)", why), false; };
+    if (!d) return bad("null");
+    if (d->upscale != 4 && d->upscale != 2 && d->upscale != 1) return bad("upscale must be 1, 2 or 4");
+    if (d->n <= 0 || d->h <= 0 || d->w <= 0 || d->n_blocks <= 0 || d->in_channels <= 0 || d->out_channels <= 0) return bad("a size is not positive");
     p.d = *d;
     p.r = d->upscale == 4 ? 1 : (d->upscale == 2 ? 2 : 4);
-    if ((d->h % p.r) || (d->w % p.r)) return false;
+    if ((d->h % p.r) || (d->w % p.r)) return bad("h, w must be multiples of the pixel-unshuffle factor");
     p.h = d->h / p.r;
     p.w = d->w / p.r;
     p.ci_real = d->in_channels * p.r * p.r;
     p.ci_pad = round32(p.ci_real);
-    if (p.ci_pad > 64 || d->out_channels > 32) return false;
+    if (p.ci_pad > 64 || d->out_channels > 32) return bad("too many channels");
+    if (!resolve_x2_plan(*d, p.x2)) return false;
     p.nrdb = d->n_blocks * 3;
     size_t off = 0;
     auto add = [&](int cout, int cin) {
@@ -211,7 +236,7 @@ int splits_for(const Plan& p, int npairs, int h, int w, int nquads = 0) {
     if (p.d.wgrad_splits > 0) return p.d.wgrad_splits;
     const int th = wgrad_tile_rows(p.d.dtype);
     const long tiles = (long)((w + 31) / 32) * ((h + th - 1) / th) * p.d.n;
-    if (p.d.dtype == RESR_F16X2 && nquads > 0 && tiles >= 64 && !getenv("RESR_X2_WGRAD_OLD_SPLITS")) {
+    if (p.d.dtype == RESR_F16X2 && nquads > 0 && tiles >= 64) {
         long best_s = 8;
         double best = 1e30;
         for (long s = 8; s <= 256 && s <= tiles / 2; s += 8) {
@@ -236,7 +261,7 @@ int splits_for(const Plan& p, int npairs, int h, int w, int nquads = 0) {
 }
 
 void carve(const Plan& p, char* base, Bufs& b) {
-    const size_t es = elem_size(p.d.dtype) * (act_tensors(p.d.dtype) + (plan_mx(p.d) ? 1 : 0));   // bytes per activation element (hi + lo [+ q])
+    const size_t es = elem_size(p.d.dtype) * (act_tensors(p.d.dtype) + (p.x2.mx ? 1 : 0));   // bytes per activation element (hi + lo [+ q])
     const int wm = p.d.dtype == RESR_F16X2 ? 3 : 1;                     // weight-gradient jobs per product (upper bound: sizes the slab buffer)
     const size_t px = (size_t)p.d.n * p.h * p.w;
     size_t off = 0;
@@ -251,7 +276,7 @@ void carve(const Plan& p, char* base, Bufs& b) {
     b.x_in = take(px * p.ci_pad * es);
     const int nws = p.d.training ? p.nrdb : 3;
     b.ws.resize(nws);
-    for (int i = 0; i < nws; ++i) b.ws[i] = take(px * 192 * (es + (plan_mx_wgrad(p.d) ? 2 : 0)));   // (MX_WGRAD: hi, lo and q tensors)
+    for (int i = 0; i < nws; ++i) b.ws[i] = take(px * 192 * (es + (p.x2.mx_wgrad ? 2 : 0)));   // (mx_wgrad: hi, lo and q tensors)
     b.bits.clear();
     if (p.d.training)
         for (int i = 0; i < p.nrdb; ++i) b.bits.push_back(take(px * 4 * sizeof(uint32_t)));
@@ -261,7 +286,7 @@ void carve(const Plan& p, char* base, Bufs& b) {
     else { b.out1 = take(px * 64 * es); b.out1_stride = 64; }  // rotating workspaces overwrite ws[0]
     b.trunk_out = take(px * 64 * es);
     b.feat = take(px * 64 * es);
-    const size_t est = es + (plan_mx_tail(p.d) ? 2 : 0);   // RESR_X2_PLAN_MX_TAIL: hi, lo and q tensors
+    const size_t est = es + (p.x2.mx_tail ? 2 : 0);   // mx_tail: hi, lo and q tensors
     b.u1 = take(px * 4 * 64 * est);
     b.u2 = take(px * 16 * 64 * est);
     b.c3 = take(px * 16 * 64 * est);
@@ -272,7 +297,7 @@ void carve(const Plan& p, char* base, Bufs& b) {
         b.gB = take(px * 16 * 64 * est);
         b.gM1 = take(px * 4 * 64 * es);
         b.gF = take(px * 64 * es);
-        const size_t esg = es + (plan_mx_bwd(p.d) ? 2 : 0);   // RESR_X2_PLAN_MX_BWD: hi, lo and q tensors
+        const size_t esg = es + (p.x2.grad_q ? 2 : 0);   // hi, lo and q tensors
         for (int i = 0; i < 4; ++i) b.gT[i] = take(px * 64 * esg);
         for (int i = 0; i < 3; ++i) b.gS[i] = take(px * 128 * esg);
         b.gxin = take(px * p.ci_pad * es);
@@ -284,15 +309,15 @@ void carve(const Plan& p, char* base, Bufs& b) {
             for (int m = 1; m <= 4; m *= 2) {
                 const long tiles = (long)((p.w * m + 31) / 32) * ((p.h * m + th - 1) / th) * p.d.n;
                 const long smax = tiles / 2 < 256 ? (tiles / 2 < 1 ? 1 : tiles / 2) : 256;
-                // (a single 64 -> 64 convolution: 12 tap-products; RESR_X2_PLAN_MX_TAIL: 4 f16 jobs + 4 MX jobs whose launch takes up to 4 x the splits)
-                const size_t q = (size_t)(m == 1 ? 78 : (plan_mx_tail(p.d) ? 20 : 12)) * (size_t)smax * slab;
+                // (a single 64 -> 64 convolution: 12 tap-products; mx_tail: 4 f16 jobs + 4 MX jobs whose launch takes up to 4 x the splits)
+                const size_t q = (size_t)(m == 1 ? 78 : (p.x2.mx_tail ? 20 : 12)) * (size_t)smax * slab;
                 if (q > pb) pb = q;
             }
         }
         for (int k = 1; k <= wm; k += 2) {          // both weight-gradient settings of RESR_F16X2 (1 or 3 jobs per product)
             const size_t q0 = (size_t)26 * k * splits_for(p, 26 * k, p.h, p.w) * slab;
             if (q0 > pb) pb = q0;
-            if (k == 3) {   // RESR_X2_PLAN_GROWTH_GRAD_F16: conv1..conv4 (14 products) two tap-products each + 4 bias jobs, conv5 (12) three
+            if (k == 3) {   // gg_single: conv1..conv4 (14 products) two tap-products each + 4 bias jobs, conv5 (12) three
                 const size_t qg = (size_t)68 * splits_for(p, 68, p.h, p.w) * slab;
                 if (qg > pb) pb = qg;
             }
@@ -347,7 +372,7 @@ size_t generator_mx_offset(const ResrGeneratorDesc* d) {
 size_t generator_packed_bytes(const ResrGeneratorDesc* d, int backward) {
     Plan p;
     if (!build_plan(d, p)) return 0;
-    if (d->dtype == RESR_F16X2 && (d->x2_plan & (RESR_X2_PLAN_MX_INFER | RESR_X2_PLAN_MX_BWD | RESR_X2_PLAN_MX_WGRAD))) return generator_mx_offset(d) + p.pk_total_elems * 2 + 16384;
+    if (p.x2.packed_mx) return generator_mx_offset(d) + p.pk_total_elems * 2 + 16384;
     // + two dummy (chunk,tap) of slack: conv3x3_kernel prefetches two taps past the end
     return (backward ? p.pk_total_elems : p.pk_fwd_elems) * elem_size(d->dtype) * (d->dtype == RESR_F16X2 ? 3 : 1) + 16384;
 }
@@ -361,7 +386,6 @@ size_t generator_chain_state_bytes(const ResrGeneratorDesc* d) {
 size_t generator_workspace_bytes(const ResrGeneratorDesc* d) {
     Plan p;
     if (!build_plan(d, p)) return 0;
-    if (!plan_mx_train_ok(*d)) { (void)fail(RESR_ERR_ARG, "generator: x2_plan MX_TRAIN_FORWARD (2048) needs bits 1 + 32 + 64 + 256"); return 0; }
     Bufs b;
     carve(p, nullptr, b);
     return b.total;
@@ -370,7 +394,7 @@ size_t generator_workspace_bytes(const ResrGeneratorDesc* d) {
 // debug/test aid: byte offsets of the named workspace buffers (order documented in include/resr.h)
 int64_t generator_buffer_offsets(const ResrGeneratorDesc* d, int64_t* out, int64_t cap) {
     Plan p;
-    if (!build_plan(d, p)) return fail(RESR_ERR_ARG, "generator: bad descriptor");
+    if (!build_plan(d, p)) return RESR_ERR_ARG;
     Bufs b;
     char* base = reinterpret_cast<char*>(4096);  // fake non-null base, only differences are used
     carve(p, base, b);
@@ -386,7 +410,7 @@ int64_t generator_buffer_offsets(const ResrGeneratorDesc* d, int64_t* out, int64
 
 int64_t generator_pack_table(const ResrGeneratorDesc* d, int backward, ResrPackChunk* out, int64_t cap) {
     Plan p;
-    if (!build_plan(d, p)) return fail(RESR_ERR_ARG, "generator: bad descriptor");
+    if (!build_plan(d, p)) return RESR_ERR_ARG;
     std::vector<ResrPackChunk> t;
     auto push = [&](const ConvSpec& c, size_t dst, int m_off, int m_count, int k_off, int k_count, int mt, int tr,
                     float scale) {
@@ -470,8 +494,7 @@ static bool debug_sync() {
 int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* params, const void* packed,
                       void* workspace, size_t workspace_bytes, float* y, hipStream_t st) {
     Plan p;
-    if (!build_plan(d, p)) return fail(RESR_ERR_ARG, "generator_forward: bad descriptor");
-    if (!plan_mx_train_ok(*d)) return fail(RESR_ERR_ARG, "generator_forward: x2_plan MX_TRAIN_FORWARD (2048) needs bits 1 + 32 + 64 + 256");
+    if (!build_plan(d, p)) return RESR_ERR_ARG;
     if (!x || !params || !packed || !workspace || !y) return fail(RESR_ERR_ARG, "generator_forward: null argument");
     Bufs b;
     carve(p, (char*)workspace, b);
@@ -484,40 +507,32 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
     const int nws = (int)b.ws.size();
     if ((long)N * h * w * 32 * 16 > 0x7fffffffL) return fail(RESR_ERR_ARG, "generator: batch x resolution too large for 32-bit chunk strides");
     const int plane = N * h * w * 32;  // elements per 32-channel plane of the chunk-planar trunk tensors
-    // exact16 inference with single-f16 growth planes (RESR_X2_PLAN_GROWTH_F16_INFER): o1..o4 are stored without a lo tensor and
-    // read as two-stage chunks; a training forward keeps every pre-activation fp32-class (a rounded input flips LeakyReLU masks) --
-    // unless it runs the inference MX plan on purpose (RESR_X2_PLAN_MX_TRAIN_FORWARD: the same bits as that inference forward)
-    const bool mx_train = plan_mx_train(*d);
-    const bool growth_single = x2 && (!d->training || mx_train) && (d->x2_plan & RESR_X2_PLAN_GROWTH_F16_INFER);
-    const bool growth_w16 = growth_single && (d->x2_plan & RESR_X2_PLAN_GROWTH_W16_INFER);   // ... and meet f16 weights: one stage per growth chunk
+    const X2Plan& xp = p.x2;
     // RESR_F16X2: element offset hi -> lo of a buffer holding `planes` 32-channel planes of `pl` elements
     auto LO = [&](long planes, long pl) -> int64_t { return x2 ? planes * pl : 0; };
     const int64_t lo_ws = LO(6, plane), lo_t = LO(2, plane), lo_xin = x2 ? (int64_t)N * h * w * p.ci_pad : 0;
     const int64_t lo_out1 = b.out1 == b.ws[0] ? lo_ws : LO(2, plane);
     auto W = [&](const ConvSpec& c) { return pk + c.pk_fwd * wes; };
     auto Bias = [&](const ConvSpec& c) { return params + c.b_off; };
-    // RESR_X2_PLAN_MX_INFER: the q tensor of a buffer follows its lo tensor (element offset hi -> q = twice hi -> lo); a pass whose
+    // xp.mx: the q tensor of a buffer follows its lo tensor (element offset hi -> q = twice hi -> lo); a pass whose
     // pair chunks take the MX stage says so (in_q = its input's hi -> q offset), names its convolution's MX blocks, and emits the q
     // tensor of its own output when a later pass reads that output through an MX stage (out_q; 0: none)
-    const bool mx = plan_mx(*d);
-    const bool mxw = plan_mx_wgrad(*d);
-    const bool mxt = plan_mx_tail(*d);     // the training forward also emits the q tensors of u1, u2, c3
-    const char* pk_mx = mx ? pk + generator_mx_offset(d) : nullptr;
+    const char* pk_mx = xp.mx ? pk + generator_mx_offset(d) : nullptr;
     auto MXP = [&](ResrConvDesc& cd, const ConvSpec& c, int64_t in_q, int64_t out_q) {
-        if (!mx) return;
-        cd.flags |= RESR_CONV_MX_PAIRS | (mx_train ? RESR_CONV_MX_SIGNBITS : 0);   // (a training forward's LeakyReLU passes write sign words)
+        if (!xp.mx) return;
+        cd.flags |= RESR_CONV_MX_PAIRS | (xp.mx_train ? RESR_CONV_MX_SIGNBITS : 0);   // (a training forward's LeakyReLU passes write sign words)
         cd.in0_q_offset = in_q; cd.out_q_offset = out_q;
         cd.w_mx_offset = (int64_t)((pk_mx + c.pk_fwd * 2) - W(c));
     };
 
-    RUN(nchw_to_nhwc_q_dispatch(x, b.x_in, N, d->in_channels, d->h, d->w, p.r, p.ci_pad, d->dtype, nullptr, st, (long)lo_xin, nullptr, mx ? 2L * (long)lo_xin : 0L));
+    RUN(nchw_to_nhwc_q_dispatch(x, b.x_in, N, d->in_channels, d->h, d->w, p.r, p.ci_pad, d->dtype, nullptr, st, (long)lo_xin, nullptr, xp.mx ? 2L * (long)lo_xin : 0L));
     {   // conv1 -> ws[0][0:64]                                           model.py:259
         const ConvSpec& c = p.convs[p.i_conv1];
         ResrConvDesc cd = conv_desc(p, N, h, w, p.ci_pad, p.ci_pad, p.ci_pad, 0, 64, 64, 32, 0);
         cd.out_chunk_stride = plane;
         cd.in0_lo_offset = lo_xin; cd.out_lo_offset = lo_ws;
         MXP(cd, c, 2 * lo_xin, 2 * lo_ws);
-        if (mxw) cd.out_q_offset = 2 * lo_ws;    // training, MX_WGRAD: the stream's q tensor for the weight gradients' MX jobs (a plain three-stage pass emits it)
+        if (xp.mx_wgrad) cd.out_q_offset = 2 * lo_ws;    // training, mx_wgrad: the stream's q tensor for the weight gradients' MX jobs (a plain three-stage pass emits it)
         RUN(conv3x3_dispatch(&cd, b.x_in, nullptr, W(c), Bias(c), nullptr, nullptr, nullptr, b.ws[0], nullptr, st));
         if (b.out1 != b.ws[0]) {  // inference: second copy of out1 (0.01 % of the FLOPs) instead of a pinned workspace
             cd.out_stride = b.out1_stride; cd.out_chunk_stride = 0; cd.out_lo_offset = lo_out1;
@@ -538,7 +553,7 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
                 ResrConvDesc cd = conv_desc(p, N, h, w, c.cin, c.cin, 32, 0, 32, 32, 32, RESR_CONV_LRELU);
                 cd.in0_chunk_stride = plane;
                 cd.in0_lo_offset = lo_ws; cd.out_lo_offset = lo_ws;
-                if (growth_single) { cd.x2_pair_chunks = 2; cd.flags |= RESR_CONV_OUT_SINGLE | (growth_w16 ? RESR_CONV_SINGLE_W16 : 0); }
+                if (xp.growth_single) { cd.x2_pair_chunks = 2; cd.flags |= RESR_CONV_OUT_SINGLE | (xp.growth_w16 ? RESR_CONV_SINGLE_W16 : 0); }
                 MXP(cd, c, 2 * lo_ws, 0);
                 char* signs = nullptr;
                 if (d->training) {   // the backward pass reads the 1-bit mask, not the activation
@@ -556,9 +571,9 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
             cd.in0_chunk_stride = plane;
             cd.out_chunk_stride = plane;
             cd.in0_lo_offset = lo_ws; cd.out_lo_offset = last ? lo_t : lo_ws;
-            if (growth_single) { cd.x2_pair_chunks = 2; if (growth_w16) cd.flags |= RESR_CONV_SINGLE_W16; }
+            if (xp.growth_single) { cd.x2_pair_chunks = 2; if (xp.growth_w16) cd.flags |= RESR_CONV_SINGLE_W16; }
             MXP(cd, c, 2 * lo_ws, last ? 2 * lo_t : 2 * lo_ws);
-            if (mxw && !last) cd.out_q_offset = 2 * lo_ws;   // (the next block's stream planes; the trunk's output is no dense block's X)
+            if (xp.mx_wgrad && !last) cd.out_q_offset = 2 * lo_ws;   // (the next block's stream planes; the trunk's output is no dense block's X)
             cd.s0 = 0.2f; cd.t0 = 1.f; cd.res0_stride = 32; cd.res0_chunk_stride = plane; cd.res0_lo_offset = lo_ws;  // model.py:95-96
             const char* res1 = nullptr;
             if (r % 3 == 2) {  // model.py:129-130
@@ -585,7 +600,7 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
         cd.in0_chunk_stride = plane; cd.out_chunk_stride = 4 * plane;
         cd.in0_lo_offset = lo_t; cd.out_lo_offset = LO(2, 4L * plane);
         MXP(cd, c, 2 * lo_t, 2 * LO(2, 4L * plane));
-        if (mxt) cd.out_q_offset = 2 * LO(2, 4L * plane);
+        if (xp.mx_tail) cd.out_q_offset = 2 * LO(2, 4L * plane);
         RUN(conv3x3_dispatch(&cd, b.feat, nullptr, W(c), Bias(c), nullptr, nullptr, nullptr, b.u1, nullptr, st));
     }
     {   // model.py:265
@@ -595,7 +610,7 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
         cd.in0_lo_offset = LO(2, 4L * plane); cd.out_lo_offset = LO(2, 16L * plane);
         if (d->training) cd.flags |= RESR_CONV_WRITE_SIGNBITS;
         MXP(cd, c, 2 * LO(2, 4L * plane), 2 * LO(2, 16L * plane));
-        if (mxt) cd.out_q_offset = 2 * LO(2, 16L * plane);
+        if (xp.mx_tail) cd.out_q_offset = 2 * LO(2, 16L * plane);
         RUN(conv3x3_dispatch(&cd, b.u1, nullptr, W(c), Bias(c), nullptr, nullptr, nullptr, b.u2, b.bits_u2, st));
     }
     {   // model.py:267
@@ -605,7 +620,7 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
         cd.in0_lo_offset = LO(2, 16L * plane); cd.out_lo_offset = LO(2, 16L * plane);
         if (d->training) cd.flags |= RESR_CONV_WRITE_SIGNBITS;
         MXP(cd, c, 2 * LO(2, 16L * plane), 0);   // (conv4 -- 0.15 % of the FLOPs, the fp32 NCHW epilogue -- keeps its three f16 stages: no q tensor of c3)
-        if (mxt) cd.out_q_offset = 2 * LO(2, 16L * plane);
+        if (xp.mx_tail) cd.out_q_offset = 2 * LO(2, 16L * plane);
         RUN(conv3x3_dispatch(&cd, b.u2, nullptr, W(c), Bias(c), nullptr, nullptr, nullptr, b.c3, b.bits_c3, st));
     }
     {   // model.py:268-270
@@ -624,8 +639,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
                        void* const* events, int n_events) {
     (void)params;
     Plan p;
-    if (!build_plan(d, p)) return fail(RESR_ERR_ARG, "generator_backward: bad descriptor");
-    if (!plan_mx_train_ok(*d)) return fail(RESR_ERR_ARG, "generator_backward: x2_plan MX_TRAIN_FORWARD (2048) needs bits 1 + 32 + 64 + 256");
+    if (!build_plan(d, p)) return RESR_ERR_ARG;
     if (n_events != 0 && (!events || n_events != d->n_blocks + 2))
         return fail(RESR_ERR_ARG, "generator_backward: grad_ready_events needs n_blocks + 2 = %d events, got %d", d->n_blocks + 2, n_events);
     // a range of the gradient arena is final once its weight-gradient reductions are enqueued: tell the caller's comm stream
@@ -640,23 +654,16 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
     Bufs b;
     carve(p, (char*)workspace, b);
     if (b.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "generator_backward: workspace %zu < %zu", workspace_bytes, b.total);
-    // RESR_X2_PLAN_F16_BACKWARD (opt-in): an exact16 FORWARD (every pre-activation fp32-class: reference-exact LeakyReLU masks, losses at
-    // 2e-6) followed by fast mode's backward pass -- plain f16 on the hi tensors of the saved activations, the sign words the forward
-    // wrote, single f16 gradient planes, f16 packed weights (`packed` is then a RESR_F16 packing of the same table).  The workspace is
-    // the exact16 one (carve below keeps the caller's descriptor); every descriptor of the pass says `dt`.
-    const bool f16bwd = d->dtype == RESR_F16X2 && (d->x2_plan & RESR_X2_PLAN_F16_BACKWARD);
-    const int dt = f16bwd ? (int)RESR_F16 : d->dtype;
+    // xp.f16_backward: fast mode's backward pass behind the exact16 forward -- plain f16 on the hi tensors of the saved activations, the sign words the
+    // forward wrote, f16 packed weights (`packed` is then a RESR_F16 packing of the same table).  The workspace stays the exact16 one; every descriptor of the pass says `dt`.
+    const X2Plan& xp = p.x2;
+    const int dt = xp.f16_backward ? (int)RESR_F16 : d->dtype;
     Plan pb = p;
     pb.d.dtype = dt;
     const size_t es = elem_size(dt);
     const bool x2 = dt == RESR_F16X2;
     const size_t wes = es * (x2 ? 3 : 1);
     const int wm = x2 ? wgrad_x2_products() : 1;
-    // exact16, RESR_X2_PLAN_GROWTH_GRAD_F16: the growth-plane gradients g_o1..g_o4 are READ as single f16 tensors -- two stages on
-    // their chunks in every backward-data pass, two tap-products in conv1..conv4's weight gradients.  They are still STORED as
-    // pairs: the bias gradient (a plain sum of G, which cancels where the weight products do not) takes hi + lo through the one
-    // (x_hi chunk 0, g_lo) job per convolution that carries the bias sum -- with a single-f16 G the worst bias tensor of the
-    // emulation reached 6.7e-4 at 1 x 128^2.
     // The 16-bit modes lift a small incoming gradient into f16's normal range: when max |g_y| < 2^6 the pass runs on g_y * 2^k with
     // max |g_y * 2^k| in [2^6, 2^7) and hands every result out times 2^-k (both exact; common.h grad_prescale).  The pass is linear in
     // g_y, and its f16 tensors -- the hi halves that the plan below reads alone most of all -- keep their 11 bits whatever loss scale
@@ -671,14 +678,6 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
     // reads 4.3e-3 at a GradScaler's initial 2^16 and 1.4e-3 from 2^20 on (median 7.7e-4 throughout; garbage at 2^10) -- the difference is
     // f16 underflow, not f16 arithmetic (tools/fast_loss_scale_probe.py).  strict (f32) needs none.
     const unsigned* gsc = (dt != RESR_F32 && !no_prescale) ? b.gscale : nullptr;
-    // RESR_X2_PLAN_MX_BWD: the dense blocks' backward-data passes read every gradient chunk as a pair on an f16 + an MX stage
-    const bool mxb = plan_mx_bwd(*d) && !f16bwd;
-    const bool mxw = plan_mx_wgrad(*d) && mxb;
-    const bool mxt = plan_mx_tail(*d) && mxw;
-    const bool gg_single = x2 && (d->x2_plan & RESR_X2_PLAN_GROWTH_GRAD_F16);
-    const bool gg_store_single = gg_single && (d->x2_plan & RESR_X2_PLAN_GROWTH_GRAD_STORE_F16);   // opt-in: no lo store, biases from hi alone
-    // RESR_X2_PLAN_GROWTH_ACT_F16_WGRAD: the weight products of conv2..conv5 read the growth planes (X chunks 2..) as their hi tensor
-    const int wx_pairs = (x2 && (d->x2_plan & RESR_X2_PLAN_GROWTH_ACT_F16_WGRAD)) ? 2 : 0;
     const char* pk = (const char*)packed;
     const int N = d->n, h = p.h, w = p.w;
     const int H4 = 4 * h, W4 = 4 * w, H2 = 2 * h, W2 = 2 * w;
@@ -712,7 +711,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
                      int flags, float scale, long x_chunk, long g_chunk, long x_lo, long g_lo, long x_q = 0, long g_q = 0) -> int {
         WgradConv wc = wconv(c, x0, cin, s0, g, gstride, scale, x_lo, g_lo);
         wc.x_chunk_stride = x_chunk; wc.g_chunk_stride = g_chunk;
-        wc.x_q_off = x_q; wc.g_q_off = g_q;     // both != 0 (RESR_X2_PLAN_MX_TAIL): the correction tap-products as MX jobs
+        wc.x_q_off = x_q; wc.g_q_off = g_q;     // both != 0 (mx_tail): the correction tap-products as MX jobs
         return wgrad_run(&wc, 1, hh, ww, flags);
     };
     // backward-data pass descriptor: in0 (cin0 channels, lo offset lo0) [+ in1 (lo offset lo1)] -> out (lo offset lo_out)
@@ -725,17 +724,17 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
 
     // clamp_ backward + layout                                              model.py:270
     if (gsc) RUN(absmax_dispatch(gy, (long)N * d->out_channels * H4 * W4, b.gscale, pre_log2, st));
-    RUN(nchw_to_nhwc_q_dispatch(gy, b.g4, N, d->out_channels, H4, W4, 1, 32, dt, b.ymask, st, lo_g4, gsc, mxt ? 2 * lo_g4 : 0L));
-    const char* pk_mx = mxb ? pk + generator_mx_offset(d) : nullptr;
+    RUN(nchw_to_nhwc_q_dispatch(gy, b.g4, N, d->out_channels, H4, W4, 1, 32, dt, b.ymask, st, lo_g4, gsc, xp.mx_tail ? 2 * lo_g4 : 0L));
+    const char* pk_mx = xp.mx_bwd ? pk + generator_mx_offset(d) : nullptr;
     auto MXT = [&](ResrConvDesc& cd, size_t pk_off, long in_q, long out_q) {   // a tail pass on one f16 + one MX stage per chunk of its gradient input
-        if (!mxt) return;
+        if (!xp.mx_tail) return;
         cd.flags |= RESR_CONV_MX_PAIRS;
         cd.in0_q_offset = in_q; cd.out_q_offset = out_q;
         cd.w_mx_offset = (int64_t)((pk_mx + pk_off * 2) - (pk + pk_off * wes));
     };
     {   // conv4                                                            model.py:268
         const ConvSpec& c = p.convs[p.i_conv4];
-        RUN(wgrad(c, H4, W4, b.c3, 64, 32, b.g4, 32, 0, 1.f, pl4, 0, lo_4, lo_g4, mxt ? 2 * lo_4 : 0, mxt ? 2 * lo_g4 : 0));
+        RUN(wgrad(c, H4, W4, b.c3, 64, 32, b.g4, 32, 0, 1.f, pl4, 0, lo_4, lo_g4, xp.mx_tail ? 2 * lo_4 : 0, xp.mx_tail ? 2 * lo_g4 : 0));
         ResrConvDesc cd = dgrad(H4, W4, 32, 32, 32, 0, 64, 64, 32, RESR_CONV_MASK | RESR_CONV_MASK_BITS, lo_g4, 0, lo_4);
         cd.out_chunk_stride = pl4;
         MXT(cd, p.pk_bwd_conv4, 2 * lo_g4, 2 * lo_4);
@@ -743,7 +742,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
     }
     {   // conv3                                                            model.py:267
         const ConvSpec& c = p.convs[p.i_conv3];
-        RUN(wgrad(c, H4, W4, b.u2, 64, 32, b.gA, 32, 0, 1.f, pl4, pl4, lo_4, lo_4, mxt ? 2 * lo_4 : 0, mxt ? 2 * lo_4 : 0));
+        RUN(wgrad(c, H4, W4, b.u2, 64, 32, b.gA, 32, 0, 1.f, pl4, pl4, lo_4, lo_4, xp.mx_tail ? 2 * lo_4 : 0, xp.mx_tail ? 2 * lo_4 : 0));
         ResrConvDesc cd = dgrad(H4, W4, 64, 32, 64, 0, 64, 64, 32, RESR_CONV_MASK | RESR_CONV_MASK_BITS, lo_4, 0, lo_4);
         cd.in0_chunk_stride = pl4; cd.out_chunk_stride = pl4;
         MXT(cd, p.pk_bwd_conv3, 2 * lo_4, 2 * lo_4);
@@ -752,7 +751,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
     if (debug_stop() == 1) return RESR_OK;
     {   // upsampling2                                                      model.py:265
         const ConvSpec& c = p.convs[p.i_up2];
-        RUN(wgrad(c, H4, W4, b.u1, 64, 32, b.gB, 32, RESR_CONV_UPSAMPLE_IN, 1.f, pl2, pl4, lo_2, lo_4, mxt ? 2 * lo_2 : 0, mxt ? 2 * lo_4 : 0));
+        RUN(wgrad(c, H4, W4, b.u1, 64, 32, b.gB, 32, RESR_CONV_UPSAMPLE_IN, 1.f, pl2, pl4, lo_2, lo_4, xp.mx_tail ? 2 * lo_2 : 0, xp.mx_tail ? 2 * lo_4 : 0));
         ResrConvDesc cd = dgrad(H4, W4, 64, 32, 64, 0, 64, 64, 32, 0, lo_4, 0, lo_4);
         cd.in0_chunk_stride = pl4; cd.out_chunk_stride = pl4;
         MXT(cd, p.pk_bwd_up2, 2 * lo_4, 0);     // (its output feeds the sum-pool: no q tensor)
@@ -779,11 +778,11 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
         RUN(wgrad(c, h, w, b.trunk_out, 64, 32, b.gF, 32, 0, 1.f, plane, plane, lo_t, lo_t));
         ResrConvDesc cd = dgrad(h, w, 64, 32, 64, 0, 64, 64, 32, 0, lo_t, 0, lo_t);
         cd.in0_chunk_stride = plane; cd.out_chunk_stride = plane;   // the gT ring (gradient wrt the RDB chain) is chunk-planar [2][N,h,w,32]
-        if (mxb) cd.out_q_offset = 2 * lo_t;   // the first dense block's passes read gT[0] through MX stages: this (plain) pass emits its q tensor
+        if (xp.mx_bwd) cd.out_q_offset = 2 * lo_t;   // the first dense block's passes read gT[0] through MX stages: this (plain) pass emits its q tensor
         RUN(conv3x3_dispatch(&cd, b.gF, nullptr, pk + p.pk_bwd_conv2 * wes, nullptr, nullptr, nullptr, nullptr, b.gT[0], nullptr, st));
     }
     auto MXB = [&](ResrConvDesc& cd, size_t pk_off, long out_q) {   // gin (in0) and the slab gS (in1) with their q tensors, the pass's MX blocks
-        if (!mxb) return;
+        if (!xp.mx_bwd) return;
         cd.flags |= RESR_CONV_MX_PAIRS;
         cd.x2_pair_chunks = 0;   // every chunk a pair: the growth-plane gradients enter with both halves
         cd.in0_q_offset = 2 * lo_t; cd.in1_q_offset = 2 * lo_gs; cd.out_q_offset = out_q;
@@ -809,9 +808,9 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
         WgradConv* wcb = wc + (batch_rrdb ? 5 * pos : 0);
         wcb[4] = wconv(p.convs[p.i_trunk0 + r * 5 + 4], act, 192, 32, gin, 32, fold, lo_ws, lo_t);   // conv5: G = fold * gin
         wcb[4].x_chunk_stride = plane; wcb[4].g_chunk_stride = plane;
-        wcb[4].x_pair_chunks = wx_pairs;
-        wcb[4].x_single_g_hi = (wx_pairs && (d->x2_plan & RESR_X2_PLAN_GROWTH_ACT_G_HI_WGRAD)) ? 1 : 0;
-        if (mxw) { wcb[4].x_q_off = 2 * lo_ws; wcb[4].g_q_off = 2 * lo_t; }   // MX jobs for the stream chunks' corrections (X: ws planes 0, 1; G: gin)
+        wcb[4].x_pair_chunks = xp.wx_pairs;
+        wcb[4].x_single_g_hi = xp.x_single_g_hi ? 1 : 0;
+        if (xp.mx_wgrad) { wcb[4].x_q_off = 2 * lo_ws; wcb[4].g_q_off = 2 * lo_t; }   // MX jobs for the stream chunks' corrections (X: ws planes 0, 1; G: gin)
         ResrConvDesc cds[4];
         const void* ws4[4];
         const void* masks4[4];
@@ -821,18 +820,18 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
             const int cin = 64 + 32 * ps;
             ResrConvDesc cd = dgrad(h, w, 64, 32, cin, 32, 32, 32, 32, RESR_CONV_MASK | RESR_CONV_MASK_BITS, lo_t, lo_gs, lo_gs);
             cd.in0_chunk_stride = plane; cd.in1_chunk_stride = plane;
-            if (gg_single) cd.x2_pair_chunks = 2;   // g_y (in0): pairs; the slab (in1) is read as single f16 chunks, written as a pair
-            if (gg_store_single) cd.flags |= RESR_CONV_OUT_SINGLE;
+            if (xp.gg_single) cd.x2_pair_chunks = 2;   // g_y (in0): pairs; the slab (in1) is read as single f16 chunks, written as a pair
+            if (xp.gg_store_single) cd.flags |= RESR_CONV_OUT_SINGLE;
             MXB(cd, p.pk_bwd_trunk[(size_t)r * 5 + ps], 2 * lo_gs);
             char* out = gS + (size_t)ps * plane * es;
             const char* mask = b.bits[r] + (size_t)(k - 1) * N * h * w * sizeof(uint32_t);   // sign plane of o_k
             cds[ps] = cd; ws4[ps] = pk + p.pk_bwd_trunk[(size_t)r * 5 + ps] * wes; masks4[ps] = mask; outs4[ps] = out;
             const ConvSpec& c = p.convs[p.i_trunk0 + r * 5 + k - 1];
-            wcb[k - 1] = wconv(c, act, c.cin, 32, out, 32, 1.f, lo_ws, gg_store_single ? 0 : lo_gs);
+            wcb[k - 1] = wconv(c, act, c.cin, 32, out, 32, 1.f, lo_ws, xp.gg_store_single ? 0 : lo_gs);
             wcb[k - 1].x_chunk_stride = plane;
-            wcb[k - 1].g_lo_bias_only = (gg_single && !gg_store_single) ? 1 : 0;
-            wcb[k - 1].x_pair_chunks = wx_pairs;
-            if (mxw) { wcb[k - 1].x_q_off = 2 * lo_ws; wcb[k - 1].g_q_off = 2 * lo_gs; }   // (the stream chunks' MX job carries (x_hi, g_lo) too; the growth chunks keep the plan's reads)
+            wcb[k - 1].g_lo_bias_only = (xp.gg_single && !xp.gg_store_single) ? 1 : 0;
+            wcb[k - 1].x_pair_chunks = xp.wx_pairs;
+            if (xp.mx_wgrad) { wcb[k - 1].x_q_off = 2 * lo_ws; wcb[k - 1].g_q_off = 2 * lo_gs; }   // (the stream chunks' MX job carries (x_hi, g_lo) too; the growth chunks keep the plan's reads)
         }
         {   // the four mirrored cout-32 passes, then g_x = convT(all) + (skip terms): one chained launch where the kernel supports
             // it (g_x joins on small launches), else one launch per pass
@@ -840,7 +839,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
             if (nxt == e_idx && pos != 2) nxt = (nxt + 1) & 3;
             ResrConvDesc cd = dgrad(h, w, 64, 32, 192, 32, 64, 64, 32, 0, lo_t, lo_gs, lo_t);
             cd.in0_chunk_stride = plane; cd.in1_chunk_stride = plane; cd.out_chunk_stride = plane;
-            if (gg_single) cd.x2_pair_chunks = 2;
+            if (xp.gg_single) cd.x2_pair_chunks = 2;
             const char* res0 = gin;
             const char* res1 = nullptr;
             cd.res0_stride = 32; cd.res0_chunk_stride = plane; cd.s0 = 1.f; cd.res0_lo_offset = lo_t;

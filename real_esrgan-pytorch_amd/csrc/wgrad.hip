@@ -46,8 +46,7 @@ struct WgradJob {
     const char* g;        // G base + channel offset of the job's 32-channel tile
     unsigned xstride_b, gstride_b;
     unsigned slab_off;    // float offset of this job's [splits][kSlab] slabs in `partial`
-    unsigned want_bias;   // bit 0: also produce sum_p G[p][co] (one job per co tile does); bit 1: ONLY that -- the quad kernel skips the job's tap
-                          // products (its dW slabs are zeros): the (x_hi chunk 0, g_lo) job of WgradConv.g_lo_bias_only
+    unsigned want_bias;   // 1: also produce sum_p G[p][co] (one job per co tile does)
     unsigned xsub;        // 0..3: X chunk lies in sub-position (i*2+j) of a space-to-depth image -- only 2x2 of the 9 taps of the
                           // virtual kernel of a 4x4 / stride-2 conv are non-zero there; 4: all taps
     unsigned mx;          // 1: an MX job -- x and g are q tensors (bf8 records); the job yields (x_hi, g_lo) + (x_lo, g_hi) in one slab (quad kernel only)
@@ -409,7 +408,7 @@ struct WgradQuad {
     const char* g[2];
     unsigned xstride_b[2], gstride_b[2];
     unsigned slab_off[4];   // float offset of product p's [splits][kSlab] slabs, ~0u = product not wanted
-    unsigned bias_mask;     // bit p: product p also yields sum_p G (one product per G tile does); bit 4 + p: product p yields ONLY that (no taps);
+    unsigned bias_mask;     // bit p: product p also yields sum_p G (one product per G tile does); bit 4 + p: product p yields ONLY that (no taps; no launch sets it);
                             // bit 8 + p: product p is an MX job (q records, 8-bit MFMAs)
     unsigned xsub;          // byte xi: tap pattern of X chunk xi (WgradJob::xsub)
 };
@@ -1024,7 +1023,6 @@ static int build_quads(const WgradArgs& a, int nj_all, WgradQuadArgs& q, unsigne
             const WgradJob& j = a.jobs[jid[qi.prod[p]]];
             w.slab_off[p] = j.slab_off;
             if (j.want_bias & 1u) w.bias_mask |= 1u << p;
-            if (j.want_bias & 2u) w.bias_mask |= 16u << p;
             if (j.mx) w.bias_mask |= 256u << p;
         }
     }
@@ -1363,7 +1361,6 @@ int wgrad_batch(const WgradConv* convs, int nconv, int n, int h, int w, int dtyp
                     if (part == 3 && want_bias) q.c_bias = 1;
                     // (x_hi chunk 0, g_lo) carries the bias sum AND a real term of dW: skipping its taps was measured (+1 % on the exact16 step)
                     // and rejected -- the worst gradient tensor against the all-pairs plan rises by a fifth (32 x 64^2: 5.1e-4 -> 6.3e-4)
-                    if (part == 1 && c.g_lo_bias_only && getenv("RESR_WGRAD_BIAS_JOBS_NO_TAPS")) j.want_bias |= 2u;   // experiment knob, read per call
                     j.xsub = (c.x_s2d_c > 0 && dtype != RESR_F32) ? (unsigned)((ck * 32) / c.x_s2d_c) : 4u;
                     // (the reduction takes dW = A + (B + C) 2^-12 with the bias from A and B -- and from C where C is an MX job that summed g_lo: c_bias)
                     if (part == 1) q.slab_b = off;

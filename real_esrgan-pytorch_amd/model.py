@@ -226,7 +226,7 @@ class Generator(nn.Module):
     MFMAs per product, fp32 accumulate: meets the 1e-3 parity tolerance vs the fp32 CPU path at about a third
     of fast mode's throughput), "strict" = f32 operands on v_mfma_f32_32x32x2_f32 (bit-for-bit fp32 FMA chains).
     Default from $RESR_PRECISION, else "fast".
-    `x2_plan` (exact16 only; bit set of _lib.X2_PLAN_*, default from $RESR_X2_PLAN, else 763 = bits 0, 1, 3, 4, 5, 6, 7, 9; 59 = round 5's default without the MX stages): which tensors of the dense
+    `x2_plan` (exact16 only; bit set of _lib.X2_PLAN_*, which bit needs which: _lib.X2_PLAN_RULES; default from $RESR_X2_PLAN, else 763 = bits 0, 1, 3, 4, 5, 6, 7, 9; 59 = round 5's default without the MX stages): which tensors of the dense
     blocks are single f16 instead of hi/lo pairs -- bit 0: the growth planes o1..o4 of an INFERENCE forward (50 instead of 60
     stages per block; forward ~1e-6 at the reference's init scale, gate 2e-4), bit 1: the growth-plane gradients of the backward
     pass are READ as single f16 (two stages / two tap-products on their chunks; the bias sums still take hi + lo; worst gradient
@@ -265,22 +265,9 @@ class Generator(nn.Module):
         self.precision = precision or os.environ.get("RESR_PRECISION", "fast")
         self._dtype = _precision_to_dtype(self.precision)
         self.x2_plan = int(os.environ.get("RESR_X2_PLAN", "763")) if x2_plan is None else int(x2_plan)
-        if not 0 <= self.x2_plan <= 4095:
-            raise ValueError(f"x2_plan must be a bit set of X2_PLAN_GROWTH_F16_INFER (1) | X2_PLAN_GROWTH_GRAD_F16 (2) | "
-                             f"X2_PLAN_GROWTH_GRAD_STORE_F16 (4) | X2_PLAN_GROWTH_ACT_F16_WGRAD (8) | X2_PLAN_GROWTH_ACT_G_HI_WGRAD (16) | X2_PLAN_GROWTH_W16_INFER (32) | "
-                             f"X2_PLAN_MX_INFER (64) | X2_PLAN_MX_BWD (128) | X2_PLAN_F16_BACKWARD (256) | X2_PLAN_MX_WGRAD (512) | X2_PLAN_MX_TAIL (1024) | "
-                             f"X2_PLAN_MX_TRAIN_FORWARD (2048), got {self.x2_plan}")
-        if (self.x2_plan & 128) and (self.x2_plan & 4):
-            raise ValueError(f"x2_plan={self.x2_plan}: MX_BWD (128) reads the growth-plane gradients as pairs; GROWTH_GRAD_STORE_F16 (4) stores them single")
-        # a bit that only refines another one means nothing without it: refuse instead of silently ignoring it
-        for bit, needs, name in ((4, 2, "GROWTH_GRAD_STORE_F16 (4) refines GROWTH_GRAD_F16 (2)"), (16, 8, "GROWTH_ACT_G_HI_WGRAD (16) refines GROWTH_ACT_F16_WGRAD (8)"),
-                                 (32, 1, "GROWTH_W16_INFER (32) refines GROWTH_F16_INFER (1)"), (64, 33, "MX_INFER (64) rides on GROWTH_F16_INFER (1) + GROWTH_W16_INFER (32)"),
-                                 (512, 128 + 8, "MX_WGRAD (512) rides on MX_BWD (128: the gradient planes' q tensors) + GROWTH_ACT_F16_WGRAD (8: the stream chunks are the pair chunks)"),
-                                 (1024, 512 + 128 + 8, "MX_TAIL (1024) extends MX_WGRAD (512) to the 4x-resolution tail"),
-                                 (2048, 1 + 32 + 64 + 256, "MX_TRAIN_FORWARD (2048) runs the inference MX forward (1 + 32 + 64) in training, "
-                                                           "in front of the f16 backward pass (256)")):
-            if (self.x2_plan & bit) and (self.x2_plan & needs) != needs:
-                raise ValueError(f"x2_plan={self.x2_plan}: {name}")
+        err = _lib.x2_plan_error(self.x2_plan)   # the rule table of _lib.X2_PLAN_RULES / include/resr.h
+        if err:
+            raise ValueError(err)
         self.n_blocks = n_blocks or self.N_BLOCKS
         if upscale_factor == 2:
             conv_in, downscale_factor = in_channels * 4, 2
@@ -433,15 +420,14 @@ class Generator(nn.Module):
         raw, n = self._table_dev[key]
         _lib.check(L.resr_pack_weights(_lib.ptr(raw), n, _lib.ptr(flat), _lib.ptr(self._packed), self._dtype,
                                        _lib.stream_ptr(flat)), "resr_pack_weights")
-        if self._dtype == _lib.RESR_F16X2 and backward and (desc.x2_plan & _lib.X2_PLAN_F16_BACKWARD):
+        if self._dtype == _lib.RESR_F16X2 and backward and _lib.x2_plan_f16_backward(desc.x2_plan):
             fd = _lib.GeneratorDesc(desc.n, desc.h, desc.w, desc.in_channels, desc.out_channels, desc.upscale, desc.n_blocks, _lib.RESR_F16, 1, 0, 0, 0)
             nb16 = L.resr_generator_packed_bytes(C.byref(fd), 1)
             if self._packed_f16 is None or self._packed_f16.numel() < nb16 or self._packed_f16.device != flat.device:
                 self._packed_f16 = torch.zeros(nb16, dtype=torch.uint8, device=flat.device)
             _lib.check(L.resr_pack_weights(_lib.ptr(raw), n, _lib.ptr(flat), _lib.ptr(self._packed_f16), _lib.RESR_F16, _lib.stream_ptr(flat)),
                        "resr_pack_weights (f16 backward)")
-        if self._dtype == _lib.RESR_F16X2 and (((desc.x2_plan & _lib.X2_PLAN_MX_INFER) and not desc.training) or
-                                               ((desc.x2_plan & (_lib.X2_PLAN_MX_BWD | _lib.X2_PLAN_MX_TRAIN_FORWARD)) and desc.training)):
+        if self._dtype == _lib.RESR_F16X2 and _lib.x2_plan_packs_mx(desc.x2_plan, bool(desc.training)):
             # the MX blocks of the same table ([bf8(W1) | bf8(W2)] per tap and row), behind the f16 blocks of the packed buffer
             mx_off = int(L.resr_generator_mx_offset(C.byref(desc)))
             _lib.check(L.resr_pack_weights_mx(_lib.ptr(raw), n, _lib.ptr(flat), C.c_void_p(self._packed.data_ptr() + mx_off),
@@ -449,14 +435,14 @@ class Generator(nn.Module):
 
     def _workspace(self, desc: _lib.GeneratorDesc, device) -> _Workspace:
         L = _lib.lib()
-        key = (desc.n, desc.h, desc.w, desc.training, desc.dtype, desc.wgrad_splits, desc.x2_plan & (_lib.X2_PLAN_MX_INFER | _lib.X2_PLAN_MX_BWD | _lib.X2_PLAN_MX_WGRAD | _lib.X2_PLAN_MX_TAIL | _lib.X2_PLAN_MX_TRAIN_FORWARD))   # (the MX plans carry q tensors)
+        key = (desc.n, desc.h, desc.w, desc.training, desc.dtype, desc.wgrad_splits, _lib.x2_plan_layout_key(desc.x2_plan))
         pool = self._workspaces.setdefault(key, [])
         for ws in pool:
             if not ws.busy:
                 return ws
         nbytes = L.resr_generator_workspace_bytes(C.byref(desc))
         if nbytes == 0:
-            raise RuntimeError("resr_generator_workspace_bytes: unsupported shape")
+            raise RuntimeError(f"resr_generator_workspace_bytes: unsupported shape ({(L.resr_last_error() or b'').decode()})")
         ws = _Workspace(nbytes, device, int(L.resr_generator_chain_state_bytes(C.byref(desc))))
         pool.append(ws)
         return ws
@@ -502,7 +488,7 @@ class Generator(nn.Module):
                 e.record(torch.cuda.current_stream(gy.device))
                 self._events.append(e)
             ev_arr = (C.c_void_p * n_ev)(*[e.cuda_event for e in self._events[:n_ev]])
-        f16bwd = self._dtype == _lib.RESR_F16X2 and (desc.x2_plan & _lib.X2_PLAN_F16_BACKWARD)
+        f16bwd = self._dtype == _lib.RESR_F16X2 and _lib.x2_plan_f16_backward(desc.x2_plan)
         _lib.check(L.resr_generator_backward(C.byref(desc), _lib.ptr(gy), _lib.ptr(flat), _lib.ptr(self._packed_f16 if f16bwd else self._packed),
                                              _lib.ptr(ws.buf), ws.buf.numel(), _lib.ptr(self._flat_grad),
                                              _lib.ptr(gx), _lib.stream_ptr(gy), ev_arr, n_ev),
