@@ -451,6 +451,44 @@ int resr_compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x_u8
                                    const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
                                    int32_t taps_x, void* stream);
 
+/* YUV 4:2:0 frames (real_esrgan-pytorch_amd/csrc/frames.hip): what video decoders deliver and encoders consume, 1.5 bytes per pixel.
+ * A frame of luma size H x W (both even) is H * W * 3 / 2 bytes, seen as a uint8 array [3H/2, W]; batches are [N,3H/2,W], contiguous:
+ *   RESR_YUV_I420: Y [H,W], then Cb [H/2,W/2], then Cr [H/2,W/2];      RESR_YUV_NV12: Y [H,W], then [H/2,W/2,2] interleaved Cb,Cr.
+ * The path is DEFINED as a composition over the uint8 RGB path above, bit for bit, with no tolerance anywhere:
+ *   resr_compact_forward_yuv420(f) == resr_rgb_to_yuv420(resr_compact_forward_u8(resr_yuv420_to_rgb(f)))
+ * and the two colour conversions are integer functions of bytes (int32 throughout, >> arithmetic i.e. floor), studio range, with
+ * the Q16 tables of the descriptor (rows of fq: Y, Cb, Cr over R, G, B; rows of iq: R, G, B over Y - 16, Cb - 128, Cr - 128;
+ * frames.yuv420_tables computes them for BT.601 / BT.709):
+ *   yuv420_to_rgb: pixel (y, x) takes Y[y,x], Cb[y/2,x/2], Cr[y/2,x/2] (chroma replicated over its 2x2 block);
+ *                  rgb[c] = clamp((iq[c][0] * (Y - 16) + iq[c][1] * (Cb - 128) + iq[c][2] * (Cr - 128) + 32768) >> 16, 0, 255);
+ *                  every byte value is legal input, values outside the studio range clamp.
+ *   rgb_to_yuv420: Y = (fq[0] . rgb + (16 << 16) + 32768) >> 16 per pixel; with S the sum of a 2x2 block's four (R, G, B):
+ *                  Cb = (fq[1] . S + (128 << 18) + (1 << 17)) >> 18, Cr likewise with fq[2] (a centre-sited box average of the
+ *                  unrounded chroma).  The kernels do not clamp: with the tables of frames.yuv420_tables no RGB triple leaves
+ *                  Y 16..235, Cb / Cr 16..240; a caller's own tables must keep every result within 0..255.
+ * A NaN inside the net is outside the contract exactly as for resr_compact_forward_u8 (it quantises to the byte 0 here).
+ *
+ * resr_compact_forward_yuv420: resr_compact_forward_u8 with both conversions fused into its first and last kernel: x_yuv
+ * [N, 3 d->h / 2, d->w] -> y_yuv [N, 3 s d->h / 2, s d->w], same layout both ways.  Same descriptor, packed weights and workspace
+ * (resr_compact_workspace_bytes: nothing more), same checks and codes.  No RGB frame exists on this path: the tail recomputes the
+ * residual from x_yuv, which must stay valid until the call has run.
+ * resr_yuv420_to_rgb / resr_rgb_to_yuv420: the generic conversions, one launch each, [N,3H/2,W] <-> uint8 HWC [N,H,W,3], for every
+ * case whose ends are not fused (the RRDB generator, tiled frames, outscale).
+ * RESR_ERR_ARG before any launch: a null pointer; n, h, w <= 0; an odd h or w (d->h, d->w: then the output's are even too); a
+ * layout other than RESR_YUV_*; a destination (for resr_rgb_to_yuv420 the source too) that is not aligned for the wide stores its
+ * width selects: 8 bytes for y_yuv when s * d->w is a multiple of 8, 4 bytes for the generic conversions when w is a multiple of 4
+ * (other even widths take byte stores and need no alignment). */
+enum { RESR_YUV_I420 = 0, RESR_YUV_NV12 = 1 };
+typedef struct {
+    int32_t layout;           /* RESR_YUV_*                                                       */
+    int32_t fq[9];            /* RGB -> YCbCr, Q16, row-major                                     */
+    int32_t iq[9];            /* YCbCr -> RGB, Q16, row-major                                     */
+} ResrYuvDesc;                /* host struct; the kernels take it by value                        */
+int resr_compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x_yuv, const float* params, const void* packed,
+                                void* workspace, size_t workspace_bytes, uint8_t* y_yuv, const ResrYuvDesc* yuv, void* stream);
+int resr_yuv420_to_rgb(const uint8_t* src, uint8_t* dst_hwc, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream);
+int resr_rgb_to_yuv420(const uint8_t* src_hwc, uint8_t* dst, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream);
+
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */
 

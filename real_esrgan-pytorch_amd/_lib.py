@@ -129,6 +129,13 @@ class CompactDesc(C.Structure):
                 ("act", C.c_int32), ("dtype", C.c_int32), ("reserved_", C.c_int32)]
 
 
+YUV_I420, YUV_NV12 = 0, 1   # ResrYuvDesc.layout
+
+
+class YuvDesc(C.Structure):
+    _fields_ = [("layout", C.c_int32), ("fq", C.c_int32 * 9), ("iq", C.c_int32 * 9)]
+
+
 class DiscriminatorDesc(C.Structure):
     _fields_ = [("n", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("dtype", C.c_int32), ("training", C.c_int32),
                 ("sn_training", C.c_int32)]
@@ -179,6 +186,9 @@ _PROTOS = {
     "resr_image_resize": (C.c_int, [_P, _P] + [C.c_int32] * 6 + [_P, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
     "resr_u8_to_nchw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     "resr_nchw_to_u8": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "resr_compact_forward_yuv420": (C.c_int, [C.POINTER(CompactDesc), _P, _P, _P, _P, C.c_size_t, _P, C.POINTER(YuvDesc), _P]),
+    "resr_yuv420_to_rgb": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvDesc), _P]),
+    "resr_rgb_to_yuv420": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvDesc), _P]),
     "resr_ema_update": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P]),
     "resr_debug_tr_probe": (C.c_int, [_P, _P]),
     "resr_debug_conv_trace": (C.c_int, [_P]),

@@ -10,6 +10,9 @@ conv 64->3*s*s, pixel-shuffle, + the nearest-upsampled input.  There is no PyTor
 way in is fused into the first kernel and the `* 255`, clamp and truncation of `imgproc.tensor_to_image` into the last, so its
 result equals `tensor_to_image(forward(float frame))` bit for bit and a quarter of the output bytes leave the device.  It is
 forward only as well (frames.py builds the pipelined host-to-host stream on it).
+
+`forward_yuv420` is that sequence for YUV 4:2:0 frames (I420 / NV12, `resr_compact_forward_yuv420`): the integer colour conversions
+of frames.py fused into the same two kernels, so its result equals `rgb_to_yuv420_np(forward_u8(yuv420_to_rgb_np(f)))` bit for bit.
 """
 from __future__ import annotations
 
@@ -226,6 +229,30 @@ class SRVGGNetCompact(nn.Module):
         _lib.check(_lib.lib().resr_compact_forward_u8(C.byref(desc), _lib.ptr(frames), _lib.ptr(flat), _lib.ptr(self._packed),
                                                       _lib.ptr(ws), ws.numel(), _lib.ptr(y), _lib.stream_ptr(frames)),
                    "resr_compact_forward_u8")
+        return y
+
+    def forward_yuv420(self, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601") -> torch.Tensor:
+        """frames uint8 [N,3H/2,W] (YUV 4:2:0, H and W even; `layout` "i420" or "nv12", `matrix` "bt601" or "bt709": frames.py) on
+        the model's device, contiguous -> uint8 [N,3sH/2,sW] in the same layout: bit for bit
+        `frames.rgb_to_yuv420_np(self.forward_u8(frames.yuv420_to_rgb_np(f)))`.  `resr_compact_forward_yuv420`: the launch sequence
+        of `forward_u8` with the two integer colour conversions inside its first and last kernel -- no RGB frame exists on the
+        device, and half the bytes enter and leave.  Same guard, packing and workspace caches as `forward`."""
+        from . import frames as _frames
+        ydesc = _frames.yuv_desc(layout, matrix)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self._ordered_params()):
+            raise RuntimeError("SRVGGNetCompact: the compact generator's backward pass is not implemented on the MI355X path; "
+                               "run inference under torch.no_grad() (or with requires_grad_(False) parameters)")
+        n, h, w = _frames.check_yuv420(frames, "SRVGGNetCompact.forward_yuv420")
+        flat = self.flat_parameters()
+        _lib.require_cuda(flat, "SRVGGNetCompact parameters")
+        desc = self._desc(n, h, w)
+        self._pack(desc, flat)
+        ws = self._workspace(desc, frames.device)
+        s = self.upscale
+        y = torch.empty((n, h * s * 3 // 2, w * s), dtype=torch.uint8, device=frames.device)
+        _lib.check(_lib.lib().resr_compact_forward_yuv420(C.byref(desc), _lib.ptr(frames), _lib.ptr(flat), _lib.ptr(self._packed),
+                                                          _lib.ptr(ws), ws.numel(), _lib.ptr(y), C.byref(ydesc),
+                                                          _lib.stream_ptr(frames)), "resr_compact_forward_yuv420")
         return y
 
     def load_official_state_dict(self, checkpoint) -> None:

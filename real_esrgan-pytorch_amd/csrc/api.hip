@@ -107,6 +107,10 @@ int compact_forward_u8_scaled(const ResrCompactDesc*, const uint8_t*, const floa
                               const int32_t*, const float*, int, const int32_t*, const float*, int, hipStream_t);
 int image_resize_dispatch(const float*, void*, int, int, int, int, int, int, const int32_t*, const float*, int, const int32_t*,
                           const float*, int, int, hipStream_t);
+int compact_forward_yuv420(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, const ResrYuvDesc*,
+                           hipStream_t);
+int yuv420_to_rgb_dispatch(const uint8_t*, uint8_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
+int rgb_to_yuv420_dispatch(const uint8_t*, uint8_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
 int u8_to_nchw_dispatch(const uint8_t*, float*, int, int, int, hipStream_t);
 int nchw_to_u8_dispatch(const float*, uint8_t*, int, int, int, hipStream_t);
 
@@ -307,6 +311,22 @@ int resr_u8_to_nchw(const uint8_t* src_u8, float* dst_f32, int32_t n, int32_t h,
 int resr_nchw_to_u8(const float* src_f32, uint8_t* dst_u8, int32_t n, int32_t h, int32_t w, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return nchw_to_u8_dispatch(src_f32, dst_u8, n, h, w, (hipStream_t)stream);
+}
+
+int resr_compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x_yuv, const float* params, const void* packed,
+                                void* workspace, size_t workspace_bytes, uint8_t* y_yuv, const ResrYuvDesc* yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_yuv420(d, x_yuv, params, packed, workspace, workspace_bytes, y_yuv, yuv, (hipStream_t)stream);
+}
+
+int resr_yuv420_to_rgb(const uint8_t* src, uint8_t* dst_hwc, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return yuv420_to_rgb_dispatch(src, dst_hwc, n, h, w, yuv, (hipStream_t)stream);
+}
+
+int resr_rgb_to_yuv420(const uint8_t* src_hwc, uint8_t* dst, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return rgb_to_yuv420_dispatch(src_hwc, dst, n, h, w, yuv, (hipStream_t)stream);
 }
 
 size_t resr_discriminator_param_count(void) { return discriminator_param_count(); }

@@ -12,6 +12,7 @@
 // (pixel-shuffle + residual + * 255, clamp, truncate) in place of compact_tail_kernel; same plan, same workspace.
 // compact_forward_u8_scaled ("outscale") is that sequence with image_resize.hip's fused tail in place of the u8 tail: the HR
 // frame is formed tile by tile in LDS and only the resized uint8 frame [N,oh,ow,3] is written; same plan, same workspace.
+// compact_forward_yuv420 is compact_forward_u8 for YUV 4:2:0 frames [N,3H/2,W]: frames.hip's YUV head and YUV tail at the two ends.
 #include <vector>
 
 #include "common.h"
@@ -24,6 +25,9 @@ int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const 
 int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
 int u8_head_dispatch(const uint8_t*, void*, int, int, int, int, hipStream_t, long);                      // frames.hip
 int compact_tail_u8(const float*, const uint8_t*, uint8_t*, int, int, int, int, hipStream_t);
+int yuv420_forward_check(const char*, int, int, int, int, const uint8_t*, const ResrYuvDesc*);
+int yuv_head_dispatch(const uint8_t*, void*, int, int, int, int, hipStream_t, long, const ResrYuvDesc*);
+int compact_tail_yuv420(const float*, const uint8_t*, uint8_t*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
 int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, bool,
                 const void*, ResizeGeom*);                                                                      // image_resize.hip
 int compact_tail_u8_scaled(const float*, const uint8_t*, uint8_t*, int, int, int, int, const int32_t*, const float*, const int32_t*,
@@ -177,6 +181,7 @@ namespace {
 // The launch sequence both entries share.  U8 = false: x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32 (layout.hip head, compact_tail);
 // U8 = true: x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8 (frames.hip: the conversions fused into the head and the tail; the convs,
 // the packed weights and the workspace plan are the same).  sc (U8 only): the resized tail of compact_forward_u8_scaled.
+// yuv (U8 only): x and y are YUV 4:2:0 frames [N,3H/2,W] -> [N,3sH/2,sW], the colour conversions fused into the same two kernels.
 // Every argument check comes before the first launch.
 struct ScaledTail {
     int oh, ow, taps_y, taps_x;
@@ -186,11 +191,16 @@ struct ScaledTail {
 
 template <bool U8>
 int compact_run(const ResrCompactDesc* d, const void* x, const float* params, const void* packed, void* workspace,
-                size_t workspace_bytes, void* y, hipStream_t st, const char* who, const ScaledTail* sc = nullptr) {
+                size_t workspace_bytes, void* y, hipStream_t st, const char* who, const ScaledTail* sc = nullptr,
+                const ResrYuvDesc* yuv = nullptr) {
     CPlan p;
     if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "%s: bad descriptor", who);
     if (!x || !params || !packed || !workspace || !y) return fail(RESR_ERR_ARG, "%s: null argument", who);
-    if (U8 && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
+    if (U8 && !yuv && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
+    if (yuv) {
+        const int rc = yuv420_forward_check(who, d->n, d->h, d->w, d->upscale, (const uint8_t*)y, yuv);
+        if (rc) return rc;
+    }
     ResizeGeom geom;
     if (sc) {
         const int rc = resize_plan(who, d->n, 3, d->h * d->upscale, d->w * d->upscale, sc->oh, sc->ow, sc->idx_y, sc->w_y, sc->taps_y,
@@ -207,7 +217,8 @@ int compact_run(const ResrCompactDesc* d, const void* x, const float* params, co
     float* t = reinterpret_cast<float*>(base + p.off_t);
     const int N = d->n, H = d->h, W = d->w;
     const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
-    int rc = U8 ? u8_head_dispatch((const uint8_t*)x, xin, N, H, W, d->dtype, st, (long)lo32)
+    int rc = yuv ? yuv_head_dispatch((const uint8_t*)x, xin, N, H, W, d->dtype, st, (long)lo32, yuv)
+             : U8 ? u8_head_dispatch((const uint8_t*)x, xin, N, H, W, d->dtype, st, (long)lo32)
                 : nchw_to_nhwc_dispatch((const float*)x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) {
@@ -248,6 +259,7 @@ int compact_run(const ResrCompactDesc* d, const void* x, const float* params, co
     if (U8 && sc)
         return compact_tail_u8_scaled(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, sc->idx_y, sc->w_y, sc->idx_x, sc->w_x,
                                       &geom, st);
+    if (yuv) return compact_tail_yuv420(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, yuv, st);
     if (U8) return compact_tail_u8(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, st);
     return compact_tail(t, (const float*)x, (float*)y, N, H, W, d->upscale, st);
 }
@@ -262,6 +274,12 @@ int compact_forward(const ResrCompactDesc* d, const float* x, const float* param
 int compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
                        size_t workspace_bytes, uint8_t* y, hipStream_t st) {
     return compact_run<true>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward_u8");
+}
+
+int compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
+                           size_t workspace_bytes, uint8_t* y, const ResrYuvDesc* yuv, hipStream_t st) {
+    if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420: null argument");
+    return compact_run<true>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward_yuv420", nullptr, yuv);
 }
 
 int compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,

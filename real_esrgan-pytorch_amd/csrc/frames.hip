@@ -4,6 +4,8 @@
 //   compact_tail_u8: t [N,3S^2,H,W] fp32 + the u8 input frame -> u8 [N,H*S,W*S,3]   (pixel-shuffle + residual + quantise)
 //   u8_to_nchw     : u8 [N,H,W,3] -> fp32 [N,3,H,W]                (models whose first kernel is not ours to fuse)
 //   nchw_to_u8     : fp32 [N,3,H,W] -> u8 [N,H,W,3]                (... and whose last one is not: RRDB Generator, the tiler)
+//   yuv_head, compact_tail_yuv420 : the two fused ends with YUV 4:2:0 frames [N,3H/2,W] (I420 / NV12) in place of RGB ones
+//   yuv420_to_rgb, rgb_to_yuv420  : the integer colour conversions on their own, u8 [N,3H/2,W] <-> u8 [N,H,W,3]
 //
 // The result is DEFINED as what the float path followed by imgproc.tensor_to_image produces, bit for bit:
 //   in : x = (float)u8 / 255.0f, one IEEE division (numpy's astype(float32) / 255.0), then converted to the model's type exactly
@@ -11,6 +13,7 @@
 //   out: v = t + x (fp32, the single add of compact_tail_kernel; the generic kernel has no add), then v * 255.0f, clamp to
 //        [0, 255], truncate -- in this order, nothing re-associated (t * 255 + x * 255 is another number).
 // A NaN in v is outside the contract (the float path's astype(uint8) of a NaN is undefined too); here it quantises to 0.
+// The YUV path is DEFINED as rgb_to_yuv420(the u8 path(yuv420_to_rgb(frame))), two integer functions of bytes (include/resr.h).
 // Every index that can pass 2^31 is 64-bit.  Vector stores only.
 #include "common.h"
 
@@ -114,7 +117,311 @@ __global__ __launch_bounds__(256) void u8_to_nchw_kernel(const uint8_t* __restri
     for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + r] = u8_unit(src[p * 3 + c]);
 }
 
+// ---- YUV 4:2:0 (include/resr.h: the integer definition; frames.py holds it once more in numpy, which the tests compare with) ----
+
+// The three samples of pixel (y, x) of one image of luma size h x w (both even): chroma is replicated over its 2x2 block.
+__device__ __forceinline__ void yuv_load(const uint8_t* __restrict__ img, int h, int w, int layout, int y, int x, int& Y, int& Cb,
+                                         int& Cr) {
+    const long luma = (long)h * w;
+    Y = img[(long)y * w + x];
+    if (layout == RESR_YUV_NV12) {
+        const uint8_t* c = img + luma + (long)(y >> 1) * w + (x & ~1);
+        Cb = c[0];
+        Cr = c[1];
+    } else {
+        const long o = (long)(y >> 1) * (w >> 1) + (x >> 1);
+        Cb = img[luma + o];
+        Cr = img[luma + (luma >> 2) + o];
+    }
+}
+
+__device__ __forceinline__ void yuv_to_rgb(const ResrYuvDesc& q, int Y, int Cb, int Cr, unsigned (&rgb)[3]) {
+    const int y = Y - 16, cb = Cb - 128, cr = Cr - 128;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        int v = (q.iq[3 * c] * y + q.iq[3 * c + 1] * cb + q.iq[3 * c + 2] * cr + 32768) >> 16;
+        v = v > 0 ? v : 0;
+        rgb[c] = (unsigned)(v < 255 ? v : 255);
+    }
+}
+
+__device__ __forceinline__ unsigned luma_of(const ResrYuvDesc& q, unsigned r, unsigned g, unsigned b) {
+    return (unsigned)((q.fq[0] * (int)r + q.fq[1] * (int)g + q.fq[2] * (int)b + (16 << 16) + 32768) >> 16) & 255u;
+}
+
+// row = 1: Cb, row = 2: Cr; s: the sums of a 2x2 block's four pixels
+__device__ __forceinline__ unsigned chroma_of(const ResrYuvDesc& q, int row, const int (&s)[3]) {
+    return (unsigned)((q.fq[3 * row] * s[0] + q.fq[3 * row + 1] * s[1] + q.fq[3 * row + 2] * s[2] + (128 << 18) + (1 << 17)) >> 18) & 255u;
+}
+
+__device__ __forceinline__ unsigned pack4(const unsigned* b) { return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); }
+
+// u8_head_kernel with a YUV source: piece 0 forms the RGB bytes from (Y, Cb, Cr), then does what u8_head_kernel does.
+template <typename T>
+__global__ __launch_bounds__(256) void yuv_head_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, long px, long lo_off, int h,
+                                                       int w, ResrYuvDesc q) {
+    constexpr int E = 16 / (int)sizeof(T);
+    constexpr int PIECES = 32 / E;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= px * PIECES) return;
+    const long p = idx / PIECES;
+    const int piece = (int)(idx - p * PIECES);
+    uint4 out = make_uint4(0u, 0u, 0u, 0u), outl = make_uint4(0u, 0u, 0u, 0u);
+    if (piece == 0) {
+        const long plane = (long)h * w;
+        const long b = p / plane, r = p - b * plane;
+        const int yy = (int)(r / w), xx = (int)(r - (long)yy * w);
+        int Y, Cb, Cr;
+        yuv_load(src + b * (plane + (plane >> 1)), h, w, q.layout, yy, xx, Y, Cb, Cr);
+        unsigned rgb[3];
+        yuv_to_rgb(q, Y, Cb, Cr, rgb);
+        T* o = reinterpret_cast<T*>(&out);
+        T* ol = reinterpret_cast<T*>(&outl);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float v = u8_unit(rgb[c]);
+            if constexpr (sizeof(T) == 2) {
+                if (lo_off) split_f16(v, o[c], ol[c]);
+                else o[c] = (T)v;
+            } else {
+                o[c] = (T)v;
+            }
+        }
+    }
+    *reinterpret_cast<uint4*>(dst + p * 32 + piece * E) = out;
+    if (sizeof(T) == 2 && lo_off) *reinterpret_cast<uint4*>(dst + lo_off + p * 32 + piece * E) = outl;
+}
+
+// compact_tail_u8_kernel with YUV at both ends.  A thread owns 2 rows x 8 columns of the output, i.e. four whole chroma samples;
+// adjacent lanes are adjacent in x.  Per pixel: the residual byte is recomputed from the YUV input (no RGB frame exists here),
+// v = t + u8_unit(rgb_in), quantise_u8(v) unchanged, then the integer RGB -> YUV formula.  wide (the output width is a multiple of 8,
+// y 8-byte aligned: then every plane row, both chroma bases and the per-image stride are aligned as the stores below need): two
+// 8-byte Y stores and a dword each of Cb and Cr (I420) or one 8-byte CbCr store (NV12); a wavefront writes 512 contiguous bytes
+// per Y row.  Every other even width: byte stores, the columns past the right edge skipped (rows always come in whole pairs).
+template <int S, int LAYOUT>
+__global__ __launch_bounds__(256) void compact_tail_yuv420_kernel(const float* __restrict__ t, const uint8_t* __restrict__ x,
+                                                                  uint8_t* __restrict__ y, int n, int h, int w, int wide, ResrYuvDesc q) {
+    const int HS = h * S, WS = w * S;
+    const int groups = (WS + 7) >> 3;
+    const long total = (long)n * (HS >> 1) * groups;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const long rp = gid / groups;              // b * HS / 2 + Y / 2
+    const int X0 = (int)(gid - rp * groups) * 8;
+    const long b = rp / (HS >> 1);
+    const int Y0 = (int)(rp - b * (HS >> 1)) * 2;
+    const long plane = (long)h * w;
+    const uint8_t* xin = x + b * (plane + (plane >> 1));
+    const float* tb = t + b * 3 * S * S * plane;
+    unsigned yb[2][8];
+    int sum[4][3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) sum[j][0] = sum[j][1] = sum[j][2] = 0;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        // an even S keeps a row pair inside one LR row, a divisor of 8 keeps k / S a constant: the loads below then coincide
+        const int yy = S % 2 == 0 ? Y0 / S : (Y0 + r) / S;
+        const int sy = Y0 + r - yy * S;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int X = X0 + k;
+            yb[r][k] = 0u;
+            if (X < WS) {
+                const int xx = 8 % S == 0 ? X0 / S + k / S : X / S;
+                const int sx = X - xx * S;
+                int Yi, Cb, Cr;
+                yuv_load(xin, h, w, LAYOUT, yy, xx, Yi, Cb, Cr);
+                unsigned rgb_in[3], o[3];
+                yuv_to_rgb(q, Yi, Cb, Cr, rgb_in);
+                const float* tp = tb + (long)(sy * S + sx) * plane + (long)yy * w + xx;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float v = tp[(long)c * S * S * plane] + u8_unit(rgb_in[c]);
+                    o[c] = quantise_u8(v);
+                    sum[k >> 1][c] += (int)o[c];
+                }
+                yb[r][k] = luma_of(q, o[0], o[1], o[2]);
+            }
+        }
+    }
+    unsigned cb[4], cr[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        cb[j] = chroma_of(q, 1, sum[j]);
+        cr[j] = chroma_of(q, 2, sum[j]);
+    }
+    const long luma = (long)HS * WS;
+    uint8_t* yo = y + b * (luma + (luma >> 1));
+    uint8_t* row0 = yo + (long)Y0 * WS + X0;
+    if (wide) {
+        *reinterpret_cast<uint2*>(row0) = make_uint2(pack4(yb[0]), pack4(yb[0] + 4));
+        *reinterpret_cast<uint2*>(row0 + WS) = make_uint2(pack4(yb[1]), pack4(yb[1] + 4));
+        if constexpr (LAYOUT == RESR_YUV_NV12) {
+            *reinterpret_cast<uint2*>(yo + luma + (long)(Y0 >> 1) * WS + X0) =
+                make_uint2(cb[0] | (cr[0] << 8) | (cb[1] << 16) | (cr[1] << 24), cb[2] | (cr[2] << 8) | (cb[3] << 16) | (cr[3] << 24));
+        } else {
+            uint8_t* c0 = yo + luma + (long)(Y0 >> 1) * (WS >> 1) + (X0 >> 1);
+            *reinterpret_cast<unsigned*>(c0) = pack4(cb);
+            *reinterpret_cast<unsigned*>(c0 + (luma >> 2)) = pack4(cr);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (X0 + k < WS) {
+                row0[k] = (uint8_t)yb[0][k];
+                row0[WS + k] = (uint8_t)yb[1][k];
+            }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (X0 + 2 * j < WS) {
+                if constexpr (LAYOUT == RESR_YUV_NV12) {
+                    uint8_t* c0 = yo + luma + (long)(Y0 >> 1) * WS + X0 + 2 * j;
+                    c0[0] = (uint8_t)cb[j];
+                    c0[1] = (uint8_t)cr[j];
+                } else {
+                    uint8_t* c0 = yo + luma + (long)(Y0 >> 1) * (WS >> 1) + (X0 >> 1) + j;
+                    c0[0] = (uint8_t)cb[j];
+                    c0[luma >> 2] = (uint8_t)cr[j];
+                }
+            }
+    }
+}
+
+// The generic conversions: a thread owns 2 rows x 4 columns (two chroma samples).  wide (w a multiple of 4, the HWC side 4-byte
+// aligned): the 12 RGB bytes of a row are three dwords; the YUV side of rgb_to_yuv420 is a dword per Y row and a dword of CbCr
+// (NV12) or two 2-byte stores (I420).  Every other even width moves bytes, the columns past the right edge skipped.
+__global__ __launch_bounds__(256) void yuv420_to_rgb_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int h,
+                                                            int w, int wide, ResrYuvDesc q) {
+    const int groups = (w + 3) >> 2;
+    const long total = (long)n * (h >> 1) * groups;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const long rp = gid / groups;
+    const int X0 = (int)(gid - rp * groups) * 4;
+    const long b = rp / (h >> 1);
+    const int Y0 = (int)(rp - b * (h >> 1)) * 2;
+    const long plane = (long)h * w;
+    const uint8_t* img = src + b * (plane + (plane >> 1));
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        unsigned bytes[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            unsigned rgb[3] = {0u, 0u, 0u};
+            if (X0 + k < w) {
+                int Y, Cb, Cr;
+                yuv_load(img, h, w, q.layout, Y0 + r, X0 + k, Y, Cb, Cr);
+                yuv_to_rgb(q, Y, Cb, Cr, rgb);
+            }
+            bytes[3 * k] = rgb[0];
+            bytes[3 * k + 1] = rgb[1];
+            bytes[3 * k + 2] = rgb[2];
+        }
+        uint8_t* o = dst + (b * plane + (long)(Y0 + r) * w + X0) * 3;
+        if (wide) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) reinterpret_cast<unsigned*>(o)[d] = pack4(bytes + 4 * d);
+        } else {
+            const int left = (w - X0 < 4 ? w - X0 : 4) * 3;
+#pragma unroll
+            for (int i = 0; i < 12; ++i)
+                if (i < left) o[i] = (uint8_t)bytes[i];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int h,
+                                                            int w, int wide, ResrYuvDesc q) {
+    const int groups = (w + 3) >> 2;
+    const long total = (long)n * (h >> 1) * groups;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return;
+    const long rp = gid / groups;
+    const int X0 = (int)(gid - rp * groups) * 4;
+    const long b = rp / (h >> 1);
+    const int Y0 = (int)(rp - b * (h >> 1)) * 2;
+    const long plane = (long)h * w;
+    unsigned yb[2][4];
+    int sum[2][3] = {{0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const uint8_t* in = src + (b * plane + (long)(Y0 + r) * w + X0) * 3;
+        unsigned bytes[12];
+        if (wide) {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) {
+                const unsigned v = reinterpret_cast<const unsigned*>(in)[d];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) bytes[4 * d + i] = (v >> (8 * i)) & 255u;
+            }
+        } else {
+            const int left = (w - X0 < 4 ? w - X0 : 4) * 3;
+#pragma unroll
+            for (int i = 0; i < 12; ++i) bytes[i] = i < left ? in[i] : 0u;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            yb[r][k] = luma_of(q, bytes[3 * k], bytes[3 * k + 1], bytes[3 * k + 2]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sum[k >> 1][c] += (int)bytes[3 * k + c];
+        }
+    }
+    unsigned cb[2], cr[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        cb[j] = chroma_of(q, 1, sum[j]);
+        cr[j] = chroma_of(q, 2, sum[j]);
+    }
+    uint8_t* yo = dst + b * (plane + (plane >> 1));
+    uint8_t* row0 = yo + (long)Y0 * w + X0;
+    const bool nv12 = q.layout == RESR_YUV_NV12;
+    uint8_t* c0 = nv12 ? yo + plane + (long)(Y0 >> 1) * w + X0 : yo + plane + (long)(Y0 >> 1) * (w >> 1) + (X0 >> 1);
+    if (wide) {
+        *reinterpret_cast<unsigned*>(row0) = pack4(yb[0]);
+        *reinterpret_cast<unsigned*>(row0 + w) = pack4(yb[1]);
+        if (nv12) {
+            *reinterpret_cast<unsigned*>(c0) = cb[0] | (cr[0] << 8) | (cb[1] << 16) | (cr[1] << 24);
+        } else {
+            *reinterpret_cast<unsigned short*>(c0) = (unsigned short)(cb[0] | (cb[1] << 8));
+            *reinterpret_cast<unsigned short*>(c0 + (plane >> 2)) = (unsigned short)(cr[0] | (cr[1] << 8));
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (X0 + k < w) {
+                row0[k] = (uint8_t)yb[0][k];
+                row0[w + k] = (uint8_t)yb[1][k];
+            }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (X0 + 2 * j < w) {
+                if (nv12) {
+                    c0[2 * j] = (uint8_t)cb[j];
+                    c0[2 * j + 1] = (uint8_t)cr[j];
+                } else {
+                    c0[j] = (uint8_t)cb[j];
+                    c0[(plane >> 2) + j] = (uint8_t)cr[j];
+                }
+            }
+    }
+}
+
 bool grid_ok(long threads) { return threads > 0 && (threads + 255) / 256 <= 0x7fffffffL; }
+
+bool yuv_ok(const ResrYuvDesc* q) { return q && (q->layout == RESR_YUV_I420 || q->layout == RESR_YUV_NV12); }
+
+template <int S, int LAYOUT>
+void launch_tail_yuv_layout(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int wide, const ResrYuvDesc& q, hipStream_t st) {
+    const long threads = (long)n * (h * S / 2) * ((w * S + 7) / 8);
+    hipLaunchKernelGGL((compact_tail_yuv420_kernel<S, LAYOUT>), dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, t, x, y, n, h, w,
+                       wide, q);
+}
+
+template <int S>
+void launch_tail_yuv(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int wide, const ResrYuvDesc& q, hipStream_t st) {
+    if (q.layout == RESR_YUV_NV12) launch_tail_yuv_layout<S, RESR_YUV_NV12>(t, x, y, n, h, w, wide, q, st);
+    else launch_tail_yuv_layout<S, RESR_YUV_I420>(t, x, y, n, h, w, wide, q, st);
+}
 
 template <int S, bool RES>
 void launch_tail(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, hipStream_t st) {
@@ -178,6 +485,86 @@ int nchw_to_u8_dispatch(const float* src, uint8_t* dst, int n, int h, int w, hip
     launch_tail<1, false>(src, nullptr, dst, n, h, w, st);
     prof_after(st, 31031, 0.0, (double)total * 15.0);
     RESR_CHECK_LAUNCH("nchw_to_u8_kernel");
+    return RESR_OK;
+}
+
+// ---- YUV 4:2:0 ----
+
+// Everything compact_forward_yuv420 has to refuse about its frames, before its first launch (d->h, d->w even: the output's are too).
+int yuv420_forward_check(const char* who, int n, int h, int w, int s, const uint8_t* y, const ResrYuvDesc* q) {
+    if (!yuv_ok(q)) return fail(RESR_ERR_ARG, "%s: the YUV descriptor is null or its layout is neither RESR_YUV_I420 nor RESR_YUV_NV12", who);
+    if ((h & 1) || (w & 1)) return fail(RESR_ERR_ARG, "%s: a 4:2:0 frame has an even height and width, got %dx%d", who, h, w);
+    if ((w * s) % 8 == 0 && ((size_t)y & 7) != 0) return fail(RESR_ERR_ARG, "%s: y_yuv must be 8-byte aligned at an output width of %d", who, w * s);
+    if (!grid_ok((long)n * (h * s / 2) * ((w * s + 7) / 8))) return fail(RESR_ERR_ARG, "%s: %dx%dx%d beyond the grid", who, n, h * s, w * s);
+    return RESR_OK;
+}
+
+int yuv_head_dispatch(const uint8_t* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q) {
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || (h & 1) || (w & 1) || !yuv_ok(q)) return fail(RESR_ERR_ARG, "yuv_head: bad argument");
+    const long px = (long)n * h * w;
+    const int pieces = dtype != RESR_F32 ? 4 : 8;
+    if (!grid_ok(px * pieces)) return fail(RESR_ERR_ARG, "yuv_head: %ld pixels beyond the grid", px);
+    const dim3 grid((unsigned)((px * pieces + 255) / 256));
+    if (dtype != RESR_F16X2) lo_off = 0;
+    prof_before(st);
+    if (dtype != RESR_F32)
+        hipLaunchKernelGGL(yuv_head_kernel<half_t>, grid, dim3(256), 0, st, src, (half_t*)dst, px, lo_off, h, w, *q);
+    else
+        hipLaunchKernelGGL(yuv_head_kernel<float>, grid, dim3(256), 0, st, src, (float*)dst, px, 0L, h, w, *q);
+    prof_after(st, 31021, 0.0, (double)px * (1.5 + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
+    RESR_CHECK_LAUNCH("yuv_head_kernel");
+    return RESR_OK;
+}
+
+int compact_tail_yuv420(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, const ResrYuvDesc* q, hipStream_t st) {
+    const int rc = yuv420_forward_check("compact_tail_yuv420", n, h, w, s, y, q);
+    if (rc) return rc;
+    const int wide = (w * s) % 8 == 0;
+    prof_before(st);
+    switch (s) {
+        case 1: launch_tail_yuv<1>(t, x, y, n, h, w, wide, *q, st); break;
+        case 2: launch_tail_yuv<2>(t, x, y, n, h, w, wide, *q, st); break;
+        case 3: launch_tail_yuv<3>(t, x, y, n, h, w, wide, *q, st); break;
+        case 4: launch_tail_yuv<4>(t, x, y, n, h, w, wide, *q, st); break;
+        default: return fail(RESR_ERR_ARG, "compact_tail_yuv420: upscale %d", s);
+    }
+    // per LR pixel: 3 s^2 floats of t, 1.5 bytes of x, 1.5 s^2 bytes out
+    prof_after(st, 31040 + s, 0.0, (double)n * h * w * (s * s * 13.5 + 1.5));
+    RESR_CHECK_LAUNCH("compact_tail_yuv420_kernel");
+    return RESR_OK;
+}
+
+namespace {
+int yuv420_convert_check(const char* who, const uint8_t* src, const uint8_t* dst, const uint8_t* hwc, int n, int h, int w,
+                         const ResrYuvDesc* q) {
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "%s: bad argument (n=%d h=%d w=%d)", who, n, h, w);
+    if (!yuv_ok(q)) return fail(RESR_ERR_ARG, "%s: the YUV descriptor is null or its layout is neither RESR_YUV_I420 nor RESR_YUV_NV12", who);
+    if ((h & 1) || (w & 1)) return fail(RESR_ERR_ARG, "%s: a 4:2:0 frame has an even height and width, got %dx%d", who, h, w);
+    if (w % 4 == 0 && ((((size_t)dst | (size_t)hwc) & 3) != 0)) return fail(RESR_ERR_ARG, "%s: 4-byte aligned frames at a width of %d", who, w);
+    if (!grid_ok((long)n * (h / 2) * ((w + 3) / 4))) return fail(RESR_ERR_ARG, "%s: %dx%dx%d beyond the grid", who, n, h, w);
+    return RESR_OK;
+}
+}  // namespace
+
+int yuv420_to_rgb_dispatch(const uint8_t* src, uint8_t* dst, int n, int h, int w, const ResrYuvDesc* q, hipStream_t st) {
+    const int rc = yuv420_convert_check("yuv420_to_rgb", src, dst, dst, n, h, w, q);
+    if (rc) return rc;
+    const long threads = (long)n * (h / 2) * ((w + 3) / 4);
+    prof_before(st);
+    hipLaunchKernelGGL(yuv420_to_rgb_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, src, dst, n, h, w, (int)(w % 4 == 0), *q);
+    prof_after(st, 31032, 0.0, (double)n * h * w * 4.5);
+    RESR_CHECK_LAUNCH("yuv420_to_rgb_kernel");
+    return RESR_OK;
+}
+
+int rgb_to_yuv420_dispatch(const uint8_t* src, uint8_t* dst, int n, int h, int w, const ResrYuvDesc* q, hipStream_t st) {
+    const int rc = yuv420_convert_check("rgb_to_yuv420", src, dst, src, n, h, w, q);
+    if (rc) return rc;
+    const long threads = (long)n * (h / 2) * ((w + 3) / 4);
+    prof_before(st);
+    hipLaunchKernelGGL(rgb_to_yuv420_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, src, dst, n, h, w, (int)(w % 4 == 0), *q);
+    prof_after(st, 31033, 0.0, (double)n * h * w * 4.5);
+    RESR_CHECK_LAUNCH("rgb_to_yuv420_kernel");
     return RESR_OK;
 }
 

@@ -29,10 +29,24 @@ OUTSCALE -- a final size that is not the network's factor (upstream's `-s / --ou
 A model with a fused entry runs `resr_compact_forward_u8_scaled` (the full-size frame exists as LDS tiles only); every other case is
 `super_resolve` -> `resr_image_resize` with uint8 output, the same device routine, hence the same bits.  A frame too small for the
 reference's symmetric edge copy raises ValueError before any launch, as the reference's `image_resize` raises.
+
+YUV 4:2:0 -- what video decoders deliver and encoders consume (NV12 from hardware, I420 / `yuv420p` from software): 1.5 bytes per
+pixel instead of 3, which halves every byte count that bounds a stream.  A frame of luma size H x W (both even) is a uint8 array
+[3H/2, W] (the usual numpy / OpenCV view; batches [N,3H/2,W], contiguous): `layout="i420"` is Y [H,W], Cb [H/2,W/2], Cr [H/2,W/2];
+`layout="nv12"` is Y [H,W], then [H/2,W/2,2] interleaved Cb,Cr.  The path is DEFINED as a composition over the RGB one, bit for bit:
+
+    upscale_yuv420(model, f) == rgb_to_yuv420_np(upscale_u8(model, yuv420_to_rgb_np(f)))
+
+and the two colour conversions are integer functions of bytes (studio range, BT.601 or BT.709, Q16 tables `yuv420_tables`, chroma
+replicated on the way in and box-averaged unrounded on the way out): `yuv420_to_rgb_np` / `rgb_to_yuv420_np` below ARE the
+definition; `yuv420_to_rgb` / `rgb_to_yuv420` are the same functions on the device, one launch each.  A model with a fused entry
+(`SRVGGNetCompact.forward_yuv420`: both conversions inside the compact net's first and last kernel) runs it when the frame fits one
+call; every other case (the RRDB `Generator`, tiled frames, outscale) is the composition of the device launches.
 """
 from __future__ import annotations
 
 import collections
+import functools
 import math
 from typing import Deque, Iterable, Iterator, List, Optional, Tuple
 
@@ -41,7 +55,11 @@ import torch
 
 from . import _lib, tiling
 
-__all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream", "output_size", "check_outscale"]
+__all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream", "output_size", "check_outscale", "yuv420_tables", "yuv420_to_rgb_np",
+           "rgb_to_yuv420_np", "yuv420_to_rgb", "rgb_to_yuv420", "upscale_yuv420"]
+
+YUV_LAYOUTS = {"i420": _lib.YUV_I420, "nv12": _lib.YUV_NV12}
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}          # (Kr, Kb); Kg = 1 - Kr - Kb
 
 
 def check_outscale(outscale, s: int, what: str) -> Optional[float]:
@@ -118,14 +136,170 @@ def upscale_u8(model, frames: torch.Tensor, halo: Optional[int] = None, outscale
     return resize_with_plan(tiling.super_resolve(model, from_u8(frames), halo), plan, u8=True)
 
 
+# ---- YUV 4:2:0 ----------------------------------------------------------------------------------------------------------------
+def _yuv_names(layout: str, matrix: str, what: str) -> None:
+    if layout not in YUV_LAYOUTS:
+        raise ValueError(f"{what}: layout must be one of {sorted(YUV_LAYOUTS)}, got {layout!r}")
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"{what}: matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}")
+
+
+def yuv420_tables(matrix: str = "bt601", quantised: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """(FQ, IQ), int32 [3,3]: the Q16 tables of the studio-range conversions.  F (per uint8 level; rows Y, Cb, Cr over R, G, B) and
+    I (rows R, G, B over Y - 16, Cb - 128, Cr - 128) are computed in float64 from the matrix' (Kr, Kb); FQ = rint(F * 65536),
+    IQ = rint(I * 65536).  `quantised=False` returns the float64 (F, I) themselves (bt601: F * 255 and I / 255 are the tables the
+    reference prints in `rgb2ycbcr` / `ycbcr2rgb`)."""
+    _yuv_names("i420", matrix, "yuv420_tables")
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    f = np.array([[219 * kr, 219 * kg, 219 * kb],
+                  [-112 * kr / (1 - kb), -112 * kg / (1 - kb), 112.0],
+                  [112.0, -112 * kg / (1 - kr), -112 * kb / (1 - kr)]], dtype=np.float64) / 255.0
+    a, c = 255.0 / 219.0, 255.0 / 224.0
+    i = np.array([[a, 0.0, c * 2 * (1 - kr)],
+                  [a, -c * 2 * (1 - kb) * kb / kg, -c * 2 * (1 - kr) * kr / kg],
+                  [a, c * 2 * (1 - kb), 0.0]], dtype=np.float64)
+    if not quantised:
+        return f, i
+    return np.rint(f * 65536).astype(np.int32), np.rint(i * 65536).astype(np.int32)
+
+
+def _yuv_geometry(shape, what: str) -> Tuple[int, int]:
+    """(H, W) of the luma plane of a [..., 3H/2, W] array."""
+    if len(shape) < 2 or shape[-2] < 3 or shape[-2] % 3 or shape[-1] < 2 or shape[-1] % 2:
+        raise ValueError(f"{what}: a 4:2:0 frame is [3H/2, W] with H and W even (rows a multiple of 3), got {tuple(shape)}")
+    return shape[-2] // 3 * 2, shape[-1]
+
+
+def yuv420_to_rgb_np(frames: np.ndarray, layout: str = "i420", matrix: str = "bt601") -> np.ndarray:
+    """THE DEFINITION (host, numpy): uint8 [..., 3H/2, W] -> uint8 [..., H, W, 3].  Pixel (y, x) takes Y[y,x], Cb[y//2,x//2],
+    Cr[y//2,x//2]; rgb[c] = clamp((IQ[c] . (Y - 16, Cb - 128, Cr - 128) + 32768) >> 16, 0, 255), int32, >> = floor.  Every byte
+    value is legal input."""
+    _yuv_names(layout, matrix, "yuv420_to_rgb_np")
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint8:
+        raise ValueError(f"yuv420_to_rgb_np: expected uint8, got {frames.dtype}")
+    h, w = _yuv_geometry(frames.shape, "yuv420_to_rgb_np")
+    lead = frames.shape[:-2]
+    y = frames[..., :h, :].astype(np.int32) - 16
+    chroma = frames[..., h:, :].reshape(lead + (-1,))
+    if layout == "nv12":
+        pairs = chroma.reshape(lead + (h // 2, w // 2, 2))
+        cb, cr = pairs[..., 0], pairs[..., 1]
+    else:
+        planes = chroma.reshape(lead + (2, h // 2, w // 2))
+        cb, cr = planes[..., 0, :, :], planes[..., 1, :, :]
+    cb = np.repeat(np.repeat(cb.astype(np.int32) - 128, 2, axis=-2), 2, axis=-1)
+    cr = np.repeat(np.repeat(cr.astype(np.int32) - 128, 2, axis=-2), 2, axis=-1)
+    iq = yuv420_tables(matrix)[1]
+    rgb = np.stack([(int(iq[c, 0]) * y + int(iq[c, 1]) * cb + int(iq[c, 2]) * cr + 32768) >> 16 for c in range(3)], axis=-1)
+    return np.clip(rgb, 0, 255).astype(np.uint8)
+
+
+def rgb_to_yuv420_np(rgb: np.ndarray, layout: str = "i420", matrix: str = "bt601") -> np.ndarray:
+    """THE DEFINITION (host, numpy): uint8 [..., H, W, 3] (H, W even) -> uint8 [..., 3H/2, W].  Y = (FQ[0] . rgb + (16 << 16) +
+    32768) >> 16 per pixel; Cb = (FQ[1] . S + (128 << 18) + (1 << 17)) >> 18 per 2x2 block, S the sum of its four (R, G, B), Cr
+    likewise with FQ[2]: a centre-sited box average of the unrounded chroma.  No clamp is needed: over all RGB triples the
+    outputs lie in Y 16..235, Cb / Cr 16..240."""
+    _yuv_names(layout, matrix, "rgb_to_yuv420_np")
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim < 3 or rgb.shape[-1] != 3 or rgb.shape[-3] < 2 or rgb.shape[-3] % 2 or rgb.shape[-2] < 2 or rgb.shape[-2] % 2:
+        raise ValueError(f"rgb_to_yuv420_np: expected uint8 [..., H, W, 3] with H and W even, got {rgb.dtype} {rgb.shape}")
+    lead, (h, w) = rgb.shape[:-3], rgb.shape[-3:-1]
+    fq = yuv420_tables(matrix)[0].astype(np.int32)
+    v = rgb.astype(np.int32)
+    y = ((v * fq[0]).sum(-1) + (16 << 16) + 32768) >> 16
+    s = v.reshape(lead + (h // 2, 2, w // 2, 2, 3)).sum(axis=(-4, -2))
+    cb = ((s * fq[1]).sum(-1) + (128 << 18) + (1 << 17)) >> 18
+    cr = ((s * fq[2]).sum(-1) + (128 << 18) + (1 << 17)) >> 18
+    chroma = np.stack([cb, cr], axis=-1) if layout == "nv12" else np.stack([cb, cr], axis=-3)
+    out = np.concatenate([y.reshape(lead + (h * w,)), chroma.reshape(lead + (h * w // 2,))], axis=-1)
+    return out.reshape(lead + (h * 3 // 2, w)).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def yuv_desc(layout: str, matrix: str) -> _lib.YuvDesc:
+    """The ResrYuvDesc of include/resr.h for these names (cached: the tables are a pure function of them)."""
+    _yuv_names(layout, matrix, "yuv_desc")
+    fq, iq = yuv420_tables(matrix)
+    i9 = _lib.C.c_int32 * 9
+    return _lib.YuvDesc(YUV_LAYOUTS[layout], i9(*[int(v) for v in fq.reshape(-1)]), i9(*[int(v) for v in iq.reshape(-1)]))
+
+
+def check_yuv420(frames: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    """(n, H, W) of a uint8 [N,3H/2,W] device tensor; RuntimeError for anything else."""
+    _lib.require_cuda(frames, what)
+    if (frames.dtype != torch.uint8 or frames.dim() != 3 or min(frames.shape) < 1 or frames.shape[1] % 3 or frames.shape[2] % 2):
+        raise RuntimeError(f"{what}: expected a uint8 [N,3H/2,W] tensor with H and W even, got {frames.dtype} {tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise RuntimeError(f"{what}: frames must be contiguous (planes one after the other, as a video decoder leaves them)")
+    return frames.shape[0], frames.shape[1] // 3 * 2, frames.shape[2]
+
+
+@torch.no_grad()
+def yuv420_to_rgb(frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601") -> torch.Tensor:
+    """uint8 [N,3H/2,W] -> uint8 [N,H,W,3] on the device, one launch (resr_yuv420_to_rgb): `yuv420_to_rgb_np`, bit for bit."""
+    desc = yuv_desc(layout, matrix)
+    n, h, w = check_yuv420(frames, "yuv420_to_rgb")
+    rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=frames.device)
+    _lib.check(_lib.lib().resr_yuv420_to_rgb(_lib.ptr(frames), _lib.ptr(rgb), n, h, w, _lib.C.byref(desc), _lib.stream_ptr(frames)),
+               "resr_yuv420_to_rgb")
+    return rgb
+
+
+@torch.no_grad()
+def rgb_to_yuv420(rgb: torch.Tensor, layout: str = "i420", matrix: str = "bt601") -> torch.Tensor:
+    """uint8 [N,H,W,3] (H, W even) -> uint8 [N,3H/2,W] on the device, one launch (resr_rgb_to_yuv420): `rgb_to_yuv420_np`, bit for bit."""
+    desc = yuv_desc(layout, matrix)
+    _check_frames(rgb, "rgb_to_yuv420")
+    n, h, w, _ = rgb.shape
+    if h % 2 or w % 2:
+        raise RuntimeError(f"rgb_to_yuv420: a 4:2:0 frame has an even height and width, got {h}x{w}")
+    out = torch.empty((n, h * 3 // 2, w), dtype=torch.uint8, device=rgb.device)
+    _lib.check(_lib.lib().resr_rgb_to_yuv420(_lib.ptr(rgb), _lib.ptr(out), n, h, w, _lib.C.byref(desc), _lib.stream_ptr(rgb)),
+               "resr_rgb_to_yuv420")
+    return out
+
+
+def yuv420_output_size(h: int, w: int, s: int, outscale, what: str) -> Tuple[int, int]:
+    """`output_size`, which for a 4:2:0 result must be even both ways: ValueError otherwise (before any launch)."""
+    out_h, out_w = output_size(h, w, s, outscale)
+    if out_h % 2 or out_w % 2:
+        raise ValueError(f"{what}: outscale={outscale!r} turns {h}x{w} into {out_h}x{out_w}; a 4:2:0 frame needs an even height and width")
+    return out_h, out_w
+
+
+@torch.no_grad()
+def upscale_yuv420(model, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601", halo: Optional[int] = None,
+                   outscale: Optional[float] = None, plan=None) -> torch.Tensor:
+    """uint8 [N,3H/2,W] on the model's device -> uint8 [N,3sH/2,sW], same layout: bit for bit
+    `rgb_to_yuv420_np(upscale_u8(model, yuv420_to_rgb_np(frames)))` (module docstring).  The one place that chooses between the
+    fused call and the composition, as `upscale_u8` is for RGB; `halo`, `outscale` and `plan` are `upscale_u8`'s.  With `outscale`
+    the result is [N, 3 out_h / 2, out_w] for `output_size(H, W, s, outscale)`; an odd out_h or out_w is a ValueError before any
+    launch."""
+    yuv_desc(layout, matrix)
+    n, h, w = check_yuv420(frames, "upscale_yuv420")
+    s = model.upscale_factor
+    o = check_outscale(outscale, s, "upscale_yuv420")
+    if o is None and hasattr(model, "forward_yuv420") and tiling.fits_whole(model, n, h, w):
+        return model.forward_yuv420(frames, layout, matrix)
+    if o is not None:
+        yuv420_output_size(h, w, s, o, "upscale_yuv420")
+        if plan is None:
+            from .imgproc import ResizePlan
+            plan = ResizePlan(h * s, w * s, o / s, frames.device)         # ValueError before any launch, as in upscale_u8
+    rgb = upscale_u8(model, yuv420_to_rgb(frames, layout, matrix), halo, outscale=o, plan=plan)
+    return rgb_to_yuv420(rgb, layout, matrix)
+
+
 class _Slot:
     """One frame in flight: pinned host buffers, the device input, the events that order its three stages."""
 
-    def __init__(self, h: int, w: int, out_h: int, out_w: int, device) -> None:
-        self.pin_in = torch.empty((1, h, w, 3), dtype=torch.uint8, pin_memory=True)
-        self.pin_out = torch.empty((1, out_h, out_w, 3), dtype=torch.uint8, pin_memory=True)
+    def __init__(self, in_shape: Tuple[int, ...], out_shape: Tuple[int, ...], device) -> None:
+        self.pin_in = torch.empty((1,) + in_shape, dtype=torch.uint8, pin_memory=True)
+        self.pin_out = torch.empty((1,) + out_shape, dtype=torch.uint8, pin_memory=True)
         self.np_in, self.np_out = self.pin_in.numpy()[0], self.pin_out.numpy()[0]
-        self.dev_in = torch.empty((1, h, w, 3), dtype=torch.uint8, device=device)
+        self.dev_in = torch.empty((1,) + in_shape, dtype=torch.uint8, device=device)
         self.dev_out: Optional[torch.Tensor] = None      # held until the slot's next submit: its download has been waited for by then
         self.uploaded, self.computed, self.downloaded = (torch.cuda.Event() for _ in range(3))
         self.used = False
@@ -146,11 +320,21 @@ class FrameStream:
     another size drains the pipeline (pending results are kept, in order) and reallocates.  No graph capture here.
 
     `outscale` (module docstring): results are `output_size(H, W, s, outscale)` frames; the slots are sized by it and the tap
-    tables of the frame size are built once, kept with the slots and dropped with them on a change of size."""
+    tables of the frame size are built once, kept with the slots and dropped with them on a change of size.
 
-    def __init__(self, model, depth: int = 2, outscale: Optional[float] = None) -> None:
+    `pix_fmt`: "rgb24" (default: everything above) or a YUV 4:2:0 layout, "i420" / "nv12" (module docstring), with `matrix`
+    "bt601" / "bt709": `submit` takes a [3H/2, W] uint8 ndarray and `result` returns [3 out_h / 2, out_w]; each frame is
+    `upscale_yuv420` of it, the slots are half the bytes, everything else is as above."""
+
+    PIX_FMTS = ("rgb24", "i420", "nv12")
+
+    def __init__(self, model, depth: int = 2, outscale: Optional[float] = None, pix_fmt: str = "rgb24", matrix: str = "bt601") -> None:
         if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
             raise ValueError(f"FrameStream: depth must be an int >= 1, got {depth!r}")
+        if pix_fmt not in self.PIX_FMTS:
+            raise ValueError(f"FrameStream: pix_fmt must be one of {self.PIX_FMTS}, got {pix_fmt!r}")
+        _yuv_names("i420", matrix, "FrameStream")
+        self.pix_fmt, self.matrix = pix_fmt, matrix
         self.outscale = check_outscale(outscale, getattr(model, "upscale_factor", 0), "FrameStream")
         self._plan = None
         param = next(iter(model.parameters()), None)
@@ -170,6 +354,13 @@ class FrameStream:
         if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3 or min(frame.shape) < 1:
             got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
             raise ValueError(f"FrameStream: expected an HxWx3 uint8 ndarray, got {got}")
+
+    @staticmethod
+    def check_frame_yuv420(frame) -> None:
+        if (not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 2 or frame.shape[0] < 3 or frame.shape[0] % 3
+                or frame.shape[1] < 2 or frame.shape[1] % 2):
+            got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
+            raise ValueError(f"FrameStream: expected a [3H/2, W] uint8 ndarray with H and W even (a 4:2:0 frame), got {got}")
 
     def __len__(self) -> int:
         """Results not yet taken."""
@@ -194,22 +385,34 @@ class FrameStream:
                 st.synchronize()
         s = self.model.upscale_factor
         self._plan = None
+        if self.pix_fmt != "rgb24":
+            yuv420_output_size(h, w, s, self.outscale, "FrameStream")      # an odd result: ValueError before anything is allocated
         if self.outscale is not None:
             from .imgproc import ResizePlan
             self._plan = ResizePlan(h * s, w * s, self.outscale / s, self.device)
-        out_h, out_w = output_size(h, w, s, self.outscale)
+        if self.pix_fmt == "rgb24":
+            out_h, out_w = output_size(h, w, s, self.outscale)
+            in_shape, out_shape = (h, w, 3), (out_h, out_w, 3)
+        else:
+            out_h, out_w = yuv420_output_size(h, w, s, self.outscale, "FrameStream")
+            in_shape, out_shape = (h * 3 // 2, w), (out_h * 3 // 2, out_w)
         with torch.cuda.device(self.device):
-            self._slots = [_Slot(h, w, out_h, out_w, self.device) for _ in range(self.depth)]
+            self._slots = [_Slot(in_shape, out_shape, self.device) for _ in range(self.depth)]
         self._shape, self._next = (h, w), 0
 
     def submit(self, frame: np.ndarray) -> None:
         if self._closed:
             raise RuntimeError("FrameStream: closed")
-        self.check_frame(frame)
+        if self.pix_fmt == "rgb24":
+            self.check_frame(frame)
+            size = frame.shape[:2]
+        else:
+            self.check_frame_yuv420(frame)
+            size = (frame.shape[0] // 3 * 2, frame.shape[1])
         if len(self._pending) >= self.depth:
             raise RuntimeError(f"FrameStream: {self.depth} frames are pending already; take a result() first")
-        if frame.shape[:2] != self._shape:
-            self._allocate(frame.shape[0], frame.shape[1])
+        if size != self._shape:
+            self._allocate(*size)
         slot = self._slots[self._next]
         self._next = (self._next + 1) % self.depth
         np.copyto(slot.np_in, frame)                 # (the slot's previous upload finished before its result was handed back)
@@ -220,7 +423,10 @@ class FrameStream:
             slot.uploaded.record(self._up)
         with torch.cuda.stream(self._compute):
             self._compute.wait_event(slot.uploaded)
-            slot.dev_out = upscale_u8(self.model, slot.dev_in, outscale=self.outscale, plan=self._plan)
+            if self.pix_fmt == "rgb24":
+                slot.dev_out = upscale_u8(self.model, slot.dev_in, outscale=self.outscale, plan=self._plan)
+            else:
+                slot.dev_out = upscale_yuv420(self.model, slot.dev_in, self.pix_fmt, self.matrix, outscale=self.outscale, plan=self._plan)
             slot.computed.record(self._compute)
         with torch.cuda.stream(self._down):
             self._down.wait_event(slot.computed)

@@ -1,0 +1,111 @@
+"""Raw YUV 4:2:0 video through the frame path (frames.py, YUV 4:2:0): the shape that sits between the rawvideo pipes of a decoder
+and an encoder, with no colour conversion on the host and no dependency beyond this package.
+
+    python -m real_esrgan_pytorch_amd.inference_rawvideo --input in.yuv --output out.yuv --size 1920x1080 --weights_path g.pth \\
+        [--pix_fmt yuv420p|nv12 --matrix bt601|bt709 --model_type rrdb|compact --num_conv 16 --act_type prelu
+         --precision fast|exact16|strict --depth 2 --outscale 2]
+
+    ffmpeg -i in.mp4 -f rawvideo -pix_fmt yuv420p - | \\
+        python -m real_esrgan_pytorch_amd.inference_rawvideo --input - --output - --size 1920x1080 --model_type compact \\
+            --weights_path realesr-animevideov3.pth | \\
+        ffmpeg -f rawvideo -pix_fmt yuv420p -s 7680x4320 -r 24 -i - out.mp4
+
+`--input` / `--output`: a file, or `-` for stdin / stdout (every message then goes to stderr).  Frames of W * H * 3 / 2 bytes are
+read one after the other and streamed through `FrameStream(pix_fmt=...)` with `copy=False`; each written frame is
+`frames.upscale_yuv420` of the frame read, in the same pixel format.  The output size is printed (the encoder has to be told it).
+A trailing partial frame is an error that names its byte count.  The model is built and the checkpoint loaded as `inference.py`
+does (inference_frames.build_model).
+"""
+import argparse
+import contextlib
+import re
+import sys
+
+import numpy as np
+import torch
+
+from . import config
+from .frames import FrameStream, yuv420_output_size
+from .inference_frames import build_model
+
+PIX_FMTS = {"yuv420p": "i420", "nv12": "nv12"}      # the rawvideo names -> frames.py's layouts
+
+
+def parse_size(text: str):
+    """'WxH' -> (W, H), both even and positive."""
+    m = re.fullmatch(r"(\d+)[xX](\d+)", text or "")
+    if not m:
+        raise ValueError(f"--size must be WxH, got {text!r}")
+    w, h = int(m.group(1)), int(m.group(2))
+    if w < 2 or h < 2 or w % 2 or h % 2:
+        raise ValueError(f"--size: a 4:2:0 frame has an even, positive width and height, got {w}x{h}")
+    return w, h
+
+
+def read_frames(stream, w: int, h: int):
+    """The [3H/2, W] uint8 frames of a byte stream; ValueError for a trailing partial frame."""
+    nbytes = w * h * 3 // 2
+    index = 0
+    while True:
+        buf = bytearray()
+        while len(buf) < nbytes:                       # a pipe hands out what it has: read until the frame is whole
+            chunk = stream.read(nbytes - len(buf))
+            if not chunk:
+                break
+            buf += chunk
+        if not buf:
+            return
+        if len(buf) != nbytes:
+            raise ValueError(f"frame {index}: {len(buf)} trailing bytes, a {w}x{h} 4:2:0 frame has {nbytes}")
+        yield np.frombuffer(buf, dtype=np.uint8).reshape(h * 3 // 2, w)
+        index += 1
+
+
+def main(args) -> int:
+    w, h = parse_size(args.size)
+    layout = PIX_FMTS[getattr(args, "pix_fmt", "yuv420p") or "yuv420p"]
+    matrix = getattr(args, "matrix", "bt601") or "bt601"
+    log = sys.stderr if args.output == "-" else sys.stdout
+    torch.cuda.set_device(config.device)
+    with contextlib.redirect_stdout(log):
+        model = build_model(args)
+    outscale = getattr(args, "outscale", None)
+    out_h, out_w = yuv420_output_size(h, w, model.upscale_factor, outscale, "inference_rawvideo")
+    print(f"Output size {out_w}x{out_h} ({getattr(args, 'pix_fmt', 'yuv420p') or 'yuv420p'}, {out_w * out_h * 3 // 2} bytes per frame).", file=log)
+    count = 0
+    with contextlib.ExitStack() as stack:
+        src = sys.stdin.buffer if args.input == "-" else stack.enter_context(open(args.input, "rb"))
+        dst = sys.stdout.buffer if args.output == "-" else stack.enter_context(open(args.output, "wb"))
+        stream = stack.enter_context(FrameStream(model, depth=getattr(args, "depth", 2) or 2, outscale=outscale, pix_fmt=layout,
+                                                 matrix=matrix))
+        # copy=False: the pinned view is written out before the next result is asked for, i.e. before its slot is submitted to again
+        for sr in stream.map(read_frames(src, w, h), copy=False):
+            dst.write(sr.data)
+            count += 1
+        dst.flush()
+    print(f"{count} frames written to `{args.output}`.", file=log)
+    return count
+
+
+def get_parser() -> argparse.ArgumentParser:
+    parser = argparse.ArgumentParser(description="Using the Real_ESRGAN model generator super-resolution raw YUV 4:2:0 video.")
+    parser.add_argument("--input", type=str, required=True, help="Raw video file, or - for stdin.")
+    parser.add_argument("--output", type=str, required=True, help="Raw video file, or - for stdout.")
+    parser.add_argument("--size", type=str, required=True, help="Input frame size WxH (both even), e.g. 1920x1080.")
+    parser.add_argument("--pix_fmt", type=str, default="yuv420p", choices=sorted(PIX_FMTS), help="pixel format of input and output")
+    parser.add_argument("--matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="colour matrix (studio range)")
+    parser.add_argument("--weights_path", type=str, required=True, help="Model weights file path.")
+    parser.add_argument("--precision", type=str, default=None, choices=["fast", "exact16", "strict"],
+                        help="kernel arithmetic; default config.inference_precision = exact16")
+    parser.add_argument("--model_type", type=str, default="rrdb", choices=["rrdb", "compact"],
+                        help="rrdb: Generator (RRDBNet); compact: upstream's SRVGGNetCompact (realesr-animevideov3 / realesr-general-x4v3)")
+    parser.add_argument("--num_conv", type=int, default=16, help="compact: body convs (16 animevideov3, 32 general-x4v3)")
+    parser.add_argument("--act_type", type=str, default="prelu", choices=["prelu", "leakyrelu", "relu"], help="compact: activation")
+    parser.add_argument("--depth", type=int, default=2, help="frames in flight (FrameStream)")
+    parser.add_argument("--outscale", type=float, default=None,
+                        help="final upscaling factor (default: the model's own); the output width and height must come out even")
+    return parser
+
+
+if __name__ == "__main__":
+    main(get_parser().parse_args())

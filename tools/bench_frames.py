@@ -20,6 +20,15 @@ one `summary` line per case with the ratios and whether each exceeds the spread 
   B2/2/outscale, .../view   FrameStream(depth=2, outscale=O), copy=True / copy=False
 
     python tools/bench_frames.py --outscale 2 --out profiles/frames_outscale_1080p.jsonl
+
+`--pix_fmt i420 [nv12]` measures the YUV 4:2:0 path (frames.py, YUV 4:2:0) against the rgb24 one of the same run, alternated the same
+way, per case (with `--outscale O` every path below runs at that final factor, the YUV ones as the composition over the generic launches):
+  dev/forward_u8            model.forward_u8(frame uint8 RGB)                  (upscale_u8(..., outscale=O) with --outscale)
+  dev/forward_<fmt>         model.forward_yuv420(frame, layout=<fmt>)          (upscale_yuv420(..., outscale=O) with --outscale)
+  B2/2, B2/2/view           FrameStream(depth=2), rgb24, copy=True / copy=False
+  B2/2/<fmt>, .../view      FrameStream(depth=2, pix_fmt=<fmt>), copy=True / copy=False
+
+    python tools/bench_frames.py --pix_fmt i420 nv12 --out profiles/frames_yuv420_1080p.jsonl
 """
 import argparse
 import json
@@ -136,6 +145,81 @@ def main_outscale(args):
                 f.write(json.dumps(line) + "\n")
 
 
+def main_yuv(args):
+    o = args.outscale
+    torch.cuda.set_device(0)
+    box = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]}
+    rs = np.random.RandomState(0)
+    pool = [rs.randint(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(4)]
+    many = [pool[i % 4] for i in range(args.frames * 4)]
+    # the same pictures as 4:2:0 frames, so that every path upscales the same content
+    yuv = {fmt: [R.rgb_to_yuv420_np(f, fmt) for f in pool] for fmt in args.pix_fmt}
+    many_yuv = {fmt: [yuv[fmt][i % 4] for i in range(args.frames * 4)] for fmt in args.pix_fmt}
+    oh, ow = R.output_size(H, W, S, o)
+    lines = []
+    for num_conv in (16, 32):
+        for precision in ("fast", "exact16"):
+            torch.manual_seed(0)
+            model = R.SRVGGNetCompact(num_conv=num_conv, upscale=S, precision=precision).cuda().eval().requires_grad_(False)
+            streams = {"rgb24": R.FrameStream(model, depth=2, outscale=o)}
+            x_u8 = torch.from_numpy(pool[0])[None].cuda()
+            dev = {"dev/forward_u8": lambda: R.upscale_u8(model, x_u8, outscale=o)}
+            paths = {"B2/2": (many, lambda fr: sum(1 for _ in streams["rgb24"].map(fr)), H * W * 3, oh * ow * 3),
+                     "B2/2/view": (many, lambda fr: sum(1 for _ in streams["rgb24"].map(fr, copy=False)), H * W * 3, oh * ow * 3)}
+            same = {}
+            for fmt in args.pix_fmt:
+                streams[fmt] = R.FrameStream(model, depth=2, outscale=o, pix_fmt=fmt)
+                x_yuv = torch.from_numpy(yuv[fmt][0])[None].cuda()
+                dev[f"dev/forward_{fmt}"] = lambda x=x_yuv, fmt=fmt: R.upscale_yuv420(model, x, fmt, outscale=o)
+                paths[f"B2/2/{fmt}"] = (many_yuv[fmt], lambda fr, fmt=fmt: sum(1 for _ in streams[fmt].map(fr)), H * W * 3 // 2, oh * ow * 3 // 2)
+                paths[f"B2/2/{fmt}/view"] = (many_yuv[fmt], lambda fr, fmt=fmt: sum(1 for _ in streams[fmt].map(fr, copy=False)),
+                                             H * W * 3 // 2, oh * ow * 3 // 2)
+                # the definition, on a timed frame: the stream's result is the composition over the RGB path
+                want = R.rgb_to_yuv420(R.upscale_u8(model, R.yuv420_to_rgb(x_yuv, fmt), outscale=o), fmt)[0].cpu().numpy()
+                same[fmt] = bool(np.array_equal(next(iter(streams[fmt].map(yuv[fmt][:1]))), want))
+            with torch.no_grad():
+                for fn in dev.values():
+                    for _ in range(3):
+                        fn()
+            for fr, run, _, _ in paths.values():
+                run(fr[:2])
+            ms = {name: [] for name in list(dev) + list(paths)}
+            for _ in range(args.rounds):
+                with torch.no_grad():
+                    for name, fn in dev.items():
+                        ms[name].append(device_ms(fn, args.device_steps))
+                for name, (fr, run, _, _) in paths.items():
+                    ms[name].append(wall_ms(run, fr))
+            case = dict(tool="bench_frames", pix_fmt=list(args.pix_fmt), outscale=o, num_conv=num_conv, precision=precision,
+                        frame=f"{W}x{H}->{ow}x{oh}", **box)
+            med = {name: statistics.median(v) for name, v in ms.items()}
+            for name, v in ms.items():
+                extra = dict(steps=args.device_steps)
+                if name in paths:
+                    extra = dict(h2d_bytes_per_frame=paths[name][2], d2h_bytes_per_frame=paths[name][3],
+                                 d2h_gb_per_s=round(paths[name][3] / (med[name] * 1e-3) / 1e9, 2))
+                line = dict(case, path=name, ms_per_frame_rounds=[round(x, 3) for x in v], ms_per_frame=round(med[name], 3),
+                            spread_ms=round(max(v) - min(v), 3), frames_per_s=round(1e3 / med[name], 2), **extra)
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+            line = dict(case, path="summary", yuv_equals_composition=same)
+            for fmt in args.pix_fmt:
+                line[f"device_{fmt}_over_u8"] = round(med[f"dev/forward_{fmt}"] / med["dev/forward_u8"], 3)
+                line[f"device_{fmt}_minus_u8_ms"] = round(med[f"dev/forward_{fmt}"] - med["dev/forward_u8"], 3)
+                line[f"stream_{fmt}_over_rgb24_frames_per_s"] = round(med["B2/2"] / med[f"B2/2/{fmt}"], 2)
+                line[f"stream_view_{fmt}_over_rgb24_frames_per_s"] = round(med["B2/2/view"] / med[f"B2/2/{fmt}/view"], 2)
+            print(json.dumps(line), flush=True)
+            lines.append(line)
+            for st in streams.values():
+                st.close()
+            del model, streams, dev, paths
+            torch.cuda.empty_cache()
+    if args.out:
+        with open(args.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -143,8 +227,12 @@ def main():
     ap.add_argument("--device-steps", type=int, default=20)
     ap.add_argument("--out", default=None, help="also append the lines to this file")
     ap.add_argument("--outscale", type=float, default=None, help="measure the outscale path at this final factor instead (see above)")
+    ap.add_argument("--pix_fmt", nargs="+", default=None, choices=["i420", "nv12"],
+                    help="measure the YUV 4:2:0 path in these layouts against rgb24 instead (see above; combines with --outscale)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_frames.py measures on the GPU"
+    if args.pix_fmt:
+        return main_yuv(args)
     if args.outscale is not None:
         return main_outscale(args)
     torch.cuda.set_device(0)
