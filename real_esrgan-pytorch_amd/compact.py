@@ -6,6 +6,8 @@ PixelShuffle), so an official `.pth` loads with a plain `load_state_dict` (or `m
 one C-ABI call, `resr_compact_forward` (include/resr.h, csrc/compact.hip): conv 3->64 + act, num_conv x (conv 64->64 + act),
 conv 64->3*s*s, pixel-shuffle, + the nearest-upsampled input.  There is no PyTorch / CPU fallback and no backward pass.
 
+Every forward checks its own input, allocates its own result and goes through one call path (`_call`).
+
 `forward_u8` is the same launch sequence for uint8 HWC frames (`resr_compact_forward_u8`, csrc/frames.hip): the `/ 255` of the
 way in is fused into the first kernel and the `* 255`, clamp and truncation of `imgproc.tensor_to_image` into the last, so its
 result equals `tensor_to_image(forward(float frame))` bit for bit and a quarter of the output bytes leave the device.  It is
@@ -161,27 +163,33 @@ class SRVGGNetCompact(nn.Module):
             self._workspaces[key] = ws
         return ws
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
-        params = self._ordered_params()
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+    def _guard(self, x: Optional[torch.Tensor] = None) -> None:
+        if torch.is_grad_enabled() and ((x is not None and x.requires_grad) or any(p.requires_grad for p in self._ordered_params())):
             raise RuntimeError("SRVGGNetCompact: the compact generator's backward pass is not implemented on the MI355X path; "
                                "run inference under torch.no_grad() (or with requires_grad_(False) parameters)")
+
+    def _call(self, entry: str, src: torch.Tensor, n: int, h: int, w: int, y: torch.Tensor, *extra) -> torch.Tensor:
+        """What every forward shares once its own input is checked: the arena, the descriptor of n LR frames h x w, packing, the
+        workspace, then `entry` (its ends `src` and `y`; `extra`: the arguments between y and the stream)."""
+        flat = self.flat_parameters()
+        _lib.require_cuda(flat, "SRVGGNetCompact parameters")
+        desc = self._desc(n, h, w)
+        self._pack(desc, flat)
+        ws = self._workspace(desc, src.device)
+        _lib.check(getattr(_lib.lib(), entry)(C.byref(desc), _lib.ptr(src), _lib.ptr(flat), _lib.ptr(self._packed), _lib.ptr(ws),
+                                              ws.numel(), _lib.ptr(y), *extra, _lib.stream_ptr(src)), entry)
+        return y
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        self._guard(x)
         _lib.require_cuda(x, "SRVGGNetCompact.forward")
         if x.dim() != 4 or x.shape[1] != self.num_in_ch:
             raise RuntimeError(f"SRVGGNetCompact: expected an [N,{self.num_in_ch},H,W] input, got {tuple(x.shape)}")
-        flat = self.flat_parameters()
-        _lib.require_cuda(flat, "SRVGGNetCompact parameters")
         xc = x.detach().float().contiguous()   # also normalises channels_last strides
         n, _, h, w = xc.shape
-        desc = self._desc(n, h, w)
-        self._pack(desc, flat)
-        ws = self._workspace(desc, xc.device)
         s = self.upscale
         y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=xc.device)
-        _lib.check(_lib.lib().resr_compact_forward(C.byref(desc), _lib.ptr(xc), _lib.ptr(flat), _lib.ptr(self._packed),
-                                                   _lib.ptr(ws), ws.numel(), _lib.ptr(y), _lib.stream_ptr(xc)),
-                   "resr_compact_forward")
-        return y
+        return self._call("resr_compact_forward", xc, n, h, w, y)
 
     def forward_u8(self, frames: torch.Tensor, outscale: Optional[float] = None, plan=None) -> torch.Tensor:
         """frames uint8 [N,H,W,3] on the model's device, contiguous -> uint8 [N,H*s,W*s,3]: bit for bit
@@ -194,42 +202,27 @@ class SRVGGNetCompact(nn.Module):
         only the resized uint8 frame; bit for bit `imgproc.image_resize_native(self(float frames), r, u8=True)`.  `plan`: a cached
         `imgproc.ResizePlan` for this frame size and r (FrameStream keeps one).  None or the model's factor: the path above."""
         from . import frames as _frames
-        from .imgproc import ResizePlan
         o = _frames.check_outscale(outscale, self.upscale, "SRVGGNetCompact.forward_u8")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._ordered_params()):
-            raise RuntimeError("SRVGGNetCompact: the compact generator's backward pass is not implemented on the MI355X path; "
-                               "run inference under torch.no_grad() (or with requires_grad_(False) parameters)")
+        self._guard()
         _lib.require_cuda(frames, "SRVGGNetCompact.forward_u8")
         if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != self.num_in_ch:
             raise RuntimeError(f"SRVGGNetCompact.forward_u8: expected a uint8 [N,H,W,{self.num_in_ch}] tensor, got "
                                f"{frames.dtype} {tuple(frames.shape)}")
         if not frames.is_contiguous():
             raise RuntimeError("SRVGGNetCompact.forward_u8: frames must be contiguous (HWC bytes, as an image decoder leaves them)")
-        flat = self.flat_parameters()
-        _lib.require_cuda(flat, "SRVGGNetCompact parameters")
         n, h, w, _ = frames.shape
         s = self.upscale
-        if o is not None:
-            if plan is None:
-                plan = ResizePlan(h * s, w * s, o / s, frames.device)      # raises before any launch for a frame the rule refuses
-            elif (plan.in_h, plan.in_w, plan.scale_factor) != (h * s, w * s, o / s) or plan.idx_y.device != frames.device:
-                raise ValueError(f"SRVGGNetCompact.forward_u8: a plan for {plan.in_h}x{plan.in_w} x {plan.scale_factor}, "
-                                 f"the call is {h * s}x{w * s} x {o / s}")
-            plan.check("SRVGGNetCompact.forward_u8")
-        desc = self._desc(n, h, w)
-        self._pack(desc, flat)
-        ws = self._workspace(desc, frames.device)
-        if o is not None:
-            y = torch.empty((n, plan.out_h, plan.out_w, self.num_out_ch), dtype=torch.uint8, device=frames.device)
-            _lib.check(_lib.lib().resr_compact_forward_u8_scaled(C.byref(desc), _lib.ptr(frames), _lib.ptr(flat), _lib.ptr(self._packed),
-                                                                 _lib.ptr(ws), ws.numel(), _lib.ptr(y), *plan.args(),
-                                                                 _lib.stream_ptr(frames)), "resr_compact_forward_u8_scaled")
-            return y
-        y = torch.empty((n, h * s, w * s, self.num_out_ch), dtype=torch.uint8, device=frames.device)
-        _lib.check(_lib.lib().resr_compact_forward_u8(C.byref(desc), _lib.ptr(frames), _lib.ptr(flat), _lib.ptr(self._packed),
-                                                      _lib.ptr(ws), ws.numel(), _lib.ptr(y), _lib.stream_ptr(frames)),
-                   "resr_compact_forward_u8")
-        return y
+        if o is None:
+            y = torch.empty((n, h * s, w * s, self.num_out_ch), dtype=torch.uint8, device=frames.device)
+            return self._call("resr_compact_forward_u8", frames, n, h, w, y)
+        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
+        if plan is not None and ((plan.in_h, plan.in_w, plan.scale_factor) != (h * s, w * s, o / s) or plan.idx_y.device != frames.device):
+            raise ValueError(f"SRVGGNetCompact.forward_u8: a plan for {plan.in_h}x{plan.in_w} x {plan.scale_factor}, "
+                             f"the call is {h * s}x{w * s} x {o / s}")
+        plan = _frames._resize_plan(h, w, s, o, frames.device, plan)   # raises before any launch for a frame the rule refuses
+        plan.check("SRVGGNetCompact.forward_u8")
+        y = torch.empty((n, plan.out_h, plan.out_w, self.num_out_ch), dtype=torch.uint8, device=frames.device)
+        return self._call("resr_compact_forward_u8_scaled", frames, n, h, w, y, *plan.args())
 
     def forward_yuv420(self, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601") -> torch.Tensor:
         """frames uint8 [N,3H/2,W] (YUV 4:2:0, H and W even; `layout` "i420" or "nv12", `matrix` "bt601" or "bt709": frames.py) on
@@ -239,21 +232,11 @@ class SRVGGNetCompact(nn.Module):
         device, and half the bytes enter and leave.  Same guard, packing and workspace caches as `forward`."""
         from . import frames as _frames
         ydesc = _frames.yuv_desc(layout, matrix)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._ordered_params()):
-            raise RuntimeError("SRVGGNetCompact: the compact generator's backward pass is not implemented on the MI355X path; "
-                               "run inference under torch.no_grad() (or with requires_grad_(False) parameters)")
+        self._guard()
         n, h, w = _frames.check_yuv420(frames, "SRVGGNetCompact.forward_yuv420")
-        flat = self.flat_parameters()
-        _lib.require_cuda(flat, "SRVGGNetCompact parameters")
-        desc = self._desc(n, h, w)
-        self._pack(desc, flat)
-        ws = self._workspace(desc, frames.device)
         s = self.upscale
         y = torch.empty((n, h * s * 3 // 2, w * s), dtype=torch.uint8, device=frames.device)
-        _lib.check(_lib.lib().resr_compact_forward_yuv420(C.byref(desc), _lib.ptr(frames), _lib.ptr(flat), _lib.ptr(self._packed),
-                                                          _lib.ptr(ws), ws.numel(), _lib.ptr(y), C.byref(ydesc),
-                                                          _lib.stream_ptr(frames)), "resr_compact_forward_yuv420")
-        return y
+        return self._call("resr_compact_forward_yuv420", frames, n, h, w, y, C.byref(ydesc))
 
     def load_official_state_dict(self, checkpoint) -> None:
         """Upstream's `{"params_ema": sd}` / `{"params": sd}` (params_ema preferred) or a bare state dict (model.load_official_state_dict)."""

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "resr.h"
 #include "resr_debug.h"
 
@@ -39,6 +41,18 @@ inline size_t act_tensors(int dtype) { return dtype == RESR_F16X2 ? 2 : 1; }
 constexpr float kLoScale = 4096.f, kLoInv = 1.f / 4096.f;
 constexpr int kMaxDevices = 16;   // per-device caches (occupancy, zero pages, CU counts) are indexed by hipGetDevice()
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// A runtime upscale factor s in {1, 2, 3, 4} as a compile-time one: f(std::integral_constant<int, s>()); false for any other s.
+template <typename F>
+inline bool with_scale(int s, F&& f) {
+    switch (s) {
+        case 1: f(std::integral_constant<int, 1>()); return true;
+        case 2: f(std::integral_constant<int, 2>()); return true;
+        case 3: f(std::integral_constant<int, 3>()); return true;
+        case 4: f(std::integral_constant<int, 4>()); return true;
+        default: return false;
+    }
+}
 
 // RESR_F16X2 (lo_off != 0 with T = f16): every tensor of T is a (hi, lo) pair, lo at element offset lo_off; values are
 // split / recombined in fp32 (see include/resr.h).  Shared by layout.hip and frames.hip: one rounding for every way in.

@@ -8,11 +8,12 @@
 //   y[n,c,Y,X] = t[n, c*s*s + (Y%s)*s + X%s, Y/s, X/s] + x[n,c,Y/s,X/s]      (one launch, 64-bit indexing)
 // T = f16 (fast) / f32 (strict); RESR_F16X2 (exact16): every NHWC tensor is a hi/lo pair, the lo tensor right behind the hi one,
 // three stages per chunk.  No padding beyond each conv's own pad = 1: any H, W >= 1.
-// compact_forward_u8 is the same sequence for uint8 HWC frames: frames.hip's u8 head in place of the layout kernel, its u8 tail
-// (pixel-shuffle + residual + * 255, clamp, truncate) in place of compact_tail_kernel; same plan, same workspace.
-// compact_forward_u8_scaled ("outscale") is that sequence with image_resize.hip's fused tail in place of the u8 tail: the HR
-// frame is formed tile by tile in LDS and only the resized uint8 frame [N,oh,ow,3] is written; same plan, same workspace.
-// compact_forward_yuv420 is compact_forward_u8 for YUV 4:2:0 frames [N,3H/2,W]: frames.hip's YUV head and YUV tail at the two ends.
+// The three frame entries are the same sequence with another pair of ends (Ends below), same plan, same workspace:
+//   compact_forward_u8        uint8 HWC frames: frames.hip's head in place of the layout kernel, its u8 tail (pixel-shuffle +
+//                             residual + * 255, clamp, truncate) in place of compact_tail_kernel;
+//   compact_forward_u8_scaled ("outscale") image_resize.hip's fused tail in place of the u8 tail: the HR frame is formed tile by
+//                             tile in LDS and only the resized uint8 frame [N,oh,ow,3] is written;
+//   compact_forward_yuv420    YUV 4:2:0 frames [N,3H/2,W]: frames.hip's head reading YUV, and its YUV tail.
 #include <vector>
 
 #include "common.h"
@@ -23,10 +24,9 @@ int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*,
                      const void*, const void*, void*, void*, hipStream_t);
 int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const float*, const float*, void*, hipStream_t);
 int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
-int u8_head_dispatch(const uint8_t*, void*, int, int, int, int, hipStream_t, long);                      // frames.hip
+int frame_head_dispatch(const uint8_t*, void*, int, int, int, int, hipStream_t, long, const ResrYuvDesc*);   // frames.hip
 int compact_tail_u8(const float*, const uint8_t*, uint8_t*, int, int, int, int, hipStream_t);
 int yuv420_forward_check(const char*, int, int, int, int, const uint8_t*, const ResrYuvDesc*);
-int yuv_head_dispatch(const uint8_t*, void*, int, int, int, int, hipStream_t, long, const ResrYuvDesc*);
 int compact_tail_yuv420(const float*, const uint8_t*, uint8_t*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
 int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, bool,
                 const void*, ResizeGeom*);                                                                      // image_resize.hip
@@ -121,13 +121,8 @@ int compact_tail(const float* t, const float* x, float* y, int n, int h, int w, 
     const long rows = (long)n * 3 * h * s;
     const dim3 grid((unsigned)((w * s + 255) / 256), (unsigned)(rows > 65535 ? 65535 : rows));
     prof_before(st);
-    switch (s) {
-        case 1: hipLaunchKernelGGL(compact_tail_kernel<1>, grid, dim3(256), 0, st, t, x, y, n, h, w); break;
-        case 2: hipLaunchKernelGGL(compact_tail_kernel<2>, grid, dim3(256), 0, st, t, x, y, n, h, w); break;
-        case 3: hipLaunchKernelGGL(compact_tail_kernel<3>, grid, dim3(256), 0, st, t, x, y, n, h, w); break;
-        case 4: hipLaunchKernelGGL(compact_tail_kernel<4>, grid, dim3(256), 0, st, t, x, y, n, h, w); break;
-        default: return fail(RESR_ERR_ARG, "compact_tail: upscale %d", s);
-    }
+    if (!with_scale(s, [&](auto S) { hipLaunchKernelGGL(compact_tail_kernel<S()>, grid, dim3(256), 0, st, t, x, y, n, h, w); }))
+        return fail(RESR_ERR_ARG, "compact_tail: upscale %d", s);
     prof_after(st, 31000 + s, 0.0, (double)n * 3 * h * w * (s * s * 8.0 + 4.0));
     RESR_CHECK_LAUNCH("compact_tail_kernel");
     return RESR_OK;
@@ -178,36 +173,61 @@ int64_t compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t
 
 namespace {
 
-// The launch sequence both entries share.  U8 = false: x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32 (layout.hip head, compact_tail);
-// U8 = true: x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8 (frames.hip: the conversions fused into the head and the tail; the convs,
-// the packed weights and the workspace plan are the same).  sc (U8 only): the resized tail of compact_forward_u8_scaled.
-// yuv (U8 only): x and y are YUV 4:2:0 frames [N,3H/2,W] -> [N,3sH/2,sW], the colour conversions fused into the same two kernels.
-// Every argument check comes before the first launch.
 struct ScaledTail {
     int oh, ow, taps_y, taps_x;
     const int32_t *idx_y, *idx_x;
     const float *w_y, *w_x;
 };
 
-template <bool U8>
-int compact_run(const ResrCompactDesc* d, const void* x, const float* params, const void* packed, void* workspace,
-                size_t workspace_bytes, void* y, hipStream_t st, const char* who, const ScaledTail* sc = nullptr,
-                const ResrYuvDesc* yuv = nullptr) {
+// The two ends of one forward pass: what x and y are, and what else that kind of end needs.
+enum EndKind {
+    F32_NCHW,        // x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32: layout.hip's head, compact_tail
+    U8_HWC,          // x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8: frames.hip, the conversions fused into the head and the tail
+    U8_HWC_SCALED,   // ... -> y [N,oh,ow,3]: the resized tail of image_resize.hip (sc)
+    YUV420,          // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames: the colour conversions (yuv) fused into the same two kernels
+};
+
+struct Ends {
+    EndKind kind;
+    const float* x_f32;      // F32_NCHW
+    float* y_f32;
+    const uint8_t* x_u8;     // every other kind
+    uint8_t* y_u8;
+    ScaledTail sc;           // U8_HWC_SCALED
+    const ResrYuvDesc* yuv;  // YUV420, else null
+};
+
+// Everything a call can be refused for after its descriptor, before the first launch.  U8_HWC_SCALED: fills geom.
+int check_ends(const CPlan& p, const Ends& e, const float* params, const void* packed, const void* workspace, size_t workspace_bytes,
+               const char* who, ResizeGeom* geom) {
+    const ResrCompactDesc& d = p.d;
+    const bool no_ends = e.kind == F32_NCHW ? !e.x_f32 || !e.y_f32 : !e.x_u8 || !e.y_u8;
+    if (no_ends || !params || !packed || !workspace) return fail(RESR_ERR_ARG, "%s: null argument", who);
+    int rc = RESR_OK;
+    switch (e.kind) {
+        case F32_NCHW: break;
+        case U8_HWC:
+        case U8_HWC_SCALED:
+            if (((size_t)e.y_u8 & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
+            if (e.kind == U8_HWC_SCALED)
+                rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y,
+                                 e.sc.idx_x, e.sc.w_x, e.sc.taps_x, true, e.y_u8, geom);
+            break;
+        case YUV420: rc = yuv420_forward_check(who, d.n, d.h, d.w, d.upscale, e.y_u8, e.yuv); break;
+    }
+    if (rc) return rc;
+    if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
+    return RESR_OK;
+}
+
+// The launch sequence every entry shares: plan, refusals, head, convs, tail.
+int compact_run(const ResrCompactDesc* d, const Ends& e, const float* params, const void* packed, void* workspace,
+                size_t workspace_bytes, hipStream_t st, const char* who) {
     CPlan p;
     if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "%s: bad descriptor", who);
-    if (!x || !params || !packed || !workspace || !y) return fail(RESR_ERR_ARG, "%s: null argument", who);
-    if (U8 && !yuv && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
-    if (yuv) {
-        const int rc = yuv420_forward_check(who, d->n, d->h, d->w, d->upscale, (const uint8_t*)y, yuv);
-        if (rc) return rc;
-    }
     ResizeGeom geom;
-    if (sc) {
-        const int rc = resize_plan(who, d->n, 3, d->h * d->upscale, d->w * d->upscale, sc->oh, sc->ow, sc->idx_y, sc->w_y, sc->taps_y,
-                                   sc->idx_x, sc->w_x, sc->taps_x, true, y, &geom);
-        if (rc) return rc;
-    }
-    if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
+    int rc = check_ends(p, e, params, packed, workspace, workspace_bytes, who, &geom);
+    if (rc) return rc;
     const bool x2 = d->dtype == RESR_F16X2;
     const size_t wes = elem_size(d->dtype) * (x2 ? 3 : 1);   // bytes per element of the packed layout
     const char* pk = (const char*)packed;
@@ -217,9 +237,10 @@ int compact_run(const ResrCompactDesc* d, const void* x, const float* params, co
     float* t = reinterpret_cast<float*>(base + p.off_t);
     const int N = d->n, H = d->h, W = d->w;
     const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
-    int rc = yuv ? yuv_head_dispatch((const uint8_t*)x, xin, N, H, W, d->dtype, st, (long)lo32, yuv)
-             : U8 ? u8_head_dispatch((const uint8_t*)x, xin, N, H, W, d->dtype, st, (long)lo32)
-                : nchw_to_nhwc_dispatch((const float*)x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
+    switch (e.kind) {
+        case F32_NCHW: rc = nchw_to_nhwc_dispatch(e.x_f32, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32); break;
+        default: rc = frame_head_dispatch(e.x_u8, xin, N, H, W, d->dtype, st, (long)lo32, e.yuv); break;   // yuv null: RGB bytes
+    }
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) {
         ResrConvDesc cd;
@@ -256,37 +277,42 @@ int compact_run(const ResrCompactDesc* d, const void* x, const float* params, co
         rc = conv3x3_dispatch(&cd, in, nullptr, pk + c.pk * wes, params + c.b_off, nullptr, nullptr, nullptr, t, nullptr, st);
         if (rc) return rc;
     }
-    if (U8 && sc)
-        return compact_tail_u8_scaled(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, sc->idx_y, sc->w_y, sc->idx_x, sc->w_x,
-                                      &geom, st);
-    if (yuv) return compact_tail_yuv420(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, yuv, st);
-    if (U8) return compact_tail_u8(t, (const uint8_t*)x, (uint8_t*)y, N, H, W, d->upscale, st);
-    return compact_tail(t, (const float*)x, (float*)y, N, H, W, d->upscale, st);
+    switch (e.kind) {
+        case F32_NCHW: return compact_tail(t, e.x_f32, e.y_f32, N, H, W, d->upscale, st);
+        case U8_HWC: return compact_tail_u8(t, e.x_u8, e.y_u8, N, H, W, d->upscale, st);
+        case U8_HWC_SCALED:
+            return compact_tail_u8_scaled(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, &geom, st);
+        case YUV420: return compact_tail_yuv420(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.yuv, st);
+    }
+    return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
 }
 
 }  // namespace
 
 int compact_forward(const ResrCompactDesc* d, const float* x, const float* params, const void* packed, void* workspace,
                     size_t workspace_bytes, float* y, hipStream_t st) {
-    return compact_run<false>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward");
+    const Ends e{F32_NCHW, x, y, nullptr, nullptr, {}, nullptr};
+    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward");
 }
 
 int compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
                        size_t workspace_bytes, uint8_t* y, hipStream_t st) {
-    return compact_run<true>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward_u8");
+    const Ends e{U8_HWC, nullptr, nullptr, x, y, {}, nullptr};
+    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_u8");
 }
 
 int compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
                            size_t workspace_bytes, uint8_t* y, const ResrYuvDesc* yuv, hipStream_t st) {
     if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420: null argument");
-    return compact_run<true>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward_yuv420", nullptr, yuv);
+    const Ends e{YUV420, nullptr, nullptr, x, y, {}, yuv};
+    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420");
 }
 
 int compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
                               size_t workspace_bytes, uint8_t* y, int oh, int ow, const int32_t* idx_y, const float* w_y, int taps_y,
                               const int32_t* idx_x, const float* w_x, int taps_x, hipStream_t st) {
-    const ScaledTail sc{oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x};
-    return compact_run<true>(d, x, params, packed, workspace, workspace_bytes, y, st, "compact_forward_u8_scaled", &sc);
+    const Ends e{U8_HWC_SCALED, nullptr, nullptr, x, y, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, nullptr};
+    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_u8_scaled");
 }
 
 }  // namespace resr

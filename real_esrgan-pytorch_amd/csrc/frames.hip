@@ -1,10 +1,11 @@
 // frames.hip -- the uint8 frame path: u8 HWC images in, u8 HWC images out.
 //
-//   u8_head        : u8 [N,H,W,3] -> the compact net's x_in [N,H,W,32] in the model's arithmetic (channels 3..31 zero)
+//   frame_head     : u8 [N,H,W,3], or a YUV 4:2:0 frame [N,3H/2,W] (I420 / NV12), -> the compact net's x_in [N,H,W,32] in the
+//                    model's arithmetic (channels 3..31 zero): one kernel, the source of a pixel's RGB bytes its parameter
 //   compact_tail_u8: t [N,3S^2,H,W] fp32 + the u8 input frame -> u8 [N,H*S,W*S,3]   (pixel-shuffle + residual + quantise)
 //   u8_to_nchw     : u8 [N,H,W,3] -> fp32 [N,3,H,W]                (models whose first kernel is not ours to fuse)
 //   nchw_to_u8     : fp32 [N,3,H,W] -> u8 [N,H,W,3]                (... and whose last one is not: RRDB Generator, the tiler)
-//   yuv_head, compact_tail_yuv420 : the two fused ends with YUV 4:2:0 frames [N,3H/2,W] (I420 / NV12) in place of RGB ones
+//   compact_tail_yuv420           : compact_tail_u8 with YUV 4:2:0 frames at both of its ends
 //   yuv420_to_rgb, rgb_to_yuv420  : the integer colour conversions on their own, u8 [N,3H/2,W] <-> u8 [N,H,W,3]
 //
 // The result is DEFINED as what the float path followed by imgproc.tensor_to_image produces, bit for bit:
@@ -28,34 +29,6 @@ __device__ __forceinline__ unsigned quantise_u8(float v) {
     v = v > 0.f ? v : 0.f;          // (a NaN compares false: 0)
     v = v < 255.f ? v : 255.f;
     return (unsigned)v;             // truncation, as astype(uint8) of a value in [0, 255]
-}
-
-// One thread per 16-byte piece of an output pixel (as nchw_to_nhwc_kernel): only piece 0 holds the three real channels.
-template <typename T>
-__global__ __launch_bounds__(256) void u8_head_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, long px, long lo_off) {
-    constexpr int E = 16 / (int)sizeof(T);
-    constexpr int PIECES = 32 / E;
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= px * PIECES) return;
-    const long p = idx / PIECES;
-    const int piece = (int)(idx - p * PIECES);
-    uint4 out = make_uint4(0u, 0u, 0u, 0u), outl = make_uint4(0u, 0u, 0u, 0u);
-    if (piece == 0) {
-        T* o = reinterpret_cast<T*>(&out);
-        T* ol = reinterpret_cast<T*>(&outl);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = u8_unit(src[p * 3 + c]);
-            if constexpr (sizeof(T) == 2) {
-                if (lo_off) split_f16(v, o[c], ol[c]);
-                else o[c] = (T)v;
-            } else {
-                o[c] = (T)v;
-            }
-        }
-    }
-    *reinterpret_cast<uint4*>(dst + p * 32 + piece * E) = out;
-    if (sizeof(T) == 2 && lo_off) *reinterpret_cast<uint4*>(dst + lo_off + p * 32 + piece * E) = outl;
 }
 
 // The output is a flat array of n * hS * wS pixels of 3 bytes; a thread owns 4 consecutive pixels = 12 bytes = three dword
@@ -156,10 +129,33 @@ __device__ __forceinline__ unsigned chroma_of(const ResrYuvDesc& q, int row, con
 
 __device__ __forceinline__ unsigned pack4(const unsigned* b) { return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); }
 
-// u8_head_kernel with a YUV source: piece 0 forms the RGB bytes from (Y, Cb, Cr), then does what u8_head_kernel does.
-template <typename T>
-__global__ __launch_bounds__(256) void yuv_head_kernel(const uint8_t* __restrict__ src, T* __restrict__ dst, long px, long lo_off, int h,
-                                                       int w, ResrYuvDesc q) {
+// Where frame_head_kernel takes the three RGB bytes of pixel p from: an RGB frame holds them ...
+struct RgbSrc {
+    const uint8_t* __restrict__ src;
+    __device__ __forceinline__ void operator()(long p, unsigned (&rgb)[3]) const {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rgb[c] = src[p * 3 + c];
+    }
+};
+
+// ... a YUV 4:2:0 frame (images of luma size h x w) yields them through the integer conversion.
+struct YuvSrc {
+    const uint8_t* __restrict__ src;
+    int h, w;
+    ResrYuvDesc q;
+    __device__ __forceinline__ void operator()(long p, unsigned (&rgb)[3]) const {
+        const long plane = (long)h * w;
+        const long b = p / plane, r = p - b * plane;
+        const int yy = (int)(r / w), xx = (int)(r - (long)yy * w);
+        int Y, Cb, Cr;
+        yuv_load(src + b * (plane + (plane >> 1)), h, w, q.layout, yy, xx, Y, Cb, Cr);
+        yuv_to_rgb(q, Y, Cb, Cr, rgb);
+    }
+};
+
+// One thread per 16-byte piece of an output pixel (as nchw_to_nhwc_kernel): only piece 0 holds the three real channels.
+template <typename T, typename Src>
+__global__ __launch_bounds__(256) void frame_head_kernel(Src src, T* __restrict__ dst, long px, long lo_off) {
     constexpr int E = 16 / (int)sizeof(T);
     constexpr int PIECES = 32 / E;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -168,13 +164,8 @@ __global__ __launch_bounds__(256) void yuv_head_kernel(const uint8_t* __restrict
     const int piece = (int)(idx - p * PIECES);
     uint4 out = make_uint4(0u, 0u, 0u, 0u), outl = make_uint4(0u, 0u, 0u, 0u);
     if (piece == 0) {
-        const long plane = (long)h * w;
-        const long b = p / plane, r = p - b * plane;
-        const int yy = (int)(r / w), xx = (int)(r - (long)yy * w);
-        int Y, Cb, Cr;
-        yuv_load(src + b * (plane + (plane >> 1)), h, w, q.layout, yy, xx, Y, Cb, Cr);
         unsigned rgb[3];
-        yuv_to_rgb(q, Y, Cb, Cr, rgb);
+        src(p, rgb);
         T* o = reinterpret_cast<T*>(&out);
         T* ol = reinterpret_cast<T*>(&outl);
 #pragma unroll
@@ -192,6 +183,23 @@ __global__ __launch_bounds__(256) void yuv_head_kernel(const uint8_t* __restrict
     if (sizeof(T) == 2 && lo_off) *reinterpret_cast<uint4*>(dst + lo_off + p * 32 + piece * E) = outl;
 }
 
+// The image b, first row Y0 and first column X0 of the thread that owns 2 rows x COLS columns of n images of rows x cols pixels
+// (rows even); false for a thread past the last such block.
+template <int COLS>
+__device__ __forceinline__ bool block_2xcols(int n, int rows, int cols, long& b, int& Y0, int& X0) {
+    constexpr int SHIFT = COLS == 8 ? 3 : 2;
+    static_assert(COLS == 1 << SHIFT, "4 or 8 columns");
+    const int groups = (cols + COLS - 1) >> SHIFT;
+    const long total = (long)n * (rows >> 1) * groups;
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= total) return false;
+    const long rp = gid / groups;              // b * rows / 2 + Y0 / 2
+    X0 = (int)(gid - rp * groups) * COLS;
+    b = rp / (rows >> 1);
+    Y0 = (int)(rp - b * (rows >> 1)) * 2;
+    return true;
+}
+
 // compact_tail_u8_kernel with YUV at both ends.  A thread owns 2 rows x 8 columns of the output, i.e. four whole chroma samples;
 // adjacent lanes are adjacent in x.  Per pixel: the residual byte is recomputed from the YUV input (no RGB frame exists here),
 // v = t + u8_unit(rgb_in), quantise_u8(v) unchanged, then the integer RGB -> YUV formula.  wide (the output width is a multiple of 8,
@@ -202,14 +210,9 @@ template <int S, int LAYOUT>
 __global__ __launch_bounds__(256) void compact_tail_yuv420_kernel(const float* __restrict__ t, const uint8_t* __restrict__ x,
                                                                   uint8_t* __restrict__ y, int n, int h, int w, int wide, ResrYuvDesc q) {
     const int HS = h * S, WS = w * S;
-    const int groups = (WS + 7) >> 3;
-    const long total = (long)n * (HS >> 1) * groups;
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= total) return;
-    const long rp = gid / groups;              // b * HS / 2 + Y / 2
-    const int X0 = (int)(gid - rp * groups) * 8;
-    const long b = rp / (HS >> 1);
-    const int Y0 = (int)(rp - b * (HS >> 1)) * 2;
+    long b;
+    int Y0, X0;
+    if (!block_2xcols<8>(n, HS, WS, b, Y0, X0)) return;
     const long plane = (long)h * w;
     const uint8_t* xin = x + b * (plane + (plane >> 1));
     const float* tb = t + b * 3 * S * S * plane;
@@ -292,14 +295,9 @@ __global__ __launch_bounds__(256) void compact_tail_yuv420_kernel(const float* _
 // (NV12) or two 2-byte stores (I420).  Every other even width moves bytes, the columns past the right edge skipped.
 __global__ __launch_bounds__(256) void yuv420_to_rgb_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int h,
                                                             int w, int wide, ResrYuvDesc q) {
-    const int groups = (w + 3) >> 2;
-    const long total = (long)n * (h >> 1) * groups;
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= total) return;
-    const long rp = gid / groups;
-    const int X0 = (int)(gid - rp * groups) * 4;
-    const long b = rp / (h >> 1);
-    const int Y0 = (int)(rp - b * (h >> 1)) * 2;
+    long b;
+    int Y0, X0;
+    if (!block_2xcols<4>(n, h, w, b, Y0, X0)) return;
     const long plane = (long)h * w;
     const uint8_t* img = src + b * (plane + (plane >> 1));
 #pragma unroll
@@ -332,14 +330,9 @@ __global__ __launch_bounds__(256) void yuv420_to_rgb_kernel(const uint8_t* __res
 
 __global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int n, int h,
                                                             int w, int wide, ResrYuvDesc q) {
-    const int groups = (w + 3) >> 2;
-    const long total = (long)n * (h >> 1) * groups;
-    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
-    if (gid >= total) return;
-    const long rp = gid / groups;
-    const int X0 = (int)(gid - rp * groups) * 4;
-    const long b = rp / (h >> 1);
-    const int Y0 = (int)(rp - b * (h >> 1)) * 2;
+    long b;
+    int Y0, X0;
+    if (!block_2xcols<4>(n, h, w, b, Y0, X0)) return;
     const long plane = (long)h * w;
     unsigned yb[2][4];
     int sum[2][3] = {{0, 0, 0}, {0, 0, 0}};
@@ -431,34 +424,34 @@ void launch_tail(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int
 
 }  // namespace
 
-// lo_off: the hi -> lo element offset of x_in (RESR_F16X2), as compact_forward passes it to nchw_to_nhwc_dispatch
-int u8_head_dispatch(const uint8_t* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off) {
-    if (!src || !dst || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "u8_head: bad argument");
+// lo_off: the hi -> lo element offset of x_in (RESR_F16X2), as compact_forward passes it to nchw_to_nhwc_dispatch.
+// q: the frames are YUV 4:2:0 [n,3h/2,w]; null: RGB [n,h,w,3].
+int frame_head_dispatch(const uint8_t* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q) {
+    const char* who = q ? "yuv_head" : "u8_head";
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || (q && ((h & 1) || (w & 1) || !yuv_ok(q)))) return fail(RESR_ERR_ARG, "%s: bad argument", who);
     const long px = (long)n * h * w;
     const int pieces = dtype != RESR_F32 ? 4 : 8;
-    if (!grid_ok(px * pieces)) return fail(RESR_ERR_ARG, "u8_head: %ld pixels beyond the grid", px);
+    if (!grid_ok(px * pieces)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, px);
     const dim3 grid((unsigned)((px * pieces + 255) / 256));
     if (dtype != RESR_F16X2) lo_off = 0;
+    auto launch = [&](auto from) {
+        if (dtype != RESR_F32)
+            hipLaunchKernelGGL((frame_head_kernel<half_t, decltype(from)>), grid, dim3(256), 0, st, from, (half_t*)dst, px, lo_off);
+        else
+            hipLaunchKernelGGL((frame_head_kernel<float, decltype(from)>), grid, dim3(256), 0, st, from, (float*)dst, px, 0L);
+    };
     prof_before(st);
-    if (dtype != RESR_F32)
-        hipLaunchKernelGGL(u8_head_kernel<half_t>, grid, dim3(256), 0, st, src, (half_t*)dst, px, lo_off);
-    else
-        hipLaunchKernelGGL(u8_head_kernel<float>, grid, dim3(256), 0, st, src, (float*)dst, px, 0L);
-    prof_after(st, 31020, 0.0, (double)px * (3.0 + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
-    RESR_CHECK_LAUNCH("u8_head_kernel");
+    if (q) launch(YuvSrc{src, h, w, *q});
+    else launch(RgbSrc{src});
+    prof_after(st, q ? 31021 : 31020, 0.0, (double)px * ((q ? 1.5 : 3.0) + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
+    RESR_CHECK_LAUNCH("frame_head_kernel");
     return RESR_OK;
 }
 
+// y 4-byte aligned: compact_run has checked it
 int compact_tail_u8(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, hipStream_t st) {
-    if (((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "compact_tail_u8: the output must be 4-byte aligned");
     prof_before(st);
-    switch (s) {
-        case 1: launch_tail<1, true>(t, x, y, n, h, w, st); break;
-        case 2: launch_tail<2, true>(t, x, y, n, h, w, st); break;
-        case 3: launch_tail<3, true>(t, x, y, n, h, w, st); break;
-        case 4: launch_tail<4, true>(t, x, y, n, h, w, st); break;
-        default: return fail(RESR_ERR_ARG, "compact_tail_u8: upscale %d", s);
-    }
+    if (!with_scale(s, [&](auto S) { launch_tail<S(), true>(t, x, y, n, h, w, st); })) return fail(RESR_ERR_ARG, "compact_tail_u8: upscale %d", s);
     // per LR pixel: 3 s^2 floats of t, 3 bytes of x, 3 s^2 bytes out
     prof_after(st, 31010 + s, 0.0, (double)n * h * w * (s * s * 15.0 + 3.0));
     RESR_CHECK_LAUNCH("compact_tail_u8_kernel");
@@ -499,35 +492,11 @@ int yuv420_forward_check(const char* who, int n, int h, int w, int s, const uint
     return RESR_OK;
 }
 
-int yuv_head_dispatch(const uint8_t* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q) {
-    if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || (h & 1) || (w & 1) || !yuv_ok(q)) return fail(RESR_ERR_ARG, "yuv_head: bad argument");
-    const long px = (long)n * h * w;
-    const int pieces = dtype != RESR_F32 ? 4 : 8;
-    if (!grid_ok(px * pieces)) return fail(RESR_ERR_ARG, "yuv_head: %ld pixels beyond the grid", px);
-    const dim3 grid((unsigned)((px * pieces + 255) / 256));
-    if (dtype != RESR_F16X2) lo_off = 0;
-    prof_before(st);
-    if (dtype != RESR_F32)
-        hipLaunchKernelGGL(yuv_head_kernel<half_t>, grid, dim3(256), 0, st, src, (half_t*)dst, px, lo_off, h, w, *q);
-    else
-        hipLaunchKernelGGL(yuv_head_kernel<float>, grid, dim3(256), 0, st, src, (float*)dst, px, 0L, h, w, *q);
-    prof_after(st, 31021, 0.0, (double)px * (1.5 + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
-    RESR_CHECK_LAUNCH("yuv_head_kernel");
-    return RESR_OK;
-}
-
+// the frames have passed yuv420_forward_check: compact_run has called it
 int compact_tail_yuv420(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, const ResrYuvDesc* q, hipStream_t st) {
-    const int rc = yuv420_forward_check("compact_tail_yuv420", n, h, w, s, y, q);
-    if (rc) return rc;
     const int wide = (w * s) % 8 == 0;
     prof_before(st);
-    switch (s) {
-        case 1: launch_tail_yuv<1>(t, x, y, n, h, w, wide, *q, st); break;
-        case 2: launch_tail_yuv<2>(t, x, y, n, h, w, wide, *q, st); break;
-        case 3: launch_tail_yuv<3>(t, x, y, n, h, w, wide, *q, st); break;
-        case 4: launch_tail_yuv<4>(t, x, y, n, h, w, wide, *q, st); break;
-        default: return fail(RESR_ERR_ARG, "compact_tail_yuv420: upscale %d", s);
-    }
+    if (!with_scale(s, [&](auto S) { launch_tail_yuv<S()>(t, x, y, n, h, w, wide, *q, st); })) return fail(RESR_ERR_ARG, "compact_tail_yuv420: upscale %d", s);
     // per LR pixel: 3 s^2 floats of t, 1.5 bytes of x, 1.5 s^2 bytes out
     prof_after(st, 31040 + s, 0.0, (double)n * h * w * (s * s * 13.5 + 1.5));
     RESR_CHECK_LAUNCH("compact_tail_yuv420_kernel");

@@ -114,6 +114,15 @@ def to_u8(sr: torch.Tensor) -> torch.Tensor:
     return y
 
 
+def _resize_plan(h: int, w: int, s: int, o: Optional[float], device, plan=None):
+    """The `imgproc.ResizePlan` of an h x w frame through a model of factor s at outscale o: `plan` when the caller holds one, else
+    a new one (ValueError before any launch for a frame the rule refuses); None when o is."""
+    if o is None or plan is not None:
+        return plan
+    from .imgproc import ResizePlan        # (function-local, as every use of imgproc on the frame path)
+    return ResizePlan(h * s, w * s, o / s, device)
+
+
 @torch.no_grad()
 def upscale_u8(model, frames: torch.Tensor, halo: Optional[int] = None, outscale: Optional[float] = None, plan=None) -> torch.Tensor:
     """uint8 [N,H,W,3] on the model's device -> uint8 [N,sH,sW,3].  `halo`: the tiler's, for frames it has to cut
@@ -128,9 +137,8 @@ def upscale_u8(model, frames: torch.Tensor, halo: Optional[int] = None, outscale
         if hasattr(model, "forward_u8") and tiling.fits_whole(model, n, h, w):
             return model.forward_u8(frames)
         return to_u8(tiling.super_resolve(model, from_u8(frames), halo))
-    from .imgproc import ResizePlan, resize_with_plan
-    if plan is None:
-        plan = ResizePlan(h * s, w * s, o / s, frames.device)         # ValueError before any launch for a frame the rule refuses
+    from .imgproc import resize_with_plan
+    plan = _resize_plan(h, w, s, o, frames.device, plan)
     if hasattr(model, "forward_u8") and tiling.fits_whole(model, n, h, w):
         return model.forward_u8(frames, outscale=o, plan=plan)
     return resize_with_plan(tiling.super_resolve(model, from_u8(frames), halo), plan, u8=True)
@@ -164,11 +172,18 @@ def yuv420_tables(matrix: str = "bt601", quantised: bool = True) -> Tuple[np.nda
     return np.rint(f * 65536).astype(np.int32), np.rint(i * 65536).astype(np.int32)
 
 
-def _yuv_geometry(shape, what: str) -> Tuple[int, int]:
-    """(H, W) of the luma plane of a [..., 3H/2, W] array."""
+def _yuv_hw(shape) -> Optional[Tuple[int, int]]:
+    """THE RULE: (H, W) of the luma plane of a [..., 3H/2, W] array, H and W even; None for any other shape."""
     if len(shape) < 2 or shape[-2] < 3 or shape[-2] % 3 or shape[-1] < 2 or shape[-1] % 2:
-        raise ValueError(f"{what}: a 4:2:0 frame is [3H/2, W] with H and W even (rows a multiple of 3), got {tuple(shape)}")
+        return None
     return shape[-2] // 3 * 2, shape[-1]
+
+
+def _yuv_geometry(shape, what: str) -> Tuple[int, int]:
+    hw = _yuv_hw(shape)
+    if hw is None:
+        raise ValueError(f"{what}: a 4:2:0 frame is [3H/2, W] with H and W even (rows a multiple of 3), got {tuple(shape)}")
+    return hw
 
 
 def yuv420_to_rgb_np(frames: np.ndarray, layout: str = "i420", matrix: str = "bt601") -> np.ndarray:
@@ -229,11 +244,12 @@ def yuv_desc(layout: str, matrix: str) -> _lib.YuvDesc:
 def check_yuv420(frames: torch.Tensor, what: str) -> Tuple[int, int, int]:
     """(n, H, W) of a uint8 [N,3H/2,W] device tensor; RuntimeError for anything else."""
     _lib.require_cuda(frames, what)
-    if (frames.dtype != torch.uint8 or frames.dim() != 3 or min(frames.shape) < 1 or frames.shape[1] % 3 or frames.shape[2] % 2):
+    hw = _yuv_hw(frames.shape) if frames.dtype == torch.uint8 and frames.dim() == 3 and frames.shape[0] >= 1 else None
+    if hw is None:
         raise RuntimeError(f"{what}: expected a uint8 [N,3H/2,W] tensor with H and W even, got {frames.dtype} {tuple(frames.shape)}")
     if not frames.is_contiguous():
         raise RuntimeError(f"{what}: frames must be contiguous (planes one after the other, as a video decoder leaves them)")
-    return frames.shape[0], frames.shape[1] // 3 * 2, frames.shape[2]
+    return (frames.shape[0],) + hw
 
 
 @torch.no_grad()
@@ -285,9 +301,7 @@ def upscale_yuv420(model, frames: torch.Tensor, layout: str = "i420", matrix: st
         return model.forward_yuv420(frames, layout, matrix)
     if o is not None:
         yuv420_output_size(h, w, s, o, "upscale_yuv420")
-        if plan is None:
-            from .imgproc import ResizePlan
-            plan = ResizePlan(h * s, w * s, o / s, frames.device)         # ValueError before any launch, as in upscale_u8
+        plan = _resize_plan(h, w, s, o, frames.device, plan)              # ValueError before any launch, as in upscale_u8
     rgb = upscale_u8(model, yuv420_to_rgb(frames, layout, matrix), halo, outscale=o, plan=plan)
     return rgb_to_yuv420(rgb, layout, matrix)
 
@@ -335,6 +349,7 @@ class FrameStream:
             raise ValueError(f"FrameStream: pix_fmt must be one of {self.PIX_FMTS}, got {pix_fmt!r}")
         _yuv_names("i420", matrix, "FrameStream")
         self.pix_fmt, self.matrix = pix_fmt, matrix
+        self._fmt = _Rgb24 if pix_fmt == "rgb24" else _Yuv420(pix_fmt, matrix)
         self.outscale = check_outscale(outscale, getattr(model, "upscale_factor", 0), "FrameStream")
         self._plan = None
         param = next(iter(model.parameters()), None)
@@ -357,8 +372,7 @@ class FrameStream:
 
     @staticmethod
     def check_frame_yuv420(frame) -> None:
-        if (not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 2 or frame.shape[0] < 3 or frame.shape[0] % 3
-                or frame.shape[1] < 2 or frame.shape[1] % 2):
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 2 or _yuv_hw(frame.shape) is None:
             got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
             raise ValueError(f"FrameStream: expected a [3H/2, W] uint8 ndarray with H and W even (a 4:2:0 frame), got {got}")
 
@@ -385,17 +399,8 @@ class FrameStream:
                 st.synchronize()
         s = self.model.upscale_factor
         self._plan = None
-        if self.pix_fmt != "rgb24":
-            yuv420_output_size(h, w, s, self.outscale, "FrameStream")      # an odd result: ValueError before anything is allocated
-        if self.outscale is not None:
-            from .imgproc import ResizePlan
-            self._plan = ResizePlan(h * s, w * s, self.outscale / s, self.device)
-        if self.pix_fmt == "rgb24":
-            out_h, out_w = output_size(h, w, s, self.outscale)
-            in_shape, out_shape = (h, w, 3), (out_h, out_w, 3)
-        else:
-            out_h, out_w = yuv420_output_size(h, w, s, self.outscale, "FrameStream")
-            in_shape, out_shape = (h * 3 // 2, w), (out_h * 3 // 2, out_w)
+        in_shape, out_shape = self._fmt.shapes(h, w, s, self.outscale)     # an odd 4:2:0 result: ValueError before anything is allocated
+        self._plan = _resize_plan(h, w, s, self.outscale, self.device)
         with torch.cuda.device(self.device):
             self._slots = [_Slot(in_shape, out_shape, self.device) for _ in range(self.depth)]
         self._shape, self._next = (h, w), 0
@@ -403,12 +408,7 @@ class FrameStream:
     def submit(self, frame: np.ndarray) -> None:
         if self._closed:
             raise RuntimeError("FrameStream: closed")
-        if self.pix_fmt == "rgb24":
-            self.check_frame(frame)
-            size = frame.shape[:2]
-        else:
-            self.check_frame_yuv420(frame)
-            size = (frame.shape[0] // 3 * 2, frame.shape[1])
+        size = self._fmt.size(frame)
         if len(self._pending) >= self.depth:
             raise RuntimeError(f"FrameStream: {self.depth} frames are pending already; take a result() first")
         if size != self._shape:
@@ -423,10 +423,7 @@ class FrameStream:
             slot.uploaded.record(self._up)
         with torch.cuda.stream(self._compute):
             self._compute.wait_event(slot.uploaded)
-            if self.pix_fmt == "rgb24":
-                slot.dev_out = upscale_u8(self.model, slot.dev_in, outscale=self.outscale, plan=self._plan)
-            else:
-                slot.dev_out = upscale_yuv420(self.model, slot.dev_in, self.pix_fmt, self.matrix, outscale=self.outscale, plan=self._plan)
+            slot.dev_out = self._fmt.upscale(self.model, slot.dev_in, self.outscale, self._plan)
             slot.computed.record(self._compute)
         with torch.cuda.stream(self._down):
             self._down.wait_event(slot.computed)
@@ -468,3 +465,41 @@ class FrameStream:
 
     def __exit__(self, *exc) -> None:
         self.close()
+
+
+class _Rgb24:
+    """What FrameStream asks of its pixel format: `size(frame)` checks a host frame and returns its (h, w); `shapes(h, w, s,
+    outscale)` the slots' (in_shape, out_shape), ValueError for a result the format cannot hold; `upscale(model, dev_in, outscale,
+    plan)` runs one slot on the device."""
+
+    @staticmethod
+    def size(frame):
+        FrameStream.check_frame(frame)
+        return frame.shape[:2]
+
+    @staticmethod
+    def shapes(h, w, s, outscale):
+        out_h, out_w = output_size(h, w, s, outscale)
+        return (h, w, 3), (out_h, out_w, 3)
+
+    @staticmethod
+    def upscale(model, dev_in, outscale, plan):
+        return upscale_u8(model, dev_in, outscale=outscale, plan=plan)
+
+
+class _Yuv420:
+    def __init__(self, layout: str, matrix: str) -> None:
+        self.layout, self.matrix = layout, matrix
+
+    @staticmethod
+    def size(frame):
+        FrameStream.check_frame_yuv420(frame)
+        return _yuv_hw(frame.shape)
+
+    @staticmethod
+    def shapes(h, w, s, outscale):
+        out_h, out_w = yuv420_output_size(h, w, s, outscale, "FrameStream")
+        return (h * 3 // 2, w), (out_h * 3 // 2, out_w)
+
+    def upscale(self, model, dev_in, outscale, plan):
+        return upscale_yuv420(model, dev_in, self.layout, self.matrix, outscale=outscale, plan=plan)

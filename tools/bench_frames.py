@@ -36,6 +36,7 @@ import os
 import statistics
 import sys
 import time
+from types import SimpleNamespace
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
@@ -82,62 +83,72 @@ def device_ms(fn, steps):
     return start.elapsed_time(end) / steps
 
 
-def main_outscale(args):
-    o = args.outscale
+def run_cases(args, build):
+    """The measurement every mode shares.  `build(model)` describes a mode for one model, a SimpleNamespace of
+      head, frame   the case's fields between `tool` and `num_conv`, and its `frame` text
+      dev           {name: fn}: device callables, timed with HIP events under no_grad (dev_extra: {name: more fields of its line})
+      paths         {name: (frames, run, fields)}: host-to-host loops, `run(frames)` returns how many results came back; `fields` go
+                    on the path's line (gbps: also d2h_gb_per_s from its d2h_bytes_per_frame)
+      host_first    the paths come before the device callables in the warm-up, in every round and in the output
+      check         () -> what the summary reports about equal results, taken before the warm-up
+      summary       (med, spread, ms, same) -> the fields of the summary line
+      streams       what to close after the case
+    Owns the (num_conv, precision) grid, warm-up, the alternated rounds, the lines and --out."""
     torch.cuda.set_device(0)
     box = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]}
-    rs = np.random.RandomState(0)
-    pool = [rs.randint(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(4)]
-    many = [pool[i % 4] for i in range(args.frames * 4)]
-    oh, ow = R.output_size(H, W, S, o)
     lines = []
+
+    def emit(line):
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+
     for num_conv in (16, 32):
         for precision in ("fast", "exact16"):
             torch.manual_seed(0)
             model = R.SRVGGNetCompact(num_conv=num_conv, upscale=S, precision=precision).cuda().eval().requires_grad_(False)
-            x4, scaled = R.FrameStream(model, depth=2), R.FrameStream(model, depth=2, outscale=o)
-            x_u8 = torch.from_numpy(pool[0])[None].cuda()
-            x_f32 = R.from_u8(x_u8)
-            plan = imgproc.ResizePlan(H * S, W * S, o / S, x_u8.device)
-            dev = {"dev/forward_u8": lambda: model.forward_u8(x_u8),
-                   "dev/forward_u8_outscale": lambda: model.forward_u8(x_u8, outscale=o, plan=plan),
-                   "dev/unfused_outscale": lambda: imgproc.resize_with_plan(model(x_f32), plan, u8=True)}
-            paths = {"B2/2": (lambda fr: sum(1 for _ in x4.map(fr)), OUT_U8),
-                     "B2/2/view": (lambda fr: sum(1 for _ in x4.map(fr, copy=False)), OUT_U8),
-                     "B2/2/outscale": (lambda fr: sum(1 for _ in scaled.map(fr)), oh * ow * 3),
-                     "B2/2/outscale/view": (lambda fr: sum(1 for _ in scaled.map(fr, copy=False)), oh * ow * 3)}
-            with torch.no_grad():
-                same = bool(torch.equal(dev["dev/forward_u8_outscale"](), dev["dev/unfused_outscale"]()))
-                for fn in dev.values():
-                    for _ in range(3):
-                        fn()
-            for run, _ in paths.values():
-                run(many[:2])
-            ms = {name: [] for name in list(dev) + list(paths)}
-            for _ in range(args.rounds):
+            m = build(model)
+
+            def dev_pass(ms):            # ms None: the warm-up
                 with torch.no_grad():
-                    for name, fn in dev.items():
-                        ms[name].append(device_ms(fn, args.device_steps))
-                for name, (run, _) in paths.items():
-                    ms[name].append(wall_ms(run, many))
-            case = dict(tool="bench_frames", outscale=o, num_conv=num_conv, precision=precision, frame=f"{W}x{H}->{ow}x{oh}", **box)
+                    for name, fn in m.dev.items():
+                        if ms is None:
+                            for _ in range(3):
+                                fn()
+                        else:
+                            ms[name].append(device_ms(fn, args.device_steps))
+
+            def host_pass(ms):
+                for name, (fr, run, _) in m.paths.items():
+                    if ms is None:
+                        run(fr[:2])
+                    else:
+                        ms[name].append(wall_ms(run, fr))
+
+            passes = (host_pass, dev_pass) if m.host_first else (dev_pass, host_pass)
+            with torch.no_grad():
+                same = m.check()
+            for one in passes:
+                one(None)
+            ms = {name: [] for name in (list(m.paths) + list(m.dev) if m.host_first else list(m.dev) + list(m.paths))}
+            for _ in range(args.rounds):
+                for one in passes:
+                    one(ms)
+            case = dict(tool="bench_frames", **m.head, num_conv=num_conv, precision=precision, frame=m.frame, **box)
             med = {name: statistics.median(v) for name, v in ms.items()}
+            spread = {name: max(v) - min(v) for name, v in ms.items()}
             for name, v in ms.items():
-                extra = dict(d2h_bytes_per_frame=paths[name][1]) if name in paths else dict(steps=args.device_steps)
-                line = dict(case, path=name, ms_per_frame_rounds=[round(x, 3) for x in v], ms_per_frame=round(med[name], 3),
-                            spread_ms=round(max(v) - min(v), 3), frames_per_s=round(1e3 / med[name], 2), **extra)
-                print(json.dumps(line), flush=True)
-                lines.append(line)
-            line = dict(case, path="summary", fused_equals_unfused=same,
-                        fused_over_x4_device=round(med["dev/forward_u8_outscale"] / med["dev/forward_u8"], 3),
-                        fused_over_unfused_device=round(med["dev/forward_u8_outscale"] / med["dev/unfused_outscale"], 3),
-                        stream_outscale_over_x4_frames_per_s=round(med["B2/2"] / med["B2/2/outscale"], 2),
-                        stream_view_outscale_over_x4_frames_per_s=round(med["B2/2/view"] / med["B2/2/outscale/view"], 2))
-            print(json.dumps(line), flush=True)
-            lines.append(line)
-            x4.close()
-            scaled.close()
-            del model, x4, scaled, dev, paths
+                if name in m.paths:
+                    extra = dict(m.paths[name][2])
+                    if m.gbps:
+                        extra["d2h_gb_per_s"] = round(extra["d2h_bytes_per_frame"] / (med[name] * 1e-3) / 1e9, 2)
+                else:
+                    extra = dict(steps=args.device_steps, **m.dev_extra.get(name, {}))
+                emit(dict(case, path=name, ms_per_frame_rounds=[round(x, 3) for x in v], ms_per_frame=round(med[name], 3),
+                          spread_ms=round(spread[name], 3), frames_per_s=round(1e3 / med[name], 2), **extra))
+            emit(dict(case, path="summary", **m.summary(med, spread, ms, same)))
+            for st in m.streams:
+                st.close()
+            del model, m
             torch.cuda.empty_cache()
     if args.out:
         with open(args.out, "a") as f:
@@ -145,79 +156,128 @@ def main_outscale(args):
                 f.write(json.dumps(line) + "\n")
 
 
-def main_yuv(args):
-    o = args.outscale
-    torch.cuda.set_device(0)
-    box = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]}
+def frame_pool(args):
     rs = np.random.RandomState(0)
     pool = [rs.randint(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(4)]
-    many = [pool[i % 4] for i in range(args.frames * 4)]
+    return pool, [pool[i % 4] for i in range(args.frames * 4)]
+
+
+def count(results):
+    return sum(1 for _ in results)
+
+
+def mode_x4(args):
+    pool, many = frame_pool(args)
+    few = many[:args.frames]
+
+    def build(model):
+        streams = {d: R.FrameStream(model, depth=d) for d in (2, 3)}
+        x_u8 = torch.from_numpy(pool[0])[None].cuda()
+        x_f32 = R.from_u8(x_u8)
+        f32 = dict(frames_per_loop=len(few), h2d_bytes_per_frame=IN_U8 * 4, d2h_bytes_per_frame=OUT_U8 * 4)
+        u8 = dict(h2d_bytes_per_frame=IN_U8, d2h_bytes_per_frame=OUT_U8)
+        one, loop = dict(frames_per_loop=len(few), **u8), dict(frames_per_loop=len(many), **u8)
+        paths = {"A": (few, lambda fr: sum(1 for f in fr if path_a(model, f) is not None), f32),
+                 "B1": (few, lambda fr: sum(1 for f in fr if path_b1(model, f) is not None), one),
+                 "B2/2": (many, lambda fr: count(streams[2].map(fr)), loop),
+                 "B2/3": (many, lambda fr: count(streams[3].map(fr)), loop),
+                 "B2/2/view": (many, lambda fr: count(streams[2].map(fr, copy=False)), loop)}
+
+        def summary(med, spread, ms, same):
+            best = min(("B2/2", "B2/3"), key=lambda k: med[k])
+            return dict(outputs_equal=same, speedup_b1_over_a=round(med["A"] / med["B1"], 2),
+                        speedup_b2_depth2_over_a=round(med["A"] / med["B2/2"], 2), speedup_b2_depth3_over_a=round(med["A"] / med["B2/3"], 2),
+                        b2_faster_than_a_beyond_spread=bool(max(ms[best]) + 0.0 < min(ms["A"])),
+                        device_u8_over_float=round(med["dev/forward_u8"] / med["dev/forward"], 3),
+                        device_u8_not_slower_beyond_spread=bool(med["dev/forward_u8"] <= med["dev/forward"] + max(spread["dev/forward"], spread["dev/forward_u8"])))
+
+        return SimpleNamespace(
+            head={}, frame=f"{W}x{H}->x{S}", host_first=True, gbps=True, paths=paths, streams=list(streams.values()), summary=summary,
+            dev={"dev/forward": lambda: model(x_f32), "dev/forward_u8": lambda: model.forward_u8(x_u8)},
+            dev_extra={"dev/forward": dict(out_bytes_per_frame=OUT_U8 * 4), "dev/forward_u8": dict(out_bytes_per_frame=OUT_U8)},
+            # results must not change: the two ends of the comparison give the same bytes on a timed frame
+            check=lambda: bool(np.array_equal(path_a(model, pool[0]), path_b1(model, pool[0])) and
+                               np.array_equal(next(iter(streams[2].map(pool[:1]))), path_b1(model, pool[0]))))
+
+    return build
+
+
+def mode_outscale(args):
+    o = args.outscale
+    pool, many = frame_pool(args)
+    oh, ow = R.output_size(H, W, S, o)
+
+    def build(model):
+        x4, scaled = R.FrameStream(model, depth=2), R.FrameStream(model, depth=2, outscale=o)
+        x_u8 = torch.from_numpy(pool[0])[None].cuda()
+        x_f32 = R.from_u8(x_u8)
+        plan = imgproc.ResizePlan(H * S, W * S, o / S, x_u8.device)
+        dev = {"dev/forward_u8": lambda: model.forward_u8(x_u8),
+               "dev/forward_u8_outscale": lambda: model.forward_u8(x_u8, outscale=o, plan=plan),
+               "dev/unfused_outscale": lambda: imgproc.resize_with_plan(model(x_f32), plan, u8=True)}
+        paths = {"B2/2": (many, lambda fr: count(x4.map(fr)), dict(d2h_bytes_per_frame=OUT_U8)),
+                 "B2/2/view": (many, lambda fr: count(x4.map(fr, copy=False)), dict(d2h_bytes_per_frame=OUT_U8)),
+                 "B2/2/outscale": (many, lambda fr: count(scaled.map(fr)), dict(d2h_bytes_per_frame=oh * ow * 3)),
+                 "B2/2/outscale/view": (many, lambda fr: count(scaled.map(fr, copy=False)), dict(d2h_bytes_per_frame=oh * ow * 3))}
+
+        def summary(med, spread, ms, same):
+            return dict(fused_equals_unfused=same,
+                        fused_over_x4_device=round(med["dev/forward_u8_outscale"] / med["dev/forward_u8"], 3),
+                        fused_over_unfused_device=round(med["dev/forward_u8_outscale"] / med["dev/unfused_outscale"], 3),
+                        stream_outscale_over_x4_frames_per_s=round(med["B2/2"] / med["B2/2/outscale"], 2),
+                        stream_view_outscale_over_x4_frames_per_s=round(med["B2/2/view"] / med["B2/2/outscale/view"], 2))
+
+        return SimpleNamespace(head=dict(outscale=o), frame=f"{W}x{H}->{ow}x{oh}", host_first=False, gbps=False, dev=dev, dev_extra={},
+                               paths=paths, streams=[x4, scaled], summary=summary,
+                               check=lambda: bool(torch.equal(dev["dev/forward_u8_outscale"](), dev["dev/unfused_outscale"]())))
+
+    return build
+
+
+def mode_yuv(args):
+    o = args.outscale
+    pool, many = frame_pool(args)
     # the same pictures as 4:2:0 frames, so that every path upscales the same content
     yuv = {fmt: [R.rgb_to_yuv420_np(f, fmt) for f in pool] for fmt in args.pix_fmt}
     many_yuv = {fmt: [yuv[fmt][i % 4] for i in range(args.frames * 4)] for fmt in args.pix_fmt}
     oh, ow = R.output_size(H, W, S, o)
-    lines = []
-    for num_conv in (16, 32):
-        for precision in ("fast", "exact16"):
-            torch.manual_seed(0)
-            model = R.SRVGGNetCompact(num_conv=num_conv, upscale=S, precision=precision).cuda().eval().requires_grad_(False)
-            streams = {"rgb24": R.FrameStream(model, depth=2, outscale=o)}
-            x_u8 = torch.from_numpy(pool[0])[None].cuda()
-            dev = {"dev/forward_u8": lambda: R.upscale_u8(model, x_u8, outscale=o)}
-            paths = {"B2/2": (many, lambda fr: sum(1 for _ in streams["rgb24"].map(fr)), H * W * 3, oh * ow * 3),
-                     "B2/2/view": (many, lambda fr: sum(1 for _ in streams["rgb24"].map(fr, copy=False)), H * W * 3, oh * ow * 3)}
+    rgb_bytes = dict(h2d_bytes_per_frame=H * W * 3, d2h_bytes_per_frame=oh * ow * 3)
+    yuv_bytes = dict(h2d_bytes_per_frame=H * W * 3 // 2, d2h_bytes_per_frame=oh * ow * 3 // 2)
+
+    def build(model):
+        streams = {"rgb24": R.FrameStream(model, depth=2, outscale=o)}
+        x_u8 = torch.from_numpy(pool[0])[None].cuda()
+        dev = {"dev/forward_u8": lambda: R.upscale_u8(model, x_u8, outscale=o)}
+        paths = {"B2/2": (many, lambda fr: count(streams["rgb24"].map(fr)), rgb_bytes),
+                 "B2/2/view": (many, lambda fr: count(streams["rgb24"].map(fr, copy=False)), rgb_bytes)}
+        x_yuv = {}
+        for fmt in args.pix_fmt:
+            streams[fmt] = R.FrameStream(model, depth=2, outscale=o, pix_fmt=fmt)
+            x_yuv[fmt] = torch.from_numpy(yuv[fmt][0])[None].cuda()
+            dev[f"dev/forward_{fmt}"] = lambda fmt=fmt: R.upscale_yuv420(model, x_yuv[fmt], fmt, outscale=o)
+            paths[f"B2/2/{fmt}"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr)), yuv_bytes)
+            paths[f"B2/2/{fmt}/view"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr, copy=False)), yuv_bytes)
+
+        def check():     # the definition, on a timed frame: the stream's result is the composition over the RGB path
             same = {}
             for fmt in args.pix_fmt:
-                streams[fmt] = R.FrameStream(model, depth=2, outscale=o, pix_fmt=fmt)
-                x_yuv = torch.from_numpy(yuv[fmt][0])[None].cuda()
-                dev[f"dev/forward_{fmt}"] = lambda x=x_yuv, fmt=fmt: R.upscale_yuv420(model, x, fmt, outscale=o)
-                paths[f"B2/2/{fmt}"] = (many_yuv[fmt], lambda fr, fmt=fmt: sum(1 for _ in streams[fmt].map(fr)), H * W * 3 // 2, oh * ow * 3 // 2)
-                paths[f"B2/2/{fmt}/view"] = (many_yuv[fmt], lambda fr, fmt=fmt: sum(1 for _ in streams[fmt].map(fr, copy=False)),
-                                             H * W * 3 // 2, oh * ow * 3 // 2)
-                # the definition, on a timed frame: the stream's result is the composition over the RGB path
-                want = R.rgb_to_yuv420(R.upscale_u8(model, R.yuv420_to_rgb(x_yuv, fmt), outscale=o), fmt)[0].cpu().numpy()
+                want = R.rgb_to_yuv420(R.upscale_u8(model, R.yuv420_to_rgb(x_yuv[fmt], fmt), outscale=o), fmt)[0].cpu().numpy()
                 same[fmt] = bool(np.array_equal(next(iter(streams[fmt].map(yuv[fmt][:1]))), want))
-            with torch.no_grad():
-                for fn in dev.values():
-                    for _ in range(3):
-                        fn()
-            for fr, run, _, _ in paths.values():
-                run(fr[:2])
-            ms = {name: [] for name in list(dev) + list(paths)}
-            for _ in range(args.rounds):
-                with torch.no_grad():
-                    for name, fn in dev.items():
-                        ms[name].append(device_ms(fn, args.device_steps))
-                for name, (fr, run, _, _) in paths.items():
-                    ms[name].append(wall_ms(run, fr))
-            case = dict(tool="bench_frames", pix_fmt=list(args.pix_fmt), outscale=o, num_conv=num_conv, precision=precision,
-                        frame=f"{W}x{H}->{ow}x{oh}", **box)
-            med = {name: statistics.median(v) for name, v in ms.items()}
-            for name, v in ms.items():
-                extra = dict(steps=args.device_steps)
-                if name in paths:
-                    extra = dict(h2d_bytes_per_frame=paths[name][2], d2h_bytes_per_frame=paths[name][3],
-                                 d2h_gb_per_s=round(paths[name][3] / (med[name] * 1e-3) / 1e9, 2))
-                line = dict(case, path=name, ms_per_frame_rounds=[round(x, 3) for x in v], ms_per_frame=round(med[name], 3),
-                            spread_ms=round(max(v) - min(v), 3), frames_per_s=round(1e3 / med[name], 2), **extra)
-                print(json.dumps(line), flush=True)
-                lines.append(line)
-            line = dict(case, path="summary", yuv_equals_composition=same)
+            return same
+
+        def summary(med, spread, ms, same):
+            line = dict(yuv_equals_composition=same)
             for fmt in args.pix_fmt:
                 line[f"device_{fmt}_over_u8"] = round(med[f"dev/forward_{fmt}"] / med["dev/forward_u8"], 3)
                 line[f"device_{fmt}_minus_u8_ms"] = round(med[f"dev/forward_{fmt}"] - med["dev/forward_u8"], 3)
                 line[f"stream_{fmt}_over_rgb24_frames_per_s"] = round(med["B2/2"] / med[f"B2/2/{fmt}"], 2)
                 line[f"stream_view_{fmt}_over_rgb24_frames_per_s"] = round(med["B2/2/view"] / med[f"B2/2/{fmt}/view"], 2)
-            print(json.dumps(line), flush=True)
-            lines.append(line)
-            for st in streams.values():
-                st.close()
-            del model, streams, dev, paths
-            torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+            return line
+
+        return SimpleNamespace(head=dict(pix_fmt=list(args.pix_fmt), outscale=o), frame=f"{W}x{H}->{ow}x{oh}", host_first=False, gbps=True,
+                               dev=dev, dev_extra={}, paths=paths, streams=list(streams.values()), summary=summary, check=check)
+
+    return build
 
 
 def main():
@@ -231,80 +291,8 @@ def main():
                     help="measure the YUV 4:2:0 path in these layouts against rgb24 instead (see above; combines with --outscale)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_frames.py measures on the GPU"
-    if args.pix_fmt:
-        return main_yuv(args)
-    if args.outscale is not None:
-        return main_outscale(args)
-    torch.cuda.set_device(0)
-    box = {"device": torch.cuda.get_device_name(0), "arch": torch.cuda.get_device_properties(0).gcnArchName.split(":")[0]}
-    rs = np.random.RandomState(0)
-    pool = [rs.randint(0, 256, size=(H, W, 3), dtype=np.uint8) for _ in range(4)]
-    few = [pool[i % 4] for i in range(args.frames)]
-    many = [pool[i % 4] for i in range(args.frames * 4)]
-    lines = []
-
-    def emit(line):
-        print(json.dumps(line), flush=True)
-        lines.append(line)
-
-    for num_conv in (16, 32):
-        for precision in ("fast", "exact16"):
-            torch.manual_seed(0)
-            model = R.SRVGGNetCompact(num_conv=num_conv, upscale=S, precision=precision).cuda().eval().requires_grad_(False)
-            streams = {d: R.FrameStream(model, depth=d) for d in (2, 3)}
-            paths = {
-                "A": (few, lambda fr: sum(1 for f in fr if path_a(model, f) is not None), IN_U8 * 4, OUT_U8 * 4),
-                "B1": (few, lambda fr: sum(1 for f in fr if path_b1(model, f) is not None), IN_U8, OUT_U8),
-                "B2/2": (many, lambda fr: sum(1 for _ in streams[2].map(fr)), IN_U8, OUT_U8),
-                "B2/3": (many, lambda fr: sum(1 for _ in streams[3].map(fr)), IN_U8, OUT_U8),
-                "B2/2/view": (many, lambda fr: sum(1 for _ in streams[2].map(fr, copy=False)), IN_U8, OUT_U8),
-            }
-            # results must not change: the two ends of the comparison give the same bytes on a timed frame
-            same = bool(np.array_equal(path_a(model, pool[0]), path_b1(model, pool[0])) and
-                        np.array_equal(next(iter(streams[2].map(pool[:1]))), path_b1(model, pool[0])))
-            x_f32 = R.from_u8(torch.from_numpy(pool[0])[None].cuda())
-            x_u8 = torch.from_numpy(pool[0])[None].cuda()
-            dev = {"dev/forward": lambda: model(x_f32), "dev/forward_u8": lambda: model.forward_u8(x_u8)}
-            for name, (fr, run, _, _) in paths.items():      # warm-up of every path
-                run(fr[:2])
-            with torch.no_grad():
-                for fn in dev.values():
-                    for _ in range(3):
-                        fn()
-            ms = {name: [] for name in list(paths) + list(dev)}
-            for _ in range(args.rounds):
-                for name, (fr, run, _, _) in paths.items():
-                    ms[name].append(wall_ms(run, fr))
-                with torch.no_grad():
-                    for name, fn in dev.items():
-                        ms[name].append(device_ms(fn, args.device_steps))
-            case = dict(tool="bench_frames", num_conv=num_conv, precision=precision, frame=f"{W}x{H}->x{S}", **box)
-            med, spread = {}, {}
-            for name, v in ms.items():
-                med[name], spread[name] = statistics.median(v), max(v) - min(v)
-                extra = {}
-                if name in paths:
-                    extra = dict(frames_per_loop=len(paths[name][0]), h2d_bytes_per_frame=paths[name][2], d2h_bytes_per_frame=paths[name][3],
-                                 d2h_gb_per_s=round(paths[name][3] / (med[name] * 1e-3) / 1e9, 2))
-                else:
-                    extra = dict(steps=args.device_steps, out_bytes_per_frame=OUT_U8 * (4 if name == "dev/forward" else 1))
-                emit(dict(case, path=name, ms_per_frame_rounds=[round(x, 3) for x in v], ms_per_frame=round(med[name], 3),
-                          spread_ms=round(spread[name], 3), frames_per_s=round(1e3 / med[name], 2), **extra))
-            best = min(("B2/2", "B2/3"), key=lambda k: med[k])
-            emit(dict(case, path="summary", outputs_equal=same,
-                      speedup_b1_over_a=round(med["A"] / med["B1"], 2), speedup_b2_depth2_over_a=round(med["A"] / med["B2/2"], 2),
-                      speedup_b2_depth3_over_a=round(med["A"] / med["B2/3"], 2),
-                      b2_faster_than_a_beyond_spread=bool(max(ms[best]) + 0.0 < min(ms["A"])),
-                      device_u8_over_float=round(med["dev/forward_u8"] / med["dev/forward"], 3),
-                      device_u8_not_slower_beyond_spread=bool(med["dev/forward_u8"] <= med["dev/forward"] + max(spread["dev/forward"], spread["dev/forward_u8"]))))
-            for st in streams.values():
-                st.close()
-            del model, streams, paths, dev
-            torch.cuda.empty_cache()
-    if args.out:
-        with open(args.out, "a") as f:
-            for line in lines:
-                f.write(json.dumps(line) + "\n")
+    mode = mode_yuv if args.pix_fmt else mode_outscale if args.outscale is not None else mode_x4
+    run_cases(args, mode(args))
 
 
 if __name__ == "__main__":
