@@ -489,6 +489,39 @@ int resr_compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x_yuv, 
 int resr_yuv420_to_rgb(const uint8_t* src, uint8_t* dst_hwc, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream);
 int resr_rgb_to_yuv420(const uint8_t* src_hwc, uint8_t* dst, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream);
 
+/* 10-bit YUV 4:2:0 frames (frames.hip): what decoders deliver for most HEVC / AV1 material, 1024 levels instead of 256 at both ends
+ * of the network.  The geometry is that of the 8-bit frames with a little-endian 16-bit word per sample, 3 bytes per pixel: a frame
+ * of luma size H x W (both even) is a uint16 array [3H/2, W], batches [N,3H/2,W], contiguous:
+ *   RESR_YUV_I420P10 (yuv420p10le): planes as RESR_YUV_I420, the sample in the low 10 bits: read word & 1023, written with the
+ *                                   high 6 bits zero;
+ *   RESR_YUV_P010 (p010le):         planes as RESR_YUV_NV12, the sample in the high 10 bits: read word >> 6, written as
+ *                                   sample << 6 with the low 6 bits zero.
+ * Every 16-bit word is legal input.  The descriptor is ResrYuvDesc with one of these two layouts and the Q16 tables of the 10-bit
+ * studio range (frames.yuv420p10_tables; rows of iq over Y - 64, Cb - 512, Cr - 512); the conversions are the 8-bit ones with 64 /
+ * 512 / 1023 in place of 16 / 128 / 255, int32 throughout (the largest accumulator is below 2^28 with those tables):
+ *   in : rgb10[c] = clamp((iq[c] . (Y - 64, Cb - 512, Cr - 512) + 32768) >> 16, 0, 1023), chroma replicated over its 2x2 block;
+ *        the model's input is (float)rgb10 / 1023.0f, one IEEE division;
+ *   out: q10(v) = trunc(clamp(v * 1023.0f, 0, 1023)) (a NaN gives 0); Y = (fq[0] . q10 + (64 << 16) + 32768) >> 16 per pixel;
+ *        Cb = (fq[1] . S + (512 << 18) + (1 << 17)) >> 18 with S the sum of a 2x2 block's four q10 triples, Cr likewise with fq[2].
+ *        The kernels mask the results to 10 bits and do not clamp: with the tables above Y stays in 64..940, Cb / Cr in 64..960.
+ * The path is DEFINED as a composition, bit for bit:
+ *   resr_compact_forward_yuv420p10(f) == resr_nchw_to_yuv420p10(resr_compact_forward(resr_yuv420p10_to_nchw(f)))
+ * resr_compact_forward_yuv420p10: resr_compact_forward_yuv420 for these frames, both conversions inside the first and the last
+ * kernel, x_yuv [N, 3 d->h / 2, d->w] -> y_yuv [N, 3 s d->h / 2, s d->w] in the same layout; same descriptor, packed weights and
+ * workspace, same checks and codes.  Neither an RGB frame nor an fp32 copy of the input exists: the tail recomputes the residual
+ * from x_yuv, which must stay valid until the call has run.
+ * resr_yuv420p10_to_nchw / resr_nchw_to_yuv420p10: the generic conversions, one launch each, straight between the frames and fp32
+ * [N,3,H,W], for every case whose ends are not fused (the RRDB generator, tiled frames, outscale).
+ * RESR_ERR_ARG before any launch: a null pointer; n, h, w <= 0; an odd h or w; a layout other than these two (the 8-bit entries
+ * refuse these two in turn); a misaligned end: y_yuv 16-byte aligned when s * d->w is a multiple of 8; for resr_nchw_to_yuv420p10
+ * dst 8-byte and src_f32 16-byte aligned when w is a multiple of 4; 2 bytes per word and 4 per float everywhere else.
+ * Mixed depths (8 bits in, 10 out), 12 / 16-bit samples, full range and 4:2:2 / 4:4:4 are not provided. */
+enum { RESR_YUV_I420P10 = 2, RESR_YUV_P010 = 3 };
+int resr_compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x_yuv, const float* params, const void* packed,
+                                   void* workspace, size_t workspace_bytes, uint16_t* y_yuv, const ResrYuvDesc* yuv, void* stream);
+int resr_yuv420p10_to_nchw(const uint16_t* src, float* dst_f32, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream);
+int resr_nchw_to_yuv420p10(const float* src_f32, uint16_t* dst, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream);
+
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */
 

@@ -130,6 +130,7 @@ class CompactDesc(C.Structure):
 
 
 YUV_I420, YUV_NV12 = 0, 1   # ResrYuvDesc.layout
+YUV_I420P10, YUV_P010 = 2, 3   # ... of the 10-bit entries: 16-bit words, the sample in the low / the high 10 bits
 
 
 class YuvDesc(C.Structure):
@@ -189,6 +190,9 @@ _PROTOS = {
     "resr_compact_forward_yuv420": (C.c_int, [C.POINTER(CompactDesc), _P, _P, _P, _P, C.c_size_t, _P, C.POINTER(YuvDesc), _P]),
     "resr_yuv420_to_rgb": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvDesc), _P]),
     "resr_rgb_to_yuv420": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvDesc), _P]),
+    "resr_compact_forward_yuv420p10": (C.c_int, [C.POINTER(CompactDesc), _P, _P, _P, _P, C.c_size_t, _P, C.POINTER(YuvDesc), _P]),
+    "resr_yuv420p10_to_nchw": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvDesc), _P]),
+    "resr_nchw_to_yuv420p10": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(YuvDesc), _P]),
     "resr_ema_update": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P]),
     "resr_debug_tr_probe": (C.c_int, [_P, _P]),
     "resr_debug_conv_trace": (C.c_int, [_P]),

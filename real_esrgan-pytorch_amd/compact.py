@@ -238,6 +238,20 @@ class SRVGGNetCompact(nn.Module):
         y = torch.empty((n, h * s * 3 // 2, w * s), dtype=torch.uint8, device=frames.device)
         return self._call("resr_compact_forward_yuv420", frames, n, h, w, y, C.byref(ydesc))
 
+    def forward_yuv420p10(self, frames: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601") -> torch.Tensor:
+        """frames uint16 [N,3H/2,W] (10-bit YUV 4:2:0, H and W even; `layout` "i420p10" or "p010", `matrix` "bt601" or "bt709":
+        frames.py) on the model's device, contiguous -> uint16 [N,3sH/2,sW] in the same layout: bit for bit
+        `frames.rgb_to_yuv420p10_np(q10(self(frames.yuv420p10_to_rgb_np(f) / 1023)))`.  `resr_compact_forward_yuv420p10`: the launch
+        sequence of `forward_yuv420` with 1023 levels at both ends -- neither an RGB frame nor an fp32 copy of the input exists on
+        the device.  Same guard, packing and workspace caches as `forward`."""
+        from . import frames as _frames
+        ydesc = _frames.yuv10_desc(layout, matrix)
+        self._guard()
+        n, h, w = _frames.check_yuv420p10(frames, "SRVGGNetCompact.forward_yuv420p10")
+        s = self.upscale
+        y = torch.empty((n, h * s * 3 // 2, w * s), dtype=torch.uint16, device=frames.device)
+        return self._call("resr_compact_forward_yuv420p10", frames, n, h, w, y, C.byref(ydesc))
+
     def load_official_state_dict(self, checkpoint) -> None:
         """Upstream's `{"params_ema": sd}` / `{"params": sd}` (params_ema preferred) or a bare state dict (model.load_official_state_dict)."""
         from .model import load_official_state_dict

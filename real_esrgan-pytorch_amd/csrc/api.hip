@@ -111,6 +111,10 @@ int compact_forward_yuv420(const ResrCompactDesc*, const uint8_t*, const float*,
                            hipStream_t);
 int yuv420_to_rgb_dispatch(const uint8_t*, uint8_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
 int rgb_to_yuv420_dispatch(const uint8_t*, uint8_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
+int compact_forward_yuv420p10(const ResrCompactDesc*, const uint16_t*, const float*, const void*, void*, size_t, uint16_t*, const ResrYuvDesc*,
+                              hipStream_t);
+int yuv420p10_to_nchw_dispatch(const uint16_t*, float*, int, int, int, const ResrYuvDesc*, hipStream_t);
+int nchw_to_yuv420p10_dispatch(const float*, uint16_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
 int u8_to_nchw_dispatch(const uint8_t*, float*, int, int, int, hipStream_t);
 int nchw_to_u8_dispatch(const float*, uint8_t*, int, int, int, hipStream_t);
 
@@ -327,6 +331,22 @@ int resr_yuv420_to_rgb(const uint8_t* src, uint8_t* dst_hwc, int32_t n, int32_t 
 int resr_rgb_to_yuv420(const uint8_t* src_hwc, uint8_t* dst, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return rgb_to_yuv420_dispatch(src_hwc, dst, n, h, w, yuv, (hipStream_t)stream);
+}
+
+int resr_compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x_yuv, const float* params, const void* packed,
+                                   void* workspace, size_t workspace_bytes, uint16_t* y_yuv, const ResrYuvDesc* yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_yuv420p10(d, x_yuv, params, packed, workspace, workspace_bytes, y_yuv, yuv, (hipStream_t)stream);
+}
+
+int resr_yuv420p10_to_nchw(const uint16_t* src, float* dst_f32, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return yuv420p10_to_nchw_dispatch(src, dst_f32, n, h, w, yuv, (hipStream_t)stream);
+}
+
+int resr_nchw_to_yuv420p10(const float* src_f32, uint16_t* dst, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return nchw_to_yuv420p10_dispatch(src_f32, dst, n, h, w, yuv, (hipStream_t)stream);
 }
 
 size_t resr_discriminator_param_count(void) { return discriminator_param_count(); }

@@ -13,7 +13,8 @@
 //                             residual + * 255, clamp, truncate) in place of compact_tail_kernel;
 //   compact_forward_u8_scaled ("outscale") image_resize.hip's fused tail in place of the u8 tail: the HR frame is formed tile by
 //                             tile in LDS and only the resized uint8 frame [N,oh,ow,3] is written;
-//   compact_forward_yuv420    YUV 4:2:0 frames [N,3H/2,W]: frames.hip's head reading YUV, and its YUV tail.
+//   compact_forward_yuv420    YUV 4:2:0 frames [N,3H/2,W]: frames.hip's head reading YUV, and its YUV tail;
+//   compact_forward_yuv420p10 the same for 10-bit frames of 16-bit words (yuv420p10le / P010): 1023 levels at both ends.
 #include <vector>
 
 #include "common.h"
@@ -24,10 +25,12 @@ int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*,
                      const void*, const void*, void*, void*, hipStream_t);
 int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const float*, const float*, void*, hipStream_t);
 int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
-int frame_head_dispatch(const uint8_t*, void*, int, int, int, int, hipStream_t, long, const ResrYuvDesc*);   // frames.hip
+int frame_head_dispatch(const void*, void*, int, int, int, int, hipStream_t, long, const ResrYuvDesc*);   // frames.hip
 int compact_tail_u8(const float*, const uint8_t*, uint8_t*, int, int, int, int, hipStream_t);
 int yuv420_forward_check(const char*, int, int, int, int, const uint8_t*, const ResrYuvDesc*);
 int compact_tail_yuv420(const float*, const uint8_t*, uint8_t*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
+int yuv420p10_forward_check(const char*, int, int, int, int, const uint16_t*, const ResrYuvDesc*);
+int compact_tail_yuv420p10(const float*, const uint16_t*, uint16_t*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
 int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, bool,
                 const void*, ResizeGeom*);                                                                      // image_resize.hip
 int compact_tail_u8_scaled(const float*, const uint8_t*, uint8_t*, int, int, int, int, const int32_t*, const float*, const int32_t*,
@@ -185,6 +188,7 @@ enum EndKind {
     U8_HWC,          // x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8: frames.hip, the conversions fused into the head and the tail
     U8_HWC_SCALED,   // ... -> y [N,oh,ow,3]: the resized tail of image_resize.hip (sc)
     YUV420,          // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames: the colour conversions (yuv) fused into the same two kernels
+    YUV420P10,       // ... of 16-bit words holding 10-bit samples (x_u8 / y_u8 point at uint16_t)
 };
 
 struct Ends {
@@ -194,7 +198,7 @@ struct Ends {
     const uint8_t* x_u8;     // every other kind
     uint8_t* y_u8;
     ScaledTail sc;           // U8_HWC_SCALED
-    const ResrYuvDesc* yuv;  // YUV420, else null
+    const ResrYuvDesc* yuv;  // YUV420, YUV420P10, else null
 };
 
 // Everything a call can be refused for after its descriptor, before the first launch.  U8_HWC_SCALED: fills geom.
@@ -214,6 +218,7 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
                                  e.sc.idx_x, e.sc.w_x, e.sc.taps_x, true, e.y_u8, geom);
             break;
         case YUV420: rc = yuv420_forward_check(who, d.n, d.h, d.w, d.upscale, e.y_u8, e.yuv); break;
+        case YUV420P10: rc = yuv420p10_forward_check(who, d.n, d.h, d.w, d.upscale, (const uint16_t*)e.y_u8, e.yuv); break;
     }
     if (rc) return rc;
     if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
@@ -239,7 +244,7 @@ int compact_run(const ResrCompactDesc* d, const Ends& e, const float* params, co
     const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
     switch (e.kind) {
         case F32_NCHW: rc = nchw_to_nhwc_dispatch(e.x_f32, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32); break;
-        default: rc = frame_head_dispatch(e.x_u8, xin, N, H, W, d->dtype, st, (long)lo32, e.yuv); break;   // yuv null: RGB bytes
+        default: rc = frame_head_dispatch(e.x_u8, xin, N, H, W, d->dtype, st, (long)lo32, e.yuv); break;   // yuv null: RGB bytes; its layout: bytes or 16-bit words
     }
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) {
@@ -283,6 +288,7 @@ int compact_run(const ResrCompactDesc* d, const Ends& e, const float* params, co
         case U8_HWC_SCALED:
             return compact_tail_u8_scaled(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, &geom, st);
         case YUV420: return compact_tail_yuv420(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.yuv, st);
+        case YUV420P10: return compact_tail_yuv420p10(t, (const uint16_t*)e.x_u8, (uint16_t*)e.y_u8, N, H, W, d->upscale, e.yuv, st);
     }
     return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
 }
@@ -306,6 +312,13 @@ int compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x, const flo
     if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420: null argument");
     const Ends e{YUV420, nullptr, nullptr, x, y, {}, yuv};
     return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420");
+}
+
+int compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x, const float* params, const void* packed, void* workspace,
+                              size_t workspace_bytes, uint16_t* y, const ResrYuvDesc* yuv, hipStream_t st) {
+    if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420p10: null argument");
+    const Ends e{YUV420P10, nullptr, nullptr, (const uint8_t*)x, (uint8_t*)y, {}, yuv};
+    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420p10");
 }
 
 int compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,

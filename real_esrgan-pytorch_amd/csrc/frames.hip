@@ -7,6 +7,8 @@
 //   nchw_to_u8     : fp32 [N,3,H,W] -> u8 [N,H,W,3]                (... and whose last one is not: RRDB Generator, the tiler)
 //   compact_tail_yuv420           : compact_tail_u8 with YUV 4:2:0 frames at both of its ends
 //   yuv420_to_rgb, rgb_to_yuv420  : the integer colour conversions on their own, u8 [N,3H/2,W] <-> u8 [N,H,W,3]
+//   frame_head / compact_tail_yuv420p10 : the same two ends for 10-bit 4:2:0 frames, 16-bit words [N,3H/2,W] (yuv420p10le / P010)
+//   yuv420p10_to_nchw, nchw_to_yuv420p10: 10-bit YUV [N,3H/2,W] <-> fp32 [N,3,H,W], one launch each, no RGB frame in between
 //
 // The result is DEFINED as what the float path followed by imgproc.tensor_to_image produces, bit for bit:
 //   in : x = (float)u8 / 255.0f, one IEEE division (numpy's astype(float32) / 255.0), then converted to the model's type exactly
@@ -15,6 +17,8 @@
 //        [0, 255], truncate -- in this order, nothing re-associated (t * 255 + x * 255 is another number).
 // A NaN in v is outside the contract (the float path's astype(uint8) of a NaN is undefined too); here it quantises to 0.
 // The YUV path is DEFINED as rgb_to_yuv420(the u8 path(yuv420_to_rgb(frame))), two integer functions of bytes (include/resr.h).
+// The 10-bit YUV path is the same composition with 1023 levels: the integer functions with 64 / 512 / 1023 for 16 / 128 / 255,
+// x = (float)rgb10 / 1023.0f on the way in and v * 1023.0f, clamp to [0, 1023], truncate on the way out (include/resr.h).
 // Every index that can pass 2^31 is 64-bit.  Vector stores only.
 #include "common.h"
 
@@ -22,14 +26,20 @@ namespace resr {
 
 namespace {
 
-__device__ __forceinline__ float u8_unit(unsigned v) { return (float)v / 255.0f; }
+// TOP: the highest level of a sample, 255 (8 bits) or 1023 (10 bits)
+template <int TOP>
+__device__ __forceinline__ float unit_of(unsigned v) { return (float)v / (float)TOP; }
 
-__device__ __forceinline__ unsigned quantise_u8(float v) {
-    v *= 255.0f;
+template <int TOP>
+__device__ __forceinline__ unsigned quantise(float v) {
+    v *= (float)TOP;
     v = v > 0.f ? v : 0.f;          // (a NaN compares false: 0)
-    v = v < 255.f ? v : 255.f;
+    v = v < (float)TOP ? v : (float)TOP;
     return (unsigned)v;             // truncation, as astype(uint8) of a value in [0, 255]
 }
+
+__device__ __forceinline__ float u8_unit(unsigned v) { return unit_of<255>(v); }
+__device__ __forceinline__ unsigned quantise_u8(float v) { return quantise<255>(v); }
 
 // The output is a flat array of n * hS * wS pixels of 3 bytes; a thread owns 4 consecutive pixels = 12 bytes = three dword
 // stores (y is 4-byte aligned and 12 k is, whatever wS is), a wavefront writes 768 contiguous bytes.  Each pixel decodes its
@@ -92,39 +102,69 @@ __global__ __launch_bounds__(256) void u8_to_nchw_kernel(const uint8_t* __restri
 
 // ---- YUV 4:2:0 (include/resr.h: the integer definition; frames.py holds it once more in numpy, which the tests compare with) ----
 
+// BITS per sample, 8 or 10 (every template below defaults to 8): the word a sample is stored in, the highest level, and the studio
+// offsets 16 / 128, which scale with the depth (64 / 512 at 10 bits).
+template <int BITS> struct Depth { typedef uint8_t word; };
+template <> struct Depth<10> { typedef uint16_t word; };
+template <int BITS> constexpr int kTop = (1 << BITS) - 1;
+template <int BITS> constexpr int kLumaOff = 16 << (BITS - 8);
+template <int BITS> constexpr int kChromaOff = 128 << (BITS - 8);
+
+// NV12 and P010 hold one interleaved CbCr plane, I420 and I420P10 a Cb and a Cr plane
+__device__ __forceinline__ constexpr bool semi_planar(int layout) { return layout == RESR_YUV_NV12 || layout == RESR_YUV_P010; }
+
+// A 10-bit sample sits in the low bits of its 16-bit word (I420P10; the high 6 ignored on the way in, zero on the way out) or in the
+// high bits (P010; the low 6 likewise).  A byte is its sample.
+template <int BITS>
+__device__ __forceinline__ int sample_of(unsigned word, int layout) {
+    if constexpr (BITS == 8) return (int)word;
+    else return (int)(layout == RESR_YUV_P010 ? word >> 6 : word & 1023u);
+}
+
+template <int BITS>
+__device__ __forceinline__ unsigned word_of(unsigned sample, int layout) {
+    if constexpr (BITS == 8) return sample;
+    else return layout == RESR_YUV_P010 ? sample << 6 : sample;
+}
+
 // The three samples of pixel (y, x) of one image of luma size h x w (both even): chroma is replicated over its 2x2 block.
-__device__ __forceinline__ void yuv_load(const uint8_t* __restrict__ img, int h, int w, int layout, int y, int x, int& Y, int& Cb,
-                                         int& Cr) {
+template <int BITS = 8>
+__device__ __forceinline__ void yuv_load(const typename Depth<BITS>::word* __restrict__ img, int h, int w, int layout, int y, int x, int& Y,
+                                         int& Cb, int& Cr) {
     const long luma = (long)h * w;
-    Y = img[(long)y * w + x];
-    if (layout == RESR_YUV_NV12) {
-        const uint8_t* c = img + luma + (long)(y >> 1) * w + (x & ~1);
-        Cb = c[0];
-        Cr = c[1];
+    Y = sample_of<BITS>(img[(long)y * w + x], layout);
+    if (semi_planar(layout)) {
+        const typename Depth<BITS>::word* c = img + luma + (long)(y >> 1) * w + (x & ~1);
+        Cb = sample_of<BITS>(c[0], layout);
+        Cr = sample_of<BITS>(c[1], layout);
     } else {
         const long o = (long)(y >> 1) * (w >> 1) + (x >> 1);
-        Cb = img[luma + o];
-        Cr = img[luma + (luma >> 2) + o];
+        Cb = sample_of<BITS>(img[luma + o], layout);
+        Cr = sample_of<BITS>(img[luma + (luma >> 2) + o], layout);
     }
 }
 
+template <int BITS = 8>
 __device__ __forceinline__ void yuv_to_rgb(const ResrYuvDesc& q, int Y, int Cb, int Cr, unsigned (&rgb)[3]) {
-    const int y = Y - 16, cb = Cb - 128, cr = Cr - 128;
+    const int y = Y - kLumaOff<BITS>, cb = Cb - kChromaOff<BITS>, cr = Cr - kChromaOff<BITS>;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         int v = (q.iq[3 * c] * y + q.iq[3 * c + 1] * cb + q.iq[3 * c + 2] * cr + 32768) >> 16;
         v = v > 0 ? v : 0;
-        rgb[c] = (unsigned)(v < 255 ? v : 255);
+        rgb[c] = (unsigned)(v < kTop<BITS> ? v : kTop<BITS>);
     }
 }
 
+template <int BITS = 8>
 __device__ __forceinline__ unsigned luma_of(const ResrYuvDesc& q, unsigned r, unsigned g, unsigned b) {
-    return (unsigned)((q.fq[0] * (int)r + q.fq[1] * (int)g + q.fq[2] * (int)b + (16 << 16) + 32768) >> 16) & 255u;
+    return (unsigned)((q.fq[0] * (int)r + q.fq[1] * (int)g + q.fq[2] * (int)b + (kLumaOff<BITS> << 16) + 32768) >> 16) & (unsigned)kTop<BITS>;
 }
 
 // row = 1: Cb, row = 2: Cr; s: the sums of a 2x2 block's four pixels
+template <int BITS = 8>
 __device__ __forceinline__ unsigned chroma_of(const ResrYuvDesc& q, int row, const int (&s)[3]) {
-    return (unsigned)((q.fq[3 * row] * s[0] + q.fq[3 * row + 1] * s[1] + q.fq[3 * row + 2] * s[2] + (128 << 18) + (1 << 17)) >> 18) & 255u;
+    return (unsigned)((q.fq[3 * row] * s[0] + q.fq[3 * row + 1] * s[1] + q.fq[3 * row + 2] * s[2] + (kChromaOff<BITS> << 18) + (1 << 17)) >> 18) &
+           (unsigned)kTop<BITS>;
 }
 
 __device__ __forceinline__ unsigned pack4(const unsigned* b) { return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); }
@@ -136,11 +176,14 @@ struct RgbSrc {
 #pragma unroll
         for (int c = 0; c < 3; ++c) rgb[c] = src[p * 3 + c];
     }
+    static __device__ __forceinline__ float unit(unsigned v) { return u8_unit(v); }
 };
 
-// ... a YUV 4:2:0 frame (images of luma size h x w) yields them through the integer conversion.
+// ... a YUV 4:2:0 frame (images of luma size h x w; bytes, or 16-bit words of 10-bit samples: three 16-bit loads and a mask or a
+// shift) yields them through the integer conversion, as levels of 255 or of 1023: `unit` is the division that goes with them.
+template <int BITS>
 struct YuvSrc {
-    const uint8_t* __restrict__ src;
+    const typename Depth<BITS>::word* __restrict__ src;
     int h, w;
     ResrYuvDesc q;
     __device__ __forceinline__ void operator()(long p, unsigned (&rgb)[3]) const {
@@ -148,9 +191,10 @@ struct YuvSrc {
         const long b = p / plane, r = p - b * plane;
         const int yy = (int)(r / w), xx = (int)(r - (long)yy * w);
         int Y, Cb, Cr;
-        yuv_load(src + b * (plane + (plane >> 1)), h, w, q.layout, yy, xx, Y, Cb, Cr);
-        yuv_to_rgb(q, Y, Cb, Cr, rgb);
+        yuv_load<BITS>(src + b * (plane + (plane >> 1)), h, w, q.layout, yy, xx, Y, Cb, Cr);
+        yuv_to_rgb<BITS>(q, Y, Cb, Cr, rgb);
     }
+    static __device__ __forceinline__ float unit(unsigned v) { return unit_of<kTop<BITS>>(v); }
 };
 
 // One thread per 16-byte piece of an output pixel (as nchw_to_nhwc_kernel): only piece 0 holds the three real channels.
@@ -170,7 +214,7 @@ __global__ __launch_bounds__(256) void frame_head_kernel(Src src, T* __restrict_
         T* ol = reinterpret_cast<T*>(&outl);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const float v = u8_unit(rgb[c]);
+            const float v = Src::unit(rgb[c]);
             if constexpr (sizeof(T) == 2) {
                 if (lo_off) split_f16(v, o[c], ol[c]);
                 else o[c] = (T)v;
@@ -200,21 +244,31 @@ __device__ __forceinline__ bool block_2xcols(int n, int rows, int cols, long& b,
     return true;
 }
 
-// compact_tail_u8_kernel with YUV at both ends.  A thread owns 2 rows x 8 columns of the output, i.e. four whole chroma samples;
-// adjacent lanes are adjacent in x.  Per pixel: the residual byte is recomputed from the YUV input (no RGB frame exists here),
-// v = t + u8_unit(rgb_in), quantise_u8(v) unchanged, then the integer RGB -> YUV formula.  wide (the output width is a multiple of 8,
-// y 8-byte aligned: then every plane row, both chroma bases and the per-image stride are aligned as the stores below need): two
-// 8-byte Y stores and a dword each of Cb and Cr (I420) or one 8-byte CbCr store (NV12); a wavefront writes 512 contiguous bytes
-// per Y row.  Every other even width: byte stores, the columns past the right edge skipped (rows always come in whole pairs).
-template <int S, int LAYOUT>
-__global__ __launch_bounds__(256) void compact_tail_yuv420_kernel(const float* __restrict__ t, const uint8_t* __restrict__ x,
-                                                                  uint8_t* __restrict__ y, int n, int h, int w, int wide, ResrYuvDesc q) {
+// Two sample words of a 10-bit layout in one dword, the first in the low half (little-endian words).
+template <int LAYOUT>
+__device__ __forceinline__ unsigned pack2(unsigned a, unsigned b) { return word_of<10>(a, LAYOUT) | (word_of<10>(b, LAYOUT) << 16); }
+
+// compact_tail_u8_kernel with YUV at both ends, of BITS = 8 (bytes; LAYOUT RESR_YUV_I420 / RESR_YUV_NV12) or 10 bits per sample
+// (16-bit words; RESR_YUV_I420P10 / RESR_YUV_P010).  A thread owns 2 rows x 8 columns of the output, i.e. four whole chroma
+// samples; adjacent lanes are adjacent in x.  Per pixel: the residual level is recomputed from the YUV input (no RGB frame exists
+// here), v = t + unit(rgb_in), quantise(v) unchanged (255 or 1023 levels), then the integer RGB -> YUV formula; the sums of the 2x2
+// blocks stay in registers.  wide (the output width WS is a multiple of 8, y aligned to one Y store: then every plane row, both
+// chroma bases and the per-image stride are aligned as the stores below need -- HS is even, so the luma plane is a multiple of 16
+// samples, a chroma row WS / 2 and a chroma plane HS / 2 * WS / 2 are multiples of 4, an image is 3 / 2 luma planes):
+//   8 bits : two 8-byte Y stores and a dword each of Cb and Cr (I420) or one 8-byte CbCr store (NV12); a wavefront writes 512
+//            contiguous bytes per Y row;
+//   10 bits: two 16-byte Y stores and 8 bytes each of Cb and Cr (I420P10) or one 16-byte CbCr store (P010); 1 KiB per Y row.
+// Every other even width: one sample word per store, the columns past the right edge skipped (rows always come in whole pairs).
+template <int S, int LAYOUT, int BITS>
+__device__ __forceinline__ void compact_tail_yuv(const float* __restrict__ t, const typename Depth<BITS>::word* __restrict__ x,
+                                                 typename Depth<BITS>::word* __restrict__ y, int n, int h, int w, int wide, const ResrYuvDesc& q) {
+    typedef typename Depth<BITS>::word word;
     const int HS = h * S, WS = w * S;
     long b;
     int Y0, X0;
     if (!block_2xcols<8>(n, HS, WS, b, Y0, X0)) return;
     const long plane = (long)h * w;
-    const uint8_t* xin = x + b * (plane + (plane >> 1));
+    const word* xin = x + b * (plane + (plane >> 1));
     const float* tb = t + b * 3 * S * S * plane;
     unsigned yb[2][8];
     int sum[4][3];
@@ -233,58 +287,174 @@ __global__ __launch_bounds__(256) void compact_tail_yuv420_kernel(const float* _
                 const int xx = 8 % S == 0 ? X0 / S + k / S : X / S;
                 const int sx = X - xx * S;
                 int Yi, Cb, Cr;
-                yuv_load(xin, h, w, LAYOUT, yy, xx, Yi, Cb, Cr);
+                yuv_load<BITS>(xin, h, w, LAYOUT, yy, xx, Yi, Cb, Cr);
                 unsigned rgb_in[3], o[3];
-                yuv_to_rgb(q, Yi, Cb, Cr, rgb_in);
+                yuv_to_rgb<BITS>(q, Yi, Cb, Cr, rgb_in);
                 const float* tp = tb + (long)(sy * S + sx) * plane + (long)yy * w + xx;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const float v = tp[(long)c * S * S * plane] + u8_unit(rgb_in[c]);
-                    o[c] = quantise_u8(v);
+                    const float v = tp[(long)c * S * S * plane] + unit_of<kTop<BITS>>(rgb_in[c]);
+                    o[c] = quantise<kTop<BITS>>(v);
                     sum[k >> 1][c] += (int)o[c];
                 }
-                yb[r][k] = luma_of(q, o[0], o[1], o[2]);
+                yb[r][k] = luma_of<BITS>(q, o[0], o[1], o[2]);
             }
         }
     }
     unsigned cb[4], cr[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        cb[j] = chroma_of(q, 1, sum[j]);
-        cr[j] = chroma_of(q, 2, sum[j]);
+        cb[j] = chroma_of<BITS>(q, 1, sum[j]);
+        cr[j] = chroma_of<BITS>(q, 2, sum[j]);
     }
     const long luma = (long)HS * WS;
-    uint8_t* yo = y + b * (luma + (luma >> 1));
-    uint8_t* row0 = yo + (long)Y0 * WS + X0;
+    word* yo = y + b * (luma + (luma >> 1));
+    word* row0 = yo + (long)Y0 * WS + X0;
+    word* c0 = semi_planar(LAYOUT) ? yo + luma + (long)(Y0 >> 1) * WS + X0 : yo + luma + (long)(Y0 >> 1) * (WS >> 1) + (X0 >> 1);
     if (wide) {
-        *reinterpret_cast<uint2*>(row0) = make_uint2(pack4(yb[0]), pack4(yb[0] + 4));
-        *reinterpret_cast<uint2*>(row0 + WS) = make_uint2(pack4(yb[1]), pack4(yb[1] + 4));
-        if constexpr (LAYOUT == RESR_YUV_NV12) {
-            *reinterpret_cast<uint2*>(yo + luma + (long)(Y0 >> 1) * WS + X0) =
-                make_uint2(cb[0] | (cr[0] << 8) | (cb[1] << 16) | (cr[1] << 24), cb[2] | (cr[2] << 8) | (cb[3] << 16) | (cr[3] << 24));
+        if constexpr (BITS == 8) {
+            *reinterpret_cast<uint2*>(row0) = make_uint2(pack4(yb[0]), pack4(yb[0] + 4));
+            *reinterpret_cast<uint2*>(row0 + WS) = make_uint2(pack4(yb[1]), pack4(yb[1] + 4));
+            if constexpr (semi_planar(LAYOUT)) {
+                *reinterpret_cast<uint2*>(c0) =
+                    make_uint2(cb[0] | (cr[0] << 8) | (cb[1] << 16) | (cr[1] << 24), cb[2] | (cr[2] << 8) | (cb[3] << 16) | (cr[3] << 24));
+            } else {
+                *reinterpret_cast<unsigned*>(c0) = pack4(cb);
+                *reinterpret_cast<unsigned*>(c0 + (luma >> 2)) = pack4(cr);
+            }
         } else {
-            uint8_t* c0 = yo + luma + (long)(Y0 >> 1) * (WS >> 1) + (X0 >> 1);
-            *reinterpret_cast<unsigned*>(c0) = pack4(cb);
-            *reinterpret_cast<unsigned*>(c0 + (luma >> 2)) = pack4(cr);
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+                *reinterpret_cast<uint4*>(row0 + (long)r * WS) =
+                    make_uint4(pack2<LAYOUT>(yb[r][0], yb[r][1]), pack2<LAYOUT>(yb[r][2], yb[r][3]), pack2<LAYOUT>(yb[r][4], yb[r][5]),
+                               pack2<LAYOUT>(yb[r][6], yb[r][7]));
+            if constexpr (semi_planar(LAYOUT)) {
+                *reinterpret_cast<uint4*>(c0) =
+                    make_uint4(pack2<LAYOUT>(cb[0], cr[0]), pack2<LAYOUT>(cb[1], cr[1]), pack2<LAYOUT>(cb[2], cr[2]), pack2<LAYOUT>(cb[3], cr[3]));
+            } else {
+                *reinterpret_cast<uint2*>(c0) = make_uint2(pack2<LAYOUT>(cb[0], cb[1]), pack2<LAYOUT>(cb[2], cb[3]));
+                *reinterpret_cast<uint2*>(c0 + (luma >> 2)) = make_uint2(pack2<LAYOUT>(cr[0], cr[1]), pack2<LAYOUT>(cr[2], cr[3]));
+            }
         }
     } else {
 #pragma unroll
         for (int k = 0; k < 8; ++k)
             if (X0 + k < WS) {
-                row0[k] = (uint8_t)yb[0][k];
-                row0[WS + k] = (uint8_t)yb[1][k];
+                row0[k] = (word)word_of<BITS>(yb[0][k], LAYOUT);
+                row0[WS + k] = (word)word_of<BITS>(yb[1][k], LAYOUT);
             }
 #pragma unroll
         for (int j = 0; j < 4; ++j)
             if (X0 + 2 * j < WS) {
-                if constexpr (LAYOUT == RESR_YUV_NV12) {
-                    uint8_t* c0 = yo + luma + (long)(Y0 >> 1) * WS + X0 + 2 * j;
-                    c0[0] = (uint8_t)cb[j];
-                    c0[1] = (uint8_t)cr[j];
+                if constexpr (semi_planar(LAYOUT)) {
+                    c0[2 * j] = (word)word_of<BITS>(cb[j], LAYOUT);
+                    c0[2 * j + 1] = (word)word_of<BITS>(cr[j], LAYOUT);
                 } else {
-                    uint8_t* c0 = yo + luma + (long)(Y0 >> 1) * (WS >> 1) + (X0 >> 1) + j;
-                    c0[0] = (uint8_t)cb[j];
-                    c0[luma >> 2] = (uint8_t)cr[j];
+                    c0[j] = (word)word_of<BITS>(cb[j], LAYOUT);
+                    c0[(luma >> 2) + j] = (word)word_of<BITS>(cr[j], LAYOUT);
+                }
+            }
+    }
+}
+
+template <int S, int LAYOUT>
+__global__ __launch_bounds__(256) void compact_tail_yuv420_kernel(const float* __restrict__ t, const uint8_t* __restrict__ x,
+                                                                  uint8_t* __restrict__ y, int n, int h, int w, int wide, ResrYuvDesc q) {
+    compact_tail_yuv<S, LAYOUT, 8>(t, x, y, n, h, w, wide, q);
+}
+
+template <int S, int LAYOUT>
+__global__ __launch_bounds__(256) void compact_tail_yuv420p10_kernel(const float* __restrict__ t, const uint16_t* __restrict__ x,
+                                                                     uint16_t* __restrict__ y, int n, int h, int w, int wide, ResrYuvDesc q) {
+    compact_tail_yuv<S, LAYOUT, 10>(t, x, y, n, h, w, wide, q);
+}
+
+// 10-bit YUV [N,3H/2,W] -> fp32 [N,3,H,W], one thread per pixel as u8_to_nchw_kernel: three 16-bit loads, the integer conversion,
+// / 1023.0f, one coalesced dword store per plane.
+__global__ __launch_bounds__(256) void yuv420p10_to_nchw_kernel(YuvSrc<10> src, float* __restrict__ dst, long total, long plane) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= total) return;
+    const long b = p / plane, r = p - b * plane;
+    unsigned rgb[3];
+    src(p, rgb);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + r] = YuvSrc<10>::unit(rgb[c]);
+}
+
+// fp32 [N,3,H,W] (H, W even) -> 10-bit YUV [N,3H/2,W]: a thread owns 2 rows x 4 columns (two chroma samples), quantises its 8 pixels
+// (v * 1023, clamp, truncate) and applies the integer formula.  wide (w a multiple of 4, src 16-byte and dst 8-byte aligned: then
+// every row of every plane is): a 16-byte load per plane row, an 8-byte store per Y row, a dword each of Cb and Cr (I420P10) or 8
+// bytes of CbCr (P010).  Every other even width moves single floats and words, the columns past the right edge skipped.
+__global__ __launch_bounds__(256) void nchw_to_yuv420p10_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst, int n, int h,
+                                                                int w, int wide, ResrYuvDesc q) {
+    long b;
+    int Y0, X0;
+    if (!block_2xcols<4>(n, h, w, b, Y0, X0)) return;
+    const long plane = (long)h * w;
+    const int L = q.layout;
+    unsigned yb[2][4];
+    int sum[2][3] = {{0, 0, 0}, {0, 0, 0}};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const float* in = src + b * 3 * plane + (long)(Y0 + r) * w + X0;
+        unsigned o[4][3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (wide) {
+                const float4 f = *reinterpret_cast<const float4*>(in + c * plane);
+                v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (X0 + k < w) v[k] = in[c * plane + k];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) o[k][c] = quantise<1023>(v[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            yb[r][k] = luma_of<10>(q, o[k][0], o[k][1], o[k][2]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sum[k >> 1][c] += (int)o[k][c];
+        }
+    }
+    unsigned cb[2], cr[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        cb[j] = chroma_of<10>(q, 1, sum[j]);
+        cr[j] = chroma_of<10>(q, 2, sum[j]);
+    }
+    auto two = [L](unsigned a, unsigned c) { return word_of<10>(a, L) | (word_of<10>(c, L) << 16); };
+    uint16_t* yo = dst + b * (plane + (plane >> 1));
+    uint16_t* row0 = yo + (long)Y0 * w + X0;
+    const bool semi = semi_planar(L);
+    uint16_t* c0 = semi ? yo + plane + (long)(Y0 >> 1) * w + X0 : yo + plane + (long)(Y0 >> 1) * (w >> 1) + (X0 >> 1);
+    if (wide) {
+        *reinterpret_cast<uint2*>(row0) = make_uint2(two(yb[0][0], yb[0][1]), two(yb[0][2], yb[0][3]));
+        *reinterpret_cast<uint2*>(row0 + w) = make_uint2(two(yb[1][0], yb[1][1]), two(yb[1][2], yb[1][3]));
+        if (semi) {
+            *reinterpret_cast<uint2*>(c0) = make_uint2(two(cb[0], cr[0]), two(cb[1], cr[1]));
+        } else {
+            *reinterpret_cast<unsigned*>(c0) = two(cb[0], cb[1]);
+            *reinterpret_cast<unsigned*>(c0 + (plane >> 2)) = two(cr[0], cr[1]);
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (X0 + k < w) {
+                row0[k] = (uint16_t)word_of<10>(yb[0][k], L);
+                row0[w + k] = (uint16_t)word_of<10>(yb[1][k], L);
+            }
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            if (X0 + 2 * j < w) {
+                if (semi) {
+                    c0[2 * j] = (uint16_t)word_of<10>(cb[j], L);
+                    c0[2 * j + 1] = (uint16_t)word_of<10>(cr[j], L);
+                } else {
+                    c0[j] = (uint16_t)word_of<10>(cb[j], L);
+                    c0[(plane >> 2) + j] = (uint16_t)word_of<10>(cr[j], L);
                 }
             }
     }
@@ -402,6 +572,7 @@ __global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const uint8_t* __res
 bool grid_ok(long threads) { return threads > 0 && (threads + 255) / 256 <= 0x7fffffffL; }
 
 bool yuv_ok(const ResrYuvDesc* q) { return q && (q->layout == RESR_YUV_I420 || q->layout == RESR_YUV_NV12); }
+bool yuv10_ok(const ResrYuvDesc* q) { return q && (q->layout == RESR_YUV_I420P10 || q->layout == RESR_YUV_P010); }
 
 template <int S, int LAYOUT>
 void launch_tail_yuv_layout(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int wide, const ResrYuvDesc& q, hipStream_t st) {
@@ -416,6 +587,15 @@ void launch_tail_yuv(const float* t, const uint8_t* x, uint8_t* y, int n, int h,
     else launch_tail_yuv_layout<S, RESR_YUV_I420>(t, x, y, n, h, w, wide, q, st);
 }
 
+template <int S>
+void launch_tail_yuv10(const float* t, const uint16_t* x, uint16_t* y, int n, int h, int w, int wide, const ResrYuvDesc& q, hipStream_t st) {
+    const dim3 grid((unsigned)(((long)n * (h * S / 2) * ((w * S + 7) / 8) + 255) / 256));
+    if (q.layout == RESR_YUV_P010)
+        hipLaunchKernelGGL((compact_tail_yuv420p10_kernel<S, RESR_YUV_P010>), grid, dim3(256), 0, st, t, x, y, n, h, w, wide, q);
+    else
+        hipLaunchKernelGGL((compact_tail_yuv420p10_kernel<S, RESR_YUV_I420P10>), grid, dim3(256), 0, st, t, x, y, n, h, w, wide, q);
+}
+
 template <int S, bool RES>
 void launch_tail(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, hipStream_t st) {
     const long groups = ((long)n * h * S * w * S + 3) / 4;
@@ -425,10 +605,11 @@ void launch_tail(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int
 }  // namespace
 
 // lo_off: the hi -> lo element offset of x_in (RESR_F16X2), as compact_forward passes it to nchw_to_nhwc_dispatch.
-// q: the frames are YUV 4:2:0 [n,3h/2,w]; null: RGB [n,h,w,3].
-int frame_head_dispatch(const uint8_t* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q) {
-    const char* who = q ? "yuv_head" : "u8_head";
-    if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || (q && ((h & 1) || (w & 1) || !yuv_ok(q)))) return fail(RESR_ERR_ARG, "%s: bad argument", who);
+// q: the frames are YUV 4:2:0 [n,3h/2,w], of bytes or (a 10-bit layout) of 16-bit words; null: RGB bytes [n,h,w,3].
+int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q) {
+    const bool ten = yuv10_ok(q);
+    const char* who = ten ? "yuv10_head" : q ? "yuv_head" : "u8_head";
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || (q && ((h & 1) || (w & 1) || !(ten || yuv_ok(q))))) return fail(RESR_ERR_ARG, "%s: bad argument", who);
     const long px = (long)n * h * w;
     const int pieces = dtype != RESR_F32 ? 4 : 8;
     if (!grid_ok(px * pieces)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, px);
@@ -441,9 +622,10 @@ int frame_head_dispatch(const uint8_t* src, void* dst, int n, int h, int w, int 
             hipLaunchKernelGGL((frame_head_kernel<float, decltype(from)>), grid, dim3(256), 0, st, from, (float*)dst, px, 0L);
     };
     prof_before(st);
-    if (q) launch(YuvSrc{src, h, w, *q});
-    else launch(RgbSrc{src});
-    prof_after(st, q ? 31021 : 31020, 0.0, (double)px * ((q ? 1.5 : 3.0) + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
+    if (ten) launch(YuvSrc<10>{(const uint16_t*)src, h, w, *q});
+    else if (q) launch(YuvSrc<8>{(const uint8_t*)src, h, w, *q});
+    else launch(RgbSrc{(const uint8_t*)src});
+    prof_after(st, ten ? 31022 : q ? 31021 : 31020, 0.0, (double)px * ((q ? ten ? 3.0 : 1.5 : 3.0) + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
     RESR_CHECK_LAUNCH("frame_head_kernel");
     return RESR_OK;
 }
@@ -500,6 +682,61 @@ int compact_tail_yuv420(const float* t, const uint8_t* x, uint8_t* y, int n, int
     // per LR pixel: 3 s^2 floats of t, 1.5 bytes of x, 1.5 s^2 bytes out
     prof_after(st, 31040 + s, 0.0, (double)n * h * w * (s * s * 13.5 + 1.5));
     RESR_CHECK_LAUNCH("compact_tail_yuv420_kernel");
+    return RESR_OK;
+}
+
+// ---- 10-bit YUV 4:2:0 ----
+
+// yuv420_forward_check for compact_forward_yuv420p10: the wide stores are 16 bytes, every store at least a 16-bit word.
+int yuv420p10_forward_check(const char* who, int n, int h, int w, int s, const uint16_t* y, const ResrYuvDesc* q) {
+    if (!yuv10_ok(q)) return fail(RESR_ERR_ARG, "%s: the YUV descriptor is null or its layout is neither RESR_YUV_I420P10 nor RESR_YUV_P010", who);
+    if ((h & 1) || (w & 1)) return fail(RESR_ERR_ARG, "%s: a 4:2:0 frame has an even height and width, got %dx%d", who, h, w);
+    if (((size_t)y & ((w * s) % 8 == 0 ? 15 : 1)) != 0)
+        return fail(RESR_ERR_ARG, "%s: y_yuv must be 16-byte aligned at an output width of %d (2-byte at a width that is no multiple of 8)", who, w * s);
+    if (!grid_ok((long)n * (h * s / 2) * ((w * s + 7) / 8))) return fail(RESR_ERR_ARG, "%s: %dx%dx%d beyond the grid", who, n, h * s, w * s);
+    return RESR_OK;
+}
+
+// the frames have passed yuv420p10_forward_check: compact_run has called it
+int compact_tail_yuv420p10(const float* t, const uint16_t* x, uint16_t* y, int n, int h, int w, int s, const ResrYuvDesc* q, hipStream_t st) {
+    const int wide = (w * s) % 8 == 0;
+    prof_before(st);
+    if (!with_scale(s, [&](auto S) { launch_tail_yuv10<S()>(t, x, y, n, h, w, wide, *q, st); })) return fail(RESR_ERR_ARG, "compact_tail_yuv420p10: upscale %d", s);
+    // per LR pixel: 3 s^2 floats of t, 3 bytes of x, 3 s^2 bytes out
+    prof_after(st, 31060 + s, 0.0, (double)n * h * w * (s * s * 15.0 + 3.0));
+    RESR_CHECK_LAUNCH("compact_tail_yuv420p10_kernel");
+    return RESR_OK;
+}
+
+int yuv420p10_to_nchw_dispatch(const uint16_t* src, float* dst, int n, int h, int w, const ResrYuvDesc* q, hipStream_t st) {
+    const char* who = "yuv420p10_to_nchw";
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "%s: bad argument (n=%d h=%d w=%d)", who, n, h, w);
+    if (!yuv10_ok(q)) return fail(RESR_ERR_ARG, "%s: the YUV descriptor is null or its layout is neither RESR_YUV_I420P10 nor RESR_YUV_P010", who);
+    if ((h & 1) || (w & 1)) return fail(RESR_ERR_ARG, "%s: a 4:2:0 frame has an even height and width, got %dx%d", who, h, w);
+    if ((((size_t)src & 1) | ((size_t)dst & 3)) != 0) return fail(RESR_ERR_ARG, "%s: 2-byte aligned frames, a 4-byte aligned float tensor", who);
+    const long plane = (long)h * w, total = plane * n;
+    if (!grid_ok(total)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, total);
+    prof_before(st);
+    hipLaunchKernelGGL(yuv420p10_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, YuvSrc<10>{src, h, w, *q}, dst, total, plane);
+    prof_after(st, 31034, 0.0, (double)total * 15.0);
+    RESR_CHECK_LAUNCH("yuv420p10_to_nchw_kernel");
+    return RESR_OK;
+}
+
+int nchw_to_yuv420p10_dispatch(const float* src, uint16_t* dst, int n, int h, int w, const ResrYuvDesc* q, hipStream_t st) {
+    const char* who = "nchw_to_yuv420p10";
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "%s: bad argument (n=%d h=%d w=%d)", who, n, h, w);
+    if (!yuv10_ok(q)) return fail(RESR_ERR_ARG, "%s: the YUV descriptor is null or its layout is neither RESR_YUV_I420P10 nor RESR_YUV_P010", who);
+    if ((h & 1) || (w & 1)) return fail(RESR_ERR_ARG, "%s: a 4:2:0 frame has an even height and width, got %dx%d", who, h, w);
+    const int wide = w % 4 == 0;
+    if ((((size_t)src & (wide ? 15 : 3)) | ((size_t)dst & (wide ? 7 : 1))) != 0)
+        return fail(RESR_ERR_ARG, "%s: at a width of %d the float tensor must be %d-byte and the frames %d-byte aligned", who, w, wide ? 16 : 4, wide ? 8 : 2);
+    const long threads = (long)n * (h / 2) * ((w + 3) / 4);
+    if (!grid_ok(threads)) return fail(RESR_ERR_ARG, "%s: %dx%dx%d beyond the grid", who, n, h, w);
+    prof_before(st);
+    hipLaunchKernelGGL(nchw_to_yuv420p10_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, src, dst, n, h, w, wide, *q);
+    prof_after(st, 31035, 0.0, (double)n * h * w * 15.0);
+    RESR_CHECK_LAUNCH("nchw_to_yuv420p10_kernel");
     return RESR_OK;
 }
 

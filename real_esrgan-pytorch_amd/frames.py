@@ -42,6 +42,24 @@ replicated on the way in and box-averaged unrounded on the way out): `yuv420_to_
 definition; `yuv420_to_rgb` / `rgb_to_yuv420` are the same functions on the device, one launch each.  A model with a fused entry
 (`SRVGGNetCompact.forward_yuv420`: both conversions inside the compact net's first and last kernel) runs it when the frame fits one
 call; every other case (the RRDB `Generator`, tiled frames, outscale) is the composition of the device launches.
+
+10-BIT YUV 4:2:0 -- what decoders deliver for most HEVC / AV1 material (P010 from hardware, `yuv420p10le` from software), and what an
+encoder needs to keep 1024 levels of a smooth gradient instead of 256.  The geometry is the 8-bit one with a little-endian uint16 word
+per sample: a frame is a uint16 array [3H/2, W] (batches [N,3H/2,W], contiguous; `torch.uint16` on the device), 3 bytes per pixel --
+the rgb24 stream's byte count, not the 8-bit YUV stream's 1.5: this path buys precision and removes the host conversion, it does not
+halve bytes again.  `layout="i420p10"` (rawvideo `yuv420p10le`): planes as "i420", the sample in the low 10 bits (read `word & 1023`,
+written with the high 6 bits zero); `layout="p010"` (`p010le`): planes as "nv12", the sample in the high 10 bits (read `word >> 6`,
+written `sample << 6`).  Every 16-bit word is legal input.  The conversions are the 8-bit ones with 64 / 512 / 1023 in place of
+16 / 128 / 255 (`yuv420p10_tables`, `yuv420p10_to_rgb_np`, `rgb_to_yuv420p10_np`: these ARE the definition), a sample enters the
+model as `rgb10 / 1023.0f` and leaves as q10(v) = trunc(clamp(v * 1023.0f, 0, 1023)), and the path is a composition, bit for bit:
+
+    upscale_yuv420p10(model, f) == rgb_to_yuv420p10_np(q10(float_path(model, yuv420p10_to_rgb_np(f) / 1023.0f)))
+
+with `float_path` the model's forward (or `tiling.super_resolve`) on fp32 NCHW, followed by `resize_with_plan` with `outscale`.  A model
+with a fused entry (`SRVGGNetCompact.forward_yuv420p10`) runs it when the frame fits one call: neither an RGB frame nor an fp32 copy of
+the input exists then.  Every other case is `to_yuv420p10(float_path(from_yuv420p10(f)))`, one launch each way, straight between the
+frames and fp32.  Not provided: mixed depths (8 bits in, 10 out, or the reverse), 12 / 16-bit samples (16 bits would overflow the int32
+accumulators), full range, 4:2:2 / 4:4:4, a fused 10-bit outscale tail.
 """
 from __future__ import annotations
 
@@ -56,9 +74,11 @@ import torch
 from . import _lib, tiling
 
 __all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream", "output_size", "check_outscale", "yuv420_tables", "yuv420_to_rgb_np",
-           "rgb_to_yuv420_np", "yuv420_to_rgb", "rgb_to_yuv420", "upscale_yuv420"]
+           "rgb_to_yuv420_np", "yuv420_to_rgb", "rgb_to_yuv420", "upscale_yuv420", "yuv420p10_tables", "yuv420p10_to_rgb_np",
+           "rgb_to_yuv420p10_np", "from_yuv420p10", "to_yuv420p10", "upscale_yuv420p10"]
 
 YUV_LAYOUTS = {"i420": _lib.YUV_I420, "nv12": _lib.YUV_NV12}
+YUV10_LAYOUTS = {"i420p10": _lib.YUV_I420P10, "p010": _lib.YUV_P010}
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}          # (Kr, Kb); Kg = 1 - Kr - Kb
 
 
@@ -306,14 +326,166 @@ def upscale_yuv420(model, frames: torch.Tensor, layout: str = "i420", matrix: st
     return rgb_to_yuv420(rgb, layout, matrix)
 
 
+# ---- 10-bit YUV 4:2:0 -----------------------------------------------------------------------------------------------------------
+def _yuv10_names(layout: str, matrix: str, what: str) -> None:
+    if layout not in YUV10_LAYOUTS:
+        raise ValueError(f"{what}: layout must be one of {sorted(YUV10_LAYOUTS)}, got {layout!r}")
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"{what}: matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}")
+
+
+def yuv420p10_tables(matrix: str = "bt601", quantised: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """`yuv420_tables` for 10-bit samples: the same (Kr, Kb), the studio constants 876 / 448 / 1023 in place of 219 / 112 / 255
+    (F per 10-bit level; I over Y - 64, Cb - 512, Cr - 512 with a = 1023 / 876, c = 1023 / 896).  (FQ, IQ) int32 [3,3], Q16, or
+    with `quantised=False` the float64 (F, I)."""
+    _yuv_names("i420", matrix, "yuv420p10_tables")
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    f = np.array([[876 * kr, 876 * kg, 876 * kb],
+                  [-448 * kr / (1 - kb), -448 * kg / (1 - kb), 448.0],
+                  [448.0, -448 * kg / (1 - kr), -448 * kb / (1 - kr)]], dtype=np.float64) / 1023.0
+    a, c = 1023.0 / 876.0, 1023.0 / 896.0
+    i = np.array([[a, 0.0, c * 2 * (1 - kr)],
+                  [a, -c * 2 * (1 - kb) * kb / kg, -c * 2 * (1 - kr) * kr / kg],
+                  [a, c * 2 * (1 - kb), 0.0]], dtype=np.float64)
+    if not quantised:
+        return f, i
+    return np.rint(f * 65536).astype(np.int32), np.rint(i * 65536).astype(np.int32)
+
+
+def yuv420p10_to_rgb_np(frames: np.ndarray, layout: str = "i420p10", matrix: str = "bt601") -> np.ndarray:
+    """THE DEFINITION (host, numpy): uint16 [..., 3H/2, W] -> uint16 [..., H, W, 3], levels 0..1023.  A sample is `word & 1023`
+    ("i420p10") or `word >> 6` ("p010"); pixel (y, x) takes Y[y,x], Cb[y//2,x//2], Cr[y//2,x//2]; rgb10[c] = clamp((IQ[c] . (Y - 64,
+    Cb - 512, Cr - 512) + 32768) >> 16, 0, 1023), int32, >> = floor.  Every 16-bit word is legal input."""
+    _yuv10_names(layout, matrix, "yuv420p10_to_rgb_np")
+    frames = np.asarray(frames)
+    if frames.dtype != np.uint16:
+        raise ValueError(f"yuv420p10_to_rgb_np: expected uint16, got {frames.dtype}")
+    h, w = _yuv_geometry(frames.shape, "yuv420p10_to_rgb_np")
+    lead = frames.shape[:-2]
+    v = frames.astype(np.int32)
+    v = v >> 6 if layout == "p010" else v & 1023
+    y = v[..., :h, :] - 64
+    chroma = v[..., h:, :].reshape(lead + (-1,))
+    if layout == "p010":
+        pairs = chroma.reshape(lead + (h // 2, w // 2, 2))
+        cb, cr = pairs[..., 0], pairs[..., 1]
+    else:
+        planes = chroma.reshape(lead + (2, h // 2, w // 2))
+        cb, cr = planes[..., 0, :, :], planes[..., 1, :, :]
+    cb = np.repeat(np.repeat(cb - 512, 2, axis=-2), 2, axis=-1)
+    cr = np.repeat(np.repeat(cr - 512, 2, axis=-2), 2, axis=-1)
+    iq = yuv420p10_tables(matrix)[1]
+    rgb = np.stack([(int(iq[c, 0]) * y + int(iq[c, 1]) * cb + int(iq[c, 2]) * cr + 32768) >> 16 for c in range(3)], axis=-1)
+    return np.clip(rgb, 0, 1023).astype(np.uint16)
+
+
+def rgb_to_yuv420p10_np(rgb: np.ndarray, layout: str = "i420p10", matrix: str = "bt601") -> np.ndarray:
+    """THE DEFINITION (host, numpy): uint16 [..., H, W, 3] of levels 0..1023 (H, W even; a larger value is a ValueError) -> uint16
+    [..., 3H/2, W].  Y = (FQ[0] . rgb10 + (64 << 16) + 32768) >> 16 per pixel; Cb = (FQ[1] . S + (512 << 18) + (1 << 17)) >> 18 per
+    2x2 block, S the sum of its four (R, G, B), Cr likewise with FQ[2].  No clamp is needed: the outputs lie in Y 64..940, Cb / Cr
+    64..960, and the largest accumulator is 251,789,200.  "i420p10" stores the sample (high 6 bits zero), "p010" `sample << 6`."""
+    _yuv10_names(layout, matrix, "rgb_to_yuv420p10_np")
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint16 or rgb.ndim < 3 or rgb.shape[-1] != 3 or rgb.shape[-3] < 2 or rgb.shape[-3] % 2 or rgb.shape[-2] < 2 or rgb.shape[-2] % 2:
+        raise ValueError(f"rgb_to_yuv420p10_np: expected uint16 [..., H, W, 3] with H and W even, got {rgb.dtype} {rgb.shape}")
+    if rgb.size and int(rgb.max()) > 1023:
+        raise ValueError(f"rgb_to_yuv420p10_np: a 10-bit level is at most 1023, got {int(rgb.max())}")
+    lead, (h, w) = rgb.shape[:-3], rgb.shape[-3:-1]
+    fq = yuv420p10_tables(matrix)[0].astype(np.int32)
+    v = rgb.astype(np.int32)
+    y = ((v * fq[0]).sum(-1) + (64 << 16) + 32768) >> 16
+    s = v.reshape(lead + (h // 2, 2, w // 2, 2, 3)).sum(axis=(-4, -2))
+    cb = ((s * fq[1]).sum(-1) + (512 << 18) + (1 << 17)) >> 18
+    cr = ((s * fq[2]).sum(-1) + (512 << 18) + (1 << 17)) >> 18
+    chroma = np.stack([cb, cr], axis=-1) if layout == "p010" else np.stack([cb, cr], axis=-3)
+    out = np.concatenate([y.reshape(lead + (h * w,)), chroma.reshape(lead + (h * w // 2,))], axis=-1)
+    out = out << 6 if layout == "p010" else out
+    return out.reshape(lead + (h * 3 // 2, w)).astype(np.uint16)
+
+
+@functools.lru_cache(maxsize=None)
+def yuv10_desc(layout: str, matrix: str) -> _lib.YuvDesc:
+    """`yuv_desc` for the 10-bit entries: a 10-bit layout and the tables of `yuv420p10_tables`."""
+    _yuv10_names(layout, matrix, "yuv10_desc")
+    fq, iq = yuv420p10_tables(matrix)
+    i9 = _lib.C.c_int32 * 9
+    return _lib.YuvDesc(YUV10_LAYOUTS[layout], i9(*[int(v) for v in fq.reshape(-1)]), i9(*[int(v) for v in iq.reshape(-1)]))
+
+
+def check_yuv420p10(frames: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    """(n, H, W) of a uint16 [N,3H/2,W] device tensor; RuntimeError for anything else."""
+    _lib.require_cuda(frames, what)
+    hw = _yuv_hw(frames.shape) if frames.dtype == torch.uint16 and frames.dim() == 3 and frames.shape[0] >= 1 else None
+    if hw is None:
+        raise RuntimeError(f"{what}: expected a uint16 [N,3H/2,W] tensor with H and W even, got {frames.dtype} {tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise RuntimeError(f"{what}: frames must be contiguous (planes one after the other, as a video decoder leaves them)")
+    return (frames.shape[0],) + hw
+
+
+@torch.no_grad()
+def from_yuv420p10(frames: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601") -> torch.Tensor:
+    """uint16 [N,3H/2,W] -> fp32 [N,3,H,W] on the device, one launch (resr_yuv420p10_to_nchw): `yuv420p10_to_rgb_np(f) / 1023.0f`
+    as NCHW, bit for bit."""
+    desc = yuv10_desc(layout, matrix)
+    n, h, w = check_yuv420p10(frames, "from_yuv420p10")
+    x = torch.empty((n, 3, h, w), dtype=torch.float32, device=frames.device)
+    _lib.check(_lib.lib().resr_yuv420p10_to_nchw(_lib.ptr(frames), _lib.ptr(x), n, h, w, _lib.C.byref(desc), _lib.stream_ptr(frames)),
+               "resr_yuv420p10_to_nchw")
+    return x
+
+
+@torch.no_grad()
+def to_yuv420p10(sr: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601") -> torch.Tensor:
+    """fp32 [N,3,H,W] (H, W even) -> uint16 [N,3H/2,W] on the device, one launch (resr_nchw_to_yuv420p10): `* 1023`, clamp to
+    [0, 1023], truncate, then `rgb_to_yuv420p10_np`, bit for bit."""
+    desc = yuv10_desc(layout, matrix)
+    _lib.require_cuda(sr, "to_yuv420p10")
+    if sr.dtype != torch.float32 or sr.dim() != 4 or sr.shape[1] != 3 or min(sr.shape) < 1:
+        raise RuntimeError(f"to_yuv420p10: expected an fp32 [N,3,H,W] tensor, got {sr.dtype} {tuple(sr.shape)}")
+    n, _, h, w = sr.shape
+    if h % 2 or w % 2:
+        raise RuntimeError(f"to_yuv420p10: a 4:2:0 frame has an even height and width, got {h}x{w}")
+    if not sr.is_contiguous():
+        sr = sr.contiguous()
+    out = torch.empty((n, h * 3 // 2, w), dtype=torch.uint16, device=sr.device)
+    _lib.check(_lib.lib().resr_nchw_to_yuv420p10(_lib.ptr(sr), _lib.ptr(out), n, h, w, _lib.C.byref(desc), _lib.stream_ptr(sr)),
+               "resr_nchw_to_yuv420p10")
+    return out
+
+
+@torch.no_grad()
+def upscale_yuv420p10(model, frames: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601", halo: Optional[int] = None,
+                      outscale: Optional[float] = None, plan=None) -> torch.Tensor:
+    """uint16 [N,3H/2,W] (10-bit 4:2:0) on the model's device -> uint16 [N,3sH/2,sW], same layout: the composition of the module
+    docstring, bit for bit.  The one place that chooses between the fused call and the composition, as `upscale_yuv420` is for 8
+    bits; `halo`, `outscale` and `plan` are `upscale_u8`'s.  With `outscale` the float frame is resized (`resize_with_plan`, fp32
+    out) before it is quantised; an odd out_h or out_w is a ValueError before any launch."""
+    yuv10_desc(layout, matrix)
+    n, h, w = check_yuv420p10(frames, "upscale_yuv420p10")
+    s = model.upscale_factor
+    o = check_outscale(outscale, s, "upscale_yuv420p10")
+    if o is None and hasattr(model, "forward_yuv420p10") and tiling.fits_whole(model, n, h, w):
+        return model.forward_yuv420p10(frames, layout, matrix)
+    if o is not None:
+        yuv420_output_size(h, w, s, o, "upscale_yuv420p10")
+        plan = _resize_plan(h, w, s, o, frames.device, plan)              # ValueError before any launch, as in upscale_u8
+    sr = tiling.super_resolve(model, from_yuv420p10(frames, layout, matrix), halo)
+    if o is not None:
+        from .imgproc import resize_with_plan
+        sr = resize_with_plan(sr, plan)
+    return to_yuv420p10(sr, layout, matrix)
+
+
 class _Slot:
     """One frame in flight: pinned host buffers, the device input, the events that order its three stages."""
 
-    def __init__(self, in_shape: Tuple[int, ...], out_shape: Tuple[int, ...], device) -> None:
-        self.pin_in = torch.empty((1,) + in_shape, dtype=torch.uint8, pin_memory=True)
-        self.pin_out = torch.empty((1,) + out_shape, dtype=torch.uint8, pin_memory=True)
+    def __init__(self, in_shape: Tuple[int, ...], out_shape: Tuple[int, ...], device, dtype=torch.uint8) -> None:
+        self.pin_in = torch.empty((1,) + in_shape, dtype=dtype, pin_memory=True)
+        self.pin_out = torch.empty((1,) + out_shape, dtype=dtype, pin_memory=True)
         self.np_in, self.np_out = self.pin_in.numpy()[0], self.pin_out.numpy()[0]
-        self.dev_in = torch.empty((1,) + in_shape, dtype=torch.uint8, device=device)
+        self.dev_in = torch.empty((1,) + in_shape, dtype=dtype, device=device)
         self.dev_out: Optional[torch.Tensor] = None      # held until the slot's next submit: its download has been waited for by then
         self.uploaded, self.computed, self.downloaded = (torch.cuda.Event() for _ in range(3))
         self.used = False
@@ -338,9 +510,10 @@ class FrameStream:
 
     `pix_fmt`: "rgb24" (default: everything above) or a YUV 4:2:0 layout, "i420" / "nv12" (module docstring), with `matrix`
     "bt601" / "bt709": `submit` takes a [3H/2, W] uint8 ndarray and `result` returns [3 out_h / 2, out_w]; each frame is
-    `upscale_yuv420` of it, the slots are half the bytes, everything else is as above."""
+    `upscale_yuv420` of it, the slots are half the bytes, everything else is as above.  "i420p10" / "p010" (10-bit 4:2:0, module
+    docstring): the same with uint16 ndarrays, each frame `upscale_yuv420p10` of it, the slots 3 bytes per pixel as for rgb24."""
 
-    PIX_FMTS = ("rgb24", "i420", "nv12")
+    PIX_FMTS = ("rgb24", "i420", "nv12", "i420p10", "p010")
 
     def __init__(self, model, depth: int = 2, outscale: Optional[float] = None, pix_fmt: str = "rgb24", matrix: str = "bt601") -> None:
         if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
@@ -349,7 +522,7 @@ class FrameStream:
             raise ValueError(f"FrameStream: pix_fmt must be one of {self.PIX_FMTS}, got {pix_fmt!r}")
         _yuv_names("i420", matrix, "FrameStream")
         self.pix_fmt, self.matrix = pix_fmt, matrix
-        self._fmt = _Rgb24 if pix_fmt == "rgb24" else _Yuv420(pix_fmt, matrix)
+        self._fmt = _Rgb24 if pix_fmt == "rgb24" else _Yuv420p10(pix_fmt, matrix) if pix_fmt in YUV10_LAYOUTS else _Yuv420(pix_fmt, matrix)
         self.outscale = check_outscale(outscale, getattr(model, "upscale_factor", 0), "FrameStream")
         self._plan = None
         param = next(iter(model.parameters()), None)
@@ -375,6 +548,12 @@ class FrameStream:
         if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 2 or _yuv_hw(frame.shape) is None:
             got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
             raise ValueError(f"FrameStream: expected a [3H/2, W] uint8 ndarray with H and W even (a 4:2:0 frame), got {got}")
+
+    @staticmethod
+    def check_frame_yuv420p10(frame) -> None:
+        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint16 or frame.ndim != 2 or _yuv_hw(frame.shape) is None:
+            got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
+            raise ValueError(f"FrameStream: expected a [3H/2, W] uint16 ndarray with H and W even (a 10-bit 4:2:0 frame), got {got}")
 
     def __len__(self) -> int:
         """Results not yet taken."""
@@ -402,7 +581,7 @@ class FrameStream:
         in_shape, out_shape = self._fmt.shapes(h, w, s, self.outscale)     # an odd 4:2:0 result: ValueError before anything is allocated
         self._plan = _resize_plan(h, w, s, self.outscale, self.device)
         with torch.cuda.device(self.device):
-            self._slots = [_Slot(in_shape, out_shape, self.device) for _ in range(self.depth)]
+            self._slots = [_Slot(in_shape, out_shape, self.device, getattr(self._fmt, "dtype", torch.uint8)) for _ in range(self.depth)]
         self._shape, self._next = (h, w), 0
 
     def submit(self, frame: np.ndarray) -> None:
@@ -503,3 +682,16 @@ class _Yuv420:
 
     def upscale(self, model, dev_in, outscale, plan):
         return upscale_yuv420(model, dev_in, self.layout, self.matrix, outscale=outscale, plan=plan)
+
+
+class _Yuv420p10(_Yuv420):
+    """10-bit 4:2:0: the shapes of `_Yuv420`, 16-bit words in the slots."""
+    dtype = torch.uint16
+
+    @staticmethod
+    def size(frame):
+        FrameStream.check_frame_yuv420p10(frame)
+        return _yuv_hw(frame.shape)
+
+    def upscale(self, model, dev_in, outscale, plan):
+        return upscale_yuv420p10(model, dev_in, self.layout, self.matrix, outscale=outscale, plan=plan)

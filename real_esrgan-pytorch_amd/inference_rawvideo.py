@@ -2,7 +2,7 @@
 and an encoder, with no colour conversion on the host and no dependency beyond this package.
 
     python -m real_esrgan_pytorch_amd.inference_rawvideo --input in.yuv --output out.yuv --size 1920x1080 --weights_path g.pth \\
-        [--pix_fmt yuv420p|nv12 --matrix bt601|bt709 --model_type rrdb|compact --num_conv 16 --act_type prelu
+        [--pix_fmt yuv420p|nv12|yuv420p10le|p010le --matrix bt601|bt709 --model_type rrdb|compact --num_conv 16 --act_type prelu
          --precision fast|exact16|strict --depth 2 --outscale 2]
 
     ffmpeg -i in.mp4 -f rawvideo -pix_fmt yuv420p - | \\
@@ -10,9 +10,10 @@ and an encoder, with no colour conversion on the host and no dependency beyond t
             --weights_path realesr-animevideov3.pth | \\
         ffmpeg -f rawvideo -pix_fmt yuv420p -s 7680x4320 -r 24 -i - out.mp4
 
-`--input` / `--output`: a file, or `-` for stdin / stdout (every message then goes to stderr).  Frames of W * H * 3 / 2 bytes are
-read one after the other and streamed through `FrameStream(pix_fmt=...)` with `copy=False`; each written frame is
-`frames.upscale_yuv420` of the frame read, in the same pixel format.  The output size is printed (the encoder has to be told it).
+`--input` / `--output`: a file, or `-` for stdin / stdout (every message then goes to stderr).  Frames of W * H * 3 / 2 bytes (8-bit
+formats) or W * H * 3 bytes (`yuv420p10le` / `p010le`: a little-endian 16-bit word per sample; use the same `-pix_fmt` on both ffmpeg
+pipes) are read one after the other and streamed through `FrameStream(pix_fmt=...)` with `copy=False`; each written frame is
+`frames.upscale_yuv420` (`frames.upscale_yuv420p10`) of the frame read, in the same pixel format.  The output size is printed (the encoder has to be told it).
 A trailing partial frame is an error that names its byte count.  The model is built and the checkpoint loaded as `inference.py`
 does (inference_frames.build_model).
 """
@@ -28,7 +29,8 @@ from . import config
 from .frames import FrameStream, yuv420_output_size
 from .inference_frames import build_model
 
-PIX_FMTS = {"yuv420p": "i420", "nv12": "nv12"}      # the rawvideo names -> frames.py's layouts
+PIX_FMTS = {"yuv420p": "i420", "nv12": "nv12", "yuv420p10le": "i420p10", "p010le": "p010"}      # the rawvideo names -> frames.py's layouts
+WORD = {"i420": np.dtype(np.uint8), "nv12": np.dtype(np.uint8), "i420p10": np.dtype("<u2"), "p010": np.dtype("<u2")}   # a sample's word
 
 
 def parse_size(text: str):
@@ -42,9 +44,15 @@ def parse_size(text: str):
     return w, h
 
 
-def read_frames(stream, w: int, h: int):
-    """The [3H/2, W] uint8 frames of a byte stream; ValueError for a trailing partial frame."""
-    nbytes = w * h * 3 // 2
+def frame_bytes(w: int, h: int, word=np.uint8) -> int:
+    """Bytes of one W x H 4:2:0 frame of `word` samples: W * H * 3 / 2 for bytes, W * H * 3 for 16-bit words."""
+    return w * h * 3 // 2 * np.dtype(word).itemsize
+
+
+def read_frames(stream, w: int, h: int, word=np.uint8):
+    """The [3H/2, W] frames (uint8, or little-endian uint16 for `word=WORD["i420p10"]`) of a byte stream; ValueError for a
+    trailing partial frame."""
+    nbytes = frame_bytes(w, h, word)
     index = 0
     while True:
         buf = bytearray()
@@ -57,13 +65,17 @@ def read_frames(stream, w: int, h: int):
             return
         if len(buf) != nbytes:
             raise ValueError(f"frame {index}: {len(buf)} trailing bytes, a {w}x{h} 4:2:0 frame has {nbytes}")
-        yield np.frombuffer(buf, dtype=np.uint8).reshape(h * 3 // 2, w)
+        yield np.frombuffer(buf, dtype=word).astype(np.dtype(word).newbyteorder("="), copy=False).reshape(h * 3 // 2, w)
         index += 1
 
 
 def main(args) -> int:
     w, h = parse_size(args.size)
-    layout = PIX_FMTS[getattr(args, "pix_fmt", "yuv420p") or "yuv420p"]
+    pix_fmt = getattr(args, "pix_fmt", "yuv420p") or "yuv420p"
+    if pix_fmt not in PIX_FMTS:
+        raise ValueError(f"--pix_fmt must be one of {sorted(PIX_FMTS)}, got {pix_fmt!r}")
+    layout = PIX_FMTS[pix_fmt]
+    word = WORD[layout]
     matrix = getattr(args, "matrix", "bt601") or "bt601"
     log = sys.stderr if args.output == "-" else sys.stdout
     torch.cuda.set_device(config.device)
@@ -71,7 +83,7 @@ def main(args) -> int:
         model = build_model(args)
     outscale = getattr(args, "outscale", None)
     out_h, out_w = yuv420_output_size(h, w, model.upscale_factor, outscale, "inference_rawvideo")
-    print(f"Output size {out_w}x{out_h} ({getattr(args, 'pix_fmt', 'yuv420p') or 'yuv420p'}, {out_w * out_h * 3 // 2} bytes per frame).", file=log)
+    print(f"Output size {out_w}x{out_h} ({pix_fmt}, {frame_bytes(out_w, out_h, word)} bytes per frame).", file=log)
     count = 0
     with contextlib.ExitStack() as stack:
         src = sys.stdin.buffer if args.input == "-" else stack.enter_context(open(args.input, "rb"))
@@ -79,8 +91,8 @@ def main(args) -> int:
         stream = stack.enter_context(FrameStream(model, depth=getattr(args, "depth", 2) or 2, outscale=outscale, pix_fmt=layout,
                                                  matrix=matrix))
         # copy=False: the pinned view is written out before the next result is asked for, i.e. before its slot is submitted to again
-        for sr in stream.map(read_frames(src, w, h), copy=False):
-            dst.write(sr.data)
+        for sr in stream.map(read_frames(src, w, h, word), copy=False):
+            dst.write(sr.astype(word, copy=False).data)     # (little-endian words: a view on every host this runs on)
             count += 1
         dst.flush()
     print(f"{count} frames written to `{args.output}`.", file=log)

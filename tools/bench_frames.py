@@ -29,6 +29,11 @@ way, per case (with `--outscale O` every path below runs at that final factor, t
   B2/2/<fmt>, .../view      FrameStream(depth=2, pix_fmt=<fmt>), copy=True / copy=False
 
     python tools/bench_frames.py --pix_fmt i420 nv12 --out profiles/frames_yuv420_1080p.jsonl
+
+`--pix_fmt i420p10 p010` (10-bit 4:2:0, uint16 frames of 3 bytes per pixel: frames.py, 10-BIT YUV 4:2:0) may be mixed with the 8-bit
+names; its paths are `upscale_yuv420p10` / `FrameStream(pix_fmt=<fmt>)` and its check the composition over the generic launches.
+
+    python tools/bench_frames.py --pix_fmt i420 i420p10 p010 --out profiles/frames_yuv420p10_1080p.jsonl
 """
 import argparse
 import json
@@ -238,11 +243,20 @@ def mode_yuv(args):
     o = args.outscale
     pool, many = frame_pool(args)
     # the same pictures as 4:2:0 frames, so that every path upscales the same content
-    yuv = {fmt: [R.rgb_to_yuv420_np(f, fmt) for f in pool] for fmt in args.pix_fmt}
+    ten = set(R.frames.YUV10_LAYOUTS)
+
+    def to_yuv(f, fmt):      # (10 bits: the same picture at level * 4, so that the two depths upscale the same content)
+        return R.rgb_to_yuv420p10_np(f.astype(np.uint16) * 4, fmt) if fmt in ten else R.rgb_to_yuv420_np(f, fmt)
+
+    def upscale(model, x, fmt):
+        return (R.upscale_yuv420p10 if fmt in ten else R.upscale_yuv420)(model, x, fmt, outscale=o)
+
+    yuv = {fmt: [to_yuv(f, fmt) for f in pool] for fmt in args.pix_fmt}
     many_yuv = {fmt: [yuv[fmt][i % 4] for i in range(args.frames * 4)] for fmt in args.pix_fmt}
     oh, ow = R.output_size(H, W, S, o)
     rgb_bytes = dict(h2d_bytes_per_frame=H * W * 3, d2h_bytes_per_frame=oh * ow * 3)
-    yuv_bytes = dict(h2d_bytes_per_frame=H * W * 3 // 2, d2h_bytes_per_frame=oh * ow * 3 // 2)
+    yuv_bytes = {fmt: dict(h2d_bytes_per_frame=H * W * 3 // 2 * (2 if fmt in ten else 1),
+                           d2h_bytes_per_frame=oh * ow * 3 // 2 * (2 if fmt in ten else 1)) for fmt in args.pix_fmt}
 
     def build(model):
         streams = {"rgb24": R.FrameStream(model, depth=2, outscale=o)}
@@ -254,14 +268,20 @@ def mode_yuv(args):
         for fmt in args.pix_fmt:
             streams[fmt] = R.FrameStream(model, depth=2, outscale=o, pix_fmt=fmt)
             x_yuv[fmt] = torch.from_numpy(yuv[fmt][0])[None].cuda()
-            dev[f"dev/forward_{fmt}"] = lambda fmt=fmt: R.upscale_yuv420(model, x_yuv[fmt], fmt, outscale=o)
-            paths[f"B2/2/{fmt}"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr)), yuv_bytes)
-            paths[f"B2/2/{fmt}/view"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr, copy=False)), yuv_bytes)
+            dev[f"dev/forward_{fmt}"] = lambda fmt=fmt: upscale(model, x_yuv[fmt], fmt)
+            paths[f"B2/2/{fmt}"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr)), yuv_bytes[fmt])
+            paths[f"B2/2/{fmt}/view"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr, copy=False)), yuv_bytes[fmt])
 
         def check():     # the definition, on a timed frame: the stream's result is the composition over the RGB path
             same = {}
             for fmt in args.pix_fmt:
-                want = R.rgb_to_yuv420(R.upscale_u8(model, R.yuv420_to_rgb(x_yuv[fmt], fmt), outscale=o), fmt)[0].cpu().numpy()
+                if fmt in ten:
+                    sr = model(R.from_yuv420p10(x_yuv[fmt], fmt))
+                    if o is not None and o != S:
+                        sr = imgproc.resize_with_plan(sr, imgproc.ResizePlan(H * S, W * S, o / S, sr.device))
+                    want = R.to_yuv420p10(sr, fmt)[0].cpu().numpy()
+                else:
+                    want = R.rgb_to_yuv420(R.upscale_u8(model, R.yuv420_to_rgb(x_yuv[fmt], fmt), outscale=o), fmt)[0].cpu().numpy()
                 same[fmt] = bool(np.array_equal(next(iter(streams[fmt].map(yuv[fmt][:1]))), want))
             return same
 
@@ -287,8 +307,8 @@ def main():
     ap.add_argument("--device-steps", type=int, default=20)
     ap.add_argument("--out", default=None, help="also append the lines to this file")
     ap.add_argument("--outscale", type=float, default=None, help="measure the outscale path at this final factor instead (see above)")
-    ap.add_argument("--pix_fmt", nargs="+", default=None, choices=["i420", "nv12"],
-                    help="measure the YUV 4:2:0 path in these layouts against rgb24 instead (see above; combines with --outscale)")
+    ap.add_argument("--pix_fmt", nargs="+", default=None, choices=["i420", "nv12", "i420p10", "p010"],
+                    help="measure the YUV 4:2:0 path in these layouts (8-bit, or the 10-bit i420p10 / p010) against rgb24 instead (see above; combines with --outscale)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_frames.py measures on the GPU"
     mode = mode_yuv if args.pix_fmt else mode_outscale if args.outscale is not None else mode_x4
