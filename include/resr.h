@@ -473,7 +473,7 @@ int resr_compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x_u8
  * (resr_compact_workspace_bytes: nothing more), same checks and codes.  No RGB frame exists on this path: the tail recomputes the
  * residual from x_yuv, which must stay valid until the call has run.
  * resr_yuv420_to_rgb / resr_rgb_to_yuv420: the generic conversions, one launch each, [N,3H/2,W] <-> uint8 HWC [N,H,W,3], for every
- * case whose ends are not fused (the RRDB generator, tiled frames, outscale).
+ * case whose ends are not fused (the RRDB generator, tiled frames, an outscale the entries under "YUV outscale" do not take).
  * RESR_ERR_ARG before any launch: a null pointer; n, h, w <= 0; an odd h or w (d->h, d->w: then the output's are even too); a
  * layout other than RESR_YUV_*; a destination (for resr_rgb_to_yuv420 the source too) that is not aligned for the wide stores its
  * width selects: 8 bytes for y_yuv when s * d->w is a multiple of 8, 4 bytes for the generic conversions when w is a multiple of 4
@@ -511,7 +511,7 @@ int resr_rgb_to_yuv420(const uint8_t* src_hwc, uint8_t* dst, int32_t n, int32_t 
  * workspace, same checks and codes.  Neither an RGB frame nor an fp32 copy of the input exists: the tail recomputes the residual
  * from x_yuv, which must stay valid until the call has run.
  * resr_yuv420p10_to_nchw / resr_nchw_to_yuv420p10: the generic conversions, one launch each, straight between the frames and fp32
- * [N,3,H,W], for every case whose ends are not fused (the RRDB generator, tiled frames, outscale).
+ * [N,3,H,W], for every case whose ends are not fused (the RRDB generator, tiled frames, an outscale "YUV outscale" does not take).
  * RESR_ERR_ARG before any launch: a null pointer; n, h, w <= 0; an odd h or w; a layout other than these two (the 8-bit entries
  * refuse these two in turn); a misaligned end: y_yuv 16-byte aligned when s * d->w is a multiple of 8; for resr_nchw_to_yuv420p10
  * dst 8-byte and src_f32 16-byte aligned when w is a multiple of 4; 2 bytes per word and 4 per float everywhere else.
@@ -521,6 +521,33 @@ int resr_compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x_y
                                    void* workspace, size_t workspace_bytes, uint16_t* y_yuv, const ResrYuvDesc* yuv, void* stream);
 int resr_yuv420p10_to_nchw(const uint16_t* src, float* dst_f32, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream);
 int resr_nchw_to_yuv420p10(const float* src_f32, uint16_t* dst, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream);
+
+/* YUV outscale: the YUV 4:2:0 ends (8 and 10 bits) on the resized tail of resr_compact_forward_u8_scaled (image_resize.hip).  x_yuv
+ * [N, 3 d->h / 2, d->w] -> y_yuv [N, 3 oh / 2, ow] in the same layout; oh x ow and the tap tables as for resr_compact_forward_u8_scaled
+ * (a resize of the s d->h x s d->w frame).  DEFINED by the compositions above, bit for bit:
+ *   resr_compact_forward_yuv420_scaled(f)    == resr_rgb_to_yuv420(resr_compact_forward_u8_scaled(resr_yuv420_to_rgb(f)))
+ *   resr_compact_forward_yuv420p10_scaled(f) == resr_nchw_to_yuv420p10(resr_image_resize(resr_compact_forward(resr_yuv420p10_to_nchw(f))))
+ * One launch sequence: the YUV head, the convs, one tail.  The tail forms the frame resr_compact_forward would have stored tile by
+ * tile in LDS (t + level / 255.0f or / 1023.0f, the level recomputed from x_yuv: neither an RGB nor an fp32 frame exists), resizes
+ * it, quantises the three sums of every pixel (* 255.0f or * 1023.0f, clamp, truncate) and applies the integer RGB -> YUV formulas to
+ * the levels of each 2x2 block.  Output tiles have an even height and width, so every chroma sample has one owner.
+ * Same descriptor, packed weights and workspace as resr_compact_forward (resr_compact_workspace_bytes: nothing more).
+ * RESR_ERR_ARG before any launch: a null pointer; an odd d->h, d->w, oh or ow; a descriptor of the other bit depth or an unknown
+ * layout; y_yuv not 4-byte aligned (rows leave as dword stores); oh, ow <= 0, taps outside [1, 4096], N > 65535; a scale so small that
+ * the taps of one 2x2 block of outputs do not fit a 64 KB LDS tile.
+ * resr_compact_yuv420_scaled_fits: that last condition as a query with no device work -- 1 when a tile of even height and width
+ * fits for an h x w frame through a model of factor s resized to oh x ow with these taps (bits: 8 or 10), else 0 (bad arguments
+ * included).  A caller asks it to choose between these entries and the composition, which takes any scale the RGB tail takes. */
+int resr_compact_forward_yuv420_scaled(const ResrCompactDesc* d, const uint8_t* x_yuv, const float* params, const void* packed,
+                                       void* workspace, size_t workspace_bytes, uint8_t* y_yuv, int32_t oh, int32_t ow,
+                                       const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
+                                       int32_t taps_x, const ResrYuvDesc* yuv, void* stream);
+int resr_compact_forward_yuv420p10_scaled(const ResrCompactDesc* d, const uint16_t* x_yuv, const float* params, const void* packed,
+                                          void* workspace, size_t workspace_bytes, uint16_t* y_yuv, int32_t oh, int32_t ow,
+                                          const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
+                                          int32_t taps_x, const ResrYuvDesc* yuv, void* stream);
+int resr_compact_yuv420_scaled_fits(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x,
+                                    int32_t bits);
 
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */

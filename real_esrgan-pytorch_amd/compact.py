@@ -15,6 +15,8 @@ forward only as well (frames.py builds the pipelined host-to-host stream on it).
 
 `forward_yuv420` is that sequence for YUV 4:2:0 frames (I420 / NV12, `resr_compact_forward_yuv420`): the integer colour conversions
 of frames.py fused into the same two kernels, so its result equals `rgb_to_yuv420_np(forward_u8(yuv420_to_rgb_np(f)))` bit for bit.
+`forward_yuv420p10` is the same for 10-bit frames.  Both take `outscale` as `forward_u8` does (`resr_compact_forward_yuv420_scaled` /
+`_yuv420p10_scaled`, csrc/image_resize.hip): the resized tail with a YUV 4:2:0 output stage, still one launch sequence.
 """
 from __future__ import annotations
 
@@ -216,38 +218,80 @@ class SRVGGNetCompact(nn.Module):
             y = torch.empty((n, h * s, w * s, self.num_out_ch), dtype=torch.uint8, device=frames.device)
             return self._call("resr_compact_forward_u8", frames, n, h, w, y)
         _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
-        if plan is not None and ((plan.in_h, plan.in_w, plan.scale_factor) != (h * s, w * s, o / s) or plan.idx_y.device != frames.device):
-            raise ValueError(f"SRVGGNetCompact.forward_u8: a plan for {plan.in_h}x{plan.in_w} x {plan.scale_factor}, "
-                             f"the call is {h * s}x{w * s} x {o / s}")
-        plan = _frames._resize_plan(h, w, s, o, frames.device, plan)   # raises before any launch for a frame the rule refuses
-        plan.check("SRVGGNetCompact.forward_u8")
+        plan = self._scaled_plan(frames, h, w, o, plan, "SRVGGNetCompact.forward_u8")
         y = torch.empty((n, plan.out_h, plan.out_w, self.num_out_ch), dtype=torch.uint8, device=frames.device)
         return self._call("resr_compact_forward_u8_scaled", frames, n, h, w, y, *plan.args())
 
-    def forward_yuv420(self, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601") -> torch.Tensor:
+    def _scaled_plan(self, frames: torch.Tensor, h: int, w: int, o: float, plan, what: str):
+        """The checked `imgproc.ResizePlan` of an outscale call on h x w frames: the caller's `plan` when it is one for this call,
+        else a new one.  Raises before any launch (a plan for another size, a frame the reference's rule refuses)."""
+        from . import frames as _frames
+        s = self.upscale
+        if plan is not None and ((plan.in_h, plan.in_w, plan.scale_factor) != (h * s, w * s, o / s) or plan.idx_y.device != frames.device):
+            raise ValueError(f"{what}: a plan for {plan.in_h}x{plan.in_w} x {plan.scale_factor}, the call is {h * s}x{w * s} x {o / s}")
+        plan = _frames._resize_plan(h, w, s, o, frames.device, plan)
+        plan.check(what)
+        return plan
+
+    def _forward_yuv_scaled(self, entry: str, frames: torch.Tensor, n: int, h: int, w: int, o: float, plan, ydesc, what: str) -> torch.Tensor:
+        """The outscale call of `forward_yuv420` / `forward_yuv420p10` once the frames are checked (the result has their dtype)."""
+        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
+        plan = self._scaled_plan(frames, h, w, o, plan, what)
+        y = torch.empty((n, plan.out_h * 3 // 2, plan.out_w), dtype=frames.dtype, device=frames.device)
+        return self._call(entry, frames, n, h, w, y, *plan.args(), C.byref(ydesc))
+
+    def _yuv_outscale(self, frames: torch.Tensor, outscale, what: str) -> Optional[float]:
+        """`outscale` of a YUV call, checked as `forward_u8` checks it, and the 4:2:0 rule of its result -- an odd height or width is
+        a ValueError -- before the device is looked at."""
+        from . import frames as _frames
+        o = _frames.check_outscale(outscale, self.upscale, what)
+        hw = _frames._yuv_hw(frames.shape) if o is not None and isinstance(frames, torch.Tensor) else None
+        if hw is not None:
+            _frames.yuv420_output_size(hw[0], hw[1], self.upscale, o, what)
+        return o
+
+    def forward_yuv420(self, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601", outscale: Optional[float] = None,
+                       plan=None) -> torch.Tensor:
         """frames uint8 [N,3H/2,W] (YUV 4:2:0, H and W even; `layout` "i420" or "nv12", `matrix` "bt601" or "bt709": frames.py) on
         the model's device, contiguous -> uint8 [N,3sH/2,sW] in the same layout: bit for bit
         `frames.rgb_to_yuv420_np(self.forward_u8(frames.yuv420_to_rgb_np(f)))`.  `resr_compact_forward_yuv420`: the launch sequence
         of `forward_u8` with the two integer colour conversions inside its first and last kernel -- no RGB frame exists on the
-        device, and half the bytes enter and leave.  Same guard, packing and workspace caches as `forward`."""
+        device, and half the bytes enter and leave.  Same guard, packing and workspace caches as `forward`.
+
+        `outscale`, `plan`: as `forward_u8`'s -> uint8 [N, 3 out_h / 2, out_w] for `frames.output_size(H, W, s, outscale)`, which
+        must be even both ways (ValueError) -- `resr_compact_forward_yuv420_scaled`: bit for bit
+        `rgb_to_yuv420_np(self.forward_u8(yuv420_to_rgb_np(f), outscale=outscale))`, still with no RGB frame on the device.  A scale
+        so small that no even tile fits the kernel's LDS is an error here; `frames.upscale_yuv420` asks first and composes."""
         from . import frames as _frames
+        o = self._yuv_outscale(frames, outscale, "SRVGGNetCompact.forward_yuv420")
         ydesc = _frames.yuv_desc(layout, matrix)
         self._guard()
         n, h, w = _frames.check_yuv420(frames, "SRVGGNetCompact.forward_yuv420")
+        if o is not None:
+            return self._forward_yuv_scaled("resr_compact_forward_yuv420_scaled", frames, n, h, w, o, plan, ydesc, "SRVGGNetCompact.forward_yuv420")
         s = self.upscale
         y = torch.empty((n, h * s * 3 // 2, w * s), dtype=torch.uint8, device=frames.device)
         return self._call("resr_compact_forward_yuv420", frames, n, h, w, y, C.byref(ydesc))
 
-    def forward_yuv420p10(self, frames: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601") -> torch.Tensor:
+    def forward_yuv420p10(self, frames: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601", outscale: Optional[float] = None,
+                          plan=None) -> torch.Tensor:
         """frames uint16 [N,3H/2,W] (10-bit YUV 4:2:0, H and W even; `layout` "i420p10" or "p010", `matrix` "bt601" or "bt709":
         frames.py) on the model's device, contiguous -> uint16 [N,3sH/2,sW] in the same layout: bit for bit
         `frames.rgb_to_yuv420p10_np(q10(self(frames.yuv420p10_to_rgb_np(f) / 1023)))`.  `resr_compact_forward_yuv420p10`: the launch
         sequence of `forward_yuv420` with 1023 levels at both ends -- neither an RGB frame nor an fp32 copy of the input exists on
-        the device.  Same guard, packing and workspace caches as `forward`."""
+        the device.  Same guard, packing and workspace caches as `forward`.
+
+        `outscale`, `plan`: as `forward_yuv420`'s -> uint16 [N, 3 out_h / 2, out_w] -- `resr_compact_forward_yuv420p10_scaled`: bit for
+        bit `rgb_to_yuv420p10_np(q10(resize_with_plan(self(yuv420p10_to_rgb_np(f) / 1023), plan)))`; the fp32 frames of that
+        composition exist as LDS tiles only."""
         from . import frames as _frames
+        o = self._yuv_outscale(frames, outscale, "SRVGGNetCompact.forward_yuv420p10")
         ydesc = _frames.yuv10_desc(layout, matrix)
         self._guard()
         n, h, w = _frames.check_yuv420p10(frames, "SRVGGNetCompact.forward_yuv420p10")
+        if o is not None:
+            return self._forward_yuv_scaled("resr_compact_forward_yuv420p10_scaled", frames, n, h, w, o, plan, ydesc,
+                                            "SRVGGNetCompact.forward_yuv420p10")
         s = self.upscale
         y = torch.empty((n, h * s * 3 // 2, w * s), dtype=torch.uint16, device=frames.device)
         return self._call("resr_compact_forward_yuv420p10", frames, n, h, w, y, C.byref(ydesc))

@@ -105,6 +105,11 @@ int compact_forward(const ResrCompactDesc*, const float*, const float*, const vo
 int compact_forward_u8(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, hipStream_t);
 int compact_forward_u8_scaled(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, int, int,
                               const int32_t*, const float*, int, const int32_t*, const float*, int, hipStream_t);
+int compact_forward_yuv420_scaled(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, int, int,
+                                  const int32_t*, const float*, int, const int32_t*, const float*, int, const ResrYuvDesc*, hipStream_t);
+int compact_forward_yuv420p10_scaled(const ResrCompactDesc*, const uint16_t*, const float*, const void*, void*, size_t, uint16_t*, int, int,
+                                     const int32_t*, const float*, int, const int32_t*, const float*, int, const ResrYuvDesc*, hipStream_t);
+int compact_yuv420_scaled_fits(int, int, int, int, int, int, int, int);
 int image_resize_dispatch(const float*, void*, int, int, int, int, int, int, const int32_t*, const float*, int, const int32_t*,
                           const float*, int, int, hipStream_t);
 int compact_forward_yuv420(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, const ResrYuvDesc*,
@@ -347,6 +352,28 @@ int resr_yuv420p10_to_nchw(const uint16_t* src, float* dst_f32, int32_t n, int32
 int resr_nchw_to_yuv420p10(const float* src_f32, uint16_t* dst, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return nchw_to_yuv420p10_dispatch(src_f32, dst, n, h, w, yuv, (hipStream_t)stream);
+}
+
+int resr_compact_forward_yuv420_scaled(const ResrCompactDesc* d, const uint8_t* x_yuv, const float* params, const void* packed,
+                                       void* workspace, size_t workspace_bytes, uint8_t* y_yuv, int32_t oh, int32_t ow,
+                                       const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
+                                       int32_t taps_x, const ResrYuvDesc* yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_yuv420_scaled(d, x_yuv, params, packed, workspace, workspace_bytes, y_yuv, oh, ow, idx_y, w_y, taps_y, idx_x,
+                                         w_x, taps_x, yuv, (hipStream_t)stream);
+}
+
+int resr_compact_forward_yuv420p10_scaled(const ResrCompactDesc* d, const uint16_t* x_yuv, const float* params, const void* packed,
+                                          void* workspace, size_t workspace_bytes, uint16_t* y_yuv, int32_t oh, int32_t ow,
+                                          const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
+                                          int32_t taps_x, const ResrYuvDesc* yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_yuv420p10_scaled(d, x_yuv, params, packed, workspace, workspace_bytes, y_yuv, oh, ow, idx_y, w_y, taps_y, idx_x,
+                                            w_x, taps_x, yuv, (hipStream_t)stream);
+}
+
+int resr_compact_yuv420_scaled_fits(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x, int32_t bits) {
+    return compact_yuv420_scaled_fits(h, w, s, oh, ow, taps_y, taps_x, bits);
 }
 
 size_t resr_discriminator_param_count(void) { return discriminator_param_count(); }

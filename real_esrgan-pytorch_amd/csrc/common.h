@@ -111,5 +111,8 @@ struct ResizeGeom {
     int rh, rw, pitch;    // capacity of the staged region, LDS row pitch (floats)
     int cgroups;          // ceil(c / 3)
 };
+// ... and what it stores: fp32 NCHW, uint8 HWC, or a YUV 4:2:0 frame of 8- or 10-bit samples (the latter two: even tiles only, and
+// a staging buffer of levels as wide as the sample's word)
+enum ResizeOut { RESIZE_F32 = 0, RESIZE_U8 = 1, RESIZE_YUV8 = 2, RESIZE_YUV10 = 3 };
 
 }  // namespace resr

@@ -14,7 +14,8 @@
 //   compact_forward_u8_scaled ("outscale") image_resize.hip's fused tail in place of the u8 tail: the HR frame is formed tile by
 //                             tile in LDS and only the resized uint8 frame [N,oh,ow,3] is written;
 //   compact_forward_yuv420    YUV 4:2:0 frames [N,3H/2,W]: frames.hip's head reading YUV, and its YUV tail;
-//   compact_forward_yuv420p10 the same for 10-bit frames of 16-bit words (yuv420p10le / P010): 1023 levels at both ends.
+//   compact_forward_yuv420p10 the same for 10-bit frames of 16-bit words (yuv420p10le / P010): 1023 levels at both ends;
+//   compact_forward_yuv420_scaled / _yuv420p10_scaled  the YUV head and image_resize.hip's resized tail with a YUV 4:2:0 output stage.
 #include <vector>
 
 #include "common.h"
@@ -31,10 +32,12 @@ int yuv420_forward_check(const char*, int, int, int, int, const uint8_t*, const 
 int compact_tail_yuv420(const float*, const uint8_t*, uint8_t*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
 int yuv420p10_forward_check(const char*, int, int, int, int, const uint16_t*, const ResrYuvDesc*);
 int compact_tail_yuv420p10(const float*, const uint16_t*, uint16_t*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
-int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, bool,
+int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, int,
                 const void*, ResizeGeom*);                                                                      // image_resize.hip
 int compact_tail_u8_scaled(const float*, const uint8_t*, uint8_t*, int, int, int, int, const int32_t*, const float*, const int32_t*,
                            const float*, const ResizeGeom*, hipStream_t);
+int compact_tail_yuv420_scaled(const float*, const void*, void*, int, int, int, int, int, const int32_t*, const float*, const int32_t*,
+                               const float*, const ResrYuvDesc*, const ResizeGeom*, hipStream_t);
 
 namespace {
 
@@ -189,6 +192,8 @@ enum EndKind {
     U8_HWC_SCALED,   // ... -> y [N,oh,ow,3]: the resized tail of image_resize.hip (sc)
     YUV420,          // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames: the colour conversions (yuv) fused into the same two kernels
     YUV420P10,       // ... of 16-bit words holding 10-bit samples (x_u8 / y_u8 point at uint16_t)
+    YUV420_SCALED,     // YUV420 -> y [N,3oh/2,ow]: the resized tail with a YUV 4:2:0 output stage (sc and yuv)
+    YUV420P10_SCALED,  // YUV420P10 likewise
 };
 
 struct Ends {
@@ -197,11 +202,11 @@ struct Ends {
     float* y_f32;
     const uint8_t* x_u8;     // every other kind
     uint8_t* y_u8;
-    ScaledTail sc;           // U8_HWC_SCALED
-    const ResrYuvDesc* yuv;  // YUV420, YUV420P10, else null
+    ScaledTail sc;           // U8_HWC_SCALED, YUV420_SCALED, YUV420P10_SCALED
+    const ResrYuvDesc* yuv;  // every YUV kind, else null
 };
 
-// Everything a call can be refused for after its descriptor, before the first launch.  U8_HWC_SCALED: fills geom.
+// Everything a call can be refused for after its descriptor, before the first launch.  The scaled kinds: fills geom.
 int check_ends(const CPlan& p, const Ends& e, const float* params, const void* packed, const void* workspace, size_t workspace_bytes,
                const char* who, ResizeGeom* geom) {
     const ResrCompactDesc& d = p.d;
@@ -215,10 +220,19 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
             if (((size_t)e.y_u8 & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
             if (e.kind == U8_HWC_SCALED)
                 rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y,
-                                 e.sc.idx_x, e.sc.w_x, e.sc.taps_x, true, e.y_u8, geom);
+                                 e.sc.idx_x, e.sc.w_x, e.sc.taps_x, RESIZE_U8, e.y_u8, geom);
             break;
         case YUV420: rc = yuv420_forward_check(who, d.n, d.h, d.w, d.upscale, e.y_u8, e.yuv); break;
         case YUV420P10: rc = yuv420p10_forward_check(who, d.n, d.h, d.w, d.upscale, (const uint16_t*)e.y_u8, e.yuv); break;
+        case YUV420_SCALED:
+        case YUV420P10_SCALED:
+            // the descriptor and the LR frame (the output pointer's rule is the plan's: nullptr passes the unscaled tail's), then the plan
+            rc = e.kind == YUV420_SCALED ? yuv420_forward_check(who, d.n, d.h, d.w, d.upscale, nullptr, e.yuv)
+                                         : yuv420p10_forward_check(who, d.n, d.h, d.w, d.upscale, nullptr, e.yuv);
+            if (!rc)
+                rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y,
+                                 e.sc.idx_x, e.sc.w_x, e.sc.taps_x, e.kind == YUV420_SCALED ? RESIZE_YUV8 : RESIZE_YUV10, e.y_u8, geom);
+            break;
     }
     if (rc) return rc;
     if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
@@ -289,6 +303,10 @@ int compact_run(const ResrCompactDesc* d, const Ends& e, const float* params, co
             return compact_tail_u8_scaled(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, &geom, st);
         case YUV420: return compact_tail_yuv420(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.yuv, st);
         case YUV420P10: return compact_tail_yuv420p10(t, (const uint16_t*)e.x_u8, (uint16_t*)e.y_u8, N, H, W, d->upscale, e.yuv, st);
+        case YUV420_SCALED:
+        case YUV420P10_SCALED:
+            return compact_tail_yuv420_scaled(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.kind == YUV420_SCALED ? 8 : 10, e.sc.idx_y, e.sc.w_y,
+                                              e.sc.idx_x, e.sc.w_x, e.yuv, &geom, st);
     }
     return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
 }
@@ -319,6 +337,22 @@ int compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x, const
     if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420p10: null argument");
     const Ends e{YUV420P10, nullptr, nullptr, (const uint8_t*)x, (uint8_t*)y, {}, yuv};
     return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420p10");
+}
+
+int compact_forward_yuv420_scaled(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
+                                  size_t workspace_bytes, uint8_t* y, int oh, int ow, const int32_t* idx_y, const float* w_y, int taps_y,
+                                  const int32_t* idx_x, const float* w_x, int taps_x, const ResrYuvDesc* yuv, hipStream_t st) {
+    if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420_scaled: null argument");
+    const Ends e{YUV420_SCALED, nullptr, nullptr, x, y, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv};
+    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420_scaled");
+}
+
+int compact_forward_yuv420p10_scaled(const ResrCompactDesc* d, const uint16_t* x, const float* params, const void* packed, void* workspace,
+                                     size_t workspace_bytes, uint16_t* y, int oh, int ow, const int32_t* idx_y, const float* w_y,
+                                     int taps_y, const int32_t* idx_x, const float* w_x, int taps_x, const ResrYuvDesc* yuv, hipStream_t st) {
+    if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420p10_scaled: null argument");
+    const Ends e{YUV420P10_SCALED, nullptr, nullptr, (const uint8_t*)x, (uint8_t*)y, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv};
+    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420p10_scaled");
 }
 
 int compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,

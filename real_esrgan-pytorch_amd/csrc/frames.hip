@@ -21,22 +21,11 @@
 // x = (float)rgb10 / 1023.0f on the way in and v * 1023.0f, clamp to [0, 1023], truncate on the way out (include/resr.h).
 // Every index that can pass 2^31 is 64-bit.  Vector stores only.
 #include "common.h"
+#include "yuv.h"
 
 namespace resr {
 
 namespace {
-
-// TOP: the highest level of a sample, 255 (8 bits) or 1023 (10 bits)
-template <int TOP>
-__device__ __forceinline__ float unit_of(unsigned v) { return (float)v / (float)TOP; }
-
-template <int TOP>
-__device__ __forceinline__ unsigned quantise(float v) {
-    v *= (float)TOP;
-    v = v > 0.f ? v : 0.f;          // (a NaN compares false: 0)
-    v = v < (float)TOP ? v : (float)TOP;
-    return (unsigned)v;             // truncation, as astype(uint8) of a value in [0, 255]
-}
 
 __device__ __forceinline__ float u8_unit(unsigned v) { return unit_of<255>(v); }
 __device__ __forceinline__ unsigned quantise_u8(float v) { return quantise<255>(v); }
@@ -102,71 +91,7 @@ __global__ __launch_bounds__(256) void u8_to_nchw_kernel(const uint8_t* __restri
 
 // ---- YUV 4:2:0 (include/resr.h: the integer definition; frames.py holds it once more in numpy, which the tests compare with) ----
 
-// BITS per sample, 8 or 10 (every template below defaults to 8): the word a sample is stored in, the highest level, and the studio
-// offsets 16 / 128, which scale with the depth (64 / 512 at 10 bits).
-template <int BITS> struct Depth { typedef uint8_t word; };
-template <> struct Depth<10> { typedef uint16_t word; };
-template <int BITS> constexpr int kTop = (1 << BITS) - 1;
-template <int BITS> constexpr int kLumaOff = 16 << (BITS - 8);
-template <int BITS> constexpr int kChromaOff = 128 << (BITS - 8);
-
-// NV12 and P010 hold one interleaved CbCr plane, I420 and I420P10 a Cb and a Cr plane
-__device__ __forceinline__ constexpr bool semi_planar(int layout) { return layout == RESR_YUV_NV12 || layout == RESR_YUV_P010; }
-
-// A 10-bit sample sits in the low bits of its 16-bit word (I420P10; the high 6 ignored on the way in, zero on the way out) or in the
-// high bits (P010; the low 6 likewise).  A byte is its sample.
-template <int BITS>
-__device__ __forceinline__ int sample_of(unsigned word, int layout) {
-    if constexpr (BITS == 8) return (int)word;
-    else return (int)(layout == RESR_YUV_P010 ? word >> 6 : word & 1023u);
-}
-
-template <int BITS>
-__device__ __forceinline__ unsigned word_of(unsigned sample, int layout) {
-    if constexpr (BITS == 8) return sample;
-    else return layout == RESR_YUV_P010 ? sample << 6 : sample;
-}
-
-// The three samples of pixel (y, x) of one image of luma size h x w (both even): chroma is replicated over its 2x2 block.
-template <int BITS = 8>
-__device__ __forceinline__ void yuv_load(const typename Depth<BITS>::word* __restrict__ img, int h, int w, int layout, int y, int x, int& Y,
-                                         int& Cb, int& Cr) {
-    const long luma = (long)h * w;
-    Y = sample_of<BITS>(img[(long)y * w + x], layout);
-    if (semi_planar(layout)) {
-        const typename Depth<BITS>::word* c = img + luma + (long)(y >> 1) * w + (x & ~1);
-        Cb = sample_of<BITS>(c[0], layout);
-        Cr = sample_of<BITS>(c[1], layout);
-    } else {
-        const long o = (long)(y >> 1) * (w >> 1) + (x >> 1);
-        Cb = sample_of<BITS>(img[luma + o], layout);
-        Cr = sample_of<BITS>(img[luma + (luma >> 2) + o], layout);
-    }
-}
-
-template <int BITS = 8>
-__device__ __forceinline__ void yuv_to_rgb(const ResrYuvDesc& q, int Y, int Cb, int Cr, unsigned (&rgb)[3]) {
-    const int y = Y - kLumaOff<BITS>, cb = Cb - kChromaOff<BITS>, cr = Cr - kChromaOff<BITS>;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        int v = (q.iq[3 * c] * y + q.iq[3 * c + 1] * cb + q.iq[3 * c + 2] * cr + 32768) >> 16;
-        v = v > 0 ? v : 0;
-        rgb[c] = (unsigned)(v < kTop<BITS> ? v : kTop<BITS>);
-    }
-}
-
-template <int BITS = 8>
-__device__ __forceinline__ unsigned luma_of(const ResrYuvDesc& q, unsigned r, unsigned g, unsigned b) {
-    return (unsigned)((q.fq[0] * (int)r + q.fq[1] * (int)g + q.fq[2] * (int)b + (kLumaOff<BITS> << 16) + 32768) >> 16) & (unsigned)kTop<BITS>;
-}
-
-// row = 1: Cb, row = 2: Cr; s: the sums of a 2x2 block's four pixels
-template <int BITS = 8>
-__device__ __forceinline__ unsigned chroma_of(const ResrYuvDesc& q, int row, const int (&s)[3]) {
-    return (unsigned)((q.fq[3 * row] * s[0] + q.fq[3 * row + 1] * s[1] + q.fq[3 * row + 2] * s[2] + (kChromaOff<BITS> << 18) + (1 << 17)) >> 18) &
-           (unsigned)kTop<BITS>;
-}
-
+// (the integer conversions themselves: yuv.h, shared with the outscale tail of image_resize.hip)
 __device__ __forceinline__ unsigned pack4(const unsigned* b) { return b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24); }
 
 // Where frame_head_kernel takes the three RGB bytes of pixel p from: an RGB frame holds them ...

@@ -28,9 +28,23 @@
 // A table entry outside the region bound (tables not built by the rule above) is clamped into it: never an access out of bounds.
 // u8 rows leave as dword stores where the address is 4-byte aligned and byte stores at the row ends; every index that can pass
 // 2^31 is 64-bit.  Vector stores only.
+//
+// YUV OUTSCALE.  The same tile with YUV 4:2:0 frames at both ends, 8 bits (I420 / NV12) or 10 (I420P10 / P010), the tail of
+// resr_compact_forward_yuv420_scaled / _yuv420p10_scaled.  The staged value is t + unit(rgb_in), rgb_in the integer conversion of the
+// YUV input pixel (yuv.h: what compact_tail_yuv of frames.hip adds); after the W pass the three sums of a pixel are quantised to
+// levels (255 or 1023) and staged in LDS as bytes or 16-bit words; after a barrier every Y row and every chroma row of the tile is
+// written by the row writer of the u8 stage (dwords where the address is 4-byte aligned, single words at the row ends), each word
+// formed on the fly from the staged levels: luma_of per pixel, chroma_of on the unrounded sum of a 2x2 block's four levels.  A
+// thread owns a dword of an output row, not a block: adjacent lanes read adjacent staged pixels (a stride of 3 or 6 bytes per
+// sample, odd in dwords: no bank conflict on the Y rows, 2-way on the chroma rows, whose lanes are two pixels apart) and write
+// adjacent dwords; a block's levels are read once for Y and once per chroma plane, a few LDS reads against the 3 * taps of the W
+// pass.  Tiles have an even height and width (resize_plan skips the odd entries of its list), so tile origins are even, the edge
+// tile of an even output is even, and every chroma sample belongs to one workgroup.  The results are the compositions of
+// include/resr.h bit for bit: the sums are those of the two stages above, the integer functions those of frames.hip.
 #include <limits.h>
 
 #include "common.h"
+#include "yuv.h"
 
 namespace resr {
 
@@ -49,8 +63,19 @@ __device__ __forceinline__ unsigned quantise_u8(float v) {   // frames.hip's
     return (unsigned)v;
 }
 
+// What resize_tile stores: fp32 [N,C,oh,ow], u8 [N,oh,ow,3], or a YUV 4:2:0 frame [N,3oh/2,ow] of BITS-bit samples in LAYOUT.
+struct OutF32 { static constexpr int kind = RESIZE_F32; };
+struct OutU8 { static constexpr int kind = RESIZE_U8; };
+template <int BITS, int LAYOUT>
+struct OutYuv {
+    static constexpr int kind = BITS == 8 ? RESIZE_YUV8 : RESIZE_YUV10;
+    static constexpr int bits = BITS, layout = LAYOUT;
+    const ResrYuvDesc* q;
+};
+
 // fp32 [N,C,H,W]
 struct PlanarSrc {
+    static constexpr bool kTriple = false;
     const float* x;
     int c, h, w;
     __device__ __forceinline__ float load(long b, int ch, int Y, int X) const {
@@ -61,6 +86,7 @@ struct PlanarSrc {
 // the compact net's last conv t [N,3S^2,h,w] + its u8 input frame [N,h,w,3]: pixel-shuffle + residual of HR pixel (Y, X)
 template <int S>
 struct ShuffleSrc {
+    static constexpr bool kTriple = false;
     const float* t;
     const uint8_t* x;
     int h, w;             // LR
@@ -72,9 +98,53 @@ struct ShuffleSrc {
     }
 };
 
-// The whole tile: region bounds, staging, both passes, quantisation and stores.  y: fp32 [N,C,oh,ow] or u8 [N,oh,ow,3] (U8).
-template <typename Src, bool U8>
-__device__ __forceinline__ void resize_tile(const Src& src, void* __restrict__ y, const int32_t* __restrict__ idx_y,
+// ... + its YUV 4:2:0 input frames [N,3h/2,w] of BITS-bit samples: the residual level of an LR pixel is the integer conversion of
+// its three samples, so the three channels of HR pixel (Y, X) come together (kTriple: load3 in place of load)
+template <int S, int BITS, int LAYOUT>
+struct YuvShuffleSrc {
+    static constexpr bool kTriple = true;
+    const float* t;
+    const typename Depth<BITS>::word* x;
+    int h, w;             // LR
+    ResrYuvDesc q;
+    __device__ __forceinline__ void load3(long b, int Y, int X, float (&v)[3]) const {
+        const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
+        const long plane = (long)h * w;
+        int Yi, Cb, Cr;
+        yuv_load<BITS>(x + b * (plane + (plane >> 1)), h, w, LAYOUT, yy, xx, Yi, Cb, Cr);
+        unsigned rgb_in[3];
+        yuv_to_rgb<BITS>(q, Yi, Cb, Cr, rgb_in);
+        const float* tp = t + (b * 3 * S * S + sy * S + sx) * plane + (long)yy * w + xx;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = tp[(long)c * S * S * plane] + unit_of<kTop<BITS>>(rgb_in[c]);
+    }
+};
+
+// Slot j of a row of `len` words that starts at gp (word-aligned): slot 0 writes the words before the first 4-byte boundary, slot
+// j >= 1 one dword (or, at the row's end, the words that are left); at(k) is word k of the row.  len / WPD + 2 slots cover a row.
+template <typename word, typename At>
+__device__ __forceinline__ void store_row_slot(word* __restrict__ gp, int len, int j, At&& at) {
+    constexpr int WPD = 4 / (int)sizeof(word);
+    const int head = min((int)(((4 - ((size_t)gp & 3)) & 3) / sizeof(word)), len);
+    if (j == 0) {
+        for (int k = 0; k < head; ++k) gp[k] = (word)at(k);
+    } else {
+        const int off = head + WPD * (j - 1);
+        if (off + WPD <= len) {
+            unsigned v = 0u;
+#pragma unroll
+            for (int i = 0; i < WPD; ++i) v |= (unsigned)at(off + i) << (8 * (int)sizeof(word) * i);
+            *reinterpret_cast<unsigned*>(gp + off) = v;
+        } else {
+            for (int k = off; k < len; ++k) gp[k] = (word)at(k);
+        }
+    }
+}
+
+// The whole tile: region bounds, staging, both passes, quantisation and stores.  y: fp32 [N,C,oh,ow], u8 [N,oh,ow,3] or a YUV
+// 4:2:0 frame [N,3oh/2,ow] (Out).
+template <typename Src, typename Out>
+__device__ __forceinline__ void resize_tile(const Src& src, const Out& out, void* __restrict__ y, const int32_t* __restrict__ idx_y,
                                             const float* __restrict__ w_y, const int32_t* __restrict__ idx_x,
                                             const float* __restrict__ w_x, const ResizeGeom& g) {
     extern __shared__ __attribute__((aligned(16))) char resize_smem[];
@@ -122,11 +192,21 @@ __device__ __forceinline__ void resize_tile(const Src& src, void* __restrict__ y
         s_wx[i] = w_x[(long)ox0 * g.px + i];
     }
     const int region = rh * rw;
-    for (int c = 0; c < nc; ++c)
+    if constexpr (Src::kTriple) {
         for (int i = tid; i < region; i += kResizeThreads) {
             const int ry = i / rw, rx = i - ry * rw;
-            s_src[(c * g.rh + ry) * g.pitch + rx] = src.load(b, c0 + c, ymin + ry, xmin + rx);
+            float v[3];
+            src.load3(b, ymin + ry, xmin + rx, v);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) s_src[(c * g.rh + ry) * g.pitch + rx] = v[c];
         }
+    } else {
+        for (int c = 0; c < nc; ++c)
+            for (int i = tid; i < region; i += kResizeThreads) {
+                const int ry = i / rw, rx = i - ry * rw;
+                s_src[(c * g.rh + ry) * g.pitch + rx] = src.load(b, c0 + c, ymin + ry, xmin + rx);
+            }
+    }
     __syncthreads();
 
     // ---- H pass: LDS -> LDS ---------------------------------------------------------------------------------------------------
@@ -144,7 +224,7 @@ __device__ __forceinline__ void resize_tile(const Src& src, void* __restrict__ y
     __syncthreads();
 
     // ---- W pass: LDS -> registers, store --------------------------------------------------------------------------------------
-    if constexpr (!U8) {
+    if constexpr (Out::kind == RESIZE_F32) {
         float* yf = reinterpret_cast<float*>(y);
         const int outs = th * tw;
         for (int c = 0; c < nc; ++c)
@@ -157,7 +237,7 @@ __device__ __forceinline__ void resize_tile(const Src& src, void* __restrict__ y
                 for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
                 yf[((b * g.c + c0 + c) * g.oh + oy0 + ty) * (long)g.ow + ox0 + tx] = acc;
             }
-    } else {
+    } else if constexpr (Out::kind == RESIZE_U8) {
         const int outs = th * tw;
         for (int i = tid; i < outs; i += kResizeThreads) {
             const int ty = i / tw, tx = i - ty * tw;
@@ -194,6 +274,68 @@ __device__ __forceinline__ void resize_tile(const Src& src, void* __restrict__ y
                 }
             }
         }
+    } else {
+        // YUV 4:2:0 (th, tw, oy0, ox0, g.oh, g.ow all even): the levels of the tile, pixel by pixel as (R, G, B) words
+        constexpr int BITS = Out::bits, LAYOUT = Out::layout;
+        typedef typename Depth<BITS>::word word;
+        constexpr int WPD = 4 / (int)sizeof(word);
+        const ResrYuvDesc& q = *out.q;
+        word* s_lv = reinterpret_cast<word*>(s_out);
+        const int outs = th * tw;
+        for (int i = tid; i < outs; i += kResizeThreads) {
+            const int ty = i / tw, tx = i - ty * tw;
+            const int* ix = s_ix + tx * g.px;
+            const float* wx = s_wx + tx * g.px;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float* row = s_mid + (c * g.th + ty) * g.pitch;
+                float acc = 0.f;
+                for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
+                s_lv[i * 3 + c] = (word)quantise<kTop<BITS>>(acc);
+            }
+        }
+        __syncthreads();
+        const long luma = (long)g.oh * g.ow;
+        word* img = reinterpret_cast<word*>(y) + b * (luma + (luma >> 1));
+        // a tile row of Y is tw contiguous words of the frame
+        const int slots = tw / WPD + 2;
+        for (int i = tid; i < th * slots; i += kResizeThreads) {
+            const int ty = i / slots, j = i - ty * slots;
+            const word* lv = s_lv + ty * tw * 3;
+            store_row_slot(img + (long)(oy0 + ty) * g.ow + ox0, tw, j, [&](int k) {
+                return word_of<BITS>(luma_of<BITS>(q, lv[3 * k], lv[3 * k + 1], lv[3 * k + 2]), LAYOUT);
+            });
+        }
+        // the sums of block (cy, bx) of the tile: its four pixels' levels, unrounded
+        auto block_sum = [&](int cy, int bx, int (&sum)[3]) {
+            const word* p0 = s_lv + (2 * cy * tw + 2 * bx) * 3;
+            const word* p1 = p0 + tw * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sum[c] = (int)p0[c] + (int)p0[3 + c] + (int)p1[c] + (int)p1[3 + c];
+        };
+        if constexpr (semi_planar(LAYOUT)) {   // a tile row of CbCr pairs is tw contiguous words as well
+            for (int i = tid; i < (th >> 1) * slots; i += kResizeThreads) {
+                const int cy = i / slots, j = i - cy * slots;
+                store_row_slot(img + luma + (long)((oy0 >> 1) + cy) * g.ow + ox0, tw, j, [&](int k) {
+                    int sum[3];
+                    block_sum(cy, k >> 1, sum);
+                    const unsigned cb = chroma_of<BITS>(q, 1, sum), cr = chroma_of<BITS>(q, 2, sum);
+                    return word_of<BITS>((k & 1) ? cr : cb, LAYOUT);
+                });
+            }
+        } else {                               // ... of the Cb plane and of the Cr plane tw / 2
+            const int cslots = (tw >> 1) / WPD + 2;
+#pragma unroll
+            for (int pl = 0; pl < 2; ++pl)
+                for (int i = tid; i < (th >> 1) * cslots; i += kResizeThreads) {
+                    const int cy = i / cslots, j = i - cy * cslots;
+                    store_row_slot(img + luma + pl * (luma >> 2) + (long)((oy0 >> 1) + cy) * (g.ow >> 1) + (ox0 >> 1), tw >> 1, j, [&](int k) {
+                        int sum[3];
+                        block_sum(cy, k, sum);
+                        return word_of<BITS>(chroma_of<BITS>(q, 1 + pl, sum), LAYOUT);
+                    });
+                }
+        }
     }
 }
 
@@ -201,7 +343,7 @@ template <bool U8>
 __global__ __launch_bounds__(kResizeThreads) void image_resize_kernel(PlanarSrc src, void* __restrict__ y, const int32_t* __restrict__ idx_y,
                                                                       const float* __restrict__ w_y, const int32_t* __restrict__ idx_x,
                                                                       const float* __restrict__ w_x, ResizeGeom g) {
-    resize_tile<PlanarSrc, U8>(src, y, idx_y, w_y, idx_x, w_x, g);
+    resize_tile(src, std::conditional_t<U8, OutU8, OutF32>(), y, idx_y, w_y, idx_x, w_x, g);
 }
 
 template <int S>
@@ -209,7 +351,15 @@ __global__ __launch_bounds__(kResizeThreads) void compact_tail_u8_scaled_kernel(
                                                                                 const int32_t* __restrict__ idx_y, const float* __restrict__ w_y,
                                                                                 const int32_t* __restrict__ idx_x, const float* __restrict__ w_x,
                                                                                 ResizeGeom g) {
-    resize_tile<ShuffleSrc<S>, true>(src, y, idx_y, w_y, idx_x, w_x, g);
+    resize_tile(src, OutU8(), y, idx_y, w_y, idx_x, w_x, g);
+}
+
+template <int S, int BITS, int LAYOUT>
+__global__ __launch_bounds__(kResizeThreads) void compact_tail_yuv_scaled_kernel(YuvShuffleSrc<S, BITS, LAYOUT> src, void* __restrict__ y,
+                                                                                 const int32_t* __restrict__ idx_y, const float* __restrict__ w_y,
+                                                                                 const int32_t* __restrict__ idx_x, const float* __restrict__ w_x,
+                                                                                 ResizeGeom g) {
+    resize_tile(src, OutYuv<BITS, LAYOUT>{&src.q}, y, idx_y, w_y, idx_x, w_x, g);
 }
 
 // source pixels that t consecutive outputs of an axis (in -> out pixels, p taps) can reach
@@ -219,16 +369,35 @@ int span_bound(int t, int in, int out, int p) {
     return (int)(s < in ? s : in);
 }
 
-size_t lds_bytes(const ResizeGeom& g, bool u8) {
+// tables + region + intermediate + the staging buffer of the output stage: three bytes (RESIZE_U8, RESIZE_YUV8) or three 16-bit
+// words (RESIZE_YUV10) per pixel of the tile
+size_t lds_bytes(const ResizeGeom& g, int out) {
     size_t floats = 2 * ((size_t)g.th * g.py + (size_t)g.tw * g.px) + 3 * ((size_t)g.rh + g.th) * g.pitch;
-    return floats * 4 + (u8 ? align_up((size_t)g.th * g.tw * 3, 4) : 0);
+    return floats * 4 + (out == RESIZE_F32 ? 0 : align_up((size_t)g.th * g.tw * 3 * (out == RESIZE_YUV10 ? 2 : 1), 4));
+}
+
+// The largest tile of the list whose LDS fits the budget (g: everything but th, tw, rh, rw, pitch); a YUV 4:2:0 output takes the
+// tiles of even height and width only.  false: none fits.
+bool choose_tile(ResizeGeom& g, int out) {
+    static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {8, 8}, {4, 8}, {4, 4}, {2, 4}, {2, 2}, {1, 2}, {1, 1}};
+    const bool yuv = out == RESIZE_YUV8 || out == RESIZE_YUV10;
+    for (const auto& t : tiles) {
+        if (yuv && ((t[0] | t[1]) & 1)) continue;
+        g.th = t[0]; g.tw = t[1];
+        g.rh = span_bound(g.th < g.oh ? g.th : g.oh, g.h, g.oh, g.py);
+        g.rw = span_bound(g.tw < g.ow ? g.tw : g.ow, g.w, g.ow, g.px);
+        g.pitch = g.rw | 1;
+        if (lds_bytes(g, out) <= kResizeLdsBudget) return true;
+    }
+    return false;
 }
 
 }  // namespace
 
 // Every check of a resize launch and the choice of its tile: no device work.  c, h, w: the source; who: the entry's name.
 int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, const void* idx_y, const void* w_y, int taps_y,
-                const void* idx_x, const void* w_x, int taps_x, bool u8, const void* y, ResizeGeom* out) {
+                const void* idx_x, const void* w_x, int taps_x, int kind, const void* y, ResizeGeom* out) {
+    const bool yuv = kind == RESIZE_YUV8 || kind == RESIZE_YUV10, u8 = kind == RESIZE_U8;
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0)
         return fail(RESR_ERR_ARG, "%s: bad shape (n=%d c=%d h=%d w=%d oh=%d ow=%d)", who, n, c, h, w, oh, ow);
     if (!idx_y || !w_y || !idx_x || !w_x) return fail(RESR_ERR_ARG, "%s: null tap table", who);
@@ -236,36 +405,41 @@ int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, con
         return fail(RESR_ERR_ARG, "%s: taps %d, %d outside [1, %d]", who, taps_y, taps_x, kResizeMaxTaps);
     if (u8 && c != 3) return fail(RESR_ERR_ARG, "%s: uint8 output wants 3 channels, got %d", who, c);
     if (u8 && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the uint8 output must be 4-byte aligned", who);
+    if (yuv && (c != 3 || ((oh | ow) & 1))) return fail(RESR_ERR_ARG, "%s: a 4:2:0 output wants 3 channels and an even height and width, got %d, %dx%d", who, c, oh, ow);
+    if (yuv && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the YUV output must be 4-byte aligned", who);
     ResizeGeom g;
     g.c = c; g.h = h; g.w = w; g.oh = oh; g.ow = ow; g.py = taps_y; g.px = taps_x;
     g.cgroups = (c + 2) / 3;
     if ((long)n * g.cgroups > 65535) return fail(RESR_ERR_ARG, "%s: n * ceil(c / 3) = %ld beyond the grid", who, (long)n * g.cgroups);
-    static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {8, 8}, {4, 8}, {4, 4}, {2, 4}, {2, 2}, {1, 2}, {1, 1}};
-    for (const auto& t : tiles) {
-        g.th = t[0]; g.tw = t[1];
-        g.rh = span_bound(g.th < oh ? g.th : oh, h, oh, taps_y);
-        g.rw = span_bound(g.tw < ow ? g.tw : ow, w, ow, taps_x);
-        g.pitch = g.rw | 1;
-        if (lds_bytes(g, u8) <= kResizeLdsBudget) {
-            if ((oh + g.th - 1) / g.th > 65535)
-                return fail(RESR_ERR_ARG, "%s: %d x %d outputs in %d x %d tiles beyond the grid", who, oh, ow, g.th, g.tw);
-            *out = g;
-            return RESR_OK;
-        }
-    }
-    return fail(RESR_ERR_ARG, "%s: the footprint of one output pixel (%d x %d taps) does not fit the LDS tile: scale too small", who,
-                taps_y, taps_x);
+    if (!choose_tile(g, kind))
+        return fail(RESR_ERR_ARG, "%s: the footprint of one output %s (%d x %d taps) does not fit the LDS tile: scale too small", who,
+                    yuv ? "2x2 block" : "pixel", taps_y, taps_x);
+    if ((oh + g.th - 1) / g.th > 65535)
+        return fail(RESR_ERR_ARG, "%s: %d x %d outputs in %d x %d tiles beyond the grid", who, oh, ow, g.th, g.tw);
+    *out = g;
+    return RESR_OK;
+}
+
+// resr_compact_yuv420_scaled_fits: would resize_plan find an even tile?  No device work, no error text.
+int compact_yuv420_scaled_fits(int h, int w, int s, int oh, int ow, int taps_y, int taps_x, int bits) {
+    if (h <= 0 || w <= 0 || s < 1 || s > 4 || oh <= 0 || ow <= 0 || ((h | w | oh | ow) & 1) || (bits != 8 && bits != 10)) return 0;
+    if (taps_y < 1 || taps_y > kResizeMaxTaps || taps_x < 1 || taps_x > kResizeMaxTaps) return 0;
+    if ((long)h * s > INT_MAX || (long)w * s > INT_MAX) return 0;
+    ResizeGeom g;
+    g.c = 3; g.h = h * s; g.w = w * s; g.oh = oh; g.ow = ow; g.py = taps_y; g.px = taps_x;
+    g.cgroups = 1;
+    return choose_tile(g, bits == 10 ? RESIZE_YUV10 : RESIZE_YUV8) ? 1 : 0;
 }
 
 int image_resize_dispatch(const float* x, void* y, int n, int c, int h, int w, int oh, int ow, const int32_t* idx_y, const float* w_y,
                           int taps_y, const int32_t* idx_x, const float* w_x, int taps_x, int u8, hipStream_t st) {
     if (!x || !y) return fail(RESR_ERR_ARG, "image_resize: null argument");
     ResizeGeom g;
-    const int rc = resize_plan("image_resize", n, c, h, w, oh, ow, idx_y, w_y, taps_y, idx_x, w_x, taps_x, u8 != 0, y, &g);
+    const int rc = resize_plan("image_resize", n, c, h, w, oh, ow, idx_y, w_y, taps_y, idx_x, w_x, taps_x, u8 ? RESIZE_U8 : RESIZE_F32, y, &g);
     if (rc) return rc;
     const dim3 grid((unsigned)((ow + g.tw - 1) / g.tw), (unsigned)((oh + g.th - 1) / g.th), (unsigned)(n * g.cgroups));
     const PlanarSrc src{x, c, h, w};
-    const size_t lds = lds_bytes(g, u8 != 0);
+    const size_t lds = lds_bytes(g, u8 ? RESIZE_U8 : RESIZE_F32);
     prof_before(st);
     if (u8)
         hipLaunchKernelGGL(image_resize_kernel<true>, grid, dim3(kResizeThreads), lds, st, src, y, idx_y, w_y, idx_x, w_x, g);
@@ -282,7 +456,7 @@ int compact_tail_u8_scaled(const float* t, const uint8_t* x, uint8_t* y, int n, 
                            const float* w_y, const int32_t* idx_x, const float* w_x, const ResizeGeom* gp, hipStream_t st) {
     const ResizeGeom g = *gp;
     const dim3 grid((unsigned)((g.ow + g.tw - 1) / g.tw), (unsigned)((g.oh + g.th - 1) / g.th), (unsigned)n);
-    const size_t lds = lds_bytes(g, true);
+    const size_t lds = lds_bytes(g, RESIZE_U8);
     prof_before(st);
     switch (s) {
 #define RESR_SCALED_TAIL(S)                                                                                                       \
@@ -300,6 +474,41 @@ int compact_tail_u8_scaled(const float* t, const uint8_t* x, uint8_t* y, int n, 
     prof_after(st, 31050 + s, 2.0 * n * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
                (double)n * h * w * (s * s * 12.0 + 3.0) + (double)n * g.oh * g.ow * 3.0);
     RESR_CHECK_LAUNCH("compact_tail_u8_scaled_kernel");
+    return RESR_OK;
+}
+
+namespace {
+template <int S, int BITS, int LAYOUT>
+void launch_tail_yuv_scaled(const float* t, const void* x, void* y, int n, int h, int w, const int32_t* idx_y, const float* w_y,
+                            const int32_t* idx_x, const float* w_x, const ResrYuvDesc& q, const ResizeGeom& g, hipStream_t st) {
+    const dim3 grid((unsigned)((g.ow + g.tw - 1) / g.tw), (unsigned)((g.oh + g.th - 1) / g.th), (unsigned)n);
+    const size_t lds = lds_bytes(g, BITS == 8 ? RESIZE_YUV8 : RESIZE_YUV10);
+    const YuvShuffleSrc<S, BITS, LAYOUT> src{t, (const typename Depth<BITS>::word*)x, h, w, q};
+    hipLaunchKernelGGL((compact_tail_yuv_scaled_kernel<S, BITS, LAYOUT>), grid, dim3(kResizeThreads), lds, st, src, y, idx_y, w_y, idx_x, w_x, g);
+}
+}  // namespace
+
+// The fused tail of compact_forward_yuv420_scaled / _yuv420p10_scaled: x, y frames of bytes (bits = 8) or 16-bit words (10), q of
+// that depth (the caller has checked it), g planned by resize_plan for c = 3, h = H * s, w = W * s, RESIZE_YUV8 / RESIZE_YUV10.
+int compact_tail_yuv420_scaled(const float* t, const void* x, void* y, int n, int h, int w, int s, int bits, const int32_t* idx_y,
+                               const float* w_y, const int32_t* idx_x, const float* w_x, const ResrYuvDesc* q, const ResizeGeom* gp,
+                               hipStream_t st) {
+    const ResizeGeom g = *gp;
+    prof_before(st);
+    const bool ok = with_scale(s, [&](auto S) {
+        switch (q->layout) {
+            case RESR_YUV_I420: launch_tail_yuv_scaled<S(), 8, RESR_YUV_I420>(t, x, y, n, h, w, idx_y, w_y, idx_x, w_x, *q, g, st); break;
+            case RESR_YUV_NV12: launch_tail_yuv_scaled<S(), 8, RESR_YUV_NV12>(t, x, y, n, h, w, idx_y, w_y, idx_x, w_x, *q, g, st); break;
+            case RESR_YUV_I420P10: launch_tail_yuv_scaled<S(), 10, RESR_YUV_I420P10>(t, x, y, n, h, w, idx_y, w_y, idx_x, w_x, *q, g, st); break;
+            default: launch_tail_yuv_scaled<S(), 10, RESR_YUV_P010>(t, x, y, n, h, w, idx_y, w_y, idx_x, w_x, *q, g, st); break;
+        }
+    });
+    if (!ok) return fail(RESR_ERR_ARG, "compact_tail_yuv420_scaled: upscale %d", s);
+    // per LR pixel: 3 s^2 floats of t and 1.5 words of x; per output pixel 1.5 words
+    const double wb = bits == 10 ? 2.0 : 1.0;
+    prof_after(st, (bits == 10 ? 31080 : 31070) + s, 2.0 * n * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
+               (double)n * h * w * (s * s * 12.0 + 1.5 * wb) + (double)n * g.oh * g.ow * 1.5 * wb);
+    RESR_CHECK_LAUNCH("compact_tail_yuv_scaled_kernel");
     return RESR_OK;
 }
 

@@ -41,7 +41,9 @@ and the two colour conversions are integer functions of bytes (studio range, BT.
 replicated on the way in and box-averaged unrounded on the way out): `yuv420_to_rgb_np` / `rgb_to_yuv420_np` below ARE the
 definition; `yuv420_to_rgb` / `rgb_to_yuv420` are the same functions on the device, one launch each.  A model with a fused entry
 (`SRVGGNetCompact.forward_yuv420`: both conversions inside the compact net's first and last kernel) runs it when the frame fits one
-call; every other case (the RRDB `Generator`, tiled frames, outscale) is the composition of the device launches.
+call, with `outscale` too (`resr_compact_forward_yuv420_scaled`: the resized tail of the RGB path with a YUV 4:2:0 output stage, one
+launch sequence, no RGB frame); every other case (the RRDB `Generator`, tiled frames, a scale so small that no tile of even height and
+width fits the resize kernel's LDS) is the composition of the device launches.
 
 10-BIT YUV 4:2:0 -- what decoders deliver for most HEVC / AV1 material (P010 from hardware, `yuv420p10le` from software), and what an
 encoder needs to keep 1024 levels of a smooth gradient instead of 256.  The geometry is the 8-bit one with a little-endian uint16 word
@@ -56,10 +58,11 @@ model as `rgb10 / 1023.0f` and leaves as q10(v) = trunc(clamp(v * 1023.0f, 0, 10
     upscale_yuv420p10(model, f) == rgb_to_yuv420p10_np(q10(float_path(model, yuv420p10_to_rgb_np(f) / 1023.0f)))
 
 with `float_path` the model's forward (or `tiling.super_resolve`) on fp32 NCHW, followed by `resize_with_plan` with `outscale`.  A model
-with a fused entry (`SRVGGNetCompact.forward_yuv420p10`) runs it when the frame fits one call: neither an RGB frame nor an fp32 copy of
-the input exists then.  Every other case is `to_yuv420p10(float_path(from_yuv420p10(f)))`, one launch each way, straight between the
-frames and fp32.  Not provided: mixed depths (8 bits in, 10 out, or the reverse), 12 / 16-bit samples (16 bits would overflow the int32
-accumulators), full range, 4:2:2 / 4:4:4, a fused 10-bit outscale tail.
+with a fused entry (`SRVGGNetCompact.forward_yuv420p10`) runs it when the frame fits one call, with `outscale` too
+(`resr_compact_forward_yuv420p10_scaled`): neither an RGB frame nor an fp32 copy of the input exists then, and the fp32 frames of the
+float path exist as LDS tiles only.  Every other case is `to_yuv420p10(float_path(from_yuv420p10(f)))`, one launch each way, straight
+between the frames and fp32.  Not provided: mixed depths (8 bits in, 10 out, or the reverse), 12 / 16-bit samples (16 bits would
+overflow the int32 accumulators), full range, 4:2:2 / 4:4:4.
 """
 from __future__ import annotations
 
@@ -297,6 +300,14 @@ def rgb_to_yuv420(rgb: torch.Tensor, layout: str = "i420", matrix: str = "bt601"
     return out
 
 
+def _fused_yuv_outscale(model, method: str, n: int, h: int, w: int, plan, bits: int) -> bool:
+    """Does the fused YUV outscale call take this frame?  The model has the method, the frame fits one call, and the library finds a
+    tile of even height and width within the resize kernel's LDS (`resr_compact_yuv420_scaled_fits`: no device work)."""
+    if not hasattr(model, method) or not tiling.fits_whole(model, n, h, w):
+        return False
+    return bool(_lib.lib().resr_compact_yuv420_scaled_fits(h, w, model.upscale_factor, plan.out_h, plan.out_w, plan.taps_y, plan.taps_x, bits))
+
+
 def yuv420_output_size(h: int, w: int, s: int, outscale, what: str) -> Tuple[int, int]:
     """`output_size`, which for a 4:2:0 result must be even both ways: ValueError otherwise (before any launch)."""
     out_h, out_w = output_size(h, w, s, outscale)
@@ -322,6 +333,8 @@ def upscale_yuv420(model, frames: torch.Tensor, layout: str = "i420", matrix: st
     if o is not None:
         yuv420_output_size(h, w, s, o, "upscale_yuv420")
         plan = _resize_plan(h, w, s, o, frames.device, plan)              # ValueError before any launch, as in upscale_u8
+        if _fused_yuv_outscale(model, "forward_yuv420", n, h, w, plan, 8):
+            return model.forward_yuv420(frames, layout, matrix, outscale=o, plan=plan)
     rgb = upscale_u8(model, yuv420_to_rgb(frames, layout, matrix), halo, outscale=o, plan=plan)
     return rgb_to_yuv420(rgb, layout, matrix)
 
@@ -461,7 +474,8 @@ def upscale_yuv420p10(model, frames: torch.Tensor, layout: str = "i420p10", matr
     """uint16 [N,3H/2,W] (10-bit 4:2:0) on the model's device -> uint16 [N,3sH/2,sW], same layout: the composition of the module
     docstring, bit for bit.  The one place that chooses between the fused call and the composition, as `upscale_yuv420` is for 8
     bits; `halo`, `outscale` and `plan` are `upscale_u8`'s.  With `outscale` the float frame is resized (`resize_with_plan`, fp32
-    out) before it is quantised; an odd out_h or out_w is a ValueError before any launch."""
+    out) before it is quantised -- inside the fused call's last kernel, or as launches of its own where that call does not apply; an
+    odd out_h or out_w is a ValueError before any launch."""
     yuv10_desc(layout, matrix)
     n, h, w = check_yuv420p10(frames, "upscale_yuv420p10")
     s = model.upscale_factor
@@ -471,6 +485,8 @@ def upscale_yuv420p10(model, frames: torch.Tensor, layout: str = "i420p10", matr
     if o is not None:
         yuv420_output_size(h, w, s, o, "upscale_yuv420p10")
         plan = _resize_plan(h, w, s, o, frames.device, plan)              # ValueError before any launch, as in upscale_u8
+        if _fused_yuv_outscale(model, "forward_yuv420p10", n, h, w, plan, 10):
+            return model.forward_yuv420p10(frames, layout, matrix, outscale=o, plan=plan)
     sr = tiling.super_resolve(model, from_yuv420p10(frames, layout, matrix), halo)
     if o is not None:
         from .imgproc import resize_with_plan

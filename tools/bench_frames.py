@@ -22,7 +22,8 @@ one `summary` line per case with the ratios and whether each exceeds the spread 
     python tools/bench_frames.py --outscale 2 --out profiles/frames_outscale_1080p.jsonl
 
 `--pix_fmt i420 [nv12]` measures the YUV 4:2:0 path (frames.py, YUV 4:2:0) against the rgb24 one of the same run, alternated the same
-way, per case (with `--outscale O` every path below runs at that final factor, the YUV ones as the composition over the generic launches):
+way, per case (with `--outscale O` every path below runs at that final factor; the YUV ones take the fused scaled tail, and
+`dev/composed_<fmt>` is the same result as the composition over the generic launches, which is what they ran before that tail existed):
   dev/forward_u8            model.forward_u8(frame uint8 RGB)                  (upscale_u8(..., outscale=O) with --outscale)
   dev/forward_<fmt>         model.forward_yuv420(frame, layout=<fmt>)          (upscale_yuv420(..., outscale=O) with --outscale)
   B2/2, B2/2/view           FrameStream(depth=2), rgb24, copy=True / copy=False
@@ -251,6 +252,19 @@ def mode_yuv(args):
     def upscale(model, x, fmt):
         return (R.upscale_yuv420p10 if fmt in ten else R.upscale_yuv420)(model, x, fmt, outscale=o)
 
+    scaled = o is not None and o != S
+    plans = {}
+
+    def composed(model, x, fmt):     # the definition as launches: generic conversion, the RGB / float path, generic conversion
+        if fmt in ten:
+            sr = model(R.from_yuv420p10(x, fmt))
+            if scaled:
+                if x.device not in plans:
+                    plans[x.device] = imgproc.ResizePlan(H * S, W * S, o / S, x.device)
+                sr = imgproc.resize_with_plan(sr, plans[x.device])
+            return R.to_yuv420p10(sr, fmt)
+        return R.rgb_to_yuv420(R.upscale_u8(model, R.yuv420_to_rgb(x, fmt), outscale=o), fmt)
+
     yuv = {fmt: [to_yuv(f, fmt) for f in pool] for fmt in args.pix_fmt}
     many_yuv = {fmt: [yuv[fmt][i % 4] for i in range(args.frames * 4)] for fmt in args.pix_fmt}
     oh, ow = R.output_size(H, W, S, o)
@@ -269,19 +283,15 @@ def mode_yuv(args):
             streams[fmt] = R.FrameStream(model, depth=2, outscale=o, pix_fmt=fmt)
             x_yuv[fmt] = torch.from_numpy(yuv[fmt][0])[None].cuda()
             dev[f"dev/forward_{fmt}"] = lambda fmt=fmt: upscale(model, x_yuv[fmt], fmt)
+            if scaled:
+                dev[f"dev/composed_{fmt}"] = lambda fmt=fmt: composed(model, x_yuv[fmt], fmt)
             paths[f"B2/2/{fmt}"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr)), yuv_bytes[fmt])
             paths[f"B2/2/{fmt}/view"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr, copy=False)), yuv_bytes[fmt])
 
         def check():     # the definition, on a timed frame: the stream's result is the composition over the RGB path
             same = {}
             for fmt in args.pix_fmt:
-                if fmt in ten:
-                    sr = model(R.from_yuv420p10(x_yuv[fmt], fmt))
-                    if o is not None and o != S:
-                        sr = imgproc.resize_with_plan(sr, imgproc.ResizePlan(H * S, W * S, o / S, sr.device))
-                    want = R.to_yuv420p10(sr, fmt)[0].cpu().numpy()
-                else:
-                    want = R.rgb_to_yuv420(R.upscale_u8(model, R.yuv420_to_rgb(x_yuv[fmt], fmt), outscale=o), fmt)[0].cpu().numpy()
+                want = composed(model, x_yuv[fmt], fmt)[0].cpu().numpy()
                 same[fmt] = bool(np.array_equal(next(iter(streams[fmt].map(yuv[fmt][:1]))), want))
             return same
 
@@ -292,6 +302,11 @@ def mode_yuv(args):
                 line[f"device_{fmt}_minus_u8_ms"] = round(med[f"dev/forward_{fmt}"] - med["dev/forward_u8"], 3)
                 line[f"stream_{fmt}_over_rgb24_frames_per_s"] = round(med["B2/2"] / med[f"B2/2/{fmt}"], 2)
                 line[f"stream_view_{fmt}_over_rgb24_frames_per_s"] = round(med["B2/2/view"] / med[f"B2/2/{fmt}/view"], 2)
+                if scaled:       # the fused tail against the composition of the same run
+                    a, b = f"dev/forward_{fmt}", f"dev/composed_{fmt}"
+                    line[f"device_{fmt}_fused_over_composed"] = round(med[a] / med[b], 3)
+                    line[f"device_{fmt}_fused_minus_composed_ms"] = round(med[a] - med[b], 3)
+                    line[f"device_{fmt}_fused_not_slower_beyond_spread"] = bool(med[a] <= med[b] + max(spread[a], spread[b]))
             return line
 
         return SimpleNamespace(head=dict(pix_fmt=list(args.pix_fmt), outscale=o), frame=f"{W}x{H}->{ow}x{oh}", host_first=False, gbps=True,
