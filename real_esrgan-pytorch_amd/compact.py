@@ -233,22 +233,27 @@ class SRVGGNetCompact(nn.Module):
         plan.check(what)
         return plan
 
-    def _forward_yuv_scaled(self, entry: str, frames: torch.Tensor, n: int, h: int, w: int, o: float, plan, ydesc, what: str) -> torch.Tensor:
-        """The outscale call of `forward_yuv420` / `forward_yuv420p10` once the frames are checked (the result has their dtype)."""
-        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
-        plan = self._scaled_plan(frames, h, w, o, plan, what)
-        y = torch.empty((n, plan.out_h * 3 // 2, plan.out_w), dtype=frames.dtype, device=frames.device)
-        return self._call(entry, frames, n, h, w, y, *plan.args(), C.byref(ydesc))
-
-    def _yuv_outscale(self, frames: torch.Tensor, outscale, what: str) -> Optional[float]:
-        """`outscale` of a YUV call, checked as `forward_u8` checks it, and the 4:2:0 rule of its result -- an odd height or width is
-        a ValueError -- before the device is looked at."""
+    def _forward_yuv(self, frames: torch.Tensor, layout: str, matrix: str, outscale, plan, bits: int) -> torch.Tensor:
+        """`forward_yuv420` (bits = 8) / `forward_yuv420p10` (10).  `outscale` is checked as `forward_u8` checks it, with the 4:2:0
+        rule of its result -- an odd height or width is a ValueError -- before the device is looked at."""
         from . import frames as _frames
+        name = _frames._yuv_name(bits)
+        what, entry = "SRVGGNetCompact.forward_" + name, "resr_compact_forward_" + name
         o = _frames.check_outscale(outscale, self.upscale, what)
         hw = _frames._yuv_hw(frames.shape) if o is not None and isinstance(frames, torch.Tensor) else None
         if hw is not None:
             _frames.yuv420_output_size(hw[0], hw[1], self.upscale, o, what)
-        return o
+        ydesc = _frames._desc(bits, layout, matrix)
+        self._guard()
+        n, h, w = _frames._check_yuv(frames, what, bits)
+        s = self.upscale
+        if o is None:
+            y = torch.empty((n, h * s * 3 // 2, w * s), dtype=frames.dtype, device=frames.device)
+            return self._call(entry, frames, n, h, w, y, C.byref(ydesc))
+        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
+        plan = self._scaled_plan(frames, h, w, o, plan, what)
+        y = torch.empty((n, plan.out_h * 3 // 2, plan.out_w), dtype=frames.dtype, device=frames.device)
+        return self._call(entry + "_scaled", frames, n, h, w, y, *plan.args(), C.byref(ydesc))
 
     def forward_yuv420(self, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601", outscale: Optional[float] = None,
                        plan=None) -> torch.Tensor:
@@ -262,16 +267,7 @@ class SRVGGNetCompact(nn.Module):
         must be even both ways (ValueError) -- `resr_compact_forward_yuv420_scaled`: bit for bit
         `rgb_to_yuv420_np(self.forward_u8(yuv420_to_rgb_np(f), outscale=outscale))`, still with no RGB frame on the device.  A scale
         so small that no even tile fits the kernel's LDS is an error here; `frames.upscale_yuv420` asks first and composes."""
-        from . import frames as _frames
-        o = self._yuv_outscale(frames, outscale, "SRVGGNetCompact.forward_yuv420")
-        ydesc = _frames.yuv_desc(layout, matrix)
-        self._guard()
-        n, h, w = _frames.check_yuv420(frames, "SRVGGNetCompact.forward_yuv420")
-        if o is not None:
-            return self._forward_yuv_scaled("resr_compact_forward_yuv420_scaled", frames, n, h, w, o, plan, ydesc, "SRVGGNetCompact.forward_yuv420")
-        s = self.upscale
-        y = torch.empty((n, h * s * 3 // 2, w * s), dtype=torch.uint8, device=frames.device)
-        return self._call("resr_compact_forward_yuv420", frames, n, h, w, y, C.byref(ydesc))
+        return self._forward_yuv(frames, layout, matrix, outscale, plan, 8)
 
     def forward_yuv420p10(self, frames: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601", outscale: Optional[float] = None,
                           plan=None) -> torch.Tensor:
@@ -284,17 +280,7 @@ class SRVGGNetCompact(nn.Module):
         `outscale`, `plan`: as `forward_yuv420`'s -> uint16 [N, 3 out_h / 2, out_w] -- `resr_compact_forward_yuv420p10_scaled`: bit for
         bit `rgb_to_yuv420p10_np(q10(resize_with_plan(self(yuv420p10_to_rgb_np(f) / 1023), plan)))`; the fp32 frames of that
         composition exist as LDS tiles only."""
-        from . import frames as _frames
-        o = self._yuv_outscale(frames, outscale, "SRVGGNetCompact.forward_yuv420p10")
-        ydesc = _frames.yuv10_desc(layout, matrix)
-        self._guard()
-        n, h, w = _frames.check_yuv420p10(frames, "SRVGGNetCompact.forward_yuv420p10")
-        if o is not None:
-            return self._forward_yuv_scaled("resr_compact_forward_yuv420p10_scaled", frames, n, h, w, o, plan, ydesc,
-                                            "SRVGGNetCompact.forward_yuv420p10")
-        s = self.upscale
-        y = torch.empty((n, h * s * 3 // 2, w * s), dtype=torch.uint16, device=frames.device)
-        return self._call("resr_compact_forward_yuv420p10", frames, n, h, w, y, C.byref(ydesc))
+        return self._forward_yuv(frames, layout, matrix, outscale, plan, 10)
 
     def load_official_state_dict(self, checkpoint) -> None:
         """Upstream's `{"params_ema": sd}` / `{"params": sd}` (params_ema preferred) or a bare state dict (model.load_official_state_dict)."""

@@ -101,23 +101,12 @@ size_t compact_param_count(const ResrCompactDesc*);
 size_t compact_packed_bytes(const ResrCompactDesc*);
 size_t compact_workspace_bytes(const ResrCompactDesc*);
 int64_t compact_pack_table(const ResrCompactDesc*, ResrPackChunk*, int64_t);
-int compact_forward(const ResrCompactDesc*, const float*, const float*, const void*, void*, size_t, float*, hipStream_t);
-int compact_forward_u8(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, hipStream_t);
-int compact_forward_u8_scaled(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, int, int,
-                              const int32_t*, const float*, int, const int32_t*, const float*, int, hipStream_t);
-int compact_forward_yuv420_scaled(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, int, int,
-                                  const int32_t*, const float*, int, const int32_t*, const float*, int, const ResrYuvDesc*, hipStream_t);
-int compact_forward_yuv420p10_scaled(const ResrCompactDesc*, const uint16_t*, const float*, const void*, void*, size_t, uint16_t*, int, int,
-                                     const int32_t*, const float*, int, const int32_t*, const float*, int, const ResrYuvDesc*, hipStream_t);
+int compact_forward_ends(const ResrCompactDesc*, const Ends&, const float*, const void*, void*, size_t, hipStream_t, const char*);
 int compact_yuv420_scaled_fits(int, int, int, int, int, int, int, int);
 int image_resize_dispatch(const float*, void*, int, int, int, int, int, int, const int32_t*, const float*, int, const int32_t*,
                           const float*, int, int, hipStream_t);
-int compact_forward_yuv420(const ResrCompactDesc*, const uint8_t*, const float*, const void*, void*, size_t, uint8_t*, const ResrYuvDesc*,
-                           hipStream_t);
 int yuv420_to_rgb_dispatch(const uint8_t*, uint8_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
 int rgb_to_yuv420_dispatch(const uint8_t*, uint8_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
-int compact_forward_yuv420p10(const ResrCompactDesc*, const uint16_t*, const float*, const void*, void*, size_t, uint16_t*, const ResrYuvDesc*,
-                              hipStream_t);
 int yuv420p10_to_nchw_dispatch(const uint16_t*, float*, int, int, int, const ResrYuvDesc*, hipStream_t);
 int nchw_to_yuv420p10_dispatch(const float*, uint16_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
 int u8_to_nchw_dispatch(const uint8_t*, float*, int, int, int, hipStream_t);
@@ -287,13 +276,15 @@ int64_t resr_compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* chunks,
 int resr_compact_forward(const ResrCompactDesc* d, const float* x_nchw, const float* params, const void* packed,
                          void* workspace, size_t workspace_bytes, float* y_nchw, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward(d, x_nchw, params, packed, workspace, workspace_bytes, y_nchw, (hipStream_t)stream);
+    return compact_forward_ends(d, {END_F32, false, x_nchw, y_nchw, {}, nullptr, 0}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+                                "compact_forward");
 }
 
 int resr_compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
                             void* workspace, size_t workspace_bytes, uint8_t* y_u8, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_u8(d, x_u8, params, packed, workspace, workspace_bytes, y_u8, (hipStream_t)stream);
+    return compact_forward_ends(d, {END_RGB8, false, x_u8, y_u8, {}, nullptr, 0}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+                                "compact_forward_u8");
 }
 
 int resr_compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
@@ -301,8 +292,8 @@ int resr_compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x_u8
                                    const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
                                    int32_t taps_x, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_u8_scaled(d, x_u8, params, packed, workspace, workspace_bytes, y_u8, oh, ow, idx_y, w_y, taps_y, idx_x, w_x,
-                                     taps_x, (hipStream_t)stream);
+    return compact_forward_ends(d, {END_RGB8, true, x_u8, y_u8, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, nullptr, 0}, params, packed,
+                                workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_u8_scaled");
 }
 
 int resr_image_resize(const float* src_f32, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow,
@@ -325,7 +316,8 @@ int resr_nchw_to_u8(const float* src_f32, uint8_t* dst_u8, int32_t n, int32_t h,
 int resr_compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x_yuv, const float* params, const void* packed,
                                 void* workspace, size_t workspace_bytes, uint8_t* y_yuv, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_yuv420(d, x_yuv, params, packed, workspace, workspace_bytes, y_yuv, yuv, (hipStream_t)stream);
+    return compact_forward_ends(d, {END_YUV, false, x_yuv, y_yuv, {}, yuv, 8}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+                                "compact_forward_yuv420");
 }
 
 int resr_yuv420_to_rgb(const uint8_t* src, uint8_t* dst_hwc, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream) {
@@ -341,7 +333,8 @@ int resr_rgb_to_yuv420(const uint8_t* src_hwc, uint8_t* dst, int32_t n, int32_t 
 int resr_compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x_yuv, const float* params, const void* packed,
                                    void* workspace, size_t workspace_bytes, uint16_t* y_yuv, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_yuv420p10(d, x_yuv, params, packed, workspace, workspace_bytes, y_yuv, yuv, (hipStream_t)stream);
+    return compact_forward_ends(d, {END_YUV, false, x_yuv, y_yuv, {}, yuv, 10}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+                                "compact_forward_yuv420p10");
 }
 
 int resr_yuv420p10_to_nchw(const uint16_t* src, float* dst_f32, int32_t n, int32_t h, int32_t w, const ResrYuvDesc* yuv, void* stream) {
@@ -359,8 +352,8 @@ int resr_compact_forward_yuv420_scaled(const ResrCompactDesc* d, const uint8_t* 
                                        const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
                                        int32_t taps_x, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_yuv420_scaled(d, x_yuv, params, packed, workspace, workspace_bytes, y_yuv, oh, ow, idx_y, w_y, taps_y, idx_x,
-                                         w_x, taps_x, yuv, (hipStream_t)stream);
+    return compact_forward_ends(d, {END_YUV, true, x_yuv, y_yuv, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv, 8}, params, packed,
+                                workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_yuv420_scaled");
 }
 
 int resr_compact_forward_yuv420p10_scaled(const ResrCompactDesc* d, const uint16_t* x_yuv, const float* params, const void* packed,
@@ -368,8 +361,8 @@ int resr_compact_forward_yuv420p10_scaled(const ResrCompactDesc* d, const uint16
                                           const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
                                           int32_t taps_x, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_yuv420p10_scaled(d, x_yuv, params, packed, workspace, workspace_bytes, y_yuv, oh, ow, idx_y, w_y, taps_y, idx_x,
-                                            w_x, taps_x, yuv, (hipStream_t)stream);
+    return compact_forward_ends(d, {END_YUV, true, x_yuv, y_yuv, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv, 10}, params, packed,
+                                workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_yuv420p10_scaled");
 }
 
 int resr_compact_yuv420_scaled_fits(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x, int32_t bits) {

@@ -115,4 +115,27 @@ struct ResizeGeom {
 // a staging buffer of levels as wide as the sample's word)
 enum ResizeOut { RESIZE_F32 = 0, RESIZE_U8 = 1, RESIZE_YUV8 = 2, RESIZE_YUV10 = 3 };
 
+
+// compact.hip: the two ends of one forward pass (compact_forward_ends; api.hip builds one per entry): what x and y are, and what
+// else that kind of end needs.
+struct ScaledTail {
+    int oh, ow, taps_y, taps_x;
+    const int32_t *idx_y, *idx_x;
+    const float *w_y, *w_x;
+};
+enum EndFormat {
+    END_F32,    // x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32: layout.hip's head, compact_tail
+    END_RGB8,   // x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8: frames.hip, the conversions fused into the head and the tail
+    END_YUV,    // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames of bytes or 16-bit words (yuv->layout): the colour conversions too
+};
+struct Ends {
+    EndFormat format;
+    bool scaled;             // END_RGB8, END_YUV: y is the frame resized to sc.oh x sc.ow by the tail of image_resize.hip
+    const void* x;
+    void* y;
+    ScaledTail sc;           // scaled
+    const ResrYuvDesc* yuv;  // END_YUV, else null
+    int bits_expected;       // END_YUV: the depth the entry is for, 8 or 10; a descriptor of another is refused
+};
+
 }  // namespace resr

@@ -8,14 +8,13 @@
 //   y[n,c,Y,X] = t[n, c*s*s + (Y%s)*s + X%s, Y/s, X/s] + x[n,c,Y/s,X/s]      (one launch, 64-bit indexing)
 // T = f16 (fast) / f32 (strict); RESR_F16X2 (exact16): every NHWC tensor is a hi/lo pair, the lo tensor right behind the hi one,
 // three stages per chunk.  No padding beyond each conv's own pad = 1: any H, W >= 1.
-// The three frame entries are the same sequence with another pair of ends (Ends below), same plan, same workspace:
-//   compact_forward_u8        uint8 HWC frames: frames.hip's head in place of the layout kernel, its u8 tail (pixel-shuffle +
-//                             residual + * 255, clamp, truncate) in place of compact_tail_kernel;
-//   compact_forward_u8_scaled ("outscale") image_resize.hip's fused tail in place of the u8 tail: the HR frame is formed tile by
-//                             tile in LDS and only the resized uint8 frame [N,oh,ow,3] is written;
-//   compact_forward_yuv420    YUV 4:2:0 frames [N,3H/2,W]: frames.hip's head reading YUV, and its YUV tail;
-//   compact_forward_yuv420p10 the same for 10-bit frames of 16-bit words (yuv420p10le / P010): 1023 levels at both ends;
-//   compact_forward_yuv420_scaled / _yuv420p10_scaled  the YUV head and image_resize.hip's resized tail with a YUV 4:2:0 output stage.
+// Every entry of the C ABI is this sequence with its own pair of ends (Ends of common.h: a format and a flag), same plan, same workspace:
+//   END_RGB8          uint8 HWC frames: frames.hip's head in place of the layout kernel, its u8 tail (pixel-shuffle + residual +
+//                     * 255, clamp, truncate) in place of compact_tail_kernel;
+//   END_YUV           YUV 4:2:0 frames [N,3H/2,W] of bytes or of 16-bit words holding 10-bit samples (yuv420p10le / P010: 1023
+//                     levels at both ends): frames.hip's head reading YUV, and its YUV tail;
+//   ... and scaled    ("outscale") image_resize.hip's fused tail in place of either: the HR frame is formed tile by tile in LDS and
+//                     only the resized frame, uint8 [N,oh,ow,3] or YUV 4:2:0 [N,3oh/2,ow], is written.
 #include <vector>
 
 #include "common.h"
@@ -28,15 +27,13 @@ int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const 
 int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
 int frame_head_dispatch(const void*, void*, int, int, int, int, hipStream_t, long, const ResrYuvDesc*);   // frames.hip
 int compact_tail_u8(const float*, const uint8_t*, uint8_t*, int, int, int, int, hipStream_t);
-int yuv420_forward_check(const char*, int, int, int, int, const uint8_t*, const ResrYuvDesc*);
-int compact_tail_yuv420(const float*, const uint8_t*, uint8_t*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
-int yuv420p10_forward_check(const char*, int, int, int, int, const uint16_t*, const ResrYuvDesc*);
-int compact_tail_yuv420p10(const float*, const uint16_t*, uint16_t*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
+int yuv_forward_check(const char*, int, int, int, int, const void*, const ResrYuvDesc*, int);
+int compact_tail_yuv(const float*, const void*, void*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
 int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, int,
                 const void*, ResizeGeom*);                                                                      // image_resize.hip
 int compact_tail_u8_scaled(const float*, const uint8_t*, uint8_t*, int, int, int, int, const int32_t*, const float*, const int32_t*,
                            const float*, const ResizeGeom*, hipStream_t);
-int compact_tail_yuv420_scaled(const float*, const void*, void*, int, int, int, int, int, const int32_t*, const float*, const int32_t*,
+int compact_tail_yuv420_scaled(const float*, const void*, void*, int, int, int, int, const int32_t*, const float*, const int32_t*,
                                const float*, const ResrYuvDesc*, const ResizeGeom*, hipStream_t);
 
 namespace {
@@ -179,69 +176,30 @@ int64_t compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t
 
 namespace {
 
-struct ScaledTail {
-    int oh, ow, taps_y, taps_x;
-    const int32_t *idx_y, *idx_x;
-    const float *w_y, *w_x;
-};
-
-// The two ends of one forward pass: what x and y are, and what else that kind of end needs.
-enum EndKind {
-    F32_NCHW,        // x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32: layout.hip's head, compact_tail
-    U8_HWC,          // x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8: frames.hip, the conversions fused into the head and the tail
-    U8_HWC_SCALED,   // ... -> y [N,oh,ow,3]: the resized tail of image_resize.hip (sc)
-    YUV420,          // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames: the colour conversions (yuv) fused into the same two kernels
-    YUV420P10,       // ... of 16-bit words holding 10-bit samples (x_u8 / y_u8 point at uint16_t)
-    YUV420_SCALED,     // YUV420 -> y [N,3oh/2,ow]: the resized tail with a YUV 4:2:0 output stage (sc and yuv)
-    YUV420P10_SCALED,  // YUV420P10 likewise
-};
-
-struct Ends {
-    EndKind kind;
-    const float* x_f32;      // F32_NCHW
-    float* y_f32;
-    const uint8_t* x_u8;     // every other kind
-    uint8_t* y_u8;
-    ScaledTail sc;           // U8_HWC_SCALED, YUV420_SCALED, YUV420P10_SCALED
-    const ResrYuvDesc* yuv;  // every YUV kind, else null
-};
-
-// Everything a call can be refused for after its descriptor, before the first launch.  The scaled kinds: fills geom.
+// Everything a call can be refused for after its descriptor, before the first launch.  Scaled ends: fills geom.
 int check_ends(const CPlan& p, const Ends& e, const float* params, const void* packed, const void* workspace, size_t workspace_bytes,
                const char* who, ResizeGeom* geom) {
     const ResrCompactDesc& d = p.d;
-    const bool no_ends = e.kind == F32_NCHW ? !e.x_f32 || !e.y_f32 : !e.x_u8 || !e.y_u8;
-    if (no_ends || !params || !packed || !workspace) return fail(RESR_ERR_ARG, "%s: null argument", who);
+    if (!e.x || !e.y || !params || !packed || !workspace) return fail(RESR_ERR_ARG, "%s: null argument", who);
+    if (e.format == END_F32 && e.scaled) return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
+    if (e.format == END_RGB8 && ((size_t)e.y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
     int rc = RESR_OK;
-    switch (e.kind) {
-        case F32_NCHW: break;
-        case U8_HWC:
-        case U8_HWC_SCALED:
-            if (((size_t)e.y_u8 & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
-            if (e.kind == U8_HWC_SCALED)
-                rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y,
-                                 e.sc.idx_x, e.sc.w_x, e.sc.taps_x, RESIZE_U8, e.y_u8, geom);
-            break;
-        case YUV420: rc = yuv420_forward_check(who, d.n, d.h, d.w, d.upscale, e.y_u8, e.yuv); break;
-        case YUV420P10: rc = yuv420p10_forward_check(who, d.n, d.h, d.w, d.upscale, (const uint16_t*)e.y_u8, e.yuv); break;
-        case YUV420_SCALED:
-        case YUV420P10_SCALED:
-            // the descriptor and the LR frame (the output pointer's rule is the plan's: nullptr passes the unscaled tail's), then the plan
-            rc = e.kind == YUV420_SCALED ? yuv420_forward_check(who, d.n, d.h, d.w, d.upscale, nullptr, e.yuv)
-                                         : yuv420p10_forward_check(who, d.n, d.h, d.w, d.upscale, nullptr, e.yuv);
-            if (!rc)
-                rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y,
-                                 e.sc.idx_x, e.sc.w_x, e.sc.taps_x, e.kind == YUV420_SCALED ? RESIZE_YUV8 : RESIZE_YUV10, e.y_u8, geom);
-            break;
-    }
+    // the descriptor and the LR frame; of scaled ends the output pointer's rule is the plan's (nullptr passes the unscaled tail's)
+    if (e.format == END_YUV) rc = yuv_forward_check(who, d.n, d.h, d.w, d.upscale, e.scaled ? nullptr : e.y, e.yuv, e.bits_expected);
+    if (!rc && e.scaled)
+        rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y, e.sc.idx_x,
+                         e.sc.w_x, e.sc.taps_x, e.format == END_RGB8 ? RESIZE_U8 : e.bits_expected == 8 ? RESIZE_YUV8 : RESIZE_YUV10, e.y, geom);
     if (rc) return rc;
     if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
     return RESR_OK;
 }
 
+}  // namespace
+
 // The launch sequence every entry shares: plan, refusals, head, convs, tail.
-int compact_run(const ResrCompactDesc* d, const Ends& e, const float* params, const void* packed, void* workspace,
-                size_t workspace_bytes, hipStream_t st, const char* who) {
+int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* params, const void* packed, void* workspace,
+                         size_t workspace_bytes, hipStream_t st, const char* who) {
+    if (e.format == END_YUV && !e.yuv) return fail(RESR_ERR_ARG, "%s: null argument", who);
     CPlan p;
     if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "%s: bad descriptor", who);
     ResizeGeom geom;
@@ -256,10 +214,8 @@ int compact_run(const ResrCompactDesc* d, const Ends& e, const float* params, co
     float* t = reinterpret_cast<float*>(base + p.off_t);
     const int N = d->n, H = d->h, W = d->w;
     const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
-    switch (e.kind) {
-        case F32_NCHW: rc = nchw_to_nhwc_dispatch(e.x_f32, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32); break;
-        default: rc = frame_head_dispatch(e.x_u8, xin, N, H, W, d->dtype, st, (long)lo32, e.yuv); break;   // yuv null: RGB bytes; its layout: bytes or 16-bit words
-    }
+    if (e.format == END_F32) rc = nchw_to_nhwc_dispatch((const float*)e.x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
+    else rc = frame_head_dispatch(e.x, xin, N, H, W, d->dtype, st, (long)lo32, e.yuv);   // yuv null: RGB bytes; its layout: bytes or 16-bit words
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) {
         ResrConvDesc cd;
@@ -296,70 +252,17 @@ int compact_run(const ResrCompactDesc* d, const Ends& e, const float* params, co
         rc = conv3x3_dispatch(&cd, in, nullptr, pk + c.pk * wes, params + c.b_off, nullptr, nullptr, nullptr, t, nullptr, st);
         if (rc) return rc;
     }
-    switch (e.kind) {
-        case F32_NCHW: return compact_tail(t, e.x_f32, e.y_f32, N, H, W, d->upscale, st);
-        case U8_HWC: return compact_tail_u8(t, e.x_u8, e.y_u8, N, H, W, d->upscale, st);
-        case U8_HWC_SCALED:
-            return compact_tail_u8_scaled(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, &geom, st);
-        case YUV420: return compact_tail_yuv420(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.yuv, st);
-        case YUV420P10: return compact_tail_yuv420p10(t, (const uint16_t*)e.x_u8, (uint16_t*)e.y_u8, N, H, W, d->upscale, e.yuv, st);
-        case YUV420_SCALED:
-        case YUV420P10_SCALED:
-            return compact_tail_yuv420_scaled(t, e.x_u8, e.y_u8, N, H, W, d->upscale, e.kind == YUV420_SCALED ? 8 : 10, e.sc.idx_y, e.sc.w_y,
-                                              e.sc.idx_x, e.sc.w_x, e.yuv, &geom, st);
+    const int s = d->upscale;
+    switch (e.format) {
+        case END_F32: return compact_tail(t, (const float*)e.x, (float*)e.y, N, H, W, s, st);
+        case END_RGB8:
+            if (!e.scaled) return compact_tail_u8(t, (const uint8_t*)e.x, (uint8_t*)e.y, N, H, W, s, st);
+            return compact_tail_u8_scaled(t, (const uint8_t*)e.x, (uint8_t*)e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, &geom, st);
+        case END_YUV:
+            if (!e.scaled) return compact_tail_yuv(t, e.x, e.y, N, H, W, s, e.yuv, st);
+            return compact_tail_yuv420_scaled(t, e.x, e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, e.yuv, &geom, st);
     }
     return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
-}
-
-}  // namespace
-
-int compact_forward(const ResrCompactDesc* d, const float* x, const float* params, const void* packed, void* workspace,
-                    size_t workspace_bytes, float* y, hipStream_t st) {
-    const Ends e{F32_NCHW, x, y, nullptr, nullptr, {}, nullptr};
-    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward");
-}
-
-int compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
-                       size_t workspace_bytes, uint8_t* y, hipStream_t st) {
-    const Ends e{U8_HWC, nullptr, nullptr, x, y, {}, nullptr};
-    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_u8");
-}
-
-int compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
-                           size_t workspace_bytes, uint8_t* y, const ResrYuvDesc* yuv, hipStream_t st) {
-    if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420: null argument");
-    const Ends e{YUV420, nullptr, nullptr, x, y, {}, yuv};
-    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420");
-}
-
-int compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x, const float* params, const void* packed, void* workspace,
-                              size_t workspace_bytes, uint16_t* y, const ResrYuvDesc* yuv, hipStream_t st) {
-    if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420p10: null argument");
-    const Ends e{YUV420P10, nullptr, nullptr, (const uint8_t*)x, (uint8_t*)y, {}, yuv};
-    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420p10");
-}
-
-int compact_forward_yuv420_scaled(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
-                                  size_t workspace_bytes, uint8_t* y, int oh, int ow, const int32_t* idx_y, const float* w_y, int taps_y,
-                                  const int32_t* idx_x, const float* w_x, int taps_x, const ResrYuvDesc* yuv, hipStream_t st) {
-    if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420_scaled: null argument");
-    const Ends e{YUV420_SCALED, nullptr, nullptr, x, y, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv};
-    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420_scaled");
-}
-
-int compact_forward_yuv420p10_scaled(const ResrCompactDesc* d, const uint16_t* x, const float* params, const void* packed, void* workspace,
-                                     size_t workspace_bytes, uint16_t* y, int oh, int ow, const int32_t* idx_y, const float* w_y,
-                                     int taps_y, const int32_t* idx_x, const float* w_x, int taps_x, const ResrYuvDesc* yuv, hipStream_t st) {
-    if (!yuv) return fail(RESR_ERR_ARG, "compact_forward_yuv420p10_scaled: null argument");
-    const Ends e{YUV420P10_SCALED, nullptr, nullptr, (const uint8_t*)x, (uint8_t*)y, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv};
-    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_yuv420p10_scaled");
-}
-
-int compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x, const float* params, const void* packed, void* workspace,
-                              size_t workspace_bytes, uint8_t* y, int oh, int ow, const int32_t* idx_y, const float* w_y, int taps_y,
-                              const int32_t* idx_x, const float* w_x, int taps_x, hipStream_t st) {
-    const Ends e{U8_HWC_SCALED, nullptr, nullptr, x, y, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, nullptr};
-    return compact_run(d, e, params, packed, workspace, workspace_bytes, st, "compact_forward_u8_scaled");
 }
 
 }  // namespace resr

@@ -27,6 +27,23 @@ template <int BITS> constexpr int kTop = (1 << BITS) - 1;
 template <int BITS> constexpr int kLumaOff = 16 << (BITS - 8);
 template <int BITS> constexpr int kChromaOff = 128 << (BITS - 8);
 
+// Bits per sample of a layout: 8, 10, or 0 for a value that is no RESR_YUV_*
+constexpr int yuv_bits(int layout) {
+    return layout == RESR_YUV_I420 || layout == RESR_YUV_NV12 ? 8 : layout == RESR_YUV_I420P10 || layout == RESR_YUV_P010 ? 10 : 0;
+}
+
+// A runtime layout as a compile-time one, as with_scale: f(std::integral_constant<int, layout>()); false for any other value.
+template <typename F>
+inline bool with_yuv_layout(int layout, F&& f) {
+    switch (layout) {
+        case RESR_YUV_I420: f(std::integral_constant<int, RESR_YUV_I420>()); return true;
+        case RESR_YUV_NV12: f(std::integral_constant<int, RESR_YUV_NV12>()); return true;
+        case RESR_YUV_I420P10: f(std::integral_constant<int, RESR_YUV_I420P10>()); return true;
+        case RESR_YUV_P010: f(std::integral_constant<int, RESR_YUV_P010>()); return true;
+        default: return false;
+    }
+}
+
 // NV12 and P010 hold one interleaved CbCr plane, I420 and I420P10 a Cb and a Cr plane
 __device__ __forceinline__ constexpr bool semi_planar(int layout) { return layout == RESR_YUV_NV12 || layout == RESR_YUV_P010; }
 

@@ -9,6 +9,9 @@ bit: a frame enters as `u8 / 255.0f`, runs through the model in the model's arit
     upscale_u8(model, frames)  uint8 [N,H,W,3] -> uint8 [N,sH,sW,3]        any model, any frame size
     FrameStream(model, depth)  host ndarray in -> host ndarray out, `depth` frames in flight
     output_size(h, w, s, o)    the size of a frame upscaled with `outscale=o`: the one place that formula lives
+    PIXEL_FORMATS              one record per pixel format name (layout id, bits, packing, dtypes): the table `YUV_LAYOUTS`,
+                               `YUV10_LAYOUTS` and `FrameStream.PIX_FMTS` are read from, and the 8- and 10-bit functions below share
+                               their bodies through
 
 `upscale_u8` is the one definition of the path: a model with a fused entry (`SRVGGNetCompact.forward_u8`) runs it when the frame
 fits one call; every other case (the RRDB `Generator`, frames the tiler has to cut) is `to_u8(super_resolve(model, from_u8(f)))`.
@@ -69,7 +72,7 @@ from __future__ import annotations
 import collections
 import functools
 import math
-from typing import Deque, Iterable, Iterator, List, Optional, Tuple
+from typing import Deque, Iterable, Iterator, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -80,8 +83,32 @@ __all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream", "output_size", "chec
            "rgb_to_yuv420_np", "yuv420_to_rgb", "rgb_to_yuv420", "upscale_yuv420", "yuv420p10_tables", "yuv420p10_to_rgb_np",
            "rgb_to_yuv420p10_np", "from_yuv420p10", "to_yuv420p10", "upscale_yuv420p10"]
 
-YUV_LAYOUTS = {"i420": _lib.YUV_I420, "nv12": _lib.YUV_NV12}
-YUV10_LAYOUTS = {"i420p10": _lib.YUV_I420P10, "p010": _lib.YUV_P010}
+class PixelFormat(NamedTuple):
+    """One row of `PIXEL_FORMATS`: everything the frame path knows about a pixel format by name.  `layout`: ResrYuvDesc.layout of
+    include/resr.h (None: "rgb24", HWC bytes, no descriptor); `bits` per sample; `semi_planar`: one interleaved CbCr plane instead of
+    a Cb and a Cr plane; `high_bits`: the sample sits in the high bits of its 16-bit word ("p010")."""
+    layout: Optional[int]
+    bits: int
+    semi_planar: bool
+    high_bits: bool
+    np_dtype: np.dtype
+    torch_dtype: torch.dtype
+
+    @property
+    def top(self) -> int:
+        """The highest level of a sample: 255 or 1023."""
+        return (1 << self.bits) - 1
+
+
+_U8, _U16 = (np.dtype(np.uint8), torch.uint8), (np.dtype(np.uint16), torch.uint16)
+PIXEL_FORMATS = {"rgb24": PixelFormat(None, 8, False, False, *_U8),
+                 "i420": PixelFormat(_lib.YUV_I420, 8, False, False, *_U8),
+                 "nv12": PixelFormat(_lib.YUV_NV12, 8, True, False, *_U8),
+                 "i420p10": PixelFormat(_lib.YUV_I420P10, 10, False, False, *_U16),
+                 "p010": PixelFormat(_lib.YUV_P010, 10, True, True, *_U16)}
+YUV_LAYOUTS = {name: f.layout for name, f in PIXEL_FORMATS.items() if f.layout is not None and f.bits == 8}
+YUV10_LAYOUTS = {name: f.layout for name, f in PIXEL_FORMATS.items() if f.layout is not None and f.bits == 10}
+_YUV_BY_BITS = {8: (YUV_LAYOUTS, *_U8), 10: (YUV10_LAYOUTS, *_U16)}            # per depth: its layout names, numpy and torch dtype
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}          # (Kr, Kb); Kg = 1 - Kr - Kb
 
 
@@ -167,12 +194,41 @@ def upscale_u8(model, frames: torch.Tensor, halo: Optional[int] = None, outscale
     return resize_with_plan(tiling.super_resolve(model, from_u8(frames), halo), plan, u8=True)
 
 
-# ---- YUV 4:2:0 ----------------------------------------------------------------------------------------------------------------
-def _yuv_names(layout: str, matrix: str, what: str) -> None:
-    if layout not in YUV_LAYOUTS:
-        raise ValueError(f"{what}: layout must be one of {sorted(YUV_LAYOUTS)}, got {layout!r}")
+# ---- YUV 4:2:0, 8 and 10 bits: one body each, the public names of a depth pick their rows of PIXEL_FORMATS ------------------------
+def _check_matrix(matrix: str, what: str) -> None:
     if matrix not in YUV_MATRICES:
         raise ValueError(f"{what}: matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}")
+
+
+def _yuv_format(layout: str, matrix: str, what: str, bits: int) -> PixelFormat:
+    """The row of a 4:2:0 layout of this depth; ValueError for any other name (the other depth's included) or an unknown matrix."""
+    names = _YUV_BY_BITS[bits][0]
+    if layout not in names:
+        raise ValueError(f"{what}: layout must be one of {sorted(names)}, got {layout!r}")
+    _check_matrix(matrix, what)
+    return PIXEL_FORMATS[layout]
+
+
+def _yuv_name(bits: int) -> str:
+    """What the functions and C entries of a depth are called after."""
+    return "yuv420" if bits == 8 else f"yuv420p{bits}"
+
+
+def _tables(bits: int, matrix: str, quantised: bool, what: str) -> Tuple[np.ndarray, np.ndarray]:
+    _check_matrix(matrix, what)
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    top, ys, cs = float((1 << bits) - 1), float(219 << (bits - 8)), float(112 << (bits - 8))      # 255, 219, 112 / 1023, 876, 448
+    f = np.array([[ys * kr, ys * kg, ys * kb],
+                  [-cs * kr / (1 - kb), -cs * kg / (1 - kb), cs],
+                  [cs, -cs * kg / (1 - kr), -cs * kb / (1 - kr)]], dtype=np.float64) / top
+    a, c = top / ys, top / (2 * cs)
+    i = np.array([[a, 0.0, c * 2 * (1 - kr)],
+                  [a, -c * 2 * (1 - kb) * kb / kg, -c * 2 * (1 - kr) * kr / kg],
+                  [a, c * 2 * (1 - kb), 0.0]], dtype=np.float64)
+    if not quantised:
+        return f, i
+    return np.rint(f * 65536).astype(np.int32), np.rint(i * 65536).astype(np.int32)
 
 
 def yuv420_tables(matrix: str = "bt601", quantised: bool = True) -> Tuple[np.ndarray, np.ndarray]:
@@ -180,19 +236,14 @@ def yuv420_tables(matrix: str = "bt601", quantised: bool = True) -> Tuple[np.nda
     I (rows R, G, B over Y - 16, Cb - 128, Cr - 128) are computed in float64 from the matrix' (Kr, Kb); FQ = rint(F * 65536),
     IQ = rint(I * 65536).  `quantised=False` returns the float64 (F, I) themselves (bt601: F * 255 and I / 255 are the tables the
     reference prints in `rgb2ycbcr` / `ycbcr2rgb`)."""
-    _yuv_names("i420", matrix, "yuv420_tables")
-    kr, kb = YUV_MATRICES[matrix]
-    kg = 1.0 - kr - kb
-    f = np.array([[219 * kr, 219 * kg, 219 * kb],
-                  [-112 * kr / (1 - kb), -112 * kg / (1 - kb), 112.0],
-                  [112.0, -112 * kg / (1 - kr), -112 * kb / (1 - kr)]], dtype=np.float64) / 255.0
-    a, c = 255.0 / 219.0, 255.0 / 224.0
-    i = np.array([[a, 0.0, c * 2 * (1 - kr)],
-                  [a, -c * 2 * (1 - kb) * kb / kg, -c * 2 * (1 - kr) * kr / kg],
-                  [a, c * 2 * (1 - kb), 0.0]], dtype=np.float64)
-    if not quantised:
-        return f, i
-    return np.rint(f * 65536).astype(np.int32), np.rint(i * 65536).astype(np.int32)
+    return _tables(8, matrix, quantised, "yuv420_tables")
+
+
+def yuv420p10_tables(matrix: str = "bt601", quantised: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+    """`yuv420_tables` for 10-bit samples: the same (Kr, Kb), the studio constants 876 / 448 / 1023 in place of 219 / 112 / 255
+    (F per 10-bit level; I over Y - 64, Cb - 512, Cr - 512 with a = 1023 / 876, c = 1023 / 896).  (FQ, IQ) int32 [3,3], Q16, or
+    with `quantised=False` the float64 (F, I)."""
+    return _tables(10, matrix, quantised, "yuv420p10_tables")
 
 
 def _yuv_hw(shape) -> Optional[Tuple[int, int]]:
@@ -202,36 +253,57 @@ def _yuv_hw(shape) -> Optional[Tuple[int, int]]:
     return shape[-2] // 3 * 2, shape[-1]
 
 
-def _yuv_geometry(shape, what: str) -> Tuple[int, int]:
-    hw = _yuv_hw(shape)
+def _yuv_to_rgb_np(frames: np.ndarray, layout: str, matrix: str, what: str, bits: int) -> np.ndarray:
+    fmt = _yuv_format(layout, matrix, what, bits)
+    frames = np.asarray(frames)
+    if frames.dtype != fmt.np_dtype:
+        raise ValueError(f"{what}: expected {fmt.np_dtype}, got {frames.dtype}")
+    hw = _yuv_hw(frames.shape)
     if hw is None:
-        raise ValueError(f"{what}: a 4:2:0 frame is [3H/2, W] with H and W even (rows a multiple of 3), got {tuple(shape)}")
-    return hw
+        raise ValueError(f"{what}: a 4:2:0 frame is [3H/2, W] with H and W even (rows a multiple of 3), got {tuple(frames.shape)}")
+    (h, w), lead = hw, frames.shape[:-2]
+    v = frames.astype(np.int32)
+    v = v >> 6 if fmt.high_bits else v & fmt.top
+    y = v[..., :h, :] - (16 << (bits - 8))
+    chroma = v[..., h:, :].reshape(lead + (-1,))
+    if fmt.semi_planar:
+        pairs = chroma.reshape(lead + (h // 2, w // 2, 2))
+        cb, cr = pairs[..., 0], pairs[..., 1]
+    else:
+        planes = chroma.reshape(lead + (2, h // 2, w // 2))
+        cb, cr = planes[..., 0, :, :], planes[..., 1, :, :]
+    cb = np.repeat(np.repeat(cb - (128 << (bits - 8)), 2, axis=-2), 2, axis=-1)
+    cr = np.repeat(np.repeat(cr - (128 << (bits - 8)), 2, axis=-2), 2, axis=-1)
+    iq = _tables(bits, matrix, True, what)[1]
+    rgb = np.stack([(int(iq[c, 0]) * y + int(iq[c, 1]) * cb + int(iq[c, 2]) * cr + 32768) >> 16 for c in range(3)], axis=-1)
+    return np.clip(rgb, 0, fmt.top).astype(fmt.np_dtype)
+
+
+def _rgb_to_yuv_np(rgb: np.ndarray, layout: str, matrix: str, what: str, bits: int) -> np.ndarray:
+    fmt = _yuv_format(layout, matrix, what, bits)
+    rgb = np.asarray(rgb)
+    if rgb.dtype != fmt.np_dtype or rgb.ndim < 3 or rgb.shape[-1] != 3 or rgb.shape[-3] < 2 or rgb.shape[-3] % 2 or rgb.shape[-2] < 2 or rgb.shape[-2] % 2:
+        raise ValueError(f"{what}: expected {fmt.np_dtype} [..., H, W, 3] with H and W even, got {rgb.dtype} {rgb.shape}")
+    if bits > 8 and rgb.size and int(rgb.max()) > fmt.top:
+        raise ValueError(f"{what}: a {bits}-bit level is at most {fmt.top}, got {int(rgb.max())}")
+    lead, (h, w) = rgb.shape[:-3], rgb.shape[-3:-1]
+    fq = _tables(bits, matrix, True, what)[0].astype(np.int32)
+    v = rgb.astype(np.int32)
+    y = ((v * fq[0]).sum(-1) + ((16 << (bits - 8)) << 16) + 32768) >> 16
+    s = v.reshape(lead + (h // 2, 2, w // 2, 2, 3)).sum(axis=(-4, -2))
+    cb = ((s * fq[1]).sum(-1) + ((128 << (bits - 8)) << 18) + (1 << 17)) >> 18
+    cr = ((s * fq[2]).sum(-1) + ((128 << (bits - 8)) << 18) + (1 << 17)) >> 18
+    chroma = np.stack([cb, cr], axis=-1) if fmt.semi_planar else np.stack([cb, cr], axis=-3)
+    out = np.concatenate([y.reshape(lead + (h * w,)), chroma.reshape(lead + (h * w // 2,))], axis=-1)
+    out = out << 6 if fmt.high_bits else out
+    return out.reshape(lead + (h * 3 // 2, w)).astype(fmt.np_dtype)
 
 
 def yuv420_to_rgb_np(frames: np.ndarray, layout: str = "i420", matrix: str = "bt601") -> np.ndarray:
     """THE DEFINITION (host, numpy): uint8 [..., 3H/2, W] -> uint8 [..., H, W, 3].  Pixel (y, x) takes Y[y,x], Cb[y//2,x//2],
     Cr[y//2,x//2]; rgb[c] = clamp((IQ[c] . (Y - 16, Cb - 128, Cr - 128) + 32768) >> 16, 0, 255), int32, >> = floor.  Every byte
     value is legal input."""
-    _yuv_names(layout, matrix, "yuv420_to_rgb_np")
-    frames = np.asarray(frames)
-    if frames.dtype != np.uint8:
-        raise ValueError(f"yuv420_to_rgb_np: expected uint8, got {frames.dtype}")
-    h, w = _yuv_geometry(frames.shape, "yuv420_to_rgb_np")
-    lead = frames.shape[:-2]
-    y = frames[..., :h, :].astype(np.int32) - 16
-    chroma = frames[..., h:, :].reshape(lead + (-1,))
-    if layout == "nv12":
-        pairs = chroma.reshape(lead + (h // 2, w // 2, 2))
-        cb, cr = pairs[..., 0], pairs[..., 1]
-    else:
-        planes = chroma.reshape(lead + (2, h // 2, w // 2))
-        cb, cr = planes[..., 0, :, :], planes[..., 1, :, :]
-    cb = np.repeat(np.repeat(cb.astype(np.int32) - 128, 2, axis=-2), 2, axis=-1)
-    cr = np.repeat(np.repeat(cr.astype(np.int32) - 128, 2, axis=-2), 2, axis=-1)
-    iq = yuv420_tables(matrix)[1]
-    rgb = np.stack([(int(iq[c, 0]) * y + int(iq[c, 1]) * cb + int(iq[c, 2]) * cr + 32768) >> 16 for c in range(3)], axis=-1)
-    return np.clip(rgb, 0, 255).astype(np.uint8)
+    return _yuv_to_rgb_np(frames, layout, matrix, "yuv420_to_rgb_np", 8)
 
 
 def rgb_to_yuv420_np(rgb: np.ndarray, layout: str = "i420", matrix: str = "bt601") -> np.ndarray:
@@ -239,40 +311,62 @@ def rgb_to_yuv420_np(rgb: np.ndarray, layout: str = "i420", matrix: str = "bt601
     32768) >> 16 per pixel; Cb = (FQ[1] . S + (128 << 18) + (1 << 17)) >> 18 per 2x2 block, S the sum of its four (R, G, B), Cr
     likewise with FQ[2]: a centre-sited box average of the unrounded chroma.  No clamp is needed: over all RGB triples the
     outputs lie in Y 16..235, Cb / Cr 16..240."""
-    _yuv_names(layout, matrix, "rgb_to_yuv420_np")
-    rgb = np.asarray(rgb)
-    if rgb.dtype != np.uint8 or rgb.ndim < 3 or rgb.shape[-1] != 3 or rgb.shape[-3] < 2 or rgb.shape[-3] % 2 or rgb.shape[-2] < 2 or rgb.shape[-2] % 2:
-        raise ValueError(f"rgb_to_yuv420_np: expected uint8 [..., H, W, 3] with H and W even, got {rgb.dtype} {rgb.shape}")
-    lead, (h, w) = rgb.shape[:-3], rgb.shape[-3:-1]
-    fq = yuv420_tables(matrix)[0].astype(np.int32)
-    v = rgb.astype(np.int32)
-    y = ((v * fq[0]).sum(-1) + (16 << 16) + 32768) >> 16
-    s = v.reshape(lead + (h // 2, 2, w // 2, 2, 3)).sum(axis=(-4, -2))
-    cb = ((s * fq[1]).sum(-1) + (128 << 18) + (1 << 17)) >> 18
-    cr = ((s * fq[2]).sum(-1) + (128 << 18) + (1 << 17)) >> 18
-    chroma = np.stack([cb, cr], axis=-1) if layout == "nv12" else np.stack([cb, cr], axis=-3)
-    out = np.concatenate([y.reshape(lead + (h * w,)), chroma.reshape(lead + (h * w // 2,))], axis=-1)
-    return out.reshape(lead + (h * 3 // 2, w)).astype(np.uint8)
+    return _rgb_to_yuv_np(rgb, layout, matrix, "rgb_to_yuv420_np", 8)
+
+
+def yuv420p10_to_rgb_np(frames: np.ndarray, layout: str = "i420p10", matrix: str = "bt601") -> np.ndarray:
+    """THE DEFINITION (host, numpy): uint16 [..., 3H/2, W] -> uint16 [..., H, W, 3], levels 0..1023.  A sample is `word & 1023`
+    ("i420p10") or `word >> 6` ("p010"); pixel (y, x) takes Y[y,x], Cb[y//2,x//2], Cr[y//2,x//2]; rgb10[c] = clamp((IQ[c] . (Y - 64,
+    Cb - 512, Cr - 512) + 32768) >> 16, 0, 1023), int32, >> = floor.  Every 16-bit word is legal input."""
+    return _yuv_to_rgb_np(frames, layout, matrix, "yuv420p10_to_rgb_np", 10)
+
+
+def rgb_to_yuv420p10_np(rgb: np.ndarray, layout: str = "i420p10", matrix: str = "bt601") -> np.ndarray:
+    """THE DEFINITION (host, numpy): uint16 [..., H, W, 3] of levels 0..1023 (H, W even; a larger value is a ValueError) -> uint16
+    [..., 3H/2, W].  Y = (FQ[0] . rgb10 + (64 << 16) + 32768) >> 16 per pixel; Cb = (FQ[1] . S + (512 << 18) + (1 << 17)) >> 18 per
+    2x2 block, S the sum of its four (R, G, B), Cr likewise with FQ[2].  No clamp is needed: the outputs lie in Y 64..940, Cb / Cr
+    64..960, and the largest accumulator is 251,789,200.  "i420p10" stores the sample (high 6 bits zero), "p010" `sample << 6`."""
+    return _rgb_to_yuv_np(rgb, layout, matrix, "rgb_to_yuv420p10_np", 10)
 
 
 @functools.lru_cache(maxsize=None)
+def _desc(bits: int, layout: str, matrix: str) -> _lib.YuvDesc:
+    what = "yuv_desc" if bits == 8 else "yuv10_desc"
+    fmt = _yuv_format(layout, matrix, what, bits)
+    fq, iq = _tables(bits, matrix, True, what)
+    i9 = _lib.C.c_int32 * 9
+    return _lib.YuvDesc(fmt.layout, i9(*[int(v) for v in fq.reshape(-1)]), i9(*[int(v) for v in iq.reshape(-1)]))
+
+
 def yuv_desc(layout: str, matrix: str) -> _lib.YuvDesc:
     """The ResrYuvDesc of include/resr.h for these names (cached: the tables are a pure function of them)."""
-    _yuv_names(layout, matrix, "yuv_desc")
-    fq, iq = yuv420_tables(matrix)
-    i9 = _lib.C.c_int32 * 9
-    return _lib.YuvDesc(YUV_LAYOUTS[layout], i9(*[int(v) for v in fq.reshape(-1)]), i9(*[int(v) for v in iq.reshape(-1)]))
+    return _desc(8, layout, matrix)
+
+
+def yuv10_desc(layout: str, matrix: str) -> _lib.YuvDesc:
+    """`yuv_desc` for the 10-bit entries: a 10-bit layout and the tables of `yuv420p10_tables`."""
+    return _desc(10, layout, matrix)
+
+
+def _check_yuv(frames: torch.Tensor, what: str, bits: int) -> Tuple[int, int, int]:
+    _, np_dtype, torch_dtype = _YUV_BY_BITS[bits]
+    _lib.require_cuda(frames, what)
+    hw = _yuv_hw(frames.shape) if frames.dtype == torch_dtype and frames.dim() == 3 and frames.shape[0] >= 1 else None
+    if hw is None:
+        raise RuntimeError(f"{what}: expected a {np_dtype} [N,3H/2,W] tensor with H and W even, got {frames.dtype} {tuple(frames.shape)}")
+    if not frames.is_contiguous():
+        raise RuntimeError(f"{what}: frames must be contiguous (planes one after the other, as a video decoder leaves them)")
+    return (frames.shape[0],) + hw
 
 
 def check_yuv420(frames: torch.Tensor, what: str) -> Tuple[int, int, int]:
     """(n, H, W) of a uint8 [N,3H/2,W] device tensor; RuntimeError for anything else."""
-    _lib.require_cuda(frames, what)
-    hw = _yuv_hw(frames.shape) if frames.dtype == torch.uint8 and frames.dim() == 3 and frames.shape[0] >= 1 else None
-    if hw is None:
-        raise RuntimeError(f"{what}: expected a uint8 [N,3H/2,W] tensor with H and W even, got {frames.dtype} {tuple(frames.shape)}")
-    if not frames.is_contiguous():
-        raise RuntimeError(f"{what}: frames must be contiguous (planes one after the other, as a video decoder leaves them)")
-    return (frames.shape[0],) + hw
+    return _check_yuv(frames, what, 8)
+
+
+def check_yuv420p10(frames: torch.Tensor, what: str) -> Tuple[int, int, int]:
+    """(n, H, W) of a uint16 [N,3H/2,W] device tensor; RuntimeError for anything else."""
+    return _check_yuv(frames, what, 10)
 
 
 @torch.no_grad()
@@ -298,143 +392,6 @@ def rgb_to_yuv420(rgb: torch.Tensor, layout: str = "i420", matrix: str = "bt601"
     _lib.check(_lib.lib().resr_rgb_to_yuv420(_lib.ptr(rgb), _lib.ptr(out), n, h, w, _lib.C.byref(desc), _lib.stream_ptr(rgb)),
                "resr_rgb_to_yuv420")
     return out
-
-
-def _fused_yuv_outscale(model, method: str, n: int, h: int, w: int, plan, bits: int) -> bool:
-    """Does the fused YUV outscale call take this frame?  The model has the method, the frame fits one call, and the library finds a
-    tile of even height and width within the resize kernel's LDS (`resr_compact_yuv420_scaled_fits`: no device work)."""
-    if not hasattr(model, method) or not tiling.fits_whole(model, n, h, w):
-        return False
-    return bool(_lib.lib().resr_compact_yuv420_scaled_fits(h, w, model.upscale_factor, plan.out_h, plan.out_w, plan.taps_y, plan.taps_x, bits))
-
-
-def yuv420_output_size(h: int, w: int, s: int, outscale, what: str) -> Tuple[int, int]:
-    """`output_size`, which for a 4:2:0 result must be even both ways: ValueError otherwise (before any launch)."""
-    out_h, out_w = output_size(h, w, s, outscale)
-    if out_h % 2 or out_w % 2:
-        raise ValueError(f"{what}: outscale={outscale!r} turns {h}x{w} into {out_h}x{out_w}; a 4:2:0 frame needs an even height and width")
-    return out_h, out_w
-
-
-@torch.no_grad()
-def upscale_yuv420(model, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601", halo: Optional[int] = None,
-                   outscale: Optional[float] = None, plan=None) -> torch.Tensor:
-    """uint8 [N,3H/2,W] on the model's device -> uint8 [N,3sH/2,sW], same layout: bit for bit
-    `rgb_to_yuv420_np(upscale_u8(model, yuv420_to_rgb_np(frames)))` (module docstring).  The one place that chooses between the
-    fused call and the composition, as `upscale_u8` is for RGB; `halo`, `outscale` and `plan` are `upscale_u8`'s.  With `outscale`
-    the result is [N, 3 out_h / 2, out_w] for `output_size(H, W, s, outscale)`; an odd out_h or out_w is a ValueError before any
-    launch."""
-    yuv_desc(layout, matrix)
-    n, h, w = check_yuv420(frames, "upscale_yuv420")
-    s = model.upscale_factor
-    o = check_outscale(outscale, s, "upscale_yuv420")
-    if o is None and hasattr(model, "forward_yuv420") and tiling.fits_whole(model, n, h, w):
-        return model.forward_yuv420(frames, layout, matrix)
-    if o is not None:
-        yuv420_output_size(h, w, s, o, "upscale_yuv420")
-        plan = _resize_plan(h, w, s, o, frames.device, plan)              # ValueError before any launch, as in upscale_u8
-        if _fused_yuv_outscale(model, "forward_yuv420", n, h, w, plan, 8):
-            return model.forward_yuv420(frames, layout, matrix, outscale=o, plan=plan)
-    rgb = upscale_u8(model, yuv420_to_rgb(frames, layout, matrix), halo, outscale=o, plan=plan)
-    return rgb_to_yuv420(rgb, layout, matrix)
-
-
-# ---- 10-bit YUV 4:2:0 -----------------------------------------------------------------------------------------------------------
-def _yuv10_names(layout: str, matrix: str, what: str) -> None:
-    if layout not in YUV10_LAYOUTS:
-        raise ValueError(f"{what}: layout must be one of {sorted(YUV10_LAYOUTS)}, got {layout!r}")
-    if matrix not in YUV_MATRICES:
-        raise ValueError(f"{what}: matrix must be one of {sorted(YUV_MATRICES)}, got {matrix!r}")
-
-
-def yuv420p10_tables(matrix: str = "bt601", quantised: bool = True) -> Tuple[np.ndarray, np.ndarray]:
-    """`yuv420_tables` for 10-bit samples: the same (Kr, Kb), the studio constants 876 / 448 / 1023 in place of 219 / 112 / 255
-    (F per 10-bit level; I over Y - 64, Cb - 512, Cr - 512 with a = 1023 / 876, c = 1023 / 896).  (FQ, IQ) int32 [3,3], Q16, or
-    with `quantised=False` the float64 (F, I)."""
-    _yuv_names("i420", matrix, "yuv420p10_tables")
-    kr, kb = YUV_MATRICES[matrix]
-    kg = 1.0 - kr - kb
-    f = np.array([[876 * kr, 876 * kg, 876 * kb],
-                  [-448 * kr / (1 - kb), -448 * kg / (1 - kb), 448.0],
-                  [448.0, -448 * kg / (1 - kr), -448 * kb / (1 - kr)]], dtype=np.float64) / 1023.0
-    a, c = 1023.0 / 876.0, 1023.0 / 896.0
-    i = np.array([[a, 0.0, c * 2 * (1 - kr)],
-                  [a, -c * 2 * (1 - kb) * kb / kg, -c * 2 * (1 - kr) * kr / kg],
-                  [a, c * 2 * (1 - kb), 0.0]], dtype=np.float64)
-    if not quantised:
-        return f, i
-    return np.rint(f * 65536).astype(np.int32), np.rint(i * 65536).astype(np.int32)
-
-
-def yuv420p10_to_rgb_np(frames: np.ndarray, layout: str = "i420p10", matrix: str = "bt601") -> np.ndarray:
-    """THE DEFINITION (host, numpy): uint16 [..., 3H/2, W] -> uint16 [..., H, W, 3], levels 0..1023.  A sample is `word & 1023`
-    ("i420p10") or `word >> 6` ("p010"); pixel (y, x) takes Y[y,x], Cb[y//2,x//2], Cr[y//2,x//2]; rgb10[c] = clamp((IQ[c] . (Y - 64,
-    Cb - 512, Cr - 512) + 32768) >> 16, 0, 1023), int32, >> = floor.  Every 16-bit word is legal input."""
-    _yuv10_names(layout, matrix, "yuv420p10_to_rgb_np")
-    frames = np.asarray(frames)
-    if frames.dtype != np.uint16:
-        raise ValueError(f"yuv420p10_to_rgb_np: expected uint16, got {frames.dtype}")
-    h, w = _yuv_geometry(frames.shape, "yuv420p10_to_rgb_np")
-    lead = frames.shape[:-2]
-    v = frames.astype(np.int32)
-    v = v >> 6 if layout == "p010" else v & 1023
-    y = v[..., :h, :] - 64
-    chroma = v[..., h:, :].reshape(lead + (-1,))
-    if layout == "p010":
-        pairs = chroma.reshape(lead + (h // 2, w // 2, 2))
-        cb, cr = pairs[..., 0], pairs[..., 1]
-    else:
-        planes = chroma.reshape(lead + (2, h // 2, w // 2))
-        cb, cr = planes[..., 0, :, :], planes[..., 1, :, :]
-    cb = np.repeat(np.repeat(cb - 512, 2, axis=-2), 2, axis=-1)
-    cr = np.repeat(np.repeat(cr - 512, 2, axis=-2), 2, axis=-1)
-    iq = yuv420p10_tables(matrix)[1]
-    rgb = np.stack([(int(iq[c, 0]) * y + int(iq[c, 1]) * cb + int(iq[c, 2]) * cr + 32768) >> 16 for c in range(3)], axis=-1)
-    return np.clip(rgb, 0, 1023).astype(np.uint16)
-
-
-def rgb_to_yuv420p10_np(rgb: np.ndarray, layout: str = "i420p10", matrix: str = "bt601") -> np.ndarray:
-    """THE DEFINITION (host, numpy): uint16 [..., H, W, 3] of levels 0..1023 (H, W even; a larger value is a ValueError) -> uint16
-    [..., 3H/2, W].  Y = (FQ[0] . rgb10 + (64 << 16) + 32768) >> 16 per pixel; Cb = (FQ[1] . S + (512 << 18) + (1 << 17)) >> 18 per
-    2x2 block, S the sum of its four (R, G, B), Cr likewise with FQ[2].  No clamp is needed: the outputs lie in Y 64..940, Cb / Cr
-    64..960, and the largest accumulator is 251,789,200.  "i420p10" stores the sample (high 6 bits zero), "p010" `sample << 6`."""
-    _yuv10_names(layout, matrix, "rgb_to_yuv420p10_np")
-    rgb = np.asarray(rgb)
-    if rgb.dtype != np.uint16 or rgb.ndim < 3 or rgb.shape[-1] != 3 or rgb.shape[-3] < 2 or rgb.shape[-3] % 2 or rgb.shape[-2] < 2 or rgb.shape[-2] % 2:
-        raise ValueError(f"rgb_to_yuv420p10_np: expected uint16 [..., H, W, 3] with H and W even, got {rgb.dtype} {rgb.shape}")
-    if rgb.size and int(rgb.max()) > 1023:
-        raise ValueError(f"rgb_to_yuv420p10_np: a 10-bit level is at most 1023, got {int(rgb.max())}")
-    lead, (h, w) = rgb.shape[:-3], rgb.shape[-3:-1]
-    fq = yuv420p10_tables(matrix)[0].astype(np.int32)
-    v = rgb.astype(np.int32)
-    y = ((v * fq[0]).sum(-1) + (64 << 16) + 32768) >> 16
-    s = v.reshape(lead + (h // 2, 2, w // 2, 2, 3)).sum(axis=(-4, -2))
-    cb = ((s * fq[1]).sum(-1) + (512 << 18) + (1 << 17)) >> 18
-    cr = ((s * fq[2]).sum(-1) + (512 << 18) + (1 << 17)) >> 18
-    chroma = np.stack([cb, cr], axis=-1) if layout == "p010" else np.stack([cb, cr], axis=-3)
-    out = np.concatenate([y.reshape(lead + (h * w,)), chroma.reshape(lead + (h * w // 2,))], axis=-1)
-    out = out << 6 if layout == "p010" else out
-    return out.reshape(lead + (h * 3 // 2, w)).astype(np.uint16)
-
-
-@functools.lru_cache(maxsize=None)
-def yuv10_desc(layout: str, matrix: str) -> _lib.YuvDesc:
-    """`yuv_desc` for the 10-bit entries: a 10-bit layout and the tables of `yuv420p10_tables`."""
-    _yuv10_names(layout, matrix, "yuv10_desc")
-    fq, iq = yuv420p10_tables(matrix)
-    i9 = _lib.C.c_int32 * 9
-    return _lib.YuvDesc(YUV10_LAYOUTS[layout], i9(*[int(v) for v in fq.reshape(-1)]), i9(*[int(v) for v in iq.reshape(-1)]))
-
-
-def check_yuv420p10(frames: torch.Tensor, what: str) -> Tuple[int, int, int]:
-    """(n, H, W) of a uint16 [N,3H/2,W] device tensor; RuntimeError for anything else."""
-    _lib.require_cuda(frames, what)
-    hw = _yuv_hw(frames.shape) if frames.dtype == torch.uint16 and frames.dim() == 3 and frames.shape[0] >= 1 else None
-    if hw is None:
-        raise RuntimeError(f"{what}: expected a uint16 [N,3H/2,W] tensor with H and W even, got {frames.dtype} {tuple(frames.shape)}")
-    if not frames.is_contiguous():
-        raise RuntimeError(f"{what}: frames must be contiguous (planes one after the other, as a video decoder leaves them)")
-    return (frames.shape[0],) + hw
 
 
 @torch.no_grad()
@@ -468,6 +425,51 @@ def to_yuv420p10(sr: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601
     return out
 
 
+def yuv420_output_size(h: int, w: int, s: int, outscale, what: str) -> Tuple[int, int]:
+    """`output_size`, which for a 4:2:0 result must be even both ways: ValueError otherwise (before any launch)."""
+    out_h, out_w = output_size(h, w, s, outscale)
+    if out_h % 2 or out_w % 2:
+        raise ValueError(f"{what}: outscale={outscale!r} turns {h}x{w} into {out_h}x{out_w}; a 4:2:0 frame needs an even height and width")
+    return out_h, out_w
+
+
+def _upscale_yuv(model, frames: torch.Tensor, layout: str, matrix: str, outscale, plan, bits: int, compose) -> torch.Tensor:
+    """What `upscale_yuv420` and `upscale_yuv420p10` share: the names, the geometry, `outscale` and the even-output rule, the plan, and
+    the choice of the model's fused call -- with `outscale` only where the library finds a tile of even height and width within the
+    resize kernel's LDS (`resr_compact_yuv420_scaled_fits`: no device work).  `compose(o, plan)`: the depth's own composition."""
+    what = "upscale_" + _yuv_name(bits)
+    _desc(bits, layout, matrix)
+    n, h, w = _check_yuv(frames, what, bits)
+    s = model.upscale_factor
+    o = check_outscale(outscale, s, what)
+    method = "forward_" + _yuv_name(bits)
+
+    def fused() -> bool:
+        return hasattr(model, method) and tiling.fits_whole(model, n, h, w)
+    if o is None and fused():
+        return getattr(model, method)(frames, layout, matrix)
+    if o is not None:
+        yuv420_output_size(h, w, s, o, what)
+        plan = _resize_plan(h, w, s, o, frames.device, plan)              # ValueError before any launch, as in upscale_u8
+        if fused() and _lib.lib().resr_compact_yuv420_scaled_fits(h, w, s, plan.out_h, plan.out_w, plan.taps_y, plan.taps_x, bits):
+            return getattr(model, method)(frames, layout, matrix, outscale=o, plan=plan)
+    return compose(o, plan)
+
+
+@torch.no_grad()
+def upscale_yuv420(model, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601", halo: Optional[int] = None,
+                   outscale: Optional[float] = None, plan=None) -> torch.Tensor:
+    """uint8 [N,3H/2,W] on the model's device -> uint8 [N,3sH/2,sW], same layout: bit for bit
+    `rgb_to_yuv420_np(upscale_u8(model, yuv420_to_rgb_np(frames)))` (module docstring).  The one place that chooses between the
+    fused call and the composition, as `upscale_u8` is for RGB; `halo`, `outscale` and `plan` are `upscale_u8`'s.  With `outscale`
+    the result is [N, 3 out_h / 2, out_w] for `output_size(H, W, s, outscale)`; an odd out_h or out_w is a ValueError before any
+    launch."""
+    def compose(o, plan):
+        rgb = upscale_u8(model, yuv420_to_rgb(frames, layout, matrix), halo, outscale=o, plan=plan)
+        return rgb_to_yuv420(rgb, layout, matrix)
+    return _upscale_yuv(model, frames, layout, matrix, outscale, plan, 8, compose)
+
+
 @torch.no_grad()
 def upscale_yuv420p10(model, frames: torch.Tensor, layout: str = "i420p10", matrix: str = "bt601", halo: Optional[int] = None,
                       outscale: Optional[float] = None, plan=None) -> torch.Tensor:
@@ -476,22 +478,13 @@ def upscale_yuv420p10(model, frames: torch.Tensor, layout: str = "i420p10", matr
     bits; `halo`, `outscale` and `plan` are `upscale_u8`'s.  With `outscale` the float frame is resized (`resize_with_plan`, fp32
     out) before it is quantised -- inside the fused call's last kernel, or as launches of its own where that call does not apply; an
     odd out_h or out_w is a ValueError before any launch."""
-    yuv10_desc(layout, matrix)
-    n, h, w = check_yuv420p10(frames, "upscale_yuv420p10")
-    s = model.upscale_factor
-    o = check_outscale(outscale, s, "upscale_yuv420p10")
-    if o is None and hasattr(model, "forward_yuv420p10") and tiling.fits_whole(model, n, h, w):
-        return model.forward_yuv420p10(frames, layout, matrix)
-    if o is not None:
-        yuv420_output_size(h, w, s, o, "upscale_yuv420p10")
-        plan = _resize_plan(h, w, s, o, frames.device, plan)              # ValueError before any launch, as in upscale_u8
-        if _fused_yuv_outscale(model, "forward_yuv420p10", n, h, w, plan, 10):
-            return model.forward_yuv420p10(frames, layout, matrix, outscale=o, plan=plan)
-    sr = tiling.super_resolve(model, from_yuv420p10(frames, layout, matrix), halo)
-    if o is not None:
-        from .imgproc import resize_with_plan
-        sr = resize_with_plan(sr, plan)
-    return to_yuv420p10(sr, layout, matrix)
+    def compose(o, plan):
+        sr = tiling.super_resolve(model, from_yuv420p10(frames, layout, matrix), halo)
+        if o is not None:
+            from .imgproc import resize_with_plan
+            sr = resize_with_plan(sr, plan)
+        return to_yuv420p10(sr, layout, matrix)
+    return _upscale_yuv(model, frames, layout, matrix, outscale, plan, 10, compose)
 
 
 class _Slot:
@@ -529,16 +522,16 @@ class FrameStream:
     `upscale_yuv420` of it, the slots are half the bytes, everything else is as above.  "i420p10" / "p010" (10-bit 4:2:0, module
     docstring): the same with uint16 ndarrays, each frame `upscale_yuv420p10` of it, the slots 3 bytes per pixel as for rgb24."""
 
-    PIX_FMTS = ("rgb24", "i420", "nv12", "i420p10", "p010")
+    PIX_FMTS = tuple(PIXEL_FORMATS)
 
     def __init__(self, model, depth: int = 2, outscale: Optional[float] = None, pix_fmt: str = "rgb24", matrix: str = "bt601") -> None:
         if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
             raise ValueError(f"FrameStream: depth must be an int >= 1, got {depth!r}")
         if pix_fmt not in self.PIX_FMTS:
             raise ValueError(f"FrameStream: pix_fmt must be one of {self.PIX_FMTS}, got {pix_fmt!r}")
-        _yuv_names("i420", matrix, "FrameStream")
+        _check_matrix(matrix, "FrameStream")
         self.pix_fmt, self.matrix = pix_fmt, matrix
-        self._fmt = _Rgb24 if pix_fmt == "rgb24" else _Yuv420p10(pix_fmt, matrix) if pix_fmt in YUV10_LAYOUTS else _Yuv420(pix_fmt, matrix)
+        self._fmt = _StreamFormat(pix_fmt, matrix)
         self.outscale = check_outscale(outscale, getattr(model, "upscale_factor", 0), "FrameStream")
         self._plan = None
         param = next(iter(model.parameters()), None)
@@ -555,21 +548,15 @@ class FrameStream:
 
     @staticmethod
     def check_frame(frame) -> None:
-        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3 or min(frame.shape) < 1:
-            got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
-            raise ValueError(f"FrameStream: expected an HxWx3 uint8 ndarray, got {got}")
+        _check_host_frame(frame, PIXEL_FORMATS["rgb24"])
 
     @staticmethod
     def check_frame_yuv420(frame) -> None:
-        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint8 or frame.ndim != 2 or _yuv_hw(frame.shape) is None:
-            got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
-            raise ValueError(f"FrameStream: expected a [3H/2, W] uint8 ndarray with H and W even (a 4:2:0 frame), got {got}")
+        _check_host_frame(frame, PIXEL_FORMATS["i420"])
 
     @staticmethod
     def check_frame_yuv420p10(frame) -> None:
-        if not isinstance(frame, np.ndarray) or frame.dtype != np.uint16 or frame.ndim != 2 or _yuv_hw(frame.shape) is None:
-            got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
-            raise ValueError(f"FrameStream: expected a [3H/2, W] uint16 ndarray with H and W even (a 10-bit 4:2:0 frame), got {got}")
+        _check_host_frame(frame, PIXEL_FORMATS["i420p10"])
 
     def __len__(self) -> int:
         """Results not yet taken."""
@@ -597,7 +584,7 @@ class FrameStream:
         in_shape, out_shape = self._fmt.shapes(h, w, s, self.outscale)     # an odd 4:2:0 result: ValueError before anything is allocated
         self._plan = _resize_plan(h, w, s, self.outscale, self.device)
         with torch.cuda.device(self.device):
-            self._slots = [_Slot(in_shape, out_shape, self.device, getattr(self._fmt, "dtype", torch.uint8)) for _ in range(self.depth)]
+            self._slots = [_Slot(in_shape, out_shape, self.device, self._fmt.dtype) for _ in range(self.depth)]
         self._shape, self._next = (h, w), 0
 
     def submit(self, frame: np.ndarray) -> None:
@@ -662,52 +649,40 @@ class FrameStream:
         self.close()
 
 
-class _Rgb24:
-    """What FrameStream asks of its pixel format: `size(frame)` checks a host frame and returns its (h, w); `shapes(h, w, s,
-    outscale)` the slots' (in_shape, out_shape), ValueError for a result the format cannot hold; `upscale(model, dev_in, outscale,
-    plan)` runs one slot on the device."""
-
-    @staticmethod
-    def size(frame):
-        FrameStream.check_frame(frame)
-        return frame.shape[:2]
-
-    @staticmethod
-    def shapes(h, w, s, outscale):
-        out_h, out_w = output_size(h, w, s, outscale)
-        return (h, w, 3), (out_h, out_w, 3)
-
-    @staticmethod
-    def upscale(model, dev_in, outscale, plan):
-        return upscale_u8(model, dev_in, outscale=outscale, plan=plan)
+def _check_host_frame(frame, fmt: PixelFormat) -> None:
+    """ValueError unless `frame` is a host frame of this format: HxWx3 bytes ("rgb24"), else [3H/2, W] words of the format's depth."""
+    rgb = fmt.layout is None
+    if isinstance(frame, np.ndarray) and frame.dtype == fmt.np_dtype:
+        if (frame.ndim == 3 and frame.shape[2] == 3 and min(frame.shape) >= 1) if rgb else (frame.ndim == 2 and _yuv_hw(frame.shape) is not None):
+            return
+    got = f"{frame.dtype} {frame.shape}" if isinstance(frame, np.ndarray) else type(frame).__name__
+    want = "an HxWx3 uint8 ndarray" if rgb else (f"a [3H/2, W] {fmt.np_dtype} ndarray with H and W even "
+                                                  f"(a {'10-bit ' if fmt.bits == 10 else ''}4:2:0 frame)")
+    raise ValueError(f"FrameStream: expected {want}, got {got}")
 
 
-class _Yuv420:
-    def __init__(self, layout: str, matrix: str) -> None:
-        self.layout, self.matrix = layout, matrix
+class _StreamFormat:
+    """What FrameStream asks of its pixel format, answered from its row of PIXEL_FORMATS: `dtype` of the slots; `size(frame)` checks
+    a host frame and returns its (h, w); `shapes(h, w, s, outscale)` the slots' (in_shape, out_shape), ValueError for a result the
+    format cannot hold; `upscale(model, dev_in, outscale, plan)` runs one slot on the device."""
 
-    @staticmethod
-    def size(frame):
-        FrameStream.check_frame_yuv420(frame)
-        return _yuv_hw(frame.shape)
+    def __init__(self, name: str, matrix: str) -> None:
+        self.name, self.matrix, self.fmt = name, matrix, PIXEL_FORMATS[name]
+        self.dtype, self.rgb = self.fmt.torch_dtype, self.fmt.layout is None
 
-    @staticmethod
-    def shapes(h, w, s, outscale):
+    def size(self, frame):
+        _check_host_frame(frame, self.fmt)
+        return frame.shape[:2] if self.rgb else _yuv_hw(frame.shape)
+
+    def shapes(self, h, w, s, outscale):
+        if self.rgb:
+            out_h, out_w = output_size(h, w, s, outscale)
+            return (h, w, 3), (out_h, out_w, 3)
         out_h, out_w = yuv420_output_size(h, w, s, outscale, "FrameStream")
         return (h * 3 // 2, w), (out_h * 3 // 2, out_w)
 
     def upscale(self, model, dev_in, outscale, plan):
-        return upscale_yuv420(model, dev_in, self.layout, self.matrix, outscale=outscale, plan=plan)
-
-
-class _Yuv420p10(_Yuv420):
-    """10-bit 4:2:0: the shapes of `_Yuv420`, 16-bit words in the slots."""
-    dtype = torch.uint16
-
-    @staticmethod
-    def size(frame):
-        FrameStream.check_frame_yuv420p10(frame)
-        return _yuv_hw(frame.shape)
-
-    def upscale(self, model, dev_in, outscale, plan):
-        return upscale_yuv420p10(model, dev_in, self.layout, self.matrix, outscale=outscale, plan=plan)
+        if self.rgb:
+            return upscale_u8(model, dev_in, outscale=outscale, plan=plan)
+        fn = upscale_yuv420 if self.fmt.bits == 8 else upscale_yuv420p10
+        return fn(model, dev_in, self.name, self.matrix, outscale=outscale, plan=plan)

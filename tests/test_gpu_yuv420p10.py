@@ -75,7 +75,7 @@ def _launches(fn):
 # 1 ---- the generic launches against the numpy definition ---------------------------------------------------------------------
 @pytest.mark.parametrize("matrix", MATRICES)
 @pytest.mark.parametrize("layout", LAYOUTS)
-@pytest.mark.parametrize("n,h,w", [(1, 2, 2), (3, 2, 6), (2, 4, 10), (1, 6, 8), (2, 8, 16), (1, 4, 24)])
+@pytest.mark.parametrize("n,h,w", [(1, 2, 2), (3, 2, 6), (2, 4, 10), (1, 6, 8), (2, 8, 16), (1, 4, 24), (1, 2, 12)])
 def test_generic_conversions_are_the_numpy_definition(n, h, w, layout, matrix):
     import real_esrgan_pytorch_amd as R
     f = random_yuv10(n, h, w, seed=h * w + n)

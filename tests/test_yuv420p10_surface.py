@@ -4,6 +4,7 @@ the integer conversions against rint of the float64 studio formula, the ValueErr
 bound, argument checks before any launch), the package exports, FrameStream's and the rawvideo CLI's checks.  Nothing here touches a
 device."""
 import ctypes as C
+import inspect
 import io
 import itertools
 import os
@@ -193,6 +194,55 @@ def test_package_exports(R):
         assert hasattr(R, name) and name in R.__all__ and name in R.frames.__all__, name
         assert getattr(R, name) is getattr(R.frames, name)
     assert callable(R.SRVGGNetCompact.forward_yuv420p10)
+
+
+SIGNATURES = {        # recorded from the commit before the pixel-format table: the public surface did not move with it
+    "yuv420_tables": "(matrix: 'str' = 'bt601', quantised: 'bool' = True) -> 'Tuple[np.ndarray, np.ndarray]'",
+    "yuv420_to_rgb_np": "(frames: 'np.ndarray', layout: 'str' = 'i420', matrix: 'str' = 'bt601') -> 'np.ndarray'",
+    "rgb_to_yuv420_np": "(rgb: 'np.ndarray', layout: 'str' = 'i420', matrix: 'str' = 'bt601') -> 'np.ndarray'",
+    "yuv420_to_rgb": "(frames: 'torch.Tensor', layout: 'str' = 'i420', matrix: 'str' = 'bt601') -> 'torch.Tensor'",
+    "rgb_to_yuv420": "(rgb: 'torch.Tensor', layout: 'str' = 'i420', matrix: 'str' = 'bt601') -> 'torch.Tensor'",
+    "upscale_yuv420": "(model, frames: 'torch.Tensor', layout: 'str' = 'i420', matrix: 'str' = 'bt601', halo: 'Optional[int]' = None, "
+                      "outscale: 'Optional[float]' = None, plan=None) -> 'torch.Tensor'",
+    "yuv420p10_tables": "(matrix: 'str' = 'bt601', quantised: 'bool' = True) -> 'Tuple[np.ndarray, np.ndarray]'",
+    "yuv420p10_to_rgb_np": "(frames: 'np.ndarray', layout: 'str' = 'i420p10', matrix: 'str' = 'bt601') -> 'np.ndarray'",
+    "rgb_to_yuv420p10_np": "(rgb: 'np.ndarray', layout: 'str' = 'i420p10', matrix: 'str' = 'bt601') -> 'np.ndarray'",
+    "from_yuv420p10": "(frames: 'torch.Tensor', layout: 'str' = 'i420p10', matrix: 'str' = 'bt601') -> 'torch.Tensor'",
+    "to_yuv420p10": "(sr: 'torch.Tensor', layout: 'str' = 'i420p10', matrix: 'str' = 'bt601') -> 'torch.Tensor'",
+    "upscale_yuv420p10": "(model, frames: 'torch.Tensor', layout: 'str' = 'i420p10', matrix: 'str' = 'bt601', halo: 'Optional[int]' = None, "
+                         "outscale: 'Optional[float]' = None, plan=None) -> 'torch.Tensor'",
+}
+FORWARD_SIGNATURES = {
+    "forward_u8": "(self, frames: 'torch.Tensor', outscale: 'Optional[float]' = None, plan=None) -> 'torch.Tensor'",
+    "forward_yuv420": "(self, frames: 'torch.Tensor', layout: 'str' = 'i420', matrix: 'str' = 'bt601', outscale: 'Optional[float]' = None, "
+                      "plan=None) -> 'torch.Tensor'",
+    "forward_yuv420p10": "(self, frames: 'torch.Tensor', layout: 'str' = 'i420p10', matrix: 'str' = 'bt601', "
+                         "outscale: 'Optional[float]' = None, plan=None) -> 'torch.Tensor'",
+}
+
+
+def test_pixel_formats_are_one_table(R):
+    table = R.frames.PIXEL_FORMATS
+    assert R.FrameStream.PIX_FMTS == tuple(table) == ("rgb24", "i420", "nv12", "i420p10", "p010")
+    yuv = {name: f for name, f in table.items() if f.layout is not None}
+    assert R.frames.YUV_LAYOUTS == {name: f.layout for name, f in yuv.items() if f.bits == 8} and list(R.frames.YUV_LAYOUTS) == ["i420", "nv12"]
+    assert R.frames.YUV10_LAYOUTS == {name: f.layout for name, f in yuv.items() if f.bits == 10} and list(R.frames.YUV10_LAYOUTS) == list(LAYOUTS)
+    hdr = open(os.path.join(ROOT, "include", "resr.h")).read()
+    ids = {name: int(value) for name, value in re.findall(r"\b(RESR_YUV_[A-Z0-9]+) = (\d+)", hdr)}
+    assert sorted(ids) == ["RESR_YUV_I420", "RESR_YUV_I420P10", "RESR_YUV_NV12", "RESR_YUV_P010"]
+    for name, f in yuv.items():
+        assert f.layout == ids["RESR_YUV_" + name.upper()], name
+        assert (f.bits, f.top) == ((10, 1023) if name in LAYOUTS else (8, 255)), name
+        assert f.semi_planar == (name in ("nv12", "p010")) and f.high_bits == (name == "p010"), name
+        assert (f.np_dtype, f.torch_dtype) == ((np.uint16, torch.uint16) if f.bits == 10 else (np.uint8, torch.uint8)), name
+    rgb = table["rgb24"]
+    assert (rgb.layout, rgb.bits, rgb.top, rgb.np_dtype, rgb.torch_dtype) == (None, 8, 255, np.uint8, torch.uint8)
+    with pytest.raises(AttributeError):                               # a record is immutable
+        rgb.bits = 10
+    for name, want in SIGNATURES.items():
+        assert str(inspect.signature(getattr(R.frames, name))) == want, name
+    for name, want in FORWARD_SIGNATURES.items():
+        assert str(inspect.signature(getattr(R.SRVGGNetCompact, name))) == want, name
 
 
 def _fake(nbytes=128):
