@@ -515,7 +515,8 @@ int resr_rgb_to_yuv420(const uint8_t* src_hwc, uint8_t* dst, int32_t n, int32_t 
  * RESR_ERR_ARG before any launch: a null pointer; n, h, w <= 0; an odd h or w; a layout other than these two (the 8-bit entries
  * refuse these two in turn); a misaligned end: y_yuv 16-byte aligned when s * d->w is a multiple of 8; for resr_nchw_to_yuv420p10
  * dst 8-byte and src_f32 16-byte aligned when w is a multiple of 4; 2 bytes per word and 4 per float everywhere else.
- * Mixed depths (8 bits in, 10 out), 12 / 16-bit samples, full range and 4:2:2 / 4:4:4 are not provided. */
+ * A source and a destination of different depth, layout or matrix: "Mixed frame formats" below.  12 / 16-bit samples, full range and
+ * 4:2:2 / 4:4:4 are not provided. */
 enum { RESR_YUV_I420P10 = 2, RESR_YUV_P010 = 3 };
 int resr_compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x_yuv, const float* params, const void* packed,
                                    void* workspace, size_t workspace_bytes, uint16_t* y_yuv, const ResrYuvDesc* yuv, void* stream);
@@ -548,6 +549,31 @@ int resr_compact_forward_yuv420p10_scaled(const ResrCompactDesc* d, const uint16
                                           int32_t taps_x, const ResrYuvDesc* yuv, void* stream);
 int resr_compact_yuv420_scaled_fits(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x,
                                     int32_t bits);
+
+/* Mixed frame formats: a source descriptor and a destination descriptor, each any of the four layouts above with its own tables --
+ * 8 bits in and 10 out (or the reverse), NV12 / P010 in and planar out (or the reverse), BT.601 in and BT.709 out.  With top = 255
+ * or 1023 for the depth of a side, DEFINED bit for bit by the functions above:
+ *   y = rgb_to_yuv_dst(q_dst(float_path(yuv_to_rgb_src(x) / top_src)))            q(v) = trunc(clamp(v * top, 0, top)), fp32
+ * float_path: resr_compact_forward on fp32 NCHW, for the scaled entry followed by resr_image_resize (fp32 out).  With src_yuv and
+ * dst_yuv equal this is, term for term, the definition of the four same-format entries, and the same kernels run.
+ * resr_compact_forward_yuv420_mixed: x_yuv [N, 3 d->h / 2, d->w] in src_yuv's layout -> y_yuv [N, 3 s d->h / 2, s d->w] in dst_yuv's;
+ * bytes or 16-bit words on either side as that side's layout says.  One launch sequence: the head of the source's depth, the convs,
+ * one tail that recomputes the residual from x_yuv with the source's word type, layout, iq and / top_src, and quantises, converts
+ * and stores with the destination's top, fq and layout.  resr_compact_forward_yuv420_mixed_scaled: the same on the resized tail
+ * of "YUV outscale" -> y_yuv [N, 3 oh / 2, ow].  Same descriptor, packed weights and workspace as resr_compact_forward.
+ * RESR_ERR_ARG before any launch: a null pointer; a layout on either side that is no RESR_YUV_*; an odd d->h or d->w; y_yuv not
+ * aligned as the destination's depth asks at its width (8-bit: 8 bytes when s * d->w is a multiple of 8; 10-bit: 16 bytes then,
+ * else 2; the scaled entry: 4 bytes); for the scaled entry everything resr_compact_forward_yuv420_scaled refuses (an odd oh or ow,
+ * a null table, taps outside [1, 4096], N > 65535, a scale with no even LDS tile: resr_compact_yuv420_scaled_fits with the
+ * destination's bits).  An rgb24 frame on one side is not fused: compose resr_u8_to_nchw / resr_nchw_to_u8 with the generic
+ * conversions above. */
+int resr_compact_forward_yuv420_mixed(const ResrCompactDesc* d, const void* x_yuv, const ResrYuvDesc* src_yuv, const float* params,
+                                      const void* packed, void* workspace, size_t workspace_bytes, void* y_yuv,
+                                      const ResrYuvDesc* dst_yuv, void* stream);
+int resr_compact_forward_yuv420_mixed_scaled(const ResrCompactDesc* d, const void* x_yuv, const ResrYuvDesc* src_yuv, const float* params,
+                                             const void* packed, void* workspace, size_t workspace_bytes, void* y_yuv, int32_t oh,
+                                             int32_t ow, const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x,
+                                             const float* w_x, int32_t taps_x, const ResrYuvDesc* dst_yuv, void* stream);
 
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */

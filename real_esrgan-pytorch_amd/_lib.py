@@ -198,6 +198,11 @@ _PROTOS = {
     "resr_compact_forward_yuv420p10_scaled": (C.c_int, [C.POINTER(CompactDesc), _P, _P, _P, _P, C.c_size_t, _P, C.c_int32, C.c_int32,
                                                         _P, _P, C.c_int32, _P, _P, C.c_int32, C.POINTER(YuvDesc), _P]),
     "resr_compact_yuv420_scaled_fits": (C.c_int, [C.c_int32] * 8),
+    "resr_compact_forward_yuv420_mixed": (C.c_int, [C.POINTER(CompactDesc), _P, C.POINTER(YuvDesc), _P, _P, _P, C.c_size_t, _P,
+                                                    C.POINTER(YuvDesc), _P]),
+    "resr_compact_forward_yuv420_mixed_scaled": (C.c_int, [C.POINTER(CompactDesc), _P, C.POINTER(YuvDesc), _P, _P, _P, C.c_size_t, _P,
+                                                           C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, _P, C.c_int32,
+                                                           C.POINTER(YuvDesc), _P]),
     "resr_ema_update": (C.c_int, [_P, _P, C.c_int64, C.c_double, _P]),
     "resr_debug_tr_probe": (C.c_int, [_P, _P]),
     "resr_debug_conv_trace": (C.c_int, [_P]),

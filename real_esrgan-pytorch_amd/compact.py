@@ -17,6 +17,8 @@ forward only as well (frames.py builds the pipelined host-to-host stream on it).
 of frames.py fused into the same two kernels, so its result equals `rgb_to_yuv420_np(forward_u8(yuv420_to_rgb_np(f)))` bit for bit.
 `forward_yuv420p10` is the same for 10-bit frames.  Both take `outscale` as `forward_u8` does (`resr_compact_forward_yuv420_scaled` /
 `_yuv420p10_scaled`, csrc/image_resize.hip): the resized tail with a YUV 4:2:0 output stage, still one launch sequence.
+`forward_yuv420_mixed` is the sequence with a source and a destination format of their own (`resr_compact_forward_yuv420_mixed`, `_scaled`):
+8 bits in and 10 out, NV12 / P010 in and planar out, BT.601 in and BT.709 out -- the head reads the source, the tail writes the destination.
 """
 from __future__ import annotations
 
@@ -170,15 +172,16 @@ class SRVGGNetCompact(nn.Module):
             raise RuntimeError("SRVGGNetCompact: the compact generator's backward pass is not implemented on the MI355X path; "
                                "run inference under torch.no_grad() (or with requires_grad_(False) parameters)")
 
-    def _call(self, entry: str, src: torch.Tensor, n: int, h: int, w: int, y: torch.Tensor, *extra) -> torch.Tensor:
+    def _call(self, entry: str, src: torch.Tensor, n: int, h: int, w: int, y: torch.Tensor, *extra, after_src=()) -> torch.Tensor:
         """What every forward shares once its own input is checked: the arena, the descriptor of n LR frames h x w, packing, the
-        workspace, then `entry` (its ends `src` and `y`; `extra`: the arguments between y and the stream)."""
+        workspace, then `entry` (its ends `src` and `y`; `extra`: the arguments between y and the stream; `after_src`: those between
+        src and the parameters, the mixed entries' source descriptor)."""
         flat = self.flat_parameters()
         _lib.require_cuda(flat, "SRVGGNetCompact parameters")
         desc = self._desc(n, h, w)
         self._pack(desc, flat)
         ws = self._workspace(desc, src.device)
-        _lib.check(getattr(_lib.lib(), entry)(C.byref(desc), _lib.ptr(src), _lib.ptr(flat), _lib.ptr(self._packed), _lib.ptr(ws),
+        _lib.check(getattr(_lib.lib(), entry)(C.byref(desc), _lib.ptr(src), *after_src, _lib.ptr(flat), _lib.ptr(self._packed), _lib.ptr(ws),
                                               ws.numel(), _lib.ptr(y), *extra, _lib.stream_ptr(src)), entry)
         return y
 
@@ -281,6 +284,40 @@ class SRVGGNetCompact(nn.Module):
         bit `rgb_to_yuv420p10_np(q10(resize_with_plan(self(yuv420p10_to_rgb_np(f) / 1023), plan)))`; the fp32 frames of that
         composition exist as LDS tiles only."""
         return self._forward_yuv(frames, layout, matrix, outscale, plan, 10)
+
+    def forward_yuv420_mixed(self, frames: torch.Tensor, src, dst, outscale: Optional[float] = None, plan=None) -> torch.Tensor:
+        """frames [N,3H/2,W] in the YUV 4:2:0 format `src` (a `frames.FrameFormat` or a `(pix_fmt, matrix)` pair: "i420" / "nv12" uint8,
+        "i420p10" / "p010" uint16; H and W even) on the model's device, contiguous -> [N,3sH/2,sW] in the format `dst`, whose depth,
+        layout and matrix need not be the source's.  Bit for bit, with top = 255 or 1023 of a side,
+
+            rgb_to_yuv_np_dst(q_dst(self(yuv_to_rgb_np_src(f) / top_src)))          q(v) = trunc(clamp(v * top, 0, top)) in fp32
+
+        (frames.py, MIXED FRAME FORMATS).  `resr_compact_forward_yuv420_mixed`: the head of the source's depth, the convs, one tail that
+        recomputes the residual from `frames` in the source's format and quantises, converts and stores in the destination's.  With
+        `src == dst` this is `forward_yuv420` / `forward_yuv420p10`: the same kernels run.  "rgb24" on a side is a ValueError here --
+        that end is not fused; `frames.upscale_frames` composes it.  `outscale`, `plan`: as `forward_yuv420`'s
+        (`resr_compact_forward_yuv420_mixed_scaled`): the result is [N, 3 out_h / 2, out_w], resized in fp32 before `q_dst`.  Every
+        ValueError (a format, a matrix, an odd frame, an odd result) comes before the device is looked at; same guard, packing and
+        workspace caches as `forward`."""
+        from . import frames as _frames
+        what = "SRVGGNetCompact.forward_yuv420_mixed"
+        a, b = _frames.frame_format(src, what), _frames.frame_format(dst, what)
+        for f in (a, b):
+            if f.pix_fmt == "rgb24":
+                raise ValueError(f"{what}: rgb24 is not fused to a YUV format; frames.upscale_frames composes it")
+        o = _frames.check_outscale(outscale, self.upscale, what)
+        _frames.mixed_geometry(frames, a, b, self.upscale, o, what)
+        qa, qb = _frames.format_desc(a), _frames.format_desc(b)
+        self._guard()
+        n, h, w = _frames._check_yuv(frames, what, a.fmt.bits)
+        s = self.upscale
+        if o is None:
+            y = torch.empty((n, h * s * 3 // 2, w * s), dtype=b.fmt.torch_dtype, device=frames.device)
+            return self._call("resr_compact_forward_yuv420_mixed", frames, n, h, w, y, C.byref(qb), after_src=(C.byref(qa),))
+        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
+        plan = self._scaled_plan(frames, h, w, o, plan, what)
+        y = torch.empty((n, plan.out_h * 3 // 2, plan.out_w), dtype=b.fmt.torch_dtype, device=frames.device)
+        return self._call("resr_compact_forward_yuv420_mixed_scaled", frames, n, h, w, y, *plan.args(), C.byref(qb), after_src=(C.byref(qa),))
 
     def load_official_state_dict(self, checkpoint) -> None:
         """Upstream's `{"params_ema": sd}` / `{"params": sd}` (params_ema preferred) or a bare state dict (model.load_official_state_dict)."""

@@ -276,14 +276,14 @@ int64_t resr_compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* chunks,
 int resr_compact_forward(const ResrCompactDesc* d, const float* x_nchw, const float* params, const void* packed,
                          void* workspace, size_t workspace_bytes, float* y_nchw, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_F32, false, x_nchw, y_nchw, {}, nullptr, 0}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+    return compact_forward_ends(d, {END_F32, false, x_nchw, y_nchw, {}, nullptr, nullptr, 0}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
                                 "compact_forward");
 }
 
 int resr_compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
                             void* workspace, size_t workspace_bytes, uint8_t* y_u8, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_RGB8, false, x_u8, y_u8, {}, nullptr, 0}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+    return compact_forward_ends(d, {END_RGB8, false, x_u8, y_u8, {}, nullptr, nullptr, 0}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
                                 "compact_forward_u8");
 }
 
@@ -292,7 +292,7 @@ int resr_compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x_u8
                                    const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
                                    int32_t taps_x, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_RGB8, true, x_u8, y_u8, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, nullptr, 0}, params, packed,
+    return compact_forward_ends(d, {END_RGB8, true, x_u8, y_u8, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, nullptr, nullptr, 0}, params, packed,
                                 workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_u8_scaled");
 }
 
@@ -316,7 +316,7 @@ int resr_nchw_to_u8(const float* src_f32, uint8_t* dst_u8, int32_t n, int32_t h,
 int resr_compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x_yuv, const float* params, const void* packed,
                                 void* workspace, size_t workspace_bytes, uint8_t* y_yuv, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_YUV, false, x_yuv, y_yuv, {}, yuv, 8}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+    return compact_forward_ends(d, {END_YUV, false, x_yuv, y_yuv, {}, yuv, yuv, 8}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
                                 "compact_forward_yuv420");
 }
 
@@ -333,7 +333,7 @@ int resr_rgb_to_yuv420(const uint8_t* src_hwc, uint8_t* dst, int32_t n, int32_t 
 int resr_compact_forward_yuv420p10(const ResrCompactDesc* d, const uint16_t* x_yuv, const float* params, const void* packed,
                                    void* workspace, size_t workspace_bytes, uint16_t* y_yuv, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_YUV, false, x_yuv, y_yuv, {}, yuv, 10}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+    return compact_forward_ends(d, {END_YUV, false, x_yuv, y_yuv, {}, yuv, yuv, 10}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
                                 "compact_forward_yuv420p10");
 }
 
@@ -352,7 +352,7 @@ int resr_compact_forward_yuv420_scaled(const ResrCompactDesc* d, const uint8_t* 
                                        const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
                                        int32_t taps_x, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_YUV, true, x_yuv, y_yuv, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv, 8}, params, packed,
+    return compact_forward_ends(d, {END_YUV, true, x_yuv, y_yuv, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv, yuv, 8}, params, packed,
                                 workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_yuv420_scaled");
 }
 
@@ -361,8 +361,25 @@ int resr_compact_forward_yuv420p10_scaled(const ResrCompactDesc* d, const uint16
                                           const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
                                           int32_t taps_x, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_YUV, true, x_yuv, y_yuv, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv, 10}, params, packed,
+    return compact_forward_ends(d, {END_YUV, true, x_yuv, y_yuv, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, yuv, yuv, 10}, params, packed,
                                 workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_yuv420p10_scaled");
+}
+
+int resr_compact_forward_yuv420_mixed(const ResrCompactDesc* d, const void* x_yuv, const ResrYuvDesc* src_yuv, const float* params,
+                                      const void* packed, void* workspace, size_t workspace_bytes, void* y_yuv,
+                                      const ResrYuvDesc* dst_yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_ends(d, {END_YUV, false, x_yuv, y_yuv, {}, src_yuv, dst_yuv, 0}, params, packed, workspace, workspace_bytes,
+                                (hipStream_t)stream, "compact_forward_yuv420_mixed");
+}
+
+int resr_compact_forward_yuv420_mixed_scaled(const ResrCompactDesc* d, const void* x_yuv, const ResrYuvDesc* src_yuv, const float* params,
+                                             const void* packed, void* workspace, size_t workspace_bytes, void* y_yuv, int32_t oh,
+                                             int32_t ow, const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x,
+                                             const float* w_x, int32_t taps_x, const ResrYuvDesc* dst_yuv, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_ends(d, {END_YUV, true, x_yuv, y_yuv, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, src_yuv, dst_yuv, 0}, params,
+                                packed, workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_yuv420_mixed_scaled");
 }
 
 int resr_compact_yuv420_scaled_fits(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x, int32_t bits) {

@@ -126,7 +126,7 @@ struct ScaledTail {
 enum EndFormat {
     END_F32,    // x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32: layout.hip's head, compact_tail
     END_RGB8,   // x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8: frames.hip, the conversions fused into the head and the tail
-    END_YUV,    // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames of bytes or 16-bit words (yuv->layout): the colour conversions too
+    END_YUV,    // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames of bytes or 16-bit words (src->layout, dst->layout): the colour conversions too
 };
 struct Ends {
     EndFormat format;
@@ -134,8 +134,10 @@ struct Ends {
     const void* x;
     void* y;
     ScaledTail sc;           // scaled
-    const ResrYuvDesc* yuv;  // END_YUV, else null
-    int bits_expected;       // END_YUV: the depth the entry is for, 8 or 10; a descriptor of another is refused
+    const ResrYuvDesc* src;  // END_YUV: what the frames of x are (layout, matrix tables), else null
+    const ResrYuvDesc* dst;  // END_YUV: what the frames of y are; the same-format entries pass src again
+    int bits_expected;       // END_YUV: the depth the entry is for, 8 or 10 (a descriptor of another is refused); 0: the mixed
+                             // entries, any depth on either side
 };
 
 }  // namespace resr

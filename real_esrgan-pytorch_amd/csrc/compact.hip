@@ -12,12 +12,15 @@
 //   END_RGB8          uint8 HWC frames: frames.hip's head in place of the layout kernel, its u8 tail (pixel-shuffle + residual +
 //                     * 255, clamp, truncate) in place of compact_tail_kernel;
 //   END_YUV           YUV 4:2:0 frames [N,3H/2,W] of bytes or of 16-bit words holding 10-bit samples (yuv420p10le / P010: 1023
-//                     levels at both ends): frames.hip's head reading YUV, and its YUV tail;
+//                     levels): frames.hip's head reading YUV, and its YUV tail.  The source and the destination each have their
+//                     own descriptor (Ends::src, Ends::dst): the head and the tail's residual follow the source's depth, layout
+//                     and matrix, the tail's quantisation and stores the destination's; the same-format entries pass one twice;
 //   ... and scaled    ("outscale") image_resize.hip's fused tail in place of either: the HR frame is formed tile by tile in LDS and
 //                     only the resized frame, uint8 [N,oh,ow,3] or YUV 4:2:0 [N,3oh/2,ow], is written.
 #include <vector>
 
 #include "common.h"
+#include "yuv.h"
 
 namespace resr {
 
@@ -27,14 +30,14 @@ int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const 
 int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
 int frame_head_dispatch(const void*, void*, int, int, int, int, hipStream_t, long, const ResrYuvDesc*);   // frames.hip
 int compact_tail_u8(const float*, const uint8_t*, uint8_t*, int, int, int, int, hipStream_t);
-int yuv_forward_check(const char*, int, int, int, int, const void*, const ResrYuvDesc*, int);
-int compact_tail_yuv(const float*, const void*, void*, int, int, int, int, const ResrYuvDesc*, hipStream_t);
+int yuv_forward_check(const char*, int, int, int, int, const void*, const ResrYuvDesc*, const ResrYuvDesc*, int);
+int compact_tail_yuv(const float*, const void*, void*, int, int, int, int, const ResrYuvDesc*, const ResrYuvDesc*, hipStream_t);
 int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, int,
                 const void*, ResizeGeom*);                                                                      // image_resize.hip
 int compact_tail_u8_scaled(const float*, const uint8_t*, uint8_t*, int, int, int, int, const int32_t*, const float*, const int32_t*,
                            const float*, const ResizeGeom*, hipStream_t);
 int compact_tail_yuv420_scaled(const float*, const void*, void*, int, int, int, int, const int32_t*, const float*, const int32_t*,
-                               const float*, const ResrYuvDesc*, const ResizeGeom*, hipStream_t);
+                               const float*, const ResrYuvDesc*, const ResrYuvDesc*, const ResizeGeom*, hipStream_t);
 
 namespace {
 
@@ -185,10 +188,10 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
     if (e.format == END_RGB8 && ((size_t)e.y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
     int rc = RESR_OK;
     // the descriptor and the LR frame; of scaled ends the output pointer's rule is the plan's (nullptr passes the unscaled tail's)
-    if (e.format == END_YUV) rc = yuv_forward_check(who, d.n, d.h, d.w, d.upscale, e.scaled ? nullptr : e.y, e.yuv, e.bits_expected);
+    if (e.format == END_YUV) rc = yuv_forward_check(who, d.n, d.h, d.w, d.upscale, e.scaled ? nullptr : e.y, e.src, e.dst, e.bits_expected);
     if (!rc && e.scaled)
         rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y, e.sc.idx_x,
-                         e.sc.w_x, e.sc.taps_x, e.format == END_RGB8 ? RESIZE_U8 : e.bits_expected == 8 ? RESIZE_YUV8 : RESIZE_YUV10, e.y, geom);
+                         e.sc.w_x, e.sc.taps_x, e.format == END_RGB8 ? RESIZE_U8 : yuv_bits(e.dst->layout) == 8 ? RESIZE_YUV8 : RESIZE_YUV10, e.y, geom);
     if (rc) return rc;
     if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
     return RESR_OK;
@@ -199,7 +202,7 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
 // The launch sequence every entry shares: plan, refusals, head, convs, tail.
 int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* params, const void* packed, void* workspace,
                          size_t workspace_bytes, hipStream_t st, const char* who) {
-    if (e.format == END_YUV && !e.yuv) return fail(RESR_ERR_ARG, "%s: null argument", who);
+    if (e.format == END_YUV && (!e.src || !e.dst)) return fail(RESR_ERR_ARG, "%s: null argument", who);
     CPlan p;
     if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "%s: bad descriptor", who);
     ResizeGeom geom;
@@ -215,7 +218,7 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
     const int N = d->n, H = d->h, W = d->w;
     const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
     if (e.format == END_F32) rc = nchw_to_nhwc_dispatch((const float*)e.x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
-    else rc = frame_head_dispatch(e.x, xin, N, H, W, d->dtype, st, (long)lo32, e.yuv);   // yuv null: RGB bytes; its layout: bytes or 16-bit words
+    else rc = frame_head_dispatch(e.x, xin, N, H, W, d->dtype, st, (long)lo32, e.src);   // src null: RGB bytes; its layout: bytes or 16-bit words
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) {
         ResrConvDesc cd;
@@ -259,8 +262,8 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
             if (!e.scaled) return compact_tail_u8(t, (const uint8_t*)e.x, (uint8_t*)e.y, N, H, W, s, st);
             return compact_tail_u8_scaled(t, (const uint8_t*)e.x, (uint8_t*)e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, &geom, st);
         case END_YUV:
-            if (!e.scaled) return compact_tail_yuv(t, e.x, e.y, N, H, W, s, e.yuv, st);
-            return compact_tail_yuv420_scaled(t, e.x, e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, e.yuv, &geom, st);
+            if (!e.scaled) return compact_tail_yuv(t, e.x, e.y, N, H, W, s, e.src, e.dst, st);
+            return compact_tail_yuv420_scaled(t, e.x, e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, e.src, e.dst, &geom, st);
     }
     return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
 }

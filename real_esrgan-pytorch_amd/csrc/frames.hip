@@ -6,7 +6,8 @@
 //   u8_to_nchw     : u8 [N,H,W,3] -> fp32 [N,3,H,W]                (models whose first kernel is not ours to fuse)
 //   nchw_to_u8     : fp32 [N,3,H,W] -> u8 [N,H,W,3]                (... and whose last one is not: RRDB Generator, the tiler)
 //   compact_tail_yuv              : compact_tail_u8 with YUV 4:2:0 frames at both of its ends, of bytes or, as frame_head, of the
-//                                   16-bit words of 10-bit samples (yuv420p10le / P010): one kernel, the layout its parameter
+//                                   16-bit words of 10-bit samples (yuv420p10le / P010): one kernel, the layout of the source and
+//                                   the layout of the destination its parameters (one format twice, or a mixed pair)
 //   yuv420_to_rgb, rgb_to_yuv420  : the integer colour conversions on their own, u8 [N,3H/2,W] <-> u8 [N,H,W,3]
 //   yuv420p10_to_nchw, nchw_to_yuv420p10: 10-bit YUV [N,3H/2,W] <-> fp32 [N,3,H,W], one launch each, no RGB frame in between
 //
@@ -248,18 +249,22 @@ __device__ __forceinline__ void store_yuv_block(typename Depth<BITS>::word* img,
 //            contiguous bytes per Y row;
 //   10 bits: two 16-byte Y stores and 8 bytes each of Cb and Cr (I420P10) or one 16-byte CbCr store (P010); 1 KiB per Y row.
 // Every other even width: one sample word per store, the columns past the right edge skipped (rows always come in whole pairs).
-template <int S, int LAYOUT>
-__global__ __launch_bounds__(256) void compact_tail_yuv_kernel(const float* __restrict__ t, const typename Depth<yuv_bits(LAYOUT)>::word* __restrict__ x,
+// The two ends are separate: SRC is the layout of x (its word type, where its samples sit, and with qs.iq and unit_of<top of SRC> the
+// residual level), LAYOUT that of y (quantise<top of LAYOUT>, qd.fq, the stores and the wide rule above).  SRC == LAYOUT with the same
+// tables in qs and qd is the same-format path, instruction for instruction what it was with one descriptor; the twelve other pairs
+// per S are the mixed tails (8 bits in and 10 out, NV12 in and I420 out, ...; BT.601 in and BT.709 out is a pair of tables, no instance).
+template <int S, int SRC, int LAYOUT>
+__global__ __launch_bounds__(256) void compact_tail_yuv_kernel(const float* __restrict__ t, const typename Depth<yuv_bits(SRC)>::word* __restrict__ x,
                                                                typename Depth<yuv_bits(LAYOUT)>::word* __restrict__ y, int n, int h, int w, int wide,
-                                                               ResrYuvDesc q) {
-    constexpr int BITS = yuv_bits(LAYOUT);
+                                                               ResrYuvDesc qs, ResrYuvDesc qd) {
+    constexpr int BITS = yuv_bits(LAYOUT), SBITS = yuv_bits(SRC);
     typedef typename Depth<BITS>::word word;
     const int HS = h * S, WS = w * S;
     long b;
     int Y0, X0;
     if (!block_2xcols<8>(n, HS, WS, b, Y0, X0)) return;
     const long plane = (long)h * w;
-    const word* xin = x + b * (plane + (plane >> 1));
+    const typename Depth<SBITS>::word* xin = x + b * (plane + (plane >> 1));
     const float* tb = t + b * 3 * S * S * plane;
     unsigned yb[2][8];
     int sum[4][3];
@@ -278,25 +283,25 @@ __global__ __launch_bounds__(256) void compact_tail_yuv_kernel(const float* __re
                 const int xx = 8 % S == 0 ? X0 / S + k / S : X / S;
                 const int sx = X - xx * S;
                 int Yi, Cb, Cr;
-                yuv_load<BITS>(xin, h, w, LAYOUT, yy, xx, Yi, Cb, Cr);
+                yuv_load<SBITS>(xin, h, w, SRC, yy, xx, Yi, Cb, Cr);
                 unsigned rgb_in[3], o[3];
-                yuv_to_rgb<BITS>(q, Yi, Cb, Cr, rgb_in);
+                yuv_to_rgb<SBITS>(qs, Yi, Cb, Cr, rgb_in);
                 const float* tp = tb + (long)(sy * S + sx) * plane + (long)yy * w + xx;
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
-                    const float v = tp[(long)c * S * S * plane] + unit_of<kTop<BITS>>(rgb_in[c]);
+                    const float v = tp[(long)c * S * S * plane] + unit_of<kTop<SBITS>>(rgb_in[c]);
                     o[c] = quantise<kTop<BITS>>(v);
                     sum[k >> 1][c] += (int)o[c];
                 }
-                yb[r][k] = luma_of<BITS>(q, o[0], o[1], o[2]);
+                yb[r][k] = luma_of<BITS>(qd, o[0], o[1], o[2]);
             }
         }
     }
     unsigned cb[4], cr[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-        cb[j] = chroma_of<BITS>(q, 1, sum[j]);
-        cr[j] = chroma_of<BITS>(q, 2, sum[j]);
+        cb[j] = chroma_of<BITS>(qd, 1, sum[j]);
+        cr[j] = chroma_of<BITS>(qd, 2, sum[j]);
     }
     const long luma = (long)HS * WS;
     word* yo = y + b * (luma + (luma >> 1));
@@ -487,11 +492,12 @@ __global__ __launch_bounds__(256) void rgb_to_yuv420_kernel(const uint8_t* __res
 
 bool grid_ok(long threads) { return threads > 0 && (threads + 255) / 256 <= 0x7fffffffL; }
 
-// The refusals every YUV entry shares, in their order: a descriptor that is null or not of the entry's depth, then an odd frame.
+// The refusals every YUV entry shares, in their order: a descriptor that is null or not of the entry's depth (bits = 0, the mixed
+// entries: of no depth at all), then an odd frame.
 int yuv_desc_check(const char* who, int h, int w, const ResrYuvDesc* q, int bits) {
-    if (!q || yuv_bits(q->layout) != bits)
+    if (!q || !yuv_bits(q->layout) || (bits && yuv_bits(q->layout) != bits))
         return fail(RESR_ERR_ARG, "%s: the YUV descriptor is null or its layout is neither %s", who,
-                    bits == 8 ? "RESR_YUV_I420 nor RESR_YUV_NV12" : "RESR_YUV_I420P10 nor RESR_YUV_P010");
+                    bits == 8 ? "RESR_YUV_I420 nor RESR_YUV_NV12" : bits ? "RESR_YUV_I420P10 nor RESR_YUV_P010" : "of these nor any other RESR_YUV_*");
     if ((h & 1) || (w & 1)) return fail(RESR_ERR_ARG, "%s: a 4:2:0 frame has an even height and width, got %dx%d", who, h, w);
     return RESR_OK;
 }
@@ -573,11 +579,14 @@ int nchw_to_u8_dispatch(const float* src, uint8_t* dst, int n, int h, int w, hip
 // ---- YUV 4:2:0 ----
 
 // Everything a YUV entry of compact_forward_ends has to refuse about its frames, before its first launch (d->h, d->w even: the
-// output's are too).  bits: the entry's depth.  The alignment of y is the wide store of that depth (8 sample words) at an output
-// width that is a multiple of 8, else one word.
-int yuv_forward_check(const char* who, int n, int h, int w, int s, const void* y, const ResrYuvDesc* q, int bits) {
-    if (const int rc = yuv_desc_check(who, h, w, q, bits)) return rc;
-    const int word = bits == 8 ? 1 : 2;
+// output's are too).  bits: the entry's depth, 0 for the mixed entries (src and dst each of any depth; the same-format entries pass
+// one descriptor twice).  The alignment of y is the wide store of the destination's depth (8 sample words) at an output width that
+// is a multiple of 8, else one word.
+int yuv_forward_check(const char* who, int n, int h, int w, int s, const void* y, const ResrYuvDesc* src, const ResrYuvDesc* dst, int bits) {
+    if (const int rc = yuv_desc_check(who, h, w, src, bits)) return rc;
+    if (dst != src)
+        if (const int rc = yuv_desc_check(who, h, w, dst, bits)) return rc;
+    const int word = yuv_bits(dst->layout) == 8 ? 1 : 2;
     if (((size_t)y & (size_t)(((w * s) % 8 == 0 ? 8 * word : word) - 1)) != 0)
         return fail(RESR_ERR_ARG, "%s: y_yuv must be %d-byte aligned at an output width of %d%s", who, 8 * word, w * s,
                     word > 1 ? " (2-byte at a width that is no multiple of 8)" : "");
@@ -585,24 +594,30 @@ int yuv_forward_check(const char* who, int n, int h, int w, int s, const void* y
     return RESR_OK;
 }
 
-// the frames have passed yuv_forward_check: compact_forward_ends has called it.  x, y: bytes or 16-bit words, as q->layout says.
+// the frames have passed yuv_forward_check: compact_forward_ends has called it.  x, y: bytes or 16-bit words, as qs->layout and
+// qd->layout say.  Profiling ids name the instance: 31040 + s / 31060 + s where the two layouts are one (8 / 10 bits; another matrix
+// on one side is the same instance), 31090 + s for the mixed tails.
 // (31040 + s is also image_resize's 31040 + u8 at s = 1, u8 = 1: both are 31041.  Tests assert the values, so they stay.)
-int compact_tail_yuv(const float* t, const void* x, void* y, int n, int h, int w, int s, const ResrYuvDesc* q, hipStream_t st) {
+int compact_tail_yuv(const float* t, const void* x, void* y, int n, int h, int w, int s, const ResrYuvDesc* qs, const ResrYuvDesc* qd,
+                     hipStream_t st) {
     const int wide = (w * s) % 8 == 0;
     const dim3 grid((unsigned)(((long)n * (h * s / 2) * ((w * s + 7) / 8) + 255) / 256));
     prof_before(st);
     const bool ok = with_scale(s, [&](auto S) {
-        with_yuv_layout(q->layout, [&](auto L) {
-            typedef typename Depth<yuv_bits(decltype(L)::value)>::word word;
-            hipLaunchKernelGGL((compact_tail_yuv_kernel<decltype(S)::value, decltype(L)::value>), grid, dim3(256), 0, st, t, (const word*)x,
-                               (word*)y, n, h, w, wide, *q);
+        with_yuv_layout(qs->layout, [&](auto A) {
+            with_yuv_layout(qd->layout, [&](auto L) {
+                typedef typename Depth<yuv_bits(decltype(A)::value)>::word sword;
+                typedef typename Depth<yuv_bits(decltype(L)::value)>::word word;
+                hipLaunchKernelGGL((compact_tail_yuv_kernel<decltype(S)::value, decltype(A)::value, decltype(L)::value>), grid, dim3(256), 0, st, t,
+                                   (const sword*)x, (word*)y, n, h, w, wide, *qs, *qd);
+            });
         });
     });
     if (!ok) return fail(RESR_ERR_ARG, "compact_tail_yuv: upscale %d", s);
-    // per LR pixel: 3 s^2 floats of t, 1.5 words of x, 1.5 s^2 words out
-    const bool ten = yuv_bits(q->layout) == 10;
-    const double wb = ten ? 2.0 : 1.0;
-    prof_after(st, (ten ? 31060 : 31040) + s, 0.0, (double)n * h * w * (s * s * (12.0 + 1.5 * wb) + 1.5 * wb));
+    // per LR pixel: 3 s^2 floats of t, 1.5 source words of x, 1.5 s^2 destination words out
+    const bool ten = yuv_bits(qd->layout) == 10;
+    const double wb = ten ? 2.0 : 1.0, sb = yuv_bits(qs->layout) == 10 ? 2.0 : 1.0;
+    prof_after(st, (qs->layout != qd->layout ? 31090 : ten ? 31060 : 31040) + s, 0.0, (double)n * h * w * (s * s * (12.0 + 1.5 * wb) + 1.5 * sb));
     RESR_CHECK_LAUNCH("compact_tail_yuv_kernel");
     return RESR_OK;
 }

@@ -31,7 +31,8 @@
 //
 // YUV OUTSCALE.  The same tile with YUV 4:2:0 frames at both ends, 8 bits (I420 / NV12) or 10 (I420P10 / P010), the tail of
 // resr_compact_forward_yuv420_scaled / _yuv420p10_scaled.  The staged value is t + unit(rgb_in), rgb_in the integer conversion of the
-// YUV input pixel (yuv.h: what compact_tail_yuv of frames.hip adds); after the W pass the three sums of a pixel are quantised to
+// YUV input pixel (yuv.h: what compact_tail_yuv of frames.hip adds; the input frames' own depth, layout and tables, which need not
+// be the output's: resr_compact_forward_yuv420_mixed_scaled); after the W pass the three sums of a pixel are quantised to
 // levels (255 or 1023) and staged in LDS as bytes or 16-bit words; after a barrier every Y row and every chroma row of the tile is
 // written by the row writer of the u8 stage (dwords where the address is 4-byte aligned, single words at the row ends), each word
 // formed on the fly from the staged levels: luma_of per pixel, chroma_of on the unrounded sum of a 2x2 block's four levels.  A
@@ -332,12 +333,15 @@ __global__ __launch_bounds__(kResizeThreads) void compact_tail_u8_scaled_kernel(
     resize_tile(src, OutU8(), y, idx_y, w_y, idx_x, w_x, g);
 }
 
-template <int S, int BITS, int LAYOUT>
-__global__ __launch_bounds__(kResizeThreads) void compact_tail_yuv_scaled_kernel(YuvShuffleSrc<S, BITS, LAYOUT> src, void* __restrict__ y,
-                                                                                 const int32_t* __restrict__ idx_y, const float* __restrict__ w_y,
-                                                                                 const int32_t* __restrict__ idx_x, const float* __restrict__ w_x,
-                                                                                 ResizeGeom g) {
-    resize_tile(src, OutYuv<BITS, LAYOUT>{&src.q}, y, idx_y, w_y, idx_x, w_x, g);
+// SRC: the layout of the input frames (the staged value is t + level / top of SRC, src.q the source's tables), LAYOUT that of the
+// output stage (qd: the destination's).  SRC == LAYOUT with the same tables twice is the same-format tail; the other pairs are the
+// mixed ones (frames.hip, compact_tail_yuv_kernel).
+template <int S, int SRC, int LAYOUT>
+__global__ __launch_bounds__(kResizeThreads) void compact_tail_yuv_scaled_kernel(YuvShuffleSrc<S, yuv_bits(SRC), SRC> src, ResrYuvDesc qd,
+                                                                                 void* __restrict__ y, const int32_t* __restrict__ idx_y,
+                                                                                 const float* __restrict__ w_y, const int32_t* __restrict__ idx_x,
+                                                                                 const float* __restrict__ w_x, ResizeGeom g) {
+    resize_tile(src, OutYuv<yuv_bits(LAYOUT), LAYOUT>{&qd}, y, idx_y, w_y, idx_x, w_x, g);
 }
 
 // source pixels that t consecutive outputs of an axis (in -> out pixels, p taps) can reach
@@ -448,28 +452,32 @@ int compact_tail_u8_scaled(const float* t, const uint8_t* x, uint8_t* y, int n, 
     return RESR_OK;
 }
 
-// The fused tail of the scaled YUV ends of compact_forward_ends: x, y frames of bytes or 16-bit words as q->layout says (the caller
-// has checked it), g planned by resize_plan for c = 3, h = H * s, w = W * s, RESIZE_YUV8 / RESIZE_YUV10.
+// The fused tail of the scaled YUV ends of compact_forward_ends: x, y frames of bytes or 16-bit words as qs->layout and qd->layout
+// say (the caller has checked both), g planned by resize_plan for c = 3, h = H * s, w = W * s and the destination's RESIZE_YUV8 /
+// RESIZE_YUV10.  Profiling ids name the instance: 31070 + s / 31080 + s where the two layouts are one, 31095 + s for the mixed tails.
 int compact_tail_yuv420_scaled(const float* t, const void* x, void* y, int n, int h, int w, int s, const int32_t* idx_y, const float* w_y,
-                               const int32_t* idx_x, const float* w_x, const ResrYuvDesc* q, const ResizeGeom* gp, hipStream_t st) {
+                               const int32_t* idx_x, const float* w_x, const ResrYuvDesc* qs, const ResrYuvDesc* qd, const ResizeGeom* gp,
+                               hipStream_t st) {
     const ResizeGeom g = *gp;
-    const bool ten = yuv_bits(q->layout) == 10;
+    const bool ten = yuv_bits(qd->layout) == 10;
     const dim3 grid((unsigned)((g.ow + g.tw - 1) / g.tw), (unsigned)((g.oh + g.th - 1) / g.th), (unsigned)n);
     const size_t lds = lds_bytes(g, ten ? RESIZE_YUV10 : RESIZE_YUV8);
     prof_before(st);
     const bool ok = with_scale(s, [&](auto S) {
-        with_yuv_layout(q->layout, [&](auto L) {
-            constexpr int BITS = yuv_bits(decltype(L)::value);
-            const YuvShuffleSrc<decltype(S)::value, BITS, decltype(L)::value> src{t, (const typename Depth<BITS>::word*)x, h, w, *q};
-            hipLaunchKernelGGL((compact_tail_yuv_scaled_kernel<decltype(S)::value, BITS, decltype(L)::value>), grid, dim3(kResizeThreads), lds, st,
-                               src, y, idx_y, w_y, idx_x, w_x, g);
+        with_yuv_layout(qs->layout, [&](auto A) {
+            with_yuv_layout(qd->layout, [&](auto L) {
+                constexpr int SBITS = yuv_bits(decltype(A)::value);
+                const YuvShuffleSrc<decltype(S)::value, SBITS, decltype(A)::value> src{t, (const typename Depth<SBITS>::word*)x, h, w, *qs};
+                hipLaunchKernelGGL((compact_tail_yuv_scaled_kernel<decltype(S)::value, decltype(A)::value, decltype(L)::value>), grid,
+                                   dim3(kResizeThreads), lds, st, src, *qd, y, idx_y, w_y, idx_x, w_x, g);
+            });
         });
     });
     if (!ok) return fail(RESR_ERR_ARG, "compact_tail_yuv420_scaled: upscale %d", s);
-    // per LR pixel: 3 s^2 floats of t and 1.5 words of x; per output pixel 1.5 words
-    const double wb = ten ? 2.0 : 1.0;
-    prof_after(st, (ten ? 31080 : 31070) + s, 2.0 * n * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
-               (double)n * h * w * (s * s * 12.0 + 1.5 * wb) + (double)n * g.oh * g.ow * 1.5 * wb);
+    // per LR pixel: 3 s^2 floats of t and 1.5 source words of x; per output pixel 1.5 destination words
+    const double wb = ten ? 2.0 : 1.0, sb = yuv_bits(qs->layout) == 10 ? 2.0 : 1.0;
+    prof_after(st, (qs->layout != qd->layout ? 31095 : ten ? 31080 : 31070) + s, 2.0 * n * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
+               (double)n * h * w * (s * s * 12.0 + 1.5 * sb) + (double)n * g.oh * g.ow * 1.5 * wb);
     RESR_CHECK_LAUNCH("compact_tail_yuv_scaled_kernel");
     return RESR_OK;
 }

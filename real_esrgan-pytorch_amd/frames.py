@@ -64,8 +64,24 @@ with `float_path` the model's forward (or `tiling.super_resolve`) on fp32 NCHW, 
 with a fused entry (`SRVGGNetCompact.forward_yuv420p10`) runs it when the frame fits one call, with `outscale` too
 (`resr_compact_forward_yuv420p10_scaled`): neither an RGB frame nor an fp32 copy of the input exists then, and the fp32 frames of the
 float path exist as LDS tiles only.  Every other case is `to_yuv420p10(float_path(from_yuv420p10(f)))`, one launch each way, straight
-between the frames and fp32.  Not provided: mixed depths (8 bits in, 10 out, or the reverse), 12 / 16-bit samples (16 bits would
-overflow the int32 accumulators), full range, 4:2:2 / 4:4:4.
+between the frames and fp32.  Not provided: 12 / 16-bit samples (16 bits would overflow the int32 accumulators), full range,
+4:2:2 / 4:4:4.
+
+MIXED FRAME FORMATS -- a source and a destination format of their own: 8 bits in and 10 out (the 1024 levels of the network's fp32
+output for an 8-bit source), BT.601 in and BT.709 out (SD material upscaled to HD), NV12 / P010 surfaces in and planar frames out, rgb24
+on one side.  A frame format is a name of `PIXEL_FORMATS` plus, for the YUV names, a matrix (`FrameFormat`).  For a source `A` and a
+destination `B`, with top = 255 or 1023 of a side:
+
+    upscale_frames(model, f, A, B) == encode_B(q_B(float_path(decode_A(f) / top_A)))
+
+`decode_A`: the identity on HWC bytes ("rgb24"), else `yuv420_to_rgb_np` / `yuv420p10_to_rgb_np` with A's layout and matrix; `/ top_A` one
+fp32 IEEE division; `float_path` as above (with `outscale`: followed by `resize_with_plan`); q_B(v) = trunc(clamp(v * top_B, 0, top_B))
+in fp32; `encode_B`: the identity, else `rgb_to_yuv420_np` / `rgb_to_yuv420p10_np` with B's layout and matrix.  For A == B this is, term
+for term, what `upscale_u8`, `upscale_yuv420` and `upscale_yuv420p10` are defined as, and `upscale_frames` calls them.  YUV to YUV on a
+model with the fused entry (`SRVGGNetCompact.forward_yuv420_mixed`: the head reads A, the tail recomputes the residual from A and writes
+B) runs it when the frame fits one call -- with `outscale` where `resr_compact_yuv420_scaled_fits` finds an even tile for B's depth;
+every other case (the RRDB `Generator`, tiled frames, "rgb24" on a side, a scale with no even tile) is the composition of the generic
+launches above, the same functions on the same values, hence the same bits.
 """
 from __future__ import annotations
 
@@ -81,7 +97,8 @@ from . import _lib, tiling
 
 __all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream", "output_size", "check_outscale", "yuv420_tables", "yuv420_to_rgb_np",
            "rgb_to_yuv420_np", "yuv420_to_rgb", "rgb_to_yuv420", "upscale_yuv420", "yuv420p10_tables", "yuv420p10_to_rgb_np",
-           "rgb_to_yuv420p10_np", "from_yuv420p10", "to_yuv420p10", "upscale_yuv420p10"]
+           "rgb_to_yuv420p10_np", "from_yuv420p10", "to_yuv420p10", "upscale_yuv420p10", "PixelFormat", "PIXEL_FORMATS", "YUV_MATRICES",
+           "FrameFormat", "frame_format", "upscale_frames"]
 
 class PixelFormat(NamedTuple):
     """One row of `PIXEL_FORMATS`: everything the frame path knows about a pixel format by name.  `layout`: ResrYuvDesc.layout of
@@ -110,6 +127,35 @@ YUV_LAYOUTS = {name: f.layout for name, f in PIXEL_FORMATS.items() if f.layout i
 YUV10_LAYOUTS = {name: f.layout for name, f in PIXEL_FORMATS.items() if f.layout is not None and f.bits == 10}
 _YUV_BY_BITS = {8: (YUV_LAYOUTS, *_U8), 10: (YUV10_LAYOUTS, *_U16)}            # per depth: its layout names, numpy and torch dtype
 YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}          # (Kr, Kb); Kg = 1 - Kr - Kb
+
+
+class FrameFormat(NamedTuple):
+    """What the frames of one side of `upscale_frames` are: a name of `PIXEL_FORMATS` and, for the YUV names, one of `YUV_MATRICES`
+    ("rgb24" has none).  A plain `(pix_fmt, matrix)` pair is taken wherever a FrameFormat is; `frame_format` checks either."""
+    pix_fmt: str
+    matrix: Optional[str] = None
+
+    @property
+    def fmt(self) -> PixelFormat:
+        return PIXEL_FORMATS[self.pix_fmt]
+
+
+def frame_format(f, what: str) -> FrameFormat:
+    """`f` (a FrameFormat, a `(pix_fmt, matrix)` pair, or the bare name "rgb24") as a checked FrameFormat; ValueError for a name that is
+    not in PIXEL_FORMATS, a matrix that is not in YUV_MATRICES (a YUV name needs one) and a matrix given for "rgb24"."""
+    if isinstance(f, str):
+        f = (f,)
+    if not isinstance(f, (tuple, list)) or not 1 <= len(f) <= 2:
+        raise ValueError(f"{what}: a frame format is a FrameFormat or a (pix_fmt, matrix) pair, got {f!r}")
+    f = FrameFormat(*f)
+    if not isinstance(f.pix_fmt, str) or f.pix_fmt not in PIXEL_FORMATS:
+        raise ValueError(f"{what}: pix_fmt must be one of {tuple(PIXEL_FORMATS)}, got {f.pix_fmt!r}")
+    if f.fmt.layout is None:
+        if f.matrix is not None:
+            raise ValueError(f"{what}: rgb24 takes no matrix, got {f.matrix!r}")
+    elif not isinstance(f.matrix, str) or f.matrix not in YUV_MATRICES:
+        raise ValueError(f"{what}: the matrix of {f.pix_fmt!r} must be one of {sorted(YUV_MATRICES)}, got {f.matrix!r}")
+    return f
 
 
 def check_outscale(outscale, s: int, what: str) -> Optional[float]:
@@ -487,12 +533,82 @@ def upscale_yuv420p10(model, frames: torch.Tensor, layout: str = "i420p10", matr
     return _upscale_yuv(model, frames, layout, matrix, outscale, plan, 10, compose)
 
 
+# ---- a source and a destination format of their own (module docstring, MIXED FRAME FORMATS) --------------------------------------
+def format_desc(f: FrameFormat) -> _lib.YuvDesc:
+    """The ResrYuvDesc of a checked YUV frame format."""
+    return _desc(f.fmt.bits, f.pix_fmt, f.matrix)
+
+
+def mixed_geometry(frames, a: FrameFormat, b: FrameFormat, s: int, o: Optional[float], what: str) -> Optional[Tuple[int, int, int, int]]:
+    """(H, W, out_h, out_w) of `frames` in format `a` through a model of factor s (at outscale `o`) into format `b`, from the shape alone:
+    ValueError for a YUV source that is not [N,3H/2,W] with H and W even, and for a YUV destination whose height or width comes out odd.
+    None for a shape the device-side checks will refuse anyway."""
+    shape = tuple(getattr(frames, "shape", ()))
+    if a.fmt.layout is None:
+        if len(shape) != 4 or shape[3] != 3 or min(shape) < 1:
+            return None
+        h, w = shape[1], shape[2]
+    else:
+        hw = _yuv_hw(shape) if len(shape) == 3 and shape[0] >= 1 else None
+        if hw is None:
+            raise ValueError(f"{what}: a {a.pix_fmt} frame batch is [N,3H/2,W] with H and W even (rows a multiple of 3), got {shape}")
+        h, w = hw
+    out_h, out_w = output_size(h, w, s, o) if b.fmt.layout is None else yuv420_output_size(h, w, s, o, what)
+    return h, w, out_h, out_w
+
+
+@torch.no_grad()
+def upscale_frames(model, frames: torch.Tensor, src, dst=None, halo: Optional[int] = None, outscale: Optional[float] = None,
+                   plan=None) -> torch.Tensor:
+    """Frames in the format `src` on the model's device -> the upscaled frames in the format `dst` (None: `src`); each a `FrameFormat`
+    or a `(pix_fmt, matrix)` pair: uint8 [N,H,W,3] for "rgb24", else [N,3H/2,W] uint8 ("i420", "nv12") or uint16 ("i420p10", "p010").
+    Bit for bit `encode_dst(q_dst(float_path(decode_src(frames) / top_src)))` (module docstring, MIXED FRAME FORMATS).  The one place
+    that chooses: the same format on both sides is `upscale_u8` / `upscale_yuv420` / `upscale_yuv420p10`; YUV to YUV on a model with
+    `forward_yuv420_mixed`, a frame that fits one call and (with `outscale`) an even tile for the destination's depth is that fused
+    call; everything else is the composition of the generic launches.  `halo`, `outscale`, `plan`: `upscale_u8`'s.  ValueError before
+    the device is looked at: an unknown format or matrix, a matrix for "rgb24", an odd YUV source, an odd size of a YUV result."""
+    what = "upscale_frames"
+    a = frame_format(src, what)
+    b = a if dst is None else frame_format(dst, what)
+    s = model.upscale_factor
+    o = check_outscale(outscale, s, what)
+    geom = mixed_geometry(frames, a, b, s, o, what)
+    if a == b:
+        if a.fmt.layout is None:
+            return upscale_u8(model, frames, halo, outscale=o, plan=plan)
+        same = upscale_yuv420 if a.fmt.bits == 8 else upscale_yuv420p10
+        return same(model, frames, a.pix_fmt, a.matrix, halo, outscale=o, plan=plan)
+    if a.fmt.layout is None:
+        _check_frames(frames, what)
+        n = frames.shape[0]
+    else:
+        n = _check_yuv(frames, what, a.fmt.bits)[0]
+    h, w = geom[:2]
+    plan = _resize_plan(h, w, s, o, frames.device, plan)                      # ValueError before any launch, as in upscale_u8
+    yuv_both = a.fmt.layout is not None and b.fmt.layout is not None
+    if yuv_both and hasattr(model, "forward_yuv420_mixed") and tiling.fits_whole(model, n, h, w):
+        if o is None or _lib.lib().resr_compact_yuv420_scaled_fits(h, w, s, plan.out_h, plan.out_w, plan.taps_y, plan.taps_x, b.fmt.bits):
+            return model.forward_yuv420_mixed(frames, a, b, outscale=o, plan=plan)
+    # the composition: the generic launch(es) of the way in, the float path, those of the way out
+    if a.fmt.bits == 10:
+        x = from_yuv420p10(frames, a.pix_fmt, a.matrix)
+    else:
+        x = from_u8(frames if a.fmt.layout is None else yuv420_to_rgb(frames, a.pix_fmt, a.matrix))
+    sr = tiling.super_resolve(model, x, halo)
+    if o is not None:
+        from .imgproc import resize_with_plan
+    if b.fmt.bits == 10:
+        return to_yuv420p10(sr if o is None else resize_with_plan(sr, plan), b.pix_fmt, b.matrix)
+    rgb = to_u8(sr) if o is None else resize_with_plan(sr, plan, u8=True)
+    return rgb if b.fmt.layout is None else rgb_to_yuv420(rgb, b.pix_fmt, b.matrix)
+
+
 class _Slot:
     """One frame in flight: pinned host buffers, the device input, the events that order its three stages."""
 
-    def __init__(self, in_shape: Tuple[int, ...], out_shape: Tuple[int, ...], device, dtype=torch.uint8) -> None:
+    def __init__(self, in_shape: Tuple[int, ...], out_shape: Tuple[int, ...], device, dtype=torch.uint8, out_dtype=None) -> None:
         self.pin_in = torch.empty((1,) + in_shape, dtype=dtype, pin_memory=True)
-        self.pin_out = torch.empty((1,) + out_shape, dtype=dtype, pin_memory=True)
+        self.pin_out = torch.empty((1,) + out_shape, dtype=out_dtype or dtype, pin_memory=True)
         self.np_in, self.np_out = self.pin_in.numpy()[0], self.pin_out.numpy()[0]
         self.dev_in = torch.empty((1,) + in_shape, dtype=dtype, device=device)
         self.dev_out: Optional[torch.Tensor] = None      # held until the slot's next submit: its download has been waited for by then
@@ -520,18 +636,27 @@ class FrameStream:
     `pix_fmt`: "rgb24" (default: everything above) or a YUV 4:2:0 layout, "i420" / "nv12" (module docstring), with `matrix`
     "bt601" / "bt709": `submit` takes a [3H/2, W] uint8 ndarray and `result` returns [3 out_h / 2, out_w]; each frame is
     `upscale_yuv420` of it, the slots are half the bytes, everything else is as above.  "i420p10" / "p010" (10-bit 4:2:0, module
-    docstring): the same with uint16 ndarrays, each frame `upscale_yuv420p10` of it, the slots 3 bytes per pixel as for rgb24."""
+    docstring): the same with uint16 ndarrays, each frame `upscale_yuv420p10` of it, the slots 3 bytes per pixel as for rgb24.
+
+    `out_pix_fmt`, `out_matrix`: the format of the results when it is not the input's (None, the default: the input's) -- "nv12" in
+    and "p010" out, "bt601" in and "bt709" out, "rgb24" on one side (then `out_matrix` stays None); each frame is `upscale_frames` of
+    it (module docstring, MIXED FRAME FORMATS) and the output slots get the result's dtype and shape (`slot_layout`)."""
 
     PIX_FMTS = tuple(PIXEL_FORMATS)
 
-    def __init__(self, model, depth: int = 2, outscale: Optional[float] = None, pix_fmt: str = "rgb24", matrix: str = "bt601") -> None:
+    def __init__(self, model, depth: int = 2, outscale: Optional[float] = None, pix_fmt: str = "rgb24", matrix: str = "bt601",
+                 out_pix_fmt: Optional[str] = None, out_matrix: Optional[str] = None) -> None:
         if isinstance(depth, bool) or not isinstance(depth, int) or depth < 1:
             raise ValueError(f"FrameStream: depth must be an int >= 1, got {depth!r}")
         if pix_fmt not in self.PIX_FMTS:
             raise ValueError(f"FrameStream: pix_fmt must be one of {self.PIX_FMTS}, got {pix_fmt!r}")
         _check_matrix(matrix, "FrameStream")
         self.pix_fmt, self.matrix = pix_fmt, matrix
-        self._fmt = _StreamFormat(pix_fmt, matrix)
+        # what is not given is the input's; a result in rgb24 has no matrix, and one given for it is refused
+        self.out_pix_fmt = pix_fmt if out_pix_fmt is None else out_pix_fmt
+        self.out_matrix = out_matrix if out_matrix is not None or self.out_pix_fmt == "rgb24" else matrix
+        frame_format((self.out_pix_fmt, self.out_matrix), "FrameStream")
+        self._fmt = _StreamFormat(pix_fmt, matrix, self.out_pix_fmt, self.out_matrix)
         self.outscale = check_outscale(outscale, getattr(model, "upscale_factor", 0), "FrameStream")
         self._plan = None
         param = next(iter(model.parameters()), None)
@@ -557,6 +682,12 @@ class FrameStream:
     @staticmethod
     def check_frame_yuv420p10(frame) -> None:
         _check_host_frame(frame, PIXEL_FORMATS["i420p10"])
+
+    def slot_layout(self, h: int, w: int):
+        """((in_shape, in_dtype), (out_shape, out_dtype)) of the slots of an h x w frame, numpy dtypes: what `submit` takes and
+        `result` returns.  No device work; ValueError for a result the output format cannot hold (an odd 4:2:0 size)."""
+        in_shape, out_shape = self._fmt.shapes(h, w, self.model.upscale_factor, self.outscale)
+        return (in_shape, self._fmt.fmt.np_dtype), (out_shape, self._fmt.out_fmt.np_dtype)
 
     def __len__(self) -> int:
         """Results not yet taken."""
@@ -584,7 +715,7 @@ class FrameStream:
         in_shape, out_shape = self._fmt.shapes(h, w, s, self.outscale)     # an odd 4:2:0 result: ValueError before anything is allocated
         self._plan = _resize_plan(h, w, s, self.outscale, self.device)
         with torch.cuda.device(self.device):
-            self._slots = [_Slot(in_shape, out_shape, self.device, self._fmt.dtype) for _ in range(self.depth)]
+            self._slots = [_Slot(in_shape, out_shape, self.device, self._fmt.dtype, self._fmt.out_dtype) for _ in range(self.depth)]
         self._shape, self._next = (h, w), 0
 
     def submit(self, frame: np.ndarray) -> None:
@@ -664,24 +795,32 @@ def _check_host_frame(frame, fmt: PixelFormat) -> None:
 class _StreamFormat:
     """What FrameStream asks of its pixel format, answered from its row of PIXEL_FORMATS: `dtype` of the slots; `size(frame)` checks
     a host frame and returns its (h, w); `shapes(h, w, s, outscale)` the slots' (in_shape, out_shape), ValueError for a result the
-    format cannot hold; `upscale(model, dev_in, outscale, plan)` runs one slot on the device."""
+    format cannot hold; `upscale(model, dev_in, outscale, plan)` runs one slot on the device.  `out_name`, `out_matrix`: the
+    destination, None for the source's -- then everything is as it was with one format; else `out_dtype` and the output shape are
+    the destination's and a slot runs `upscale_frames`."""
 
-    def __init__(self, name: str, matrix: str) -> None:
+    def __init__(self, name: str, matrix: str, out_name: Optional[str] = None, out_matrix: Optional[str] = None) -> None:
         self.name, self.matrix, self.fmt = name, matrix, PIXEL_FORMATS[name]
         self.dtype, self.rgb = self.fmt.torch_dtype, self.fmt.layout is None
+        self.out_name = name if out_name is None else out_name
+        self.out_fmt = PIXEL_FORMATS[self.out_name]
+        self.out_dtype, self.out_rgb = self.out_fmt.torch_dtype, self.out_fmt.layout is None
+        self.out_matrix = matrix if out_matrix is None and not self.out_rgb else out_matrix
+        # one format on both sides (rgb24 has no matrix to differ in): the same-format functions, as before there was a destination
+        self.mixed = self.out_name != name or (not self.rgb and self.out_matrix != matrix)
 
     def size(self, frame):
         _check_host_frame(frame, self.fmt)
         return frame.shape[:2] if self.rgb else _yuv_hw(frame.shape)
 
     def shapes(self, h, w, s, outscale):
-        if self.rgb:
-            out_h, out_w = output_size(h, w, s, outscale)
-            return (h, w, 3), (out_h, out_w, 3)
-        out_h, out_w = yuv420_output_size(h, w, s, outscale, "FrameStream")
-        return (h * 3 // 2, w), (out_h * 3 // 2, out_w)
+        out_h, out_w = output_size(h, w, s, outscale) if self.out_rgb else yuv420_output_size(h, w, s, outscale, "FrameStream")
+        return (h, w, 3) if self.rgb else (h * 3 // 2, w), (out_h, out_w, 3) if self.out_rgb else (out_h * 3 // 2, out_w)
 
     def upscale(self, model, dev_in, outscale, plan):
+        if self.mixed:
+            return upscale_frames(model, dev_in, (self.name, None if self.rgb else self.matrix),
+                                  (self.out_name, None if self.out_rgb else self.out_matrix), outscale=outscale, plan=plan)
         if self.rgb:
             return upscale_u8(model, dev_in, outscale=outscale, plan=plan)
         fn = upscale_yuv420 if self.fmt.bits == 8 else upscale_yuv420p10

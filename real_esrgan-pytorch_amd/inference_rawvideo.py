@@ -2,8 +2,8 @@
 and an encoder, with no colour conversion on the host and no dependency beyond this package.
 
     python -m real_esrgan_pytorch_amd.inference_rawvideo --input in.yuv --output out.yuv --size 1920x1080 --weights_path g.pth \\
-        [--pix_fmt yuv420p|nv12|yuv420p10le|p010le --matrix bt601|bt709 --model_type rrdb|compact --num_conv 16 --act_type prelu
-         --precision fast|exact16|strict --depth 2 --outscale 2]
+        [--pix_fmt yuv420p|nv12|yuv420p10le|p010le --matrix bt601|bt709 --out_pix_fmt ... --out_matrix ... --model_type rrdb|compact
+         --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2]
 
     ffmpeg -i in.mp4 -f rawvideo -pix_fmt yuv420p - | \\
         python -m real_esrgan_pytorch_amd.inference_rawvideo --input - --output - --size 1920x1080 --model_type compact \\
@@ -14,6 +14,9 @@ and an encoder, with no colour conversion on the host and no dependency beyond t
 formats) or W * H * 3 bytes (`yuv420p10le` / `p010le`: a little-endian 16-bit word per sample; use the same `-pix_fmt` on both ffmpeg
 pipes) are read one after the other and streamed through `FrameStream(pix_fmt=...)` with `copy=False`; each written frame is
 `frames.upscale_yuv420` (`frames.upscale_yuv420p10`) of the frame read, in the same pixel format.  The output size is printed (the encoder has to be told it).
+`--out_pix_fmt` / `--out_matrix` (default: the input's) write another format than the one read -- an 8-bit source as 10-bit frames,
+BT.601 in and BT.709 out, NV12 surfaces in and planar frames out: each written frame is `frames.upscale_frames` of the frame read
+(frames.py, MIXED FRAME FORMATS); the second ffmpeg pipe takes the output's `-pix_fmt`.
 A trailing partial frame is an error that names its byte count.  The model is built and the checkpoint loaded as `inference.py`
 does (inference_frames.build_model).
 """
@@ -69,30 +72,38 @@ def read_frames(stream, w: int, h: int, word=np.uint8):
         index += 1
 
 
+def formats(args):
+    """(pix_fmt, matrix, out_pix_fmt, out_matrix) of the arguments, rawvideo names: the output's default to the input's."""
+    pix_fmt = getattr(args, "pix_fmt", "yuv420p") or "yuv420p"
+    matrix = getattr(args, "matrix", "bt601") or "bt601"
+    out_pix_fmt = getattr(args, "out_pix_fmt", None) or pix_fmt
+    for flag, name in (("--pix_fmt", pix_fmt), ("--out_pix_fmt", out_pix_fmt)):
+        if name not in PIX_FMTS:
+            raise ValueError(f"{flag} must be one of {sorted(PIX_FMTS)}, got {name!r}")
+    return pix_fmt, matrix, out_pix_fmt, getattr(args, "out_matrix", None) or matrix
+
+
 def main(args) -> int:
     w, h = parse_size(args.size)
-    pix_fmt = getattr(args, "pix_fmt", "yuv420p") or "yuv420p"
-    if pix_fmt not in PIX_FMTS:
-        raise ValueError(f"--pix_fmt must be one of {sorted(PIX_FMTS)}, got {pix_fmt!r}")
-    layout = PIX_FMTS[pix_fmt]
-    word = WORD[layout]
-    matrix = getattr(args, "matrix", "bt601") or "bt601"
+    pix_fmt, matrix, out_pix_fmt, out_matrix = formats(args)
+    layout, out_layout = PIX_FMTS[pix_fmt], PIX_FMTS[out_pix_fmt]
+    word, out_word = WORD[layout], WORD[out_layout]
     log = sys.stderr if args.output == "-" else sys.stdout
     torch.cuda.set_device(config.device)
     with contextlib.redirect_stdout(log):
         model = build_model(args)
     outscale = getattr(args, "outscale", None)
     out_h, out_w = yuv420_output_size(h, w, model.upscale_factor, outscale, "inference_rawvideo")
-    print(f"Output size {out_w}x{out_h} ({pix_fmt}, {frame_bytes(out_w, out_h, word)} bytes per frame).", file=log)
+    print(f"Output size {out_w}x{out_h} ({out_pix_fmt}, {frame_bytes(out_w, out_h, out_word)} bytes per frame).", file=log)
     count = 0
     with contextlib.ExitStack() as stack:
         src = sys.stdin.buffer if args.input == "-" else stack.enter_context(open(args.input, "rb"))
         dst = sys.stdout.buffer if args.output == "-" else stack.enter_context(open(args.output, "wb"))
         stream = stack.enter_context(FrameStream(model, depth=getattr(args, "depth", 2) or 2, outscale=outscale, pix_fmt=layout,
-                                                 matrix=matrix))
+                                                 matrix=matrix, out_pix_fmt=out_layout, out_matrix=out_matrix))
         # copy=False: the pinned view is written out before the next result is asked for, i.e. before its slot is submitted to again
         for sr in stream.map(read_frames(src, w, h, word), copy=False):
-            dst.write(sr.astype(word, copy=False).data)     # (little-endian words: a view on every host this runs on)
+            dst.write(sr.astype(out_word, copy=False).data)     # (little-endian words: a view on every host this runs on)
             count += 1
         dst.flush()
     print(f"{count} frames written to `{args.output}`.", file=log)
@@ -104,8 +115,10 @@ def get_parser() -> argparse.ArgumentParser:
     parser.add_argument("--input", type=str, required=True, help="Raw video file, or - for stdin.")
     parser.add_argument("--output", type=str, required=True, help="Raw video file, or - for stdout.")
     parser.add_argument("--size", type=str, required=True, help="Input frame size WxH (both even), e.g. 1920x1080.")
-    parser.add_argument("--pix_fmt", type=str, default="yuv420p", choices=sorted(PIX_FMTS), help="pixel format of input and output")
+    parser.add_argument("--pix_fmt", type=str, default="yuv420p", choices=sorted(PIX_FMTS), help="pixel format of the input (and of the output, unless --out_pix_fmt)")
     parser.add_argument("--matrix", type=str, default="bt601", choices=["bt601", "bt709"], help="colour matrix (studio range)")
+    parser.add_argument("--out_pix_fmt", type=str, default=None, choices=sorted(PIX_FMTS), help="pixel format of the output (default: --pix_fmt)")
+    parser.add_argument("--out_matrix", type=str, default=None, choices=["bt601", "bt709"], help="colour matrix of the output (default: --matrix)")
     parser.add_argument("--weights_path", type=str, required=True, help="Model weights file path.")
     parser.add_argument("--precision", type=str, default=None, choices=["fast", "exact16", "strict"],
                         help="kernel arithmetic; default config.inference_precision = exact16")

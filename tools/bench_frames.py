@@ -35,8 +35,19 @@ way, per case (with `--outscale O` every path below runs at that final factor; t
 names; its paths are `upscale_yuv420p10` / `FrameStream(pix_fmt=<fmt>)` and its check the composition over the generic launches.
 
     python tools/bench_frames.py --pix_fmt i420 i420p10 p010 --out profiles/frames_yuv420p10_1080p.jsonl
+
+`--out_pix_fmt FMT [--out_matrix M]` adds, for every `--pix_fmt` source, the mixed path to FMT (frames.py, MIXED FRAME FORMATS) next to the
+same-format paths of the source and of FMT (FMT joins the list if it is not on it):
+  dev/forward_<src>_to_<FMT>      upscale_frames(frame, (src, bt601), (FMT, M)): the fused mixed call
+  dev/composed_<src>_to_<FMT>     the same result as the composition over the generic launches (with --outscale)
+  B2/2/<src>_to_<FMT>, .../view   FrameStream(depth=2, pix_fmt=src, out_pix_fmt=FMT, out_matrix=M)
+and the summary reports `tail_ms`: the device time of the last launch of each dev/forward_* call (the tail, by the library's own
+per-launch timer, median of 5 calls outside the timed rounds) and whether the mixed tail lies between the two same-format ones.
+
+    python tools/bench_frames.py --pix_fmt nv12 --out_pix_fmt p010 --outscale 2 --out profiles/frames_mixed_outscale_1080p.jsonl
 """
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -240,9 +251,32 @@ def mode_outscale(args):
     return build
 
 
+def tail_ms(fn, repeats=5):
+    """(kernel id, ms) of the last launch of `fn()`, by the library's in-situ profiler: the median of `repeats` calls."""
+    lib = R._lib.lib()
+    ms, kid = [], None
+    for _ in range(repeats):
+        lib.resr_profile_begin()
+        try:
+            fn()
+        finally:
+            torch.cuda.synchronize()
+            buf = (R._lib.ProfEntry * 4096)()
+            n = int(lib.resr_profile_end(ctypes.cast(buf, ctypes.c_void_p), 4096))
+        kid = buf[n - 1].kernel_id
+        ms.append(buf[n - 1].ms)
+    return kid, round(statistics.median(ms), 4)
+
+
 def mode_yuv(args):
     o = args.outscale
     pool, many = frame_pool(args)
+    dst = args.out_pix_fmt
+    sources = list(args.pix_fmt)
+    if dst and dst not in args.pix_fmt:
+        args.pix_fmt = list(args.pix_fmt) + [dst]          # the destination's own same-format path, next to the mixed one
+    dst_matrix = args.out_matrix or "bt601"
+    mixed = [(a, dst) for a in sources if (a, "bt601") != (dst, dst_matrix)] if dst else []
     # the same pictures as 4:2:0 frames, so that every path upscales the same content
     ten = set(R.frames.YUV10_LAYOUTS)
 
@@ -265,12 +299,22 @@ def mode_yuv(args):
             return R.to_yuv420p10(sr, fmt)
         return R.rgb_to_yuv420(R.upscale_u8(model, R.yuv420_to_rgb(x, fmt), outscale=o), fmt)
 
+    def composed_mixed(model, x, a, b):     # a's generic launches in, the float path, b's out
+        sr = model(R.from_yuv420p10(x, a) if a in ten else R.from_u8(R.yuv420_to_rgb(x, a)))
+        if scaled and x.device not in plans:
+            plans[x.device] = imgproc.ResizePlan(H * S, W * S, o / S, x.device)
+        if b in ten:
+            return R.to_yuv420p10(imgproc.resize_with_plan(sr, plans[x.device]) if scaled else sr, b, dst_matrix)
+        return R.rgb_to_yuv420(imgproc.resize_with_plan(sr, plans[x.device], u8=True) if scaled else R.to_u8(sr), b, dst_matrix)
+
     yuv = {fmt: [to_yuv(f, fmt) for f in pool] for fmt in args.pix_fmt}
     many_yuv = {fmt: [yuv[fmt][i % 4] for i in range(args.frames * 4)] for fmt in args.pix_fmt}
     oh, ow = R.output_size(H, W, S, o)
     rgb_bytes = dict(h2d_bytes_per_frame=H * W * 3, d2h_bytes_per_frame=oh * ow * 3)
     yuv_bytes = {fmt: dict(h2d_bytes_per_frame=H * W * 3 // 2 * (2 if fmt in ten else 1),
                            d2h_bytes_per_frame=oh * ow * 3 // 2 * (2 if fmt in ten else 1)) for fmt in args.pix_fmt}
+    mixed_bytes = {(a, b): dict(h2d_bytes_per_frame=yuv_bytes[a]["h2d_bytes_per_frame"], d2h_bytes_per_frame=yuv_bytes[b]["d2h_bytes_per_frame"])
+                   for a, b in mixed}
 
     def build(model):
         streams = {"rgb24": R.FrameStream(model, depth=2, outscale=o)}
@@ -287,12 +331,23 @@ def mode_yuv(args):
                 dev[f"dev/composed_{fmt}"] = lambda fmt=fmt: composed(model, x_yuv[fmt], fmt)
             paths[f"B2/2/{fmt}"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr)), yuv_bytes[fmt])
             paths[f"B2/2/{fmt}/view"] = (many_yuv[fmt], lambda fr, fmt=fmt: count(streams[fmt].map(fr, copy=False)), yuv_bytes[fmt])
+        for a, b in mixed:
+            key = f"{a}_to_{b}"
+            streams[key] = R.FrameStream(model, depth=2, outscale=o, pix_fmt=a, out_pix_fmt=b, out_matrix=dst_matrix)
+            dev[f"dev/forward_{key}"] = lambda a=a, b=b: R.upscale_frames(model, x_yuv[a], (a, "bt601"), (b, dst_matrix), outscale=o)
+            if scaled:
+                dev[f"dev/composed_{key}"] = lambda a=a, b=b: composed_mixed(model, x_yuv[a], a, b)
+            paths[f"B2/2/{key}"] = (many_yuv[a], lambda fr, key=key: count(streams[key].map(fr)), mixed_bytes[(a, b)])
+            paths[f"B2/2/{key}/view"] = (many_yuv[a], lambda fr, key=key: count(streams[key].map(fr, copy=False)), mixed_bytes[(a, b)])
 
         def check():     # the definition, on a timed frame: the stream's result is the composition over the RGB path
             same = {}
             for fmt in args.pix_fmt:
                 want = composed(model, x_yuv[fmt], fmt)[0].cpu().numpy()
                 same[fmt] = bool(np.array_equal(next(iter(streams[fmt].map(yuv[fmt][:1]))), want))
+            for a, b in mixed:
+                want = composed_mixed(model, x_yuv[a], a, b)[0].cpu().numpy()
+                same[f"{a}_to_{b}"] = bool(np.array_equal(next(iter(streams[f"{a}_to_{b}"].map(yuv[a][:1]))), want))
             return same
 
         def summary(med, spread, ms, same):
@@ -307,9 +362,21 @@ def mode_yuv(args):
                     line[f"device_{fmt}_fused_over_composed"] = round(med[a] / med[b], 3)
                     line[f"device_{fmt}_fused_minus_composed_ms"] = round(med[a] - med[b], 3)
                     line[f"device_{fmt}_fused_not_slower_beyond_spread"] = bool(med[a] <= med[b] + max(spread[a], spread[b]))
+            if mixed:            # the tails alone: the mixed one reads the source's words and writes the destination's
+                with torch.no_grad():
+                    tails = {name[len("dev/forward_"):]: tail_ms(fn) for name, fn in dev.items() if name.startswith("dev/forward_") and name != "dev/forward_u8"}
+                line["tail_ms"] = {k: dict(kernel_id=v[0], ms=v[1]) for k, v in tails.items()}
+                for a, b in mixed:
+                    key = f"{a}_to_{b}"
+                    lo, hi = sorted((tails[a][1], tails[b][1]))
+                    line[f"tail_{key}_between_same_format_tails"] = bool(lo <= tails[key][1] <= hi)
+                    line[f"device_{key}_over_{a}"] = round(med[f"dev/forward_{key}"] / med[f"dev/forward_{a}"], 3)
+                    line[f"device_{key}_over_{b}"] = round(med[f"dev/forward_{key}"] / med[f"dev/forward_{b}"], 3)
+                    line[f"stream_{key}_over_{a}_frames_per_s"] = round(med[f"B2/2/{a}"] / med[f"B2/2/{key}"], 2)
+                    line[f"stream_view_{key}_over_{a}_frames_per_s"] = round(med[f"B2/2/{a}/view"] / med[f"B2/2/{key}/view"], 2)
             return line
 
-        return SimpleNamespace(head=dict(pix_fmt=list(args.pix_fmt), outscale=o), frame=f"{W}x{H}->{ow}x{oh}", host_first=False, gbps=True,
+        return SimpleNamespace(head=dict(pix_fmt=list(args.pix_fmt), outscale=o, **(dict(out_pix_fmt=dst, out_matrix=dst_matrix) if dst else {})), frame=f"{W}x{H}->{ow}x{oh}", host_first=False, gbps=True,
                                dev=dev, dev_extra={}, paths=paths, streams=list(streams.values()), summary=summary, check=check)
 
     return build
@@ -324,7 +391,12 @@ def main():
     ap.add_argument("--outscale", type=float, default=None, help="measure the outscale path at this final factor instead (see above)")
     ap.add_argument("--pix_fmt", nargs="+", default=None, choices=["i420", "nv12", "i420p10", "p010"],
                     help="measure the YUV 4:2:0 path in these layouts (8-bit, or the 10-bit i420p10 / p010) against rgb24 instead (see above; combines with --outscale)")
+    ap.add_argument("--out_pix_fmt", default=None, choices=["i420", "nv12", "i420p10", "p010"],
+                    help="with --pix_fmt: also measure the mixed path from every --pix_fmt source to this format (see above)")
+    ap.add_argument("--out_matrix", default=None, choices=["bt601", "bt709"], help="the matrix of --out_pix_fmt (default bt601, the sources')")
     args = ap.parse_args()
+    if args.out_pix_fmt and not args.pix_fmt:
+        ap.error("--out_pix_fmt needs --pix_fmt (the sources)")
     assert torch.cuda.is_available(), "bench_frames.py measures on the GPU"
     mode = mode_yuv if args.pix_fmt else mode_outscale if args.outscale is not None else mode_x4
     run_cases(args, mode(args))
