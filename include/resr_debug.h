@@ -36,6 +36,29 @@ int resr_debug_wgrad_dense_blocks(int32_t nblocks, const void* const* x_ws, cons
 /* test probe: lane/element map of ds_read_b64_tr_b16 (256 floats out) */
 int resr_debug_tr_probe(float* out256, void* stream);
 
+/* Test entries (tests/test_gpu_disc_helpers.py) of the discriminator helpers that the product reaches only from inside the native
+ * passes (csrc/disc_native.hip): the existing dispatch functions, callable alone.  Shapes, types and RESR_F16X2 pairs as for the
+ * helpers of resr.h -- every lo tensor directly behind its hi tensor.
+ * resr_debug_d2s_add_mask: out[n,h,w,c] = (depth_to_space(src[n,h/2,w/2,4c]) + add) * (mask > 0 ? 1 : slope); add, mask optional,
+ *   both of out's shape.  The sign of a RESR_F16X2 mask is its hi tensor's, or its lo tensor's where hi is zero.
+ * resr_debug_bilinear_up2x_bwd_mask: gin[n,h,w,c] = resr_bilinear_up2x's backward of g[n,2h,2w,c], and in the same pass
+ *   gmasked = gin * (mask > 0 ? 1 : slope); the mask (same sign rule) and gmasked have gin's shape. */
+int resr_debug_d2s_add_mask(const void* src, const void* add, const void* mask, void* out, int32_t n, int32_t h, int32_t w, int32_t c,
+                            int32_t dtype, float slope, void* stream);
+int resr_debug_bilinear_up2x_bwd_mask(const void* g, void* gin, const void* mask, void* gmasked, int32_t n, int32_t h, int32_t w,
+                                      int32_t c, int32_t dtype, float slope, void* stream);
+/* The batched launches: `n` layers at once (<= 8; fold: <= 4) through HOST arrays of device pointers and of sizes; per layer the
+ * operands of resr_spectral_norm / resr_spectral_norm_bwd (accumulate = 0) / resr_fold4x4, and bit-identical results.
+ * tmp[i] = rows[i] + ceil(rows[i] / 32) * cols[i] floats; dot = 8 * 512 floats shared by the layers. */
+int resr_debug_spectral_norm_batch(int32_t n, const float* const* w, float* const* u, float* const* v, const int32_t* rows,
+                                   const int32_t* cols, int32_t training, float eps, float* const* sigma2, float* const* tmp,
+                                   void* stream);
+int resr_debug_spectral_norm_bwd_batch(int32_t n, const float* const* g, const float* const* w, const float* const* u,
+                                       const float* const* v, const float* const* sigma2, float* const* dst, const int32_t* rows,
+                                       const int32_t* cols, float* dot, void* stream);
+int resr_debug_fold4x4_batch(int32_t n, const float* const* dw3, float* const* dw4, const int32_t* cout, const int32_t* c,
+                             void* stream);
+
 /* What THIS board sustains once it sits at its power cap (bench.py's `roofline.vs_sustained`): 256 workgroups launched back to
  * back for `seconds` (last third timed) -- mode 1: an LDS-DMA stream over `src` (`bytes` >= 64 MB of readable device memory),
  * mode 2: eight waves per workgroup issuing v_mfma_f32_32x32x16_f16 on random f16 operands, mode 3: both at once.  Returns the

@@ -150,6 +150,13 @@ int spectral_norm_dispatch(const float*, float*, float*, int, int, int, float, f
 int spectral_norm_bwd_dispatch(const float*, const float*, const float*, const float*, const float*, float*, int, int, int, float*,
                                hipStream_t);
 int fold4x4_dispatch(const float*, float*, int, int, hipStream_t);
+int d2s_add_mask_dispatch(const void*, const void*, const void*, void*, int, int, int, int, int, float, hipStream_t, long, long, long);
+int bilinear_up_bwd_mask_dispatch(const void*, void*, const void*, void*, int, int, int, int, int, float, hipStream_t, long, long);
+int spectral_norm_batch_dispatch(int, const float* const*, float* const*, float* const*, const int*, const int*, int, float, float* const*,
+                                 float* const*, hipStream_t);
+int spectral_norm_bwd_batch_dispatch(int, const float* const*, const float* const*, const float* const*, const float* const*, const float* const*,
+                                     float* const*, const int*, const int*, float*, hipStream_t);
+int fold4x4_batch_dispatch(int, const float* const*, float* const*, const int*, const int*, hipStream_t);
 int maxpool2x2_dispatch(const void*, void*, int, int, int, int, int, hipStream_t, long, long, uint8_t*);
 int maxpool2x2_bwd_dispatch(const void*, const uint8_t*, void*, int, int, int, int, int, hipStream_t, long, long);
 
@@ -588,6 +595,42 @@ int resr_maxpool2x2_bwd(const void* g, const uint8_t* arg, void* gin, int32_t n,
 int resr_fold4x4(const float* dw3, float* dw4, int32_t cout, int32_t c, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return fold4x4_dispatch(dw3, dw4, cout, c, (hipStream_t)stream);
+}
+
+// test entries of the helpers that only the native discriminator passes call (include/resr_debug.h); RESR_F16X2: every lo tensor
+// directly behind its hi tensor
+int resr_debug_d2s_add_mask(const void* src, const void* add, const void* mask, void* out, int32_t n, int32_t h, int32_t w, int32_t c,
+                            int32_t dtype, float slope, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    const long px = dtype == RESR_F16X2 ? (long)n * h * w * c : 0L;   // src [n,h/2,w/2,4c], add and out [n,h,w,c]: the same element count
+    return d2s_add_mask_dispatch(src, add, mask, out, n, h, w, c, dtype, slope, (hipStream_t)stream, px, px, px);
+}
+
+int resr_debug_bilinear_up2x_bwd_mask(const void* g, void* gin, const void* mask, void* gmasked, int32_t n, int32_t h, int32_t w,
+                                      int32_t c, int32_t dtype, float slope, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    const long px = dtype == RESR_F16X2 ? (long)n * h * w * c : 0L;
+    return bilinear_up_bwd_mask_dispatch(g, gin, mask, gmasked, n, h, w, c, dtype, slope, (hipStream_t)stream, 4 * px, px);
+}
+
+int resr_debug_spectral_norm_batch(int32_t n, const float* const* w, float* const* u, float* const* v, const int32_t* rows,
+                                   const int32_t* cols, int32_t training, float eps, float* const* sigma2, float* const* tmp,
+                                   void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return spectral_norm_batch_dispatch(n, w, u, v, rows, cols, training, eps, sigma2, tmp, (hipStream_t)stream);
+}
+
+int resr_debug_spectral_norm_bwd_batch(int32_t n, const float* const* g, const float* const* w, const float* const* u,
+                                       const float* const* v, const float* const* sigma2, float* const* dst, const int32_t* rows,
+                                       const int32_t* cols, float* dot, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return spectral_norm_bwd_batch_dispatch(n, g, w, u, v, sigma2, dst, rows, cols, dot, (hipStream_t)stream);
+}
+
+int resr_debug_fold4x4_batch(int32_t n, const float* const* dw3, float* const* dw4, const int32_t* cout, const int32_t* c,
+                             void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return fold4x4_batch_dispatch(n, dw3, dw4, cout, c, (hipStream_t)stream);
 }
 
 int resr_profile_begin(void) {

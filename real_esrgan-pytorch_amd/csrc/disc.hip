@@ -68,7 +68,13 @@ __device__ __forceinline__ void mask_mult(const T* at, long lo, float slope, flo
         }
     }
 #pragma unroll
-    for (int e = 0; e < E; ++e) v[e] *= pos[e] ? 1.f : slope;
+    for (int e = 0; e < E; ++e) {
+        v[e] *= pos[e] ? 1.f : slope;
+        // opaque: ONE fp32 product for every later use.  Left visible, the compiler folded the multiply into the f16 conversion of
+        // some uses (v_fma_mixlo_f16: one rounding of the exact product) and not of others (multiply, then convert), and st_vals
+        // stored the hi of one with the lo that belongs to the other: one f16 ulp apart where the fp32 product sits on an f16 tie
+        if constexpr (sizeof(T) == 2) asm("" : "+v"(v[e]));
+    }
 }
 
 // dst[Y][X][(i*2+j)*C + c] = src[2Y+i][2X+j][c]   (inverse: the other way round).  A pure permutation: RESR_F16X2 callers run it
@@ -111,13 +117,8 @@ __global__ __launch_bounds__(256) void d2s_add_mask_kernel(const T* __restrict__
 #pragma unroll
         for (int e = 0; e < E; ++e) v[e] += va[e];
     }
-    if (mask) {
-        if (lo_out == 0) {   // plain tensors: the sum is rounded to T before the mask multiplies it (two passes' roundings)
-#pragma unroll
-            for (int e = 0; e < E; ++e) v[e] = (float)(T)v[e];
-        }
-        mask_mult(mask + full, lo_out, slope, v);   // the mask has out's shape, hence its hi -> lo offset
-    }
+    if (mask) mask_mult(mask + full, lo_out, slope, v);   // the mask has out's shape, hence its hi -> lo offset; the fp32 sum meets the
+                                                          // multiplier unrounded, as in add_mask: ONE rounding to T, in st_vals
     st_vals(out + full, lo_out, v);
 }
 
@@ -694,7 +695,7 @@ __global__ __launch_bounds__(256) void sn_bwd_apply_kernel(const float* __restri
 
 int spectral_norm_bwd_dispatch(const float* G, const float* W, const float* u, const float* v, const float* sigma2, float* dst,
                                int rows, int cols, int accumulate, float* tmp1, hipStream_t st) {
-    if (!G || !W || !u || !v || !sigma2 || !dst || !tmp1) return fail(RESR_ERR_ARG, "spectral_norm_bwd: bad argument");
+    if (!G || !W || !u || !v || !sigma2 || !dst || !tmp1 || rows <= 0 || cols <= 0) return fail(RESR_ERR_ARG, "spectral_norm_bwd: bad argument");
     const long count = (long)rows * cols;
     long blocks = (count + 255) / 256;
     if (blocks > 512) blocks = 512;
@@ -756,6 +757,8 @@ int spectral_norm_bwd_batch_dispatch(int n, const float* const* G, const float* 
     int dots = 0;
     long ablk = 0;
     for (int i = 0; i < n; ++i) {
+        if (!G[i] || !W[i] || !u[i] || !v[i] || !sigma2[i] || !dst[i] || rows[i] <= 0 || cols[i] <= 0)
+            return fail(RESR_ERR_ARG, "spectral_norm_bwd_batch: bad argument");
         SnBwdLayer& L = a.l[i];
         L.G = G[i]; L.W = W[i]; L.u = u[i]; L.v = v[i]; L.sigma2 = sigma2[i]; L.dst = dst[i];
         L.count = (long)rows[i] * cols[i]; L.cols = cols[i];
@@ -791,6 +794,7 @@ int fold4x4_batch_dispatch(int n, const float* const* src, float* const* dst, co
     a.n = n;
     long blk = 0;
     for (int i = 0; i < n; ++i) {
+        if (!src[i] || !dst[i] || cout[i] <= 0 || C[i] <= 0) return fail(RESR_ERR_ARG, "fold4x4_batch: bad argument");
         a.src[i] = src[i]; a.dst[i] = dst[i]; a.cout[i] = cout[i]; a.C[i] = C[i];
         a.blk0[i] = blk; blk += ((long)cout[i] * C[i] * 16 + 255) / 256;
     }
