@@ -110,6 +110,33 @@ class PackChunk(C.Structure):
                 ("scale_ptr", C.c_void_p)]
 
 
+PACKED_SLACK = 16384   # bytes added behind a packed weight buffer a caller sizes itself, as resr_*_packed_bytes add them natively
+
+
+def packed_elem_bytes(dtype: int) -> int:
+    """Bytes per packed weight element: f16, f32, or exact16's three f16 blocks (W0, W1, W2)."""
+    return {RESR_F16: 2, RESR_F32: 4, RESR_F16X2: 6}[dtype]
+
+
+def fetch_pack_table(call, what: str):
+    """A native pack table as a host `PackChunk` array.  `call(chunks, capacity)` is the table function with its leading arguments
+    bound: asked with (None, 0) for its length, then with an array of that length."""
+    n = int(call(None, 0))
+    if n <= 0:
+        check(n if n < 0 else -1, what)
+    host = (PackChunk * n)()
+    got = int(call(C.cast(host, C.c_void_p), n))
+    if got != n:
+        check(got if got < 0 else -1, what)
+    return host
+
+
+def upload_chunks(chunks, device):
+    """A `PackChunk` array as the device byte tensor resr_pack_weights reads."""
+    import torch
+    return torch.frombuffer(bytearray(bytes(chunks)), dtype=torch.uint8).to(device)
+
+
 class ProfEntry(C.Structure):
     _fields_ = [("kernel_id", C.c_int32), ("ms", C.c_float), ("flop", C.c_double), ("bytes", C.c_double)]
 

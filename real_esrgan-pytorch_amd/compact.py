@@ -29,7 +29,7 @@ from typing import Dict, List, Optional
 import torch
 from torch import nn
 
-from . import _lib
+from . import _arena, _lib
 from .model import _precision_to_dtype
 
 __all__ = ["SRVGGNetCompact"]
@@ -107,28 +107,10 @@ class SRVGGNetCompact(nn.Module):
     def _ordered_params(self) -> List[nn.Parameter]:
         return [p for _, p in self.named_parameters()]
 
-    def _arena_ok(self) -> bool:
-        if self._flat is None:
-            return False
-        base, off = self._flat.data_ptr(), 0
-        for p in self._ordered_params():
-            if p.data_ptr() != base + off * 4 or p.dtype != torch.float32:
-                return False
-            off += p.numel()
-        return off == self._flat.numel()
-
     def flat_parameters(self) -> torch.Tensor:
         """The fp32 arena all parameters are views of (named_parameters order = resr_compact_forward's layout)."""
-        if not self._arena_ok():
-            params = self._ordered_params()
-            flat = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=params[0].device)
-            off = 0
-            for p in params:
-                n = p.numel()
-                flat[off:off + n].copy_(p.data.reshape(-1).float())
-                p.data = flat[off:off + n].view(p.shape)
-                off += n
-            self._flat = flat
+        if not _arena.is_arena(self._flat, self._ordered_params()):
+            self._flat = _arena.build(self.named_parameters(), lambda name, p, view: setattr(p, "data", view))
             self._packed = None
             self._table_dev = None
             self._workspaces.clear()
@@ -142,12 +124,8 @@ class SRVGGNetCompact(nn.Module):
         """One resr_pack_weights launch per forward: a load_state_dict or an in-place edit is always seen (graph replays too)."""
         L = _lib.lib()
         if self._table_dev is None or self._table_dev[0].device != flat.device:
-            n = L.resr_compact_pack_table(C.byref(desc), None, 0)
-            if n <= 0:
-                _lib.check(int(n) if n < 0 else -1, "resr_compact_pack_table")
-            host = (_lib.PackChunk * n)()
-            assert L.resr_compact_pack_table(C.byref(desc), C.cast(host, C.c_void_p), n) == n
-            self._table_dev = (torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(flat.device), int(n))
+            host = _lib.fetch_pack_table(lambda out, cap: L.resr_compact_pack_table(C.byref(desc), out, cap), "resr_compact_pack_table")
+            self._table_dev = (_lib.upload_chunks(host, flat.device), len(host))
         nbytes = L.resr_compact_packed_bytes(C.byref(desc))
         if self._packed is None or self._packed.numel() < nbytes or self._packed.device != flat.device:
             self._packed = torch.zeros(nbytes, dtype=torch.uint8, device=flat.device)

@@ -152,14 +152,14 @@ class ContentLoss(nn.Module):
                 table[idx] = gl
             src += cout * cin * 9
         host = (L.PackChunk * len(chunks))(*chunks)
-        table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(device)
-        self._wes = {L.RESR_F16: 2, L.RESR_F32: 4, L.RESR_F16X2: 6}[self._dtype]
-        packed = torch.zeros(off * self._wes + 16384, dtype=torch.uint8, device=device)
+        table = L.upload_chunks(host, device)
+        self._wes = L.packed_elem_bytes(self._dtype)
+        packed = torch.zeros(off * self._wes + L.PACKED_SLACK, dtype=torch.uint8, device=device)
         L.check(L.lib().resr_pack_weights(L.ptr(table), len(chunks), L.ptr(flat), L.ptr(packed), self._dtype, L.stream_ptr(flat)),
                 "resr_pack_weights")
         self._packed_f16 = None
         if self.f16_backward:
-            self._packed_f16 = torch.zeros(off * 2 + 16384, dtype=torch.uint8, device=device)
+            self._packed_f16 = torch.zeros(off * L.packed_elem_bytes(L.RESR_F16) + L.PACKED_SLACK, dtype=torch.uint8, device=device)
             L.check(L.lib().resr_pack_weights(L.ptr(table), len(chunks), L.ptr(flat), L.ptr(self._packed_f16), L.RESR_F16,
                                               L.stream_ptr(flat)), "resr_pack_weights (f16 backward)")
         self._packed = (packed, fwd, bwd)

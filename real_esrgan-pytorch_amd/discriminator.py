@@ -24,43 +24,21 @@ import torch
 from torch import nn
 from torch.nn.utils import spectral_norm
 
-from . import _lib
+from . import _arena, _lib
 from .model import _f16_backward_flag, _precision_to_dtype
 
 
-class _DWorkspace:
-    """One workspace + the pack table that points into it; `busy` while a graph that saved into it is alive."""
+class _DWorkspace(_arena.Workspace):
+    """One workspace + the pack table that points into it."""
 
     def __init__(self, nbytes: int, device, desc) -> None:
+        # the head: 1 / sigma + the gradient pre-scale slot with its sticky back-off words, zero once (include/resr.h)
+        super().__init__(nbytes, device, 256)
         L = _lib.lib()
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self.buf[:256].zero_()     # 1 / sigma + the gradient pre-scale slot with its sticky back-off words: zero once (include/resr.h)
-        n = int(L.resr_discriminator_pack_table(C.byref(desc), _lib.ptr(self.buf), None, 0))
-        host = (_lib.PackChunk * n)()
-        got = int(L.resr_discriminator_pack_table(C.byref(desc), _lib.ptr(self.buf), C.cast(host, C.c_void_p), n))
-        if got != n:
-            _lib.check(got if got < 0 else -1, "resr_discriminator_pack_table")
-        self.table = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(device)
-        self.n_chunks = n
-        self.busy = False
-        self.owner = 0
-
-    def acquire(self) -> int:
-        self.owner += 1
-        self.busy = True
-        return self.owner
-
-    def release(self, owner: int) -> None:
-        if owner == self.owner:
-            self.busy = False
-
-
-class _DToken:
-    def __init__(self, ws: _DWorkspace, owner: int) -> None:
-        self.ws, self.owner = ws, owner
-
-    def __del__(self) -> None:
-        self.ws.release(self.owner)
+        host = _lib.fetch_pack_table(lambda out, cap: L.resr_discriminator_pack_table(C.byref(desc), _lib.ptr(self.buf), out, cap),
+                                     "resr_discriminator_pack_table")
+        self.table = _lib.upload_chunks(host, device)
+        self.n_chunks = len(host)
 
 
 class _DiscFn(torch.autograd.Function):
@@ -70,16 +48,14 @@ class _DiscFn(torch.autograd.Function):
         ctx.module, ctx.desc, ctx.ws = module, desc, ws
         ctx.x_needs_grad = x.requires_grad
         ctx.param_needs = [p.requires_grad for p in params]
-        ctx.owner = 0
-        if training:
-            ctx.owner = ws.acquire()
-            ctx._token = _DToken(ws, ctx.owner)
+        if training:     # frees the workspace when backward has run, or when the graph is dropped without one
+            ctx._token = _arena.GraphToken(ws)
         return y
 
     @staticmethod
     def backward(ctx, gy: torch.Tensor):
         grads, gx = ctx.module._run_backward(ctx.desc, ctx.ws, gy.contiguous().float(), ctx.x_needs_grad, any(ctx.param_needs))
-        ctx.ws.release(ctx.owner)
+        ctx._token.finish()
         return (None, None, gx) + tuple(g if need else None for g, need in zip(grads, ctx.param_needs))
 
 
@@ -111,42 +87,19 @@ class Discriminator(nn.Module):
         self.conv4 = nn.Conv2d(64, 1, (3, 3), (1, 1), (1, 1))
         self._flat: Optional[torch.Tensor] = None       # fp32 parameter arena (named_parameters order)
         self._uv: Optional[torch.Tensor] = None         # fp32 spectral-norm arena (named_buffers order)
-        self._offsets: Dict[str, int] = {}
         self._workspaces: Dict[tuple, List[_DWorkspace]] = {}
         self.grad_hook = None   # optional callable(flat_grad) after a backward that produced weight gradients
-        self.__dict__["_flat_param"] = None   # see flat_parameter(); kept out of nn.Module's parameter registry
 
     # ---- arenas ---------------------------------------------------------------------------------------------
     def _ordered_params(self) -> List[nn.Parameter]:
         return [p for _, p in self.named_parameters()]
 
-    @staticmethod
-    def _is_arena(flat: Optional[torch.Tensor], tensors) -> bool:
-        if flat is None:
-            return False
-        off = 0
-        for t in tensors:
-            if t.dtype != torch.float32 or t.data_ptr() != flat.data_ptr() + 4 * off:
-                return False
-            off += t.numel()
-        return off == flat.numel()
-
     def flat_parameters(self) -> torch.Tensor:
         params = self._ordered_params()
-        if not self._is_arena(self._flat, params):
-            total = sum(p.numel() for p in params)
-            if total != _lib.lib().resr_discriminator_param_count():
+        if not _arena.is_arena(self._flat, params):
+            if sum(p.numel() for p in params) != _lib.lib().resr_discriminator_param_count():
                 raise RuntimeError("Discriminator: parameter count differs from the native plan")
-            flat = torch.empty(total, dtype=torch.float32, device=params[0].device)
-            off = 0
-            self._offsets = {}
-            for name, p in self.named_parameters():
-                n = p.numel()
-                flat[off:off + n].copy_(p.data.reshape(-1).float())
-                p.data = flat[off:off + n].view(p.shape)
-                self._offsets[name] = off
-                off += n
-            self._flat = flat
+            self._flat = _arena.build(self.named_parameters(), lambda name, p, view: setattr(p, "data", view))
             self._workspaces.clear()
         return self._flat
 
@@ -158,22 +111,15 @@ class Discriminator(nn.Module):
         into this Parameter's `.grad` (autograd semantics) and hands out no per-tensor gradients; `zero_grad()` clears it; setting
         `requires_grad` on the module's parameters (the frozen discriminator of the generator step, :465-466) is mirrored onto it
         by `requires_grad_`.  `state_dict()` is unchanged."""
-        flat = self.flat_parameters()
-        fp = self.__dict__["_flat_param"]
-        if fp is None:
-            fp = nn.Parameter(flat, requires_grad=True)
-            self.__dict__["_flat_param"] = fp
-        elif fp.data_ptr() != flat.data_ptr():
-            fp.data = flat
-        return fp
+        return _arena.flat_alias(self, self.flat_parameters(), create=True)
 
     def flat_grad(self) -> Optional[torch.Tensor]:
-        fp = self.__dict__["_flat_param"]
+        fp = _arena.flat_alias(self)
         return None if fp is None else fp.grad
 
     def zero_grad(self, set_to_none: bool = True) -> None:
         super().zero_grad(set_to_none=set_to_none)
-        fp = self.__dict__["_flat_param"]
+        fp = _arena.flat_alias(self)
         if fp is not None and fp.grad is not None:
             if set_to_none:
                 fp.grad = None
@@ -181,7 +127,7 @@ class Discriminator(nn.Module):
                 fp.grad.zero_()
 
     def requires_grad_(self, requires_grad: bool = True):
-        fp = self.__dict__["_flat_param"]
+        fp = _arena.flat_alias(self)
         if fp is not None:
             fp.requires_grad_(requires_grad)
         return super().requires_grad_(requires_grad)
@@ -190,35 +136,27 @@ class Discriminator(nn.Module):
         """The spectral-norm vectors (`weight_u`, `weight_v` of the eight normalised convs, named_buffers order) as views of
         one arena: the native forward updates them in place, a data-parallel broadcast moves them in one message."""
         named = list(self.named_buffers())
-        if not self._is_arena(self._uv, [b for _, b in named]):
-            total = sum(b.numel() for _, b in named)
-            if total != _lib.lib().resr_discriminator_uv_count():
+        if not _arena.is_arena(self._uv, [b for _, b in named]):
+            if sum(b.numel() for _, b in named) != _lib.lib().resr_discriminator_uv_count():
                 raise RuntimeError("Discriminator: spectral-norm buffer count differs from the native plan")
-            flat = torch.empty(total, dtype=torch.float32, device=named[0][1].device)
-            off = 0
-            for name, b in named:
-                n = b.numel()
-                flat[off:off + n].copy_(b.reshape(-1).float())
+
+            def assign(name: str, b: torch.Tensor, view: torch.Tensor) -> None:
                 mod, leaf = name.rsplit(".", 1)
-                setattr(self.get_submodule(mod), leaf, flat[off:off + n].view(b.shape))
-                off += n
-            self._uv = flat
+                setattr(self.get_submodule(mod), leaf, view)
+            self._uv = _arena.build(named, assign)
         return self._uv
 
     # ---- C-ABI plumbing ---------------------------------------------------------------------------------------
     def _workspace(self, desc, device) -> _DWorkspace:
         # the output-parity backward leaves f16 weights in a training workspace's packed region: a pool of its own
         key = (desc.n, desc.h, desc.w, desc.training, desc.dtype) + ((True,) if self.f16_backward and desc.training else ())
-        pool = self._workspaces.setdefault(key, [])
-        for ws in pool:
-            if not ws.busy and ws.buf.device == device:
-                return ws
-        nbytes = _lib.lib().resr_discriminator_workspace_bytes(C.byref(desc))
-        if nbytes == 0:
-            raise RuntimeError("Discriminator: expected [N,3,H,W] with H, W divisible by 8")
-        ws = _DWorkspace(nbytes, device, desc)
-        pool.append(ws)
-        return ws
+
+        def make() -> _DWorkspace:
+            nbytes = _lib.lib().resr_discriminator_workspace_bytes(C.byref(desc))
+            if nbytes == 0:
+                raise RuntimeError("Discriminator: expected [N,3,H,W] with H, W divisible by 8")
+            return _DWorkspace(nbytes, device, desc)
+        return _arena.take(self._workspaces, key, device, make)
 
     def _run_forward(self, x: torch.Tensor, training: bool):
         L = _lib.lib()
@@ -255,27 +193,18 @@ class Discriminator(nn.Module):
             return [None] * len(self._ordered_params()), gx
         if self.grad_hook is not None:
             self.grad_hook(gflat)
-        fp = self.__dict__["_flat_param"]
+        fp = _arena.flat_alias(self, flat)
         if fp is not None:                        # flat_parameter() mode: accumulate into the alias, no per-tensor gradients
-            if fp.data_ptr() != flat.data_ptr():
-                fp.data = flat
             if fp.grad is None:
                 fp.grad = gflat
             else:
                 fp.grad.add_(gflat)
             return [None], gx
-        grads = []
-        for name, p in self.named_parameters():
-            off = self._offsets[name]
-            grads.append(gflat[off:off + p.numel()].view(p.shape))
-        return grads, gx
+        return list(_arena.views(gflat, self.named_parameters()).values()), gx
 
     # ---- module surface -----------------------------------------------------------------------------------------
     def _forward_impl(self, x: torch.Tensor) -> torch.Tensor:
-        flat = self.flat_parameters()
-        fp = self.__dict__["_flat_param"]
-        if fp is not None and fp.data_ptr() != flat.data_ptr():
-            fp.data = flat                                               # the arena was rebuilt (.to(), new tensors loaded): keep the alias on it
+        fp = _arena.flat_alias(self, self.flat_parameters())           # the arena may have been rebuilt: the alias follows it
         params = [fp] if fp is not None else self._ordered_params()     # flat_parameter() mode: one graph input for all 19 tensors
         training = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         return _DiscFn.apply(self, training, x, *params)

@@ -19,7 +19,7 @@ from typing import Dict, List, Optional
 import torch
 from torch import nn
 
-from . import _lib
+from . import _arena, _lib
 
 __all__ = ["EMA", "ResidualDenseBlock", "ResidualResidualDenseBlock", "Generator", "load_official_state_dict"]
 
@@ -94,9 +94,8 @@ def _pack_one(conv: nn.Conv2d, dtype: int) -> torch.Tensor:
     chunks = (_lib.PackChunk * nck)()
     for ck in range(nck):
         chunks[ck] = _lib.PackChunk(0, ck * 9 * mt * 1024, cout, cin, 0, cout, ck * 32, min(32, cin - ck * 32), mt, 0, 1.0, 0, None)
-    table = torch.frombuffer(bytearray(bytes(chunks)), dtype=torch.uint8).to(w.device)
-    es = {_lib.RESR_F16: 2, _lib.RESR_F32: 4, _lib.RESR_F16X2: 6}[dtype]
-    packed = torch.zeros(nck * 9 * mt * 1024 * es + 16384, dtype=torch.uint8, device=w.device)
+    table = _lib.upload_chunks(chunks, w.device)
+    packed = torch.zeros(nck * 9 * mt * 1024 * _lib.packed_elem_bytes(dtype) + _lib.PACKED_SLACK, dtype=torch.uint8, device=w.device)
     _lib.check(_lib.lib().resr_pack_weights(_lib.ptr(table), nck, _lib.ptr(w.reshape(-1)), _lib.ptr(packed), dtype,
                                             _lib.stream_ptr(w)), "resr_pack_weights")
     return packed
@@ -149,28 +148,6 @@ def _dense_blocks_forward(rdbs, x: torch.Tensor, rrdb: bool, precision: Optional
     return y
 
 
-class _Workspace:
-    """One activation workspace; `busy` while an autograd graph that saved into it is alive.  `owner` counts the
-    training-mode forwards that took it: only the graph that still owns it may release it (a stale token of an earlier
-    graph, collected late, must not free a workspace a newer graph saved its activations in)."""
-
-    def __init__(self, nbytes: int, device, zero_head: int = 0) -> None:
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        if zero_head:      # the chain state of the dense-block launches: zero once (include/resr.h)
-            self.buf[:zero_head].zero_()
-        self.busy = False
-        self.owner = 0
-
-    def acquire(self) -> int:
-        self.owner += 1
-        self.busy = True
-        return self.owner
-
-    def release(self, owner: int) -> None:
-        if owner == self.owner:
-            self.busy = False
-
-
 class _GeneratorFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module: "Generator", training: bool, x: torch.Tensor, *params: torch.Tensor):
@@ -178,10 +155,8 @@ class _GeneratorFn(torch.autograd.Function):
         ctx.module, ctx.desc, ctx.ws = module, desc, ws
         ctx.x_needs_grad = x.requires_grad
         ctx.n_params = len(params)
-        ctx.owner = 0
-        if training:
-            ctx.owner = ws.acquire()
-            ctx._token = _WsToken(ws, ctx.owner, module)   # frees the workspace when the graph is dropped without backward
+        if training:     # a live graph of the module until backward has run or the graph is dropped without one; then the workspace is free
+            ctx._token = _arena.GraphToken(ws, module._graph_opened, module._graph_finished)
         return y
 
     @staticmethod
@@ -196,24 +171,6 @@ class _GeneratorFn(torch.autograd.Function):
         if len(grads) != ctx.n_params:             # flat_parameter() mode: the one alias was the graph's only parameter input
             grads = [None] * ctx.n_params
         return (None, None, gx) + tuple(grads)
-
-
-class _WsToken:
-    """Lifetime of one training-mode graph: counts it among the module's live graphs and gives the workspace back
-    when its backward has run or when the graph is dropped without one."""
-
-    def __init__(self, ws: _Workspace, owner: int, module: "Generator") -> None:
-        self.ws, self.owner, self.module, self.open = ws, owner, module, True
-        module._live_graphs += 1
-
-    def finish(self) -> None:
-        if self.open:
-            self.open = False
-            self.module._live_graphs -= 1
-            self.ws.release(self.owner)
-
-    def __del__(self) -> None:
-        self.finish()
 
 
 class Generator(nn.Module):
@@ -290,14 +247,13 @@ class Generator(nn.Module):
         self._packed: Optional[torch.Tensor] = None
         self._packed_f16: Optional[torch.Tensor] = None   # x2_plan bit 8: a RESR_F16 packing of the same table for the f16 backward pass
         self._table_dev: Dict[int, tuple] = {}
-        self._workspaces: Dict[tuple, List[_Workspace]] = {}
+        self._workspaces: Dict[tuple, List[_arena.Workspace]] = {}
         self.grad_hook = None   # callable(flat_grad) run after backward wrote the arena (data-parallel all-reduce)
         # callable(flat_grad, ranges, events): data-parallel exchange OVERLAPPED with the backward pass -- events[i] fires on
         # the backward stream as soon as arena range ranges[i] is final (resr_generator_backward's grad_ready_events)
         self.grad_ready_hook = None
         self._events: List[torch.cuda.Event] = []
         self._live_graphs = 0   # training-mode forwards whose backward has not run yet
-        self.__dict__["_flat_param"] = None   # see flat_parameter(); kept out of nn.Module's parameter registry
 
     # ---- what the tiler needs (tiling.py; SRVGGNetCompact defines the same) ---------------------------------------------
     @property
@@ -320,39 +276,14 @@ class Generator(nn.Module):
     def _ordered_params(self) -> List[nn.Parameter]:
         return [p for _, p in self.named_parameters()]
 
-    def _flatten(self) -> None:
-        params = self._ordered_params()
-        dev = params[0].device
-        total = sum(p.numel() for p in params)
-        flat = torch.empty(total, dtype=torch.float32, device=dev)
-        off = 0
-        for p in params:
-            n = p.numel()
-            flat[off:off + n].copy_(p.data.reshape(-1).float())
-            p.data = flat[off:off + n].view(p.shape)
-            off += n
-        self._flat = flat
-        self._flat_grad = None
-        self._packed = None
-        self._table_dev.clear()
-        self._workspaces.clear()
-
-    def _arena_ok(self) -> bool:
-        if self._flat is None:
-            return False
-        params = self._ordered_params()
-        base = self._flat.data_ptr()
-        off = 0
-        for p in params:
-            if p.data_ptr() != base + off * 4 or p.dtype != torch.float32:
-                return False
-            off += p.numel()
-        return off == self._flat.numel()
-
     def flat_parameters(self) -> torch.Tensor:
         """The fp32 arena all parameters are views of (reference named_parameters order)."""
-        if not self._arena_ok():
-            self._flatten()
+        if not _arena.is_arena(self._flat, self._ordered_params()):
+            self._flat = _arena.build(self.named_parameters(), lambda name, p, view: setattr(p, "data", view))
+            self._flat_grad = None
+            self._packed = None
+            self._table_dev.clear()
+            self._workspaces.clear()
         return self._flat
 
     def flat_grad(self) -> Optional[torch.Tensor]:
@@ -382,14 +313,7 @@ class Generator(nn.Module):
         to this Parameter's `.grad` (overwritten, not accumulated) and returns no per-tensor gradients.  The per-tensor
         Parameters stay valid views of the same storage; `state_dict()` is unchanged, the optimizer's own state_dict
         then holds one tensor (not loadable into the reference's per-tensor Adam state)."""
-        flat = self.flat_parameters()
-        fp = self.__dict__["_flat_param"]
-        if fp is None:
-            fp = nn.Parameter(flat, requires_grad=True)
-            self.__dict__["_flat_param"] = fp
-        elif fp.data_ptr() != flat.data_ptr():
-            fp.data = flat
-        return fp
+        return _arena.flat_alias(self, self.flat_parameters(), create=True)
 
     # ---- C-ABI plumbing -------------------------------------------------------------------------
     def _desc(self, x: torch.Tensor, training: bool) -> _lib.GeneratorDesc:
@@ -406,14 +330,8 @@ class Generator(nn.Module):
         flat = self.flat_parameters()
         key = 1 if backward else 0
         if key not in self._table_dev:
-            n = L.resr_generator_pack_table(C.byref(desc), key, None, 0)
-            if n <= 0:
-                _lib.check(int(n) if n < 0 else -1, "resr_generator_pack_table")
-            host = (_lib.PackChunk * n)()
-            n2 = L.resr_generator_pack_table(C.byref(desc), key, C.cast(host, C.c_void_p), n)
-            assert n2 == n
-            raw = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(flat.device)
-            self._table_dev[key] = (raw, int(n))
+            host = _lib.fetch_pack_table(lambda out, cap: L.resr_generator_pack_table(C.byref(desc), key, out, cap), "resr_generator_pack_table")
+            self._table_dev[key] = (_lib.upload_chunks(host, flat.device), len(host))
         nbytes = L.resr_generator_packed_bytes(C.byref(desc), 1)
         if self._packed is None or self._packed.numel() < nbytes or self._packed.device != flat.device:
             self._packed = torch.zeros(nbytes, dtype=torch.uint8, device=flat.device)
@@ -433,19 +351,23 @@ class Generator(nn.Module):
             _lib.check(L.resr_pack_weights_mx(_lib.ptr(raw), n, _lib.ptr(flat), C.c_void_p(self._packed.data_ptr() + mx_off),
                                               _lib.stream_ptr(flat)), "resr_pack_weights_mx")
 
-    def _workspace(self, desc: _lib.GeneratorDesc, device) -> _Workspace:
+    def _workspace(self, desc: _lib.GeneratorDesc, device) -> _arena.Workspace:
         L = _lib.lib()
+
+        def make() -> _arena.Workspace:
+            nbytes = L.resr_generator_workspace_bytes(C.byref(desc))
+            if nbytes == 0:
+                raise RuntimeError(f"resr_generator_workspace_bytes: unsupported shape ({(L.resr_last_error() or b'').decode()})")
+            # the head is the chain state of the dense-block launches: zero once (include/resr.h)
+            return _arena.Workspace(nbytes, device, int(L.resr_generator_chain_state_bytes(C.byref(desc))))
         key = (desc.n, desc.h, desc.w, desc.training, desc.dtype, desc.wgrad_splits, _lib.x2_plan_layout_key(desc.x2_plan))
-        pool = self._workspaces.setdefault(key, [])
-        for ws in pool:
-            if not ws.busy:
-                return ws
-        nbytes = L.resr_generator_workspace_bytes(C.byref(desc))
-        if nbytes == 0:
-            raise RuntimeError(f"resr_generator_workspace_bytes: unsupported shape ({(L.resr_last_error() or b'').decode()})")
-        ws = _Workspace(nbytes, device, int(L.resr_generator_chain_state_bytes(C.byref(desc))))
-        pool.append(ws)
-        return ws
+        return _arena.take(self._workspaces, key, device, make)
+
+    def _graph_opened(self) -> None:     # the two ends of a training-mode graph (_arena.GraphToken)
+        self._live_graphs += 1
+
+    def _graph_finished(self) -> None:
+        self._live_graphs -= 1
 
     def _run_forward(self, x: torch.Tensor, training: bool):
         _lib.require_cuda(x, "Generator.forward")
@@ -463,7 +385,7 @@ class Generator(nn.Module):
                    "resr_generator_forward")
         return y, desc, ws
 
-    def _run_backward(self, desc, ws: _Workspace, gy: torch.Tensor, need_gx: bool, private: bool = False):
+    def _run_backward(self, desc, ws: _arena.Workspace, gy: torch.Tensor, need_gx: bool, private: bool = False):
         L = _lib.lib()
         flat = self.flat_parameters()
         if self._flat_grad is None or self._flat_grad.device != flat.device:
@@ -477,7 +399,7 @@ class Generator(nn.Module):
         # handed out as a separate tensor for autograd to add.
         # (flat_parameter() mode keeps its documented overwrite semantics: the alias is not a module parameter, so
         # `model.zero_grad()` never clears its .grad, and every backward simply replaces the arena.)
-        fp = self.__dict__["_flat_param"]
+        fp = _arena.flat_alias(self, flat)
         accumulate = fp is None and any(p.grad is not None for p in self._ordered_params())
         prev = self._flat_grad.clone() if accumulate else None
         ev_arr, n_ev = None, 0
@@ -498,8 +420,6 @@ class Generator(nn.Module):
         elif self.grad_hook is not None:
             self.grad_hook(self._flat_grad)
         if fp is not None:                       # flat_parameter() mode: the arena is the gradient of the alias
-            if fp.data_ptr() != flat.data_ptr():
-                fp.data = flat
             fp.grad = self._flat_grad
             return [None] * len(self._ordered_params()), gx
         src = self._flat_grad
@@ -508,19 +428,12 @@ class Generator(nn.Module):
             self._flat_grad.copy_(prev)          # the earlier ones back where .grad may be looking
         elif private:
             src = self._flat_grad.clone()        # another live graph will overwrite the arena before autograd reads these
-        grads, off = [], 0
-        for p in self._ordered_params():
-            n = p.numel()
-            grads.append(src[off:off + n].view(p.shape) if p.requires_grad else None)
-            off += n
-        return grads, gx
+        named = list(self.named_parameters())
+        return [g if p.requires_grad else None for g, (_, p) in zip(_arena.views(src, named).values(), named)], gx
 
     # ---- module surface ---------------------------------------------------------------------------
     def _forward_impl(self, x: torch.Tensor) -> torch.Tensor:
-        flat = self.flat_parameters()
-        fp = self.__dict__["_flat_param"]
-        if fp is not None and fp.data_ptr() != flat.data_ptr():
-            fp.data = flat                       # the arena was rebuilt (.to(), new tensors loaded): keep the alias on it
+        fp = _arena.flat_alias(self, self.flat_parameters())   # the arena may have been rebuilt: the alias follows it
         # flat_parameter() mode: the alias stands for all 702 tensors in the autograd graph (its .grad is set by hand in backward),
         # so a backward pass does not walk 702 AccumulateGrad nodes that would each receive None
         params = [fp] if fp is not None else self._ordered_params()
@@ -597,12 +510,7 @@ class EMA(nn.Module):
             flat = self.model.flat_parameters()
             _lib.require_cuda(flat, "EMA.register")
             self._flat_shadow = flat.detach().clone()
-            off = 0
-            self.shadow = {}
-            for name, p in self.model.named_parameters():
-                n = p.numel()
-                self.shadow[name] = self._flat_shadow[off:off + n].view(p.shape)
-                off += n
+            self.shadow = _arena.views(self._flat_shadow, self.model.named_parameters())
             return
         for name, param in self.model.named_parameters():
             if param.requires_grad:

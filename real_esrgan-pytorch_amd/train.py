@@ -11,13 +11,14 @@ One process per GPU (`setup_distributed`).  Exchanges per optimiser step (`DataP
 from __future__ import annotations
 
 import os
-from typing import Callable, Iterable, List, Optional
+from typing import Callable, Iterable, Optional
 
 import torch
 import torch.distributed as dist
 from torch import nn
 
 from . import losses
+from ._arena import arena_of as _arena_of, flat_alias
 from .model import EMA, Generator
 
 
@@ -40,20 +41,6 @@ def setup_distributed(backend: Optional[str] = None) -> tuple:
         else:
             dist.init_process_group(backend, rank=rank, world_size=world)
     return rank, world, device
-
-
-def _arena_of(tensors: List[torch.Tensor]) -> Optional[torch.Tensor]:
-    """The flat fp32 tensor `tensors` are consecutive views of, if they are (same storage, back to back)."""
-    if not tensors or any(t.dtype != torch.float32 or not t.is_contiguous() for t in tensors):
-        return None
-    base = tensors[0]
-    off = base.storage_offset()
-    for t in tensors:
-        if t.untyped_storage().data_ptr() != base.untyped_storage().data_ptr() or t.storage_offset() != off:
-            return None
-        off += t.numel()
-    total = off - base.storage_offset()
-    return torch.as_strided(base, (total,), (1,), base.storage_offset())
 
 
 class DataParallel:
@@ -284,12 +271,12 @@ class RealESRGANStep:
         """train_realesrgan.py:465-466 / :491-492, including the one-tensor alias of `Discriminator.flat_parameter()`."""
         for p in self.d.parameters():
             p.requires_grad = flag
-        fp = self.d.__dict__.get("_flat_param")
+        fp = flat_alias(self.d)
         if fp is not None:
             fp.requires_grad = flag
 
     def _d_grad_holders(self):
-        fp = self.d.__dict__.get("_flat_param")
+        fp = flat_alias(self.d)
         return [fp] if fp is not None else list(self.d.parameters())
 
     def _content_w(self, device) -> torch.Tensor:

@@ -574,3 +574,28 @@ def test_bilinear_up2x_quad_kernel_vs_torch_and_f32_kernel(shape):
     ref.backward(g32.permute(0, 3, 1, 2))
     torch.cuda.synchronize()
     assert (gin32 - x.grad.permute(0, 2, 3, 1)).abs().max().item() <= 1e-5
+
+
+def test_dropped_graphs_give_their_workspace_back():
+    """Three training-mode forwards whose graphs are dropped without a backward leave one pooled workspace; the step behind them
+    equals that of a fresh module with the same weights and spectral-norm vectors."""
+    import real_esrgan_pytorch_amd as R
+    d, _, _ = _make("fast", 7)
+    d.train()
+    x = torch.rand(1, 3, 16, 16, generator=torch.Generator().manual_seed(3)).cuda()
+    for _ in range(3):
+        y = d(x)
+        assert y.requires_grad and [ws.busy for v in d._workspaces.values() for ws in v] == [True]
+        del y
+        assert [ws.busy for v in d._workspaces.values() for ws in v] == [False]
+    fresh = R.Discriminator(precision="fast")
+    fresh.load_state_dict(d.state_dict())             # the three forwards above moved u / v
+    fresh = fresh.cuda().train()
+    for m in (d, fresh):
+        m(x).square().sum().mul(256.0).backward()
+    torch.cuda.synchronize()
+    assert sum(len(v) for v in d._workspaces.values()) == 1
+    assert [ws.busy for v in d._workspaces.values() for ws in v] == [False]
+    for (name, p), q in zip(d.named_parameters(), fresh.parameters()):
+        assert p.grad is not None and torch.equal(p.grad, q.grad), name
+    assert torch.equal(d.flat_uv(), fresh.flat_uv())

@@ -335,6 +335,26 @@ def test_two_backwards_accumulate():
         assert ((p.grad.cpu() - ref).norm() / ref.norm().clamp_min(1e-12)).item() < 1e-4, name
 
 
+def test_dropped_graphs_give_their_workspace_back():
+    """Three training-mode forwards whose graphs are dropped without a backward leave one pooled workspace and no live graph;
+    the step behind them equals a fresh module's."""
+    g, sd, _ = _setup(4, 1, 3, "fast")
+    fresh, _, _ = _setup(4, 1, 3, "fast")
+    x = torch.rand(1, 3, 8, 8, generator=torch.Generator().manual_seed(3)).cuda()
+    for _ in range(3):
+        y = g(x)
+        assert y.requires_grad and g._live_graphs == 1
+        del y
+        assert g._live_graphs == 0
+    for m in (g, fresh):
+        m(x).square().sum().mul(256.0).backward()
+    torch.cuda.synchronize()
+    assert sum(len(v) for v in g._workspaces.values()) == 1
+    assert g._live_graphs == 0
+    for (name, p), q in zip(g.named_parameters(), fresh.parameters()):
+        assert p.grad is not None and torch.equal(p.grad, q.grad), name
+
+
 def test_exact16_three_product_weight_gradients_knob():
     """exact16's weight gradients use all three tap-products by default (X_hi^T G_hi + 2^-12 (X_hi^T G_lo + X_lo^T G_hi)): every
     one of the 702 tensors of the 23-block case within 2e-5 of the float64 evaluation (measured 5.8e-6).  RESR_X2_WGRAD_PRODUCTS=1
