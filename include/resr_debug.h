@@ -59,6 +59,12 @@ int resr_debug_spectral_norm_bwd_batch(int32_t n, const float* const* g, const f
 int resr_debug_fold4x4_batch(int32_t n, const float* const* dw3, float* const* dw4, const int32_t* cout, const int32_t* c,
                              void* stream);
 
+/* Test entry (tests/test_gpu_kernels.py) of the compact generator's body pass, which the product reaches only from inside
+ * resr_compact_forward*: resr_conv3x3 on one input tensor with a plain epilogue (flags: RESR_CONV_NO_BIAS or 0; NHWC output of one
+ * output group) followed by per-output-channel PReLU, v = v > 0 ? v : prelu[co] * v, `prelu` = d->cout floats.  bias may be NULL. */
+int resr_debug_conv3x3_prelu(const ResrConvDesc* d, const void* in0, const void* w_packed, const float* bias, const float* prelu,
+                             void* out, void* stream);
+
 /* What THIS board sustains once it sits at its power cap (bench.py's `roofline.vs_sustained`): 256 workgroups launched back to
  * back for `seconds` (last third timed) -- mode 1: an LDS-DMA stream over `src` (`bytes` >= 64 MB of readable device memory),
  * mode 2: eight waves per workgroup issuing v_mfma_f32_32x32x16_f16 on random f16 operands, mode 3: both at once.  Returns the

@@ -239,6 +239,7 @@ _PROTOS = {
     "resr_debug_sustained": (C.c_int, [C.c_int32, C.c_double, _P, C.c_size_t, _P, C.POINTER(C.c_double), C.POINTER(C.c_double), _P]),
     "resr_debug_d2s_add_mask": (C.c_int, [_P, _P, _P, _P] + [C.c_int32] * 5 + [C.c_float, _P]),
     "resr_debug_bilinear_up2x_bwd_mask": (C.c_int, [_P, _P, _P, _P] + [C.c_int32] * 5 + [C.c_float, _P]),
+    "resr_debug_conv3x3_prelu": (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
     "resr_debug_spectral_norm_batch": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_float, _P, _P, _P]),
     "resr_debug_spectral_norm_bwd_batch": (C.c_int, [C.c_int32] + [_P] * 10),
     "resr_debug_fold4x4_batch": (C.c_int, [C.c_int32, _P, _P, _P, _P, _P]),

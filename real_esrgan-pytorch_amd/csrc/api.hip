@@ -73,6 +73,7 @@ void conv_trace_set(void*);
 long long conv3x3_chain_errors();
 int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*, const float*, const void*,
                      const void*, const void*, void*, void*, hipStream_t);
+int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const float*, const float*, void*, hipStream_t);
 int conv3x3_chain_dispatch(int, const ResrConvDesc*, const void*, const void*, const void* const*, const float* const*,
                            const void* const*, void* const*, void* const*, void*, size_t, hipStream_t);
 size_t conv3x3_chain_state_bytes(int, int, int);
@@ -611,6 +612,14 @@ int resr_debug_bilinear_up2x_bwd_mask(const void* g, void* gin, const void* mask
     RESR_DEVICE_SCOPE(stream);
     const long px = dtype == RESR_F16X2 ? (long)n * h * w * c : 0L;
     return bilinear_up_bwd_mask_dispatch(g, gin, mask, gmasked, n, h, w, c, dtype, slope, (hipStream_t)stream, 4 * px, px);
+}
+
+// test entry of the compact generator's PReLU pass (tests/test_gpu_kernels.py): the dispatch function compact.hip calls, alone
+int resr_debug_conv3x3_prelu(const ResrConvDesc* d, const void* in0, const void* w_packed, const float* bias, const float* prelu,
+                             void* out, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    if (!d) return fail(RESR_ERR_ARG, "resr_debug_conv3x3_prelu: null descriptor");
+    return conv3x3_dispatch_prelu(d, in0, w_packed, bias, prelu, out, (hipStream_t)stream);
 }
 
 int resr_debug_spectral_norm_batch(int32_t n, const float* const* w, float* const* u, float* const* v, const int32_t* rows,

@@ -1,0 +1,164 @@
+"""Plain references of resr_conv3x3 and resr_conv3x3_wgrad (csrc/conv3x3.hip, conv3x3_ws.h, wgrad.hip), CPU only, and the rule that
+judges a kernel against them.
+
+Every function restates the operation from its DEFINITION in include/resr.h on NCHW tensors -- a sum over the nine taps of a
+zero-padded image, then the epilogue steps in the documented order -- and shares no index arithmetic with the kernels.  Each
+evaluates in the precision it is asked for: float64 is the reference, float32 ON THE SAME INPUTS is the yardstick the allowance
+is derived from.  tests/test_conv_ref.py checks the references against torch and shows that the rule rejects wrong kernels before
+tests/test_gpu_kernels.py lets it judge a real one.
+
+Values.  A case runs on exactly the values the kernel is given: f16 / f32 operands after tests/gpu_util.quant, exact16 operands as
+hi + lo / 4096 (pair_value), weights as handed to resr_pack_weights (f16: their f16 rounding; exact16: the fp32 values).  Scalars
+(slope, s0, t0, s1, t1, scale) are taken as float32 and then widened: the kernel's constant is the reference's constant.
+"""
+import numpy as np
+import torch
+
+F16_HALF_ULP = 2.0 ** -11 * 1.01    # half an f16 ulp relative to the value (11 significand bits), 1 % slack for the binade's lower end
+F16_SUBNORMAL = 2.0 ** -24          # spacing of the f16 subnormals
+PAIR_TENSOR_REL = 2e-6              # exact16 outputs: tests/test_gpu_x2_plan.py test_conv_reads_single_chunks_and_writes_single_output
+
+
+def f32scalar(v, dtype):
+    """A descriptor's float field: the float32 nearest to v, widened."""
+    return torch.tensor(float(np.float32(v)), dtype=dtype)
+
+
+def pair_split(t):
+    """fp32 [..] -> (hi, lo) f16 tensors of an exact16 pair: hi = f16(v), lo = f16((v - hi) * 4096)."""
+    hi = t.half()
+    lo = ((t.double() - hi.double()) * 4096.0).half()
+    return hi, lo
+
+
+def pair_value(hi, lo):
+    """The exact float64 value of a pair."""
+    return hi.double() + lo.double() / 4096.0
+
+
+def upsample2(x):
+    """Nearest x2: out[.., y, x] = in[.., y // 2, x // 2]."""
+    n, c, h, w = x.shape
+    return x.reshape(n, c, h, 1, w, 1).expand(n, c, h, 2, w, 2).reshape(n, c, 2 * h, 2 * w)
+
+
+def _padded(x):
+    n, c, h, w = x.shape
+    xp = torch.zeros(n, c, h + 2, w + 2, dtype=x.dtype)
+    xp[:, :, 1:h + 1, 1:w + 1] = x
+    return xp
+
+
+def correlate(x, wt, dtype=torch.float64, up=False):
+    """acc[n,o,y,x] = sum_{c,dy,dx} W[o,c,dy,dx] * in[n,c,y+dy-1,x+dx-1], zero outside the image; `up`: in = nearest x2 of x.
+
+    float32 is evaluated PLAINLY: one fp32 accumulator per output, the 9 * cin products added one after the other.  That is the
+    yardstick the allowance needs.  A BLAS evaluation sums in blocks and in several accumulators per output, which no kernel's single
+    chain of matrix instructions does; its error against float64 is several times below that of ANY single-accumulator order of the
+    same sum (measured on the MI355X with the einsum below as the fp32 yardstick: the f32 kernel, one chain of 9 * cin / 2
+    v_mfma_f32_32x32x2_f32 per output, reached 1.5 x A = 6 x e32 on 1e-4 of the elements of rdb_conv3_2seg).  "Another summation
+    order" (the factor 4 of A) is meant between such chains.  float64 takes the einsum: its error is nothing at this scale."""
+    x, wt = x.to(dtype), wt.to(dtype)
+    if up:
+        x = upsample2(x)
+    n, c, h, w = x.shape
+    xp = _padded(x)
+    acc = torch.zeros(n, wt.shape[0], h, w, dtype=dtype)
+    if dtype == torch.float32:
+        for ci in range(c):
+            for dy in range(3):
+                for dx in range(3):
+                    acc.addcmul_(xp[:, ci:ci + 1, dy:dy + h, dx:dx + w], wt[:, ci, dy, dx].view(1, -1, 1, 1))
+        return acc
+    for dy in range(3):
+        for dx in range(3):
+            acc += torch.einsum("oc,nchw->nohw", wt[:, :, dy, dx], xp[:, :, dy:dy + h, dx:dx + w])
+    return acc
+
+
+def epilogue(acc, dtype=torch.float64, bias=None, mask=None, slope=0.2, lrelu=False, prelu=None, res0=None, s0=1.0, t0=1.0,
+             res1=None, s1=1.0, t1=1.0, clamp=False):
+    """include/resr.h: v = acc + bias; mask / lrelu / prelu / (v*s0 + t0*res0) / (v*s1 + t1*res1) / clamp, in that order.
+    Returns (v, v before the clamp)."""
+    v = acc.to(dtype)
+    sl = f32scalar(slope, dtype)
+    if bias is not None:
+        v = v + bias.to(dtype).view(1, -1, 1, 1)
+    if mask is not None:
+        v = v * torch.where(mask > 0, torch.ones((), dtype=dtype), sl)
+    if lrelu:
+        v = torch.where(v > 0, v, v * sl)
+    if prelu is not None:
+        v = torch.where(v > 0, v, v * prelu.to(dtype).view(1, -1, 1, 1))
+    if res0 is not None:
+        v = v * f32scalar(s0, dtype) + f32scalar(t0, dtype) * res0.to(dtype)
+    if res1 is not None:
+        v = v * f32scalar(s1, dtype) + f32scalar(t1, dtype) * res1.to(dtype)
+    pre = v
+    if clamp:
+        v = v.clamp(0.0, 1.0)
+    return v, pre
+
+
+def conv3x3(x, wt, dtype=torch.float64, up=False, **epi):
+    return epilogue(correlate(x, wt, dtype, up), dtype, **epi)
+
+
+def wgrad(x, g, scale, dtype=torch.float64, up=False):
+    """dW[o,c,dy,dx] = scale * sum_{n,y,x} G[n,o,y,x] * in[n,c,y+dy-1,x+dx-1], db[o] = scale * sum_{n,y,x} G[n,o,y,x]."""
+    x, g = x.to(dtype), g.to(dtype)
+    if up:
+        x = upsample2(x)
+    n, c, h, w = x.shape
+    xp = _padded(x)
+    dw = torch.zeros(g.shape[1], c, 3, 3, dtype=dtype)
+    for dy in range(3):
+        for dx in range(3):
+            dw[:, :, dy, dx] = torch.einsum("nohw,nchw->oc", g, xp[:, :, dy:dy + h, dx:dx + w])
+    sc = f32scalar(scale, dtype)
+    return dw * sc, g.sum(dim=(0, 2, 3)) * sc
+
+
+# ---- the rule (stated in the module docstring of tests/test_gpu_kernels.py) ------------------------------------------------------
+def allowance(ref64, ref32):
+    """(A, e32): e32 = max |ref32 - ref64|, A = max(4 * e32, one fp32 ulp of max |ref64|)."""
+    ref64 = ref64.double()
+    e32 = float((ref32.double() - ref64).abs().max())
+    floor = float(np.spacing(np.float32(float(ref64.abs().max()))))
+    return max(4.0 * e32, floor), e32
+
+
+def bound(ref64, A, kind):
+    """The per-element bound on |got - ref64|.  kind: "f32" (any fp32 output), "f16" (an f16 store: + half an ulp of the element),
+    "pair" (exact16 pair / exact16 fp32 outputs: the per-tensor bound of the x2-plan tests; A plays no part)."""
+    ref64 = ref64.double()
+    if kind == "f32":
+        return torch.full_like(ref64, A)
+    if kind == "f16":
+        return A + torch.clamp(F16_HALF_ULP * ref64.abs(), min=F16_SUBNORMAL)
+    if kind == "pair":
+        return torch.full_like(ref64, PAIR_TENSOR_REL * max(1.0, float(ref64.abs().max())))
+    raise ValueError(kind)
+
+
+def judge(got, ref64, ref32, kind):
+    """Returns a record {cpu32_err, allowance, kernel_err, ratio, bad, worst}: ratio = max over the tensor of |got - ref64| / bound,
+    bad = number of elements beyond their bound (NaNs count), allowance = A (f32, f16) or the tensor bound (pair)."""
+    ref64 = ref64.double()
+    A, e32 = allowance(ref64, ref32)
+    b = bound(ref64, A, kind)
+    err = (got.double() - ref64).abs()
+    bad = ~(err <= b)
+    ratio = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err / b)
+    worst = int(ratio.argmax())
+    return {"cpu32_err": e32, "allowance": float(b.max()) if kind == "pair" else A, "kernel_err": float(err.max()), "ratio": float(ratio.max()),
+            "bad": int(bad.sum()), "frac_bad": float(bad.double().mean()), "worst": worst, "got": float(got.reshape(-1)[worst]),
+            "want": float(ref64.reshape(-1)[worst])}
+
+
+def pass_mask_ok(got_mask, pre64, A):
+    """RESR_CONV_CLAMP01's pass-mask (0 <= v <= 1 before the clamp) may differ from the reference's only where the reference's
+    pre-clamp value lies within A of 0 or 1.  Returns the number of elements that differ anywhere else."""
+    want = (pre64 >= 0) & (pre64 <= 1)
+    near = (pre64.abs() <= A) | ((pre64 - 1.0).abs() <= A)
+    return int(((got_mask.bool() != want) & ~near).sum())
