@@ -7,7 +7,7 @@
 #include <mutex>
 #include <vector>
 
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 
@@ -68,98 +68,6 @@ struct DeviceScope {
     }
 };
 #define RESR_DEVICE_SCOPE(stream) DeviceScope resr_device_scope_(stream)
-
-void conv_trace_set(void*);
-long long conv3x3_chain_errors();
-int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*, const float*, const void*,
-                     const void*, const void*, void*, void*, hipStream_t);
-int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const float*, const float*, void*, hipStream_t);
-int conv3x3_chain_dispatch(int, const ResrConvDesc*, const void*, const void*, const void* const*, const float* const*,
-                           const void* const*, void* const*, void* const*, void*, size_t, hipStream_t);
-size_t conv3x3_chain_state_bytes(int, int, int);
-int wgrad_dispatch(const ResrWgradDesc*, const void*, const void*, const void*, float*, float*, float*, hipStream_t);
-size_t wgrad_partial_bytes(const ResrWgradDesc*);
-int wgrad_debug_plan(const int*, const int*, int, int*, int);
-int wgrad_debug_dense_blocks(int, const void* const*, const void* const*, int, int, int, int, float*, size_t, float*, hipStream_t);
-int pack_dispatch(const ResrPackChunk*, int, const float*, void*, int, hipStream_t);
-int pack_mx_dispatch(const ResrPackChunk*, int, const float*, void*, hipStream_t);
-size_t generator_mx_offset(const ResrGeneratorDesc*);
-int ema_dispatch(float*, const float*, long, double, hipStream_t);
-int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
-int nhwc_to_nchw_dispatch(const void*, float*, int, int, int, int, int, int, int, hipStream_t, long);
-int sumpool2x2_dispatch(const void*, void*, const void*, int, int, int, int, int, float, hipStream_t, long, long);
-size_t generator_param_count(const ResrGeneratorDesc*);
-size_t generator_packed_bytes(const ResrGeneratorDesc*, int);
-size_t generator_workspace_bytes(const ResrGeneratorDesc*);
-size_t generator_chain_state_bytes(const ResrGeneratorDesc*);
-int64_t generator_pack_table(const ResrGeneratorDesc*, int, ResrPackChunk*, int64_t);
-int64_t generator_buffer_offsets(const ResrGeneratorDesc*, int64_t*, int64_t);
-int generator_forward(const ResrGeneratorDesc*, const float*, const float*, const void*, void*, size_t, float*, hipStream_t);
-int generator_backward(const ResrGeneratorDesc*, const float*, const float*, const void*, void*, size_t, float*, float*,
-                       hipStream_t, void* const*, int);
-
-size_t compact_param_count(const ResrCompactDesc*);
-size_t compact_packed_bytes(const ResrCompactDesc*);
-size_t compact_workspace_bytes(const ResrCompactDesc*);
-int64_t compact_pack_table(const ResrCompactDesc*, ResrPackChunk*, int64_t);
-int compact_forward_ends(const ResrCompactDesc*, const Ends&, const float*, const void*, void*, size_t, hipStream_t, const char*);
-int compact_yuv420_scaled_fits(int, int, int, int, int, int, int, int);
-int image_resize_dispatch(const float*, void*, int, int, int, int, int, int, const int32_t*, const float*, int, const int32_t*,
-                          const float*, int, int, hipStream_t);
-int yuv420_to_rgb_dispatch(const uint8_t*, uint8_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
-int rgb_to_yuv420_dispatch(const uint8_t*, uint8_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
-int yuv420p10_to_nchw_dispatch(const uint16_t*, float*, int, int, int, const ResrYuvDesc*, hipStream_t);
-int nchw_to_yuv420p10_dispatch(const float*, uint16_t*, int, int, int, const ResrYuvDesc*, hipStream_t);
-int u8_to_nchw_dispatch(const uint8_t*, float*, int, int, int, hipStream_t);
-int nchw_to_u8_dispatch(const float*, uint8_t*, int, int, int, hipStream_t);
-
-size_t discriminator_param_count();
-size_t discriminator_uv_count();
-size_t discriminator_workspace_bytes(const ResrDiscriminatorDesc*);
-int64_t discriminator_pack_table(const ResrDiscriminatorDesc*, const void*, ResrPackChunk*, int64_t);
-int discriminator_forward(const ResrDiscriminatorDesc*, const float*, const float*, float*, const ResrPackChunk*, int, void*, size_t, float*,
-                          hipStream_t);
-int discriminator_backward(const ResrDiscriminatorDesc*, const float*, const float*, void*, size_t, float*, float*, hipStream_t);
-int discriminator_backward_f16(const ResrDiscriminatorDesc*, const float*, const float*, const ResrPackChunk*, int, void*, size_t, float*,
-                               float*, hipStream_t);
-
-int filter2d_dispatch(const float*, float*, const float*, int, int, int, int, int, int, int, hipStream_t);
-int usm_dispatch(const float*, float*, float*, const float*, int, float, float, int, int, int, int, hipStream_t, int);
-int resize_dispatch(const float*, float*, int, int, int, int, int, int, int, double, double, hipStream_t);
-int usm_bwd_dispatch(const float*, const float*, const float*, float*, float*, const float*, int, float, int, int, int, int, hipStream_t);
-int randn_dispatch(float*, long, uint64_t, uint64_t, hipStream_t);
-int gauss_noise_dispatch(const float*, float*, const float*, const float*, const float*, const float*, int, int, int, int, int,
-                         hipStream_t);
-int poisson_noise_dispatch(const float*, float*, const float*, const float*, uint64_t, void*, int, int, int, int, int, hipStream_t);
-int jpeg_dispatch(const float*, float*, const float*, float*, int, int, int, int, hipStream_t);
-int quantize_crop_dispatch(const float*, const float*, float*, float*, int, int, int, int, int, int, int, int, int, int, hipStream_t);
-
-int filter2d_u8_dispatch(const uint8_t*, uint8_t*, const int32_t*, int, int, int, int, int, int, int, hipStream_t);
-int jpeg_u8_dispatch(const uint8_t*, uint8_t*, const float*, int32_t*, int, int, int, hipStream_t);
-int resize_u8_dispatch(const uint8_t*, uint8_t*, int, int, int, int, int, int, int, const int32_t*, const int32_t*, const int32_t*,
-                       const int32_t*, hipStream_t);
-
-int s2d_dispatch(const void*, void*, int, int, int, int, int, int, hipStream_t);
-int bilinear_up_dispatch(const void*, void*, int, int, int, int, int, int, hipStream_t, long, long);
-int add_mask_dispatch(const void*, const void*, const void*, void*, long, int, float, hipStream_t);
-int l1_partial_dispatch(const void*, const void*, long, int, long, float*, int, hipStream_t);
-int bce_logits_const_dispatch(const float*, long, float, float, float*, float*, float*, hipStream_t);   // loss.hip
-int l1_mean_dispatch(const float*, const float*, long, float, float*, float*, float*, hipStream_t);
-int weighted_rows_dispatch(const float*, int, int, const float*, float*, hipStream_t);
-int sustained_run(int, double, const void*, size_t, void*, double*, double*, hipStream_t);   // sustained.hip
-int spectral_norm_dispatch(const float*, float*, float*, int, int, int, float, float*, float*, hipStream_t);
-int spectral_norm_bwd_dispatch(const float*, const float*, const float*, const float*, const float*, float*, int, int, int, float*,
-                               hipStream_t);
-int fold4x4_dispatch(const float*, float*, int, int, hipStream_t);
-int d2s_add_mask_dispatch(const void*, const void*, const void*, void*, int, int, int, int, int, float, hipStream_t, long, long, long);
-int bilinear_up_bwd_mask_dispatch(const void*, void*, const void*, void*, int, int, int, int, int, float, hipStream_t, long, long);
-int spectral_norm_batch_dispatch(int, const float* const*, float* const*, float* const*, const int*, const int*, int, float, float* const*,
-                                 float* const*, hipStream_t);
-int spectral_norm_bwd_batch_dispatch(int, const float* const*, const float* const*, const float* const*, const float* const*, const float* const*,
-                                     float* const*, const int*, const int*, float*, hipStream_t);
-int fold4x4_batch_dispatch(int, const float* const*, float* const*, const int*, const int*, hipStream_t);
-int maxpool2x2_dispatch(const void*, void*, int, int, int, int, int, hipStream_t, long, long, uint8_t*);
-int maxpool2x2_bwd_dispatch(const void*, const uint8_t*, void*, int, int, int, int, int, hipStream_t, long, long);
 
 // probe used by tests: what does ds_read_b64_tr_b16 hand to (lane, element)?  LDS holds the element
 // index at every position; lane l supplies byte address l*8.

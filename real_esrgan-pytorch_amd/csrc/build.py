@@ -16,6 +16,8 @@ LIB = os.path.join(HERE, "libresr_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(ROOT, "include"), "-I", HERE,
          "-Wno-unused-result"]
+# --no-undefined: a call whose declaration matches no definition fails here, at the link, not in the first process that loads the library
+LINK_FLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,--no-undefined"]
 
 
 def _stale(target, deps):
@@ -26,7 +28,8 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=False):
-    hdrs = [os.path.join(HERE, "common.h"), os.path.join(HERE, "conv3x3.h"), os.path.join(HERE, "conv3x3_ws.h"), os.path.join(HERE, "conv3x3_ws_chain.h"), os.path.join(HERE, "wgrad.h"), os.path.join(HERE, "yuv.h"), os.path.join(ROOT, "include", "resr.h"), os.path.join(ROOT, "include", "resr_debug.h"), os.path.abspath(__file__)]
+    # every header of csrc/ and include/, and this file: a new header cannot be left out of the staleness check
+    hdrs = [os.path.join(d, f) for d in (HERE, os.path.join(ROOT, "include")) for f in sorted(os.listdir(d)) if f.endswith(".h")] + [os.path.abspath(__file__)]
     extra = [s for s in os.listdir(HERE) if s.endswith(".hip") and s not in SOURCES]
     srcs = SOURCES + sorted(extra)
     objs, jobs = [], []
@@ -51,7 +54,7 @@ def build(force=False, verbose=False):
             if r.returncode:
                 raise RuntimeError("hipcc failed: " + " ".join(cmd))
     if force or jobs or _stale(LIB, objs):
-        cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs
+        cmd = [HIPCC] + LINK_FLAGS + ["-o", LIB] + objs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode:
             sys.stderr.write(r.stdout + r.stderr)

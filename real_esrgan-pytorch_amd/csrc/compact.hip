@@ -19,25 +19,10 @@
 //                     only the resized frame, uint8 [N,oh,ow,3] or YUV 4:2:0 [N,3oh/2,ow], is written.
 #include <vector>
 
-#include "common.h"
+#include "host_api.h"
 #include "yuv.h"
 
 namespace resr {
-
-int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*, const float*, const void*,
-                     const void*, const void*, void*, void*, hipStream_t);
-int conv3x3_dispatch_prelu(const ResrConvDesc*, const void*, const void*, const float*, const float*, void*, hipStream_t);
-int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
-int frame_head_dispatch(const void*, void*, int, int, int, int, hipStream_t, long, const ResrYuvDesc*);   // frames.hip
-int compact_tail_u8(const float*, const uint8_t*, uint8_t*, int, int, int, int, hipStream_t);
-int yuv_forward_check(const char*, int, int, int, int, const void*, const ResrYuvDesc*, const ResrYuvDesc*, int);
-int compact_tail_yuv(const float*, const void*, void*, int, int, int, int, const ResrYuvDesc*, const ResrYuvDesc*, hipStream_t);
-int resize_plan(const char*, int, int, int, int, int, int, const void*, const void*, int, const void*, const void*, int, int,
-                const void*, ResizeGeom*);                                                                      // image_resize.hip
-int compact_tail_u8_scaled(const float*, const uint8_t*, uint8_t*, int, int, int, int, const int32_t*, const float*, const int32_t*,
-                           const float*, const ResizeGeom*, hipStream_t);
-int compact_tail_yuv420_scaled(const float*, const void*, void*, int, int, int, int, const int32_t*, const float*, const int32_t*,
-                               const float*, const ResrYuvDesc*, const ResrYuvDesc*, const ResizeGeom*, hipStream_t);
 
 namespace {
 

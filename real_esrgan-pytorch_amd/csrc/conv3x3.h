@@ -1,7 +1,8 @@
 // Shared pieces of the 3x3 convolution kernels (conv3x3.hip: register-staged tiles; conv3x3_ws.hip: persistent,
-// producer/consumer wave-specialised tiles).
+// producer/consumer wave-specialised tiles): the argument structs, the declarations of the host launchers that take them,
+// and the fragment / vector helpers of the kernels.
 #pragma once
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 
@@ -101,6 +102,27 @@ struct ChainArgs {
     ChainJob job[kMaxChain];
 };
 struct ChainNone {};
+
+// The host launchers that take these types, each declared here once (the rule of host_api.h), grouped by defining file.  tile_rows: rows
+// of a workgroup's tile (16 or 8); x2: RESR_F16X2 operands; mt: 32-row output tiles per workgroup (1: cout <= 32, 2: cout 64); flop, bytes:
+// for the profile (chain_f16: per job; chain_launch*: their sums).
+// conv3x3_ws.hip.  chain_f16: RESR_OK launched; 1 = cannot chain here (the caller's state too small / misaligned): one launch per job instead
+bool conv3x3_ws_supported(const ConvArgs& a);
+int conv3x3_ws_f16(const ConvArgs& a, int mt, bool x2, hipStream_t stream);
+int conv3x3_ws_chain_f16(const ConvArgs& a, const ChainJob* jobs, int njobs, const double* flop, const double* bytes, bool x2, void* state, size_t state_bytes, hipStream_t stream);
+// conv3x3_ws_mt1.hip, _mt2.hip (f16), conv3x3_ws_x2_mt1.hip, _x2_mt2.hip (RESR_F16X2), conv3x3_ws_mx.hip (RESR_CONV_MX_PAIRS)
+int conv3x3_ws_mt1(const ConvArgs& a, int tile_rows, hipStream_t stream);
+int conv3x3_ws_mt2(const ConvArgs& a, int tile_rows, hipStream_t stream);
+int conv3x3_ws_x2_mt1(const ConvArgs& a, int tile_rows, hipStream_t stream);
+int conv3x3_ws_x2_mt2(const ConvArgs& a, int tile_rows, hipStream_t stream);
+int conv3x3_ws_mx_mt1(const ConvArgs& a, int tile_rows, hipStream_t stream);
+int conv3x3_ws_mx_mt2(const ConvArgs& a, int tile_rows, hipStream_t stream);
+// conv3x3_ws_sp.hip.  sp: 1 = the sparse taps of the forward pass, 2 = of backward-data (conv3x3_ws.h, SP)
+int conv3x3_ws_sparse(const ConvArgs& a, int tile_rows, int sp, bool x2, hipStream_t stream);
+// conv3x3_ws_chain.hip, _chain_x2.hip, _chain_mx.hip.  kind: 0 inference forward, 1 training forward, 2 backward-data (conv3x3_ws_chain.h)
+int conv3x3_ws_chain_launch(const ConvArgs& a, const ChainArgs& cj, int tile_rows, int kind, bool x2, double flop, double bytes, hipStream_t stream);
+int conv3x3_ws_chain_launch_x2(const ConvArgs& a, const ChainArgs& cj, int tile_rows, int kind, double flop, double bytes, hipStream_t stream);
+int conv3x3_ws_chain_launch_mx(const ConvArgs& a, const ChainArgs& cj, int tile_rows, int kind, double flop, double bytes, hipStream_t stream);
 
 // Algorithmic HBM bytes of one pass: input channels + output (+ mask, residuals, aux) once per pixel.
 // (es = 4 for RESR_F16X2 pairs: single f16 chunks / a single f16 output count 2 bytes per element)

@@ -295,12 +295,6 @@ static int launch_conv(const ConvArgs& a, hipStream_t stream) {
     return RESR_OK;
 }
 
-int conv3x3_ws_f16(const ConvArgs& a, int mt, bool x2, hipStream_t stream);  // conv3x3_ws.hip
-bool conv3x3_ws_supported(const ConvArgs& a);
-bool conv3x3_chain_device_ok();
-
-int conv3x3_ws_chain_f16(const ConvArgs& a, const ChainJob* jobs, int njobs, const double* flop, const double* bytes, bool x2, void* state, size_t state_bytes,
-                         hipStream_t stream);   // conv3x3_ws.hip (1 = the state buffer does not cover this geometry)
 static int conv3x3_route(const ResrConvDesc* d, ConvArgs& a, bool have_bias, bool have_in1, hipStream_t stream);
 
 // descriptor + pointers -> kernel arguments (validation included)

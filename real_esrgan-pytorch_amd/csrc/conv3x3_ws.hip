@@ -11,13 +11,6 @@ namespace resr {
 unsigned long long* g_conv_trace = nullptr;
 void conv_trace_set(void* p) { g_conv_trace = (unsigned long long*)p; }
 
-int conv3x3_ws_mt1(const ConvArgs& a, int tile_rows, hipStream_t stream);
-int conv3x3_ws_mt2(const ConvArgs& a, int tile_rows, hipStream_t stream);
-int conv3x3_ws_x2_mt1(const ConvArgs& a, int tile_rows, hipStream_t stream);   // RESR_F16X2 instantiations
-int conv3x3_ws_x2_mt2(const ConvArgs& a, int tile_rows, hipStream_t stream);
-int conv3x3_ws_mx_mt1(const ConvArgs& a, int tile_rows, hipStream_t stream);   // RESR_CONV_MX_PAIRS instantiations (conv3x3_ws_mx.hip)
-int conv3x3_ws_mx_mt2(const ConvArgs& a, int tile_rows, hipStream_t stream);
-
 // Preconditions of the producer's 24 x 24-bit offsets and of the 8-channel epilogue; otherwise the caller uses the
 // one-role kernel.
 // The chained launches split the image range over 8 XCDs of 32 CUs (conv3x3_ws.h, CH): only on the full device (an
@@ -60,9 +53,6 @@ static int pick_rows(const ConvArgs& a, const int* rows, int nrows) {
     }
     return rows[nrows - 1];
 }
-
-int conv3x3_ws_sparse(const ConvArgs& a, int tile_rows, int sp, bool x2, hipStream_t stream);   // conv3x3_ws_sp.hip
-int conv3x3_ws_chain_launch(const ConvArgs& a, const ChainArgs& cj, int tile_rows, int kind, bool x2, double flop, double bytes, hipStream_t stream);   // conv3x3_ws_chain.hip
 
 // ---- chained dense-block passes (conv3x3_ws.h, CH) ----
 // All device-side state (epoch, tickets, flags, error counters) lives in memory the CALLER hands in (conv3x3.h, ChainArgs):

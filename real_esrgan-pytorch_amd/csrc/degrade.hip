@@ -16,7 +16,7 @@
 
 #include <stdlib.h>
 
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 
@@ -653,7 +653,7 @@ __global__ void unique_vals_kernel(const unsigned* __restrict__ flags, float* __
 
 // Poisson sampler: inversion for small means, Hormann's PTRS (transformed rejection) otherwise -- the same
 // two regimes torch.poisson uses.
-__device__ float poisson_draw(float lam, Philox& ph) {
+static __device__ float poisson_draw(float lam, Philox& ph) {
     uint32_t r[4];
     if (lam <= 0.f) return 0.f;
     if (lam < 10.f) {

@@ -19,7 +19,7 @@
 #include <cmath>
 #include <mutex>
 
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 

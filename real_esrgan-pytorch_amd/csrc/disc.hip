@@ -9,7 +9,7 @@
 //   add_mask                          skip-connection gradient merge fused with the LeakyReLU backward
 //   fold4x4                           virtual 3x3x4C weight gradient -> real 4x4xC layout
 // All HBM-bound helpers; pixel-major (NHWC) activations of type T.
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(256) void sn_wt_u_kernel(const SnArgs a) {
     L.vraw[(size_t)grp * cols + k] = (s0 + s1) + (s2 + s3);
 }
 
-__device__ float block_sum(float v, float* red) {
+static __device__ float block_sum(float v, float* red) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;

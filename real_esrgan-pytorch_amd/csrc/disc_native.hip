@@ -18,38 +18,9 @@
 // stage of the conv kernel (16 of 36 tap blocks), all 64-channel output groups of a layer in one launch (f16).
 #include <vector>
 
-#include "common.h"
-#include "wgrad.h"
+#include "host_api.h"
 
 namespace resr {
-
-int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*, const float*, const void*, const void*,
-                     const void*, void*, void*, hipStream_t);
-size_t wgrad_batch_partial_bytes(const WgradConv*, int, int, int);
-int wgrad_batch(const WgradConv*, int, int, int, int, int, int, int, float*, hipStream_t);
-int wgrad_tile_rows(int dtype);
-int wgrad_layer(const WgradConv*, int, int, int, int, int, int, float*, hipStream_t);   // (called as resr::wgrad_layer below: a lambda shares the name)
-size_t wgrad_layer_partial_bytes(int cin, int cout_pad, int splits, int dtype);
-int wgrad_x2_products();
-int wgrad_x2_products();
-int pack_dispatch(const ResrPackChunk*, int, const float*, void*, int, hipStream_t);
-int nchw_to_nhwc_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long);
-int nhwc_to_nchw_dispatch(const void*, float*, int, int, int, int, int, int, int, hipStream_t, long);
-int absmax_dispatch(const float*, long, unsigned*, int, hipStream_t);
-int nchw_to_nhwc_scaled_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long, const unsigned*);
-int nhwc_to_nchw_scaled_dispatch(const void*, float*, int, int, int, int, int, int, int, hipStream_t, long, const unsigned*);
-int s2d_dispatch(const void*, void*, int, int, int, int, int, int, hipStream_t);
-int bilinear_up_dispatch(const void*, void*, int, int, int, int, int, int, hipStream_t, long, long);
-int d2s_add_mask_dispatch(const void*, const void*, const void*, void*, int, int, int, int, int, float, hipStream_t, long, long, long);
-int bilinear_up_bwd_mask_dispatch(const void*, void*, const void*, void*, int, int, int, int, int, float, hipStream_t, long, long);
-int spectral_norm_batch_dispatch(int, const float* const*, float* const*, float* const*, const int*, const int*, int, float, float* const*,
-                                 float* const*, hipStream_t);
-int spectral_norm_bwd_dispatch(const float*, const float*, const float*, const float*, const float*, float*, int, int, int, float*,
-                               hipStream_t);
-int fold4x4_dispatch(const float*, float*, int, int, hipStream_t);
-int spectral_norm_bwd_batch_dispatch(int, const float* const*, const float* const*, const float* const*, const float* const*, const float* const*,
-                                     float* const*, const int*, const int*, float*, hipStream_t);
-int fold4x4_batch_dispatch(int, const float* const*, float* const*, const int*, const int*, hipStream_t);
 
 namespace {
 
@@ -441,7 +412,7 @@ int backward_pass(const DPlan& pc, int dt, const float* gy, const float* params,
             c.unscale = gsc;
             const int splits = layer_splits(chunks * (c.cout_pad / 32), N, h, w, parts);
             if (wgrad_layer_partial_bytes(cin_pad, c.cout_pad, splits, dt) > b.partial_bytes) return fail(RESR_ERR_WORKSPACE, "discriminator: wgrad slabs (layer mode)");
-            DRUN(resr::wgrad_layer(&c, N, h, w, dt, 0, splits, b.partial, st));
+            DRUN(resr::wgrad_layer(&c, N, h, w, dt, 0, splits, b.partial, st));   // resr:: -- the lambda shares the name
         } else {
         int tiles_per = kWgradMaxJobs / (chunks * parts);
         if (tiles_per > 80 / chunks) tiles_per = 80 / chunks;

@@ -21,7 +21,7 @@
 // The 10-bit YUV path is the same composition with 1023 levels: the integer functions with 64 / 512 / 1023 for 16 / 128 / 255,
 // x = (float)rgb10 / 1023.0f on the way in and v * 1023.0f, clamp to [0, 1023], truncate on the way out (include/resr.h).
 // Every index that can pass 2^31 is 64-bit.  Vector stores only.
-#include "common.h"
+#include "host_api.h"
 #include "yuv.h"
 
 namespace resr {

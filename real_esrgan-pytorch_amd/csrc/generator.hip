@@ -27,29 +27,9 @@
 #include <stdlib.h>
 #include <vector>
 
-#include "common.h"
-#include "wgrad.h"
+#include "host_api.h"
 
 namespace resr {
-
-int conv3x3_dispatch(const ResrConvDesc*, const void*, const void*, const void*, const float*, const void*,
-                     const void*, const void*, void*, void*, hipStream_t);
-size_t wgrad_batch_partial_bytes(const WgradConv*, int, int, int);
-int conv3x3_block_dispatch(int njobs, const ResrConvDesc* d, const void* in0, const void* in1, const void* const* w,
-                           const float* const* bias, const void* const* mask, void* const* out, void* const* aux,
-                           const ResrConvDesc* d5, const void* w5, const float* bias5, const void* res0_5, const void* res1_5,
-                           void* out5, void* chain_state, size_t chain_state_bytes, hipStream_t stream);
-size_t conv3x3_chain_state_bytes(int, int, int);
-int wgrad_batch(const WgradConv*, int, int, int, int, int, int, int, float*, hipStream_t);
-int wgrad_batch_jobs(const WgradConv*, int, int);
-int wgrad_batch_quads(const WgradConv*, int, int);
-int wgrad_tile_rows(int dtype);
-int wgrad_x2_products();
-int absmax_dispatch(const float*, long, unsigned*, int, hipStream_t);
-int nchw_to_nhwc_q_dispatch(const float*, void*, int, int, int, int, int, int, int, const uint8_t*, hipStream_t, long, const unsigned*, long);
-int nhwc_to_nchw_scaled_dispatch(const void*, float*, int, int, int, int, int, int, int, hipStream_t, long, const unsigned*);
-int sumpool2x2_dispatch(const void*, void*, const void*, int, int, int, int, int, float, hipStream_t, long, long);
-int add_inplace_dispatch(void*, const void*, long, int, hipStream_t, long, long);
 
 namespace {
 

@@ -44,7 +44,7 @@
 // include/resr.h bit for bit: the sums are those of the two stages above, the integer functions those of frames.hip.
 #include <limits.h>
 
-#include "common.h"
+#include "host_api.h"
 #include "yuv.h"
 
 namespace resr {

@@ -10,7 +10,7 @@
 // All are one-pass, 16-byte vectorised where the layout allows; each thread owns one pixel.
 #include <math.h>
 
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 
@@ -270,10 +270,6 @@ int absmax_dispatch(const float* src, long count, unsigned* slot, int target_log
     return RESR_OK;
 }
 
-int nchw_to_nhwc_q_dispatch(const float* src, void* dst, int n, int c, int h, int w, int r, int c_pad, int dtype,
-                            const uint8_t* mask, hipStream_t stream, long lo_off, const unsigned* amax, long q_off);
-int nchw_to_nhwc_scaled_dispatch(const float* src, void* dst, int n, int c, int h, int w, int r, int c_pad, int dtype,
-                                 const uint8_t* mask, hipStream_t stream, long lo_off, const unsigned* amax);
 int nchw_to_nhwc_dispatch(const float* src, void* dst, int n, int c, int h, int w, int r, int c_pad, int dtype,
                           const uint8_t* mask, hipStream_t stream, long lo_off) {
     return nchw_to_nhwc_scaled_dispatch(src, dst, n, c, h, w, r, c_pad, dtype, mask, stream, lo_off, nullptr);
@@ -302,8 +298,6 @@ int nchw_to_nhwc_q_dispatch(const float* src, void* dst, int n, int c, int h, in
     return RESR_OK;
 }
 
-int nhwc_to_nchw_scaled_dispatch(const void* src, float* dst, int n, int c, int h, int w, int r, int src_stride, int dtype,
-                                 hipStream_t stream, long lo_off, const unsigned* amax);
 int nhwc_to_nchw_dispatch(const void* src, float* dst, int n, int c, int h, int w, int r, int src_stride, int dtype,
                           hipStream_t stream, long lo_off) {
     return nhwc_to_nchw_scaled_dispatch(src, dst, n, c, h, w, r, src_stride, dtype, stream, lo_off, nullptr);

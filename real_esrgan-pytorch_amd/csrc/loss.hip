@@ -9,7 +9,7 @@
 // and 1/N folded in -- and one partial sum; the LAST workgroup to arrive (a device-scope counter in the caller's scratch) adds
 // the partials in a fixed order, so the value is deterministic and bit-reproducible from run to run, and re-arms the counter.
 // HBM-bound: 4 B read (+ 4 B for the second operand of L1) and 4 B written per value.
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 

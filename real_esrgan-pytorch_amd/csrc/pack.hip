@@ -7,7 +7,7 @@
 // so that a wave's A-fragment is one contiguous, coalesced 1 KiB load.
 // Backward-data chunks are gathered transposed (M = cin, K = cout) with flipped taps and an optional
 // scale (the 0.2 residual scalings of model.py:95,129 folded into the weights).
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 

@@ -6,7 +6,7 @@
 //   mode 2  8 waves per workgroup issuing v_mfma_f32_32x32x16_f16 on random f16 operands
 //   mode 3  both at once
 // Launched back to back for `seconds`; the last third is timed with events.
-#include "common.h"
+#include "host_api.h"
 
 namespace resr {
 

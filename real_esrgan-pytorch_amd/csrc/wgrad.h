@@ -1,5 +1,6 @@
 // wgrad.h -- host-side description of one convolution of a batched weight-gradient launch (wgrad.hip); shared with
-// the whole-network planners (generator.hip, disc_native.hip).
+// the whole-network planners (generator.hip, disc_native.hip).  The functions that take it (wgrad_batch, wgrad_layer, ...) are
+// declared in host_api.h, which includes this file.
 #pragma once
 
 namespace resr {

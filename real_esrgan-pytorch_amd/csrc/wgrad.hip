@@ -30,8 +30,7 @@
 #include <mutex>
 #include <vector>
 
-#include "common.h"
-#include "wgrad.h"
+#include "host_api.h"
 
 namespace resr {
 

@@ -11,19 +11,20 @@ from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "real_esrgan-pytorch_amd", "csrc")
+sys.path.insert(0, CSRC)
+from build import FLAGS, HIPCC, LINK_FLAGS  # noqa: E402  (the compiler and the flags of the real build, plus this variant's)
 
 
 def main():
     name, extra = sys.argv[1], sys.argv[2:]
     out_dir = os.path.join(ROOT, "tools", "ab", name)
     os.makedirs(out_dir, exist_ok=True)
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
-             "-Wno-unused-result"] + extra
+    flags = FLAGS + extra
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
 
     def cc(f):
         obj = os.path.join(out_dir, f.replace(".hip", ".o"))
-        r = subprocess.run(["/opt/rocm/bin/hipcc"] + flags + ["-c", os.path.join(CSRC, f), "-o", obj], capture_output=True, text=True)
+        r = subprocess.run([HIPCC] + flags + ["-c", os.path.join(CSRC, f), "-o", obj], capture_output=True, text=True)
         if r.returncode:
             raise RuntimeError(r.stderr)
         return obj
@@ -31,7 +32,7 @@ def main():
     with ThreadPoolExecutor(max_workers=6) as ex:
         objs = list(ex.map(cc, srcs))
     lib = os.path.join(ROOT, "tools", "ab", name + ".so")
-    subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib] + objs, check=True)
+    subprocess.run([HIPCC] + LINK_FLAGS + ["-o", lib] + objs, check=True)
     print(lib)
 
 
