@@ -77,7 +77,7 @@ struct Plan {
 
 int round32(int v) { return (v + 31) / 32 * 32; }
 
-// The prerequisite rules of the plan bits, {bit, the bits it needs, text}: the table of include/resr.h (real_esrgan-pytorch_amd/_lib.py holds the same one for the module)
+// The prerequisite rules of the plan bits, {bit, the bits it needs, text}: the table of include/resr.h, checked here alone (the module asks: _lib.x2_plan_error)
 constexpr struct X2Rule { int bit, needs; const char* text; } kX2Rules[] = {
     {RESR_X2_PLAN_GROWTH_GRAD_STORE_F16, 2, "GROWTH_GRAD_STORE_F16 (4) refines GROWTH_GRAD_F16 (2)"},
     {RESR_X2_PLAN_GROWTH_ACT_G_HI_WGRAD, 8, "GROWTH_ACT_G_HI_WGRAD (16) refines GROWTH_ACT_F16_WGRAD (8)"},

@@ -183,7 +183,7 @@ class Generator(nn.Module):
     MFMAs per product, fp32 accumulate: meets the 1e-3 parity tolerance vs the fp32 CPU path at about a third
     of fast mode's throughput), "strict" = f32 operands on v_mfma_f32_32x32x2_f32 (bit-for-bit fp32 FMA chains).
     Default from $RESR_PRECISION, else "fast".
-    `x2_plan` (exact16 only; bit set of _lib.X2_PLAN_*, which bit needs which: _lib.X2_PLAN_RULES; default from $RESR_X2_PLAN, else 763 = bits 0, 1, 3, 4, 5, 6, 7, 9; 59 = round 5's default without the MX stages): which tensors of the dense
+    `x2_plan` (exact16 only; bit set of _lib.X2_PLAN_*, which bit needs which: the table above the RESR_X2_PLAN_* enum in include/resr.h; default from $RESR_X2_PLAN, else 763 = bits 0, 1, 3, 4, 5, 6, 7, 9; 59 = round 5's default without the MX stages): which tensors of the dense
     blocks are single f16 instead of hi/lo pairs -- bit 0: the growth planes o1..o4 of an INFERENCE forward (50 instead of 60
     stages per block; forward ~1e-6 at the reference's init scale, gate 2e-4), bit 1: the growth-plane gradients of the backward
     pass are READ as single f16 (two stages / two tap-products on their chunks; the bias sums still take hi + lo; worst gradient
@@ -222,7 +222,7 @@ class Generator(nn.Module):
         self.precision = precision or os.environ.get("RESR_PRECISION", "fast")
         self._dtype = _precision_to_dtype(self.precision)
         self.x2_plan = int(os.environ.get("RESR_X2_PLAN", "763")) if x2_plan is None else int(x2_plan)
-        err = _lib.x2_plan_error(self.x2_plan)   # the rule table of _lib.X2_PLAN_RULES / include/resr.h
+        err = _lib.x2_plan_error(self.x2_plan)   # the library checks the rule table of include/resr.h; the text is its own
         if err:
             raise ValueError(err)
         self.n_blocks = n_blocks or self.N_BLOCKS

@@ -34,7 +34,7 @@ def test_library_exports_every_declared_symbol(built):
         for name in names:
             assert hasattr(lib, name), f"{name} declared in include/{h} but not exported"
         declared += names
-    assert set(built._lib.exported_symbols()) <= set(declared)
+    assert set(built._lib.exported_symbols()) == set(declared)      # the binding is read from the same headers: nothing more, nothing less
     assert lib.resr_version() == built._lib.RESR_VERSION == 3
 
 
@@ -44,6 +44,34 @@ def test_struct_layouts_match_header(built):
     assert ctypes.sizeof(L.WgradDesc) == 16 * 4 + 4 * 8   # 15 fields + padding + 2 hi->lo offsets + 2 chunk strides
     assert ctypes.sizeof(L.PackChunk) == 64
     assert ctypes.sizeof(L.GeneratorDesc) == 12 * 4   # + x2_plan, reserved_ (ABI version 2)
+    assert ctypes.sizeof(L.CompactDesc) == 8 * 4
+    assert ctypes.sizeof(L.YuvDesc) == 4 + 9 * 4 + 9 * 4
+    assert ctypes.sizeof(L.DiscriminatorDesc) == 6 * 4
+    assert ctypes.sizeof(L.ProfEntry) == 4 + 4 + 8 + 8
+    # 26 4-byte fields, 5 hi->lo offsets, s2d_in / s2d_out / cout_groups / x2_pair_chunks / reserved2_ (164) and 4 bytes of padding
+    assert L.ConvDesc.mask_lo_offset.offset == 26 * 4 + 5 * 8 + 5 * 4 + 4 == 168 and L.ConvDesc.w_mx_offset.offset == 168 + 4 * 8
+
+
+def test_header_reader_refuses_what_it_cannot_read(built):
+    """_header.parse raises on a statement it cannot classify and quotes it: nothing of a header is skipped silently."""
+    from real_esrgan_pytorch_amd import _header
+    wrap = 'extern "C" {\n%s\n}\n'
+    abi = _header.parse(wrap % "typedef struct { int32_t n, h; int64_t big[2]; const float* p; } ResrToyDesc;\n"
+                               "enum { RESR_A = 1 << 3, RESR_B = -2 };\nsize_t resr_toy(const ResrToyDesc* d, const void* const* pp, void* s);")
+    toy = abi.structs["ResrToyDesc"]
+    assert [f[0] for f in toy._fields_] == ["n", "h", "big", "p"] and ctypes.sizeof(toy) == 8 + 16 + 8
+    assert abi.consts == {"RESR_A": 8, "RESR_B": -2}
+    assert abi.protos == {"resr_toy": (ctypes.c_size_t, [ctypes.POINTER(toy), ctypes.c_void_p, ctypes.c_void_p])}
+    for bad in ("int resr_toy(unsigned long n, void* stream);",              # a scalar type outside the ABI's
+                "int resr_toy(int32_t n, void (*done)(int), void* stream);",  # a function-pointer parameter
+                "enum { RESR_A = 1, RESR_B = RESR_A + 1 };",                  # a value that is neither an integer nor a shift
+                "typedef struct { short n; } ResrToyDesc;",
+                "int resr_toy(const ResrMissingDesc* d);",
+                "static const int resr_toy = 3;"):
+        with pytest.raises(ValueError, match=re.escape(bad.rstrip(";"))):
+            _header.parse(wrap % bad)
+    with pytest.raises(RuntimeError, match=re.escape(os.path.join("nowhere", "resr.h"))):
+        _header.read(os.path.join("nowhere", "resr.h"))
 
 
 def test_host_planning_calls_need_no_gpu(built):

@@ -1,5 +1,6 @@
-"""CPU: the prerequisite rules of ResrGeneratorDesc.x2_plan live twice -- _lib.X2_PLAN_RULES for the module, csrc/generator.hip
-resolve_x2_plan for the C ABI -- and must refuse exactly the same plans, over all 4096 of them and both `training` values."""
+"""CPU: the prerequisite rules of ResrGeneratorDesc.x2_plan live once, in csrc/generator.hip resolve_x2_plan; the module asks the library
+(_lib.x2_plan_error: a size query on a minimal descriptor).  Its answer and every entry point that takes the descriptor must refuse
+exactly the same plans, over all 4096 of them and both `training` values, and name the broken rule's bit."""
 import ctypes as C
 
 import pytest
@@ -77,7 +78,7 @@ def test_other_dtypes_ignore_the_field(L):
                 assert got == want, (dtype, training, plan)
 
 
-def test_generator_raises_the_rules_text():
+def test_generator_raises_the_rules_text(L):
     import real_esrgan_pytorch_amd as R
     for plan, bit in REFUSED:
         with pytest.raises(ValueError, match=rf"\b{bit}\b"):
