@@ -59,6 +59,13 @@ int resr_debug_spectral_norm_bwd_batch(int32_t n, const float* const* g, const f
 int resr_debug_fold4x4_batch(int32_t n, const float* const* dw3, float* const* dw4, const int32_t* cout, const int32_t* c,
                              void* stream);
 
+/* Test entry (tests/test_gpu_pad_skip.py): resr_nchw_to_nhwc with the gradient prescale the generator's backward pass applies to its
+ * incoming gradient.  amax: device pointer to the bits of a float m (what the pass's absmax kernel leaves), or NULL: src is read times
+ * 2^-floor(log2 m) where 2^-126 <= m < 1, times 1 otherwise.  RESR_NO_PAD_SKIP=1 in the environment (read per call) sends every
+ * argument combination to the generic kernel, and the 21 x 21 taps of resr_filter2d through their zero border. */
+int resr_debug_nchw_to_nhwc(const float* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t unshuffle, int32_t c_pad,
+                            int32_t dtype, const uint8_t* mask, const void* amax, void* stream);
+
 /* Test entry (tests/test_gpu_kernels.py) of the compact generator's body pass, which the product reaches only from inside
  * resr_compact_forward*: resr_conv3x3 on one input tensor with a plain epilogue (flags: RESR_CONV_NO_BIAS or 0; NHWC output of one
  * output group) followed by per-output-channel PReLU, v = v > 0 ? v : prelu[co] * v, `prelu` = d->cout floats.  bias may be NULL. */

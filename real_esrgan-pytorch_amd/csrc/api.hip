@@ -522,6 +522,13 @@ int resr_debug_bilinear_up2x_bwd_mask(const void* g, void* gin, const void* mask
     return bilinear_up_bwd_mask_dispatch(g, gin, mask, gmasked, n, h, w, c, dtype, slope, (hipStream_t)stream, 4 * px, px);
 }
 
+// test entry of nchw_to_nhwc with a prescale slot (tests/test_gpu_pad_skip.py): resr_nchw_to_nhwc passes none
+int resr_debug_nchw_to_nhwc(const float* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t unshuffle, int32_t c_pad, int32_t dtype,
+                            const uint8_t* mask, const void* amax, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return nchw_to_nhwc_scaled_dispatch(src, dst, n, c, h, w, unshuffle, c_pad, dtype, mask, (hipStream_t)stream, -1L, (const unsigned*)amax);
+}
+
 // test entry of the compact generator's PReLU pass (tests/test_gpu_kernels.py): the dispatch function compact.hip calls, alone
 int resr_debug_conv3x3_prelu(const ResrConvDesc* d, const void* in0, const void* w_packed, const float* bias, const float* prelu,
                              void* out, void* stream) {

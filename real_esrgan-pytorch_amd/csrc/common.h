@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <type_traits>
@@ -41,6 +42,9 @@ inline size_t act_tensors(int dtype) { return dtype == RESR_F16X2 ? 2 : 1; }
 constexpr float kLoScale = 4096.f, kLoInv = 1.f / 4096.f;
 constexpr int kMaxDevices = 16;   // per-device caches (occupancy, zero pages, CU counts) are indexed by hipGetDevice()
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// RESR_NO_PAD_SKIP in the environment (read per call; A/B arm and test control): the kernels that skip work on padding -- the few-channel
+// nchw_to_nhwc (layout.hip) and the zero border of the 21 x 21 blur taps (degrade.hip) -- give way to the paths that compute on it
+inline bool no_pad_skip() { return getenv("RESR_NO_PAD_SKIP") != nullptr; }
 
 // A runtime upscale factor s in {1, 2, 3, 4} as a compile-time one: f(std::integral_constant<int, s>()); false for any other s.
 template <typename F>

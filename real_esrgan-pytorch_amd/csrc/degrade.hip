@@ -68,42 +68,91 @@ __global__ __launch_bounds__(256) void filter2d_kernel(const float* __restrict__
 
 // 21 x 21 taps (every blur / sinc kernel of the degradation is zero-padded to 21 x 21, dataset.py:101-103): the generic
 // kernel above reads LDS once per FMA and is LDS-bound at ~28 % of the vector rate.  Here a thread owns 8 consecutive
-// outputs of one row of a 64 x 32 tile: per tap row it reads its 28-float window (7 x ds_read_b128) once for 168 FMAs, and the 21
+// outputs of one row of a 64 x 32 tile: per tap row it reads its window (ds_read_b128) once for up to 168 FMAs, and the
 // taps of the row come through the SCALAR cache into SGPRs (they are uniform over the workgroup: one sample's kernel) -- as LDS
 // broadcast reads they were half of the kernel's LDS traffic, and the LDS pipe, not the vector pipe, set its rate.
-// Same accumulation order (dy, then dx) per output as the generic kernel: the results are the same bits.
-__global__ __launch_bounds__(256) void filter2d21_kernel(const float* __restrict__ src, float* __restrict__ dst,
-                                                         const float* __restrict__ kern, int c, int h, int w, int per_sample) {
+// Same accumulation order (dy, then dx) per output as the generic kernel; the rounding of each step: tap_step below.
+// The zero border is skipped: the kernels are drawn at 7 x 7 .. 21 x 21 (mean k^2 = 217 of 441), a fifth of the final sinc kernels
+// are one centre tap.  The workgroup finds the radius r of its sample's non-zero taps (workgroup-uniform), loads the rows and
+// columns r needs and runs dy, dx over R - r .. R + r, the body instantiated per r so that the dx loop stays unrolled and the taps
+// stay scalar.  The skipped terms are +-0 * finite added to an accumulator that starts at +0: the same bits again.  full != 0
+// (RESR_NO_PAD_SKIP) runs r = R without looking.
+// One multiply-add of the 21 x 21 kernel, with the rounding this kernel has had since it was written as `acc += t * w`: the compiler fused
+// 144 of a thread's 168 multiply-adds per tap row and left those of its last two outputs from the tenth tap on as a rounded product plus
+// an add.  Every output of the degradation since -- the pipeline goldens, a training run's LR batches (an ulp here moves JPEG
+// coefficients across a rounding step) -- carries those bits, so they are written out: no instantiation below and no other compiler
+// decides them again.
+__device__ __forceinline__ float tap_step(float acc, float t, float w, int j, int dx) {
+#pragma clang fp contract(off)   // (the product below is rounded on its own: nothing may fuse it into the add)
+    if (j >= 6 && dx >= 9) {
+        const float p = t * w;
+        return acc + p;
+    }
+    return __builtin_fmaf(t, w, acc);
+}
+
+__global__ __launch_bounds__(256) void filter2d21_kernel(const float* __restrict__ src, float* __restrict__ dst, const float* __restrict__ kern, int c, int h, int w, int per_sample, int full) {
     constexpr int K = 21, R = 10, OW = 64, TW = OW + 2 * R, TH = 32 + 2 * R;   // 84 x 52 tile for 64 x 32 outputs
     __shared__ __attribute__((aligned(16))) float tile[TH * TW];
+    __shared__ int wave_r[4];
     const int plane = blockIdx.z;                       // n * c + ch
     const int x0 = blockIdx.x * OW, y0 = blockIdx.y * 32;
     const float* sp = src + (size_t)plane * h * w;
     const float* kp = kern + (per_sample ? (size_t)(plane / c) * K * K : 0);     // workgroup-uniform
-    for (int i = threadIdx.x; i < TW * TH; i += 256) {
-        const int ty = i / TW, tx = i - ty * TW;
-        const int iy = reflect(y0 + ty - R, h), ix = reflect(x0 + tx - R, w);
-        tile[i] = (iy >= 0 && iy < h && ix >= 0 && ix < w) ? sp[(size_t)iy * w + ix] : 0.f;
+    int r = R;
+    if (!full) {
+        r = 0;
+        for (int i = threadIdx.x; i < K * K; i += 256) {
+            const int ky = i / K, kx = i - ky * K;
+            if (kp[i] != 0.f) r = max(r, max(abs(ky - R), abs(kx - R)));   // (a NaN tap counts)
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) r = max(r, __shfl_xor(r, o));
+        if ((threadIdx.x & 63) == 0) wave_r[threadIdx.x >> 6] = r;
+        __syncthreads();
+        r = __builtin_amdgcn_readfirstlane(max(max(wave_r[0], wave_r[1]), max(wave_r[2], wave_r[3])));
     }
-    __syncthreads();
     const int cg = threadIdx.x & 7, row = threadIdx.x >> 3;   // 8 column groups of 8 x 32 rows
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    auto body = [&](auto r_c) {
+        constexpr int RR = decltype(r_c)::value, LW = OW + 2 * RR, LH = 32 + 2 * RR;   // the part of the tile this radius reads
+        for (int i = threadIdx.x; i < LW * LH; i += 256) {
+            const int ty = i / LW + (R - RR), tx = i % LW + (R - RR);
+            const int iy = reflect(y0 + ty - R, h), ix = reflect(x0 + tx - R, w);
+            tile[ty * TW + tx] = (iy >= 0 && iy < h && ix >= 0 && ix < w) ? sp[(size_t)iy * w + ix] : 0.f;
+        }
+        __syncthreads();
+        constexpr int Q0 = (R - RR) / 4, Q1 = (R + RR + 7) / 4;   // the float4s of the 28-float window that hold columns R - RR .. R + RR + 7
 #pragma unroll 1
-    for (int dy = 0; dy < K; ++dy) {
-        float win[28];
-        const float4* wp = reinterpret_cast<const float4*>(tile + (row + dy) * TW + cg * 8);
+        for (int dy = R - RR; dy <= R + RR; ++dy) {
+            float win[28];
+            const float4* wp = reinterpret_cast<const float4*>(tile + (row + dy) * TW + cg * 8);
 #pragma unroll
-        for (int q = 0; q < 7; ++q) {
-            const float4 v = wp[q];
-            win[q * 4] = v.x; win[q * 4 + 1] = v.y; win[q * 4 + 2] = v.z; win[q * 4 + 3] = v.w;
+            for (int q = Q0; q <= Q1; ++q) {
+                const float4 v = wp[q];
+                win[q * 4] = v.x; win[q * 4 + 1] = v.y; win[q * 4 + 2] = v.z; win[q * 4 + 3] = v.w;
+            }
+            const float* tr = kp + dy * K;
+#pragma unroll
+            for (int dx = R - RR; dx <= R + RR; ++dx) {
+                const float t = tr[dx];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) acc[j] = tap_step(acc[j], t, win[j + dx], j, dx);
+            }
         }
-        const float* tr = kp + dy * K;
-#pragma unroll
-        for (int dx = 0; dx < K; ++dx) {
-            const float t = tr[dx];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[j] += t * win[j + dx];
-        }
+    };
+    switch (r) {   // workgroup-uniform
+        case 0: body(std::integral_constant<int, 0>{}); break;
+        case 1: body(std::integral_constant<int, 1>{}); break;
+        case 2: body(std::integral_constant<int, 2>{}); break;
+        case 3: body(std::integral_constant<int, 3>{}); break;
+        case 4: body(std::integral_constant<int, 4>{}); break;
+        case 5: body(std::integral_constant<int, 5>{}); break;
+        case 6: body(std::integral_constant<int, 6>{}); break;
+        case 7: body(std::integral_constant<int, 7>{}); break;
+        case 8: body(std::integral_constant<int, 8>{}); break;
+        case 9: body(std::integral_constant<int, 9>{}); break;
+        default: body(std::integral_constant<int, 10>{}); break;
     }
     const int y = y0 + row;
     if (y < h) {
@@ -176,7 +225,7 @@ int filter2d_dispatch(const float* src, float* dst, const float* kern, int n, in
     static const char* generic_env = getenv("RESR_FILTER_GENERIC");   // test knob: every size on the generic kernel
     if (kh == 21 && kw == 21 && !generic_env) {
         hipLaunchKernelGGL(filter2d21_kernel, dim3((w + 63) / 64, (h + 31) / 32, n * c), dim3(256), 0, st, src, dst, kern, c, h, w,
-                           per_sample);
+                           per_sample, no_pad_skip() ? 1 : 0);
         RESR_CHECK_LAUNCH("filter2d21_kernel");
         return RESR_OK;
     }

@@ -81,6 +81,43 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
     }
 }
 
+// r = 1, c <= 8, f16 (no lo / q tensor): the 3-channel ends of the generator (the LR input, the output gradient).  All real channels
+// lie in piece 0 of a pixel's record, so in the kernel above only every (c_pad / 8)-th lane loads, a quarter-filled instruction per
+// channel and mask byte.  Here a wave owns 64 consecutive pixels of one image (the planes are contiguous over h * w, so rows may end
+// inside a wave).  Loads run with lane = pixel: 64 consecutive floats per channel plane, 64 consecutive mask bytes.  Stores run with
+// lane = 16-byte piece of the wave's contiguous 64 * c_pad * 2 bytes, 1 KB per instruction; piece 0 of a pixel comes from the lane
+// that loaded it (ds_bpermute), the other pieces are zero.  Same conversions in the same order: the same bits as the kernel above.
+__global__ __launch_bounds__(256) void nchw_to_nhwc_few_kernel(const float* __restrict__ src, half_t* __restrict__ dst, int n, int c, long hw, int c_pad, const uint8_t* __restrict__ mask, const unsigned* __restrict__ amax) {
+    const int pieces = c_pad / 8, lane = (int)(threadIdx.x & 63u);
+    const long p0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 64;   // the wave's first pixel (wave-uniform)
+    if (p0 >= hw) return;
+    const long p = p0 + lane;
+    const float pre = amax ? grad_prescale(*amax, false) : 1.f;   // (exact: a power of two)
+    for (int b = (int)blockIdx.y; b < n; b += (int)gridDim.y) {
+        half8 o;
+#pragma unroll
+        for (int ch = 0; ch < 8; ++ch) {
+            float v = 0.f;
+            if (ch < c && p < hw) {
+                const size_t q = ((size_t)b * c + ch) * (size_t)hw + (size_t)p;
+                v = src[q] * pre;
+                if (mask) v = mask[q] ? v : 0.f;
+            }
+            o[ch] = (half_t)v;
+        }
+        const uint4 rec = __builtin_bit_cast(uint4, o);
+        uint4* out = reinterpret_cast<uint4*>(dst + ((size_t)b * (size_t)hw + (size_t)p0) * c_pad);
+        for (int k = 0; k < pieces; ++k) {   // (no lane leaves before the last shuffle)
+            const int u = k * 64 + lane, px = u / pieces, piece = u - px * pieces;
+            uint4 v;
+            v.x = (unsigned)__shfl((int)rec.x, px); v.y = (unsigned)__shfl((int)rec.y, px);
+            v.z = (unsigned)__shfl((int)rec.z, px); v.w = (unsigned)__shfl((int)rec.w, px);
+            if (piece) v = make_uint4(0u, 0u, 0u, 0u);
+            if (p0 + px < hw) out[u] = v;
+        }
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T* __restrict__ src, float* __restrict__ dst,
                                                            int n, int c, int h, int w, int r, int src_stride, long lo_off, int wsh,
@@ -287,6 +324,13 @@ int nchw_to_nhwc_q_dispatch(const float* src, void* dst, int n, int c, int h, in
     if (q_off != 0 && (dtype != RESR_F16X2 || (c_pad & 31))) return fail(RESR_ERR_ARG, "nchw_to_nhwc: a q tensor goes with RESR_F16X2 and c_pad %% 32 == 0");
     if (!src || !dst || n <= 0 || c <= 0 || h <= 0 || w <= 0 || r <= 0 || (h % r) || (w % r) || c * r * r > c_pad || (c_pad & 7))
         return fail(RESR_ERR_ARG, "nchw_to_nhwc: bad argument (c=%d r=%d c_pad=%d h=%d w=%d)", c, r, c_pad, h, w);
+    if (r == 1 && c <= 8 && dtype == RESR_F16 && q_off == 0 && !no_pad_skip()) {
+        const long hw = (long)h * w;
+        if ((hw + 255) / 256 > 0x7fffffffL) return fail(RESR_ERR_ARG, "nchw_to_nhwc: image beyond 2^39 pixels");
+        hipLaunchKernelGGL(nchw_to_nhwc_few_kernel, dim3((unsigned)((hw + 255) / 256), (unsigned)(n > 65535 ? 65535 : n)), dim3(256), 0, stream, src, (half_t*)dst, n, c, hw, c_pad, mask, amax);
+        RESR_CHECK_LAUNCH("nchw_to_nhwc_few_kernel");
+        return RESR_OK;
+    }
     const dim3 grid(blocks_for((long)(w / r) * (c_pad / (dtype != RESR_F32 ? 8 : 4))), (unsigned)(h / r > 65535 ? 65535 : h / r), (unsigned)(n > 65535 ? 65535 : n));
     if (dtype == RESR_F16X2 && lo_off < 0) lo_off = (long)n * (h / r) * (w / r) * c_pad;
     if (dtype != RESR_F16X2) lo_off = 0;
