@@ -235,6 +235,19 @@ int resr_pack_weights(const ResrPackChunk* chunks_dev, int32_t n_chunks, const f
  * f16(w 2^12), W1 = f16(w 2^12 - W0), W2 = f16(W0 2^-12)), in the A-fragment order of v_mfma_scale_f32_32x32x64_f8f6f4 (lane (row,
  * half h): K = 16 h .. 16 h + 15 of either block). */
 int resr_pack_weights_mx(const ResrPackChunk* chunks_dev, int32_t n_chunks, const float* arena, void* packed_mx, void* stream);
+/* Host helpers (no GPU needed) for a caller that packs convolutions of its own; the format itself is stated once, in csrc/packed_layout.h.
+ * resr_conv_pack_table: the chunk table of ONE OIHW 3x3 convolution [cout][cin][3][3] at arena element offset src_off, in the forward
+ *   (transposed = 0) or the backward-data orientation (1), packed from element dst_off on: output rows in groups of at most 64, each
+ *   group holding its 32-channel input chunks.  A group starts at each chunk with k_off == 0; its dst_off and mt are what a launch of
+ *   that group takes.  Returns the chunk count (`chunks` may be NULL to ask for it) or RESR_ERR_ARG.
+ * resr_conv_packed_elems: the elements that table takes in the packed buffer (the same in both orientations): the next table's dst_off.
+ * resr_packed_bytes: bytes of a packed buffer of `elems` elements of the plain layout in `dtype`, the slack the kernels' prefetch needs
+ *   included.  resr_packed_mx_offset: byte offset of the MX region (resr_pack_weights_mx) behind an RESR_F16X2 packing of `elems`. */
+int64_t resr_conv_pack_table(int32_t cout, int32_t cin, int32_t transposed, int64_t src_off, int64_t dst_off, float scale,
+                             ResrPackChunk* chunks, int64_t capacity);
+int64_t resr_conv_packed_elems(int32_t cout, int32_t cin);
+size_t resr_packed_bytes(int64_t elems, int32_t dtype);
+size_t resr_packed_mx_offset(int64_t elems);
 
 /* Layout helpers around the generator (model.py:257 PixelUnshuffle, NCHW fp32 module surface). */
 int resr_nchw_to_nhwc(const float* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w,

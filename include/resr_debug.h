@@ -30,7 +30,7 @@ int resr_debug_wgrad_plan(const int32_t* cin, const int32_t* cout_pad, int32_t n
  * convolutions of `nblocks` (1..3) dense blocks, 26 products each, as ONE batched launch -- on caller-made f16 operands.
  * x_ws[b]: chunk-planar [6][n,h,w,32] (conv_k reads the first 2 + (k - 1) planes); g_ws[b]: chunk-planar [6][n,h,w,32] (planes
  * 0,1 = the closing convolution's 64 gradient channels, plane 1 + k = conv_k's 32); dw: nblocks * 26624 * 9 floats;
- * partial: `partial_bytes` of slab scratch (26 * nblocks * splits * (9 * 1024 + 32) floats). */
+ * partial: `partial_bytes` of slab scratch (26 * nblocks * splits slabs of kSlab floats: csrc/wgrad.h, wgrad_slab_bytes). */
 int resr_debug_wgrad_dense_blocks(int32_t nblocks, const void* const* x_ws, const void* const* g_ws, int32_t n, int32_t h, int32_t w,
                                   int32_t splits, float* partial, size_t partial_bytes, float* dw, void* stream);
 /* test probe: lane/element map of ds_read_b64_tr_b16 (256 floats out) */

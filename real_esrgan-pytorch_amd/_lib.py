@@ -29,7 +29,6 @@ _PROTOS = _ABI.protos   # name -> (restype, [argtypes]) of every function the tw
 # the named "output parity" training plan: bits 0 + 5 + 6 (the inference MX forward) + 8 (f16 backward) + 11 (MX_TRAIN_FORWARD)
 X2_PLAN_OUTPUT_PARITY = (X2_PLAN_GROWTH_F16_INFER | X2_PLAN_GROWTH_W16_INFER | X2_PLAN_MX_INFER | X2_PLAN_F16_BACKWARD
                          | X2_PLAN_MX_TRAIN_FORWARD)   # 2401
-PACKED_SLACK = 16384   # bytes added behind a packed weight buffer a caller sizes itself, as resr_*_packed_bytes add them natively
 
 
 def x2_plan_error(plan: int):
@@ -55,11 +54,6 @@ def x2_plan_layout_key(plan: int) -> int:
     return plan & (X2_PLAN_MX_INFER | X2_PLAN_MX_BWD | X2_PLAN_MX_WGRAD | X2_PLAN_MX_TAIL | X2_PLAN_MX_TRAIN_FORWARD)
 
 
-def packed_elem_bytes(dtype: int) -> int:
-    """Bytes per packed weight element: f16, f32, or exact16's three f16 blocks (W0, W1, W2)."""
-    return {RESR_F16: 2, RESR_F32: 4, RESR_F16X2: 6}[dtype]
-
-
 def fetch_pack_table(call, what: str):
     """A native pack table as a host `PackChunk` array.  `call(chunks, capacity)` is the table function with its leading arguments
     bound: asked with (None, 0) for its length, then with an array of that length."""
@@ -71,6 +65,14 @@ def fetch_pack_table(call, what: str):
     if got != n:
         check(got if got < 0 else -1, what)
     return host
+
+
+def conv_pack_table(cout: int, cin: int, transposed: int = 0, src_off: int = 0, dst_off: int = 0, scale: float = 1.0):
+    """The library's chunk table of one OIHW 3x3 convolution in one orientation (resr_conv_pack_table: the packed format is the
+    library's alone, csrc/packed_layout.h) and the packed elements it takes from `dst_off` on."""
+    host = fetch_pack_table(lambda chunks, n: lib().resr_conv_pack_table(cout, cin, transposed, src_off, dst_off, scale, chunks, n),
+                            "resr_conv_pack_table")
+    return host, int(lib().resr_conv_packed_elems(cout, cin))
 
 
 def upload_chunks(chunks, device):

@@ -127,42 +127,42 @@ class ContentLoss(nn.Module):
         self._packed_f16 = None                   # f16_backward: the f16 packing of the same weights (same table, plain layout)
 
     # ---- weights ---------------------------------------------------------------------------------------------
-    def _pack(self, device):
-        """Pack all 16 convs once (frozen weights): the forward form per conv -- cout groups of 64, K chunks of 32 -- and the
-        backward-data form (M = cin groups of 64, K = cout chunks, taps flipped).  f16_backward: the same table once more in
-        RESR_F16 (the table counts elements of the plain layout, so the group offsets serve both buffers)."""
-        if self._packed is not None and self._packed[0].device == device and (self._packed_f16 is not None or not self.f16_backward):
-            return
+    def _table(self):
+        """Host only: the chunk table of all 16 convs -- per conv the forward form, then the backward-data form (M = cin, K = cout,
+        taps flipped), each the library's (resr_conv_pack_table) -- as (chunks, forward groups, backward groups, packed elements).
+        groups: conv index -> the (element offset, mt) of each launch group of 64 output channels: a group starts at every chunk
+        with k_off == 0.  The table counts elements of the plain layout, so the offsets serve a packing in any dtype."""
         L = _lib
-        flat = torch.cat([getattr(self.features, str(l[1])).weight.detach().float().reshape(-1) for l in self.layers if l[0] == "conv"]).to(device)
         chunks, fwd, bwd, off, src = [], {}, {}, 0, 0
         for l in self.layers:
             if l[0] != "conv":
                 continue
             _, idx, cin, cout = l
-            for table, m_real, k_real, tr in ((fwd, cout, cin, 0), (bwd, cin, cout, 1)):
-                gl = []
-                for g0 in range(0, _r32(m_real), 64):
-                    mt = min(64, _r32(m_real) - g0) // 32
-                    gl.append((off, mt))
-                    for ck in range(_r32(k_real) // 32):
-                        chunks.append(L.PackChunk(src, off, cout, cin, g0, max(0, min(64, m_real - g0)), ck * 32,
-                                                  max(0, min(32, k_real - ck * 32)), mt, tr, 1.0, 0, None))
-                        off += 9 * mt * 1024
-                table[idx] = gl
+            for groups, tr in ((fwd, 0), (bwd, 1)):
+                part, elems = L.conv_pack_table(cout, cin, tr, src, off)
+                groups[idx] = [(c.dst_off, c.mt) for c in part if c.k_off == 0]
+                chunks.extend(part)
+                off += elems
             src += cout * cin * 9
-        host = (L.PackChunk * len(chunks))(*chunks)
+        return (L.PackChunk * len(chunks))(*chunks), fwd, bwd, off
+
+    def _pack(self, device):
+        """Pack all 16 convs once (frozen weights).  f16_backward: the same table once more in RESR_F16."""
+        if self._packed is not None and self._packed[0].device == device and (self._packed_f16 is not None or not self.f16_backward):
+            return
+        L = _lib
+        flat = torch.cat([getattr(self.features, str(l[1])).weight.detach().float().reshape(-1) for l in self.layers if l[0] == "conv"]).to(device)
+        host, fwd, bwd, elems = self._table()
         table = L.upload_chunks(host, device)
-        self._wes = L.packed_elem_bytes(self._dtype)
-        packed = torch.zeros(off * self._wes + L.PACKED_SLACK, dtype=torch.uint8, device=device)
-        L.check(L.lib().resr_pack_weights(L.ptr(table), len(chunks), L.ptr(flat), L.ptr(packed), self._dtype, L.stream_ptr(flat)),
-                "resr_pack_weights")
-        self._packed_f16 = None
-        if self.f16_backward:
-            self._packed_f16 = torch.zeros(off * L.packed_elem_bytes(L.RESR_F16) + L.PACKED_SLACK, dtype=torch.uint8, device=device)
-            L.check(L.lib().resr_pack_weights(L.ptr(table), len(chunks), L.ptr(flat), L.ptr(self._packed_f16), L.RESR_F16,
-                                              L.stream_ptr(flat)), "resr_pack_weights (f16 backward)")
-        self._packed = (packed, fwd, bwd)
+
+        def pack(dtype, what):
+            packed = torch.zeros(L.lib().resr_packed_bytes(elems, dtype), dtype=torch.uint8, device=device)
+            L.check(L.lib().resr_pack_weights(L.ptr(table), len(host), L.ptr(flat), L.ptr(packed), dtype, L.stream_ptr(flat)), what)
+            return packed
+        # bytes per element of the packed layout, as the library sizes it
+        self._wes = L.lib().resr_packed_bytes(1, self._dtype) - L.lib().resr_packed_bytes(0, self._dtype)
+        self._packed_f16 = pack(L.RESR_F16, "resr_pack_weights (f16 backward)") if self.f16_backward else None
+        self._packed = (pack(self._dtype, "resr_pack_weights"), fwd, bwd)
 
     def load_state_dict(self, state_dict, strict: bool = True):
         self._packed = self._packed_f16 = None

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "host_api.h"
+#include "packed_layout.h"
 
 namespace resr {
 
@@ -136,6 +137,17 @@ int resr_pack_weights_mx(const ResrPackChunk* chunks_dev, int32_t n_chunks, cons
     RESR_DEVICE_SCOPE(stream);
     return pack_mx_dispatch(chunks_dev, n_chunks, arena, packed_mx, (hipStream_t)stream);
 }
+
+int64_t resr_conv_pack_table(int32_t cout, int32_t cin, int32_t transposed, int64_t src_off, int64_t dst_off, float scale, ResrPackChunk* chunks,
+                             int64_t capacity) {
+    if (cout <= 0 || cin <= 0 || (transposed != 0 && transposed != 1)) return fail(RESR_ERR_ARG, "conv_pack_table: cout=%d cin=%d transposed=%d", cout, cin, transposed);
+    std::vector<ResrPackChunk> t;
+    emit_conv_chunks(t, src_off, cout, cin, transposed, dst_off, scale);
+    return copy_pack_table(t, chunks, capacity, "conv_pack_table");
+}
+int64_t resr_conv_packed_elems(int32_t cout, int32_t cin) { return cout > 0 && cin > 0 ? (int64_t)packed_conv_elems(round32(cout), round32(cin)) : 0; }
+size_t resr_packed_bytes(int64_t elems, int32_t dtype) { return packed_buffer_bytes((size_t)elems, dtype); }
+size_t resr_packed_mx_offset(int64_t elems) { return packed_mx_offset((size_t)elems); }
 
 int resr_nchw_to_nhwc(const float* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t unshuffle,
                       int32_t c_pad, int32_t dtype, const uint8_t* mask, void* stream) {

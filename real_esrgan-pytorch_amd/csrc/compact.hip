@@ -19,7 +19,8 @@
 //                     only the resized frame, uint8 [N,oh,ow,3] or YUV 4:2:0 [N,3oh/2,ow], is written.
 #include <vector>
 
-#include "host_api.h"
+#include "conv3x3.h"
+#include "packed_layout.h"
 #include "yuv.h"
 
 namespace resr {
@@ -55,7 +56,7 @@ bool build_cplan(const ResrCompactDesc* d, CPlan& p) {
     size_t off = 0;
     auto add = [&](int cin, int cout, bool act) {
         CConv c;
-        c.cin = cin; c.cin_pad = (cin + 31) / 32 * 32; c.cout = cout; c.cout_pad = (cout + 31) / 32 * 32;
+        c.cin = cin; c.cin_pad = round32(cin); c.cout = cout; c.cout_pad = round32(cout);
         c.w_off = off; off += (size_t)cout * cin * 9;
         c.b_off = off; off += cout;
         c.a_off = -1;
@@ -70,7 +71,7 @@ bool build_cplan(const ResrCompactDesc* d, CPlan& p) {
     size_t pk = 0;
     for (auto& c : p.convs) {
         c.pk = pk;
-        pk += (size_t)(c.cin_pad / 32) * 9 * (c.cout_pad / 32) * 1024;
+        pk += packed_conv_elems(c.cout_pad, c.cin_pad);
     }
     p.pk_elems = pk;
     const size_t es = elem_size(d->dtype) * act_tensors(d->dtype);
@@ -128,9 +129,7 @@ size_t compact_param_count(const ResrCompactDesc* d) {
 
 size_t compact_packed_bytes(const ResrCompactDesc* d) {
     CPlan p;
-    if (!build_cplan(d, p)) return 0;
-    // + slack: the one-role kernel prefetches two (chunk, tap) blocks past the end
-    return p.pk_elems * elem_size(d->dtype) * (d->dtype == RESR_F16X2 ? 3 : 1) + 16384;
+    return build_cplan(d, p) ? packed_buffer_bytes(p.pk_elems, d->dtype) : 0;
 }
 
 size_t compact_workspace_bytes(const ResrCompactDesc* d) {
@@ -142,24 +141,8 @@ int64_t compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t
     CPlan p;
     if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "compact: bad descriptor");
     std::vector<ResrPackChunk> t;
-    for (const auto& c : p.convs) {
-        const int mt = c.cout_pad / 32;
-        for (int ck = 0; ck < c.cin_pad / 32; ++ck) {
-            ResrPackChunk ch;
-            memset(&ch, 0, sizeof(ch));
-            const int kc = c.cin - ck * 32;
-            ch.src_off = (int64_t)c.w_off; ch.dst_off = (int64_t)(c.pk + (size_t)ck * 9 * mt * 1024);
-            ch.src_cout = c.cout; ch.src_cin = c.cin;
-            ch.m_off = 0; ch.m_count = c.cout; ch.k_off = ck * 32; ch.k_count = kc > 32 ? 32 : kc;
-            ch.mt = mt; ch.transposed = 0; ch.scale = 1.f;
-            t.push_back(ch);
-        }
-    }
-    if (out) {
-        if ((int64_t)t.size() > cap) return fail(RESR_ERR_ARG, "compact_pack_table: capacity %lld < %zu", (long long)cap, t.size());
-        memcpy(out, t.data(), t.size() * sizeof(ResrPackChunk));
-    }
-    return (int64_t)t.size();
+    for (const auto& c : p.convs) emit_conv_chunks(t, (int64_t)c.w_off, c.cout, c.cin, 0, (int64_t)c.pk);
+    return copy_pack_table(t, out, cap, "compact_pack_table");
 }
 
 namespace {
@@ -194,7 +177,7 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
     int rc = check_ends(p, e, params, packed, workspace, workspace_bytes, who, &geom);
     if (rc) return rc;
     const bool x2 = d->dtype == RESR_F16X2;
-    const size_t wes = elem_size(d->dtype) * (x2 ? 3 : 1);   // bytes per element of the packed layout
+    const size_t wes = packed_elem_bytes(d->dtype);   // bytes per element of the packed layout
     const char* pk = (const char*)packed;
     char* base = (char*)workspace;
     char* xin = base + p.off_xin;
@@ -206,15 +189,10 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
     else rc = frame_head_dispatch(e.x, xin, N, H, W, d->dtype, st, (long)lo32, e.src);   // src null: RGB bytes; its layout: bytes or 16-bit words
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) {
-        ResrConvDesc cd;
-        memset(&cd, 0, sizeof(cd));
-        cd.n = N; cd.h = H; cd.w = W;
+        ResrConvDesc cd = conv_desc_base(N, H, W, d->dtype, flags, d->act == RESR_COMPACT_LRELU ? 0.1f : 0.f);
         cd.cin = cd.cin0 = cd.in0_stride = c.cin_pad;
         cd.cout = c.cout; cd.cout_pad = c.cout_pad;
         cd.out_stride = (flags & RESR_CONV_OUT_NCHW_F32) ? 0 : c.cout_pad;
-        cd.dtype = d->dtype; cd.flags = flags;
-        cd.s0 = cd.s1 = cd.t0 = cd.t1 = 1.f;
-        cd.slope = d->act == RESR_COMPACT_LRELU ? 0.1f : 0.f;
         cd.in0_lo_offset = c.cin_pad == 32 ? lo32 : lo64;
         cd.out_lo_offset = (flags & RESR_CONV_OUT_NCHW_F32) ? 0 : lo64;
         return cd;

@@ -124,6 +124,16 @@ int conv3x3_ws_chain_launch(const ConvArgs& a, const ChainArgs& cj, int tile_row
 int conv3x3_ws_chain_launch_x2(const ConvArgs& a, const ChainArgs& cj, int tile_rows, int kind, double flop, double bytes, hipStream_t stream);
 int conv3x3_ws_chain_launch_mx(const ConvArgs& a, const ChainArgs& cj, int tile_rows, int kind, double flop, double bytes, hipStream_t stream);
 
+// The base of every descriptor the planners fill (generator.hip, disc_native.hip, compact.hip): all zero but the geometry, the arithmetic,
+// the flags, the activation slope and unit residual scales (s0 = t0 = s1 = t1 = 1); the planner sets its channels, strides and offsets on top.
+inline ResrConvDesc conv_desc_base(int n, int h, int w, int dtype, int flags, float slope) {
+    ResrConvDesc c;
+    memset(&c, 0, sizeof(c));
+    c.n = n; c.h = h; c.w = w; c.dtype = dtype; c.flags = flags;
+    c.s0 = c.t0 = c.s1 = c.t1 = 1.f; c.slope = slope;
+    return c;
+}
+
 // Algorithmic HBM bytes of one pass: input channels + output (+ mask, residuals, aux) once per pixel.
 // (es = 4 for RESR_F16X2 pairs: single f16 chunks / a single f16 output count 2 bytes per element)
 inline double conv_algorithmic_bytes(const ConvArgs& a, size_t es) {

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "conv3x3.h"
+#include "packed_layout.h"
 
 namespace resr {
 
@@ -385,7 +386,7 @@ static int conv3x3_args(const ResrConvDesc* d, const void* in0, const void* in1,
             (d->flags & (RESR_CONV_OUT_NCHW_F32 | RESR_CONV_WRITE_SIGNBITS | RESR_CONV_MASK_BITS | RESR_CONV_CLAMP01)))
             return fail(RESR_ERR_ARG, "conv3x3: cout_groups > 1 needs f16 / f16x2, cout = cout_pad = 64 per group, NHWC output, no sign-bit tensors, and at most %d groups with a bias", kMaxBiasGroups);
         a.ngroups = groups;
-        a.w_group_b = (size_t)(d->cin / 32) * 9 * 2 * 1024 * es * (d->dtype == RESR_F16X2 ? 3 : 1);
+        a.w_group_b = packed_group_elems(d->cin, 2) * packed_elem_bytes(d->dtype);
     }
     if (d->s2d_in_channels > 0) {
         if ((d->s2d_in_channels & 31) || d->cin != 4 * d->s2d_in_channels)

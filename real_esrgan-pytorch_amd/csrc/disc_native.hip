@@ -18,7 +18,8 @@
 // stage of the conv kernel (16 of 36 tap blocks), all 64-channel output groups of a layer in one launch (f16).
 #include <vector>
 
-#include "host_api.h"
+#include "conv3x3.h"
+#include "packed_layout.h"
 
 namespace resr {
 
@@ -30,8 +31,6 @@ const Layer kL[kLayers] = {{3, 64, 0, 0, 1},    {64, 128, 1, 1, 0},  {128, 256, 
                            {256, 128, 0, 1, 0}, {128, 64, 0, 1, 0},  {64, 64, 0, 1, 0},   {64, 64, 0, 1, 0},   {64, 1, 0, 0, 1}};
 enum { CONV1 = 0, DOWN1, DOWN2, DOWN3, UP1, UP2, UP3, CONV2, CONV3, CONV4 };
 constexpr float kSlope = 0.2f;
-
-int r32(int v) { return (v + 31) / 32 * 32; }
 
 struct DPlan {
     ResrDiscriminatorDesc d;
@@ -56,21 +55,16 @@ bool build(const ResrDiscriminatorDesc* d, DPlan& p) {
         p.u_off[i] = uv; if (l.sn) uv += l.cout;
         p.v_off[i] = uv; if (l.sn) uv += (size_t)l.cin * kk;
         p.cin_v[i] = l.k4 ? 4 * l.cin : l.cin;
-        p.cin_pad[i] = r32(p.cin_v[i]);
-        p.cout_pad[i] = r32(l.cout);
+        p.cin_pad[i] = round32(p.cin_v[i]);
+        p.cout_pad[i] = round32(l.cout);
     }
     p.n_params = off; p.n_uv = uv;
     for (int i = 0; i < kLayers; ++i) {   // forward groups of a layer, then its backward-data groups (as pack_table emits them)
         p.pk_fwd[i] = pk;
-        for (int g0 = 0; g0 < p.cout_pad[i]; g0 += 64) {
-            const int mt = (p.cout_pad[i] - g0 < 64 ? p.cout_pad[i] - g0 : 64) / 32;
-            pk += (size_t)(p.cin_pad[i] / 32) * 9 * mt * 1024; nch += p.cin_pad[i] / 32;
-        }
+        pk += packed_conv_elems(p.cout_pad[i], p.cin_pad[i]);
         p.pk_bwd[i] = pk;
-        for (int g0 = 0; g0 < p.cin_pad[i]; g0 += 64) {
-            const int mt = (p.cin_pad[i] - g0 < 64 ? p.cin_pad[i] - g0 : 64) / 32;
-            pk += (size_t)(p.cout_pad[i] / 32) * 9 * mt * 1024; nch += p.cout_pad[i] / 32;
-        }
+        pk += packed_conv_elems(p.cin_pad[i], p.cout_pad[i]);
+        nch += packed_conv_chunks(p.cout_pad[i], p.cin_pad[i]) + packed_conv_chunks(p.cin_pad[i], p.cout_pad[i]);
     }
     p.pk_elems = pk; p.n_chunks = nch;
     return true;
@@ -93,16 +87,6 @@ struct DBufs {
                                 // run as three batched launches at the end of the pass
     size_t partial_bytes, total;
 };
-
-int wsplits(int dtype, int jobs, int n, int h, int w) {
-    const int th = wgrad_tile_rows(dtype);
-    const long tiles = (long)((w + 31) / 32) * ((h + th - 1) / th) * n;
-    long s;
-    if (dtype != RESR_F32) { s = 512 / ((jobs + 3) / 4); if (s >= 16) s &= ~7L; if (s > 256) s = 256; }
-    else { s = 768 / jobs; if (s > 128) s = 128; }
-    if (s > tiles / 2) s = tiles / 2;
-    return (int)(s < 1 ? 1 : s);
-}
 
 // Layers with more products than a launch's job table holds (>= 96: the 256..512-channel layers) run their weight gradients as ONE
 // layer-mode launch pair (wgrad.hip, WgradLayer): one residency round of workgroups -- 256 / quad jobs pixel splits -- instead of
@@ -137,7 +121,7 @@ void carve(const DPlan& p, char* base, DBufs& b) {
     b.sigma = (float*)take(kLayers * 2 * sizeof(float));   // (64 of the slot's 256 bytes)
     b.gscale = base ? reinterpret_cast<unsigned*>(base + 128) : nullptr;   // the gradient pre-scale slot (common.h): inside the head the caller zero-fills once
     b.uv = (float*)take(p.n_uv * sizeof(float));
-    b.packed = take(p.pk_elems * elem_size(p.d.dtype) * (p.d.dtype == RESR_F16X2 ? 3 : 1) + 16384);
+    b.packed = take(packed_buffer_bytes(p.pk_elems, p.d.dtype));
     {   // spectral-norm scratch of every normalised layer (all layers iterate in the same four launches): rows + ceil(rows / 32) * cols floats each
         size_t fl = 0;
         for (int i = 0; i < kLayers; ++i)
@@ -173,12 +157,12 @@ void carve(const DPlan& p, char* base, DBufs& b) {
             b.raw_l[li] = (float*)take((size_t)kL[li].cout * p.cin_v[li] * 9 * sizeof(float));
             if (kL[li].k4) b.fold_l[li] = (float*)take((size_t)kL[li].cout * kL[li].cin * 16 * sizeof(float));
         }
-        // weight-gradient slabs: the largest launch is <= 80 products (wgrad.hip kMaxJobs) x its splits
+        // weight-gradient slabs (wgrad.h): the largest launch is <= 80 products (wgrad.hip kMaxJobs) x its splits
         size_t pb = 0;
         const int res[4][2] = {{p.d.h, p.d.w}, {p.d.h / 2, p.d.w / 2}, {p.d.h / 4, p.d.w / 4}, {p.d.h / 8, p.d.w / 8}};
         for (int q = 0; q < 4; ++q)
             for (int jobs = 1; jobs <= 96; ++jobs) {
-                const size_t v = (size_t)jobs * wsplits(p.d.dtype, jobs, p.d.n, res[q][0], res[q][1]) * (9 * 1024 + 32) * sizeof(float);
+                const size_t v = wgrad_slab_bytes(jobs, wgrad_default_splits(p.d.dtype, jobs, p.d.n, res[q][0], res[q][1]));
                 if (v > pb) pb = v;
             }
         if (p.d.dtype == RESR_F16 || p.d.dtype == RESR_F16X2)   // layer-mode launches (one per 256..512-channel layer)
@@ -188,7 +172,7 @@ void carve(const DPlan& p, char* base, DBufs& b) {
                 const int q = li == DOWN1 || li == UP2 ? 1 : li == DOWN2 || li == UP1 ? 2 : li == DOWN3 ? 3 : 0;
                 // exact16: one or three tap-products per product ($RESR_X2_WGRAD_PRODUCTS is read per call) -- room for either
                 for (int parts = 1; parts <= (p.d.dtype == RESR_F16X2 ? 3 : 1); parts += 2) {
-                    const size_t v = (size_t)products * parts * layer_splits(products, p.d.n, res[q][0], res[q][1], parts) * (9 * 1024 + 32) * sizeof(float);
+                    const size_t v = wgrad_slab_bytes(products * parts, layer_splits(products, p.d.n, res[q][0], res[q][1], parts));
                     if (v > pb) pb = v;
                 }
             }
@@ -202,11 +186,9 @@ void carve(const DPlan& p, char* base, DBufs& b) {
 }
 
 ResrConvDesc cdesc(const DPlan& p, int n, int h, int w, int cin_pad, int in_stride, int cout, int cout_pad, int out_stride, int flags) {
-    ResrConvDesc c;
-    memset(&c, 0, sizeof(c));
-    c.n = n; c.h = h; c.w = w; c.cin = cin_pad; c.cin0 = cin_pad; c.in0_stride = in_stride;
-    c.cout = cout; c.cout_pad = cout_pad; c.out_stride = out_stride; c.dtype = p.d.dtype; c.flags = flags;
-    c.s0 = c.t0 = c.s1 = c.t1 = 1.f; c.slope = kSlope;
+    ResrConvDesc c = conv_desc_base(n, h, w, p.d.dtype, flags, kSlope);
+    c.cin = cin_pad; c.cin0 = cin_pad; c.in0_stride = in_stride;
+    c.cout = cout; c.cout_pad = cout_pad; c.out_stride = out_stride;
     return c;
 }
 
@@ -220,13 +202,13 @@ int conv_layer(const DPlan& p, const DBufs& b, int li, bool backward, const char
                int out_stride, int flags, const float* bias, const char* res0, int res0_stride, const char* mask, int mask_stride,
                char* aux, int s2d_in, int s2d_out, hipStream_t st, long lo_x, long lo_out, long lo_res0, float* out_nchw = nullptr) {
     const size_t es = elem_size(p.d.dtype);
-    const size_t wes = es * (p.d.dtype == RESR_F16X2 ? 3 : 1);   // bytes per element of the plain packed layout
+    const size_t wes = packed_elem_bytes(p.d.dtype);   // bytes per element of the plain packed layout
     const int kin = backward ? p.cout_pad[li] : p.cin_pad[li];                  // K channels read
     const int mtot = backward ? p.cin_pad[li] : p.cout_pad[li];                 // M channels written (padded)
     const bool nchw = flags & RESR_CONV_OUT_NCHW_F32;
     // NHWC outputs are written in whole 32-channel chunks (packed rows beyond the real count are zero); the planar fp32
     // output of conv4 holds the real channels only
-    const int mreal = nchw ? kL[li].cout : r32(backward ? p.cin_v[li] : kL[li].cout);
+    const int mreal = nchw ? kL[li].cout : round32(backward ? p.cin_v[li] : kL[li].cout);
     const size_t pk0 = backward ? p.pk_bwd[li] : p.pk_fwd[li];
     const int ngroups = (mtot + 63) / 64;
     if (ngroups > 1 && p.d.dtype != RESR_F32 && mreal == 64 * ngroups && !bias && !nchw && (flags & RESR_CONV_NO_BIAS)) {
@@ -239,7 +221,7 @@ int conv_layer(const DPlan& p, const DBufs& b, int li, bool backward, const char
     }
     size_t pk = pk0;
     for (int g0 = 0; g0 < mtot; g0 += 64) {
-        const int mt = (mtot - g0 < 64 ? mtot - g0 : 64) / 32;
+        const int mt = packed_group_mt(mtot, g0);
         int co = mreal - g0; if (co > mt * 32) co = mt * 32;
         if (co > 0) {
             ResrConvDesc c = cdesc(p, n, h, w, kin, in_stride, co, mt * 32, nchw ? 0 : out_stride, flags);
@@ -251,7 +233,7 @@ int conv_layer(const DPlan& p, const DBufs& b, int li, bool backward, const char
             DRUN(conv3x3_dispatch(&c, x, nullptr, b.packed + pk * wes, bias ? bias + g0 : nullptr, sh(res0), nullptr, sh(mask),
                                   nchw ? (void*)out_nchw : (void*)(out + (size_t)g0 * es), aux ? aux + (size_t)g0 * es : nullptr, st));
         }
-        pk += (size_t)(kin / 32) * 9 * mt * 1024;
+        pk += packed_group_elems(kin, mt);
     }
     return RESR_OK;
 }
@@ -275,34 +257,17 @@ int64_t discriminator_pack_table(const ResrDiscriminatorDesc* d, const void* wor
     DPlan p;
     if (!build(d, p)) return fail(RESR_ERR_ARG, "discriminator: bad descriptor");
     if (!out) return p.n_chunks;
-    if (cap < p.n_chunks || !workspace) return fail(RESR_ERR_ARG, "discriminator_pack_table: capacity / workspace");
+    if (!workspace) return fail(RESR_ERR_ARG, "discriminator_pack_table: workspace");
     DBufs b;
     carve(p, (char*)workspace, b);
-    int64_t n = 0;
+    std::vector<ResrPackChunk> t;
     for (int li = 0; li < kLayers; ++li) {
         const Layer& l = kL[li];
         const float* sp = l.sn ? b.sigma + li * 2 + 1 : nullptr;
-        for (int pass = 0; pass < 2; ++pass) {   // 0: forward (M = cout, K = cin_v); 1: backward-data (M = cin_v, K = cout)
-            const int mtot = pass ? p.cin_pad[li] : p.cout_pad[li], mreal = pass ? p.cin_v[li] : l.cout;
-            const int ktot = pass ? p.cout_pad[li] : p.cin_pad[li], kreal = pass ? l.cout : p.cin_v[li];
-            size_t pk = pass ? p.pk_bwd[li] : p.pk_fwd[li];
-            for (int g0 = 0; g0 < mtot; g0 += 64) {
-                const int mt = (mtot - g0 < 64 ? mtot - g0 : 64) / 32;
-                for (int ck = 0; ck < ktot / 32; ++ck) {
-                    ResrPackChunk c;
-                    memset(&c, 0, sizeof(c));
-                    c.src_off = (int64_t)p.w_off[li]; c.dst_off = (int64_t)pk;
-                    c.src_cout = l.cout; c.src_cin = l.cin;
-                    c.m_off = g0; c.m_count = mreal - g0 < 64 ? (mreal - g0 > 0 ? mreal - g0 : 0) : 64;
-                    c.k_off = ck * 32; c.k_count = kreal - ck * 32 < 32 ? (kreal - ck * 32 > 0 ? kreal - ck * 32 : 0) : 32;
-                    c.mt = mt; c.transposed = pass; c.scale = 1.f; c.virtual4x4 = l.k4; c.scale_ptr = sp;
-                    out[n++] = c;
-                    pk += (size_t)9 * mt * 1024;
-                }
-            }
-        }
+        emit_conv_chunks(t, (int64_t)p.w_off[li], l.cout, l.cin, 0, (int64_t)p.pk_fwd[li], 1.f, l.k4, sp);   // forward (M = cout, K = cin_v)
+        emit_conv_chunks(t, (int64_t)p.w_off[li], l.cout, l.cin, 1, (int64_t)p.pk_bwd[li], 1.f, l.k4, sp);   // backward-data (M = cin_v, K = cout)
     }
-    return n;
+    return copy_pack_table(t, out, cap, "discriminator_pack_table");
 }
 
 int discriminator_forward(const ResrDiscriminatorDesc* d, const float* x, const float* params, float* uv, const ResrPackChunk* table,
@@ -402,10 +367,10 @@ int backward_pass(const DPlan& pc, int dt, const float* gy, const float* params,
         // algorithmic products (its reduction's argument block) -- a 128..256-channel layer is one or two launch pairs, not 2..4
         const int parts = x2 ? wgrad_x2_products() : 1;
         const char* no_layer_mode = getenv("RESR_WGRAD_NO_LAYER_MODE");   // A/B knob, read per call: the table-mode launch pairs
-        if ((dt == RESR_F16 || dt == RESR_F16X2) && chunks * (r32(l.cout) / 32) >= kLayerModeProducts && !no_layer_mode) {
+        if ((dt == RESR_F16 || dt == RESR_F16X2) && chunks * (round32(l.cout) / 32) >= kLayerModeProducts && !no_layer_mode) {
             WgradConv c;
             c.x0 = x; c.cin = cin_pad; c.in0_stride = xs; c.cin_real = cin_v;
-            c.g = g; c.cout = l.cout; c.cout_pad = r32(l.cout); c.g_stride = gs;
+            c.g = g; c.cout = l.cout; c.cout_pad = round32(l.cout); c.g_stride = gs;
             c.x_chunk_stride = c.g_chunk_stride = 0; c.x_lo_off = x2 ? lo_xw : 0; c.g_lo_off = x2 ? lo_gw : 0;
             c.x_s2d_c = l.k4 ? l.cin : 0; c.g_lo_bias_only = 0;
             c.dw = raw; c.db = (l.bias ? grad + p.b_off[li] : nullptr); c.scale = 1.f;
@@ -418,16 +383,16 @@ int backward_pass(const DPlan& pc, int dt, const float* gy, const float* params,
         if (tiles_per > 80 / chunks) tiles_per = 80 / chunks;
         if (tiles_per < 1) tiles_per = 1;
         const int step = tiles_per * 32;
-        for (int g0 = 0; g0 < r32(l.cout); g0 += step) {       // one launch pair per `step` output channels, as convolutions of <= 64
+        for (int g0 = 0; g0 < round32(l.cout); g0 += step) {       // one launch pair per `step` output channels, as convolutions of <= 64
             WgradConv cs[8];
             int nc = 0, jobs = 0;
-            for (int q0 = g0; q0 < g0 + step && q0 < r32(l.cout) && nc < 8; q0 += 64) {
+            for (int q0 = g0; q0 < g0 + step && q0 < round32(l.cout) && nc < 8; q0 += 64) {
                 int co = l.cout - q0; if (co > 64) co = 64;
                 if (g0 + step - q0 < co) co = g0 + step - q0;
                 if (co <= 0) continue;
                 WgradConv& c = cs[nc++];
                 c.x0 = x; c.cin = cin_pad; c.in0_stride = xs; c.cin_real = cin_v;
-                c.g = g + (size_t)q0 * es; c.cout = co; c.cout_pad = r32(co); c.g_stride = gs;
+                c.g = g + (size_t)q0 * es; c.cout = co; c.cout_pad = round32(co); c.g_stride = gs;
                 c.x_chunk_stride = c.g_chunk_stride = 0; c.x_lo_off = lo_xw; c.g_lo_off = lo_gw;
                 c.g_lo_bias_only = 0;
                 c.x_s2d_c = l.k4 ? l.cin : 0;      // 4x4 / stride-2 layers: X is the space-to-depth image, skip the virtual kernel's zero taps
@@ -438,7 +403,7 @@ int backward_pass(const DPlan& pc, int dt, const float* gy, const float* params,
             if (!nc) continue;
             // slabs are per TAP-product (three per algorithmic product in exact16's default form): split by that count, which is
             // also what carve() sized the slab buffer for
-            const int splits = wsplits(dt, jobs * parts, N, h, w);
+            const int splits = wgrad_default_splits(dt, jobs * parts, N, h, w);
             if (wgrad_batch_partial_bytes(cs, nc, splits, dt) > b.partial_bytes) return fail(RESR_ERR_WORKSPACE, "discriminator: wgrad slabs");
             DRUN(wgrad_batch(cs, nc, N, h, w, dt, 0, splits, b.partial, st));
         }

@@ -27,7 +27,8 @@
 #include <stdlib.h>
 #include <vector>
 
-#include "host_api.h"
+#include "conv3x3.h"
+#include "packed_layout.h"
 
 namespace resr {
 
@@ -36,7 +37,7 @@ namespace {
 struct ConvSpec {
     int cout, cin, cin_pad, cout_pad;
     size_t w_off, b_off;      // element offsets in the fp32 parameter arena
-    size_t pk_fwd, pk_bwd;    // element offsets in the packed buffer (bwd: first pass of this conv)
+    size_t pk_fwd, pk_bwd;    // element offsets in the packed buffer (bwd: the transposed form of the six convs outside the trunk)
 };
 
 // ResrGeneratorDesc.x2_plan (RESR_X2_PLAN_*, include/resr.h) validated and resolved once by resolve_x2_plan(): one named answer per question the layout or a pass asks, all
@@ -70,12 +71,10 @@ struct Plan {
     size_t pk_fwd_elems, pk_total_elems;
     // indices
     int i_conv1, i_trunk0, i_conv2, i_up1, i_up2, i_conv3, i_conv4;
+    int i_bwd[6];   // the six convs outside the trunk, in the order their transposed forms lie in the packed buffer (ConvSpec.pk_bwd)
     // backward packed offsets of trunk passes: [rdb][pass 0..4] (pass 0 -> g_o4 ... pass 4 -> g_x)
     std::vector<size_t> pk_bwd_trunk;
-    size_t pk_bwd_conv4, pk_bwd_conv3, pk_bwd_up2, pk_bwd_up1, pk_bwd_conv2, pk_bwd_conv1;
 };
-
-int round32(int v) { return (v + 31) / 32 * 32; }
 
 // The prerequisite rules of the plan bits, {bit, the bits it needs, text}: the table of include/resr.h, checked here alone (the module asks: _lib.x2_plan_error)
 constexpr struct X2Rule { int bit, needs; const char* text; } kX2Rules[] = {
@@ -154,27 +153,22 @@ bool build_plan(const ResrGeneratorDesc* d, Plan& p) {
     size_t pk = 0;
     for (auto& c : p.convs) {
         c.pk_fwd = pk;
-        pk += (size_t)(c.cin_pad / 32) * 9 * (c.cout_pad / 32) * 1024;
+        pk += packed_conv_elems(c.cout_pad, c.cin_pad);
     }
     p.pk_fwd_elems = pk;
-    auto bwd_simple = [&](int idx) {  // transposed conv: M = cin_pad (as cout_pad), K = cout_pad
-        const ConvSpec& c = p.convs[idx];
-        const size_t o = pk;
-        pk += (size_t)(c.cout_pad / 32) * 9 * (c.cin_pad / 32) * 1024;
-        return o;
-    };
-    p.pk_bwd_conv4 = bwd_simple(p.i_conv4);
-    p.pk_bwd_conv3 = bwd_simple(p.i_conv3);
-    p.pk_bwd_up2 = bwd_simple(p.i_up2);
-    p.pk_bwd_up1 = bwd_simple(p.i_up1);
-    p.pk_bwd_conv2 = bwd_simple(p.i_conv2);
-    p.pk_bwd_conv1 = bwd_simple(p.i_conv1);
+    const int order[6] = {p.i_conv4, p.i_conv3, p.i_up2, p.i_up1, p.i_conv2, p.i_conv1};
+    for (int k = 0; k < 6; ++k) {   // transposed conv: M = cin_pad, K = cout_pad
+        p.i_bwd[k] = order[k];
+        ConvSpec& c = p.convs[order[k]];
+        c.pk_bwd = pk;
+        pk += packed_conv_elems(c.cin_pad, c.cout_pad);
+    }
     p.pk_bwd_trunk.resize((size_t)p.nrdb * 5);
     for (int r = 0; r < p.nrdb; ++r)
         for (int ps = 0; ps < 5; ++ps) {
             // pass ps: K chunks = 2 (g_y through conv5) + ps (conv4 .. conv(5-ps)); M tiles = 1 (ps<4) or 2
             p.pk_bwd_trunk[(size_t)r * 5 + ps] = pk;
-            pk += (size_t)(2 + ps) * 9 * (ps < 4 ? 1 : 2) * 1024;
+            pk += (size_t)(2 + ps) * packed_chunk_elems(ps < 4 ? 1 : 2);
         }
     p.pk_total_elems = pk;
     return true;
@@ -202,10 +196,8 @@ struct Bufs {
     size_t total;
 };
 
-// pixel splits of a batched weight-gradient launch (`npairs` = (X chunk, G tile) products), never fewer than two pixel
-// tiles per workgroup.  strict: one workgroup per product and split, 256 CUs filled about three times over.  fast: the
-// quad kernel runs one 8-wave workgroup per CU on npairs/4 jobs -- two rounds of 256, in whole groups of 8 splits
-// (a split's jobs share one XCD).
+// pixel splits of a batched weight-gradient launch (`npairs` = (X chunk, G tile) products): the descriptor's override, exact16's own
+// cost model, else the rule every network shares (wgrad_default_splits).
 // exact16 (nquads > 0: the launch's real quad-job count, wgrad_batch_quads): its job sets do not fill whole rounds the way fast
 // mode's do -- a dense block with single-f16 growth gradients is 17 quads, and 17 x 32 splits = 544 workgroups is a third,
 // nearly empty residency round (68 workgroups per XCD on 32 CUs).  Splits come in eights (a split's jobs share one XCD: nquads
@@ -226,18 +218,7 @@ int splits_for(const Plan& p, int npairs, int h, int w, int nquads = 0) {
         }
         return (int)best_s;
     }
-    long s;
-    if (p.d.dtype != RESR_F32) {
-        s = 512 / ((npairs + 3) / 4);
-        if (s >= 16) s &= ~7L;
-        if (s > 256) s = 256;
-    } else {
-        s = 768 / npairs;
-        if (s > 128) s = 128;
-    }
-    if (s > tiles / 2) s = tiles / 2;
-    if (s < 1) s = 1;
-    return (int)s;
+    return wgrad_default_splits(p.d.dtype, npairs, p.d.n, h, w);
 }
 
 void carve(const Plan& p, char* base, Bufs& b) {
@@ -282,7 +263,6 @@ void carve(const Plan& p, char* base, Bufs& b) {
         for (int i = 0; i < 3; ++i) b.gS[i] = take(px * 128 * esg);
         b.gxin = take(px * p.ci_pad * es);
         // wgrad slabs: largest batch (an RRDB = 78 products, a dense block = 26 at LR; single 64->64 convs = 4 jobs at 1x/2x/4x)
-        const size_t slab = (9 * 1024 + 32) * sizeof(float);
         size_t pb = 0;
         if (p.d.dtype == RESR_F16X2) {   // exact16 picks its splits per launch (splits_for with the real quad count): size for any choice
             const int th = wgrad_tile_rows(p.d.dtype);
@@ -290,25 +270,25 @@ void carve(const Plan& p, char* base, Bufs& b) {
                 const long tiles = (long)((p.w * m + 31) / 32) * ((p.h * m + th - 1) / th) * p.d.n;
                 const long smax = tiles / 2 < 256 ? (tiles / 2 < 1 ? 1 : tiles / 2) : 256;
                 // (a single 64 -> 64 convolution: 12 tap-products; mx_tail: 4 f16 jobs + 4 MX jobs whose launch takes up to 4 x the splits)
-                const size_t q = (size_t)(m == 1 ? 78 : (p.x2.mx_tail ? 20 : 12)) * (size_t)smax * slab;
+                const size_t q = wgrad_slab_bytes(m == 1 ? 78 : (p.x2.mx_tail ? 20 : 12), smax);
                 if (q > pb) pb = q;
             }
         }
         for (int k = 1; k <= wm; k += 2) {          // both weight-gradient settings of RESR_F16X2 (1 or 3 jobs per product)
-            const size_t q0 = (size_t)26 * k * splits_for(p, 26 * k, p.h, p.w) * slab;
+            const size_t q0 = wgrad_slab_bytes(26 * k, splits_for(p, 26 * k, p.h, p.w));
             if (q0 > pb) pb = q0;
             if (k == 3) {   // gg_single: conv1..conv4 (14 products) two tap-products each + 4 bias jobs, conv5 (12) three
-                const size_t qg = (size_t)68 * splits_for(p, 68, p.h, p.w) * slab;
+                const size_t qg = wgrad_slab_bytes(68, splits_for(p, 68, p.h, p.w));
                 if (qg > pb) pb = qg;
             }
             if (78 * k <= kWgradMaxJobs) {
-                const size_t q3 = (size_t)78 * k * splits_for(p, 78 * k, p.h, p.w) * slab;
+                const size_t q3 = wgrad_slab_bytes(78 * k, splits_for(p, 78 * k, p.h, p.w));
                 if (q3 > pb) pb = q3;
             }
             for (int m = 1; m <= 4; m *= 2) {
-                const size_t q = (size_t)4 * k * splits_for(p, 4 * k, p.h * m, p.w * m) * slab;
+                const size_t q = wgrad_slab_bytes(4 * k, splits_for(p, 4 * k, p.h * m, p.w * m));
                 if (q > pb) pb = q;
-                const size_t q2 = (size_t)2 * k * splits_for(p, 2 * k, p.h * m, p.w * m) * slab;
+                const size_t q2 = wgrad_slab_bytes(2 * k, splits_for(p, 2 * k, p.h * m, p.w * m));
                 if (q2 > pb) pb = q2;
             }
         }
@@ -326,11 +306,9 @@ void carve(const Plan& p, char* base, Bufs& b) {
 
 ResrConvDesc conv_desc(const Plan& p, int n, int h, int w, int cin, int cin0, int s0, int s1, int cout, int cout_pad,
                        int out_stride, int flags) {
-    ResrConvDesc c;
-    memset(&c, 0, sizeof(c));
-    c.n = n; c.h = h; c.w = w; c.cin = cin; c.cin0 = cin0; c.in0_stride = s0; c.in1_stride = s1;
-    c.cout = cout; c.cout_pad = cout_pad; c.out_stride = out_stride; c.dtype = p.d.dtype; c.flags = flags;
-    c.s0 = c.s1 = 1.f; c.t0 = c.t1 = 1.f; c.slope = 0.2f;
+    ResrConvDesc c = conv_desc_base(n, h, w, p.d.dtype, flags, 0.2f);
+    c.cin = cin; c.cin0 = cin0; c.in0_stride = s0; c.in1_stride = s1;
+    c.cout = cout; c.cout_pad = cout_pad; c.out_stride = out_stride;
     return c;
 }
 
@@ -346,15 +324,14 @@ size_t generator_param_count(const ResrGeneratorDesc* d) {
 size_t generator_mx_offset(const ResrGeneratorDesc* d) {
     Plan p;
     if (!build_plan(d, p) || d->dtype != RESR_F16X2) return 0;
-    return align_up(p.pk_total_elems * 2 * 3 + 16384, 256);
+    return packed_mx_offset(p.pk_total_elems);
 }
 
 size_t generator_packed_bytes(const ResrGeneratorDesc* d, int backward) {
     Plan p;
     if (!build_plan(d, p)) return 0;
-    if (p.x2.packed_mx) return generator_mx_offset(d) + p.pk_total_elems * 2 + 16384;
-    // + two dummy (chunk,tap) of slack: conv3x3_kernel prefetches two taps past the end
-    return (backward ? p.pk_total_elems : p.pk_fwd_elems) * elem_size(d->dtype) * (d->dtype == RESR_F16X2 ? 3 : 1) + 16384;
+    if (p.x2.packed_mx) return packed_mx_buffer_bytes(p.pk_total_elems);
+    return packed_buffer_bytes(backward ? p.pk_total_elems : p.pk_fwd_elems, d->dtype);
 }
 
 // the zero-filled head of a workspace: the chain state of the dense-block launches + the gradient pre-scale slot behind it
@@ -392,38 +369,13 @@ int64_t generator_pack_table(const ResrGeneratorDesc* d, int backward, ResrPackC
     Plan p;
     if (!build_plan(d, p)) return RESR_ERR_ARG;
     std::vector<ResrPackChunk> t;
-    auto push = [&](const ConvSpec& c, size_t dst, int m_off, int m_count, int k_off, int k_count, int mt, int tr,
-                    float scale) {
-        ResrPackChunk ch;
-        memset(&ch, 0, sizeof(ch));
-        ch.src_off = (int64_t)c.w_off; ch.dst_off = (int64_t)dst;
-        ch.src_cout = c.cout; ch.src_cin = c.cin;
-        ch.m_off = m_off; ch.m_count = m_count; ch.k_off = k_off; ch.k_count = k_count;
-        ch.mt = mt; ch.transposed = tr; ch.scale = scale;
-        t.push_back(ch);
-    };
-    for (const auto& c : p.convs) {
-        const int mt = c.cout_pad / 32;
-        for (int ck = 0; ck < c.cin_pad / 32; ++ck) {
-            const int kc = c.cin - ck * 32;
-            push(c, c.pk_fwd + (size_t)ck * 9 * mt * 1024, 0, c.cout, ck * 32, kc > 32 ? 32 : kc, mt, 0, 1.f);
-        }
-    }
+    for (const auto& c : p.convs) emit_conv_chunks(t, (int64_t)c.w_off, c.cout, c.cin, 0, (int64_t)c.pk_fwd);
     if (backward) {
-        auto simple = [&](int idx, size_t base) {
-            const ConvSpec& c = p.convs[idx];
-            const int mt = c.cin_pad / 32;
-            for (int ck = 0; ck < c.cout_pad / 32; ++ck) {
-                const int kc = c.cout - ck * 32;
-                push(c, base + (size_t)ck * 9 * mt * 1024, 0, c.cin, ck * 32, kc > 32 ? 32 : kc, mt, 1, 1.f);
-            }
+        for (int idx : p.i_bwd) emit_conv_chunks(t, (int64_t)p.convs[idx].w_off, p.convs[idx].cout, p.convs[idx].cin, 1, (int64_t)p.convs[idx].pk_bwd);
+        // the dense blocks' mirrored passes: slices (m_off) of conv5 / conv_k with the residual scalings folded in
+        auto push = [&](const ConvSpec& c, size_t dst, int m_off, int m_count, int k_off, int mt, float scale) {
+            t.push_back(pack_chunk((int64_t)c.w_off, (int64_t)dst, c.cout, c.cin, m_off, m_count, k_off, 32, mt, 1, scale));
         };
-        simple(p.i_conv4, p.pk_bwd_conv4);
-        simple(p.i_conv3, p.pk_bwd_conv3);
-        simple(p.i_up2, p.pk_bwd_up2);
-        simple(p.i_up1, p.pk_bwd_up1);
-        simple(p.i_conv2, p.pk_bwd_conv2);
-        simple(p.i_conv1, p.pk_bwd_conv1);
         for (int r = 0; r < p.nrdb; ++r) {
             // the 0.2 of model.py:95 (and, for the third RDB of a block, the 0.2 of model.py:129) folded in
             const float fold = (r % 3 == 2) ? 0.2f * 0.2f : 0.2f;
@@ -433,21 +385,17 @@ int64_t generator_pack_table(const ResrGeneratorDesc* d, int backward, ResrPackC
                 const int m_cnt = ps < 4 ? 32 : 64;
                 size_t dst = p.pk_bwd_trunk[(size_t)r * 5 + ps];
                 const ConvSpec& c5 = p.convs[p.i_trunk0 + r * 5 + 4];
-                push(c5, dst, m_off, m_cnt, 0, 32, mt, 1, fold); dst += (size_t)9 * mt * 1024;
-                push(c5, dst, m_off, m_cnt, 32, 32, mt, 1, fold); dst += (size_t)9 * mt * 1024;
+                push(c5, dst, m_off, m_cnt, 0, mt, fold); dst += packed_chunk_elems(mt);
+                push(c5, dst, m_off, m_cnt, 32, mt, fold); dst += packed_chunk_elems(mt);
                 for (int j = 0; j < ps; ++j) {  // g_o4, g_o3, ... in gS channel order
                     const ConvSpec& ck = p.convs[p.i_trunk0 + r * 5 + (3 - j)];
-                    push(ck, dst, m_off, m_cnt, 0, 32, mt, 1, 1.f);
-                    dst += (size_t)9 * mt * 1024;
+                    push(ck, dst, m_off, m_cnt, 0, mt, 1.f);
+                    dst += packed_chunk_elems(mt);
                 }
             }
         }
     }
-    if (out) {
-        if ((int64_t)t.size() > cap) return fail(RESR_ERR_ARG, "generator_pack_table: capacity %lld < %zu", (long long)cap, t.size());
-        memcpy(out, t.data(), t.size() * sizeof(ResrPackChunk));
-    }
-    return (int64_t)t.size();
+    return copy_pack_table(t, out, cap, "generator_pack_table");
 }
 
 static int debug_stop() {
@@ -481,7 +429,7 @@ int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* p
     if (b.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "generator_forward: workspace %zu < %zu", workspace_bytes, b.total);
     const size_t es = elem_size(d->dtype);
     const bool x2 = d->dtype == RESR_F16X2;
-    const size_t wes = es * (x2 ? 3 : 1);   // bytes per element of the plain packed layout
+    const size_t wes = packed_elem_bytes(d->dtype);   // bytes per element of the plain packed layout
     const char* pk = (const char*)packed;
     const int N = d->n, h = p.h, w = p.w;
     const int nws = (int)b.ws.size();
@@ -642,7 +590,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
     pb.d.dtype = dt;
     const size_t es = elem_size(dt);
     const bool x2 = dt == RESR_F16X2;
-    const size_t wes = es * (x2 ? 3 : 1);
+    const size_t wes = packed_elem_bytes(dt);
     const int wm = x2 ? wgrad_x2_products() : 1;
     // The 16-bit modes lift a small incoming gradient into f16's normal range: when max |g_y| < 2^6 the pass runs on g_y * 2^k with
     // max |g_y * 2^k| in [2^6, 2^7) and hands every result out times 2^-k (both exact; common.h grad_prescale).  The pass is linear in
@@ -717,16 +665,16 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
         RUN(wgrad(c, H4, W4, b.c3, 64, 32, b.g4, 32, 0, 1.f, pl4, 0, lo_4, lo_g4, xp.mx_tail ? 2 * lo_4 : 0, xp.mx_tail ? 2 * lo_g4 : 0));
         ResrConvDesc cd = dgrad(H4, W4, 32, 32, 32, 0, 64, 64, 32, RESR_CONV_MASK | RESR_CONV_MASK_BITS, lo_g4, 0, lo_4);
         cd.out_chunk_stride = pl4;
-        MXT(cd, p.pk_bwd_conv4, 2 * lo_g4, 2 * lo_4);
-        RUN(conv3x3_dispatch(&cd, b.g4, nullptr, pk + p.pk_bwd_conv4 * wes, nullptr, nullptr, nullptr, b.bits_c3, b.gA, nullptr, st));
+        MXT(cd, c.pk_bwd, 2 * lo_g4, 2 * lo_4);
+        RUN(conv3x3_dispatch(&cd, b.g4, nullptr, pk + c.pk_bwd * wes, nullptr, nullptr, nullptr, b.bits_c3, b.gA, nullptr, st));
     }
     {   // conv3                                                            model.py:267
         const ConvSpec& c = p.convs[p.i_conv3];
         RUN(wgrad(c, H4, W4, b.u2, 64, 32, b.gA, 32, 0, 1.f, pl4, pl4, lo_4, lo_4, xp.mx_tail ? 2 * lo_4 : 0, xp.mx_tail ? 2 * lo_4 : 0));
         ResrConvDesc cd = dgrad(H4, W4, 64, 32, 64, 0, 64, 64, 32, RESR_CONV_MASK | RESR_CONV_MASK_BITS, lo_4, 0, lo_4);
         cd.in0_chunk_stride = pl4; cd.out_chunk_stride = pl4;
-        MXT(cd, p.pk_bwd_conv3, 2 * lo_4, 2 * lo_4);
-        RUN(conv3x3_dispatch(&cd, b.gA, nullptr, pk + p.pk_bwd_conv3 * wes, nullptr, nullptr, nullptr, b.bits_u2, b.gB, nullptr, st));
+        MXT(cd, c.pk_bwd, 2 * lo_4, 2 * lo_4);
+        RUN(conv3x3_dispatch(&cd, b.gA, nullptr, pk + c.pk_bwd * wes, nullptr, nullptr, nullptr, b.bits_u2, b.gB, nullptr, st));
     }
     if (debug_stop() == 1) return RESR_OK;
     {   // upsampling2                                                      model.py:265
@@ -734,8 +682,8 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
         RUN(wgrad(c, H4, W4, b.u1, 64, 32, b.gB, 32, RESR_CONV_UPSAMPLE_IN, 1.f, pl2, pl4, lo_2, lo_4, xp.mx_tail ? 2 * lo_2 : 0, xp.mx_tail ? 2 * lo_4 : 0));
         ResrConvDesc cd = dgrad(H4, W4, 64, 32, 64, 0, 64, 64, 32, 0, lo_4, 0, lo_4);
         cd.in0_chunk_stride = pl4; cd.out_chunk_stride = pl4;
-        MXT(cd, p.pk_bwd_up2, 2 * lo_4, 0);     // (its output feeds the sum-pool: no q tensor)
-        RUN(conv3x3_dispatch(&cd, b.gB, nullptr, pk + p.pk_bwd_up2 * wes, nullptr, nullptr, nullptr, nullptr, b.gA, nullptr, st));
+        MXT(cd, c.pk_bwd, 2 * lo_4, 0);     // (its output feeds the sum-pool: no q tensor)
+        RUN(conv3x3_dispatch(&cd, b.gB, nullptr, pk + c.pk_bwd * wes, nullptr, nullptr, nullptr, nullptr, b.gA, nullptr, st));
         for (int q = 0; q < 2; ++q)   // per 32-channel plane
             RUN(sumpool2x2_dispatch(b.gA + (size_t)q * pl4 * es, b.gM1 + (size_t)q * pl2 * es, b.u1 + (size_t)q * pl2 * es,
                                     N, H2, W2, 32, dt, 0.2f, st, lo_4, lo_2));
@@ -746,7 +694,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
         RUN(wgrad(c, H2, W2, b.feat, 64, 32, b.gM1, 32, RESR_CONV_UPSAMPLE_IN, 1.f, plane, pl2, lo_t, lo_2));
         ResrConvDesc cd = dgrad(H2, W2, 64, 32, 64, 0, 64, 64, 32, 0, lo_2, 0, lo_2);
         cd.in0_chunk_stride = pl2; cd.out_chunk_stride = pl2;
-        RUN(conv3x3_dispatch(&cd, b.gM1, nullptr, pk + p.pk_bwd_up1 * wes, nullptr, nullptr, nullptr, nullptr, b.gA, nullptr, st));
+        RUN(conv3x3_dispatch(&cd, b.gM1, nullptr, pk + c.pk_bwd * wes, nullptr, nullptr, nullptr, nullptr, b.gA, nullptr, st));
         for (int q = 0; q < 2; ++q)
             RUN(sumpool2x2_dispatch(b.gA + (size_t)q * pl2 * es, b.gF + (size_t)q * plane * es, nullptr, N, h, w, 32, dt, 0.2f, st,
                                     lo_2, lo_t));
@@ -759,7 +707,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
         ResrConvDesc cd = dgrad(h, w, 64, 32, 64, 0, 64, 64, 32, 0, lo_t, 0, lo_t);
         cd.in0_chunk_stride = plane; cd.out_chunk_stride = plane;   // the gT ring (gradient wrt the RDB chain) is chunk-planar [2][N,h,w,32]
         if (xp.mx_bwd) cd.out_q_offset = 2 * lo_t;   // the first dense block's passes read gT[0] through MX stages: this (plain) pass emits its q tensor
-        RUN(conv3x3_dispatch(&cd, b.gF, nullptr, pk + p.pk_bwd_conv2 * wes, nullptr, nullptr, nullptr, nullptr, b.gT[0], nullptr, st));
+        RUN(conv3x3_dispatch(&cd, b.gF, nullptr, pk + c.pk_bwd * wes, nullptr, nullptr, nullptr, nullptr, b.gT[0], nullptr, st));
     }
     auto MXB = [&](ResrConvDesc& cd, size_t pk_off, long out_q) {   // gin (in0) and the slab gS (in1) with their q tensors, the pass's MX blocks
         if (!xp.mx_bwd) return;
@@ -844,7 +792,7 @@ int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float*
         if (gx) {
             ResrConvDesc cd = dgrad(h, w, 64, 32, 64, 0, p.ci_pad, p.ci_pad, p.ci_pad, 0, lo_t, 0, lo_xin);
             cd.in0_chunk_stride = plane;
-            RUN(conv3x3_dispatch(&cd, b.gT[cur], nullptr, pk + p.pk_bwd_conv1 * wes, nullptr, nullptr, nullptr, nullptr, b.gxin, nullptr, st));
+            RUN(conv3x3_dispatch(&cd, b.gT[cur], nullptr, pk + c.pk_bwd * wes, nullptr, nullptr, nullptr, nullptr, b.gxin, nullptr, st));
             RUN(nhwc_to_nchw_scaled_dispatch(b.gxin, gx, N, d->in_channels, d->h, d->w, p.r, p.ci_pad, dt, st, lo_xin, gsc));
         }
     }

@@ -28,6 +28,7 @@ size_t conv3x3_chain_state_bytes(int n, int h, int w);
 // ---- wgrad.hip.  splits: pixel splits of the launch (one slab of partial sums each); partial: the slab scratch *_partial_bytes sizes;
 // flags: RESR_CONV_* of the forward convolution (RESR_CONV_UPSAMPLE_IN) ----
 int wgrad_tile_rows(int dtype);
+int wgrad_default_splits(int dtype, int jobs, int n, int h, int w);
 int wgrad_x2_products();   // tap-products per RESR_F16X2 weight gradient
 int wgrad_batch_quads(const WgradConv* convs, int nconv, int dtype);
 int wgrad_batch_jobs(const WgradConv* convs, int nconv, int dtype);

@@ -1,29 +1,22 @@
 // pack.hip -- parameter-side kernels: weight packing into MFMA A-fragment order, EMA update.
 //
-// resr_pack_weights: the module keeps the reference's OIHW fp32 parameters (state_dict surface,
-// SURVEY.md §8b).  Every optimiser step they are re-packed (one launch for all 351 convs, both the
-// forward and the backward-data forms) into the order conv3x3.hip streams them:
-//     chunk (32 K-channels) -> tap (9) -> k-step -> M-tile -> lane (kh*32 + m) -> 16 bytes
-// so that a wave's A-fragment is one contiguous, coalesced 1 KiB load.
-// Backward-data chunks are gathered transposed (M = cin, K = cout) with flipped taps and an optional
-// scale (the 0.2 residual scalings of model.py:95,129 folded into the weights).
+// resr_pack_weights: every optimiser step the module's OIHW fp32 parameters (state_dict surface) are re-packed, one
+// launch for all 351 convs and both forms, into the format packed_layout.h defines.
 #include "host_api.h"
+#include "packed_layout.h"
 
 namespace resr {
 
-//
-// RESR_F16X2 (X2 = true): a chunk becomes THREE consecutive f16 blocks of the plain chunk's size, in the stage order of
-// the conv kernel: W0 = f16(w * 2^12) (multiplies x_hi), W1 = f16(w * 2^12 - W0) (x_hi again), W2 = f16(W0 * 2^-12)
-// (multiplies x_lo, which is stored times 2^12).  The table's dst_off counts elements of the *plain* layout; the
-// kernel triples it.
+// One workgroup per chunk of the table; the index decomposition below IS the order inside a block (packed_layout.h has the rest of the
+// format).  X2 = true (RESR_F16X2): the chunk's three f16 blocks W0, W1, W2.
 template <typename T, bool X2 = false>
 __global__ __launch_bounds__(256) void pack_kernel(const ResrPackChunk* __restrict__ chunks,
                                                    const float* __restrict__ arena, T* __restrict__ packed) {
     constexpr int E = 16 / (int)sizeof(T);
     constexpr int KS = 32 / E / 2;
     const ResrPackChunk c = chunks[blockIdx.x];
-    const int total = 9 * c.mt * 1024;
-    T* dst = packed + c.dst_off * (X2 ? 3 : 1);
+    const int total = packed_chunk_elems(c.mt);
+    T* dst = packed + c.dst_off * packed_blocks(X2);
     const float* src = arena + c.src_off;
     const float sc = c.scale * (c.scale_ptr ? *c.scale_ptr : 1.f);
     for (int idx = threadIdx.x; idx < total; idx += 256) {

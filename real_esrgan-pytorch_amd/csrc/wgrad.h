@@ -2,6 +2,7 @@
 // the whole-network planners (generator.hip, disc_native.hip).  The functions that take it (wgrad_batch, wgrad_layer, ...) are
 // declared in host_api.h, which includes this file.
 #pragma once
+#include <stddef.h>
 
 namespace resr {
 
@@ -29,5 +30,8 @@ struct WgradConv {
 };
 
 constexpr int kWgradMaxJobs = 96;   // (X chunk, G tile) tap-products per weight-gradient launch (kernel arguments: 96 x 40 B + header < 4 KB)
+constexpr int kSlab = 9 * 1024 + 32;   // floats per (job, split): 9 taps x 32 co x 32 ci, then 32 bias sums
+// bytes of slab scratch (`partial`) of a launch of `jobs` tap-products in `splits` pixel splits
+inline size_t wgrad_slab_bytes(size_t jobs, size_t splits) { return jobs * splits * kSlab * sizeof(float); }
 
 }  // namespace resr

@@ -38,7 +38,6 @@ constexpr int kMaxJobs = kWgradMaxJobs;    // (X chunk, G tile) tap-products per
 constexpr int kMaxReduce = 80;  // algorithmic products per launch (ReduceArgs: 80 x 48 B)
 constexpr int kMaxQuads = 40;   // 2x2 jobs per launch of the quad kernel
 constexpr int kX2WgradProductsDefault = 3;   // see wgrad_x2_products()
-constexpr int kSlab = 9 * 1024 + 32;   // floats per (job, split): 9 taps x 32 co x 32 ci, then 32 bias sums
 
 struct WgradJob {
     const char* x;        // X base + channel offset of the job's 32-channel chunk
@@ -896,6 +895,19 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const ReduceArgs a) {
 // ---------------------------------------------------------------------------------------------------------
 int wgrad_tile_rows(int dtype) { return dtype != RESR_F32 ? 8 : 4; }
 
+// The default pixel splits of a batched launch of `jobs` tap-products, never fewer than two pixel tiles per workgroup.  strict: one
+// workgroup per product and split, 256 CUs filled about three times over.  fast: the quad kernel runs one 8-wave workgroup per CU on
+// jobs / 4 quad jobs -- two rounds of 256, in whole groups of 8 splits (a split's jobs share one XCD).
+int wgrad_default_splits(int dtype, int jobs, int n, int h, int w) {
+    const int th = wgrad_tile_rows(dtype);
+    const long tiles = (long)((w + 31) / 32) * ((h + th - 1) / th) * n;
+    long s;
+    if (dtype != RESR_F32) { s = 512 / ((jobs + 3) / 4); if (s >= 16) s &= ~7L; if (s > 256) s = 256; }
+    else { s = 768 / jobs; if (s > 128) s = 128; }
+    if (s > tiles / 2) s = tiles / 2;
+    return (int)(s < 1 ? 1 : s);
+}
+
 // `nprod`: algorithmic products of the launch (= njobs, or njobs / 3 with RESR_F16X2) for the profiling record
 template <typename T, int RPW>
 static int launch_wgrad(WgradArgs& a, int njobs, int nprod, hipStream_t stream) {
@@ -1224,7 +1236,7 @@ size_t wgrad_batch_partial_bytes(const WgradConv* convs, int nconv, int splits, 
     for (int i = 0; i < nconv; ++i) jobs += wgrad_conv_jobs(convs[i], dtype);
     const int n_mx = wgrad_mx_jobs(convs, nconv, dtype);
     jobs += (size_t)n_mx * (mx_split_factor(n_mx, splits) - 1);
-    return jobs * splits * kSlab * sizeof(float);
+    return wgrad_slab_bytes(jobs, splits);
 }
 
 // One convolution with a regular grid of more products than a launch's job table holds (WgradLayer): one launch pair for the
@@ -1287,7 +1299,7 @@ static int wgrad_layer_launch(const WgradConv& c, int n, int h, int w, int flags
 
 // floats of slab scratch a layer-mode launch needs
 size_t wgrad_layer_partial_bytes(int cin, int cout_pad, int splits, int dtype) {
-    return (size_t)(cin / 32) * (cout_pad / 32) * (dtype == RESR_F16X2 ? wgrad_x2_products() : 1) * splits * kSlab * sizeof(float);
+    return wgrad_slab_bytes((size_t)(cin / 32) * (cout_pad / 32) * (dtype == RESR_F16X2 ? wgrad_x2_products() : 1), splits);
 }
 
 // entry for the whole-network planners: one f16 convolution, cout_pad any multiple of 32, as one layer-mode launch pair
@@ -1430,7 +1442,7 @@ int wgrad_debug_dense_blocks(int nblocks, const void* const* x, const void* cons
 
 // single-conv C-ABI entry (include/resr.h resr_conv3x3_wgrad)
 size_t wgrad_partial_bytes(const ResrWgradDesc* d) {
-    return (size_t)(d->cin / 32) * (d->cout_pad / 32) * (d->dtype == RESR_F16X2 ? wgrad_x2_products() : 1) * d->splits * kSlab * sizeof(float);
+    return wgrad_slab_bytes((size_t)(d->cin / 32) * (d->cout_pad / 32) * (d->dtype == RESR_F16X2 ? wgrad_x2_products() : 1), d->splits);
 }
 
 int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw,

@@ -89,14 +89,10 @@ class ResidualResidualDenseBlock(nn.Module):
 def _pack_one(conv: nn.Conv2d, dtype: int) -> torch.Tensor:
     """Packed forward weights of ONE conv (resr_pack_weights on a one-conv table)."""
     w = conv.weight.detach().float().contiguous()
-    cout, cin = w.shape[:2]
-    mt, nck = (cout + 31) // 32, (cin + 31) // 32
-    chunks = (_lib.PackChunk * nck)()
-    for ck in range(nck):
-        chunks[ck] = _lib.PackChunk(0, ck * 9 * mt * 1024, cout, cin, 0, cout, ck * 32, min(32, cin - ck * 32), mt, 0, 1.0, 0, None)
+    chunks, elems = _lib.conv_pack_table(*w.shape[:2])
     table = _lib.upload_chunks(chunks, w.device)
-    packed = torch.zeros(nck * 9 * mt * 1024 * _lib.packed_elem_bytes(dtype) + _lib.PACKED_SLACK, dtype=torch.uint8, device=w.device)
-    _lib.check(_lib.lib().resr_pack_weights(_lib.ptr(table), nck, _lib.ptr(w.reshape(-1)), _lib.ptr(packed), dtype,
+    packed = torch.zeros(_lib.lib().resr_packed_bytes(elems, dtype), dtype=torch.uint8, device=w.device)
+    _lib.check(_lib.lib().resr_pack_weights(_lib.ptr(table), len(chunks), _lib.ptr(w.reshape(-1)), _lib.ptr(packed), dtype,
                                             _lib.stream_ptr(w)), "resr_pack_weights")
     return packed
 
