@@ -605,7 +605,8 @@ int resr_usm_sharp(const float* src, float* dst, float* tmp3, const float* k1d, 
 int resr_usm_sharp_forward_only(const float* src, float* dst, float* tmp3, const float* k1d, int32_t ksize, float weight,
                                 float threshold, int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
 /* backward of resr_usm_sharp wrt its input (the GAN step differentiates through usm_sharpener(sr),
- * train_realesrgan.py:476): saved_tmp3 = the forward's tmp3 (kept), tmp2 = 2*n*c*h*w floats of scratch. */
+ * train_realesrgan.py:476): saved_tmp3 = the forward's tmp3 (kept), tmp2 = 2*n*c*h*w floats of scratch.  RESR_ERR_ARG, before
+ * any launch, for what the forward refuses: n, c, h, w <= 0, an even ksize or one above 63, ksize / 2 >= h or w. */
 int resr_usm_sharp_bwd(const float* x, const float* saved_tmp3, const float* g, float* gx, float* tmp2, const float* k1d,
                        int32_t ksize, float weight, int32_t n, int32_t c, int32_t h, int32_t w, void* stream);
 /* F.interpolate (train_realesrnet.py:288,326-329,349-351,366-368): mode 0 area, 1 bilinear, 2 bicubic;

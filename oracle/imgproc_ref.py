@@ -64,7 +64,7 @@ def usm_sharp(img: torch.Tensor, kernel: torch.Tensor, weight: float = 0.5, thre
     """USMSharp.forward (imgproc.py:1526-1537)."""
     blur = filter2d(img, kernel)
     res = img - blur
-    mask = (res.abs() * 255 > threshold).float()
+    mask = (res.abs() * 255 > threshold).to(img.dtype)
     soft = filter2d(mask, kernel)
     sharp = (img + weight * res).clip(0, 1)
     return soft * sharp + (1 - soft) * img

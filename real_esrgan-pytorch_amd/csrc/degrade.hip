@@ -409,9 +409,19 @@ __global__ __launch_bounds__(256) void usm51_kernel(const TIN* __restrict__ src,
     }
 }
 
+// What USMSharp accepts, forward and backward: filter2d_dispatch's rules for the 1 x ksize and the ksize x 1 pass, checked before the
+// first launch of either direction (the backward launches no filter2d_dispatch that would refuse for it).
+static int usm_check_geometry(int ksize, int n, int c, int h, int w) {
+    if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "usm_sharp: bad argument");
+    if (ksize < 1 || !(ksize & 1) || ksize > 63) return fail(RESR_ERR_ARG, "Wrong kernel size.");   // imgproc.py:1106
+    if (ksize / 2 >= h || ksize / 2 >= w) return fail(RESR_ERR_ARG, "usm_sharp: reflect padding needs pad < image size");
+    return RESR_OK;
+}
+
 int usm_dispatch(const float* src, float* dst, float* tmp, const float* k1d, int ksize, float weight, float threshold,
                  int n, int c, int h, int w, hipStream_t st, int keep_for_backward) {
     if (!src || !dst || !tmp || !k1d) return fail(RESR_ERR_ARG, "usm_sharp: null argument");
+    if (int rc = usm_check_geometry(ksize, n, c, h, w)) return rc;
     const long count = (long)n * c * h * w;
     const char* six_env = getenv("RESR_USM_SIX_PASSES");   // A/B and test knob (read per call): the separate passes
     if (ksize == 51 && h > 25 && w > 25 && !six_env && (long)n * c < (1L << 24)) {
@@ -495,6 +505,7 @@ __global__ __launch_bounds__(256) void filter1d_adjoint_kernel(const float* __re
 int usm_bwd_dispatch(const float* x, const float* saved, const float* g, float* gx, float* tmp2, const float* k1d, int ksize,
                      float weight, int n, int c, int h, int w, hipStream_t st) {
     if (!x || !saved || !g || !gx || !tmp2 || !k1d) return fail(RESR_ERR_ARG, "usm_sharp_bwd: null argument");
+    if (int rc = usm_check_geometry(ksize, n, c, h, w)) return rc;   // (the adjoint below folds ONE reflection per border)
     const long count = (long)n * c * h * w;
     const float* blur = saved + count;       // layout of resr_usm_sharp's tmp3: [row pass | blur | soft]
     const float* soft = saved + 2 * count;

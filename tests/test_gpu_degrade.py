@@ -40,7 +40,8 @@ def test_usm_and_filter2d_vs_reference_golden(ip):
         ip.filter2d_torch(x, torch.ones(1, 4, 4).cuda())
 
 
-@pytest.mark.parametrize("shape", [(2, 3, 72, 64), (1, 3, 400, 400), (3, 1, 31, 97), (1, 3, 26, 26), (2, 3, 130, 67)])
+@pytest.mark.parametrize("shape", [(2, 3, 72, 64), (1, 3, 400, 400), (3, 1, 31, 97), (1, 3, 26, 26), (2, 3, 130, 67),
+                                   (1, 1, 1000, 70), (1, 1, 500, 30), (1, 2, 70, 130)])   # 8 segments x 2 strips; 4 segments, a strip narrower than 64; 3 strips
 def test_usm_two_launches_equal_six_passes(ip, shape):
     """USMSharp(50, 0).forward as two fused launches (blur + byte mask; soft mask + combine, csrc/degrade.hip usm51_kernel) against
     the six separate passes (RESR_USM_SIX_PASSES=1): same taps in the same order -> the same values to an ulp, output AND the tensors
