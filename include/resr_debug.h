@@ -66,6 +66,27 @@ int resr_debug_fold4x4_batch(int32_t n, const float* const* dw3, float* const* d
 int resr_debug_nchw_to_nhwc(const float* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t unshuffle, int32_t c_pad,
                             int32_t dtype, const uint8_t* mask, const void* amax, void* stream);
 
+/* Test entries (tests/test_gpu_layout_kernels.py) of the layout kernels as the generator's passes call them (csrc/layout.hip): the
+ * dispatch functions with every argument visible.  Offsets count elements of the tensor's type from the hi tensor; a negative lo offset
+ * means "directly behind the hi tensor", the default of the entries of resr.h; 0 where the dtype is not RESR_F16X2.
+ * resr_debug_absmax: slot[0] = the bits of m = max |src[i]| * 2^-target_log2 (|target_log2| <= 64; a NaN beats every number), after
+ *   the sticky back-off (csrc/common.h, grad_prescale): slot[1] = b (clamped to 40, raised by 4 and slot[2] cleared when slot[2] != 0),
+ *   and a normal m leaves times 2^b, its exponent clamped below infinity.  slot: three 32-bit words of device memory.
+ * resr_debug_add_inplace: dst += src over `count` elements (a multiple of 16 bytes' worth); RESR_F16X2 needs both lo offsets > 0.
+ * resr_debug_nchw_to_nhwc_q: resr_debug_nchw_to_nhwc with the lo offset named and, q_off != 0 (RESR_F16X2, c_pad % 32 == 0), the q
+ *   tensor of ResrConvDesc written q_off elements behind dst.
+ * resr_debug_nhwc_to_nchw: resr_nhwc_to_nchw with the lo offset named; amax != NULL: the result leaves times 2^floor(log2 m), the
+ *   inverse of what resr_debug_nchw_to_nhwc applied for the same slot.
+ * resr_debug_sumpool2x2: resr_sumpool2x2 with the lo offsets of src and of dst (and mask) named: one plane of a larger tensor. */
+int resr_debug_absmax(const float* src, int64_t count, void* slot, int32_t target_log2, void* stream);
+int resr_debug_add_inplace(void* dst, const void* src, int64_t count, int32_t dtype, int64_t dst_lo, int64_t src_lo, void* stream);
+int resr_debug_nchw_to_nhwc_q(const float* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t unshuffle, int32_t c_pad,
+                              int32_t dtype, const uint8_t* mask, int64_t lo_off, const void* amax, int64_t q_off, void* stream);
+int resr_debug_nhwc_to_nchw(const void* src, float* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t shuffle, int32_t src_stride,
+                            int32_t dtype, int64_t lo_off, const void* amax, void* stream);
+int resr_debug_sumpool2x2(const void* src, void* dst, const void* mask, int32_t n, int32_t h_out, int32_t w_out, int32_t c, int32_t dtype,
+                          float slope, int64_t src_lo, int64_t dst_lo, void* stream);
+
 /* Test entry (tests/test_gpu_kernels.py) of the compact generator's body pass, which the product reaches only from inside
  * resr_compact_forward*: resr_conv3x3 on one input tensor with a plain epilogue (flags: RESR_CONV_NO_BIAS or 0; NHWC output of one
  * output group) followed by per-output-channel PReLU, v = v > 0 ? v : prelu[co] * v, `prelu` = d->cout floats.  bias may be NULL. */

@@ -541,6 +541,37 @@ int resr_debug_nchw_to_nhwc(const float* src, void* dst, int32_t n, int32_t c, i
     return nchw_to_nhwc_scaled_dispatch(src, dst, n, c, h, w, unshuffle, c_pad, dtype, mask, (hipStream_t)stream, -1L, (const unsigned*)amax);
 }
 
+// test entries of the layout kernels as the generator's passes call them (tests/test_gpu_layout_kernels.py): every argument of the
+// dispatch function visible, nothing decided here
+int resr_debug_absmax(const float* src, int64_t count, void* slot, int32_t target_log2, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return absmax_dispatch(src, (long)count, (unsigned*)slot, target_log2, (hipStream_t)stream);
+}
+
+int resr_debug_add_inplace(void* dst, const void* src, int64_t count, int32_t dtype, int64_t dst_lo, int64_t src_lo, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return add_inplace_dispatch(dst, src, (long)count, dtype, (hipStream_t)stream, (long)dst_lo, (long)src_lo);
+}
+
+int resr_debug_nchw_to_nhwc_q(const float* src, void* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t unshuffle, int32_t c_pad,
+                              int32_t dtype, const uint8_t* mask, int64_t lo_off, const void* amax, int64_t q_off, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return nchw_to_nhwc_q_dispatch(src, dst, n, c, h, w, unshuffle, c_pad, dtype, mask, (hipStream_t)stream, (long)lo_off, (const unsigned*)amax,
+                                   (long)q_off);
+}
+
+int resr_debug_nhwc_to_nchw(const void* src, float* dst, int32_t n, int32_t c, int32_t h, int32_t w, int32_t shuffle, int32_t src_stride,
+                            int32_t dtype, int64_t lo_off, const void* amax, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return nhwc_to_nchw_scaled_dispatch(src, dst, n, c, h, w, shuffle, src_stride, dtype, (hipStream_t)stream, (long)lo_off, (const unsigned*)amax);
+}
+
+int resr_debug_sumpool2x2(const void* src, void* dst, const void* mask, int32_t n, int32_t h_out, int32_t w_out, int32_t c, int32_t dtype,
+                          float slope, int64_t src_lo, int64_t dst_lo, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return sumpool2x2_dispatch(src, dst, mask, n, h_out, w_out, c, dtype, slope, (hipStream_t)stream, (long)src_lo, (long)dst_lo);
+}
+
 // test entry of the compact generator's PReLU pass (tests/test_gpu_kernels.py): the dispatch function compact.hip calls, alone
 int resr_debug_conv3x3_prelu(const ResrConvDesc* d, const void* in0, const void* w_packed, const float* bias, const float* prelu,
                              void* out, void* stream) {

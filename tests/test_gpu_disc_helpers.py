@@ -22,14 +22,10 @@ import pytest
 import torch
 
 from tests import disc_helpers_ref as ref
+from tests.gpu_util import GUARD, INT, SENT, TINT, TORCH, Operand, Out, dev, np_type
 
 pytestmark = pytest.mark.gpu
 
-GUARD = 64
-SENT = {np.dtype(np.float16): 0x7E5A, np.dtype(np.float32): 0x7FC5A5A5, np.dtype(np.uint8): 0xA5}   # NaN payloads no kernel produces
-INT = {np.dtype(np.float16): np.int16, np.dtype(np.float32): np.int32, np.dtype(np.uint8): np.uint8}
-TORCH = {np.dtype(np.float16): torch.float16, np.dtype(np.float32): torch.float32, np.dtype(np.uint8): torch.uint8}
-TINT = {np.dtype(np.float16): torch.int16, np.dtype(np.float32): torch.int32, np.dtype(np.uint8): torch.uint8}
 SLOPE = float(np.float32(0.2))
 DIAG = {}
 
@@ -65,69 +61,7 @@ def E_of(L, dtype):
     return 4 if dtype == L.RESR_F32 else 8
 
 
-def np_type(L, dtype):
-    return np.dtype(np.float32 if dtype == L.RESR_F32 else np.float16)
-
-
 # ---- device buffers --------------------------------------------------------------------------------------------------------------
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-class Out:
-    """`count` elements of `np_dtype` between two guards, everything pre-filled with the sentinel."""
-
-    def __init__(self, count, np_dtype):
-        self.dt, self.count = np.dtype(np_dtype), int(count)
-        self.t = torch.empty(self.count + 2 * GUARD, dtype=TORCH[self.dt], device="cuda")
-        self.t.view(TINT[self.dt]).fill_(self._sent())
-        self.ptr = self.t.data_ptr() + GUARD * self.dt.itemsize
-
-    def _sent(self):
-        s = SENT[self.dt]
-        return int(np.array(s, dtype=np.uint32).astype(INT[self.dt])) if self.dt != np.uint8 else s
-
-    def load(self, a):
-        a = np.ascontiguousarray(a).reshape(-1)
-        assert a.dtype == self.dt and a.size == self.count
-        self.t[GUARD:GUARD + self.count] = dev(a)
-        return self
-
-    def read(self, written=True):
-        torch.cuda.synchronize()
-        a = self.t.cpu().numpy()
-        i = a.view(INT[self.dt])
-        assert (i[:GUARD] == self._sent()).all(), "the guard in front of the output was written"
-        assert (i[GUARD + self.count:] == self._sent()).all(), "the guard behind the output was written"
-        body = a[GUARD:GUARD + self.count].copy()
-        if written:
-            missed = np.flatnonzero(body.view(INT[self.dt]) == self._sent())
-            assert missed.size == 0, f"{missed.size} elements in range never written, first at {missed[0]}"
-        return body
-
-
-class Operand:
-    """An input tensor as the kernel sees it.  exact: the float64 value of every element; v32: what the kernel loads (fp32; for a
-    pair the single rounding of exact); flat: the stored elements (pair: hi tensor, then lo tensor directly behind)."""
-
-    def __init__(self, L, dtype, base=None, hi=None, lo=None):
-        if dtype == L.RESR_F16X2:
-            if hi is None:
-                hi, lo = ref.pair_split(np.asarray(base, dtype=np.float32).astype(np.float64))
-            self.hi, self.lo = np.asarray(hi, dtype=np.float16), np.asarray(lo, dtype=np.float16)
-            self.exact = ref.pair_join(self.hi, self.lo)
-            self.flat = np.concatenate([self.hi.reshape(-1), self.lo.reshape(-1)])
-        else:
-            q = np.asarray(base, dtype=np.float32).astype(np_type(L, dtype))
-            self.hi, self.lo = q, None
-            self.exact = q.astype(np.float64)
-            self.flat = q.reshape(-1)
-        self.v32 = self.exact.astype(np.float32)
-        self.shape = self.exact.shape
-        self.t = dev(self.flat)
-        self.ptr = self.t.data_ptr()
-
-
 def store(L, dtype, v32):
     """One rounding of fp32 results to the stored form (flat; pair: hi then lo).  v - hi and its scaling by 4096 are exact in fp32."""
     v32 = np.asarray(v32, dtype=np.float32)
