@@ -391,7 +391,8 @@ int resr_generator_backward(const ResrGeneratorDesc* d, const float* gy_nchw, co
                             float* grad_params, float* gx_nchw, void* stream,
                             void* const* grad_ready_events, int32_t n_events);
 
-/* Compact generator (upstream Real-ESRGAN's SRVGGNetCompact: realesr-animevideov3, realesr-general-x4v3), forward only.
+/* Compact generator (upstream Real-ESRGAN's SRVGGNetCompact: realesr-animevideov3, realesr-general-x4v3): the inference entries
+ * below, and "Compact generator: training" behind them.
  * x [N,3,H,W] -> conv 3->64, act, num_conv x (conv 64->64, act), conv 64->3*s*s, pixel-shuffle(s), + nearest-upsampled x
  * -> y [N,3,sH,sW] fp32 NCHW, no clamp.  Any H, W >= 1 (no padding beyond each conv's own).  Parameters in the upstream
  * module's named_parameters() order: per conv k = 0 .. num_conv + 1 its weight [cout,cin,3,3] and bias [cout], and behind
@@ -418,6 +419,36 @@ size_t resr_compact_workspace_bytes(const ResrCompactDesc* d);
 /* Enqueues the whole network on `stream`: no allocation, no synchronisation, graph-capture safe (as resr_generator_forward). */
 int resr_compact_forward(const ResrCompactDesc* d, const float* x_nchw, const float* params, const void* packed,
                          void* workspace, size_t workspace_bytes, float* y_nchw, void* stream);
+
+/* Compact generator: training (csrc/compact.hip, compact_train.hip).  Same descriptor, RESR_F16 (fast) or RESR_F32 (strict);
+ * RESR_F16X2 is refused by every entry below (0 / RESR_ERR_ARG: exact16 training is not built).
+ * resr_compact_forward_train: resr_compact_forward's ends and result (strict: the same bits; fast: a negative activation is rounded
+ *   twice, f16(slope * f16(z))), with every body convolution run on a plain (bias) epilogue that stores the pre-activation z_k and one
+ *   element-wise launch that stores a_k = act(z_k); both stay in the workspace for the backward pass.
+ * resr_compact_backward: gy_nchw [N,3,sH,sW] -> grad_params (the layout of the parameter arena, resr_compact_param_count floats,
+ *   OVERWRITTEN) and, gx_nchw != NULL, gx_nchw [N,3,H,W].  It reads what the forward train call left in the SAME workspace, and the same
+ *   packed buffer.  RESR_F16 lifts a small gy into f16's normal range and hands every result back unscaled, exactly as
+ *   resr_generator_backward does (the pre-scale slot and its sticky back-off); RESR_F32 gets no lift.  No floating-point atomics: the
+ *   same inputs give the same bits.
+ * Packed weights: resr_compact_train_pack_table is resr_compact_pack_table's chunks followed by every convolution's transposed
+ *   (backward-data) chunks in the same order; resr_compact_train_packed_bytes sizes the buffer.
+ * Workspace (every buffer 256-byte aligned; es = 2 or 4 bytes, px = N H W, cpl = 3 s^2 rounded up to 32):
+ *     256                          the gradient pre-scale slot: resr_compact_train_state_bytes, zero-filled ONCE by the caller
+ *   + px * 32 * es                 the input as NHWC
+ *   + 2 * (num_conv + 1) * px * 64 * es     z_k and a_k of every activation layer
+ *   + px * 3 s^2 * 4               the last convolution's fp32 output
+ *   + px * (cpl + 2 * 64 + 32) * es         the gradients g_t, two ping-pong 64-channel tensors, the input gradient
+ *   + the slope-gradient partials (PReLU: at most 1024 * 256 bytes) + the weight-gradient slabs of the largest layer.
+ * Refusals come before the first launch: RESR_ERR_ARG (a bad descriptor, RESR_F16X2, a null pointer other than gx_nchw),
+ * RESR_ERR_WORKSPACE (workspace_bytes below resr_compact_train_workspace_bytes).  Both calls only enqueue. */
+size_t resr_compact_train_packed_bytes(const ResrCompactDesc* d);
+int64_t resr_compact_train_pack_table(const ResrCompactDesc* d, ResrPackChunk* chunks, int64_t capacity);
+size_t resr_compact_train_workspace_bytes(const ResrCompactDesc* d);
+size_t resr_compact_train_state_bytes(const ResrCompactDesc* d);
+int resr_compact_forward_train(const ResrCompactDesc* d, const float* x_nchw, const float* params, const void* packed,
+                               void* workspace, size_t workspace_bytes, float* y_nchw, void* stream);
+int resr_compact_backward(const ResrCompactDesc* d, const float* gy_nchw, const float* params, const void* packed,
+                          void* workspace, size_t workspace_bytes, float* grad_params, float* gx_nchw, void* stream);
 
 /* The uint8 frame path (real_esrgan-pytorch_amd/csrc/frames.hip).  Images are uint8 HWC, contiguous: x_u8 [N,H,W,3] ->
  * y_u8 [N,sH,sW,3].  The result is defined as what the float path followed by the host's truncating uint8 conversion gives,

@@ -93,6 +93,21 @@ int resr_debug_sumpool2x2(const void* src, void* dst, const void* mask, int32_t 
 int resr_debug_conv3x3_prelu(const ResrConvDesc* d, const void* in0, const void* w_packed, const float* bias, const float* prelu,
                              void* out, void* stream);
 
+/* Test entries (tests/test_gpu_compact_train_kernels.py) of the three kernels of the compact generator's training pass, which the
+ * product reaches only from inside resr_compact_forward_train / resr_compact_backward (csrc/compact_train.hip).  z, a, g, gz:
+ * [pixels][64] NHWC tensors of `dtype` (RESR_F16 or RESR_F32), 16-byte aligned; slopes: 64 floats on the device.
+ * resr_debug_compact_act: a = z > 0 ? z : slopes[c] * z, evaluated in fp32 and rounded once to the dtype.
+ * resr_debug_compact_act_bwd: gz = g * (z > 0 ? 1 : slopes[c]), the same way; gz may be g.  dslope != NULL: also the 64 sums
+ *   dslope[c] = sum_pixels g * (z > 0 ? 0 : z) in fp32, in a fixed order (the same bits run to run), through `partial`: at least
+ *   min(1024, ceil(pixels * (dtype == RESR_F32 ? 16 : 8) / 256)) * 256 bytes of device scratch (else RESR_ERR_WORKSPACE); amax != NULL:
+ *   they leave times 2^floor(log2 m) for the float m whose bits the slot holds, as resr_debug_nhwc_to_nchw's results do.
+ * resr_debug_compact_residual_bwd: gx[n,c,y,x] += sum_{i,j < s} gy[n,c,s y + i,s x + j] for gy [n,3,h s,w s] fp32, s = 1..4: the adjoint
+ *   of the nearest-upsampled residual, summed over (i, j) in this order and ADDED (one fp32 add) to what gx [n,3,h,w] holds. */
+int resr_debug_compact_act(const void* z, void* a, const float* slopes, int64_t pixels, int32_t dtype, void* stream);
+int resr_debug_compact_act_bwd(const void* g, const void* z, void* gz, const float* slopes, int64_t pixels, int32_t dtype, float* dslope,
+                               float* partial, size_t partial_bytes, const void* amax, void* stream);
+int resr_debug_compact_residual_bwd(const float* gy, float* gx, int32_t n, int32_t h, int32_t w, int32_t s, void* stream);
+
 /* What THIS board sustains once it sits at its power cap (bench.py's `roofline.vs_sustained`): 256 workgroups launched back to
  * back for `seconds` (last third timed) -- mode 1: an LDS-DMA stream over `src` (`bytes` >= 64 MB of readable device memory),
  * mode 2: eight waves per workgroup issuing v_mfma_f32_32x32x16_f16 on random f16 operands, mode 3: both at once.  Returns the

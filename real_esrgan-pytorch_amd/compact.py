@@ -1,10 +1,16 @@
 """The compact generator of upstream Real-ESRGAN (`SRVGGNetCompact`: the realesr-animevideov3 and realesr-general-x4v3
-models) on the MI355X conv kernels, forward only.
+models) on the MI355X conv kernels: inference by default, trainable on request.
 
 Same constructor, module tree and state_dict keys as upstream (`body` = ModuleList of conv / activation, `upsampler` =
 PixelShuffle), so an official `.pth` loads with a plain `load_state_dict` (or `model.load_official_state_dict`).  `forward` is
 one C-ABI call, `resr_compact_forward` (include/resr.h, csrc/compact.hip): conv 3->64 + act, num_conv x (conv 64->64 + act),
-conv 64->3*s*s, pixel-shuffle, + the nearest-upsampled input.  There is no PyTorch / CPU fallback and no backward pass.
+conv 64->3*s*s, pixel-shuffle, + the nearest-upsampled input.  There is no PyTorch / CPU fallback.
+
+`SRVGGNetCompact(..., trainable=True)` ("fast" or "strict") adds the native backward pass: a forward with grad enabled and an
+input or parameter that requires grad runs `resr_compact_forward_train` -- the same convolutions on a plain epilogue, every
+pre-activation and activation kept in a workspace the graph owns -- and its backward `resr_compact_backward` (csrc/compact.hip,
+compact_train.hip; DESIGN, "Compact generator: training").  Every other call, and every call of a model built without the flag,
+takes the inference path below unchanged; without the flag a forward that would need a graph raises.
 
 Every forward checks its own input, allocates its own result and goes through one call path (`_call`).
 
@@ -37,17 +43,43 @@ __all__ = ["SRVGGNetCompact"]
 _ACTS = {"prelu": _lib.COMPACT_PRELU, "leakyrelu": _lib.COMPACT_LRELU, "relu": _lib.COMPACT_RELU}
 
 
+class _CompactFn(torch.autograd.Function):
+    """One training graph of a trainable SRVGGNetCompact: forward saves into a workspace of its own, backward reads it."""
+
+    @staticmethod
+    def forward(ctx, module: "SRVGGNetCompact", x: torch.Tensor, *params: torch.Tensor):
+        y, desc, ws, packed = module._run_forward_train(x)
+        ctx.module, ctx.desc, ctx.ws, ctx.packed = module, desc, ws, packed
+        ctx.x_dtype = x.dtype
+        ctx._token = _arena.GraphToken(ws)   # the workspace is this graph's until its backward has run or the graph is dropped
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: torch.Tensor):
+        if not ctx._token.open:
+            raise RuntimeError("SRVGGNetCompact: this graph's backward has run already and its workspace was given back "
+                               "(run the forward again; retain_graph is not supported on the native pass)")
+        grads, gx = ctx.module._run_backward(ctx.desc, ctx.ws, ctx.packed, gy.contiguous().float(), ctx.needs_input_grad[1],
+                                             ctx.needs_input_grad[2:])
+        ctx._token.finish()
+        return (None, gx if gx is None else gx.to(ctx.x_dtype)) + tuple(grads)
+
+
 class SRVGGNetCompact(nn.Module):
     """SRVGGNetCompact(num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type="prelu") as upstream.
 
     Keyword `precision`: "fast" (f16 MFMA), "exact16" (split-operand f16 pairs, three stages per chunk, fp32-class results) or
     "strict" (f32 MFMA); default $RESR_PRECISION, else "fast" -- the rule of `Generator`.
-    forward(x [N,3,H,W] float, NCHW or channels_last, any H, W >= 1) -> [N,3,sH,sW] fp32 NCHW, not clamped.  Forward only:
-    a call with grad enabled and an input or parameter that requires grad raises (wrap inference in torch.no_grad()).
+    forward(x [N,3,H,W] float, NCHW or channels_last, any H, W >= 1) -> [N,3,sH,sW] fp32 NCHW, not clamped.
+    Keyword `trainable` (default False): False = forward only -- a call with grad enabled and an input or parameter that requires
+    grad raises (wrap inference in torch.no_grad()).  True ("fast" or "strict"; "exact16" is a ValueError): such a call of `forward`
+    is differentiable -- gradients of every parameter that requires grad and of x, each backward handing autograd views of a fresh
+    flat fp32 tensor (plain accumulation into `.grad`); fast mode's gradients do not depend on the caller's loss scale (the lift of
+    `Generator`).  Calls that need no graph, and the frame entries (which keep raising under grad mode), are the inference path.
     """
 
     def __init__(self, num_in_ch: int = 3, num_out_ch: int = 3, num_feat: int = 64, num_conv: int = 16, upscale: int = 4,
-                 act_type: str = "prelu", precision: Optional[str] = None) -> None:
+                 act_type: str = "prelu", precision: Optional[str] = None, trainable: bool = False) -> None:
         super().__init__()
         if num_in_ch != 3 or num_out_ch != 3:
             raise ValueError(f"SRVGGNetCompact: num_in_ch = num_out_ch = 3 on this path, got {num_in_ch}, {num_out_ch}")
@@ -63,6 +95,9 @@ class SRVGGNetCompact(nn.Module):
         self.num_conv, self.upscale, self.act_type = num_conv, upscale, act_type
         self.precision = precision or os.environ.get("RESR_PRECISION", "fast")
         self._dtype = _precision_to_dtype(self.precision)
+        self.trainable = bool(trainable)
+        if self.trainable and self._dtype == _lib.RESR_F16X2:
+            raise ValueError("SRVGGNetCompact: trainable=True takes precision 'fast' or 'strict' (exact16 training is not built)")
 
         # upstream's module tree (same construction order, hence the same init under the same seed)
         self.body = nn.ModuleList()
@@ -78,6 +113,10 @@ class SRVGGNetCompact(nn.Module):
         self._packed: Optional[torch.Tensor] = None
         self._table_dev: Optional[tuple] = None
         self._workspaces: Dict[tuple, torch.Tensor] = {}
+        # training graphs (trainable=True): the packing with the transposed chunks, and pooled workspaces a live graph owns
+        self._packed_train: Optional[torch.Tensor] = None
+        self._table_train: Optional[tuple] = None
+        self._train_workspaces: Dict[tuple, List[_arena.Workspace]] = {}
 
     def _activation(self, num_feat: int) -> nn.Module:
         if self.act_type == "prelu":
@@ -114,6 +153,9 @@ class SRVGGNetCompact(nn.Module):
             self._packed = None
             self._table_dev = None
             self._workspaces.clear()
+            self._packed_train = None
+            self._table_train = None
+            self._train_workspaces.clear()
         return self._flat
 
     # ---- C-ABI plumbing ---------------------------------------------------------------------------------------------------
@@ -163,11 +205,61 @@ class SRVGGNetCompact(nn.Module):
                                               ws.numel(), _lib.ptr(y), *extra, _lib.stream_ptr(src)), entry)
         return y
 
+    # ---- training graphs (trainable=True) ---------------------------------------------------------------------------------
+    def _run_forward_train(self, x: torch.Tensor):
+        """resr_compact_forward_train on a workspace no live graph holds: (y, descriptor, workspace, packed buffer).  The packed
+        buffer is the module's, as `Generator`'s: graphs that are live together share it, so their backward passes read the weights
+        of the latest forward (the same ones, unless an optimizer stepped between a forward and its backward)."""
+        L = _lib.lib()
+        flat = self.flat_parameters()
+        _lib.require_cuda(flat, "SRVGGNetCompact parameters")
+        xc = x.detach().float().contiguous()
+        n, _, h, w = xc.shape
+        desc = self._desc(n, h, w)
+        if self._table_train is None or self._table_train[0].device != flat.device:
+            host = _lib.fetch_pack_table(lambda out, cap: L.resr_compact_train_pack_table(C.byref(desc), out, cap), "resr_compact_train_pack_table")
+            self._table_train = (_lib.upload_chunks(host, flat.device), len(host))
+        nbytes = L.resr_compact_train_packed_bytes(C.byref(desc))
+        if self._packed_train is None or self._packed_train.numel() < nbytes or self._packed_train.device != flat.device:
+            self._packed_train = torch.zeros(nbytes, dtype=torch.uint8, device=flat.device)
+        raw, nchunks = self._table_train     # one pack launch per forward; the backward reads the same buffer
+        _lib.check(L.resr_pack_weights(_lib.ptr(raw), nchunks, _lib.ptr(flat), _lib.ptr(self._packed_train), self._dtype,
+                                       _lib.stream_ptr(flat)), "resr_pack_weights")
+
+        def make() -> _arena.Workspace:
+            nb = L.resr_compact_train_workspace_bytes(C.byref(desc))
+            if nb == 0:
+                raise RuntimeError(f"resr_compact_train_workspace_bytes: unsupported shape {n}x{h}x{w} ({(L.resr_last_error() or b'').decode()})")
+            return _arena.Workspace(nb, xc.device, int(L.resr_compact_train_state_bytes(C.byref(desc))))   # the pre-scale slot: zero once
+        ws = _arena.take(self._train_workspaces, (n, h, w, desc.dtype), xc.device, make)
+        s = self.upscale
+        y = torch.empty((n, self.num_out_ch, h * s, w * s), dtype=torch.float32, device=xc.device)
+        _lib.check(L.resr_compact_forward_train(C.byref(desc), _lib.ptr(xc), _lib.ptr(flat), _lib.ptr(self._packed_train), _lib.ptr(ws.buf),
+                                                ws.buf.numel(), _lib.ptr(y), _lib.stream_ptr(xc)), "resr_compact_forward_train")
+        return y, desc, ws, self._packed_train
+
+    def _run_backward(self, desc, ws: _arena.Workspace, packed: torch.Tensor, gy: torch.Tensor, need_gx: bool, need_params):
+        """resr_compact_backward into a fresh flat gradient tensor: per-parameter views of it (None where not needed), gx or None."""
+        flat = self.flat_parameters()
+        grad = torch.empty_like(flat)
+        gx = torch.empty((desc.n, self.num_in_ch, desc.h, desc.w), dtype=torch.float32, device=gy.device) if need_gx else None
+        _lib.check(_lib.lib().resr_compact_backward(C.byref(desc), _lib.ptr(gy), _lib.ptr(flat), _lib.ptr(packed), _lib.ptr(ws.buf),
+                                                    ws.buf.numel(), _lib.ptr(grad), _lib.ptr(gx), _lib.stream_ptr(gy)), "resr_compact_backward")
+        views = _arena.views(grad, self.named_parameters()).values()
+        return [g if need else None for g, need in zip(views, need_params)], gx
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        self._guard(x)
+        # grad mode is off inside autograd.Function.forward: whether this call builds a graph is decided here
+        params = self._ordered_params()
+        training = self.trainable and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
+        if not training:
+            self._guard(x)
         _lib.require_cuda(x, "SRVGGNetCompact.forward")
         if x.dim() != 4 or x.shape[1] != self.num_in_ch:
             raise RuntimeError(f"SRVGGNetCompact: expected an [N,{self.num_in_ch},H,W] input, got {tuple(x.shape)}")
+        if training:
+            self.flat_parameters()   # (the parameters handed to the graph are the arena's views)
+            return _CompactFn.apply(self, x, *params)
         xc = x.detach().float().contiguous()   # also normalises channels_last strides
         n, _, h, w = xc.shape
         s = self.upscale

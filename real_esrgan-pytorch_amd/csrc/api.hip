@@ -208,6 +208,23 @@ int resr_compact_forward(const ResrCompactDesc* d, const float* x_nchw, const fl
                                 "compact_forward");
 }
 
+size_t resr_compact_train_packed_bytes(const ResrCompactDesc* d) { return compact_train_packed_bytes(d); }
+int64_t resr_compact_train_pack_table(const ResrCompactDesc* d, ResrPackChunk* chunks, int64_t capacity) { return compact_train_pack_table(d, chunks, capacity); }
+size_t resr_compact_train_workspace_bytes(const ResrCompactDesc* d) { return compact_train_workspace_bytes(d); }
+size_t resr_compact_train_state_bytes(const ResrCompactDesc* d) { return compact_train_state_bytes(d); }
+
+int resr_compact_forward_train(const ResrCompactDesc* d, const float* x_nchw, const float* params, const void* packed,
+                               void* workspace, size_t workspace_bytes, float* y_nchw, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_train(d, x_nchw, params, packed, workspace, workspace_bytes, y_nchw, (hipStream_t)stream);
+}
+
+int resr_compact_backward(const ResrCompactDesc* d, const float* gy_nchw, const float* params, const void* packed,
+                          void* workspace, size_t workspace_bytes, float* grad_params, float* gx_nchw, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_backward(d, gy_nchw, params, packed, workspace, workspace_bytes, grad_params, gx_nchw, (hipStream_t)stream);
+}
+
 int resr_compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
                             void* workspace, size_t workspace_bytes, uint8_t* y_u8, void* stream) {
     RESR_DEVICE_SCOPE(stream);
@@ -578,6 +595,23 @@ int resr_debug_conv3x3_prelu(const ResrConvDesc* d, const void* in0, const void*
     RESR_DEVICE_SCOPE(stream);
     if (!d) return fail(RESR_ERR_ARG, "resr_debug_conv3x3_prelu: null descriptor");
     return conv3x3_dispatch_prelu(d, in0, w_packed, bias, prelu, out, (hipStream_t)stream);
+}
+
+// test entries of the compact generator's training kernels (tests/test_gpu_compact_train_kernels.py): the dispatch functions compact.hip calls, alone
+int resr_debug_compact_act(const void* z, void* a, const float* slopes, int64_t pixels, int32_t dtype, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_act_dispatch(z, a, slopes, pixels, dtype, (hipStream_t)stream);
+}
+
+int resr_debug_compact_act_bwd(const void* g, const void* z, void* gz, const float* slopes, int64_t pixels, int32_t dtype, float* dslope,
+                               float* partial, size_t partial_bytes, const void* amax, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_act_bwd_dispatch(g, z, gz, slopes, pixels, dtype, dslope, partial, partial_bytes, (const unsigned*)amax, (hipStream_t)stream);
+}
+
+int resr_debug_compact_residual_bwd(const float* gy, float* gx, int32_t n, int32_t h, int32_t w, int32_t s, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_residual_bwd_dispatch(gy, gx, n, h, w, s, (hipStream_t)stream);
 }
 
 int resr_debug_spectral_norm_batch(int32_t n, const float* const* w, float* const* u, float* const* v, const int32_t* rows,

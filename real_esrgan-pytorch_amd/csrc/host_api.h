@@ -74,6 +74,22 @@ size_t compact_packed_bytes(const ResrCompactDesc* d);
 size_t compact_workspace_bytes(const ResrCompactDesc* d);
 int64_t compact_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t cap);
 int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* params, const void* packed, void* workspace, size_t workspace_bytes, hipStream_t st, const char* who);
+// training (fast / strict): the saved-activation forward and the backward pass; grad: the gradient arena (overwritten); gx: null = not wanted
+size_t compact_train_packed_bytes(const ResrCompactDesc* d);
+int64_t compact_train_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t cap);
+size_t compact_train_workspace_bytes(const ResrCompactDesc* d);
+size_t compact_train_state_bytes(const ResrCompactDesc* d);
+int compact_forward_train(const ResrCompactDesc* d, const float* x, const float* params, const void* packed, void* workspace, size_t workspace_bytes, float* y, hipStream_t st);
+int compact_backward(const ResrCompactDesc* d, const float* gy, const float* params, const void* packed, void* workspace, size_t workspace_bytes, float* grad, float* gx, hipStream_t st);
+// ---- compact_train.hip: the element-wise kernels of that pass on [pixels][64] NHWC tensors (RESR_F16 / RESR_F32).  slopes: 64 floats on the
+// device (compact_const_slopes: the table of RESR_COMPACT_LRELU / _RELU); dslope: the 64 slope gradients or null; partial: compact_dslope_partial_bytes
+// of scratch for them; amax: the pre-scale slot they leave through, or null; residual_bwd: gx [n,3,h,w] += the s x s sums of gy [n,3,hs,ws] ----
+const float* compact_const_slopes(int act);
+int compact_act_dispatch(const void* z, void* a, const float* slopes, int64_t pixels, int dtype, hipStream_t st);
+size_t compact_dslope_partial_bytes(int64_t pixels, int dtype);
+int compact_act_bwd_dispatch(const void* g, const void* z, void* gz, const float* slopes, int64_t pixels, int dtype, float* dslope, float* partial, size_t partial_bytes, const unsigned* amax,
+                             hipStream_t st);
+int compact_residual_bwd_dispatch(const float* gy, float* gx, int n, int h, int w, int s, hipStream_t st);
 // ---- frames.hip: the uint8 / YUV 4:2:0 ends of the compact generator.  t: the last convolution's output [n,3s^2,h,w] fp32; x: the source frames
 // (the residual); s: upscale factor; q / qs / qd: what the (source / destination) frames are, null = RGB bytes; bits: 8, 10 or 0 (Ends::bits_expected) ----
 int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q);
