@@ -619,6 +619,38 @@ int resr_compact_forward_yuv420_mixed_scaled(const ResrCompactDesc* d, const voi
                                              int32_t ow, const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x,
                                              const float* w_x, int32_t taps_x, const ResrYuvDesc* dst_yuv, void* stream);
 
+/* Image modes (frames.hip): the still images upstream's RealESRGANer.enhance takes besides 8-bit RGB -- grey, RGBA and 16 bits per
+ * channel.  An image batch is [N,H,W,C] of bytes (bits = 8, top = 255) or of little-endian 16-bit words (bits = 16, top = 65535), HWC,
+ * contiguous; C = 1 grey, 3 RGB, 4 RGBA.  planes = 2 for RGBA, else 1: the network runs on planes * N three-channel images,
+ *   to_rgb:   image b < N  is the colour of image b (grey: the level three times); image N + b (RGBA only) is the alpha plane of image b
+ *             three times -- upstream's alpha_upsampler = "realesrgan": alpha goes through the network as a grey image;
+ *   grey(r, g, b) = (4899 r + 9617 g + 1868 b + 8192) >> 14 on integer levels at both depths (cv2's fixed-point RGB2GRAY; the
+ *             coefficients sum to 2^14, so grey(v, v, v) = v, and the sum stays below 2^31 at 65535);
+ *   to_image: RGB the levels themselves; grey: grey of the three levels; RGBA: the colour of image b, and as the fourth channel
+ *             grey of the three levels of image N + b.
+ * DEFINED bit for bit, with q(v) = trunc(clamp(v * top, 0, top)) in fp32 (a NaN gives 0, outside the contract as everywhere):
+ *   resr_compact_forward_image(x) == to_image(q(resr_compact_forward(to_rgb(x) / top)))        (/ top: one IEEE fp32 division)
+ * resr_compact_forward_image: the launch sequence of resr_compact_forward with both conversions inside its first and last kernel;
+ * x [N,H,W,C] -> y [N,sH,sW,C], same channels and depth.  d->n is the NETWORK's batch, planes * N; the descriptor's other fields, the
+ * packed weights and the workspace are resr_compact_forward's (resr_compact_workspace_bytes: nothing more).  The tail re-reads x for
+ * the residual, so x must stay valid until the call has run.  channels = 3, bits = 8 runs the kernels of resr_compact_forward_u8.
+ * resr_image_to_nchw / resr_nchw_to_image: the generic conversions, one launch each, [n_images,H,W,C] <-> fp32 [planes * n_images,3,H,W]
+ * (to_rgb / top, and to_image(q(.))), for every case whose ends are not fused (the RRDB generator, tiled frames).
+ * Alignment, the widest access of each mode (a thread stores a group of output pixels whose bytes are whole dwords, and loads an RGBA
+ * pixel as one word): y / dst 16 bytes for RGBA (either depth), 8 for 16-bit grey, 4 for 8-bit grey and for RGB (either depth);
+ * x / src 4 bytes for 8-bit RGBA, 8 for 16-bit RGBA, 2 for the other 16-bit modes; the float tensor 4 bytes.
+ * RESR_ERR_ARG before any launch, nothing written: a null pointer; channels not 1, 3 or 4; bits not 8 or 16; channels = 4 with an odd
+ * d->n; a pointer not aligned as above; n_images, h, w <= 0 or more threads than a grid holds; a bad descriptor -- with RESR_F16X2 that
+ * includes planes * N * H * W > 2^24, the cap of resr_compact_forward. */
+typedef struct {
+    int32_t channels;         /* 1 grey, 3 RGB, 4 RGBA                                            */
+    int32_t bits;             /* 8 or 16 per channel                                              */
+} ResrImageDesc;
+int resr_compact_forward_image(const ResrCompactDesc* d, const void* x, const float* params, const void* packed, void* workspace,
+                               size_t workspace_bytes, void* y, const ResrImageDesc* img, void* stream);
+int resr_image_to_nchw(const void* src, float* dst_f32, int32_t n_images, int32_t h, int32_t w, const ResrImageDesc* img, void* stream);
+int resr_nchw_to_image(const float* src_f32, void* dst, int32_t n_images, int32_t h, int32_t w, const ResrImageDesc* img, void* stream);
+
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */
 

@@ -25,6 +25,10 @@ of frames.py fused into the same two kernels, so its result equals `rgb_to_yuv42
 `_yuv420p10_scaled`, csrc/image_resize.hip): the resized tail with a YUV 4:2:0 output stage, still one launch sequence.
 `forward_yuv420_mixed` is the sequence with a source and a destination format of their own (`resr_compact_forward_yuv420_mixed`, `_scaled`):
 8 bits in and 10 out, NV12 / P010 in and planar out, BT.601 in and BT.709 out -- the head reads the source, the tail writes the destination.
+
+`forward_image` is the sequence for grey, RGB and RGBA images of 8 or 16 bits (`resr_compact_forward_image`): the network runs on the
+colour (or replicated grey) images and, for RGBA, on the alpha planes as grey images behind them; the head reads the image's own
+words and the tail writes them, grey and alpha through the fixed-point grey of their three levels (frames.py, IMAGE MODES).
 """
 from __future__ import annotations
 
@@ -388,6 +392,23 @@ class SRVGGNetCompact(nn.Module):
         plan = self._scaled_plan(frames, h, w, o, plan, what)
         y = torch.empty((n, plan.out_h * 3 // 2, plan.out_w), dtype=b.fmt.torch_dtype, device=frames.device)
         return self._call("resr_compact_forward_yuv420_mixed_scaled", frames, n, h, w, y, *plan.args(), C.byref(qb), after_src=(C.byref(qa),))
+
+    def forward_image(self, images: torch.Tensor) -> torch.Tensor:
+        """images: a grey, RGB or RGBA batch -- uint8 or uint16, [N,H,W] or [N,H,W,1], [N,H,W,3], [N,H,W,4] -- on the model's device,
+        contiguous -> the same dtype and trailing shape, [N,sH,sW(,C)].  Bit for bit
+        `frames.rgb_to_image_np(q(self(frames.image_to_rgb_np(images) / top)), channels)` with top = 255 or 65535 and
+        q(v) = trunc(clamp(v * top, 0, top)) in fp32 (frames.py, IMAGE MODES).  `resr_compact_forward_image`: the launch sequence of
+        `forward_u8` on a network batch of planes * N images (RGBA: the N colour images, then the N alpha planes as grey images, as
+        upstream's `alpha_upsampler="realesrgan"`) -- the head reads the image's own words, the tail writes them; no fp32 or RGB
+        copy of either exists on the device.  uint8 RGB runs the kernels of `forward_u8`.  Same guard, packing and workspace caches
+        as `forward`.  No `outscale` here."""
+        from . import frames as _frames
+        self._guard()
+        n, h, w, c = _frames.check_images(images, "SRVGGNetCompact.forward_image")
+        idesc = _frames.image_desc(c, images.dtype)
+        s = self.upscale
+        y = torch.empty((n, h * s, w * s) + tuple(images.shape[3:]), dtype=images.dtype, device=images.device)
+        return self._call("resr_compact_forward_image", images, (2 if c == 4 else 1) * n, h, w, y, C.byref(idesc))
 
     def load_official_state_dict(self, checkpoint) -> None:
         """Upstream's `{"params_ema": sd}` / `{"params": sd}` (params_ema preferred) or a bare state dict (model.load_official_state_dict)."""

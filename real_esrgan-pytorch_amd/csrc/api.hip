@@ -258,6 +258,23 @@ int resr_nchw_to_u8(const float* src_f32, uint8_t* dst_u8, int32_t n, int32_t h,
     return nchw_to_u8_dispatch(src_f32, dst_u8, n, h, w, (hipStream_t)stream);
 }
 
+int resr_compact_forward_image(const ResrCompactDesc* d, const void* x, const float* params, const void* packed, void* workspace,
+                               size_t workspace_bytes, void* y, const ResrImageDesc* img, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_ends(d, {END_IMAGE, false, x, y, {}, nullptr, nullptr, 0, img}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+                                "compact_forward_image");
+}
+
+int resr_image_to_nchw(const void* src, float* dst_f32, int32_t n_images, int32_t h, int32_t w, const ResrImageDesc* img, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return image_to_nchw_dispatch(src, dst_f32, n_images, h, w, img, (hipStream_t)stream);
+}
+
+int resr_nchw_to_image(const float* src_f32, void* dst, int32_t n_images, int32_t h, int32_t w, const ResrImageDesc* img, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return nchw_to_image_dispatch(src_f32, dst, n_images, h, w, img, (hipStream_t)stream);
+}
+
 int resr_compact_forward_yuv420(const ResrCompactDesc* d, const uint8_t* x_yuv, const float* params, const void* packed,
                                 void* workspace, size_t workspace_bytes, uint8_t* y_yuv, const ResrYuvDesc* yuv, void* stream) {
     RESR_DEVICE_SCOPE(stream);

@@ -131,6 +131,7 @@ enum EndFormat {
     END_F32,    // x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32: layout.hip's head, compact_tail
     END_RGB8,   // x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8: frames.hip, the conversions fused into the head and the tail
     END_YUV,    // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames of bytes or 16-bit words (src->layout, dst->layout): the colour conversions too
+    END_IMAGE,  // x [N,H,W,C] -> y [N,sH,sW,C], grey / RGB / RGBA images of bytes or 16-bit words (img): the network's batch is planes * N
 };
 struct Ends {
     EndFormat format;
@@ -142,6 +143,7 @@ struct Ends {
     const ResrYuvDesc* dst;  // END_YUV: what the frames of y are; the same-format entries pass src again
     int bits_expected;       // END_YUV: the depth the entry is for, 8 or 10 (a descriptor of another is refused); 0: the mixed
                              // entries, any depth on either side
+    const ResrImageDesc* img;  // END_IMAGE: channels and bits of x and y, else null
 };
 
 }  // namespace resr

@@ -15,6 +15,10 @@
 //                     levels): frames.hip's head reading YUV, and its YUV tail.  The source and the destination each have their
 //                     own descriptor (Ends::src, Ends::dst): the head and the tail's residual follow the source's depth, layout
 //                     and matrix, the tail's quantisation and stores the destination's; the same-format entries pass one twice;
+//   END_IMAGE         grey, RGB or RGBA images [N,H,W,C] of bytes or 16-bit words (Ends::img): frames.hip's head reading them -- the
+//                     network's batch is the N colour (or grey) images and, for RGBA, the N alpha planes behind them, each level
+//                     three times -- and its image tail (grey: the fixed-point grey of the three levels; RGBA: the alpha images'
+//                     grey as the fourth channel).  No scaled variant;
 //   ... and scaled    ("outscale") image_resize.hip's fused tail in place of either: the HR frame is formed tile by tile in LDS and
 //                     only the resized frame, uint8 [N,oh,ow,3] or YUV 4:2:0 [N,3oh/2,ow], is written.
 // Training (compact_forward_train / compact_backward, at the end of this file; kernels of its own in compact_train.hip): the same
@@ -171,6 +175,7 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
     int rc = RESR_OK;
     // the descriptor and the LR frame; of scaled ends the output pointer's rule is the plan's (nullptr passes the unscaled tail's)
     if (e.format == END_YUV) rc = yuv_forward_check(who, d.n, d.h, d.w, d.upscale, e.scaled ? nullptr : e.y, e.src, e.dst, e.bits_expected);
+    if (e.format == END_IMAGE) rc = e.scaled ? fail(RESR_ERR_ARG, "%s: unknown kind of ends", who) : image_forward_check(who, d.n, d.h, d.w, d.upscale, e.x, e.y, e.img);
     if (!rc && e.scaled)
         rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y, e.sc.idx_x,
                          e.sc.w_x, e.sc.taps_x, e.format == END_RGB8 ? RESIZE_U8 : yuv_bits(e.dst->layout) == 8 ? RESIZE_YUV8 : RESIZE_YUV10, e.y, geom);
@@ -184,7 +189,7 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
 // The launch sequence every entry shares: plan, refusals, head, convs, tail.
 int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* params, const void* packed, void* workspace,
                          size_t workspace_bytes, hipStream_t st, const char* who) {
-    if (e.format == END_YUV && (!e.src || !e.dst)) return fail(RESR_ERR_ARG, "%s: null argument", who);
+    if ((e.format == END_YUV && (!e.src || !e.dst)) || (e.format == END_IMAGE && !e.img)) return fail(RESR_ERR_ARG, "%s: null argument", who);
     CPlan p;
     if (!build_cplan(d, p)) return fail(RESR_ERR_ARG, "%s: bad descriptor", who);
     ResizeGeom geom;
@@ -200,7 +205,7 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
     const int N = d->n, H = d->h, W = d->w;
     const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
     if (e.format == END_F32) rc = nchw_to_nhwc_dispatch((const float*)e.x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
-    else rc = frame_head_dispatch(e.x, xin, N, H, W, d->dtype, st, (long)lo32, e.src);   // src null: RGB bytes; its layout: bytes or 16-bit words
+    else rc = frame_head_dispatch(e.x, xin, N, H, W, d->dtype, st, (long)lo32, e.src, e.img);   // src and img null: RGB bytes; src's layout: bytes or 16-bit words
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) { return cconv_desc(*d, c, flags, lo32, lo64); };
     const int nbody = (int)p.convs.size() - 1;   // conv 0 + the num_conv body convs: 64 channels + activation
@@ -233,6 +238,7 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
         case END_YUV:
             if (!e.scaled) return compact_tail_yuv(t, e.x, e.y, N, H, W, s, e.src, e.dst, st);
             return compact_tail_yuv420_scaled(t, e.x, e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, e.src, e.dst, &geom, st);
+        case END_IMAGE: return compact_tail_image(t, e.x, e.y, e.img->channels == 4 ? N / 2 : N, H, W, s, e.img, st);
     }
     return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
 }

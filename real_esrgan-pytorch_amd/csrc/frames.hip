@@ -10,6 +10,10 @@
 //                                   the layout of the destination its parameters (one format twice, or a mixed pair)
 //   yuv420_to_rgb, rgb_to_yuv420  : the integer colour conversions on their own, u8 [N,3H/2,W] <-> u8 [N,H,W,3]
 //   yuv420p10_to_nchw, nchw_to_yuv420p10: 10-bit YUV [N,3H/2,W] <-> fp32 [N,3,H,W], one launch each, no RGB frame in between
+//   image modes                   : grey, RGB and RGBA images [N,H,W,C] of bytes or 16-bit words (255 or 65535 levels) at both ends -- a
+//                                   third source of frame_head (the network's batch: the N colour or grey images, for RGBA the N alpha
+//                                   planes behind them, each level thrice), compact_tail_image (grey and alpha leave through the
+//                                   fixed-point grey of their three levels), and the generic image_to_nchw / nchw_to_image
 //
 // The result is DEFINED as what the float path followed by imgproc.tensor_to_image produces, bit for bit:
 //   in : x = (float)u8 / 255.0f, one IEEE division (numpy's astype(float32) / 255.0), then converted to the model's type exactly
@@ -20,6 +24,7 @@
 // The YUV path is DEFINED as rgb_to_yuv420(the u8 path(yuv420_to_rgb(frame))), two integer functions of bytes (include/resr.h).
 // The 10-bit YUV path is the same composition with 1023 levels: the integer functions with 64 / 512 / 1023 for 16 / 128 / 255,
 // x = (float)rgb10 / 1023.0f on the way in and v * 1023.0f, clamp to [0, 1023], truncate on the way out (include/resr.h).
+// The image modes are DEFINED as to_image(q(the float path(to_rgb(images) / top))) with top = 255 or 65535 (include/resr.h, "Image modes").
 // Every index that can pass 2^31 is 64-bit.  Vector stores only.
 #include "host_api.h"
 #include "yuv.h"
@@ -160,6 +165,149 @@ __global__ __launch_bounds__(256) void frame_head_kernel(Src src, T* __restrict_
     }
     *reinterpret_cast<uint4*>(dst + p * 32 + piece * E) = out;
     if (sizeof(T) == 2 && lo_off) *reinterpret_cast<uint4*>(dst + lo_off + p * 32 + piece * E) = outl;
+}
+
+// ---- image modes (include/resr.h: grey, RGB and RGBA images of 8 or 16 bits; frames.py holds the definition once more in numpy) ----
+
+// cv2's fixed-point RGB2GRAY on integer levels: the coefficients sum to 2^14 (grey of (v, v, v) is v), the sum stays below 2^30 at 65535
+__device__ __forceinline__ unsigned grey_of(const unsigned (&o)[3]) { return (4899u * o[0] + 9617u * o[1] + 1868u * o[2] + 8192u) >> 14; }
+
+// The C levels of pixel p of an image batch [.,.,.,C]; an RGBA pixel is one load: a dword of four bytes, 8 bytes of four words.
+template <int C, int BITS>
+__device__ __forceinline__ void image_pixel(const typename Depth<BITS>::word* __restrict__ src, long p, unsigned (&lv)[4]) {
+    if constexpr (C == 4 && BITS == 8) {
+        const unsigned v = reinterpret_cast<const unsigned*>(src)[p];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) lv[c] = (v >> (8 * c)) & 255u;
+    } else if constexpr (C == 4) {
+        const uint2 v = reinterpret_cast<const uint2*>(src)[p];
+        lv[0] = v.x & 65535u; lv[1] = v.x >> 16; lv[2] = v.y & 65535u; lv[3] = v.y >> 16;
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) lv[c] = src[p * C + c];
+    }
+}
+
+// ... and an image batch of N images, `colour` = N * h * w pixels: network pixel p < colour is the colour of image pixel p (the grey
+// level three times), network pixel p >= colour (RGBA only: the second N images of the network's batch) the alpha level of image pixel
+// p - colour three times.
+template <int C, int BITS>
+struct ImageSrc {
+    const typename Depth<BITS>::word* __restrict__ src;
+    long colour;
+    __device__ __forceinline__ void operator()(long p, unsigned (&rgb)[3]) const {
+        const bool alpha = C == 4 && p >= colour;
+        unsigned lv[4];
+        image_pixel<C, BITS>(src, alpha ? p - colour : p, lv);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) rgb[c] = alpha ? lv[3] : C == 1 ? lv[0] : lv[c];
+    }
+    static __device__ __forceinline__ float unit(unsigned v) { return unit_of<kTop<BITS>>(v); }
+};
+
+// Output pixels a thread of the image tail owns: the fewest whose bytes are whole dwords, and a whole 16 bytes for RGBA
+constexpr int image_group(int c, int bits) { return c == 1 ? 4 : 32 / bits; }
+static_assert(image_group(1, 8) == 4 && image_group(1, 16) == 4 && image_group(3, 8) == 4 && image_group(3, 16) == 2 &&
+              image_group(4, 8) == 4 && image_group(4, 16) == 2, "grey 4 pixels, 8-bit colour 4, 16-bit colour 2");
+
+// compact_tail_u8_kernel for an image mode: t [planes * n, 3 S^2, h, w] fp32 + the input images x [n,h,w,C] -> y [n,hS,wS,C] of the
+// same words.  Per output pixel and channel v = t + unit(x level), quantise<top>(v): RGB stores the three levels; grey stores
+// grey_of them (the residual is the grey level, thrice); RGBA stores the colour of image b's planes of t and, as the fourth word,
+// grey_of the three levels of image n + b, whose residual is the alpha level.  A thread owns G = image_group consecutive output pixels
+// = DW whole dwords, one store where DW is 1, 2 or 4 (grey8 a dword, grey16 8 bytes, RGBA 16 bytes) and three dword stores for RGB
+// (12 bytes); y aligned to that store (compact_forward_ends / nchw_to_image_dispatch have checked it), a wavefront writes 64 * DW * 4
+// contiguous bytes.  The last partial group falls back to single words.  RES = false, S = 1: the generic fp32 NCHW -> image conversion.
+template <int S, int C, int BITS, bool RES>
+__global__ __launch_bounds__(256) void compact_tail_image_kernel(const float* __restrict__ t, const typename Depth<BITS>::word* __restrict__ x,
+                                                                 typename Depth<BITS>::word* __restrict__ y, int n, int h, int w) {
+    typedef typename Depth<BITS>::word word;
+    constexpr int TOP = kTop<BITS>, G = image_group(C, BITS), WPD = 32 / BITS, NW = G * C, DW = NW / WPD;
+    static_assert(NW % WPD == 0 && (DW == 1 || DW == 2 || DW == 3 || DW == 4), "a group is 1 to 4 whole dwords");
+    const int HS = h * S, WS = w * S;
+    const long plane = (long)h * w;
+    const long image = 3L * S * S * plane;     // floats of t per network image
+    const long total = (long)n * HS * WS;
+    const long q0 = ((long)blockIdx.x * 256 + threadIdx.x) * G;
+    if (q0 >= total) return;
+    const long row0 = q0 / WS;                 // b * HS + Y
+    int X = (int)(q0 - row0 * WS);
+    long b = row0 / HS;
+    int Y = (int)(row0 - b * HS);
+    unsigned words[NW];
+#pragma unroll
+    for (int k = 0; k < G; ++k) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) words[k * C + c] = 0u;
+        if (q0 + k < total) {
+            const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
+            const long off = (long)(sy * S + sx) * plane + (long)yy * w + xx;
+            unsigned lv[4] = {0u, 0u, 0u, 0u};
+            if constexpr (RES) image_pixel<C, BITS>(x, (b * h + yy) * (long)w + xx, lv);
+            const float* tp = t + b * image + off;
+            unsigned o[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float v = tp[(long)c * S * S * plane];
+                if constexpr (RES) v = v + unit_of<TOP>(lv[C == 1 ? 0 : c]);
+                o[c] = quantise<TOP>(v);
+            }
+            if constexpr (C == 1) {
+                words[k] = grey_of(o);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) words[k * C + c] = o[c];
+            }
+            if constexpr (C == 4) {
+                const float* ta = t + (n + b) * image + off;
+                unsigned a[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    float v = ta[(long)c * S * S * plane];
+                    if constexpr (RES) v = v + unit_of<TOP>(lv[3]);
+                    a[c] = quantise<TOP>(v);
+                }
+                words[k * 4 + 3] = grey_of(a);
+            }
+        }
+        if (++X == WS) {
+            X = 0;
+            if (++Y == HS) { Y = 0; ++b; }
+        }
+    }
+    word* out = y + q0 * C;
+    if (q0 + G <= total) {
+        unsigned dw[DW];
+#pragma unroll
+        for (int d = 0; d < DW; ++d) {
+            dw[d] = 0u;
+#pragma unroll
+            for (int i = 0; i < WPD; ++i) dw[d] |= words[d * WPD + i] << (BITS * i);
+        }
+        if constexpr (DW == 1) *reinterpret_cast<unsigned*>(out) = dw[0];
+        else if constexpr (DW == 2) *reinterpret_cast<uint2*>(out) = make_uint2(dw[0], dw[1]);
+        else if constexpr (DW == 4) *reinterpret_cast<uint4*>(out) = make_uint4(dw[0], dw[1], dw[2], dw[3]);
+        else {
+#pragma unroll
+            for (int d = 0; d < 3; ++d) reinterpret_cast<unsigned*>(out)[d] = dw[d];
+        }
+    } else {
+        const int left = (int)(total - q0) * C;
+#pragma unroll
+        for (int i = 0; i < NW - C; ++i)
+            if (i < left) out[i] = (word)words[i];
+    }
+}
+
+// One thread per NETWORK pixel (planes * n images), as u8_to_nchw_kernel: the pixel's levels through ImageSrc, one coalesced dword store per plane.
+template <int C, int BITS>
+__global__ __launch_bounds__(256) void image_to_nchw_kernel(ImageSrc<C, BITS> src, float* __restrict__ dst, long total, long plane) {
+    const long p = (long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= total) return;
+    const long b = p / plane, r = p - b * plane;
+    unsigned rgb[3];
+    src(p, rgb);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + r] = ImageSrc<C, BITS>::unit(rgb[c]);
 }
 
 // The image b, first row Y0 and first column X0 of the thread that owns 2 rows x COLS columns of n images of rows x cols pixels
@@ -514,15 +662,81 @@ void launch_tail(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int
     hipLaunchKernelGGL((compact_tail_u8_kernel<S, RES>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, t, x, y, n, h, w);
 }
 
+// ---- image modes ----
+
+// A runtime image mode as a compile-time one, as with_scale: f(channels, bits), both std::integral_constant; false for any other mode
+// and for 8-bit RGB, which has no image kernels of its own (image_is_rgb8: the callers run the uint8 path's).
+template <typename F>
+bool with_image_mode(const ResrImageDesc& m, F&& f) {
+    auto depth = [&](auto C) {
+        if constexpr (decltype(C)::value != 3)
+            if (m.bits == 8) { f(C, std::integral_constant<int, 8>()); return true; }
+        if (m.bits == 16) { f(C, std::integral_constant<int, 16>()); return true; }
+        return false;
+    };
+    switch (m.channels) {
+        case 1: return depth(std::integral_constant<int, 1>());
+        case 3: return depth(std::integral_constant<int, 3>());
+        case 4: return depth(std::integral_constant<int, 4>());
+        default: return false;
+    }
+}
+
+// 8-bit RGB is the uint8 frame path: its kernels run
+bool image_is_rgb8(const ResrImageDesc* m) { return m->channels == 3 && m->bits == 8; }
+long image_group_of(const ResrImageDesc* m) { return image_group(m->channels, m->bits); }
+// The widest store of the tail (16 bytes of RGBA, 8 of 16-bit grey, else a dword) and the widest load of either end (an RGBA pixel is one
+// load, every other level a word of its own): what y and x must be aligned to
+size_t image_store_align(const ResrImageDesc* m) { return m->channels == 4 ? 16 : m->channels == 1 && m->bits == 16 ? 8 : 4; }
+size_t image_load_align(const ResrImageDesc* m) { return (size_t)(m->channels == 4 ? m->bits / 2 : m->bits / 8); }
+
+int image_desc_check(const char* who, const ResrImageDesc* m) {
+    if (!m) return fail(RESR_ERR_ARG, "%s: null argument (the image descriptor)", who);
+    if (m->channels != 1 && m->channels != 3 && m->channels != 4)
+        return fail(RESR_ERR_ARG, "%s: channels must be 1 (grey), 3 (RGB) or 4 (RGBA), got %d", who, m->channels);
+    if (m->bits != 8 && m->bits != 16) return fail(RESR_ERR_ARG, "%s: bits must be 8 or 16, got %d", who, m->bits);
+    return RESR_OK;
+}
+
+int image_align_check(const char* who, const void* images_in, const void* images_out, const ResrImageDesc* m) {
+    if (images_in && ((size_t)images_in & (image_load_align(m) - 1)) != 0)
+        return fail(RESR_ERR_ARG, "%s: the source images must be %zu-byte aligned (%d channels of %d bits)", who, image_load_align(m), m->channels, m->bits);
+    if (images_out && ((size_t)images_out & (image_store_align(m) - 1)) != 0)
+        return fail(RESR_ERR_ARG, "%s: the output images must be %zu-byte aligned (%d channels of %d bits)", who, image_store_align(m), m->channels, m->bits);
+    return RESR_OK;
+}
+
+// the pointers, the descriptor and the sizes of a generic conversion, in the order they are refused
+int image_convert_check(const char* who, const void* src, const void* dst, int n_images, int h, int w, const ResrImageDesc* m) {
+    if (!src || !dst) return fail(RESR_ERR_ARG, "%s: null argument", who);
+    if (const int rc = image_desc_check(who, m)) return rc;
+    if (n_images <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "%s: bad argument (n_images=%d h=%d w=%d)", who, n_images, h, w);
+    return RESR_OK;
+}
+
+template <int S, bool RES>
+void launch_tail_image(const float* t, const void* x, void* y, int n, int h, int w, const ResrImageDesc* m, hipStream_t st) {
+    const long groups = ((long)n * h * S * w * S + image_group_of(m) - 1) / image_group_of(m);
+    with_image_mode(*m, [&](auto C, auto B) {
+        typedef typename Depth<decltype(B)::value>::word word;
+        hipLaunchKernelGGL((compact_tail_image_kernel<S, decltype(C)::value, decltype(B)::value, RES>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0,
+                           st, t, (const word*)x, (word*)y, n, h, w);
+    });
+}
+
 }  // namespace
 
 // lo_off: the hi -> lo element offset of x_in (RESR_F16X2), as compact_forward passes it to nchw_to_nhwc_dispatch.
 // q: the frames are YUV 4:2:0 [n,3h/2,w], of bytes or (a 10-bit layout) of 16-bit words; null: RGB bytes [n,h,w,3].
-int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q) {
+// img: the frames are images [n / planes,h,w,C] of that mode (q null; image_forward_check has passed): the second half of an RGBA
+// batch's n network images are the alpha planes.  8-bit RGB images are the RGB bytes above.
+int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q,
+                        const ResrImageDesc* img) {
+    if (img && image_is_rgb8(img)) img = nullptr;
     const int bits = q ? yuv_bits(q->layout) : 0;
     const bool ten = bits == 10;
-    const char* who = ten ? "yuv10_head" : q ? "yuv_head" : "u8_head";
-    if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || (q && ((h & 1) || (w & 1) || !bits))) return fail(RESR_ERR_ARG, "%s: bad argument", who);
+    const char* who = img ? "image_head" : ten ? "yuv10_head" : q ? "yuv_head" : "u8_head";
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || (q && ((h & 1) || (w & 1) || !bits || img))) return fail(RESR_ERR_ARG, "%s: bad argument", who);
     const long px = (long)n * h * w;
     const int pieces = dtype != RESR_F32 ? 4 : 8;
     if (!grid_ok(px * pieces)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, px);
@@ -535,10 +749,19 @@ int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dty
             hipLaunchKernelGGL((frame_head_kernel<float, decltype(from)>), grid, dim3(256), 0, st, from, (float*)dst, px, 0L);
     };
     prof_before(st);
-    if (ten) launch(YuvSrc<10>{(const uint16_t*)src, h, w, *q});
+    if (img) {
+        const long colour = img->channels == 4 ? px / 2 : px;
+        const bool ok = with_image_mode(*img, [&](auto C, auto B) {
+            launch(ImageSrc<decltype(C)::value, decltype(B)::value>{(const typename Depth<decltype(B)::value>::word*)src, colour});
+        });
+        if (!ok) return fail(RESR_ERR_ARG, "%s: bad argument", who);
+    }
+    else if (ten) launch(YuvSrc<10>{(const uint16_t*)src, h, w, *q});
     else if (q) launch(YuvSrc<8>{(const uint8_t*)src, h, w, *q});
     else launch(RgbSrc{(const uint8_t*)src});
-    prof_after(st, ten ? 31022 : q ? 31021 : 31020, 0.0, (double)px * ((q ? ten ? 3.0 : 1.5 : 3.0) + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
+    // an image pixel is read once per network pixel: an RGBA pixel twice, as colour and as alpha
+    const double src_bytes = img ? img->channels * img->bits / 8.0 : q ? ten ? 3.0 : 1.5 : 3.0;
+    prof_after(st, img ? 31023 : ten ? 31022 : q ? 31021 : 31020, 0.0, (double)px * (src_bytes + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
     RESR_CHECK_LAUNCH("frame_head_kernel");
     return RESR_OK;
 }
@@ -573,6 +796,68 @@ int nchw_to_u8_dispatch(const float* src, uint8_t* dst, int n, int h, int w, hip
     launch_tail<1, false>(src, nullptr, dst, n, h, w, st);
     prof_after(st, 31031, 0.0, (double)total * 15.0);
     RESR_CHECK_LAUNCH("nchw_to_u8_kernel");
+    return RESR_OK;
+}
+
+// ---- image modes ----
+
+// Everything the image entry of compact_forward_ends has to refuse about its images, before its first launch.  n: the network's batch,
+// planes * N.  The alignment rules are the widest load and store of the mode (image_load_align, image_store_align).
+int image_forward_check(const char* who, int n, int h, int w, int s, const void* x, const void* y, const ResrImageDesc* img) {
+    if (const int rc = image_desc_check(who, img)) return rc;
+    if (img->channels == 4 && (n & 1))
+        return fail(RESR_ERR_ARG, "%s: an RGBA batch is N colour images and N alpha images, the descriptor's n = %d is odd", who, n);
+    if (const int rc = image_align_check(who, x, y, img)) return rc;
+    const long out_px = (long)(img->channels == 4 ? n / 2 : n) * h * s * w * s, g = image_group_of(img);
+    if (!grid_ok((out_px + g - 1) / g)) return fail(RESR_ERR_ARG, "%s: %dx%dx%d beyond the grid", who, n, h * s, w * s);
+    return RESR_OK;
+}
+
+// x, y, n_images and img have passed image_forward_check: compact_forward_ends has called it.  Profiling id 31100 + s (8-bit RGB: the
+// uint8 tail's own).
+int compact_tail_image(const float* t, const void* x, void* y, int n_images, int h, int w, int s, const ResrImageDesc* img, hipStream_t st) {
+    if (image_is_rgb8(img)) return compact_tail_u8(t, (const uint8_t*)x, (uint8_t*)y, n_images, h, w, s, st);
+    prof_before(st);
+    if (!with_scale(s, [&](auto S) { launch_tail_image<S(), true>(t, x, y, n_images, h, w, img, st); }))
+        return fail(RESR_ERR_ARG, "compact_tail_image: upscale %d", s);
+    // per LR pixel of a network image: 3 s^2 floats of t; per LR pixel of an image: its words in, s^2 times its words out
+    const double pb = img->channels * img->bits / 8.0, planes = img->channels == 4 ? 2.0 : 1.0;
+    prof_after(st, 31100 + s, 0.0, (double)n_images * h * w * (s * s * (12.0 * planes + pb) + pb));
+    RESR_CHECK_LAUNCH("compact_tail_image_kernel");
+    return RESR_OK;
+}
+
+int image_to_nchw_dispatch(const void* src, float* dst, int n_images, int h, int w, const ResrImageDesc* img, hipStream_t st) {
+    const char* who = "image_to_nchw";
+    if (const int rc = image_convert_check(who, src, dst, n_images, h, w, img)) return rc;
+    if (const int rc = image_align_check(who, src, nullptr, img)) return rc;
+    if (((size_t)dst & 3) != 0) return fail(RESR_ERR_ARG, "%s: the float tensor must be 4-byte aligned", who);
+    const long plane = (long)h * w, colour = plane * n_images, total = img->channels == 4 ? 2 * colour : colour;
+    if (!grid_ok(total)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, total);
+    if (image_is_rgb8(img)) return u8_to_nchw_dispatch((const uint8_t*)src, dst, n_images, h, w, st);
+    prof_before(st);
+    with_image_mode(*img, [&](auto C, auto B) {
+        typedef ImageSrc<decltype(C)::value, decltype(B)::value> Src;
+        hipLaunchKernelGGL((image_to_nchw_kernel<decltype(C)::value, decltype(B)::value>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                           Src{(const typename Depth<decltype(B)::value>::word*)src, colour}, dst, total, plane);
+    });
+    prof_after(st, 31036, 0.0, (double)total * (12.0 + img->channels * img->bits / 8.0));
+    RESR_CHECK_LAUNCH("image_to_nchw_kernel");
+    return RESR_OK;
+}
+
+int nchw_to_image_dispatch(const float* src, void* dst, int n_images, int h, int w, const ResrImageDesc* img, hipStream_t st) {
+    const char* who = "nchw_to_image";
+    if (const int rc = image_convert_check(who, src, dst, n_images, h, w, img)) return rc;
+    if (const int rc = image_align_check(who, nullptr, dst, img)) return rc;
+    if (((size_t)src & 3) != 0) return fail(RESR_ERR_ARG, "%s: the float tensor must be 4-byte aligned", who);
+    const long total = (long)n_images * h * w, g = image_group_of(img);
+    if (!grid_ok((total + g - 1) / g)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, total);
+    if (image_is_rgb8(img)) return nchw_to_u8_dispatch(src, (uint8_t*)dst, n_images, h, w, st);
+    prof_before(st);
+    launch_tail_image<1, false>(src, nullptr, dst, n_images, h, w, img, st);
+    prof_after(st, 31037, 0.0, (double)total * ((img->channels == 4 ? 24.0 : 12.0) + img->channels * img->bits / 8.0));
+    RESR_CHECK_LAUNCH("nchw_to_image_kernel");
     return RESR_OK;
 }
 

@@ -91,8 +91,9 @@ int compact_act_bwd_dispatch(const void* g, const void* z, void* gz, const float
                              hipStream_t st);
 int compact_residual_bwd_dispatch(const float* gy, float* gx, int n, int h, int w, int s, hipStream_t st);
 // ---- frames.hip: the uint8 / YUV 4:2:0 ends of the compact generator.  t: the last convolution's output [n,3s^2,h,w] fp32; x: the source frames
-// (the residual); s: upscale factor; q / qs / qd: what the (source / destination) frames are, null = RGB bytes; bits: 8, 10 or 0 (Ends::bits_expected) ----
-int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q);
+// (the residual); s: upscale factor; q / qs / qd: what the (source / destination) frames are, null = RGB bytes; bits: 8, 10 or 0 (Ends::bits_expected);
+// img: the frames are images of that mode (then q is null), n of the head and of image_forward_check the network's batch planes * N, n_images N ----
+int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q, const ResrImageDesc* img);
 int compact_tail_u8(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, hipStream_t st);
 int u8_to_nchw_dispatch(const uint8_t* src, float* dst, int n, int h, int w, hipStream_t st);
 int nchw_to_u8_dispatch(const float* src, uint8_t* dst, int n, int h, int w, hipStream_t st);
@@ -102,6 +103,10 @@ int yuv420p10_to_nchw_dispatch(const uint16_t* src, float* dst, int n, int h, in
 int nchw_to_yuv420p10_dispatch(const float* src, uint16_t* dst, int n, int h, int w, const ResrYuvDesc* q, hipStream_t st);
 int yuv420_to_rgb_dispatch(const uint8_t* src, uint8_t* dst, int n, int h, int w, const ResrYuvDesc* q, hipStream_t st);
 int rgb_to_yuv420_dispatch(const uint8_t* src, uint8_t* dst, int n, int h, int w, const ResrYuvDesc* q, hipStream_t st);
+int image_forward_check(const char* who, int n, int h, int w, int s, const void* x, const void* y, const ResrImageDesc* img);
+int compact_tail_image(const float* t, const void* x, void* y, int n_images, int h, int w, int s, const ResrImageDesc* img, hipStream_t st);
+int image_to_nchw_dispatch(const void* src, float* dst, int n_images, int h, int w, const ResrImageDesc* img, hipStream_t st);
+int nchw_to_image_dispatch(const float* src, void* dst, int n_images, int h, int w, const ResrImageDesc* img, hipStream_t st);
 // ---- image_resize.hip.  idx_* / w_*: the resize tables (device), taps_* taps per output row / column; kind: a ResizeOut; c, h, w: the source;
 // gp: the launch resize_plan made for the HR frame (c = 3, h * s, w * s) ----
 int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, const void* idx_y, const void* w_y, int taps_y, const void* idx_x, const void* w_x, int taps_x, int kind,

@@ -7,7 +7,7 @@
 
 namespace resr {
 
-// TOP: the highest level of a sample, 255 (8 bits) or 1023 (10 bits)
+// TOP: the highest level of a sample, 255 (8 bits), 1023 (10 bits) or 65535 (the 16-bit image modes)
 template <int TOP>
 __device__ __forceinline__ float unit_of(unsigned v) { return (float)v / (float)TOP; }
 
@@ -20,9 +20,11 @@ __device__ __forceinline__ unsigned quantise(float v) {
 }
 
 // BITS per sample, 8 or 10 (every template below defaults to 8): the word a sample is stored in, the highest level, and the studio
-// offsets 16 / 128, which scale with the depth (64 / 512 at 10 bits).
+// offsets 16 / 128, which scale with the depth (64 / 512 at 10 bits).  16: the image modes' full 16-bit word (RGB levels only: the
+// YUV formulas below are not instantiated for it -- their int32 accumulators would overflow).
 template <int BITS> struct Depth { typedef uint8_t word; };
 template <> struct Depth<10> { typedef uint16_t word; };
+template <> struct Depth<16> { typedef uint16_t word; };
 template <int BITS> constexpr int kTop = (1 << BITS) - 1;
 template <int BITS> constexpr int kLumaOff = 16 << (BITS - 8);
 template <int BITS> constexpr int kChromaOff = 128 << (BITS - 8);

@@ -9,6 +9,7 @@ bit: a frame enters as `u8 / 255.0f`, runs through the model in the model's arit
     upscale_u8(model, frames)  uint8 [N,H,W,3] -> uint8 [N,sH,sW,3]        any model, any frame size
     FrameStream(model, depth)  host ndarray in -> host ndarray out, `depth` frames in flight
     output_size(h, w, s, o)    the size of a frame upscaled with `outscale=o`: the one place that formula lives
+    upscale_image(model, im)   grey, RGB or RGBA images of 8 or 16 bits -> the same mode, [N,sH,sW(,C)]  (IMAGE MODES below)
     PIXEL_FORMATS              one record per pixel format name (layout id, bits, packing, dtypes): the table `YUV_LAYOUTS`,
                                `YUV10_LAYOUTS` and `FrameStream.PIX_FMTS` are read from, and the 8- and 10-bit functions below share
                                their bodies through
@@ -82,6 +83,27 @@ model with the fused entry (`SRVGGNetCompact.forward_yuv420_mixed`: the head rea
 B) runs it when the frame fits one call -- with `outscale` where `resr_compact_yuv420_scaled_fits` finds an even tile for B's depth;
 every other case (the RRDB `Generator`, tiled frames, "rgb24" on a side, a scale with no even tile) is the composition of the generic
 launches above, the same functions on the same values, hence the same bits.
+
+IMAGE MODES -- the still images upstream's `RealESRGANer.enhance` takes besides 8-bit RGB: grey, RGBA and 16 bits per channel
+(transparent sprites, anime assets, 16-bit scans).  An image batch is uint8 (top = 255) or uint16 (top = 65535; `torch.uint16` on the
+device): [N,H,W] or [N,H,W,1] grey, [N,H,W,3] RGB, [N,H,W,4] RGBA; planes = 2 for RGBA, else 1.  Three numpy functions ARE the definition:
+
+    image_to_rgb_np(images) -> [planes*N,H,W,3]   RGB: itself; grey: the plane three times; RGBA: the N colour images, then the N alpha
+                                                  planes, each three times (upstream's `alpha_upsampler="realesrgan"`: alpha goes through
+                                                  the network as a grey image)
+    grey_np(rgb)                                  (4899 R + 9617 G + 1868 B + 8192) >> 14 on integer levels, at both depths (cv2's
+                                                  fixed-point RGB2GRAY: exact for R = G = B, within int32 at 65535)
+    rgb_to_image_np(levels, channels)             RGB: itself; grey: `grey_np`; RGBA: the colour of the first N images, `grey_np` of the
+                                                  last N as the fourth channel
+
+    upscale_image(model, images) == rgb_to_image_np(q(float_path(image_to_rgb_np(images) / top)), channels)
+
+`/ top` one fp32 IEEE division, `float_path` the model's fp32 forward on the planes * N images (residual included), q(v) = trunc(clamp(v *
+top, 0, top)) in fp32: `imgproc.tensor_to_image`'s rule with top for 255.  (Upstream rounds, and takes grey of the float output; the
+reference truncates, and so does this path, which takes grey of the quantised levels.)  uint8 RGB is `upscale_u8`.  A model with a fused
+entry (`SRVGGNetCompact.forward_image`: the head reads the image's own words, the tail writes them) runs it when the planes * N images
+fit one call; every other case (the RRDB `Generator`, tiled frames) is `to_image(super_resolve(model, from_image(images)))`, one launch
+each way.  No `outscale` and no `FrameStream` for these modes; `PIXEL_FORMATS` does not list them.
 """
 from __future__ import annotations
 
@@ -98,7 +120,8 @@ from . import _lib, tiling
 __all__ = ["from_u8", "to_u8", "upscale_u8", "FrameStream", "output_size", "check_outscale", "yuv420_tables", "yuv420_to_rgb_np",
            "rgb_to_yuv420_np", "yuv420_to_rgb", "rgb_to_yuv420", "upscale_yuv420", "yuv420p10_tables", "yuv420p10_to_rgb_np",
            "rgb_to_yuv420p10_np", "from_yuv420p10", "to_yuv420p10", "upscale_yuv420p10", "PixelFormat", "PIXEL_FORMATS", "YUV_MATRICES",
-           "FrameFormat", "frame_format", "upscale_frames"]
+           "FrameFormat", "frame_format", "upscale_frames", "image_to_rgb_np", "grey_np", "rgb_to_image_np", "from_image", "to_image",
+           "upscale_image"]
 
 class PixelFormat(NamedTuple):
     """One row of `PIXEL_FORMATS`: everything the frame path knows about a pixel format by name.  `layout`: ResrYuvDesc.layout of
@@ -601,6 +624,138 @@ def upscale_frames(model, frames: torch.Tensor, src, dst=None, halo: Optional[in
         return to_yuv420p10(sr if o is None else resize_with_plan(sr, plan), b.pix_fmt, b.matrix)
     rgb = to_u8(sr) if o is None else resize_with_plan(sr, plan, u8=True)
     return rgb if b.fmt.layout is None else rgb_to_yuv420(rgb, b.pix_fmt, b.matrix)
+
+
+# ---- image modes: grey, RGB and RGBA images of 8 or 16 bits (module docstring, IMAGE MODES) -------------------------------------
+_IMAGE_DTYPES = {np.dtype(np.uint8): torch.uint8, np.dtype(np.uint16): torch.uint16}
+_GREY_R, _GREY_G, _GREY_B = 4899, 9617, 1868            # cv2's fixed-point RGB2GRAY, Q14: they sum to 2^14
+
+
+def _image_geometry(shape, what: str, error=ValueError) -> Tuple[int, int, int, int]:
+    """THE RULE: (N, H, W, channels) of an image batch -- [N,H,W] or [N,H,W,1] grey, [N,H,W,3] RGB, [N,H,W,4] RGBA."""
+    shape = tuple(shape)
+    if len(shape) == 3:
+        shape += (1,)
+    if len(shape) != 4 or shape[3] not in (1, 3, 4) or min(shape) < 1:
+        raise error(f"{what}: an image batch is [N,H,W] or [N,H,W,1] (grey), [N,H,W,3] (RGB) or [N,H,W,4] (RGBA), got {tuple(shape)}")
+    return shape
+
+
+def _image_np(images, what: str) -> Tuple[np.ndarray, int]:
+    """`images` as a [N,H,W,C] array of uint8 or uint16, and C."""
+    images = np.asarray(images)
+    if images.dtype not in _IMAGE_DTYPES:
+        raise ValueError(f"{what}: expected uint8 or uint16, got {images.dtype}")
+    n, h, w, c = _image_geometry(images.shape, what)
+    return images.reshape(n, h, w, c), c
+
+
+def image_to_rgb_np(images: np.ndarray) -> np.ndarray:
+    """THE DEFINITION (host, numpy): an image batch -> the RGB images the network runs on, [planes * N, H, W, 3] of the same dtype.
+    RGB: the images themselves; grey: the plane three times; RGBA: the N colour images, then the N alpha planes, each three times
+    (upstream's `alpha_upsampler="realesrgan"`: alpha goes through the network as a grey image)."""
+    images, c = _image_np(images, "image_to_rgb_np")
+    if c == 3:
+        return images
+    if c == 1:
+        return np.repeat(images, 3, axis=3)
+    return np.concatenate([images[..., :3], np.repeat(images[..., 3:], 3, axis=3)], axis=0)
+
+
+def grey_np(rgb: np.ndarray) -> np.ndarray:
+    """THE DEFINITION (host, numpy): uint8 or uint16 [..., 3] -> [...] of the same dtype, `(4899 R + 9617 G + 1868 B + 8192) >> 14`
+    on integer levels at both depths -- cv2's fixed-point RGB2GRAY.  The coefficients sum to 2^14, so a grey triple (v, v, v) gives v
+    exactly, and the sum stays below 2^31 at 65535.  Within 1 level of rint(0.299 R + 0.587 G + 0.114 B) at 8 bits, 2 at 16."""
+    rgb = np.asarray(rgb)
+    if rgb.dtype not in _IMAGE_DTYPES or rgb.ndim < 1 or rgb.shape[-1] != 3:
+        raise ValueError(f"grey_np: expected uint8 or uint16 [..., 3], got {rgb.dtype} {rgb.shape}")
+    v = rgb.astype(np.int64)
+    return ((_GREY_R * v[..., 0] + _GREY_G * v[..., 1] + _GREY_B * v[..., 2] + 8192) >> 14).astype(rgb.dtype)
+
+
+def rgb_to_image_np(rgb_levels: np.ndarray, channels: int) -> np.ndarray:
+    """THE DEFINITION (host, numpy): the quantised network output [planes * N, H, W, 3] -> the image batch.  channels = 3: itself;
+    1: `grey_np` -> [N,H,W]; 4: the colour of the first N images and `grey_np` of the last N as the fourth channel -> [N,H,W,4]."""
+    rgb = np.asarray(rgb_levels)
+    if rgb.dtype not in _IMAGE_DTYPES or rgb.ndim != 4 or rgb.shape[3] != 3:
+        raise ValueError(f"rgb_to_image_np: expected uint8 or uint16 [planes * N, H, W, 3], got {rgb.dtype} {rgb.shape}")
+    if channels == 3:
+        return rgb
+    if channels == 1:
+        return grey_np(rgb)
+    if channels != 4:
+        raise ValueError(f"rgb_to_image_np: channels must be 1, 3 or 4, got {channels!r}")
+    if rgb.shape[0] % 2:
+        raise ValueError(f"rgb_to_image_np: an RGBA batch is N colour images and N alpha images, got {rgb.shape[0]} images")
+    n = rgb.shape[0] // 2
+    return np.concatenate([rgb[:n], grey_np(rgb[n:])[..., None]], axis=3)
+
+
+def check_images(images: torch.Tensor, what: str) -> Tuple[int, int, int, int]:
+    """(N, H, W, channels) of a contiguous uint8 / uint16 image batch on the device; RuntimeError for anything else, before any launch."""
+    _lib.require_cuda(images, what)
+    if images.dtype not in _IMAGE_DTYPES.values():
+        raise RuntimeError(f"{what}: expected a uint8 or uint16 image batch, got {images.dtype} {tuple(images.shape)}")
+    geom = _image_geometry(images.shape, what, RuntimeError)
+    if not images.is_contiguous():
+        raise RuntimeError(f"{what}: images must be contiguous (HWC words, as an image decoder leaves them)")
+    return geom
+
+
+def image_desc(channels: int, dtype) -> _lib.ImageDesc:
+    """The ResrImageDesc of include/resr.h: channels 1, 3 or 4; 8 bits for torch.uint8, 16 for torch.uint16."""
+    if channels not in (1, 3, 4) or dtype not in _IMAGE_DTYPES.values():
+        raise ValueError(f"image_desc: channels 1, 3 or 4 of torch.uint8 or torch.uint16, got {channels!r} of {dtype!r}")
+    return _lib.ImageDesc(channels, 8 if dtype == torch.uint8 else 16)
+
+
+@torch.no_grad()
+def from_image(images: torch.Tensor) -> torch.Tensor:
+    """An image batch on the device -> fp32 [planes * N, 3, H, W], one launch (resr_image_to_nchw): `image_to_rgb_np(images) / top` as
+    NCHW, bit for bit (top = 255 or 65535, one IEEE division)."""
+    n, h, w, c = check_images(images, "from_image")
+    desc = image_desc(c, images.dtype)
+    x = torch.empty(((2 if c == 4 else 1) * n, 3, h, w), dtype=torch.float32, device=images.device)
+    _lib.check(_lib.lib().resr_image_to_nchw(_lib.ptr(images), _lib.ptr(x), n, h, w, _lib.C.byref(desc), _lib.stream_ptr(images)),
+               "resr_image_to_nchw")
+    return x
+
+
+@torch.no_grad()
+def to_image(sr: torch.Tensor, channels: int, dtype) -> torch.Tensor:
+    """fp32 [planes * N, 3, H, W] -> the image batch [N,H,W,channels] of `dtype` (grey: [N,H,W]), one launch (resr_nchw_to_image):
+    `* top`, clamp to [0, top], truncate, then `rgb_to_image_np`, bit for bit."""
+    desc = image_desc(channels, dtype)
+    _lib.require_cuda(sr, "to_image")
+    planes = 2 if channels == 4 else 1
+    if sr.dtype != torch.float32 or sr.dim() != 4 or sr.shape[1] != 3 or min(sr.shape) < 1 or sr.shape[0] % planes:
+        raise RuntimeError(f"to_image: expected an fp32 [{'2N' if planes == 2 else 'N'},3,H,W] tensor, got {sr.dtype} {tuple(sr.shape)}")
+    if not sr.is_contiguous():
+        sr = sr.contiguous()
+    n, _, h, w = sr.shape
+    n //= planes
+    y = torch.empty((n, h, w) if channels == 1 else (n, h, w, channels), dtype=dtype, device=sr.device)
+    _lib.check(_lib.lib().resr_nchw_to_image(_lib.ptr(sr), _lib.ptr(y), n, h, w, _lib.C.byref(desc), _lib.stream_ptr(sr)), "resr_nchw_to_image")
+    return y
+
+
+@torch.no_grad()
+def upscale_image(model, images: torch.Tensor, halo: Optional[int] = None) -> torch.Tensor:
+    """An image batch on the model's device -- uint8 or uint16, [N,H,W] or [N,H,W,1] grey, [N,H,W,3] RGB, [N,H,W,4] RGBA, contiguous
+    -> the upscaled batch of the same dtype and trailing shape, [N,sH,sW(,C)].  Bit for bit
+    `rgb_to_image_np(q(float_path(image_to_rgb_np(images) / top)), channels)` (module docstring, IMAGE MODES).  The one place that
+    chooses, by `upscale_u8`'s rule: uint8 RGB IS `upscale_u8`; a model with the fused entry (`SRVGGNetCompact.forward_image`) runs it
+    when the network's batch of planes * N images fits one call; every other case (the RRDB `Generator`, frames the tiler has to cut)
+    is `to_image(super_resolve(model, from_image(images)))`.  `halo`: `upscale_u8`'s."""
+    n, h, w, c = check_images(images, "upscale_image")
+    s = model.upscale_factor
+    if c == 3 and images.dtype == torch.uint8:
+        return upscale_u8(model, images, halo)
+    if hasattr(model, "forward_image") and tiling.fits_whole(model, (2 if c == 4 else 1) * n, h, w):
+        out = model.forward_image(images)
+    else:
+        out = to_image(tiling.super_resolve(model, from_image(images), halo), c, images.dtype)
+    return out.reshape((n, h * s, w * s) + tuple(images.shape[3:]))
 
 
 class _Slot:

@@ -1,7 +1,7 @@
 """Directory super-resolution on the uint8 frame path (frames.py): every image of a folder, pipelined.
 
     python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
-        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2]
+        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode]
 
 The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
 walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
@@ -9,6 +9,12 @@ encode under the same file name in `--output_dir`.  Each written image equals wh
 own.  `--outscale F` (default: the model's factor) writes `frames.output_size` images instead: the model's output resized by
 F / factor with the reference's antialiased bicubic `image_resize`, on the device (frames.py, OUTSCALE).  Frames of different sizes may be mixed (a change of size drains the pipeline).  Video containers are not read here: extract
 frames first (ffmpeg -i in.mp4 lr/%06d.png), as upstream's inference_realesrgan_video.py does internally.
+
+`--keep_mode` (default off: every file is decoded with `.convert("RGB")`, as above): a file whose PIL mode is `L` (8-bit grey), `RGBA`
+or `I;16` (16-bit grey) keeps it, and `LA` becomes RGBA: such a file goes through `frames.upscale_image` on its own -- alpha through the
+network as a grey image, 16 bits in and 16 bits out -- and is written in the mode it came in.  RGB files, and every other mode through
+`.convert("RGB")`, keep going through the pipelined `FrameStream`.  `--outscale` does not apply to the kept modes (an error when both
+are given and such a file turns up).  PIL has no 16-bit RGB or RGBA mode: those are `frames.upscale_image` on arrays of your own.
 """
 import argparse
 import os
@@ -18,7 +24,7 @@ import torch
 
 from . import config
 from .compact import SRVGGNetCompact
-from .frames import FrameStream
+from .frames import FrameStream, upscale_image
 from .model import Generator, load_official_state_dict
 
 IMAGE_EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp")
@@ -50,12 +56,41 @@ def list_images(inputs_dir: str):
     return sorted(f for f in os.listdir(inputs_dir) if f.lower().endswith(IMAGE_EXTENSIONS))
 
 
+KEPT_MODES = {"L": "L", "RGBA": "RGBA", "I;16": "I;16", "LA": "RGBA"}     # PIL mode of a file -> the mode it is upscaled and written in
+
+
+def kept_mode(image):
+    """The mode `--keep_mode` upscales and writes this PIL image in, or None for one that takes the RGB stream."""
+    return KEPT_MODES.get(image.mode)
+
+
+def upscale_kept(model, image, mode: str):
+    """One PIL image of a kept mode through `frames.upscale_image` -> the PIL image of that mode."""
+    from PIL import Image
+    array = np.array(image if image.mode == mode else image.convert(mode))      # (a copy: PIL's own buffer is read-only)
+    images = torch.from_numpy(array)[None].to(next(model.parameters()).device)
+    return Image.fromarray(upscale_image(model, images)[0].cpu().numpy())
+
+
 def main(args) -> None:
     from PIL import Image
     torch.cuda.set_device(config.device)
     model = build_model(args)
     names = list_images(args.inputs_dir)
     os.makedirs(args.output_dir, exist_ok=True)
+    kept = {}           # --keep_mode: file name -> mode, for the files that leave the RGB stream below alone
+    if getattr(args, "keep_mode", False):
+        for name in names:
+            with Image.open(os.path.join(args.inputs_dir, name)) as image:      # (reads the header only)
+                if kept_mode(image) is not None:
+                    kept[name] = kept_mode(image)
+        if kept and getattr(args, "outscale", None) is not None:
+            raise ValueError(f"--keep_mode: --outscale does not apply to grey, RGBA and 16-bit files ({next(iter(kept))})")
+        names = [name for name in names if name not in kept]
+    for name, mode in kept.items():
+        with Image.open(os.path.join(args.inputs_dir, name)) as image:
+            upscale_kept(model, image, mode).save(os.path.join(args.output_dir, name))
+        print(f"SR image save to `{os.path.join(args.output_dir, name)}`")
 
     def decode():
         for name in names:
@@ -82,6 +117,8 @@ def get_parser() -> argparse.ArgumentParser:
     parser.add_argument("--depth", type=int, default=2, help="frames in flight (FrameStream)")
     parser.add_argument("--outscale", type=float, default=None,
                         help="final upscaling factor (default: the model's own); e.g. 2 writes 2x images from the x4 model")
+    parser.add_argument("--keep_mode", action="store_true",
+                        help="keep grey (L), RGBA (LA too) and 16-bit grey (I;16) files in their mode instead of converting them to RGB")
     return parser
 
 
