@@ -192,7 +192,9 @@ int64_t resr_chain_errors(void);
  * layers, model.py:140-160). */
 typedef struct {
     int32_t n, h, w;
-    int32_t cin, cin0, in0_stride, in1_stride; /* X operand, same addressing as ResrConvDesc      */
+    int32_t cin, cin0, in0_stride, in1_stride; /* X operand, same addressing as ResrConvDesc: cin0 < cin = channels [cin0, cin) come
+                                                * from x1 (job-table launches only, not layer mode; RESR_F16X2: x1's lo tensor lies
+                                                * x_lo_offset behind it too)                       */
     int32_t cin_real;                          /* rows of dW actually written (<= cin)            */
     int32_t cout, cout_pad, g_stride;          /* G operand: channels [0,cout_pad) of g           */
     int32_t dtype, flags;                      /* RESR_CONV_UPSAMPLE_IN honoured for X; RESR_CONV_OUT_SINGLE: G is a single f16 tensor */

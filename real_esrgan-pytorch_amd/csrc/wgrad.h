@@ -8,6 +8,8 @@ namespace resr {
 
 struct WgradConv {
     const void* x0; int cin, in0_stride, cin_real;     // X: channel prefix [0,cin) of x0
+    const void* x1 = nullptr; int cin0 = 0, in1_stride = 0;   // x1 != nullptr (job-table launches only): channels [cin0, cin) come from x1 (pixel
+                                                       // stride in1_stride; same chunk stride and hi -> lo offset as x0), as ResrConvDesc's in1
     const void* g; int cout, cout_pad, g_stride;       // G: channels [0,cout_pad) of g
     long x_chunk_stride, g_chunk_stride;               // elements between 32-channel chunks of X / G (0 = 32: interleaved)
     long x_lo_off, g_lo_off;                           // RESR_F16X2: element offsets hi -> lo tensor of X / G (else 0; g_lo_off = 0: G is single f16)

@@ -1347,7 +1347,8 @@ int wgrad_batch(const WgradConv* convs, int nconv, int n, int h, int w, int dtyp
         for (int ct = 0; ct < c.cout_pad / 32; ++ct)
             for (int ck = 0; ck < c.cin / 32; ++ck) {
                 if (nr >= kMaxReduce) return fail(RESR_ERR_ARG, "wgrad: more than %d products in one batch", kMaxReduce);
-                const char* xh = (const char*)c.x0 + (size_t)ck * (c.x_chunk_stride > 0 ? c.x_chunk_stride : 32) * es;
+                const bool seg1 = c.x1 != nullptr && ck * 32 >= c.cin0;   // a chunk of the second X segment
+                const char* xh = (const char*)(seg1 ? c.x1 : c.x0) + (size_t)(seg1 ? ck - c.cin0 / 32 : ck) * (c.x_chunk_stride > 0 ? c.x_chunk_stride : 32) * es;
                 const char* gh = (const char*)c.g + (size_t)ct * (c.g_chunk_stride > 0 ? c.g_chunk_stride : 32) * es;
                 const int want_bias = (ck == 0 && c.db) ? 1 : 0;
                 ReduceJob& q = r.jobs[nr++];
@@ -1363,7 +1364,7 @@ int wgrad_batch(const WgradConv* convs, int nconv, int n, int h, int w, int dtyp
                     WgradJob& j = a.jobs[nj++];
                     j.x = xh + (part == 2 ? (size_t)c.x_lo_off * es : part == 3 ? (size_t)c.x_q_off * es : 0);
                     j.g = gh + (part == 1 ? (size_t)c.g_lo_off * es : part == 3 ? (size_t)c.g_q_off * es : 0);
-                    j.xstride_b = (unsigned)(c.in0_stride * es);
+                    j.xstride_b = (unsigned)((seg1 ? c.in1_stride : c.in0_stride) * es);
                     j.gstride_b = (unsigned)(c.g_stride * es);
                     j.slab_off = off;
                     j.mx = part == 3 ? 1u : 0u;
@@ -1448,7 +1449,9 @@ size_t wgrad_partial_bytes(const ResrWgradDesc* d) {
 int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw,
                    float* db, hipStream_t stream) {
     if (!d || !x0 || !g || !partial || !dw) return fail(RESR_ERR_ARG, "wgrad: null argument");
-    if (d->cin0 != d->cin || x1) return fail(RESR_ERR_ARG, "wgrad: two-segment X is not supported (cin0 must equal cin)");
+    const bool two_seg = d->cin0 < d->cin;
+    if (d->cin0 <= 0 || (d->cin0 & 31) || d->cin0 > d->cin || (two_seg && (!x1 || d->in1_stride <= 0)) || (!two_seg && x1))
+        return fail(RESR_ERR_ARG, "wgrad: cin0=%d of cin=%d: a positive multiple of 32, with x1 and in1_stride exactly when cin0 < cin", d->cin0, d->cin);
     // (a caller built against the version-1 header passes a shorter struct: whatever lies behind it is read as chunk strides)
     {
         const int64_t px = (int64_t)d->n * d->h * d->w;
@@ -1472,11 +1475,14 @@ int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const
     c.x_chunk_stride = (long)d->x_chunk_stride; c.g_chunk_stride = (long)d->g_chunk_stride;
     c.x_lo_off = (long)d->x_lo_offset; c.g_lo_off = g_lo; c.x_s2d_c = 0; c.g_lo_bias_only = 0;
     c.dw = dw; c.db = db; c.scale = d->scale;
+    if (two_seg) { c.x1 = x1; c.cin0 = d->cin0; c.in1_stride = d->in1_stride; }
     // more products than one launch's job table holds (or an output wider than 64 channels): the layer mode (f16, exact16)
     const int tap_products = (c.cin / 32) * (c.cout_pad / 32) * (d->dtype == RESR_F16X2 ? wgrad_x2_products() : 1);
     if ((d->dtype == RESR_F16 || d->dtype == RESR_F16X2) &&
-        (c.cout_pad > 64 || (c.cin / 32) * (c.cout_pad / 32) > kMaxReduce || tap_products > kMaxJobs))
+        (c.cout_pad > 64 || (c.cin / 32) * (c.cout_pad / 32) > kMaxReduce || tap_products > kMaxJobs)) {
+        if (two_seg) return fail(RESR_ERR_ARG, "wgrad: a two-segment X needs a job-table launch (cout_pad <= 64, at most %d tap-products)", kMaxJobs);
         return wgrad_layer(&c, d->n, d->h, d->w, d->dtype, flags, d->splits, partial, stream);
+    }
     return wgrad_batch(&c, 1, d->n, d->h, d->w, d->dtype, flags, d->splits, partial, stream);
 }
 

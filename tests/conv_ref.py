@@ -36,6 +36,25 @@ def pair_value(hi, lo):
     return hi.double() + lo.double() / 4096.0
 
 
+def pair_lo_excess(hi, lo):
+    """The structure of a STORED pair: lo is a remainder of hi, |lo| / 4096 <= 1.01 * max(2^-11 * |hi|, 2^-25) -- half an f16 ulp of hi
+    (below the normal range: half the subnormal spacing), 1 % for lo's own rounding and the binade's lower end.  The passes behind
+    rely on it: "hi decides" a sign, the q records take hi's exponent.  Returns the number of elements that break it."""
+    hi, lo = hi.double().abs(), lo.double().abs()
+    return int((~(lo / 4096.0 <= 1.01 * torch.clamp(2.0 ** -11 * hi, min=2.0 ** -25))).sum())
+
+
+def split_weights(wt):
+    """The three f16 blocks resr_pack_weights keeps of an exact16 weight (include/resr.h), as float64 in the weight's own scale:
+    (W0, W1, W2) = (f16(w * 2^12), f16(w * 2^12 - W0), f16(W0 * 2^-12)) -> (W0 / 2^12, W1 / 2^12, W2).  A pair chunk computes
+    x_hi (W0 + W1) + x_lo W2, a single chunk x (W0 + W1), with RESR_CONV_SINGLE_W16 x W0."""
+    t = wt.float() * 4096.0
+    w0 = t.half()
+    w1 = (t - w0.float()).half()
+    w2 = (w0.float() / 4096.0).half()
+    return w0.double() / 4096.0, w1.double() / 4096.0, w2.double()
+
+
 def upsample2(x):
     """Nearest x2: out[.., y, x] = in[.., y // 2, x // 2]."""
     n, c, h, w = x.shape
@@ -77,19 +96,22 @@ def correlate(x, wt, dtype=torch.float64, up=False):
 
 
 def epilogue(acc, dtype=torch.float64, bias=None, mask=None, slope=0.2, lrelu=False, prelu=None, res0=None, s0=1.0, t0=1.0,
-             res1=None, s1=1.0, t1=1.0, clamp=False):
+             res1=None, s1=1.0, t1=1.0, clamp=False, with_aux=False):
     """include/resr.h: v = acc + bias; mask / lrelu / prelu / (v*s0 + t0*res0) / (v*s1 + t1*res1) / clamp, in that order.
-    Returns (v, v before the clamp)."""
+    Returns (v, v before the clamp); with_aux: (v, v before the clamp, v after the bias and before the mask -- what
+    RESR_CONV_AUX_BEFORE_MASK stores --, v after LeakyReLU / PReLU and before the residuals -- RESR_CONV_AUX_BEFORE_RES)."""
     v = acc.to(dtype)
     sl = f32scalar(slope, dtype)
     if bias is not None:
         v = v + bias.to(dtype).view(1, -1, 1, 1)
+    before_mask = v
     if mask is not None:
         v = v * torch.where(mask > 0, torch.ones((), dtype=dtype), sl)
     if lrelu:
         v = torch.where(v > 0, v, v * sl)
     if prelu is not None:
         v = torch.where(v > 0, v, v * prelu.to(dtype).view(1, -1, 1, 1))
+    before_res = v
     if res0 is not None:
         v = v * f32scalar(s0, dtype) + f32scalar(t0, dtype) * res0.to(dtype)
     if res1 is not None:
@@ -97,7 +119,7 @@ def epilogue(acc, dtype=torch.float64, bias=None, mask=None, slope=0.2, lrelu=Fa
     pre = v
     if clamp:
         v = v.clamp(0.0, 1.0)
-    return v, pre
+    return (v, pre, before_mask, before_res) if with_aux else (v, pre)
 
 
 def conv3x3(x, wt, dtype=torch.float64, up=False, **epi):
@@ -120,38 +142,55 @@ def wgrad(x, g, scale, dtype=torch.float64, up=False):
 
 
 # ---- the rule (stated in the module docstring of tests/test_gpu_kernels.py) ------------------------------------------------------
+def wgrad_lolo(x, g, scale, up=False):
+    """The second term of the exact16 weight-gradient rule, per element of dW: 2^-22 * scale * wgrad(|X|, |G|).  The kernel issues
+    three tap-products per product, dW = X_hi^T G_hi + 2^-12 (X_hi^T G_lo + X_lo^T G_hi), and drops X_lo^T G_lo; each lo half is at
+    most 2^-11 of its operand (pair_lo_excess), so the dropped product of one pixel is at most 2^-22 |x| |g| and their sum at most
+    this.  db has no such term: it is the plain sum of G's two halves."""
+    return wgrad(x.abs(), g.abs(), abs(scale), torch.float64, up)[0] * 2.0 ** -22
+
+
 def allowance(ref64, ref32):
-    """(A, e32): e32 = max |ref32 - ref64|, A = max(4 * e32, one fp32 ulp of max |ref64|)."""
+    """(A, e32): e32 = max |ref32 - ref64|, A = max(4 * e32, one fp32 ulp of max |ref64|).  ref32 = None (a "pair" judgement, where A
+    plays no part and nobody should pay for the plain fp32 evaluation): (0, 0)."""
+    if ref32 is None:
+        return 0.0, 0.0
     ref64 = ref64.double()
     e32 = float((ref32.double() - ref64).abs().max())
     floor = float(np.spacing(np.float32(float(ref64.abs().max()))))
     return max(4.0 * e32, floor), e32
 
 
-def bound(ref64, A, kind):
-    """The per-element bound on |got - ref64|.  kind: "f32" (any fp32 output), "f16" (an f16 store: + half an ulp of the element),
-    "pair" (exact16 pair / exact16 fp32 outputs: the per-tensor bound of the x2-plan tests; A plays no part)."""
+def bound(ref64, A, kind, extra=None):
+    """The per-element bound on |got - ref64|.  kind: "f32" (any fp32 output; `extra`: a per-element term on top of A -- wgrad_lolo
+    for an exact16 dW), "f16" (an f16 store: + half an ulp of the element), "pair" (exact16 pair / exact16 fp32 outputs: the
+    per-tensor bound of the x2-plan tests; A plays no part), "pair16" (the hi tensor of an exact16 pass stored alone,
+    RESR_CONV_OUT_SINGLE: the pair bound for the value the store rounds + half an f16 ulp of the element for the store, as
+    tests/test_gpu_x2_plan.py judges its single-f16 growth planes)."""
     ref64 = ref64.double()
     if kind == "f32":
-        return torch.full_like(ref64, A)
+        return torch.full_like(ref64, A) if extra is None else A + extra.double()
     if kind == "f16":
         return A + torch.clamp(F16_HALF_ULP * ref64.abs(), min=F16_SUBNORMAL)
+    pair = PAIR_TENSOR_REL * max(1.0, float(ref64.abs().max()))
     if kind == "pair":
-        return torch.full_like(ref64, PAIR_TENSOR_REL * max(1.0, float(ref64.abs().max())))
+        return torch.full_like(ref64, pair)
+    if kind == "pair16":
+        return pair + torch.clamp(F16_HALF_ULP * ref64.abs(), min=F16_SUBNORMAL)
     raise ValueError(kind)
 
 
-def judge(got, ref64, ref32, kind):
+def judge(got, ref64, ref32, kind, extra=None):
     """Returns a record {cpu32_err, allowance, kernel_err, ratio, bad, worst}: ratio = max over the tensor of |got - ref64| / bound,
     bad = number of elements beyond their bound (NaNs count), allowance = A (f32, f16) or the tensor bound (pair)."""
     ref64 = ref64.double()
     A, e32 = allowance(ref64, ref32)
-    b = bound(ref64, A, kind)
+    b = bound(ref64, A, kind, extra)
     err = (got.double() - ref64).abs()
     bad = ~(err <= b)
     ratio = torch.where(torch.isnan(err), torch.full_like(err, float("inf")), err / b)
     worst = int(ratio.argmax())
-    return {"cpu32_err": e32, "allowance": float(b.max()) if kind == "pair" else A, "kernel_err": float(err.max()), "ratio": float(ratio.max()),
+    return {"cpu32_err": e32, "allowance": float(b.min()) if kind.startswith("pair") else A, "kernel_err": float(err.max()), "ratio": float(ratio.max()),
             "bad": int(bad.sum()), "frac_bad": float(bad.double().mean()), "worst": worst, "got": float(got.reshape(-1)[worst]),
             "want": float(ref64.reshape(-1)[worst])}
 

@@ -132,3 +132,25 @@ class Operand:
         self.shape = self.exact.shape
         self.t = dev(self.flat)
         self.ptr = self.t.data_ptr()
+
+
+# ---- the record of the conv / weight-gradient judgements (test_gpu_kernels.py, test_gpu_x2_plan.py) -------------------------------
+def merge_conv_diag(diag_dir, records, restart=False):
+    """Add `records` ({case: record of tests/conv_ref.judge + dtype, kind}) to <diag_dir>/test_gpu_conv_kernels.json and renew its
+    "worst" table (the worst ratio per dtype).  restart: drop what an earlier run left first."""
+    import json
+    import os
+    path = os.path.join(diag_dir, "test_gpu_conv_kernels.json")
+    if restart and os.path.exists(path):
+        os.remove(path)
+    cases = {}
+    if os.path.exists(path):
+        with open(path) as f:
+            cases = json.load(f)["cases"]
+    cases.update(records)
+    worst = {}
+    for name, rec in cases.items():
+        if rec["dtype"] not in worst or rec["ratio"] > worst[rec["dtype"]]["ratio"]:
+            worst[rec["dtype"]] = {"case": name, "ratio": rec["ratio"]}
+    with open(path, "w") as f:
+        json.dump({"worst": worst, "cases": cases}, f, indent=1, sort_keys=True)

@@ -1,6 +1,10 @@
 """CPU: tests/conv_ref.py is right (against torch's own operators and float64 autograd), and the rule it carries has the power the
 GPU tests rely on: the plain fp32 evaluation of every case passes with a ratio <= 0.25, every wrong kernel listed below is
-rejected.  A "wrong kernel" is the float64 reference with ONE defect, stored as a correct kernel would store it."""
+rejected.  A "wrong kernel" is the float64 reference with ONE defect, stored as a correct kernel would store it.  The same for
+exact16: pair_split leaves lo a remainder of hi; the pair rule rejects a lost lo tensor (in0, in1, res0, res1, one chunk of six), a
+lost W1 block, a tap dropped at a seam and a mask decided by a zero hi half; the weight-gradient rule A + wgrad_lolo rejects X's or
+G's lo tensor lost and one tap-product skipped in one pixel split -- while the exact16 arithmetic itself (x_lo (w - W2) and
+X_lo^T G_lo dropped as documented) passes with room."""
 import numpy as np
 import pytest
 import torch
@@ -194,3 +198,187 @@ def test_rule_rejects_wrong_weight_gradients(dtype_name, up):
     m[:, :, 1, 1] -= 0.5 * gy[1, :, h - 1, w - 1].double().view(-1, 1) * xin[1, :, h - 1, w - 1].double().view(1, -1)
     _rejected(m, dw64, dw32, "f32", "border pixel (dW)")
     _rejected(db64 - 0.5 * gy[1, :, h - 1, w - 1].double(), db64, db32, "f32", "border pixel (db)")
+
+
+# ---- the added epilogue values -------------------------------------------------------------------------------------------------------
+def test_epilogue_aux_values_against_torch():
+    """with_aux: the value after the bias and before the mask (RESR_CONV_AUX_BEFORE_MASK), the value after LeakyReLU and before the
+    residuals (RESR_CONV_AUX_BEFORE_RES), on the discriminator's two uses and on a pass that has every step."""
+    x, wt, bias, r0, r1, mk = _case("f32", cin=40, cout=12, n=2, h=6, w=10)
+    sl, s0, s1, t1 = (float(np.float32(v)) for v in (0.2, 0.2, 0.3, 0.5))
+    conv = F.conv2d(x.double(), wt.double(), bias.double(), padding=1)
+    conv0 = F.conv2d(x.double(), wt.double(), None, padding=1)
+    assert len(R.conv3x3(x, wt, F64, bias=bias)) == 2                       # the callers that do not ask keep their two values
+    v, pre, bm, br = R.conv3x3(x, wt, F64, bias=bias, lrelu=True, slope=0.2, res0=r0, s0=0.2, t0=1.0, with_aux=True)
+    act = F.leaky_relu(conv, sl)
+    assert (bm - conv).abs().max().item() < 1e-13 and (br - act).abs().max().item() < 1e-13
+    assert (v - (act * s0 + r0.double())).abs().max().item() < 1e-13 and torch.equal(v, pre)
+    assert (br - v).abs().max().item() > 0.1                                   # it is not the output
+    v, pre, bm, br = R.conv3x3(x, wt, F64, mask=mk, slope=0.2, with_aux=True)
+    masked = conv0 * torch.where(mk > 0, 1.0, sl)
+    assert (bm - conv0).abs().max().item() < 1e-13 and (v - masked).abs().max().item() < 1e-13 and torch.equal(br, v)
+    assert (bm - v).abs().max().item() > 0.1
+    v, pre, bm, br = R.conv3x3(x, wt, F64, bias=bias, mask=mk, lrelu=True, slope=0.2, res0=r0, s0=0.2, t0=1.0, res1=r1, s1=0.3, t1=0.5,
+                               clamp=True, with_aux=True)
+    want_br = F.leaky_relu(conv * torch.where(mk > 0, 1.0, sl), sl)
+    want = (want_br * s0 + r0.double()) * s1 + t1 * r1.double()
+    assert (bm - conv).abs().max().item() < 1e-13 and (br - want_br).abs().max().item() < 1e-13
+    assert (pre - want).abs().max().item() < 1e-13 and (v - want.clamp(0, 1)).abs().max().item() < 1e-13
+    slopes = torch.rand(12, generator=torch.Generator().manual_seed(1)) * 2 - 0.5
+    v, pre, bm, br = R.conv3x3(x, wt, F64, bias=bias, prelu=slopes, res0=r0, s0=0.2, t0=1.0, with_aux=True)
+    assert (br - F.prelu(conv, slopes.double())).abs().max().item() < 1e-13
+
+
+# ---- exact16: the structure of a pair, the pair rule and the weight-gradient rule -----------------------------------------------------
+def test_pair_split_leaves_lo_a_remainder_of_hi():
+    """R.pair_lo_excess (what the GPU tests ask of every stored pair) holds for pair_split of fp32 data of every size -- normal,
+    f16-subnormal, below the subnormals (hi = 0), zero, binade ends -- and notices a lo that is no remainder."""
+    g = torch.Generator().manual_seed(4)
+    v = torch.randn(20000, generator=g)
+    edge = torch.tensor([0.0, -0.0, 1.0, 1.0 + 2.0 ** -11, 1.0 - 2.0 ** -12, 2.0 ** -14, 2.0 ** -14 * (1 + 2.0 ** -11), 2.0 ** -24, 2.0 ** -25,
+                         2.0 ** -25 * 0.999, 1e-9, -1e-9, 60000.0, 2047.5, 0.1, 1.0 / 3.0])
+    v = torch.cat([v, v * 100.0, v * 1e-3, v * 1e-5, v * 1e-7, v * 1e-9, torch.zeros(64), edge, -edge])
+    hi, lo = R.pair_split(v)
+    assert (hi == 0).sum() > 20000 and ((hi != 0) & (hi.abs() < 2.0 ** -14)).sum() > 1000      # both small ranges are in the data
+    assert R.pair_lo_excess(hi, lo) == 0
+    assert (R.pair_value(hi, lo) - v.double()).abs().max().item() <= 2.0 ** -22 * v.abs().max().item()
+    # a hi half that was truncated instead of rounded leaves remainders of up to a whole ulp; a lo scaled wrongly is no remainder
+    hi_t = _truncate_f16(v).half()
+    lo_t = ((v.double() - hi_t.double()) * 4096.0).half()
+    assert R.pair_lo_excess(hi_t, lo_t) > 1000
+    assert R.pair_lo_excess(hi, (lo.float() * 4.0).half()) > 1000
+    assert R.pair_lo_excess(torch.zeros(4).half(), torch.full((4,), 0.5).half()) == 4          # hi = 0: |value| must stay below 2^-25
+
+
+class _Pair:
+    """An exact16 operand: hi (float64), lo (float64, in the operand's own scale: the stored lo / 4096), value = hi + lo."""
+
+    def __init__(self, t):
+        hi, lo = R.pair_split(t)
+        self.hi, self.lo = hi.double(), lo.double() / 4096.0
+        self.value = self.hi + self.lo
+
+
+def _x2_acc(xh, xl, wt, w1=True):
+    """The exact16 accumulator in float64: x_hi (W0 + W1) + x_lo W2 -- everything the kernel computes; the documented drop is
+    x_lo (w - W2)."""
+    w0, w1_, w2 = R.split_weights(wt)
+    return R.correlate(xh, w0 + w1_ if w1 else w0, F64) + R.correlate(xl, w2, F64)
+
+
+def _store_pair(v):
+    """What a correct kernel stores of an fp32 result as a pair, joined."""
+    hi, lo = R.pair_split(v.float())
+    assert R.pair_lo_excess(hi, lo) == 0
+    return R.pair_value(hi, lo)
+
+
+def _pair_judged(got, ref64, what, reject, below=0.25):
+    """Judge `got`, stored as a pair, by the pair rule: a mutant must be rejected, an honest result pass with its ratio under `below`."""
+    rec = R.judge(_store_pair(got), ref64, None, "pair")
+    print(f"{what}: ratio {rec['ratio']:.3g} beyond {rec['frac_bad']:.2%}")
+    if reject:
+        assert rec["bad"] > 0, (what, rec)
+    else:
+        assert rec["bad"] == 0 and rec["ratio"] < below, (what, rec)
+    return rec
+
+
+def _x2_case(cin, cout, n, h, w, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = _Pair(torch.randn(n, cin, h, w, generator=g))
+    wt = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (cin * 9)) ** 0.5
+    bias = torch.randn(cout, generator=g) * 0.1
+    r0, r1 = _Pair(torch.randn(n, cout, h, w, generator=g)), _Pair(torch.randn(n, cout, h, w, generator=g))
+    return g, x, wt, bias, r0, r1
+
+
+def test_pair_rule_rejects_a_lost_input_lo_or_weight_block():
+    """rdb_conv3_2seg of tests/test_gpu_kernels.py (cin 128 in two segments of 64, cout 32, LeakyReLU, 1 x 33 x 32): the lo tensor
+    of either segment lost, the W1 block lost.  The exact arithmetic -- x_lo (w - W2) dropped as documented -- and the plain fp32
+    result stored as a pair pass with room."""
+    _, x, wt, bias, _, _ = _x2_case(128, 32, 1, 33, 32, 21)
+    kw = dict(bias=bias, lrelu=True, slope=0.2)
+    ref64 = R.conv3x3(x.value, wt, F64, **kw)[0]
+    _pair_judged(R.epilogue(_x2_acc(x.hi, x.lo, wt), F64, **kw)[0], ref64, "exact16 arithmetic", False)
+    # (ONE fp32 accumulator over the 1152 products, the slowest-converging order there is: the yardstick of the f32 rule sits at 0.54 here)
+    _pair_judged(R.conv3x3(x.value, wt, F32, **kw)[0], ref64, "plain fp32", False, below=1.0)
+    for what, sl in (("in0 lo", slice(0, 64)), ("in1 lo", slice(64, 128))):
+        xl = x.lo.clone()
+        xl[:, sl] = 0.0
+        rec = _pair_judged(R.epilogue(_x2_acc(x.hi, xl, wt), F64, **kw)[0], ref64, what + " dropped", True)
+        assert rec["frac_bad"] > 0.2, rec
+    _pair_judged(R.epilogue(_x2_acc(x.hi, x.lo, wt, w1=False), F64, **kw)[0], ref64, "W1 dropped", True)
+
+
+@pytest.mark.parametrize("where", ["col31", "col32", "row7", "row8"])
+def test_pair_rule_rejects_lost_residual_halves_chunks_and_seam_taps(where):
+    """rdb_conv5_res (cin 192, cout 64, two residuals, 2 x 16 x 70): the lo tensor of either residual lost, the lo plane of ONE of
+    the six input chunks lost (a pair chunk read as a single one), one tap of one channel lost next to a tile seam."""
+    _, x, wt, bias, r0, r1 = _x2_case(192, 64, 2, 16, 70, 22)
+    kw = dict(bias=bias, res0=r0.value, s0=0.2, t0=1.0, res1=r1.value, s1=0.2, t1=0.5)
+    acc = _x2_acc(x.hi, x.lo, wt)
+    ref64 = R.conv3x3(x.value, wt, F64, **kw)[0]
+    _pair_judged(R.epilogue(acc, F64, **kw)[0], ref64, "exact16 arithmetic", False)
+    if where == "col31":      # (the seam-independent mutants once)
+        _pair_judged(R.epilogue(acc, F64, **dict(kw, res0=r0.hi))[0], ref64, "res0 lo dropped", True)
+        _pair_judged(R.epilogue(acc, F64, **dict(kw, res1=r1.hi))[0], ref64, "res1 lo dropped", True)
+        xl = x.lo.clone()
+        xl[:, 96:128] = 0.0
+        _pair_judged(R.epilogue(_x2_acc(x.hi, xl, wt), F64, **kw)[0], ref64, "lo of chunk 3 of 6 dropped", True)
+    c, k = 17, int(where[3:])
+    w0, w1, _ = R.split_weights(wt)
+    m = acc.clone()
+    if where.startswith("col"):
+        dx = 2 if k == 31 else 0
+        m[:, :, :, k] -= (w0 + w1)[:, c, 1, dx].view(1, -1, 1) * x.hi[:, c, :, k + dx - 1].unsqueeze(1)
+    else:
+        dy = 2 if k % 8 == 7 else 0
+        m[:, :, k, :] -= (w0 + w1)[:, c, dy, 1].view(1, -1, 1) * x.hi[:, c, k + dy - 1, :].unsqueeze(1)
+    _pair_judged(R.epilogue(m, F64, **kw)[0], ref64, "tap dropped at " + where, True)
+
+
+def test_pair_rule_rejects_a_mask_decided_by_hi_alone_where_hi_is_zero():
+    """mask_only (cin 64, cout 64, no bias, 1 x 40 x 72) with a saved activation a third of whose values are +-1e-9: their hi half is
+    zero and their sign is the lo half's (include/resr.h, mask_lo_offset)."""
+    g, x, wt, _, _, _ = _x2_case(64, 64, 1, 40, 72, 23)
+    act = torch.randn(1, 64, 40, 72, generator=g)
+    act = torch.where(torch.rand(act.shape, generator=g) < 0.33, act.sign() * 1e-9, act)
+    mk = _Pair(act)
+    assert ((mk.hi == 0) & (mk.lo > 0)).sum() > 1000
+    acc = _x2_acc(x.hi, x.lo, wt)
+    ref64 = R.conv3x3(x.value, wt, F64, mask=mk.value, slope=0.2)[0]
+    _pair_judged(R.epilogue(acc, F64, mask=mk.value, slope=0.2)[0], ref64, "exact16 arithmetic", False)
+    _pair_judged(R.epilogue(acc, F64, mask=mk.hi, slope=0.2)[0], ref64, "mask from hi alone", True)
+
+
+def test_x2_wgrad_rule_rejects_lost_halves_and_a_skipped_tap_product():
+    """w_64_32 (cin 64, cout 32, 2 x 19 x 45) under |got - ref64| <= A + wgrad_lolo: the three tap-products with X_lo^T G_lo dropped
+    pass; X's lo tensor lost, G's lost (dW and db), and the (x_lo, g_hi) tap-product skipped in one of three pixel splits do not."""
+    g = torch.Generator().manual_seed(7)
+    n, cin, cout, h, w = 2, 64, 32, 19, 45
+    x, gy = _Pair(torch.randn(n, cin, h, w, generator=g)), _Pair(torch.randn(n, cout, h, w, generator=g))
+    dw64, db64 = R.wgrad(x.value, gy.value, 0.5, F64)
+    dw32, db32 = R.wgrad(x.value, gy.value, 0.5, F32)
+    extra = R.wgrad_lolo(x.value, gy.value, 0.5)
+
+    def dw_of(*products):
+        return sum(R.wgrad(a, b, 0.5, F64)[0] for a, b in products)
+    three = ((x.hi, gy.hi), (x.hi, gy.lo), (x.lo, gy.hi))
+    lolo = dw_of((x.lo, gy.lo))
+    assert (lolo.abs() <= extra).all()                    # the term is what it claims to be: a bound of the dropped product
+    rec = R.judge(dw_of(*three).float(), dw64, dw32, "f32", extra)
+    print(f"three tap-products: ratio {rec['ratio']:.3g}; lo.lo / bound {float((lolo.abs() / R.bound(dw64, rec['allowance'], 'f32', extra)).max()):.3g}")
+    assert rec["bad"] == 0 and rec["ratio"] < 0.5, rec
+    assert R.judge(db64.float(), db64, db32, "f32")["bad"] == 0
+    for what, products in (("X lo", three[:2]), ("G lo", (three[0], three[2]))):
+        rec = R.judge(dw_of(*products).float(), dw64, dw32, "f32", extra)
+        print(f"{what} dropped: ratio {rec['ratio']:.3g} beyond {rec['frac_bad']:.2%}")
+        assert rec["bad"] > 0 and rec["frac_bad"] > 0.5, (what, rec)
+    assert R.judge(R.wgrad(x.value, gy.hi, 0.5, F64)[1].float(), db64, db32, "f32")["bad"] > 0      # db from G's hi tensor alone
+    band = torch.zeros(n, 1, h, w, dtype=F64)
+    band[0, :, :13] = 1.0                                  # a third of the pixels: the first of three pixel splits
+    skipped = dw_of(*three) - R.wgrad(x.lo, gy.hi * band, 0.5, F64)[0]
+    rec = R.judge(skipped.float(), dw64, dw32, "f32", extra)
+    print(f"(x_lo, g_hi) skipped in one split: ratio {rec['ratio']:.3g} beyond {rec['frac_bad']:.2%}")
+    assert rec["bad"] > 0, rec

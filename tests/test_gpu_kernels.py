@@ -12,9 +12,23 @@ store's rounding; implemented once in tests/conv_ref.py (validated on the CPU by
   * f16 outputs: every element has |got - ref64| <= A + max(2^-11 * 1.01 * |ref64|, 2^-24): half an ulp of EACH element (the f16
     subnormal spacing as a floor), not of the tensor's maximum.
   * exact16 pair outputs and exact16 fp32 NCHW outputs: joined in float64, every element within 2e-6 * max(1, max |ref64|), as
-    test_conv_reads_single_chunks_and_writes_single_output (tests/test_gpu_x2_plan.py) judges its pair case.
-  * sign words equal (stored > 0) exactly.
-  * the RESR_CONV_CLAMP01 pass-mask may differ from the reference's only where the reference's pre-clamp value lies within A of 0 or 1.
+    test_conv_reads_single_chunks_and_writes_single_output (tests/test_gpu_x2_plan.py) judges its pair case ("pair": e32 and A play no
+    part, so the exact16-only tests do not compute the fp32 yardstick); an exact16 output stored as its hi tensor alone
+    (RESR_CONV_OUT_SINGLE): that bound + half an f16 ulp of the element ("pair16").
+  * every stored exact16 pair: |lo| / 4096 <= 1.01 * max(2^-11 * |hi|, 2^-25) -- lo is a remainder of hi (conv_ref.pair_lo_excess).
+  * exact16 dW: every element within A + 2^-22 * scale * wgrad(|X|, |G|)[element] (conv_ref.wgrad_lolo: the worst case of the dropped
+    X_lo^T G_lo product; A from the plain fp32 evaluation on the pair values); exact16 db: within A.  With RESR_CONV_OUT_SINGLE G is
+    its hi tensor, in the reference too.
+  * sign words equal (stored > 0) exactly (a pair: hi + lo / 4096; a single-f16 output: its hi tensor).
+  * the RESR_CONV_CLAMP01 pass-mask may differ from the reference's only where the reference's pre-clamp value lies within A (exact16:
+    within the pair bound) of 0 or 1.
+  * RESR_CONV_AUX_BEFORE_MASK / _RES: the aux tensor against conv_ref.epilogue's value at that point, by its dtype's rule, like out.
+What runs as a single exact16 pass: the compact net's passes (test_conv3x3_prelu, test_conv3x3_cin3_forward, test_conv3x3_nchw_tail),
+every epilogue form of launch_ws, partial cout tiles, pair / single chunks across two segments, chunk-planar operands and 16-row tiles
+(test_exact16_conv_pass), the aux-before forms (test_aux_before_forms, all three dtypes), the job-table weight gradients
+(test_exact16_wgrad*) and the layer-mode ones (test_wgrad_layer_mode_exact16).  Outputs of these tests lie between guards: every
+element in range written, nothing outside it -- the channels between cout and the pixel stride and the gap between a pair's halves
+included.
 Every judgement is written to <diag_dir>/test_gpu_conv_kernels.json: case, cpu32_err, allowance, kernel_err, ratio (the re-runs
 of the fallback kernels in a subprocess add theirs under their knob's name).  Everything else here compares against plain fp32
 torch on the CPU."""
@@ -44,26 +58,16 @@ def U():
 
 @pytest.fixture(scope="module", autouse=True)
 def _write_diag(diag_dir):
-    path = os.path.join(diag_dir, "test_gpu_conv_kernels.json")
-    if not VARIANT and os.path.exists(path):
-        os.remove(path)                      # the main run starts the file, its re-runs (which end before it does) add to it
+    import tests.gpu_util as U
+    if not VARIANT:
+        U.merge_conv_diag(diag_dir, {}, restart=True)   # the main run starts the file, its re-runs (which end before it does) add to it
     yield
-    cases = {}
-    if os.path.exists(path):
-        with open(path) as f:
-            cases = json.load(f)["cases"]
-    cases.update(DIAG)
-    worst = {}
-    for name, rec in cases.items():
-        if rec["dtype"] not in worst or rec["ratio"] > worst[rec["dtype"]]["ratio"]:
-            worst[rec["dtype"]] = {"case": name, "ratio": rec["ratio"]}
-    with open(path, "w") as f:
-        json.dump({"worst": worst, "cases": cases}, f, indent=1, sort_keys=True)
+    U.merge_conv_diag(diag_dir, DIAG)
 
 
-def judge(case, dtype_name, got, ref64, ref32, kind):
-    """The rule of the module docstring; returns the allowance (A, or the tensor bound of a pair)."""
-    rec = R.judge(got, ref64, ref32, kind)
+def judge(case, dtype_name, got, ref64, ref32, kind, extra=None):
+    """The rule of the module docstring; returns the allowance (A, or the tensor bound of a pair).  extra: tests/conv_ref.wgrad_lolo."""
+    rec = R.judge(got, ref64, ref32, kind, extra)
     rec.update(dtype=dtype_name, kind=kind)
     name = (VARIANT + "/" if VARIANT else "") + case
     DIAG[name] = rec
@@ -289,11 +293,12 @@ def test_conv3x3_one_role_and_wgrad_pair_kernel_fallbacks():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 
-def judge_wgrad(case, dtype_name, dw, db, x, gy, scale, up):
-    """dW and db of one launch against tests/conv_ref.wgrad on the values the kernel was given (both are fp32 outputs)."""
+def judge_wgrad(case, dtype_name, dw, db, x, gy, scale, up, lolo=False):
+    """dW and db of one launch against tests/conv_ref.wgrad on the values the kernel was given (both are fp32 outputs).  lolo: the
+    exact16 rule -- dW's bound is A + conv_ref.wgrad_lolo, the worst case of the dropped X_lo^T G_lo product."""
     ref_w, ref_b = R.wgrad(x, gy, scale, F64, up)
     w32, b32 = R.wgrad(x, gy, scale, F32, up)
-    judge(case + "_dW", dtype_name, dw.cpu(), ref_w, w32, "f32")
+    judge(case + "_dW", dtype_name, dw.cpu(), ref_w, w32, "f32", R.wgrad_lolo(x, gy, scale, up) if lolo else None)
     judge(case + "_db", dtype_name, db.cpu(), ref_b, b32, "f32")
 
 
@@ -416,6 +421,7 @@ def test_wgrad_layer_mode_exact16(U, case, products, diag_dir):
         json.dump({"rel_w": rel_w, "rel_b": rel_b}, f)
     if products == 3:
         assert rel_w < 5e-6 and rel_b < 5e-6, (rel_w, rel_b)
+        judge_wgrad(f"wgrad_x2_{name}", "exact16", dw, db, xv, gv, 1.0, up, lolo=True)     # and element by element
     else:
         assert 1e-5 < rel_w < 2e-3 and rel_b < 2e-3, (rel_w, rel_b)    # the hi-only form drops the 2^-12 terms: visibly coarser, still a gradient
 
@@ -795,3 +801,396 @@ def test_wgrad_small_geometry(U, case, dtype_name, splits):
     L.check(L.lib().resr_conv3x3_wgrad(C.byref(d), L.ptr(xb), None, L.ptr(gb), L.ptr(partial), L.ptr(dw.body), L.ptr(db.body),
                                        L.stream_ptr()), "resr_conv3x3_wgrad")
     judge_wgrad(f"wgrad_{name}_s{splits}_{dtype_name}", dtype_name, dw.read().reshape(cout, cin, 3, 3), db.read(), x, gy, 0.5, False)
+
+
+# ---- exact16 (RESR_F16X2), one pass at a time: conv3x3_ws_x2_mt1.hip / conv3x3_ws_x2_mt2.hip and the three tap-products of wgrad.hip ----
+class GuardedWhere(Guarded):
+    """Guarded, for an output that owns only part of its range (the real channels of a padded pixel stride; the hi tensor of a
+    single-f16 output): `owned` (bool, one per element) says which.  Every owned element must have been written and no other --
+    the channels between cout and the pixel stride, the gap between the hi and the lo tensor, a lo tensor nobody asked for."""
+
+    def __init__(self, owned, tdtype):
+        super().__init__(owned.numel(), tdtype)
+        self.owned = owned.reshape(-1)
+
+    def read(self):
+        torch.cuda.synchronize()
+        bits = self.t.view(self.idt).cpu()
+        assert (bits[:GUARD] == self.sent).all(), "the guard in front of the output was written"
+        assert (bits[GUARD + self.count:] == self.sent).all(), "the guard behind the output was written"
+        wrote = bits[GUARD:GUARD + self.count] != self.sent
+        missed = (self.owned & ~wrote).nonzero()
+        assert missed.numel() == 0, f"{missed.numel()} elements in range never written, first at {int(missed[0])}"
+        stray = (wrote & ~self.owned).nonzero()
+        assert stray.numel() == 0, f"{stray.numel()} elements outside the output's channels written, first at {int(stray[0])}"
+        return self.body.cpu()
+
+
+# elements between an operand's hi tensor and its lo tensor, on top of the hi tensor's size: every operand of a pass gets a hi -> lo
+# offset of its own, so that a kernel that takes one operand's offset for another's reads (or writes) the wrong data
+GAP = {"in0": 8, "in1": 24, "res0": 40, "res1": 56, "mask": 72, "out": 88}
+
+
+class Layout:
+    """Where the elements of an [n,h,w,c] operand or output sit in device memory: interleaved NHWC with a padded pixel stride and the
+    channels at `offset` inside the pixel, or chunk-planar [c/32][n,h,w,32].  exact16: the hi tensor, behind it (after `gap`
+    elements of nobody's) the lo tensor; single: an exact16 output stored as its hi tensor alone (the lo tensor must stay untouched).
+    index[n,h,w,c]: the element's position in the hi tensor."""
+
+    def __init__(self, L, dtype, n, h, w, c, stride=0, offset=0, gap=0, planar=False, single=False):
+        px = n * h * w
+        pix, ch = torch.arange(px).view(n, h, w, 1), torch.arange(c)
+        if planar:
+            assert c % 32 == 0 and offset == 0
+            self.index, self.size = (ch // 32) * (px * 32) + pix * 32 + ch % 32, (c // 32) * px * 32
+            self.pixel_stride, self.chunk_stride = 32, px * 32
+        else:
+            self.index, self.size = pix * stride + offset + ch, px * stride
+            self.pixel_stride, self.chunk_stride = stride, 0
+        self.pair, self.single, self.offset = dtype == L.RESR_F16X2, single, offset
+        self.tdtype = _tdtype(L, dtype)
+        self.lo_offset = self.size + gap if self.pair else 0
+        self.total = self.lo_offset + self.size if self.pair else self.size
+
+    def upload(self, x, poison_lo=None):
+        """x: NCHW fp32 (cpu).  Sets .t (device, flat), .value and .hi (NCHW float64: what the kernel is given, and its hi half);
+        poison_lo: a channel slice whose lo elements hold garbage (single chunks: never to be read)."""
+        nhwc = x.permute(0, 2, 3, 1)
+        buf = torch.zeros(self.total, dtype=self.tdtype)
+        if self.pair:
+            hi, lo = R.pair_split(nhwc)
+            self.value, self.hi = R.pair_value(hi, lo).permute(0, 3, 1, 2), hi.double().permute(0, 3, 1, 2)
+            if poison_lo is not None:
+                lo = lo.clone()
+                lo[..., poison_lo] = 777.0
+            buf[self.index], buf[self.index + self.lo_offset] = hi, lo
+        else:
+            q = nhwc.to(self.tdtype)
+            self.value = self.hi = q.double().permute(0, 3, 1, 2)
+            buf[self.index] = q
+        self.t = buf.cuda()
+        return self
+
+    def ptr(self, U):
+        return U.sptr(self.t, self.offset)
+
+    def guarded(self):
+        owned = torch.zeros(self.total, dtype=torch.bool)
+        owned[self.index] = True
+        if self.pair and not self.single:
+            owned[self.index + self.lo_offset] = True
+        self.out = GuardedWhere(owned, self.tdtype)
+        return self.out
+
+    def out_ptr(self):
+        return C.c_void_p(self.out.body.data_ptr() + self.offset * self.out.body.element_size())
+
+    def result(self):
+        """The stored output as its NCHW float64 value (a pair joined, after the check that its lo half is a remainder of its hi
+        half: conv_ref.pair_lo_excess)."""
+        flat = self.out.read()
+        hi = flat[self.index]
+        if self.pair and not self.single:
+            lo = flat[self.index + self.lo_offset]
+            assert R.pair_lo_excess(hi, lo) == 0, "a stored lo half is no remainder of its hi half"
+            return R.pair_value(hi, lo).permute(0, 3, 1, 2)
+        return hi.double().permute(0, 3, 1, 2)
+
+
+def _sign_words(n, h, w, cout):
+    return Guarded(n * h * w * ((cout + 31) // 32), torch.float32)     # (read as uint32 words; the sentinel is no word a test meets)
+
+
+def _sign_bits(words, n, h, w, cout):
+    wd = words.view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    cp = (cout + 31) // 32 * 32
+    return ((wd.unsqueeze(-1) >> torch.arange(32)) & 1).reshape(n, h, w, cp)[..., :cout].permute(0, 3, 1, 2).bool()
+
+
+_CC = {c[0]: c[1:] for c in CONV_CASES}
+X2_CONV_CASES = [
+    # id, form of launch_ws (conv3x3_ws.h), (cin, cin0, cout, flags, n, h, w) -- by name: the shape of that CONV_CASES entry --, options
+    ("rdb_conv1", 0, "rdb_conv1", {}),
+    ("up_conv", 0, "up_conv", {}),
+    ("rdb_conv3_2seg", 0, "rdb_conv3_2seg", {}),
+    ("two_seg_5chunks", 0, "two_seg_5chunks", {}),
+    ("mask_only", 1, "mask_only", {}),
+    ("mask_only_hi_alone", 1, "mask_only", {"mask_lo0": True}),        # mask_lo_offset = 0: the mask's hi tensor decides alone
+    ("dgrad_mask", 3, "dgrad_mask", {}),
+    ("res0_only", 2, "res0_only", {}),
+    ("rdb_conv5_res", 6, "rdb_conv5_res", {}),
+    ("signbits32", 16, "signbits32", {}),
+    ("signbits64", 16, "signbits64", {}),
+    ("signbits32_single", 16, "signbits32", {"out_single": True}),     # RESR_CONV_OUT_SINGLE: the lo tensor stays untouched
+    ("maskbits32", 33, "maskbits32", {}),
+    ("maskbits64", 33, "maskbits64", {}),
+    ("conv4_nchw", 15, "conv4_nchw", {}),
+    ("cout24_res", 15, "cout24_res", {}),
+    ("cout48_res", 15, "cout48_res", {}),
+    ("lrelu_slope1.5", 15, "rdb_conv1", {"slope": 1.5}),               # a slope outside [0, 1]: no max(v, slope v) form
+    ("cout8", 0, "cout8", {}),
+    ("cout16", 0, "cout16", {}),
+    ("cout24", 0, "cout24", {}),
+    ("cout48", 0, "cout48", {}),
+    # x2_pair_chunks across the segments: chunks 0-2 pairs, chunk 3 single -- in1 holds one of each, the single one's lo plane poisoned
+    ("pair_chunks3_2seg", 0, (128, 64, 32, "lrelu", 1, 33, 32), {"pair_chunks": 3}),
+    ("pair_chunks3_2seg_w16", 0, (128, 64, 32, "lrelu", 1, 33, 32), {"pair_chunks": 3, "single_w16": True}),
+    ("planar_small", 16, (64, 64, 32, "lrelu,signbits", 1, 20, 24), {"planar": True}),
+    # 16-row tiles (chosen when the launch has at least as many of them as the device has CUs): 7 x 5 x 8 = 280 tiles, the last tile
+    # row 8 of 16 rows, the last tile column 8 of 32 columns
+    ("rows16_32", 16, (64, 64, 32, "lrelu,signbits", 8, 72, 200), {}),
+    ("rows16_64", 2, (64, 64, 64, "res0", 8, 72, 200), {}),
+]
+
+
+@pytest.mark.parametrize("case", X2_CONV_CASES, ids=[c[0] for c in X2_CONV_CASES])
+def test_exact16_conv_pass(U, case):
+    """One exact16 pass per epilogue form of launch_ws, on the shapes of CONV_CASES (8-row tiles with seams and ragged edges) and on
+    16-row tiles.  Operands are interleaved NHWC pairs with padded pixel strides (planar_small: chunk-planar), each with its own
+    hi -> lo offset; the output is guarded element by element; the reference is conv_ref.conv3x3 in float64 on the pair values that
+    were uploaded and the fp32 weights, the judgement the pair rule (no fp32 yardstick is computed)."""
+    import zlib
+    L = U.L
+    dt = L.RESR_F16X2
+    ident, form, shape, opt = case
+    cin, cin0, cout, fl, n, h, w = _CC[shape] if isinstance(shape, str) else shape
+    fl = set(fl.split(","))
+    slope, planar, out_single = opt.get("slope", 0.2), opt.get("planar", False), opt.get("out_single", False)
+    g = torch.Generator().manual_seed(zlib.crc32(ident.encode()) % 1000)
+    up = "up" in fl
+    hs, ws = (h // 2, w // 2) if up else (h, w)
+    x = torch.randn(n, cin, hs, ws, generator=g)
+    wt = torch.randn(cout, cin, 3, 3, generator=g) * (2.0 / (cin * 9)) ** 0.5
+    bias = torch.randn(cout, generator=g) * 0.1
+    cout_pad, c1 = (cout + 31) // 32 * 32, cin - cin0
+    pc = opt.get("pair_chunks", 0) * 32 or cin                  # channels [0, pc) are pairs, the rest single f16 tensors
+
+    def singles(first, count):                                   # the channel slice of a segment that holds single chunks
+        return slice(max(pc - first, 0), count) if pc < first + count else None
+    a = Layout(L, dt, n, hs, ws, cin0, cin0 + 32, gap=GAP["in0"], planar=planar).upload(x[:, :cin0], singles(0, cin0))
+    b = Layout(L, dt, n, hs, ws, c1, c1 + 64, offset=32, gap=GAP["in1"]).upload(x[:, cin0:], singles(cin0, c1)) if c1 else None
+    xv = torch.cat([a.value, b.value], 1) if b else a.value
+    xh = torch.cat([a.hi, b.hi], 1) if b else a.hi
+    x_eff = torch.cat([xv[:, :pc], xh[:, pc:]], 1)
+    w_eff = wt.double()
+    flags = 0
+    if opt.get("single_w16"):                                    # the single chunks meet W0 = f16(w 2^12) alone
+        flags |= L.CONV_SINGLE_W16
+        w_eff = torch.cat([w_eff[:, :pc], R.split_weights(wt)[0][:, pc:]], 1)
+    nchw = "nchw" in fl
+    o = None if nchw else Layout(L, dt, n, h, w, cout, cout_pad + 32, gap=GAP["out"], planar=planar, single=out_single)
+    d = L.ConvDesc(n, h, w, cin, cin0, a.pixel_stride, b.pixel_stride if b else 0, cout, cout_pad, 0 if nchw else o.pixel_stride, 0, 0, 0, dt, 0,
+                   1.0, 1.0, 1.0, 1.0, slope)
+    d.in0_chunk_stride, d.in0_lo_offset = a.chunk_stride, a.lo_offset
+    d.x2_pair_chunks = opt.get("pair_chunks", 0)
+    if b:
+        d.in1_lo_offset = b.lo_offset
+    if o:
+        d.out_chunk_stride, d.out_lo_offset = o.chunk_stride, 0 if out_single else o.lo_offset
+    epi = {"slope": slope}
+    if "nobias" in fl:
+        flags |= L.CONV_NO_BIAS
+    else:
+        epi["bias"] = bias
+    if up:
+        flags |= L.CONV_UPSAMPLE_IN
+    if out_single:
+        flags |= L.CONV_OUT_SINGLE
+    mask = res0 = res1 = aux = None
+    offsets = [a.lo_offset] + ([b.lo_offset] if b else []) + ([o.lo_offset] if o else [])
+    if "mask" in fl:
+        flags |= L.CONV_MASK
+        mk = torch.randn(n, cout, h, w, generator=g)
+        if "maskbits" in fl:
+            bits = (mk > 0).permute(0, 2, 3, 1).reshape(n, h, w, cout // 32, 32).to(torch.int64)
+            words = (bits << torch.arange(32)).sum(-1)
+            mask_t = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).cuda().contiguous()
+            mask = L.ptr(mask_t)
+            flags |= L.CONV_MASK_BITS
+            epi["mask"] = mk
+        else:
+            # a saved activation, itself a pair; a fifth of it +-1e-9: the hi half is zero there and the lo half holds the sign
+            mk = torch.where(torch.rand(mk.shape, generator=g) < 0.2, mk.sign() * 1e-9, mk)
+            m = Layout(L, dt, n, h, w, cout, cout + 32, gap=GAP["mask"]).upload(mk)
+            assert ((m.hi == 0) & (m.value > 0)).sum() > 100
+            mask, d.mask_stride = m.ptr(U), m.pixel_stride
+            d.mask_lo_offset = 0 if opt.get("mask_lo0") else m.lo_offset
+            epi["mask"] = m.hi if opt.get("mask_lo0") else m.value
+            offsets.append(m.lo_offset)
+    if "lrelu" in fl:
+        flags |= L.CONV_LRELU
+        epi["lrelu"] = True
+    if "res0" in fl:
+        r0 = Layout(L, dt, n, h, w, cout, cout + 64, gap=GAP["res0"]).upload(torch.randn(n, cout, h, w, generator=g))
+        res0, d.res0_stride, d.res0_lo_offset, d.s0, d.t0 = r0.ptr(U), r0.pixel_stride, r0.lo_offset, 0.2, 1.0
+        epi.update(res0=r0.value, s0=0.2, t0=1.0)
+        offsets.append(r0.lo_offset)
+    if "res1" in fl:
+        r1 = Layout(L, dt, n, h, w, cout, cout, gap=GAP["res1"]).upload(torch.randn(n, cout, h, w, generator=g))
+        res1, d.res1_stride, d.res1_lo_offset, d.s1, d.t1 = r1.ptr(U), r1.pixel_stride, r1.lo_offset, 0.2, 0.5
+        epi.update(res1=r1.value, s1=0.2, t1=0.5)
+        offsets.append(r1.lo_offset)
+    assert len(set(offsets)) == len(offsets), "two operands share a hi -> lo offset"
+    if nchw:
+        flags |= L.CONV_OUT_NCHW_F32
+        out = Guarded(n * cout * h * w, torch.float32)
+        out_ptr = L.ptr(out.body)
+        if "clamp" in fl:
+            flags |= L.CONV_CLAMP01
+            passed = torch.full((n, cout, h, w), 9, dtype=torch.uint8, device="cuda")
+            aux = L.ptr(passed)
+            epi["clamp"] = True
+    else:
+        o.guarded()
+        out_ptr = o.out_ptr()
+    if "signbits" in fl:
+        flags |= L.CONV_WRITE_SIGNBITS
+        sw = _sign_words(n, h, w, cout)
+        aux = L.ptr(sw.body)
+    d.flags = flags
+    packed, bias_d = U.pack_conv(wt, dt), bias.cuda()
+    L.check(L.lib().resr_conv3x3(C.byref(d), a.ptr(U), b.ptr(U) if b else None, L.ptr(packed), L.ptr(bias_d), res0, res1, mask, out_ptr, aux,
+                                 L.stream_ptr()), "resr_conv3x3")
+    got = out.read().double().reshape(n, cout, h, w) if nchw else o.result()
+    ref, pre = R.conv3x3(x_eff, w_eff, F64, up, **epi)
+    bound = judge(f"conv_x2_form{form}_{ident}", "exact16", got, ref, None, "pair16" if out_single else "pair")
+    if "signbits" in fl:
+        assert torch.equal(_sign_bits(sw.read(), n, h, w, cout), got > 0), "sign tensor disagrees with the stored activation"
+    if "clamp" in fl:
+        assert set(passed.unique().tolist()) <= {0, 1}, "pass-mask bytes never written, or not 0 / 1"
+        assert R.pass_mask_ok(passed.cpu(), pre, bound) == 0
+
+
+AUX_CASES = [
+    # id, flags, output groups -- the discriminator's calls (disc_native.hip): an up block's convolution keeps its activation from before
+    # the skip connection is added; a backward-data pass keeps the gradient from before the LeakyReLU mask
+    ("before_res", "lrelu,res0,aux_res", 1),
+    ("before_mask", "mask,nobias,aux_mask", 1),
+    ("before_res_groups2", "lrelu,res0,aux_res,nobias", 2),
+]
+AUX_PARAMS = [(c, dt) for c in AUX_CASES for dt in ("f32", "f16", "exact16") if not (c[2] > 1 and dt == "f32")]
+
+
+@pytest.mark.parametrize("geo", [(2, 20, 36), (1, 33, 31)], ids=["2x20x36", "1x33x31"])
+@pytest.mark.parametrize("case,dtype_name", AUX_PARAMS, ids=[f"{c[0]}-{dt}" for c, dt in AUX_PARAMS])
+def test_aux_before_forms(U, case, dtype_name, geo):
+    """RESR_CONV_AUX_BEFORE_RES and RESR_CONV_AUX_BEFORE_MASK, cin 64 -> 64 channels per output group: f16 takes the specialised
+    epilogues 66 and 65 of launch_ws, exact16 the general one, f32 the one-role kernel.  out and aux are both guarded and both judged
+    by their dtype's rule; the exact16 aux is a pair of out's layout at out's hi -> lo offset."""
+    L = U.L
+    dtype = _dtype(L, dtype_name)
+    ident, fl, groups = case
+    fl = set(fl.split(","))
+    n, h, w = geo
+    cin, cout = 64, 64 * groups
+    g, x, wt, bias = _conv_case(len(ident) + n + h + w, cin, cout, n, h, w)
+    a = Layout(L, dtype, n, h, w, cin, cin + 32, gap=GAP["in0"]).upload(x)
+    o = Layout(L, dtype, n, h, w, cout, cout + 32, gap=GAP["out"])
+    ax = Layout(L, dtype, n, h, w, cout, cout + 32, gap=GAP["out"])
+    d = L.ConvDesc(n, h, w, cin, cin, a.pixel_stride, 0, 64, 64, o.pixel_stride, 0, 0, 0, dtype, 0, 1.0, 1.0, 1.0, 1.0, 0.2)
+    d.in0_lo_offset, d.out_lo_offset, d.cout_groups = a.lo_offset, o.lo_offset, groups if groups > 1 else 0
+    epi, flags = {"slope": 0.2}, 0
+    mask = res0 = None
+    if "nobias" in fl:
+        flags |= L.CONV_NO_BIAS
+    else:
+        epi["bias"] = bias
+    if "mask" in fl:
+        mk = torch.randn(n, cout, h, w, generator=g)
+        m = Layout(L, dtype, n, h, w, cout, cout + 64, gap=GAP["mask"]).upload(mk)
+        mask, d.mask_stride, d.mask_lo_offset = m.ptr(U), m.pixel_stride, m.lo_offset
+        flags |= L.CONV_MASK | L.CONV_AUX_BEFORE_MASK
+        epi["mask"] = m.value
+    if "lrelu" in fl:
+        flags |= L.CONV_LRELU
+        epi["lrelu"] = True
+    if "res0" in fl:
+        r0 = Layout(L, dtype, n, h, w, cout, cout + 96, gap=GAP["res0"]).upload(torch.randn(n, cout, h, w, generator=g))
+        res0, d.res0_stride, d.res0_lo_offset, d.s0, d.t0 = r0.ptr(U), r0.pixel_stride, r0.lo_offset, 1.0, 1.0
+        flags |= L.CONV_AUX_BEFORE_RES
+        epi.update(res0=r0.value, s0=1.0, t0=1.0)
+    d.flags = flags
+    if groups > 1:   # consecutive 64-row chunk tables, as resr_pack_weights lays them out (include/resr.h, cout_groups)
+        per_group = (cin // 32) * 9 * 2 * 1024 * {L.RESR_F16: 2, L.RESR_F16X2: 6}[dtype]
+        packed = torch.cat([U.pack_conv(wt[q * 64:(q + 1) * 64], dtype)[:per_group] for q in range(groups)]
+                           + [torch.zeros(16384, dtype=torch.uint8, device="cuda")])
+    else:
+        packed = U.pack_conv(wt, dtype)
+    wv = U.quant(wt, dtype) if dtype == L.RESR_F16 else wt
+    o.guarded()
+    ax.guarded()
+    bias_d = bias.cuda()
+    L.check(L.lib().resr_conv3x3(C.byref(d), a.ptr(U), None, L.ptr(packed), L.ptr(bias_d), res0, None, mask, o.out_ptr(), ax.out_ptr(),
+                                 L.stream_ptr()), "resr_conv3x3")
+    got, got_aux = o.result(), ax.result()
+    pair = dtype == L.RESR_F16X2
+    r64 = R.conv3x3(a.value, wv, F64, with_aux=True, **epi)
+    r32 = (None,) * 4 if pair else R.conv3x3(a.value, wv, F32, with_aux=True, **epi)
+    which = 3 if "aux_res" in fl else 2
+    name = f"conv_aux_{ident}_{'x'.join(map(str, geo))}_{dtype_name}"
+    judge(name + "_out", dtype_name, got, r64[0], r32[0], "pair" if pair else dtype_name)
+    judge(name + "_aux", dtype_name, got_aux, r64[which], r32[which], "pair" if pair else dtype_name)
+
+
+def _x2_wgrad(U, name, cin, cout, up, n, h, w, splits, single_g=False, cin0=None):
+    """One exact16 weight-gradient launch (the job-table one for these sizes) on interleaved NHWC pairs with padded strides and guarded
+    dW / db; |got - ref64| <= A + conv_ref.wgrad_lolo for dW, <= A for db."""
+    L = U.L
+    dt = L.RESR_F16X2
+    g = torch.Generator().manual_seed(7)
+    hs, ws = (h // 2, w // 2) if up else (h, w)
+    x = torch.randn(n, cin, hs, ws, generator=g)
+    gy = torch.randn(n, cout, h, w, generator=g)
+    cin_pad, cout_pad = (cin + 31) // 32 * 32, (cout + 31) // 32 * 32
+    cin0 = cin0 or cin_pad
+    xa = Layout(L, dt, n, hs, ws, min(cin, cin0), cin0 + 32, gap=GAP["in0"]).upload(x[:, :cin0])
+    xb = None
+    if cin0 < cin_pad:   # the second segment shares X's one hi -> lo offset: its gap makes up for its narrower pixel stride
+        stride1 = cin_pad - cin0 + 16
+        xb = Layout(L, dt, n, hs, ws, cin - cin0, stride1, gap=xa.lo_offset - n * hs * ws * stride1).upload(x[:, cin0:])
+        assert xb.lo_offset == xa.lo_offset and stride1 < xa.pixel_stride
+    gb = Layout(L, dt, n, h, w, cout, cout_pad + 32, gap=GAP["out"], single=single_g).upload(gy)
+    xv = torch.cat([xa.value, xb.value], 1) if xb else xa.value
+    gv = gb.hi if single_g else gb.value
+    d = L.WgradDesc(n, h, w, cin_pad, cin0, xa.pixel_stride, xb.pixel_stride if xb else 0, cin, cout, cout_pad, gb.pixel_stride, dt,
+                    (L.CONV_UPSAMPLE_IN if up else 0) | (L.CONV_OUT_SINGLE if single_g else 0), splits, 0.5)
+    d.x_lo_offset, d.g_lo_offset = xa.lo_offset, 0 if single_g else gb.lo_offset
+    partial = torch.empty(L.lib().resr_wgrad_partial_bytes(C.byref(d)) // 4, device="cuda")
+    dw, db = Guarded(cout * cin * 9, torch.float32), Guarded(cout, torch.float32)
+    L.check(L.lib().resr_conv3x3_wgrad(C.byref(d), xa.ptr(U), xb.ptr(U) if xb else None, gb.ptr(U), L.ptr(partial), L.ptr(dw.body),
+                                       L.ptr(db.body), L.stream_ptr()), "resr_conv3x3_wgrad")
+    judge_wgrad(f"wgrad_x2_{name}", "exact16", dw.read().reshape(cout, cin, 3, 3), db.read(), xv, gv, 0.5, up, lolo=True)
+
+
+@pytest.mark.parametrize("case", WGRAD_CASES, ids=[c[0] for c in WGRAD_CASES])
+def test_exact16_wgrad(U, case):
+    """The plain (job-table) exact16 weight-gradient launch -- what every 64 -> 32 and 64 -> 64 layer of the generator uses -- element
+    by element, at the shapes of test_wgrad."""
+    name, cin, cout, up, n, h, w = case
+    _x2_wgrad(U, name, cin, cout, up, n, h, w, 3)
+
+
+@pytest.mark.parametrize("splits", [1, 3])
+@pytest.mark.parametrize("case", [c for c in WGRAD_SMALL if c[0] in ("w_1x1", "w_row", "w_col")], ids=["w_1x1", "w_row", "w_col"])
+def test_exact16_wgrad_small_geometry(U, case, splits):
+    name, cin, cout, n, h, w, _ = case
+    _x2_wgrad(U, f"{name}_s{splits}", cin, cout, 0, n, h, w, splits)
+
+
+def test_exact16_wgrad_two_segment_x(U):
+    """X in two segments (cin 128, cin0 64, x1 given): both share the descriptor's one x_lo_offset."""
+    _x2_wgrad(U, "w_2seg", 128, 32, 0, 1, 21, 38, 3, cin0=64)
+    # refused loudly, not computed wrongly: a second segment in layer mode (an output wider than 64 channels), x1 without cin0 < cin
+    L = U.L
+    t = torch.zeros(1 << 16, dtype=torch.float16, device="cuda")
+    dw = torch.zeros(128 * 128 * 9, device="cuda")
+    for cout, cin0, x1 in ((128, 64, t), (32, 128, t), (32, 64, None)):
+        d = L.WgradDesc(1, 8, 8, 128, cin0, 96, 80, 128, cout, cout, cout + 32, L.RESR_F16X2, 0, 1, 1.0)
+        d.x_lo_offset = d.g_lo_offset = 20000
+        partial = torch.zeros(L.lib().resr_wgrad_partial_bytes(C.byref(d)) // 4, device="cuda")
+        assert L.lib().resr_conv3x3_wgrad(C.byref(d), L.ptr(t), L.ptr(x1), L.ptr(t), L.ptr(partial), L.ptr(dw), None, L.stream_ptr()) != 0
+
+
+def test_exact16_wgrad_single_g(U):
+    """RESR_CONV_OUT_SINGLE: G enters as its hi tensor (the lo tensor behind it is there and must not be read), in the reference too."""
+    _x2_wgrad(U, "w_single_g", 96, 32, 0, 1, 21, 38, 3, single_g=True)

@@ -141,7 +141,7 @@ def test_conv_mask_from_a_saved_activation_whose_hi_half_is_zero(U):
 
 
 @pytest.mark.parametrize("cin,cout,n,h,w,splits", [(96, 32, 2, 40, 36, 4), (64, 64, 1, 24, 64, 2)])
-def test_wgrad_single_g_equals_pair_g_with_zero_lo(U, cin, cout, n, h, w, splits):
+def test_wgrad_single_g_equals_pair_g_with_zero_lo(U, cin, cout, n, h, w, splits, diag_dir):
     """g_lo_offset = 0: G is a single f16 tensor -- the (x_hi, g_lo) tap-product is not issued.  Same bits as the three-product
     launch on a G pair whose lo tensor is zero (the skipped slab only ever added zeros)."""
     L = U.L
@@ -180,6 +180,18 @@ def test_wgrad_single_g_equals_pair_g_with_zero_lo(U, cin, cout, n, h, w, splits
     bs = torch.zeros(cout, dtype=torch.float64, requires_grad=True)
     (F.conv2d(x.double(), wt, bs, padding=1) * gy.half().double()).sum().backward()
     assert ((dw2.cpu().double() - wt.grad).norm() / wt.grad.norm()).item() < 5e-6
+    # and element by element, by the exact16 rule of tests/conv_ref.py: X as the pair that was uploaded, G as its hi tensor
+    from tests import conv_ref as R
+    xv = R.pair_value(xb[0].cpu(), xb[1].cpu()).permute(0, 3, 1, 2)
+    gv = gy.half().double()
+    recs = {}
+    for what, got, ref64, ref32, extra in zip(("dW", "db"), (dw2, db2), R.wgrad(xv, gv, 1.0), R.wgrad(xv, gv, 1.0, torch.float32),
+                                              (R.wgrad_lolo(xv, gv, 1.0), None)):
+        rec = R.judge(got.cpu(), ref64, ref32, "f32", extra)
+        rec.update(dtype="exact16", kind="f32")
+        recs[f"wgrad_x2_single_g_{cin}_{cout}_{what}"] = rec
+    U.merge_conv_diag(diag_dir, recs)
+    assert all(rec["bad"] == 0 for rec in recs.values()), recs
 
 
 def _setup(n_blocks, seed, x2_plan, wscale=1.0, upscale=4):
