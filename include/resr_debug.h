@@ -108,6 +108,15 @@ int resr_debug_compact_act_bwd(const void* g, const void* z, void* gz, const flo
                                float* partial, size_t partial_bytes, const void* amax, void* stream);
 int resr_debug_compact_residual_bwd(const float* gy, float* gx, int32_t n, int32_t h, int32_t w, int32_t s, void* stream);
 
+/* Test entry (tests/test_resize_surface.py, tests/test_gpu_resize_kernel.py): the launch plan of csrc/image_resize.hip, host only -- no
+ * device work, no tables.  What resr_image_resize and the scaled frame entries would launch for n sources of c x h x w resized to
+ * oh x ow through tables of taps_y / taps_x taps; kind: 0 fp32 NCHW output, 1 uint8 HWC, 2 / 3 a YUV 4:2:0 frame of 8- / 10-bit
+ * samples.  plan: six int32 -- the output tile th, tw; the capacity rh, rw of the staged source region; its LDS row pitch in
+ * floats; the LDS bytes of one workgroup.  Returns the status of that plan (RESR_ERR_ARG where the launch would be refused: a bad
+ * shape, no tile that fits ...), then `plan` is untouched. */
+int resr_debug_resize_plan(int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x,
+                           int32_t kind, int32_t* plan);
+
 /* What THIS board sustains once it sits at its power cap (bench.py's `roofline.vs_sustained`): 256 workgroups launched back to
  * back for `seconds` (last third timed) -- mode 1: an LDS-DMA stream over `src` (`bytes` >= 64 MB of readable device memory),
  * mode 2: eight waves per workgroup issuing v_mfma_f32_32x32x16_f16 on random f16 operands, mode 3: both at once.  Returns the

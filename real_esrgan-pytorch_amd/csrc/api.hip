@@ -631,6 +631,22 @@ int resr_debug_compact_residual_bwd(const float* gy, float* gx, int32_t n, int32
     return compact_residual_bwd_dispatch(gy, gx, n, h, w, s, (hipStream_t)stream);
 }
 
+// test entry of the resize launch plan (tests/test_resize_surface.py): resize_plan alone.  It only null-checks the tables and looks at
+// the alignment of y, so one aligned placeholder stands for all five.
+int resr_debug_resize_plan(int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x,
+                           int32_t kind, int32_t* plan) {
+    alignas(16) static const char placeholder[16] = {};
+    if (!plan) return fail(RESR_ERR_ARG, "resr_debug_resize_plan: null argument");
+    if (kind < RESIZE_F32 || kind > RESIZE_YUV10) return fail(RESR_ERR_ARG, "resr_debug_resize_plan: kind %d", kind);
+    ResizeGeom g;
+    const int rc = resize_plan("resr_debug_resize_plan", n, c, h, w, oh, ow, placeholder, placeholder, taps_y, placeholder, placeholder, taps_x,
+                               kind, placeholder, &g);
+    if (rc) return rc;
+    plan[0] = g.th; plan[1] = g.tw; plan[2] = g.rh; plan[3] = g.rw; plan[4] = g.pitch;
+    plan[5] = (int32_t)resize_lds_bytes(&g, kind);
+    return RESR_OK;
+}
+
 int resr_debug_spectral_norm_batch(int32_t n, const float* const* w, float* const* u, float* const* v, const int32_t* rows,
                                    const int32_t* cols, int32_t training, float eps, float* const* sigma2, float* const* tmp,
                                    void* stream) {

@@ -111,6 +111,7 @@ int nchw_to_image_dispatch(const float* src, void* dst, int n_images, int h, int
 // gp: the launch resize_plan made for the HR frame (c = 3, h * s, w * s) ----
 int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, const void* idx_y, const void* w_y, int taps_y, const void* idx_x, const void* w_x, int taps_x, int kind,
                 const void* y, ResizeGeom* out);
+size_t resize_lds_bytes(const ResizeGeom* gp, int kind);   // the dynamic LDS of one workgroup of that launch
 int compact_yuv420_scaled_fits(int h, int w, int s, int oh, int ow, int taps_y, int taps_x, int bits);
 int image_resize_dispatch(const float* x, void* y, int n, int c, int h, int w, int oh, int ow, const int32_t* idx_y, const float* w_y, int taps_y, const int32_t* idx_x, const float* w_x,
                           int taps_x, int u8, hipStream_t st);   // u8: y is uint8 HWC, else fp32 NCHW

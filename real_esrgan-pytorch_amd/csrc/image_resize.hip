@@ -402,6 +402,9 @@ int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, con
     return RESR_OK;
 }
 
+// resr_debug_resize_plan: what a launch of that plan asks for
+size_t resize_lds_bytes(const ResizeGeom* gp, int kind) { return lds_bytes(*gp, kind); }
+
 // resr_compact_yuv420_scaled_fits: would resize_plan find an even tile?  No device work, no error text.
 int compact_yuv420_scaled_fits(int h, int w, int s, int oh, int ow, int taps_y, int taps_x, int bits) {
     if (h <= 0 || w <= 0 || s < 1 || s > 4 || oh <= 0 || ow <= 0 || ((h | w | oh | ow) & 1) || (bits != 8 && bits != 10)) return 0;

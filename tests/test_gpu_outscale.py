@@ -1,8 +1,8 @@
 """GPU: outscale on the frame path (csrc/image_resize.hip, frames.py, imgproc.image_resize_native).
 
 Correctness rests on the first two tests: the float kernel and its uint8 output against the reference's own `image_resize`
-(tests/golden/image_resize_native.npz, written by tests/golden/gen_resize_golden.py).  Everything after them is an equality between
-two paths of this tree: fused tail against generic kernel, tiler against whole frame, FrameStream against single calls."""
+(tests/golden/image_resize_native.npz, written by tests/golden/gen_resize_golden.py), and on tests/test_gpu_resize_kernel.py, which
+holds the kernel to its definition bit for bit at every tile size.  Everything after them is an equality between two paths of this tree: fused tail against generic kernel, tiler against whole frame, FrameStream against single calls."""
 import math
 import os
 import types
@@ -20,6 +20,10 @@ ATOL = 1e-6                      # the project's gate for this function (tests/t
 DELTA = 255e-6                   # ... scaled to the uint8 step
 MAX_EXCLUDED = 0.005
 OUTSCALES = (1.5, 2, 3, 2.5)
+# outscale of a x4 model -> the tile resize_plan chooses for a 96 x 96 HR frame: the small entries of choose_tile's list, which the
+# outscales above (r >= 0.375: 32 x 32, 16 x 32, 16 x 16) never reach
+SMALL_TILE_OUTSCALES = ((1.2, (8, 16)), (0.8, (8, 8)), (0.6, (4, 8)), (0.5, (4, 4)), (0.4, (2, 4)), (0.32, (2, 2)), (0.28, (1, 2)),
+                        (0.25, (1, 1)))
 
 
 @pytest.fixture(scope="module")
@@ -93,6 +97,17 @@ def _generic(m, u8, o):
         return imgproc.image_resize_native(sr, o / m.upscale, u8=True)
 
 
+def _planned_tile(h, w, s, o):
+    """The tile of the fused uint8 tail for LR frames h x w: resr_debug_resize_plan on the HR frame, host only."""
+    import real_esrgan_pytorch_amd as R
+    from tests import resize_ref
+    (hh, ww), r = (h * s, w * s), o / s
+    oh, ow = R.output_size(h, w, s, o)
+    ty, tx = resize_ref.band(hh, r)[0].shape[1], resize_ref.band(ww, r)[0].shape[1]
+    plan = resize_ref.plan_of(R._lib.lib(), 1, 3, hh, ww, oh, ow, ty, tx, resize_ref.U8)
+    return (plan.th, plan.tw), (-(-oh // plan.th), -(-ow // plan.tw))
+
+
 @pytest.mark.parametrize("precision", PRECISIONS)
 @pytest.mark.parametrize("s", [2, 3, 4])
 def test_fused_equals_generic_bit_for_bit(s, precision):
@@ -122,7 +137,25 @@ def test_fused_equals_generic_bit_for_bit(s, precision):
                 m.forward_u8(torch.zeros(1, h, 9, 3, dtype=torch.uint8).cuda(), outscale=o)
             refused += 1
     assert ran >= 20
-    if s == 4:
+    if s == 4:                                # the small tiles: tile origins off the 4-byte grid, rows shorter than a dword
+        small = 0
+        for o, tile in SMALL_TILE_OUTSCALES:
+            for n, h, w in ((1, 24, 24), (2, 25, 33)):
+                assert _admits(h, w, s, o)
+                planned, (ty, tx) = _planned_tile(h, w, s, o)
+                assert planned == tile and ty >= 2 and tx >= 2, (o, h, w, planned, ty, tx)
+                u8 = random_frames(n, h, w, seed=h * w + n)
+                with torch.no_grad():
+                    got = m.forward_u8(torch.from_numpy(u8).cuda(), outscale=o)
+                torch.cuda.synchronize()
+                assert got.dtype == torch.uint8 and got.is_contiguous()
+                assert tuple(got.shape) == (n,) + R.output_size(h, w, s, o) + (3,), (o, n, h, w)
+                want = _generic(m, u8, o)
+                bad = int((got != want).sum())
+                assert bad == 0, f"s={s} o={o} n={n} {h}x{w} tile {tile}: {bad} of {want.numel()} bytes differ"
+                assert len(torch.unique(got)) > 16
+                small += 1
+        assert small == 2 * len(SMALL_TILE_OUTSCALES)
         assert _admits(1, 1, 4, 2)            # 1 x 1 at s = 4, o = 2 is among the frames above (reflection inside a tile)
     with torch.no_grad():                     # outscale None / == s is the parent's call, bit for bit
         f = torch.from_numpy(random_frames(2, 9, 11, seed=4)).cuda()

@@ -112,6 +112,40 @@ def test_fused_is_the_composition(case, bits, precision):
             fwd(dev, outscale=o, plan=_plan(h + 2, w, s, o))
 
 
+# (n, LR h, LR w, outscale of the x4 model, the even tile resize_plan chooses for the 4:2:0 tail): the small even entries of choose_tile's
+# list, which the cases above (16 x 32 and larger) never reach; several tiles per axis and outputs that are no multiple of the tile
+# (2 x 2 divides every 4:2:0 frame)
+SMALL_TILES = [(1, 28, 30, 1.2, (8, 16)), (1, 24, 24, 0.8, (8, 8)), (1, 32, 36, 0.6, (4, 8)), (2, 24, 28, 0.5, (4, 4)), (1, 24, 24, 0.4, (2, 4)),
+               (1, 24, 24, 0.32, (2, 2))]
+SMALL_LAYOUT = {8: "nv12", 10: "i420p10"}      # one semi-planar, one planar
+
+
+@pytest.mark.parametrize("bits", (8, 10))
+@pytest.mark.parametrize("case", SMALL_TILES, ids=lambda c: "n%d_%dx%d_o%s_tile%dx%d" % (c[:4] + c[4]))
+def test_fused_is_the_composition_on_the_small_tiles(case, bits):
+    import real_esrgan_pytorch_amd as R
+    from tests import resize_ref
+    n, h, w, o, tile = case
+    s = 4
+    assert _accepted((n, h, w, s, o))
+    oh, ow = R.output_size(h, w, s, o)
+    ty, tx = (resize_ref.band(v * s, o / s)[0].shape[1] for v in (h, w))
+    plan = resize_ref.plan_of(R._lib.lib(), n, 3, h * s, w * s, oh, ow, ty, tx, resize_ref.YUV8 if bits == 8 else resize_ref.YUV10)
+    assert plan is not None and (plan.th, plan.tw) == tile, (case, bits, plan)
+    assert -(-oh // plan.th) >= 2 and -(-ow // plan.tw) >= 2 and (tile == (2, 2) or oh % plan.th or ow % plan.tw)
+    m, _ = _model(2, s, "prelu", "fast", "slopes")
+    f = _frames(bits, n, h, w, seed=h * w + n + s)
+    dev = torch.from_numpy(f).cuda()
+    layout = SMALL_LAYOUT[bits]
+    want = oracle(m, f, bits, layout, "bt709", o)
+    with torch.no_grad():
+        got = (m.forward_yuv420 if bits == 8 else m.forward_yuv420p10)(dev, layout, "bt709", outscale=o)      # the fused tail: the method has no other path
+    torch.cuda.synchronize()
+    assert got.is_contiguous() and tuple(got.shape) == (n, oh * 3 // 2, ow)
+    _same(got, want, f"forward {layout} o={o} tile {tile}")
+    assert len(np.unique(want)) > 16
+
+
 # 2 ---- the fused kernels ran -----------------------------------------------------------------------------------------------------
 def test_the_fused_kernels_ran():
     import real_esrgan_pytorch_amd as R

@@ -1,6 +1,8 @@
 """CPU: the surface of outscale -- the two new C-ABI entries (exported, declared, argument checks before any launch), the banded
 tap tables against `imgproc._resize_matrix` and against the reference's own outputs (tests/golden/image_resize_native.npz, written
-by tests/golden/gen_resize_golden.py), `frames.output_size`, and the Python argument checks.  Nothing here touches a device."""
+by tests/golden/gen_resize_golden.py), `frames.output_size`, the Python argument checks, and the launch plan of the resize kernel
+(`resr_debug_resize_plan`) swept over scales, lengths and output kinds: the staged region holds every tile's taps within 64 KB of LDS.
+Nothing here touches a device."""
 import ctypes as C
 import hashlib
 import math
@@ -261,3 +263,136 @@ def test_inference_frames_parser_outscale(R):
     assert p.parse_args(base + ["--outscale", "1.5"]).outscale == 1.5
     with pytest.raises(SystemExit):
         p.parse_args(base + ["--outscale", "two"])
+
+
+# ---- the launch plan (resr_debug_resize_plan): the staged region holds every tile's taps, within 64 KB --------------------------------
+PLAN_SCALES = (0.75, 0.5, 0.4, 0.3, 0.2, 0.15, 0.125, 0.1, 0.08, 0.07, 0.0625, 0.05, 0.99, 1.0, 1.01, 1.5, 2, 3,
+               1 / 3, 0.37, 0.45, 0.618, 0.7, 0.9, 0.11, 0.055, 1.25, 2.5, 3.7)
+PLAN_LENGTHS = tuple(range(1, 140)) + (200, 257, 1000, 1920)
+PLAN_MIXED = ((0.25, 1.5), (1.5, 0.25), (0.1, 0.75), (0.0625, 3), (0.3, 0.08), (2, 0.15), (0.07, 0.5))
+TILE_LIST = ((32, 32), (16, 32), (16, 16), (8, 16), (8, 8), (4, 8), (4, 4), (2, 4), (2, 2), (1, 2), (1, 1))      # choose_tile's, in its order
+LDS_BUDGET = 64 * 1024
+KINDS = (0, 1, 2, 3)                     # csrc/common.h ResizeOut: fp32, uint8, YUV 8 bits, YUV 10 bits
+
+
+class _Axis:
+    """The tables of one axis, reduced to what the region check needs: per output the lowest and highest source index."""
+
+    def __init__(self, n, r, aa):
+        from real_esrgan_pytorch_amd import imgproc
+        self.n, self.out = n, math.ceil(n * r)
+        idx, _ = imgproc.resize_band_tables(n, self.out, r, aa)
+        self.taps = idx.shape[1]
+        self.lo, self.hi = idx.min(1), idx.max(1)
+        self._span = {}
+
+    def span(self, t):
+        """The widest reach of any tile of t consecutive outputs: max(idx) - min(idx) + 1 over the tile's table rows."""
+        if t not in self._span:
+            starts = np.arange(0, self.out, t)
+            self._span[t] = int((np.maximum.reduceat(self.hi, starts) - np.minimum.reduceat(self.lo, starts)).max()) + 1
+        return self._span[t]
+
+
+def _span_bound(t, n_in, n_out, p):
+    """csrc/image_resize.hip span_bound, restated: what one axis alone implies."""
+    s = p + ((t - 1) * n_in // (n_out - 1) + 2 if t > 1 else 0)
+    return min(s, n_in)
+
+
+def _lds_bytes(th, tw, rh, pitch, py, px, kind):
+    staging = 0 if kind == 0 else (th * tw * 3 * (2 if kind == 3 else 1) + 3) // 4 * 4
+    return 4 * (2 * (th * py + tw * px) + 3 * (rh + th) * pitch) + staging
+
+
+def _expected_plan(y, x, kind):
+    """The first tile of the list whose LDS fits, each axis sized on its own (None: none fits)."""
+    for th, tw in TILE_LIST:
+        if kind >= 2 and (th | tw) & 1:
+            continue
+        rh, rw = _span_bound(min(th, y.out), y.n, y.out, y.taps), _span_bound(min(tw, x.out), x.n, x.out, x.taps)
+        lds = _lds_bytes(th, tw, rh, rw | 1, y.taps, x.taps, kind)
+        if lds <= LDS_BUDGET:
+            return (th, tw, rh, rw, rw | 1, lds)
+    return None
+
+
+def _check_plan(lib, out6, y, x, kind, tally):
+    c = 3
+    rc = lib.resr_debug_resize_plan(1, c, y.n, x.n, y.out, x.out, y.taps, x.taps, kind, out6)
+    want = _expected_plan(y, x, kind)
+    what = (y.n, x.n, y.out, x.out, y.taps, x.taps, kind)
+    if kind >= 2 and ((y.out | x.out) & 1):
+        assert rc == ERR_ARG, what                                 # a 4:2:0 frame has an even height and width
+        return
+    if want is None:
+        assert rc == ERR_ARG, what
+        tally["refused"] += 1
+        return
+    assert rc == 0 and tuple(out6) == want, (what, rc, tuple(out6), want)
+    th, tw, rh, rw, pitch, lds = want
+    # the condition under which the kernel's clamp into the staged region never acts
+    assert y.span(th) <= rh and x.span(tw) <= rw, (what, want, y.span(th), x.span(tw))
+    assert lds <= LDS_BUDGET and pitch >= rw and pitch & 1
+    assert kind < 2 or not (th | tw) & 1, (what, want)
+    tally["plans"] += 1
+    tally["tiles"] += -(-y.out // th) * -(-x.out // tw)
+    tally[(th, tw)] = tally.get((th, tw), 0) + 1
+
+
+def test_resize_plan_regions_hold_every_tile(R):
+    lib = R._lib.lib()
+    out6 = (C.c_int32 * 6)()
+    tally = {"plans": 0, "tiles": 0, "refused": 0}
+
+    def axes(r, aa):
+        got = {}
+        for n in PLAN_LENGTHS:
+            try:
+                got[n] = _Axis(n, r, aa)
+            except ValueError:
+                pass                                               # a length the reflection rule refuses: no launch exists
+        return got
+
+    for aa in (True, False):
+        for r in PLAN_SCALES:
+            ax = axes(r, aa)
+            names = sorted(ax)
+            assert 1 in ax and len(names) > len(PLAN_LENGTHS) // 2, (r, aa, len(names))
+            for i, n in enumerate(names):
+                for m in {n, names[(7 * i + 3) % len(names)]}:     # the square source, and one of another length
+                    for kind in KINDS:
+                        _check_plan(lib, out6, ax[n], ax[m], kind, tally)
+        for ry, rx in PLAN_MIXED:                                  # two axes with different tap counts
+            ay, bx = axes(ry, aa), axes(rx, aa)
+            for i, n in enumerate(sorted(ay)):
+                ms = sorted(bx)
+                m = ms[(5 * i + 1) % len(ms)]
+                assert not aa or ay[n].taps != bx[m].taps
+                for kind in KINDS:
+                    _check_plan(lib, out6, ay[n], bx[m], kind, tally)
+    print(f"resize plans checked: {tally['plans']} over {tally['tiles']} tiles, {tally['refused']} refused (no tile fits); "
+          f"per tile {{th x tw: plans}}: { {k: v for k, v in tally.items() if isinstance(k, tuple)} }")
+    assert tally["plans"] >= 40000 and tally["tiles"] >= 1000000 and tally["refused"] > 0
+    assert all(tally.get(t, 0) > 0 for t in TILE_LIST), [t for t in TILE_LIST if not tally.get(t)]      # every entry of the list is reachable
+
+
+def test_resize_plan_entry_argument_checks(R):
+    lib = R._lib.lib()
+    out6 = (C.c_int32 * 6)(*([-7] * 6))
+    good = dict(n=1, c=3, h=96, w=96, oh=48, ow=48, ty=10, tx=10, kind=1)
+
+    def call(out=out6, **kw):
+        a = dict(good, **kw)
+        return lib.resr_debug_resize_plan(a["n"], a["c"], a["h"], a["w"], a["oh"], a["ow"], a["ty"], a["tx"], a["kind"], out)
+
+    for kw in (dict(n=0), dict(c=0), dict(h=0), dict(w=-1), dict(oh=0), dict(ow=-3), dict(ty=0), dict(tx=4097), dict(kind=-1), dict(kind=4),
+               dict(c=4), dict(c=4, kind=2), dict(oh=47, kind=2), dict(ow=47, kind=3), dict(n=65536), dict(out=None),
+               dict(h=4000, w=4000, oh=40, ow=40, ty=402, tx=402)):
+        assert call(**kw) == ERR_ARG, kw
+        assert list(out6) == [-7] * 6                              # a refused plan leaves the output untouched
+    assert call(c=4, kind=0) == 0 and call(c=7, n=3, kind=0) == 0   # channels and batch do not enter the tile
+    assert call() == 0 and list(out6) == [16, 32, 42, 75, 75, 56040 + 16 * 32 * 3]
+    assert call(kind=0) == 0 and list(out6) == [16, 32, 42, 75, 75, 56040]
+    assert call(kind=3) == 0 and list(out6) == [16, 32, 42, 75, 75, 56040 + 16 * 32 * 6]      # 16-bit words in the staging buffer
+    assert call(h=6, w=6, oh=2, ow=2, ty=16, tx=16) == 0 and list(out6)[:5] == [32, 32, 6, 6, 7]   # a region is never larger than the source
