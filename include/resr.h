@@ -653,6 +653,32 @@ int resr_compact_forward_image(const ResrCompactDesc* d, const void* x, const fl
 int resr_image_to_nchw(const void* src, float* dst_f32, int32_t n_images, int32_t h, int32_t w, const ResrImageDesc* img, void* stream);
 int resr_nchw_to_image(const float* src_f32, void* dst, int32_t n_images, int32_t h, int32_t w, const ResrImageDesc* img, void* stream);
 
+/* Image-mode outscale: the image ends on the resized tail of resr_compact_forward_u8_scaled (image_resize.hip).  x [N,H,W,C] -> y
+ * [N,oh,ow,C], same channels and depth; oh x ow and the tap tables as for resr_compact_forward_u8_scaled (a resize of the s d->h x
+ * s d->w frame).  DEFINED by the functions above, bit for bit, with no tolerance anywhere:
+ *   resr_compact_forward_image_scaled(x) == resr_nchw_to_image(resr_image_resize(resr_compact_forward(resr_image_to_nchw(x))))
+ * i.e. to_image(q(resize(float path(to_rgb(x) / top)))): the fp32 frame is resized before it is quantised, grey is taken of the three
+ * quantised, resized levels, and the RGBA alpha is the grey of the resized alpha images' levels.
+ * One launch sequence: the image head, the convs, one tail.  The tail forms the frame resr_compact_forward would have stored tile by
+ * tile in LDS (t + level / top, the level read from x: neither the fp32 x4 frames of the planes * N network images nor their resized
+ * fp32 frames exist), resizes it, quantises the three sums of every pixel and stores C words per pixel.  An RGBA tile is one workgroup,
+ * which runs colour image b and then alpha image N + b over the same LDS; the sums are resr_image_resize's per channel and do not depend
+ * on the tile.  d->n is the NETWORK's batch, planes * N, as for resr_compact_forward_image; same packed weights and workspace
+ * (resr_compact_workspace_bytes: nothing more).  x must stay valid until the call has run.  channels = 3, bits = 8 runs the kernels of
+ * resr_compact_forward_u8_scaled.
+ * RESR_ERR_ARG before any launch, nothing written: everything resr_compact_forward_image refuses, with its rule for y replaced by 4-byte
+ * alignment (rows leave as dword stores; x keeps the head's alignment); and what resr_compact_forward_u8_scaled refuses: a null table,
+ * oh, ow <= 0, taps outside [1, 4096], N > 65535, a scale so small that the taps of one output pixel do not fit a 64 KB LDS tile.
+ * resr_compact_image_scaled_fits: that last condition as a query with no device work and no error text -- 1 when a tile fits for an
+ * h x w image of that mode through a model of factor s resized to oh x ow with these taps, else 0 (bad arguments included).  A caller
+ * asks it to choose between this entry and the composition above. */
+int resr_compact_forward_image_scaled(const ResrCompactDesc* d, const void* x, const float* params, const void* packed, void* workspace,
+                                      size_t workspace_bytes, void* y, int32_t oh, int32_t ow, const int32_t* idx_y, const float* w_y,
+                                      int32_t taps_y, const int32_t* idx_x, const float* w_x, int32_t taps_x, const ResrImageDesc* img,
+                                      void* stream);
+int resr_compact_image_scaled_fits(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x,
+                                   int32_t channels, int32_t bits);
+
 /* ---- second-order degradation (imgproc.py device ops; call sites train_realesrnet.py:268-377) ----------
  * Images are planar fp32 [n,c,h,w] in [0,1].  No entry point synchronises or reads back. */
 

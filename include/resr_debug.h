@@ -116,6 +116,12 @@ int resr_debug_compact_residual_bwd(const float* gy, float* gx, int32_t n, int32
  * shape, no tile that fits ...), then `plan` is untouched. */
 int resr_debug_resize_plan(int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x,
                            int32_t kind, int32_t* plan);
+/* ... and of the image modes' scaled tail (tests/test_image_outscale_surface.py, tests/test_gpu_image_outscale.py): what
+ * resr_compact_forward_image_scaled launches for h x w images of `channels` x `bits` through a model of factor s resized to oh x ow --
+ * the same six int32, the staging buffer `channels` words of bits / 8 bytes per pixel of the tile (8-bit RGB: the uint8 plan, kind 1
+ * above).  RESR_ERR_ARG where resr_compact_image_scaled_fits says 0, then `plan` is untouched. */
+int resr_debug_image_resize_plan(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x, int32_t channels,
+                                 int32_t bits, int32_t* plan);
 
 /* What THIS board sustains once it sits at its power cap (bench.py's `roofline.vs_sustained`): 256 workgroups launched back to
  * back for `seconds` (last third timed) -- mode 1: an LDS-DMA stream over `src` (`bytes` >= 64 MB of readable device memory),

@@ -393,7 +393,7 @@ class SRVGGNetCompact(nn.Module):
         y = torch.empty((n, plan.out_h * 3 // 2, plan.out_w), dtype=b.fmt.torch_dtype, device=frames.device)
         return self._call("resr_compact_forward_yuv420_mixed_scaled", frames, n, h, w, y, *plan.args(), C.byref(qb), after_src=(C.byref(qa),))
 
-    def forward_image(self, images: torch.Tensor) -> torch.Tensor:
+    def forward_image(self, images: torch.Tensor, outscale: Optional[float] = None, plan=None) -> torch.Tensor:
         """images: a grey, RGB or RGBA batch -- uint8 or uint16, [N,H,W] or [N,H,W,1], [N,H,W,3], [N,H,W,4] -- on the model's device,
         contiguous -> the same dtype and trailing shape, [N,sH,sW(,C)].  Bit for bit
         `frames.rgb_to_image_np(q(self(frames.image_to_rgb_np(images) / top)), channels)` with top = 255 or 65535 and
@@ -401,14 +401,28 @@ class SRVGGNetCompact(nn.Module):
         `forward_u8` on a network batch of planes * N images (RGBA: the N colour images, then the N alpha planes as grey images, as
         upstream's `alpha_upsampler="realesrgan"`) -- the head reads the image's own words, the tail writes them; no fp32 or RGB
         copy of either exists on the device.  uint8 RGB runs the kernels of `forward_u8`.  Same guard, packing and workspace caches
-        as `forward`.  No `outscale` here."""
+        as `forward`.
+
+        `outscale`, `plan`: as `forward_u8`'s -> [N, *frames.output_size(H, W, s, outscale)(, C)] -- `resr_compact_forward_image_scaled`:
+        the last kernel resizes the float frames it would have quantised by r = outscale / s, tile by tile in LDS, and quantises the
+        resized sums; bit for bit `frames.to_image(imgproc.resize_with_plan(self(frames.from_image(images)), plan), C, dtype)`, whose
+        fp32 frames exist as LDS tiles only (frames.py, IMAGE MODES).  A scale so small that no tile fits the kernel's LDS is an error
+        here; `frames.upscale_image` asks first and composes.  None or the model's factor: the path above."""
         from . import frames as _frames
+        what = "SRVGGNetCompact.forward_image"
+        o = _frames.check_outscale(outscale, self.upscale, what)
         self._guard()
-        n, h, w, c = _frames.check_images(images, "SRVGGNetCompact.forward_image")
+        n, h, w, c = _frames.check_images(images, what)
         idesc = _frames.image_desc(c, images.dtype)
         s = self.upscale
-        y = torch.empty((n, h * s, w * s) + tuple(images.shape[3:]), dtype=images.dtype, device=images.device)
-        return self._call("resr_compact_forward_image", images, (2 if c == 4 else 1) * n, h, w, y, C.byref(idesc))
+        planes = 2 if c == 4 else 1
+        if o is None:
+            y = torch.empty((n, h * s, w * s) + tuple(images.shape[3:]), dtype=images.dtype, device=images.device)
+            return self._call("resr_compact_forward_image", images, planes * n, h, w, y, C.byref(idesc))
+        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
+        plan = self._scaled_plan(images, h, w, o, plan, what)
+        y = torch.empty((n, plan.out_h, plan.out_w) + tuple(images.shape[3:]), dtype=images.dtype, device=images.device)
+        return self._call("resr_compact_forward_image_scaled", images, planes * n, h, w, y, *plan.args(), C.byref(idesc))
 
     def load_official_state_dict(self, checkpoint) -> None:
         """Upstream's `{"params_ema": sd}` / `{"params": sd}` (params_ema preferred) or a bare state dict (model.load_official_state_dict)."""

@@ -265,6 +265,22 @@ int resr_compact_forward_image(const ResrCompactDesc* d, const void* x, const fl
                                 "compact_forward_image");
 }
 
+int resr_compact_forward_image_scaled(const ResrCompactDesc* d, const void* x, const float* params, const void* packed, void* workspace,
+                                      size_t workspace_bytes, void* y, int32_t oh, int32_t ow, const int32_t* idx_y, const float* w_y,
+                                      int32_t taps_y, const int32_t* idx_x, const float* w_x, int32_t taps_x, const ResrImageDesc* img,
+                                      void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return compact_forward_ends(d, {END_IMAGE, true, x, y, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, nullptr, nullptr, 0, img}, params, packed,
+                                workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_image_scaled");
+}
+
+int resr_compact_image_scaled_fits(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x, int32_t channels,
+                                   int32_t bits) {
+    ResizeGeom g;
+    int kind;
+    return image_scaled_plan(h, w, s, oh, ow, taps_y, taps_x, channels, bits, &g, &kind) ? 1 : 0;
+}
+
 int resr_image_to_nchw(const void* src, float* dst_f32, int32_t n_images, int32_t h, int32_t w, const ResrImageDesc* img, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return image_to_nchw_dispatch(src, dst_f32, n_images, h, w, img, (hipStream_t)stream);
@@ -642,6 +658,19 @@ int resr_debug_resize_plan(int32_t n, int32_t c, int32_t h, int32_t w, int32_t o
     const int rc = resize_plan("resr_debug_resize_plan", n, c, h, w, oh, ow, placeholder, placeholder, taps_y, placeholder, placeholder, taps_x,
                                kind, placeholder, &g);
     if (rc) return rc;
+    plan[0] = g.th; plan[1] = g.tw; plan[2] = g.rh; plan[3] = g.rw; plan[4] = g.pitch;
+    plan[5] = (int32_t)resize_lds_bytes(&g, kind);
+    return RESR_OK;
+}
+
+// ... and of the image modes' scaled tail (tests/test_image_outscale_surface.py): the tile resr_compact_forward_image_scaled launches
+int resr_debug_image_resize_plan(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x, int32_t channels,
+                                 int32_t bits, int32_t* plan) {
+    if (!plan) return fail(RESR_ERR_ARG, "resr_debug_image_resize_plan: null argument");
+    ResizeGeom g;
+    int kind;
+    if (!image_scaled_plan(h, w, s, oh, ow, taps_y, taps_x, channels, bits, &g, &kind))
+        return fail(RESR_ERR_ARG, "resr_debug_image_resize_plan: a bad argument, or no tile fits %d x %d taps", taps_y, taps_x);
     plan[0] = g.th; plan[1] = g.tw; plan[2] = g.rh; plan[3] = g.rw; plan[4] = g.pitch;
     plan[5] = (int32_t)resize_lds_bytes(&g, kind);
     return RESR_OK;

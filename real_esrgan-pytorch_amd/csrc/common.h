@@ -115,9 +115,14 @@ struct ResizeGeom {
     int rh, rw, pitch;    // capacity of the staged region, LDS row pitch (floats)
     int cgroups;          // ceil(c / 3)
 };
-// ... and what it stores: fp32 NCHW, uint8 HWC, or a YUV 4:2:0 frame of 8- or 10-bit samples (the latter two: even tiles only, and
-// a staging buffer of levels as wide as the sample's word)
-enum ResizeOut { RESIZE_F32 = 0, RESIZE_U8 = 1, RESIZE_YUV8 = 2, RESIZE_YUV10 = 3 };
+// ... and what it stores: fp32 NCHW, uint8 HWC, a YUV 4:2:0 frame of 8- or 10-bit samples (the latter two: even tiles only, and
+// a staging buffer of levels as wide as the sample's word), or an image batch [N,oh,ow,C] of bytes or 16-bit words: RESIZE_IMAGE +
+// 2 * C + (16 bits), resize_image_kind -- C words per pixel in the staging buffer (8-bit RGB is RESIZE_U8 itself)
+enum ResizeOut { RESIZE_F32 = 0, RESIZE_U8 = 1, RESIZE_YUV8 = 2, RESIZE_YUV10 = 3, RESIZE_IMAGE = 4 };
+constexpr int resize_image_kind(int channels, int bits) { return channels == 3 && bits == 8 ? RESIZE_U8 : RESIZE_IMAGE + 2 * channels + (bits == 16); }
+constexpr bool resize_is_image(int kind) { return kind >= RESIZE_IMAGE; }
+constexpr int resize_image_channels(int kind) { return (kind - RESIZE_IMAGE) >> 1; }
+constexpr int resize_image_word_bytes(int kind) { return 1 + ((kind - RESIZE_IMAGE) & 1); }
 
 
 // compact.hip: the two ends of one forward pass (compact_forward_ends; api.hip builds one per entry): what x and y are, and what
@@ -135,7 +140,7 @@ enum EndFormat {
 };
 struct Ends {
     EndFormat format;
-    bool scaled;             // END_RGB8, END_YUV: y is the frame resized to sc.oh x sc.ow by the tail of image_resize.hip
+    bool scaled;             // END_RGB8, END_YUV, END_IMAGE: y is the frame resized to sc.oh x sc.ow by the tail of image_resize.hip
     const void* x;
     void* y;
     ScaledTail sc;           // scaled

@@ -18,9 +18,9 @@
 //   END_IMAGE         grey, RGB or RGBA images [N,H,W,C] of bytes or 16-bit words (Ends::img): frames.hip's head reading them -- the
 //                     network's batch is the N colour (or grey) images and, for RGBA, the N alpha planes behind them, each level
 //                     three times -- and its image tail (grey: the fixed-point grey of the three levels; RGBA: the alpha images'
-//                     grey as the fourth channel).  No scaled variant;
-//   ... and scaled    ("outscale") image_resize.hip's fused tail in place of either: the HR frame is formed tile by tile in LDS and
-//                     only the resized frame, uint8 [N,oh,ow,3] or YUV 4:2:0 [N,3oh/2,ow], is written.
+//                     grey as the fourth channel);
+//   ... and scaled    ("outscale") image_resize.hip's fused tail in place of any of them: the HR frame is formed tile by tile in LDS
+//                     and only the resized frame, uint8 [N,oh,ow,3], YUV 4:2:0 [N,3oh/2,ow] or images [N,oh,ow,C], is written.
 // Training (compact_forward_train / compact_backward, at the end of this file; kernels of its own in compact_train.hip): the same
 // convolutions with a plain epilogue, every pre-activation z_k and activation a_k kept -- TPlan below states the workspace.
 #include <vector>
@@ -175,10 +175,15 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
     int rc = RESR_OK;
     // the descriptor and the LR frame; of scaled ends the output pointer's rule is the plan's (nullptr passes the unscaled tail's)
     if (e.format == END_YUV) rc = yuv_forward_check(who, d.n, d.h, d.w, d.upscale, e.scaled ? nullptr : e.y, e.src, e.dst, e.bits_expected);
-    if (e.format == END_IMAGE) rc = e.scaled ? fail(RESR_ERR_ARG, "%s: unknown kind of ends", who) : image_forward_check(who, d.n, d.h, d.w, d.upscale, e.x, e.y, e.img);
-    if (!rc && e.scaled)
-        rc = resize_plan(who, d.n, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y, e.sc.idx_x,
-                         e.sc.w_x, e.sc.taps_x, e.format == END_RGB8 ? RESIZE_U8 : yuv_bits(e.dst->layout) == 8 ? RESIZE_YUV8 : RESIZE_YUV10, e.y, geom);
+    if (e.format == END_IMAGE) rc = image_forward_check(who, d.n, d.h, d.w, d.upscale, e.x, e.scaled ? nullptr : e.y, e.img);
+    if (!rc && e.scaled) {
+        // an image tail's workgroups own whole pixels: its grid counts the N images, not the planes * N of the network
+        const int images = e.format == END_IMAGE && e.img->channels == 4 ? d.n / 2 : d.n;
+        const int kind = e.format == END_RGB8 ? RESIZE_U8 : e.format == END_IMAGE ? resize_image_kind(e.img->channels, e.img->bits)
+                         : yuv_bits(e.dst->layout) == 8 ? RESIZE_YUV8 : RESIZE_YUV10;
+        rc = resize_plan(who, images, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y, e.sc.idx_x,
+                         e.sc.w_x, e.sc.taps_x, kind, e.y, geom);
+    }
     if (rc) return rc;
     if (p.total > workspace_bytes) return fail(RESR_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, p.total);
     return RESR_OK;
@@ -238,7 +243,11 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
         case END_YUV:
             if (!e.scaled) return compact_tail_yuv(t, e.x, e.y, N, H, W, s, e.src, e.dst, st);
             return compact_tail_yuv420_scaled(t, e.x, e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, e.src, e.dst, &geom, st);
-        case END_IMAGE: return compact_tail_image(t, e.x, e.y, e.img->channels == 4 ? N / 2 : N, H, W, s, e.img, st);
+        case END_IMAGE: {
+            const int images = e.img->channels == 4 ? N / 2 : N;
+            if (!e.scaled) return compact_tail_image(t, e.x, e.y, images, H, W, s, e.img, st);
+            return compact_tail_image_scaled(t, e.x, e.y, images, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, e.img, &geom, st);
+        }
     }
     return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
 }

@@ -169,26 +169,8 @@ __global__ __launch_bounds__(256) void frame_head_kernel(Src src, T* __restrict_
 
 // ---- image modes (include/resr.h: grey, RGB and RGBA images of 8 or 16 bits; frames.py holds the definition once more in numpy) ----
 
-// cv2's fixed-point RGB2GRAY on integer levels: the coefficients sum to 2^14 (grey of (v, v, v) is v), the sum stays below 2^30 at 65535
-__device__ __forceinline__ unsigned grey_of(const unsigned (&o)[3]) { return (4899u * o[0] + 9617u * o[1] + 1868u * o[2] + 8192u) >> 14; }
-
-// The C levels of pixel p of an image batch [.,.,.,C]; an RGBA pixel is one load: a dword of four bytes, 8 bytes of four words.
-template <int C, int BITS>
-__device__ __forceinline__ void image_pixel(const typename Depth<BITS>::word* __restrict__ src, long p, unsigned (&lv)[4]) {
-    if constexpr (C == 4 && BITS == 8) {
-        const unsigned v = reinterpret_cast<const unsigned*>(src)[p];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) lv[c] = (v >> (8 * c)) & 255u;
-    } else if constexpr (C == 4) {
-        const uint2 v = reinterpret_cast<const uint2*>(src)[p];
-        lv[0] = v.x & 65535u; lv[1] = v.x >> 16; lv[2] = v.y & 65535u; lv[3] = v.y >> 16;
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) lv[c] = src[p * C + c];
-    }
-}
-
-// ... and an image batch of N images, `colour` = N * h * w pixels: network pixel p < colour is the colour of image pixel p (the grey
+// (grey_of, image_pixel, with_image_mode, image_is_rgb8: yuv.h, shared with the outscale tail of image_resize.hip)
+// The third source of frame_head_kernel, an image batch of N images, `colour` = N * h * w pixels: network pixel p < colour is the colour of image pixel p (the grey
 // level three times), network pixel p >= colour (RGBA only: the second N images of the network's batch) the alpha level of image pixel
 // p - colour three times.
 template <int C, int BITS>
@@ -664,26 +646,6 @@ void launch_tail(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int
 
 // ---- image modes ----
 
-// A runtime image mode as a compile-time one, as with_scale: f(channels, bits), both std::integral_constant; false for any other mode
-// and for 8-bit RGB, which has no image kernels of its own (image_is_rgb8: the callers run the uint8 path's).
-template <typename F>
-bool with_image_mode(const ResrImageDesc& m, F&& f) {
-    auto depth = [&](auto C) {
-        if constexpr (decltype(C)::value != 3)
-            if (m.bits == 8) { f(C, std::integral_constant<int, 8>()); return true; }
-        if (m.bits == 16) { f(C, std::integral_constant<int, 16>()); return true; }
-        return false;
-    };
-    switch (m.channels) {
-        case 1: return depth(std::integral_constant<int, 1>());
-        case 3: return depth(std::integral_constant<int, 3>());
-        case 4: return depth(std::integral_constant<int, 4>());
-        default: return false;
-    }
-}
-
-// 8-bit RGB is the uint8 frame path: its kernels run
-bool image_is_rgb8(const ResrImageDesc* m) { return m->channels == 3 && m->bits == 8; }
 long image_group_of(const ResrImageDesc* m) { return image_group(m->channels, m->bits); }
 // The widest store of the tail (16 bytes of RGBA, 8 of 16-bit grey, else a dword) and the widest load of either end (an RGBA pixel is one
 // load, every other level a word of its own): what y and x must be aligned to

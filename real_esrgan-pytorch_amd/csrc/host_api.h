@@ -119,6 +119,11 @@ int compact_tail_u8_scaled(const float* t, const uint8_t* x, uint8_t* y, int n, 
                            const ResizeGeom* gp, hipStream_t st);
 int compact_tail_yuv420_scaled(const float* t, const void* x, void* y, int n, int h, int w, int s, const int32_t* idx_y, const float* w_y, const int32_t* idx_x, const float* w_x,
                                const ResrYuvDesc* qs, const ResrYuvDesc* qd, const ResizeGeom* gp, hipStream_t st);
+// the image modes' scaled tail: x, y image batches of n_images images in mode img; image_scaled_plan: its tile without the pointer checks
+// (false: a bad argument or none fits), *kind the ResizeOut of the mode
+bool image_scaled_plan(int h, int w, int s, int oh, int ow, int taps_y, int taps_x, int channels, int bits, ResizeGeom* out, int* kind);
+int compact_tail_image_scaled(const float* t, const void* x, void* y, int n_images, int h, int w, int s, const int32_t* idx_y, const float* w_y, const int32_t* idx_x, const float* w_x,
+                              const ResrImageDesc* img, const ResizeGeom* gp, hipStream_t st);
 // ---- disc_native.hip.  uv: the spectral-norm arena; table / n_chunks: discriminator_pack_table's, on the device ----
 size_t discriminator_param_count();
 size_t discriminator_uv_count();

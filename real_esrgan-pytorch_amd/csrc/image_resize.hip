@@ -42,6 +42,17 @@
 // pass.  Tiles have an even height and width (resize_plan skips the odd entries of its list), so tile origins are even, the edge
 // tile of an even output is even, and every chroma sample belongs to one workgroup.  The results are the compositions of
 // include/resr.h bit for bit: the sums are those of the two stages above, the integer functions those of frames.hip.
+//
+// IMAGE-MODE OUTSCALE.  The same tile with an image batch [N,H,W,C] of bytes or 16-bit words at both ends (grey, RGB, RGBA; top = 255
+// or 65535), the tail of resr_compact_forward_image_scaled.  The staged value is t + unit(level), the single add of
+// compact_tail_image_kernel (frames.hip): the level is the image's own channel, the grey level thrice, or -- for the second half of an
+// RGBA batch's network images -- the alpha word thrice; the pixel is read with image_pixel, an RGBA pixel as one load.  After the W pass
+// the three sums of a pixel are quantised to levels of top and staged in LDS as C words per pixel: RGB the three levels, grey grey_of
+// them, RGBA the three colour levels and one alpha word.  RGBA is ONE workgroup per output tile (two would each write part of a dword):
+// it stages its tables once, runs region, H pass, W pass and quantisation for colour image b, then the same steps for alpha image N + b
+// over the same region and the same LDS, takes grey_of the alpha levels into the fourth word, and stores; grid.z is N.  After a
+// barrier a tile row leaves as tw * C contiguous words through the row writer of the u8 stage.  Tiles may be odd, as for uint8.  The
+// sums are resize_tile's per channel and do not depend on the tile, so the result is to_image(resr_image_resize(float path)) bit for bit.
 #include <limits.h>
 
 #include "host_api.h"
@@ -55,7 +66,7 @@ constexpr int kResizeThreads = 256;
 constexpr size_t kResizeLdsBudget = 64 * 1024;
 constexpr int kResizeMaxTaps = 4096;
 
-// What resize_tile stores: fp32 [N,C,oh,ow], u8 [N,oh,ow,3], or a YUV 4:2:0 frame [N,3oh/2,ow] of BITS-bit samples in LAYOUT.
+// What resize_tile stores: fp32 [N,C,oh,ow], u8 [N,oh,ow,3], a YUV 4:2:0 frame [N,3oh/2,ow] of BITS-bit samples in LAYOUT ...
 struct OutF32 { static constexpr int kind = RESIZE_F32; };
 struct OutU8 { static constexpr int kind = RESIZE_U8; };
 template <int BITS, int LAYOUT>
@@ -64,6 +75,19 @@ struct OutYuv {
     static constexpr int bits = BITS, layout = LAYOUT;
     const ResrYuvDesc* q;
 };
+// ... or an image batch [N,oh,ow,C] of bytes or 16-bit words, n = N images: grey and alpha leave through grey_of their three levels
+template <int C, int BITS>
+struct OutImage {
+    static constexpr int kind = resize_image_kind(C, BITS);
+    static constexpr int channels = C, bits = BITS;
+    int n;
+};
+// network images a workgroup of that output stage runs: the colour and the alpha image of an RGBA tile, else one
+template <typename Out>
+constexpr int image_planes() {
+    if constexpr (resize_is_image(Out::kind)) return Out::channels == 4 ? 2 : 1;
+    else return 1;
+}
 
 // fp32 [N,C,H,W]
 struct PlanarSrc {
@@ -112,6 +136,28 @@ struct YuvShuffleSrc {
     }
 };
 
+// ... + its input images [n,h,w,C] of bytes or 16-bit words (frames.hip, image modes): the residual level of network image b < n is the
+// colour of image b (the grey level three times), that of network image b >= n (RGBA only) the alpha word of image b - n three times.
+// The pixel is read with image_pixel, so an RGBA pixel stays one load.
+template <int S, int C, int BITS>
+struct ImageShuffleSrc {
+    static constexpr bool kTriple = true;
+    const float* t;
+    const typename Depth<BITS>::word* x;
+    int h, w;             // LR
+    int n;                // images: the network's batch is n (RGBA: 2 n)
+    __device__ __forceinline__ void load3(long b, int Y, int X, float (&v)[3]) const {
+        const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
+        const long plane = (long)h * w;
+        const bool alpha = C == 4 && b >= n;
+        unsigned lv[4];
+        image_pixel<C, BITS>(x, ((alpha ? b - n : b) * h + yy) * (long)w + xx, lv);
+        const float* tp = t + (b * 3 * S * S + sy * S + sx) * plane + (long)yy * w + xx;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c] = tp[(long)c * S * S * plane] + unit_of<kTop<BITS>>(alpha ? lv[3] : C == 1 ? lv[0] : lv[c]);
+    }
+};
+
 // Slot j of a row of `len` words that starts at gp (word-aligned): slot 0 writes the words before the first 4-byte boundary, slot
 // j >= 1 one dword (or, at the row's end, the words that are left); at(k) is word k of the row.  len / WPD + 2 slots cover a row.
 template <typename word, typename At>
@@ -133,8 +179,8 @@ __device__ __forceinline__ void store_row_slot(word* __restrict__ gp, int len, i
     }
 }
 
-// The whole tile: region bounds, staging, both passes, quantisation and stores.  y: fp32 [N,C,oh,ow], u8 [N,oh,ow,3] or a YUV
-// 4:2:0 frame [N,3oh/2,ow] (Out).
+// The whole tile: region bounds, staging, both passes, quantisation and stores.  y: fp32 [N,C,oh,ow], u8 [N,oh,ow,3], a YUV
+// 4:2:0 frame [N,3oh/2,ow] or an image batch [N,oh,ow,C] (Out).
 template <typename Src, typename Out>
 __device__ __forceinline__ void resize_tile(const Src& src, const Out& out, void* __restrict__ y, const int32_t* __restrict__ idx_y,
                                             const float* __restrict__ w_y, const int32_t* __restrict__ idx_x,
@@ -183,37 +229,75 @@ __device__ __forceinline__ void resize_tile(const Src& src, const Out& out, void
         s_ix[i] = min(max(idx_x[(long)ox0 * g.px + i] - xmin, 0), rw - 1);
         s_wx[i] = w_x[(long)ox0 * g.px + i];
     }
+    // (an RGBA image runs from here to its quantised levels twice, over the same region and LDS: colour image b, then alpha image n + b;
+    // every other kind once)
+    constexpr int kPlanes = image_planes<Out>();
     const int region = rh * rw;
-    if constexpr (Src::kTriple) {
-        for (int i = tid; i < region; i += kResizeThreads) {
-            const int ry = i / rw, rx = i - ry * rw;
-            float v[3];
-            src.load3(b, ymin + ry, xmin + rx, v);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) s_src[(c * g.rh + ry) * g.pitch + rx] = v[c];
-        }
-    } else {
-        for (int c = 0; c < nc; ++c)
+    for (int pl = 0; pl < kPlanes; ++pl) {
+        long bn = b;
+        if constexpr (kPlanes > 1) bn += (long)pl * out.n;
+        if constexpr (Src::kTriple) {
             for (int i = tid; i < region; i += kResizeThreads) {
                 const int ry = i / rw, rx = i - ry * rw;
-                s_src[(c * g.rh + ry) * g.pitch + rx] = src.load(b, c0 + c, ymin + ry, xmin + rx);
+                float v[3];
+                src.load3(bn, ymin + ry, xmin + rx, v);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) s_src[(c * g.rh + ry) * g.pitch + rx] = v[c];
             }
-    }
-    __syncthreads();
-
-    // ---- H pass: LDS -> LDS ---------------------------------------------------------------------------------------------------
-    const int mid = th * rw;
-    for (int c = 0; c < nc; ++c)
-        for (int i = tid; i < mid; i += kResizeThreads) {
-            const int ty = i / rw, col = i - ty * rw;
-            const float* col_p = s_src + c * g.rh * g.pitch + col;
-            const int* iy = s_iy + ty * g.py;
-            const float* wy = s_wy + ty * g.py;
-            float acc = 0.f;
-            for (int k = 0; k < g.py; ++k) acc = fmaf(col_p[iy[k] * g.pitch], wy[k], acc);
-            s_mid[(c * g.th + ty) * g.pitch + col] = acc;
+        } else {
+            for (int c = 0; c < nc; ++c)
+                for (int i = tid; i < region; i += kResizeThreads) {
+                    const int ry = i / rw, rx = i - ry * rw;
+                    s_src[(c * g.rh + ry) * g.pitch + rx] = src.load(bn, c0 + c, ymin + ry, xmin + rx);
+                }
         }
-    __syncthreads();
+        __syncthreads();   // (the second time round this also ends the first W pass, which read the s_mid that the H pass below overwrites)
+
+        // ---- H pass: LDS -> LDS ---------------------------------------------------------------------------------------------------
+        const int mid = th * rw;
+        for (int c = 0; c < nc; ++c)
+            for (int i = tid; i < mid; i += kResizeThreads) {
+                const int ty = i / rw, col = i - ty * rw;
+                const float* col_p = s_src + c * g.rh * g.pitch + col;
+                const int* iy = s_iy + ty * g.py;
+                const float* wy = s_wy + ty * g.py;
+                float acc = 0.f;
+                for (int k = 0; k < g.py; ++k) acc = fmaf(col_p[iy[k] * g.pitch], wy[k], acc);
+                s_mid[(c * g.th + ty) * g.pitch + col] = acc;
+            }
+        __syncthreads();
+
+        // ---- an image mode's W pass: LDS -> registers -> the levels of the tile in LDS, pixel by pixel as C words (RGB: the three levels;
+        // grey: grey_of them; RGBA: the colour levels, then grey_of the alpha image's as the fourth word -- a thread fills the fourth word
+        // of the pixels whose colour it wrote) ------------------------------------------------------------------------------------------
+        if constexpr (resize_is_image(Out::kind)) {
+            constexpr int C = Out::channels;
+            typedef typename Depth<Out::bits>::word word;
+            word* s_lv = reinterpret_cast<word*>(s_out);
+            const int outs = th * tw;
+            for (int i = tid; i < outs; i += kResizeThreads) {
+                const int ty = i / tw, tx = i - ty * tw;
+                const int* ix = s_ix + tx * g.px;
+                const float* wx = s_wx + tx * g.px;
+                unsigned o[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float* row = s_mid + (c * g.th + ty) * g.pitch;
+                    float acc = 0.f;
+                    for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
+                    o[c] = quantise<kTop<Out::bits>>(acc);
+                }
+                if constexpr (C == 1) {
+                    s_lv[i] = (word)grey_of(o);
+                } else if (pl) {
+                    s_lv[i * C + 3] = (word)grey_of(o);
+                } else {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) s_lv[i * C + c] = (word)o[c];
+                }
+            }
+        }
+    }
 
     // ---- W pass: LDS -> registers, store --------------------------------------------------------------------------------------
     if constexpr (Out::kind == RESIZE_F32) {
@@ -252,6 +336,21 @@ __device__ __forceinline__ void resize_tile(const Src& src, const Out& out, void
             const int ty = i / slots, j = i - ty * slots;
             const uint8_t* sp = s_out + ty * len;
             store_row_slot(yb + ((b * g.oh + oy0 + ty) * (long)g.ow + ox0) * 3, len, j, [&](int k) { return sp[k]; });
+        }
+    } else if constexpr (resize_is_image(Out::kind)) {
+        constexpr int C = Out::channels;
+        typedef typename Depth<Out::bits>::word word;
+        constexpr int WPD = 4 / (int)sizeof(word);
+        const word* s_lv = reinterpret_cast<const word*>(s_out);
+        __syncthreads();
+        // a tile row is tw * C contiguous words of y
+        word* yw = reinterpret_cast<word*>(y);
+        const int len = tw * C;
+        const int slots = len / WPD + 2;
+        for (int i = tid; i < th * slots; i += kResizeThreads) {
+            const int ty = i / slots, j = i - ty * slots;
+            const word* sp = s_lv + ty * len;
+            store_row_slot(yw + ((b * g.oh + oy0 + ty) * (long)g.ow + ox0) * C, len, j, [&](int k) { return sp[k]; });
         }
     } else {
         // YUV 4:2:0 (th, tw, oy0, ox0, g.oh, g.ow all even): the levels of the tile, pixel by pixel as (R, G, B) words
@@ -344,6 +443,15 @@ __global__ __launch_bounds__(kResizeThreads) void compact_tail_yuv_scaled_kernel
     resize_tile(src, OutYuv<yuv_bits(LAYOUT), LAYOUT>{&qd}, y, idx_y, w_y, idx_x, w_x, g);
 }
 
+// The image modes' tail: grid.z = n images (an RGBA workgroup runs both of its network images: resize_tile)
+template <int S, int C, int BITS>
+__global__ __launch_bounds__(kResizeThreads) void compact_tail_image_scaled_kernel(ImageShuffleSrc<S, C, BITS> src, void* __restrict__ y,
+                                                                                   const int32_t* __restrict__ idx_y, const float* __restrict__ w_y,
+                                                                                   const int32_t* __restrict__ idx_x, const float* __restrict__ w_x,
+                                                                                   ResizeGeom g) {
+    resize_tile(src, OutImage<C, BITS>{src.n}, y, idx_y, w_y, idx_x, w_x, g);
+}
+
 // source pixels that t consecutive outputs of an axis (in -> out pixels, p taps) can reach
 int span_bound(int t, int in, int out, int p) {
     long s = p;
@@ -351,15 +459,16 @@ int span_bound(int t, int in, int out, int p) {
     return (int)(s < in ? s : in);
 }
 
-// tables + region + intermediate + the staging buffer of the output stage: three bytes (RESIZE_U8, RESIZE_YUV8) or three 16-bit
-// words (RESIZE_YUV10) per pixel of the tile
+// tables + region + intermediate + the staging buffer of the output stage: three bytes (RESIZE_U8, RESIZE_YUV8), three 16-bit
+// words (RESIZE_YUV10) or the C words of an image mode per pixel of the tile
 size_t lds_bytes(const ResizeGeom& g, int out) {
     size_t floats = 2 * ((size_t)g.th * g.py + (size_t)g.tw * g.px) + 3 * ((size_t)g.rh + g.th) * g.pitch;
-    return floats * 4 + (out == RESIZE_F32 ? 0 : align_up((size_t)g.th * g.tw * 3 * (out == RESIZE_YUV10 ? 2 : 1), 4));
+    const size_t pixel = out == RESIZE_F32 ? 0 : resize_is_image(out) ? resize_image_channels(out) * resize_image_word_bytes(out) : out == RESIZE_YUV10 ? 6 : 3;
+    return floats * 4 + align_up((size_t)g.th * g.tw * pixel, 4);
 }
 
 // The largest tile of the list whose LDS fits the budget (g: everything but th, tw, rh, rw, pitch); a YUV 4:2:0 output takes the
-// tiles of even height and width only.  false: none fits.
+// tiles of even height and width only (an image mode any, as uint8).  false: none fits.
 bool choose_tile(ResizeGeom& g, int out) {
     static const int tiles[][2] = {{32, 32}, {16, 32}, {16, 16}, {8, 16}, {8, 8}, {4, 8}, {4, 4}, {2, 4}, {2, 2}, {1, 2}, {1, 1}};
     const bool yuv = out == RESIZE_YUV8 || out == RESIZE_YUV10;
@@ -379,7 +488,7 @@ bool choose_tile(ResizeGeom& g, int out) {
 // Every check of a resize launch and the choice of its tile: no device work.  c, h, w: the source; who: the entry's name.
 int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, const void* idx_y, const void* w_y, int taps_y,
                 const void* idx_x, const void* w_x, int taps_x, int kind, const void* y, ResizeGeom* out) {
-    const bool yuv = kind == RESIZE_YUV8 || kind == RESIZE_YUV10, u8 = kind == RESIZE_U8;
+    const bool yuv = kind == RESIZE_YUV8 || kind == RESIZE_YUV10, u8 = kind == RESIZE_U8, image = resize_is_image(kind);
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0 || oh <= 0 || ow <= 0)
         return fail(RESR_ERR_ARG, "%s: bad shape (n=%d c=%d h=%d w=%d oh=%d ow=%d)", who, n, c, h, w, oh, ow);
     if (!idx_y || !w_y || !idx_x || !w_x) return fail(RESR_ERR_ARG, "%s: null tap table", who);
@@ -389,6 +498,8 @@ int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, con
     if (u8 && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the uint8 output must be 4-byte aligned", who);
     if (yuv && (c != 3 || ((oh | ow) & 1))) return fail(RESR_ERR_ARG, "%s: a 4:2:0 output wants 3 channels and an even height and width, got %d, %dx%d", who, c, oh, ow);
     if (yuv && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the YUV output must be 4-byte aligned", who);
+    if (image && c != 3) return fail(RESR_ERR_ARG, "%s: an image output wants 3 channels, got %d", who, c);
+    if (image && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the output images must be 4-byte aligned", who);
     ResizeGeom g;
     g.c = c; g.h = h; g.w = w; g.oh = oh; g.ow = ow; g.py = taps_y; g.px = taps_x;
     g.cgroups = (c + 2) / 3;
@@ -414,6 +525,22 @@ int compact_yuv420_scaled_fits(int h, int w, int s, int oh, int ow, int taps_y, 
     g.c = 3; g.h = h * s; g.w = w * s; g.oh = oh; g.ow = ow; g.py = taps_y; g.px = taps_x;
     g.cgroups = 1;
     return choose_tile(g, bits == 10 ? RESIZE_YUV10 : RESIZE_YUV8) ? 1 : 0;
+}
+
+// resr_compact_image_scaled_fits / resr_debug_image_resize_plan: the tile resize_plan would choose for an image mode's scaled tail
+// (8-bit RGB: the uint8 tail's), without its pointer checks.  false: a bad argument or no tile.  No device work, no error text.
+bool image_scaled_plan(int h, int w, int s, int oh, int ow, int taps_y, int taps_x, int channels, int bits, ResizeGeom* out, int* kind) {
+    if (h <= 0 || w <= 0 || s < 1 || s > 4 || oh <= 0 || ow <= 0) return false;
+    if ((channels != 1 && channels != 3 && channels != 4) || (bits != 8 && bits != 16)) return false;
+    if (taps_y < 1 || taps_y > kResizeMaxTaps || taps_x < 1 || taps_x > kResizeMaxTaps) return false;
+    if ((long)h * s > INT_MAX || (long)w * s > INT_MAX) return false;
+    ResizeGeom g;
+    g.c = 3; g.h = h * s; g.w = w * s; g.oh = oh; g.ow = ow; g.py = taps_y; g.px = taps_x;
+    g.cgroups = 1;
+    *kind = resize_image_kind(channels, bits);
+    if (!choose_tile(g, *kind)) return false;
+    *out = g;
+    return true;
 }
 
 int image_resize_dispatch(const float* x, void* y, int n, int c, int h, int w, int oh, int ow, const int32_t* idx_y, const float* w_y,
@@ -482,6 +609,32 @@ int compact_tail_yuv420_scaled(const float* t, const void* x, void* y, int n, in
     prof_after(st, (qs->layout != qd->layout ? 31095 : ten ? 31080 : 31070) + s, 2.0 * n * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
                (double)n * h * w * (s * s * 12.0 + 1.5 * sb) + (double)n * g.oh * g.ow * 1.5 * wb);
     RESR_CHECK_LAUNCH("compact_tail_yuv_scaled_kernel");
+    return RESR_OK;
+}
+
+// The fused tail of the scaled image ends of compact_forward_ends: x, y image batches of n_images images in mode img (the caller has
+// checked it), t the planes * n_images network images, g planned by resize_plan for n_images, c = 3, h = H * s, w = W * s and
+// resize_image_kind of the mode.  Profiling id 31110 + s (8-bit RGB: the uint8 tail's own).
+int compact_tail_image_scaled(const float* t, const void* x, void* y, int n_images, int h, int w, int s, const int32_t* idx_y, const float* w_y,
+                              const int32_t* idx_x, const float* w_x, const ResrImageDesc* img, const ResizeGeom* gp, hipStream_t st) {
+    if (image_is_rgb8(img)) return compact_tail_u8_scaled(t, (const uint8_t*)x, (uint8_t*)y, n_images, h, w, s, idx_y, w_y, idx_x, w_x, gp, st);
+    const ResizeGeom g = *gp;
+    const dim3 grid((unsigned)((g.ow + g.tw - 1) / g.tw), (unsigned)((g.oh + g.th - 1) / g.th), (unsigned)n_images);
+    const size_t lds = lds_bytes(g, resize_image_kind(img->channels, img->bits));
+    prof_before(st);
+    const bool ok = with_scale(s, [&](auto S) {
+        with_image_mode(*img, [&](auto C, auto B) {
+            typedef ImageShuffleSrc<decltype(S)::value, decltype(C)::value, decltype(B)::value> Src;
+            hipLaunchKernelGGL((compact_tail_image_scaled_kernel<decltype(S)::value, decltype(C)::value, decltype(B)::value>), grid, dim3(kResizeThreads),
+                               lds, st, (Src{t, (const typename Depth<decltype(B)::value>::word*)x, h, w, n_images}), y, idx_y, w_y, idx_x, w_x, g);
+        });
+    });
+    if (!ok) return fail(RESR_ERR_ARG, "compact_tail_image_scaled: upscale %d", s);
+    // per LR pixel of a network image: 3 s^2 floats of t and the image's pixel; per output pixel its words
+    const double pb = img->channels * img->bits / 8.0, planes = img->channels == 4 ? 2.0 : 1.0;
+    prof_after(st, 31110 + s, 2.0 * n_images * planes * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
+               (double)n_images * h * w * planes * (s * s * 12.0 + pb) + (double)n_images * g.oh * g.ow * pb);
+    RESR_CHECK_LAUNCH("compact_tail_image_scaled_kernel");
     return RESR_OK;
 }
 

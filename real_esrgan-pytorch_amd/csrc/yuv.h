@@ -1,7 +1,7 @@
 // yuv.h -- the integer YUV 4:2:0 <-> RGB definition of include/resr.h as device helpers, templates over bits per sample, and the two
-// float conversions every end of the frame path uses (level -> unit float, float -> level).  Shared by frames.hip (the heads, the
-// tails at the network's own factor, the generic conversions) and image_resize.hip (the YUV ends of the outscale tail): one
-// definition of each, hence the same bits everywhere.  frames.py holds the definition once more in numpy, which the tests compare with.
+// float conversions every end of the frame path uses (level -> unit float, float -> level), and the image modes' pixel load, grey and
+// mode switch.  Shared by frames.hip (the heads, the tails at the network's own factor, the generic conversions) and image_resize.hip
+// (the YUV and image ends of the outscale tail): one definition of each, hence the same bits everywhere.  frames.py holds the definition once more in numpy, which the tests compare with.
 #pragma once
 #include "common.h"
 
@@ -102,5 +102,47 @@ __device__ __forceinline__ unsigned chroma_of(const ResrYuvDesc& q, int row, con
     return (unsigned)((q.fq[3 * row] * s[0] + q.fq[3 * row + 1] * s[1] + q.fq[3 * row + 2] * s[2] + (kChromaOff<BITS> << 18) + (1 << 17)) >> 18) &
            (unsigned)kTop<BITS>;
 }
+
+// ---- image modes (include/resr.h: grey, RGB and RGBA images of 8 or 16 bits; frames.py holds the definition once more in numpy) ----
+
+// cv2's fixed-point RGB2GRAY on integer levels: the coefficients sum to 2^14 (grey of (v, v, v) is v), the sum stays below 2^30 at 65535
+__device__ __forceinline__ unsigned grey_of(const unsigned (&o)[3]) { return (4899u * o[0] + 9617u * o[1] + 1868u * o[2] + 8192u) >> 14; }
+
+// The C levels of pixel p of an image batch [.,.,.,C]; an RGBA pixel is one load: a dword of four bytes, 8 bytes of four words.
+template <int C, int BITS>
+__device__ __forceinline__ void image_pixel(const typename Depth<BITS>::word* __restrict__ src, long p, unsigned (&lv)[4]) {
+    if constexpr (C == 4 && BITS == 8) {
+        const unsigned v = reinterpret_cast<const unsigned*>(src)[p];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) lv[c] = (v >> (8 * c)) & 255u;
+    } else if constexpr (C == 4) {
+        const uint2 v = reinterpret_cast<const uint2*>(src)[p];
+        lv[0] = v.x & 65535u; lv[1] = v.x >> 16; lv[2] = v.y & 65535u; lv[3] = v.y >> 16;
+    } else {
+#pragma unroll
+        for (int c = 0; c < C; ++c) lv[c] = src[p * C + c];
+    }
+}
+
+// A runtime image mode as a compile-time one, as with_scale: f(channels, bits), both std::integral_constant; false for any other mode
+// and for 8-bit RGB, which has no image kernels of its own (image_is_rgb8: the callers run the uint8 path's).
+template <typename F>
+inline bool with_image_mode(const ResrImageDesc& m, F&& f) {
+    auto depth = [&](auto C) {
+        if constexpr (decltype(C)::value != 3)
+            if (m.bits == 8) { f(C, std::integral_constant<int, 8>()); return true; }
+        if (m.bits == 16) { f(C, std::integral_constant<int, 16>()); return true; }
+        return false;
+    };
+    switch (m.channels) {
+        case 1: return depth(std::integral_constant<int, 1>());
+        case 3: return depth(std::integral_constant<int, 3>());
+        case 4: return depth(std::integral_constant<int, 4>());
+        default: return false;
+    }
+}
+
+// 8-bit RGB is the uint8 frame path: its kernels run
+inline bool image_is_rgb8(const ResrImageDesc* m) { return m->channels == 3 && m->bits == 8; }
 
 }  // namespace resr

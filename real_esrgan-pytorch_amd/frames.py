@@ -103,7 +103,16 @@ top, 0, top)) in fp32: `imgproc.tensor_to_image`'s rule with top for 255.  (Upst
 reference truncates, and so does this path, which takes grey of the quantised levels.)  uint8 RGB is `upscale_u8`.  A model with a fused
 entry (`SRVGGNetCompact.forward_image`: the head reads the image's own words, the tail writes them) runs it when the planes * N images
 fit one call; every other case (the RRDB `Generator`, tiled frames) is `to_image(super_resolve(model, from_image(images)))`, one launch
-each way.  No `outscale` and no `FrameStream` for these modes; `PIXEL_FORMATS` does not list them.
+each way.  With `outscale` (OUTSCALE above: r = o / s, the banded tap tables, H pass then W pass in fp32) the float frames are resized
+before they are quantised:
+
+    upscale_image(model, images, outscale=o) == rgb_to_image_np(q(resize(float_path(image_to_rgb_np(images) / top), r)), channels)
+
+so grey is taken of the three quantised, resized levels, and the RGBA alpha is the grey of the resized alpha images' levels.  The fused
+entry (`forward_image(images, outscale=o)`, `resr_compact_forward_image_scaled`: neither the fp32 x4 frames of the planes * N network
+images nor their resized fp32 frames exist on the device) runs under the rule above where `resr_compact_image_scaled_fits` finds a
+tile; every other case is `to_image(resize_with_plan(super_resolve(model, from_image(images)), plan))`, the same device routines, hence
+the same bits.  No `FrameStream` for these modes; `PIXEL_FORMATS` does not list them.
 """
 from __future__ import annotations
 
@@ -740,22 +749,41 @@ def to_image(sr: torch.Tensor, channels: int, dtype) -> torch.Tensor:
 
 
 @torch.no_grad()
-def upscale_image(model, images: torch.Tensor, halo: Optional[int] = None) -> torch.Tensor:
+def upscale_image(model, images: torch.Tensor, halo: Optional[int] = None, outscale: Optional[float] = None, plan=None) -> torch.Tensor:
     """An image batch on the model's device -- uint8 or uint16, [N,H,W] or [N,H,W,1] grey, [N,H,W,3] RGB, [N,H,W,4] RGBA, contiguous
     -> the upscaled batch of the same dtype and trailing shape, [N,sH,sW(,C)].  Bit for bit
     `rgb_to_image_np(q(float_path(image_to_rgb_np(images) / top)), channels)` (module docstring, IMAGE MODES).  The one place that
     chooses, by `upscale_u8`'s rule: uint8 RGB IS `upscale_u8`; a model with the fused entry (`SRVGGNetCompact.forward_image`) runs it
     when the network's batch of planes * N images fits one call; every other case (the RRDB `Generator`, frames the tiler has to cut)
-    is `to_image(super_resolve(model, from_image(images)))`.  `halo`: `upscale_u8`'s."""
+    is `to_image(super_resolve(model, from_image(images)))`.  `halo`: `upscale_u8`'s.
+
+    `outscale`, `plan`: `upscale_u8`'s -> [N, *output_size(H, W, s, outscale)(, C)]: the float frames are resized (`resize_with_plan`,
+    fp32 out) before they are quantised -- inside the fused call's last kernel where the library finds a tile within the resize kernel's
+    LDS (`resr_compact_image_scaled_fits`: no device work), else as a launch of its own between `super_resolve` and `to_image`.  A bad
+    outscale and a frame the resize rule refuses are ValueErrors before any launch."""
     n, h, w, c = check_images(images, "upscale_image")
     s = model.upscale_factor
+    o = check_outscale(outscale, s, "upscale_image")
     if c == 3 and images.dtype == torch.uint8:
-        return upscale_u8(model, images, halo)
-    if hasattr(model, "forward_image") and tiling.fits_whole(model, (2 if c == 4 else 1) * n, h, w):
-        out = model.forward_image(images)
+        return upscale_u8(model, images, halo, outscale=o, plan=plan)
+    planes = 2 if c == 4 else 1
+    fused = hasattr(model, "forward_image") and tiling.fits_whole(model, planes * n, h, w)
+    if o is None:
+        out_h, out_w = h * s, w * s
+        if fused:
+            out = model.forward_image(images)
+        else:
+            out = to_image(tiling.super_resolve(model, from_image(images), halo), c, images.dtype)
     else:
-        out = to_image(tiling.super_resolve(model, from_image(images), halo), c, images.dtype)
-    return out.reshape((n, h * s, w * s) + tuple(images.shape[3:]))
+        plan = _resize_plan(h, w, s, o, images.device, plan)                  # ValueError before any launch, as in upscale_u8
+        out_h, out_w = plan.out_h, plan.out_w
+        bits = 8 if images.dtype == torch.uint8 else 16
+        if fused and _lib.lib().resr_compact_image_scaled_fits(h, w, s, out_h, out_w, plan.taps_y, plan.taps_x, c, bits):
+            out = model.forward_image(images, outscale=o, plan=plan)
+        else:
+            from .imgproc import resize_with_plan
+            out = to_image(resize_with_plan(tiling.super_resolve(model, from_image(images), halo), plan), c, images.dtype)
+    return out.reshape((n, out_h, out_w) + tuple(images.shape[3:]))
 
 
 class _Slot:

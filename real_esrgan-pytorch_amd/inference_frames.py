@@ -13,8 +13,9 @@ frames first (ffmpeg -i in.mp4 lr/%06d.png), as upstream's inference_realesrgan_
 `--keep_mode` (default off: every file is decoded with `.convert("RGB")`, as above): a file whose PIL mode is `L` (8-bit grey), `RGBA`
 or `I;16` (16-bit grey) keeps it, and `LA` becomes RGBA: such a file goes through `frames.upscale_image` on its own -- alpha through the
 network as a grey image, 16 bits in and 16 bits out -- and is written in the mode it came in.  RGB files, and every other mode through
-`.convert("RGB")`, keep going through the pipelined `FrameStream`.  `--outscale` does not apply to the kept modes (an error when both
-are given and such a file turns up).  PIL has no 16-bit RGB or RGBA mode: those are `frames.upscale_image` on arrays of your own.
+`.convert("RGB")`, keep going through the pipelined `FrameStream`.  `--outscale F` applies to the kept modes too
+(`upscale_image(..., outscale=F)`: frames.py, IMAGE MODES).  PIL has no 16-bit RGB or RGBA mode: those are `frames.upscale_image` on
+arrays of your own.
 """
 import argparse
 import os
@@ -64,12 +65,12 @@ def kept_mode(image):
     return KEPT_MODES.get(image.mode)
 
 
-def upscale_kept(model, image, mode: str):
-    """One PIL image of a kept mode through `frames.upscale_image` -> the PIL image of that mode."""
+def upscale_kept(model, image, mode: str, outscale=None):
+    """One PIL image of a kept mode through `frames.upscale_image` (at `outscale`) -> the PIL image of that mode."""
     from PIL import Image
     array = np.array(image if image.mode == mode else image.convert(mode))      # (a copy: PIL's own buffer is read-only)
     images = torch.from_numpy(array)[None].to(next(model.parameters()).device)
-    return Image.fromarray(upscale_image(model, images)[0].cpu().numpy())
+    return Image.fromarray(upscale_image(model, images, outscale=outscale)[0].cpu().numpy())
 
 
 def main(args) -> None:
@@ -84,12 +85,10 @@ def main(args) -> None:
             with Image.open(os.path.join(args.inputs_dir, name)) as image:      # (reads the header only)
                 if kept_mode(image) is not None:
                     kept[name] = kept_mode(image)
-        if kept and getattr(args, "outscale", None) is not None:
-            raise ValueError(f"--keep_mode: --outscale does not apply to grey, RGBA and 16-bit files ({next(iter(kept))})")
         names = [name for name in names if name not in kept]
     for name, mode in kept.items():
         with Image.open(os.path.join(args.inputs_dir, name)) as image:
-            upscale_kept(model, image, mode).save(os.path.join(args.output_dir, name))
+            upscale_kept(model, image, mode, getattr(args, "outscale", None)).save(os.path.join(args.output_dir, name))
         print(f"SR image save to `{os.path.join(args.output_dir, name)}`")
 
     def decode():
