@@ -290,14 +290,20 @@ class SRVGGNetCompact(nn.Module):
         if not frames.is_contiguous():
             raise RuntimeError("SRVGGNetCompact.forward_u8: frames must be contiguous (HWC bytes, as an image decoder leaves them)")
         n, h, w, _ = frames.shape
+        return self._frame_tail("resr_compact_forward_u8", frames, n, h, w, lambda oh, ow: (n, oh, ow, self.num_out_ch), torch.uint8, o, plan,
+                                "SRVGGNetCompact.forward_u8")
+
+    def _frame_tail(self, entry: str, src: torch.Tensor, n: int, h: int, w: int, shape, dtype, o, plan, what: str, *desc, after_src=()) -> torch.Tensor:
+        """What the frame entries share once their own input is checked (n: the network's batch; `shape(out_h, out_w)`: the
+        result's; `desc`, `after_src`: the entry's descriptors, as `_call` places them).  o None: `entry` at the model's factor.
+        Else `entry`_scaled with the checked plan of `_scaled_plan`, the result of the plan's size."""
         s = self.upscale
         if o is None:
-            y = torch.empty((n, h * s, w * s, self.num_out_ch), dtype=torch.uint8, device=frames.device)
-            return self._call("resr_compact_forward_u8", frames, n, h, w, y)
+            return self._call(entry, src, n, h, w, torch.empty(shape(h * s, w * s), dtype=dtype, device=src.device), *desc, after_src=after_src)
         _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
-        plan = self._scaled_plan(frames, h, w, o, plan, "SRVGGNetCompact.forward_u8")
-        y = torch.empty((n, plan.out_h, plan.out_w, self.num_out_ch), dtype=torch.uint8, device=frames.device)
-        return self._call("resr_compact_forward_u8_scaled", frames, n, h, w, y, *plan.args())
+        plan = self._scaled_plan(src, h, w, o, plan, what)
+        y = torch.empty(shape(plan.out_h, plan.out_w), dtype=dtype, device=src.device)
+        return self._call(entry + "_scaled", src, n, h, w, y, *plan.args(), *desc, after_src=after_src)
 
     def _scaled_plan(self, frames: torch.Tensor, h: int, w: int, o: float, plan, what: str):
         """The checked `imgproc.ResizePlan` of an outscale call on h x w frames: the caller's `plan` when it is one for this call,
@@ -323,14 +329,7 @@ class SRVGGNetCompact(nn.Module):
         ydesc = _frames._desc(bits, layout, matrix)
         self._guard()
         n, h, w = _frames._check_yuv(frames, what, bits)
-        s = self.upscale
-        if o is None:
-            y = torch.empty((n, h * s * 3 // 2, w * s), dtype=frames.dtype, device=frames.device)
-            return self._call(entry, frames, n, h, w, y, C.byref(ydesc))
-        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
-        plan = self._scaled_plan(frames, h, w, o, plan, what)
-        y = torch.empty((n, plan.out_h * 3 // 2, plan.out_w), dtype=frames.dtype, device=frames.device)
-        return self._call(entry + "_scaled", frames, n, h, w, y, *plan.args(), C.byref(ydesc))
+        return self._frame_tail(entry, frames, n, h, w, lambda oh, ow: (n, oh * 3 // 2, ow), frames.dtype, o, plan, what, C.byref(ydesc))
 
     def forward_yuv420(self, frames: torch.Tensor, layout: str = "i420", matrix: str = "bt601", outscale: Optional[float] = None,
                        plan=None) -> torch.Tensor:
@@ -384,14 +383,8 @@ class SRVGGNetCompact(nn.Module):
         qa, qb = _frames.format_desc(a), _frames.format_desc(b)
         self._guard()
         n, h, w = _frames._check_yuv(frames, what, a.fmt.bits)
-        s = self.upscale
-        if o is None:
-            y = torch.empty((n, h * s * 3 // 2, w * s), dtype=b.fmt.torch_dtype, device=frames.device)
-            return self._call("resr_compact_forward_yuv420_mixed", frames, n, h, w, y, C.byref(qb), after_src=(C.byref(qa),))
-        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
-        plan = self._scaled_plan(frames, h, w, o, plan, what)
-        y = torch.empty((n, plan.out_h * 3 // 2, plan.out_w), dtype=b.fmt.torch_dtype, device=frames.device)
-        return self._call("resr_compact_forward_yuv420_mixed_scaled", frames, n, h, w, y, *plan.args(), C.byref(qb), after_src=(C.byref(qa),))
+        return self._frame_tail("resr_compact_forward_yuv420_mixed", frames, n, h, w, lambda oh, ow: (n, oh * 3 // 2, ow), b.fmt.torch_dtype, o, plan,
+                                what, C.byref(qb), after_src=(C.byref(qa),))
 
     def forward_image(self, images: torch.Tensor, outscale: Optional[float] = None, plan=None) -> torch.Tensor:
         """images: a grey, RGB or RGBA batch -- uint8 or uint16, [N,H,W] or [N,H,W,1], [N,H,W,3], [N,H,W,4] -- on the model's device,
@@ -414,15 +407,9 @@ class SRVGGNetCompact(nn.Module):
         self._guard()
         n, h, w, c = _frames.check_images(images, what)
         idesc = _frames.image_desc(c, images.dtype)
-        s = self.upscale
         planes = 2 if c == 4 else 1
-        if o is None:
-            y = torch.empty((n, h * s, w * s) + tuple(images.shape[3:]), dtype=images.dtype, device=images.device)
-            return self._call("resr_compact_forward_image", images, planes * n, h, w, y, C.byref(idesc))
-        _lib.require_cuda(self.flat_parameters(), "SRVGGNetCompact parameters")    # refused before a plan is looked at
-        plan = self._scaled_plan(images, h, w, o, plan, what)
-        y = torch.empty((n, plan.out_h, plan.out_w) + tuple(images.shape[3:]), dtype=images.dtype, device=images.device)
-        return self._call("resr_compact_forward_image_scaled", images, planes * n, h, w, y, *plan.args(), C.byref(idesc))
+        return self._frame_tail("resr_compact_forward_image", images, planes * n, h, w, lambda oh, ow: (n, oh, ow) + tuple(images.shape[3:]),
+                                images.dtype, o, plan, what, C.byref(idesc))
 
     def load_official_state_dict(self, checkpoint) -> None:
         """Upstream's `{"params_ema": sd}` / `{"params": sd}` (params_ema preferred) or a bare state dict (model.load_official_state_dict)."""

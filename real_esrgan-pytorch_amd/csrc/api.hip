@@ -228,7 +228,7 @@ int resr_compact_backward(const ResrCompactDesc* d, const float* gy_nchw, const 
 int resr_compact_forward_u8(const ResrCompactDesc* d, const uint8_t* x_u8, const float* params, const void* packed,
                             void* workspace, size_t workspace_bytes, uint8_t* y_u8, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_RGB8, false, x_u8, y_u8, {}, nullptr, nullptr, 0}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
+    return compact_forward_ends(d, {END_IMAGE, false, x_u8, y_u8, {}, nullptr, nullptr, 0, &kRgb8}, params, packed, workspace, workspace_bytes, (hipStream_t)stream,
                                 "compact_forward_u8");
 }
 
@@ -237,7 +237,7 @@ int resr_compact_forward_u8_scaled(const ResrCompactDesc* d, const uint8_t* x_u8
                                    const int32_t* idx_y, const float* w_y, int32_t taps_y, const int32_t* idx_x, const float* w_x,
                                    int32_t taps_x, void* stream) {
     RESR_DEVICE_SCOPE(stream);
-    return compact_forward_ends(d, {END_RGB8, true, x_u8, y_u8, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, nullptr, nullptr, 0}, params, packed,
+    return compact_forward_ends(d, {END_IMAGE, true, x_u8, y_u8, {oh, ow, taps_y, taps_x, idx_y, idx_x, w_y, w_x}, nullptr, nullptr, 0, &kRgb8}, params, packed,
                                 workspace, workspace_bytes, (hipStream_t)stream, "compact_forward_u8_scaled");
 }
 

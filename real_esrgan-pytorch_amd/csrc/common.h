@@ -115,15 +115,19 @@ struct ResizeGeom {
     int rh, rw, pitch;    // capacity of the staged region, LDS row pitch (floats)
     int cgroups;          // ceil(c / 3)
 };
-// ... and what it stores: fp32 NCHW, uint8 HWC, a YUV 4:2:0 frame of 8- or 10-bit samples (the latter two: even tiles only, and
-// a staging buffer of levels as wide as the sample's word), or an image batch [N,oh,ow,C] of bytes or 16-bit words: RESIZE_IMAGE +
-// 2 * C + (16 bits), resize_image_kind -- C words per pixel in the staging buffer (8-bit RGB is RESIZE_U8 itself)
+// ... and what it stores: fp32 NCHW, a YUV 4:2:0 frame of 8- or 10-bit samples (even tiles only, and a staging buffer of levels as
+// wide as the sample's word), or an image batch [N,oh,ow,C] of bytes or 16-bit words, C words per pixel in the staging buffer:
+// resize_image_kind.  RESIZE_U8 is the (3, 8) image kind, uint8 HWC frames; the others are RESIZE_IMAGE + 2 * C + (16 bits).
 enum ResizeOut { RESIZE_F32 = 0, RESIZE_U8 = 1, RESIZE_YUV8 = 2, RESIZE_YUV10 = 3, RESIZE_IMAGE = 4 };
 constexpr int resize_image_kind(int channels, int bits) { return channels == 3 && bits == 8 ? RESIZE_U8 : RESIZE_IMAGE + 2 * channels + (bits == 16); }
-constexpr bool resize_is_image(int kind) { return kind >= RESIZE_IMAGE; }
-constexpr int resize_image_channels(int kind) { return (kind - RESIZE_IMAGE) >> 1; }
-constexpr int resize_image_word_bytes(int kind) { return 1 + ((kind - RESIZE_IMAGE) & 1); }
+constexpr bool resize_is_image(int kind) { return kind == RESIZE_U8 || kind >= RESIZE_IMAGE; }
+constexpr int resize_image_channels(int kind) { return kind == RESIZE_U8 ? 3 : (kind - RESIZE_IMAGE) >> 1; }
+constexpr int resize_image_word_bytes(int kind) { return kind == RESIZE_U8 ? 1 : 1 + ((kind - RESIZE_IMAGE) & 1); }
 
+// uint8 RGB frames [N,H,W,3] are the (3, 8) image mode: what the uint8-typed entries pass where an image entry passes its descriptor.
+// Its launches keep the profiling ids they had before they were an image mode's (image_id: the id of that mode, of any other).
+inline const ResrImageDesc kRgb8{3, 8};
+inline int image_id(const ResrImageDesc* m, int rgb8, int other) { return m->channels == 3 && m->bits == 8 ? rgb8 : other; }
 
 // compact.hip: the two ends of one forward pass (compact_forward_ends; api.hip builds one per entry): what x and y are, and what
 // else that kind of end needs.
@@ -134,13 +138,13 @@ struct ScaledTail {
 };
 enum EndFormat {
     END_F32,    // x [N,3,H,W] fp32 -> y [N,3,sH,sW] fp32: layout.hip's head, compact_tail
-    END_RGB8,   // x [N,H,W,3] uint8 -> y [N,sH,sW,3] uint8: frames.hip, the conversions fused into the head and the tail
     END_YUV,    // x [N,3H/2,W] -> y [N,3sH/2,sW], YUV 4:2:0 frames of bytes or 16-bit words (src->layout, dst->layout): the colour conversions too
-    END_IMAGE,  // x [N,H,W,C] -> y [N,sH,sW,C], grey / RGB / RGBA images of bytes or 16-bit words (img): the network's batch is planes * N
+    END_IMAGE,  // x [N,H,W,C] -> y [N,sH,sW,C], grey / RGB / RGBA images of bytes or 16-bit words (img; uint8 RGB frames: kRgb8): frames.hip, the
+                // conversions fused into the head and the tail; the network's batch is planes * N
 };
 struct Ends {
     EndFormat format;
-    bool scaled;             // END_RGB8, END_YUV, END_IMAGE: y is the frame resized to sc.oh x sc.ow by the tail of image_resize.hip
+    bool scaled;             // END_YUV, END_IMAGE: y is the frame resized to sc.oh x sc.ow by the tail of image_resize.hip
     const void* x;
     void* y;
     ScaledTail sc;           // scaled

@@ -9,8 +9,6 @@
 // T = f16 (fast) / f32 (strict); RESR_F16X2 (exact16): every NHWC tensor is a hi/lo pair, the lo tensor right behind the hi one,
 // three stages per chunk.  No padding beyond each conv's own pad = 1: any H, W >= 1.
 // Every entry of the C ABI is this sequence with its own pair of ends (Ends of common.h: a format and a flag), same plan, same workspace:
-//   END_RGB8          uint8 HWC frames: frames.hip's head in place of the layout kernel, its u8 tail (pixel-shuffle + residual +
-//                     * 255, clamp, truncate) in place of compact_tail_kernel;
 //   END_YUV           YUV 4:2:0 frames [N,3H/2,W] of bytes or of 16-bit words holding 10-bit samples (yuv420p10le / P010: 1023
 //                     levels): frames.hip's head reading YUV, and its YUV tail.  The source and the destination each have their
 //                     own descriptor (Ends::src, Ends::dst): the head and the tail's residual follow the source's depth, layout
@@ -18,7 +16,8 @@
 //   END_IMAGE         grey, RGB or RGBA images [N,H,W,C] of bytes or 16-bit words (Ends::img): frames.hip's head reading them -- the
 //                     network's batch is the N colour (or grey) images and, for RGBA, the N alpha planes behind them, each level
 //                     three times -- and its image tail (grey: the fixed-point grey of the three levels; RGBA: the alpha images'
-//                     grey as the fourth channel);
+//                     grey as the fourth channel).  uint8 HWC frames (resr_compact_forward_u8) are the (3, 8) mode, kRgb8: the
+//                     tail is pixel-shuffle + residual + * 255, clamp, truncate in place of compact_tail_kernel;
 //   ... and scaled    ("outscale") image_resize.hip's fused tail in place of any of them: the HR frame is formed tile by tile in LDS
 //                     and only the resized frame, uint8 [N,oh,ow,3], YUV 4:2:0 [N,3oh/2,ow] or images [N,oh,ow,C], is written.
 // Training (compact_forward_train / compact_backward, at the end of this file; kernels of its own in compact_train.hip): the same
@@ -171,7 +170,8 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
     const ResrCompactDesc& d = p.d;
     if (!e.x || !e.y || !params || !packed || !workspace) return fail(RESR_ERR_ARG, "%s: null argument", who);
     if (e.format == END_F32 && e.scaled) return fail(RESR_ERR_ARG, "%s: unknown kind of ends", who);
-    if (e.format == END_RGB8 && ((size_t)e.y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
+    // (the uint8-typed entries, which pass kRgb8 itself, name their y as they always have; scaled or not)
+    if (e.img == &kRgb8 && ((size_t)e.y & 3) != 0) return fail(RESR_ERR_ARG, "%s: y_u8 must be 4-byte aligned", who);
     int rc = RESR_OK;
     // the descriptor and the LR frame; of scaled ends the output pointer's rule is the plan's (nullptr passes the unscaled tail's)
     if (e.format == END_YUV) rc = yuv_forward_check(who, d.n, d.h, d.w, d.upscale, e.scaled ? nullptr : e.y, e.src, e.dst, e.bits_expected);
@@ -179,8 +179,7 @@ int check_ends(const CPlan& p, const Ends& e, const float* params, const void* p
     if (!rc && e.scaled) {
         // an image tail's workgroups own whole pixels: its grid counts the N images, not the planes * N of the network
         const int images = e.format == END_IMAGE && e.img->channels == 4 ? d.n / 2 : d.n;
-        const int kind = e.format == END_RGB8 ? RESIZE_U8 : e.format == END_IMAGE ? resize_image_kind(e.img->channels, e.img->bits)
-                         : yuv_bits(e.dst->layout) == 8 ? RESIZE_YUV8 : RESIZE_YUV10;
+        const int kind = e.format == END_IMAGE ? resize_image_kind(e.img->channels, e.img->bits) : yuv_bits(e.dst->layout) == 8 ? RESIZE_YUV8 : RESIZE_YUV10;
         rc = resize_plan(who, images, 3, d.h * d.upscale, d.w * d.upscale, e.sc.oh, e.sc.ow, e.sc.idx_y, e.sc.w_y, e.sc.taps_y, e.sc.idx_x,
                          e.sc.w_x, e.sc.taps_x, kind, e.y, geom);
     }
@@ -210,7 +209,7 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
     const int N = d->n, H = d->h, W = d->w;
     const int64_t lo32 = x2 ? (int64_t)p.px * 32 : 0, lo64 = x2 ? (int64_t)p.px * 64 : 0;   // hi -> lo element offsets
     if (e.format == END_F32) rc = nchw_to_nhwc_dispatch((const float*)e.x, xin, N, 3, H, W, 1, 32, d->dtype, nullptr, st, (long)lo32);
-    else rc = frame_head_dispatch(e.x, xin, N, H, W, d->dtype, st, (long)lo32, e.src, e.img);   // src and img null: RGB bytes; src's layout: bytes or 16-bit words
+    else rc = frame_head_dispatch(e.x, xin, N, H, W, d->dtype, st, (long)lo32, e.src, e.img);   // src's layout: bytes or 16-bit words
     if (rc) return rc;
     auto desc = [&](const CConv& c, int flags) { return cconv_desc(*d, c, flags, lo32, lo64); };
     const int nbody = (int)p.convs.size() - 1;   // conv 0 + the num_conv body convs: 64 channels + activation
@@ -237,9 +236,6 @@ int compact_forward_ends(const ResrCompactDesc* d, const Ends& e, const float* p
     const int s = d->upscale;
     switch (e.format) {
         case END_F32: return compact_tail(t, (const float*)e.x, (float*)e.y, N, H, W, s, st);
-        case END_RGB8:
-            if (!e.scaled) return compact_tail_u8(t, (const uint8_t*)e.x, (uint8_t*)e.y, N, H, W, s, st);
-            return compact_tail_u8_scaled(t, (const uint8_t*)e.x, (uint8_t*)e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, &geom, st);
         case END_YUV:
             if (!e.scaled) return compact_tail_yuv(t, e.x, e.y, N, H, W, s, e.src, e.dst, st);
             return compact_tail_yuv420_scaled(t, e.x, e.y, N, H, W, s, e.sc.idx_y, e.sc.w_y, e.sc.idx_x, e.sc.w_x, e.src, e.dst, &geom, st);

@@ -1,19 +1,20 @@
-// frames.hip -- the uint8 frame path: u8 HWC images in, u8 HWC images out.
+// frames.hip -- the frame path: images of integer levels in, images of integer levels out.
 //
-//   frame_head     : u8 [N,H,W,3], or a YUV 4:2:0 frame [N,3H/2,W] (I420 / NV12), -> the compact net's x_in [N,H,W,32] in the
-//                    model's arithmetic (channels 3..31 zero): one kernel, the source of a pixel's RGB bytes its parameter
-//   compact_tail_u8: t [N,3S^2,H,W] fp32 + the u8 input frame -> u8 [N,H*S,W*S,3]   (pixel-shuffle + residual + quantise)
-//   u8_to_nchw     : u8 [N,H,W,3] -> fp32 [N,3,H,W]                (models whose first kernel is not ours to fuse)
-//   nchw_to_u8     : fp32 [N,3,H,W] -> u8 [N,H,W,3]                (... and whose last one is not: RRDB Generator, the tiler)
-//   compact_tail_yuv              : compact_tail_u8 with YUV 4:2:0 frames at both of its ends, of bytes or, as frame_head, of the
+//   frame_head     : an image batch [N,H,W,C] (uint8 RGB frames: C = 3, bytes), or a YUV 4:2:0 frame [N,3H/2,W], -> the compact net's
+//                    x_in [N,H,W,32] in the model's arithmetic (channels 3..31 zero): one kernel, the source of a pixel's RGB levels
+//                    its parameter
+//   compact_tail_image            : t [N,3S^2,H,W] fp32 + the input images -> images [N,H*S,W*S,C]   (pixel-shuffle + residual + quantise)
+//   image_to_nchw, nchw_to_image  : images <-> fp32 [N,3,H,W]      (models whose first and last kernel are not ours to fuse: RRDB
+//                                   Generator, the tiler); u8_to_nchw and nchw_to_u8 are their uint8 RGB entries
+//   compact_tail_yuv              : the same tail with YUV 4:2:0 frames at both of its ends, of bytes or, as frame_head, of the
 //                                   16-bit words of 10-bit samples (yuv420p10le / P010): one kernel, the layout of the source and
 //                                   the layout of the destination its parameters (one format twice, or a mixed pair)
 //   yuv420_to_rgb, rgb_to_yuv420  : the integer colour conversions on their own, u8 [N,3H/2,W] <-> u8 [N,H,W,3]
 //   yuv420p10_to_nchw, nchw_to_yuv420p10: 10-bit YUV [N,3H/2,W] <-> fp32 [N,3,H,W], one launch each, no RGB frame in between
-//   image modes                   : grey, RGB and RGBA images [N,H,W,C] of bytes or 16-bit words (255 or 65535 levels) at both ends -- a
-//                                   third source of frame_head (the network's batch: the N colour or grey images, for RGBA the N alpha
-//                                   planes behind them, each level thrice), compact_tail_image (grey and alpha leave through the
-//                                   fixed-point grey of their three levels), and the generic image_to_nchw / nchw_to_image
+//   image modes                   : grey, RGB and RGBA images [N,H,W,C] of bytes or 16-bit words (255 or 65535 levels) at both ends; the
+//                                   network's batch is the N colour or grey images, for RGBA the N alpha planes behind them, each level
+//                                   thrice; grey and alpha leave through the fixed-point grey of their three levels.  uint8 RGB is the
+//                                   (3, 8) mode (kRgb8): one template, one instance, under the profiling ids it has always had
 //
 // The result is DEFINED as what the float path followed by imgproc.tensor_to_image produces, bit for bit:
 //   in : x = (float)u8 / 255.0f, one IEEE division (numpy's astype(float32) / 255.0), then converted to the model's type exactly
@@ -33,68 +34,6 @@ namespace resr {
 
 namespace {
 
-__device__ __forceinline__ float u8_unit(unsigned v) { return unit_of<255>(v); }
-__device__ __forceinline__ unsigned quantise_u8(float v) { return quantise<255>(v); }
-
-// The output is a flat array of n * hS * wS pixels of 3 bytes; a thread owns 4 consecutive pixels = 12 bytes = three dword
-// stores (y is 4-byte aligned and 12 k is, whatever wS is), a wavefront writes 768 contiguous bytes.  Each pixel decodes its
-// own (n, Y, X); the last partial group falls back to byte stores.  The 3 x S planes read for one (Y/S, X/S) are plane-strided
-// but coalesced across lanes, as in compact_tail_kernel.  RES = false: the generic fp32 NCHW -> u8 HWC conversion (S = 1).
-template <int S, bool RES>
-__global__ __launch_bounds__(256) void compact_tail_u8_kernel(const float* __restrict__ t, const uint8_t* __restrict__ x,
-                                                              uint8_t* __restrict__ y, int n, int h, int w) {
-    const int HS = h * S, WS = w * S;
-    const long plane = (long)h * w;
-    const long total = (long)n * HS * WS;
-    const long q0 = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
-    if (q0 >= total) return;
-    const long row0 = q0 / WS;                 // b * HS + Y
-    int X = (int)(q0 - row0 * WS);
-    long b = row0 / HS;
-    int Y = (int)(row0 - b * HS);
-    unsigned bytes[12];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (q0 + k < total) {
-            const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
-            const float* tp = t + (b * 3 * S * S + sy * S + sx) * plane + (long)yy * w + xx;
-            const long xo = ((b * h + yy) * (long)w + xx) * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                float v = tp[(long)c * S * S * plane];
-                if constexpr (RES) v = v + u8_unit(x[xo + c]);
-                bytes[k * 3 + c] = quantise_u8(v);
-            }
-        } else {
-            bytes[k * 3] = bytes[k * 3 + 1] = bytes[k * 3 + 2] = 0u;
-        }
-        if (++X == WS) {
-            X = 0;
-            if (++Y == HS) { Y = 0; ++b; }
-        }
-    }
-    if (q0 + 4 <= total) {
-        unsigned* o = reinterpret_cast<unsigned*>(y + q0 * 3);
-#pragma unroll
-        for (int d = 0; d < 3; ++d)
-            o[d] = bytes[4 * d] | (bytes[4 * d + 1] << 8) | (bytes[4 * d + 2] << 16) | (bytes[4 * d + 3] << 24);
-    } else {
-        const int left = (int)(total - q0) * 3;
-#pragma unroll
-        for (int i = 0; i < 9; ++i)
-            if (i < left) y[q0 * 3 + i] = (uint8_t)bytes[i];
-    }
-}
-
-// One thread per pixel: 3 byte loads (a wavefront reads 192 contiguous bytes), one coalesced dword store per plane.
-__global__ __launch_bounds__(256) void u8_to_nchw_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, long total, long plane) {
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= total) return;
-    const long b = p / plane, r = p - b * plane;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + r] = u8_unit(src[p * 3 + c]);
-}
-
 // ---- YUV 4:2:0 (include/resr.h: the integer definition; frames.py holds it once more in numpy, which the tests compare with) ----
 
 // (the integer conversions themselves: yuv.h, shared with the outscale tail of image_resize.hip)
@@ -109,18 +48,9 @@ __device__ __forceinline__ unsigned pack_words(const unsigned* s, int layout = R
     return v;
 }
 
-// Where frame_head_kernel takes the three RGB bytes of pixel p from: an RGB frame holds them ...
-struct RgbSrc {
-    const uint8_t* __restrict__ src;
-    __device__ __forceinline__ void operator()(long p, unsigned (&rgb)[3]) const {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) rgb[c] = src[p * 3 + c];
-    }
-    static __device__ __forceinline__ float unit(unsigned v) { return u8_unit(v); }
-};
-
-// ... a YUV 4:2:0 frame (images of luma size h x w; bytes, or 16-bit words of 10-bit samples: three 16-bit loads and a mask or a
-// shift) yields them through the integer conversion, as levels of 255 or of 1023: `unit` is the division that goes with them.
+// Where frame_head_kernel and to_nchw_kernel take the three RGB levels of network pixel p from: a YUV 4:2:0 frame (images of luma
+// size h x w; bytes, or 16-bit words of 10-bit samples: three 16-bit loads and a mask or a shift) yields them through the integer
+// conversion, as levels of 255 or of 1023: `unit` is the division that goes with them.  (An image batch: ImageSrc, below.)
 template <int BITS>
 struct YuvSrc {
     const typename Depth<BITS>::word* __restrict__ src;
@@ -169,10 +99,10 @@ __global__ __launch_bounds__(256) void frame_head_kernel(Src src, T* __restrict_
 
 // ---- image modes (include/resr.h: grey, RGB and RGBA images of 8 or 16 bits; frames.py holds the definition once more in numpy) ----
 
-// (grey_of, image_pixel, with_image_mode, image_is_rgb8: yuv.h, shared with the outscale tail of image_resize.hip)
-// The third source of frame_head_kernel, an image batch of N images, `colour` = N * h * w pixels: network pixel p < colour is the colour of image pixel p (the grey
+// (grey_of, image_pixel, with_image_mode: yuv.h, shared with the outscale tail of image_resize.hip)
+// The other source of frame_head_kernel, an image batch of N images, `colour` = N * h * w pixels: network pixel p < colour is the colour of image pixel p (the grey
 // level three times), network pixel p >= colour (RGBA only: the second N images of the network's batch) the alpha level of image pixel
-// p - colour three times.
+// p - colour three times.  uint8 RGB frames are ImageSrc<3, 8>: three byte loads, a wavefront reads 192 contiguous bytes.
 template <int C, int BITS>
 struct ImageSrc {
     const typename Depth<BITS>::word* __restrict__ src;
@@ -192,8 +122,9 @@ constexpr int image_group(int c, int bits) { return c == 1 ? 4 : 32 / bits; }
 static_assert(image_group(1, 8) == 4 && image_group(1, 16) == 4 && image_group(3, 8) == 4 && image_group(3, 16) == 2 &&
               image_group(4, 8) == 4 && image_group(4, 16) == 2, "grey 4 pixels, 8-bit colour 4, 16-bit colour 2");
 
-// compact_tail_u8_kernel for an image mode: t [planes * n, 3 S^2, h, w] fp32 + the input images x [n,h,w,C] -> y [n,hS,wS,C] of the
-// same words.  Per output pixel and channel v = t + unit(x level), quantise<top>(v): RGB stores the three levels; grey stores
+// The tail of every image mode, uint8 RGB frames (C = 3, BITS = 8) among them: t [planes * n, 3 S^2, h, w] fp32 + the input images
+// x [n,h,w,C] -> y [n,hS,wS,C] of the same words.  The output is a flat array of n * hS * wS pixels; each pixel decodes its own (b, Y, X), and
+// the 3 x S planes read for one (Y/S, X/S) are plane-strided but coalesced across lanes, as in compact_tail_kernel.  Per output pixel and channel v = t + unit(x level), quantise<top>(v): RGB stores the three levels; grey stores
 // grey_of them (the residual is the grey level, thrice); RGBA stores the colour of image b's planes of t and, as the fourth word,
 // grey_of the three levels of image n + b, whose residual is the alpha level.  A thread owns G = image_group consecutive output pixels
 // = DW whole dwords, one store where DW is 1, 2 or 4 (grey8 a dword, grey16 8 bytes, RGBA 16 bytes) and three dword stores for RGB
@@ -222,10 +153,9 @@ __global__ __launch_bounds__(256) void compact_tail_image_kernel(const float* __
         for (int c = 0; c < C; ++c) words[k * C + c] = 0u;
         if (q0 + k < total) {
             const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
-            const long off = (long)(sy * S + sx) * plane + (long)yy * w + xx;
             unsigned lv[4] = {0u, 0u, 0u, 0u};
             if constexpr (RES) image_pixel<C, BITS>(x, (b * h + yy) * (long)w + xx, lv);
-            const float* tp = t + b * image + off;
+            const float* tp = t + (b * 3 * S * S + sy * S + sx) * plane + (long)yy * w + xx;
             unsigned o[3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -240,7 +170,7 @@ __global__ __launch_bounds__(256) void compact_tail_image_kernel(const float* __
                 for (int c = 0; c < 3; ++c) words[k * C + c] = o[c];
             }
             if constexpr (C == 4) {
-                const float* ta = t + (n + b) * image + off;
+                const float* ta = tp + n * image;
                 unsigned a[3];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
@@ -280,16 +210,17 @@ __global__ __launch_bounds__(256) void compact_tail_image_kernel(const float* __
     }
 }
 
-// One thread per NETWORK pixel (planes * n images), as u8_to_nchw_kernel: the pixel's levels through ImageSrc, one coalesced dword store per plane.
-template <int C, int BITS>
-__global__ __launch_bounds__(256) void image_to_nchw_kernel(ImageSrc<C, BITS> src, float* __restrict__ dst, long total, long plane) {
+// frames -> fp32 [.,3,H,W].  One thread per NETWORK pixel (an image batch: planes * n images): the pixel's levels through Src (an
+// ImageSrc, or YuvSrc<10>: three 16-bit loads and the integer conversion), / top, one coalesced dword store per plane.
+template <typename Src>
+__global__ __launch_bounds__(256) void to_nchw_kernel(Src src, float* __restrict__ dst, long total, long plane) {
     const long p = (long)blockIdx.x * 256 + threadIdx.x;
     if (p >= total) return;
     const long b = p / plane, r = p - b * plane;
     unsigned rgb[3];
     src(p, rgb);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + r] = ImageSrc<C, BITS>::unit(rgb[c]);
+    for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + r] = Src::unit(rgb[c]);
 }
 
 // The image b, first row Y0 and first column X0 of the thread that owns 2 rows x COLS columns of n images of rows x cols pixels
@@ -368,7 +299,7 @@ __device__ __forceinline__ void store_yuv_block(typename Depth<BITS>::word* img,
     }
 }
 
-// compact_tail_u8_kernel with YUV at both ends, of BITS = yuv_bits(LAYOUT) = 8 (bytes; RESR_YUV_I420 / RESR_YUV_NV12) or 10 bits per
+// compact_tail_image_kernel's job with YUV at both ends, of BITS = yuv_bits(LAYOUT) = 8 (bytes; RESR_YUV_I420 / RESR_YUV_NV12) or 10 bits per
 // sample (16-bit words; RESR_YUV_I420P10 / RESR_YUV_P010).  A thread owns 2 rows x 8 columns of the output, i.e. four whole chroma
 // samples; adjacent lanes are adjacent in x.  Per pixel: the residual level is recomputed from the YUV input (no RGB frame exists
 // here), v = t + unit(rgb_in), quantise(v) unchanged (255 or 1023 levels), then the integer RGB -> YUV formula; the sums of the 2x2
@@ -482,18 +413,6 @@ __global__ __launch_bounds__(256) void compact_tail_yuv_kernel(const float* __re
                 }
             }
     }
-}
-
-// 10-bit YUV [N,3H/2,W] -> fp32 [N,3,H,W], one thread per pixel as u8_to_nchw_kernel: three 16-bit loads, the integer conversion,
-// / 1023.0f, one coalesced dword store per plane.
-__global__ __launch_bounds__(256) void yuv420p10_to_nchw_kernel(YuvSrc<10> src, float* __restrict__ dst, long total, long plane) {
-    const long p = (long)blockIdx.x * 256 + threadIdx.x;
-    if (p >= total) return;
-    const long b = p / plane, r = p - b * plane;
-    unsigned rgb[3];
-    src(p, rgb);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) dst[(b * 3 + c) * plane + r] = YuvSrc<10>::unit(rgb[c]);
 }
 
 // fp32 [N,3,H,W] (H, W even) -> 10-bit YUV [N,3H/2,W]: a thread owns 2 rows x 4 columns (two chroma samples), quantises its 8 pixels
@@ -638,12 +557,6 @@ int yuv_frame_check(const char* who, const void* src, const void* dst, int n, in
     return yuv_desc_check(who, h, w, q, bits);
 }
 
-template <int S, bool RES>
-void launch_tail(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, hipStream_t st) {
-    const long groups = ((long)n * h * S * w * S + 3) / 4;
-    hipLaunchKernelGGL((compact_tail_u8_kernel<S, RES>), dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, st, t, x, y, n, h, w);
-}
-
 // ---- image modes ----
 
 long image_group_of(const ResrImageDesc* m) { return image_group(m->channels, m->bits); }
@@ -689,15 +602,15 @@ void launch_tail_image(const float* t, const void* x, void* y, int n, int h, int
 }  // namespace
 
 // lo_off: the hi -> lo element offset of x_in (RESR_F16X2), as compact_forward passes it to nchw_to_nhwc_dispatch.
-// q: the frames are YUV 4:2:0 [n,3h/2,w], of bytes or (a 10-bit layout) of 16-bit words; null: RGB bytes [n,h,w,3].
-// img: the frames are images [n / planes,h,w,C] of that mode (q null; image_forward_check has passed): the second half of an RGBA
-// batch's n network images are the alpha planes.  8-bit RGB images are the RGB bytes above.
+// q: the frames are YUV 4:2:0 [n,3h/2,w], of bytes or (a 10-bit layout) of 16-bit words.
+// img (q null): the frames are images [n / planes,h,w,C] of that mode (image_forward_check has passed): the second half of an RGBA
+// batch's n network images are the alpha planes.  Both null: uint8 RGB frames, the (3, 8) image mode.
 int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q,
                         const ResrImageDesc* img) {
-    if (img && image_is_rgb8(img)) img = nullptr;
+    if (!img && !q) img = &kRgb8;
     const int bits = q ? yuv_bits(q->layout) : 0;
     const bool ten = bits == 10;
-    const char* who = img ? "image_head" : ten ? "yuv10_head" : q ? "yuv_head" : "u8_head";
+    const char* who = ten ? "yuv10_head" : q ? "yuv_head" : image_id(img, 0, 1) ? "image_head" : "u8_head";
     if (!src || !dst || n <= 0 || h <= 0 || w <= 0 || (q && ((h & 1) || (w & 1) || !bits || img))) return fail(RESR_ERR_ARG, "%s: bad argument", who);
     const long px = (long)n * h * w;
     const int pieces = dtype != RESR_F32 ? 4 : 8;
@@ -711,53 +624,19 @@ int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dty
             hipLaunchKernelGGL((frame_head_kernel<float, decltype(from)>), grid, dim3(256), 0, st, from, (float*)dst, px, 0L);
     };
     prof_before(st);
-    if (img) {
+    if (ten) launch(YuvSrc<10>{(const uint16_t*)src, h, w, *q});
+    else if (q) launch(YuvSrc<8>{(const uint8_t*)src, h, w, *q});
+    else {
         const long colour = img->channels == 4 ? px / 2 : px;
         const bool ok = with_image_mode(*img, [&](auto C, auto B) {
             launch(ImageSrc<decltype(C)::value, decltype(B)::value>{(const typename Depth<decltype(B)::value>::word*)src, colour});
         });
         if (!ok) return fail(RESR_ERR_ARG, "%s: bad argument", who);
     }
-    else if (ten) launch(YuvSrc<10>{(const uint16_t*)src, h, w, *q});
-    else if (q) launch(YuvSrc<8>{(const uint8_t*)src, h, w, *q});
-    else launch(RgbSrc{(const uint8_t*)src});
     // an image pixel is read once per network pixel: an RGBA pixel twice, as colour and as alpha
-    const double src_bytes = img ? img->channels * img->bits / 8.0 : q ? ten ? 3.0 : 1.5 : 3.0;
-    prof_after(st, img ? 31023 : ten ? 31022 : q ? 31021 : 31020, 0.0, (double)px * (src_bytes + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
+    const double src_bytes = img ? img->channels * img->bits / 8.0 : ten ? 3.0 : 1.5;
+    prof_after(st, ten ? 31022 : q ? 31021 : image_id(img, 31020, 31023), 0.0, (double)px * (src_bytes + 32.0 * (double)(elem_size(dtype) * act_tensors(dtype))));
     RESR_CHECK_LAUNCH("frame_head_kernel");
-    return RESR_OK;
-}
-
-// y 4-byte aligned: compact_forward_ends has checked it
-int compact_tail_u8(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, hipStream_t st) {
-    prof_before(st);
-    if (!with_scale(s, [&](auto S) { launch_tail<S(), true>(t, x, y, n, h, w, st); })) return fail(RESR_ERR_ARG, "compact_tail_u8: upscale %d", s);
-    // per LR pixel: 3 s^2 floats of t, 3 bytes of x, 3 s^2 bytes out
-    prof_after(st, 31010 + s, 0.0, (double)n * h * w * (s * s * 15.0 + 3.0));
-    RESR_CHECK_LAUNCH("compact_tail_u8_kernel");
-    return RESR_OK;
-}
-
-int u8_to_nchw_dispatch(const uint8_t* src, float* dst, int n, int h, int w, hipStream_t st) {
-    if (!src || !dst || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "u8_to_nchw: bad argument (n=%d h=%d w=%d)", n, h, w);
-    const long plane = (long)h * w, total = plane * n;
-    if (!grid_ok(total)) return fail(RESR_ERR_ARG, "u8_to_nchw: %ld pixels beyond the grid", total);
-    prof_before(st);
-    hipLaunchKernelGGL(u8_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, src, dst, total, plane);
-    prof_after(st, 31030, 0.0, (double)total * 15.0);
-    RESR_CHECK_LAUNCH("u8_to_nchw_kernel");
-    return RESR_OK;
-}
-
-int nchw_to_u8_dispatch(const float* src, uint8_t* dst, int n, int h, int w, hipStream_t st) {
-    if (!src || !dst || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "nchw_to_u8: bad argument (n=%d h=%d w=%d)", n, h, w);
-    if (((size_t)dst & 3) != 0) return fail(RESR_ERR_ARG, "nchw_to_u8: the output must be 4-byte aligned");
-    const long total = (long)n * h * w;
-    if (!grid_ok((total + 3) / 4)) return fail(RESR_ERR_ARG, "nchw_to_u8: %ld pixels beyond the grid", total);
-    prof_before(st);
-    launch_tail<1, false>(src, nullptr, dst, n, h, w, st);
-    prof_after(st, 31031, 0.0, (double)total * 15.0);
-    RESR_CHECK_LAUNCH("nchw_to_u8_kernel");
     return RESR_OK;
 }
 
@@ -775,37 +654,53 @@ int image_forward_check(const char* who, int n, int h, int w, int s, const void*
     return RESR_OK;
 }
 
-// x, y, n_images and img have passed image_forward_check: compact_forward_ends has called it.  Profiling id 31100 + s (8-bit RGB: the
-// uint8 tail's own).
+// x, y, n_images and img have passed image_forward_check: compact_forward_ends has called it.  Profiling id 31100 + s (uint8 RGB: 31010 + s).
 int compact_tail_image(const float* t, const void* x, void* y, int n_images, int h, int w, int s, const ResrImageDesc* img, hipStream_t st) {
-    if (image_is_rgb8(img)) return compact_tail_u8(t, (const uint8_t*)x, (uint8_t*)y, n_images, h, w, s, st);
     prof_before(st);
     if (!with_scale(s, [&](auto S) { launch_tail_image<S(), true>(t, x, y, n_images, h, w, img, st); }))
         return fail(RESR_ERR_ARG, "compact_tail_image: upscale %d", s);
     // per LR pixel of a network image: 3 s^2 floats of t; per LR pixel of an image: its words in, s^2 times its words out
     const double pb = img->channels * img->bits / 8.0, planes = img->channels == 4 ? 2.0 : 1.0;
-    prof_after(st, 31100 + s, 0.0, (double)n_images * h * w * (s * s * (12.0 * planes + pb) + pb));
+    prof_after(st, image_id(img, 31010, 31100) + s, 0.0, (double)n_images * h * w * (s * s * (12.0 * planes + pb) + pb));
     RESR_CHECK_LAUNCH("compact_tail_image_kernel");
     return RESR_OK;
 }
+
+namespace {
+
+// The generic conversions once their entry (who) has checked its pointers, sizes and alignment: the grid, the launch, the mode's id
+int image_to_nchw_launch(const char* who, const void* src, float* dst, int n_images, int h, int w, const ResrImageDesc* img, hipStream_t st) {
+    const long plane = (long)h * w, colour = plane * n_images, total = img->channels == 4 ? 2 * colour : colour;
+    if (!grid_ok(total)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, total);
+    prof_before(st);
+    with_image_mode(*img, [&](auto C, auto B) {
+        typedef ImageSrc<decltype(C)::value, decltype(B)::value> Src;
+        hipLaunchKernelGGL(to_nchw_kernel<Src>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                           Src{(const typename Depth<decltype(B)::value>::word*)src, colour}, dst, total, plane);
+    });
+    prof_after(st, image_id(img, 31030, 31036), 0.0, (double)total * (12.0 + img->channels * img->bits / 8.0));
+    RESR_CHECK_LAUNCH("to_nchw_kernel");
+    return RESR_OK;
+}
+
+int nchw_to_image_launch(const char* who, const float* src, void* dst, int n_images, int h, int w, const ResrImageDesc* img, hipStream_t st) {
+    const long total = (long)n_images * h * w, g = image_group_of(img);
+    if (!grid_ok((total + g - 1) / g)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, total);
+    prof_before(st);
+    launch_tail_image<1, false>(src, nullptr, dst, n_images, h, w, img, st);
+    prof_after(st, image_id(img, 31031, 31037), 0.0, (double)total * ((img->channels == 4 ? 24.0 : 12.0) + img->channels * img->bits / 8.0));
+    RESR_CHECK_LAUNCH("nchw_to_image_kernel");
+    return RESR_OK;
+}
+
+}  // namespace
 
 int image_to_nchw_dispatch(const void* src, float* dst, int n_images, int h, int w, const ResrImageDesc* img, hipStream_t st) {
     const char* who = "image_to_nchw";
     if (const int rc = image_convert_check(who, src, dst, n_images, h, w, img)) return rc;
     if (const int rc = image_align_check(who, src, nullptr, img)) return rc;
     if (((size_t)dst & 3) != 0) return fail(RESR_ERR_ARG, "%s: the float tensor must be 4-byte aligned", who);
-    const long plane = (long)h * w, colour = plane * n_images, total = img->channels == 4 ? 2 * colour : colour;
-    if (!grid_ok(total)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, total);
-    if (image_is_rgb8(img)) return u8_to_nchw_dispatch((const uint8_t*)src, dst, n_images, h, w, st);
-    prof_before(st);
-    with_image_mode(*img, [&](auto C, auto B) {
-        typedef ImageSrc<decltype(C)::value, decltype(B)::value> Src;
-        hipLaunchKernelGGL((image_to_nchw_kernel<decltype(C)::value, decltype(B)::value>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                           Src{(const typename Depth<decltype(B)::value>::word*)src, colour}, dst, total, plane);
-    });
-    prof_after(st, 31036, 0.0, (double)total * (12.0 + img->channels * img->bits / 8.0));
-    RESR_CHECK_LAUNCH("image_to_nchw_kernel");
-    return RESR_OK;
+    return image_to_nchw_launch(who, src, dst, n_images, h, w, img, st);
 }
 
 int nchw_to_image_dispatch(const float* src, void* dst, int n_images, int h, int w, const ResrImageDesc* img, hipStream_t st) {
@@ -813,14 +708,19 @@ int nchw_to_image_dispatch(const float* src, void* dst, int n_images, int h, int
     if (const int rc = image_convert_check(who, src, dst, n_images, h, w, img)) return rc;
     if (const int rc = image_align_check(who, nullptr, dst, img)) return rc;
     if (((size_t)src & 3) != 0) return fail(RESR_ERR_ARG, "%s: the float tensor must be 4-byte aligned", who);
-    const long total = (long)n_images * h * w, g = image_group_of(img);
-    if (!grid_ok((total + g - 1) / g)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, total);
-    if (image_is_rgb8(img)) return nchw_to_u8_dispatch(src, (uint8_t*)dst, n_images, h, w, st);
-    prof_before(st);
-    launch_tail_image<1, false>(src, nullptr, dst, n_images, h, w, img, st);
-    prof_after(st, 31037, 0.0, (double)total * ((img->channels == 4 ? 24.0 : 12.0) + img->channels * img->bits / 8.0));
-    RESR_CHECK_LAUNCH("nchw_to_image_kernel");
-    return RESR_OK;
+    return nchw_to_image_launch(who, src, dst, n_images, h, w, img, st);
+}
+
+// The uint8-typed entries (include/resr.h: resr_u8_to_nchw, resr_nchw_to_u8): the (3, 8) image mode behind their own refusals.
+int u8_to_nchw_dispatch(const uint8_t* src, float* dst, int n, int h, int w, hipStream_t st) {
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "u8_to_nchw: bad argument (n=%d h=%d w=%d)", n, h, w);
+    return image_to_nchw_launch("u8_to_nchw", src, dst, n, h, w, &kRgb8, st);
+}
+
+int nchw_to_u8_dispatch(const float* src, uint8_t* dst, int n, int h, int w, hipStream_t st) {
+    if (!src || !dst || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "nchw_to_u8: bad argument (n=%d h=%d w=%d)", n, h, w);
+    if (((size_t)dst & 3) != 0) return fail(RESR_ERR_ARG, "nchw_to_u8: the output must be 4-byte aligned");
+    return nchw_to_image_launch("nchw_to_u8", src, dst, n, h, w, &kRgb8, st);
 }
 
 // ---- YUV 4:2:0 ----
@@ -878,9 +778,9 @@ int yuv420p10_to_nchw_dispatch(const uint16_t* src, float* dst, int n, int h, in
     const long plane = (long)h * w, total = plane * n;
     if (!grid_ok(total)) return fail(RESR_ERR_ARG, "%s: %ld pixels beyond the grid", who, total);
     prof_before(st);
-    hipLaunchKernelGGL(yuv420p10_to_nchw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, YuvSrc<10>{src, h, w, *q}, dst, total, plane);
+    hipLaunchKernelGGL(to_nchw_kernel<YuvSrc<10>>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, YuvSrc<10>{src, h, w, *q}, dst, total, plane);
     prof_after(st, 31034, 0.0, (double)total * 15.0);
-    RESR_CHECK_LAUNCH("yuv420p10_to_nchw_kernel");
+    RESR_CHECK_LAUNCH("to_nchw_kernel");
     return RESR_OK;
 }
 

@@ -91,10 +91,10 @@ int compact_act_bwd_dispatch(const void* g, const void* z, void* gz, const float
                              hipStream_t st);
 int compact_residual_bwd_dispatch(const float* gy, float* gx, int n, int h, int w, int s, hipStream_t st);
 // ---- frames.hip: the uint8 / YUV 4:2:0 ends of the compact generator.  t: the last convolution's output [n,3s^2,h,w] fp32; x: the source frames
-// (the residual); s: upscale factor; q / qs / qd: what the (source / destination) frames are, null = RGB bytes; bits: 8, 10 or 0 (Ends::bits_expected);
-// img: the frames are images of that mode (then q is null), n of the head and of image_forward_check the network's batch planes * N, n_images N ----
+// (the residual); s: upscale factor; q / qs / qd: what the (source / destination) frames are; bits: 8, 10 or 0 (Ends::bits_expected);
+// img: the frames are images of that mode (then q is null; uint8 RGB frames are kRgb8), n of the head and of image_forward_check the network's batch
+// planes * N, n_images N ----
 int frame_head_dispatch(const void* src, void* dst, int n, int h, int w, int dtype, hipStream_t st, long lo_off, const ResrYuvDesc* q, const ResrImageDesc* img);
-int compact_tail_u8(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, hipStream_t st);
 int u8_to_nchw_dispatch(const uint8_t* src, float* dst, int n, int h, int w, hipStream_t st);
 int nchw_to_u8_dispatch(const float* src, uint8_t* dst, int n, int h, int w, hipStream_t st);
 int yuv_forward_check(const char* who, int n, int h, int w, int s, const void* y, const ResrYuvDesc* src, const ResrYuvDesc* dst, int bits);
@@ -115,8 +115,6 @@ size_t resize_lds_bytes(const ResizeGeom* gp, int kind);   // the dynamic LDS of
 int compact_yuv420_scaled_fits(int h, int w, int s, int oh, int ow, int taps_y, int taps_x, int bits);
 int image_resize_dispatch(const float* x, void* y, int n, int c, int h, int w, int oh, int ow, const int32_t* idx_y, const float* w_y, int taps_y, const int32_t* idx_x, const float* w_x,
                           int taps_x, int u8, hipStream_t st);   // u8: y is uint8 HWC, else fp32 NCHW
-int compact_tail_u8_scaled(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, const int32_t* idx_y, const float* w_y, const int32_t* idx_x, const float* w_x,
-                           const ResizeGeom* gp, hipStream_t st);
 int compact_tail_yuv420_scaled(const float* t, const void* x, void* y, int n, int h, int w, int s, const int32_t* idx_y, const float* w_y, const int32_t* idx_x, const float* w_x,
                                const ResrYuvDesc* qs, const ResrYuvDesc* qd, const ResizeGeom* gp, hipStream_t st);
 // the image modes' scaled tail: x, y image batches of n_images images in mode img; image_scaled_plan: its tile without the pointer checks

@@ -17,7 +17,7 @@
 // pitch), the W pass LDS -> registers (lanes along an output row: a stride of 1/r words, 2-way conflicts at r = 0.5; the pitch is
 // odd so that the two rows a wavefront covers do not add to them) and stores.  resr_image_resize stages fp32 NCHW; the fused
 // tail of resr_compact_forward_u8_scaled forms the staged value of HR pixel (Y, X), channel c, on the fly as
-//   t[c*s*s + (Y%s)*s + X%s][Y/s][X/s] + x_u8[Y/s][X/s][c] / 255.0f        (the single fp32 add of compact_tail_u8_kernel)
+//   t[c*s*s + (Y%s)*s + X%s][Y/s][X/s] + x_u8[Y/s][X/s][c] / 255.0f        (the single fp32 add of compact_tail_image_kernel)
 // so the HR frame exists as LDS tiles only.  Both call resize_tile(): fused and generic results are the same bits.
 //
 // The host picks the largest tile of a fixed list whose tables + region + intermediate (+ the u8 row buffer) stay within 64 KB:
@@ -34,7 +34,7 @@
 // YUV input pixel (yuv.h: what compact_tail_yuv of frames.hip adds; the input frames' own depth, layout and tables, which need not
 // be the output's: resr_compact_forward_yuv420_mixed_scaled); after the W pass the three sums of a pixel are quantised to
 // levels (255 or 1023) and staged in LDS as bytes or 16-bit words; after a barrier every Y row and every chroma row of the tile is
-// written by the row writer of the u8 stage (dwords where the address is 4-byte aligned, single words at the row ends), each word
+// written by the row writer of the image stage (dwords where the address is 4-byte aligned, single words at the row ends), each word
 // formed on the fly from the staged levels: luma_of per pixel, chroma_of on the unrounded sum of a 2x2 block's four levels.  A
 // thread owns a dword of an output row, not a block: adjacent lanes read adjacent staged pixels (a stride of 3 or 6 bytes per
 // sample, odd in dwords: no bank conflict on the Y rows, 2-way on the chroma rows, whose lanes are two pixels apart) and write
@@ -51,7 +51,7 @@
 // them, RGBA the three colour levels and one alpha word.  RGBA is ONE workgroup per output tile (two would each write part of a dword):
 // it stages its tables once, runs region, H pass, W pass and quantisation for colour image b, then the same steps for alpha image N + b
 // over the same region and the same LDS, takes grey_of the alpha levels into the fourth word, and stores; grid.z is N.  After a
-// barrier a tile row leaves as tw * C contiguous words through the row writer of the u8 stage.  Tiles may be odd, as for uint8.  The
+// barrier a tile row leaves as tw * C contiguous words through store_row_slot.  uint8 RGB frames are the (3, 8) mode.  Tiles may be odd, as for uint8.  The
 // sums are resize_tile's per channel and do not depend on the tile, so the result is to_image(resr_image_resize(float path)) bit for bit.
 #include <limits.h>
 
@@ -66,9 +66,8 @@ constexpr int kResizeThreads = 256;
 constexpr size_t kResizeLdsBudget = 64 * 1024;
 constexpr int kResizeMaxTaps = 4096;
 
-// What resize_tile stores: fp32 [N,C,oh,ow], u8 [N,oh,ow,3], a YUV 4:2:0 frame [N,3oh/2,ow] of BITS-bit samples in LAYOUT ...
+// What resize_tile stores: fp32 [N,C,oh,ow], a YUV 4:2:0 frame [N,3oh/2,ow] of BITS-bit samples in LAYOUT ...
 struct OutF32 { static constexpr int kind = RESIZE_F32; };
-struct OutU8 { static constexpr int kind = RESIZE_U8; };
 template <int BITS, int LAYOUT>
 struct OutYuv {
     static constexpr int kind = BITS == 8 ? RESIZE_YUV8 : RESIZE_YUV10;
@@ -76,6 +75,7 @@ struct OutYuv {
     const ResrYuvDesc* q;
 };
 // ... or an image batch [N,oh,ow,C] of bytes or 16-bit words, n = N images: grey and alpha leave through grey_of their three levels
+// (uint8 RGB frames [N,oh,ow,3] are OutImage<3, 8>, whose kind is RESIZE_U8)
 template <int C, int BITS>
 struct OutImage {
     static constexpr int kind = resize_image_kind(C, BITS);
@@ -99,23 +99,19 @@ struct PlanarSrc {
     }
 };
 
-// the compact net's last conv t [N,3S^2,h,w] + its u8 input frame [N,h,w,3]: pixel-shuffle + residual of HR pixel (Y, X)
+// The compact net's last conv t [N,3S^2,h,w] under pixel-shuffle: HR pixel (Y, X) of network image b is LR pixel (yy, xx), and its
+// channel c the float at the returned pointer + c * S * S * h * w.  The one decode of the fused tails' sources below.
 template <int S>
-struct ShuffleSrc {
-    static constexpr bool kTriple = false;
-    const float* t;
-    const uint8_t* x;
-    int h, w;             // LR
-    __device__ __forceinline__ float load(long b, int ch, int Y, int X) const {
-        const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
-        const long plane = (long)h * w;
-        const float tv = t[(b * 3 * S * S + ch * S * S + sy * S + sx) * plane + (long)yy * w + xx];
-        return tv + unit_of<255>(x[((b * h + yy) * (long)w + xx) * 3 + ch]);
-    }
-};
+__device__ __forceinline__ const float* shuffle_decode(const float* t, int h, int w, long b, int Y, int X, int& yy, int& xx) {
+    yy = Y / S;
+    xx = X / S;
+    const int sy = Y - yy * S, sx = X - xx * S;
+    const long plane = (long)h * w;
+    return t + (b * 3 * S * S + sy * S + sx) * plane + (long)yy * w + xx;
+}
 
-// ... + its YUV 4:2:0 input frames [N,3h/2,w] of BITS-bit samples: the residual level of an LR pixel is the integer conversion of
-// its three samples, so the three channels of HR pixel (Y, X) come together (kTriple: load3 in place of load)
+// t + the residual of its YUV 4:2:0 input frames [N,3h/2,w] of BITS-bit samples: the level of an LR pixel is the integer conversion
+// of its three samples, so the three channels of HR pixel (Y, X) come together (kTriple: load3 in place of load)
 template <int S, int BITS, int LAYOUT>
 struct YuvShuffleSrc {
     static constexpr bool kTriple = true;
@@ -124,21 +120,21 @@ struct YuvShuffleSrc {
     int h, w;             // LR
     ResrYuvDesc q;
     __device__ __forceinline__ void load3(long b, int Y, int X, float (&v)[3]) const {
-        const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
+        int yy, xx;
+        const float* tp = shuffle_decode<S>(t, h, w, b, Y, X, yy, xx);
         const long plane = (long)h * w;
         int Yi, Cb, Cr;
         yuv_load<BITS>(x + b * (plane + (plane >> 1)), h, w, LAYOUT, yy, xx, Yi, Cb, Cr);
         unsigned rgb_in[3];
         yuv_to_rgb<BITS>(q, Yi, Cb, Cr, rgb_in);
-        const float* tp = t + (b * 3 * S * S + sy * S + sx) * plane + (long)yy * w + xx;
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = tp[(long)c * S * S * plane] + unit_of<kTop<BITS>>(rgb_in[c]);
     }
 };
 
-// ... + its input images [n,h,w,C] of bytes or 16-bit words (frames.hip, image modes): the residual level of network image b < n is the
-// colour of image b (the grey level three times), that of network image b >= n (RGBA only) the alpha word of image b - n three times.
-// The pixel is read with image_pixel, so an RGBA pixel stays one load.
+// t + the residual of its input images [n,h,w,C] of bytes or 16-bit words (frames.hip, image modes; uint8 RGB frames are C = 3, BITS = 8): the
+// residual level of network image b < n is the colour of image b (the grey level three times), that of network image b >= n (RGBA
+// only) the alpha word of image b - n three times.  The pixel is read with image_pixel, so an RGBA pixel stays one load.
 template <int S, int C, int BITS>
 struct ImageShuffleSrc {
     static constexpr bool kTriple = true;
@@ -147,12 +143,12 @@ struct ImageShuffleSrc {
     int h, w;             // LR
     int n;                // images: the network's batch is n (RGBA: 2 n)
     __device__ __forceinline__ void load3(long b, int Y, int X, float (&v)[3]) const {
-        const int yy = Y / S, sy = Y - yy * S, xx = X / S, sx = X - xx * S;
+        int yy, xx;
+        const float* tp = shuffle_decode<S>(t, h, w, b, Y, X, yy, xx);
         const long plane = (long)h * w;
         const bool alpha = C == 4 && b >= n;
         unsigned lv[4];
         image_pixel<C, BITS>(x, ((alpha ? b - n : b) * h + yy) * (long)w + xx, lv);
-        const float* tp = t + (b * 3 * S * S + sy * S + sx) * plane + (long)yy * w + xx;
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c] = tp[(long)c * S * S * plane] + unit_of<kTop<BITS>>(alpha ? lv[3] : C == 1 ? lv[0] : lv[c]);
     }
@@ -179,8 +175,19 @@ __device__ __forceinline__ void store_row_slot(word* __restrict__ gp, int len, i
     }
 }
 
-// The whole tile: region bounds, staging, both passes, quantisation and stores.  y: fp32 [N,C,oh,ow], u8 [N,oh,ow,3], a YUV
-// 4:2:0 frame [N,3oh/2,ow] or an image batch [N,oh,ow,C] (Out).
+// The W pass of output (c, ty, tx) of a tile, LDS -> a register: THE definition of that pass for every output stage -- acc from 0, the
+// taps in ascending order, one fmaf each, fp32.  s_mid: the H pass's result; s_ix, s_wx: the tile's region-relative column tables.
+__device__ __forceinline__ float w_pass(const float* s_mid, const int* s_ix, const float* s_wx, const ResizeGeom& g, int c, int ty, int tx) {
+    const float* row = s_mid + (c * g.th + ty) * g.pitch;
+    const int* ix = s_ix + tx * g.px;
+    const float* wx = s_wx + tx * g.px;
+    float acc = 0.f;
+    for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
+    return acc;
+}
+
+// The whole tile: region bounds, staging, both passes, quantisation and stores.  y: fp32 [N,C,oh,ow], a YUV 4:2:0 frame
+// [N,3oh/2,ow] or an image batch [N,oh,ow,C] (Out).
 template <typename Src, typename Out>
 __device__ __forceinline__ void resize_tile(const Src& src, const Out& out, void* __restrict__ y, const int32_t* __restrict__ idx_y,
                                             const float* __restrict__ w_y, const int32_t* __restrict__ idx_x,
@@ -277,16 +284,9 @@ __device__ __forceinline__ void resize_tile(const Src& src, const Out& out, void
             const int outs = th * tw;
             for (int i = tid; i < outs; i += kResizeThreads) {
                 const int ty = i / tw, tx = i - ty * tw;
-                const int* ix = s_ix + tx * g.px;
-                const float* wx = s_wx + tx * g.px;
                 unsigned o[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float* row = s_mid + (c * g.th + ty) * g.pitch;
-                    float acc = 0.f;
-                    for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
-                    o[c] = quantise<kTop<Out::bits>>(acc);
-                }
+                for (int c = 0; c < 3; ++c) o[c] = quantise<kTop<Out::bits>>(w_pass(s_mid, s_ix, s_wx, g, c, ty, tx));
                 if constexpr (C == 1) {
                     s_lv[i] = (word)grey_of(o);
                 } else if (pl) {
@@ -306,37 +306,8 @@ __device__ __forceinline__ void resize_tile(const Src& src, const Out& out, void
         for (int c = 0; c < nc; ++c)
             for (int i = tid; i < outs; i += kResizeThreads) {
                 const int ty = i / tw, tx = i - ty * tw;
-                const float* row = s_mid + (c * g.th + ty) * g.pitch;
-                const int* ix = s_ix + tx * g.px;
-                const float* wx = s_wx + tx * g.px;
-                float acc = 0.f;
-                for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
-                yf[((b * g.c + c0 + c) * g.oh + oy0 + ty) * (long)g.ow + ox0 + tx] = acc;
+                yf[((b * g.c + c0 + c) * g.oh + oy0 + ty) * (long)g.ow + ox0 + tx] = w_pass(s_mid, s_ix, s_wx, g, c, ty, tx);
             }
-    } else if constexpr (Out::kind == RESIZE_U8) {
-        const int outs = th * tw;
-        for (int i = tid; i < outs; i += kResizeThreads) {
-            const int ty = i / tw, tx = i - ty * tw;
-            const int* ix = s_ix + tx * g.px;
-            const float* wx = s_wx + tx * g.px;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float* row = s_mid + (c * g.th + ty) * g.pitch;
-                float acc = 0.f;
-                for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
-                s_out[i * 3 + c] = (uint8_t)quantise<255>(acc);
-            }
-        }
-        __syncthreads();
-        // a tile row is tw * 3 contiguous bytes of y
-        uint8_t* yb = reinterpret_cast<uint8_t*>(y);
-        const int len = tw * 3;
-        const int slots = len / 4 + 2;
-        for (int i = tid; i < th * slots; i += kResizeThreads) {
-            const int ty = i / slots, j = i - ty * slots;
-            const uint8_t* sp = s_out + ty * len;
-            store_row_slot(yb + ((b * g.oh + oy0 + ty) * (long)g.ow + ox0) * 3, len, j, [&](int k) { return sp[k]; });
-        }
     } else if constexpr (resize_is_image(Out::kind)) {
         constexpr int C = Out::channels;
         typedef typename Depth<Out::bits>::word word;
@@ -362,15 +333,8 @@ __device__ __forceinline__ void resize_tile(const Src& src, const Out& out, void
         const int outs = th * tw;
         for (int i = tid; i < outs; i += kResizeThreads) {
             const int ty = i / tw, tx = i - ty * tw;
-            const int* ix = s_ix + tx * g.px;
-            const float* wx = s_wx + tx * g.px;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float* row = s_mid + (c * g.th + ty) * g.pitch;
-                float acc = 0.f;
-                for (int k = 0; k < g.px; ++k) acc = fmaf(row[ix[k]], wx[k], acc);
-                s_lv[i * 3 + c] = (word)quantise<kTop<BITS>>(acc);
-            }
+            for (int c = 0; c < 3; ++c) s_lv[i * 3 + c] = (word)quantise<kTop<BITS>>(w_pass(s_mid, s_ix, s_wx, g, c, ty, tx));
         }
         __syncthreads();
         const long luma = (long)g.oh * g.ow;
@@ -421,15 +385,7 @@ template <bool U8>
 __global__ __launch_bounds__(kResizeThreads) void image_resize_kernel(PlanarSrc src, void* __restrict__ y, const int32_t* __restrict__ idx_y,
                                                                       const float* __restrict__ w_y, const int32_t* __restrict__ idx_x,
                                                                       const float* __restrict__ w_x, ResizeGeom g) {
-    resize_tile(src, std::conditional_t<U8, OutU8, OutF32>(), y, idx_y, w_y, idx_x, w_x, g);
-}
-
-template <int S>
-__global__ __launch_bounds__(kResizeThreads) void compact_tail_u8_scaled_kernel(ShuffleSrc<S> src, void* __restrict__ y,
-                                                                                const int32_t* __restrict__ idx_y, const float* __restrict__ w_y,
-                                                                                const int32_t* __restrict__ idx_x, const float* __restrict__ w_x,
-                                                                                ResizeGeom g) {
-    resize_tile(src, OutU8(), y, idx_y, w_y, idx_x, w_x, g);
+    resize_tile(src, std::conditional_t<U8, OutImage<3, 8>, OutF32>(), y, idx_y, w_y, idx_x, w_x, g);
 }
 
 // SRC: the layout of the input frames (the staged value is t + level / top of SRC, src.q the source's tables), LAYOUT that of the
@@ -459,8 +415,8 @@ int span_bound(int t, int in, int out, int p) {
     return (int)(s < in ? s : in);
 }
 
-// tables + region + intermediate + the staging buffer of the output stage: three bytes (RESIZE_U8, RESIZE_YUV8), three 16-bit
-// words (RESIZE_YUV10) or the C words of an image mode per pixel of the tile
+// tables + region + intermediate + the staging buffer of the output stage: three bytes (RESIZE_YUV8), three 16-bit words
+// (RESIZE_YUV10) or the C words of an image mode (RESIZE_U8: three bytes) per pixel of the tile
 size_t lds_bytes(const ResizeGeom& g, int out) {
     size_t floats = 2 * ((size_t)g.th * g.py + (size_t)g.tw * g.px) + 3 * ((size_t)g.rh + g.th) * g.pitch;
     const size_t pixel = out == RESIZE_F32 ? 0 : resize_is_image(out) ? resize_image_channels(out) * resize_image_word_bytes(out) : out == RESIZE_YUV10 ? 6 : 3;
@@ -494,12 +450,10 @@ int resize_plan(const char* who, int n, int c, int h, int w, int oh, int ow, con
     if (!idx_y || !w_y || !idx_x || !w_x) return fail(RESR_ERR_ARG, "%s: null tap table", who);
     if (taps_y < 1 || taps_y > kResizeMaxTaps || taps_x < 1 || taps_x > kResizeMaxTaps)
         return fail(RESR_ERR_ARG, "%s: taps %d, %d outside [1, %d]", who, taps_y, taps_x, kResizeMaxTaps);
-    if (u8 && c != 3) return fail(RESR_ERR_ARG, "%s: uint8 output wants 3 channels, got %d", who, c);
-    if (u8 && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the uint8 output must be 4-byte aligned", who);
     if (yuv && (c != 3 || ((oh | ow) & 1))) return fail(RESR_ERR_ARG, "%s: a 4:2:0 output wants 3 channels and an even height and width, got %d, %dx%d", who, c, oh, ow);
     if (yuv && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the YUV output must be 4-byte aligned", who);
-    if (image && c != 3) return fail(RESR_ERR_ARG, "%s: an image output wants 3 channels, got %d", who, c);
-    if (image && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the output images must be 4-byte aligned", who);
+    if (image && c != 3) return fail(RESR_ERR_ARG, "%s: %s output wants 3 channels, got %d", who, u8 ? "uint8" : "an image", c);
+    if (image && ((size_t)y & 3) != 0) return fail(RESR_ERR_ARG, "%s: the %s must be 4-byte aligned", who, u8 ? "uint8 output" : "output images");
     ResizeGeom g;
     g.c = c; g.h = h; g.w = w; g.oh = oh; g.ow = ow; g.py = taps_y; g.px = taps_x;
     g.cgroups = (c + 2) / 3;
@@ -564,24 +518,6 @@ int image_resize_dispatch(const float* x, void* y, int n, int c, int h, int w, i
     return RESR_OK;
 }
 
-// The fused tail of the scaled RGB ends of compact_forward_ends: g planned by resize_plan for c = 3, h = H * s, w = W * s, u8.
-int compact_tail_u8_scaled(const float* t, const uint8_t* x, uint8_t* y, int n, int h, int w, int s, const int32_t* idx_y,
-                           const float* w_y, const int32_t* idx_x, const float* w_x, const ResizeGeom* gp, hipStream_t st) {
-    const ResizeGeom g = *gp;
-    const dim3 grid((unsigned)((g.ow + g.tw - 1) / g.tw), (unsigned)((g.oh + g.th - 1) / g.th), (unsigned)n);
-    const size_t lds = lds_bytes(g, RESIZE_U8);
-    prof_before(st);
-    const bool ok = with_scale(s, [&](auto S) {
-        hipLaunchKernelGGL(compact_tail_u8_scaled_kernel<decltype(S)::value>, grid, dim3(kResizeThreads), lds, st,
-                           (ShuffleSrc<decltype(S)::value>{t, x, h, w}), (void*)y, idx_y, w_y, idx_x, w_x, g);
-    });
-    if (!ok) return fail(RESR_ERR_ARG, "compact_tail_u8_scaled: upscale %d", s);
-    prof_after(st, 31050 + s, 2.0 * n * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
-               (double)n * h * w * (s * s * 12.0 + 3.0) + (double)n * g.oh * g.ow * 3.0);
-    RESR_CHECK_LAUNCH("compact_tail_u8_scaled_kernel");
-    return RESR_OK;
-}
-
 // The fused tail of the scaled YUV ends of compact_forward_ends: x, y frames of bytes or 16-bit words as qs->layout and qd->layout
 // say (the caller has checked both), g planned by resize_plan for c = 3, h = H * s, w = W * s and the destination's RESIZE_YUV8 /
 // RESIZE_YUV10.  Profiling ids name the instance: 31070 + s / 31080 + s where the two layouts are one, 31095 + s for the mixed tails.
@@ -614,10 +550,9 @@ int compact_tail_yuv420_scaled(const float* t, const void* x, void* y, int n, in
 
 // The fused tail of the scaled image ends of compact_forward_ends: x, y image batches of n_images images in mode img (the caller has
 // checked it), t the planes * n_images network images, g planned by resize_plan for n_images, c = 3, h = H * s, w = W * s and
-// resize_image_kind of the mode.  Profiling id 31110 + s (8-bit RGB: the uint8 tail's own).
+// resize_image_kind of the mode.  Profiling id 31110 + s (uint8 RGB: 31050 + s).
 int compact_tail_image_scaled(const float* t, const void* x, void* y, int n_images, int h, int w, int s, const int32_t* idx_y, const float* w_y,
                               const int32_t* idx_x, const float* w_x, const ResrImageDesc* img, const ResizeGeom* gp, hipStream_t st) {
-    if (image_is_rgb8(img)) return compact_tail_u8_scaled(t, (const uint8_t*)x, (uint8_t*)y, n_images, h, w, s, idx_y, w_y, idx_x, w_x, gp, st);
     const ResizeGeom g = *gp;
     const dim3 grid((unsigned)((g.ow + g.tw - 1) / g.tw), (unsigned)((g.oh + g.th - 1) / g.th), (unsigned)n_images);
     const size_t lds = lds_bytes(g, resize_image_kind(img->channels, img->bits));
@@ -632,7 +567,7 @@ int compact_tail_image_scaled(const float* t, const void* x, void* y, int n_imag
     if (!ok) return fail(RESR_ERR_ARG, "compact_tail_image_scaled: upscale %d", s);
     // per LR pixel of a network image: 3 s^2 floats of t and the image's pixel; per output pixel its words
     const double pb = img->channels * img->bits / 8.0, planes = img->channels == 4 ? 2.0 : 1.0;
-    prof_after(st, 31110 + s, 2.0 * n_images * planes * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
+    prof_after(st, image_id(img, 31050, 31110) + s, 2.0 * n_images * planes * 3 * ((double)g.oh * g.w * g.py + (double)g.oh * g.ow * g.px),
                (double)n_images * h * w * planes * (s * s * 12.0 + pb) + (double)n_images * g.oh * g.ow * pb);
     RESR_CHECK_LAUNCH("compact_tail_image_scaled_kernel");
     return RESR_OK;

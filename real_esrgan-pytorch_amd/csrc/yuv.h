@@ -124,13 +124,11 @@ __device__ __forceinline__ void image_pixel(const typename Depth<BITS>::word* __
     }
 }
 
-// A runtime image mode as a compile-time one, as with_scale: f(channels, bits), both std::integral_constant; false for any other mode
-// and for 8-bit RGB, which has no image kernels of its own (image_is_rgb8: the callers run the uint8 path's).
+// A runtime image mode as a compile-time one, as with_scale: f(channels, bits), both std::integral_constant; false for any other mode.
 template <typename F>
 inline bool with_image_mode(const ResrImageDesc& m, F&& f) {
     auto depth = [&](auto C) {
-        if constexpr (decltype(C)::value != 3)
-            if (m.bits == 8) { f(C, std::integral_constant<int, 8>()); return true; }
+        if (m.bits == 8) { f(C, std::integral_constant<int, 8>()); return true; }
         if (m.bits == 16) { f(C, std::integral_constant<int, 16>()); return true; }
         return false;
     };
@@ -141,8 +139,5 @@ inline bool with_image_mode(const ResrImageDesc& m, F&& f) {
         default: return false;
     }
 }
-
-// 8-bit RGB is the uint8 frame path: its kernels run
-inline bool image_is_rgb8(const ResrImageDesc* m) { return m->channels == 3 && m->bits == 8; }
 
 }  // namespace resr

@@ -117,6 +117,45 @@ def test_uint8_rgb_is_forward_u8(precision):
     _same(want, float_reference(m, u8)[0])
 
 
+def test_uint8_rgb_entries_are_the_3x8_image_mode():
+    """The uint8-typed entries and the image entries at {3, 8} are one path: the same bytes and the same profiling ids, on the frames
+    of ODD_WIDTHS (every partial 4-pixel group of the tail), through the scaled pair at outscale = s / 2 (an even and an odd output
+    width) and through the generic conversions at 1x3x5."""
+    import real_esrgan_pytorch_amd as R
+    L = R._lib
+
+    def both(a, b):
+        """a() and b(): equal results (bit for bit), equal lists of profiling ids.  Returns (result, ids)."""
+        with torch.no_grad():
+            ya, yb = a(), b()
+            ia, ib = _prof_ids_once(L, a), _prof_ids_once(L, b)
+        assert ya.dtype == yb.dtype and ya.shape == yb.shape and torch.equal(ya.view(torch.uint8), yb.view(torch.uint8))
+        assert ia == ib and len(ia) > 0, (ia, ib)
+        return ya, ia
+
+    n, h = 3, 3
+    widths = set()
+    for s, w in ODD_WIDTHS:
+        m, _ = _model(2, s, "prelu", "fast", "slopes")
+        frames = torch.from_numpy(random_frames(n, h, w, seed=w * 10 + s)).cuda()
+        y, ids = both(lambda: m.forward_image(frames), lambda: m.forward_u8(frames))
+        assert y.shape == (n, h * s, w * s, 3) and (ids[0], ids[-1]) == (31020, 31010 + s), ids
+        if s == 1:         # (an HR frame of 3 rows is shorter than the symmetric copy r = 0.5 needs: the reference refuses it too)
+            continue
+        o = s / 2          # s = 3: the HR frame 9 x 9, 9 x 18, 9 x 15 -> 5 x 5, 5 x 9, 5 x 8
+        y, ids = both(lambda: m.forward_image(frames, outscale=o), lambda: m.forward_u8(frames, outscale=o))
+        assert y.shape == (n,) + tuple(R.output_size(h, w, s, o)) + (3,) and (ids[0], ids[-1]) == (31020, 31050 + s), ids
+        widths.add(y.shape[2] % 2)
+    assert widths == {0, 1}
+    # the generic conversions
+    frames = torch.from_numpy(random_frames(1, 3, 5, seed=1)).cuda()
+    x, ids = both(lambda: R.from_image(frames), lambda: R.from_u8(frames))
+    assert x.shape == (1, 3, 3, 5) and ids == [31030]
+    sr = (torch.rand(1, 3, 3, 5, generator=torch.Generator().manual_seed(3)) * 2 - 0.5).cuda()
+    y, ids = both(lambda: R.to_image(sr, 3, torch.uint8), lambda: R.to_u8(sr))
+    assert y.shape == (1, 3, 5, 3) and ids == [31031]
+
+
 # ---- 2. store groups --------------------------------------------------------------------------------------------------------------
 def _odd_cases():
     """(mode, s, w) with n = 3, h = 3: neither the output width nor the output's pixel count is a multiple of the thread's group, so
