@@ -45,6 +45,9 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // RESR_NO_PAD_SKIP in the environment (read per call; A/B arm and test control): the kernels that skip work on padding -- the few-channel
 // nchw_to_nhwc (layout.hip) and the zero border of the 21 x 21 blur taps (degrade.hip) -- give way to the paths that compute on it
 inline bool no_pad_skip() { return getenv("RESR_NO_PAD_SKIP") != nullptr; }
+// RESR_DEGRADE_PARENT_KERNELS in the environment (read per call; A/B arm and test control): USMSharp and DiffJPEG run the kernels they
+// had before usm51_stream_kernel / jpeg_run_kernel (degrade.hip) -- same bits, the older schedule
+inline bool degrade_parent_kernels() { return getenv("RESR_DEGRADE_PARENT_KERNELS") != nullptr; }
 
 // A runtime upscale factor s in {1, 2, 3, 4} as a compile-time one: f(std::integral_constant<int, s>()); false for any other s.
 template <typename F>

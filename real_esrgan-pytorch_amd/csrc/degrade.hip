@@ -7,7 +7,7 @@
 //   resize        F.interpolate area / bilinear / bicubic, align_corners=False, scale_factor= or size=
 //   noise         Gaussian (one gray field shared by the batch, imgproc.py:854) and Poisson (per-sample
 //                 unique-value count without host sync, imgproc.py:892-905) with Philox4x32-10 sampling
-//   jpeg          DiffJPEG(differentiable=False) (imgproc.py:1195-1494), one workgroup per 16x16 macroblock
+//   jpeg          DiffJPEG(differentiable=False) (imgproc.py:1195-1494), persistent workgroups over runs of four 16x16 macroblocks
 //   quantize+crop train_realesrnet.py:374-377, imgproc.py:1894-1934
 // No host synchronisation anywhere: per-sample scalars live in small device arrays.
 #include <math.h>
@@ -409,6 +409,247 @@ __global__ __launch_bounds__(256) void usm51_kernel(const TIN* __restrict__ src,
     }
 }
 
+// ---- the same two launches, scheduled for the vector unit ---------------------------------------------------------------
+// usm51_kernel above compiles to 168 / 171 VGPRs (the uint8_t instantiation then runs two waves per SIMD where LDS allows three) and
+// spills 220 SGPRs: its 51 taps, hoisted out of the chunk loop, do not fit next to the scalars of fetch() / commit(), and every tap
+// comes back through a v_readlane_b32 in front of its multiply-adds (552 of them).  Here, with the same strip walk, ring, XCD ranges and
+// launch pair:
+//   * the taps are re-read through the scalar cache at the head of each pass (tap_ptr hides the pointer from the hoisting): 51 SGPRs
+//     that live for one pass;
+//   * both passes STREAM: a thread owns 4 adjacent outputs of a row (row pass) or 2 rows x 4 adjacent columns (column pass: 16 row
+//     pairs x 16 column groups = 256 threads) and feeds each float4 it reads (ds_read_b128, conflict-free: a 16-lane group covers 16
+//     different column groups) to every accumulator chain it belongs to, at tap t = position - output.  No 54-value window in registers;
+//   * a thread fetches ONE input column (0 .. 113) of 16 rows of a chunk: its reflected column is found once, a chunk costs the
+//     (wave-uniform) row reflection and 32-bit offsets from the plane's base;
+//   * the four mask bytes of a thread's row are one word: no staging in LDS and no third barrier;  x / blur / soft / out go as
+//     float4 where the rows are 16-byte aligned (vec).
+// Every value has the chain of the kernel above, acc = fma(tap[t], v[t], acc), t = 0 .. 50 from +0, with that kernel's roundings as
+// its gfx950 code had them: all steps fused, except -- in the float instantiation's column pass -- taps 41 .. 50 of the rows
+// y = 0 (mod 4), which the compiler had packed as products (v_pk_mul_f32) and added one by one.  blur, mask, soft and out are the
+// bytes of usm51_kernel (tests/test_gpu_degrade_fast.py).
+typedef const __attribute__((address_space(4))) float* tap_ptr_t;
+__device__ __forceinline__ tap_ptr_t tap_ptr(const float* kern) {
+    uint64_t a = reinterpret_cast<uint64_t>(kern);
+    asm volatile("" : "+s"(a));   // (uniform, and opaque: the loads behind it stay in the pass that issues them)
+    return (tap_ptr_t)a;
+}
+// One fused step with the tap as the instruction's scalar operand.  Written as the instruction: left to the vectorizer, pairs of steps
+// become v_pk_fma_f32 with a PAIR of taps as the scalar operand, each tap is then kept in two pairs (even and odd alignment), and 51
+// taps no longer fit the SGPR file -- the spills this kernel is there to remove.
+__device__ __forceinline__ float fma_tap(float t, float v, float acc) {
+    asm("v_fmac_f32 %0, %1, %2" : "+v"(acc) : "s"(t), "v"(v));
+    return acc;
+}
+__device__ __forceinline__ float4 fma4(float t, float4 v, float4 a) {
+    return make_float4(fma_tap(t, v.x, a.x), fma_tap(t, v.y, a.y), fma_tap(t, v.z, a.z), fma_tap(t, v.w, a.w));
+}
+// (a chain is computed where it is written: without this the compiler sinks it into the branch that stores its result, away from the
+// reads it was scheduled against)
+__device__ __forceinline__ void pin4(float4& a) { asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w)); }
+__device__ __forceinline__ float4 mul_add4(float t, float4 v, float4 a) {
+#pragma clang fp contract(off)   // (each product is rounded on its own)
+    const float px = t * v.x, py = t * v.y, pz = t * v.z, pw = t * v.w;
+    return make_float4(a.x + px, a.y + py, a.z + pz, a.w + pw);
+}
+// out = soft * sharp + (1 - soft) * x as usm51_kernel<uint8_t, 1> computes it: two rounded products (one v_pk_mul_f32) and an add
+__device__ __forceinline__ float usm_blend(float sv, float sharp, float xv) {
+#pragma clang fp contract(off)
+    const float p0 = xv * (1.f - sv), p1 = sv * sharp;
+    return p0 + p1;
+}
+
+// (waves_per_eu: 48 KB of LDS put three workgroups on a CU, three waves on a SIMD -- the register budget the scheduler may plan with)
+template <typename TIN, int EPI>   // EPI 0: blur + byte mask (TIN = float);  EPI 1: soft mask + combine (TIN = uint8_t)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void usm51_stream_kernel(const TIN* __restrict__ src, const float* __restrict__ x, float* __restrict__ blur,
+                                                           uint8_t* __restrict__ mask, float* __restrict__ soft, float* __restrict__ out,
+                                                           const float* __restrict__ kern, int planes, int h, int w, int strips, int segs,
+                                                           float threshold, float weight, int keep_soft, int vec) {
+    constexpr int K = 51, R = 25, SW = 64, CH = 32, IW = SW + 2 * R, IWP = 128, RING = 128;   // 114-column input rows at a 512-byte pitch
+    __shared__ __attribute__((aligned(16))) float in[CH * IWP];      // 16 KB: the newest 32 input rows
+    __shared__ __attribute__((aligned(16))) float ring[RING * SW];   // 32 KB: row-passed rows, slot = (row + 32) & 127
+    const long items = (long)planes * segs * strips, per_xcd = (items + 7) / 8;
+    const long item = (long)(blockIdx.x & 7u) * per_xcd + (blockIdx.x >> 3);
+    if ((long)(blockIdx.x >> 3) >= per_xcd || item >= items) return;
+    const int plane = (int)(item / ((long)segs * strips)), rem = (int)(item - (long)plane * segs * strips);
+    const int seg = rem / strips, strip = rem - seg * strips;
+    const int tiles_y = (h + CH - 1) / CH;
+    const int t_begin = (int)((long)tiles_y * seg / segs), t_end = (int)((long)tiles_y * (seg + 1) / segs);   // this segment's output tiles
+    const int x0 = strip * SW;
+    const size_t pbase = (size_t)plane * h * w;   // uniform; offsets inside the plane are 32-bit (the dispatch checks h * w)
+    const TIN* sp = src + pbase;
+    const int tid = threadIdx.x;
+    const int cg = tid & 15, rsel = tid >> 4;     // both passes: column group of 4, row selector
+    // chunk loads: thread = (input column fc, rows fr, fr + 2, .. of the chunk); the column's reflection does not depend on the chunk
+    const int fc = tid & 127, fr = __builtin_amdgcn_readfirstlane(tid >> 7);
+    const int fix = reflect(x0 + fc - R, w);
+    // Rows / columns whose reflection still falls outside (h, w > 25: rows beyond 2 h - 2 or columns beyond 2 w - 2) only feed outputs
+    // beyond the image, which are never stored: where usm51_kernel puts a zero, the nearest element inside the plane is loaded instead
+    // -- no branch around the load and no validity mask kept until commit().
+    const int fixc = min(max(fix, 0), w - 1);
+    float pre[CH / 2];   // the next chunk's input elements of this thread (global loads in flight under the column pass of the current tile)
+    auto fetch = [&](int k) {
+        const int r0 = 32 * k - R + fr;
+#pragma unroll
+        for (int jj = 0; jj < CH / 2; ++jj) {
+            const int iy = reflect(r0 + 2 * jj, h);   // (wave-uniform)
+            pre[jj] = (float)sp[(unsigned)(min(max(iy, 0), h - 1) * w + fixc)];
+        }
+    };
+    auto commit = [&]() {
+        if (fc < IW) {
+#pragma unroll
+            for (int jj = 0; jj < CH / 2; ++jj) in[(fr + 2 * jj) * IWP + fc] = pre[jj];
+        }
+    };
+    // row pass of the 32 new rows: thread = (rows rsel and rsel + 16, 4 outputs at column 4 cg); input element e of the 56 it reads is tap
+    // e - j of output j.  (Columns 114 .. 115 of `in` are read with the last float4 and feed nothing.)
+    auto row_pass = [&](int r0) {
+        const tap_ptr_t kp = tap_ptr(kern);
+        float tp[K];
+#pragma unroll
+        for (int q = 0; q < K; ++q) tp[q] = kp[q];
+#pragma unroll 1
+        for (int rr = rsel; rr < CH; rr += 16) {
+            const float4* wp = reinterpret_cast<const float4*>(in + rr * IWP + cg * 4);
+            float acc[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int m = 0; m < 14; ++m) {
+                const float4 v = wp[m];
+                const float ve[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int t = m * 4 + e - j;
+                        if (t >= 0 && t < K) acc[j] = fma_tap(tp[t], ve[e], acc[j]);
+                    }
+            }
+            *reinterpret_cast<float4*>(ring + ((r0 + rr + 32) & (RING - 1)) * SW + cg * 4) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        }
+    };
+    // column pass of tile t: thread = (rows ly, ly + 1, 4 columns at 4 cg).  Waves 0 and 1 take the row pairs at y = 0 (mod 4), waves 2
+    // and 3 those at y = 2 (mod 4), so that the one chain with unfused steps (TAIL) is a wave-uniform choice.  Ring row q of the 52 is
+    // tap q of row ly and tap q - 1 of row ly + 1.
+    auto col_pass = [&](int t, auto tail_c) {
+        constexpr bool TAIL = decltype(tail_c)::value;
+        const int y0 = t * CH, ly = (((rsel & 7) << 1) | (rsel >> 3)) * 2;
+        const int gx = x0 + cg * 4;
+        // the epilogue's global operands first: their round trip runs under the ring reads and the multiply-adds
+        float xg[2][4], bg[2][4];
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int gy = y0 + ly + r;
+            const unsigned off = (unsigned)(gy * w + gx);
+            if (vec) {
+                float4 xv = make_float4(0.f, 0.f, 0.f, 0.f), bv = xv;
+                if (gy < h && gx < w) {
+                    xv = *reinterpret_cast<const float4*>(x + pbase + off);
+                    if (EPI == 1) bv = *reinterpret_cast<const float4*>(blur + pbase + off);
+                }
+                xg[r][0] = xv.x; xg[r][1] = xv.y; xg[r][2] = xv.z; xg[r][3] = xv.w;
+                bg[r][0] = bv.x; bg[r][1] = bv.y; bg[r][2] = bv.z; bg[r][3] = bv.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const bool ok = gy < h && gx + e < w;
+                    xg[r][e] = ok ? x[pbase + off + e] : 0.f;
+                    bg[r][e] = (EPI == 1 && ok) ? blur[pbase + off + e] : 0.f;
+                }
+            }
+        }
+        const tap_ptr_t kp = tap_ptr(kern);
+        float tp[K];
+#pragma unroll
+        for (int q = 0; q < K; ++q) tp[q] = kp[q];
+        float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
+        const int s0 = y0 + ly - R + 32;
+        // 13 groups of 4 ring rows; group g + 1 is read while group g is consumed, and the scheduler may not pull later reads forward
+        // past that (all 52 float4s at once are 208 registers: one wave per SIMD)
+        constexpr int G = 4, NG = (K + 1) / G;
+        float4 cur[G], nxt[G];
+        auto load = [&](float4 (&d)[G], int g) {
+#pragma unroll
+            for (int i = 0; i < G; ++i) d[i] = *reinterpret_cast<const float4*>(ring + ((s0 + g * G + i) & (RING - 1)) * SW + cg * 4);
+        };
+        load(cur, 0);
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            if (g + 1 < NG) load(nxt, g + 1);
+#pragma unroll
+            for (int i = 0; i < G; ++i) {
+                const int q = g * G + i;
+                if (q < K) a0 = (TAIL && q >= 41) ? mul_add4(tp[q], cur[i], a0) : fma4(tp[q], cur[i], a0);
+                if (q >= 1) a1 = fma4(tp[q - 1], cur[i], a1);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int i = 0; i < G; ++i) cur[i] = nxt[i];
+        }
+        pin4(a0);
+        pin4(a1);
+#pragma unroll
+        for (int r = 0; r < 2; ++r) {
+            const int gy = y0 + ly + r;
+            if (gy >= h || gx >= w) continue;
+            const float4 a = r == 0 ? a0 : a1;
+            const float av[4] = {a.x, a.y, a.z, a.w};
+            const size_t q = pbase + (unsigned)(gy * w + gx);
+            if constexpr (EPI == 0) {
+                uint32_t mword = 0;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) mword |= ((fabsf(xg[r][e] - av[e]) * 255.f > threshold) ? 1u : 0u) << (8 * e);
+                uint8_t* mp = mask + q;
+                if (vec) {
+                    *reinterpret_cast<float4*>(blur + q) = a;
+                    *reinterpret_cast<uint32_t*>(mp) = mword;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (gx + e < w) blur[q + e] = av[e];
+                    if (gx + 3 < w && (((size_t)mp) & 3) == 0) *reinterpret_cast<uint32_t*>(mp) = mword;
+                    else for (int e = 0; e < 4 && gx + e < w; ++e) mp[e] = (uint8_t)(mword >> (8 * e));
+                }
+            } else {
+                float ov[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float xv = xg[r][e];
+                    const float sharp = fminf(fmaxf(__builtin_fmaf(weight, xv - bg[r][e], xv), 0.f), 1.f);
+                    ov[e] = usm_blend(av[e], sharp, xv);
+                }
+                if (vec) {
+                    if (keep_soft) *reinterpret_cast<float4*>(soft + q) = a;   // only the backward pass reads it
+                    *reinterpret_cast<float4*>(out + q) = make_float4(ov[0], ov[1], ov[2], ov[3]);
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (gx + e < w) {
+                            if (keep_soft) soft[q + e] = av[e];
+                            out[q + e] = ov[e];
+                        }
+                }
+            }
+        }
+    };
+    fetch(t_begin);
+    // Output tile t (rows 32 t .. 32 t + 31) needs input rows 32 t - 25 .. 32 t + 56.  Chunk k = input rows 32 k - 25 .. 32 k + 6,
+    // so tile t is complete after chunk t + 2 (rows up to 32 t + 70), and the ring's 128 slots hold tile t's 82 rows next to the
+    // 32 rows of the chunk being written (rows 128 apart share a slot: the row a new one replaces is older than 32 t - 25).
+    for (int k = t_begin; k < t_end + 2; ++k) {
+        commit();
+        __syncthreads();   // `in` is written: the row pass may read it.  (It also ends the previous tile's column pass, whose ring rows
+                           // 32 k - 121 .. 32 k - 40 the row pass below does not overwrite anyway: it replaces rows 32 k - 153 .. 32 k - 122.)
+        row_pass(32 * k - R);
+        if (k + 1 < t_end + 2) fetch(k + 1);
+        __syncthreads();   // the chunk's ring rows are written: the column pass may read them; every row pass has read `in`: the next
+                           // commit() may overwrite it
+        const int t = k - 2;                    // the tile whose last rows have just arrived
+        if (t < t_begin) continue;              // (uniform: the segment's first two chunks only fill the ring)
+        if (EPI == 0 && fr == 0) col_pass(t, std::true_type{});
+        else col_pass(t, std::false_type{});
+    }
+}
+
 // What USMSharp accepts, forward and backward: filter2d_dispatch's rules for the 1 x ksize and the ksize x 1 pass, checked before the
 // first launch of either direction (the backward launches no filter2d_dispatch that would refuse for it).
 static int usm_check_geometry(int ksize, int n, int c, int h, int w) {
@@ -435,6 +676,16 @@ int usm_dispatch(const float* src, float* dst, float* tmp, const float* k1d, int
         while (segs < 8 && (long)n * c * strips * segs < 512 && tiles_y / (segs * 2) >= 4) segs *= 2;
         const long items = (long)n * c * strips * segs;
         const unsigned grid = (unsigned)(((items + 7) / 8) * 8);
+        if (!degrade_parent_kernels() && (long)h * w < (1L << 31)) {   // (the stream kernels address a plane with 32 bits)
+            const int vec = (w & 3) == 0 && ((reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(tmp)) & 15) == 0;
+            hipLaunchKernelGGL((usm51_stream_kernel<float, 0>), dim3(grid), dim3(256), 0, st, src, src, blur, mask, (float*)nullptr, (float*)nullptr,
+                               k1d, n * c, h, w, strips, segs, threshold, weight, 0, vec);
+            RESR_CHECK_LAUNCH("usm51_stream_kernel (blur + mask)");
+            hipLaunchKernelGGL((usm51_stream_kernel<uint8_t, 1>), dim3(grid), dim3(256), 0, st, (const uint8_t*)mask, src, blur, (uint8_t*)nullptr,
+                               soft, dst, k1d, n * c, h, w, strips, segs, threshold, weight, keep_for_backward, vec);
+            RESR_CHECK_LAUNCH("usm51_stream_kernel (soft + combine)");
+            return RESR_OK;
+        }
         hipLaunchKernelGGL((usm51_kernel<float, 0>), dim3(grid), dim3(256), 0, st, src, src, blur, mask, (float*)nullptr, (float*)nullptr, k1d,
                            n * c, h, w, strips, segs, threshold, weight, 0);
         RESR_CHECK_LAUNCH("usm51_kernel (blur + mask)");
@@ -903,6 +1154,151 @@ __global__ __launch_bounds__(256) void jpeg_kernel(const float* __restrict__ src
     }
 }
 
+// The same codec, scheduled for the vector unit.  jpeg_kernel above reads, for every multiply-add of its two dense 8 x 8 transforms, one
+// broadcast value from LDS and one basis value from the global table, fills 384 of 512 thread slots in both loops and is launched once
+// per macroblock (four barriers for 98 K multiply-adds).  Here a workgroup is persistent over RUNS of JPEG_RUN = 4 consecutive
+// macroblocks of one macroblock row of one image (the last run of a row may be short; a run never crosses images: quality is per image):
+//   * the 64 x 64 basis is staged into LDS once per workgroup, at a pitch of 65 floats: lanes walk uv, so both basis[xy][uv] (forward)
+//     and basis[uv][xy] (inverse) are conflict-free;
+//   * a wave owns one macroblock of the run and a lane one uv of its 6 blocks: a basis value read once serves 6 accumulator chains, the
+//     block values come as broadcast float4s -- 10 LDS reads per 24 multiply-adds instead of 48, and all 256 threads work;
+//   * pixels are loaded and stored by rows of the 64-pixel strip: 256 contiguous bytes per wave.
+// The sums are the dense ones, xy = 0 .. 63 in order, one fused chain from +0 per coefficient; the colour matrices, the chroma average
+// and the output expressions carry the contractions jpeg_kernel's gfx950 code has, written out (jpeg_ycc, jpeg_rgb): dst and coeffs are
+// its bytes (tests/test_gpu_degrade_fast.py).
+constexpr int JPEG_RUN = 4, JPEG_BP = 65;
+__device__ __forceinline__ void jpeg_ycc(float r, float g, float bl, float& yv, float& cb, float& cr) {
+#pragma clang fp contract(off)   // (the fusions are the ones spelled here)
+    yv = __builtin_fmaf(bl, 0.114f, __builtin_fmaf(g, 0.587f, 0.299f * r)) + 0.f;
+    cb = __builtin_fmaf(0.5f, bl, __builtin_fmaf(g, -0.331264f, -0.168736f * r)) + 128.f;
+    cr = __builtin_fmaf(bl, -0.081312f, __builtin_fmaf(0.5f, r, -0.418688f * g)) + 128.f;
+}
+__device__ __forceinline__ void jpeg_rgb(float yv, float cb, float cr, float& r, float& g, float& bl) {
+    r = __builtin_fmaf(cr, 1.402f, yv);
+    g = __builtin_fmaf(cr, -0.714136f, __builtin_fmaf(cb, -0.344136f, yv));
+    bl = __builtin_fmaf(cb, 1.772f, yv);
+}
+
+__global__ __launch_bounds__(256) void jpeg_run_kernel(const float* __restrict__ src, float* __restrict__ dst,
+                                                       const float* __restrict__ quality, float* __restrict__ coeffs, int h,
+                                                       int w, int mbx, int mby, int clamp_in, int runs_per_row, int total_runs) {
+    constexpr int RUN = JPEG_RUN, BP = JPEG_BP, SWD = 16 * RUN;   // a run is a 16-row strip of SWD pixels
+    static_assert(RUN == 4, "a wave owns one macroblock of the run");
+    __shared__ float basis[64 * BP];                                   // 16.25 KB, [xy][uv] at pitch 65
+    __shared__ float chroma[RUN][2][256];                              // Cb, Cr at full resolution
+    __shared__ __attribute__((aligned(16))) float blk[RUN * 6][64];    // level-shifted blocks
+    __shared__ __attribute__((aligned(16))) float coef[RUN * 6][64];   // dequantised coefficients * alpha
+    __shared__ float rec[RUN * 6][64];
+    const int t = threadIdx.x, uv = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
+    for (int i = t; i < 4096; i += 256) basis[(i >> 6) * BP + (i & 63)] = g_jpeg.basis[i];
+    // (the first barrier of the loop orders the staging against the transforms)
+    const size_t hw = (size_t)h * w;
+    const int nyb = mbx * 2 * mby * 2, ncb = mbx * mby;
+    for (int run = blockIdx.x; run < total_runs; run += gridDim.x) {
+        const int b = run / (mby * runs_per_row), rrem = run - b * (mby * runs_per_row);
+        const int my = rrem / runs_per_row, mx0 = (rrem - my * runs_per_row) * RUN;
+        const int nmb = min(RUN, mbx - mx0);   // macroblocks of this run
+        const float* sp = src + (size_t)b * 3 * hw;
+        // colour transform: pixel p of the strip, row-major; Y goes straight to its block, Cb / Cr wait for their neighbours
+#pragma unroll
+        for (int k = 0; k < RUN; ++k) {
+            const int p = t + 256 * k, ly = p / SWD, sx = p - ly * SWD, m = sx >> 4, lx = sx & 15;
+            const int y = my * 16 + ly, x = mx0 * 16 + sx;
+            float r = 0.f, g = 0.f, bl = 0.f;                 // zero padding up to a multiple of 16 (imgproc.py:1488)
+            if (y < h && x < w) {
+                r = sp[(size_t)y * w + x]; g = sp[hw + (size_t)y * w + x]; bl = sp[2 * hw + (size_t)y * w + x];
+                if (clamp_in) {            // torch.clamp(out, 0, 1) of train_realesrnet.py:308,357,362 folded in
+                    r = fminf(fmaxf(r, 0.f), 1.f); g = fminf(fmaxf(g, 0.f), 1.f); bl = fminf(fmaxf(bl, 0.f), 1.f);
+                }
+                r *= 255.f; g *= 255.f; bl *= 255.f;
+            }
+            float yv, cb, cr;
+            jpeg_ycc(r, g, bl, yv, cb, cr);
+            blk[m * 6 + (ly >> 3) * 2 + (lx >> 3)][(ly & 7) * 8 + (lx & 7)] = yv - 128.f;
+            chroma[m][0][ly * 16 + lx] = cb;
+            chroma[m][1][ly * 16 + lx] = cr;
+        }
+        __syncthreads();   // chroma is written.  (blk / chroma were last read two and three barriers ago.)
+        // chroma blocks = 2 x 2 average: RUN x 2 x 64 values
+#pragma unroll
+        for (int k = 0; k < RUN * 128 / 256; ++k) {
+            const int i = t + 256 * k, m = i >> 7, cidx = (i >> 6) & 1, e = i & 63, cy = e >> 3, cx = e & 7;
+            const float* pc = chroma[m][cidx];
+            const float s = ((pc[(2 * cy) * 16 + 2 * cx] + pc[(2 * cy) * 16 + 2 * cx + 1]) + pc[(2 * cy + 1) * 16 + 2 * cx]) +
+                            pc[(2 * cy + 1) * 16 + 2 * cx + 1];
+            blk[m * 6 + 4 + cidx][e] = __builtin_fmaf(s, 0.25f, -128.f);
+        }
+        __syncthreads();   // blk is complete
+        const float qv = quality[b];
+        const float factor = qv < 50.f ? (5000.f / qv) / 100.f : (200.f - qv * 2.f) / 100.f;   // imgproc.py:1134-1139
+        if (wv < nmb) {     // wave wv = macroblock mx0 + wv, lane = uv of each of its 6 blocks
+            float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int xy = 0; xy < 64; xy += 4) {
+                const float b0 = basis[xy * BP + uv], b1 = basis[(xy + 1) * BP + uv], b2 = basis[(xy + 2) * BP + uv], b3 = basis[(xy + 3) * BP + uv];
+#pragma unroll
+                for (int bi = 0; bi < 6; ++bi) {
+                    const float4 v = *reinterpret_cast<const float4*>(&blk[wv * 6 + bi][xy]);
+                    s[bi] = __builtin_fmaf(v.x, b0, s[bi]);
+                    s[bi] = __builtin_fmaf(v.y, b1, s[bi]);
+                    s[bi] = __builtin_fmaf(v.z, b2, s[bi]);
+                    s[bi] = __builtin_fmaf(v.w, b3, s[bi]);
+                }
+            }
+            const int mx = mx0 + wv;
+            const float scale = g_jpeg.scale[uv], alpha = g_jpeg.alpha[uv], ytab = g_jpeg.ytab[uv] * factor, ctab = g_jpeg.ctab[uv] * factor;
+#pragma unroll
+            for (int bi = 0; bi < 6; ++bi) {
+                const float table = bi < 4 ? ytab : ctab;
+                const float q = rintf((scale * s[bi]) / table);                                 // torch.round: half to even
+                if (coeffs) {
+                    // layout: per image [Y blocks (H/8 * W/8) | Cb blocks | Cr blocks] x 64, block order row-major
+                    size_t off;
+                    if (bi < 4) off = (size_t)((my * 2 + (bi >> 1)) * (mbx * 2) + mx * 2 + (bi & 1));
+                    else off = (size_t)nyb + (size_t)(bi - 4) * ncb + (size_t)my * mbx + mx;
+                    coeffs[((size_t)b * (nyb + 2 * ncb) + off) * 64 + uv] = q;
+                }
+                coef[wv * 6 + bi][uv] = (q * table) * alpha;
+            }
+        }
+        __syncthreads();   // coef is complete
+        if (wv < nmb) {     // here uv indexes the spatial position of the output; basis^T: [u][v][x][y]
+            float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+            for (int xy = 0; xy < 64; xy += 4) {
+                const float b0 = basis[uv * BP + xy], b1 = basis[uv * BP + xy + 1], b2 = basis[uv * BP + xy + 2], b3 = basis[uv * BP + xy + 3];
+#pragma unroll
+                for (int bi = 0; bi < 6; ++bi) {
+                    const float4 v = *reinterpret_cast<const float4*>(&coef[wv * 6 + bi][xy]);
+                    s[bi] = __builtin_fmaf(v.x, b0, s[bi]);
+                    s[bi] = __builtin_fmaf(v.y, b1, s[bi]);
+                    s[bi] = __builtin_fmaf(v.z, b2, s[bi]);
+                    s[bi] = __builtin_fmaf(v.w, b3, s[bi]);
+                }
+            }
+#pragma unroll
+            for (int bi = 0; bi < 6; ++bi) rec[wv * 6 + bi][uv] = __builtin_fmaf(s[bi], 0.25f, 128.f);
+        }
+        __syncthreads();   // rec is complete.  (The next run writes blk / chroma / coef / rec only behind barriers that follow these reads.)
+        float* dp0 = dst + (size_t)b * 3 * hw;
+#pragma unroll
+        for (int k = 0; k < RUN; ++k) {
+            const int p = t + 256 * k, ly = p / SWD, sx = p - ly * SWD, m = sx >> 4, lx = sx & 15;
+            const int y = my * 16 + ly, x = mx0 * 16 + sx;
+            if (y < h && x < w) {
+                const float Y = rec[m * 6 + (ly >> 3) * 2 + (lx >> 3)][(ly & 7) * 8 + (lx & 7)];
+                const float cb = rec[m * 6 + 4][(ly >> 1) * 8 + (lx >> 1)] - 128.f, cr = rec[m * 6 + 5][(ly >> 1) * 8 + (lx >> 1)] - 128.f;
+                float* dp = dp0 + (size_t)y * w + x;
+                float R, G, B;
+                jpeg_rgb(Y, cb, cr, R, G, B);
+                dp[0] = fminf(fmaxf(R, 0.f), 255.f) / 255.f;
+                dp[hw] = fminf(fmaxf(G, 0.f), 255.f) / 255.f;
+                dp[2 * hw] = fminf(fmaxf(B, 0.f), 255.f) / 255.f;
+            }
+        }
+    }
+}
+
 int jpeg_dispatch(const float* src, float* dst, const float* quality, float* coeffs, int n, int h, int w, int flags,
                   hipStream_t st) {
     if (!src || !dst || !quality || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "jpeg: bad argument");
@@ -917,6 +1313,16 @@ int jpeg_dispatch(const float* src, float* dst, const float* quality, float* coe
     });
     if (err != hipSuccess) return fail(RESR_ERR_LAUNCH, "jpeg: table upload failed: %s", hipGetErrorString(err));
     const int mbx = (w + 15) / 16, mby = (h + 15) / 16;
+    const int runs_per_row = (mbx + JPEG_RUN - 1) / JPEG_RUN;
+    const long total_runs = (long)n * mby * runs_per_row;
+    if (!degrade_parent_kernels() && total_runs < (1L << 31)) {
+        // persistent workgroups: three fit a CU's LDS; a few per slot even out the short runs at the right edge
+        const unsigned grid = (unsigned)(total_runs < 3072 ? total_runs : 3072);
+        hipLaunchKernelGGL(jpeg_run_kernel, dim3(grid), dim3(256), 0, st, src, dst, quality, coeffs, h, w, mbx, mby, flags & 1, runs_per_row,
+                           (int)total_runs);
+        RESR_CHECK_LAUNCH("jpeg_run_kernel");
+        return RESR_OK;
+    }
     hipLaunchKernelGGL(jpeg_kernel, dim3(mbx, mby, n), dim3(256), 0, st, src, dst, quality, coeffs, h, w, mbx, mby, flags & 1);
     RESR_CHECK_LAUNCH("jpeg_kernel");
     return RESR_OK;
