@@ -26,6 +26,35 @@ int resr_debug_occupy(int32_t workgroups, int32_t lds_bytes, int32_t micros, voi
  * grouped into 2x2 jobs of the quad kernel.  out[q*4 + p] = index of the product computed by slot p of job q (products are
  * numbered conv-major, then G tile, then X chunk), -1 = slot unused.  Returns the number of jobs (<= max_jobs) or < 0. */
 int resr_debug_wgrad_plan(const int32_t* cin, const int32_t* cout_pad, int32_t nconv, int32_t* out, int32_t max_jobs);
+/* Host logic of a whole batched weight-gradient launch (csrc/wgrad.hip, wgrad_batch), no GPU needed and no HIP call made: the library's
+ * planner runs on `nconv` (<= 16) convolutions whose operands lie at synthetic, never-dereferenced addresses, and the tables it would hand
+ * to its kernels come back as integers (tests/test_wgrad_plan.py, tests/golden/gen_wgrad_plan_golden.py).  RESR_X2_WGRAD_PRODUCTS is read
+ * per call, as by the launch.
+ * convs: RESR_DEBUG_WGRAD_CONV_FIELDS int32 per convolution --
+ *    0 cin   1 cin0 (< cin: channels [cin0, cin) come from a second X tensor)   2 cin_real   3 cout   4 cout_pad   5 has a bias
+ *    6 X chunk-planar (else interleaved)   7 G chunk-planar   8 pixel stride of X   9 ... of the second X tensor   10 ... of G  (elements)
+ *   11 buffer id of X   12 ... of the second X tensor   13 ... of G (0..63: convolutions that name one id read one tensor)
+ *   14 first 32-channel tile of G inside its buffer (0..63)
+ *   15 G has a lo tensor (0: single f16)   16 g_lo_bias_only   17 x_pair_chunks   18 x_single_g_hi   19 X and G carry q tensors
+ *   20 x_s2d_c   21 id of the `unscale` pointer (0: none)          (15..19: RESR_F16X2, the fields of csrc/wgrad.h WgradConv)
+ * dtype, n, h, w, flags (RESR_CONV_UPSAMPLE_IN or 0), splits: as wgrad_batch takes them.
+ * totals: RESR_DEBUG_WGRAD_TOTALS int32 -- 0 tap-product jobs  1 algorithmic products  2 MX jobs  3 quads of the f16 launch (0: the pair
+ *   kernel runs)  4 quads of the MX launch  5 splits_mx  6 splits_c  7 fast_addr  8 wgrad_batch_jobs  9 wgrad_batch_quads
+ *   10 wgrad_batch_partial_bytes / 4 -- the last three as the planners ask them for the same batch.
+ * jobs: RESR_DEBUG_WGRAD_JOB_FIELDS per job (room for 96) -- 0 X operand  1 G operand (each numbered in order of first appearance)
+ *   2 part (0 (x_hi, g_hi)  1 (x_hi, g_lo)  2 (x_lo, g_hi)  3 MX)  3 slab_off  4 want_bias  5 xsub  6 mx  7 xstride_b  8 gstride_b.
+ * reduce: RESR_DEBUG_WGRAD_REDUCE_FIELDS per product (room for 80) -- 0 slab_off  1 slab_b  2 slab_c (-1: none)  3 co_base  4 ci_base
+ *   5 cout  6 cin_real  7 want_bias  8 c_bias  9 index of the convolution whose dw / db it writes  10 db present.
+ * quads, quads_mx: RESR_DEBUG_WGRAD_QUAD_FIELDS per quad of the f16 / the MX launch (room for 40 each) -- 0..3 slab_off of the four
+ *   slots (-1: unused)  4 bias_mask  5 xsub  6, 7 the X operands  8, 9 the G operands (numbered as in `jobs`, -1: none).
+ * Returns RESR_OK, or the status with which wgrad_batch refuses the batch (resr_last_error has the text); the outputs are then undefined. */
+#define RESR_DEBUG_WGRAD_CONV_FIELDS 22
+#define RESR_DEBUG_WGRAD_TOTALS 11
+#define RESR_DEBUG_WGRAD_JOB_FIELDS 9
+#define RESR_DEBUG_WGRAD_REDUCE_FIELDS 11
+#define RESR_DEBUG_WGRAD_QUAD_FIELDS 10
+int resr_debug_wgrad_batch_plan(const int32_t* convs, int32_t nconv, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t flags,
+                                int32_t splits, int32_t* totals, int32_t* jobs, int32_t* reduce, int32_t* quads, int32_t* quads_mx);
 /* Measurement aid (tools/energy.py): the weight-gradient launch pair the generator's backward pass issues per RRDB -- the five
  * convolutions of `nblocks` (1..3) dense blocks, 26 products each, as ONE batched launch -- on caller-made f16 operands.
  * x_ws[b]: chunk-planar [6][n,h,w,32] (conv_k reads the first 2 + (k - 1) planes); g_ws[b]: chunk-planar [6][n,h,w,32] (planes

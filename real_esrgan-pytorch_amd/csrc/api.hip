@@ -732,6 +732,11 @@ int resr_debug_wgrad_plan(const int32_t* cin, const int32_t* cout_pad, int32_t n
     return wgrad_debug_plan(cin, cout_pad, nconv, out, max_jobs);
 }
 
+int resr_debug_wgrad_batch_plan(const int32_t* convs, int32_t nconv, int32_t dtype, int32_t n, int32_t h, int32_t w, int32_t flags, int32_t splits,
+                                int32_t* totals, int32_t* jobs, int32_t* reduce, int32_t* quads, int32_t* quads_mx) {
+    return wgrad_debug_batch_plan(convs, nconv, dtype, n, h, w, flags, splits, totals, jobs, reduce, quads, quads_mx);
+}
+
 // debug: device buffer of 32*2*64 uint64 receiving s_memrealtime stamps of the next conv launches (null = off)
 int resr_debug_conv_trace(void* dev_buf) {
     resr::conv_trace_set(dev_buf);

@@ -24,6 +24,11 @@
 // Either way the waves of a workgroup are summed through LDS at the end and one fp32 slab [9][32][32] (+32 bias
 // sums) per (product, split) is written; a second launch reduces the slabs in a fixed order (deterministic) into
 // the OIHW fp32 gradient arena.
+//
+// Host side.  A batch is planned completely before anything is launched.  walk_taps() is the one walk conv -> G tile -> X chunk ->
+// parts over a batch's tap-products (operand addresses, strides, part): the job count, the quad count, the slab size, the job and
+// reduction tables of plan_batch() and both debug plans read it.  plan_batch_quads() groups the jobs of each kind into quads
+// (plan_quads, cached per operand pattern), wgrad_batch() launches.  tests/test_wgrad_plan.py pins every table without a GPU.
 #include <stdlib.h>
 
 #include <map>
@@ -908,6 +913,17 @@ int wgrad_default_splits(int dtype, int jobs, int n, int h, int w) {
     return (int)(s < 1 ? 1 : s);
 }
 
+// 32-bit lane offsets are enough when every operand (`px` pixels at up to `smax` bytes each) stays below 2^24 pixels and 4 GB
+static bool offsets_fit_32(size_t px, size_t smax) { return px <= (1u << 24) && smax < (1u << 24) && px * smax + 64 < (1ull << 32); }
+
+// the 16 zero bytes in global memory that every weight-gradient kernel reads for a pixel outside the image
+static int zero_page(const char** zero) {
+    void* zp = nullptr;
+    if (hipGetSymbolAddress(&zp, HIP_SYMBOL(g_zero16)) != hipSuccess || !zp) return fail(RESR_ERR_LAUNCH, "wgrad: zero page");
+    *zero = (const char*)zp;
+    return RESR_OK;
+}
+
 // `nprod`: algorithmic products of the launch (= njobs, or njobs / 3 with RESR_F16X2) for the profiling record
 template <typename T, int RPW>
 static int launch_wgrad(WgradArgs& a, int njobs, int nprod, hipStream_t stream) {
@@ -926,11 +942,7 @@ static int launch_wgrad(WgradArgs& a, int njobs, int nprod, hipStream_t stream) 
         attr_done = true;
     }
     a.njobs = njobs;
-    {
-        void* zp = nullptr;
-        if (hipGetSymbolAddress(&zp, HIP_SYMBOL(g_zero16)) != hipSuccess || !zp) return fail(RESR_ERR_LAUNCH, "wgrad: zero page");
-        a.zero = (const char*)zp;
-    }
+    if (const int rc = zero_page(&a.zero)) return rc;
     const int splits8 = (a.splits + 7) / 8 * 8;
     prof_before(stream);
     hipLaunchKernelGGL((wgrad_kernel<T, RPW>), dim3(njobs * splits8), dim3(256), lds, stream, a);
@@ -1000,34 +1012,42 @@ static const std::vector<QuadIdx>* plan_quads(const int* jx, const int* jg, int 
     return &out;
 }
 
+// The distinct operand tensors of a launch in order of first appearance; first[i]: what the caller named then (build_quads: the job with its stride and tap pattern)
+struct Operands {
+    const char* p[kMaxJobs];
+    int first[kMaxJobs];
+    int n = 0;
+    int of(const char* q, int who = 0) {
+        int i = 0;
+        while (i < n && p[i] != q) ++i;
+        if (i == n) { p[n] = q; first[n] = who; ++n; }
+        return i;
+    }
+};
+
 // quads of the jobs of one kind (mx = 0: the f16 tap-products, 1: the MX jobs -- their operands are q tensors, so the two kinds never share
 // an operand, and they run as two launches of two kernel instantiations); 0 when there is no job of the kind
 static int build_quads(const WgradArgs& a, int nj_all, WgradQuadArgs& q, unsigned mx = 0) {
-    const char* xs[kMaxJobs]; const char* gs[kMaxJobs];
-    unsigned xstr[kMaxJobs], gstr[kMaxJobs], xsub[kMaxJobs];
-    int nx = 0, ng = 0, nj = 0;
+    Operands xs, gs;
+    int nj = 0;
     int jx[kMaxJobs], jg[kMaxJobs], jid[kMaxJobs];
     for (int i = 0; i < nj_all; ++i) {
         if (a.jobs[i].mx != mx) continue;
-        int xi = 0, gi = 0;
-        while (xi < nx && xs[xi] != a.jobs[i].x) ++xi;
-        if (xi == nx) { xs[nx] = a.jobs[i].x; xstr[nx] = a.jobs[i].xstride_b; xsub[nx] = a.jobs[i].xsub; ++nx; }
-        while (gi < ng && gs[gi] != a.jobs[i].g) ++gi;
-        if (gi == ng) { gs[ng] = a.jobs[i].g; gstr[ng] = a.jobs[i].gstride_b; ++ng; }
-        jx[nj] = xi; jg[nj] = gi; jid[nj] = i; ++nj;
+        jx[nj] = xs.of(a.jobs[i].x, i); jg[nj] = gs.of(a.jobs[i].g, i); jid[nj] = i; ++nj;
     }
     if (nj == 0) return 0;
-    const std::vector<QuadIdx>* plan = plan_quads(jx, jg, nj, nx, ng);
+    const std::vector<QuadIdx>* plan = plan_quads(jx, jg, nj, xs.n, gs.n);
     if (!plan) return -1;
     int nq = 0;
     for (const QuadIdx& qi : *plan) {
         WgradQuad& w = q.jobs[nq++];
         memset(&w, 0, sizeof(w));
-        w.x[0] = xs[qi.xa]; w.xstride_b[0] = xstr[qi.xa];
-        w.xsub = xsub[qi.xa] | (4u << 8);
-        if (qi.xb != qi.xa) { w.x[1] = xs[qi.xb]; w.xstride_b[1] = xstr[qi.xb]; w.xsub = xsub[qi.xa] | (xsub[qi.xb] << 8); }
-        w.g[0] = gs[qi.ga]; w.gstride_b[0] = gstr[qi.ga];
-        if (qi.gb != qi.ga) { w.g[1] = gs[qi.gb]; w.gstride_b[1] = gstr[qi.gb]; }
+        const WgradJob &xa = a.jobs[xs.first[qi.xa]], &xb = a.jobs[xs.first[qi.xb]], &ga = a.jobs[gs.first[qi.ga]], &gb = a.jobs[gs.first[qi.gb]];
+        w.x[0] = xa.x; w.xstride_b[0] = xa.xstride_b;
+        w.xsub = xa.xsub | (4u << 8);
+        if (qi.xb != qi.xa) { w.x[1] = xb.x; w.xstride_b[1] = xb.xstride_b; w.xsub = xa.xsub | (xb.xsub << 8); }
+        w.g[0] = ga.g; w.gstride_b[0] = ga.gstride_b;
+        if (qi.gb != qi.ga) { w.g[1] = gb.g; w.gstride_b[1] = gb.gstride_b; }
         for (int p = 0; p < 4; ++p) {
             w.slab_off[p] = ~0u;
             if (qi.prod[p] < 0) continue;
@@ -1040,83 +1060,45 @@ static int build_quads(const WgradArgs& a, int nj_all, WgradQuadArgs& q, unsigne
     return nq;
 }
 
+constexpr size_t kQuadLds = 2 * kQBUF;   // dynamic LDS of a quad-kernel workgroup: two stages
+// what every launch of the quad kernel sets up, table mode or layer mode: geometry and 8 x 32 tiles, the LDS attribute (once per instantiation), the zero page
 template <bool MXK>
-static int launch_wgrad_quad_kind(const WgradArgs& a, int nj, int nprod, hipStream_t stream, bool* done);
-
-static int launch_wgrad_quad(const WgradArgs& a, int nj, int nprod, hipStream_t stream, bool* done) {
-    bool any_mx = false;
-    for (int i = 0; i < nj; ++i) any_mx = any_mx || a.jobs[i].mx;
-    const int rc = launch_wgrad_quad_kind<false>(a, nj, nprod, stream, done);
-    if (rc || !*done || !any_mx) return rc;
-    *done = false;     // the MX jobs' quads: a second launch (wgrad_quad_kernel_t<true>); no pair-kernel fallback exists for them
-    return launch_wgrad_quad_kind<true>(a, nj, nprod, stream, done);
-}
-
-template <bool MXK>
-static int launch_wgrad_quad_kind(const WgradArgs& a, int nj, int nprod, hipStream_t stream, bool* done) {
-    static thread_local WgradQuadArgs q;
-    *done = false;
-    const int nq = build_quads(a, nj, q, MXK ? 1u : 0u);
-    if (nq <= 0) return RESR_OK;
-    q.partial = a.partial;
-    q.n = a.n; q.h = a.h; q.w_ = a.w_; q.hs = a.hs; q.ws = a.ws; q.up = a.up; q.splits = MXK ? a.splits_mx : a.splits; q.njobs = nq;
-    q.tiles_x = (a.w_ + 31) / 32;
-    q.tiles_y = (a.h + 7) / 8;
-    q.ntiles = q.tiles_x * q.tiles_y * a.n;
-    const size_t lds = 2 * kQBUF;
+static int quad_launch_setup(WgradQuadArgs& q, float* partial, int n, int h, int w, bool up, int splits, int njobs) {
+    q.partial = partial;
+    q.n = n; q.h = h; q.w_ = w; q.hs = up ? h / 2 : h; q.ws = up ? w / 2 : w; q.up = up ? 1 : 0; q.splits = splits; q.njobs = njobs;
+    q.tiles_x = (w + 31) / 32; q.tiles_y = (h + 7) / 8; q.ntiles = q.tiles_x * q.tiles_y * n;
     static bool attr_done = false;     // (one flag per instantiation of this function template)
     if (!attr_done) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_quad_kernel_t<MXK>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds) != hipSuccess)
-            return fail(RESR_ERR_LAUNCH, "wgrad: cannot reserve %zu B of LDS", lds);
+                                (int)kQuadLds) != hipSuccess)
+            return fail(RESR_ERR_LAUNCH, "wgrad: cannot reserve %zu B of LDS", kQuadLds);
         attr_done = true;
     }
-    void* zp = nullptr;
-    if (hipGetSymbolAddress(&zp, HIP_SYMBOL(g_zero16)) != hipSuccess || !zp) return fail(RESR_ERR_LAUNCH, "wgrad: zero page");
-    q.zero = (const char*)zp;
+    return zero_page(&q.zero);
+}
+
+// one launch of the `nq` quads of a batch's f16 jobs, or (MXK, wgrad_quad_kernel_t<true>) of its MX jobs on their own pixel splits
+template <bool MXK>
+static int launch_wgrad_quads(WgradQuadArgs& q, int nq, const WgradArgs& a, int nj, int nprod, hipStream_t stream) {
+    if (const int rc = quad_launch_setup<MXK>(q, a.partial, a.n, a.h, a.w_, a.up != 0, MXK ? a.splits_mx : a.splits, nq)) return rc;
     const int splits8 = (q.splits + 7) / 8 * 8;
     double staged = 0;
     for (int i = 0; i < nq; ++i) staged += 1 + (q.jobs[i].x[1] != nullptr) + 1 + (q.jobs[i].g[1] != nullptr);
     prof_before(stream);
-    hipLaunchKernelGGL(wgrad_quad_kernel_t<MXK>, dim3(nq * splits8), dim3(512), lds, stream, q);
+    hipLaunchKernelGGL(wgrad_quad_kernel_t<MXK>, dim3(nq * splits8), dim3(512), kQuadLds, stream, q);
     // algorithmic bytes: every quad's X chunks and G tiles once (quads that share an operand find it in their XCD's L2)
     // (the MX launch: kernel id 50600, no algorithmic FLOPs of its own -- the products are counted with the f16 launch)
     prof_after(stream, MXK ? 50600 : (nprod != nj ? 50500 : 50200), MXK ? 0.0 : 2.0 * 9 * 32 * 32 * nprod * (double)a.n * a.h * a.w_, staged * 64.0 * (double)a.n * a.h * a.w_);
     RESR_CHECK_LAUNCH("wgrad_quad_kernel");
-    *done = true;
     return RESR_OK;
 }
 
-// resr_debug_wgrad_plan (include/resr.h): the grouping above on synthetic operand addresses
-int wgrad_debug_plan(const int* cin, const int* cout_pad, int nconv, int* out, int max_jobs) {
-    if (!cin || !cout_pad || !out || nconv <= 0 || max_jobs <= 0) return fail(RESR_ERR_ARG, "wgrad plan: null argument");
-    static thread_local WgradArgs a;
-    static thread_local WgradQuadArgs q;
-    memset(&a, 0, sizeof(a));
-    const char* xbase = reinterpret_cast<const char*>(0x10000000);   // never dereferenced
-    const char* gbase = reinterpret_cast<const char*>(0x20000000);
-    int nj = 0, gt = 0;
-    for (int i = 0; i < nconv; ++i) {
-        if (cin[i] <= 0 || (cin[i] & 31) || (cout_pad[i] != 32 && cout_pad[i] != 64)) return fail(RESR_ERR_ARG, "wgrad plan: cin=%d cout_pad=%d", cin[i], cout_pad[i]);
-        for (int ct = 0; ct < cout_pad[i] / 32; ++ct, ++gt)
-            for (int ck = 0; ck < cin[i] / 32; ++ck) {
-                if (nj >= kMaxJobs) return fail(RESR_ERR_ARG, "wgrad plan: more than %d products", kMaxJobs);
-                a.jobs[nj].x = xbase + ck * 64;
-                a.jobs[nj].g = gbase + gt * 64;
-                a.jobs[nj].slab_off = (unsigned)nj;     // product index
-                a.jobs[nj].xsub = 4;
-                ++nj;
-            }
-    }
-    const int nq = build_quads(a, nj, q);
-    if (nq < 0 || nq > max_jobs) return fail(RESR_ERR_ARG, "wgrad plan: %d jobs", nq);
-    for (int i = 0; i < nq; ++i)
-        for (int p = 0; p < 4; ++p) out[i * 4 + p] = q.jobs[i].slab_off[p] == ~0u ? -1 : (int)q.jobs[i].slab_off[p];
-    return nq;
+// the quad launches of a batch (plan_batch_quads): the f16 jobs' quads, then the MX jobs' as a second launch
+static int launch_batch_quads(WgradQuadArgs q[2], const int nq[2], const WgradArgs& a, int nj, int nprod, hipStream_t stream) {
+    const int rc = launch_wgrad_quads<false>(q[0], nq[0], a, nj, nprod, stream);
+    return rc || nq[1] <= 0 ? rc : launch_wgrad_quads<true>(q[1], nq[1], a, nj, nprod, stream);
 }
 
-// One batched launch pair.  `convs` (wgrad.h) describes up to a dense block's worth of convolutions that share
-// n/h/w/flags; jobs are generated as (conv, ci chunk, co tile) -- three per product with RESR_F16X2.
 // RESR_F16X2: tap-products per algorithmic product of a weight gradient.  3 (default): dW = X_hi^T G_hi + 2^-12 (X_hi^T G_lo +
 // X_lo^T G_hi) -- fp32-class (every one of the 702 tensors of the 23-block generator within 5.8e-6 of the float64 evaluation of the
 // oracle), nothing rests on averaging.  $RESR_X2_WGRAD_PRODUCTS=1 (opt-in): the hi tensors only, dW = X_hi^T G_hi, a third of the
@@ -1133,6 +1115,7 @@ int wgrad_x2_products() {
     if (e && e[0] == '1') return 1;
     return kX2WgradProductsDefault;
 }
+static int x2_parts(int dtype) { return dtype == RESR_F16X2 ? wgrad_x2_products() : 1; }   // tap-products per product of a launch of `dtype`
 
 // The jobs (kernel launches' slab regions) of ONE algorithmic product (G tile ct, X chunk ck): part 0 (x_hi, g_hi) always; RESR_F16X2 with
 // three tap-products adds 1 = (x_hi, g_lo) and 2 = (x_lo, g_hi) as the plan bits allow -- or, where both operands carry q tensors and the
@@ -1140,7 +1123,7 @@ int wgrad_x2_products() {
 // g_lo's share of the bias (X chunk 0) from the bf8 bytes of its own G fragments.  (Until late in round 6 a tap-free f16 job (x_hi chunk 0, g_lo)
 // per G tile summed that share from the f16 lo tensor: six product slots per dense block that staged two tiles per step for 32 sums each --
 // 7.4 ms of the 262 ms exact16 step, measured by leaving them out.  The bf8 rounding of a 2^-12-weighted term is 2^-15 of the gradient.)
-// One definition for the job count, the quad count and the job table.
+// Only walk_taps() below asks: it is the one place that turns a batch into tap-products.
 static int product_parts(const WgradConv& c, int dtype, int nparts, int ck, int parts[4]) {
     int n = 0;
     parts[n++] = 0;
@@ -1160,70 +1143,98 @@ static int product_parts(const WgradConv& c, int dtype, int nparts, int ck, int 
     return n;
 }
 
-// tap-products of one convolution
-static size_t wgrad_conv_jobs(const WgradConv& c, int dtype) {
-    const int nparts = dtype == RESR_F16X2 ? wgrad_x2_products() : 1;
-    size_t jobs = 0;
-    int parts[4];
-    for (int ck = 0; ck < c.cin / 32; ++ck) jobs += (size_t)product_parts(c, dtype, nparts, ck, parts);
-    return jobs * (size_t)(c.cout_pad / 32);
-}
+struct Tap {                             // one tap-product of a batch
+    int conv, ct, ck;                    // its product: convolution, G tile, X chunk (counted over both X segments)
+    int part, pi, np;                    // product_parts: the pi-th of the product's np tap-products
+    const char* x; const char* g;        // the tensors the job reads: hi, lo or q of the X chunk and of the G tile
+    unsigned xstride_b, gstride_b;
+};
 
-// Quad jobs (workgroups per pixel split) the batched launch of `convs` will run: the planners size their pixel splits by it --
-// a dense block's 64 exact16 tap-products with single-f16 growth gradients group into 17 quads, not 64 / 4 (the plan is cached
-// per operand pattern, so this costs a map lookup after the first call).  Falls back to ceil(jobs / 4).
-int wgrad_batch_quads(const WgradConv* convs, int nconv, int dtype) {
+// THE walk over a batch: conv -> G tile -> X chunk -> parts, f(conv, tap) for every tap-product in the order of the job table; a non-zero
+// answer of f ends it and is returned.  Everything that counts, sizes, groups or tabulates a batch's jobs goes through here, so an
+// operand rule (the second X segment, chunk-planar tensors, the lo and q offsets) or a plan bit is stated once.
+template <typename F>
+static int walk_taps(const WgradConv* convs, int nconv, int dtype, F&& f) {
     const size_t es = elem_size(dtype);
-    const bool x2 = dtype == RESR_F16X2;
-    const int nparts = x2 ? wgrad_x2_products() : 1;
-    const char* xs[kMaxJobs]; const char* gs[kMaxJobs];
-    int jx[kMaxJobs], jg[kMaxJobs], nx = 0, ng = 0, nj = 0, total = 0;
+    const int nparts = x2_parts(dtype);
     for (int i = 0; i < nconv; ++i) {
         const WgradConv& c = convs[i];
         for (int ct = 0; ct < c.cout_pad / 32; ++ct)
             for (int ck = 0; ck < c.cin / 32; ++ck) {
+                const bool seg1 = c.x1 != nullptr && ck * 32 >= c.cin0;   // a chunk of the second X segment
+                const char* xh = (const char*)(seg1 ? c.x1 : c.x0) + (size_t)(seg1 ? ck - c.cin0 / 32 : ck) * (c.x_chunk_stride > 0 ? c.x_chunk_stride : 32) * es;
+                const char* gh = (const char*)c.g + (size_t)ct * (c.g_chunk_stride > 0 ? c.g_chunk_stride : 32) * es;
                 int parts[4];
                 const int np = product_parts(c, dtype, nparts, ck, parts);
                 for (int pi = 0; pi < np; ++pi) {
                     const int part = parts[pi];
-                    if (part == 3) continue;     // (the MX jobs run as their own launch with their own pixel splits: mx_split_factor)
-                    ++total;
-                    if (nj >= kMaxJobs) continue;
-                    const char* xp = (const char*)c.x0 + (size_t)ck * (c.x_chunk_stride > 0 ? c.x_chunk_stride : 32) * es + (part == 2 ? (size_t)c.x_lo_off * es : part == 3 ? (size_t)c.x_q_off * es : 0);
-                    const char* gp = (const char*)c.g + (size_t)ct * (c.g_chunk_stride > 0 ? c.g_chunk_stride : 32) * es + (part == 1 ? (size_t)c.g_lo_off * es : part == 3 ? (size_t)c.g_q_off * es : 0);
-                    int xi = 0, gi = 0;
-                    while (xi < nx && xs[xi] != xp) ++xi;
-                    if (xi == nx) xs[nx++] = xp;
-                    while (gi < ng && gs[gi] != gp) ++gi;
-                    if (gi == ng) gs[ng++] = gp;
-                    jx[nj] = xi; jg[nj] = gi; ++nj;
+                    const Tap t = {i, ct, ck, part, pi, np, xh + (part == 2 ? (size_t)c.x_lo_off * es : part == 3 ? (size_t)c.x_q_off * es : 0),
+                                   gh + (part == 1 ? (size_t)c.g_lo_off * es : part == 3 ? (size_t)c.g_q_off * es : 0),
+                                   (unsigned)((seg1 ? c.in1_stride : c.in0_stride) * es), (unsigned)(c.g_stride * es)};
+                    if (const int rc = f(c, t)) return rc;
                 }
             }
     }
+    return RESR_OK;
+}
+
+// tap-products (= slab regions, kernel jobs) of a batched launch, and how many of them are MX jobs
+struct TapCount { int jobs = 0, mx = 0; };
+static TapCount count_taps(const WgradConv* convs, int nconv, int dtype) {
+    TapCount n;
+    walk_taps(convs, nconv, dtype, [&](const WgradConv&, const Tap& t) { ++n.jobs; n.mx += t.part == 3; return 0; });
+    return n;
+}
+int wgrad_batch_jobs(const WgradConv* convs, int nconv, int dtype) { return count_taps(convs, nconv, dtype).jobs; }
+
+// Quad jobs (workgroups per pixel split) the batched launch of `convs` will run: the planners size their pixel splits by it --
+// a dense block's 64 exact16 tap-products with single-f16 growth gradients group into 17 quads, not 64 / 4 (the plan is cached
+// per operand pattern, so this costs a map lookup after the first call).  Falls back to ceil(jobs / 4).
+// (The MX jobs are not counted: they run as their own launch with their own pixel splits, mx_split_factor.)
+int wgrad_batch_quads(const WgradConv* convs, int nconv, int dtype) {
+    Operands xs, gs;
+    int jx[kMaxJobs], jg[kMaxJobs], nj = 0, total = 0;
+    walk_taps(convs, nconv, dtype, [&](const WgradConv&, const Tap& t) {
+        if (t.part == 3) return 0;
+        if (total++ < kMaxJobs) { jx[nj] = xs.of(t.x); jg[nj] = gs.of(t.g); ++nj; }
+        return 0;
+    });
     if (total > kMaxJobs || dtype == RESR_F32) return (total + 3) / 4;
-    const std::vector<QuadIdx>* plan = plan_quads(jx, jg, nj, nx, ng);
+    const std::vector<QuadIdx>* plan = plan_quads(jx, jg, nj, xs.n, gs.n);
     return plan ? (int)plan->size() : (total + 3) / 4;
 }
 
-// tap-products (= slab regions, kernel jobs) of a batched launch
-int wgrad_batch_jobs(const WgradConv* convs, int nconv, int dtype) {
-    size_t jobs = 0;
-    for (int i = 0; i < nconv; ++i) jobs += wgrad_conv_jobs(convs[i], dtype);
-    return (int)jobs;
+// resr_debug_wgrad_plan (include/resr_debug.h): the grouping of build_quads on synthetic operand addresses
+int wgrad_debug_plan(const int* cin, const int* cout_pad, int nconv, int* out, int max_jobs) {
+    if (!cin || !cout_pad || !out || nconv <= 0 || max_jobs <= 0) return fail(RESR_ERR_ARG, "wgrad plan: null argument");
+    static thread_local WgradArgs a;
+    static thread_local WgradQuadArgs q;
+    memset(&a, 0, sizeof(a));
+    int nj = 0, gt = 0;
+    for (int i = 0; i < nconv; ++i) {
+        if (cin[i] <= 0 || (cin[i] & 31) || (cout_pad[i] != 32 && cout_pad[i] != 64)) return fail(RESR_ERR_ARG, "wgrad plan: cin=%d cout_pad=%d", cin[i], cout_pad[i]);
+        WgradConv c = {};     // interleaved f16 operands (never dereferenced): one X for all, the G tiles of the convolutions back to back
+        c.x0 = reinterpret_cast<const char*>(0x10000000); c.cin = cin[i];
+        c.g = reinterpret_cast<const char*>(0x20000000) + gt * 64; c.cout_pad = cout_pad[i];
+        gt += cout_pad[i] / 32;
+        const int rc = walk_taps(&c, 1, RESR_F16, [&](const WgradConv&, const Tap& t) {
+            if (nj >= kMaxJobs) return fail(RESR_ERR_ARG, "wgrad plan: more than %d products", kMaxJobs);
+            a.jobs[nj].x = t.x; a.jobs[nj].g = t.g; a.jobs[nj].xsub = 4;
+            a.jobs[nj].slab_off = (unsigned)nj;     // product index
+            return ++nj, (int)RESR_OK;
+        });
+        if (rc) return rc;
+    }
+    const int nq = build_quads(a, nj, q);
+    if (nq < 0 || nq > max_jobs) return fail(RESR_ERR_ARG, "wgrad plan: %d jobs", nq);
+    for (int i = 0; i < nq; ++i)
+        for (int p = 0; p < 4; ++p) out[i * 4 + p] = q.jobs[i].slab_off[p] == ~0u ? -1 : (int)q.jobs[i].slab_off[p];
+    return nq;
 }
 
-// MX jobs of a batch, and the factor their launch's pixel splits take over the f16 launch's: a dense block has 12 of them = three quads,
-// and 3 x 32 workgroups would leave two thirds of the CUs idle -- k x splits with 3 quads x k x splits ~ one residency round (256)
-static int wgrad_mx_jobs(const WgradConv* convs, int nconv, int dtype) {
-    const int nparts = dtype == RESR_F16X2 ? wgrad_x2_products() : 1;
-    int n = 0, parts[4];
-    for (int i = 0; i < nconv; ++i)
-        for (int ck = 0; ck < convs[i].cin / 32; ++ck) {
-            const int np = product_parts(convs[i], dtype, nparts, ck, parts);
-            for (int pi = 0; pi < np; ++pi) n += parts[pi] == 3 ? convs[i].cout_pad / 32 : 0;
-        }
-    return n;
-}
+// The factor the pixel splits of a batch's MX launch take over the f16 launch's: a dense block has 12 MX jobs = three quads, and
+// 3 x 32 workgroups would leave two thirds of the CUs idle -- k x splits with 3 quads x k x splits ~ one residency round (256).
+// (plan_batch caps it by the geometry; wgrad_batch_partial_bytes, asked before the geometry is known, sizes for the uncapped factor)
 static int mx_split_factor(int n_mx, int splits) {
     if (n_mx <= 0) return 1;
     const int nq = (n_mx + 3) / 4, s8 = (splits + 7) / 8 * 8;
@@ -1232,12 +1243,12 @@ static int mx_split_factor(int n_mx, int splits) {
 }
 
 size_t wgrad_batch_partial_bytes(const WgradConv* convs, int nconv, int splits, int dtype) {
-    size_t jobs = 0;
-    for (int i = 0; i < nconv; ++i) jobs += wgrad_conv_jobs(convs[i], dtype);
-    const int n_mx = wgrad_mx_jobs(convs, nconv, dtype);
-    jobs += (size_t)n_mx * (mx_split_factor(n_mx, splits) - 1);
-    return wgrad_slab_bytes(jobs, splits);
+    const TapCount n = count_taps(convs, nconv, dtype);
+    return wgrad_slab_bytes((size_t)n.jobs + (size_t)n.mx * (mx_split_factor(n.mx, splits) - 1), splits);
 }
+
+// tap-products of ONE convolution whose products form the regular (X chunk, G tile) grid: layer mode, and the single-conv entry that chooses it
+static size_t layer_tap_products(int cin, int cout_pad, int nparts) { return (size_t)(cin / 32) * (cout_pad / 32) * nparts; }
 
 // One convolution with a regular grid of more products than a launch's job table holds (WgradLayer): one launch pair for the
 // whole layer.  RESR_F16 and RESR_F16X2 (nparts = 3: the (hi, lo) and (lo, hi) tap-products as two more rounds of quad jobs with
@@ -1259,31 +1270,15 @@ static int wgrad_layer_launch(const WgradConv& c, int n, int h, int w, int flags
     L.x_s2d_c = c.x_s2d_c; L.want_bias = c.db ? 1 : 0;
     L.nparts = nparts; L.ngp = (nct + 1) / 2;
     L.x_lo_b = c.x_lo_off * (long)es; L.g_lo_b = c.g_lo_off * (long)es;
-    L.part_slabs = (unsigned)((size_t)nck * nct * splits * kSlab);
+    L.part_slabs = (unsigned)(layer_tap_products(c.cin, c.cout_pad, 1) * splits * kSlab);
     const int nq = L.nxp * L.ngp * nparts;
-    {   // 32-bit lane offsets: every operand below 2^24 pixels and 4 GB
-        const size_t px = (size_t)n * h * w;
-        const size_t smax = L.xstride_b > L.gstride_b ? L.xstride_b : L.gstride_b;
-        if (!(px <= (1u << 24) && smax < (1u << 24) && px * smax + 64 < (1ull << 32))) return fail(RESR_ERR_ARG, "wgrad (layer mode): operand too large for 32-bit offsets");
-        if ((size_t)nck * nct * splits * kSlab * nparts >= (1ull << 32)) return fail(RESR_ERR_ARG, "wgrad (layer mode): slab offsets exceed 32 bits");
-    }
-    q.partial = partial;
-    q.n = n; q.h = h; q.w_ = w; q.hs = up ? h / 2 : h; q.ws = up ? w / 2 : w; q.up = up ? 1 : 0; q.splits = splits; q.njobs = nq;
-    q.tiles_x = (w + 31) / 32; q.tiles_y = (h + 7) / 8; q.ntiles = q.tiles_x * q.tiles_y * n;
-    const size_t lds = 2 * kQBUF;
-    static bool attr_done = false;
-    if (!attr_done) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_quad_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return fail(RESR_ERR_LAUNCH, "wgrad: cannot reserve %zu B of LDS", lds);
-        attr_done = true;
-    }
-    void* zp = nullptr;
-    if (hipGetSymbolAddress(&zp, HIP_SYMBOL(g_zero16)) != hipSuccess || !zp) return fail(RESR_ERR_LAUNCH, "wgrad: zero page");
-    q.zero = (const char*)zp;
+    if (!offsets_fit_32((size_t)n * h * w, L.xstride_b > L.gstride_b ? L.xstride_b : L.gstride_b)) return fail(RESR_ERR_ARG, "wgrad (layer mode): operand too large for 32-bit offsets");
+    if (layer_tap_products(c.cin, c.cout_pad, nparts) * splits * kSlab >= (1ull << 32)) return fail(RESR_ERR_ARG, "wgrad (layer mode): slab offsets exceed 32 bits");
+    if (const int rc = quad_launch_setup<false>(q, partial, n, h, w, up, splits, nq)) return rc;
     const int per_xcd = (nq * splits + 7) / 8;          // (quad job, split) pairs per XCD: eight contiguous ranges
     const double sparse = c.x_s2d_c > 0 ? 4.0 / 9.0 : 1.0;
     prof_before(stream);
-    hipLaunchKernelGGL(wgrad_quad_kernel, dim3(per_xcd * 8), dim3(512), lds, stream, q);
+    hipLaunchKernelGGL(wgrad_quad_kernel, dim3(per_xcd * 8), dim3(512), kQuadLds, stream, q);
     prof_after(stream, 50200, 2.0 * 9 * 32 * 32 * sparse * nck * nct * nparts * (double)n * h * w, (double)(nck + nct) * 64.0 * nparts * (double)n * h * w);
     RESR_CHECK_LAUNCH("wgrad_quad_kernel (layer mode)");
     ReduceJob& j = r.jobs[0];
@@ -1299,7 +1294,7 @@ static int wgrad_layer_launch(const WgradConv& c, int n, int h, int w, int flags
 
 // floats of slab scratch a layer-mode launch needs
 size_t wgrad_layer_partial_bytes(int cin, int cout_pad, int splits, int dtype) {
-    return wgrad_slab_bytes((size_t)(cin / 32) * (cout_pad / 32) * (dtype == RESR_F16X2 ? wgrad_x2_products() : 1), splits);
+    return wgrad_slab_bytes(layer_tap_products(cin, cout_pad, x2_parts(dtype)), splits);
 }
 
 // entry for the whole-network planners: one f16 convolution, cout_pad any multiple of 32, as one layer-mode launch pair
@@ -1311,32 +1306,19 @@ int wgrad_layer(const WgradConv* c, int n, int h, int w, int dtype, int flags, i
     if (c->cin <= 0 || (c->cin & 31) || c->cout_pad <= 0 || (c->cout_pad & 31) || c->cout <= 0 || c->cout > c->cout_pad || c->cin_real <= 0 || c->cin_real > c->cin)
         return fail(RESR_ERR_ARG, "wgrad_layer: cin=%d cin_real=%d cout=%d cout_pad=%d", c->cin, c->cin_real, c->cout, c->cout_pad);
     if ((flags & RESR_CONV_UPSAMPLE_IN) && ((h | w) & 1)) return fail(RESR_ERR_ARG, "wgrad_layer: upsampled input needs even h,w");
-    return wgrad_layer_launch(*c, n, h, w, flags, splits, dtype == RESR_F16X2 ? wgrad_x2_products() : 1, partial, stream);
+    return wgrad_layer_launch(*c, n, h, w, flags, splits, x2_parts(dtype), partial, stream);
 }
 
-int wgrad_batch(const WgradConv* convs, int nconv, int n, int h, int w, int dtype, int flags, int splits,
-                float* partial, hipStream_t stream) {
-    if (!convs || nconv <= 0 || !partial) return fail(RESR_ERR_ARG, "wgrad: null argument");
+// Everything wgrad_batch decides before it launches, as the tables its kernels take (no device work; `partial` is left to the launch):
+// `a`, one WgradJob per tap-product (a.njobs of them, each job's slabs behind the previous job's), and `r`, one ReduceJob per
+// algorithmic product.  Returns the number of products, or the (negative) status of a refusal.
+static int plan_batch(const WgradConv* convs, int nconv, int n, int h, int w, int dtype, int flags, int splits, WgradArgs& a, ReduceArgs& r) {
     if (splits <= 0 || splits > 65535) return fail(RESR_ERR_ARG, "wgrad: splits=%d", splits);
     const bool up = flags & RESR_CONV_UPSAMPLE_IN;
     if (up && ((h | w) & 1)) return fail(RESR_ERR_ARG, "wgrad: upsampled input needs even h,w");
-    const size_t es = elem_size(dtype);
-    WgradArgs a;
-    ReduceArgs r;
     memset(&a, 0, sizeof(a));
     memset(&r, 0, sizeof(r));
-    int nj = 0, nr = 0;
-    unsigned off = 0;
-    bool any_mx = false;
     const bool x2 = dtype == RESR_F16X2;
-    const int nparts = x2 ? wgrad_x2_products() : 1;
-    int splits_mx = splits;   // the MX launch's own pixel splits: a multiple of `splits`, at least two tiles per workgroup (the size check above assumes the uncapped factor)
-    {
-        const long tiles = (long)((w + 31) / 32) * ((h + 7) / 8) * n;
-        int k = mx_split_factor(wgrad_mx_jobs(convs, nconv, dtype), splits);
-        while (k > 1 && (long)splits * k > tiles / 2) --k;
-        splits_mx = splits * k;
-    }
     for (int i = 0; i < nconv; ++i) {
         const WgradConv& c = convs[i];
         if (!c.x0 || !c.g || !c.dw) return fail(RESR_ERR_ARG, "wgrad: null tensor");
@@ -1344,72 +1326,90 @@ int wgrad_batch(const WgradConv* convs, int nconv, int n, int h, int w, int dtyp
         if (c.cin <= 0 || (c.cin & 31) || (c.cout_pad != 32 && c.cout_pad != 64) || c.cout <= 0 || c.cout > c.cout_pad ||
             c.cin_real <= 0 || c.cin_real > c.cin)
             return fail(RESR_ERR_ARG, "wgrad: cin=%d cin_real=%d cout=%d cout_pad=%d", c.cin, c.cin_real, c.cout, c.cout_pad);
-        for (int ct = 0; ct < c.cout_pad / 32; ++ct)
-            for (int ck = 0; ck < c.cin / 32; ++ck) {
-                if (nr >= kMaxReduce) return fail(RESR_ERR_ARG, "wgrad: more than %d products in one batch", kMaxReduce);
-                const bool seg1 = c.x1 != nullptr && ck * 32 >= c.cin0;   // a chunk of the second X segment
-                const char* xh = (const char*)(seg1 ? c.x1 : c.x0) + (size_t)(seg1 ? ck - c.cin0 / 32 : ck) * (c.x_chunk_stride > 0 ? c.x_chunk_stride : 32) * es;
-                const char* gh = (const char*)c.g + (size_t)ct * (c.g_chunk_stride > 0 ? c.g_chunk_stride : 32) * es;
-                const int want_bias = (ck == 0 && c.db) ? 1 : 0;
-                ReduceJob& q = r.jobs[nr++];
-                q.dw = c.dw; q.db = c.db; q.slab_off = off; q.slab_b = q.slab_c = ~0u;
-                q.co_base = (short)(ct * 32); q.ci_base = (short)(ck * 32);
-                q.cout = c.cout; q.cin_real = c.cin_real; q.scale = c.scale; q.want_bias = (short)want_bias; q.c_bias = 0;
-                // parts: (x_hi, g_hi); RESR_F16X2 adds (x_hi, g_lo) and (x_lo, g_hi) -- or the MX job for both: product_parts
-                int parts[4];
-                const int np = product_parts(c, dtype, nparts, ck, parts);
-                if (nj + np > kMaxJobs) return fail(RESR_ERR_ARG, "wgrad: more than %d jobs in one batch", kMaxJobs);
-                for (int pi = 0; pi < np; ++pi) {
-                    const int part = parts[pi];
-                    WgradJob& j = a.jobs[nj++];
-                    j.x = xh + (part == 2 ? (size_t)c.x_lo_off * es : part == 3 ? (size_t)c.x_q_off * es : 0);
-                    j.g = gh + (part == 1 ? (size_t)c.g_lo_off * es : part == 3 ? (size_t)c.g_q_off * es : 0);
-                    j.xstride_b = (unsigned)((seg1 ? c.in1_stride : c.in0_stride) * es);
-                    j.gstride_b = (unsigned)(c.g_stride * es);
-                    j.slab_off = off;
-                    j.mx = part == 3 ? 1u : 0u;
-                    any_mx = any_mx || part == 3;
-                    j.want_bias = (part < 2 || part == 3) ? want_bias : 0;   // (an MX job sums the bf8 g_lo bytes of its G fragments)
-                    if (part == 3 && want_bias) q.c_bias = 1;
-                    // (x_hi chunk 0, g_lo) carries the bias sum AND a real term of dW: skipping its taps was measured (+1 % on the exact16 step)
-                    // and rejected -- the worst gradient tensor against the all-pairs plan rises by a fifth (32 x 64^2: 5.1e-4 -> 6.3e-4)
-                    j.xsub = (c.x_s2d_c > 0 && dtype != RESR_F32) ? (unsigned)((ck * 32) / c.x_s2d_c) : 4u;
-                    // (the reduction takes dW = A + (B + C) 2^-12 with the bias from A and B -- and from C where C is an MX job that summed g_lo: c_bias)
-                    if (part == 1) q.slab_b = off;
-                    if (part == 2 || part == 3) q.slab_c = off;
-                    off += (unsigned)((part == 3 ? splits_mx : splits) * kSlab);
-                }
-            }
     }
-    a.partial = partial; r.partial = partial; r.splits = splits;
+    const long tiles = (long)((w + 31) / 32) * ((h + 7) / 8) * n;
+    int k = mx_split_factor(count_taps(convs, nconv, dtype).mx, splits);
+    while (k > 1 && (long)splits * k > tiles / 2) --k;
+    const int splits_mx = splits * k;   // the MX launch's own pixel splits: a multiple of `splits`, at least two tiles per workgroup
+    int nj = 0, nr = 0;
+    unsigned off = 0;
+    bool any_mx = false, f16_c = false;     // f16_c: an f16 (x_lo, g_hi) job wrote some product's slab_c region
+    const int rc = walk_taps(convs, nconv, dtype, [&](const WgradConv& c, const Tap& t) {
+        const int want_bias = (t.ck == 0 && c.db) ? 1 : 0;
+        if (t.pi == 0) {     // a new algorithmic product
+            if (nr >= kMaxReduce) return fail(RESR_ERR_ARG, "wgrad: more than %d products in one batch", kMaxReduce);
+            if (nj + t.np > kMaxJobs) return fail(RESR_ERR_ARG, "wgrad: more than %d jobs in one batch", kMaxJobs);
+            ReduceJob& q = r.jobs[nr++];
+            q.dw = c.dw; q.db = c.db; q.slab_off = off; q.slab_b = q.slab_c = ~0u;
+            q.co_base = (short)(t.ct * 32); q.ci_base = (short)(t.ck * 32);
+            q.cout = c.cout; q.cin_real = c.cin_real; q.scale = c.scale; q.want_bias = (short)want_bias; q.c_bias = 0;
+        }
+        ReduceJob& q = r.jobs[nr - 1];
+        WgradJob& j = a.jobs[nj++];
+        j.x = t.x; j.g = t.g; j.xstride_b = t.xstride_b; j.gstride_b = t.gstride_b;
+        j.slab_off = off;
+        j.mx = t.part == 3 ? 1u : 0u;
+        any_mx = any_mx || t.part == 3;
+        f16_c = f16_c || t.part == 2;
+        j.want_bias = (t.part < 2 || t.part == 3) ? want_bias : 0;   // (an MX job sums the bf8 g_lo bytes of its G fragments)
+        if (t.part == 3 && want_bias) q.c_bias = 1;
+        // (x_hi chunk 0, g_lo) carries the bias sum AND a real term of dW: skipping its taps was measured (+1 % on the exact16 step)
+        // and rejected -- the worst gradient tensor against the all-pairs plan rises by a fifth (32 x 64^2: 5.1e-4 -> 6.3e-4)
+        j.xsub = (c.x_s2d_c > 0 && dtype != RESR_F32) ? (unsigned)((t.ck * 32) / c.x_s2d_c) : 4u;
+        // (the reduction takes dW = A + (B + C) 2^-12 with the bias from A and B -- and from C where C is an MX job that summed g_lo: c_bias)
+        if (t.part == 1) q.slab_b = off;
+        if (t.part == 2 || t.part == 3) q.slab_c = off;
+        off += (unsigned)((t.part == 3 ? splits_mx : splits) * kSlab);
+        return (int)RESR_OK;
+    });
+    if (rc) return rc;
+    // ReduceArgs.splits_c is ONE slab count for every slab_c region of the launch: the MX jobs' -- an f16 (x_lo, g_hi) job beside them wrote `splits` slabs
+    if (any_mx && f16_c && splits_mx != splits)
+        return fail(RESR_ERR_ARG, "wgrad: a batch whose MX jobs run on %d pixel splits cannot also hold f16 (x_lo, g_hi) jobs on splits=%d (one slab count per launch for the third slab region)", splits_mx, splits);
+    r.splits = splits;
     r.splits_c = any_mx ? splits_mx : 0;
     a.splits_mx = splits_mx;
     r.unscale = convs[0].unscale;
     for (int i = 1; i < nconv; ++i)
         if (convs[i].unscale != convs[0].unscale) return fail(RESR_ERR_ARG, "wgrad: one pre-scale per launch");
-    {   // 32-bit lane offsets are enough when every operand stays below 2^24 pixels and 4 GB
-        const size_t px = (size_t)n * h * w;
-        size_t smax = 0;
-        for (int i = 0; i < nj; ++i) smax = smax > a.jobs[i].xstride_b ? smax : a.jobs[i].xstride_b, smax = smax > a.jobs[i].gstride_b ? smax : a.jobs[i].gstride_b;
-        a.fast_addr = (px <= (1u << 24) && smax < (1u << 24) && px * smax + 64 < (1ull << 32)) ? 1 : 0;
-        static const char* env = getenv("RESR_WGRAD_GENERIC_ADDR");  // test knob: force the 64-bit addressing path
-        if (env) a.fast_addr = 0;
-    }
-    a.n = n; a.h = h; a.w_ = w; a.hs = up ? h / 2 : h; a.ws = up ? w / 2 : w; a.up = up ? 1 : 0; a.splits = splits;
-    int rc;
-    bool quad_done = false;
+    size_t smax = 0;
+    for (int i = 0; i < nj; ++i) smax = smax > a.jobs[i].xstride_b ? smax : a.jobs[i].xstride_b, smax = smax > a.jobs[i].gstride_b ? smax : a.jobs[i].gstride_b;
+    static const char* env = getenv("RESR_WGRAD_GENERIC_ADDR");  // test knob: force the 64-bit addressing path
+    a.fast_addr = offsets_fit_32((size_t)n * h * w, smax) && !env ? 1 : 0;
+    a.n = n; a.h = h; a.w_ = w; a.hs = up ? h / 2 : h; a.ws = up ? w / 2 : w; a.up = up ? 1 : 0; a.splits = splits; a.njobs = nj;
+    return nr;
+}
+
+// The kernels of a planned batch: nq[0] quads of its f16 jobs in q[0] -- 0: the pair kernel takes them (strict mode, operands beyond
+// 32-bit offsets, products that do not group, the test knob) -- and nq[1] quads of its MX jobs in q[1], which no other kernel runs
+static int plan_batch_quads(const WgradArgs& a, bool any_mx, int dtype, WgradQuadArgs q[2], int nq[2]) {
+    nq[0] = nq[1] = 0;
     static const char* pair_env = getenv("RESR_WGRAD_PAIR_KERNEL");   // test knob: keep the f16 pair kernel
     if (dtype != RESR_F32 && a.fast_addr && !pair_env) {
-        rc = launch_wgrad_quad(a, nj, nr, stream, &quad_done);
-        if (rc) return rc;
+        nq[0] = build_quads(a, a.njobs, q[0], 0u);
+        if (nq[0] < 0) nq[0] = 0;
+        if (nq[0] > 0 && any_mx) nq[1] = build_quads(a, a.njobs, q[1], 1u);
     }
-    if (quad_done) rc = RESR_OK;
-    else if (any_mx) return fail(RESR_ERR_ARG, "wgrad: MX jobs (x_q_off / g_q_off) need the quad kernel's preconditions (32-bit addressing, a quad plan of the products)");
-    else if (dtype == RESR_F16 || dtype == RESR_F16X2) rc = launch_wgrad<half_t, 2>(a, nj, nr, stream);
-    else if (dtype == RESR_F32) rc = launch_wgrad<float, 1>(a, nj, nr, stream);
+    if (any_mx && nq[1] <= 0) return fail(RESR_ERR_ARG, "wgrad: MX jobs (x_q_off / g_q_off) need the quad kernel's preconditions (32-bit addressing, a quad plan of the products)");
+    return RESR_OK;
+}
+
+int wgrad_batch(const WgradConv* convs, int nconv, int n, int h, int w, int dtype, int flags, int splits,
+                float* partial, hipStream_t stream) {
+    if (!convs || nconv <= 0 || !partial) return fail(RESR_ERR_ARG, "wgrad: null argument");
+    WgradArgs a; ReduceArgs r;
+    static thread_local WgradQuadArgs q[2];
+    int nq[2], rc;
+    const int nr = plan_batch(convs, nconv, n, h, w, dtype, flags, splits, a, r);
+    if (nr < 0) return nr;
+    if ((rc = plan_batch_quads(a, r.splits_c != 0, dtype, q, nq))) return rc;     // (every refusal comes before the first launch)
+    a.partial = partial; r.partial = partial;
+    if (nq[0] > 0) rc = launch_batch_quads(q, nq, a, a.njobs, nr, stream);
+    else if (dtype == RESR_F16 || dtype == RESR_F16X2) rc = launch_wgrad<half_t, 2>(a, a.njobs, nr, stream);
+    else if (dtype == RESR_F32) rc = launch_wgrad<float, 1>(a, a.njobs, nr, stream);
     else return fail(RESR_ERR_ARG, "wgrad: dtype=%d", dtype);
     if (rc) return rc;
-    if (splits <= 8 && !x2) hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3(nr, (kSlab + 255) / 256), dim3(256), 0, stream, r);
+    if (splits <= 8 && dtype != RESR_F16X2) hipLaunchKernelGGL(wgrad_reduce_wide_kernel, dim3(nr, (kSlab + 255) / 256), dim3(256), 0, stream, r);
     else hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(nr, (kSlab + 31) / 32), dim3(256), 0, stream, r);
     RESR_CHECK_LAUNCH("wgrad_reduce_kernel");
     return RESR_OK;
@@ -1443,7 +1443,7 @@ int wgrad_debug_dense_blocks(int nblocks, const void* const* x, const void* cons
 
 // single-conv C-ABI entry (include/resr.h resr_conv3x3_wgrad)
 size_t wgrad_partial_bytes(const ResrWgradDesc* d) {
-    return wgrad_slab_bytes((size_t)(d->cin / 32) * (d->cout_pad / 32) * (d->dtype == RESR_F16X2 ? wgrad_x2_products() : 1), d->splits);
+    return wgrad_slab_bytes(layer_tap_products(d->cin, d->cout_pad, x2_parts(d->dtype)), d->splits);
 }
 
 int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw,
@@ -1477,13 +1477,95 @@ int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const
     c.dw = dw; c.db = db; c.scale = d->scale;
     if (two_seg) { c.x1 = x1; c.cin0 = d->cin0; c.in1_stride = d->in1_stride; }
     // more products than one launch's job table holds (or an output wider than 64 channels): the layer mode (f16, exact16)
-    const int tap_products = (c.cin / 32) * (c.cout_pad / 32) * (d->dtype == RESR_F16X2 ? wgrad_x2_products() : 1);
     if ((d->dtype == RESR_F16 || d->dtype == RESR_F16X2) &&
-        (c.cout_pad > 64 || (c.cin / 32) * (c.cout_pad / 32) > kMaxReduce || tap_products > kMaxJobs)) {
+        (c.cout_pad > 64 || layer_tap_products(c.cin, c.cout_pad, 1) > kMaxReduce || layer_tap_products(c.cin, c.cout_pad, x2_parts(d->dtype)) > kMaxJobs)) {
         if (two_seg) return fail(RESR_ERR_ARG, "wgrad: a two-segment X needs a job-table launch (cout_pad <= 64, at most %d tap-products)", kMaxJobs);
         return wgrad_layer(&c, d->n, d->h, d->w, d->dtype, flags, d->splits, partial, stream);
     }
     return wgrad_batch(&c, 1, d->n, d->h, d->w, d->dtype, flags, d->splits, partial, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// resr_debug_wgrad_batch_plan (include/resr_debug.h): the tables of one batched launch as integers, host only
+// ---------------------------------------------------------------------------------------------------------
+int wgrad_debug_batch_plan(const int* cv, int nconv, int dtype, int n, int h, int w, int flags, int splits, int* totals, int* jobs,
+                           int* reduce, int* quads, int* quads_mx) {
+    if (!cv || !totals || !jobs || !reduce || !quads || !quads_mx) return fail(RESR_ERR_ARG, "wgrad batch plan: null argument");
+    if (nconv <= 0 || nconv > 16 || n <= 0 || h <= 0 || w <= 0) return fail(RESR_ERR_ARG, "wgrad batch plan: nconv=%d (1..16) n=%d h=%d w=%d", nconv, n, h, w);
+    const bool x2 = dtype == RESR_F16X2, up = flags & RESR_CONV_UPSAMPLE_IN;
+    const long px_g = (long)n * h * w, px_x = up ? px_g / 4 : px_g;
+    const uintptr_t kX = (uintptr_t)1 << 44, kG = (uintptr_t)1 << 45, kBuf = (uintptr_t)1 << 38;   // never dereferenced
+    const size_t es = elem_size(dtype);
+    WgradConv wc[16];
+    for (int i = 0; i < nconv; ++i) {
+        const int* f = cv + i * RESR_DEBUG_WGRAD_CONV_FIELDS;
+        for (int k = 11; k <= 14; ++k)
+            if (f[k] < 0 || f[k] >= 64) return fail(RESR_ERR_ARG, "wgrad batch plan: conv %d: buffer id / G tile %d outside 0..63", i, f[k]);
+        if (f[0] > 256 || f[4] > 256) return fail(RESR_ERR_ARG, "wgrad batch plan: conv %d: more than 256 channels", i);
+        WgradConv& c = wc[i];
+        c.x0 = reinterpret_cast<const void*>(kX + f[11] * kBuf); c.cin = f[0]; c.in0_stride = f[8]; c.cin_real = f[2];
+        if (f[1] < f[0]) { c.x1 = reinterpret_cast<const void*>(kX + f[12] * kBuf); c.cin0 = f[1]; c.in1_stride = f[9]; }
+        c.cout = f[3]; c.cout_pad = f[4]; c.g_stride = f[10];
+        c.x_chunk_stride = f[6] ? px_x * 32 : 0;
+        c.g_chunk_stride = f[7] ? px_g * 32 : 0;
+        c.g = reinterpret_cast<const void*>(kG + f[13] * kBuf + (size_t)f[14] * (f[7] ? px_g * 32 : 32) * es);
+        // hi -> lo -> q: 8 planes each (chunk-planar) or one whole tensor each (interleaved), as the networks lay their pairs out
+        const long x_lo = f[6] ? 8 * px_x * 32 : px_x * f[8], g_lo = f[7] ? 8 * px_g * 32 : px_g * f[10];
+        c.x_lo_off = x2 ? x_lo : 0;
+        c.g_lo_off = x2 && f[15] ? g_lo : 0;
+        c.g_lo_bias_only = f[16]; c.x_pair_chunks = f[17]; c.x_single_g_hi = f[18];
+        if (f[19]) { c.x_q_off = 2 * x_lo; c.g_q_off = 2 * g_lo; }
+        c.x_s2d_c = f[20];
+        c.dw = reinterpret_cast<float*>((uintptr_t)0x30000000 + (uintptr_t)i * 0x10000);
+        c.db = f[5] ? c.dw + 0x2000 : nullptr;
+        c.scale = 1.f;
+        c.unscale = f[21] ? reinterpret_cast<const unsigned*>((uintptr_t)0x40000000 + (uintptr_t)f[21] * 64) : nullptr;
+    }
+    static thread_local WgradArgs a;
+    static thread_local ReduceArgs r;
+    static thread_local WgradQuadArgs q[2];
+    int nq[2];
+    const int nr = plan_batch(wc, nconv, n, h, w, dtype, flags, splits, a, r);
+    if (nr < 0) return nr;
+    if (const int rc = plan_batch_quads(a, r.splits_c != 0, dtype, q, nq)) return rc;
+    const int nj = a.njobs;
+    const size_t partial_bytes = wgrad_batch_partial_bytes(wc, nconv, splits, dtype);
+    if (partial_bytes / 4 > 0x7fffffffu) return fail(RESR_ERR_ARG, "wgrad batch plan: more than 2^31 floats of slabs");
+    int n_mx = 0;
+    Operands xs, gs;   // numbered in order of first appearance: the output does not depend on the synthetic addresses
+    auto off32 = [](unsigned v) { return v == ~0u ? -1 : (int)v; };
+    for (int i = 0, k = 0; i < nj; ++i) {
+        const WgradJob& j = a.jobs[i];
+        while (k + 1 < nr && j.slab_off >= r.jobs[k + 1].slab_off) ++k;     // the product whose slabs this job writes
+        const ReduceJob& p = r.jobs[k];
+        int* o = jobs + i * RESR_DEBUG_WGRAD_JOB_FIELDS;
+        o[0] = xs.of(j.x); o[1] = gs.of(j.g);
+        o[2] = j.mx ? 3 : j.slab_off == p.slab_c ? 2 : j.slab_off == p.slab_b ? 1 : 0;
+        o[3] = (int)j.slab_off; o[4] = (int)j.want_bias; o[5] = (int)j.xsub; o[6] = (int)j.mx;
+        o[7] = (int)j.xstride_b; o[8] = (int)j.gstride_b;
+        n_mx += j.mx ? 1 : 0;
+    }
+    for (int i = 0; i < nr; ++i) {
+        const ReduceJob& p = r.jobs[i];
+        int* o = reduce + i * RESR_DEBUG_WGRAD_REDUCE_FIELDS;
+        o[0] = (int)p.slab_off; o[1] = off32(p.slab_b); o[2] = off32(p.slab_c); o[3] = p.co_base; o[4] = p.ci_base;
+        o[5] = p.cout; o[6] = p.cin_real; o[7] = p.want_bias; o[8] = p.c_bias;
+        o[9] = (int)(((uintptr_t)p.dw - (uintptr_t)0x30000000) / 0x10000);     // the convolution whose gradient it writes
+        o[10] = p.db ? 1 : 0;
+    }
+    for (int kind = 0; kind < 2; ++kind)
+        for (int i = 0; i < nq[kind]; ++i) {
+            const WgradQuad& u = q[kind].jobs[i];
+            int* o = (kind ? quads_mx : quads) + i * RESR_DEBUG_WGRAD_QUAD_FIELDS;
+            for (int s = 0; s < 4; ++s) o[s] = off32(u.slab_off[s]);
+            o[4] = (int)u.bias_mask; o[5] = (int)u.xsub;
+            o[6] = xs.of(u.x[0]); o[7] = u.x[1] ? xs.of(u.x[1]) : -1; o[8] = gs.of(u.g[0]); o[9] = u.g[1] ? gs.of(u.g[1]) : -1;
+        }
+    totals[0] = nj; totals[1] = nr; totals[2] = n_mx; totals[3] = nq[0]; totals[4] = nq[1];
+    totals[5] = a.splits_mx; totals[6] = r.splits_c; totals[7] = a.fast_addr;
+    totals[8] = wgrad_batch_jobs(wc, nconv, dtype); totals[9] = wgrad_batch_quads(wc, nconv, dtype);
+    totals[10] = (int)(partial_bytes / 4);
+    return RESR_OK;
 }
 
 }  // namespace resr
