@@ -62,6 +62,15 @@ int resr_debug_wgrad_batch_plan(const int32_t* convs, int32_t nconv, int32_t dty
  * partial: `partial_bytes` of slab scratch (26 * nblocks * splits slabs of kSlab floats: csrc/wgrad.h, wgrad_slab_bytes). */
 int resr_debug_wgrad_dense_blocks(int32_t nblocks, const void* const* x_ws, const void* const* g_ws, int32_t n, int32_t h, int32_t w,
                                   int32_t splits, float* partial, size_t partial_bytes, float* dw, void* stream);
+/* Test entry (tests/test_gpu_sparse_taps.py) of the sparse-tap weight gradient, which the product reaches only from inside the native
+ * discriminator passes (csrc/disc_native.hip, the 4x4 / stride-2 layers): resr_conv3x3_wgrad, every argument as there, on an X that is
+ * the 2x2 space-to-depth image of x_s2d_c channels per sub-position (sub-position-major: channel sub * x_s2d_c + c).  x_s2d_c: a
+ * positive multiple of 32 with d->cin == 4 * x_s2d_c, else RESR_ERR_ARG.  RESR_F16 / RESR_F16X2: an X chunk of sub-position (i, j)
+ * contributes only the taps dy in {1,2} (i = 0) / {0,1} (i = 1), dx likewise by j -- the 16 of 36 (tap, sub-position) blocks where
+ * the virtual kernel of csrc/pack.hip is non-zero; dw [cout, cin, 3, 3] holds zeros in the other 20 (the quad kernel; where the pair
+ * kernel takes a launch -- RESR_WGRAD_PAIR_KERNEL, operands beyond 32-bit offsets -- it computes all taps).  RESR_F32: all taps. */
+int resr_debug_conv3x3_wgrad_s2d(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw,
+                                 float* db, int32_t x_s2d_c, void* stream);
 /* test probe: lane/element map of ds_read_b64_tr_b16 (256 floats out) */
 int resr_debug_tr_probe(float* out256, void* stream);
 

@@ -127,6 +127,13 @@ int resr_conv3x3_wgrad(const ResrWgradDesc* d, const void* x0, const void* x1, c
     return wgrad_dispatch(d, x0, x1, g, partial, dw, db, (hipStream_t)stream);
 }
 
+// test entry of the sparse-tap weight gradient (tests/test_gpu_sparse_taps.py): resr_conv3x3_wgrad on a space-to-depth X
+int resr_debug_conv3x3_wgrad_s2d(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial,
+                                 float* dw, float* db, int32_t x_s2d_c, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return wgrad_debug_s2d(d, x0, x1, g, partial, dw, db, x_s2d_c, (hipStream_t)stream);
+}
+
 int resr_pack_weights(const ResrPackChunk* chunks_dev, int32_t n_chunks, const float* arena, void* packed,
                       int32_t dtype, void* stream) {
     RESR_DEVICE_SCOPE(stream);

@@ -38,6 +38,7 @@ int wgrad_layer(const WgradConv* c, int n, int h, int w, int dtype, int flags, i
 int wgrad_batch(const WgradConv* convs, int nconv, int n, int h, int w, int dtype, int flags, int splits, float* partial, hipStream_t stream);
 size_t wgrad_partial_bytes(const ResrWgradDesc* d);
 int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw, float* db, hipStream_t stream);
+int wgrad_debug_s2d(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw, float* db, int x_s2d_c, hipStream_t stream);
 int wgrad_debug_plan(const int* cin, const int* cout_pad, int nconv, int* out, int max_jobs);
 int wgrad_debug_batch_plan(const int* convs, int nconv, int dtype, int n, int h, int w, int flags, int splits, int* totals, int* jobs, int* reduce, int* quads, int* quads_mx);
 int wgrad_debug_dense_blocks(int nblocks, const void* const* x, const void* const* g, int n, int h, int w, int splits, float* partial, size_t partial_bytes, float* dw, hipStream_t stream);

@@ -1446,8 +1446,9 @@ size_t wgrad_partial_bytes(const ResrWgradDesc* d) {
     return wgrad_slab_bytes(layer_tap_products(d->cin, d->cout_pad, x2_parts(d->dtype)), d->splits);
 }
 
-int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw,
-                   float* db, hipStream_t stream) {
+// x_s2d_c: WgradConv::x_s2d_c -- 0 from the C ABI; the test entry below names it
+static int wgrad_dispatch_s2d(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw,
+                              float* db, int x_s2d_c, hipStream_t stream) {
     if (!d || !x0 || !g || !partial || !dw) return fail(RESR_ERR_ARG, "wgrad: null argument");
     const bool two_seg = d->cin0 < d->cin;
     if (d->cin0 <= 0 || (d->cin0 & 31) || d->cin0 > d->cin || (two_seg && (!x1 || d->in1_stride <= 0)) || (!two_seg && x1))
@@ -1473,7 +1474,7 @@ int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const
     c.x0 = x0; c.cin = d->cin; c.in0_stride = d->in0_stride; c.cin_real = d->cin_real;
     c.g = g; c.cout = d->cout; c.cout_pad = d->cout_pad; c.g_stride = d->g_stride;
     c.x_chunk_stride = (long)d->x_chunk_stride; c.g_chunk_stride = (long)d->g_chunk_stride;
-    c.x_lo_off = (long)d->x_lo_offset; c.g_lo_off = g_lo; c.x_s2d_c = 0; c.g_lo_bias_only = 0;
+    c.x_lo_off = (long)d->x_lo_offset; c.g_lo_off = g_lo; c.x_s2d_c = x_s2d_c; c.g_lo_bias_only = 0;
     c.dw = dw; c.db = db; c.scale = d->scale;
     if (two_seg) { c.x1 = x1; c.cin0 = d->cin0; c.in1_stride = d->in1_stride; }
     // more products than one launch's job table holds (or an output wider than 64 channels): the layer mode (f16, exact16)
@@ -1483,6 +1484,21 @@ int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const
         return wgrad_layer(&c, d->n, d->h, d->w, d->dtype, flags, d->splits, partial, stream);
     }
     return wgrad_batch(&c, 1, d->n, d->h, d->w, d->dtype, flags, d->splits, partial, stream);
+}
+
+int wgrad_dispatch(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw,
+                   float* db, hipStream_t stream) {
+    return wgrad_dispatch_s2d(d, x0, x1, g, partial, dw, db, 0, stream);
+}
+
+// resr_debug_conv3x3_wgrad_s2d (include/resr_debug.h): the single-conv entry on a space-to-depth X, the sparse-tap path the
+// discriminator's 4x4 / stride-2 layers take (disc_native.hip) -- the job-table launch and the layer mode alike
+int wgrad_debug_s2d(const ResrWgradDesc* d, const void* x0, const void* x1, const void* g, float* partial, float* dw, float* db,
+                    int x_s2d_c, hipStream_t stream) {
+    if (!d) return fail(RESR_ERR_ARG, "wgrad: null argument");
+    if (x_s2d_c <= 0 || (x_s2d_c & 31) || d->cin != 4 * x_s2d_c)
+        return fail(RESR_ERR_ARG, "wgrad: x_s2d_c=%d: a positive multiple of 32 with cin = 4 * x_s2d_c (cin=%d)", x_s2d_c, d->cin);
+    return wgrad_dispatch_s2d(d, x0, x1, g, partial, dw, db, x_s2d_c, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """Plain references of resr_conv3x3 and resr_conv3x3_wgrad (csrc/conv3x3.hip, conv3x3_ws.h, wgrad.hip), CPU only, and the rule that
-judges a kernel against them.
+judges a kernel against them.  Also of the 4x4 / stride-2 convolution whose forward, backward-data and weight-gradient passes the library
+runs as sparse-tap 3x3 passes over the space-to-depth image (correlate4x4s2 and below; tests/test_gpu_sparse_taps.py).
 
 Every function restates the operation from its DEFINITION in include/resr.h on NCHW tensors -- a sum over the nine taps of a
 zero-padded image, then the epilogue steps in the documented order -- and shares no index arithmetic with the kernels.  Each
@@ -139,6 +140,103 @@ def wgrad(x, g, scale, dtype=torch.float64, up=False):
             dw[:, :, dy, dx] = torch.einsum("nohw,nchw->oc", g, xp[:, :, dy:dy + h, dx:dx + w])
     sc = f32scalar(scale, dtype)
     return dw * sc, g.sum(dim=(0, 2, 3)) * sc
+
+
+# ---- the 4x4 / stride-2 / padding-1 convolution of the discriminator's DOWN layers (csrc/conv3x3_ws.h SP, csrc/wgrad.hip xsub) --------
+# Stated on the ORIGINAL image [N,C,2h,2w] with the [cout,C,4,4] weight: out[Y,X] reads in[2Y + ky - 1, 2X + kx - 1].  Nothing here knows
+# the space-to-depth image or the virtual 3x3 kernel the library computes through; s2d / d2s below only carry tensors between the views.
+def _taps4(xp, h, w, ky, kx):
+    """The h x w pixels in[2Y + ky - 1, 2X + kx - 1] of the image padded by one."""
+    return xp[:, :, ky:ky + 2 * h:2, kx:kx + 2 * w:2]
+
+
+def correlate4x4s2(x, w4, dtype=torch.float64):
+    """acc[n,o,Y,X] = sum_{c,ky,kx} W[o,c,ky,kx] * in[n,c,2Y+ky-1,2X+kx-1], zero outside the image; x [N,C,2h,2w] -> [N,cout,h,w].
+    float32: one accumulator per output, the 16 * C products one after the other (see correlate)."""
+    x, w4 = x.to(dtype), w4.to(dtype)
+    n, c, hh, ww = x.shape
+    h, w = hh // 2, ww // 2
+    xp = _padded(x)
+    acc = torch.zeros(n, w4.shape[0], h, w, dtype=dtype)
+    if dtype == torch.float32:
+        for ci in range(c):
+            for ky in range(4):
+                for kx in range(4):
+                    acc.addcmul_(_taps4(xp[:, ci:ci + 1], h, w, ky, kx), w4[:, ci, ky, kx].view(1, -1, 1, 1))
+        return acc
+    for ky in range(4):
+        for kx in range(4):
+            acc += torch.einsum("oc,nchw->nohw", w4[:, :, ky, kx], _taps4(xp, h, w, ky, kx))
+    return acc
+
+
+def conv4x4s2(x, w4, dtype=torch.float64, **epi):
+    """conv2d(x, w4, stride 2, padding 1), then the epilogue of include/resr.h."""
+    return epilogue(correlate4x4s2(x, w4, dtype), dtype, **epi)
+
+
+def dgrad4x4s2(g, w4, dtype=torch.float64):
+    """The adjoint, conv_transpose2d(g, w4, stride 2, padding 1): gin[n,c,2Y+ky-1,2X+kx-1] += g[n,o,Y,X] * W[o,c,ky,kx];
+    g [N,cout,h,w] -> [N,C,2h,2w].  float32: one accumulator per output, its 4 * cout products one after the other."""
+    g, w4 = g.to(dtype), w4.to(dtype)
+    n, co, h, w = g.shape
+    ginp = torch.zeros(n, w4.shape[1], 2 * h + 2, 2 * w + 2, dtype=dtype)
+    for ky in range(4):
+        for kx in range(4):
+            dst = _taps4(ginp, h, w, ky, kx)
+            if dtype == torch.float32:
+                for o in range(co):
+                    dst.addcmul_(g[:, o:o + 1], w4[o, :, ky, kx].view(1, -1, 1, 1))
+            else:
+                dst += torch.einsum("oc,nohw->nchw", w4[:, :, ky, kx], g)
+    return ginp[:, :, 1:2 * h + 1, 1:2 * w + 1].contiguous()
+
+
+def wgrad4x4s2(x, g, scale, dtype=torch.float64):
+    """dW4[o,c,ky,kx] = scale * sum_{n,Y,X} G[n,o,Y,X] * in[n,c,2Y+ky-1,2X+kx-1]; x [N,C,2h,2w], g [N,cout,h,w]."""
+    x, g = x.to(dtype), g.to(dtype)
+    h, w = g.shape[2:]
+    xp = _padded(x)
+    dw = torch.zeros(g.shape[1], x.shape[1], 4, 4, dtype=dtype)
+    for ky in range(4):
+        for kx in range(4):
+            dw[:, :, ky, kx] = torch.einsum("nohw,nchw->oc", g, _taps4(xp, h, w, ky, kx))
+    return dw * f32scalar(scale, dtype)
+
+
+def s2d(x):
+    """[N,C,2h,2w] -> [N,4C,h,w] in the library's channel order (include/resr.h, resr_space_to_depth): sub-position-major,
+    channel (i*2 + j) * C + c of pixel (Y, X) = x[c, 2Y+i, 2X+j]."""
+    return torch.cat([x[:, :, i::2, j::2] for i in range(2) for j in range(2)], dim=1)
+
+
+def d2s(p):
+    """The inverse: [N,4C,h,w] -> [N,C,2h,2w]."""
+    n, c4, h, w = p.shape
+    c = c4 // 4
+    x = torch.zeros(n, c, 2 * h, 2 * w, dtype=p.dtype)
+    for i in range(2):
+        for j in range(2):
+            x[:, :, i::2, j::2] = p[:, (i * 2 + j) * c:(i * 2 + j + 1) * c]
+    return x
+
+
+def live_taps(sub, transposed=False):
+    """The (ty, tx) taps of the virtual 3x3 kernel that are non-zero for sub-position sub = i*2 + j, from the definition: tap ty of
+    sub-row i carries ky = 2 ty + i - 1 when that lies in 0..3.  transposed: the backward-data form (taps flipped, t -> 2 - t)."""
+    def axis(i):
+        ts = [t for t in range(3) if 0 <= 2 * t + i - 1 < 4]
+        return [2 - t for t in ts] if transposed else ts
+    return [(ty, tx) for ty in axis(sub >> 1) for tx in axis(sub & 1)]
+
+
+def live_mask(c):
+    """bool [4c,3,3]: True at the 16 live (tap, sub-position) blocks of a [cout,4c,3,3] virtual weight (gradient)."""
+    m = torch.zeros(4 * c, 3, 3, dtype=torch.bool)
+    for sub in range(4):
+        for ty, tx in live_taps(sub):
+            m[sub * c:(sub + 1) * c, ty, tx] = True
+    return m
 
 
 # ---- the rule (stated in the module docstring of tests/test_gpu_kernels.py) ------------------------------------------------------

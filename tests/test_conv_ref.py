@@ -382,3 +382,121 @@ def test_x2_wgrad_rule_rejects_lost_halves_and_a_skipped_tap_product():
     rec = R.judge(skipped.float(), dw64, dw32, "f32", extra)
     print(f"(x_lo, g_hi) skipped in one split: ratio {rec['ratio']:.3g} beyond {rec['frac_bad']:.2%}")
     assert rec["bad"] > 0, rec
+
+
+# ---- the 4x4 / stride-2 convolution and the virtual 3x3 kernel the library computes it through ------------------------------------
+def _virtual(w4):
+    """The virtual 3x3 kernel [cout,4C,3,3] of a [cout,C,4,4] weight by the formula csrc/pack.hip documents: virtual channel ci has
+    sub = ci / C, and tap t = ty*3 + tx carries ky = 2*(t/3) + (sub>>1) - 1, kx = 2*(t%3) + (sub&1) - 1, zero outside [0,4)."""
+    cout, c = w4.shape[:2]
+    w3 = torch.zeros(cout, 4 * c, 3, 3, dtype=w4.dtype)
+    for ci in range(4 * c):
+        sub, ch = ci // c, ci % c
+        for t in range(9):
+            ky, kx = 2 * (t // 3) + (sub >> 1) - 1, 2 * (t % 3) + (sub & 1) - 1
+            if 0 <= ky < 4 and 0 <= kx < 4:
+                w3[:, ci, t // 3, t % 3] = w4[:, ch, ky, kx]
+    return w3
+
+
+def _case4(n=2, c=5, cout=7, h=5, w=6, seed=31):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(n, c, 2 * h, 2 * w, generator=g), torch.randn(cout, c, 4, 4, generator=g) * (2.0 / (c * 16)) ** 0.5,
+            torch.randn(n, cout, h, w, generator=g))
+
+
+def test_s2d_is_the_library_order_and_d2s_inverts_it():
+    from tests import disc_helpers_ref as D
+    x, _, _ = _case4()
+    p = R.s2d(x)
+    assert p.shape == (2, 20, 5, 6)
+    assert float(p[1, 3 * 5 + 2, 4, 3]) == float(x[1, 2, 2 * 4 + 1, 2 * 3 + 1])          # sub = 3: (i, j) = (1, 1)
+    assert float(p[0, 1 * 5 + 4, 2, 5]) == float(x[0, 4, 2 * 2 + 0, 2 * 5 + 1])          # sub = 1: (i, j) = (0, 1)
+    assert np.array_equal(p.permute(0, 2, 3, 1).numpy(), D.s2d_ref(x.permute(0, 2, 3, 1).numpy()))
+    assert torch.equal(R.d2s(p), x)
+
+
+def test_4x4s2_references_against_torch():
+    x, w4, gy = _case4()
+    conv = F.conv2d(x.double(), w4.double(), stride=2, padding=1)
+    assert (R.correlate4x4s2(x, w4, F64) - conv).abs().max().item() < 1e-13
+    assert (R.correlate4x4s2(x, w4, F32).double() - conv).abs().max().item() < 1e-5
+    got, _ = R.conv4x4s2(x, w4, F64, lrelu=True, slope=0.2)
+    assert (got - F.leaky_relu(conv, float(np.float32(0.2)))).abs().max().item() < 1e-13
+    tr = F.conv_transpose2d(gy.double(), w4.double(), stride=2, padding=1)
+    assert tr.shape == x.shape and (R.dgrad4x4s2(gy, w4, F64) - tr).abs().max().item() < 1e-13
+    assert (R.dgrad4x4s2(gy, w4, F32).double() - tr).abs().max().item() < 1e-5
+    wt = w4.double().clone().requires_grad_(True)
+    (F.conv2d(x.double(), wt, stride=2, padding=1) * gy.double()).sum().backward()
+    assert (R.wgrad4x4s2(x, gy, 0.5, F64) - 0.5 * wt.grad).abs().max().item() < 1e-13
+    assert (R.wgrad4x4s2(x, gy, 0.5, F32).double() - 0.5 * wt.grad).abs().max().item() < 1e-4
+    # the adjoint pair: <conv(x), g> = <x, dgrad(g)>
+    assert abs(float((conv * gy.double()).sum() - (x.double() * tr).sum())) < 1e-10
+
+
+def test_virtual_kernel_over_s2d_equals_the_4x4s2_definition():
+    """Forward, transposed pass and the fold of the 3x3 weight gradient: the dense 3x3 operation with the virtual kernel over the
+    space-to-depth image IS the 4x4 / stride-2 operation on the original image (float64, to rounding)."""
+    from tests import disc_helpers_ref as D
+    x, w4, gy = _case4()
+    w3 = _virtual(w4)
+    assert np.array_equal(w3.numpy(), D.virtual_ref(w4.numpy()))
+    assert (R.correlate(R.s2d(x), w3, F64) - R.correlate4x4s2(x, w4, F64)).abs().max().item() < 1e-13
+    # backward-data: the 3x3 convolution of g with the transposed, tap-flipped virtual kernel gives the s2d image of the input gradient
+    w3t = w3.permute(1, 0, 2, 3).flip(2, 3)
+    assert (R.d2s(R.correlate(gy, w3t, F64)) - R.dgrad4x4s2(gy, w4, F64)).abs().max().item() < 1e-13
+    # weight gradient: each real tap reads the one virtual tap that carries it
+    dw3, _ = R.wgrad(R.s2d(x), gy, 0.5, F64)
+    folded = torch.from_numpy(D.fold_ref(dw3.numpy()))
+    assert (folded - R.wgrad4x4s2(x, gy, 0.5, F64)).abs().max().item() < 1e-13
+    # ... and the 3x3 gradient is NOT zero in the blocks the virtual kernel leaves empty: a kernel that skips them stores something else
+    assert (dw3[:, ~R.live_mask(5)].abs() > 1e-3).any()
+
+
+def test_sixteen_of_36_blocks_are_live_and_they_are_the_ones_the_kernel_names():
+    _, w4, _ = _case4()
+    w4 = w4.abs() + 1.0                                      # no accidental zeros
+    w3 = _virtual(w4)
+    c = w4.shape[1]
+    live = {(sub, ty, tx) for sub in range(4) for ty in range(3) for tx in range(3) if (w3[:, sub * c:(sub + 1) * c, ty, tx] != 0).any()}
+    dead = {(sub, ty, tx) for sub in range(4) for ty in range(3) for tx in range(3) if (w3[:, sub * c:(sub + 1) * c, ty, tx] == 0).all()}
+    assert len(live) == 16 and len(dead) == 20
+    # csrc/conv3x3_ws.h, sparse_stage, SP = 1: i = 0 -> ty in {1,2}, i = 1 -> ty in {0,1}; tx by j alike
+    rows = {0: (1, 2), 1: (0, 1)}
+    assert live == {(i * 2 + j, ty, tx) for i in range(2) for j in range(2) for ty in rows[i] for tx in rows[j]}
+    assert all(set(R.live_taps(sub)) == {(ty, tx) for s, ty, tx in live if s == sub} for sub in range(4))
+    assert int(R.live_mask(c).sum()) == 16 * c and (w3[:, R.live_mask(c)] != 0).all() and (w3[:, ~R.live_mask(c)] == 0).all()
+    # SP = 2 (backward-data, taps flipped: pack.hip t = 8 - tap): i = 0 -> {0,1}, i = 1 -> {1,2}
+    w3t = w3.permute(1, 0, 2, 3).flip(2, 3)                 # [4C (M), cout (K), 3, 3]
+    live_t = {(sub, ty, tx) for sub in range(4) for ty in range(3) for tx in range(3) if (w3t[sub * c:(sub + 1) * c, :, ty, tx] != 0).any()}
+    rows_t = {0: (0, 1), 1: (1, 2)}
+    assert live_t == {(i * 2 + j, ty, tx) for i in range(2) for j in range(2) for ty in rows_t[i] for tx in rows_t[j]}
+    assert all(set(R.live_taps(sub, transposed=True)) == {(ty, tx) for s, ty, tx in live_t if s == sub} for sub in range(4))
+
+
+def test_rule_rejects_an_index_mutation_of_the_sparse_stage():
+    """What tests/test_gpu_sparse_taps.py must be able to see: the forward pass with the two column offsets of sub-position j exchanged
+    (each sub-position multiplies its two live tap columns against the wrong pair of halo columns) -- every index still inside the
+    3x3 window, no value out of place but the selection.  Both storage rules reject it; the unmutated evaluation passes."""
+    g = torch.Generator().manual_seed(41)
+    n, c, cout, h, w = 1, 32, 64, 9, 33
+    x = _q(torch.randn(n, c, 2 * h, 2 * w, generator=g), "f16")
+    w4 = _q(torch.randn(cout, c, 4, 4, generator=g) * (2.0 / (c * 16)) ** 0.5, "f16")
+    ref64, _ = R.conv4x4s2(x, w4, F64, lrelu=True, slope=0.2)
+    ref32, _ = R.conv4x4s2(x, w4, F32, lrelu=True, slope=0.2)
+    w3 = _virtual(w4)
+    xs = R.s2d(x)
+    assert R.judge(_store(R.conv3x3(xs, w3, F64, lrelu=True, slope=0.2)[0], "f16"), ref64, ref32, "f16")["bad"] == 0
+    xp = torch.zeros(n, 4 * c, h + 2, w + 2, dtype=F64)
+    xp[:, :, 1:-1, 1:-1] = xs
+    acc = torch.zeros(n, cout, h, w, dtype=F64)
+    for sub in range(4):
+        dx0 = 1 if (sub & 1) == 0 else 0
+        wrong_dx0 = 1 - dx0                                  # the mutation
+        for ty, tx in R.live_taps(sub):
+            sx = wrong_dx0 + (tx - dx0)
+            acc += torch.einsum("oc,nchw->nohw", w3[:, sub * c:(sub + 1) * c, ty, tx].double(), xp[:, sub * c:(sub + 1) * c, ty:ty + h, sx:sx + w])
+    wrong = R.epilogue(acc, F64, lrelu=True, slope=0.2)[0]
+    for kind in ("f16", "pair"):
+        rec = R.judge(_store(wrong, "f16") if kind == "f16" else wrong, ref64, ref32, kind)
+        assert rec["frac_bad"] > 0.9, (kind, rec)
