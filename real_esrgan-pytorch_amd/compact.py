@@ -10,7 +10,9 @@ conv 64->3*s*s, pixel-shuffle, + the nearest-upsampled input.  There is no PyTor
 input or parameter that requires grad runs `resr_compact_forward_train` -- the same convolutions on a plain epilogue, every
 pre-activation and activation kept in a workspace the graph owns -- and its backward `resr_compact_backward` (csrc/compact.hip,
 compact_train.hip; DESIGN, "Compact generator: training").  Every other call, and every call of a model built without the flag,
-takes the inference path below unchanged; without the flag a forward that would need a graph raises.
+takes the inference path below unchanged; without the flag a forward that would need a graph raises.  The training surface is
+`Generator`'s: `grad_hook` (the data-parallel exchange, `train.DataParallel.attach`), `flat_parameter()` / `flat_grad()` (one
+optimiser tensor, one graph input), and the train scripts reach the model through `config.build_generator` ($RESR_G_ARCH=compact).
 
 Every forward checks its own input, allocates its own result and goes through one call path (`_call`).
 
@@ -55,6 +57,7 @@ class _CompactFn(torch.autograd.Function):
         y, desc, ws, packed = module._run_forward_train(x)
         ctx.module, ctx.desc, ctx.ws, ctx.packed = module, desc, ws, packed
         ctx.x_dtype = x.dtype
+        ctx.one_tensor = len(params) == 1 and params[0] is _arena.flat_alias(module)   # flat_parameter() mode: the alias stands for all
         ctx._token = _arena.GraphToken(ws)   # the workspace is this graph's until its backward has run or the graph is dropped
         return y
 
@@ -64,7 +67,7 @@ class _CompactFn(torch.autograd.Function):
             raise RuntimeError("SRVGGNetCompact: this graph's backward has run already and its workspace was given back "
                                "(run the forward again; retain_graph is not supported on the native pass)")
         grads, gx = ctx.module._run_backward(ctx.desc, ctx.ws, ctx.packed, gy.contiguous().float(), ctx.needs_input_grad[1],
-                                             ctx.needs_input_grad[2:])
+                                             ctx.needs_input_grad[2:], ctx.one_tensor)
         ctx._token.finish()
         return (None, gx if gx is None else gx.to(ctx.x_dtype)) + tuple(grads)
 
@@ -121,6 +124,7 @@ class SRVGGNetCompact(nn.Module):
         self._packed_train: Optional[torch.Tensor] = None
         self._table_train: Optional[tuple] = None
         self._train_workspaces: Dict[tuple, List[_arena.Workspace]] = {}
+        self.grad_hook = None   # optional callable(flat_grad) after a backward that produced weight gradients (data-parallel all-reduce)
 
     def _activation(self, num_feat: int) -> nn.Module:
         if self.act_type == "prelu":
@@ -160,7 +164,37 @@ class SRVGGNetCompact(nn.Module):
             self._packed_train = None
             self._table_train = None
             self._train_workspaces.clear()
+            _arena.flat_alias(self, self._flat)   # the arena was rebuilt (`.to()`, EMA.apply_shadow / restore): the alias follows it
         return self._flat
+
+    def flat_parameter(self) -> nn.Parameter:
+        """One leaf Parameter aliasing the whole fp32 arena (as `Generator.flat_parameter`, `Discriminator.flat_parameter`):
+        `optim.Adam([g.flat_parameter()], fused=True)` and the GradScaler's unscale / inf check are single launches, and a training
+        graph carries ONE parameter input instead of 3 * num_conv + 5 (PReLU).  Once it exists (and requires grad) a training
+        `forward` hands autograd this tensor alone and backward returns the fresh flat gradient tensor for it: `.grad` of the alias
+        accumulates by autograd's own add, the per-tensor Parameters receive no gradients; `zero_grad()` clears it and
+        `requires_grad_` is mirrored onto it.  `parameters()`, `state_dict()` and their key order are unchanged; on a model built
+        without `trainable` it may be held by an optimiser and changes nothing about the guard."""
+        return _arena.flat_alias(self, self.flat_parameters(), create=True)
+
+    def flat_grad(self) -> Optional[torch.Tensor]:
+        fp = _arena.flat_alias(self)
+        return None if fp is None else fp.grad
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        super().zero_grad(set_to_none=set_to_none)
+        fp = _arena.flat_alias(self)
+        if fp is not None and fp.grad is not None:
+            if set_to_none:
+                fp.grad = None
+            else:
+                fp.grad.zero_()
+
+    def requires_grad_(self, requires_grad: bool = True):
+        fp = _arena.flat_alias(self)
+        if fp is not None:
+            fp.requires_grad_(requires_grad)
+        return super().requires_grad_(requires_grad)
 
     # ---- C-ABI plumbing ---------------------------------------------------------------------------------------------------
     def _desc(self, n: int, h: int, w: int) -> _lib.CompactDesc:
@@ -242,19 +276,30 @@ class SRVGGNetCompact(nn.Module):
                                                 ws.buf.numel(), _lib.ptr(y), _lib.stream_ptr(xc)), "resr_compact_forward_train")
         return y, desc, ws, self._packed_train
 
-    def _run_backward(self, desc, ws: _arena.Workspace, packed: torch.Tensor, gy: torch.Tensor, need_gx: bool, need_params):
-        """resr_compact_backward into a fresh flat gradient tensor: per-parameter views of it (None where not needed), gx or None."""
+    def _run_backward(self, desc, ws: _arena.Workspace, packed: torch.Tensor, gy: torch.Tensor, need_gx: bool, need_params,
+                      one_tensor: bool = False):
+        """resr_compact_backward into a fresh flat gradient tensor: per-parameter views of it (None where not needed), gx or None.
+        `grad_hook` sees the flat tensor first, once, when any parameter gradient is wanted.  `one_tensor` (the graph's parameter
+        input is the `flat_parameter()` alias): the flat tensor itself is the one gradient handed back."""
         flat = self.flat_parameters()
         grad = torch.empty_like(flat)
         gx = torch.empty((desc.n, self.num_in_ch, desc.h, desc.w), dtype=torch.float32, device=gy.device) if need_gx else None
         _lib.check(_lib.lib().resr_compact_backward(C.byref(desc), _lib.ptr(gy), _lib.ptr(flat), _lib.ptr(packed), _lib.ptr(ws.buf),
                                                     ws.buf.numel(), _lib.ptr(grad), _lib.ptr(gx), _lib.stream_ptr(gy)), "resr_compact_backward")
+        if self.grad_hook is not None and any(need_params):
+            self.grad_hook(grad)
+        if one_tensor:
+            return [grad if need_params[0] else None], gx
         views = _arena.views(grad, self.named_parameters()).values()
         return [g if need else None for g, need in zip(views, need_params)], gx
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         # grad mode is off inside autograd.Function.forward: whether this call builds a graph is decided here
         params = self._ordered_params()
+        if self.trainable:
+            fp = _arena.flat_alias(self, self.flat_parameters())
+            if fp is not None and fp.requires_grad:   # flat_parameter() mode: one graph input for all tensors (a frozen alias: the per-tensor flags decide)
+                params = [fp]
         training = self.trainable and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params))
         if not training:
             self._guard(x)

@@ -69,6 +69,19 @@ precision = os.environ.get("RESR_PRECISION", "exact16" if output_parity else "fa
 if output_parity and precision != "exact16":
     raise ValueError(f"RESR_OUTPUT_PARITY=1 runs in exact16; RESR_PRECISION={precision!r} contradicts it")
 inference_precision = os.environ.get("RESR_INFERENCE_PRECISION", "exact16")
+# Generator architecture of the train scripts, their validate() and test.py (build_generator() below): "rrdb" = `Generator`, the
+# reference's RRDBNet; "compact" = `SRVGGNetCompact` (upstream's realesr-animevideov3 / realesr-general-x4v3 family) with
+# `compact_num_conv` body convs and `compact_act_type` activations, trainable=True in the train scripts ("fast" or "strict").
+g_arch = os.environ.get("RESR_G_ARCH", "rrdb")
+if g_arch not in ("rrdb", "compact"):
+    raise ValueError(f"RESR_G_ARCH={g_arch!r}: expected 'rrdb' or 'compact'")
+if output_parity and g_arch == "compact":
+    raise ValueError("RESR_OUTPUT_PARITY=1 runs in exact16; exact16 training of the compact generator (RESR_G_ARCH=compact) is not built")
+compact_num_conv = int(os.environ.get("RESR_COMPACT_NUM_CONV", "16"))
+compact_act_type = os.environ.get("RESR_COMPACT_ACT", "prelu")
+# An upstream checkpoint ({"params_ema": sd} / {"params": sd} / a bare state dict: model.load_official_state_dict, RRDB or compact
+# keys) loaded into the generator after build_model() and before any `resume*` is applied; "" = none.
+pretrained_g = os.environ.get("RESR_PRETRAINED_G", "")
 niqe_model_path = "./results/pretrained_models/niqe_model.mat"
 in_channels = 3
 out_channels = 3
@@ -137,6 +150,21 @@ def generator_options() -> dict:
     if output_parity:
         opts["x2_plan"] = _lib.X2_PLAN_OUTPUT_PARITY
     return opts
+
+
+def build_generator(training: bool):
+    """The generator of `g_arch`, not yet on a device: the training module of the train scripts' build_model() (training=True) or
+    the fp32 call site of test.py (training=False: `inference_precision`)."""
+    if g_arch == "compact":
+        from .compact import SRVGGNetCompact
+        return SRVGGNetCompact(num_conv=compact_num_conv, upscale=upscale_factor, act_type=compact_act_type,
+                               precision=train_precision() if training else inference_precision, trainable=training)
+    if g_arch != "rrdb":
+        raise ValueError(f"config.g_arch={g_arch!r}: expected 'rrdb' or 'compact'")
+    from .model import Generator
+    if training:
+        return Generator(in_channels, out_channels, upscale_factor, **generator_options())        # (output parity: above)
+    return Generator(in_channels, out_channels, upscale_factor, precision=inference_precision)    # fp32 call site: test.py:79-80 (no autocast)
 
 
 def backward_options() -> dict:

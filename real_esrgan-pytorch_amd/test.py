@@ -16,7 +16,7 @@ import torch
 
 from . import _lib, config, imgproc
 from .image_quality_assessment import NIQE
-from .model import Generator
+from .compact import SRVGGNetCompact
 from .tiling import super_resolve
 
 
@@ -28,8 +28,8 @@ def natural_sorted(names: List[str]) -> List[str]:
 def main() -> float:
     torch.cuda.set_device(config.device)            # one process per GPU: every launch and side stream on this device
     from PIL import Image
-    model = Generator(config.in_channels, config.out_channels, config.upscale_factor,
-                      precision=config.inference_precision)                     # fp32 call site: test.py:79-80 (no autocast)
+    # config.g_arch: Generator or SRVGGNetCompact, at config.inference_precision -- the fp32 call site, test.py:79-80 (no autocast)
+    model = config.build_generator(False)
     model = model.to(device=config.device, memory_format=torch.channels_last)              # test.py:32
     print("Build Real_ESRGAN model successfully.")
     checkpoint = torch.load(config.model_path, map_location=lambda storage, loc: storage, weights_only=False)
@@ -50,6 +50,8 @@ def main() -> float:
         lr_tensor = lr_tensor.to(device=config.device, memory_format=torch.channels_last, non_blocking=True)
         with torch.no_grad():
             sr_tensor = super_resolve(model, lr_tensor)                                    # test.py:79 (any frame size)
+        if isinstance(model, SRVGGNetCompact):
+            sr_tensor.clamp_(0, 1)      # the compact module does not clamp (Generator does, inside); upstream's inference does, NIQE quantises to 0..255
         Image.fromarray(imgproc.tensor_to_image(sr_tensor, False, False)).save(os.path.join(config.sr_dir, name))
         niqe_metrics += niqe(sr_tensor).item()
     _lib.chain_health()             # fail loudly if a chained conv launch ever gave up on a neighbouring tile

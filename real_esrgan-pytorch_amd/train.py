@@ -4,13 +4,15 @@ data-parallel ready.
 One process per GPU (`setup_distributed`).  Exchanges per optimiser step (`DataParallel`):
   * generator: its backward writes every weight gradient into one flat fp32 arena and fires an event per finished range
     (tail convs, RRDB 22 ... 0, conv1); the ranges are all-reduced bucket by bucket on a communication stream WHILE the
-    rest of the backward pass runs (`attach` / `all_reduce_ranges_`);
+    rest of the backward pass runs (`attach` / `all_reduce_ranges_`); the compact generator (SRVGGNetCompact(trainable=True))
+    hands its fresh flat gradient tensor to the same `attach`, one message behind its backward pass (`all_reduce_mean_`);
   * discriminator (GAN step): its gradients are the sum of two backward passes, reduced once after the second
     (`attach_discriminator` / `all_reduce_grads_`); weights and spectral-norm u / v are broadcast at attach time.
 """
 from __future__ import annotations
 
 import os
+import warnings
 from typing import Callable, Iterable, Optional
 
 import torch
@@ -20,6 +22,8 @@ from torch import nn
 from . import losses
 from ._arena import arena_of as _arena_of, flat_alias
 from .model import EMA, Generator
+
+_OVERLAP_WARNED = False   # DataParallel.attach: the overlapped exchange was asked for on a model without gradient-ready events (said once)
 
 
 def setup_distributed(backend: Optional[str] = None) -> tuple:
@@ -102,7 +106,7 @@ class DataParallel:
             w.wait()
         self._finish_mean_(flat)
 
-    def attach(self, model: Generator, overlap: Optional[bool] = None) -> None:
+    def attach(self, model: nn.Module, overlap: Optional[bool] = None) -> None:
         """Generator: identical initial weights, then the gradient arena is all-reduced once per backward (the generator runs
         exactly one backward per optimiser step in both training scripts: train_realesrnet.py:388, train_realesrgan.py:484).
         overlap=True: bucket by bucket on a communication stream WHILE the rest of the backward pass runs -- the native
@@ -111,12 +115,29 @@ class DataParallel:
         and overlaps the NEXT batch's degradation on its side stream only.  Why off: the backward pass runs its dense blocks
         as chained launches that need every CU (conv3x3_ws.h); an RCCL kernel next to them only delays them (tests/
         test_gpu_chain.py holds CUs with a stand-in kernel), but that combination has not run on a multi-GPU box yet, and
-        what overlap buys is small -- 67 MB over xGMI is under a millisecond of a 120 ms step."""
+        what overlap buys is small -- 67 MB over xGMI is under a millisecond of a 120 ms step.
+
+        Any module with `flat_parameters()` and a `grad_hook` attribute is taken (SRVGGNetCompact(trainable=True): its backward
+        calls the hook on the fresh flat gradient tensor before autograd sees it).  The overlapped exchange also needs
+        `grad_ready_hook` and `grad_ranges()`: asked for on a model without them, the one-message exchange is used, `overlap`
+        is False and a warning says so once.  A compact model built without `trainable` has no backward to hook into: ValueError."""
+        if not (hasattr(model, "flat_parameters") and hasattr(model, "grad_hook")):
+            raise TypeError(f"DataParallel.attach: {type(model).__name__} has no flat_parameters() / grad_hook")
+        if not getattr(model, "trainable", True):
+            raise ValueError(f"DataParallel.attach: {type(model).__name__} was built with trainable=False: it has no backward pass "
+                             "that could exchange gradients")
         flat = model.flat_parameters()
         self.warm_up(flat.device)
         self.broadcast_(flat)
         if overlap is None:
             overlap = os.environ.get("RESR_DP_OVERLAP", "0") == "1"
+        if overlap and not (hasattr(model, "grad_ready_hook") and hasattr(model, "grad_ranges")):
+            global _OVERLAP_WARNED
+            if not _OVERLAP_WARNED:
+                _OVERLAP_WARNED = True
+                warnings.warn(f"DataParallel.attach: {type(model).__name__} fires no gradient-ready events; the overlapped exchange "
+                              "is not available for it, its gradients are exchanged in one message behind the backward pass", RuntimeWarning)
+            overlap = False
         self.overlap = bool(overlap and self.active)
         if self.overlap:
             model.grad_ready_hook = self.all_reduce_ranges_

@@ -27,7 +27,7 @@ from .dataset import CUDAPrefetcher
 from .degrade import DegradationPrefetcher
 from .discriminator import Discriminator
 from .image_quality_assessment import NIQE
-from .model import EMA, Generator
+from .model import EMA, Generator  # noqa: F401  (Generator: the reference's script-level name)
 from . import train_realesrnet as _net
 from .train import DataParallel, RealESRGANStep, setup_distributed
 from .meters import AverageMeter, ProgressMeter, Summary  # noqa: F401
@@ -37,8 +37,7 @@ from .train_realesrnet import ScalarWriter, load_dataset, validate  # noqa: F401
 def build_model() -> List[nn.Module]:
     """Reference train_realesrgan.py:223-237."""
     discriminator = Discriminator(**config.backward_options()).to(device=config.device)    # (output parity: config.py)
-    generator = Generator(config.in_channels, config.out_channels, config.upscale_factor,
-                          **config.generator_options()).to(device=config.device)
+    generator = config.build_generator(True).to(device=config.device)   # config.g_arch: Generator or SRVGGNetCompact
     ema_model = EMA(generator, config.ema_model_weight_decay).to(device=config.device)
     ema_model.register()
     return [discriminator, generator, ema_model]
@@ -92,6 +91,8 @@ def main() -> None:
     pixel_criterion, content_criterion, adversarial_criterion = define_loss()
     d_optimizer, g_optimizer = define_optimizer(discriminator, generator)
     d_scheduler, g_scheduler = define_scheduler(d_optimizer, g_optimizer)
+    if config.pretrained_g:                               # an upstream checkpoint, before any way of resuming; the EMA starts from it
+        _net.load_pretrained(config.pretrained_g, generator, ema_model)
     if config.resume:                                     # RealESRNet weights into the generator (:60-65)
         generator.load_state_dict(_load(config.resume)["state_dict"])
         print("Loaded RealESRNet model weights.")

@@ -27,7 +27,8 @@ from .dataset import CUDAPrefetcher, TestImageDataset, TrainValidImageDataset
 from .degrade import DegradationPrefetcher
 from .image_quality_assessment import NIQE
 from .meters import AverageMeter, ProgressMeter, Summary  # noqa: F401  (the reference's script-level names)
-from .model import EMA, Generator
+from .compact import SRVGGNetCompact
+from .model import EMA, Generator, load_official_state_dict  # noqa: F401  (Generator: the reference's script-level name)
 from .train import DataParallel, RealESRNetStep, setup_distributed
 
 
@@ -82,11 +83,18 @@ def load_dataset() -> List[CUDAPrefetcher]:
 
 def build_model() -> List[nn.Module]:
     """Reference train_realesrnet.py:175-183."""
-    model = Generator(config.in_channels, config.out_channels, config.upscale_factor,
-                      **config.generator_options()).to(device=config.device)        # (output parity: config.py)
+    model = config.build_generator(True).to(device=config.device)      # config.g_arch: Generator or SRVGGNetCompact (output parity: config.py)
     ema_model = EMA(model, config.ema_model_weight_decay).to(device=config.device)
     ema_model.register()
     return [model, ema_model]
+
+
+def load_pretrained(path: str, model: nn.Module, ema_model: EMA) -> None:
+    """`config.pretrained_g`: an upstream checkpoint into the generator (model.load_official_state_dict), and the EMA shadow
+    registered again from the loaded weights -- a fine-tune must not average from the random init of build_model()."""
+    load_official_state_dict(model, torch.load(path, map_location=lambda storage, loc: storage, weights_only=False))
+    ema_model.register()
+    print(f"Loaded pretrained generator weights `{os.path.abspath(path)}`.")
 
 
 def define_loss() -> nn.L1Loss:
@@ -135,6 +143,8 @@ def main() -> None:
     start_epoch, best_niqe = 0, 100.0
     train_prefetcher, valid_prefetcher, test_prefetcher = load_dataset()
     model, ema_model = build_model()
+    if config.pretrained_g:                              # before the broadcast below and before `resume`
+        load_pretrained(config.pretrained_g, model, ema_model)
     dp = DataParallel()
     dp.attach(model)                                     # broadcast of the initial weights + all-reduce of the gradient arena per step
     dp.attach_ema(ema_model)                             # ... and of the EMA shadow (registered from each rank's own init above)
@@ -224,6 +234,8 @@ def validate(model: nn.Module, ema_model: nn.Module, data_prefetcher: CUDAPrefet
         while batch_data is not None:
             lr = batch_data["lr"].to(device=config.device, non_blocking=True)
             sr = model(lr)
+            if isinstance(model, SRVGGNetCompact):
+                sr.clamp_(0, 1)     # the compact module does not clamp (Generator does, inside); upstream's inference does, and NIQE quantises to 0..255
             niqe = niqe_model(sr)
             niqe_metrics.update(niqe.reshape(()), lr.size(0))
             batch_time.update(time.time() - end)
