@@ -748,6 +748,36 @@ int resr_resize_u8(const uint8_t* src, uint8_t* dst, int32_t n, int32_t c, int32
 int resr_jpeg_u8(const uint8_t* src, uint8_t* dst, const float* quality, int32_t* coeffs, int32_t n, int32_t h, int32_t w,
                  void* stream);
 
+/* ---- device-resident training data source (device_data.py; the host side of dataset.py:66-143 as two launches) ------------
+ * resr_tile_batch: dst[b] = the augmented fp32 CHW image of tile index[b] under code aug[b] -- tiles uint8 [M,T,T,3] (RGB, HWC),
+ *   index int32 [B] and aug uint8 [B] on the device, dst fp32 [B,3,T,T].  Code: bits 0-1 = angle / 90 of the rotation about the
+ *   integer centre (T / 2, T / 2) (imgproc._rotate_right_angle: an exact pixel permutation; with an even T a 90 / 180 / 270
+ *   rotation loses one row / column and gains a zero one), bit 2 = horizontal flip, bit 3 = vertical flip, applied in that order;
+ *   then value / 255.0f.  Bit for bit device_data.augment_np.  One launch; 90 / 270 are staged through an LDS tile, so reads and
+ *   writes are both row-contiguous; 64-bit offsets throughout.  The kernel TRUSTS index (0 <= index[b] < M: the caller checks before
+ *   upload) and reads aug's low four bits.  RESR_ERR_ARG before any launch: a null pointer, M, B or T < 1, B > 65535 or
+ *   ceil(T / 32)^2 >= 2^31 (the grid).
+ * resr_blur_kernels: n blur kernels of the degradation stage from n records, one workgroup each -- params float64
+ *   [n][RESR_BLUR_RECORD] on the device, dst fp32 [n,K,K].  A record (doubles):
+ *     [0] family   RESR_BLUR_GAUSSIAN / _GENERALIZED / _PLATEAU / _SINC / _DELTA
+ *     [1] side     odd, 1 <= side <= K: the kernel is side x side, centred in the K x K output, zeros around it (delta: side 1)
+ *     [2] sigma_x  [3] sigma_y  [4] theta   Gaussian families: cov = R(theta) diag(sigma_x^2, sigma_y^2) R(theta)^T ...
+ *     [5] beta     generalized: exp(-q^beta / 2); plateau: 1 / (q^beta + 1); gaussian: exp(-q / 2); q = (x, y) cov^-1 (x, y)^T
+ *     [6] aniso    ... when != 0, else cov = diag(sigma_x^2, sigma_x^2) (sigma_y, theta unused)
+ *     [7] cutoff   sinc: cutoff * J1(cutoff r) / (2 pi r), the centre tap cutoff^2 / (4 pi)
+ *   Taps in float64 (closed-form 2x2 inverse), summed in LDS in a fixed order (the same bits run to run), divided by the sum --
+ *   twice for the Gaussian families, as imgproc.random_mixed_kernels does --, zero-padded to K, cast to fp32.  The definition is
+ *   device_data.blur_kernels_from_params_np (numpy's summation order and LAPACK's inverse differ in the last float64 bits: an fp32
+ *   tap may differ by one ulp).  A family or side outside this definition is refused by the caller before upload (the kernel
+ *   clamps side into [1, K] and never leaves its tile).  RESR_ERR_ARG before any launch: a null pointer, n < 1, K even,
+ *   K < 1 or K > RESR_BLUR_MAX_SIDE. */
+#define RESR_BLUR_RECORD 8
+#define RESR_BLUR_MAX_SIDE 31
+enum { RESR_BLUR_GAUSSIAN = 0, RESR_BLUR_GENERALIZED = 1, RESR_BLUR_PLATEAU = 2, RESR_BLUR_SINC = 3, RESR_BLUR_DELTA = 4 };
+int resr_tile_batch(const uint8_t* tiles, const int32_t* index, const uint8_t* aug, int32_t m, int32_t b, int32_t t, float* dst,
+                    void* stream);
+int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, void* stream);
+
 /* ---- discriminator helpers (model.py:135-203) -------------------------------------------------------- */
 /* 2x2 space-to-depth of an NHWC tensor [n,h,w,c] -> [n,h/2,w/2,4c] (inverse != 0: depth-to-space) */
 int resr_space_to_depth(const void* src, void* dst, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype,

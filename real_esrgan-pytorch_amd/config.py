@@ -82,6 +82,12 @@ compact_act_type = os.environ.get("RESR_COMPACT_ACT", "prelu")
 # An upstream checkpoint ({"params_ema": sd} / {"params": sd} / a bare state dict: model.load_official_state_dict, RRDB or compact
 # keys) loaded into the generator after build_model() and before any `resume*` is applied; "" = none.
 pretrained_g = os.environ.get("RESR_PRETRAINED_G", "")
+# Where the train scripts' training batches come from (their load_dataset(); validation and test are the loader's either way):
+# "loader" = DataLoader workers + `dataset.CUDAPrefetcher`, the reference's host pipeline; "device" = `device_data.DeviceTileSource`,
+# the training tiles resident in HBM as uint8, augmentation and blur-kernel synthesis as two launches per batch.
+data_source = os.environ.get("RESR_DATA_SOURCE", "loader")
+if data_source not in ("loader", "device"):
+    raise ValueError(f"RESR_DATA_SOURCE={data_source!r}: expected 'loader' or 'device'")
 niqe_model_path = "./results/pretrained_models/niqe_model.mat"
 in_channels = 3
 out_channels = 3

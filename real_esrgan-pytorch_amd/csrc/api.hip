@@ -404,6 +404,16 @@ int resr_ema_update(float* shadow, const float* params, int64_t count, double de
     return ema_dispatch(shadow, params, (long)count, decay, (hipStream_t)stream);
 }
 
+int resr_tile_batch(const uint8_t* tiles, const int32_t* index, const uint8_t* aug, int32_t m, int32_t b, int32_t t, float* dst, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return tile_batch_dispatch(tiles, index, aug, m, b, t, dst, (hipStream_t)stream);
+}
+
+int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return blur_kernels_dispatch(params, n, k, dst, (hipStream_t)stream);
+}
+
 int resr_filter2d(const float* src, float* dst, const float* kernel, int32_t n, int32_t c, int32_t h, int32_t w, int32_t kh,
                   int32_t kw, int32_t per_sample, void* stream) {
     RESR_DEVICE_SCOPE(stream);

@@ -1,0 +1,173 @@
+// data_source.hip -- the device-resident training data source (device_data.py): the two launches that make one batch.
+//   tile_batch   : uint8 tiles [M,T,T,3] in HBM -> the batch's fp32 [B,3,T,T]: gather by index, right-angle rotation about the
+//                  integer centre (zero fill where an even side loses a row / column), horizontal / vertical flip, / 255.0f,
+//                  HWC -> CHW.  Bit for bit device_data.augment_np (the imgproc chain of dataset.py).
+//   blur_kernels : one record of RESR_BLUR_RECORD doubles per kernel (include/resr.h) -> fp32 [n,K,K]: the float64 synthesis of
+//                  imgproc._kernel_of / generate_sinc_kernel, normalised, zero-padded to K, cast.  One workgroup per kernel.
+#include <math.h>
+
+#include "host_api.h"
+
+namespace resr {
+
+// ---- tile_batch ------------------------------------------------------------------------------------------------------------------
+// A workgroup owns one TS x TS tile of one output image.  Under every one of the 16 codes the source pixels of such a tile are a
+// TS x TS block of the source tile (rows and columns swap under 90 / 270), so the block is staged in LDS with row-contiguous
+// reads -- consecutive lanes read consecutive bytes of the 3-byte pixels -- and the plane rows leave with consecutive lanes on
+// consecutive floats; the permutation happens between the two, in LDS.  Source coordinates one past the tile (the column / row an
+// even side loses) are staged as zeros: the fill of the rotation.
+constexpr int kTileSide = 32;
+constexpr int kTilePitch = kTileSide * 3 + 4;   // bytes per staged row: 25 dwords, odd, so a column walk spreads over the banks
+
+__global__ __launch_bounds__(256) void tile_batch_kernel(const uint8_t* __restrict__ tiles, const int32_t* __restrict__ index,
+                                                         const uint8_t* __restrict__ aug, float* __restrict__ dst, int T, int tiles_x) {
+    __shared__ uint8_t lds[kTileSide * kTilePitch];
+    const int b = (int)blockIdx.y;
+    const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * kTileSide, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * kTileSide;
+    const int code = aug[b], rot = code & 3;
+    const bool hf = code & 4, vf = code & 8;
+    const int x_end = min(x0 + kTileSide, T) - 1, y_end = min(y0 + kTileSide, T) - 1;   // last destination column / row of the tile
+    // the tile's coordinates before the flips (x1, y1): an interval each
+    const int x1_lo = hf ? T - 1 - x_end : x0, x1_hi = hf ? T - 1 - x0 : x_end;
+    const int y1_lo = vf ? T - 1 - y_end : y0, y1_hi = vf ? T - 1 - y0 : y_end;
+    const int c2 = 2 * (T / 2);   // cx + cy of the rotation about (T / 2, T / 2)
+    // source block: columns sx_lo.., rows sy_lo.. (rot 0: (x1, y1); 90: (c2 - y1, x1); 180: (c2 - x1, c2 - y1); 270: (y1, c2 - x1))
+    int sx_lo, sy_lo;
+    switch (rot) {
+        case 0: sx_lo = x1_lo; sy_lo = y1_lo; break;
+        case 1: sx_lo = c2 - y1_hi; sy_lo = x1_lo; break;
+        case 2: sx_lo = c2 - x1_hi; sy_lo = c2 - y1_hi; break;
+        default: sx_lo = y1_lo; sy_lo = c2 - x1_hi; break;
+    }
+    const uint8_t* src = tiles + (size_t)index[b] * (size_t)T * (size_t)T * 3;
+    for (int i = (int)threadIdx.x; i < kTileSide * kTileSide * 3; i += 256) {
+        const int r = i / (kTileSide * 3), k = i - r * (kTileSide * 3);
+        const int sy = sy_lo + r, sx = sx_lo + k / 3;
+        uint8_t v = 0;
+        if (sy < T && sx < T) v = src[((size_t)sy * T + sx_lo) * 3 + k];   // (sx_lo, sy_lo >= 0 for every code)
+        lds[r * kTilePitch + k] = v;
+    }
+    __syncthreads();
+    const int tx = (int)(threadIdx.x & 31u), x = x0 + tx;
+    if (x > x_end) return;
+    const int x1 = hf ? T - 1 - x : x;
+    const size_t plane = (size_t)T * (size_t)T;
+    for (int ty = (int)(threadIdx.x >> 5); ty < kTileSide; ty += 8) {
+        const int y = y0 + ty;
+        if (y > y_end) break;
+        const int y1 = vf ? T - 1 - y : y;
+        int sx, sy;
+        switch (rot) {
+            case 0: sx = x1; sy = y1; break;
+            case 1: sx = c2 - y1; sy = x1; break;
+            case 2: sx = c2 - x1; sy = c2 - y1; break;
+            default: sx = y1; sy = c2 - x1; break;
+        }
+        const uint8_t* p = lds + (sy - sy_lo) * kTilePitch + (sx - sx_lo) * 3;
+        float* o = dst + (size_t)b * 3 * plane + (size_t)y * T + x;
+        o[0] = (float)p[0] / 255.0f;
+        o[plane] = (float)p[1] / 255.0f;
+        o[2 * plane] = (float)p[2] / 255.0f;
+    }
+}
+
+int tile_batch_dispatch(const uint8_t* tiles, const int32_t* index, const uint8_t* aug, int M, int B, int T, float* dst, hipStream_t st) {
+    if (!tiles || !index || !aug || !dst || M < 1 || B < 1 || T < 1) return fail(RESR_ERR_ARG, "tile_batch: bad argument (M=%d B=%d T=%d)", M, B, T);
+    const int64_t tiles_x = ((int64_t)T + kTileSide - 1) / kTileSide;
+    if (tiles_x * tiles_x > 0x7fffffffLL || B > 65535) return fail(RESR_ERR_ARG, "tile_batch: grid overflow (B=%d above 65535, or T=%d)", B, T);
+    prof_before(st);
+    hipLaunchKernelGGL(tile_batch_kernel, dim3((unsigned)(tiles_x * tiles_x), (unsigned)B), dim3(256), 0, st, tiles, index, aug, dst, T, (int)tiles_x);
+    prof_after(st, 33000, 0.0, (double)B * T * T * 15.0);
+    RESR_CHECK_LAUNCH("tile_batch_kernel");
+    return RESR_OK;
+}
+
+// ---- blur_kernels ----------------------------------------------------------------------------------------------------------------
+constexpr int kBlurMaxSide = RESR_BLUR_MAX_SIDE;
+constexpr int kBlurThreads = 256;
+
+// sum of v[0 .. count) in a fixed order: thread t adds v[t], v[t + 256], ... in that order, then the 256 partial sums halve in LDS.
+// Every thread returns the same double; the bits do not depend on the launch.
+__device__ __forceinline__ double fixed_sum(const double* v, int count, double* part) {
+    double s = 0.0;
+    for (int i = (int)threadIdx.x; i < count; i += kBlurThreads) s += v[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int half = kBlurThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half) part[threadIdx.x] += part[threadIdx.x + half];
+        __syncthreads();
+    }
+    const double total = part[0];
+    __syncthreads();
+    return total;
+}
+
+__global__ __launch_bounds__(kBlurThreads) void blur_kernels_kernel(const double* __restrict__ params, float* __restrict__ dst, int K) {
+    __shared__ double taps[kBlurMaxSide * kBlurMaxSide];
+    __shared__ double part[kBlurThreads];
+    const double* r = params + (size_t)blockIdx.x * RESR_BLUR_RECORD;
+    const int family = (int)r[0];
+    int side = (int)r[1];
+    side = side < 1 ? 1 : side > K ? K : side;   // (refused before upload; never index past the LDS tile)
+    const int count = side * side;
+    const double half_side = (double)(side / 2);
+    if (family == RESR_BLUR_DELTA) {
+        for (int i = (int)threadIdx.x; i < count; i += kBlurThreads) taps[i] = i == count / 2 ? 1.0 : 0.0;
+        __syncthreads();
+    } else if (family == RESR_BLUR_SINC) {
+        const double cutoff = r[7];
+        for (int i = (int)threadIdx.x; i < count; i += kBlurThreads) {
+            const double dy = (double)(i / side) - half_side, dx = (double)(i % side) - half_side;
+            const double rad = sqrt(dy * dy + dx * dx);
+            taps[i] = i == count / 2 ? cutoff * cutoff / (4.0 * M_PI) : cutoff * j1(cutoff * rad) / (2.0 * M_PI * rad);
+        }
+        __syncthreads();
+        const double total = fixed_sum(taps, count, part);
+        for (int i = (int)threadIdx.x; i < count; i += kBlurThreads) taps[i] = taps[i] / total;
+        __syncthreads();
+    } else {
+        // inverse of cov = R diag(sx^2, sy^2) R^T in closed form (isotropic: diag(sx^2, sx^2))
+        const double sx2 = r[2] * r[2], sy2 = r[3] * r[3], beta = r[5];
+        double i00, i01, i10, i11;
+        if (r[6] != 0.0) {
+            const double c = cos(r[4]), s = sin(r[4]);
+            const double a00 = c * sx2 * c + s * sy2 * s, a01 = c * sx2 * s - s * sy2 * c, a11 = s * sx2 * s + c * sy2 * c;
+            const double det = a00 * a11 - a01 * a01;
+            i00 = a11 / det; i01 = -a01 / det; i10 = i01; i11 = a00 / det;
+        } else {
+            i00 = i11 = 1.0 / sx2; i01 = i10 = 0.0;
+        }
+        for (int i = (int)threadIdx.x; i < count; i += kBlurThreads) {
+            const double y = (double)(i / side) - half_side, x = (double)(i % side) - half_side;
+            const double q = (x * i00 + y * i10) * x + (x * i01 + y * i11) * y;
+            double v;
+            if (family == RESR_BLUR_GAUSSIAN) v = exp(-0.5 * q);
+            else if (family == RESR_BLUR_GENERALIZED) v = exp(-0.5 * pow(q, beta));
+            else v = 1.0 / (pow(q, beta) + 1.0);
+            taps[i] = v;
+        }
+        __syncthreads();
+        for (int pass = 0; pass < 2; ++pass) {   // imgproc._kernel_of normalises, random_mixed_kernels normalises again
+            const double total = fixed_sum(taps, count, part);
+            for (int i = (int)threadIdx.x; i < count; i += kBlurThreads) taps[i] = taps[i] / total;
+            __syncthreads();
+        }
+    }
+    const int pad = (K - side) / 2;
+    float* out = dst + (size_t)blockIdx.x * (size_t)K * (size_t)K;
+    for (int i = (int)threadIdx.x; i < K * K; i += kBlurThreads) {
+        const int y = i / K - pad, x = i % K - pad;
+        out[i] = (y >= 0 && y < side && x >= 0 && x < side) ? (float)taps[y * side + x] : 0.f;
+    }
+}
+
+int blur_kernels_dispatch(const double* params, int n, int K, float* dst, hipStream_t st) {
+    if (!params || !dst || n < 1 || K < 1 || (K & 1) == 0 || K > kBlurMaxSide) return fail(RESR_ERR_ARG, "blur_kernels: bad argument (n=%d K=%d, K odd and at most %d)", n, K, kBlurMaxSide);
+    prof_before(st);
+    hipLaunchKernelGGL(blur_kernels_kernel, dim3((unsigned)n), dim3(kBlurThreads), 0, st, params, dst, K);
+    prof_after(st, 33100, 0.0, (double)n * (RESR_BLUR_RECORD * 8.0 + 4.0 * K * K));
+    RESR_CHECK_LAUNCH("blur_kernels_kernel");
+    return RESR_OK;
+}
+
+}  // namespace resr

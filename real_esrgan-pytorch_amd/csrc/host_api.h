@@ -172,6 +172,9 @@ int filter2d_u8_dispatch(const uint8_t* src, uint8_t* dst, const int32_t* taps, 
 int resize_u8_dispatch(const uint8_t* src, uint8_t* dst, int n, int c, int h, int w, int oh, int ow, int mode, const int32_t* idx_y, const int32_t* w_y, const int32_t* idx_x,
                        const int32_t* w_x, hipStream_t st);
 int jpeg_u8_dispatch(const uint8_t* src, uint8_t* dst, const float* quality, int32_t* coeffs, int n, int h, int w, hipStream_t st);
+// ---- data_source.hip: a batch of the device-resident training set.  tiles [M,T,T,3] bytes, index / aug [B] on the device; params n records ----
+int tile_batch_dispatch(const uint8_t* tiles, const int32_t* index, const uint8_t* aug, int M, int B, int T, float* dst, hipStream_t st);
+int blur_kernels_dispatch(const double* params, int n, int K, float* dst, hipStream_t st);
 // ---- loss.hip.  loss, grad: outputs (grad may be null) ----
 int bce_logits_const_dispatch(const float* x, long count, float label, float weight, float* loss, float* grad, float* scratch, hipStream_t st);
 int l1_mean_dispatch(const float* a, const float* b, long count, float weight, float* loss, float* grad, float* scratch, hipStream_t st);

@@ -77,8 +77,19 @@ def load_dataset() -> List[CUDAPrefetcher]:
                                   pin_memory=True, drop_last=False, persistent_workers=workers > 0)
     test_dataloader = DataLoader(test_datasets, batch_size=1, shuffle=False, num_workers=min(1, workers),
                                  pin_memory=True, drop_last=False, persistent_workers=workers > 0)
-    return [CUDAPrefetcher(train_dataloader, config.device), CUDAPrefetcher(valid_dataloader, config.device),
-            CUDAPrefetcher(test_dataloader, config.device)]
+    if config.data_source == "device":
+        # the training tiles resident in HBM, augmentation and kernel synthesis on the device (device_data.py): the same batch
+        # dictionary, draws and sampler classes; the DataLoader above is never iterated (no workers start)
+        from .device_data import DeviceTileSource
+        count = len(train_datasets)
+        sampler = torch.utils.data.distributed.DistributedSampler(range(count), _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
+        train_source = DeviceTileSource.from_dir(config.train_image_dir, config.batch_size, config.device, sampler=sampler,
+                                                 P=config.degradation_model_parameters_dict)
+    elif config.data_source == "loader":
+        train_source = CUDAPrefetcher(train_dataloader, config.device)
+    else:
+        raise ValueError(f"config.data_source={config.data_source!r}: expected 'loader' or 'device'")
+    return [train_source, CUDAPrefetcher(valid_dataloader, config.device), CUDAPrefetcher(test_dataloader, config.device)]
 
 
 def build_model() -> List[nn.Module]:
