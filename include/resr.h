@@ -778,6 +778,57 @@ int resr_tile_batch(const uint8_t* tiles, const int32_t* index, const uint8_t* a
                     void* stream);
 int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, void* stream);
 
+/* ---- native NIQE (image_quality_assessment.niqe_native; csrc/niqe.hip): the metric up to its 36 features per block ---------
+ * The tail of the score (NaN-aware mean, covariance, pinv, distance) stays in torch.  float64 wherever the torch path is float64.
+ * resr_niqe_luma_f32 / _u8: src fp32 [n,3,h,w] in [0,1] / uint8 [n,h,w,3] (a byte enters as (float)byte / 255.0f) -> dst uint8
+ *   [n,out_h,out_w]: the luma level of source pixel (crop + y, crop + x) -- crop_border and the trim to whole blocks fused into the
+ *   read.  level = rint(t) (half to even, pinned into 0..255) of the fp32 chain, every operation rounded once, no contraction:
+ *     t = r * 65.481f;  t = t + g * 128.553f;  t = t + b * 24.966f;  t = t + 16.0f
+ *   (tests/niqe_ref.niqe_luma_np is the same chain in numpy).  One launch, profiling ids 34000 (fp32) / 34001 (uint8).
+ *   RESR_ERR_ARG before any launch: a null pointer, n, h, w, out_h or out_w < 1, crop < 0, 2 crop + out_h > h or 2 crop + out_w > w,
+ *   n or out_h above 65535.
+ * resr_niqe_features: luma uint8 [n,h,w] -> feats float64 [n, blocks, 36], block (by, bx) at row by * (w / bw) + bx; columns
+ *   0..17 are scale 1, 18..35 scale 2, each in the order of _block_features.  Four launches:
+ *     34100  the half-size image imresize(y / 255, 0.5) * 255 in float64, H pass then W pass, from the banded tables below;
+ *     34200 / 34201  MSCN + block moments at scale 1 (from the levels) / scale 2 (from the half-size image), one workgroup per block:
+ *            mu and E[y^2] by the 49 taps of `win` with replicate padding at the IMAGE edge, sigma = sqrt(|E[y^2] - mu^2| + 1e-8),
+ *            (y - mu) / (sigma + 1) kept in LDS only, and for each of five maps (the block; its products with the copies rolled by
+ *            (0,1), (1,0), (1,1), (1,-1) inside the block) six float64 words: negatives, positives, sum of squares over the
+ *            negatives, over the positives, sum of magnitudes, sum of squares -- summed in a fixed order: the same bits every call;
+ *     34300  the AGGD fit of every (block, map): the first minimum of |r_gam[i] - rhat_norm| over the grid, then the features.
+ *   Descriptor: n, h, w the luma batch and size (h, w multiples of bh, bw); bh, bw even; the tables on the device:
+ *     start_h int32 [h / 2], w_h float64 [h / 2][taps_h]: output row i = sum_k w_h[i][k] * src[start_h[i] + k], k ascending (the
+ *     non-zero band of imgproc._resize_matrix(h, h / 2, 0.5, True, float64)); start_w / w_w the same for the columns; a start that
+ *     would leave the axis is pinned into it (undefined values, never undefined accesses); taps at most 16.
+ *     grid / r_gam float64 [n_grid]: the shape grid and its ratio table, as _aggd computes them.  win: _gaussian_window() as float64.
+ *   workspace: resr_niqe_workspace_bytes(d) bytes, 8-byte aligned, laid out [half-size image float64 [n, h / 2, w / 2], padded to
+ *     256 bytes | moments float64 [2 scales][n * blocks][5][6]]; it needs no initialisation and holds these after the call (tests
+ *     read them).  The query returns 0 for a descriptor the entry refuses (pointers and tables aside).
+ *   RESR_ERR_ARG before any launch: a null pointer, a bad size, odd or non-dividing blocks, a block whose LDS tile (MSCN block in
+ *   float64 + halo tile + 1920 bytes) exceeds 160 KiB at either scale, taps outside 1..16 or above the axis, misaligned workspace /
+ *   feats; RESR_ERR_WORKSPACE: workspace_bytes too small. */
+typedef struct {
+    int32_t n, h, w;
+    int32_t bh, bw;
+    int32_t taps_h, taps_w;
+    int32_t n_grid;
+    const int32_t* start_h;
+    const double* w_h;
+    const int32_t* start_w;
+    const double* w_w;
+    const double* grid;
+    const double* r_gam;
+    void* workspace;
+    size_t workspace_bytes;
+    double win[49];
+} ResrNiqeDesc;
+int resr_niqe_luma_f32(const float* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, int32_t crop, int32_t out_h, int32_t out_w,
+                       void* stream);
+int resr_niqe_luma_u8(const uint8_t* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, int32_t crop, int32_t out_h, int32_t out_w,
+                      void* stream);
+size_t resr_niqe_workspace_bytes(const ResrNiqeDesc* d);
+int resr_niqe_features(const ResrNiqeDesc* d, const uint8_t* luma, double* feats, void* stream);
+
 /* ---- discriminator helpers (model.py:135-203) -------------------------------------------------------- */
 /* 2x2 space-to-depth of an NHWC tensor [n,h,w,c] -> [n,h/2,w/2,4c] (inverse != 0: depth-to-space) */
 int resr_space_to_depth(const void* src, void* dst, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype,

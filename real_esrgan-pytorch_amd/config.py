@@ -89,6 +89,11 @@ data_source = os.environ.get("RESR_DATA_SOURCE", "loader")
 if data_source not in ("loader", "device"):
     raise ValueError(f"RESR_DATA_SOURCE={data_source!r}: expected 'loader' or 'device'")
 niqe_model_path = "./results/pretrained_models/niqe_model.mat"
+# How validate() and test.py compute NIQE (build_niqe() below): "torch" = `image_quality_assessment.NIQE`, plain torch in float64;
+# "native" = `NativeNIQE`, the features by the kernels of csrc/niqe.hip (same tail, same prior; its luma is the kernels' stated fp32 order).
+niqe_backend = os.environ.get("RESR_NIQE", "torch")
+if niqe_backend not in ("torch", "native"):
+    raise ValueError(f"RESR_NIQE={niqe_backend!r}: expected 'torch' or 'native'")
 in_channels = 3
 out_channels = 3
 upscale_factor = 4
@@ -171,6 +176,15 @@ def build_generator(training: bool):
     if training:
         return Generator(in_channels, out_channels, upscale_factor, **generator_options())        # (output parity: above)
     return Generator(in_channels, out_channels, upscale_factor, precision=inference_precision)    # fp32 call site: test.py:79-80 (no autocast)
+
+
+def build_niqe():
+    """The NIQE module of `niqe_backend` on `device`: NIQE(upscale_factor, niqe_model_path) of the train scripts and test.py."""
+    from .image_quality_assessment import NIQE, NativeNIQE
+    if niqe_backend not in ("torch", "native"):
+        raise ValueError(f"config.niqe_backend={niqe_backend!r}: expected 'torch' or 'native'")
+    cls = NativeNIQE if niqe_backend == "native" else NIQE
+    return cls(upscale_factor, niqe_model_path).to(device=device)
 
 
 def backward_options() -> dict:

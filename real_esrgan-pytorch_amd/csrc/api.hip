@@ -414,6 +414,23 @@ int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, vo
     return blur_kernels_dispatch(params, n, k, dst, (hipStream_t)stream);
 }
 
+int resr_niqe_luma_f32(const float* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, int32_t crop, int32_t out_h, int32_t out_w, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return niqe_luma_dispatch(src, 0, dst, n, h, w, crop, out_h, out_w, (hipStream_t)stream);
+}
+
+int resr_niqe_luma_u8(const uint8_t* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, int32_t crop, int32_t out_h, int32_t out_w, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return niqe_luma_dispatch(src, 1, dst, n, h, w, crop, out_h, out_w, (hipStream_t)stream);
+}
+
+size_t resr_niqe_workspace_bytes(const ResrNiqeDesc* d) { return niqe_workspace_bytes(d); }
+
+int resr_niqe_features(const ResrNiqeDesc* d, const uint8_t* luma, double* feats, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return niqe_features_dispatch(d, luma, feats, (hipStream_t)stream);
+}
+
 int resr_filter2d(const float* src, float* dst, const float* kernel, int32_t n, int32_t c, int32_t h, int32_t w, int32_t kh,
                   int32_t kw, int32_t per_sample, void* stream) {
     RESR_DEVICE_SCOPE(stream);

@@ -175,6 +175,10 @@ int jpeg_u8_dispatch(const uint8_t* src, uint8_t* dst, const float* quality, int
 // ---- data_source.hip: a batch of the device-resident training set.  tiles [M,T,T,3] bytes, index / aug [B] on the device; params n records ----
 int tile_batch_dispatch(const uint8_t* tiles, const int32_t* index, const uint8_t* aug, int M, int B, int T, float* dst, hipStream_t st);
 int blur_kernels_dispatch(const double* params, int n, int K, float* dst, hipStream_t st);
+// ---- niqe.hip: the native NIQE stages (include/resr.h).  u8: src is uint8 [n,h,w,3], else fp32 [n,3,h,w] ----
+int niqe_luma_dispatch(const void* src, int u8, uint8_t* dst, int n, int h, int w, int crop, int oh, int ow, hipStream_t st);
+size_t niqe_workspace_bytes(const ResrNiqeDesc* d);
+int niqe_features_dispatch(const ResrNiqeDesc* d, const uint8_t* luma, double* feats, hipStream_t st);
 // ---- loss.hip.  loss, grad: outputs (grad may be null) ----
 int bce_logits_const_dispatch(const float* x, long count, float label, float weight, float* loss, float* grad, float* scratch, hipStream_t st);
 int l1_mean_dispatch(const float* a, const float* b, long count, float weight, float* loss, float* grad, float* scratch, hipStream_t st);

@@ -823,7 +823,11 @@ class FrameStream:
 
     `out_pix_fmt`, `out_matrix`: the format of the results when it is not the input's (None, the default: the input's) -- "nv12" in
     and "p010" out, "bt601" in and "bt709" out, "rgb24" on one side (then `out_matrix` stays None); each frame is `upscale_frames` of
-    it (module docstring, MIXED FRAME FORMATS) and the output slots get the result's dtype and shape (`slot_layout`)."""
+    it (module docstring, MIXED FRAME FORMATS) and the output slots get the result's dtype and shape (`slot_layout`).
+
+    `on_device` (attribute, default None): a callable given every result as the device tensor the last kernel wrote ([1, ...] of
+    the output format), on the compute stream, right behind the frame's launches and before its download -- a quality score taken
+    from the frame where it lies (`inference_frames --niqe`).  What it returns is dropped; it must not keep the tensor."""
 
     PIX_FMTS = tuple(PIXEL_FORMATS)
 
@@ -853,6 +857,7 @@ class FrameStream:
         self._ready: Deque[np.ndarray] = collections.deque()     # results drained by a change of frame size
         self._up = self._down = self._compute = None
         self._closed = False
+        self.on_device = None
 
     @staticmethod
     def check_frame(frame) -> None:
@@ -921,6 +926,8 @@ class FrameStream:
             self._compute.wait_event(slot.uploaded)
             slot.dev_out = self._fmt.upscale(self.model, slot.dev_in, self.outscale, self._plan)
             slot.computed.record(self._compute)
+            if self.on_device is not None:
+                self.on_device(slot.dev_out)
         with torch.cuda.stream(self._down):
             self._down.wait_event(slot.computed)
             slot.pin_out.copy_(slot.dev_out, non_blocking=True)

@@ -2,9 +2,10 @@
 `train_realesrnet.py:102,430-466` / `train_realesrgan.py` evaluate on every validation batch
 (reference image_quality_assessment.py:803-1032, MATLAB NIQE semantics).
 
-Plain torch in float64 on whatever device the SR batch lives on (a handful of 7x7 filters and per-block moment
-statistics: control-plane work, not a kernel target).  The prior (mean / covariance of the 36 natural-scene features)
-is the reference's `results/pretrained_models/niqe_model.mat`; a copy of that data file is kept as a test fixture
+`niqe` / `NIQE` are plain torch in float64 on whatever device the SR batch lives on.  `niqe_native` / `NativeNIQE` (opt-in:
+`config.niqe_backend`) compute the same 36 features per block with the kernels of csrc/niqe.hip -- from a float [B,3,H,W] batch or
+straight from a uint8 [B,H,W,3] frame -- and share the tail of the score (`_score_from_features`) with `niqe`.
+The prior (mean / covariance of the 36 natural-scene features) is the reference's `results/pretrained_models/niqe_model.mat`; a copy of that data file is kept as a test fixture
 (`tests/golden/niqe_model.mat`).
 """
 from __future__ import annotations
@@ -19,7 +20,7 @@ from torch import nn
 
 from . import imgproc
 
-__all__ = ["NIQE", "niqe"]
+__all__ = ["NIQE", "niqe", "NativeNIQE", "niqe_native"]
 
 
 def _gaussian_window(size: int = 7, sigma: float = 7.0 / 6.0) -> torch.Tensor:
@@ -32,11 +33,17 @@ def _gaussian_window(size: int = 7, sigma: float = 7.0 / 6.0) -> torch.Tensor:
     return torch.from_numpy(h.astype(np.float32))
 
 
+def _aggd_grid(like: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The shape grid 0.2:0.001:10 and its ratio table r(alpha), in `like`'s dtype and on its device."""
+    grid = torch.arange(0.2, 10 + 0.001, 0.001).to(like)                    # float32 grid values, as in the reference
+    r_gam = (2 * torch.lgamma(2.0 / grid) - (torch.lgamma(1.0 / grid) + torch.lgamma(3.0 / grid))).exp()
+    return grid, r_gam
+
+
 def _aggd(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """Asymmetric generalised Gaussian fit of every block x[n,1,h,w] by moment matching on the grid 0.2:0.001:10
     (iqa.py:803-851, the `get_sigma=True` form): shape alpha, left / right scale."""
-    grid = torch.arange(0.2, 10 + 0.001, 0.001).to(x)                       # float32 grid values, as in the reference
-    r_gam = (2 * torch.lgamma(2.0 / grid) - (torch.lgamma(1.0 / grid) + torch.lgamma(3.0 / grid))).exp()
+    grid, r_gam = _aggd_grid(x)
     neg, pos = x < 0, x > 0
     n_neg = neg.sum(dim=(-1, -2), dtype=torch.float32)
     n_pos = pos.sum(dim=(-1, -2), dtype=torch.float32)
@@ -96,8 +103,13 @@ def niqe(tensor: torch.Tensor, crop_border: int, mu_prior: torch.Tensor, cov_pri
         if scale == 1:
             y = _resize_half(y / 255.0) * 255.0
     dist = torch.cat(feats, dim=-1)                                         # [b, nblocks, 36]
+    return _score_from_features(dist, mu_prior, cov_prior)
+
+
+def _score_from_features(dist: torch.Tensor, mu_prior: torch.Tensor, cov_prior: torch.Tensor) -> torch.Tensor:
+    """The score of every image from its block features [b, nblocks, 36] (iqa.py:960-998): the tail `niqe` and `niqe_native` share."""
     scores = []
-    for i in range(b):                                                      # blocks with a NaN feature are dropped
+    for i in range(dist.shape[0]):                                          # blocks with a NaN feature are dropped
         rows = dist[i]
         nan = torch.isnan(rows)
         mu_d = torch.where(nan, torch.zeros_like(rows), rows).sum(0) / (~nan).to(rows.dtype).sum(0)
@@ -131,3 +143,146 @@ class NIQE(nn.Module):
         mu = self.mu_prisparam.to(raw_tensor.dtype).to(torch.float64)
         cov = self.cov_prisparam.to(raw_tensor.dtype).to(torch.float64)
         return niqe(raw_tensor, self.crop_border, mu, cov, self.block_size_height, self.block_size_width)
+
+
+# ---- native backend (csrc/niqe.hip) ----------------------------------------------------------------------------------------------
+def half_band_table(n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The non-zero band of `imgproc._resize_matrix(n, ceil(n / 2), 0.5, True, float64)` as (start int32 [out], w float64 [out, P]):
+    row i of the matrix is zero outside columns start[i] .. start[i] + P - 1 and equals w[i] there, bit for bit -- the taps are
+    accumulated in the order `_resize_matrix` accumulates them, without the dense matrix ever being built."""
+    out = math.ceil(n * 0.5)
+    idx, w = imgproc._resize_taps(n, out, 0.5, True, np.float64)
+    idx = imgproc._reflect_symmetric(idx, n) - 1
+    if idx.min() < 0 or idx.max() >= n:
+        raise ValueError(f"half_band_table: an axis of {n} pixels is shorter than the symmetric copy its taps reach for")
+    p = min(int((idx.max(1) - idx.min(1)).max()) + 1, n)
+    start = np.minimum(idx.min(1), n - p)
+    band = np.zeros((out, p), np.float64)
+    np.add.at(band, (np.repeat(np.arange(out), idx.shape[1]), (idx - start[:, None]).reshape(-1)), w.reshape(-1))
+    return start.astype(np.int32), band
+
+
+_NATIVE_TABLES: dict = {}
+
+
+def _native_tables(h: int, w: int, device: torch.device) -> dict:
+    """Device tables of one luma size, built once: the banded half-size taps, the AGGD grid and ratio table (the module's own torch
+    expression, evaluated on the host in float64), the window."""
+    key = (h, w, str(device))
+    t = _NATIVE_TABLES.get(key)
+    if t is None:
+        shared = _NATIVE_TABLES.get(("grid", str(device)))
+        if shared is None:
+            grid, r_gam = _aggd_grid(torch.zeros((), dtype=torch.float64))
+            shared = _NATIVE_TABLES[("grid", str(device))] = (grid.to(device), r_gam.to(device))
+        sh, wh = half_band_table(h)
+        sw, ww = half_band_table(w)
+        if len(_NATIVE_TABLES) > 16:                                        # a handful of validation sizes live here, not a history
+            for k in [k for k in _NATIVE_TABLES if k[0] != "grid"]:
+                del _NATIVE_TABLES[k]
+        t = _NATIVE_TABLES[key] = {"start_h": torch.from_numpy(sh).to(device), "w_h": torch.from_numpy(wh).to(device),
+                                   "start_w": torch.from_numpy(sw).to(device), "w_w": torch.from_numpy(ww).to(device),
+                                   "grid": shared[0], "r_gam": shared[1], "win": _gaussian_window().double().reshape(-1).tolist()}
+    return t
+
+
+def check_native_blocks(bh: int, bw: int) -> None:
+    """ValueError for a block size the kernels refuse: an odd side, or an LDS tile (the float64 MSCN block and its halo) beyond a CU's
+    160 KiB.  There is no fallback onto the torch path."""
+    from . import _lib
+    if isinstance(bh, bool) or isinstance(bw, bool) or not isinstance(bh, int) or not isinstance(bw, int) or bh < 2 or bw < 2 or bh % 2 or bw % 2:
+        raise ValueError(f"native NIQE needs even block sides of at least 2, got {bh}x{bw}")
+    d = _lib.NiqeDesc()
+    d.n, d.h, d.w, d.bh, d.bw = 1, bh, bw, bh, bw
+    if not _lib.lib().resr_niqe_workspace_bytes(d):
+        raise ValueError(f"native NIQE: {_lib.lib().resr_last_error().decode()}")
+
+
+def niqe_luma_native(tensor: torch.Tensor, crop_border: int, out_h: int, out_w: int) -> torch.Tensor:
+    """The luma levels uint8 [B, out_h, out_w] of a float [B,3,H,W] batch in [0,1] or a uint8 [B,H,W,3] batch, read from
+    `crop_border` pixels inside the image (resr_niqe_luma_f32 / _u8, on the current stream)."""
+    from . import _lib
+    _lib.require_cuda(tensor, "niqe_native")
+    if tensor.dtype == torch.uint8:
+        if tensor.dim() != 4 or tensor.shape[-1] != 3:
+            raise ValueError(f"niqe_native: a uint8 batch is [B,H,W,3], got {tuple(tensor.shape)}")
+        b, h, w = tensor.shape[:3]
+        entry, name = _lib.lib().resr_niqe_luma_u8, "resr_niqe_luma_u8"
+    else:
+        if tensor.dim() != 4 or tensor.shape[1] != 3 or not tensor.is_floating_point():
+            raise ValueError(f"niqe_native: a float batch is [B,3,H,W], got {tensor.dtype} {tuple(tensor.shape)}")
+        b, _, h, w = tensor.shape
+        tensor = tensor.float()
+        entry, name = _lib.lib().resr_niqe_luma_f32, "resr_niqe_luma_f32"
+    tensor = tensor.contiguous()
+    luma = torch.empty((b, out_h, out_w), dtype=torch.uint8, device=tensor.device)
+    _lib.check(entry(_lib.ptr(tensor), _lib.ptr(luma), b, h, w, crop_border, out_h, out_w, _lib.stream_ptr(tensor)), name)
+    return luma
+
+
+def niqe_features_native(luma: torch.Tensor, bh: int = 96, bw: int = 96, keep: bool = False):
+    """resr_niqe_features on the current stream: luma uint8 [B,h,w] (h, w multiples of bh, bw) -> float64 [B, blocks, 36].
+    keep=True also returns the workspace's contents as views: (features, half-size image [B,h/2,w/2], moments [2,B,blocks,5,6])."""
+    from . import _lib
+    import ctypes as C
+    _lib.require_cuda(luma, "niqe_features_native")
+    if luma.dtype != torch.uint8 or luma.dim() != 3 or not luma.is_contiguous():
+        raise ValueError(f"niqe_features_native: luma must be a contiguous uint8 [B,h,w] tensor, got {luma.dtype} {tuple(luma.shape)}")
+    check_native_blocks(bh, bw)
+    b, h, w = luma.shape
+    if h < bh or w < bw or h % bh or w % bw:
+        raise ValueError(f"niqe_features_native: a luma of {h}x{w} is no whole number of {bh}x{bw} blocks")
+    t = _native_tables(h, w, luma.device)
+    d = _lib.NiqeDesc()
+    d.n, d.h, d.w, d.bh, d.bw = b, h, w, bh, bw
+    d.taps_h, d.taps_w, d.n_grid = t["w_h"].shape[1], t["w_w"].shape[1], t["grid"].numel()
+    for name in ("start_h", "w_h", "start_w", "w_w", "grid", "r_gam"):
+        setattr(d, name, t[name].data_ptr())
+    d.win[:] = t["win"]
+    need = int(_lib.lib().resr_niqe_workspace_bytes(d))
+    if not need:
+        raise ValueError(f"native NIQE: {_lib.lib().resr_last_error().decode()}")
+    ws = torch.empty(need // 8, dtype=torch.float64, device=luma.device)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    nblk = (h // bh) * (w // bw)
+    feats = torch.empty((b, nblk, 36), dtype=torch.float64, device=luma.device)
+    _lib.check(_lib.lib().resr_niqe_features(C.byref(d), _lib.ptr(luma), _lib.ptr(feats), _lib.stream_ptr(luma)), "resr_niqe_features")
+    if not keep:
+        return feats
+    n_half = b * (h // 2) * (w // 2)
+    return feats, ws[:n_half].view(b, h // 2, w // 2), ws[need // 8 - 2 * b * nblk * 30:].view(2, b, nblk, 5, 6)
+
+
+def niqe_native(tensor: torch.Tensor, crop_border: int, mu_prior: torch.Tensor, cov_prior: torch.Tensor,
+                bh: int = 96, bw: int = 96) -> torch.Tensor:
+    """`niqe` with the features computed by the kernels of csrc/niqe.hip: a float [B,3,H,W] batch in [0,1], or a uint8 [B,H,W,3]
+    batch scored without a float image ever existing.  Everything is enqueued on the current stream; the shared tail
+    (`_score_from_features`) is `niqe`'s.  The luma is the kernel's stated fp32 order (include/resr.h), which may differ from the
+    torch path's matmul at a pixel whose luma lies within an fp32 rounding of a half ("Native NIQE")."""
+    check_native_blocks(bh, bw)
+    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
+        raise ValueError(f"niqe_native: crop_border must be a non-negative int, got {crop_border!r}")
+    if tensor.dim() != 4:
+        raise ValueError(f"niqe_native: expected a 4-D batch, got {tuple(tensor.shape)}")
+    h, w = (tensor.shape[1:3] if tensor.dtype == torch.uint8 else tensor.shape[2:])
+    nbh, nbw = (h - 2 * crop_border) // bh, (w - 2 * crop_border) // bw
+    if nbh <= 0 or nbw <= 0:
+        raise ValueError(f"NIQE needs at least one {bh}x{bw} block, got {h - 2 * crop_border}x{w - 2 * crop_border}")
+    luma = niqe_luma_native(tensor, crop_border, nbh * bh, nbw * bw)
+    feats = niqe_features_native(luma, bh, bw)
+    return _score_from_features(feats, mu_prior, cov_prior)
+
+
+class NativeNIQE(NIQE):
+    """`NIQE` on the native backend: same constructor and call; also takes uint8 [B,H,W,3] frames.  Block sizes the kernels refuse
+    are a ValueError here, at construction."""
+
+    def __init__(self, crop_border: int, niqe_model_path: str, block_size_height: int = 96, block_size_width: int = 96) -> None:
+        check_native_blocks(block_size_height, block_size_width)
+        super().__init__(crop_border, niqe_model_path, block_size_height, block_size_width)
+
+    def forward(self, raw_tensor: torch.Tensor) -> torch.Tensor:
+        as_float = raw_tensor.dtype if raw_tensor.is_floating_point() else torch.float32
+        mu = self.mu_prisparam.to(as_float).to(torch.float64)
+        cov = self.cov_prisparam.to(as_float).to(torch.float64)
+        return niqe_native(raw_tensor, self.crop_border, mu, cov, self.block_size_height, self.block_size_width)

@@ -1,7 +1,7 @@
 """Directory super-resolution on the uint8 frame path (frames.py): every image of a folder, pipelined.
 
     python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
-        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode]
+        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode --niqe]
 
 The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
 walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
@@ -16,6 +16,11 @@ network as a grey image, 16 bits in and 16 bits out -- and is written in the mod
 `.convert("RGB")`, keep going through the pipelined `FrameStream`.  `--outscale F` applies to the kept modes too
 (`upscale_image(..., outscale=F)`: frames.py, IMAGE MODES).  PIL has no 16-bit RGB or RGBA mode: those are `frames.upscale_image` on
 arrays of your own.
+
+`--niqe`: every frame of the RGB stream is scored where the last kernel wrote it -- `image_quality_assessment.niqe_native` on the uint8
+device frame, on the compute stream, before the download (crop_border = the model's factor, as test.py; the prior from
+`--niqe_model_path`) -- and the scores are read once, at the end: `NIQE <file>: <score>` per frame in input order, then
+`NIQE mean: <score>`.  Files that `--keep_mode` takes out of the RGB stream are not scored.
 """
 import argparse
 import os
@@ -91,15 +96,28 @@ def main(args) -> None:
             upscale_kept(model, image, mode, getattr(args, "outscale", None)).save(os.path.join(args.output_dir, name))
         print(f"SR image save to `{os.path.join(args.output_dir, name)}`")
 
+    scores = []         # --niqe: one device scalar per frame of the stream, in input order
+    niqe_model = None
+    if getattr(args, "niqe", False):
+        from .image_quality_assessment import NativeNIQE
+        niqe_model = NativeNIQE(config.upscale_factor, getattr(args, "niqe_model_path", None) or config.niqe_model_path).to(device=config.device)
+
     def decode():
         for name in names:
             yield np.asarray(Image.open(os.path.join(args.inputs_dir, name)).convert("RGB"))
 
     with FrameStream(model, depth=getattr(args, "depth", 2) or 2, outscale=getattr(args, "outscale", None)) as stream:
+        if niqe_model is not None:
+            stream.on_device = lambda frame: scores.append(niqe_model(frame).reshape(()))
         # copy=False: the pinned view is encoded before the next result is asked for, i.e. before its slot is submitted to again
         for name, sr_image in zip(names, stream.map(decode(), copy=False)):
             Image.fromarray(sr_image).save(os.path.join(args.output_dir, name))
             print(f"SR image save to `{os.path.join(args.output_dir, name)}`")
+    if scores:
+        values = torch.stack(scores).cpu().tolist()      # the one read-back of the scores
+        for name, value in zip(names, values):
+            print(f"NIQE {name}: {value:.6f}")
+        print(f"NIQE mean: {sum(values) / len(values):.6f}")
 
 
 def get_parser() -> argparse.ArgumentParser:
@@ -118,6 +136,9 @@ def get_parser() -> argparse.ArgumentParser:
                         help="final upscaling factor (default: the model's own); e.g. 2 writes 2x images from the x4 model")
     parser.add_argument("--keep_mode", action="store_true",
                         help="keep grey (L), RGBA (LA too) and 16-bit grey (I;16) files in their mode instead of converting them to RGB")
+    parser.add_argument("--niqe", action="store_true",
+                        help="score every RGB frame on the device (native NIQE of the uint8 result) and print the scores and their mean")
+    parser.add_argument("--niqe_model_path", type=str, default=None, help="NIQE prior (.mat); default config.niqe_model_path")
     return parser
 
 

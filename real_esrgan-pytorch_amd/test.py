@@ -15,7 +15,6 @@ from typing import List
 import torch
 
 from . import _lib, config, imgproc
-from .image_quality_assessment import NIQE
 from .compact import SRVGGNetCompact
 from .tiling import super_resolve
 
@@ -39,7 +38,7 @@ def main() -> float:
     print(f"Load Real_ESRGAN model weights `{os.path.abspath(config.model_path)}` successfully.")
     os.makedirs(config.sr_dir, exist_ok=True)
     model.eval()
-    niqe = NIQE(config.upscale_factor, config.niqe_model_path).to(device=config.device)
+    niqe = config.build_niqe()
     niqe_metrics = 0.0
     file_names = natural_sorted(os.listdir(config.lr_dir))
     total_files = len(file_names)

@@ -26,7 +26,6 @@ from .content_loss import ContentLoss
 from .dataset import CUDAPrefetcher
 from .degrade import DegradationPrefetcher
 from .discriminator import Discriminator
-from .image_quality_assessment import NIQE
 from .model import EMA, Generator  # noqa: F401  (Generator: the reference's script-level name)
 from . import train_realesrnet as _net
 from .train import DataParallel, RealESRGANStep, setup_distributed
@@ -123,7 +122,7 @@ def main() -> None:
     os.makedirs(results_dir, exist_ok=True)
     writer = ScalarWriter(os.path.join("samples", "logs", config.exp_name), enabled=rank == 0)
     scaler = torch.amp.GradScaler("cuda") if config.train_precision() != "strict" else None
-    niqe_model = NIQE(config.upscale_factor, config.niqe_model_path).to(device=config.device)
+    niqe_model = config.build_niqe()
     for epoch in range(start_epoch, config.epochs):
         sampler = getattr(train_prefetcher.original_dataloader, "sampler", None)
         if hasattr(sampler, "set_epoch"):

@@ -25,7 +25,6 @@ from . import config, imgproc
 from . import _lib
 from .dataset import CUDAPrefetcher, TestImageDataset, TrainValidImageDataset
 from .degrade import DegradationPrefetcher
-from .image_quality_assessment import NIQE
 from .meters import AverageMeter, ProgressMeter, Summary  # noqa: F401  (the reference's script-level names)
 from .compact import SRVGGNetCompact
 from .model import EMA, Generator, load_official_state_dict  # noqa: F401  (Generator: the reference's script-level name)
@@ -173,7 +172,7 @@ def main() -> None:
     os.makedirs(results_dir, exist_ok=True)
     writer = ScalarWriter(os.path.join("samples", "logs", config.exp_name), enabled=_RANK == 0)
     scaler = torch.amp.GradScaler("cuda") if config.train_precision() != "strict" else None
-    niqe_model = NIQE(config.upscale_factor, config.niqe_model_path).to(device=config.device)
+    niqe_model = config.build_niqe()
     for epoch in range(start_epoch, config.epochs):
         sampler = getattr(train_prefetcher.original_dataloader, "sampler", None)
         if hasattr(sampler, "set_epoch"):
