@@ -779,7 +779,8 @@ int resr_tile_batch(const uint8_t* tiles, const int32_t* index, const uint8_t* a
 int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, void* stream);
 
 /* ---- native NIQE (image_quality_assessment.niqe_native; csrc/niqe.hip): the metric up to its 36 features per block ---------
- * The tail of the score (NaN-aware mean, covariance, pinv, distance) stays in torch.  float64 wherever the torch path is float64.
+ * The tail of the score (NaN-aware mean, covariance, pinv, distance) is torch's, or resr_niqe_score's below.  float64 wherever the
+ * torch path is float64.
  * resr_niqe_luma_f32 / _u8: src fp32 [n,3,h,w] in [0,1] / uint8 [n,h,w,3] (a byte enters as (float)byte / 255.0f) -> dst uint8
  *   [n,out_h,out_w]: the luma level of source pixel (crop + y, crop + x) -- crop_border and the trim to whole blocks fused into the
  *   read.  level = rint(t) (half to even, pinned into 0..255) of the fp32 chain, every operation rounded once, no contraction:
@@ -828,6 +829,56 @@ int resr_niqe_luma_u8(const uint8_t* src, uint8_t* dst, int32_t n, int32_t h, in
                       void* stream);
 size_t resr_niqe_workspace_bytes(const ResrNiqeDesc* d);
 int resr_niqe_features(const ResrNiqeDesc* d, const uint8_t* luma, double* feats, void* stream);
+
+/* ---- native NIQE tail (image_quality_assessment.niqe_score_native; csrc/niqe.hip): features -> score, batched, on the device --------
+ * resr_niqe_score: feats float64 [n, blocks, 36] (the layout resr_niqe_features writes: the two chain with no copy) -> scores
+ *   float64 [n], the tail of image_quality_assessment._score_from_features in float64 throughout.  Two launches whatever n is, one
+ *   workgroup per image each (1024 threads, then 256); no host synchronisation, no allocation, no read-back.  Per image:
+ *   34400  mean, covariance, A.
+ *     mu_d[c] = (sum of the non-NaN entries of column c) / (their count); 0 / 0 = NaN for a column of NaNs.
+ *     ok = the rows without a NaN, m of them.  Two passes: mean_ok[c] = sum over ok / m, then cov_d[i][j] = (sum over ok of
+ *     (x[r][i] - mean_ok[i]) * (x[r][j] - mean_ok[j])) / (m - 1) -- so m = 1 gives 0 / 0 = NaN and m = 0 gives -0, as the torch tail.
+ *     A = (cov_prior + cov_d) / 2.  Only i <= j is computed; A[j][i] is a copy of A[i][j]: A is exactly symmetric.
+ *     Order of every sum (the same bits on every call): a wave takes whole rows, lane c column c.  A column sum is held by 16
+ *     threads, one per wave: wave w adds rows w, w + 16, ... in ascending order, and the 16 partial sums are then added in ascending
+ *     w.  A covariance sum is held by 5 threads (which own A[i][4k .. 4k + 3]): the centred rows pass through LDS 112 at a time,
+ *     thread g adds rows g, g + 5, ... of chunk after chunk in ascending order, each term one fused multiply-add, and the 5 partial
+ *     sums are then added in ascending g; a row that is not ok enters as an exact zero.
+ *   34500  eigen-decomposition, cut, score.
+ *     A with an entry that is not finite: the eigenvalues are NaN, the kept count 0, the score NaN.  Otherwise cyclic Jacobi on A
+ *     in LDS (leading dimension 37, so that column walks meet no bank twice), the eigenvectors accumulated from the identity.
+ *     Ordering: round robin, 35 steps per sweep, 18 disjoint pairs per step, rotated at once: in step s (0 .. 34) pair 0 is 35 with s
+ *     and pair k = 1 .. 17 is (s + k) mod 35 with (s - k) mod 35; p is the smaller index of a pair, q the larger.
+ *     Rotation of (p, q): none (c = 1, s = 0, t = 0) when a_pq^2 <= 2^-106 |a_pp a_qq| -- that is a_pq == 0, or |a_pq| <=
+ *     2^-53 sqrt(|a_pp a_qq|) -- otherwise, with d = a_qq - a_pp and h = 2 a_pq,
+ *       t = h / (d + sign(d) sqrt(d^2 + h^2))   (= sign(theta) / (|theta| + sqrt(theta^2 + 1)) for theta = d / h; sign(0) = +1),
+ *       c = rsqrt(t^2 + 1) (the device library's reciprocal square root), s = t c, and none after all if s == 0.
+ *     The step's J^T A J, every x y +- z w one multiplication and one fused multiply-add: in the pair's own block a_pp -= t a_pq,
+ *     a_qq += t a_pq, a_pq = 0 (a_pq stays when there is no rotation); in the block of pairs k1 < k2 first the columns by pair k2,
+ *       u[i][p2] = c2 a[i][p2] - s2 a[i][q2], u[i][q2] = s2 a[i][p2] + c2 a[i][q2]   for i = p1, q1,
+ *     then the rows by pair k1, a'[p1][j] = c1 u[p1][j] - s1 u[q1][j], a'[q1][j] = s1 u[p1][j] + c1 u[q1][j] for j = p2, q2; a'[j][i]
+ *     is a copy of a'[i][j].  Eigenvectors: v[r][p] = c v[r][p] - s v[r][q], v[r][q] = s v[r][p] + c v[r][q].
+ *     The loop ends after the first sweep that applied no rotation, and is capped at 30 sweeps: a matrix still rotating then
+ *     scores NaN (its eigenvalues as they stand are stored).
+ *     Cut (torch.linalg.pinv's default): eigenvalue k is kept iff |lambda_k| > 36 * 2^-52 * max |lambda|.
+ *     score = sqrt(sum over kept k, ascending, of (v_k . diff)^2 / lambda_k), diff = mu_prior - mu_d, each dot product summed in
+ *     ascending row order by one thread; a negative sum gives NaN.
+ *   workspace: resr_niqe_score_workspace_bytes(d) = n * (36 + 1296 + 36 + 1) * 8 bytes, 8-byte aligned, all float64, laid out
+ *     [mu_d [n][36] | A [n][36][36] | eigenvalues [n][36], in the order the sweeps leave them on the diagonal | kept count [n], stored
+ *     as a double]; it needs no initialisation and holds these after the call (tests read them).  The query needs no device and
+ *     returns 0, with the reason in resr_last_error(), for a descriptor whose sizes the entry refuses.
+ *   RESR_ERR_ARG before any launch, "niqe_score" in resr_last_error(): a null descriptor or pointer (feats, scores, mu_prior,
+ *   cov_prior, workspace), n < 1, blocks < 1, blocks * 36 above 2^31 - 1 (offsets inside an image are int32), a workspace smaller
+ *   than the query's answer, a pointer that is not 8-byte aligned. */
+typedef struct {
+    int32_t n, blocks;
+    const double* mu_prior;    /* [36] */
+    const double* cov_prior;   /* [36][36], row-major */
+    void* workspace;
+    size_t workspace_bytes;
+} ResrNiqeScoreDesc;
+size_t resr_niqe_score_workspace_bytes(const ResrNiqeScoreDesc* d);
+int resr_niqe_score(const ResrNiqeScoreDesc* d, const double* feats, double* scores, void* stream);
 
 /* ---- discriminator helpers (model.py:135-203) -------------------------------------------------------- */
 /* 2x2 space-to-depth of an NHWC tensor [n,h,w,c] -> [n,h/2,w/2,4c] (inverse != 0: depth-to-space) */

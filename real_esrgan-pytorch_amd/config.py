@@ -94,6 +94,13 @@ niqe_model_path = "./results/pretrained_models/niqe_model.mat"
 niqe_backend = os.environ.get("RESR_NIQE", "torch")
 if niqe_backend not in ("torch", "native"):
     raise ValueError(f"RESR_NIQE={niqe_backend!r}: expected 'torch' or 'native'")
+# The tail of the native score (features -> score): "torch" = the function `niqe()` uses, image by image; "native" = two launches for the
+# whole batch (resr_niqe_score), no host round trip.  Only the native backend has a choice.
+niqe_tail = os.environ.get("RESR_NIQE_TAIL", "torch")
+if niqe_tail not in ("torch", "native"):
+    raise ValueError(f"RESR_NIQE_TAIL={niqe_tail!r}: expected 'torch' or 'native'")
+if niqe_tail == "native" and niqe_backend != "native":
+    raise ValueError("RESR_NIQE_TAIL=native needs RESR_NIQE=native: the torch backend has no native tail")
 in_channels = 3
 out_channels = 3
 upscale_factor = 4
@@ -179,12 +186,17 @@ def build_generator(training: bool):
 
 
 def build_niqe():
-    """The NIQE module of `niqe_backend` on `device`: NIQE(upscale_factor, niqe_model_path) of the train scripts and test.py."""
+    """The NIQE module of `niqe_backend` (and `niqe_tail`) on `device`: NIQE(upscale_factor, niqe_model_path) of the train scripts and test.py."""
     from .image_quality_assessment import NIQE, NativeNIQE
     if niqe_backend not in ("torch", "native"):
         raise ValueError(f"config.niqe_backend={niqe_backend!r}: expected 'torch' or 'native'")
-    cls = NativeNIQE if niqe_backend == "native" else NIQE
-    return cls(upscale_factor, niqe_model_path).to(device=device)
+    if niqe_tail not in ("torch", "native"):
+        raise ValueError(f"config.niqe_tail={niqe_tail!r}: expected 'torch' or 'native'")
+    if niqe_backend == "native":
+        return NativeNIQE(upscale_factor, niqe_model_path, tail=niqe_tail).to(device=device)
+    if niqe_tail == "native":
+        raise ValueError("config.niqe_tail='native' needs config.niqe_backend='native': the torch backend has no native tail")
+    return NIQE(upscale_factor, niqe_model_path).to(device=device)
 
 
 def backward_options() -> dict:

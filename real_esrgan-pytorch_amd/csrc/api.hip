@@ -431,6 +431,13 @@ int resr_niqe_features(const ResrNiqeDesc* d, const uint8_t* luma, double* feats
     return niqe_features_dispatch(d, luma, feats, (hipStream_t)stream);
 }
 
+size_t resr_niqe_score_workspace_bytes(const ResrNiqeScoreDesc* d) { return niqe_score_workspace_bytes(d); }
+
+int resr_niqe_score(const ResrNiqeScoreDesc* d, const double* feats, double* scores, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return niqe_score_dispatch(d, feats, scores, (hipStream_t)stream);
+}
+
 int resr_filter2d(const float* src, float* dst, const float* kernel, int32_t n, int32_t c, int32_t h, int32_t w, int32_t kh,
                   int32_t kw, int32_t per_sample, void* stream) {
     RESR_DEVICE_SCOPE(stream);

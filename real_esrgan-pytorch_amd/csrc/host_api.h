@@ -179,6 +179,8 @@ int blur_kernels_dispatch(const double* params, int n, int K, float* dst, hipStr
 int niqe_luma_dispatch(const void* src, int u8, uint8_t* dst, int n, int h, int w, int crop, int oh, int ow, hipStream_t st);
 size_t niqe_workspace_bytes(const ResrNiqeDesc* d);
 int niqe_features_dispatch(const ResrNiqeDesc* d, const uint8_t* luma, double* feats, hipStream_t st);
+size_t niqe_score_workspace_bytes(const ResrNiqeScoreDesc* d);
+int niqe_score_dispatch(const ResrNiqeScoreDesc* d, const double* feats, double* scores, hipStream_t st);
 // ---- loss.hip.  loss, grad: outputs (grad may be null) ----
 int bce_logits_const_dispatch(const float* x, long count, float label, float weight, float* loss, float* grad, float* scratch, hipStream_t st);
 int l1_mean_dispatch(const float* a, const float* b, long count, float weight, float* loss, float* grad, float* scratch, hipStream_t st);

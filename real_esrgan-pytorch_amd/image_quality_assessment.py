@@ -4,7 +4,8 @@
 
 `niqe` / `NIQE` are plain torch in float64 on whatever device the SR batch lives on.  `niqe_native` / `NativeNIQE` (opt-in:
 `config.niqe_backend`) compute the same 36 features per block with the kernels of csrc/niqe.hip -- from a float [B,3,H,W] batch or
-straight from a uint8 [B,H,W,3] frame -- and share the tail of the score (`_score_from_features`) with `niqe`.
+straight from a uint8 [B,H,W,3] frame -- and share the tail of the score (`_score_from_features`) with `niqe`, or, with
+`tail="native"` (`config.niqe_tail`), run it as two more launches for the whole batch (`niqe_score_native`): no host round trip.
 The prior (mean / covariance of the 36 natural-scene features) is the reference's `results/pretrained_models/niqe_model.mat`; a copy of that data file is kept as a test fixture
 (`tests/golden/niqe_model.mat`).
 """
@@ -20,7 +21,7 @@ from torch import nn
 
 from . import imgproc
 
-__all__ = ["NIQE", "niqe", "NativeNIQE", "niqe_native"]
+__all__ = ["NIQE", "niqe", "NativeNIQE", "niqe_native", "niqe_score_native"]
 
 
 def _gaussian_window(size: int = 7, sigma: float = 7.0 / 6.0) -> torch.Tensor:
@@ -253,12 +254,50 @@ def niqe_features_native(luma: torch.Tensor, bh: int = 96, bw: int = 96, keep: b
     return feats, ws[:n_half].view(b, h // 2, w // 2), ws[need // 8 - 2 * b * nblk * 30:].view(2, b, nblk, 5, 6)
 
 
+def niqe_score_native(feats: torch.Tensor, mu_prior: torch.Tensor, cov_prior: torch.Tensor, keep: bool = False):
+    """`_score_from_features` as resr_niqe_score on the current stream: feats float64 [B, blocks, 36] on the device -> scores [B],
+    squeezed as `_score_from_features` squeezes them.  Two launches for the whole batch, no host synchronisation.  The priors are
+    float64 [36] and [36, 36]; tensors already on feats' device in float64 are used as they are.
+    keep=True also returns the workspace's contents as views: (scores, mu_d [B,36], A [B,36,36], eigenvalues [B,36], kept count [B])."""
+    from . import _lib
+    import ctypes as C
+    if not isinstance(feats, torch.Tensor) or not feats.is_cuda:
+        raise ValueError(f"niqe_score_native: the features must be a tensor on the device, got {getattr(feats, 'device', type(feats))}")
+    if feats.dtype != torch.float64 or feats.dim() != 3 or feats.shape[2] != 36 or feats.shape[0] < 1 or feats.shape[1] < 1:
+        raise ValueError(f"niqe_score_native: the features must be float64 [B, blocks, 36], got {feats.dtype} {tuple(feats.shape)}")
+    if mu_prior.numel() != 36 or tuple(cov_prior.shape) != (36, 36):
+        raise ValueError(f"niqe_score_native: the priors must be [36] and [36, 36], got {tuple(mu_prior.shape)} and {tuple(cov_prior.shape)}")
+    feats = feats.contiguous()
+    mu = mu_prior.to(device=feats.device, dtype=torch.float64).reshape(36).contiguous()
+    cov = cov_prior.to(device=feats.device, dtype=torch.float64).contiguous()
+    b, blocks, _ = feats.shape
+    d = _lib.NiqeScoreDesc()
+    d.n, d.blocks, d.mu_prior, d.cov_prior = b, blocks, mu.data_ptr(), cov.data_ptr()
+    need = int(_lib.lib().resr_niqe_score_workspace_bytes(d))
+    if not need:
+        raise ValueError(f"native NIQE: {_lib.lib().resr_last_error().decode()}")
+    ws = torch.empty(need // 8, dtype=torch.float64, device=feats.device)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    scores = torch.empty(b, dtype=torch.float64, device=feats.device)
+    _lib.check(_lib.lib().resr_niqe_score(C.byref(d), _lib.ptr(feats), _lib.ptr(scores), _lib.stream_ptr(feats)), "resr_niqe_score")
+    if not keep:
+        return scores.squeeze()
+    o = (0, 36 * b, (36 + 1296) * b, (36 + 1296 + 36) * b)
+    return scores.squeeze(), ws[o[0]:o[1]].view(b, 36), ws[o[1]:o[2]].view(b, 36, 36), ws[o[2]:o[3]].view(b, 36), ws[o[3]:]
+
+
+TAILS = ("torch", "native")
+
+
 def niqe_native(tensor: torch.Tensor, crop_border: int, mu_prior: torch.Tensor, cov_prior: torch.Tensor,
-                bh: int = 96, bw: int = 96) -> torch.Tensor:
+                bh: int = 96, bw: int = 96, tail: str = "torch") -> torch.Tensor:
     """`niqe` with the features computed by the kernels of csrc/niqe.hip: a float [B,3,H,W] batch in [0,1], or a uint8 [B,H,W,3]
-    batch scored without a float image ever existing.  Everything is enqueued on the current stream; the shared tail
-    (`_score_from_features`) is `niqe`'s.  The luma is the kernel's stated fp32 order (include/resr.h), which may differ from the
+    batch scored without a float image ever existing.  Everything is enqueued on the current stream; the tail is `niqe`'s
+    (`_score_from_features`, tail="torch") or `niqe_score_native` (tail="native": two launches for the batch, no host round trip).
+    The luma is the kernel's stated fp32 order (include/resr.h), which may differ from the
     torch path's matmul at a pixel whose luma lies within an fp32 rounding of a half ("Native NIQE")."""
+    if tail not in TAILS:
+        raise ValueError(f"niqe_native: tail must be 'torch' or 'native', got {tail!r}")
     check_native_blocks(bh, bw)
     if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
         raise ValueError(f"niqe_native: crop_border must be a non-negative int, got {crop_border!r}")
@@ -270,19 +309,34 @@ def niqe_native(tensor: torch.Tensor, crop_border: int, mu_prior: torch.Tensor, 
         raise ValueError(f"NIQE needs at least one {bh}x{bw} block, got {h - 2 * crop_border}x{w - 2 * crop_border}")
     luma = niqe_luma_native(tensor, crop_border, nbh * bh, nbw * bw)
     feats = niqe_features_native(luma, bh, bw)
+    if tail == "native":
+        return niqe_score_native(feats, mu_prior, cov_prior)
     return _score_from_features(feats, mu_prior, cov_prior)
 
 
 class NativeNIQE(NIQE):
     """`NIQE` on the native backend: same constructor and call; also takes uint8 [B,H,W,3] frames.  Block sizes the kernels refuse
-    are a ValueError here, at construction."""
+    are a ValueError here, at construction.  tail="native" scores through `niqe_score_native`; its priors are made once per device and
+    input precision and kept."""
 
-    def __init__(self, crop_border: int, niqe_model_path: str, block_size_height: int = 96, block_size_width: int = 96) -> None:
+    def __init__(self, crop_border: int, niqe_model_path: str, block_size_height: int = 96, block_size_width: int = 96,
+                 tail: str = "torch") -> None:
+        if tail not in TAILS:
+            raise ValueError(f"NativeNIQE: tail must be 'torch' or 'native', got {tail!r}")
         check_native_blocks(block_size_height, block_size_width)
         super().__init__(crop_border, niqe_model_path, block_size_height, block_size_width)
+        self.tail = tail
+        self._tail_priors: dict = {}
 
     def forward(self, raw_tensor: torch.Tensor) -> torch.Tensor:
         as_float = raw_tensor.dtype if raw_tensor.is_floating_point() else torch.float32
+        if self.tail == "native":
+            key = (str(raw_tensor.device), as_float)
+            priors = self._tail_priors.get(key)
+            if priors is None:
+                priors = self._tail_priors[key] = tuple(p.to(as_float).to(device=raw_tensor.device, dtype=torch.float64).contiguous()
+                                                        for p in (self.mu_prisparam, self.cov_prisparam))
+            return niqe_native(raw_tensor, self.crop_border, priors[0], priors[1], self.block_size_height, self.block_size_width, tail="native")
         mu = self.mu_prisparam.to(as_float).to(torch.float64)
         cov = self.cov_prisparam.to(as_float).to(torch.float64)
         return niqe_native(raw_tensor, self.crop_border, mu, cov, self.block_size_height, self.block_size_width)

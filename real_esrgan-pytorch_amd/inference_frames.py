@@ -1,7 +1,8 @@
 """Directory super-resolution on the uint8 frame path (frames.py): every image of a folder, pipelined.
 
     python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
-        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode --niqe]
+        [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode
+         --niqe --niqe_tail torch|native]
 
 The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
 walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
@@ -20,7 +21,9 @@ arrays of your own.
 `--niqe`: every frame of the RGB stream is scored where the last kernel wrote it -- `image_quality_assessment.niqe_native` on the uint8
 device frame, on the compute stream, before the download (crop_border = the model's factor, as test.py; the prior from
 `--niqe_model_path`) -- and the scores are read once, at the end: `NIQE <file>: <score>` per frame in input order, then
-`NIQE mean: <score>`.  Files that `--keep_mode` takes out of the RGB stream are not scored.
+`NIQE mean: <score>`.  Files that `--keep_mode` takes out of the RGB stream are not scored.  `--niqe_tail native` (default `torch`)
+turns the features into the score on the device too (`niqe_score_native`): a frame's score is enqueued behind its features and the
+host never waits for it before the one read at the end.
 """
 import argparse
 import os
@@ -100,7 +103,8 @@ def main(args) -> None:
     niqe_model = None
     if getattr(args, "niqe", False):
         from .image_quality_assessment import NativeNIQE
-        niqe_model = NativeNIQE(config.upscale_factor, getattr(args, "niqe_model_path", None) or config.niqe_model_path).to(device=config.device)
+        niqe_model = NativeNIQE(config.upscale_factor, getattr(args, "niqe_model_path", None) or config.niqe_model_path,
+                                tail=getattr(args, "niqe_tail", None) or "torch").to(device=config.device)
 
     def decode():
         for name in names:
@@ -139,6 +143,8 @@ def get_parser() -> argparse.ArgumentParser:
     parser.add_argument("--niqe", action="store_true",
                         help="score every RGB frame on the device (native NIQE of the uint8 result) and print the scores and their mean")
     parser.add_argument("--niqe_model_path", type=str, default=None, help="NIQE prior (.mat); default config.niqe_model_path")
+    parser.add_argument("--niqe_tail", type=str, default="torch", choices=["torch", "native"],
+                        help="--niqe: the features-to-score tail; native = on the device for the frame, no host round trip")
     return parser
 
 

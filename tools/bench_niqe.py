@@ -1,5 +1,6 @@
 """What a NIQE score costs on the device: the torch path (`image_quality_assessment.NIQE`, float64 framework ops) against the native
-path (`NativeNIQE`, csrc/niqe.hip) from a float batch and from a uint8 frame, on
+path (`NativeNIQE`, csrc/niqe.hip) from a float batch and from a uint8 frame, and against the native path with the native tail
+(`NativeNIQE(..., tail="native")`, resr_niqe_score: features -> score in two more launches, no host round trip) from a uint8 frame, on
 
     8k      one 7680 x 4320 image (the x4 result of a 1080p frame; 80 x 45 blocks of 96 x 96)
     16x1k   sixteen 1024 x 1024 images (10 x 10 blocks each)
@@ -8,10 +9,11 @@ of smooth colour fields plus grain (seeded).  The arms are alternated round by r
 arm between two device events; the figure of an arm is the median over `--rounds` rounds, its spread their minimum and maximum.  Peak
 memory is torch.cuda.max_memory_allocated over one call of the arm, above what the inputs hold.  The scores of the arms are compared
 too (the native luma is one stated fp32 order: a near-tie pixel may round the other way than torch's matmul, DESIGN "Native NIQE").
-A last, separate pass times the native launches one by one (resr_profile_*).  The yardstick is the torch path of the same run; every
-figure is recorded, whatever it is.
+A last, separate pass times the native launches one by one (resr_profile_*).  The yardstick is the torch path of the same run -- and,
+for the native tail, the native-features + torch-tail arm (`native_u8`) of the same run, never the new arm itself; every figure is
+recorded, whatever it is.  `forward_u8_ms` (3.26, DESIGN "uint8 frame path") is the frame the 8K call scores.
 
-    python tools/bench_niqe.py [--rounds 5] [--calls 3] [--niqe_model_path tests/golden/niqe_model.mat] [--out profiles/niqe.jsonl]
+    python tools/bench_niqe.py [--rounds 5] [--calls 3] [--niqe_model_path tests/golden/niqe_model.mat] [--out profiles/niqe_tail.jsonl]
 """
 import argparse
 import ctypes as C
@@ -28,8 +30,10 @@ import real_esrgan_pytorch_amd as R  # noqa: E402
 from real_esrgan_pytorch_amd.image_quality_assessment import NIQE, NativeNIQE  # noqa: E402
 
 SIZES = {"8k": (1, 4320, 7680), "16x1k": (16, 1024, 1024)}
-ARMS = ("torch", "native_f32", "native_u8")
+ARMS = ("torch", "native_f32", "native_u8", "native_u8_tail")
 STAGES = {34000: "luma_f32", 34001: "luma_u8", 34100: "half", 34200: "mscn_scale1", 34201: "mscn_scale2", 34300: "aggd"}
+TAIL_STAGES = {34400: "tail_stats", 34500: "tail_eig"}
+FORWARD_U8_MS = 3.26
 CROP = 4
 
 
@@ -63,12 +67,14 @@ def main():
         sys.exit("bench_niqe: needs the MI355X")
     torch.cuda.set_device(0)
     L = R._lib
-    modules = {"torch": NIQE(CROP, args.niqe_model_path).cuda(), "native": NativeNIQE(CROP, args.niqe_model_path).cuda()}
+    modules = {"torch": NIQE(CROP, args.niqe_model_path).cuda(), "native": NativeNIQE(CROP, args.niqe_model_path).cuda(),
+               "native_tail": NativeNIQE(CROP, args.niqe_model_path, tail="native").cuda()}
     for size, (b, h, w) in SIZES.items():
         u8 = make_frames(b, h, w)
         # (divided on the host: one IEEE division per byte, the frame path's (float)byte / 255.0f; the device's division is not correctly rounded)
         f32 = (u8.permute(0, 3, 1, 2).cpu().float() / 255.0).contiguous().cuda()
-        calls = {"torch": lambda: modules["torch"](f32), "native_f32": lambda: modules["native"](f32), "native_u8": lambda: modules["native"](u8)}
+        calls = {"torch": lambda: modules["torch"](f32), "native_f32": lambda: modules["native"](f32), "native_u8": lambda: modules["native"](u8),
+                 "native_u8_tail": lambda: modules["native_tail"](u8)}
         line = dict(tool="bench_niqe", size=size, batch=b, height=h, width=w, crop_border=CROP, block=96, rounds=args.rounds, calls=args.calls,
                     yardstick="torch (NIQE, the same run)", device=torch.cuda.get_device_name(0),
                     arch=torch.cuda.get_device_properties(0).gcnArchName.split(":")[0])
@@ -106,6 +112,22 @@ def main():
                 stages[STAGES[e.kernel_id]] = round(e.ms, 4)
         line["native_stage_ms"] = stages
         line["native_tail_ms"] = round(line["native_u8_ms"] - sum(v for k, v in stages.items() if k != "luma_f32"), 3)   # the torch tail and the gaps
+        # the native tail: its two launches, and the call against the native-features + torch-tail arm of this run
+        L.lib().resr_profile_begin()
+        calls["native_u8_tail"]()
+        torch.cuda.synchronize()
+        n = int(L.lib().resr_profile_end(C.cast(buf, C.c_void_p), 64))
+        tail = {TAIL_STAGES[e.kernel_id]: round(e.ms, 4) for e in (buf[i] for i in range(n)) if e.kernel_id in TAIL_STAGES}
+        line["native_tail_stage_ms"] = tail
+        line["native_tail_kernels_ms"] = round(sum(tail.values()), 4)
+        line["native_tail_launches"] = n
+        line["tail_yardstick"] = "native_u8 (native features + torch tail, the same run)"
+        line["native_u8_over_native_u8_tail"] = round(line["native_u8_ms"] / line["native_u8_tail_ms"], 2)
+        line["native_u8_tail_beats_native_u8_beyond_spread"] = bool(max(times["native_u8_tail"]) < min(times["native_u8"]))
+        line["native_u8_tail_vs_native_u8_score_max_rel_dev"] = float(((scores["native_u8_tail"] - scores["native_u8"]).abs() / scores["native_u8"].abs()).max())
+        line["forward_u8_ms"] = FORWARD_U8_MS
+        line["native_u8_over_forward_u8"] = round(line["native_u8_ms"] / FORWARD_U8_MS, 3)
+        line["native_u8_tail_over_forward_u8"] = round(line["native_u8_tail_ms"] / FORWARD_U8_MS, 3)
         print(json.dumps(line), flush=True)
         if args.out:
             with open(args.out, "a") as f:
