@@ -880,6 +880,52 @@ typedef struct {
 size_t resr_niqe_score_workspace_bytes(const ResrNiqeScoreDesc* d);
 int resr_niqe_score(const ResrNiqeScoreDesc* d, const double* feats, double* scores, void* stream);
 
+/* ---- native PSNR / SSIM (image_quality_assessment.full_ref_native; csrc/fullref.hip): sr against its ground truth, on the device ----
+ * resr_fullref: sr and hr, each fp32 [n,3,h,w] in [0,1] (sr_u8 / hr_u8 = 0) or uint8 [n,h,w,3] (= 1), independently -> per image
+ *   sse int64 [n], psnr float64 [n], ssim float64 [n] of the Y channel.  Two launches whatever n is, no host synchronisation, no
+ *   float64 map in memory.  crop >= 0 pixels leave on every side of both images; the rest, hc x wc = (h - 2 crop) x (w - 2 crop), must
+ *   be at least 11 x 11.
+ *   Levels: X (sr) and Y (hr) are the luma levels of resr_niqe_luma_* above (the same device function; a byte enters as
+ *     (float)byte / 255.0f), uint8 in 0..255.
+ *   PSNR: sse = sum of (X - Y)^2 over the hc * wc pixels, an exact integer; psnr = 10 * log10(65025 / (sse / (hc * wc) + 1e-8)) in
+ *     float64, each operation rounded once (identical images: 128.13 dB).
+ *   SSIM: k[i] = exp(-(i - 5)^2 / 4.5), i = 0 .. 10, divided by their sum (added for i ascending), float64, made by the host's libm.
+ *     The map has (hc - 10) x (wc - 10) values; with x, y the levels as float64, at map position (r, c) the five window sums
+ *       S_v = sum_b k[b] * (sum_a k[a] * v(r + a, c + b)),   v = x, y, x * x, y * y, x * y (exact integers),
+ *     are taken in ONE order: the inner (H) sum over a ascending and then the outer (W) sum over b ascending, each from 0.0 with one
+ *     fused multiply-add per tap.  Then, every operation rounded once and none fused,
+ *       m11 = S_x * S_x, m22 = S_y * S_y, m12 = S_x * S_y;  s11 = S_xx - m11, s22 = S_yy - m22, s12 = S_xy - m12;
+ *       value = ((2 * m12 + 6.5025) * (2 * s12 + 58.5225)) / (((m11 + m22) + 6.5025) * ((s11 + s22) + 58.5225)),
+ *     so that sr == hr gives value == 1.0, and ssim == 1.0, exactly.
+ *   34600 + sr_u8 + 2 hr_u8  fullref_tile_kernel: one workgroup of 256 threads per RESR_FULLREF_TILE x RESR_FULLREF_TILE tile of the
+ *     map of one image, tile (ty, tx) at index ty * tiles_x + tx, tiles_x = ceil((wc - 10) / 32), tiles_y = ceil((hc - 10) / 32).
+ *     Its map sum: thread t adds its values (t / 8, 4 (t % 8) + q) of the tile for q = 0 .. 3 ascending (a position outside the map
+ *     is +0.0); the 64 lanes of a wave meet in the butterfly v += shuffle_xor(v, 32), 16, 8, 4, 2, 1; the four wave sums are added in
+ *     ascending order.  Its sse: the pixels (r, c) of the cropped image with r / 32 == ty, or r >= 32 tiles_y for the last tile row, and
+ *     the same for the columns: every pixel belongs to exactly one tile.
+ *   34700  fullref_finish_kernel: one workgroup of RESR_FULLREF_FINISH_THREADS threads per image.  Thread t adds the map sums of tiles
+ *     t, t + 256, ... in ascending order from 0.0; lanes meet in the same butterfly, the wave sums are added in ascending order;
+ *     ssim = sum / ((hc - 10) * (wc - 10)).  The sse partials are added as integers.  The same input gives the same bits on every call.
+ *   workspace: resr_fullref_workspace_bytes(d) = n * tiles_y * tiles_x * 16 bytes, 8-byte aligned: per image and tile [sse uint64 |
+ *     map sum float64]; it needs no initialisation and holds these after the call (tests read them).  The query needs no device and
+ *     returns 0, with the reason in resr_last_error(), for a descriptor whose sizes the entry refuses.
+ *   RESR_ERR_ARG before any launch, "fullref" in resr_last_error(): a null descriptor or pointer (sr, hr, sse, psnr, ssim, workspace),
+ *   n, h or w < 1, crop < 0, a crop that leaves less than 11 x 11, n * tiles_y * tiles_x above 2^31 - 1 (the launch's tile index is
+ *   int32; every offset into the images is 64-bit), a workspace smaller than the query's answer, an output or workspace pointer that
+ *   is not 8-byte aligned, a float image that is not 4-byte aligned (uint8 images need no alignment at any width).
+ *   Not built: RGB-channel scoring, MS-SSIM, padding modes, windows other than 11 taps / sigma 1.5. */
+#define RESR_FULLREF_TILE 32
+#define RESR_FULLREF_FINISH_THREADS 256
+typedef struct {
+    int32_t n, h, w;           /* the images as stored, before the crop */
+    int32_t crop;
+    int32_t sr_u8, hr_u8;
+    void* workspace;
+    size_t workspace_bytes;
+} ResrFullRefDesc;
+size_t resr_fullref_workspace_bytes(const ResrFullRefDesc* d);
+int resr_fullref(const ResrFullRefDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, void* stream);
+
 /* ---- discriminator helpers (model.py:135-203) -------------------------------------------------------- */
 /* 2x2 space-to-depth of an NHWC tensor [n,h,w,c] -> [n,h/2,w/2,4c] (inverse != 0: depth-to-space) */
 int resr_space_to_depth(const void* src, void* dst, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype,

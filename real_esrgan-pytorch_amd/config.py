@@ -101,6 +101,12 @@ if niqe_tail not in ("torch", "native"):
     raise ValueError(f"RESR_NIQE_TAIL={niqe_tail!r}: expected 'torch' or 'native'")
 if niqe_tail == "native" and niqe_backend != "native":
     raise ValueError("RESR_NIQE_TAIL=native needs RESR_NIQE=native: the torch backend has no native tail")
+# Whether validate() and test.py also score SR against its ground truth (build_full_ref() below): "off" = NIQE alone, the code as it
+# was; "torch" = PSNR / SSIM of the Y channel in torch float64 (`image_quality_assessment.psnr` / `ssim`); "native" = `NativeFullRef`,
+# both in one pass of csrc/fullref.hip.
+full_ref = os.environ.get("RESR_FULL_REF", "off")
+if full_ref not in ("off", "torch", "native"):
+    raise ValueError(f"RESR_FULL_REF={full_ref!r}: expected 'off', 'torch' or 'native'")
 in_channels = 3
 out_channels = 3
 upscale_factor = 4
@@ -197,6 +203,16 @@ def build_niqe():
     if niqe_tail == "native":
         raise ValueError("config.niqe_tail='native' needs config.niqe_backend='native': the torch backend has no native tail")
     return NIQE(upscale_factor, niqe_model_path).to(device=device)
+
+
+def build_full_ref():
+    """None for `full_ref` = "off", else a module on `device` with forward(sr, hr) -> (psnr [B], ssim [B]), crop_border = upscale_factor."""
+    from .image_quality_assessment import NativeFullRef, TorchFullRef
+    if full_ref not in ("off", "torch", "native"):
+        raise ValueError(f"config.full_ref={full_ref!r}: expected 'off', 'torch' or 'native'")
+    if full_ref == "off":
+        return None
+    return (NativeFullRef if full_ref == "native" else TorchFullRef)(upscale_factor).to(device=device)
 
 
 def backward_options() -> dict:

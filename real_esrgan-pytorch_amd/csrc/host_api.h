@@ -181,7 +181,10 @@ size_t niqe_workspace_bytes(const ResrNiqeDesc* d);
 int niqe_features_dispatch(const ResrNiqeDesc* d, const uint8_t* luma, double* feats, hipStream_t st);
 size_t niqe_score_workspace_bytes(const ResrNiqeScoreDesc* d);
 int niqe_score_dispatch(const ResrNiqeScoreDesc* d, const double* feats, double* scores, hipStream_t st);
-// ---- loss.hip.  loss, grad: outputs (grad may be null) ----
+// ---- fullref.hip: PSNR / SSIM of sr against hr (include/resr.h) ----
+size_t fullref_workspace_bytes(const ResrFullRefDesc* d);
+int fullref_dispatch(const ResrFullRefDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, hipStream_t st);
+// ---- loss.hip. loss, grad: outputs (grad may be null) ----
 int bce_logits_const_dispatch(const float* x, long count, float label, float weight, float* loss, float* grad, float* scratch, hipStream_t st);
 int l1_mean_dispatch(const float* a, const float* b, long count, float weight, float* loss, float* grad, float* scratch, hipStream_t st);
 int weighted_rows_dispatch(const float* partial, int rows, int cols, const float* coef, float* out, hipStream_t st);

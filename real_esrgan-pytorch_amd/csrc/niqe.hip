@@ -20,22 +20,12 @@
 #include <math.h>
 
 #include "host_api.h"
+#include "luma_level.h"
 
 namespace resr {
 
 // ---- luma ------------------------------------------------------------------------------------------------------------------------
-// (the pragma, not __fmul_rn / __fadd_rn: those are plain operators in this toolchain, and the build's default contraction turned
-// them into fused multiply-adds -- 37 of the 2^24 byte triples then rounded the other way)
-__device__ __forceinline__ uint8_t niqe_level(float r, float g, float b) {
-#pragma clang fp contract(off)
-    float t = r * 65.481f;
-    t = t + g * 128.553f;
-    t = t + b * 24.966f;
-    t = t + 16.0f;
-    t = rintf(t);                                   // half to even, as torch.round
-    return (uint8_t)fminf(fmaxf(t, 0.f), 255.f);    // 16..235 for inputs in [0, 1]; anything else is pinned into a byte
-}
-
+// niqe_level, unit_of_byte: luma_level.h (shared with fullref.hip)
 template <bool U8>
 __global__ __launch_bounds__(256) void niqe_luma_kernel(const void* __restrict__ src, uint8_t* __restrict__ dst, int H, int W, int crop, int oh, int ow) {
     const int x = (int)(blockIdx.x * 256u + threadIdx.x), y = (int)blockIdx.y, b = (int)blockIdx.z;
@@ -44,9 +34,9 @@ __global__ __launch_bounds__(256) void niqe_luma_kernel(const void* __restrict__
     float r, g, bl;
     if (U8) {
         const uint8_t* p = (const uint8_t*)src + ((size_t)b * plane + at) * 3;
-        r = (float)p[0] / 255.0f;    // the correctly rounded division of the build's default, as yuv.h's unit_of (all 2^24 triples are tested)
-        g = (float)p[1] / 255.0f;
-        bl = (float)p[2] / 255.0f;
+        r = unit_of_byte(p[0]);
+        g = unit_of_byte(p[1]);
+        bl = unit_of_byte(p[2]);
     } else {
         const float* p = (const float*)src + (size_t)b * 3 * plane + at;
         r = p[0];

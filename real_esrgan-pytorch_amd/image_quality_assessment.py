@@ -8,6 +8,11 @@ straight from a uint8 [B,H,W,3] frame -- and share the tail of the score (`_scor
 `tail="native"` (`config.niqe_tail`), run it as two more launches for the whole batch (`niqe_score_native`): no host round trip.
 The prior (mean / covariance of the 36 natural-scene features) is the reference's `results/pretrained_models/niqe_model.mat`; a copy of that data file is kept as a test fixture
 (`tests/golden/niqe_model.mat`).
+
+Full-reference metrics ("Native PSNR / SSIM"; the reference has none, include/resr.h is the specification): `psnr` / `ssim` /
+`PSNR` / `SSIM` score an SR batch against its ground truth on the Y channel in plain torch float64 (the "torch" backend of
+`config.full_ref`); `full_ref_native` / `NativeFullRef` compute both in one pass of csrc/fullref.hip, from float [B,3,H,W] or uint8
+[B,H,W,3] tensors on either side.  Not built: RGB-channel scoring, MS-SSIM, padding modes, windows other than 11 taps / sigma 1.5.
 """
 from __future__ import annotations
 
@@ -21,7 +26,8 @@ from torch import nn
 
 from . import imgproc
 
-__all__ = ["NIQE", "niqe", "NativeNIQE", "niqe_native", "niqe_score_native"]
+__all__ = ["NIQE", "niqe", "NativeNIQE", "niqe_native", "niqe_score_native",
+           "PSNR", "SSIM", "psnr", "ssim", "NativeFullRef", "full_ref_native"]
 
 
 def _gaussian_window(size: int = 7, sigma: float = 7.0 / 6.0) -> torch.Tensor:
@@ -340,3 +346,163 @@ class NativeNIQE(NIQE):
         mu = self.mu_prisparam.to(as_float).to(torch.float64)
         cov = self.cov_prisparam.to(as_float).to(torch.float64)
         return niqe_native(raw_tensor, self.crop_border, mu, cov, self.block_size_height, self.block_size_width)
+
+
+# ---- full-reference metrics: PSNR and SSIM of the Y channel ------------------------------------------------------------------------
+FULL_REF_WINDOW = 11       # the SSIM window: 11 taps, sigma 1.5 (Wang et al.; MATLAB / BasicSR on the Y channel)
+FULL_REF_SIGMA = 1.5
+FULL_REF_C1, FULL_REF_C2 = (0.01 * 255) ** 2, (0.03 * 255) ** 2      # 6.5025, 58.5225
+FULL_REF_BACKENDS = ("off", "torch", "native")
+
+
+def _full_ref_kind(t, name: str, who: str) -> str:
+    """"u8" for a uint8 [B,H,W,3] tensor, "float" for a floating [B,3,H,W] one; ValueError for anything else."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise ValueError(f"{who}: {name} must be a float [B,3,H,W] or a uint8 [B,H,W,3] tensor, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    if t.dtype == torch.uint8 and t.shape[3] == 3:
+        return "u8"
+    if t.is_floating_point() and t.shape[1] == 3:
+        return "float"
+    raise ValueError(f"{who}: {name} must be a float [B,3,H,W] or a uint8 [B,H,W,3] tensor, got {t.dtype} {tuple(t.shape)}")
+
+
+def _full_ref_check(sr, hr, crop_border, who: str):
+    """The checks every full-reference entry makes before any device work -> (kind of sr, kind of hr, B, H, W)."""
+    kinds = _full_ref_kind(sr, "sr", who), _full_ref_kind(hr, "hr", who)
+    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
+        raise ValueError(f"{who}: crop_border must be a non-negative int, got {crop_border!r}")
+    sizes = [(t.shape[0],) + (tuple(t.shape[1:3]) if k == "u8" else tuple(t.shape[2:])) for t, k in zip((sr, hr), kinds)]
+    if sizes[0] != sizes[1]:
+        raise ValueError(f"{who}: sr is {sizes[0][0]} images of {sizes[0][1]}x{sizes[0][2]}, hr {sizes[1][0]} of {sizes[1][1]}x{sizes[1][2]}: the shapes must match")
+    if sr.device != hr.device:
+        raise ValueError(f"{who}: sr is on {sr.device}, hr on {hr.device}: both must be on one device")
+    b, h, w = sizes[0]
+    if b < 1 or h - 2 * crop_border < FULL_REF_WINDOW or w - 2 * crop_border < FULL_REF_WINDOW:
+        raise ValueError(f"{who}: a crop of {crop_border} leaves {h - 2 * crop_border}x{w - 2 * crop_border} of {b} images of {h}x{w}; the window needs at least 11x11")
+    return kinds[0], kinds[1], b, h, w
+
+
+def _y_levels(t: torch.Tensor, kind: str, crop_border: int) -> torch.Tensor:
+    """The luma levels float64 [B,1,h,w] of the cropped batch: the luma as `niqe()` takes it, rounded to levels.  A uint8 frame enters
+    as (float)byte / 255.0f."""
+    if kind == "u8":
+        # (a tensor divisor: a Python scalar may be turned into a multiplication by its reciprocal, which is not that division)
+        t = (t.to(torch.float32) / torch.full((), 255.0, dtype=torch.float32, device=t.device)).permute(0, 3, 1, 2)
+    if crop_border > 0:
+        t = t[:, :, crop_border:-crop_border, crop_border:-crop_border]
+    return (imgproc.rgb2ycbcr_torch(t.float(), only_use_y_channel=True) * 255.0).round().clamp(0, 255).to(torch.float64)
+
+
+def _ssim_window(like: torch.Tensor) -> torch.Tensor:
+    k = torch.exp(-(torch.arange(FULL_REF_WINDOW, dtype=torch.float64) - FULL_REF_WINDOW // 2) ** 2 / (2 * FULL_REF_SIGMA ** 2))
+    k = k / k.sum()
+    return torch.outer(k, k).to(like).view(1, 1, FULL_REF_WINDOW, FULL_REF_WINDOW)
+
+
+def _psnr_of_levels(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    mse = ((x - y) ** 2).sum(dim=(1, 2, 3)) / (x.shape[2] * x.shape[3])     # integers below 2^53: the sum is exact
+    return 10.0 * torch.log10(65025.0 / (mse + 1e-8))
+
+
+def _ssim_of_levels(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    g = _ssim_window(x)
+    mu1, mu2 = F.conv2d(x, g), F.conv2d(y, g)
+    m11, m22, m12 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+    s11, s22, s12 = F.conv2d(x * x, g) - m11, F.conv2d(y * y, g) - m22, F.conv2d(x * y, g) - m12
+    value = ((2 * m12 + FULL_REF_C1) * (2 * s12 + FULL_REF_C2)) / (((m11 + m22) + FULL_REF_C1) * ((s11 + s22) + FULL_REF_C2))
+    return value.mean(dim=(1, 2, 3))
+
+
+def psnr(sr: torch.Tensor, hr: torch.Tensor, crop_border: int) -> torch.Tensor:
+    """PSNR [B] (float64) of the Y levels of sr against hr, each float [B,3,H,W] in [0,1] or uint8 [B,H,W,3]:
+    10 log10(65025 / (mean (X - Y)^2 + 1e-8)) over the image without `crop_border` pixels on every side."""
+    ks, kh, *_ = _full_ref_check(sr, hr, crop_border, "psnr")
+    return _psnr_of_levels(_y_levels(sr, ks, crop_border), _y_levels(hr, kh, crop_border))
+
+
+def ssim(sr: torch.Tensor, hr: torch.Tensor, crop_border: int) -> torch.Tensor:
+    """SSIM [B] (float64) of the Y levels of sr against hr: the mean of the 11 x 11 / sigma 1.5 Gaussian-window map, valid
+    convolution, C1 = 6.5025, C2 = 58.5225 (the MATLAB / BasicSR form)."""
+    ks, kh, *_ = _full_ref_check(sr, hr, crop_border, "ssim")
+    return _ssim_of_levels(_y_levels(sr, ks, crop_border), _y_levels(hr, kh, crop_border))
+
+
+class PSNR(nn.Module):
+    def __init__(self, crop_border: int) -> None:
+        super().__init__()
+        self.crop_border = crop_border
+
+    def forward(self, sr: torch.Tensor, hr: torch.Tensor) -> torch.Tensor:
+        return psnr(sr, hr, self.crop_border)
+
+
+class SSIM(nn.Module):
+    def __init__(self, crop_border: int) -> None:
+        super().__init__()
+        self.crop_border = crop_border
+
+    def forward(self, sr: torch.Tensor, hr: torch.Tensor) -> torch.Tensor:
+        return ssim(sr, hr, self.crop_border)
+
+
+class TorchFullRef(nn.Module):
+    """`forward(sr, hr) -> (psnr [B], ssim [B])` on the torch backend: one luma of each image for both metrics."""
+
+    def __init__(self, crop_border: int) -> None:
+        super().__init__()
+        self.crop_border = crop_border
+
+    def forward(self, sr: torch.Tensor, hr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        ks, kh, *_ = _full_ref_check(sr, hr, self.crop_border, "full_ref")
+        x, y = _y_levels(sr, ks, self.crop_border), _y_levels(hr, kh, self.crop_border)
+        return _psnr_of_levels(x, y), _ssim_of_levels(x, y)
+
+
+def full_ref_tiles(h: int, w: int) -> Tuple[int, int]:
+    """Tile rows and columns of the SSIM map of a cropped h x w image (include/resr.h, resr_fullref)."""
+    from . import _lib
+    t = _lib.RESR_FULLREF_TILE
+    return -(-(h - FULL_REF_WINDOW + 1) // t), -(-(w - FULL_REF_WINDOW + 1) // t)
+
+
+def full_ref_native(sr: torch.Tensor, hr: torch.Tensor, crop_border: int, keep: bool = False):
+    """(psnr [B], ssim [B]) in float64 by resr_fullref on the current stream: two launches for the batch, no host round trip.  sr and
+    hr are each float [B,3,H,W] in [0,1] or uint8 [B,H,W,3].  The luma is the native NIQE's (one stated fp32 order).  There is no
+    fallback onto torch: tensors that are not on the device are an error.
+    keep=True also returns sse int64 [B] and the per-tile partials as views of the workspace: (psnr, ssim, sse, tile sse int64
+    [B, tiles_y, tiles_x], tile map sums float64 [B, tiles_y, tiles_x])."""
+    from . import _lib
+    import ctypes as C
+    ks, kh, b, h, w = _full_ref_check(sr, hr, crop_border, "full_ref_native")
+    _lib.require_cuda(sr, "full_ref_native")
+    sr = (sr if ks == "u8" else sr.float()).contiguous()
+    hr = (hr if kh == "u8" else hr.float()).contiguous()
+    d = _lib.FullRefDesc()
+    d.n, d.h, d.w, d.crop, d.sr_u8, d.hr_u8 = b, h, w, crop_border, ks == "u8", kh == "u8"
+    need = int(_lib.lib().resr_fullref_workspace_bytes(d))
+    if not need:
+        raise ValueError(f"full_ref_native: {_lib.lib().resr_last_error().decode()}")
+    ws = torch.empty(need // 8, dtype=torch.int64, device=sr.device)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    sse = torch.empty(b, dtype=torch.int64, device=sr.device)
+    out = torch.empty((2, b), dtype=torch.float64, device=sr.device)
+    _lib.check(_lib.lib().resr_fullref(C.byref(d), _lib.ptr(sr), _lib.ptr(hr), _lib.ptr(sse), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.stream_ptr(sr)),
+               "resr_fullref")
+    if not keep:
+        return out[0], out[1]
+    ty, tx = full_ref_tiles(h - 2 * crop_border, w - 2 * crop_border)
+    parts = ws.view(b, ty, tx, 2)
+    return out[0], out[1], sse, parts[..., 0], parts.view(torch.float64)[..., 1]
+
+
+class NativeFullRef(nn.Module):
+    """`forward(sr, hr) -> (psnr [B], ssim [B])` through `full_ref_native`: both metrics in one pass over the two images."""
+
+    def __init__(self, crop_border: int) -> None:
+        super().__init__()
+        if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
+            raise ValueError(f"NativeFullRef: crop_border must be a non-negative int, got {crop_border!r}")
+        self.crop_border = crop_border
+
+    def forward(self, sr: torch.Tensor, hr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        return full_ref_native(sr, hr, self.crop_border)

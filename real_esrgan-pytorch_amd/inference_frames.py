@@ -2,7 +2,7 @@
 
     python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
         [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode
-         --niqe --niqe_tail torch|native]
+         --niqe --niqe_tail torch|native --reference_dir gt/]
 
 The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
 walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
@@ -24,6 +24,12 @@ device frame, on the compute stream, before the download (crop_border = the mode
 `NIQE mean: <score>`.  Files that `--keep_mode` takes out of the RGB stream are not scored.  `--niqe_tail native` (default `torch`)
 turns the features into the score on the device too (`niqe_score_native`): a frame's score is enqueued behind its features and the
 host never waits for it before the one read at the end.
+
+`--reference_dir DIR`: every frame of the RGB stream is scored against the file of the same name in DIR, uploaded as uint8 HWC --
+`image_quality_assessment.full_ref_native` (PSNR and SSIM of the Y channel, crop_border = the model's factor) on the uint8 device
+frame, on the compute stream, as `--niqe` -- and the scores are read once, at the end: `PSNR/SSIM <file>: <dB> <ssim>` per frame, then
+`PSNR/SSIM mean: ...`.  A missing reference, or one whose size is not the written image's (an `--outscale` that does not lead to the
+reference's size), is an error that names the file, raised before any frame is computed.
 """
 import argparse
 import os
@@ -106,13 +112,37 @@ def main(args) -> None:
         niqe_model = NativeNIQE(config.upscale_factor, getattr(args, "niqe_model_path", None) or config.niqe_model_path,
                                 tail=getattr(args, "niqe_tail", None) or "torch").to(device=config.device)
 
+    reference_dir = getattr(args, "reference_dir", None)
+    references, full_scores = {}, []        # --reference_dir: file name -> uint8 [1,H,W,3] host tensor; one (psnr, ssim) device pair per frame
+    if reference_dir:
+        from .frames import output_size
+        from .image_quality_assessment import full_ref_native
+        for name in names:
+            path = os.path.join(reference_dir, name)
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"--reference_dir: no reference `{path}` for `{name}`")
+            with Image.open(os.path.join(args.inputs_dir, name)) as image:
+                want = output_size(image.height, image.width, config.upscale_factor, getattr(args, "outscale", None))
+            with Image.open(path) as image:
+                if (image.height, image.width) != tuple(want):
+                    raise ValueError(f"--reference_dir: the reference `{path}` is {image.height}x{image.width}, the output for `{name}` "
+                                     f"{want[0]}x{want[1]} (--outscale must lead to the reference's size)")
+                references[name] = torch.from_numpy(np.array(image.convert("RGB")))[None]
+    pending = iter(names)                   # on_device sees the frames in input order
+
     def decode():
         for name in names:
             yield np.asarray(Image.open(os.path.join(args.inputs_dir, name)).convert("RGB"))
 
     with FrameStream(model, depth=getattr(args, "depth", 2) or 2, outscale=getattr(args, "outscale", None)) as stream:
-        if niqe_model is not None:
-            stream.on_device = lambda frame: scores.append(niqe_model(frame).reshape(()))
+        if niqe_model is not None or references:
+            def on_device(frame):
+                if niqe_model is not None:
+                    scores.append(niqe_model(frame).reshape(()))
+                if references:
+                    hr = references[next(pending)].to(device=frame.device, non_blocking=True)
+                    full_scores.append(torch.stack(full_ref_native(frame if frame.dim() == 4 else frame[None], hr, config.upscale_factor)).reshape(2))
+            stream.on_device = on_device
         # copy=False: the pinned view is encoded before the next result is asked for, i.e. before its slot is submitted to again
         for name, sr_image in zip(names, stream.map(decode(), copy=False)):
             Image.fromarray(sr_image).save(os.path.join(args.output_dir, name))
@@ -122,6 +152,11 @@ def main(args) -> None:
         for name, value in zip(names, values):
             print(f"NIQE {name}: {value:.6f}")
         print(f"NIQE mean: {sum(values) / len(values):.6f}")
+    if full_scores:
+        values = torch.stack(full_scores).cpu().tolist()      # the one read-back of these scores
+        for name, (p, q) in zip(names, values):
+            print(f"PSNR/SSIM {name}: {p:.6f} {q:.6f}")
+        print(f"PSNR/SSIM mean: {sum(v[0] for v in values) / len(values):.6f} {sum(v[1] for v in values) / len(values):.6f}")
 
 
 def get_parser() -> argparse.ArgumentParser:
@@ -145,6 +180,8 @@ def get_parser() -> argparse.ArgumentParser:
     parser.add_argument("--niqe_model_path", type=str, default=None, help="NIQE prior (.mat); default config.niqe_model_path")
     parser.add_argument("--niqe_tail", type=str, default="torch", choices=["torch", "native"],
                         help="--niqe: the features-to-score tail; native = on the device for the frame, no host round trip")
+    parser.add_argument("--reference_dir", type=str, default=None,
+                        help="ground-truth directory (same file names): PSNR / SSIM of the Y channel of every RGB frame, scored on the device")
     return parser
 
 

@@ -123,6 +123,7 @@ def main() -> None:
     writer = ScalarWriter(os.path.join("samples", "logs", config.exp_name), enabled=rank == 0)
     scaler = torch.amp.GradScaler("cuda") if config.train_precision() != "strict" else None
     niqe_model = config.build_niqe()
+    full_ref = config.build_full_ref()
     for epoch in range(start_epoch, config.epochs):
         sampler = getattr(train_prefetcher.original_dataloader, "sampler", None)
         if hasattr(sampler, "set_epoch"):
@@ -130,8 +131,8 @@ def main() -> None:
         train(discriminator, generator, ema_model, train_prefetcher, pixel_criterion, content_criterion,
               adversarial_criterion, d_optimizer, g_optimizer, epoch, scaler, writer)
         _lib.chain_health(sync=True)   # fail loudly if a chained conv launch ever gave up on a neighbouring tile
-        _ = validate(generator, ema_model, valid_prefetcher, epoch, writer, niqe_model, "Valid")
-        niqe = validate(generator, ema_model, test_prefetcher, epoch, writer, niqe_model, "Test")
+        _ = validate(generator, ema_model, valid_prefetcher, epoch, writer, niqe_model, "Valid", full_ref=full_ref)
+        niqe = validate(generator, ema_model, test_prefetcher, epoch, writer, niqe_model, "Test", full_ref=full_ref)
         print("\n")
         d_scheduler.step()
         g_scheduler.step()
