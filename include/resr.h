@@ -778,6 +778,23 @@ int resr_tile_batch(const uint8_t* tiles, const int32_t* index, const uint8_t* a
                     void* stream);
 int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, void* stream);
 
+/* ---- paired training data source (device_data.PairedDeviceSource): LR / HR pairs resident as uint8, one launch a batch ------------
+ * resr_pair_batch: for sample b with records[b] = (image, top, left, code): lr_dst[b] = the LR crop [top, top + patch) x [left, left + patch)
+ *   of image's LR side, hr_dst[b] = the HR crop [scale * top, scale * top + scale * patch) x [scale * left, ...) of its HR side, both
+ *   under the same dihedral code -- bit 0 = horizontal flip, bit 1 = vertical flip, bit 2 = transpose, applied in that order -- then
+ *   value / 255.0f, HWC -> CHW.  Bit for bit device_data.paired_sample_np.
+ *   hr_arena / lr_arena: the images of each side back to back, HWC RGB bytes, any size, sizes differing from image to image; table int64
+ *   [m,4] = (hr_offset, lr_offset, lr_h, lr_w) in bytes / pixels, image i's HR side being (scale * lr_h, scale * lr_w); records int32
+ *   [b,4]; lr_dst fp32 [b,3,patch,patch], hr_dst fp32 [b,3,scale * patch,scale * patch]; everything on the device.
+ *   ONE launch writes both outputs (a workgroup owns one 32 x 32 tile of one output image, staged through LDS so that reads and
+ *   writes are both row-contiguous); 64-bit offsets throughout, byte loads (a row starts at any address).  The kernel clamps image into
+ *   0..m-1, top / left into the image and code to 3 bits: a wrong record gives wrong values, never an access outside the arenas; the
+ *   caller refuses such records before upload (device_data.check_paired_records).  The table is trusted.
+ *   RESR_ERR_ARG before any launch: a null pointer, m, b or patch < 1, scale outside 1..4, b > 65535, scale * patch > 2^31 - 1, or
+ *   ceil(patch / 32)^2 + ceil(scale * patch / 32)^2 >= 2^31 (the grid). */
+int resr_pair_batch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int64_t* table, const int32_t* records, int32_t m, int32_t b,
+                    int32_t patch, int32_t scale, float* lr_dst, float* hr_dst, void* stream);
+
 /* ---- native NIQE (image_quality_assessment.niqe_native; csrc/niqe.hip): the metric up to its 36 features per block ---------
  * The tail of the score (NaN-aware mean, covariance, pinv, distance) is torch's, or resr_niqe_score's below.  float64 wherever the
  * torch path is float64.

@@ -85,9 +85,18 @@ pretrained_g = os.environ.get("RESR_PRETRAINED_G", "")
 # Where the train scripts' training batches come from (their load_dataset(); validation and test are the loader's either way):
 # "loader" = DataLoader workers + `dataset.CUDAPrefetcher`, the reference's host pipeline; "device" = `device_data.DeviceTileSource`,
 # the training tiles resident in HBM as uint8, augmentation and blur-kernel synthesis as two launches per batch.
+# "paired" / "paired_loader" = fine-tuning on LR / HR pairs of the user's own instead of pairs the degradation stage synthesises: the HR
+# files in `train_image_dir`, their LR partners (same names, 1 / upscale_factor the size) in `paired_lr_image_dir` ($RESR_PAIRED_LR_DIR);
+# "paired" = `device_data.PairedDeviceSource`, both sides resident in HBM as uint8 and a batch one launch; "paired_loader" =
+# `dataset.PairedImageDataset` in DataLoader workers, the fallback for a set that does not fit.  The LR patch is paired_patch() below.
+DATA_SOURCES = ("loader", "device", "paired", "paired_loader")
+PAIRED_DATA_SOURCES = ("paired", "paired_loader")
 data_source = os.environ.get("RESR_DATA_SOURCE", "loader")
-if data_source not in ("loader", "device"):
-    raise ValueError(f"RESR_DATA_SOURCE={data_source!r}: expected 'loader' or 'device'")
+if data_source not in DATA_SOURCES:
+    raise ValueError(f"RESR_DATA_SOURCE={data_source!r}: expected 'loader', 'device', 'paired' or 'paired_loader'")
+paired_lr_image_dir = os.environ.get("RESR_PAIRED_LR_DIR", "")
+if data_source in PAIRED_DATA_SOURCES and not paired_lr_image_dir:
+    raise ValueError(f"RESR_DATA_SOURCE={data_source!r} needs RESR_PAIRED_LR_DIR: the directory of the LR partners of the files in train_image_dir")
 niqe_model_path = "./results/pretrained_models/niqe_model.mat"
 # How validate() and test.py compute NIQE (build_niqe() below): "torch" = `image_quality_assessment.NIQE`, plain torch in float64;
 # "native" = `NativeNIQE`, the features by the kernels of csrc/niqe.hip (same tail, same prior; its luma is the kernels' stated fp32 order).
@@ -160,6 +169,18 @@ if mode == "test":
     sr_dir = f"./results/test/{exp_name}"
     hr_dir = "./data/Set5/GTmod12"
     model_path = "./results/pretrained_models/RealESRGAN_x4-DFO2K-678bf481.pth.tar"
+
+
+def paired_patch() -> int:
+    """The LR patch side of the paired data sources: image_size // upscale_factor (image_size stays the HR crop, as in the other modes)."""
+    if image_size < upscale_factor or image_size % upscale_factor:
+        raise ValueError(f"config.image_size={image_size} is not a multiple of upscale_factor={upscale_factor}: the paired data sources "
+                         "crop an LR patch of image_size // upscale_factor and its exact HR block")
+    return image_size // upscale_factor
+
+
+if data_source in PAIRED_DATA_SOURCES and mode in ("train_realesrnet", "train_realesrgan"):
+    paired_patch()
 
 
 def train_precision() -> str:

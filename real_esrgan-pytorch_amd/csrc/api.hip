@@ -414,6 +414,12 @@ int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, vo
     return blur_kernels_dispatch(params, n, k, dst, (hipStream_t)stream);
 }
 
+int resr_pair_batch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int64_t* table, const int32_t* records, int32_t m, int32_t b, int32_t patch,
+                    int32_t scale, float* lr_dst, float* hr_dst, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return pair_batch_dispatch(hr_arena, lr_arena, table, records, m, b, patch, scale, lr_dst, hr_dst, (hipStream_t)stream);
+}
+
 int resr_niqe_luma_f32(const float* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, int32_t crop, int32_t out_h, int32_t out_w, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return niqe_luma_dispatch(src, 0, dst, n, h, w, crop, out_h, out_w, (hipStream_t)stream);

@@ -1,7 +1,10 @@
-// data_source.hip -- the device-resident training data source (device_data.py): the two launches that make one batch.
+// data_source.hip -- the device-resident training data sources (device_data.py): the two launches that make one batch of tiles, and
+// the one launch that makes a batch of LR / HR pairs.
 //   tile_batch   : uint8 tiles [M,T,T,3] in HBM -> the batch's fp32 [B,3,T,T]: gather by index, right-angle rotation about the
 //                  integer centre (zero fill where an even side loses a row / column), horizontal / vertical flip, / 255.0f,
 //                  HWC -> CHW.  Bit for bit device_data.augment_np (the imgproc chain of dataset.py).
+//   pair_batch   : uint8 images of any size, both sides of each pair in an arena -> fp32 LR [B,3,P,P] and HR [B,3,sP,sP]: crop, the
+//                  same dihedral code on both sides, / 255.0f, HWC -> CHW.  Bit for bit device_data.paired_sample_np.
 //   blur_kernels : one record of RESR_BLUR_RECORD doubles per kernel (include/resr.h) -> fp32 [n,K,K]: the float64 synthesis of
 //                  imgproc._kernel_of / generate_sinc_kernel, normalised, zero-padded to K, cast.  One workgroup per kernel.
 #include <math.h>
@@ -79,6 +82,89 @@ int tile_batch_dispatch(const uint8_t* tiles, const int32_t* index, const uint8_
     hipLaunchKernelGGL(tile_batch_kernel, dim3((unsigned)(tiles_x * tiles_x), (unsigned)B), dim3(256), 0, st, tiles, index, aug, dst, T, (int)tiles_x);
     prof_after(st, 33000, 0.0, (double)B * T * T * 15.0);
     RESR_CHECK_LAUNCH("tile_batch_kernel");
+    return RESR_OK;
+}
+
+// ---- pair_batch ------------------------------------------------------------------------------------------------------------------
+// The paired source (device_data.PairedDeviceSource): one launch crops, augments and converts BOTH sides of every sample.  grid.x
+// runs over the 32 x 32 tiles of the LR patch [P, P] and then over those of the HR patch [sP, sP]; grid.y is the sample.  The three
+// bits of the dihedral code are a horizontal flip, a vertical flip and a transpose of the crop, in that order, so -- as in tile_batch
+// -- the source pixels of a tile are a block of at most 32 x 32 pixels of the crop (rows and columns swap under the transpose),
+// staged through the same LDS tile.  Images have any size and start at any byte, so the arena is read byte by byte: consecutive
+// lanes on consecutive bytes of a row.  Every offset is 64-bit.
+__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : v > hi ? hi : v; }
+
+__global__ __launch_bounds__(256) void pair_batch_kernel(const uint8_t* __restrict__ hr_arena, const uint8_t* __restrict__ lr_arena,
+                                                         const int64_t* __restrict__ table, const int32_t* __restrict__ records, int M, int P,
+                                                         int scale, float* __restrict__ lr_dst, float* __restrict__ hr_dst, int lr_tiles_x,
+                                                         int hr_tiles_x) {
+    __shared__ uint8_t lds[kTileSide * kTilePitch];
+    const int b = (int)blockIdx.y;
+    const int32_t* rec = records + (size_t)b * 4;
+    // nothing of a record is trusted (check_paired_records refuses a wrong one before upload): a clamped record reads inside its image
+    const int image = min(max(rec[0], 0), M - 1);
+    const int code = rec[3] & 7;
+    const int64_t* row = table + (size_t)image * 4;
+    const int64_t lr_h = row[2], lr_w = row[3];
+    // (an image below the patch, which from_dirs refuses: the crop starts at 0 and the guard of the read keeps it inside)
+    int64_t top = clamp64(rec[1], 0, lr_h > P ? lr_h - P : 0), left = clamp64(rec[2], 0, lr_w > P ? lr_w - P : 0);
+    const unsigned lr_tiles = (unsigned)lr_tiles_x * (unsigned)lr_tiles_x;
+    const bool is_hr = blockIdx.x >= lr_tiles;
+    const unsigned tile = is_hr ? blockIdx.x - lr_tiles : blockIdx.x;
+    const int tiles_x = is_hr ? hr_tiles_x : lr_tiles_x;
+    const int s = is_hr ? scale : 1;
+    const int N = s * P;                                                               // the side of this output
+    const int64_t H = s * lr_h, W = s * lr_w;
+    top *= s;
+    left *= s;
+    const uint8_t* src = is_hr ? hr_arena + row[0] : lr_arena + row[1];
+    float* dst = (is_hr ? hr_dst : lr_dst) + (size_t)b * 3 * (size_t)N * (size_t)N;
+    const bool hf = code & 1, vf = code & 2, tr = code & 4;
+    const int x0 = (int)(tile % (unsigned)tiles_x) * kTileSide, y0 = (int)(tile / (unsigned)tiles_x) * kTileSide;
+    const int x_end = min(x0 + kTileSide, N) - 1, y_end = min(y0 + kTileSide, N) - 1;  // last destination column / row of the tile
+    // out[y][x] = crop[vf ? N-1-y2 : y2][hf ? N-1-x2 : x2] with (y2, x2) = tr ? (x, y) : (y, x): an interval of crop rows and one of columns
+    const int r_lo = tr ? x0 : y0, r_hi = tr ? x_end : y_end, c_lo = tr ? y0 : x0, c_hi = tr ? y_end : x_end;
+    const int cy_lo = vf ? N - 1 - r_hi : r_lo, cy_hi = vf ? N - 1 - r_lo : r_hi;
+    const int cx_lo = hf ? N - 1 - c_hi : c_lo, cx_hi = hf ? N - 1 - c_lo : c_hi;
+    for (int i = (int)threadIdx.x; i < kTileSide * kTileSide * 3; i += 256) {
+        const int r = i / (kTileSide * 3), k = i - r * (kTileSide * 3);
+        const int cy = cy_lo + r, cx = cx_lo + k / 3;
+        const int64_t sy = top + cy, sx = left + cx;
+        uint8_t v = 0;
+        if (cy <= cy_hi && cx <= cx_hi && sy < H && sx < W) v = src[(sy * W + left + cx_lo) * 3 + k];
+        lds[r * kTilePitch + k] = v;
+    }
+    __syncthreads();
+    const int tx = (int)(threadIdx.x & 31u), x = x0 + tx;
+    if (x > x_end) return;
+    const size_t plane = (size_t)N * (size_t)N;
+    for (int ty = (int)(threadIdx.x >> 5); ty < kTileSide; ty += 8) {
+        const int y = y0 + ty;
+        if (y > y_end) break;
+        const int y2 = tr ? x : y, x2 = tr ? y : x;
+        const int cy = vf ? N - 1 - y2 : y2, cx = hf ? N - 1 - x2 : x2;
+        const uint8_t* p = lds + (cy - cy_lo) * kTilePitch + (cx - cx_lo) * 3;
+        float* o = dst + (size_t)y * N + x;
+        o[0] = (float)p[0] / 255.0f;
+        o[plane] = (float)p[1] / 255.0f;
+        o[2 * plane] = (float)p[2] / 255.0f;
+    }
+}
+
+int pair_batch_dispatch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int64_t* table, const int32_t* records, int M, int B, int P,
+                        int scale, float* lr_dst, float* hr_dst, hipStream_t st) {
+    if (!hr_arena || !lr_arena || !table || !records || !lr_dst || !hr_dst || M < 1 || B < 1 || P < 1 || scale < 1 || scale > 4)
+        return fail(RESR_ERR_ARG, "pair_batch: bad argument (M=%d B=%d patch=%d scale=%d, scale in 1..4)", M, B, P, scale);
+    const int64_t hr_side = (int64_t)scale * P;
+    if (B > 65535 || hr_side > 0x7fffffffLL) return fail(RESR_ERR_ARG, "pair_batch: B=%d above 65535, or scale * patch = %lld above 2^31 - 1", B, (long long)hr_side);
+    const int64_t lr_tiles_x = ((int64_t)P + kTileSide - 1) / kTileSide, hr_tiles_x = (hr_side + kTileSide - 1) / kTileSide;
+    if (lr_tiles_x * lr_tiles_x + hr_tiles_x * hr_tiles_x > 0x7fffffffLL)
+        return fail(RESR_ERR_ARG, "pair_batch: grid overflow (patch=%d scale=%d: %lld tiles a sample)", P, scale, (long long)(lr_tiles_x * lr_tiles_x + hr_tiles_x * hr_tiles_x));
+    prof_before(st);
+    hipLaunchKernelGGL(pair_batch_kernel, dim3((unsigned)(lr_tiles_x * lr_tiles_x + hr_tiles_x * hr_tiles_x), (unsigned)B), dim3(256), 0, st, hr_arena,
+                       lr_arena, table, records, M, P, scale, lr_dst, hr_dst, (int)lr_tiles_x, (int)hr_tiles_x);
+    prof_after(st, 33001, 0.0, (double)B * (double)P * P * 15.0 * (1.0 + (double)scale * scale));
+    RESR_CHECK_LAUNCH("pair_batch_kernel");
     return RESR_OK;
 }
 

@@ -175,6 +175,9 @@ int jpeg_u8_dispatch(const uint8_t* src, uint8_t* dst, const float* quality, int
 // ---- data_source.hip: a batch of the device-resident training set.  tiles [M,T,T,3] bytes, index / aug [B] on the device; params n records ----
 int tile_batch_dispatch(const uint8_t* tiles, const int32_t* index, const uint8_t* aug, int M, int B, int T, float* dst, hipStream_t st);
 int blur_kernels_dispatch(const double* params, int n, int K, float* dst, hipStream_t st);
+// a batch of LR / HR pairs: both arenas bytes, table [M,4] int64 (hr_offset, lr_offset, lr_h, lr_w), records [B,4] int32 (image, top, left, code)
+int pair_batch_dispatch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int64_t* table, const int32_t* records, int M, int B, int P, int scale,
+                        float* lr_dst, float* hr_dst, hipStream_t st);
 // ---- niqe.hip: the native NIQE stages (include/resr.h).  u8: src is uint8 [n,h,w,3], else fp32 [n,3,h,w] ----
 int niqe_luma_dispatch(const void* src, int u8, uint8_t* dst, int n, int h, int w, int crop, int oh, int ow, hipStream_t st);
 size_t niqe_workspace_bytes(const ResrNiqeDesc* d);

@@ -13,9 +13,10 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from . import imgproc
+from . import device_data, imgproc
 from .degrade import sample_blur_kernels
 
+# (the reference's list, dataset.py:27-30; PairedImageDataset and PairedPrefetcher are this project's, outside it)
 __all__ = ["TrainValidImageDataset", "TestImageDataset", "PrefetchGenerator", "PrefetchDataLoader", "CPUPrefetcher", "CUDAPrefetcher"]
 
 
@@ -71,6 +72,31 @@ class TestImageDataset(Dataset):
         return len(self.lr_image_file_names)
 
 
+class PairedImageDataset(Dataset):
+    """The loader path of the paired data source (config.data_source = "paired_loader"): LR / HR pairs of the user's own, files of
+    the same name in two directories (`device_data.paired_files`: os.listdir(hr_dir) order).  A sample is both files decoded, the
+    draws of `device_data.sample_paired_draw` and the arithmetic of `device_data.paired_sample_np` -- the definition the resident
+    source (`device_data.PairedDeviceSource`) is judged against, so at num_workers=0 both give the same batches under the same seeds.
+    `patch` is the LR patch side; the HR patch is `scale` times it."""
+
+    def __init__(self, hr_dir: str, lr_dir: str, patch: int, scale: int) -> None:
+        super().__init__()
+        self.hr_file_names, self.lr_file_names = device_data.paired_files(hr_dir, lr_dir)
+        self.patch, self.scale = int(patch), int(scale)
+
+    def __getitem__(self, batch_index: int) -> dict:
+        hr = device_data._read_tile(self.hr_file_names[batch_index])
+        lr = device_data._read_tile(self.lr_file_names[batch_index])
+        if lr.shape[0] < self.patch or lr.shape[1] < self.patch:
+            raise ValueError(f"paired dataset: {self.lr_file_names[batch_index]} is {lr.shape[1]}x{lr.shape[0]}, below the patch {self.patch}")
+        top, left, code = device_data.sample_paired_draw(lr.shape[0], lr.shape[1], self.patch)
+        lr_f, hr_f = device_data.paired_sample_np(hr, lr, top, left, code, self.patch, self.scale)
+        return {"lr": torch.from_numpy(lr_f), "hr": torch.from_numpy(hr_f)}
+
+    def __len__(self) -> int:
+        return len(self.hr_file_names)
+
+
 class CUDAPrefetcher:
     """The reference's batch source for the train / validation loops (`next()` -> batch dict or None, `reset()`, `len()`;
     reference dataset.py:271-312) as a small HBM staging pipeline: while the step of batch i runs, batch i+1 is uploaded
@@ -116,6 +142,32 @@ class CUDAPrefetcher:
 
     def __len__(self) -> int:
         return len(self.original_dataloader)
+
+
+class PairedPrefetcher:
+    """`CUDAPrefetcher` over a DataLoader of `PairedImageDataset` under `degrade.DegradationPrefetcher`'s contract, which the train
+    loops iterate: `next()` -> (lr, hr, batch) or None, batch = {"lr", "hr", "index"} with the number of the batch within the
+    pass; `reset()`, `len()`, `original_dataloader`."""
+
+    def __init__(self, dataloader: DataLoader, device: torch.device) -> None:
+        self._inner = CUDAPrefetcher(dataloader, device)
+        self.original_dataloader = dataloader
+        self._count = 0
+
+    def next(self):
+        batch = self._inner.next()
+        if batch is None:
+            return None
+        batch = {"lr": batch["lr"], "hr": batch["hr"], "index": self._count}
+        self._count += 1
+        return batch["lr"], batch["hr"], batch
+
+    def reset(self) -> None:
+        self._count = 0
+        self._inner.reset()
+
+    def __len__(self) -> int:
+        return len(self._inner)
 
 
 class PrefetchGenerator:

@@ -8,6 +8,12 @@ the loader path's batches.  `DeviceTileSource` has `dataset.CUDAPrefetcher`'s co
 Host definitions (numpy, float64 where the loader path's are): `sample_blur_params` / `blur_kernels_from_params_np` split
 `degrade.sample_blur_kernels` into its draws and its arithmetic, `sample_augment` / `augment_np` do the same for the
 `imgproc.random_rotate` / `random_horizontally_flip` / `random_vertically_flip` chain.  The kernels are judged against them.
+
+The paired source (config.data_source = "paired") feeds LR / HR pairs of the user's own instead of synthesised ones: both sides of
+every pair resident as uint8 in two arenas, a batch -- crop, dihedral augmentation, /255, HWC -> CHW of both sides -- ONE launch
+(resr_pair_batch).  `paired_sample_np` is the definition, `sample_paired_draw` the host's draws, `PairedDeviceSource` the source; it
+has `degrade.DegradationPrefetcher`'s contract, because it stands in its place in the train scripts.  The loader path over the same
+two directories is `dataset.PairedImageDataset` / `PairedPrefetcher`.
 """
 from __future__ import annotations
 
@@ -24,7 +30,8 @@ from . import _lib, imgproc
 from .config import degradation_model_parameters_dict as MODEL_P
 
 __all__ = ["sample_blur_params", "blur_kernels_from_params_np", "check_blur_records", "sample_augment", "augment_np",
-           "tile_batch", "blur_kernels", "DeviceTileSource", "RECORD", "FAMILIES"]
+           "tile_batch", "blur_kernels", "DeviceTileSource", "RECORD", "FAMILIES",
+           "paired_sample_np", "sample_paired_draw", "check_paired_records", "paired_files", "pair_batch", "PairedDeviceSource"]
 
 # One blur-kernel record: RECORD float64 words, the layout include/resr.h documents (resr_blur_kernels).
 RECORD = 8
@@ -335,6 +342,303 @@ class DeviceTileSource:
 
     def reset(self) -> None:
         self._it = iter(self._batches)
+        self._stage()
+
+    def __len__(self) -> int:
+        return len(self._batches)
+
+
+# ---- the paired source: the definition -------------------------------------------------------------------------------------------
+PAIR_SCALES = (1, 2, 3, 4)
+
+
+def paired_sample_np(hr_u8: np.ndarray, lr_u8: np.ndarray, top: int, left: int, code: int, patch: int, scale: int):
+    """THE definition of one paired sample: hr uint8 [s*h, s*w, 3] and lr uint8 [h, w, 3] -> (lr float32 [3, P, P], hr float32
+    [3, s*P, s*P]), P = patch, s = scale.  The LR crop is lr[top:top+P, left:left+P], the HR crop its `scale`-times block; both get
+    the same dihedral code -- bit 0 a horizontal flip, bit 1 a vertical flip, bit 2 a transpose, in that order --, then
+    astype(float32) / float32(255) and HWC -> CHW."""
+    hr_u8, lr_u8 = np.asarray(hr_u8), np.asarray(lr_u8)
+    top, left, code, P, s = int(top), int(left), int(code), int(patch), int(scale)
+    for name, a in (("hr", hr_u8), ("lr", lr_u8)):
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError(f"paired_sample_np: {name} must be uint8 [H, W, 3], got {a.dtype} {a.shape}")
+    h, w = lr_u8.shape[:2]
+    if s not in PAIR_SCALES or P < 1:
+        raise ValueError(f"paired_sample_np: scale {scale} outside 1..4, or patch {patch} below 1")
+    if hr_u8.shape[:2] != (s * h, s * w):
+        raise ValueError(f"paired_sample_np: hr is {hr_u8.shape[0]}x{hr_u8.shape[1]}, not {s} x the {h}x{w} lr")
+    if not (0 <= top <= h - P and 0 <= left <= w - P):
+        raise ValueError(f"paired_sample_np: the {P}x{P} crop at (top {top}, left {left}) leaves the {h}x{w} lr image")
+    if not 0 <= code < 8:
+        raise ValueError(f"paired_sample_np: code {code} outside 0..7")
+    out = []
+    for a in (lr_u8[top:top + P, left:left + P], hr_u8[s * top:s * top + s * P, s * left:s * left + s * P]):
+        if code & 1:
+            a = a[:, ::-1]
+        if code & 2:
+            a = a[::-1]
+        if code & 4:
+            a = a.transpose(1, 0, 2)
+        out.append(np.ascontiguousarray((a.astype(np.float32) / np.float32(255)).transpose(2, 0, 1)))
+    return out[0], out[1]
+
+
+def sample_paired_draw(h: int, w: int, patch: int):
+    """The host's draws of one paired sample, five from `random` in this order: top, left, then the three bits of the code."""
+    top = random.randint(0, h - patch)
+    left = random.randint(0, w - patch)
+    code = 0
+    for bit in range(3):
+        code |= (random.random() < 0.5) << bit
+    return top, left, int(code)
+
+
+def check_paired_records(records, table, patch: int) -> np.ndarray:
+    """`records` as an int32 [B, 4] array of (image, top, left, code) rows, or ValueError for what the definition excludes: an image
+    index outside 0..M-1, a crop that leaves its image, a code above 7.  `table` is the source's int64 [M, 4] = (hr_offset, lr_offset,
+    lr_h, lr_w)."""
+    rec = np.asarray(records)
+    table = np.asarray(table).reshape(-1, 4)
+    if rec.size < 4 or rec.size % 4 or not np.issubdtype(rec.dtype, np.integer):
+        raise ValueError(f"paired records: expected integer (image, top, left, code) rows, got {rec.dtype} {rec.shape}")
+    rec = rec.reshape(-1, 4).astype(np.int64)
+    M = table.shape[0]
+    image, top, left, code = rec.T
+    bad = np.flatnonzero((image < 0) | (image >= M))
+    if bad.size:
+        raise ValueError(f"paired records: image index {int(image[bad[0]])} of record {int(bad[0])} outside 0..{M - 1}")
+    h, w = table[image, 2], table[image, 3]
+    bad = np.flatnonzero((top < 0) | (top > h - patch))
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError(f"paired records: top {int(top[k])} of record {k} takes the {patch}-row crop out of image {int(image[k])} ({int(h[k])}x{int(w[k])})")
+    bad = np.flatnonzero((left < 0) | (left > w - patch))
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError(f"paired records: left {int(left[k])} of record {k} takes the {patch}-column crop out of image {int(image[k])} ({int(h[k])}x{int(w[k])})")
+    bad = np.flatnonzero((code < 0) | (code > 7))
+    if bad.size:
+        raise ValueError(f"paired records: code {int(code[bad[0]])} of record {int(bad[0])} outside 0..7")
+    return np.ascontiguousarray(rec.astype(np.int32))
+
+
+def paired_files(hr_dir: str, lr_dir: str):
+    """The pairs of two directories: files of the same name, in os.listdir(hr_dir) order, as (hr paths, lr paths).  A file of either
+    directory without its partner is a ValueError that names it."""
+    names = os.listdir(hr_dir)
+    if not names:
+        raise ValueError(f"paired data source: no files in {hr_dir}")
+    theirs = set(os.listdir(lr_dir))
+    for name in names:
+        if name not in theirs:
+            raise ValueError(f"paired data source: {os.path.join(hr_dir, name)} has no partner {os.path.join(lr_dir, name)}")
+    orphans = sorted(theirs - set(names))
+    if orphans:
+        raise ValueError(f"paired data source: {os.path.join(lr_dir, orphans[0])} has no partner {os.path.join(hr_dir, orphans[0])}")
+    return [os.path.join(hr_dir, n) for n in names], [os.path.join(lr_dir, n) for n in names]
+
+
+def _pair_table(hr_sizes, lr_sizes, names, patch: int, scale: int, max_bytes: int) -> np.ndarray:
+    """(h, w) of both sides of every pair -> the int64 [M, 4] table (hr_offset, lr_offset, lr_h, lr_w), images back to back; every
+    refusal of a set (host only) is made here and names the pair."""
+    if scale not in PAIR_SCALES or patch < 1:
+        raise ValueError(f"paired data source: scale {scale} outside 1..4, or patch {patch} below 1")
+    if not names:
+        raise ValueError("paired data source: no pairs")
+    table = np.zeros((len(names), 4), dtype=np.int64)
+    hr_off = lr_off = 0
+    for i, ((H, W), (h, w), name) in enumerate(zip(hr_sizes, lr_sizes, names)):
+        if (H, W) != (scale * h, scale * w):
+            raise ValueError(f"paired data source: {name}: the HR side is {W}x{H}, not {scale} x the {w}x{h} LR side")
+        if h < patch or w < patch:
+            raise ValueError(f"paired data source: {name}: the {w}x{h} LR side is below the patch {patch}")
+        table[i] = (hr_off, lr_off, h, w)
+        hr_off += H * W * 3
+        lr_off += h * w * 3
+    if hr_off + lr_off > max_bytes:
+        raise ValueError(f"paired data source: {len(names)} pairs are {hr_off} + {lr_off} bytes, above max_bytes={max_bytes}")
+    return table
+
+
+def pair_batch(hr_arena: torch.Tensor, lr_arena: torch.Tensor, table: torch.Tensor, records: torch.Tensor, patch: int, scale: int, out=None):
+    """resr_pair_batch on the current stream: both arenas uint8 [bytes], table int64 [M,4], records int32 [B,4] (checked by
+    check_paired_records before they were uploaded), all on one device -> (lr float32 [B,3,P,P], hr float32 [B,3,sP,sP]); `out` is
+    such a pair to write into."""
+    _lib.require_cuda(hr_arena, "pair_batch")
+    for name, a in (("hr_arena", hr_arena), ("lr_arena", lr_arena)):
+        if a.dtype != torch.uint8 or a.dim() != 1 or not a.is_contiguous() or a.device != hr_arena.device:
+            raise ValueError(f"pair_batch: {name} must be a contiguous uint8 [bytes] tensor on the device, got {a.dtype} {tuple(a.shape)}")
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4 or not table.is_contiguous() or table.device != hr_arena.device:
+        raise ValueError("pair_batch: table must be a contiguous int64 [M,4] tensor on the arenas' device")
+    if records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 4 or not records.is_contiguous() or records.device != hr_arena.device:
+        raise ValueError("pair_batch: records must be a contiguous int32 [B,4] tensor on the arenas' device")
+    M, B, P, s = int(table.shape[0]), int(records.shape[0]), int(patch), int(scale)
+    if out is None:
+        out = (torch.empty(B, 3, P, P, dtype=torch.float32, device=hr_arena.device),
+               torch.empty(B, 3, s * P, s * P, dtype=torch.float32, device=hr_arena.device))
+    lr, hr = out
+    for t, side in ((lr, P), (hr, s * P)):
+        if t.dtype != torch.float32 or tuple(t.shape) != (B, 3, side, side) or not t.is_contiguous() or t.device != hr_arena.device:
+            raise ValueError(f"pair_batch: out must be contiguous float32 [B,3,{P},{P}] and [B,3,{s * P},{s * P}] tensors on the arenas' device")
+    _lib.check(_lib.lib().resr_pair_batch(_lib.ptr(hr_arena), _lib.ptr(lr_arena), _lib.ptr(table), _lib.ptr(records), M, B, P, s, _lib.ptr(lr),
+                                          _lib.ptr(hr), _lib.stream_ptr(hr_arena)), "resr_pair_batch")
+    return lr, hr
+
+
+# ---- the paired source -----------------------------------------------------------------------------------------------------------
+def _image_size(path: str):
+    w, h = _tile_size(path)
+    return h, w
+
+
+class PairedDeviceSource:
+    """`degrade.DegradationPrefetcher`'s contract -- `next()` -> (lr, hr, batch) or None, `reset()`, `len()`,
+    `original_dataloader.sampler` -- over LR / HR pairs held on the device as uint8: the train scripts iterate it directly
+    (config.data_source = "paired"), no degradation stage in between.
+
+    `next()` returns lr f32 [B,3,P,P], hr f32 [B,3,sP,sP] and the dict {"lr", "hr", "index"}, index being the number of the batch
+    within the pass.  Batch i+1 is drawn and enqueued inside `next()` of batch i: per sample `sample_paired_draw`, in the batch's
+    order -- `dataset.PairedImageDataset.__getitem__`'s draws, so a fixed seed gives the loader path's batches at num_workers=0.
+    Per batch: one pinned upload of the records and ONE launch on the source's side stream; the consumer is ordered behind them by
+    an event, and the caching allocator is told of the consumer stream.  Nothing synchronises with the host.
+
+    The order of a pass is `sampler`'s (default: torch's RandomSampler over range(M); a DistributedSampler for world > 1), batched
+    with drop_last=True."""
+
+    def __init__(self, hr_arena: torch.Tensor, lr_arena: torch.Tensor, table: np.ndarray, batch_size: int, patch: int, scale: int, sampler=None) -> None:
+        _lib.require_cuda(hr_arena, "PairedDeviceSource")
+        _lib.require_cuda(lr_arena, "PairedDeviceSource")
+        if batch_size < 1:
+            raise ValueError(f"PairedDeviceSource: batch_size {batch_size}")
+        self.table_host = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, 4))
+        self.hr_arena, self.lr_arena = hr_arena, lr_arena
+        self.device = hr_arena.device
+        self.batch_size, self.patch, self.scale = int(batch_size), int(patch), int(scale)
+        self.M = int(self.table_host.shape[0])
+        self.table = torch.from_numpy(self.table_host).to(self.device)
+        if sampler is None:
+            sampler = torch.utils.data.RandomSampler(range(self.M))
+        self._batches = torch.utils.data.BatchSampler(sampler, self.batch_size, drop_last=True)
+        # what the epoch loops of the train scripts look at: `original_dataloader.sampler.set_epoch`
+        self.original_dataloader = types.SimpleNamespace(sampler=sampler, batch_size=self.batch_size, drop_last=True)
+        self._side = torch.cuda.Stream(device=self.device)
+        self._side.wait_stream(torch.cuda.current_stream(self.device))      # the upload of the arenas and the table
+        self._it = None
+        self._staged = None
+        self._count = 0
+        self.reset()
+
+    # -- construction --
+    @classmethod
+    def from_arrays(cls, hr_list, lr_list, batch_size: int, patch: int, scale: int, device, sampler=None, max_bytes: int = DEFAULT_MAX_BYTES):
+        """Two lists of uint8 [H,W,3] arrays, hr_list[i] being `scale` x lr_list[i] -> a source on `device`."""
+        hr_list, lr_list = [np.asarray(a) for a in hr_list], [np.asarray(a) for a in lr_list]
+        if len(hr_list) != len(lr_list):
+            raise ValueError(f"paired data source: {len(hr_list)} HR images for {len(lr_list)} LR images")
+        for i, a in enumerate(hr_list + lr_list):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"paired data source: image {i % max(1, len(hr_list))} must be uint8 [H,W,3], got {a.dtype} {a.shape}")
+        table = _pair_table([a.shape[:2] for a in hr_list], [a.shape[:2] for a in lr_list], [f"pair {i}" for i in range(len(hr_list))],
+                            patch, scale, max_bytes)
+        device = torch.device(device)
+        arenas = []
+        for images in (hr_list, lr_list):
+            host = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in images])).pin_memory()
+            arenas.append(host.to(device, non_blocking=True))
+        return cls(arenas[0], arenas[1], table, batch_size, patch, scale, sampler)
+
+    @classmethod
+    def from_dirs(cls, hr_dir: str, lr_dir: str, batch_size: int, patch: int, scale: int, device, sampler=None,
+                  max_bytes: int = DEFAULT_MAX_BYTES, chunk_bytes: int = 64 << 20):
+        """The pairs of two directories (`paired_files`) decoded once with PIL on a thread pool and moved through two pinned staging
+        buffers into the two arenas.  The headers are read first: a missing partner, an HR size that is not `scale` x the LR size, an
+        LR side below `patch` and a total above `max_bytes` are refused, by file name, before any device work."""
+        from concurrent.futures import ThreadPoolExecutor
+        device = torch.device(device)
+        hr_paths, lr_paths = paired_files(hr_dir, lr_dir)
+        workers = max(1, min(16, os.cpu_count() or 1))
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            hr_sizes, lr_sizes = list(pool.map(_image_size, hr_paths)), list(pool.map(_image_size, lr_paths))
+        table = _pair_table(hr_sizes, lr_sizes, hr_paths, patch, scale, max_bytes)
+        M = len(hr_paths)
+        jobs = {"hr": [(hr_paths[i], int(table[i, 0]), hr_sizes[i]) for i in range(M)],
+                "lr": [(lr_paths[i], int(table[i, 1]), lr_sizes[i]) for i in range(M)]}
+        totals = {side: jobs[side][-1][1] + jobs[side][-1][2][0] * jobs[side][-1][2][1] * 3 for side in jobs}
+        largest = max(h * w * 3 for h, w in hr_sizes + lr_sizes)
+        room = max(largest, min(int(chunk_bytes), max(totals.values())))
+        arenas = {side: torch.empty(totals[side], dtype=torch.uint8, device=device) for side in jobs}
+        staging = [torch.empty(room, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        free = [None, None]      # the event behind the last copy out of each staging buffer
+
+        def decode(job):
+            view, path, (h, w) = job
+            a = _read_tile(path)
+            if a.shape != (h, w, 3):
+                raise ValueError(f"paired data source: {path} decodes to {a.shape[1]}x{a.shape[0]}, its header said {w}x{h}")
+            np.copyto(view.numpy().reshape(h, w, 3), a)
+
+        k = 0
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            for side in ("hr", "lr"):
+                todo = jobs[side]
+                first = 0
+                while first < len(todo):
+                    start = todo[first][1]      # a chunk: consecutive images of the arena, as many as the staging buffer holds
+                    last = first
+                    while last < len(todo) and todo[last][1] + todo[last][2][0] * todo[last][2][1] * 3 - start <= room:
+                        last += 1
+                    end = todo[last - 1][1] + todo[last - 1][2][0] * todo[last - 1][2][1] * 3
+                    buf = staging[k % 2]
+                    if free[k % 2] is not None:
+                        free[k % 2].synchronize()       # start-up only: the buffer is read by an earlier copy
+                    list(pool.map(decode, [(buf[off - start:off - start + h * w * 3], path, (h, w)) for path, off, (h, w) in todo[first:last]]))
+                    arenas[side][start:end].copy_(buf[:end - start], non_blocking=True)
+                    free[k % 2] = torch.cuda.Event()
+                    free[k % 2].record(torch.cuda.current_stream(device))
+                    first, k = last, k + 1
+        for e in free:
+            if e is not None:
+                e.synchronize()                         # the staging buffers go back to the allocator after this
+        return cls(arenas["hr"], arenas["lr"], table, batch_size, patch, scale, sampler)
+
+    # -- the batch source --
+    def _stage(self) -> None:
+        try:
+            indices = next(self._it)
+        except StopIteration:
+            self._staged = None
+            return
+        B = self.batch_size
+        if len(indices) != B or min(indices) < 0 or max(indices) >= self.M:
+            raise IndexError(f"paired data source: the sampler gave {indices} for {self.M} pairs and batch size {B}")
+        host = torch.empty(B, 4, dtype=torch.int32, pin_memory=True)
+        rec = host.numpy()
+        for b, i in enumerate(indices):
+            rec[b, 0] = i
+            rec[b, 1:] = sample_paired_draw(int(self.table_host[i, 2]), int(self.table_host[i, 3]), self.patch)
+        check_paired_records(rec, self.table_host, self.patch)
+        with torch.cuda.stream(self._side):
+            records = host.to(self.device, non_blocking=True)
+            lr, hr = pair_batch(self.hr_arena, self.lr_arena, self.table, records, self.patch, self.scale)
+            done = torch.cuda.Event()
+            done.record(self._side)
+        self._staged = (lr, hr, {"lr": lr, "hr": hr, "index": self._count}, done)
+        self._count += 1
+
+    def next(self):
+        if self._staged is None:
+            return None
+        lr, hr, batch, done = self._staged
+        consumer = torch.cuda.current_stream(self.device)
+        consumer.wait_event(done)
+        lr.record_stream(consumer)
+        hr.record_stream(consumer)
+        self._stage()
+        return lr, hr, batch
+
+    def reset(self) -> None:
+        self._it = iter(self._batches)
+        self._count = 0
         self._stage()
 
     def __len__(self) -> int:

@@ -20,11 +20,11 @@ import torch
 from torch import nn, optim
 from torch.optim import lr_scheduler
 
-from . import config, imgproc
+from . import config, imgproc  # noqa: F401  (imgproc: a script-level name of the reference)
 from . import _lib
 from .content_loss import ContentLoss
 from .dataset import CUDAPrefetcher
-from .degrade import DegradationPrefetcher
+from .degrade import DegradationPrefetcher  # noqa: F401  (attached by train_realesrnet.train_pairs)
 from .discriminator import Discriminator
 from .model import EMA, Generator  # noqa: F401  (Generator: the reference's script-level name)
 from . import train_realesrnet as _net
@@ -160,8 +160,6 @@ def train(discriminator: nn.Module, generator: nn.Module, ema_model: nn.Module, 
           adversarial_criterion: nn.BCEWithLogitsLoss, d_optimizer: optim.Adam, g_optimizer: optim.Adam, epoch: int,
           scaler: Optional["torch.amp.GradScaler"], writer: Any) -> None:
     """Reference train_realesrgan.py:282-553."""
-    jpeg_operation = imgproc.DiffJPEG(False)
-    usm_sharpener = imgproc.USMSharp(50, 0).to(device=config.device)
     batches = len(train_prefetcher)
     names = ["pixel_loss", "content_loss", "adversarial_loss", "d_loss_hr", "d_loss_sr", "d_hr_probability", "d_sr_probability"]
     batch_time = AverageMeter("Time", ":6.3f", Summary.NONE)              # :295-309
@@ -173,9 +171,9 @@ def train(discriminator: nn.Module, generator: nn.Module, ema_model: nn.Module, 
     discriminator.train()
     generator.train()
 
-    # the second-order degradation (:330-452) one batch ahead on a side stream, under the previous batch's step
-    degraded = DegradationPrefetcher(train_prefetcher, usm_sharpener, jpeg_operation, config.upscale_factor, config.image_size,
-                                     config.device)
+    # the second-order degradation (:330-452) one batch ahead on a side stream, under the previous batch's step -- or, for
+    # config.data_source = "paired" / "paired_loader", the paired source itself: pairs of the user's own, nothing synthesised
+    degraded = _net.train_pairs(train_prefetcher)
     step = RealESRGANStep(generator, discriminator, ema_model, g_optimizer, d_optimizer, scaler, None,
                           config.pixel_weight, config.adversarial_weight, content_criterion, config.content_weight,
                           return_probabilities=True, dp=_DP)

@@ -63,33 +63,74 @@ def seed_rank(rank: int, world: int, base: int = 0) -> None:
 
 def load_dataset() -> List[CUDAPrefetcher]:
     """Reference train_realesrnet.py:131-172."""
-    train_datasets = TrainValidImageDataset(config.train_image_dir, config.image_size, config.upscale_factor, "Train",
-                                            config.degradation_model_parameters_dict)
     valid_datasets = TrainValidImageDataset(config.valid_image_dir, config.image_size, config.upscale_factor, "Valid",
                                             config.degradation_model_parameters_dict)
     test_datasets = TestImageDataset(config.test_lr_image_dir, config.test_hr_image_dir)
+    workers = config.num_workers
+    valid_dataloader = DataLoader(valid_datasets, batch_size=1, shuffle=False, num_workers=min(1, workers),
+                                  pin_memory=True, drop_last=False, persistent_workers=workers > 0)
+    test_dataloader = DataLoader(test_datasets, batch_size=1, shuffle=False, num_workers=min(1, workers),
+                                 pin_memory=True, drop_last=False, persistent_workers=workers > 0)
+    if config.data_source in config.PAIRED_DATA_SOURCES:
+        train_source = _paired_source()
+    elif config.data_source in ("loader", "device"):
+        train_source = _synthesised_source()
+    else:
+        raise ValueError(f"config.data_source={config.data_source!r}: expected one of {config.DATA_SOURCES}")
+    return [train_source, CUDAPrefetcher(valid_dataloader, config.device), CUDAPrefetcher(test_dataloader, config.device)]
+
+
+def _synthesised_source():
+    """The train source of "loader" / "device": HR tiles and their blur kernels, for `DegradationPrefetcher` to make the pairs from."""
+    train_datasets = TrainValidImageDataset(config.train_image_dir, config.image_size, config.upscale_factor, "Train",
+                                            config.degradation_model_parameters_dict)
     workers = config.num_workers
     # data parallel: every rank draws its own shard of each epoch (batch_size is per GPU, as in the reference's per-process config)
     sampler = torch.utils.data.distributed.DistributedSampler(train_datasets, _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
     train_dataloader = DataLoader(train_datasets, batch_size=config.batch_size, shuffle=sampler is None, sampler=sampler,
                                   num_workers=workers, pin_memory=True, drop_last=True, persistent_workers=workers > 0)
-    valid_dataloader = DataLoader(valid_datasets, batch_size=1, shuffle=False, num_workers=min(1, workers),
-                                  pin_memory=True, drop_last=False, persistent_workers=workers > 0)
-    test_dataloader = DataLoader(test_datasets, batch_size=1, shuffle=False, num_workers=min(1, workers),
-                                 pin_memory=True, drop_last=False, persistent_workers=workers > 0)
     if config.data_source == "device":
         # the training tiles resident in HBM, augmentation and kernel synthesis on the device (device_data.py): the same batch
         # dictionary, draws and sampler classes; the DataLoader above is never iterated (no workers start)
         from .device_data import DeviceTileSource
         count = len(train_datasets)
         sampler = torch.utils.data.distributed.DistributedSampler(range(count), _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
-        train_source = DeviceTileSource.from_dir(config.train_image_dir, config.batch_size, config.device, sampler=sampler,
-                                                 P=config.degradation_model_parameters_dict)
-    elif config.data_source == "loader":
-        train_source = CUDAPrefetcher(train_dataloader, config.device)
-    else:
-        raise ValueError(f"config.data_source={config.data_source!r}: expected 'loader' or 'device'")
-    return [train_source, CUDAPrefetcher(valid_dataloader, config.device), CUDAPrefetcher(test_dataloader, config.device)]
+        return DeviceTileSource.from_dir(config.train_image_dir, config.batch_size, config.device, sampler=sampler,
+                                         P=config.degradation_model_parameters_dict)
+    return CUDAPrefetcher(train_dataloader, config.device)
+
+
+def _paired_source():
+    """The train source of "paired" / "paired_loader": LR / HR pairs of the user's own (HR in config.train_image_dir, LR in
+    config.paired_lr_image_dir), handed out as (lr, hr, batch) -- what train() iterates, with no degradation stage in between."""
+    from .dataset import PairedImageDataset, PairedPrefetcher
+    from .device_data import PairedDeviceSource, paired_files
+    if not getattr(config, "paired_lr_image_dir", ""):
+        raise ValueError(f"config.data_source={config.data_source!r} needs config.paired_lr_image_dir (RESR_PAIRED_LR_DIR)")
+    patch, scale = config.paired_patch(), config.upscale_factor
+    if config.data_source == "paired":
+        count = len(paired_files(config.train_image_dir, config.paired_lr_image_dir)[0])
+        sampler = torch.utils.data.distributed.DistributedSampler(range(count), _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
+        return PairedDeviceSource.from_dirs(config.train_image_dir, config.paired_lr_image_dir, config.batch_size, patch, scale, config.device,
+                                            sampler=sampler)
+    train_datasets = PairedImageDataset(config.train_image_dir, config.paired_lr_image_dir, patch, scale)
+    workers = config.num_workers
+    sampler = torch.utils.data.distributed.DistributedSampler(train_datasets, _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
+    train_dataloader = DataLoader(train_datasets, batch_size=config.batch_size, shuffle=sampler is None, sampler=sampler,
+                                  num_workers=workers, pin_memory=True, drop_last=True, persistent_workers=workers > 0)
+    return PairedPrefetcher(train_dataloader, config.device)
+
+
+def train_pairs(train_prefetcher):
+    """What train() of both scripts iterates: (lr, hr, batch) items.  A paired source hands them out itself; every other source gets the
+    second-order degradation attached (reference train_realesrnet.py:262-377: host draws in the reference's order, blur kernels from
+    the dataset batch), which runs ONE BATCH AHEAD on a side stream: batch i+1's kernels are enqueued before step i is issued and run
+    under it.  No degradation kernel is launched and no degradation draw is made for a paired source."""
+    if config.data_source in config.PAIRED_DATA_SOURCES:
+        return train_prefetcher
+    jpeg_operation = imgproc.DiffJPEG(False)
+    usm_sharpener = imgproc.USMSharp(50, 0).to(device=config.device)
+    return DegradationPrefetcher(train_prefetcher, usm_sharpener, jpeg_operation, config.upscale_factor, config.image_size, config.device)
 
 
 def build_model() -> List[nn.Module]:
@@ -194,8 +235,6 @@ def main() -> None:
 def train(model: nn.Module, ema_model: nn.Module, train_prefetcher: CUDAPrefetcher, pixel_criterion: nn.L1Loss,
           optimizer: optim.Adam, epoch: int, scaler: Optional["torch.amp.GradScaler"], writer: ScalarWriter) -> None:
     """Reference train_realesrnet.py:218-413."""
-    jpeg_operation = imgproc.DiffJPEG(False)
-    usm_sharpener = imgproc.USMSharp(50, 0).to(device=config.device)
     batches = len(train_prefetcher)
     batch_time = AverageMeter("Time", ":6.3f", Summary.NONE)            # :219-224
     data_time = AverageMeter("Data", ":6.3f", Summary.NONE)
@@ -203,10 +242,7 @@ def train(model: nn.Module, ema_model: nn.Module, train_prefetcher: CUDAPrefetch
     progress = ProgressMeter(batches, [batch_time, data_time, losses], prefix=f"Epoch: [{epoch + 1}]")
     model.train()
 
-    # The second-order degradation (:262-377: host draws in the reference's order, blur kernels from the dataset batch) runs
-    # ONE BATCH AHEAD on a side stream: batch i+1's kernels are enqueued before step i is issued and run under it.
-    degraded = DegradationPrefetcher(train_prefetcher, usm_sharpener, jpeg_operation, config.upscale_factor, config.image_size,
-                                     config.device)
+    degraded = train_pairs(train_prefetcher)     # the degradation stage over the source, or the paired source itself
     step = RealESRNetStep(model, ema_model, optimizer, scaler, None)
     step.criterion = pixel_criterion
     batch_index = 0
