@@ -795,6 +795,24 @@ int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, vo
 int resr_pair_batch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int64_t* table, const int32_t* records, int32_t m, int32_t b,
                     int32_t patch, int32_t scale, float* lr_dst, float* hr_dst, void* stream);
 
+/* ---- training pair pool (device_data.PairPool): a resident queue of finished LR / HR pairs, one exchange launch a step ------------
+ * resr_pool_exchange: for sample i < b with slot = slots[i]: lr_out[i] = pool_lr[slot], then pool_lr[slot] = lr_in[i]; the same for hr.
+ *   pool_lr fp32 [q, lr_elems], pool_hr fp32 [q, hr_elems]; lr_in / lr_out fp32 [b, lr_elems], hr_in / hr_out fp32 [b, hr_elems]; slots int32
+ *   [b]; everything on the device.  Bit for bit device_data.pool_exchange_np: the payload moves as 32-bit words, never as floats, so NaN
+ *   payloads and subnormals keep their bits; there is no arithmetic.
+ *   ONE launch moves both tensors (grid.y the sample, grid.x the 16 KiB chunks of its LR and then of its HR side; a thread issues all
+ *   its loads before its stores).  16-byte loads and stores on a side whose sample size is a multiple of 4 floats and whose pool, input
+ *   and output base pointers are 16-byte aligned; word by word otherwise, the same result.  64-bit offsets throughout.
+ *   lr_out = hr_out = NULL: the stores only (device_data.pool_store_np, the fill of the pool); the pool is then not read.
+ *   An output may be exactly its input (lr_out == lr_in: the swap in place).  The slots of a call must differ from each other; the
+ *   kernel clamps a slot into 0..q-1: a wrong slot gives wrong values, never an access outside the pool, and the caller refuses such
+ *   slots before upload (device_data.check_pool_slots).
+ *   RESR_ERR_ARG before any launch: a null pointer (exactly one null output included), q, b, lr_elems or hr_elems < 1, b > q, b > 65535,
+ *   ceil(lr_elems / 4096) + ceil(hr_elems / 4096) >= 2^31 (the grid), or, on either side, an overlap among the pool, the input and the
+ *   output other than output == input. */
+int resr_pool_exchange(float* pool_lr, float* pool_hr, const float* lr_in, const float* hr_in, float* lr_out, float* hr_out, const int32_t* slots,
+                       int32_t q, int32_t b, int64_t lr_elems, int64_t hr_elems, void* stream);
+
 /* ---- native NIQE (image_quality_assessment.niqe_native; csrc/niqe.hip): the metric up to its 36 features per block ---------
  * The tail of the score (NaN-aware mean, covariance, pinv, distance) is torch's, or resr_niqe_score's below.  float64 wherever the
  * torch path is float64.

@@ -3,7 +3,7 @@
 Import as `real_esrgan_pytorch_amd` (the sibling shim package maps the importable name onto this
 directory, whose name is fixed by the project layout and is not a valid Python identifier).
 
-Contents: `model` (Generator / EMA behind the reference's nn.Module surface), `compact` (upstream's SRVGGNetCompact, forward only), `frames` (uint8 frames in, uint8 frames out: `upscale_u8`, `FrameStream`, `outscale`; YUV 4:2:0 frames: `upscale_yuv420`, 10-bit ones: `upscale_yuv420p10`; a source and a destination format of their own: `upscale_frames`, `FrameFormat`; grey, RGBA and 16-bit images: `upscale_image`), `device_data` (the training tiles resident in HBM: `DeviceTileSource`, config.data_source = "device"; LR / HR pairs of the user's own resident in HBM: `PairedDeviceSource`, config.data_source = "paired"), `_lib` (ctypes
+Contents: `model` (Generator / EMA behind the reference's nn.Module surface), `compact` (upstream's SRVGGNetCompact, forward only), `frames` (uint8 frames in, uint8 frames out: `upscale_u8`, `FrameStream`, `outscale`; YUV 4:2:0 frames: `upscale_yuv420`, 10-bit ones: `upscale_yuv420p10`; a source and a destination format of their own: `upscale_frames`, `FrameFormat`; grey, RGBA and 16-bit images: `upscale_image`), `device_data` (the training tiles resident in HBM: `DeviceTileSource`, config.data_source = "device"; LR / HR pairs of the user's own resident in HBM: `PairedDeviceSource`, config.data_source = "paired"; the training pair pool behind either: `PairPool`, config.pair_pool_size), `_lib` (ctypes
 binding of csrc/libresr_hip.so, C-ABI in include/resr.h), `csrc/` (HIP kernels + the C-ABI).
 """
 from . import _lib  # noqa: F401

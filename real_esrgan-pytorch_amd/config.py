@@ -97,6 +97,13 @@ if data_source not in DATA_SOURCES:
 paired_lr_image_dir = os.environ.get("RESR_PAIRED_LR_DIR", "")
 if data_source in PAIRED_DATA_SOURCES and not paired_lr_image_dir:
     raise ValueError(f"RESR_DATA_SOURCE={data_source!r} needs RESR_PAIRED_LR_DIR: the directory of the LR partners of the files in train_image_dir")
+# The training pair pool of the train scripts (device_data.PairPool, attached by train_realesrnet.train_pairs behind every data source):
+# 0 = off, the code as it was; Q > 0 = a resident queue of Q finished (lr, hr) pairs that each step's batch is exchanged with once it is
+# full, so that a batch mixes samples of many degradation plans.  Upstream Real-ESRGAN trains with 180 (at 12 per GPU); in a training
+# mode Q must be a multiple of batch_size (checked below, where batch_size is known).
+pair_pool_size = int(os.environ.get("RESR_PAIR_POOL", "0"))
+if pair_pool_size < 0:
+    raise ValueError(f"RESR_PAIR_POOL={pair_pool_size}: expected 0 (off) or the number of pairs the pool holds")
 niqe_model_path = "./results/pretrained_models/niqe_model.mat"
 # How validate() and test.py compute NIQE (build_niqe() below): "torch" = `image_quality_assessment.NIQE`, plain torch in float64;
 # "native" = `NativeNIQE`, the features by the kernels of csrc/niqe.hip (same tail, same prior; its luma is the kernels' stated fp32 order).
@@ -181,6 +188,19 @@ def paired_patch() -> int:
 
 if data_source in PAIRED_DATA_SOURCES and mode in ("train_realesrnet", "train_realesrgan"):
     paired_patch()
+
+
+def pair_pool() -> int:
+    """The size of the training pair pool, 0 = off: `pair_pool_size`, which must be a multiple of batch_size (the pool fills and
+    exchanges in whole batches)."""
+    if pair_pool_size < 0 or (pair_pool_size and pair_pool_size % batch_size):
+        raise ValueError(f"config.pair_pool_size={pair_pool_size} (RESR_PAIR_POOL) is not a multiple of batch_size={batch_size}: the training "
+                         "pair pool fills and exchanges in whole batches")
+    return pair_pool_size
+
+
+if mode in ("train_realesrnet", "train_realesrgan"):
+    pair_pool()
 
 
 def train_precision() -> str:

@@ -420,6 +420,12 @@ int resr_pair_batch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int6
     return pair_batch_dispatch(hr_arena, lr_arena, table, records, m, b, patch, scale, lr_dst, hr_dst, (hipStream_t)stream);
 }
 
+int resr_pool_exchange(float* pool_lr, float* pool_hr, const float* lr_in, const float* hr_in, float* lr_out, float* hr_out, const int32_t* slots, int32_t q,
+                       int32_t b, int64_t lr_elems, int64_t hr_elems, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return pool_exchange_dispatch(pool_lr, pool_hr, lr_in, hr_in, lr_out, hr_out, slots, q, b, lr_elems, hr_elems, (hipStream_t)stream);
+}
+
 int resr_niqe_luma_f32(const float* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, int32_t crop, int32_t out_h, int32_t out_w, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return niqe_luma_dispatch(src, 0, dst, n, h, w, crop, out_h, out_w, (hipStream_t)stream);

@@ -1,10 +1,12 @@
 // data_source.hip -- the device-resident training data sources (device_data.py): the two launches that make one batch of tiles, and
-// the one launch that makes a batch of LR / HR pairs.
+// the one launch that makes a batch of LR / HR pairs, and the one launch that exchanges a batch with the training pair pool.
 //   tile_batch   : uint8 tiles [M,T,T,3] in HBM -> the batch's fp32 [B,3,T,T]: gather by index, right-angle rotation about the
 //                  integer centre (zero fill where an even side loses a row / column), horizontal / vertical flip, / 255.0f,
 //                  HWC -> CHW.  Bit for bit device_data.augment_np (the imgproc chain of dataset.py).
 //   pair_batch   : uint8 images of any size, both sides of each pair in an arena -> fp32 LR [B,3,P,P] and HR [B,3,sP,sP]: crop, the
 //                  same dihedral code on both sides, / 255.0f, HWC -> CHW.  Bit for bit device_data.paired_sample_np.
+//   pool_exchange: fp32 batch LR [B,3,P,P] / HR [B,3,sP,sP] <-> slots of the resident pool [Q,...]: out[i] = pool[slots[i]], pool[slots[i]] =
+//                  in[i], both sides, 32-bit words moved.  Bit for bit device_data.pool_exchange_np / pool_store_np.
 //   blur_kernels : one record of RESR_BLUR_RECORD doubles per kernel (include/resr.h) -> fp32 [n,K,K]: the float64 synthesis of
 //                  imgproc._kernel_of / generate_sinc_kernel, normalised, zero-padded to K, cast.  One workgroup per kernel.
 #include <math.h>
@@ -165,6 +167,120 @@ int pair_batch_dispatch(const uint8_t* hr_arena, const uint8_t* lr_arena, const 
                        lr_arena, table, records, M, P, scale, lr_dst, hr_dst, (int)lr_tiles_x, (int)hr_tiles_x);
     prof_after(st, 33001, 0.0, (double)B * (double)P * P * 15.0 * (1.0 + (double)scale * scale));
     RESR_CHECK_LAUNCH("pair_batch_kernel");
+    return RESR_OK;
+}
+
+// ---- pool_exchange ---------------------------------------------------------------------------------------------------------------
+// The training pair pool (device_data.PairPool): sample i of the batch changes places with slot slots[i] of the resident pool, on
+// both sides, in ONE launch.  grid.y is the sample; grid.x runs over the chunks of the LR sample and then over those of the HR sample.
+// A chunk is kPoolChunk 32-bit words: a thread owns kPoolVecs 16-byte vectors of it (consecutive lanes on consecutive vectors), loads
+// them from in[i] and from pool[slot] -- every load before the first store, 2 * kPoolVecs * 16 bytes in flight per lane -- and stores
+// them to out[i] and pool[slot].  A side whose sample is no multiple of 4 words, or one of whose base pointers is not 16-byte aligned,
+// takes the scalar form of the same chunk: word by word, consecutive lanes on consecutive words, the same result.  The payload moves
+// as 32-bit words, never as floats.  out == nullptr stores only (the fill of the pool).  out may be in itself: a thread has read
+// every word it writes, and no other thread touches them.  Every offset is 64-bit.
+constexpr int kPoolThreads = 256;
+constexpr int kPoolVecs = 4;                                   // 16-byte vectors per thread and source
+constexpr int kPoolChunk = kPoolThreads * kPoolVecs * 4;       // 32-bit words per chunk: 16 KiB of each tensor it touches
+
+__global__ __launch_bounds__(kPoolThreads) void pool_exchange_kernel(uint32_t* pool_lr, uint32_t* pool_hr, const uint32_t* lr_in, const uint32_t* hr_in,
+                                                                     uint32_t* lr_out, uint32_t* hr_out, const int32_t* __restrict__ slots, int Q,
+                                                                     int64_t lr_elems, int64_t hr_elems, unsigned lr_chunks, int lr_vec, int hr_vec) {
+    const int b = (int)blockIdx.y;
+    // the slot is not trusted (check_pool_slots refuses a wrong one before upload): a clamped slot stays inside the pool
+    const int slot = min(max(slots[b], 0), Q - 1);
+    const bool is_hr = blockIdx.x >= lr_chunks;
+    const int64_t chunk = is_hr ? blockIdx.x - lr_chunks : blockIdx.x;
+    const int64_t elems = is_hr ? hr_elems : lr_elems;
+    const bool vec = is_hr ? hr_vec : lr_vec;
+    uint32_t* pool = (is_hr ? pool_hr : pool_lr) + (int64_t)slot * elems;
+    const uint32_t* in = (is_hr ? hr_in : lr_in) + (int64_t)b * elems;
+    uint32_t* out = is_hr ? hr_out : lr_out;
+    const bool swap = out != nullptr;
+    if (swap) out += (int64_t)b * elems;
+    if (vec) {
+        const int64_t count = elems >> 2, first = chunk * (kPoolThreads * kPoolVecs) + threadIdx.x;
+        const uint4* in4 = reinterpret_cast<const uint4*>(in);
+        uint4* pool4 = reinterpret_cast<uint4*>(pool);
+        uint4* out4 = reinterpret_cast<uint4*>(out);
+        uint4 a[kPoolVecs], p[kPoolVecs];
+#pragma unroll
+        for (int k = 0; k < kPoolVecs; ++k) {
+            const int64_t i = first + k * kPoolThreads;
+            a[k] = p[k] = make_uint4(0u, 0u, 0u, 0u);
+            if (i < count) {
+                a[k] = in4[i];
+                if (swap) p[k] = pool4[i];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kPoolVecs; ++k) {
+            const int64_t i = first + k * kPoolThreads;
+            if (i < count) {
+                if (swap) out4[i] = p[k];
+                pool4[i] = a[k];
+            }
+        }
+    } else {
+        constexpr int kWords = kPoolVecs * 4;
+        const int64_t first = chunk * kPoolChunk + threadIdx.x;
+        uint32_t a[kWords], p[kWords];
+#pragma unroll
+        for (int k = 0; k < kWords; ++k) {
+            const int64_t i = first + k * kPoolThreads;
+            a[k] = p[k] = 0u;
+            if (i < elems) {
+                a[k] = in[i];
+                if (swap) p[k] = pool[i];
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kWords; ++k) {
+            const int64_t i = first + k * kPoolThreads;
+            if (i < elems) {
+                if (swap) out[i] = p[k];
+                pool[i] = a[k];
+            }
+        }
+    }
+}
+
+// [p, p + bytes) and [q, q + bytes2) share a byte
+static bool pool_overlap(const void* p, unsigned __int128 bytes, const void* q, unsigned __int128 bytes2) {
+    const unsigned __int128 a = (uintptr_t)p, c = (uintptr_t)q;
+    return a < c + bytes2 && c < a + bytes;
+}
+
+int pool_exchange_dispatch(float* pool_lr, float* pool_hr, const float* lr_in, const float* hr_in, float* lr_out, float* hr_out, const int32_t* slots,
+                           int Q, int B, int64_t lr_elems, int64_t hr_elems, hipStream_t st) {
+    if (!pool_lr || !pool_hr || !lr_in || !hr_in || !slots || (lr_out == nullptr) != (hr_out == nullptr))
+        return fail(RESR_ERR_ARG, "pool_exchange: a null pointer (both outputs null = store only; exactly one null is refused)");
+    if (Q < 1 || B < 1 || lr_elems < 1 || hr_elems < 1 || B > Q || B > 65535)
+        return fail(RESR_ERR_ARG, "pool_exchange: bad argument (Q=%d B=%d lr_elems=%lld hr_elems=%lld; 1 <= B <= Q, B <= 65535)", Q, B, (long long)lr_elems,
+                    (long long)hr_elems);
+    // (rounded up without an addition that could overflow)
+    const int64_t lr_chunks = lr_elems / kPoolChunk + (lr_elems % kPoolChunk != 0), hr_chunks = hr_elems / kPoolChunk + (hr_elems % kPoolChunk != 0);
+    if (lr_chunks + hr_chunks > 0x7fffffffLL)
+        return fail(RESR_ERR_ARG, "pool_exchange: grid overflow (lr_elems=%lld hr_elems=%lld: above 2^31 - 1 chunks of %d words a sample)", (long long)lr_elems,
+                    (long long)hr_elems, kPoolChunk);
+    int vec[2];
+    for (int side = 0; side < 2; ++side) {
+        const void* pool = side ? (const void*)pool_hr : pool_lr;
+        const void* in = side ? (const void*)hr_in : lr_in;
+        const void* out = side ? (const void*)hr_out : lr_out;
+        const int64_t elems = side ? hr_elems : lr_elems;
+        const unsigned __int128 pool_bytes = (unsigned __int128)Q * elems * 4, batch_bytes = (unsigned __int128)B * elems * 4;
+        if (pool_overlap(pool, pool_bytes, in, batch_bytes) || (out && pool_overlap(pool, pool_bytes, out, batch_bytes)) ||
+            (out && out != in && pool_overlap(in, batch_bytes, out, batch_bytes)))
+            return fail(RESR_ERR_ARG, "pool_exchange: the %s pool, input and output overlap (an output may only be exactly its input)", side ? "hr" : "lr");
+        vec[side] = elems % 4 == 0 && (((uintptr_t)pool | (uintptr_t)in | (uintptr_t)out) & 15u) == 0;
+    }
+    prof_before(st);
+    hipLaunchKernelGGL(pool_exchange_kernel, dim3((unsigned)(lr_chunks + hr_chunks), (unsigned)B), dim3(kPoolThreads), 0, st, (uint32_t*)pool_lr,
+                       (uint32_t*)pool_hr, (const uint32_t*)lr_in, (const uint32_t*)hr_in, (uint32_t*)lr_out, (uint32_t*)hr_out, slots, Q, lr_elems, hr_elems,
+                       (unsigned)lr_chunks, vec[0], vec[1]);
+    prof_after(st, 33002, 0.0, (double)B * ((double)lr_elems + (double)hr_elems) * (lr_out ? 16.0 : 8.0));
+    RESR_CHECK_LAUNCH("pool_exchange_kernel");
     return RESR_OK;
 }
 

@@ -14,6 +14,11 @@ every pair resident as uint8 in two arenas, a batch -- crop, dihedral augmentati
 (resr_pair_batch).  `paired_sample_np` is the definition, `sample_paired_draw` the host's draws, `PairedDeviceSource` the source; it
 has `degrade.DegradationPrefetcher`'s contract, because it stands in its place in the train scripts.  The loader path over the same
 two directories is `dataset.PairedImageDataset` / `PairedPrefetcher`.
+
+The training pair pool (config.pair_pool_size > 0) stands behind whichever source hands out (lr, hr, batch): a resident queue of
+finished pairs that a step's batch is exchanged with, so that a batch mixes samples of many degradation plans.  `pool_exchange_np` /
+`pool_store_np` are the definition, `sample_pool_slots` the host's draw (from a `random.Random` of the pool's own), `PairPool` the
+wrapper; an exchange is ONE launch (resr_pool_exchange) on the consumer's stream.
 """
 from __future__ import annotations
 
@@ -31,7 +36,9 @@ from .config import degradation_model_parameters_dict as MODEL_P
 
 __all__ = ["sample_blur_params", "blur_kernels_from_params_np", "check_blur_records", "sample_augment", "augment_np",
            "tile_batch", "blur_kernels", "DeviceTileSource", "RECORD", "FAMILIES",
-           "paired_sample_np", "sample_paired_draw", "check_paired_records", "paired_files", "pair_batch", "PairedDeviceSource"]
+           "paired_sample_np", "sample_paired_draw", "check_paired_records", "paired_files", "pair_batch", "PairedDeviceSource",
+           "pool_exchange_np", "pool_store_np", "sample_pool_slots", "check_pool_slots", "pool_exchange", "pool_store", "PairPool",
+           "HostPairPool"]
 
 # One blur-kernel record: RECORD float64 words, the layout include/resr.h documents (resr_blur_kernels).
 RECORD = 8
@@ -643,3 +650,231 @@ class PairedDeviceSource:
 
     def __len__(self) -> int:
         return len(self._batches)
+
+
+# ---- the training pair pool: the definition ----------------------------------------------------------------------------------------
+# The rule (upstream Real-ESRGAN's training pair pool, restated): finished (lr, hr) pairs go into a queue of Q samples.  While fewer
+# than Q samples are stored, a batch of B is written to slots ptr..ptr+B-1, ptr += B, and handed out unchanged.  Once the pool is full,
+# every step hands out B pooled samples and stores the incoming ones in their slots.  Upstream permutes the whole pool and takes its
+# first B; the first B positions of a uniform permutation are a uniformly random ordered B-subset, which is what `sample_pool_slots`
+# draws -- so the pool here never moves, and only the B slots drawn are touched.
+POOL_DEFAULT_MAX_BYTES = 8 << 30
+
+
+def _pool_views(who: str, pool_lr, pool_hr, lr, hr, slots):
+    """The four arrays as int32 views (bits are moved) and the checked slots."""
+    arrays = []
+    for name, a in (("pool_lr", pool_lr), ("pool_hr", pool_hr), ("lr", lr), ("hr", hr)):
+        if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim < 2 or not a.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"{who}: {name} must be a C-contiguous float32 array [n, ...]")
+        arrays.append(a.view(np.int32))
+    p_lr, p_hr, b_lr, b_hr = arrays
+    if p_lr.shape[0] != p_hr.shape[0] or b_lr.shape[0] != b_hr.shape[0] or p_lr.shape[1:] != b_lr.shape[1:] or p_hr.shape[1:] != b_hr.shape[1:]:
+        raise ValueError(f"{who}: pools {pool_lr.shape} / {pool_hr.shape} do not hold samples of the batch {lr.shape} / {hr.shape}")
+    return p_lr, p_hr, b_lr, b_hr, check_pool_slots(slots, p_lr.shape[0], b_lr.shape[0])
+
+
+def pool_exchange_np(pool_lr: np.ndarray, pool_hr: np.ndarray, lr: np.ndarray, hr: np.ndarray, slots):
+    """THE definition of an exchange: for i < B, out_lr[i] = pool_lr[slots[i]], then pool_lr[slots[i]] = lr[i]; the same for hr.  Returns
+    (out_lr, out_hr) and updates the pools in place.  float32 arrays [Q, ...] and [B, ...]; bits are moved, there is no arithmetic."""
+    p_lr, p_hr, b_lr, b_hr, slots = _pool_views("pool_exchange_np", pool_lr, pool_hr, lr, hr, slots)
+    out_lr, out_hr = np.empty_like(b_lr), np.empty_like(b_hr)
+    for i, s in enumerate(slots.tolist()):
+        out_lr[i] = p_lr[s]
+        p_lr[s] = b_lr[i]
+        out_hr[i] = p_hr[s]
+        p_hr[s] = b_hr[i]
+    return out_lr.view(np.float32), out_hr.view(np.float32)
+
+
+def pool_store_np(pool_lr: np.ndarray, pool_hr: np.ndarray, lr: np.ndarray, hr: np.ndarray, slots) -> None:
+    """The fill form of `pool_exchange_np`: the stores only."""
+    p_lr, p_hr, b_lr, b_hr, slots = _pool_views("pool_store_np", pool_lr, pool_hr, lr, hr, slots)
+    for i, s in enumerate(slots.tolist()):
+        p_lr[s] = b_lr[i]
+        p_hr[s] = b_hr[i]
+
+
+def sample_pool_slots(rng: random.Random, Q: int, B: int):
+    """The host's draw of one exchange: B different slots of 0..Q-1 in a random order, from `rng` -- a `random.Random` the pool owns,
+    so `random`, `numpy.random` and torch's generators are never touched."""
+    return rng.sample(range(Q), B)
+
+
+def check_pool_slots(slots, Q: int, B: int) -> np.ndarray:
+    """`slots` as an int32 [B] array, or ValueError for what the definition excludes: a count other than B, a slot outside 0..Q-1, a
+    slot named twice.  Called before every upload."""
+    s = np.asarray(slots)
+    if s.ndim != 1 or not np.issubdtype(s.dtype, np.integer) or s.size != B:
+        raise ValueError(f"pool slots: expected {B} integer slots, got {s.dtype} {s.shape}")
+    s = s.astype(np.int64)
+    bad = np.flatnonzero((s < 0) | (s >= Q))
+    if bad.size:
+        raise ValueError(f"pool slots: slot {int(s[bad[0]])} of entry {int(bad[0])} outside 0..{Q - 1}")
+    order = np.argsort(s, kind="stable")
+    twice = np.flatnonzero(np.diff(s[order]) == 0)
+    if twice.size:
+        j, k = sorted((int(order[twice[0]]), int(order[twice[0] + 1])))
+        raise ValueError(f"pool slots: slot {int(s[j])} repeated (entries {j} and {k}): two samples of a batch cannot share a slot")
+    return np.ascontiguousarray(s.astype(np.int32))
+
+
+# ---- the training pair pool: the launch --------------------------------------------------------------------------------------------
+def _pool_launch(who: str, pool_lr, pool_hr, lr, hr, slots, out):
+    _lib.require_cuda(pool_lr, who)
+    dev = pool_lr.device
+    for name, t in (("pool_lr", pool_lr), ("pool_hr", pool_hr), ("lr", lr), ("hr", hr)) + ((("out[0]", out[0]), ("out[1]", out[1])) if out else ()):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() < 2 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{who}: {name} must be a contiguous float32 [n, ...] tensor on the pool's device")
+    Q, B = int(pool_lr.shape[0]), int(lr.shape[0])
+    if pool_hr.shape[0] != Q or hr.shape[0] != B or pool_lr.shape[1:] != lr.shape[1:] or pool_hr.shape[1:] != hr.shape[1:]:
+        raise ValueError(f"{who}: pools {tuple(pool_lr.shape)} / {tuple(pool_hr.shape)} do not hold samples of the batch {tuple(lr.shape)} / {tuple(hr.shape)}")
+    if out and (out[0].shape != lr.shape or out[1].shape != hr.shape):
+        raise ValueError(f"{who}: out must be a pair of the batch's shapes {tuple(lr.shape)} / {tuple(hr.shape)}")
+    if slots.dtype != torch.int32 or slots.dim() != 1 or slots.numel() != B or not slots.is_contiguous() or slots.device != dev:
+        raise ValueError(f"{who}: slots must be a contiguous int32 [{B}] tensor on the pool's device")
+    _lib.check(_lib.lib().resr_pool_exchange(_lib.ptr(pool_lr), _lib.ptr(pool_hr), _lib.ptr(lr), _lib.ptr(hr), _lib.ptr(out[0]) if out else None,
+                                             _lib.ptr(out[1]) if out else None, _lib.ptr(slots), Q, B, lr[0].numel(), hr[0].numel(),
+                                             _lib.stream_ptr(pool_lr)), "resr_pool_exchange")
+
+
+def pool_exchange(pool_lr: torch.Tensor, pool_hr: torch.Tensor, lr: torch.Tensor, hr: torch.Tensor, slots: torch.Tensor, out=None):
+    """resr_pool_exchange on the current stream: pools float32 [Q, ...], the batch float32 [B, ...] of the same sample shapes, slots
+    int32 [B] (checked by check_pool_slots before they were uploaded), all contiguous and on one device -> (out_lr, out_hr), what the
+    slots held; the pools now hold the batch there.  `out` is such a pair to write into; (lr, hr) itself swaps in place."""
+    if out is None:
+        out = (torch.empty_like(lr), torch.empty_like(hr))
+    _pool_launch("pool_exchange", pool_lr, pool_hr, lr, hr, slots, tuple(out))
+    return out[0], out[1]
+
+
+def pool_store(pool_lr: torch.Tensor, pool_hr: torch.Tensor, lr: torch.Tensor, hr: torch.Tensor, slots: torch.Tensor) -> None:
+    """The fill form of `pool_exchange`, the same launch with no outputs: the batch is stored in its slots, the pools are not read."""
+    _pool_launch("pool_store", pool_lr, pool_hr, lr, hr, slots, None)
+
+
+# ---- the training pair pool: the wrapper -------------------------------------------------------------------------------------------
+class PairPool:
+    """The training pair pool around a source of (lr, hr, batch) items -- `degrade.DegradationPrefetcher`, `PairedDeviceSource`,
+    `dataset.PairedPrefetcher` --, with that contract: `next()` -> (lr, hr, batch) or None, `reset()`, `len()`, and the source's
+    `original_dataloader` when it has one.
+
+    `size` samples (Q) are held on the device as fp32 [Q,3,P,P] and [Q,3,sP,sP], allocated at the first batch from that batch's shapes;
+    a later batch of another shape is a ValueError.  A size that is no multiple of the batch, a size below the batch and a byte count
+    above `max_bytes` are ValueErrors before anything is allocated.  While the pool fills, `next()` stores the source's batch in slots
+    ptr..ptr+B-1 and hands the source's own tensors out.  Once it is full, `next()` draws B slots (`sample_pool_slots`), hands out what
+    they held and stores the incoming batch there: per step one pinned upload of the checked slots and ONE launch, in line on the
+    consumer's current stream, behind the source's own hand-over.  Nothing synchronises with the host.
+
+    The third item is always the INCOMING batch's dictionary, unchanged: it describes what entered the pool in this step, not the
+    tensors handed out next to it.  A source's None ends the pass; the pool is not drained.  `reset()` resets the source and keeps the
+    pool's contents and fill pointer, `attach(source)` swaps the wrapped source and keeps them too (the train scripts make a new source
+    object every epoch).  The pool is not saved in a checkpoint.
+
+    The draws come from the pool's own `random.Random(seed)` (the train scripts pass seed + rank): `random`, `numpy.random` and
+    torch's generators are never touched, so under a fixed seed the source, and the degradation stage behind it, produce the same
+    sequence with the pool on or off."""
+
+    def __init__(self, source, size: int, seed: int = 0, max_bytes: int = POOL_DEFAULT_MAX_BYTES) -> None:
+        if int(size) < 1:
+            raise ValueError(f"pair pool: size {size} below 1")
+        self.source, self.size, self.max_bytes = source, int(size), int(max_bytes)
+        self.filled = 0                      # the fill pointer: samples stored so far, Q once the pool is full
+        self.pool_lr = self.pool_hr = None
+        self._rng = random.Random(seed)
+        self._shapes = None
+        self._home = self._last = None
+
+    @property
+    def original_dataloader(self):
+        return self.source.original_dataloader      # (AttributeError where the source has none)
+
+    def attach(self, source) -> None:
+        self.source = source
+
+    def reset(self) -> None:
+        self.source.reset()
+
+    def __len__(self) -> int:
+        return len(self.source)
+
+    # -- the rule --
+    def _admit(self, lr, hr) -> int:
+        """The batch size of a batch the pool can take; the first batch sizes the pool (every refusal before the allocation)."""
+        shapes = (tuple(lr.shape), tuple(hr.shape))
+        if lr.dtype != torch.float32 or hr.dtype != torch.float32 or len(shapes[0]) < 2 or len(shapes[1]) < 2 or shapes[0][0] != shapes[1][0] or shapes[0][0] < 1:
+            raise ValueError(f"pair pool: a batch must be float32 [B, ...] on both sides, got {lr.dtype} {shapes[0]} and {hr.dtype} {shapes[1]}")
+        B = shapes[0][0]
+        if self._shapes is None:
+            if self.size < B:
+                raise ValueError(f"pair pool: size {self.size} below the batch size {B}")
+            if self.size % B:
+                raise ValueError(f"pair pool: size {self.size} is not a multiple of the batch size {B}")
+            count = self.size * 4 * (math.prod(shapes[0][1:]) + math.prod(shapes[1][1:]))
+            if count > self.max_bytes:
+                raise ValueError(f"pair pool: {self.size} pairs of {shapes[0][1:]} and {shapes[1][1:]} float32 are {count} bytes, above max_bytes={self.max_bytes}")
+            self._allocate(lr, hr)
+            self._shapes = shapes
+        elif shapes != self._shapes:
+            raise ValueError(f"pair pool: a batch of {shapes[0]} / {shapes[1]} after the pool was sized for {self._shapes[0]} / {self._shapes[1]}")
+        return B
+
+    def next(self):
+        item = self.source.next()
+        if item is None:
+            return None
+        lr, hr, batch = item
+        B = self._admit(lr, hr)
+        if self.filled < self.size:
+            self._store(lr, hr, check_pool_slots(np.arange(self.filled, self.filled + B), self.size, B))
+            self.filled += B
+            return lr, hr, batch
+        out_lr, out_hr = self._exchange(lr, hr, check_pool_slots(sample_pool_slots(self._rng, self.size, B), self.size, B))
+        return out_lr, out_hr, batch
+
+    # -- the device: what HostPairPool replaces --
+    def _allocate(self, lr, hr) -> None:
+        _lib.require_cuda(lr, "PairPool")
+        _lib.require_cuda(hr, "PairPool")
+        self._home = torch.cuda.current_stream(lr.device)
+        self.pool_lr = torch.empty((self.size,) + tuple(lr.shape[1:]), dtype=torch.float32, device=lr.device)
+        self.pool_hr = torch.empty((self.size,) + tuple(hr.shape[1:]), dtype=torch.float32, device=hr.device)
+
+    def _launch(self, lr, hr, slots: np.ndarray, swap: bool):
+        device = self.pool_lr.device
+        consumer = torch.cuda.current_stream(device)
+        if self._last is not None:
+            consumer.wait_event(self._last)          # the pool's last exchange, on whichever stream it ran
+        if consumer != self._home:
+            self.pool_lr.record_stream(consumer)
+            self.pool_hr.record_stream(consumer)
+        host = torch.empty(slots.size, dtype=torch.int32, pin_memory=True)
+        host.numpy()[:] = slots
+        slots_dev = host.to(device, non_blocking=True)
+        lr, hr = lr.contiguous(), hr.contiguous()
+        out = pool_exchange(self.pool_lr, self.pool_hr, lr, hr, slots_dev) if swap else pool_store(self.pool_lr, self.pool_hr, lr, hr, slots_dev)
+        self._last = torch.cuda.Event()
+        self._last.record(consumer)
+        return out
+
+    def _store(self, lr, hr, slots: np.ndarray) -> None:
+        self._launch(lr, hr, slots, False)
+
+    def _exchange(self, lr, hr, slots: np.ndarray):
+        return self._launch(lr, hr, slots, True)
+
+
+class HostPairPool(PairPool):
+    """`PairPool`'s rule -- the same draws, fill and refusals -- over CPU tensors, by `pool_exchange_np` / `pool_store_np`: the mirror
+    the device pool is judged against."""
+
+    def _allocate(self, lr, hr) -> None:
+        self.pool_lr = torch.zeros((self.size,) + tuple(lr.shape[1:]), dtype=torch.float32)
+        self.pool_hr = torch.zeros((self.size,) + tuple(hr.shape[1:]), dtype=torch.float32)
+
+    def _store(self, lr, hr, slots: np.ndarray) -> None:
+        pool_store_np(self.pool_lr.numpy(), self.pool_hr.numpy(), lr.contiguous().numpy(), hr.contiguous().numpy(), slots)
+
+    def _exchange(self, lr, hr, slots: np.ndarray):
+        out_lr, out_hr = pool_exchange_np(self.pool_lr.numpy(), self.pool_hr.numpy(), lr.contiguous().numpy(), hr.contiguous().numpy(), slots)
+        return torch.from_numpy(out_lr), torch.from_numpy(out_hr)

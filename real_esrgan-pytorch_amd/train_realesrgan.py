@@ -82,6 +82,7 @@ def main() -> None:
     global _DP
     rank, world, device = setup_distributed()            # one process per GPU: cuda:LOCAL_RANK, RCCL group when WORLD_SIZE > 1
     _net._RANK, _net._WORLD = rank, world
+    _net._PAIR_POOL = None                               # a run starts with no training pair pool (train_realesrnet._pooled makes it)
     config.device = device
     _net.seed_rank(rank, world)
     start_epoch, best_niqe = 0, 100.0

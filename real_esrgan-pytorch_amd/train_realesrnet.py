@@ -125,12 +125,33 @@ def train_pairs(train_prefetcher):
     """What train() of both scripts iterates: (lr, hr, batch) items.  A paired source hands them out itself; every other source gets the
     second-order degradation attached (reference train_realesrnet.py:262-377: host draws in the reference's order, blur kernels from
     the dataset batch), which runs ONE BATCH AHEAD on a side stream: batch i+1's kernels are enqueued before step i is issued and run
-    under it.  No degradation kernel is launched and no degradation draw is made for a paired source."""
+    under it.  No degradation kernel is launched and no degradation draw is made for a paired source.  With config.pair_pool_size > 0
+    either one stands behind the process's training pair pool (`_pooled`); with 0, the default, nothing changes."""
     if config.data_source in config.PAIRED_DATA_SOURCES:
-        return train_prefetcher
+        return _pooled(train_prefetcher)
     jpeg_operation = imgproc.DiffJPEG(False)
     usm_sharpener = imgproc.USMSharp(50, 0).to(device=config.device)
-    return DegradationPrefetcher(train_prefetcher, usm_sharpener, jpeg_operation, config.upscale_factor, config.image_size, config.device)
+    return _pooled(DegradationPrefetcher(train_prefetcher, usm_sharpener, jpeg_operation, config.upscale_factor, config.image_size, config.device))
+
+
+_PAIR_POOL = None     # the process's training pair pool: train() asks for its pairs once per epoch, and the pool must outlive the epoch
+
+
+def _pooled(source):
+    """`source` itself with the pool off; else the process's `device_data.PairPool` re-attached to this epoch's source, made at the
+    first call.  Its draws come from a generator of its own, seeded with the rank (seed_rank's spirit: no two ranks draw the same
+    slots), so the source's and the degradation stage's draws are the ones they make with the pool off.  main() of either script
+    clears it when it starts: two runs in one process are independent."""
+    global _PAIR_POOL
+    size = config.pair_pool()      # (checked against the batch size again: both may have been set after import)
+    if size <= 0:
+        return source
+    from .device_data import PairPool
+    if _PAIR_POOL is None:
+        _PAIR_POOL = PairPool(source, size, seed=_RANK)
+    else:
+        _PAIR_POOL.attach(source)
+    return _PAIR_POOL
 
 
 def build_model() -> List[nn.Module]:
@@ -188,7 +209,8 @@ def save_checkpoint(epoch: int, best_niqe: float, is_best: bool, model, ema_mode
 
 
 def main() -> None:
-    global _RANK, _WORLD
+    global _RANK, _WORLD, _PAIR_POOL
+    _PAIR_POOL = None                                    # a run starts with no training pair pool: it is made at the first epoch
     _RANK, _WORLD, device = setup_distributed()          # one process per GPU: cuda:LOCAL_RANK, RCCL group when WORLD_SIZE > 1
     config.device = device
     seed_rank(_RANK, _WORLD)
