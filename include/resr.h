@@ -795,6 +795,25 @@ int resr_blur_kernels(const double* params, int32_t n, int32_t k, float* dst, vo
 int resr_pair_batch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int64_t* table, const int32_t* records, int32_t m, int32_t b,
                     int32_t patch, int32_t scale, float* lr_dst, float* hr_dst, void* stream);
 
+/* ---- whole-image training data source (device_data.ImageCropSource): images of any size resident as uint8, the crop in the launch ----
+ * resr_crop_batch: for sample b with records[b] = (image, top, left, code): dst[b] = the t x t window of that image at (top, left) under
+ *   resr_tile_batch's 16 codes (bits 0-1 = angle / 90 about the integer centre with its zero row / column at an even t, bit 2 =
+ *   horizontal flip, bit 3 = vertical flip), then value / 255.0f, HWC -> CHW.  The window is
+ *     win[y][x] = image[reflect101(top + y, h)][reflect101(left + x, w)],   reflect101(i, n) = 0 for n = 1, else with p = 2n - 2 and
+ *     j = i mod p: j below n, else p - j
+ *   -- an image below t in an axis continues below / to the right by reflection about its last pixel, for a pad of any width.  Bit for bit
+ *   device_data.crop_sample_np.
+ *   arena: the images back to back, HWC RGB bytes, any size (h, w below 2^31), starting at any byte; table int64 [m,3] = (offset in bytes,
+ *   h, w); records int32 [b,4]; dst fp32 [b,3,t,t]; everything on the device.  ONE launch (a workgroup owns one 32 x 32 tile of one
+ *   sample, staged through LDS so that reads and writes are both row-contiguous; a staged block inside the image is read row by row, one
+ *   that reaches the padding pixel by pixel through reflect101); 64-bit offsets throughout, byte loads.  The kernel clamps image into
+ *   0..m-1, top into 0..max(h, t) - t, left into 0..max(w, t) - t and reads the code's low four bits: a wrong record gives wrong values,
+ *   never an access outside the image; the caller refuses such records before upload (device_data.check_crop_records).  The table is
+ *   trusted.  Profiling id 33003.
+ *   RESR_ERR_ARG before any launch: a null pointer, m, b or t < 1, b > 65535, or ceil(t / 32)^2 >= 2^31 (the grid). */
+int resr_crop_batch(const uint8_t* arena, const int64_t* table, const int32_t* records, int32_t m, int32_t b, int32_t t, float* dst,
+                    void* stream);
+
 /* ---- training pair pool (device_data.PairPool): a resident queue of finished LR / HR pairs, one exchange launch a step ------------
  * resr_pool_exchange: for sample i < b with slot = slots[i]: lr_out[i] = pool_lr[slot], then pool_lr[slot] = lr_in[i]; the same for hr.
  *   pool_lr fp32 [q, lr_elems], pool_hr fp32 [q, hr_elems]; lr_in / lr_out fp32 [b, lr_elems], hr_in / hr_out fp32 [b, hr_elems]; slots int32

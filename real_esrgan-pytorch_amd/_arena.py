@@ -86,9 +86,12 @@ class Workspace:
     graph, collected late, must not free a workspace a newer graph saved its activations in)."""
 
     def __init__(self, nbytes: int, device, zero_head: int = 0) -> None:
-        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        if zero_head:      # state the native passes expect zeroed once, at allocation (include/resr.h)
-            self.buf[:zero_head].zero_()
+        # Zeroed once, at allocation, all of it.  The native passes ask that only of the head (`zero_head` bytes: include/resr.h), but
+        # the weight-gradient reduction also looks at slab entries no launch of the pass has written (padding rows / columns, the bias
+        # part of a job without a bias) when it decides whether a lifted pass overflowed (csrc/wgrad.hip, common.h grad_prescale): a
+        # non-finite bit pattern that recycled memory happened to hold there set the sticky back-off of a workspace's FIRST pass, so
+        # that pass and the next one differed by the lift -- depending on what the process had freed before.
+        self.buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self.busy = False
         self.owner = 0
 

@@ -89,11 +89,18 @@ pretrained_g = os.environ.get("RESR_PRETRAINED_G", "")
 # files in `train_image_dir`, their LR partners (same names, 1 / upscale_factor the size) in `paired_lr_image_dir` ($RESR_PAIRED_LR_DIR);
 # "paired" = `device_data.PairedDeviceSource`, both sides resident in HBM as uint8 and a batch one launch; "paired_loader" =
 # `dataset.PairedImageDataset` in DataLoader workers, the fallback for a set that does not fit.  The LR patch is paired_patch() below.
-DATA_SOURCES = ("loader", "device", "paired", "paired_loader")
+# "images" / "images_loader" = whole training images of any size in `train_image_dir`, no offline tiling: a sample is a random
+# `train_tile` x `train_tile` window of its image, reflect-padded below / to the right where the image is smaller (upstream's
+# crop_pad_size); "images" = `device_data.ImageCropSource`, the images resident in HBM as uint8 and the crop inside the batch's launch;
+# "images_loader" = `dataset.CropImageDataset` in DataLoader workers, the fallback for a set that does not fit.
+DATA_SOURCES = ("loader", "device", "paired", "paired_loader", "images", "images_loader")
 PAIRED_DATA_SOURCES = ("paired", "paired_loader")
+IMAGE_DATA_SOURCES = ("images", "images_loader")
 data_source = os.environ.get("RESR_DATA_SOURCE", "loader")
 if data_source not in DATA_SOURCES:
-    raise ValueError(f"RESR_DATA_SOURCE={data_source!r}: expected 'loader', 'device', 'paired' or 'paired_loader'")
+    raise ValueError(f"RESR_DATA_SOURCE={data_source!r}: expected one of " + ", ".join(repr(name) for name in DATA_SOURCES))
+# The window side T of the two whole-image sources (upstream's crop_pad_size); the other sources never read it.
+train_tile = int(os.environ.get("RESR_TRAIN_TILE", "400"))
 paired_lr_image_dir = os.environ.get("RESR_PAIRED_LR_DIR", "")
 if data_source in PAIRED_DATA_SOURCES and not paired_lr_image_dir:
     raise ValueError(f"RESR_DATA_SOURCE={data_source!r} needs RESR_PAIRED_LR_DIR: the directory of the LR partners of the files in train_image_dir")
@@ -188,6 +195,18 @@ def paired_patch() -> int:
 
 if data_source in PAIRED_DATA_SOURCES and mode in ("train_realesrnet", "train_realesrgan"):
     paired_patch()
+
+
+def train_window() -> int:
+    """The window side of the whole-image data sources: `train_tile`, which the degradation stage crops its image_size HR patch from."""
+    if train_tile < image_size:
+        raise ValueError(f"config.train_tile={train_tile} (RESR_TRAIN_TILE) is below image_size={image_size}: the whole-image data sources "
+                         "hand out train_tile windows, and the HR crop of image_size is taken inside them")
+    return train_tile
+
+
+if data_source in IMAGE_DATA_SOURCES and mode in ("train_realesrnet", "train_realesrgan"):
+    train_window()
 
 
 def pair_pool() -> int:

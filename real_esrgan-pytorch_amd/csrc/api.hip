@@ -420,6 +420,11 @@ int resr_pair_batch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int6
     return pair_batch_dispatch(hr_arena, lr_arena, table, records, m, b, patch, scale, lr_dst, hr_dst, (hipStream_t)stream);
 }
 
+int resr_crop_batch(const uint8_t* arena, const int64_t* table, const int32_t* records, int32_t m, int32_t b, int32_t t, float* dst, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return crop_batch_dispatch(arena, table, records, m, b, t, dst, (hipStream_t)stream);
+}
+
 int resr_pool_exchange(float* pool_lr, float* pool_hr, const float* lr_in, const float* hr_in, float* lr_out, float* hr_out, const int32_t* slots, int32_t q,
                        int32_t b, int64_t lr_elems, int64_t hr_elems, void* stream) {
     RESR_DEVICE_SCOPE(stream);

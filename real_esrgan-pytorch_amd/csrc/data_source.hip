@@ -5,6 +5,8 @@
 //                  HWC -> CHW.  Bit for bit device_data.augment_np (the imgproc chain of dataset.py).
 //   pair_batch   : uint8 images of any size, both sides of each pair in an arena -> fp32 LR [B,3,P,P] and HR [B,3,sP,sP]: crop, the
 //                  same dihedral code on both sides, / 255.0f, HWC -> CHW.  Bit for bit device_data.paired_sample_np.
+//   crop_batch   : uint8 images of any size in an arena -> fp32 [B,3,T,T]: the T x T window at (top, left), continued by reflection where
+//                  the image is smaller, tile_batch's 16 codes, / 255.0f, HWC -> CHW.  Bit for bit device_data.crop_sample_np.
 //   pool_exchange: fp32 batch LR [B,3,P,P] / HR [B,3,sP,sP] <-> slots of the resident pool [Q,...]: out[i] = pool[slots[i]], pool[slots[i]] =
 //                  in[i], both sides, 32-bit words moved.  Bit for bit device_data.pool_exchange_np / pool_store_np.
 //   blur_kernels : one record of RESR_BLUR_RECORD doubles per kernel (include/resr.h) -> fp32 [n,K,K]: the float64 synthesis of
@@ -24,56 +26,80 @@ namespace resr {
 constexpr int kTileSide = 32;
 constexpr int kTilePitch = kTileSide * 3 + 4;   // bytes per staged row: 25 dwords, odd, so a column walk spreads over the banks
 
-__global__ __launch_bounds__(256) void tile_batch_kernel(const uint8_t* __restrict__ tiles, const int32_t* __restrict__ index,
-                                                         const uint8_t* __restrict__ aug, float* __restrict__ dst, int T, int tiles_x) {
-    __shared__ uint8_t lds[kTileSide * kTilePitch];
-    const int b = (int)blockIdx.y;
-    const int x0 = (int)(blockIdx.x % (unsigned)tiles_x) * kTileSide, y0 = (int)(blockIdx.x / (unsigned)tiles_x) * kTileSide;
-    const int code = aug[b], rot = code & 3;
-    const bool hf = code & 4, vf = code & 8;
-    const int x_end = min(x0 + kTileSide, T) - 1, y_end = min(y0 + kTileSide, T) - 1;   // last destination column / row of the tile
-    // the tile's coordinates before the flips (x1, y1): an interval each
-    const int x1_lo = hf ? T - 1 - x_end : x0, x1_hi = hf ? T - 1 - x0 : x_end;
-    const int y1_lo = vf ? T - 1 - y_end : y0, y1_hi = vf ? T - 1 - y0 : y_end;
-    const int c2 = 2 * (T / 2);   // cx + cy of the rotation about (T / 2, T / 2)
-    // source block: columns sx_lo.., rows sy_lo.. (rot 0: (x1, y1); 90: (c2 - y1, x1); 180: (c2 - x1, c2 - y1); 270: (y1, c2 - x1))
-    int sx_lo, sy_lo;
-    switch (rot) {
-        case 0: sx_lo = x1_lo; sy_lo = y1_lo; break;
-        case 1: sx_lo = c2 - y1_hi; sy_lo = x1_lo; break;
-        case 2: sx_lo = c2 - x1_hi; sy_lo = c2 - y1_hi; break;
-        default: sx_lo = y1_lo; sy_lo = c2 - x1_hi; break;
-    }
-    const uint8_t* src = tiles + (size_t)index[b] * (size_t)T * (size_t)T * 3;
-    for (int i = (int)threadIdx.x; i < kTileSide * kTileSide * 3; i += 256) {
-        const int r = i / (kTileSide * 3), k = i - r * (kTileSide * 3);
-        const int sy = sy_lo + r, sx = sx_lo + k / 3;
-        uint8_t v = 0;
-        if (sy < T && sx < T) v = src[((size_t)sy * T + sx_lo) * 3 + k];   // (sx_lo, sy_lo >= 0 for every code)
-        lds[r * kTilePitch + k] = v;
-    }
-    __syncthreads();
-    const int tx = (int)(threadIdx.x & 31u), x = x0 + tx;
-    if (x > x_end) return;
-    const int x1 = hf ? T - 1 - x : x;
-    const size_t plane = (size_t)T * (size_t)T;
-    for (int ty = (int)(threadIdx.x >> 5); ty < kTileSide; ty += 8) {
-        const int y = y0 + ty;
-        if (y > y_end) break;
-        const int y1 = vf ? T - 1 - y : y;
-        int sx, sy;
+// The 16-code permutation of one workgroup, shared by tile_batch and crop_batch: which block of the source the tile needs (block),
+// and the tile's plane rows out of the staged block (store).
+struct AugTile {
+    int T, x0, y0, x_end, y_end;   // the side; the tile's first and last destination column / row
+    int rot, c2;                   // angle / 90; cx + cy of the rotation about (T / 2, T / 2)
+    bool hf, vf;
+    int sx_lo, sy_lo;              // the source block: columns sx_lo.., rows sy_lo.. (>= 0 for every code; at most T, one past the side)
+
+    // source coordinates of destination (x, y): rot 0: (x1, y1); 90: (c2 - y1, x1); 180: (c2 - x1, c2 - y1); 270: (y1, c2 - x1)
+    __device__ __forceinline__ void source(int x1, int y1, int& sx, int& sy) const {
         switch (rot) {
             case 0: sx = x1; sy = y1; break;
             case 1: sx = c2 - y1; sy = x1; break;
             case 2: sx = c2 - x1; sy = c2 - y1; break;
             default: sx = y1; sy = c2 - x1; break;
         }
-        const uint8_t* p = lds + (sy - sy_lo) * kTilePitch + (sx - sx_lo) * 3;
-        float* o = dst + (size_t)b * 3 * plane + (size_t)y * T + x;
-        o[0] = (float)p[0] / 255.0f;
-        o[plane] = (float)p[1] / 255.0f;
-        o[2 * plane] = (float)p[2] / 255.0f;
     }
+
+    __device__ __forceinline__ AugTile(int code, int T_, int tile, int tiles_x) : T(T_) {
+        x0 = (int)((unsigned)tile % (unsigned)tiles_x) * kTileSide;
+        y0 = (int)((unsigned)tile / (unsigned)tiles_x) * kTileSide;
+        rot = code & 3;
+        hf = code & 4;
+        vf = code & 8;
+        x_end = min(x0 + kTileSide, T) - 1;
+        y_end = min(y0 + kTileSide, T) - 1;
+        // the tile's coordinates before the flips (x1, y1): an interval each
+        const int x1_lo = hf ? T - 1 - x_end : x0, x1_hi = hf ? T - 1 - x0 : x_end;
+        const int y1_lo = vf ? T - 1 - y_end : y0, y1_hi = vf ? T - 1 - y0 : y_end;
+        c2 = 2 * (T / 2);
+        switch (rot) {
+            case 0: sx_lo = x1_lo; sy_lo = y1_lo; break;
+            case 1: sx_lo = c2 - y1_hi; sy_lo = x1_lo; break;
+            case 2: sx_lo = c2 - x1_hi; sy_lo = c2 - y1_hi; break;
+            default: sx_lo = y1_lo; sy_lo = c2 - x1_hi; break;
+        }
+    }
+
+    // after the barrier behind the staging: the tile of image `dst` [3, T, T], consecutive lanes on consecutive floats of a plane row
+    __device__ __forceinline__ void store(const uint8_t* lds, float* __restrict__ dst) const {
+        const int tx = (int)(threadIdx.x & 31u), x = x0 + tx;
+        if (x > x_end) return;
+        const int x1 = hf ? T - 1 - x : x;
+        const size_t plane = (size_t)T * (size_t)T;
+        for (int ty = (int)(threadIdx.x >> 5); ty < kTileSide; ty += 8) {
+            const int y = y0 + ty;
+            if (y > y_end) break;
+            const int y1 = vf ? T - 1 - y : y;
+            int sx, sy;
+            source(x1, y1, sx, sy);
+            const uint8_t* p = lds + (sy - sy_lo) * kTilePitch + (sx - sx_lo) * 3;
+            float* o = dst + (size_t)y * T + x;
+            o[0] = (float)p[0] / 255.0f;
+            o[plane] = (float)p[1] / 255.0f;
+            o[2 * plane] = (float)p[2] / 255.0f;
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void tile_batch_kernel(const uint8_t* __restrict__ tiles, const int32_t* __restrict__ index,
+                                                         const uint8_t* __restrict__ aug, float* __restrict__ dst, int T, int tiles_x) {
+    __shared__ uint8_t lds[kTileSide * kTilePitch];
+    const int b = (int)blockIdx.y;
+    const AugTile a(aug[b], T, (int)blockIdx.x, tiles_x);
+    const uint8_t* src = tiles + (size_t)index[b] * (size_t)T * (size_t)T * 3;
+    for (int i = (int)threadIdx.x; i < kTileSide * kTileSide * 3; i += 256) {
+        const int r = i / (kTileSide * 3), k = i - r * (kTileSide * 3);
+        const int sy = a.sy_lo + r, sx = a.sx_lo + k / 3;
+        uint8_t v = 0;
+        if (sy < T && sx < T) v = src[((size_t)sy * T + a.sx_lo) * 3 + k];
+        lds[r * kTilePitch + k] = v;
+    }
+    __syncthreads();
+    a.store(lds, dst + (size_t)b * 3 * (size_t)T * (size_t)T);
 }
 
 int tile_batch_dispatch(const uint8_t* tiles, const int32_t* index, const uint8_t* aug, int M, int B, int T, float* dst, hipStream_t st) {
@@ -167,6 +193,71 @@ int pair_batch_dispatch(const uint8_t* hr_arena, const uint8_t* lr_arena, const 
                        lr_arena, table, records, M, P, scale, lr_dst, hr_dst, (int)lr_tiles_x, (int)hr_tiles_x);
     prof_after(st, 33001, 0.0, (double)B * (double)P * P * 15.0 * (1.0 + (double)scale * scale));
     RESR_CHECK_LAUNCH("pair_batch_kernel");
+    return RESR_OK;
+}
+
+// ---- crop_batch ------------------------------------------------------------------------------------------------------------------
+// The whole-image source (device_data.ImageCropSource): images of any size in one arena, a sample the T x T window of its image at
+// (top, left) under tile_batch's 16 codes.  An image below T in an axis is continued below / to the right by reflection about its last
+// pixel (reflect101: the period is 2n - 2, so a pad of any width is defined).  The work split and the permutation are tile_batch's
+// (AugTile); what differs is the staging.  A staged block that lies inside the image is read as pair_batch reads: row-contiguous bytes,
+// consecutive lanes on consecutive bytes.  A block that reaches the padding maps every pixel through reflect101 in both axes; only
+// those blocks pay for the two remainders.  Window coordinates one past T (the rotation's fill) are staged as zeros in both forms.
+// Every offset is 64-bit.
+__device__ __forceinline__ int64_t reflect101(uint32_t i, uint32_t n) {      // i < 2^31, 1 <= n < 2^31
+    if (n == 1u) return 0;
+    const uint32_t p = 2u * n - 2u, j = i % p;
+    return j < n ? j : p - j;
+}
+
+__global__ __launch_bounds__(256) void crop_batch_kernel(const uint8_t* __restrict__ arena, const int64_t* __restrict__ table,
+                                                         const int32_t* __restrict__ records, int M, int T, float* __restrict__ dst, int tiles_x) {
+    __shared__ uint8_t lds[kTileSide * kTilePitch];
+    const int b = (int)blockIdx.y;
+    const int32_t* rec = records + (size_t)b * 4;
+    // nothing of a record is trusted (check_crop_records refuses a wrong one before upload): a clamped record reads inside its image
+    const int image = min(max(rec[0], 0), M - 1);
+    const int64_t* row = table + (size_t)image * 3;
+    const int64_t h = row[1], w = row[2];
+    const int64_t top = clamp64(rec[1], 0, h > T ? h - T : 0), left = clamp64(rec[2], 0, w > T ? w - T : 0);
+    const AugTile a(rec[3] & 15, T, (int)blockIdx.x, tiles_x);
+    const uint8_t* src = arena + row[0];
+    // the window rows and columns the block holds: sy_lo .. sy_hi, sx_lo .. sx_hi (the rest of the 32 x 32 is one past T, or unused)
+    const int sy_hi = min(a.sy_lo + kTileSide, T) - 1, sx_hi = min(a.sx_lo + kTileSide, T) - 1;
+    if (top + sy_hi < h && left + sx_hi < w) {
+        for (int i = (int)threadIdx.x; i < kTileSide * kTileSide * 3; i += 256) {
+            const int r = i / (kTileSide * 3), k = i - r * (kTileSide * 3);
+            const int sy = a.sy_lo + r, sx = a.sx_lo + k / 3;
+            uint8_t v = 0;
+            if (sy <= sy_hi && sx <= sx_hi) v = src[((top + sy) * w + left + a.sx_lo) * 3 + k];
+            lds[r * kTilePitch + k] = v;
+        }
+    } else {
+        for (int i = (int)threadIdx.x; i < kTileSide * kTileSide * 3; i += 256) {
+            const int r = i / (kTileSide * 3), k = i - r * (kTileSide * 3), px = k / 3;
+            const int sy = a.sy_lo + r, sx = a.sx_lo + px;
+            uint8_t v = 0;
+            if (sy <= sy_hi && sx <= sx_hi) {
+                const int64_t iy = reflect101((uint32_t)(top + sy), (uint32_t)h), ix = reflect101((uint32_t)(left + sx), (uint32_t)w);
+                v = src[(iy * w + ix) * 3 + (k - px * 3)];
+            }
+            lds[r * kTilePitch + k] = v;
+        }
+    }
+    __syncthreads();
+    a.store(lds, dst + (size_t)b * 3 * (size_t)T * (size_t)T);
+}
+
+int crop_batch_dispatch(const uint8_t* arena, const int64_t* table, const int32_t* records, int M, int B, int T, float* dst, hipStream_t st) {
+    if (!arena || !table || !records || !dst) return fail(RESR_ERR_ARG, "crop_batch: a null pointer (arena, table, records and dst are all needed)");
+    if (M < 1 || B < 1 || T < 1) return fail(RESR_ERR_ARG, "crop_batch: m=%d, b=%d or t=%d below 1", M, B, T);
+    if (B > 65535) return fail(RESR_ERR_ARG, "crop_batch: b=%d above 65535 (the grid's y dimension)", B);
+    const int64_t tiles_x = ((int64_t)T + kTileSide - 1) / kTileSide;
+    if (tiles_x * tiles_x > 0x7fffffffLL) return fail(RESR_ERR_ARG, "crop_batch: grid overflow (t=%d: %lld tiles a sample)", T, (long long)(tiles_x * tiles_x));
+    prof_before(st);
+    hipLaunchKernelGGL(crop_batch_kernel, dim3((unsigned)(tiles_x * tiles_x), (unsigned)B), dim3(256), 0, st, arena, table, records, M, T, dst, (int)tiles_x);
+    prof_after(st, 33003, 0.0, (double)B * T * T * 15.0);
+    RESR_CHECK_LAUNCH("crop_batch_kernel");
     return RESR_OK;
 }
 

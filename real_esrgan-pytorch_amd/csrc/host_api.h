@@ -178,6 +178,8 @@ int blur_kernels_dispatch(const double* params, int n, int K, float* dst, hipStr
 // a batch of LR / HR pairs: both arenas bytes, table [M,4] int64 (hr_offset, lr_offset, lr_h, lr_w), records [B,4] int32 (image, top, left, code)
 int pair_batch_dispatch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int64_t* table, const int32_t* records, int M, int B, int P, int scale,
                         float* lr_dst, float* hr_dst, hipStream_t st);
+// a batch of windows of whole images: arena bytes, table [M,3] int64 (offset, h, w), records [B,4] int32 (image, top, left, code)
+int crop_batch_dispatch(const uint8_t* arena, const int64_t* table, const int32_t* records, int M, int B, int T, float* dst, hipStream_t st);
 // the training pair pool: pools [Q, *_elems], batches [B, *_elems] fp32, slots [B] int32 on the device; both outputs null = store only
 int pool_exchange_dispatch(float* pool_lr, float* pool_hr, const float* lr_in, const float* hr_in, float* lr_out, float* hr_out, const int32_t* slots, int Q,
                            int B, int64_t lr_elems, int64_t hr_elems, hipStream_t st);

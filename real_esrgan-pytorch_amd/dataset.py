@@ -16,8 +16,15 @@ from torch.utils.data import DataLoader, Dataset
 from . import device_data, imgproc
 from .degrade import sample_blur_kernels
 
-# (the reference's list, dataset.py:27-30; PairedImageDataset and PairedPrefetcher are this project's, outside it)
+# (the reference's list, dataset.py:27-30; PairedImageDataset, PairedPrefetcher and CropImageDataset are this project's, outside it)
 __all__ = ["TrainValidImageDataset", "TestImageDataset", "PrefetchGenerator", "PrefetchDataLoader", "CPUPrefetcher", "CUDAPrefetcher"]
+
+
+def _train_item(hr_tensor: torch.Tensor, parameters: dict) -> dict:
+    """A training sample: the HR tensor and the three blur kernels drawn for it (reference dataset.py:82-143, same draw order)."""
+    kernel1, kernel2, sinc_kernel = sample_blur_kernels(parameters)
+    return {"hr": hr_tensor, "kernel1": torch.from_numpy(kernel1), "kernel2": torch.from_numpy(kernel2),
+            "sinc_kernel": torch.from_numpy(sinc_kernel)}
 
 
 class TrainValidImageDataset(Dataset):
@@ -40,9 +47,7 @@ class TrainValidImageDataset(Dataset):
             hr_image = imgproc.random_horizontally_flip(hr_image, 0.5)               # :71
             hr_image = imgproc.random_vertically_flip(hr_image, 0.5)                 # :72
             hr_tensor = imgproc.image_to_tensor(hr_image, False, False)              # :79
-            kernel1, kernel2, sinc_kernel = sample_blur_kernels(self.parameters)     # :82-137, same draw order
-            return {"hr": hr_tensor, "kernel1": torch.from_numpy(kernel1), "kernel2": torch.from_numpy(kernel2),
-                    "sinc_kernel": torch.from_numpy(sinc_kernel)}
+            return _train_item(hr_tensor, self.parameters)
         if self.mode == "Valid":
             hr_image = imgproc.center_crop(image, self.image_size)                   # :146
             lr_image = imgproc.image_resize(hr_image, 1 / self.upscale_factor)       # :148
@@ -95,6 +100,33 @@ class PairedImageDataset(Dataset):
 
     def __len__(self) -> int:
         return len(self.hr_file_names)
+
+
+class CropImageDataset(Dataset):
+    """The loader path of the whole-image data source (config.data_source = "images_loader"): training images of any size in one
+    directory (os.listdir order), a sample the file decoded, the draws of `device_data.sample_crop_draw` and `sample_augment`, the
+    arithmetic of `device_data.crop_sample_np` and the three blur kernels of `TrainValidImageDataset`'s Train branch -- the same
+    dictionary, served through `CUDAPrefetcher`.  It is the definition the resident source (`device_data.ImageCropSource`) is judged
+    against: at num_workers=0 both give the same batches under the same seeds.  `tile` is the window side T."""
+
+    def __init__(self, image_dir: str, tile: int, degradation_model_parameters_dict: dict) -> None:
+        super().__init__()
+        if int(tile) < 1:
+            raise ValueError(f"crop dataset: tile {tile} below 1")
+        self.image_file_names = [os.path.join(image_dir, name) for name in os.listdir(image_dir)]
+        if not self.image_file_names:
+            raise ValueError(f"crop dataset: no files in {image_dir}")
+        self.tile = int(tile)
+        self.parameters = degradation_model_parameters_dict
+
+    def __getitem__(self, batch_index: int) -> dict:
+        image = device_data._read_tile(self.image_file_names[batch_index])
+        top, left = device_data.sample_crop_draw(image.shape[0], image.shape[1], self.tile)
+        code = device_data.sample_augment()
+        return _train_item(device_data.crop_sample_np(image, top, left, code, self.tile), self.parameters)
+
+    def __len__(self) -> int:
+        return len(self.image_file_names)
 
 
 class CUDAPrefetcher:

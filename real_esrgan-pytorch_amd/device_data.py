@@ -15,6 +15,12 @@ every pair resident as uint8 in two arenas, a batch -- crop, dihedral augmentati
 has `degrade.DegradationPrefetcher`'s contract, because it stands in its place in the train scripts.  The loader path over the same
 two directories is `dataset.PairedImageDataset` / `PairedPrefetcher`.
 
+The whole-image source (config.data_source = "images") lifts the tile source's one limit, that every file is a square tile of one size:
+images of any size resident in one arena, a batch -- random T x T window, reflect padding of an image below T, the tile source's
+rotation and flips, /255, HWC -> CHW -- ONE launch (resr_crop_batch) in front of resr_blur_kernels.  `reflect101` / `crop_sample_np` are
+the definition, `sample_crop_draw` the host's extra draw, `ImageCropSource` the source, with `DeviceTileSource`'s contract; the loader
+path over the same directory is `dataset.CropImageDataset`.
+
 The training pair pool (config.pair_pool_size > 0) stands behind whichever source hands out (lr, hr, batch): a resident queue of
 finished pairs that a step's batch is exchanged with, so that a batch mixes samples of many degradation plans.  `pool_exchange_np` /
 `pool_store_np` are the definition, `sample_pool_slots` the host's draw (from a `random.Random` of the pool's own), `PairPool` the
@@ -37,6 +43,7 @@ from .config import degradation_model_parameters_dict as MODEL_P
 __all__ = ["sample_blur_params", "blur_kernels_from_params_np", "check_blur_records", "sample_augment", "augment_np",
            "tile_batch", "blur_kernels", "DeviceTileSource", "RECORD", "FAMILIES",
            "paired_sample_np", "sample_paired_draw", "check_paired_records", "paired_files", "pair_batch", "PairedDeviceSource",
+           "reflect101", "crop_sample_np", "sample_crop_draw", "check_crop_records", "crop_batch", "ImageCropSource",
            "pool_exchange_np", "pool_store_np", "sample_pool_slots", "check_pool_slots", "pool_exchange", "pool_store", "PairPool",
            "HostPairPool"]
 
@@ -498,6 +505,49 @@ def _image_size(path: str):
     return h, w
 
 
+def _load_arenas(jobs: dict, device, chunk_bytes: int, workers: int, who: str) -> dict:
+    """The loader of the arena sources (`PairedDeviceSource.from_dirs`, `ImageCropSource.from_dir`).  `jobs`: arena name -> its images as
+    (path, byte offset, (h, w)), back to back in offset order.  Every file is decoded once with PIL on a thread pool of `workers` and
+    moved through two pinned staging buffers of `chunk_bytes` (or of the largest image) into one uint8 device tensor per arena."""
+    from concurrent.futures import ThreadPoolExecutor
+    totals = {side: jobs[side][-1][1] + jobs[side][-1][2][0] * jobs[side][-1][2][1] * 3 for side in jobs}
+    largest = max(h * w * 3 for side in jobs for _, _, (h, w) in jobs[side])
+    room = max(largest, min(int(chunk_bytes), max(totals.values())))
+    arenas = {side: torch.empty(totals[side], dtype=torch.uint8, device=device) for side in jobs}
+    staging = [torch.empty(room, dtype=torch.uint8).pin_memory() for _ in range(2)]
+    free = [None, None]      # the event behind the last copy out of each staging buffer
+
+    def decode(job):
+        view, path, (h, w) = job
+        a = _read_tile(path)
+        if a.shape != (h, w, 3):
+            raise ValueError(f"{who}: {path} decodes to {a.shape[1]}x{a.shape[0]}, its header said {w}x{h}")
+        np.copyto(view.numpy().reshape(h, w, 3), a)
+
+    k = 0
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        for side, todo in jobs.items():
+            first = 0
+            while first < len(todo):
+                start = todo[first][1]      # a chunk: consecutive images of the arena, as many as the staging buffer holds
+                last = first
+                while last < len(todo) and todo[last][1] + todo[last][2][0] * todo[last][2][1] * 3 - start <= room:
+                    last += 1
+                end = todo[last - 1][1] + todo[last - 1][2][0] * todo[last - 1][2][1] * 3
+                buf = staging[k % 2]
+                if free[k % 2] is not None:
+                    free[k % 2].synchronize()       # start-up only: the buffer is read by an earlier copy
+                list(pool.map(decode, [(buf[off - start:off - start + h * w * 3], path, (h, w)) for path, off, (h, w) in todo[first:last]]))
+                arenas[side][start:end].copy_(buf[:end - start], non_blocking=True)
+                free[k % 2] = torch.cuda.Event()
+                free[k % 2].record(torch.cuda.current_stream(device))
+                first, k = last, k + 1
+    for e in free:
+        if e is not None:
+            e.synchronize()                         # the staging buffers go back to the allocator after this
+    return arenas
+
+
 class PairedDeviceSource:
     """`degrade.DegradationPrefetcher`'s contract -- `next()` -> (lr, hr, batch) or None, `reset()`, `len()`,
     `original_dataloader.sampler` -- over LR / HR pairs held on the device as uint8: the train scripts iterate it directly
@@ -568,44 +618,9 @@ class PairedDeviceSource:
             hr_sizes, lr_sizes = list(pool.map(_image_size, hr_paths)), list(pool.map(_image_size, lr_paths))
         table = _pair_table(hr_sizes, lr_sizes, hr_paths, patch, scale, max_bytes)
         M = len(hr_paths)
-        jobs = {"hr": [(hr_paths[i], int(table[i, 0]), hr_sizes[i]) for i in range(M)],
-                "lr": [(lr_paths[i], int(table[i, 1]), lr_sizes[i]) for i in range(M)]}
-        totals = {side: jobs[side][-1][1] + jobs[side][-1][2][0] * jobs[side][-1][2][1] * 3 for side in jobs}
-        largest = max(h * w * 3 for h, w in hr_sizes + lr_sizes)
-        room = max(largest, min(int(chunk_bytes), max(totals.values())))
-        arenas = {side: torch.empty(totals[side], dtype=torch.uint8, device=device) for side in jobs}
-        staging = [torch.empty(room, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        free = [None, None]      # the event behind the last copy out of each staging buffer
-
-        def decode(job):
-            view, path, (h, w) = job
-            a = _read_tile(path)
-            if a.shape != (h, w, 3):
-                raise ValueError(f"paired data source: {path} decodes to {a.shape[1]}x{a.shape[0]}, its header said {w}x{h}")
-            np.copyto(view.numpy().reshape(h, w, 3), a)
-
-        k = 0
-        with ThreadPoolExecutor(max_workers=workers) as pool:
-            for side in ("hr", "lr"):
-                todo = jobs[side]
-                first = 0
-                while first < len(todo):
-                    start = todo[first][1]      # a chunk: consecutive images of the arena, as many as the staging buffer holds
-                    last = first
-                    while last < len(todo) and todo[last][1] + todo[last][2][0] * todo[last][2][1] * 3 - start <= room:
-                        last += 1
-                    end = todo[last - 1][1] + todo[last - 1][2][0] * todo[last - 1][2][1] * 3
-                    buf = staging[k % 2]
-                    if free[k % 2] is not None:
-                        free[k % 2].synchronize()       # start-up only: the buffer is read by an earlier copy
-                    list(pool.map(decode, [(buf[off - start:off - start + h * w * 3], path, (h, w)) for path, off, (h, w) in todo[first:last]]))
-                    arenas[side][start:end].copy_(buf[:end - start], non_blocking=True)
-                    free[k % 2] = torch.cuda.Event()
-                    free[k % 2].record(torch.cuda.current_stream(device))
-                    first, k = last, k + 1
-        for e in free:
-            if e is not None:
-                e.synchronize()                         # the staging buffers go back to the allocator after this
+        arenas = _load_arenas({"hr": [(hr_paths[i], int(table[i, 0]), hr_sizes[i]) for i in range(M)],
+                               "lr": [(lr_paths[i], int(table[i, 1]), lr_sizes[i]) for i in range(M)]}, device, chunk_bytes, workers,
+                              "paired data source")
         return cls(arenas["hr"], arenas["lr"], table, batch_size, patch, scale, sampler)
 
     # -- the batch source --
@@ -646,6 +661,245 @@ class PairedDeviceSource:
     def reset(self) -> None:
         self._it = iter(self._batches)
         self._count = 0
+        self._stage()
+
+    def __len__(self) -> int:
+        return len(self._batches)
+
+
+# ---- the whole-image source: the definition ----------------------------------------------------------------------------------------
+CROP_TABLE_COLUMNS = 3       # (byte offset, h, w)
+
+
+def reflect101(i: int, n: int) -> int:
+    """Index i >= 0 mapped into an axis of length n >= 1 by reflection about the last pixel, period 2n - 2: np.pad(..., mode="reflect") below
+    / to the right for a pad of any width, cv2's BORDER_REFLECT_101 for a pad below n."""
+    i, n = int(i), int(n)
+    if i < 0 or n < 1:
+        raise ValueError(f"reflect101: index {i} below 0, or length {n} below 1")
+    if n == 1:
+        return 0
+    p = 2 * n - 2
+    j = i % p
+    return j if j < n else p - j
+
+
+def _crop_range(h: int, w: int, T: int):
+    """The last legal (top, left) of a T x T window of an h x w image: padding exists only below and to the right."""
+    return max(h, T) - T, max(w, T) - T
+
+
+def crop_sample_np(image_u8: np.ndarray, top: int, left: int, code: int, T: int) -> torch.Tensor:
+    """THE definition of one sample of the whole-image source: uint8 [h, w, 3] -> float32 [3, T, T], `augment_np(win, code)` of the window
+    win[y, x] = image[reflect101(top + y, h), reflect101(left + x, w)], y, x < T.  Legal: 0 <= top <= max(h, T) - T, 0 <= left <=
+    max(w, T) - T -- a window never starts inside the padding of an image that is large enough."""
+    image_u8 = np.asarray(image_u8)
+    top, left, T = int(top), int(left), int(T)
+    if image_u8.dtype != np.uint8 or image_u8.ndim != 3 or image_u8.shape[2] != 3 or image_u8.shape[0] < 1 or image_u8.shape[1] < 1:
+        raise ValueError(f"crop_sample_np: expected a uint8 [h, w, 3] image, got {image_u8.dtype} {image_u8.shape}")
+    if T < 1:
+        raise ValueError(f"crop_sample_np: window side {T} below 1")
+    h, w = image_u8.shape[:2]
+    top_max, left_max = _crop_range(h, w, T)
+    if not (0 <= top <= top_max and 0 <= left <= left_max):
+        raise ValueError(f"crop_sample_np: the {T}x{T} window at (top {top}, left {left}) is outside 0..{top_max}, 0..{left_max} of the {h}x{w} image")
+    rows = [reflect101(top + y, h) for y in range(T)]
+    cols = [reflect101(left + x, w) for x in range(T)]
+    return augment_np(np.ascontiguousarray(image_u8[np.ix_(rows, cols)]), code)
+
+
+def sample_crop_draw(h: int, w: int, T: int):
+    """The host's crop draw of one sample, from `random`: top = randint(0, max(h, T) - T) only when h > T, else 0 and NO draw; left the
+    same.  On T x T tiles nothing is drawn."""
+    top = random.randint(0, h - T) if h > T else 0
+    left = random.randint(0, w - T) if w > T else 0
+    return top, left
+
+
+def check_crop_records(records, table, T: int) -> np.ndarray:
+    """`records` as an int32 [B, 4] array of (image, top, left, code) rows, or ValueError for what the definition excludes: a wrong shape
+    or dtype, an image index outside 0..M-1, a top or left outside the legal range of its image, a code outside 0..15.  `table` is the
+    source's int64 [M, 3] = (offset, h, w)."""
+    rec = np.asarray(records)
+    table = np.asarray(table).reshape(-1, CROP_TABLE_COLUMNS)
+    if rec.size < 4 or rec.size % 4 or not np.issubdtype(rec.dtype, np.integer):
+        raise ValueError(f"crop records: expected integer (image, top, left, code) rows, got {rec.dtype} {rec.shape}")
+    rec = rec.reshape(-1, 4).astype(np.int64)
+    M = table.shape[0]
+    image, top, left, code = rec.T
+    bad = np.flatnonzero((image < 0) | (image >= M))
+    if bad.size:
+        raise ValueError(f"crop records: image index {int(image[bad[0]])} of record {int(bad[0])} outside 0..{M - 1}")
+    h, w = table[image, 1], table[image, 2]
+    for name, value, side in (("top", top, h), ("left", left, w)):
+        last = np.maximum(side, T) - T
+        bad = np.flatnonzero((value < 0) | (value > last))
+        if bad.size:
+            k = int(bad[0])
+            raise ValueError(f"crop records: {name} {int(value[k])} of record {k} outside 0..{int(last[k])}, the legal range of a {T}-pixel window "
+                             f"of image {int(image[k])} ({int(h[k])}x{int(w[k])})")
+    bad = np.flatnonzero((code < 0) | (code > 15))
+    if bad.size:
+        raise ValueError(f"crop records: code {int(code[bad[0]])} of record {int(bad[0])} outside 0..15")
+    return np.ascontiguousarray(rec.astype(np.int32))
+
+
+def _crop_table(sizes, names, max_bytes: int) -> np.ndarray:
+    """(h, w) of every image -> the int64 [M, 3] table (offset, h, w), images back to back; every refusal of a set (host only) is made
+    here and names the image."""
+    if not names:
+        raise ValueError("image data source: no images")
+    table = np.zeros((len(names), CROP_TABLE_COLUMNS), dtype=np.int64)
+    off = 0
+    for i, ((h, w), name) in enumerate(zip(sizes, names)):
+        if h < 1 or w < 1 or h >= 2 ** 31 or w >= 2 ** 31:
+            raise ValueError(f"image data source: {name} is {w}x{h}; a side must be in 1..2^31 - 1")
+        table[i] = (off, h, w)
+        off += h * w * 3
+    if off > max_bytes:
+        raise ValueError(f"image data source: {len(names)} images are {off} bytes, above max_bytes={max_bytes}")
+    return table
+
+
+def crop_batch(arena: torch.Tensor, table: torch.Tensor, records: torch.Tensor, T: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """resr_crop_batch on the current stream: arena uint8 [bytes], table int64 [M,3], records int32 [B,4] (checked by check_crop_records
+    before they were uploaded), all on one device -> float32 [B,3,T,T]; `out` is such a tensor to write into."""
+    _lib.require_cuda(arena, "crop_batch")
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError(f"crop_batch: arena must be a contiguous uint8 [bytes] tensor on the device, got {arena.dtype} {tuple(arena.shape)}")
+    if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != CROP_TABLE_COLUMNS or not table.is_contiguous() or table.device != arena.device:
+        raise ValueError("crop_batch: table must be a contiguous int64 [M,3] tensor on the arena's device")
+    if records.dtype != torch.int32 or records.dim() != 2 or records.shape[1] != 4 or not records.is_contiguous() or records.device != arena.device:
+        raise ValueError("crop_batch: records must be a contiguous int32 [B,4] tensor on the arena's device")
+    M, B, T = int(table.shape[0]), int(records.shape[0]), int(T)
+    if T < 1:
+        raise ValueError(f"crop_batch: window side {T} below 1")
+    if out is None:
+        out = torch.empty(B, 3, T, T, dtype=torch.float32, device=arena.device)
+    if out.dtype != torch.float32 or tuple(out.shape) != (B, 3, T, T) or not out.is_contiguous() or out.device != arena.device:
+        raise ValueError(f"crop_batch: out must be a contiguous float32 [B,3,{T},{T}] tensor on the arena's device")
+    _lib.check(_lib.lib().resr_crop_batch(_lib.ptr(arena), _lib.ptr(table), _lib.ptr(records), M, B, T, _lib.ptr(out), _lib.stream_ptr(arena)),
+               "resr_crop_batch")
+    return out
+
+
+# ---- the whole-image source --------------------------------------------------------------------------------------------------------
+class ImageCropSource:
+    """`DeviceTileSource`'s contract -- `next()` -> {"hr": f32 [B,3,T,T], "kernel1", "kernel2", "sinc_kernel": f32 [B,21,21]} or None,
+    `reset()`, `len()`, `original_dataloader.sampler` -- over training images of ANY size held on the device as uint8 in one arena
+    (config.data_source = "images"): a sample is a random T x T window of its image, reflect-padded below / to the right where the image
+    is smaller (`crop_sample_np`), so a folder of whole images needs no offline tiling.
+
+    Batch i+1 is drawn and enqueued inside `next()` of batch i: per sample `sample_crop_draw`, `sample_augment`, then
+    `sample_blur_params` -- `dataset.CropImageDataset.__getitem__`'s order, so a fixed seed gives that loader path's batches at
+    num_workers=0; on a set of T x T tiles no crop draw is made and the draws and batches are `DeviceTileSource`'s.  Per batch: one pinned
+    upload (blur records, crop records) and two launches on the source's side stream (resr_crop_batch, resr_blur_kernels); the consumer is
+    ordered behind them by an event, and the caching allocator is told of the consumer stream.  Nothing synchronises with the host.
+
+    The order of a pass is `sampler`'s (default: torch's RandomSampler over range(M); a DistributedSampler for world > 1), batched with
+    drop_last=True."""
+
+    def __init__(self, arena: torch.Tensor, table: np.ndarray, batch_size: int, tile: int, sampler=None, P: dict = MODEL_P) -> None:
+        _lib.require_cuda(arena, "ImageCropSource")
+        if batch_size < 1 or int(tile) < 1:
+            raise ValueError(f"ImageCropSource: batch_size {batch_size} or tile {tile} below 1")
+        self.table_host = np.ascontiguousarray(np.asarray(table, dtype=np.int64).reshape(-1, CROP_TABLE_COLUMNS))
+        self.arena = arena
+        self.device = arena.device
+        self.batch_size, self.T = int(batch_size), int(tile)
+        self.parameters = P
+        self.M = int(self.table_host.shape[0])
+        self.table = torch.from_numpy(self.table_host).to(self.device)
+        if sampler is None:
+            sampler = torch.utils.data.RandomSampler(range(self.M))
+        self._batches = torch.utils.data.BatchSampler(sampler, self.batch_size, drop_last=True)
+        # what the epoch loops of the train scripts look at: `original_dataloader.sampler.set_epoch`
+        self.original_dataloader = types.SimpleNamespace(sampler=sampler, batch_size=self.batch_size, drop_last=True)
+        self._side = torch.cuda.Stream(device=self.device)
+        self._side.wait_stream(torch.cuda.current_stream(self.device))      # the upload of the arena and the table
+        self._rec_bytes = 3 * self.batch_size * RECORD * 8
+        self._it = None
+        self._staged = None
+        self.reset()
+
+    # -- construction --
+    @classmethod
+    def from_arrays(cls, images, batch_size: int, tile: int, device, sampler=None, max_bytes: int = DEFAULT_MAX_BYTES, P: dict = MODEL_P):
+        """A list of uint8 [h,w,3] arrays of any sizes -> a source on `device`."""
+        if int(tile) < 1:
+            raise ValueError(f"image data source: tile {tile} below 1")
+        images = [np.asarray(a) for a in images]
+        for i, a in enumerate(images):
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+                raise ValueError(f"image data source: image {i} must be uint8 [h,w,3], got {a.dtype} {a.shape}")
+        table = _crop_table([a.shape[:2] for a in images], [f"image {i}" for i in range(len(images))], max_bytes)
+        host = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in images])).pin_memory()
+        return cls(host.to(torch.device(device), non_blocking=True), table, batch_size, tile, sampler, P)
+
+    @classmethod
+    def from_dir(cls, image_dir: str, batch_size: int, tile: int, device, sampler=None, max_bytes: int = DEFAULT_MAX_BYTES, P: dict = MODEL_P,
+                 chunk_bytes: int = 64 << 20):
+        """Every file of `image_dir` (os.listdir order, `.convert("RGB")`), of any size from 1 x 1, through `PairedDeviceSource.from_dirs`'s
+        loader into one arena.  The headers are read first: an empty directory and a total above `max_bytes` are refused before any device
+        work."""
+        from concurrent.futures import ThreadPoolExecutor
+        if int(tile) < 1:
+            raise ValueError(f"image data source: tile {tile} below 1")
+        device = torch.device(device)
+        paths = [os.path.join(image_dir, name) for name in os.listdir(image_dir)]
+        if not paths:
+            raise ValueError(f"image data source: no files in {image_dir}")
+        workers = max(1, min(16, os.cpu_count() or 1))
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            sizes = list(pool.map(_image_size, paths))
+        table = _crop_table(sizes, paths, max_bytes)
+        arenas = _load_arenas({"images": [(paths[i], int(table[i, 0]), sizes[i]) for i in range(len(paths))]}, device, chunk_bytes, workers,
+                              "image data source")
+        return cls(arenas["images"], table, batch_size, tile, sampler, P)
+
+    # -- the batch source --
+    def _stage(self) -> None:
+        try:
+            indices = next(self._it)
+        except StopIteration:
+            self._staged = None
+            return
+        B = self.batch_size
+        if len(indices) != B or min(indices) < 0 or max(indices) >= self.M:
+            raise IndexError(f"image data source: the sampler gave {indices} for {self.M} images and batch size {B}")
+        host = torch.empty(self._rec_bytes + B * 16, dtype=torch.uint8, pin_memory=True)
+        raw = host.numpy()
+        rec = raw[:self._rec_bytes].view(np.float64).reshape(3, B, RECORD)      # kernel-major: [kernel1 | kernel2 | sinc_kernel] x B
+        crops = raw[self._rec_bytes:].view(np.int32).reshape(B, 4)
+        for b, i in enumerate(indices):
+            top, left = sample_crop_draw(int(self.table_host[i, 1]), int(self.table_host[i, 2]), self.T)
+            crops[b] = (i, top, left, sample_augment())
+            rec[:, b] = sample_blur_params(self.parameters)
+        check_crop_records(crops, self.table_host, self.T)
+        check_blur_records(rec, KERNEL_SIDE)
+        with torch.cuda.stream(self._side):
+            dev = host.to(self.device, non_blocking=True)
+            records = dev[:self._rec_bytes].view(torch.float64).view(3 * B, RECORD)
+            hr = crop_batch(self.arena, self.table, dev[self._rec_bytes:].view(torch.int32).view(B, 4), self.T)
+            kernels = blur_kernels(records, KERNEL_SIDE)
+            done = torch.cuda.Event()
+            done.record(self._side)
+        batch = {"hr": hr, "kernel1": kernels[:B], "kernel2": kernels[B:2 * B], "sinc_kernel": kernels[2 * B:]}
+        self._staged = (batch, done)
+
+    def next(self):
+        if self._staged is None:
+            return None
+        batch, done = self._staged
+        consumer = torch.cuda.current_stream(self.device)
+        consumer.wait_event(done)
+        for v in batch.values():
+            v.record_stream(consumer)
+        self._stage()
+        return batch
+
+    def reset(self) -> None:
+        self._it = iter(self._batches)
         self._stage()
 
     def __len__(self) -> int:

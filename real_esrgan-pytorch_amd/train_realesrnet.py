@@ -73,7 +73,7 @@ def load_dataset() -> List[CUDAPrefetcher]:
                                  pin_memory=True, drop_last=False, persistent_workers=workers > 0)
     if config.data_source in config.PAIRED_DATA_SOURCES:
         train_source = _paired_source()
-    elif config.data_source in ("loader", "device"):
+    elif config.data_source in ("loader", "device") + config.IMAGE_DATA_SOURCES:
         train_source = _synthesised_source()
     else:
         raise ValueError(f"config.data_source={config.data_source!r}: expected one of {config.DATA_SOURCES}")
@@ -81,7 +81,10 @@ def load_dataset() -> List[CUDAPrefetcher]:
 
 
 def _synthesised_source():
-    """The train source of "loader" / "device": HR tiles and their blur kernels, for `DegradationPrefetcher` to make the pairs from."""
+    """The train source of "loader" / "device" / "images" / "images_loader": HR tiles and their blur kernels, for
+    `DegradationPrefetcher` to make the pairs from."""
+    if config.data_source in config.IMAGE_DATA_SOURCES:
+        return _image_source()
     train_datasets = TrainValidImageDataset(config.train_image_dir, config.image_size, config.upscale_factor, "Train",
                                             config.degradation_model_parameters_dict)
     workers = config.num_workers
@@ -97,6 +100,25 @@ def _synthesised_source():
         sampler = torch.utils.data.distributed.DistributedSampler(range(count), _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
         return DeviceTileSource.from_dir(config.train_image_dir, config.batch_size, config.device, sampler=sampler,
                                          P=config.degradation_model_parameters_dict)
+    return CUDAPrefetcher(train_dataloader, config.device)
+
+
+def _image_source():
+    """The train source of "images" / "images_loader": whole images of any size in config.train_image_dir, a sample a random
+    config.train_tile window of its image -- the batch dictionary of the tile sources, so the degradation stage takes it unchanged."""
+    from .dataset import CropImageDataset
+    from .device_data import ImageCropSource
+    tile = config.train_window()      # (checked against image_size again: both may have been set after import)
+    if config.data_source == "images":
+        count = len(os.listdir(config.train_image_dir))
+        sampler = torch.utils.data.distributed.DistributedSampler(range(count), _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
+        return ImageCropSource.from_dir(config.train_image_dir, config.batch_size, tile, config.device, sampler=sampler,
+                                        P=config.degradation_model_parameters_dict)
+    train_datasets = CropImageDataset(config.train_image_dir, tile, config.degradation_model_parameters_dict)
+    workers = config.num_workers
+    sampler = torch.utils.data.distributed.DistributedSampler(train_datasets, _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
+    train_dataloader = DataLoader(train_datasets, batch_size=config.batch_size, shuffle=sampler is None, sampler=sampler,
+                                  num_workers=workers, pin_memory=True, drop_last=True, persistent_workers=workers > 0)
     return CUDAPrefetcher(train_dataloader, config.device)
 
 
