@@ -814,6 +814,34 @@ int resr_pair_batch(const uint8_t* hr_arena, const uint8_t* lr_arena, const int6
 int resr_crop_batch(const uint8_t* arena, const int64_t* table, const int32_t* records, int32_t m, int32_t b, int32_t t, float* dst,
                     void* stream);
 
+/* ---- multi-scale copies of the whole-image source (device_data.ImageCropSource, scales / short_side): Pillow's 8-bit LANCZOS resize ----
+ * The rule (device_data.resample_tables_np / resample_u8_np are the definition; they are checked against Pillow itself): per axis a table
+ * of `out` rows, row xx = (xmin, count) and ksize Q22 integer coefficients, ksize = ceil(3 * max(in / out, 1)) * 2 + 1; a pass gives
+ * clip((2^21 + sum_k pixel[xmin + k] * coeff[k]) >> 22, 0, 255) with an int32 sum; the horizontal pass is stored as bytes before the vertical
+ * pass; a pass over an axis whose size does not change is skipped.
+ * resr_resample_ksize: the row length of in_size -> out_size, or RESR_ERR_ARG for a size outside 1..2^31 - 1.  Host only.
+ * resr_resample_tables: bounds int32 [out_size,2] and coeffs int32 [out_size,ksize_capacity] (a row's ksize coefficients, zeros behind them)
+ *   of in_size -> out_size, HOST memory; plain host arithmetic in double with libm's sin and no contraction, no GPU call.  RESR_ERR_ARG: a
+ *   size outside 1..2^31 - 1, a null pointer, ksize_capacity below resr_resample_ksize, and a row with 255 * sum|coeff| + 2^21 >= 2^31 (the
+ *   int32 sum could overflow; never the case for this filter).
+ * resr_resample_u8: j jobs in ONE launch, each one HWC RGB uint8 image of `arena` resampled into another place of the same arena.  A job is 8
+ *   int64: (source offset, h, w, destination offset, oh, ow, row table, column table) -- offsets in bytes, the tables as word offsets into
+ *   `tables` (int32 [table_words], device): at a table's offset `out` pairs (xmin, count), then `out` rows of resr_resample_ksize(in, out)
+ *   coefficients, the row table for h -> oh, the column table for w -> ow; the table of an unchanged axis is not read.  The jobs are passed
+ *   twice: jobs_host (host memory, read by the checks below) and jobs_dev (the same 8 * j words on the device, read by the kernel).  Bit for
+ *   bit device_data.resample_u8_np.  A workgroup owns a 64 x 16 tile of one output, stages source rows in LDS (consecutive lanes on consecutive
+ *   bytes), keeps the horizontal pass's bytes in LDS and stores whole aligned dwords wherever a row starts; int32 multiply-adds; no
+ *   temporary buffer.  Images start at any byte; 64-bit offsets throughout.  The kernel clamps every xmin into 0..in - 1 and every count into
+ *   0..min(ksize, in - xmin): a wrong table gives wrong values, never a read outside the image.  Profiling id 33004, its record's bytes the
+ *   source plus destination bytes of the jobs.
+ *   RESR_ERR_ARG before any launch: a null pointer; j < 1 or j > 65535; arena_bytes < 1; a side below 1 or at or above 2^31; ksize of a changed
+ *   axis outside 1..4096; a table that leaves `tables`; a source or destination that leaves the arena; a destination that shares a byte with a
+ *   source or another destination of the call ("overlapping source and destination"); more than 2^31 - 1 tiles in a job. */
+int resr_resample_ksize(int64_t in_size, int64_t out_size);
+int resr_resample_tables(int64_t in_size, int64_t out_size, int32_t* bounds, int32_t* coeffs, int32_t ksize_capacity);
+int resr_resample_u8(uint8_t* arena, int64_t arena_bytes, const int64_t* jobs_host, const int64_t* jobs_dev, int32_t j, const int32_t* tables, int64_t table_words,
+                     void* stream);
+
 /* ---- training pair pool (device_data.PairPool): a resident queue of finished LR / HR pairs, one exchange launch a step ------------
  * resr_pool_exchange: for sample i < b with slot = slots[i]: lr_out[i] = pool_lr[slot], then pool_lr[slot] = lr_in[i]; the same for hr.
  *   pool_lr fp32 [q, lr_elems], pool_hr fp32 [q, hr_elems]; lr_in / lr_out fp32 [b, lr_elems], hr_in / hr_out fp32 [b, hr_elems]; slots int32

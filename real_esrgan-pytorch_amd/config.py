@@ -101,6 +101,12 @@ if data_source not in DATA_SOURCES:
     raise ValueError(f"RESR_DATA_SOURCE={data_source!r}: expected one of " + ", ".join(repr(name) for name in DATA_SOURCES))
 # The window side T of the two whole-image sources (upstream's crop_pad_size); the other sources never read it.
 train_tile = int(os.environ.get("RESR_TRAIN_TILE", "400"))
+# The multi-scale copies of the two whole-image sources (step 1 of upstream's data preparation, made at load instead of offline): every
+# image also enters the set as its Pillow-LANCZOS copy at each of `train_scales` (RESR_TRAIN_SCALES: comma-separated, each a float or a/b,
+# e.g. "0.75,0.5,1/3") and, with `train_short_side` = S > 0 (RESR_TRAIN_SHORT_SIDE, upstream: 400), as one more copy whose shorter side is
+# S.  Empty / 0 = no copies, the sources as they were.  Parsed and checked by train_copies() below; the other sources never read them.
+train_scales = os.environ.get("RESR_TRAIN_SCALES", "")
+train_short_side = int(os.environ.get("RESR_TRAIN_SHORT_SIDE", "0"))
 paired_lr_image_dir = os.environ.get("RESR_PAIRED_LR_DIR", "")
 if data_source in PAIRED_DATA_SOURCES and not paired_lr_image_dir:
     raise ValueError(f"RESR_DATA_SOURCE={data_source!r} needs RESR_PAIRED_LR_DIR: the directory of the LR partners of the files in train_image_dir")
@@ -205,8 +211,46 @@ def train_window() -> int:
     return train_tile
 
 
+def check_train_copies(scales, short_side):
+    """(scales as a tuple of floats, short_side as an int), or ValueError by name: a scale that is not finite or not in (0, 1) -- 1 would
+    duplicate the image --, a negative short side."""
+    import math
+    try:
+        scales = tuple(float(s) for s in scales)
+    except (TypeError, ValueError):
+        raise ValueError(f"train_scales={scales!r}: expected a sequence of numbers") from None
+    for s in scales:
+        if not math.isfinite(s) or not 0.0 < s < 1.0:
+            raise ValueError(f"train_scales: scale {s} is not a finite number in (0, 1): a copy is smaller than its image (1 would duplicate it)")
+    if isinstance(short_side, float) and not short_side.is_integer():
+        raise ValueError(f"train_short_side={short_side}: expected a whole number of pixels")
+    short_side = int(short_side)
+    if short_side < 0:
+        raise ValueError(f"train_short_side={short_side} is negative: expected 0 (no such copy) or the shorter side of the copy")
+    return scales, short_side
+
+
+def train_copies():
+    """The multi-scale copies of the whole-image data sources as (scales, short_side): `train_scales` -- a string as RESR_TRAIN_SCALES gives
+    it ("0.75,0.5,1/3") or a sequence of numbers -- and `train_short_side`, checked by check_train_copies."""
+    scales = train_scales
+    if isinstance(scales, str):
+        parsed = []
+        for item in (part.strip() for part in scales.split(",")):
+            if not item:
+                continue
+            try:
+                top, _, bottom = item.partition("/")
+                parsed.append(float(top) / float(bottom) if bottom else float(top))
+            except (ValueError, ZeroDivisionError):
+                raise ValueError(f"train_scales={scales!r} (RESR_TRAIN_SCALES): {item!r} is neither a number nor a/b") from None
+        scales = parsed
+    return check_train_copies(scales, train_short_side)
+
+
 if data_source in IMAGE_DATA_SOURCES and mode in ("train_realesrnet", "train_realesrgan"):
     train_window()
+    train_copies()
 
 
 def pair_pool() -> int:

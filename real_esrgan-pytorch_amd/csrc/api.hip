@@ -431,6 +431,18 @@ int resr_pool_exchange(float* pool_lr, float* pool_hr, const float* lr_in, const
     return pool_exchange_dispatch(pool_lr, pool_hr, lr_in, hr_in, lr_out, hr_out, slots, q, b, lr_elems, hr_elems, (hipStream_t)stream);
 }
 
+int resr_resample_ksize(int64_t in_size, int64_t out_size) { return resample_ksize(in_size, out_size); }
+
+int resr_resample_tables(int64_t in_size, int64_t out_size, int32_t* bounds, int32_t* coeffs, int32_t ksize_capacity) {
+    return resample_tables(in_size, out_size, bounds, coeffs, ksize_capacity);
+}
+
+int resr_resample_u8(uint8_t* arena, int64_t arena_bytes, const int64_t* jobs_host, const int64_t* jobs_dev, int32_t j, const int32_t* tables, int64_t table_words,
+                     void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return resample_u8_dispatch(arena, arena_bytes, jobs_host, jobs_dev, j, tables, table_words, (hipStream_t)stream);
+}
+
 int resr_niqe_luma_f32(const float* src, uint8_t* dst, int32_t n, int32_t h, int32_t w, int32_t crop, int32_t out_h, int32_t out_w, void* stream) {
     RESR_DEVICE_SCOPE(stream);
     return niqe_luma_dispatch(src, 0, dst, n, h, w, crop, out_h, out_w, (hipStream_t)stream);

@@ -183,6 +183,12 @@ int crop_batch_dispatch(const uint8_t* arena, const int64_t* table, const int32_
 // the training pair pool: pools [Q, *_elems], batches [B, *_elems] fp32, slots [B] int32 on the device; both outputs null = store only
 int pool_exchange_dispatch(float* pool_lr, float* pool_hr, const float* lr_in, const float* hr_in, float* lr_out, float* hr_out, const int32_t* slots, int Q,
                            int B, int64_t lr_elems, int64_t hr_elems, hipStream_t st);
+// ---- resample_u8.hip: the multi-scale copies of the whole-image source.  Tables: bounds [out,2] (xmin, count), coeffs [out,ksize_capacity] Q22 (host
+// memory, no GPU call); jobs [J,8] int64 (src offset, h, w, dst offset, oh, ow, row table, column table), on the host for the checks and on the device ----
+int resample_ksize(int64_t in_size, int64_t out_size);
+int resample_tables(int64_t in_size, int64_t out_size, int32_t* bounds, int32_t* coeffs, int ksize_capacity);
+int resample_u8_dispatch(uint8_t* arena, int64_t arena_bytes, const int64_t* jobs_host, const int64_t* jobs_dev, int J, const int32_t* tables, int64_t table_words,
+                         hipStream_t st);
 // ---- niqe.hip: the native NIQE stages (include/resr.h).  u8: src is uint8 [n,h,w,3], else fp32 [n,3,h,w] ----
 int niqe_luma_dispatch(const void* src, int u8, uint8_t* dst, int n, int h, int w, int crop, int oh, int ow, hipStream_t st);
 size_t niqe_workspace_bytes(const ResrNiqeDesc* d);

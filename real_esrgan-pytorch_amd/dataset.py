@@ -107,26 +107,40 @@ class CropImageDataset(Dataset):
     directory (os.listdir order), a sample the file decoded, the draws of `device_data.sample_crop_draw` and `sample_augment`, the
     arithmetic of `device_data.crop_sample_np` and the three blur kernels of `TrainValidImageDataset`'s Train branch -- the same
     dictionary, served through `CUDAPrefetcher`.  It is the definition the resident source (`device_data.ImageCropSource`) is judged
-    against: at num_workers=0 both give the same batches under the same seeds.  `tile` is the window side T."""
+    against: at num_workers=0 both give the same batches under the same seeds.  `tile` is the window side T.
 
-    def __init__(self, image_dir: str, tile: int, degradation_model_parameters_dict: dict) -> None:
+    `scales` / `short_side` add upstream's multi-scale copies (`device_data.multiscale_sizes`): with M files and K copies each the set has
+    M * (1 + K) items, item j >= M being copy j // M - 1 of file j % M, resized on the spot by Pillow itself
+    (`Image.resize((ow, oh), Image.LANCZOS)`) -- the bits the resident source's copies are held to."""
+
+    def __init__(self, image_dir: str, tile: int, degradation_model_parameters_dict: dict, scales=(), short_side: int = 0) -> None:
         super().__init__()
         if int(tile) < 1:
             raise ValueError(f"crop dataset: tile {tile} below 1")
+        self.scales, self.short_side = device_data.check_train_copies(scales, short_side)
         self.image_file_names = [os.path.join(image_dir, name) for name in os.listdir(image_dir)]
         if not self.image_file_names:
             raise ValueError(f"crop dataset: no files in {image_dir}")
         self.tile = int(tile)
         self.parameters = degradation_model_parameters_dict
 
+    def _image(self, index: int) -> np.ndarray:
+        M = len(self.image_file_names)
+        image = device_data._read_tile(self.image_file_names[index % M])
+        if index >= M:
+            from PIL import Image
+            oh, ow = device_data.multiscale_sizes(image.shape[0], image.shape[1], self.scales, self.short_side)[index // M - 1]
+            image = np.asarray(Image.fromarray(image).resize((ow, oh), Image.LANCZOS), dtype=np.uint8)
+        return image
+
     def __getitem__(self, batch_index: int) -> dict:
-        image = device_data._read_tile(self.image_file_names[batch_index])
+        image = self._image(batch_index)
         top, left = device_data.sample_crop_draw(image.shape[0], image.shape[1], self.tile)
         code = device_data.sample_augment()
         return _train_item(device_data.crop_sample_np(image, top, left, code, self.tile), self.parameters)
 
     def __len__(self) -> int:
-        return len(self.image_file_names)
+        return len(self.image_file_names) * (1 + len(self.scales) + (self.short_side > 0))
 
 
 class CUDAPrefetcher:

@@ -19,7 +19,10 @@ The whole-image source (config.data_source = "images") lifts the tile source's o
 images of any size resident in one arena, a batch -- random T x T window, reflect padding of an image below T, the tile source's
 rotation and flips, /255, HWC -> CHW -- ONE launch (resr_crop_batch) in front of resr_blur_kernels.  `reflect101` / `crop_sample_np` are
 the definition, `sample_crop_draw` the host's extra draw, `ImageCropSource` the source, with `DeviceTileSource`'s contract; the loader
-path over the same directory is `dataset.CropImageDataset`.
+path over the same directory is `dataset.CropImageDataset`.  With `scales` / `short_side` the set also holds upstream's multi-scale copies of
+every image, made on the device at construction (resr_resample_u8, one launch per group of copies): Pillow's 8-bit LANCZOS resize as an
+integer rule -- `resample_tables_np` / `resample_u8_np` are the definition, `multiscale_sizes` the sizes -- which the loader twin makes with
+Pillow itself, to the same bits.
 
 The training pair pool (config.pair_pool_size > 0) stands behind whichever source hands out (lr, hr, batch): a resident queue of
 finished pairs that a step's batch is exchanged with, so that a batch mixes samples of many degradation plans.  `pool_exchange_np` /
@@ -38,12 +41,13 @@ import numpy as np
 import torch
 
 from . import _lib, imgproc
-from .config import degradation_model_parameters_dict as MODEL_P
+from .config import check_train_copies, degradation_model_parameters_dict as MODEL_P
 
 __all__ = ["sample_blur_params", "blur_kernels_from_params_np", "check_blur_records", "sample_augment", "augment_np",
            "tile_batch", "blur_kernels", "DeviceTileSource", "RECORD", "FAMILIES",
            "paired_sample_np", "sample_paired_draw", "check_paired_records", "paired_files", "pair_batch", "PairedDeviceSource",
            "reflect101", "crop_sample_np", "sample_crop_draw", "check_crop_records", "crop_batch", "ImageCropSource",
+           "resample_ksize", "resample_tables_np", "resample_tables", "resample_u8_np", "multiscale_sizes", "resample_jobs", "resample_u8",
            "pool_exchange_np", "pool_store_np", "sample_pool_slots", "check_pool_slots", "pool_exchange", "pool_store", "PairPool",
            "HostPairPool"]
 
@@ -505,15 +509,16 @@ def _image_size(path: str):
     return h, w
 
 
-def _load_arenas(jobs: dict, device, chunk_bytes: int, workers: int, who: str) -> dict:
+def _load_arenas(jobs: dict, device, chunk_bytes: int, workers: int, who: str, arena_bytes: Optional[dict] = None) -> dict:
     """The loader of the arena sources (`PairedDeviceSource.from_dirs`, `ImageCropSource.from_dir`).  `jobs`: arena name -> its images as
     (path, byte offset, (h, w)), back to back in offset order.  Every file is decoded once with PIL on a thread pool of `workers` and
-    moved through two pinned staging buffers of `chunk_bytes` (or of the largest image) into one uint8 device tensor per arena."""
+    moved through two pinned staging buffers of `chunk_bytes` (or of the largest image) into one uint8 device tensor per arena;
+    `arena_bytes`: arena name -> the size to allocate where an arena is to hold more than these images (the rest is left unwritten)."""
     from concurrent.futures import ThreadPoolExecutor
     totals = {side: jobs[side][-1][1] + jobs[side][-1][2][0] * jobs[side][-1][2][1] * 3 for side in jobs}
     largest = max(h * w * 3 for side in jobs for _, _, (h, w) in jobs[side])
     room = max(largest, min(int(chunk_bytes), max(totals.values())))
-    arenas = {side: torch.empty(totals[side], dtype=torch.uint8, device=device) for side in jobs}
+    arenas = {side: torch.empty(max(totals[side], (arena_bytes or {}).get(side, 0)), dtype=torch.uint8, device=device) for side in jobs}
     staging = [torch.empty(room, dtype=torch.uint8).pin_memory() for _ in range(2)]
     free = [None, None]      # the event behind the last copy out of each staging buffer
 
@@ -744,20 +749,31 @@ def check_crop_records(records, table, T: int) -> np.ndarray:
     return np.ascontiguousarray(rec.astype(np.int32))
 
 
-def _crop_table(sizes, names, max_bytes: int) -> np.ndarray:
-    """(h, w) of every image -> the int64 [M, 3] table (offset, h, w), images back to back; every refusal of a set (host only) is made
-    here and names the image."""
+def _crop_table(sizes, names, max_bytes: int, scales=(), short_side: int = 0) -> np.ndarray:
+    """(h, w) of every image -> the int64 [M * (1 + K), 3] table (offset, h, w), images back to back: rows 0..M-1 the originals, row
+    M * (1 + k) + i copy k of image i (`multiscale_sizes`: the scale copies in the order given, the short-side copy last); every refusal of
+    a set (host only) is made here and names the image."""
+    scales, short_side = check_train_copies(scales, short_side)
     if not names:
         raise ValueError("image data source: no images")
-    table = np.zeros((len(names), CROP_TABLE_COLUMNS), dtype=np.int64)
-    off = 0
-    for i, ((h, w), name) in enumerate(zip(sizes, names)):
+    M = len(names)
+    for (h, w), name in zip(sizes, names):
         if h < 1 or w < 1 or h >= 2 ** 31 or w >= 2 ** 31:
             raise ValueError(f"image data source: {name} is {w}x{h}; a side must be in 1..2^31 - 1")
-        table[i] = (off, h, w)
-        off += h * w * 3
+    copies = [multiscale_sizes(h, w, scales, short_side) for h, w in sizes]
+    K = len(scales) + (short_side > 0)
+    table = np.zeros((M * (1 + K), CROP_TABLE_COLUMNS), dtype=np.int64)
+    off = 0
+    for k in range(1 + K):
+        for i in range(M):
+            h, w = sizes[i] if k == 0 else copies[i][k - 1]
+            if h >= 2 ** 31 or w >= 2 ** 31:
+                raise ValueError(f"image data source: copy {k - 1} of {names[i]} is {w}x{h}; a side must be in 1..2^31 - 1")
+            table[M * k + i] = (off, h, w)
+            off += h * w * 3
     if off > max_bytes:
-        raise ValueError(f"image data source: {len(names)} images are {off} bytes, above max_bytes={max_bytes}")
+        what = f"{M} images" + (f" and their {K} copies each" if K else "")
+        raise ValueError(f"image data source: {what} are {off} bytes, above max_bytes={max_bytes}")
     return table
 
 
@@ -783,6 +799,238 @@ def crop_batch(arena: torch.Tensor, table: torch.Tensor, records: torch.Tensor, 
     return out
 
 
+# ---- multi-scale copies: the definition --------------------------------------------------------------------------------------------
+# Pillow's 8-bit `Image.resize(..., LANCZOS)` restated (tests/test_multiscale_surface.py holds it to Pillow itself, bit for bit): per axis a
+# table of integer coefficients rounded once to Q22, int32 accumulation, the horizontal pass stored as bytes before the vertical pass, a pass
+# over an unchanged axis skipped.
+RESAMPLE_BITS = 22
+RESAMPLE_MAX_TAPS = 4096
+RESAMPLE_JOB_COLUMNS = 8     # (source offset, h, w, destination offset, oh, ow, row table, column table)
+
+
+def _lanczos3(t: float) -> float:
+    if not -3.0 <= t < 3.0:
+        return 0.0
+    out = 1.0
+    for x in (t, t / 3):
+        if x != 0.0:
+            x = x * math.pi
+            out = out * (math.sin(x) / x)
+    return out
+
+
+def resample_ksize(in_size: int, out_size: int, support: float = 3.0) -> int:
+    """The taps of one table row: ceil(support * max(in / out, 1)) * 2 + 1."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"resample tables: in_size={in_size} or out_size={out_size} below 1")
+    return int(math.ceil(support * max(in_size / out_size, 1.0))) * 2 + 1
+
+
+def resample_tables_np(in_size: int, out_size: int, support: float = 3.0):
+    """THE definition of one axis's table: bounds int32 [out, 2] = (xmin, count) and coeffs int32 [out, ksize], all in Python floats (libm's
+    sin): center = (xx + 0.5) * scale, xmin = max(0, int(center - sup + 0.5)), xmax = min(in, int(center + sup + 0.5)), weights
+    lanczos((x + xmin - center + 0.5) * (1 / fs)) summed in index order and each divided by the sum, then int(+-0.5 + w * 2^22), truncating.  A
+    row with 255 * sum|coeff| + 2^21 >= 2^31 (an int32 sum could overflow) is a ValueError."""
+    ksize = resample_ksize(in_size, out_size, support)
+    in_size, out_size = int(in_size), int(out_size)
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    sup, ss = support * fs, 1.0 / fs
+    bounds = np.zeros((out_size, 2), dtype=np.int32)
+    coeffs = np.zeros((out_size, ksize), dtype=np.int32)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(0, int(center - sup + 0.5))
+        xmax = min(in_size, int(center + sup + 0.5))
+        weights = [_lanczos3((x + xmin - center + 0.5) * ss) for x in range(xmax - xmin)]
+        total = 0.0
+        for v in weights:
+            total += v
+        reach = 0
+        for x, v in enumerate(weights):
+            if total != 0.0:
+                v = v / total
+            q = int(-0.5 + v * (1 << RESAMPLE_BITS)) if v < 0 else int(0.5 + v * (1 << RESAMPLE_BITS))
+            coeffs[xx, x] = q
+            reach += abs(q)
+        if 255 * reach + (1 << (RESAMPLE_BITS - 1)) >= 2 ** 31:
+            raise ValueError(f"resample tables: row {xx} of {in_size} -> {out_size}: 255 * sum|coeff| + 2^21 would overflow the int32 accumulator")
+        bounds[xx] = (xmin, xmax - xmin)
+    return bounds, coeffs
+
+
+def resample_tables(in_size: int, out_size: int):
+    """`resample_tables_np` by the library's host builder (resr_resample_tables: the same arithmetic in C++, no GPU call)."""
+    lib = _lib.lib()
+    ksize = int(lib.resr_resample_ksize(int(in_size), int(out_size)))
+    if ksize < 1:
+        _lib.check(ksize, "resr_resample_ksize")
+    bounds = np.zeros((int(out_size), 2), dtype=np.int32)
+    coeffs = np.zeros((int(out_size), ksize), dtype=np.int32)
+    _lib.check(lib.resr_resample_tables(int(in_size), int(out_size), bounds.ctypes.data, coeffs.ctypes.data, ksize), "resr_resample_tables")
+    return bounds, coeffs
+
+
+def _resample_axis_np(a: np.ndarray, bounds: np.ndarray, coeffs: np.ndarray) -> np.ndarray:
+    """One pass along axis 0 of a uint8 array.  As on the device nothing of `bounds` is trusted for addressing: xmin is clamped into
+    0..n - 1, count into 0..min(ksize, n - xmin); the sum is int32 (two's complement)."""
+    n, ksize = a.shape[0], coeffs.shape[1]
+    out = np.empty((bounds.shape[0],) + a.shape[1:], dtype=np.uint8)
+    wide = a.astype(np.int32)
+    for xx in range(bounds.shape[0]):
+        xmin = min(max(int(bounds[xx, 0]), 0), n - 1)
+        count = min(max(int(bounds[xx, 1]), 0), min(ksize, n - xmin))
+        acc = np.full(a.shape[1:], 1 << (RESAMPLE_BITS - 1), dtype=np.int32)
+        for k in range(count):
+            acc += wide[xmin + k] * coeffs[xx, k]
+        out[xx] = np.clip(acc >> RESAMPLE_BITS, 0, 255)
+    return out
+
+
+def resample_u8_np(image_u8: np.ndarray, oh: int, ow: int, tables=None) -> np.ndarray:
+    """THE definition of a copy: uint8 [h, w, 3] -> uint8 [oh, ow, 3].  The horizontal pass runs when ow != w -- acc = 2^21 + sum_x pixel *
+    coeff in int32, out = clip(acc >> 22, 0, 255) --, then the vertical pass on the BYTES of the horizontal result when oh != h; an axis whose
+    size does not change is skipped.  `tables` = ((row bounds, row coeffs), (column bounds, column coeffs)) stands in for
+    `resample_tables_np(h, oh)` / `(w, ow)` (the table of a skipped axis is not read)."""
+    image_u8 = np.asarray(image_u8)
+    oh, ow = int(oh), int(ow)
+    if image_u8.dtype != np.uint8 or image_u8.ndim != 3 or image_u8.shape[2] != 3 or image_u8.shape[0] < 1 or image_u8.shape[1] < 1:
+        raise ValueError(f"resample_u8_np: expected a uint8 [h, w, 3] image, got {image_u8.dtype} {image_u8.shape}")
+    if oh < 1 or ow < 1:
+        raise ValueError(f"resample_u8_np: output {ow}x{oh} below 1")
+    h, w = image_u8.shape[:2]
+    out = image_u8
+    if ow != w:
+        bounds, coeffs = tables[1] if tables is not None else resample_tables_np(w, ow)
+        out = _resample_axis_np(out.transpose(1, 0, 2), np.asarray(bounds), np.asarray(coeffs)).transpose(1, 0, 2)
+    if oh != h:
+        bounds, coeffs = tables[0] if tables is not None else resample_tables_np(h, oh)
+        out = _resample_axis_np(out, np.asarray(bounds), np.asarray(coeffs))
+    return out.copy() if out is image_u8 else np.ascontiguousarray(out)
+
+
+def multiscale_sizes(h: int, w: int, scales=(), short_side: int = 0):
+    """The (h, w) of the copies of an h x w image, in the order given: a scale s gives (max(1, int(h * s)), max(1, int(w * s))); short_side =
+    S > 0 one more, last: the shorter side becomes S and the other max(1, int(S * (longer / shorter)))."""
+    h, w = int(h), int(w)
+    out = [(max(1, int(h * s)), max(1, int(w * s))) for s in scales]
+    S = int(short_side)
+    if S > 0:
+        out.append((S, max(1, int(S * (w / h)))) if h <= w else (max(1, int(S * (h / w))), S))
+    return out
+
+
+def resample_jobs(pairs, place=None):
+    """(source offset, h, w, destination offset, oh, ow) rows -> (jobs int64 [J, 8], tables int32 [words]) for `resample_u8`: the tables of the
+    library's host builder, one per distinct (in, out) pair of a changed axis.  `place(words) -> int32 array` hands out the table buffer
+    (default: a new array); the builds run wherever `place.map` says (default: here, one after the other)."""
+    pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 6)
+    jobs = np.zeros((pairs.shape[0], RESAMPLE_JOB_COLUMNS), dtype=np.int64)
+    jobs[:, :6] = pairs
+    where, words = {}, 0
+    for j, (_, h, w, _, oh, ow) in enumerate(pairs.tolist()):
+        for column, (n, out) in ((6, (h, oh)), (7, (w, ow))):
+            if n != out and (n, out) not in where:
+                where[(n, out)] = words
+                words += out * (2 + _native_ksize(n, out))
+            jobs[j, column] = where.get((n, out), 0)
+    tables = place(max(words, 1)) if place is not None else np.zeros(max(words, 1), dtype=np.int32)
+    base = tables.ctypes.data
+    lib = _lib.lib()
+
+    def build(item):
+        (n, out), at = item
+        _lib.check(lib.resr_resample_tables(n, out, base + 4 * at, base + 4 * (at + 2 * out), _native_ksize(n, out)), "resr_resample_tables")
+    list(getattr(place, "map", map)(build, where.items()))
+    return jobs, tables
+
+
+def _native_ksize(in_size: int, out_size: int) -> int:
+    ksize = int(_lib.lib().resr_resample_ksize(int(in_size), int(out_size)))
+    if ksize < 1:
+        _lib.check(ksize, "resr_resample_ksize")
+    if ksize > RESAMPLE_MAX_TAPS:
+        raise ValueError(f"resample tables: {in_size} -> {out_size} takes {ksize} taps a row, above {RESAMPLE_MAX_TAPS}")
+    return ksize
+
+
+def resample_u8(arena: torch.Tensor, jobs, tables: torch.Tensor, jobs_dev: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """resr_resample_u8 on the current stream: arena uint8 [bytes] and tables int32 [words] on one device, jobs int64 [J, 8] on the HOST
+    (numpy or a CPU tensor: the library checks them before the launch -- sizes, tables and ranges inside their buffers, no destination
+    overlapping a source or another destination); `jobs_dev` is their copy on the device where the caller has made one already.  Every job's
+    image is resampled inside the arena; returns the arena."""
+    _lib.require_cuda(arena, "resample_u8")
+    if arena.dtype != torch.uint8 or arena.dim() != 1 or not arena.is_contiguous():
+        raise ValueError(f"resample_u8: arena must be a contiguous uint8 [bytes] tensor on the device, got {arena.dtype} {tuple(arena.shape)}")
+    if tables.dtype != torch.int32 or tables.dim() != 1 or not tables.is_contiguous() or tables.device != arena.device:
+        raise ValueError("resample_u8: tables must be a contiguous int32 [words] tensor on the arena's device")
+    host = jobs.numpy() if torch.is_tensor(jobs) and not jobs.is_cuda else jobs
+    if not isinstance(host, np.ndarray) or host.dtype != np.int64 or host.ndim != 2 or host.shape[1] != RESAMPLE_JOB_COLUMNS:
+        raise ValueError(f"resample_u8: jobs must be an int64 [J,{RESAMPLE_JOB_COLUMNS}] array on the host")
+    host = np.ascontiguousarray(host)
+    if jobs_dev is None:
+        jobs_dev = torch.from_numpy(host).to(arena.device)
+    if (jobs_dev.dtype != torch.int64 or tuple(jobs_dev.shape) != host.shape or not jobs_dev.is_contiguous() or jobs_dev.device != arena.device):
+        raise ValueError(f"resample_u8: jobs_dev must be a contiguous int64 {list(host.shape)} tensor on the arena's device")
+    _lib.check(_lib.lib().resr_resample_u8(_lib.ptr(arena), int(arena.numel()), host.ctypes.data, _lib.ptr(jobs_dev), int(host.shape[0]), _lib.ptr(tables),
+                                           int(tables.numel()), _lib.stream_ptr(arena)), "resr_resample_u8")
+    return arena
+
+
+class _Staged:
+    """`resample_jobs`'s `place`: the tables go straight into a pinned staging buffer, behind the jobs' words, and are built on a thread pool."""
+
+    def __init__(self, buffer: torch.Tensor, skip: int, pool) -> None:
+        self.buffer, self.skip, self.map = buffer, skip, pool.map
+
+    def __call__(self, words: int) -> np.ndarray:
+        return self.buffer.numpy()[self.skip:self.skip + 4 * words].view(np.int32)
+
+
+def _make_copies(arena: torch.Tensor, table: np.ndarray, M: int, chunk_bytes: int, workers: int) -> None:
+    """The copies of a whole-image arena whose rows 0..M-1 are in place: row r >= M is the resample of row r % M.  Bounded groups of jobs;
+    per group the tables are built on a thread pool of `workers` straight into one of two pinned staging buffers of `chunk_bytes` (or of the
+    largest job), one upload and ONE launch on the current stream.  The host waits only for a staging buffer's earlier upload."""
+    from concurrent.futures import ThreadPoolExecutor
+    rows = table.shape[0]
+    if rows == M:
+        return
+    pairs = [(int(table[r % M, 0]), int(table[r % M, 1]), int(table[r % M, 2]), int(table[r, 0]), int(table[r, 1]), int(table[r, 2])) for r in range(M, rows)]
+
+    def need(h, w, oh, ow, seen):      # bytes a job adds to a group that holds the tables `seen`
+        new = {(n, out) for n, out in ((h, oh), (w, ow)) if n != out and (n, out) not in seen}
+        return 8 * RESAMPLE_JOB_COLUMNS + 4 * sum(out * (2 + _native_ksize(n, out)) for n, out in new), new
+    room = max([int(chunk_bytes)] + [need(h, w, oh, ow, set())[0] + 4 for _, h, w, _, oh, ow in pairs])
+    groups, seen, used = [[]], set(), 4
+    for job in pairs:
+        cost, new = need(*job[1:3], *job[4:6], seen)
+        if groups[-1] and (used + cost > room or len(groups[-1]) == 65535):
+            groups.append([])
+            seen, used = set(), 4
+            cost, new = need(*job[1:3], *job[4:6], seen)
+        groups[-1].append(job)
+        seen |= new
+        used += cost
+    staging = [torch.empty(room, dtype=torch.uint8).pin_memory() for _ in range(min(2, len(groups)))]
+    free = [None, None]      # the event behind the last upload out of each staging buffer
+    with ThreadPoolExecutor(max_workers=workers) as pool:
+        for k, group in enumerate(groups):
+            buf = staging[k % 2]
+            if free[k % 2] is not None:
+                free[k % 2].synchronize()       # start-up only: the buffer is read by an earlier upload
+            head = 8 * RESAMPLE_JOB_COLUMNS * len(group)
+            jobs, tables = resample_jobs(group, _Staged(buf, head, pool))
+            buf.numpy()[:head].view(np.int64)[:] = jobs.reshape(-1)
+            dev = buf[:head + 4 * tables.size].to(arena.device, non_blocking=True)
+            free[k % 2] = torch.cuda.Event()
+            free[k % 2].record(torch.cuda.current_stream(arena.device))
+            resample_u8(arena, jobs, dev[head:].view(torch.int32), jobs_dev=dev[:head].view(torch.int64).view(len(group), RESAMPLE_JOB_COLUMNS))
+    for e in free:
+        if e is not None:
+            e.synchronize()                     # the staging buffers go back to the allocator after this
+
+
 # ---- the whole-image source --------------------------------------------------------------------------------------------------------
 class ImageCropSource:
     """`DeviceTileSource`'s contract -- `next()` -> {"hr": f32 [B,3,T,T], "kernel1", "kernel2", "sinc_kernel": f32 [B,21,21]} or None,
@@ -797,7 +1045,8 @@ class ImageCropSource:
     ordered behind them by an event, and the caching allocator is told of the consumer stream.  Nothing synchronises with the host.
 
     The order of a pass is `sampler`'s (default: torch's RandomSampler over range(M); a DistributedSampler for world > 1), batched with
-    drop_last=True."""
+    drop_last=True.  M counts the table's rows: with multi-scale copies (`from_dir` / `from_arrays`, `scales` / `short_side`) every copy is
+    an image of the set like any other, made once at construction; a batch is the same launch over a longer table."""
 
     def __init__(self, arena: torch.Tensor, table: np.ndarray, batch_size: int, tile: int, sampler=None, P: dict = MODEL_P) -> None:
         _lib.require_cuda(arena, "ImageCropSource")
@@ -824,24 +1073,34 @@ class ImageCropSource:
 
     # -- construction --
     @classmethod
-    def from_arrays(cls, images, batch_size: int, tile: int, device, sampler=None, max_bytes: int = DEFAULT_MAX_BYTES, P: dict = MODEL_P):
-        """A list of uint8 [h,w,3] arrays of any sizes -> a source on `device`."""
+    def from_arrays(cls, images, batch_size: int, tile: int, device, sampler=None, max_bytes: int = DEFAULT_MAX_BYTES, P: dict = MODEL_P,
+                    scales=(), short_side: int = 0):
+        """A list of uint8 [h,w,3] arrays of any sizes -> a source on `device`; `scales` / `short_side`: as `from_dir`."""
         if int(tile) < 1:
             raise ValueError(f"image data source: tile {tile} below 1")
         images = [np.asarray(a) for a in images]
         for i, a in enumerate(images):
             if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
                 raise ValueError(f"image data source: image {i} must be uint8 [h,w,3], got {a.dtype} {a.shape}")
-        table = _crop_table([a.shape[:2] for a in images], [f"image {i}" for i in range(len(images))], max_bytes)
+        table = _crop_table([a.shape[:2] for a in images], [f"image {i}" for i in range(len(images))], max_bytes, scales, short_side)
         host = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in images])).pin_memory()
-        return cls(host.to(torch.device(device), non_blocking=True), table, batch_size, tile, sampler, P)
+        if table.shape[0] == len(images):
+            return cls(host.to(torch.device(device), non_blocking=True), table, batch_size, tile, sampler, P)
+        arena = torch.empty(int(table[-1, 0] + table[-1, 1] * table[-1, 2] * 3), dtype=torch.uint8, device=torch.device(device))
+        arena[:host.numel()].copy_(host, non_blocking=True)
+        _make_copies(arena, table, len(images), 64 << 20, max(1, min(16, os.cpu_count() or 1)))
+        return cls(arena, table, batch_size, tile, sampler, P)
 
     @classmethod
     def from_dir(cls, image_dir: str, batch_size: int, tile: int, device, sampler=None, max_bytes: int = DEFAULT_MAX_BYTES, P: dict = MODEL_P,
-                 chunk_bytes: int = 64 << 20):
+                 chunk_bytes: int = 64 << 20, scales=(), short_side: int = 0):
         """Every file of `image_dir` (os.listdir order, `.convert("RGB")`), of any size from 1 x 1, through `PairedDeviceSource.from_dirs`'s
         loader into one arena.  The headers are read first: an empty directory and a total above `max_bytes` are refused before any device
-        work."""
+        work.
+
+        `scales` (each in (0, 1)) and `short_side` (S > 0) add the multi-scale copies of upstream's data preparation to the set, made on the
+        device once the originals are resident (`multiscale_sizes`, `resample_u8_np`: Pillow's LANCZOS resize, bit for bit): table rows
+        0..M-1 stay the originals, row M * (1 + k) + i is copy k of image i.  The total that `max_bytes` bounds includes the copies."""
         from concurrent.futures import ThreadPoolExecutor
         if int(tile) < 1:
             raise ValueError(f"image data source: tile {tile} below 1")
@@ -852,9 +1111,10 @@ class ImageCropSource:
         workers = max(1, min(16, os.cpu_count() or 1))
         with ThreadPoolExecutor(max_workers=workers) as pool:
             sizes = list(pool.map(_image_size, paths))
-        table = _crop_table(sizes, paths, max_bytes)
+        table = _crop_table(sizes, paths, max_bytes, scales, short_side)
         arenas = _load_arenas({"images": [(paths[i], int(table[i, 0]), sizes[i]) for i in range(len(paths))]}, device, chunk_bytes, workers,
-                              "image data source")
+                              "image data source", {"images": int(table[-1, 0] + table[-1, 1] * table[-1, 2] * 3)})
+        _make_copies(arenas["images"], table, len(paths), chunk_bytes, workers)
         return cls(arenas["images"], table, batch_size, tile, sampler, P)
 
     # -- the batch source --

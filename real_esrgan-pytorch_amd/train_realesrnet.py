@@ -109,12 +109,13 @@ def _image_source():
     from .dataset import CropImageDataset
     from .device_data import ImageCropSource
     tile = config.train_window()      # (checked against image_size again: both may have been set after import)
+    scales, short_side = config.train_copies()      # the multi-scale copies: every image enters the set 1 + K times
     if config.data_source == "images":
-        count = len(os.listdir(config.train_image_dir))
+        count = len(os.listdir(config.train_image_dir)) * (1 + len(scales) + (short_side > 0))
         sampler = torch.utils.data.distributed.DistributedSampler(range(count), _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
         return ImageCropSource.from_dir(config.train_image_dir, config.batch_size, tile, config.device, sampler=sampler,
-                                        P=config.degradation_model_parameters_dict)
-    train_datasets = CropImageDataset(config.train_image_dir, tile, config.degradation_model_parameters_dict)
+                                        P=config.degradation_model_parameters_dict, scales=scales, short_side=short_side)
+    train_datasets = CropImageDataset(config.train_image_dir, tile, config.degradation_model_parameters_dict, scales, short_side)
     workers = config.num_workers
     sampler = torch.utils.data.distributed.DistributedSampler(train_datasets, _WORLD, _RANK, shuffle=True) if _WORLD > 1 else None
     train_dataloader = DataLoader(train_datasets, batch_size=config.batch_size, shuffle=sampler is None, sampler=sampler,
