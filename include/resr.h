@@ -995,7 +995,8 @@ int resr_niqe_score(const ResrNiqeScoreDesc* d, const double* feats, double* sco
  *   n, h or w < 1, crop < 0, a crop that leaves less than 11 x 11, n * tiles_y * tiles_x above 2^31 - 1 (the launch's tile index is
  *   int32; every offset into the images is 64-bit), a workspace smaller than the query's answer, an output or workspace pointer that
  *   is not 8-byte aligned, a float image that is not 4-byte aligned (uint8 images need no alignment at any width).
- *   Not built: RGB-channel scoring, MS-SSIM, padding modes, windows other than 11 taps / sigma 1.5. */
+ *   Not built: MS-SSIM, padding modes, windows other than 11 taps / sigma 1.5.  (RGB channels, 16-bit images and the planes of YUV
+ *   frames: resr_fullref_planes below.) */
 #define RESR_FULLREF_TILE 32
 #define RESR_FULLREF_FINISH_THREADS 256
 typedef struct {
@@ -1007,6 +1008,52 @@ typedef struct {
 } ResrFullRefDesc;
 size_t resr_fullref_workspace_bytes(const ResrFullRefDesc* d);
 int resr_fullref(const ResrFullRefDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, void* stream);
+
+/* ---- native PSNR / SSIM per plane (image_quality_assessment.full_ref_channels_native / full_ref_yuv_native; csrc/fullref.hip) ----
+ * resr_fullref_planes: `planes` planes of h x w integer levels 0 .. peak in each of n images, on both sides -> sse int64, psnr float64,
+ *   ssim float64, each [n][planes].  Two launches whatever n and planes are, no host synchronisation.  peak is 255, 1023 or 65535, one
+ *   value per call.  crop as in resr_fullref: (h - 2 crop) x (w - 2 crop) = hc x wc, at least 11 x 11, is scored.
+ *   A level comes out of a VIEW of the caller's memory, one view per side (the sr_ and hr_ fields), all strides and the base in WORDS:
+ *     word(i, p, y, x) = memory[base + i * image_stride + p * plane_stride + y * row_stride + x * pixel_stride],
+ *     word_bytes 1 or 2: an unsigned integer, level = (word >> shift) & mask;
+ *     word_bytes 4: an fp32 value v, level = trunc(clamp(v * peak, 0, peak)) in fp32, a NaN gives 0 (the rule of every uint8 / uint16
+ *       tail of this library); shift and mask are not used.
+ *     Interleaved uint8 / uint16 pixels [n,h,w,C]: pixel C, row w C, plane 1, image h w C.  fp32 planes [n,C,h,w]: pixel 1, row w, plane
+ *     h w, image C h w.  The chroma of a 4:2:0 frame of H x W luma: base H W, and planar pixel 1, row W / 2, plane H W / 4, or semi-planar
+ *     pixel 2, row W, plane 1, with h = H / 2, w = W / 2.  10-bit words: mask 1023, shift 0 (low bits) or 6 (P010).
+ *     The two sides may use different views.  THE KERNEL TRUSTS the strides and the base, as resr_tile_batch trusts its indices: every
+ *     word a view names for 0 <= i < n, p < planes, y < h, x < w must lie inside the caller's allocation.  The Python layer builds
+ *     views only from tensors whose shape it has checked.  Every offset is 64-bit; loads are byte, word or dword loads of one sample,
+ *     and nothing is assumed aligned beyond the word itself.
+ *   PSNR and SSIM are resr_fullref's, term for term, of the levels X (sr) and Y (hr), with 65025 replaced by peak * peak and
+ *     C1 = (peak * peak) / 10000.0, C2 = (9 * peak * peak) / 10000.0, each ONE float64 division of exact integers (for peak 255 these are
+ *     the bits of 6.5025 and 58.5225): the same window, H pass, W pass, unfused map expression, tile and finish orders; the same
+ *     code.  A one-plane view of the uint8 luma levels of an RGB pair gives the bits of resr_fullref on the pair.  X == Y gives
+ *     ssim == 1.0 exactly.  The thread-private squared differences are summed in 64 bits (seven of 65535^2 overflow 32).
+ *   34604  fullref_planes_tile_kernel: workgroup (image * planes + plane) * tiles + tile; levels lie in LDS as 16-bit words
+ *     (2 * 42 * 44 * 2 bytes; 61,216 bytes in all, two workgroups per CU as before).
+ *   34701  fullref_finish_kernel (the same kernel, peak * peak an argument): one workgroup per (image, plane).
+ *   workspace: resr_fullref_planes_workspace_bytes(d) = n * planes * tiles_y * tiles_x * 16 bytes, 8-byte aligned, [image][plane][tile]
+ *     [sse uint64 | map sum float64] as resr_fullref's; no initialisation needed, readable after the call.  The query needs no device,
+ *     ignores the workspace fields, and returns 0 with the reason in resr_last_error() for a descriptor the entry refuses.
+ *   RESR_ERR_ARG before any launch, "fullref_planes" in resr_last_error(): a null descriptor or pointer; n, planes, h or w < 1;
+ *   planes > 4; crop < 0; a peak other than 255, 1023, 65535; word_bytes not 1, 2 or 4; a mask above the peak or below 0; a shift
+ *   outside 0 .. 15; a pixel or row stride < 1; a negative plane or image stride or base; a crop that leaves less than 11 x 11;
+ *   n * planes * tiles above 2^31 - 1; a workspace smaller than the query's answer; a workspace or output pointer not 8-byte aligned;
+ *   sr or hr not aligned to its word. */
+typedef struct {
+    int32_t n, planes, h, w;   /* the planes as stored, before the crop */
+    int32_t crop, peak;
+    int32_t sr_word_bytes, sr_shift, sr_mask;
+    int32_t hr_word_bytes, hr_shift, hr_mask;
+    int64_t sr_base, sr_pixel_stride, sr_row_stride, sr_plane_stride, sr_image_stride;
+    int64_t hr_base, hr_pixel_stride, hr_row_stride, hr_plane_stride, hr_image_stride;
+    void* workspace;
+    size_t workspace_bytes;
+} ResrFullRefPlanesDesc;
+size_t resr_fullref_planes_workspace_bytes(const ResrFullRefPlanesDesc* d);
+int resr_fullref_planes(const ResrFullRefPlanesDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim,
+                        void* stream);
 
 /* ---- discriminator helpers (model.py:135-203) -------------------------------------------------------- */
 /* 2x2 space-to-depth of an NHWC tensor [n,h,w,c] -> [n,h/2,w/2,4c] (inverse != 0: depth-to-space) */

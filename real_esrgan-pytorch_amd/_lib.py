@@ -19,7 +19,7 @@ _INCLUDE = os.path.join(os.path.dirname(_HERE), "include")   # where csrc/build.
 _ABI = _header.read(os.path.join(_INCLUDE, "resr.h"), os.path.join(_INCLUDE, "resr_debug.h"))
 
 # The structures under their header names without "Resr", fields in header order: ConvDesc, WgradDesc, PackChunk, GeneratorDesc, CompactDesc,
-# YuvDesc, ImageDesc, DiscriminatorDesc, NiqeDesc, NiqeScoreDesc, FullRefDesc, ProfEntry.  The constants: a member of one of these families loses its RESR_ prefix (RESR_CONV_LRELU -> CONV_LRELU);
+# YuvDesc, ImageDesc, DiscriminatorDesc, NiqeDesc, NiqeScoreDesc, FullRefDesc, FullRefPlanesDesc, ProfEntry.  The constants: a member of one of these families loses its RESR_ prefix (RESR_CONV_LRELU -> CONV_LRELU);
 # everything else keeps the header's name (RESR_F16, RESR_F32, RESR_F16X2, RESR_OK, RESR_ERR_*, RESR_VERSION).
 _FAMILIES = ("CONV_", "X2_PLAN_", "COMPACT_", "YUV_")
 globals().update({cls.__name__: cls for cls in _ABI.structs.values()})

@@ -136,6 +136,12 @@ if niqe_tail == "native" and niqe_backend != "native":
 full_ref = os.environ.get("RESR_FULL_REF", "off")
 if full_ref not in ("off", "torch", "native"):
     raise ValueError(f"RESR_FULL_REF={full_ref!r}: expected 'off', 'torch' or 'native'")
+# Which quantity build_full_ref()'s module scores: "y" = the BT.601 luma level (the code as it was); "rgb" = BasicSR's
+# `test_y_channel: false`, the PSNR over all three channels and the mean of the per-channel SSIMs (`full_ref_channels*`), through the
+# backend RESR_FULL_REF selects and under the same scalar names.
+full_ref_channels = os.environ.get("RESR_FULL_REF_CHANNELS", "y")
+if full_ref_channels not in ("y", "rgb"):
+    raise ValueError(f"RESR_FULL_REF_CHANNELS={full_ref_channels!r}: expected 'y' or 'rgb'")
 in_channels = 3
 out_channels = 3
 upscale_factor = 4
@@ -310,13 +316,17 @@ def build_niqe():
 
 
 def build_full_ref():
-    """None for `full_ref` = "off", else a module on `device` with forward(sr, hr) -> (psnr [B], ssim [B]), crop_border = upscale_factor."""
-    from .image_quality_assessment import NativeFullRef, TorchFullRef
+    """None for `full_ref` = "off", else a module on `device` with forward(sr, hr) -> (psnr [B], ssim [B]), crop_border = upscale_factor:
+    of the Y channel, or with `full_ref_channels` = "rgb" (psnr over the three channels, mean of the channels' ssim)."""
+    from .image_quality_assessment import NativeFullRef, NativeFullRefChannels, TorchFullRef, TorchFullRefChannels
     if full_ref not in ("off", "torch", "native"):
         raise ValueError(f"config.full_ref={full_ref!r}: expected 'off', 'torch' or 'native'")
+    if full_ref_channels not in ("y", "rgb"):
+        raise ValueError(f"config.full_ref_channels={full_ref_channels!r}: expected 'y' or 'rgb'")
     if full_ref == "off":
         return None
-    return (NativeFullRef if full_ref == "native" else TorchFullRef)(upscale_factor).to(device=device)
+    modules = {"y": (TorchFullRef, NativeFullRef), "rgb": (TorchFullRefChannels, NativeFullRefChannels)}[full_ref_channels]
+    return modules[full_ref == "native"](upscale_factor).to(device=device)
 
 
 def backward_options() -> dict:

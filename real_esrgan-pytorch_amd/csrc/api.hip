@@ -474,6 +474,13 @@ int resr_fullref(const ResrFullRefDesc* d, const void* sr, const void* hr, int64
     return fullref_dispatch(d, sr, hr, sse, psnr, ssim, (hipStream_t)stream);
 }
 
+size_t resr_fullref_planes_workspace_bytes(const ResrFullRefPlanesDesc* d) { return fullref_planes_workspace_bytes(d); }
+
+int resr_fullref_planes(const ResrFullRefPlanesDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return fullref_planes_dispatch(d, sr, hr, sse, psnr, ssim, (hipStream_t)stream);
+}
+
 int resr_filter2d(const float* src, float* dst, const float* kernel, int32_t n, int32_t c, int32_t h, int32_t w, int32_t kh,
                   int32_t kw, int32_t per_sample, void* stream) {
     RESR_DEVICE_SCOPE(stream);

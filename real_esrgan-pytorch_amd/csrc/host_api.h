@@ -198,6 +198,8 @@ int niqe_score_dispatch(const ResrNiqeScoreDesc* d, const double* feats, double*
 // ---- fullref.hip: PSNR / SSIM of sr against hr (include/resr.h) ----
 size_t fullref_workspace_bytes(const ResrFullRefDesc* d);
 int fullref_dispatch(const ResrFullRefDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, hipStream_t st);
+size_t fullref_planes_workspace_bytes(const ResrFullRefPlanesDesc* d);
+int fullref_planes_dispatch(const ResrFullRefPlanesDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, hipStream_t st);
 // ---- loss.hip. loss, grad: outputs (grad may be null) ----
 int bce_logits_const_dispatch(const float* x, long count, float label, float weight, float* loss, float* grad, float* scratch, hipStream_t st);
 int l1_mean_dispatch(const float* a, const float* b, long count, float weight, float* loss, float* grad, float* scratch, hipStream_t st);

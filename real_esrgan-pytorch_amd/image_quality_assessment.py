@@ -12,12 +12,15 @@ The prior (mean / covariance of the 36 natural-scene features) is the reference'
 Full-reference metrics ("Native PSNR / SSIM"; the reference has none, include/resr.h is the specification): `psnr` / `ssim` /
 `PSNR` / `SSIM` score an SR batch against its ground truth on the Y channel in plain torch float64 (the "torch" backend of
 `config.full_ref`); `full_ref_native` / `NativeFullRef` compute both in one pass of csrc/fullref.hip, from float [B,3,H,W] or uint8
-[B,H,W,3] tensors on either side.  Not built: RGB-channel scoring, MS-SSIM, padding modes, windows other than 11 taps / sigma 1.5.
+[B,H,W,3] tensors on either side.  Not built: MS-SSIM, padding modes, windows other than 11 taps / sigma 1.5.
+Per plane ("Native PSNR / SSIM per plane"; resr_fullref_planes): `full_ref_channels_native` scores every channel of a float,
+uint8 or uint16 image batch (BasicSR's RGB PSNR / SSIM: `psnr_all`, `ssim_mean`), `full_ref_yuv_native` the stored Y, Cb and Cr planes
+of 8- and 10-bit 4:2:0 frames; `full_ref_channels` / `full_ref_yuv` are their torch float64 twins.
 """
 from __future__ import annotations
 
 import math
-from typing import List, Tuple
+from typing import List, NamedTuple, Tuple
 
 import numpy as np
 import torch
@@ -27,7 +30,8 @@ from torch import nn
 from . import imgproc
 
 __all__ = ["NIQE", "niqe", "NativeNIQE", "niqe_native", "niqe_score_native",
-           "PSNR", "SSIM", "psnr", "ssim", "NativeFullRef", "full_ref_native"]
+           "PSNR", "SSIM", "psnr", "ssim", "NativeFullRef", "full_ref_native",
+           "full_ref_channels", "full_ref_channels_native", "full_ref_yuv", "full_ref_yuv_native", "NativeFullRefChannels", "TorchFullRefChannels"]
 
 
 def _gaussian_window(size: int = 7, sigma: float = 7.0 / 6.0) -> torch.Tensor:
@@ -399,17 +403,17 @@ def _ssim_window(like: torch.Tensor) -> torch.Tensor:
     return torch.outer(k, k).to(like).view(1, 1, FULL_REF_WINDOW, FULL_REF_WINDOW)
 
 
-def _psnr_of_levels(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+def _psnr_of_levels(x: torch.Tensor, y: torch.Tensor, peak2: float = 65025.0) -> torch.Tensor:
     mse = ((x - y) ** 2).sum(dim=(1, 2, 3)) / (x.shape[2] * x.shape[3])     # integers below 2^53: the sum is exact
-    return 10.0 * torch.log10(65025.0 / (mse + 1e-8))
+    return 10.0 * torch.log10(peak2 / (mse + 1e-8))
 
 
-def _ssim_of_levels(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+def _ssim_of_levels(x: torch.Tensor, y: torch.Tensor, c1: float = FULL_REF_C1, c2: float = FULL_REF_C2) -> torch.Tensor:
     g = _ssim_window(x)
     mu1, mu2 = F.conv2d(x, g), F.conv2d(y, g)
     m11, m22, m12 = mu1 * mu1, mu2 * mu2, mu1 * mu2
     s11, s22, s12 = F.conv2d(x * x, g) - m11, F.conv2d(y * y, g) - m22, F.conv2d(x * y, g) - m12
-    value = ((2 * m12 + FULL_REF_C1) * (2 * s12 + FULL_REF_C2)) / (((m11 + m22) + FULL_REF_C1) * ((s11 + s22) + FULL_REF_C2))
+    value = ((2 * m12 + c1) * (2 * s12 + c2)) / (((m11 + m22) + c1) * ((s11 + s22) + c2))
     return value.mean(dim=(1, 2, 3))
 
 
@@ -506,3 +510,273 @@ class NativeFullRef(nn.Module):
 
     def forward(self, sr: torch.Tensor, hr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         return full_ref_native(sr, hr, self.crop_border)
+
+
+# ---- full-reference metrics per plane: RGB channels, 16-bit images, the planes of YUV 4:2:0 frames ---------------------------------
+# ("Native PSNR / SSIM per plane"; include/resr.h, resr_fullref_planes, is the specification.)
+FULL_REF_PEAKS = (255, 1023, 65535)
+FULL_REF_CHANNELS = ("y", "rgb")
+
+
+class PlaneView(NamedTuple):
+    """How the levels of `planes` planes of h x w lie in a flat tensor of 1-, 2- or 4-byte words (include/resr.h, resr_fullref_planes):
+    word(i, p, y, x) = flat[base + i * image_stride + p * plane_stride + y * row_stride + x * pixel_stride]; an integer word gives the
+    level (word >> shift) & mask, an fp32 word trunc(clamp(v * peak, 0, peak))."""
+    word_bytes: int
+    shift: int
+    mask: int
+    base: int
+    pixel_stride: int
+    row_stride: int
+    plane_stride: int
+    image_stride: int
+
+
+class FullRefChannels(NamedTuple):
+    """Per-channel sse int64, psnr, ssim float64 [B,C]; psnr_all [B] from the summed sse over C * hc * wc samples (BasicSR's RGB PSNR),
+    ssim_mean [B] the channel mean (BasicSR's RGB SSIM)."""
+    sse: torch.Tensor
+    psnr: torch.Tensor
+    ssim: torch.Tensor
+    psnr_all: torch.Tensor
+    ssim_mean: torch.Tensor
+
+
+class FullRefYuv(NamedTuple):
+    """PSNR and SSIM [N] float64 of the Y, Cb and Cr planes as stored; psnr_avg over all 1.5 H W samples (ffmpeg's "average")."""
+    psnr_y: torch.Tensor
+    psnr_u: torch.Tensor
+    psnr_v: torch.Tensor
+    psnr_avg: torch.Tensor
+    ssim_y: torch.Tensor
+    ssim_u: torch.Tensor
+    ssim_v: torch.Tensor
+
+
+def full_ref_constants(peak: int) -> Tuple[float, float]:
+    """(C1, C2) of the SSIM map at `peak`: one float64 division of exact integers each (6.5025, 58.5225 at 255)."""
+    return (peak * peak) / 10000.0, (9 * peak * peak) / 10000.0
+
+
+_WORD_DTYPES = {torch.uint8: 1, torch.uint16: 2, torch.float32: 4}
+
+
+def image_plane_view(t, name: str, who: str):
+    """(view, B, C, H, W, peak or None) of one side of `full_ref_channels*`: a uint8 / uint16 [B,H,W,C] image batch, C in {1, 3, 4}
+    (peak 255 / 65535), or a float [B,C,H,W] batch, C in {1, 3} (peak None: the other side's).  ValueError for anything else."""
+    what = f"{who}: {name} must be a float [B,C,H,W] tensor, C 1 or 3, or a uint8 / uint16 [B,H,W,C] tensor, C 1, 3 or 4"
+    if not isinstance(t, torch.Tensor) or t.dim() != 4:
+        raise ValueError(f"{what}, got {tuple(t.shape) if isinstance(t, torch.Tensor) else type(t)}")
+    if t.dtype in (torch.uint8, torch.uint16) and t.shape[3] in (1, 3, 4):
+        b, h, w, c = t.shape
+        return PlaneView(t.element_size(), 0, 255 if t.dtype == torch.uint8 else 65535, 0, c, w * c, 1, h * w * c), b, c, h, w, 255 if t.dtype == torch.uint8 else 65535
+    if t.is_floating_point() and t.shape[1] in (1, 3):
+        b, c, h, w = t.shape
+        return PlaneView(4, 0, 0, 0, 1, w, h * w, c * h * w), b, c, h, w, None
+    raise ValueError(f"{what}, got {t.dtype} {tuple(t.shape)}")
+
+
+def yuv_plane_views(pix_fmt: str, h: int, w: int):
+    """(luma view, chroma view, peak) of a 4:2:0 frame [N,3h/2,w] in one of the YUV names of `frames.PIXEL_FORMATS`; the luma view has
+    one h x w plane, the chroma view the two (Cb, Cr) h/2 x w/2 planes."""
+    from .frames import PIXEL_FORMATS
+    f = PIXEL_FORMATS.get(pix_fmt) if isinstance(pix_fmt, str) else None
+    if f is None or f.layout is None:
+        raise ValueError(f"full_ref_yuv: pix_fmt must be one of {tuple(n for n, p in PIXEL_FORMATS.items() if p.layout is not None)}, got {pix_fmt!r}")
+    if h < 2 or w < 2 or h % 2 or w % 2:
+        raise ValueError(f"full_ref_yuv: a 4:2:0 frame needs an even height and width, got {h}x{w}")
+    word, shift, frame = f.bits // 8 if f.bits == 8 else 2, (16 - f.bits if f.high_bits else 0), 3 * h * w // 2
+    luma = PlaneView(word, shift, f.top, 0, 1, w, 0, frame)
+    chroma = (PlaneView(word, shift, f.top, h * w, 2, w, 1, frame) if f.semi_planar
+              else PlaneView(word, shift, f.top, h * w, 1, w // 2, h * w // 4, frame))
+    return luma, chroma, f.top
+
+
+def _check_crop(crop_border, who: str):
+    if isinstance(crop_border, bool) or not isinstance(crop_border, int) or crop_border < 0:
+        raise ValueError(f"{who}: crop_border must be a non-negative int, got {crop_border!r}")
+
+
+def _channels_check(sr, hr, crop_border, who: str):
+    """The checks of `full_ref_channels*` before any device work -> (sr view, hr view, B, C, H, W, peak)."""
+    vs, *ss, ps = image_plane_view(sr, "sr", who)
+    vh, *sh, ph = image_plane_view(hr, "hr", who)
+    _check_crop(crop_border, who)
+    if ss != sh:
+        raise ValueError(f"{who}: sr is {ss[0]} images of {ss[1]} channels of {ss[2]}x{ss[3]}, hr {sh[0]} of {sh[1]} of {sh[2]}x{sh[3]}: the shapes must match")
+    if ps is not None and ph is not None and ps != ph:
+        raise ValueError(f"{who}: sr is {sr.dtype}, hr {hr.dtype}: two integer sides must have one depth")
+    if sr.device != hr.device:
+        raise ValueError(f"{who}: sr is on {sr.device}, hr on {hr.device}: both must be on one device")
+    b, c, h, w = ss
+    if b < 1 or h - 2 * crop_border < FULL_REF_WINDOW or w - 2 * crop_border < FULL_REF_WINDOW:
+        raise ValueError(f"{who}: a crop of {crop_border} leaves {h - 2 * crop_border}x{w - 2 * crop_border} of {b} images of {h}x{w}; the window needs at least 11x11")
+    return vs, vh, b, c, h, w, (ps or ph or 255)
+
+
+def _yuv_check(frames, reference, pix_fmt, ref_pix_fmt, crop_border, who: str):
+    """The checks of `full_ref_yuv*` -> (views of frames, views of the reference, N, H, W, peak)."""
+    from .frames import PIXEL_FORMATS
+    ref_pix_fmt = pix_fmt if ref_pix_fmt is None else ref_pix_fmt
+    for t, name, fmt in ((frames, "frames", pix_fmt), (reference, "reference", ref_pix_fmt)):
+        f = PIXEL_FORMATS.get(fmt) if isinstance(fmt, str) else None
+        if f is None or f.layout is None:
+            raise ValueError(f"{who}: pix_fmt must be one of {tuple(n for n, p in PIXEL_FORMATS.items() if p.layout is not None)}, got {fmt!r}")
+        if not isinstance(t, torch.Tensor) or t.dim() != 3 or t.dtype != f.torch_dtype or t.shape[1] % 3 or t.shape[2] % 2:
+            raise ValueError(f"{who}: {name} must be a {f.torch_dtype} [N,3H/2,W] tensor of {fmt!r} frames, H and W even, got "
+                             f"{(t.dtype, tuple(t.shape)) if isinstance(t, torch.Tensor) else type(t)}")
+    if PIXEL_FORMATS[pix_fmt].bits != PIXEL_FORMATS[ref_pix_fmt].bits:
+        raise ValueError(f"{who}: {pix_fmt!r} frames have {PIXEL_FORMATS[pix_fmt].bits} bits, the {ref_pix_fmt!r} reference {PIXEL_FORMATS[ref_pix_fmt].bits}: both sides must have one depth")
+    _check_crop(crop_border, who)
+    if crop_border % 2:
+        raise ValueError(f"{who}: crop_border must be even (the chroma planes are cropped by half of it), got {crop_border}")
+    if frames.shape != reference.shape:
+        raise ValueError(f"{who}: frames are {tuple(frames.shape)}, the reference {tuple(reference.shape)}: the shapes must match")
+    if frames.device != reference.device:
+        raise ValueError(f"{who}: frames are on {frames.device}, the reference on {reference.device}: both must be on one device")
+    n, h, w = frames.shape[0], frames.shape[1] // 3 * 2, frames.shape[2]
+    if n < 1 or h // 2 - crop_border < FULL_REF_WINDOW or w // 2 - crop_border < FULL_REF_WINDOW:
+        raise ValueError(f"{who}: a crop of {crop_border} leaves {h // 2 - crop_border}x{w // 2 - crop_border} of the {h // 2}x{w // 2} chroma planes; the window needs at least 11x11")
+    fl, fc, peak = yuv_plane_views(pix_fmt, h, w)
+    rl, rc, _ = yuv_plane_views(ref_pix_fmt, h, w)
+    return (fl, fc), (rl, rc), n, h, w, peak
+
+
+def _psnr_from_sse(sse: torch.Tensor, samples: int, peak: int) -> torch.Tensor:
+    """10 log10(peak^2 / (sse / samples + 1e-8)) in float64 on sse's device (sse: exact integers below 2^53)."""
+    return 10.0 * torch.log10(float(peak * peak) / (sse.to(torch.float64) / float(samples) + 1e-8))
+
+
+def _channels_result(sse, psnr, ssim, samples: int, peak: int) -> FullRefChannels:
+    """The [B,C] results plus psnr_all and ssim_mean (channels added in ascending order), all on the device, no host sync."""
+    c = sse.shape[1]
+    total = ssim[:, 0]
+    for i in range(1, c):
+        total = total + ssim[:, i]
+    return FullRefChannels(sse, psnr, ssim, _psnr_from_sse(sse.sum(dim=1), c * samples, peak), total / float(c))
+
+
+def _yuv_result(sse_y, psnr_y, ssim_y, sse_c, psnr_c, ssim_c, hc: int, wc: int, peak: int) -> FullRefYuv:
+    total = sse_y[:, 0] + sse_c[:, 0] + sse_c[:, 1]
+    return FullRefYuv(psnr_y[:, 0], psnr_c[:, 0], psnr_c[:, 1], _psnr_from_sse(total, hc * wc + 2 * (hc // 2) * (wc // 2), peak), ssim_y[:, 0], ssim_c[:, 0], ssim_c[:, 1])
+
+
+def plane_levels(t: torch.Tensor, view: PlaneView, n: int, planes: int, h: int, w: int, peak: int) -> torch.Tensor:
+    """The levels int64 [n,planes,h,w] a view names in the contiguous tensor `t`, in plain torch: the torch backend's loader."""
+    flat = t.contiguous().reshape(-1)
+    ax = lambda count, stride, shape: (torch.arange(count, device=t.device, dtype=torch.int64) * stride).view(shape)
+    at = view.base + ax(n, view.image_stride, (n, 1, 1, 1)) + ax(planes, view.plane_stride, (1, planes, 1, 1)) + ax(h, view.row_stride, (1, 1, h, 1)) + ax(w, view.pixel_stride, (1, 1, 1, w))
+    words = flat[at.reshape(-1)].view(n, planes, h, w)
+    if view.word_bytes == 4:
+        v = words.float() * torch.full((), float(peak), dtype=torch.float32, device=t.device)
+        v = torch.where(v > 0, v, torch.zeros_like(v))                      # a NaN compares false: 0
+        v = torch.where(v < float(peak), v, torch.full_like(v, float(peak)))
+        return v.to(torch.int64)
+    return (words.to(torch.int64) >> view.shift) & view.mask
+
+
+def full_ref_planes(sr, sr_view: PlaneView, hr, hr_view: PlaneView, n: int, planes: int, h: int, w: int, crop: int, peak: int):
+    """The torch float64 twin of `full_ref_planes_native`: (sse int64, psnr, ssim float64), each [n,planes]."""
+    x, y = (plane_levels(t, v, n, planes, h, w, peak)[:, :, crop:h - crop, crop:w - crop].to(torch.float64).reshape(n * planes, 1, h - 2 * crop, w - 2 * crop)
+            for t, v in ((sr, sr_view), (hr, hr_view)))
+    c1, c2 = full_ref_constants(peak)
+    sse = ((x - y) ** 2).sum(dim=(1, 2, 3)).to(torch.int64)
+    return sse.view(n, planes), _psnr_of_levels(x, y, float(peak * peak)).view(n, planes), _ssim_of_levels(x, y, c1, c2).view(n, planes)
+
+
+def full_ref_planes_native(sr, sr_view: PlaneView, hr, hr_view: PlaneView, n: int, planes: int, h: int, w: int, crop: int, peak: int, keep: bool = False):
+    """resr_fullref_planes on the current stream: (sse int64, psnr, ssim float64), each [n,planes]; two launches, no host round trip.
+    sr and hr are contiguous uint8 / uint16 / float32 device tensors whose words the views index; a view that names a word outside
+    its tensor is refused here (the kernel trusts it).  keep=True adds the per-tile partials as views of the workspace: tile sse int64
+    and tile map sums float64, each [n,planes,tiles_y,tiles_x]."""
+    from . import _lib
+    import ctypes as C
+    d = _lib.FullRefPlanesDesc()
+    d.n, d.planes, d.h, d.w, d.crop, d.peak = n, planes, h, w, crop, peak
+    for side, t, v in (("sr", sr, sr_view), ("hr", hr, hr_view)):
+        _lib.require_cuda(t, "full_ref_planes_native")
+        if _WORD_DTYPES.get(t.dtype) != v.word_bytes or not t.is_contiguous():
+            raise ValueError(f"full_ref_planes_native: {side} must be a contiguous tensor of {v.word_bytes}-byte words, got {t.dtype}")
+        for field in PlaneView._fields:
+            setattr(d, f"{side}_{field}", getattr(v, field))
+    need = int(_lib.lib().resr_fullref_planes_workspace_bytes(d))
+    if not need:
+        raise ValueError(f"full_ref_planes_native: {_lib.lib().resr_last_error().decode()}")
+    for side, t, v in (("sr", sr, sr_view), ("hr", hr, hr_view)):           # after the query: every stride is known non-negative
+        last = v.base + (n - 1) * v.image_stride + (planes - 1) * v.plane_stride + (h - 1) * v.row_stride + (w - 1) * v.pixel_stride
+        if last >= t.numel():
+            raise ValueError(f"full_ref_planes_native: the {side} view reaches word {last} of a tensor of {t.numel()}")
+    if sr.device != hr.device:
+        raise ValueError(f"full_ref_planes_native: sr is on {sr.device}, hr on {hr.device}: both must be on one device")
+    ws = torch.empty(need // 8, dtype=torch.int64, device=sr.device)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), need
+    sse = torch.empty((n, planes), dtype=torch.int64, device=sr.device)
+    out = torch.empty((2, n, planes), dtype=torch.float64, device=sr.device)
+    _lib.check(_lib.lib().resr_fullref_planes(C.byref(d), _lib.ptr(sr), _lib.ptr(hr), _lib.ptr(sse), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.stream_ptr(sr)),
+               "resr_fullref_planes")
+    if not keep:
+        return sse, out[0], out[1]
+    ty, tx = full_ref_tiles(h - 2 * crop, w - 2 * crop)
+    parts = ws.view(n, planes, ty, tx, 2)
+    return sse, out[0], out[1], parts[..., 0], parts.view(torch.float64)[..., 1]
+
+
+def _word_tensor(t: torch.Tensor) -> torch.Tensor:
+    return (t if t.dtype in (torch.uint8, torch.uint16) else t.float()).contiguous()
+
+
+def _full_ref_channels(planes_fn, who, sr, hr, crop_border, keep):
+    vs, vh, b, c, h, w, peak = _channels_check(sr, hr, crop_border, who)
+    got = planes_fn(_word_tensor(sr), vs, _word_tensor(hr), vh, b, c, h, w, crop_border, peak, **({"keep": True} if keep else {}))
+    result = _channels_result(*got[:3], (h - 2 * crop_border) * (w - 2 * crop_border), peak)
+    return (result,) + tuple(got[3:]) if keep else result
+
+
+def full_ref_channels(sr: torch.Tensor, hr: torch.Tensor, crop_border: int) -> FullRefChannels:
+    """PSNR / SSIM of every channel of sr against hr in torch float64 (the "torch" backend of RESR_FULL_REF_CHANNELS=rgb).  Each side
+    is float [B,C,H,W] (quantised to the other side's depth; 8 bits when both are float) or uint8 / uint16 [B,H,W,C]."""
+    return _full_ref_channels(full_ref_planes, "full_ref_channels", sr, hr, crop_border, False)
+
+
+def full_ref_channels_native(sr: torch.Tensor, hr: torch.Tensor, crop_border: int, keep: bool = False):
+    """`full_ref_channels` by resr_fullref_planes: one call, two launches for the batch and all channels, no host round trip and no
+    fallback onto torch.  keep=True returns (result, tile sse int64 [B,C,tiles_y,tiles_x], tile map sums float64 of that shape)."""
+    return _full_ref_channels(full_ref_planes_native, "full_ref_channels_native", sr, hr, crop_border, keep)
+
+
+def _full_ref_yuv(planes_fn, who, frames, reference, pix_fmt, ref_pix_fmt, crop_border):
+    (fl, fc), (rl, rc), n, h, w, peak = _yuv_check(frames, reference, pix_fmt, ref_pix_fmt, crop_border, who)
+    frames, reference = frames.contiguous(), reference.contiguous()
+    luma = planes_fn(frames, fl, reference, rl, n, 1, h, w, crop_border, peak)
+    chroma = planes_fn(frames, fc, reference, rc, n, 2, h // 2, w // 2, crop_border // 2, peak)
+    return _yuv_result(*luma[:3], *chroma[:3], h - 2 * crop_border, w - 2 * crop_border, peak)
+
+
+def full_ref_yuv(frames: torch.Tensor, reference: torch.Tensor, pix_fmt: str, ref_pix_fmt=None, crop_border: int = 0) -> FullRefYuv:
+    """PSNR / SSIM of the stored Y, Cb and Cr planes of 4:2:0 frames [N,3H/2,W] against a reference of the same size and depth, in
+    torch float64.  pix_fmt / ref_pix_fmt (default: pix_fmt): "i420", "nv12", "i420p10" or "p010".  crop_border must be even."""
+    return _full_ref_yuv(full_ref_planes, "full_ref_yuv", frames, reference, pix_fmt, ref_pix_fmt, crop_border)
+
+
+def full_ref_yuv_native(frames: torch.Tensor, reference: torch.Tensor, pix_fmt: str, ref_pix_fmt=None, crop_border: int = 0) -> FullRefYuv:
+    """`full_ref_yuv` by two resr_fullref_planes calls, luma and chroma, on the frames where they lie: no conversion to RGB."""
+    return _full_ref_yuv(full_ref_planes_native, "full_ref_yuv_native", frames, reference, pix_fmt, ref_pix_fmt, crop_border)
+
+
+class TorchFullRefChannels(nn.Module):
+    """`forward(sr, hr) -> (psnr_all [B], ssim_mean [B])` of the RGB channels on the torch backend (RESR_FULL_REF_CHANNELS=rgb)."""
+    score = staticmethod(full_ref_channels)
+
+    def __init__(self, crop_border: int) -> None:
+        super().__init__()
+        _check_crop(crop_border, type(self).__name__)
+        self.crop_border = crop_border
+
+    def forward(self, sr: torch.Tensor, hr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        r = self.score(sr, hr, self.crop_border)
+        return r.psnr_all, r.ssim_mean
+
+
+class NativeFullRefChannels(TorchFullRefChannels):
+    """The same through `full_ref_channels_native`."""
+    score = staticmethod(full_ref_channels_native)

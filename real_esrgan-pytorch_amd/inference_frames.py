@@ -2,7 +2,7 @@
 
     python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
         [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode
-         --niqe --niqe_tail torch|native --reference_dir gt/]
+         --niqe --niqe_tail torch|native --reference_dir gt/ --score_channels y|rgb]
 
 The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
 walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
@@ -29,7 +29,9 @@ host never waits for it before the one read at the end.
 `image_quality_assessment.full_ref_native` (PSNR and SSIM of the Y channel, crop_border = the model's factor) on the uint8 device
 frame, on the compute stream, as `--niqe` -- and the scores are read once, at the end: `PSNR/SSIM <file>: <dB> <ssim>` per frame, then
 `PSNR/SSIM mean: ...`.  A missing reference, or one whose size is not the written image's (an `--outscale` that does not lead to the
-reference's size), is an error that names the file, raised before any frame is computed.
+reference's size), is an error that names the file, raised before any frame is computed.  `--score_channels rgb` (default `y`)
+scores the three RGB channels instead -- `full_ref_channels_native`: the PSNR over all three (BasicSR's `test_y_channel: false`) and
+the mean of the channels' SSIMs -- in the same lines.
 """
 import argparse
 import os
@@ -116,7 +118,16 @@ def main(args) -> None:
     references, full_scores = {}, []        # --reference_dir: file name -> uint8 [1,H,W,3] host tensor; one (psnr, ssim) device pair per frame
     if reference_dir:
         from .frames import output_size
-        from .image_quality_assessment import full_ref_native
+        from .image_quality_assessment import full_ref_channels_native, full_ref_native
+        if (getattr(args, "score_channels", None) or "y") not in ("y", "rgb"):
+            raise ValueError(f"--score_channels must be 'y' or 'rgb', got {args.score_channels!r}")
+        if (getattr(args, "score_channels", None) or "y") == "rgb":
+            def score(frame, hr):
+                r = full_ref_channels_native(frame, hr, config.upscale_factor)
+                return r.psnr_all, r.ssim_mean
+        else:
+            def score(frame, hr):
+                return full_ref_native(frame, hr, config.upscale_factor)
         for name in names:
             path = os.path.join(reference_dir, name)
             if not os.path.isfile(path):
@@ -141,7 +152,7 @@ def main(args) -> None:
                     scores.append(niqe_model(frame).reshape(()))
                 if references:
                     hr = references[next(pending)].to(device=frame.device, non_blocking=True)
-                    full_scores.append(torch.stack(full_ref_native(frame if frame.dim() == 4 else frame[None], hr, config.upscale_factor)).reshape(2))
+                    full_scores.append(torch.stack(score(frame if frame.dim() == 4 else frame[None], hr)).reshape(2))
             stream.on_device = on_device
         # copy=False: the pinned view is encoded before the next result is asked for, i.e. before its slot is submitted to again
         for name, sr_image in zip(names, stream.map(decode(), copy=False)):
@@ -182,6 +193,8 @@ def get_parser() -> argparse.ArgumentParser:
                         help="--niqe: the features-to-score tail; native = on the device for the frame, no host round trip")
     parser.add_argument("--reference_dir", type=str, default=None,
                         help="ground-truth directory (same file names): PSNR / SSIM of the Y channel of every RGB frame, scored on the device")
+    parser.add_argument("--score_channels", type=str, default="y", choices=["y", "rgb"],
+                        help="--reference_dir: y = the BT.601 luma level; rgb = PSNR over the three channels, mean of their SSIMs")
     return parser
 
 

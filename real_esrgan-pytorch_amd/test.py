@@ -1,7 +1,8 @@
 """Directory evaluation behind the reference's `test.py` (reference test.py:29-96): super-resolve every image of
 `config.lr_dir` with the EMA weights of `config.model_path`, write the results to `config.sr_dir`, report the mean NIQE.
 With `config.full_ref` = "torch" or "native" (RESR_FULL_REF) every result is also scored against the file of the same name in
-`config.hr_dir`: the mean PSNR and SSIM of the Y channel are printed after the NIQE line.
+`config.hr_dir`: the mean PSNR and SSIM of the Y channel -- or, with `config.full_ref_channels` = "rgb" (RESR_FULL_REF_CHANNELS),
+BasicSR's RGB PSNR and channel-mean SSIM -- are printed after the NIQE line.
 
     RESR_MODE=test python -m real_esrgan_pytorch_amd.test
 

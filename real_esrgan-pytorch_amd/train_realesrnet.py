@@ -314,7 +314,8 @@ def validate(model: nn.Module, ema_model: nn.Module, data_prefetcher: CUDAPrefet
              niqe_model: Any, mode: str, full_ref: Any = None) -> float:
     """Reference train_realesrnet.py:416-488: EMA weights applied for the evaluation, restored afterwards.  full_ref
     (`config.build_full_ref()`; None = off): a module forward(sr, hr) -> (psnr, ssim) that also scores sr against the batch's ground
-    truth; `{mode}/PSNR` and `{mode}/SSIM` then go to the writer and the summary line.  The NIQE average alone is returned."""
+    truth; `{mode}/PSNR` and `{mode}/SSIM` then go to the writer and the summary line (of the Y channel, or with
+    `config.full_ref_channels` = "rgb" of the RGB channels, under the same names).  The NIQE average alone is returned."""
     if mode not in ("Valid", "Test"):
         raise ValueError("Unsupported mode, please use `Valid` or `Test`.")
     batch_time = AverageMeter("Time", ":6.3f", Summary.NONE)
