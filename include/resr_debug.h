@@ -145,6 +145,16 @@ int resr_debug_compact_act(const void* z, void* a, const float* slopes, int64_t 
 int resr_debug_compact_act_bwd(const void* g, const void* z, void* gz, const float* slopes, int64_t pixels, int32_t dtype, float* dslope,
                                float* partial, size_t partial_bytes, const void* amax, void* stream);
 int resr_debug_compact_residual_bwd(const float* gy, float* gx, int32_t n, int32_t h, int32_t w, int32_t s, void* stream);
+/* Test entry (tests/test_compact_train_surface.py, tests/test_gpu_compact_train_passes.py): where resr_compact_forward_train and
+ * resr_compact_backward keep their tensors in the training workspace of `d` (resr.h, "Compact generator: training"), host only -- no
+ * HIP call.  RESR_DEBUG_COMPACT_TRAIN_OFFSETS byte offsets from the workspace's start, in this order:
+ *   0 the pre-scale slot   1 x_in [px][32]   2 z_0 [px][64]   3 a_0 [px][64]
+ *   4 the byte stride from z_k to z_{k+1}, which is also the stride from a_k to a_{k+1} (k = 0 .. num_conv; no offset)
+ *   5 t [N,3 s^2,H,W] fp32   6 g_t [px][cpl]   7 g0   8 g1 (the two ping-pong gradient tensors [px][64])   9 g_xin [px][32]
+ * NHWC tensors of the descriptor's dtype.  Returns the count, or RESR_ERR_ARG for a descriptor the training entries refuse (RESR_F16X2
+ * included), a null `out` or a capacity below the count. */
+#define RESR_DEBUG_COMPACT_TRAIN_OFFSETS 10
+int64_t resr_debug_compact_train_offsets(const ResrCompactDesc* d, int64_t* out, int64_t capacity);
 
 /* Test entry (tests/test_resize_surface.py, tests/test_gpu_resize_kernel.py): the launch plan of csrc/image_resize.hip, host only -- no
  * device work, no tables.  What resr_image_resize and the scaled frame entries would launch for n sources of c x h x w resized to

@@ -336,6 +336,17 @@ size_t compact_train_state_bytes(const ResrCompactDesc* d) {
     return build_tplan(d, t, "compact_train_state_bytes") ? kTrainStateBytes : 0;
 }
 
+// debug/test aid: byte offsets of the named buffers of a training workspace (order documented in include/resr_debug.h); host only
+int64_t compact_train_offsets(const ResrCompactDesc* d, int64_t* out, int64_t cap) {
+    TPlan t;
+    if (!build_tplan(d, t, "compact_train_offsets")) return RESR_ERR_ARG;
+    const size_t offs[] = {t.off_slot, t.off_xin, t.off_z, t.off_a, t.act_bytes, t.off_t, t.off_gt, t.off_g[0], t.off_g[1], t.off_gxin};
+    const int64_t n = sizeof(offs) / sizeof(offs[0]);
+    if (!out || cap < n) return fail(RESR_ERR_ARG, "compact_train_offsets: capacity %lld < %lld", (long long)cap, (long long)n);
+    for (int64_t i = 0; i < n; ++i) out[i] = (int64_t)offs[i];
+    return n;
+}
+
 // compact_pack_table's chunks, then every convolution's transposed chunks in the same order
 int64_t compact_train_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t cap) {
     TPlan t;

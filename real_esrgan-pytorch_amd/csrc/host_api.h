@@ -81,6 +81,7 @@ size_t compact_train_packed_bytes(const ResrCompactDesc* d);
 int64_t compact_train_pack_table(const ResrCompactDesc* d, ResrPackChunk* out, int64_t cap);
 size_t compact_train_workspace_bytes(const ResrCompactDesc* d);
 size_t compact_train_state_bytes(const ResrCompactDesc* d);
+int64_t compact_train_offsets(const ResrCompactDesc* d, int64_t* out, int64_t cap);
 int compact_forward_train(const ResrCompactDesc* d, const float* x, const float* params, const void* packed, void* workspace, size_t workspace_bytes, float* y, hipStream_t st);
 int compact_backward(const ResrCompactDesc* d, const float* gy, const float* params, const void* packed, void* workspace, size_t workspace_bytes, float* grad, float* gx, hipStream_t st);
 // ---- compact_train.hip: the element-wise kernels of that pass on [pixels][64] NHWC tensors (RESR_F16 / RESR_F32).  slopes: 64 floats on the

@@ -69,6 +69,42 @@ def test_host_planning_calls_need_no_gpu(R):
         assert name in L.exported_symbols(), name
 
 
+def test_train_offsets_describe_the_documented_workspace(R):
+    """resr_debug_compact_train_offsets (host only): the buffers in the order include/resr_debug.h documents, each 256-byte aligned, each
+    at least as large as include/resr.h ("Compact generator: training", Workspace) says, the last one inside the workspace."""
+    L = R._lib
+    lib = L.lib()
+    count = L.RESR_DEBUG_COMPACT_TRAIN_OFFSETS
+    assert count == 10 and "resr_debug_compact_train_offsets" in L.exported_symbols()
+    n, h, w = 2, 9, 11
+    px = n * h * w
+    for s in (1, 2, 3, 4):
+        for dtype, es in ((L.RESR_F16, 2), (L.RESR_F32, 4)):
+            for num_conv, act in ((0, L.COMPACT_PRELU), (1, L.COMPACT_LRELU), (3, L.COMPACT_RELU)):
+                d = L.CompactDesc(n, h, w, num_conv, s, act, dtype, 0)
+                out = (C.c_int64 * (count + 1))(*([-7] * (count + 1)))
+                assert lib.resr_debug_compact_train_offsets(C.byref(d), out, count) == count
+                assert out[count] == -7
+                slot, xin, z0, a0, stride, t, gt, g0, g1, gxin = list(out)[:count]
+                assert all(v % 256 == 0 for v in out[:count])
+                assert slot == 0 and slot < xin < z0 < a0 < t < gt < g0 < g1 < gxin                       # the documented order
+                layers, cpl = num_conv + 1, (3 * s * s + 31) // 32 * 32
+                assert xin - slot >= lib.resr_compact_train_state_bytes(C.byref(d)) == 256
+                assert z0 - xin >= px * 32 * es
+                assert stride >= px * 64 * es and a0 - z0 >= layers * stride and t - a0 >= layers * stride    # z_k, a_k: k = 0 .. num_conv
+                assert gt - t >= px * 3 * s * s * 4
+                assert g0 - gt >= px * cpl * es
+                assert g1 - g0 >= px * 64 * es and gxin - g1 >= px * 64 * es
+                assert gxin + px * 32 * es <= lib.resr_compact_train_workspace_bytes(C.byref(d))
+                assert lib.resr_debug_compact_train_offsets(C.byref(d), out, count - 1) == L.RESR_ERR_ARG     # too small a capacity
+                assert lib.resr_debug_compact_train_offsets(C.byref(d), None, count) == L.RESR_ERR_ARG
+    out = (C.c_int64 * count)()
+    for bad in (L.CompactDesc(n, h, w, 1, 2, 0, L.RESR_F16X2, 0), L.CompactDesc(n, h, w, 1, 5, 0, L.RESR_F16, 0), L.CompactDesc(0, h, w, 1, 2, 0, L.RESR_F16, 0),
+                L.CompactDesc(n, h, w, -1, 2, 0, L.RESR_F32, 0)):                                          # what the training entries refuse
+        assert lib.resr_debug_compact_train_offsets(C.byref(bad), out, count) == L.RESR_ERR_ARG
+    assert lib.resr_debug_compact_train_offsets(None, out, count) == L.RESR_ERR_ARG
+
+
 def test_trainable_keyword(R, monkeypatch):
     monkeypatch.delenv("RESR_PRECISION", raising=False)
     assert R.SRVGGNetCompact(num_conv=2).trainable is False

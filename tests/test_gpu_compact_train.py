@@ -18,6 +18,11 @@ Measured on the MI355X (worst over the cases, worst tensor / median; DESIGN, "Co
 against float32's 1.8e-6 / 9.1e-7, the largest ratio on one case 2.5 / 2.0; fast with identity slopes 1.4e-3 / 4.8e-4 and general at
 37 x 53 4.0e-2 / 3.1e-2, both within 1 % of the emulation; the smaller general cases 5.9e-2 / 2.8e-2 (the emulation: the same).  The fast
 training forward sits at 0.93-1.06 x the inference forward's distance from float64 (worst 1.4e-4).
+
+The unpinned general cases stay here as what they are: the distance of a fast-mode step to TRUE autograd, masks that flip included.
+They cannot see a fault that fits inside one tensor's 4e-2.  The sharp judgement is tests/test_gpu_compact_train_passes.py: every pass
+of the same graph on the z_k and a_k the device itself stored, element by element, and the deeper graphs end to end with the masks
+pinned, within 2 x an emulation that sits at 7e-4 -- the small general cases included.
 """
 import ctypes as C
 import functools
