@@ -156,6 +156,25 @@ int resr_debug_compact_residual_bwd(const float* gy, float* gx, int32_t n, int32
 #define RESR_DEBUG_COMPACT_TRAIN_OFFSETS 10
 int64_t resr_debug_compact_train_offsets(const ResrCompactDesc* d, int64_t* out, int64_t capacity);
 
+/* Test entry (tests/test_generator_pass_ref.py, tests/test_gpu_generator_passes.py): where resr_generator_forward (training = 1) and
+ * resr_generator_backward keep their tensors in the workspace of `d` (csrc/generator.hip has the plan), host only -- no HIP call.
+ * resr_generator_buffer_offsets (resr.h) names ws[0] and gS[0] alone and neither the sign words nor the pre-scale slot; this entry names
+ * all of them.  RESR_DEBUG_GENERATOR_TRAIN_OFFSETS values, byte offsets from the workspace's start unless called a stride, in this order
+ * (px = N h w trunk pixels, h, w after the pixel-unshuffle; T = the descriptor's dtype; "planar" = chunk-planar [planes][pixels][32]):
+ *    0 the gradient pre-scale slot (three 32-bit words; resr_generator_chain_state_bytes - 256)   1 x_in [px][ci_pad]
+ *    2 ws[0], planar [6][px][32]: planes x (2) | o1 | o2 | o3 | o4 of dense block 0   3 the byte stride ws[r] -> ws[r + 1] (r < 3 n_blocks)
+ *    4 bits[0]: the sign words of o1..o4 of dense block 0, uint32 [4][px]   5 the byte stride bits[r] -> bits[r + 1]
+ *    6 bits_u2, 7 bits_c3: the sign words of u2 and c3, uint32 [16 px][2] (bit c of word m = channel 32 m + c)
+ *    8 trunk_out, 9 feat: planar [2][px][32]   10 u1: planar [2][4 px][32]   11 u2, 12 c3: planar [2][16 px][32]
+ *   13 ymask: uint8 [N][out_channels][4h][4w]   14 g4 [16 px][32]   15 gA, 16 gB: planar [2][16 px][32]   17 gM1: planar [2][4 px][32]
+ *   18 gF: planar [2][px][32]   19 gT[0], planar [2][px][32]   20 the byte stride gT[i] -> gT[i + 1] (the ring's four slots)
+ *   21 gS[0]: planar [4][px][32], planes g_o4 | g_o3 | g_o2 | g_o1   22 the byte stride gS[i] -> gS[i + 1] (one slab per dense block of an RRDB)
+ *   23 g_xin [px][ci_pad]   24 the weight-gradient slabs (scratch; to the workspace's end)
+ * Every offset is a multiple of 256; RESR_F16X2 tensors are followed by their lo (and q) tensors.  Returns the count, or RESR_ERR_ARG
+ * for a descriptor the training entries refuse, for training == 0, a null `out` or a capacity below the count. */
+#define RESR_DEBUG_GENERATOR_TRAIN_OFFSETS 25
+int64_t resr_debug_generator_train_offsets(const ResrGeneratorDesc* d, int64_t* out, int64_t capacity);
+
 /* Test entry (tests/test_resize_surface.py, tests/test_gpu_resize_kernel.py): the launch plan of csrc/image_resize.hip, host only -- no
  * device work, no tables.  What resr_image_resize and the scaled frame entries would launch for n sources of c x h x w resized to
  * oh x ow through tables of taps_y / taps_x taps; kind: 0 fp32 NCHW output, 1 uint8 HWC, 2 / 3 a YUV 4:2:0 frame of 8- / 10-bit

@@ -736,6 +736,11 @@ int64_t resr_debug_compact_train_offsets(const ResrCompactDesc* d, int64_t* out,
     return compact_train_offsets(d, out, capacity);
 }
 
+// test entry (tests/test_gpu_generator_passes.py): where the RRDB generator's training passes keep their tensors; host only
+int64_t resr_debug_generator_train_offsets(const ResrGeneratorDesc* d, int64_t* out, int64_t capacity) {
+    return generator_train_offsets(d, out, capacity);
+}
+
 // test entry of the resize launch plan (tests/test_resize_surface.py): resize_plan alone.  It only null-checks the tables and looks at
 // the alignment of y, so one aligned placeholder stands for all five.
 int resr_debug_resize_plan(int32_t n, int32_t c, int32_t h, int32_t w, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x,

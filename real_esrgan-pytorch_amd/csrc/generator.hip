@@ -365,6 +365,25 @@ int64_t generator_buffer_offsets(const ResrGeneratorDesc* d, int64_t* out, int64
     return n;
 }
 
+// debug/test aid: byte offsets and strides of EVERY buffer of a training workspace, the sign words and the pre-scale slot included
+// (order documented in include/resr_debug.h); host only
+int64_t generator_train_offsets(const ResrGeneratorDesc* d, int64_t* out, int64_t cap) {
+    Plan p;
+    if (!build_plan(d, p)) return RESR_ERR_ARG;
+    if (!d->training) return fail(RESR_ERR_ARG, "generator_train_offsets: training=0 keeps no training workspace");
+    Bufs b;
+    char* base = reinterpret_cast<char*>(4096);  // fake non-null base, only differences are used
+    carve(p, base, b);
+    auto at = [&](const void* ptr) { return (int64_t)((const char*)ptr - base); };
+    const int64_t offs[] = {at(b.gscale), at(b.x_in), at(b.ws[0]), b.ws[1] - b.ws[0], at(b.bits[0]), b.bits[1] - b.bits[0], at(b.bits_u2), at(b.bits_c3),
+                            at(b.trunk_out), at(b.feat), at(b.u1), at(b.u2), at(b.c3), at(b.ymask), at(b.g4), at(b.gA), at(b.gB), at(b.gM1), at(b.gF),
+                            at(b.gT[0]), b.gT[1] - b.gT[0], at(b.gS[0]), b.gS[1] - b.gS[0], at(b.gxin), at(b.partial)};
+    const int64_t n = sizeof(offs) / sizeof(offs[0]);
+    if (!out || cap < n) return fail(RESR_ERR_ARG, "generator_train_offsets: capacity %lld < %lld", (long long)cap, (long long)n);
+    for (int64_t i = 0; i < n; ++i) out[i] = offs[i];
+    return n;
+}
+
 int64_t generator_pack_table(const ResrGeneratorDesc* d, int backward, ResrPackChunk* out, int64_t cap) {
     Plan p;
     if (!build_plan(d, p)) return RESR_ERR_ARG;

@@ -66,6 +66,7 @@ size_t generator_packed_bytes(const ResrGeneratorDesc* d, int backward);
 size_t generator_chain_state_bytes(const ResrGeneratorDesc* d);
 size_t generator_workspace_bytes(const ResrGeneratorDesc* d);
 int64_t generator_buffer_offsets(const ResrGeneratorDesc* d, int64_t* out, int64_t cap);
+int64_t generator_train_offsets(const ResrGeneratorDesc* d, int64_t* out, int64_t cap);
 int64_t generator_pack_table(const ResrGeneratorDesc* d, int backward, ResrPackChunk* out, int64_t cap);
 int generator_forward(const ResrGeneratorDesc* d, const float* x, const float* params, const void* packed, void* workspace, size_t workspace_bytes, float* y, hipStream_t st);
 int generator_backward(const ResrGeneratorDesc* d, const float* gy, const float* params, const void* packed, void* workspace, size_t workspace_bytes, float* grad, float* gx, hipStream_t st,
