@@ -1055,6 +1055,56 @@ size_t resr_fullref_planes_workspace_bytes(const ResrFullRefPlanesDesc* d);
 int resr_fullref_planes(const ResrFullRefPlanesDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim,
                         void* stream);
 
+/* ---- JPEG encode (jpeg_encode.encode_jpeg; csrc/jpeg_encode.hip): finished frames leave the device as baseline JPEG files ----
+ * resr_jpeg_encode: uint8 [n,h,w,3] RGB frames on the device -> n complete JFIF files (sequential DCT, 8 bits, YCbCr, Huffman) in device
+ *   memory, file i at out + i * out_stride, and lengths int64 [n].  Three launches whatever n is, all on `stream`, no host synchronisation,
+ *   no allocation, no host read of device data (safe under graph capture).  The bytes are a definition of this library's, stated rule by
+ *   rule in DESIGN "JPEG encode" (colour in Q16 with one rounding; 4:2:0 as the colour rule on the exact 2x2 sums of R, G, B; edge
+ *   replication up to the MCU; an exact integer 8x8 DCT with a Q20 matrix, rounded once to Q13; the Annex K tables scaled by the IJG
+ *   quality rule, division half away from zero; the Annex K Huffman tables; restart segments): not libjpeg's bytes, and not the DiffJPEG
+ *   round trip of resr_jpeg_u8 above (non-integer steps, transposed tables: a degradation, not a file format).
+ *   subsampling: RESR_JPEG_444 (MCU 8x8) or RESR_JPEG_420 (MCU 16x16).  quality 1..100.  restart_interval: MCUs per restart segment,
+ *   1..65535, 0 = RESR_JPEG_DEFAULT_INTERVAL; every file has a DRI segment and RSTm markers: the segments are what is encoded in
+ *   parallel (one wave each).
+ *   resr_jpeg_encode_header: HOST only, no GPU call: SOI APP0 DQT SOF0 DHT DRI SOS of the descriptor into host_buf (cap bytes); returns
+ *     its length (RESR_JPEG_HEADER_BYTES; host_buf NULL: the length alone) or RESR_ERR_ARG.  The caller uploads it once per geometry and
+ *     passes it as header_dev / header_len; a header_len that is not the descriptor's is refused.
+ *   Overflow: out_stride is the caller's capacity per file and may be far below max_bytes.  A file that needs more gets lengths[i] =
+ *     -(bytes it needs) and NOT ONE byte of its slot is written; the other files of the batch are unaffected.  No byte at or past
+ *     out + (i + 1) * out_stride is ever written for file i.
+ *   resr_jpeg_encode_max_bytes: a bound no file of this geometry exceeds.  A block costs at most 22 bits for its DC symbol (the longest
+ *     code + size pair of the DC tables: 11 + 11, chroma) and 26 bits (16 + 10) for each of its 63 AC positions (a ZRL of at most 11 bits
+ *     stands for 16 positions, the EOB for at least one): 1660 bits.  A segment of B blocks is at most ceil(1660 B / 8) bytes, its padded
+ *     last byte included; 0xFF stuffing at most doubles it; every segment is followed by two marker bytes (RSTm or EOI).
+ *     max_bytes = RESR_JPEG_HEADER_BYTES + segments * (round16(2 * ceil(1660 B / 8)) + 2): about 6.5 times the raw frame at 4:4:4, 3.2 at 4:2:0.
+ *   workspace: resr_jpeg_encode_workspace_bytes(d) bytes, 8-byte aligned: [segment length int32 x S | pad to 8][segment offset int64 x S]
+ *     [S slots of the segment bound], S = n * segments per frame.  Only the workspace has worst-case room; it needs no initialisation.
+ *   35000 + (4:2:0)  jpeg_segment_kernel: one wave per segment: colour, DCT, quantisation and entropy coding; the coefficients stay in
+ *     registers; stuffed bytes go to the segment's slot.   35100  jpeg_scan_kernel: one workgroup per frame: segment offsets, the
+ *     length, the overflow verdict.   35200  jpeg_copy_kernel: one wave per segment: header, segment, marker into the file.
+ *   The size queries need no device and return 0, with the reason in resr_last_error(), for a descriptor the entry refuses.
+ *   RESR_ERR_ARG before any launch, "jpeg_encode" in resr_last_error(): a null descriptor or pointer; n, h or w < 1; h or w > 65535 (the
+ *   SOF0 fields); quality outside 1..100; an unknown subsampling; a restart interval below 0 or above 65535; n * segments above
+ *   2^31 - 1; a negative out_stride; a header_len other than the descriptor's; a workspace below the query's answer; a workspace or
+ *   lengths pointer that is not 8-byte aligned.  rgb_hwc and out need no alignment (byte loads and stores), out_stride may be odd.
+ *   Not built: progressive or arithmetic coding, optimised Huffman tables, 4:2:2, grey or CMYK files, EXIF / ICC, YUV frame formats as
+ *   the source, byte equality with libjpeg. */
+#define RESR_JPEG_444 0
+#define RESR_JPEG_420 1
+#define RESR_JPEG_DEFAULT_INTERVAL 8
+#define RESR_JPEG_HEADER_BYTES 613
+typedef struct {
+    int32_t n, h, w;
+    int32_t subsampling;          /* RESR_JPEG_444 / RESR_JPEG_420 */
+    int32_t quality;              /* 1..100 */
+    int32_t restart_interval;     /* MCUs per segment; 0 = RESR_JPEG_DEFAULT_INTERVAL */
+} ResrJpegEncDesc;
+size_t resr_jpeg_encode_max_bytes(const ResrJpegEncDesc* d);
+size_t resr_jpeg_encode_workspace_bytes(const ResrJpegEncDesc* d);
+int resr_jpeg_encode_header(const ResrJpegEncDesc* d, uint8_t* host_buf, size_t cap);
+int resr_jpeg_encode(const ResrJpegEncDesc* d, const uint8_t* rgb_hwc, uint8_t* out, int64_t out_stride, int64_t* lengths,
+                     const uint8_t* header_dev, int32_t header_len, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- discriminator helpers (model.py:135-203) -------------------------------------------------------- */
 /* 2x2 space-to-depth of an NHWC tensor [n,h,w,c] -> [n,h/2,w/2,4c] (inverse != 0: depth-to-space) */
 int resr_space_to_depth(const void* src, void* dst, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype,

@@ -474,6 +474,18 @@ int resr_fullref(const ResrFullRefDesc* d, const void* sr, const void* hr, int64
     return fullref_dispatch(d, sr, hr, sse, psnr, ssim, (hipStream_t)stream);
 }
 
+size_t resr_jpeg_encode_max_bytes(const ResrJpegEncDesc* d) { return jpeg_encode_max_bytes(d); }
+
+size_t resr_jpeg_encode_workspace_bytes(const ResrJpegEncDesc* d) { return jpeg_encode_workspace_bytes(d); }
+
+int resr_jpeg_encode_header(const ResrJpegEncDesc* d, uint8_t* host_buf, size_t cap) { return jpeg_encode_header(d, host_buf, cap); }
+
+int resr_jpeg_encode(const ResrJpegEncDesc* d, const uint8_t* rgb_hwc, uint8_t* out, int64_t out_stride, int64_t* lengths, const uint8_t* header_dev, int32_t header_len,
+                     void* workspace, size_t workspace_bytes, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return jpeg_encode_dispatch(d, rgb_hwc, out, out_stride, lengths, header_dev, header_len, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 size_t resr_fullref_planes_workspace_bytes(const ResrFullRefPlanesDesc* d) { return fullref_planes_workspace_bytes(d); }
 
 int resr_fullref_planes(const ResrFullRefPlanesDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, void* stream) {

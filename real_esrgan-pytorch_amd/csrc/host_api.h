@@ -202,6 +202,12 @@ size_t fullref_workspace_bytes(const ResrFullRefDesc* d);
 int fullref_dispatch(const ResrFullRefDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, hipStream_t st);
 size_t fullref_planes_workspace_bytes(const ResrFullRefPlanesDesc* d);
 int fullref_planes_dispatch(const ResrFullRefPlanesDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, hipStream_t st);
+// ---- jpeg_encode.hip: baseline JPEG files written on the device (include/resr.h) ----
+size_t jpeg_encode_max_bytes(const ResrJpegEncDesc* d);
+size_t jpeg_encode_workspace_bytes(const ResrJpegEncDesc* d);
+int jpeg_encode_header(const ResrJpegEncDesc* d, uint8_t* host_buf, size_t cap);
+int jpeg_encode_dispatch(const ResrJpegEncDesc* d, const uint8_t* rgb, uint8_t* out, int64_t out_stride, int64_t* lengths, const uint8_t* header_dev, int header_len, void* workspace,
+                         size_t workspace_bytes, hipStream_t st);
 // ---- loss.hip. loss, grad: outputs (grad may be null) ----
 int bce_logits_const_dispatch(const float* x, long count, float label, float weight, float* loss, float* grad, float* scratch, hipStream_t st);
 int l1_mean_dispatch(const float* a, const float* b, long count, float weight, float* loss, float* grad, float* scratch, hipStream_t st);

@@ -797,6 +797,8 @@ class _Slot:
         self.dev_out: Optional[torch.Tensor] = None      # held until the slot's next submit: its download has been waited for by then
         self.uploaded, self.computed, self.downloaded = (torch.cuda.Event() for _ in range(3))
         self.used = False
+        # FrameStream.jpeg: the file and its length on the device (held like dev_out), the length's pinned twin, the event behind the encode
+        self.jpeg_buf = self.jpeg_len = self.pin_len = self.encoded = None
 
 
 class FrameStream:
@@ -827,7 +829,19 @@ class FrameStream:
 
     `on_device` (attribute, default None): a callable given every result as the device tensor the last kernel wrote ([1, ...] of
     the output format), on the compute stream, right behind the frame's launches and before its download -- a quality score taken
-    from the frame where it lies (`inference_frames --niqe`).  What it returns is dropped; it must not keep the tensor."""
+    from the frame where it lies (`inference_frames --niqe`).  What it returns is dropped; it must not keep the tensor.
+
+    `jpeg` (attribute, like `on_device`; None, the default: everything above): set it to `dict(quality=95, subsampling="420",
+    restart_interval=None)`, any key optional, before the first submit or while no result is outstanding (else RuntimeError) --
+    rgb24 results only (on a stream with a YUV `pix_fmt` / `out_pix_fmt` it is a ValueError, as are options `encode_jpeg` would
+    refuse).  It is an attribute and not a constructor argument because the constructor's parameter list is pinned by the mixed-format
+    surface test.  Every result is then the frame's JPEG FILE, a 1-D
+    uint8 array: `jpeg_encode.encode_jpeg` of the frame on the compute stream, behind `on_device` (which still sees the raw frame),
+    with the raw frame's size as capacity.  Only the file's bytes and its length cross the bus: the length (8 bytes) is downloaded
+    behind the encode, `result()` waits for it and then downloads exactly that many bytes into the slot's pinned buffer (which keeps
+    the raw frame's size).  A file that does not fit the capacity (`jpeg_capacity`, None: the raw frame's bytes) is not written by
+    the device: that frame is downloaded raw and encoded by Pillow on the host with the same quality and subsampling, and counted in
+    `jpeg_fallbacks`."""
 
     PIX_FMTS = tuple(PIXEL_FORMATS)
 
@@ -844,6 +858,7 @@ class FrameStream:
         self.out_matrix = out_matrix if out_matrix is not None or self.out_pix_fmt == "rgb24" else matrix
         frame_format((self.out_pix_fmt, self.out_matrix), "FrameStream")
         self._fmt = _StreamFormat(pix_fmt, matrix, self.out_pix_fmt, self.out_matrix)
+        self._jpeg, self.jpeg_capacity, self.jpeg_fallbacks = None, None, 0
         self.outscale = check_outscale(outscale, getattr(model, "upscale_factor", 0), "FrameStream")
         self._plan = None
         param = next(iter(model.parameters()), None)
@@ -858,6 +873,26 @@ class FrameStream:
         self._up = self._down = self._compute = None
         self._closed = False
         self.on_device = None
+
+    @property
+    def jpeg(self) -> Optional[dict]:
+        """None, or the options every result is encoded with (class docstring): quality, subsampling, restart_interval."""
+        return self._jpeg
+
+    @jpeg.setter
+    def jpeg(self, options: Optional[dict]) -> None:
+        if options is not None:
+            from . import jpeg_encode
+            if not isinstance(options, dict) or set(options) - {"quality", "subsampling", "restart_interval"}:
+                raise ValueError(f"FrameStream: jpeg must be None or a dict with keys among quality, subsampling, restart_interval, got {options!r}")
+            if self.pix_fmt != "rgb24" or self.out_pix_fmt != "rgb24":
+                raise ValueError(f"FrameStream: jpeg needs rgb24 frames on both sides, got pix_fmt={self.pix_fmt!r}, out_pix_fmt={self.out_pix_fmt!r} "
+                                 "(encoding from the YUV formats is not built)")
+            options = dict(quality=options.get("quality", 95), subsampling=options.get("subsampling", "420"), restart_interval=options.get("restart_interval"))
+            jpeg_encode._check_options(options["quality"], options["subsampling"], options["restart_interval"], None, "FrameStream")
+        if len(self):
+            raise RuntimeError(f"FrameStream: {len(self)} results are outstanding; take them before jpeg is changed (they were submitted under the old setting)")
+        self._jpeg = options
 
     @staticmethod
     def check_frame(frame) -> None:
@@ -888,7 +923,30 @@ class FrameStream:
     def _take(self, slot: _Slot, copy: bool) -> np.ndarray:
         slot.downloaded.synchronize()
         _lib.chain_health()          # every launch of this frame has reported: a broken chained launch must not reach the caller
+        if self.jpeg is not None:
+            return self._take_jpeg(slot, copy)
         return slot.np_out.copy() if copy else slot.np_out
+
+    def _take_jpeg(self, slot: _Slot, copy: bool) -> np.ndarray:
+        """The file of a slot whose length has arrived (`downloaded`): its bytes, or on overflow the raw frame and Pillow."""
+        size = int(slot.pin_len[0])
+        flat = slot.pin_out.view(-1)
+        with torch.cuda.stream(self._down):      # (the download stream is behind the encode already: it carried the length)
+            if size >= 0:
+                flat[:size].copy_(slot.jpeg_buf[0, :size], non_blocking=True)
+            else:
+                slot.pin_out.copy_(slot.dev_out, non_blocking=True)
+            slot.downloaded.record(self._down)
+        slot.downloaded.synchronize()
+        if size >= 0:
+            data = flat.numpy()[:size]
+            return data.copy() if copy else data
+        import io
+        from PIL import Image
+        self.jpeg_fallbacks += 1
+        file = io.BytesIO()
+        Image.fromarray(slot.np_out).save(file, "JPEG", quality=self.jpeg["quality"], subsampling={"444": 0, "420": 2}[self.jpeg["subsampling"]])
+        return np.frombuffer(file.getvalue(), dtype=np.uint8).copy()
 
     def _allocate(self, h: int, w: int) -> None:
         self._drain()
@@ -928,9 +986,20 @@ class FrameStream:
             slot.computed.record(self._compute)
             if self.on_device is not None:
                 self.on_device(slot.dev_out)
+            if self.jpeg is not None:
+                from .jpeg_encode import encode_jpeg
+                raw = slot.dev_out[0].numel()
+                slot.jpeg_buf, slot.jpeg_len = encode_jpeg(slot.dev_out, capacity=min(self.jpeg_capacity or raw, raw), **self.jpeg)
+                if slot.pin_len is None:
+                    slot.pin_len, slot.encoded = torch.empty(1, dtype=torch.int64, pin_memory=True), torch.cuda.Event()
+                slot.encoded.record(self._compute)
         with torch.cuda.stream(self._down):
-            self._down.wait_event(slot.computed)
-            slot.pin_out.copy_(slot.dev_out, non_blocking=True)
+            if self.jpeg is not None:            # the length alone; the bytes follow when result() knows how many (_take_jpeg)
+                self._down.wait_event(slot.encoded)
+                slot.pin_len.copy_(slot.jpeg_len, non_blocking=True)
+            else:
+                self._down.wait_event(slot.computed)
+                slot.pin_out.copy_(slot.dev_out, non_blocking=True)
             slot.downloaded.record(self._down)
         slot.used = True
         self._pending.append(slot)

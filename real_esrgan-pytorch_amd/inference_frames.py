@@ -2,7 +2,8 @@
 
     python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
         [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode
-         --niqe --niqe_tail torch|native --reference_dir gt/ --score_channels y|rgb]
+         --niqe --niqe_tail torch|native --reference_dir gt/ --score_channels y|rgb
+         --ext same|jpg --jpeg_quality 95 --jpeg_subsampling 420|444 --decode_workers K]
 
 The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
 walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
@@ -32,6 +33,14 @@ frame, on the compute stream, as `--niqe` -- and the scores are read once, at th
 reference's size), is an error that names the file, raised before any frame is computed.  `--score_channels rgb` (default `y`)
 scores the three RGB channels instead -- `full_ref_channels_native`: the PSNR over all three (BasicSR's `test_y_channel: false`) and
 the mean of the channels' SSIMs -- in the same lines.
+
+`--ext jpg` (default `same`: everything above, byte for byte): every frame of the RGB stream leaves the device as a finished JPEG file
+(`FrameStream.jpeg`, `jpeg_encode.encode_jpeg`: `--jpeg_quality` 1..100, `--jpeg_subsampling` 420 or 444) and is written as
+`<stem>.jpg` straight from the returned bytes: the host encodes nothing and a few MB cross the bus instead of the raw frame.  `--niqe`
+and `--reference_dir` still score the raw frame.  Files that `--keep_mode` takes out of the stream keep their extension and the PIL path.
+
+`--decode_workers K` (default 0: the in-line decode above): the input files are decoded by a pool of min(K, 16) threads, in input
+order, at most 2 K files ahead of the stream.
 """
 import argparse
 import os
@@ -141,11 +150,35 @@ def main(args) -> None:
                 references[name] = torch.from_numpy(np.array(image.convert("RGB")))[None]
     pending = iter(names)                   # on_device sees the frames in input order
 
-    def decode():
-        for name in names:
-            yield np.asarray(Image.open(os.path.join(args.inputs_dir, name)).convert("RGB"))
+    def decode_one(name):
+        return np.asarray(Image.open(os.path.join(args.inputs_dir, name)).convert("RGB"))
 
+    workers = min(int(getattr(args, "decode_workers", 0) or 0), 16)
+    if workers < 0:
+        raise ValueError(f"--decode_workers must be at least 0, got {args.decode_workers!r}")
+
+    def decode():
+        if not workers:
+            for name in names:
+                yield decode_one(name)
+            return
+        import collections
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max_workers=workers) as pool:       # in input order, at most 2 * workers files ahead
+            ahead, todo = collections.deque(), iter(names)
+            for name in todo:
+                ahead.append(pool.submit(decode_one, name))
+                if len(ahead) >= 2 * workers:
+                    yield ahead.popleft().result()
+            while ahead:
+                yield ahead.popleft().result()
+
+    ext = getattr(args, "ext", None) or "same"
+    if ext not in ("same", "jpg"):
+        raise ValueError(f"--ext must be 'same' or 'jpg', got {ext!r}")
     with FrameStream(model, depth=getattr(args, "depth", 2) or 2, outscale=getattr(args, "outscale", None)) as stream:
+        if ext == "jpg":                         # (`same` leaves the stream as it always was)
+            stream.jpeg = dict(quality=getattr(args, "jpeg_quality", None) or 95, subsampling=str(getattr(args, "jpeg_subsampling", None) or "420"))
         if niqe_model is not None or references:
             def on_device(frame):
                 if niqe_model is not None:
@@ -156,7 +189,12 @@ def main(args) -> None:
             stream.on_device = on_device
         # copy=False: the pinned view is encoded before the next result is asked for, i.e. before its slot is submitted to again
         for name, sr_image in zip(names, stream.map(decode(), copy=False)):
-            Image.fromarray(sr_image).save(os.path.join(args.output_dir, name))
+            if ext == "jpg":                     # sr_image is the finished file: written as it came off the device
+                name = os.path.splitext(name)[0] + ".jpg"
+                with open(os.path.join(args.output_dir, name), "wb") as file:
+                    file.write(sr_image)
+            else:
+                Image.fromarray(sr_image).save(os.path.join(args.output_dir, name))
             print(f"SR image save to `{os.path.join(args.output_dir, name)}`")
     if scores:
         values = torch.stack(scores).cpu().tolist()      # the one read-back of the scores
@@ -195,6 +233,11 @@ def get_parser() -> argparse.ArgumentParser:
                         help="ground-truth directory (same file names): PSNR / SSIM of the Y channel of every RGB frame, scored on the device")
     parser.add_argument("--score_channels", type=str, default="y", choices=["y", "rgb"],
                         help="--reference_dir: y = the BT.601 luma level; rgb = PSNR over the three channels, mean of their SSIMs")
+    parser.add_argument("--ext", type=str, default="same", choices=["same", "jpg"],
+                        help="same: write every file under its own name and format (PIL); jpg: RGB frames are encoded on the device, written as <stem>.jpg")
+    parser.add_argument("--jpeg_quality", type=int, default=95, help="--ext jpg: quality 1..100 (the IJG scale)")
+    parser.add_argument("--jpeg_subsampling", type=str, default="420", choices=["420", "444"], help="--ext jpg: chroma subsampling")
+    parser.add_argument("--decode_workers", type=int, default=0, help="decode the input files on a pool of min(K, 16) threads (0: in line)")
     return parser
 
 
