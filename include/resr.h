@@ -1105,6 +1105,50 @@ int resr_jpeg_encode_header(const ResrJpegEncDesc* d, uint8_t* host_buf, size_t 
 int resr_jpeg_encode(const ResrJpegEncDesc* d, const uint8_t* rgb_hwc, uint8_t* out, int64_t out_stride, int64_t* lengths,
                      const uint8_t* header_dev, int32_t header_len, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PNG encode (png_encode.encode_png; csrc/png_encode.hip): finished images leave the device as PNG files, lossless ----
+ * resr_png_encode: uint8 or uint16 [n,h,w,channels] images on the device (channels 1, 3, 4: PNG colour types 0, 2, 6; bit_depth 8 or 16,
+ *   the samples in the device's own byte order) -> n complete PNG files in device memory, file i at out + i * out_stride, and lengths
+ *   int64 [n].  Four launches whatever n is, all on `stream`, no host synchronisation, no allocation, no host read of device data (safe
+ *   under graph capture).  The bytes are a definition of this library's, stated rule by rule in DESIGN "PNG encode" (numpy form:
+ *   tests/png_encode_ref.py): per row the filter of libpng's heuristic (smallest sum of |int8|, ties to the lowest type); the filtered
+ *   stream F, T = h (1 + w bpp) bytes, cut into segments of segment_bytes (64..65535, 0 = RESR_PNG_DEFAULT_SEGMENT_BYTES); per segment
+ *   one deflate block of literals and distance-1 matches (zlib's Z_RLE) with its own length-limited Huffman codes, or a stored block
+ *   where that is not smaller; every segment but the last is followed by an empty stored block (the Z_SYNC_FLUSH marker), so every
+ *   segment is whole bytes; one IDAT chunk per segment with its own CRC-32; a last IDAT with the Adler-32 of F; IEND.  Any reader accepts
+ *   the files; they are not libpng's bytes.
+ *   resr_png_encode_header: HOST only, no GPU call: the signature, IHDR and an IDAT holding the zlib header 78 01 into host_buf (cap
+ *     bytes); returns its length (RESR_PNG_HEADER_BYTES for every geometry; host_buf NULL: the length alone) or RESR_ERR_ARG.  The caller
+ *     uploads it once per geometry and passes it as header_dev / header_bytes.
+ *   Overflow: out_stride is the caller's capacity per file and may be below max_bytes.  A file that needs more gets lengths[i] = -(bytes
+ *     it needs) and NOT ONE byte of its slot is written; the other files of the batch are unaffected.  No byte at or past
+ *     out + (i + 1) * out_stride is ever written for file i.
+ *   resr_png_encode_max_bytes: T + 17 K + 75 for K = ceil(T / segment_bytes) segments: a stored block is 5 + its bytes and no block is
+ *     longer, 12 bytes frame a chunk, 47 + 28 bytes are the header and the two last chunks.
+ *   workspace: resr_png_encode_workspace_bytes(d) bytes, 16-byte aligned, no initialisation needed: per segment its length, offset, CRC
+ *     and Adler partials, per frame the Adler-32, per row its filter type, per segment a slot of round16(segment_bytes + 5) bytes.
+ *   35300 png_filter_kernel (one wave per row)   35400 png_segment_kernel (one wave per segment: tokens, codes, bits, CRC)
+ *   35500 png_scan_kernel (one workgroup per frame)   35600 png_copy_kernel (one wave per segment).
+ *   The size queries need no device and return 0, with the reason in resr_last_error(), for a descriptor the entry refuses.
+ *   RESR_ERR_ARG before any launch, "png_encode" in resr_last_error(): a null descriptor or pointer; n, h or w < 1; h or w above
+ *   (2^31 - 1) / bpp; channels other than 1, 3, 4; a bit depth other than 8, 16; segment_bytes other than 0 or 64..65535; n * segments or
+ *   n * h above 2^31 - 1; a negative out_stride; header_bytes other than RESR_PNG_HEADER_BYTES; a workspace below the query's answer or
+ *   not 16-byte aligned; lengths not 8-byte aligned.  src needs the alignment of its samples, out none; out_stride may be odd.
+ *   Not built: LZ77 matches beyond distance 1, fixed-Huffman blocks, palette and grey+alpha types, interlace, ancillary chunks, byte
+ *   equality with libpng. */
+#define RESR_PNG_DEFAULT_SEGMENT_BYTES 16384
+#define RESR_PNG_HEADER_BYTES 47
+typedef struct {
+    int32_t n, h, w;
+    int32_t channels;             /* 1, 3, 4 */
+    int32_t bit_depth;            /* 8, 16 */
+    int32_t segment_bytes;        /* bytes of the filtered stream per deflate block; 0 = RESR_PNG_DEFAULT_SEGMENT_BYTES */
+} ResrPngEncDesc;
+size_t resr_png_encode_max_bytes(const ResrPngEncDesc* d);
+size_t resr_png_encode_workspace_bytes(const ResrPngEncDesc* d);
+int resr_png_encode_header(const ResrPngEncDesc* d, uint8_t* host_buf, size_t cap);
+int resr_png_encode(const ResrPngEncDesc* d, const void* src, uint8_t* out, int64_t out_stride, int64_t* lengths,
+                    const uint8_t* header_dev, int32_t header_bytes, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- discriminator helpers (model.py:135-203) -------------------------------------------------------- */
 /* 2x2 space-to-depth of an NHWC tensor [n,h,w,c] -> [n,h/2,w/2,4c] (inverse != 0: depth-to-space) */
 int resr_space_to_depth(const void* src, void* dst, int32_t n, int32_t h, int32_t w, int32_t c, int32_t dtype,

@@ -190,6 +190,18 @@ int resr_debug_resize_plan(int32_t n, int32_t c, int32_t h, int32_t w, int32_t o
 int resr_debug_image_resize_plan(int32_t h, int32_t w, int32_t s, int32_t oh, int32_t ow, int32_t taps_y, int32_t taps_x, int32_t channels,
                                  int32_t bits, int32_t* plan);
 
+/* Test entries of the PNG encoder (tests/test_gpu_png_encode.py; csrc/png_encode.hip).
+ * resr_png_debug_deflate: the segment, scan and copy kernels of resr_png_encode over a given byte stream on the device (the filter
+ *   stage skipped: the stream is F itself), segments of segment_bytes (64..65535).  out receives a bare zlib stream -- 78 01, the
+ *   segments' blocks, the Adler-32 -- and *length its size, or the negative of it where out_capacity is too small (nothing written).
+ *   workspace: resr_png_debug_deflate_workspace_bytes, 16-byte aligned.  Enqueued on `stream`, no synchronisation.
+ * resr_png_debug_build_code: the device's length-limited code construction (one wave) on counts uint32 [nsym] (device memory, 1..286
+ *   symbols, their sum below 2^32) with code lengths limited to `limit` (1..15, 2^limit >= nsym) -> lengths uint8 [nsym] (device). */
+size_t resr_png_debug_deflate_workspace_bytes(int64_t stream_bytes, int32_t segment_bytes);
+int resr_png_debug_deflate(const uint8_t* stream_dev, int64_t stream_bytes, int32_t segment_bytes, uint8_t* out, int64_t out_capacity,
+                           int64_t* length, void* workspace, size_t workspace_bytes, void* stream);
+int resr_png_debug_build_code(const uint32_t* counts_dev, int32_t nsym, int32_t limit, uint8_t* lengths_dev, void* stream);
+
 /* What THIS board sustains once it sits at its power cap (bench.py's `roofline.vs_sustained`): 256 workgroups launched back to
  * back for `seconds` (last third timed) -- mode 1: an LDS-DMA stream over `src` (`bytes` >= 64 MB of readable device memory),
  * mode 2: eight waves per workgroup issuing v_mfma_f32_32x32x16_f16 on random f16 operands, mode 3: both at once.  Returns the

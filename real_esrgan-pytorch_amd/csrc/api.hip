@@ -486,6 +486,31 @@ int resr_jpeg_encode(const ResrJpegEncDesc* d, const uint8_t* rgb_hwc, uint8_t* 
     return jpeg_encode_dispatch(d, rgb_hwc, out, out_stride, lengths, header_dev, header_len, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+size_t resr_png_encode_max_bytes(const ResrPngEncDesc* d) { return png_encode_max_bytes(d); }
+
+size_t resr_png_encode_workspace_bytes(const ResrPngEncDesc* d) { return png_encode_workspace_bytes(d); }
+
+int resr_png_encode_header(const ResrPngEncDesc* d, uint8_t* host_buf, size_t cap) { return png_encode_header(d, host_buf, cap); }
+
+int resr_png_encode(const ResrPngEncDesc* d, const void* src, uint8_t* out, int64_t out_stride, int64_t* lengths, const uint8_t* header_dev, int32_t header_bytes, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return png_encode_dispatch(d, src, out, out_stride, lengths, header_dev, header_bytes, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t resr_png_debug_deflate_workspace_bytes(int64_t stream_bytes, int32_t segment_bytes) { return png_debug_deflate_workspace_bytes(stream_bytes, segment_bytes); }
+
+int resr_png_debug_deflate(const uint8_t* stream_dev, int64_t stream_bytes, int32_t segment_bytes, uint8_t* out, int64_t out_capacity, int64_t* length, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return png_debug_deflate(stream_dev, stream_bytes, segment_bytes, out, out_capacity, length, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int resr_png_debug_build_code(const uint32_t* counts_dev, int32_t nsym, int32_t limit, uint8_t* lengths_dev, void* stream) {
+    RESR_DEVICE_SCOPE(stream);
+    return png_debug_build_code(counts_dev, nsym, limit, lengths_dev, (hipStream_t)stream);
+}
+
 size_t resr_fullref_planes_workspace_bytes(const ResrFullRefPlanesDesc* d) { return fullref_planes_workspace_bytes(d); }
 
 int resr_fullref_planes(const ResrFullRefPlanesDesc* d, const void* sr, const void* hr, int64_t* sse, double* psnr, double* ssim, void* stream) {

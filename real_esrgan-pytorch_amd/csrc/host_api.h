@@ -208,6 +208,16 @@ size_t jpeg_encode_workspace_bytes(const ResrJpegEncDesc* d);
 int jpeg_encode_header(const ResrJpegEncDesc* d, uint8_t* host_buf, size_t cap);
 int jpeg_encode_dispatch(const ResrJpegEncDesc* d, const uint8_t* rgb, uint8_t* out, int64_t out_stride, int64_t* lengths, const uint8_t* header_dev, int header_len, void* workspace,
                          size_t workspace_bytes, hipStream_t st);
+// ---- png_encode.hip: PNG files written on the device (include/resr.h), and its test entries (include/resr_debug.h) ----
+size_t png_encode_max_bytes(const ResrPngEncDesc* d);
+size_t png_encode_workspace_bytes(const ResrPngEncDesc* d);
+int png_encode_header(const ResrPngEncDesc* d, uint8_t* host_buf, size_t cap);
+int png_encode_dispatch(const ResrPngEncDesc* d, const void* src, uint8_t* out, int64_t out_stride, int64_t* lengths, const uint8_t* header_dev, int header_len, void* workspace,
+                        size_t workspace_bytes, hipStream_t st);
+size_t png_debug_deflate_workspace_bytes(int64_t stream_bytes, int segment_bytes);
+int png_debug_deflate(const uint8_t* stream_dev, int64_t stream_bytes, int segment_bytes, uint8_t* out, int64_t out_capacity, int64_t* length, void* workspace, size_t workspace_bytes,
+                      hipStream_t st);
+int png_debug_build_code(const uint32_t* counts_dev, int nsym, int limit, uint8_t* lengths_dev, hipStream_t st);
 // ---- loss.hip. loss, grad: outputs (grad may be null) ----
 int bce_logits_const_dispatch(const float* x, long count, float label, float weight, float* loss, float* grad, float* scratch, hipStream_t st);
 int l1_mean_dispatch(const float* a, const float* b, long count, float weight, float* loss, float* grad, float* scratch, hipStream_t st);

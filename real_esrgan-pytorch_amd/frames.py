@@ -797,7 +797,7 @@ class _Slot:
         self.dev_out: Optional[torch.Tensor] = None      # held until the slot's next submit: its download has been waited for by then
         self.uploaded, self.computed, self.downloaded = (torch.cuda.Event() for _ in range(3))
         self.used = False
-        # FrameStream.jpeg: the file and its length on the device (held like dev_out), the length's pinned twin, the event behind the encode
+        # FrameStream.jpeg / .png: the file and its length on the device (held like dev_out), the length's pinned twin, the event behind the encode
         self.jpeg_buf = self.jpeg_len = self.pin_len = self.encoded = None
 
 
@@ -841,7 +841,14 @@ class FrameStream:
     behind the encode, `result()` waits for it and then downloads exactly that many bytes into the slot's pinned buffer (which keeps
     the raw frame's size).  A file that does not fit the capacity (`jpeg_capacity`, None: the raw frame's bytes) is not written by
     the device: that frame is downloaded raw and encoded by Pillow on the host with the same quality and subsampling, and counted in
-    `jpeg_fallbacks`."""
+    `jpeg_fallbacks`.
+
+    `png` (attribute, the lossless twin of `jpeg`; None, the default: everything above): set it to `dict(segment_bytes=None)`, the key
+    optional, under the same rules -- rgb24 results only, no result outstanding, and not together with `jpeg` (ValueError, whichever is
+    set second).  Every result is then the frame's PNG FILE, a 1-D uint8 array: `png_encode.encode_png` of the frame on the compute
+    stream, behind `on_device`, downloaded length first and then exactly its bytes.  The capacity is the raw frame's bytes, the size of the
+    slot's pinned buffer (`png_capacity`, None: that; a smaller value lowers it): a picture's file is below it, noise's is not.  A file that
+    does not fit is not written by the device: that frame is downloaded raw and saved by Pillow as PNG, and counted in `png_fallbacks`."""
 
     PIX_FMTS = tuple(PIXEL_FORMATS)
 
@@ -859,6 +866,7 @@ class FrameStream:
         frame_format((self.out_pix_fmt, self.out_matrix), "FrameStream")
         self._fmt = _StreamFormat(pix_fmt, matrix, self.out_pix_fmt, self.out_matrix)
         self._jpeg, self.jpeg_capacity, self.jpeg_fallbacks = None, None, 0
+        self._png, self.png_capacity, self.png_fallbacks = None, None, 0
         self.outscale = check_outscale(outscale, getattr(model, "upscale_factor", 0), "FrameStream")
         self._plan = None
         param = next(iter(model.parameters()), None)
@@ -890,9 +898,33 @@ class FrameStream:
                                  "(encoding from the YUV formats is not built)")
             options = dict(quality=options.get("quality", 95), subsampling=options.get("subsampling", "420"), restart_interval=options.get("restart_interval"))
             jpeg_encode._check_options(options["quality"], options["subsampling"], options["restart_interval"], None, "FrameStream")
+            if self._png is not None:
+                raise ValueError("FrameStream: jpeg and png cannot both be set: a result is one file (set png to None first)")
         if len(self):
             raise RuntimeError(f"FrameStream: {len(self)} results are outstanding; take them before jpeg is changed (they were submitted under the old setting)")
         self._jpeg = options
+
+    @property
+    def png(self) -> Optional[dict]:
+        """None, or the options every result is encoded with as a PNG file (class docstring): segment_bytes."""
+        return self._png
+
+    @png.setter
+    def png(self, options: Optional[dict]) -> None:
+        if options is not None:
+            from . import png_encode
+            if not isinstance(options, dict) or set(options) - {"segment_bytes"}:
+                raise ValueError(f"FrameStream: png must be None or a dict with no key but segment_bytes, got {options!r}")
+            if self.pix_fmt != "rgb24" or self.out_pix_fmt != "rgb24":
+                raise ValueError(f"FrameStream: png needs rgb24 frames on both sides, got pix_fmt={self.pix_fmt!r}, out_pix_fmt={self.out_pix_fmt!r} "
+                                 "(the YUV formats have no PNG colour type)")
+            options = dict(segment_bytes=options.get("segment_bytes"))
+            png_encode._check_options(options["segment_bytes"], None, "FrameStream")
+            if self._jpeg is not None:
+                raise ValueError("FrameStream: jpeg and png cannot both be set: a result is one file (set jpeg to None first)")
+        if len(self):
+            raise RuntimeError(f"FrameStream: {len(self)} results are outstanding; take them before png is changed (they were submitted under the old setting)")
+        self._png = options
 
     @staticmethod
     def check_frame(frame) -> None:
@@ -923,7 +955,7 @@ class FrameStream:
     def _take(self, slot: _Slot, copy: bool) -> np.ndarray:
         slot.downloaded.synchronize()
         _lib.chain_health()          # every launch of this frame has reported: a broken chained launch must not reach the caller
-        if self.jpeg is not None:
+        if self.jpeg is not None or self.png is not None:
             return self._take_jpeg(slot, copy)
         return slot.np_out.copy() if copy else slot.np_out
 
@@ -943,8 +975,12 @@ class FrameStream:
             return data.copy() if copy else data
         import io
         from PIL import Image
-        self.jpeg_fallbacks += 1
         file = io.BytesIO()
+        if self.png is not None:
+            self.png_fallbacks += 1
+            Image.fromarray(slot.np_out).save(file, "PNG")
+            return np.frombuffer(file.getvalue(), dtype=np.uint8).copy()
+        self.jpeg_fallbacks += 1
         Image.fromarray(slot.np_out).save(file, "JPEG", quality=self.jpeg["quality"], subsampling={"444": 0, "420": 2}[self.jpeg["subsampling"]])
         return np.frombuffer(file.getvalue(), dtype=np.uint8).copy()
 
@@ -986,15 +1022,19 @@ class FrameStream:
             slot.computed.record(self._compute)
             if self.on_device is not None:
                 self.on_device(slot.dev_out)
-            if self.jpeg is not None:
-                from .jpeg_encode import encode_jpeg
+            if self.jpeg is not None or self.png is not None:
                 raw = slot.dev_out[0].numel()
-                slot.jpeg_buf, slot.jpeg_len = encode_jpeg(slot.dev_out, capacity=min(self.jpeg_capacity or raw, raw), **self.jpeg)
+                if self.png is not None:
+                    from .png_encode import encode_png
+                    slot.jpeg_buf, slot.jpeg_len = encode_png(slot.dev_out, capacity=min(self.png_capacity or raw, raw), **self.png)
+                else:
+                    from .jpeg_encode import encode_jpeg
+                    slot.jpeg_buf, slot.jpeg_len = encode_jpeg(slot.dev_out, capacity=min(self.jpeg_capacity or raw, raw), **self.jpeg)
                 if slot.pin_len is None:
                     slot.pin_len, slot.encoded = torch.empty(1, dtype=torch.int64, pin_memory=True), torch.cuda.Event()
                 slot.encoded.record(self._compute)
         with torch.cuda.stream(self._down):
-            if self.jpeg is not None:            # the length alone; the bytes follow when result() knows how many (_take_jpeg)
+            if self.jpeg is not None or self.png is not None:      # the length alone; the bytes follow when result() knows how many (_take_jpeg)
                 self._down.wait_event(slot.encoded)
                 slot.pin_len.copy_(slot.jpeg_len, non_blocking=True)
             else:

@@ -3,7 +3,7 @@
     python -m real_esrgan_pytorch_amd.inference_frames --inputs_dir lr/ --output_dir sr/ --weights_path g.pth \\
         [--model_type rrdb|compact --num_conv 16 --act_type prelu --precision fast|exact16|strict --depth 2 --outscale 2 --keep_mode
          --niqe --niqe_tail torch|native --reference_dir gt/ --score_channels y|rgb
-         --ext same|jpg --jpeg_quality 95 --jpeg_subsampling 420|444 --decode_workers K]
+         --ext same|jpg|png --jpeg_quality 95 --jpeg_subsampling 420|444 --decode_workers K]
 
 The model is built and the checkpoint loaded exactly as `inference.py` does for one image; the files of `--inputs_dir` are then
 walked in sorted order: PIL decode -> `FrameStream.map` (upload, compute and download of successive frames overlap) -> PIL
@@ -38,6 +38,11 @@ the mean of the channels' SSIMs -- in the same lines.
 (`FrameStream.jpeg`, `jpeg_encode.encode_jpeg`: `--jpeg_quality` 1..100, `--jpeg_subsampling` 420 or 444) and is written as
 `<stem>.jpg` straight from the returned bytes: the host encodes nothing and a few MB cross the bus instead of the raw frame.  `--niqe`
 and `--reference_dir` still score the raw frame.  Files that `--keep_mode` takes out of the stream keep their extension and the PIL path.
+
+`--ext png`: the lossless twin -- every frame of the RGB stream leaves the device as a finished PNG file (`FrameStream.png`,
+`png_encode.encode_png`) and is written as `<stem>.png` from the returned bytes; the host's single-threaded PNG encoder, the slowest stage
+of `--ext same` on large frames, is not run.  With `--keep_mode` the kept files go the same way: `upscale_image`, then `encode_png` of the
+device tensor -- an `L` file becomes an 8-bit grey PNG, an `RGBA` or `LA` file an 8-bit RGBA one, an `I;16` file a 16-bit grey one.
 
 `--decode_workers K` (default 0: the in-line decode above): the input files are decoded by a pool of min(K, 16) threads, in input
 order, at most 2 K files ahead of the stream.
@@ -90,11 +95,15 @@ def kept_mode(image):
     return KEPT_MODES.get(image.mode)
 
 
-def upscale_kept(model, image, mode: str, outscale=None):
-    """One PIL image of a kept mode through `frames.upscale_image` (at `outscale`) -> the PIL image of that mode."""
+def upscale_kept(model, image, mode: str, outscale=None, png: bool = False):
+    """One PIL image of a kept mode through `frames.upscale_image` (at `outscale`) -> the PIL image of that mode; `png`: the bytes of
+    its PNG file instead, encoded on the device (`png_encode.png_files`)."""
     from PIL import Image
     array = np.array(image if image.mode == mode else image.convert(mode))      # (a copy: PIL's own buffer is read-only)
     images = torch.from_numpy(array)[None].to(next(model.parameters()).device)
+    if png:
+        from .png_encode import png_files
+        return png_files(upscale_image(model, images, outscale=outscale))[0]
     return Image.fromarray(upscale_image(model, images, outscale=outscale)[0].cpu().numpy())
 
 
@@ -111,9 +120,17 @@ def main(args) -> None:
                 if kept_mode(image) is not None:
                     kept[name] = kept_mode(image)
         names = [name for name in names if name not in kept]
+    ext = getattr(args, "ext", None) or "same"
+    if ext not in ("same", "jpg", "png"):
+        raise ValueError(f"--ext must be 'same', 'jpg' or 'png', got {ext!r}")
     for name, mode in kept.items():
         with Image.open(os.path.join(args.inputs_dir, name)) as image:
-            upscale_kept(model, image, mode, getattr(args, "outscale", None)).save(os.path.join(args.output_dir, name))
+            if ext == "png":                     # the device's bytes, as for the stream below
+                name = os.path.splitext(name)[0] + ".png"
+                with open(os.path.join(args.output_dir, name), "wb") as file:
+                    file.write(upscale_kept(model, image, mode, getattr(args, "outscale", None), png=True))
+            else:
+                upscale_kept(model, image, mode, getattr(args, "outscale", None)).save(os.path.join(args.output_dir, name))
         print(f"SR image save to `{os.path.join(args.output_dir, name)}`")
 
     scores = []         # --niqe: one device scalar per frame of the stream, in input order
@@ -173,12 +190,11 @@ def main(args) -> None:
             while ahead:
                 yield ahead.popleft().result()
 
-    ext = getattr(args, "ext", None) or "same"
-    if ext not in ("same", "jpg"):
-        raise ValueError(f"--ext must be 'same' or 'jpg', got {ext!r}")
     with FrameStream(model, depth=getattr(args, "depth", 2) or 2, outscale=getattr(args, "outscale", None)) as stream:
         if ext == "jpg":                         # (`same` leaves the stream as it always was)
             stream.jpeg = dict(quality=getattr(args, "jpeg_quality", None) or 95, subsampling=str(getattr(args, "jpeg_subsampling", None) or "420"))
+        if ext == "png":
+            stream.png = {}
         if niqe_model is not None or references:
             def on_device(frame):
                 if niqe_model is not None:
@@ -189,8 +205,8 @@ def main(args) -> None:
             stream.on_device = on_device
         # copy=False: the pinned view is encoded before the next result is asked for, i.e. before its slot is submitted to again
         for name, sr_image in zip(names, stream.map(decode(), copy=False)):
-            if ext == "jpg":                     # sr_image is the finished file: written as it came off the device
-                name = os.path.splitext(name)[0] + ".jpg"
+            if ext != "same":                    # sr_image is the finished file: written as it came off the device
+                name = os.path.splitext(name)[0] + "." + ext
                 with open(os.path.join(args.output_dir, name), "wb") as file:
                     file.write(sr_image)
             else:
@@ -233,8 +249,8 @@ def get_parser() -> argparse.ArgumentParser:
                         help="ground-truth directory (same file names): PSNR / SSIM of the Y channel of every RGB frame, scored on the device")
     parser.add_argument("--score_channels", type=str, default="y", choices=["y", "rgb"],
                         help="--reference_dir: y = the BT.601 luma level; rgb = PSNR over the three channels, mean of their SSIMs")
-    parser.add_argument("--ext", type=str, default="same", choices=["same", "jpg"],
-                        help="same: write every file under its own name and format (PIL); jpg: RGB frames are encoded on the device, written as <stem>.jpg")
+    parser.add_argument("--ext", type=str, default="same", choices=["same", "jpg", "png"],
+                        help="same: write every file under its own name and format (PIL); jpg / png: frames are encoded on the device, written as <stem>.jpg / <stem>.png")
     parser.add_argument("--jpeg_quality", type=int, default=95, help="--ext jpg: quality 1..100 (the IJG scale)")
     parser.add_argument("--jpeg_subsampling", type=str, default="420", choices=["420", "444"], help="--ext jpg: chroma subsampling")
     parser.add_argument("--decode_workers", type=int, default=0, help="decode the input files on a pool of min(K, 16) threads (0: in line)")
